@@ -1,15 +1,18 @@
 #!/usr/bin/env python
 """Headline benchmark: DenseNet121 forward+backward on synthetic 320x320 X-rays, bf16 storage.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
            bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over one minibatch resident in HBM: forward (batch-statistic
 BatchNorm), BCE loss, full backward into the flat fp32 gradient buffer, (N>1) the RCCL gradient
-all-reduce, and the fused Adam update of the fp32 masters (also timed on its own and reported in `config`).  Prints ONE JSON line
-(rank 0) with `roofline` (dominant kernel, HIP-event timed inside the timed region) and `cpu_baseline`
-(the oracle's fp32 CPU restatement of the same step on a bounded sample).
+all-reduce, and the fused Adam update of the fp32 masters.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times K steps, writes the last step's outputs (--dump-outputs) and prints the headline.  --full
+adds everything else: `roofline` (dominant kernel, HIP-event timed in an eager replica of the timed steps, or inside the timed
+region when eager), the optimiser step timed on its own and the copy yardstick (in `config`), BASELINE configs[2..4]
+(`config.other_configs`) and `cpu_baseline` (the oracle's fp32 CPU restatement of the same step on a bounded sample).
 """
 import argparse
 import ctypes
@@ -321,6 +324,28 @@ def run_other_config(name, batch, size, opt_kind, classes, dev, steps=20, warmup
     return out
 
 
+DUMP_MAX_ELEMS = 7 << 20        # per flat buffer: two of them (28 MiB each) and the logits stay under 64 MB
+
+
+def dump_outputs(d, model, loss, logits):
+    """What the last timed step hands its caller, as float32 DIR/<name>.npy: loss, logits, and the engine's flat fp32 buffers after
+    the step -- gradients and the updated parameters.  A buffer above DUMP_MAX_ELEMS is written as a fixed sample (indices drawn
+    from seed 0, sorted), the same for every build, so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    eng = model._eng()
+    arrays = {"loss": loss.reshape(1), "logits": logits, "grads": eng.flat_grad, "params": eng.flat}
+    for name, t in arrays.items():
+        if t is None:                            # an engine without flat buffers (no fused optimiser, see main)
+            continue
+        t = t.detach().float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.flatten()[idx.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.cpu().numpy())
+    log("outputs of the last timed step written to %s" % d)
+
+
 def launcher_command(n, argv, port=None):
     """`python bench.py --gpus N` without WORLD_SIZE: the command that starts the N ranks (one process per GPU over RCCL), exactly
     what the driver runs for N > 1."""
@@ -356,12 +381,19 @@ def main():
                     help="densenet121 is the headline (BASELINE configs[1]); the others are reported for reference only")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"],
                     help="activation storage type: bf16 (the headline, BASELINE configs[1]) or the fp32 parity mode (densenet121 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, optimiser step and copy yardstick, BASELINE "
+                         "configs[2..4], CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, logits, fp32 gradients and parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="enqueue every launch from Python instead of replaying the captured hipGraph")
-    ap.add_argument("--roofline-kernel", default=None, help="kernel tag to time (default: the one with the largest share)")
+    ap.add_argument("--roofline-kernel", default=None, help="kernel tag to time under --full (default: the one with the largest share)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the BASELINE configs[2..4] that the headline run reports under config.other_configs (N = 1 only)")
+                    help="--full without the BASELINE configs[2..4] reported under config.other_configs (N = 1 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -402,7 +434,8 @@ def main():
     opt = FusedAdam(model, lr=1e-4)             # the reference's optimiser (chexpert.py:473): Adam, lr 1e-4, over the flat fp32 masters
 
     timer = KernelTimer(ops)
-    timer.install()
+    if args.full:
+        timer.install()
 
     def step():
         return model.forward_backward(x, t)
@@ -426,9 +459,9 @@ def main():
         step()
     torch.cuda.synchronize()
 
-    # one instrumented step over every conv kernel family to find the dominant one
+    # --full: one instrumented step over every conv kernel family to find the dominant one
     only = args.roofline_kernel
-    if only is None:
+    if args.full and only is None:
         timer.enabled, timer.only = True, None
         model.zero_grad()
         step()
@@ -440,7 +473,7 @@ def main():
                                                              fam[k]["alg_bytes"] / fam[k]["ms"] / 1e6))
         timer.records = {}
     timer.enabled, timer.only = False, only
-    log("warm-up done; roofline kernel = %s" % only)
+    log("warm-up done" + ("; roofline kernel = %s" % only if args.full else ""))
 
     def barrier():
         if world > 1:
@@ -448,18 +481,18 @@ def main():
         torch.cuda.synchronize()
 
     def eager_steps(n):
-        l = None
+        r = None
         for _ in range(n):                      # a full training step: zero, forward, loss, backward (+ all-reduce), Adam update
             model.zero_grad()
-            l, _ = step()
+            r = step()
             if opt is not None:
                 opt.step()
-        return l
+        return r
 
     # N = 1: the step is captured once as a hipGraph (chexpert_amd/graph.py) and the timed region replays it -- the ~900
     # launches of a step cost ~18 ms of host time when enqueued one by one.  N > 1 enqueues eagerly (RCCL collectives are
-    # issued from Python between the kernels).  HIP events cannot be recorded inside a captured graph, so the dominant
-    # kernel's launch time is taken with events in an eager replica of the same K steps right after the timed region.
+    # issued from Python between the kernels).  HIP events cannot be recorded inside a captured graph, so under --full the
+    # dominant kernel's launch time is taken with events in an eager replica of the same K steps right after the timed region.
     use_graph = opt is not None and not args.no_graph and os.environ.get("CHEXPERT_BENCH_GRAPH", "1") != "0"
     gstep, capture_failed = None, 0
     if use_graph:
@@ -508,12 +541,12 @@ def main():
     t0 = time.perf_counter()
     if gstep is not None:
         for _ in range(args.steps):
-            loss, _ = gstep.replay()
+            loss, logits = gstep.replay()
     else:
-        # N = 1 eager (--no-graph): the dominant kernel's events are taken inside the timed region.  N > 1: nothing but the step
-        # runs between the barriers; the events come from an eager replica afterwards, as for the graph
-        timer.enabled, timer.only = not dp, only
-        loss = eager_steps(args.steps)
+        # N = 1 eager (--no-graph) under --full: the dominant kernel's events are taken inside the timed region.  N > 1: nothing
+        # but the step runs between the barriers; the events come from an eager replica afterwards, as for the graph
+        timer.enabled, timer.only = args.full and not dp, only
+        loss, logits = eager_steps(args.steps)
     barrier()
     dt = time.perf_counter() - t0
     if dp:
@@ -521,6 +554,39 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
     log("timed region done: %.1f ms/step (%s)" % (dt / args.steps * 1e3, "graph replay" if gstep is not None else "eager"))
+    timer.enabled = False
+    if args.dump_outputs and rank == 0:        # before anything below runs another step
+        dump_outputs(args.dump_outputs, model, loss, logits)
+    loss = float(loss.item())
+    if rank == 0:
+        ms_step = dt / args.steps * 1e3
+        value = world * args.batch * args.steps / dt
+        out = {
+            "metric": "images/sec fwd+bwd %s %dx%d %s (per-GPU rate in config.images_per_sec_per_gpu)" % (
+            "DenseNet121" if args.model == "densenet121" else args.model, args.size, args.size, args.dtype),
+            "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16" if args.dtype == "bf16" else "f32", "data": "synthetic",
+            "config": {"workload": "%s %s %dxMI355X %dx%d bs=%d per GPU, U-Ones labels (%s); %d classes; "
+                                   "random-init weights, synthetic uint8 X-rays" % (
+                                       args.model, args.dtype, world, args.size, args.size, args.batch,
+                                       "BASELINE configs[1]" if (args.model, args.dtype) == ("densenet121", "bf16") else
+                                       "not the headline config", args.classes),
+                       "per_gpu_batch": args.batch, "global_batch": args.batch * world, "parallelism": "dp%d" % world,
+                       "rccl_ranks": (dist.get_world_size() if dp else 1), "collective_backend": (dist.get_backend() if dp else None),
+                       "images_per_sec_per_gpu": round(value / world, 2),
+                       "model_hbm_roofline_frac": round(value / world * (ALG_BYTES_FP32 if args.dtype == "fp32" else ALG_BYTES)[
+                           args.model] / (HBM_PEAK_GBS * 1e9), 4),
+                       "loss": round(loss, 5), "capture_failed": capture_failed,
+                       "launch": ("hipGraph replay" if not dp else "hipGraph segments between the all-reduces") if gstep is not None else "eager enqueue"},
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if dp:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     if gstep is not None or dp:
         if gstep is not None:
             opt.sync_from_device()
@@ -543,42 +609,22 @@ def main():
 
     copy_gbs = copy_bandwidth(dev, ops) if rank == 0 else 0.0
     if rank == 0:
-        ms_step = dt / args.steps * 1e3
-        value = world * args.batch * args.steps / dt
         avg_ms = ksum["ms"] / ksum["launches"]
         achieved = ksum["alg_bytes"] / (ksum["ms"] * 1e-3) / 1e9
         traffic, traffic_src = pmc_traffic(only, args)
         mfma_util, mfma_src = committed_counter(only, args, "mfma_util")
-        out = {
-            "metric": "images/sec fwd+bwd %s %dx%d %s (per-GPU rate in config.images_per_sec_per_gpu)" % (
-            "DenseNet121" if args.model == "densenet121" else args.model, args.size, args.size, args.dtype),
-            "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16" if args.dtype == "bf16" else "f32", "data": "synthetic",
-            "config": {"workload": "%s %s %dxMI355X %dx%d bs=%d per GPU, U-Ones labels (%s); %d classes; "
-                                   "random-init weights, synthetic uint8 X-rays" % (
-                                       args.model, args.dtype, world, args.size, args.size, args.batch,
-                                       "BASELINE configs[1]" if (args.model, args.dtype) == ("densenet121", "bf16") else
-                                       "not the headline config", args.classes),
-                       "per_gpu_batch": args.batch, "global_batch": args.batch * world, "parallelism": "dp%d" % world,
-                       "rccl_ranks": (dist.get_world_size() if dp else 1), "collective_backend": (dist.get_backend() if dp else None),
-                       "images_per_sec_per_gpu": round(value / world, 2),
-                       "model_hbm_roofline_frac": round(value / world * (ALG_BYTES_FP32 if args.dtype == "fp32" else ALG_BYTES)[
-                           args.model] / (HBM_PEAK_GBS * 1e9), 4),
-                       "optimizer_step_ms": round(opt_ms, 3), "loss": round(float(loss.item()), 5),
-                       "measured_copy_GBs": round(copy_gbs, 1), "guide_copy_GBs": COPY_GUIDE_GBS,
-                       "copy_kernel": "cx_copy_stream (16 B per lane, contiguous 16 KB pieces, non-temporal; 1 GiB read + 1 GiB written)",
-                       "capture_failed": capture_failed,
-                       "launch": ("hipGraph replay" if not dp else "hipGraph segments between the all-reduces") if gstep is not None else "eager enqueue"},
-            "roofline": {"bound": "hbm", "kernel": only, "launches_per_step": ksum["launches"] // args.steps,
-                         "avg_launch_ms": round(avg_ms, 4), "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src and ("committed rocprofv3 --pmc pass %s (not measured in this run)" % traffic_src),
-                         "alg_bytes_per_launch": round(ksum["alg_bytes"] / ksum["launches"]),
-                         "mfma_util": mfma_util, "mfma_util_source": mfma_src and ("committed rocprofv3 --pmc pass %s (not measured in this run)" % mfma_src),
-                         "timing": "hip events around each kernel launch, eager replica of the timed steps" if (gstep is not None or dp)
-                         else "hip events around each kernel launch inside the timed region"},
-        }
+        out["config"].update({
+            "optimizer_step_ms": round(opt_ms, 3),
+            "measured_copy_GBs": round(copy_gbs, 1), "guide_copy_GBs": COPY_GUIDE_GBS,
+            "copy_kernel": "cx_copy_stream (16 B per lane, contiguous 16 KB pieces, non-temporal; 1 GiB read + 1 GiB written)"})
+        out["roofline"] = {"bound": "hbm", "kernel": only, "launches_per_step": ksum["launches"] // args.steps,
+                           "avg_launch_ms": round(avg_ms, 4), "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                           "traffic": traffic, "traffic_source": traffic_src and ("committed rocprofv3 --pmc pass %s (not measured in this run)" % traffic_src),
+                           "alg_bytes_per_launch": round(ksum["alg_bytes"] / ksum["launches"]),
+                           "mfma_util": mfma_util, "mfma_util_source": mfma_src and ("committed rocprofv3 --pmc pass %s (not measured in this run)" % mfma_src),
+                           "timing": "hip events around each kernel launch, eager replica of the timed steps" if (gstep is not None or dp)
+                           else "hip events around each kernel launch inside the timed region"}
         headline = (args.model, args.dtype, world) == ("densenet121", "bf16", 1) and not dp
         if headline and not args.no_other_configs:
             # BASELINE.json configs[2..4] at N = 1, after the headline's timed region (they share nothing with it): the headline

@@ -17,18 +17,18 @@ if [ "$1" != "notests" ] && [[ $PART == *A* ]]; then
 fi
 set -e
 if [[ $PART == *A* ]]; then
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err
-timeout -k 10 300 python bench.py --dtype fp32 --steps 3 --warmup 1 --no-other-configs > $O/bench_fp32.json 2>> $O/bench.err
-CHEXPERT_SERIAL_WGRAD=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --no-cpu-baseline --no-other-configs --no-graph --steps 10 --warmup 3 > $O/bench_prof.json 2>> $O/bench.err
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full --dtype fp32 --steps 3 --warmup 1 --no-other-configs > $O/bench_fp32.json 2>> $O/bench.err
+CHEXPERT_SERIAL_WGRAD=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --no-cpu-baseline --no-other-configs --no-graph --steps 10 --warmup 3 > $O/bench_prof.json 2>> $O/bench.err
 cp $(ls $O/stats/*/*_kernel_stats.csv) $O/kernel_stats.csv
 python scratch/kstats.py $O/stats 13 40 > $O/kstats_densenet121.txt; rm -rf $O/stats
 fi
 pmc() {   # model dtype batch size
   local M=$1 D=$2 B=$3 S=$4 T=$O/pmc_$1
-  timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $T/fetch -- python bench.py --model $M --dtype $D --batch $B --size $S --no-cpu-baseline --no-other-configs --no-graph --steps 2 --warmup 1 > /dev/null 2>> $O/bench.err
-  timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $T/write -- python bench.py --model $M --dtype $D --batch $B --size $S --no-cpu-baseline --no-other-configs --no-graph --steps 2 --warmup 1 > /dev/null 2>> $O/bench.err
+  timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $T/fetch -- python bench.py --full --model $M --dtype $D --batch $B --size $S --no-cpu-baseline --no-other-configs --no-graph --steps 2 --warmup 1 > /dev/null 2>> $O/bench.err
+  timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $T/write -- python bench.py --full --model $M --dtype $D --batch $B --size $S --no-cpu-baseline --no-other-configs --no-graph --steps 2 --warmup 1 > /dev/null 2>> $O/bench.err
   python scratch/pmc_summary.py $(ls $T/fetch/*/*counter_collection.csv) $(ls $T/write/*/*counter_collection.csv) $O/pmc_traffic_$M.json 4 $M:$D:$B:$S > $O/pmc_$M.txt
-  timeout -k 10 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU --kernel-trace --output-format csv -d $T/sq -- python bench.py --model $M --dtype $D --batch $B --size $S --no-cpu-baseline --no-other-configs --no-graph --steps 2 --warmup 1 > /dev/null 2>> $O/bench.err
+  timeout -k 10 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU --kernel-trace --output-format csv -d $T/sq -- python bench.py --full --model $M --dtype $D --batch $B --size $S --no-cpu-baseline --no-other-configs --no-graph --steps 2 --warmup 1 > /dev/null 2>> $O/bench.err
   python scratch/sq_summary.py $(ls $T/sq/*/*counter_collection.csv) $O/sq_counters_$M.json $M:$D:$B:$S 4 > $O/sq_$M.txt
   rm -rf $T
 }
@@ -39,8 +39,8 @@ fi
 if [[ $PART == *B* ]]; then
 for spec in "aadensenet121 128 320" "resnet152 128 320" "efficientnet-b4 64 380"; do
   set -- $spec
-  timeout -k 10 300 python bench.py --model $1 --batch $2 --size $3 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_$1.json 2>> $O/bench.err
-  CHEXPERT_SERIAL_WGRAD=1 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --model $1 --batch $2 --size $3 --no-cpu-baseline --no-graph --steps 4 --warmup 1 > /dev/null 2>> $O/bench.err
+  timeout -k 10 300 python bench.py --full --model $1 --batch $2 --size $3 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_$1.json 2>> $O/bench.err
+  CHEXPERT_SERIAL_WGRAD=1 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --model $1 --batch $2 --size $3 --no-cpu-baseline --no-graph --steps 4 --warmup 1 > /dev/null 2>> $O/bench.err
   python scratch/kstats.py $O/stats 5 30 > $O/kstats_$1.txt; rm -rf $O/stats
   pmc $1 bf16 $2 $3
 done

@@ -14,7 +14,7 @@ for r in csv.DictReader(open(sys.argv[1])):
     n[(k, r['Counter_Name'])] += 1
 steps = int(sys.argv[4])
 out = {"_note": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU "
-                "(own pass, --kernel-trace only) of `python bench.py --no-cpu-baseline --no-graph --steps 2 --warmup 1`; per-launch means; "
+                "(own pass, --kernel-trace only) of `python bench.py --full --no-cpu-baseline --no-graph --steps 2 --warmup 1`; per-launch means; "
                 "mfma_util = MFMA_BUSY / (GUI_ACTIVE/8 * 1024 SIMDs)", "workload_key": sys.argv[3], "steps": steps, "kernels": {}}
 rows = []
 for k, v in d.items():

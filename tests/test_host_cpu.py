@@ -621,3 +621,34 @@ print(json.dumps({"rc": rc, "calls": calls, "torch_after": "torch" in sys.module
     assert int(cmd[cmd.index("--master-port") + 1]) > 0
     i = cmd.index(os.path.join(ROOT, "bench.py"))
     assert cmd[i + 1:] == ["--gpus", "2", "--steps", "3", "--warmup", "1"]
+
+
+def test_bench_dump_outputs_float32_bounded_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: loss, logits and the engine's flat buffers as float32 .npy; a buffer above DUMP_MAX_ELEMS becomes
+    the same seeded sample on every run, and a dump of the largest model (ResNet152, 58.2 M parameters) stays under 64 MB."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    bench.torch = torch
+
+    class Model:
+        def __init__(self, n):
+            self.e = type("Engine", (), {})()
+            self.e.flat = torch.arange(n, dtype=torch.float64).float()
+            self.e.flat_grad = -self.e.flat
+
+        def _eng(self):
+            return self.e
+
+    small, big = 1000, 58172494
+    logits = torch.randn(256, 14).to(torch.bfloat16)
+    for d, n in (("a", small), ("b", big), ("c", big)):
+        bench.dump_outputs(str(tmp_path / d), Model(n), torch.tensor(0.25), logits)
+    a = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sorted(a) == ["grads", "logits", "loss", "params"] and all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["params"], np.arange(small)) and np.array_equal(a["grads"], -np.arange(small))
+    assert np.array_equal(a["logits"], logits.float().numpy()) and a["loss"].tolist() == [0.25]
+    b, c = ({f: np.load(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))} for d in ("b", "c"))
+    assert b["params.npy"].shape == (bench.DUMP_MAX_ELEMS,) and np.all(np.diff(b["params.npy"]) >= 0)
+    assert all(np.array_equal(b[f], c[f]) for f in b)
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in b) < 64e6
