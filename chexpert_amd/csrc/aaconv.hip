@@ -19,6 +19,14 @@ int cx_try_aa_row(int which, const void* qkv, const float* rel_h, const float* r
                   float* d_rel_h, float* d_rel_w, float* slab_h, float* slab_w, int B, int H, int W, int nh, int dk, int dv, int ldq,
                   hipStream_t st, bool* handled);
 int cx_rows_reduce_add_impl(float* dst, const float* rows, int n_rows, int C, int rstride, hipStream_t st);     // elementwise.hip
+// aaconv_heads.hip: the same four operations for head widths 1 <= dk/nh, dv/nh <= 64 (runtime values), dv <= 104
+int cx_aa_heads_fwd(int f32, const void* qkv, const float* rel_h, const float* rel_w, float* o, float* lse, int B, int H, int W, int nh,
+                    int dk, int dv, int ldq, hipStream_t st);
+int cx_aa_heads_weights(int f32, const void* qkv, const float* rel_h, const float* rel_w, const float* lse, float* wts, int B, int H, int W,
+                        int nh, int dk, int dv, int ldq, hipStream_t st);
+int cx_aa_heads_bwd(int f32, const void* qkv, const float* rel_h, const float* rel_w, const float* o, const float* d_o, const float* lse,
+                    float* dqkv, float* d_rel_h, float* d_rel_w, float* slab_h, float* slab_w, int B, int H, int W, int nh, int dk, int dv,
+                    int ldq, hipStream_t st);
 
 namespace {
 
@@ -818,10 +826,12 @@ template <typename T>
 int aa_attention_fwd_t(const void* qkv, const float* rel_h, const float* rel_w, float* o, float* lse, int B, int H, int W, int nh,
                         int dk, int dv, int ldq, void* stream) {
   if (!qkv || !rel_h || !rel_w || !o || !lse) return CX_EINVAL;
-  if (nh <= 0 || dk != nh * DKH || dv % nh || dv / nh > MAXDV || (ldq % 4)) return CX_ESHAPE;
+  if (nh <= 0 || dv % nh || (ldq % 4)) return CX_ESHAPE;
+  hipStream_t st = as_stream(stream);
+  if (dk != nh * DKH || dv / nh > MAXDV)            // other head widths: aaconv_heads.hip (CX_ESHAPE beyond dk/nh, dv/nh <= 64, dv <= 104)
+    return cx_aa_heads_fwd(!std::is_same<T, bf16>::value, qkv, rel_h, rel_w, o, lse, B, H, W, nh, dk, dv, ldq, st);
   const int dvh = dv / nh;
   AAGeo g{B, H, W, nh, dk, dv, ldq};
-  hipStream_t st = as_stream(stream);
   {
     bool handled = false;
     const int rc = !std::is_same<T, bf16>::value ? 0 : cx_try_aa_row(0, qkv, rel_h, rel_w, o, nullptr, lse, nullptr, nullptr, nullptr, nullptr, nullptr, B, H, W, nh, dk, dv,
@@ -856,7 +866,9 @@ template <typename T>
 int aa_attention_weights_t(const void* qkv, const float* rel_h, const float* rel_w, const float* lse, float* weights, int B, int H,
                             int W, int nh, int dk, int dv, int ldq, void* stream) {
   if (!qkv || !rel_h || !rel_w || !lse || !weights) return CX_EINVAL;
-  if (nh <= 0 || dk != nh * DKH || dv % nh || (ldq % 4)) return CX_ESHAPE;
+  if (nh <= 0 || dv % nh || (ldq % 4)) return CX_ESHAPE;
+  if (dk != nh * DKH)
+    return cx_aa_heads_weights(!std::is_same<T, bf16>::value, qkv, rel_h, rel_w, lse, weights, B, H, W, nh, dk, dv, ldq, as_stream(stream));
   AAGeo g{B, H, W, nh, dk, dv, ldq};
   const size_t smem = attn_lds_floats(H, W, 0) * 4;
   if (smem > 64 * 1024) return CX_ESHAPE;
@@ -870,7 +882,28 @@ int aa_attention_bwd_t(const void* qkv, const float* rel_h, const float* rel_w, 
                         float* dqkv, float* d_rel_h, float* d_rel_w, int B, int H, int W, int nh, int dk, int dv, int ldq,
                         float* scratch, int64_t scratch_floats, void* stream) {
   if (!qkv || !rel_h || !rel_w || !o || !d_o || !lse || !dqkv || !d_rel_h || !d_rel_w) return CX_EINVAL;
-  if (nh <= 0 || dk != nh * DKH || dv % nh || dv / nh > MAXDV || (ldq % 4)) return CX_ESHAPE;
+  if (nh <= 0 || dk % nh || dv % nh || (ldq % 4)) return CX_ESHAPE;
+  hipStream_t st = as_stream(stream);
+  // Reproducible relative-table gradients: every query-side workgroup plain-stores its two partial tables into the caller's
+  // workspace (one slab per workgroup: 128 queries of one (image, head)) and the slabs are added in workgroup order afterwards.
+  // Without (enough) workspace the partial tables are added with fp32 atomics, whose order changes from run to run.
+  const int dkh = dk / nh;
+  const int TH = dkh * (2 * H - 1), TW = dkh * (2 * W - 1);
+  const long long nwg = (long long)((H * W + 127) / 128) * B * nh;        // AQ = AQM = 128 queries per workgroup in every q-side kernel
+  float *slab_h = nullptr, *slab_w = nullptr;
+  if (scratch && nwg * (TH + TW) <= scratch_floats && nwg < (1ll << 30)) {
+    slab_h = scratch;
+    slab_w = scratch + nwg * TH;
+  }
+  if (dk != nh * DKH || dv / nh > MAXDV) {          // other head widths: aaconv_heads.hip, same slab protocol
+    if (const int e = cx_aa_heads_bwd(!std::is_same<T, bf16>::value, qkv, rel_h, rel_w, o, d_o, lse, dqkv, d_rel_h, d_rel_w, slab_h, slab_w,
+                                      B, H, W, nh, dk, dv, ldq, st)) return e;
+    if (slab_h) {
+      if (const int e = cx_rows_reduce_add_impl(d_rel_h, slab_h, (int)nwg, TH, TH, st)) return e;
+      return cx_rows_reduce_add_impl(d_rel_w, slab_w, (int)nwg, TW, TW, st);
+    }
+    return 0;
+  }
   const int dvh = dv / nh;
   AAGeo g{B, H, W, nh, dk, dv, ldq};
   const size_t smem_q = (attn_lds_floats(H, W, dvh) + (size_t)DKH * (2 * H - 1 + 2 * W - 1) + (size_t)AQ * (W + 1) + (size_t)AQ * (H + 1) +
@@ -878,7 +911,6 @@ int aa_attention_bwd_t(const void* qkv, const float* rel_h, const float* rel_w, 
   const size_t smem_k = ((size_t)DKH * (2 * H - 1 + 2 * W - 1) + TK * (DKH + dvh + 2)) * 4;
   if (smem_q > 160 * 1024) return CX_ESHAPE;
   dim3 grid((H * W + AQ - 1) / AQ, B * nh);
-  hipStream_t st = as_stream(stream);
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -890,16 +922,6 @@ int aa_attention_bwd_t(const void* qkv, const float* rel_h, const float* rel_w, 
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 13>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
-  }
-  // Reproducible relative-table gradients: every query-side workgroup plain-stores its two partial tables into the caller's
-  // workspace (one slab per workgroup: 128 queries of one (image, head)) and the slabs are added in workgroup order afterwards.
-  // Without (enough) workspace the partial tables are added with fp32 atomics, whose order changes from run to run.
-  const int TH = DKH * (2 * H - 1), TW = DKH * (2 * W - 1);
-  const long long nwg = (long long)((H * W + 127) / 128) * B * nh;        // AQ = AQM = 128 queries per workgroup in every q-side kernel
-  float *slab_h = nullptr, *slab_w = nullptr;
-  if (scratch && nwg * (TH + TW) <= scratch_floats && nwg < (1ll << 30)) {
-    slab_h = scratch;
-    slab_w = scratch + nwg * TH;
   }
   bool row_q = false;
   {

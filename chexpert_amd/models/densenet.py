@@ -85,11 +85,13 @@ class AAConv2d(nn.Module):
         assert dk % nh == 0, "nh must divide dk"
         assert dv % nh == 0, "nh must divide dv"
         # every configuration of the reference is constructible (parameter shapes, state_dict keys: the parameter-count
-        # self-test of attn_aug_conv.py:522-655); the HIP attention kernels cover what chexpert.py trains (relative=True; False runs too),
-        # dk/nh = 20 (k = 0.2 at 8 heads), dv/nh = 1 .. 13 with dv <= 104 (MFMA / row kernels for the sizes the reference's
-        # configurations produce -- 1,2,3,4,6,8 and 9, 13 of the CIFAR Densenet-BC at v = 0.7 -- the generic kernels for the rest).  Anything else raises when the model is RUN, not when it is built.
-        self.kernel_support = dk // nh == 20 and 1 <= dv // nh <= 13 and dv <= 104 and out_channels > dv
+        # self-test of attn_aug_conv.py:522-655).  The HIP attention kernels cover head widths dk/nh and dv/nh of 1 .. 64 with
+        # dv <= 104 (the out-projection) -- the row kernels for dk/nh = 20, dv/nh <= 13 (what chexpert.py trains; relative=False
+        # runs too), the runtime-width kernels of csrc/aaconv_heads.hip for the rest -- and the qkv projection and the convolution
+        # branch need multiples of 8 channels (conv_gemm).  Anything else raises when the model is RUN, not when it is built.
         self.dk, self.dv, self.nh, self.relative = dk, dv, nh, relative
+        self.out_channels = out_channels
+        self.kernel_support = not self.unsupported()
         padding = kwargs.pop("padding", None) or kernel_size // 2
         self.conv = Conv2dParams(in_channels, out_channels - dv, kernel_size, stride, padding, bias=False, **kwargs) \
             if out_channels > dv else None
@@ -107,6 +109,25 @@ class AAConv2d(nn.Module):
                 self.register_buffer("_rel0_" + nm, torch.zeros(dk // nh, n), persistent=False)
                 self.register_buffer("_drel0_" + nm, torch.zeros(dk // nh, n), persistent=False)
         self._last = None        # (qkv, lse) of the most recent forward, set by the parent model's engine
+
+    def unsupported(self, branch_aligned=True):
+        """The conditions of the HIP kernels this layer fails, as text ('' when it runs).  branch_aligned=False: the convolution
+        branch is padded to a multiple of 8 channels by the caller (the channel-padded CIFAR DenseNet-BC)."""
+        dkh, dvh, dk, dv = self.dk // self.nh, self.dv // self.nh, self.dk, self.dv
+        why = []
+        if not 1 <= dkh <= 64:
+            why.append("dk/nh = %d is outside 1 .. 64" % dkh)
+        if not 1 <= dvh <= 64:
+            why.append("dv/nh = %d is outside 1 .. 64" % dvh)
+        if dv > 104:
+            why.append("dv = %d is above 104 (the out-projection kernels)" % dv)
+        if self.out_channels <= dv:
+            why.append("out_channels = %d leaves no convolution branch beside dv = %d" % (self.out_channels, dv))
+        if (2 * dk + dv) % 8:
+            why.append("2dk+dv = %d qkv channels are not a multiple of 8" % (2 * dk + dv))
+        if branch_aligned and self.out_channels > dv and (self.out_channels - dv) % 8:
+            why.append("out_channels-dv = %d convolution channels are not a multiple of 8" % (self.out_channels - dv))
+        return "; ".join(why)
 
     def rel_tables(self):
         return (self.key_rel_h, self.key_rel_w) if self.relative else (self._rel0_h, self._rel0_w)
@@ -1367,9 +1388,10 @@ class DenseNet(nn.Module):
         if padded and len(self.block_config) == 4:
             raise NotImplementedError("ImageNet-stem DenseNets need growth and stem widths that are multiples of 8")
         for mod in self.modules():
-            if isinstance(mod, AAConv2d) and not mod.kernel_support:
-                raise NotImplementedError("AAConv2d(dk=%d, dv=%d, nh=%d, relative=%s): the HIP attention kernels cover dk/nh = 20, "
-                                          "dv/nh = 1 .. 13, dv <= 104 (chexpert.py:476)" % (mod.dk, mod.dv, mod.nh, mod.relative))
+            why = mod.unsupported(branch_aligned=not padded) if isinstance(mod, AAConv2d) else ""
+            if why:
+                raise NotImplementedError("AAConv2d(dk=%d, dv=%d, nh=%d, relative=%s): %s (the HIP attention kernels cover dk/nh and "
+                                          "dv/nh = 1 .. 64 with dv <= 104)" % (mod.dk, mod.dv, mod.nh, mod.relative, why))
         if self._engine is None or self._engine.c_final != self.classifier.in_features or \
                 self._engine.dtype != getattr(self, "_storage_dtype", torch.bfloat16):
             object.__setattr__(self, "_engine", _PaddedEngine(self) if padded else _Engine(self))

@@ -913,9 +913,10 @@ class _EngineNet(nn.Module):
 
     def _eng(self):
         for mod in self.modules():
-            if isinstance(mod, AAConv2d) and not mod.kernel_support:
-                raise NotImplementedError("AAConv2d(dk=%d, dv=%d, nh=%d): the HIP attention kernels cover dk/nh = 20, dv/nh in "
-                                          "1 .. 13 with dv <= 104" % (mod.dk, mod.dv, mod.nh))
+            why = mod.unsupported() if isinstance(mod, AAConv2d) else ""
+            if why:
+                raise NotImplementedError("AAConv2d(dk=%d, dv=%d, nh=%d): %s (the HIP attention kernels cover dk/nh and dv/nh = 1 .. 64 "
+                                          "with dv <= 104)" % (mod.dk, mod.dv, mod.nh, why))
         if self._engine is None or self._engine.dtype != getattr(self, "_storage_dtype", torch.bfloat16):
             object.__setattr__(self, "_engine", _Engine(self))
         return self._engine

@@ -425,10 +425,13 @@ int cx_rmsprop_step_dev(float* p, const float* g, float* sq, float* buf, size_t 
 int cx_optim_tick(float* hyper, void* stream);
 
 /* ---- attention-augmented convolution (AAConv2d, models/attn_aug_conv.py:19-100) --------------------
- * qkv: bf16 (B, H*W, ldq) output of in_proj_qkv (channels [q dk | k dk | v dv], head-major), dk = 20*nh.
+ * qkv: bf16 (B, H*W, ldq) output of in_proj_qkv (channels [q dk | k dk | v dv], head-major), ldq % 4 == 0.
+ * Head widths dkh = dk/nh and dvh = dv/nh of 1 .. 64 with dv <= 104: dkh = 20 with dvh <= 13 runs the row / generic kernels
+ * of aaconv.hip + aaconv_row.hip, every other width the runtime-width kernels of aaconv_heads.hip; CX_ESHAPE beyond that, or
+ * when a map's relative tables and tiles exceed the LDS of a workgroup (any H, W <= 40 fits).
  * o: fp32 (B, H*W, dv) attention output BEFORE out_proj; lse: fp32 (B*nh, H*W) log-sum-exp of the logits.
  * Logits include the relative terms of rel_to_abs / relative_logits_1d (:43-63) in closed form; the
- * (B,nh,HW,HW) tensors of the reference are never materialised.                                      */
+ * (B,nh,HW,HW) tensors of the reference are never materialised.  The _f32 entry points take fp32 qkv (fp32 storage mode). */
 int cx_aa_attention_fwd(const void* qkv, const float* key_rel_h, const float* key_rel_w, float* o, float* lse, int B, int H, int W,
                         int nh, int dk, int dv, int ldq, void* stream);
 /* weights: fp32 (B, nh, H*W, H*W) = softmax(logits) rebuilt from the saved lse -- the tensor the reference leaves in
