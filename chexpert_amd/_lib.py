@@ -80,6 +80,7 @@ SIGNATURES = {
     "cx_conv3x3_wgrad_batch": [C.POINTER(CxWgrad), C.POINTER(CxWgradBatch), _vp],
     "cx_chan_map_table": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "cx_conv_wgrad": [C.POINTER(CxWgrad), _vp],
+    "cx_stem_input_grad": [_vp] * 7 + [_i] * 13 + [_vp],
     "cx_conv1x1_dgrad_wgrad": [C.POINTER(CxConv), _vp, _vp],
     "cx_conv1x1_dgrad_wgrad_ws": [C.POINTER(CxConv), _vp, _vp, C.c_int64, _vp],
     "cx_conv1x1_dgrad_wgrad_ld_ws": [C.POINTER(CxConv), _vp, _i, _vp, C.c_int64, _vp],

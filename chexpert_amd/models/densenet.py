@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import CxPackDesc, check, lib, ptr, stream_ptr
+from ._autograd import check_input_grad, input_grad_buffer, params_untouched, wants_autograd
 
 
 # --------------------------------------------------------------------------------------------- parameter containers
@@ -710,21 +711,22 @@ class _Engine:
                         ops.conv_wgrad(dyc, y1, dw, kh=3, kw=3, pad=1, x_prologue=ops.PRO_AFFINE_RELU, pa=pa, pb=pb)
 
     # ---- backward
-    def backward(self, ws, dlogits):
+    def backward(self, ws, dlogits, dx=None):
+        """dx: None, or an fp32 (B,3,H,W) buffer that also receives the input gradient (cx_stem_input_grad)"""
         self._w2_items = []
         ops.set_det_wgrad(self.det)            # reproducible weight-gradient sums with the deterministic statistics
         # the ordered sums of the weight-gradient slabs run as ONE table-driven launch at the end of the pass (ops.wgrad_defer_*);
         # a data-parallel run flushes them before each gradient bucket leaves (GradReducer.pre_launch)
         deferred = os.environ.get("CHEXPERT_WGRAD_DEFER", "1") != "0" and ops.wgrad_defer_begin(self.device)
         try:
-            self._backward(ws, dlogits)
+            self._backward(ws, dlogits, dx)
             if deferred:
                 ops.wgrad_defer_flush(self.device)
         finally:
             if deferred:
                 ops.wgrad_defer_abort(self.device)
 
-    def _backward(self, ws, dlogits):
+    def _backward(self, ws, dlogits, dx=None):
         m, f, s = self.model, self.model.features, self.slots
         R = self.stat_replicas
         B = ws.B
@@ -964,6 +966,8 @@ class _Engine:
                                 G(f.norm0.bias), None, None, pa, pb, pc, ci, replicas=sred[2], rstride=sred[3])
                 ops.conv_wgrad(ws.dz0, ws.x8, G(f.conv0.weight), kh=5, kw=5, pad=2, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=pa, gb=pb,
                                gc=pc)
+                if dx is not None:
+                    ops.stem_input_grad(ws.dz0, ws.c0, pa, pb, pc, f.conv0.weight, dx, stride=1, pad=2)
             else:
                 n0, S0 = s["n0"], s["S0"]
                 if det:
@@ -980,6 +984,8 @@ class _Engine:
                                 rstride=sred[3])
                 ops.conv_wgrad(ws.dz0, ws.x4, G(f.conv0.weight), mode=ops.MODE_STEM, g_prologue=ops.PRO_AFFINE2, g2=ws.c0,
                                ga=pa, gb=pb, gc=pc)
+                if dx is not None:
+                    ops.stem_input_grad(ws.dz0, ws.c0, pa, pb, pc, f.conv0.weight, dx, stride=2, pad=3)
         main.wait_stream(side)
         if side is main and os.environ.get("CHEXPERT_W2_SIDE", "0") == "1":
             main.wait_stream(self.side)
@@ -1093,7 +1099,7 @@ class _Fn(torch.autograd.Function):
             raise NotImplementedError("autograd through the fused DenseNet needs train() mode (batch-statistic BatchNorm "
                                       "backward); for Grad-CAM use chexpert_amd.gradcam.grad_cam")
         ws = eng.forward(x, True)
-        ctx.model, ctx.ws = model, ws
+        ctx.model, ctx.ws, ctx.x_meta = model, ws, (tuple(x.shape), x.dtype, x.device)
         return ws.logits.clone()
 
     @staticmethod
@@ -1101,10 +1107,14 @@ class _Fn(torch.autograd.Function):
         eng, ws = ctx.model._engine, ctx.ws
         if ws is None:
             raise RuntimeError("backward through the fused DenseNet can only run once per forward")
-        eng.backward(ws, dlogits.contiguous().float())
+        shape, dtype, dev = ctx.x_meta
+        dx = input_grad_buffer(shape, dev) if ctx.needs_input_grad[0] else None
+        frozen = not any(p.requires_grad for p in ctx.model.parameters())
+        with params_untouched(eng.params, eng.flat_grad) if frozen else contextlib.nullcontext():
+            eng.backward(ws, dlogits.contiguous().float(), dx=dx)
         eng.release(ws)
         ctx.ws = None
-        return None, None, None
+        return (dx.to(dtype) if dx is not None else None), None, None
 
 
 # --------------------------------------------------------------------------------------------- channel-padded twin
@@ -1306,7 +1316,7 @@ class _PaddedEngine:
             self.model._nbt_pending += 1
         return ws
 
-    def backward(self, ws, dlogits):
+    def backward(self, ws, dlogits, dx=None):
         in_ = self.inner
         in_.flat_grad.zero_()
         for p, gv in zip(in_.params, in_.grad_views):
@@ -1314,7 +1324,7 @@ class _PaddedEngine:
         fresh = any(p.grad is None for p in self.params)
         if fresh:
             self.flat_grad.zero_()
-        in_.backward(ws, dlogits)
+        in_.backward(ws, dlogits, dx)       # (the twin's conv0 reads the 3 real input channels first: dx is the real one's)
         self._map(self.flat_grad, in_.flat_grad, self.ptab, 1, 1)  # gradients: padded -> real, added
         if fresh:
             for p, gv in zip(self.params, self.grad_views):
@@ -1423,7 +1433,7 @@ class DenseNet(nn.Module):
             raise RuntimeError("chexpert_amd.DenseNet runs on the GPU only (hand-written HIP kernels); there is no CPU "
                                "fallback -- move the model and the input to cuda")
         eng = self._eng()
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if self.training and wants_autograd(self, x):
             return _Fn.apply(x, self.classifier.weight, self)
         if not self.training:
             from ..gradcam import hooked_eval_forward, hooks_registered
@@ -1435,16 +1445,19 @@ class DenseNet(nn.Module):
         return out
 
     # fused training step helpers (bench / trainer fast path; same arithmetic as chexpert.py:159-163)
-    def forward_backward(self, x, target):
+    def forward_backward(self, x, target, input_grad=None):
         """logits = model(x); loss = BCEWithLogits(logits, target).sum(1).mean(0); loss.backward().
-        Returns (loss, logits) as device tensors without a host sync."""
+        Returns (loss, logits) as device tensors without a host sync.  input_grad: None, or a preallocated fp32 (B,3,H,W) tensor that
+        also receives d loss / d x (what x.grad would hold), still without a host sync."""
         eng = self._eng()
+        if input_grad is not None:
+            check_input_grad(input_grad, x)
         ws = eng.forward(x, self.training)
         B, n = ws.logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
         ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
-        eng.backward(ws, dl)
+        eng.backward(ws, dl, dx=input_grad)
         logits = ws.logits.clone()
         eng.release(ws)
         return loss, logits

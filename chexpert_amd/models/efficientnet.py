@@ -15,6 +15,7 @@ DropConnect (efficientnet.py:44-51, :100-101) and the classifier Dropout (:169-1
 per-element keep masks drawn on the GPU by `cx_dropout_mask_dev` from (model.drop_seed, device-side count of training forwards, block) -- reproducible and
 independent of torch's RNG; the parity tests feed the drawn masks (`engine.last_masks`) to the oracle.
 """
+import contextlib
 import math
 import os
 from collections import OrderedDict
@@ -26,6 +27,7 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import ops
 from .._lib import CxPackDesc, check, lib, ptr, stream_ptr
+from ._autograd import check_input_grad, input_grad_buffer, params_untouched, wants_autograd
 from .densenet import BatchNorm2dParams, Conv2dParams, PoolMarker, _FusedOnly
 
 SCALING_PARAMS = {  # width, depth, resolution, dropout (efficientnet.py:13-21)
@@ -424,18 +426,19 @@ class _Engine:
         bw["gdc"] = torch.empty(max(t["out"].numel() for t in ws.blk), dtype=bf, device=dev)     # DropConnect-masked gradient
         ws.bwd = bw
 
-    def backward(self, ws, dlogits):
+    def backward(self, ws, dlogits, dx=None):
+        """dx: None, or an fp32 (B,3,H,W) buffer that also receives the input gradient (cx_stem_input_grad)"""
         ops.set_det_wgrad(self.det)            # reproducible weight-gradient sums with the deterministic statistics
         deferred = self.det and ops.wgrad_defer_begin(self.device)
         try:
-            self._backward(ws, dlogits)
+            self._backward(ws, dlogits, dx)
             if deferred:
                 ops.wgrad_defer_flush(self.device)
         finally:
             if deferred:
                 ops.wgrad_defer_abort(self.device)
 
-    def _backward(self, ws, dlogits):
+    def _backward(self, ws, dlogits, dx=None):
         m, v, G, lb = self.model, self._v, self.G, (_LibF32(lib()) if self.dtype == torch.float32 else lib())
         det = self.det
         B = ws.B
@@ -572,6 +575,8 @@ class _Engine:
                        gb=v(ws, S0.pb), gc=v(ws, S0.pc))
         ops.wgrad_defer_flush(self.device)       # the stem gradient is read back right here: run the deferred slab sums now
         G(m.stem[0].weight).view(c0, 3, 3, 3).add_(dw8[:, :3])
+        if dx is not None:
+            ops.stem_input_grad(dzs, ws.ys, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.stem[0].weight, dx, stride=2, pad=ws.stem_pad)
         if red is not None:
             red.finish()
         if fresh:
@@ -593,7 +598,7 @@ class _Fn(torch.autograd.Function):
         if not model.training:
             raise NotImplementedError("autograd through the fused EfficientNet needs train() mode")
         ws = model._eng().forward(x, True)
-        ctx.model, ctx.ws = model, ws
+        ctx.model, ctx.ws, ctx.x_meta = model, ws, (tuple(x.shape), x.dtype, x.device)
         return ws.logits.clone()
 
     @staticmethod
@@ -601,10 +606,14 @@ class _Fn(torch.autograd.Function):
         eng, ws = ctx.model._eng(), ctx.ws
         if ws is None:
             raise RuntimeError("backward through the fused EfficientNet can only run once per forward")
-        eng.backward(ws, dlogits.contiguous().float())
+        shape, dtype, dev = ctx.x_meta
+        dx = input_grad_buffer(shape, dev) if ctx.needs_input_grad[0] else None
+        frozen = not any(p.requires_grad for p in ctx.model.parameters())
+        with params_untouched(eng.params, eng.flat_grad) if frozen else contextlib.nullcontext():
+            eng.backward(ws, dlogits.contiguous().float(), dx=dx)
         eng.release(ws)
         ctx.ws = None
-        return None, None, None
+        return (dx.to(dtype) if dx is not None else None), None, None
 
 
 class EfficientNet(nn.Module):
@@ -660,7 +669,7 @@ class EfficientNet(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("chexpert_amd EfficientNet runs on the GPU only (hand-written HIP kernels); there is no CPU fallback")
         eng = self._eng()
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if self.training and wants_autograd(self, x):
             return _Fn.apply(x, self.head[6].weight, self)
         if not self.training:
             from ..gradcam import hooked_eval_forward, hooks_registered
@@ -671,14 +680,16 @@ class EfficientNet(nn.Module):
         eng.release(ws)
         return out
 
-    def forward_backward(self, x, target):
+    def forward_backward(self, x, target, input_grad=None):
         eng = self._eng()
+        if input_grad is not None:
+            check_input_grad(input_grad, x)
         ws = eng.forward(x, self.training)
         B, n = ws.logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
         ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
-        eng.backward(ws, dl)
+        eng.backward(ws, dl, dx=input_grad)
         logits = ws.logits.clone()
         eng.release(ws)
         return loss, logits

@@ -13,6 +13,7 @@ BatchNorm outputs are never stored; backward uses the two-tensor affine form of 
 prologues of the input- and weight-gradient kernels, and the input gradient of the strided convs is the
 same implicit GEMM walking only the source positions that lie on the stride grid (`tstride`).
 """
+import contextlib
 from collections import OrderedDict
 
 import torch
@@ -20,6 +21,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import CxPackDesc, check, lib, ptr, stream_ptr
+from ._autograd import check_input_grad, input_grad_buffer, params_untouched, wants_autograd
 from .densenet import AAConv2d, BatchNorm2dParams, Conv2dParams, PoolMarker, ReLUMarker, _Vec
 
 
@@ -595,20 +597,21 @@ class _Engine:
             bw["dQKV"] = torch.empty(max(t["QKV"].numel() for t in aa_t), dtype=bf, device=dev)
         ws.bwd = bw
 
-    def backward(self, ws, dlogits):
+    def backward(self, ws, dlogits, dx=None):
+        """dx: None, or an fp32 (B,3,H,W) buffer that also receives the input gradient (cx_stem_input_grad)"""
         ops.set_det_wgrad(self.det)            # reproducible weight-gradient sums with the deterministic statistics
         # the ordered slab sums run as one table-driven launch at the end of the pass (ops.wgrad_defer_*); a data-parallel run
         # flushes them before each gradient bucket leaves (GradReducer.pre_launch); the CIFAR stem keeps immediate sums (read back at once)
         deferred = self.det and not self.cifar and ops.wgrad_defer_begin(self.device)
         try:
-            self._backward(ws, dlogits)
+            self._backward(ws, dlogits, dx)
             if deferred:
                 ops.wgrad_defer_flush(self.device)
         finally:
             if deferred:
                 ops.wgrad_defer_abort(self.device)
 
-    def _backward(self, ws, dlogits):
+    def _backward(self, ws, dlogits, dx=None):
         m, v, G = self.model, self._v, self.G
         B = ws.B
         self._alloc_bwd(ws)
@@ -785,6 +788,8 @@ class _Engine:
             ops.conv_wgrad(bw["dz0"], ws.x8, dw8, kh=3, kw=3, stride=1, pad=1, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=v(ws, S0.pa),
                            gb=v(ws, S0.pb), gc=v(ws, S0.pc))
             G(m.conv1.weight).view(c0, 3, 3, 3).add_(dw8[:, :3])
+            if dx is not None:
+                ops.stem_input_grad(bw["dz0"], ws.c0, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.conv1.weight, dx, stride=1, pad=1)
         else:
             if det:
                 rows = ops.bnrelu_maxpool_bwd(ws.c0, v(ws, S0.sc), v(ws, S0.sh), v(ws, S0.mean), v(ws, S0.rstd), ws.amax, gx, gx, ones(64),
@@ -799,6 +804,8 @@ class _Engine:
                             rstride=r0[3])
             ops.conv_wgrad(bw["dz0"], ws.x4, G(m.conv1.weight), mode=ops.MODE_STEM, g_prologue=ops.PRO_AFFINE2, g2=ws.c0,
                            ga=v(ws, S0.pa), gb=v(ws, S0.pb), gc=v(ws, S0.pc))
+            if dx is not None:
+                ops.stem_input_grad(bw["dz0"], ws.c0, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.conv1.weight, dx, stride=2, pad=3)
         if red is not None:
             red.finish()
         if fresh:
@@ -894,7 +901,7 @@ class _Fn(torch.autograd.Function):
         if not model.training:
             raise NotImplementedError("autograd through the fused ResNet needs train() mode")
         ws = model._eng().forward(x, True)
-        ctx.model, ctx.ws = model, ws
+        ctx.model, ctx.ws, ctx.x_meta = model, ws, (tuple(x.shape), x.dtype, x.device)
         return ws.logits.clone()
 
     @staticmethod
@@ -902,10 +909,14 @@ class _Fn(torch.autograd.Function):
         eng, ws = ctx.model._eng(), ctx.ws
         if ws is None:
             raise RuntimeError("backward through the fused ResNet can only run once per forward")
-        eng.backward(ws, dlogits.contiguous().float())
+        shape, dtype, dev = ctx.x_meta
+        dx = input_grad_buffer(shape, dev) if ctx.needs_input_grad[0] else None
+        frozen = not any(p.requires_grad for p in ctx.model.parameters())
+        with params_untouched(eng.params, eng.flat_grad) if frozen else contextlib.nullcontext():
+            eng.backward(ws, dlogits.contiguous().float(), dx=dx)
         eng.release(ws)
         ctx.ws = None
-        return None, None, None
+        return (dx.to(dtype) if dx is not None else None), None, None
 
 
 class _EngineNet(nn.Module):
@@ -945,7 +956,7 @@ class _EngineNet(nn.Module):
         if self.fc.in_features != self._stages()[-1][-1].bn1.num_features * self.block.expansion:
             raise RuntimeError("fc.in_features must match the last stage (%d channels)"
                                % (self._stages()[-1][-1].bn1.num_features * self.block.expansion))
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if self.training and wants_autograd(self, x):
             return _Fn.apply(x, self.fc.weight, self)
         if not self.training:
             from ..gradcam import hooked_eval_forward, hooks_registered
@@ -956,14 +967,16 @@ class _EngineNet(nn.Module):
         eng.release(ws)
         return out
 
-    def forward_backward(self, x, target):
+    def forward_backward(self, x, target, input_grad=None):
         eng = self._eng()
+        if input_grad is not None:
+            check_input_grad(input_grad, x)
         ws = eng.forward(x, self.training)
         B, n = ws.logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
         ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
-        eng.backward(ws, dl)
+        eng.backward(ws, dl, dx=input_grad)
         logits = ws.logits.clone()
         eng.release(ws)
         return loss, logits

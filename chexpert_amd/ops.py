@@ -296,6 +296,24 @@ def conv_wgrad(g, x, dw, *, kh=1, kw=1, stride=1, pad=0, mode=MODE_CONV, g_prolo
     _wgrad_used(arena, dfr)
 
 
+def stem_input_grad(dz, y, pa, pb, pc, w, dx, *, stride, pad):
+    """cx_stem_input_grad: dx (fp32 NCHW (B,3,H,W), overwritten) = input gradient of the stem convolution w (fp32 (C0,wc,k,k))
+    at the gradient g = pa*dz + pb*y + pc (dz, y: (B,Ho,Wo,C0) NHWC in the storage type).  Raises outside the kernel's geometries
+    (CX_EUNSUPPORTED): there is no other path."""
+    require_cuda(dz, y, pa, pb, pc, w, dx)
+    B, Ho, Wo, C0, ldz = _nhwc(dz)
+    By, Hy, Wy, Cy, ldy = _nhwc(y)
+    assert (By, Hy, Wy, Cy) == (B, Ho, Wo, C0) and y.dtype == dz.dtype
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 4 and w.shape[0] == C0 and w.shape[2] == w.shape[3]
+    assert dx.dtype == torch.float32 and dx.is_contiguous() and dx.dim() == 4 and dx.shape[:2] == (B, 3)
+    for t in (pa, pb, pc):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= C0
+    H, W = dx.shape[2], dx.shape[3]
+    check(lib().cx_stem_input_grad(ptr(dz), ptr(y), ptr(pa), ptr(pb), ptr(pc), ptr(w), ptr(dx), ldz, ldy, w.shape[1], B, H, W, Ho, Wo, C0,
+                                   w.shape[2], stride, pad, 1 if dz.dtype == torch.float32 else 0, stream_ptr()), "cx_stem_input_grad")
+    return dx
+
+
 def conv3x3_wgrad_batch(items):
     """cx_conv3x3_wgrad_batch: the 3x3 weight gradients of several dense layers of one block in ONE launch.
     items: [(g dense (B,H,W,32) gradient slice, x saved bottleneck tensor (B,H,W,128), pa, pb norm2 scale / shift, dw fp32 OIHW)].

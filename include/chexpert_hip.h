@@ -226,6 +226,15 @@ int cx_last_stat_rows(void);
 int cx_conv_gemm(const CxConv* p, void* stream);
 /* weight gradient (autograd of the same convs)                                                   */
 int cx_conv_wgrad(const CxWgrad* p, void* stream);
+/* input gradient of the stem convolution down to the 3-channel image (x.grad through features.conv0 / conv1 / stem[0]):
+ * dx[b][c][iy][ix] = sum_{o,ky,kx} w[o][c][ky][kx] * g[b][oy][ox][o], iy = stride*oy - pad + ky, c = 0..2, with
+ * g = pa[o]*dz + pb[o]*y + pc[o] (the stem weight gradient's CX_PRO_AFFINE2 prologue).  dz / y: (B,Ho,Wo,>=C0) NHWC, row
+ * pitches ldz / ldy, dtype 0 = bf16 (g and w rounded to bf16, fp32 sums), 1 = fp32; w: fp32 master (C0,wc,k,k), the first 3 input
+ * channels used; dx: fp32 NCHW (B,3,H,W), overwritten, deterministic (no atomics).  Geometries: k7 s2 p3, k3 s2 p0|p1
+ * (bf16: C0 % 8 == 0, C0 <= 64), k3 s1 p1, k5 s1 p2 (C0 <= 128); anything else CX_EUNSUPPORTED.                        */
+int cx_stem_input_grad(const void* dz, const void* y, const float* pa, const float* pb, const float* pc, const float* w, float* dx,
+                       int ldz, int ldy, int wc, int B, int H, int W, int Ho, int Wo, int C0, int k, int stride, int pad, int dtype,
+                       void* stream);
 
 /* Input gradient AND weight gradient of the dense-layer bottleneck 1x1 convolution in one pass over dZ and the activation
  * slice (K = 128 gradient channels, CX_EPI_MASK): p as for cx_conv_gemm (p->ex = the activation slice x, p->e_sc / p->e_sh its
