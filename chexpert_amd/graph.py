@@ -65,9 +65,7 @@ class GraphedTrainStep:
         self.replays += 1
         # the captured optimiser kernel has just changed the fp32 masters without touching tensor versions: an eval forward that
         # follows must repack the weights (Engine.pack(train=False) compares versions)
-        eng = self.model._eng()
-        if hasattr(eng, "packed_version"):
-            eng.packed_version = None
+        self.model._eng().packed_version = None
         self.model._nbt_pending += 1           # BatchNorm num_batches_tracked is host-side bookkeeping (flushed by state_dict())
         return self.loss, self.logits
 
@@ -197,8 +195,6 @@ class SegmentedTrainStep:
                 else:
                     red.wait()
         self.replays += 1
-        eng = self.model._eng()
-        if hasattr(eng, "packed_version"):
-            eng.packed_version = None
+        self.model._eng().packed_version = None
         self.model._nbt_pending += 1
         return self.loss, self.logits

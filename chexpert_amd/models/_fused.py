@@ -1,0 +1,369 @@
+"""What the fused networks (DenseNet, ResNet / WideResNet, EfficientNet) share: the nn.Module surface (FusedNet, with the one
+autograd function), the host side of their engines (FusedEngine: flat parameter masters, weight packing, workspaces, the step
+protocol of backward) and the coefficient-vector bookkeeping (_Vec, _BN)."""
+import contextlib
+import os
+
+import torch
+import torch.nn as nn
+
+from .. import ops
+from .._lib import CxPackDesc
+
+
+# --------------------------------------------------------------------------------------------- input gradient (x.grad)
+def wants_autograd(model, x):
+    """model.forward routes through the autograd function when a train-mode step under grad mode needs a backward: some parameter
+    requires a gradient, or the input does (x.grad with every parameter frozen: saliency maps, adversarial examples)."""
+    return model.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in model.parameters()))
+
+
+def input_grad_buffer(x_shape, device):
+    """fp32 (B, 3, H, W) buffer cx_stem_input_grad writes (every element)."""
+    if len(x_shape) != 4 or x_shape[1] != 3:
+        raise RuntimeError("the input gradient needs a (B,3,H,W) float input (got %s)" % (tuple(x_shape),))
+    return torch.empty(x_shape[0], 3, x_shape[2], x_shape[3], dtype=torch.float32, device=device)
+
+
+def check_input_grad(buf, x):
+    """forward_backward(input_grad=buf): a preallocated fp32 (B,3,H,W) tensor on x's device (shape checks only: no host sync)."""
+    if buf.dtype != torch.float32 or not buf.is_contiguous() or buf.device != x.device or tuple(buf.shape) != tuple(x.shape) \
+            or x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("input_grad must be a contiguous fp32 tensor of the (B,3,H,W) float input's shape on its device")
+
+
+@contextlib.contextmanager
+def params_untouched(params, flat_grad):
+    """Backward of a step in which no parameter requires a gradient (only x.grad was asked for): the engine still computes its
+    weight gradients into its flat buffer, but afterwards every parameter's .grad is what it was before (None stays None; a .grad
+    that views the flat buffer gets its values back)."""
+    saved = [p.grad for p in params]
+    backup = flat_grad.clone() if any(g is not None for g in saved) else None
+    for p in params:
+        p.grad = None
+    try:
+        yield
+    finally:
+        if backup is not None:
+            flat_grad.copy_(backup)
+        for p, g in zip(params, saved):
+            p.grad = g
+
+
+# --------------------------------------------------------------------------------------------- module side
+class _Fn(torch.autograd.Function):
+    """loss.backward() through a fused network: forward runs the engine's training forward, backward its backward pass.  `anchor`
+    is a parameter of the network, so that autograd records the call; x.grad is returned when the input needs it."""
+
+    @staticmethod
+    def forward(ctx, x, anchor, model):
+        if not model.training:
+            raise NotImplementedError("autograd through the fused %s needs train() mode (batch-statistic BatchNorm backward); for "
+                                      "Grad-CAM use chexpert_amd.gradcam.grad_cam" % type(model).__name__)
+        eng = model._engine
+        ws = eng.forward(x, True)
+        ctx.model, ctx.eng, ctx.ws, ctx.x_meta = model, eng, ws, (tuple(x.shape), x.dtype, x.device)
+        return ws.logits.clone()
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        eng, ws = ctx.eng, ctx.ws
+        if ws is None:
+            raise RuntimeError("backward through the fused %s can only run once per forward" % type(ctx.model).__name__)
+        shape, dtype, dev = ctx.x_meta
+        dx = input_grad_buffer(shape, dev) if ctx.needs_input_grad[0] else None
+        frozen = not any(p.requires_grad for p in ctx.model.parameters())
+        with params_untouched(eng.params, eng.flat_grad) if frozen else contextlib.nullcontext():
+            eng.backward(ws, dlogits.contiguous().float(), dx=dx)
+        eng.release(ws)
+        ctx.ws = None
+        return (dx.to(dtype) if dx is not None else None), None, None
+
+
+class FusedNet(nn.Module):
+    """nn.Module surface of a network whose forward / backward run as one schedule of fused HIP kernels.  A subclass supplies
+    `_eng()` (its engine, built lazily into `_engine`) and `_anchor()` (the parameter the autograd function is recorded on)."""
+
+    def __init__(self):
+        super().__init__()
+        self._nbt_pending = 0            # training forwards not yet counted in the BatchNorms' num_batches_tracked
+        self._engine = None
+
+    def storage_dtype(self, dtype):
+        """Storage type of the activations inside the fused schedule: torch.bfloat16 (default: bf16 tensors, fp32 accumulation
+        and statistics) or torch.float32 -- the parity mode of north_star ("1e-3 fp32"): the same schedule on fp32 tensors with
+        the exact f32 MFMA (csrc/conv_f32.hip).  Parameters are fp32 masters either way.  Returns self."""
+        dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}.get(dtype, dtype)
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError("storage dtype must be bf16 or fp32")
+        object.__setattr__(self, "_storage_dtype", dtype)
+        return self
+
+    def state_dict(self, *args, **kwargs):
+        if self._nbt_pending:
+            for mod in self.modules():
+                if isinstance(mod, nn.BatchNorm2d) and mod.num_batches_tracked is not None:
+                    mod.num_batches_tracked += self._nbt_pending
+            self._nbt_pending = 0
+        return super().state_dict(*args, **kwargs)
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("chexpert_amd %s runs on the GPU only (hand-written HIP kernels); there is no CPU fallback -- move "
+                               "the model and the input to cuda" % type(self).__name__)
+        eng = self._eng()
+        if wants_autograd(self, x):
+            return _Fn.apply(x, self._anchor(), self)
+        if not self.training:
+            from ..gradcam import hooked_eval_forward, hooks_registered
+            if hooks_registered(self):                     # Grad-CAM hook protocol of the reference (chexpert.py:271-272)
+                return hooked_eval_forward(self, x)
+        ws = eng.forward(x, self.training)
+        out = ws.logits.clone()
+        eng.release(ws)
+        return out
+
+    # fused training step (bench / trainer fast path; same arithmetic as chexpert.py:159-163)
+    def forward_backward(self, x, target, input_grad=None):
+        """logits = model(x); loss = BCEWithLogits(logits, target).sum(1).mean(0); loss.backward().
+        Returns (loss, logits) as device tensors without a host sync.  input_grad: None, or a preallocated fp32 (B,3,H,W) tensor that
+        also receives d loss / d x (what x.grad would hold), still without a host sync."""
+        eng = self._eng()
+        if input_grad is not None:
+            check_input_grad(input_grad, x)
+        ws = eng.forward(x, self.training)
+        B, n = ws.logits.shape
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
+        ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
+        eng.backward(ws, dl, dx=input_grad)
+        logits = ws.logits.clone()
+        eng.release(ws)
+        return loss, logits
+
+
+# --------------------------------------------------------------------------------------------- engine side
+def _up4(n):
+    return (n + 3) // 4 * 4
+
+
+def flatten(tensors, dev):
+    """Moves `tensors` into one new zero-padded fp32 buffer on dev, each at a 16-byte aligned offset, and makes every tensor's data
+    its view there.  Returns (buffer, offsets in floats)."""
+    offs, total = [], 0
+    for t in tensors:
+        offs.append(total)
+        total += _up4(t.numel())
+    flat = torch.zeros(total, dtype=torch.float32, device=dev)
+    for t, off in zip(tensors, offs):
+        flat[off:off + t.numel()].copy_(t.data.reshape(-1))
+        t.data = flat[off:off + t.numel()].view(t.shape)
+    return flat, offs
+
+
+class _Vec:
+    """Carves fp32 vectors out of one flat tensor (16-byte aligned), from offset `base` on."""
+
+    def __init__(self, base=0):
+        self.n = base
+
+    def take(self, n):
+        off = self.n
+        self.n += _up4(n)
+        return (off, n)
+
+
+class _BN:
+    """Vector slots of one BatchNorm."""
+
+    def __init__(self, V, C, fz, bz):
+        self.C = C
+        self.sum, self.sq = fz.take(C), fz.take(C)                    # zeroed every forward
+        self.S1, self.S2 = bz.take(C), bz.take(C)                     # zeroed every backward
+        self.sc, self.sh, self.mean, self.rstd = (V.take(C) for _ in range(4))
+        self.pa, self.pb, self.pc = (V.take(C) for _ in range(3))
+
+    @staticmethod
+    def plan(bns):
+        """Slots of every BatchNorm of `bns` in one vector laid out as [forward-zeroed sums | backward-zeroed sums | the rest].
+        Returns ({id(bn): _BN}, the _Vec of the rest, for more slots behind them, fwd_zero, bwd_zero)."""
+        nf = sum(2 * _up4(bn.num_features) for bn in bns)
+        fz, bz, rest = _Vec(0), _Vec(nf), _Vec(2 * nf)
+        slots = {id(bn): _BN(rest, bn.num_features, fz, bz) for bn in bns}
+        return slots, rest, (0, nf), (nf, nf)
+
+
+class FusedEngine:
+    """Host side of a fused network: binds the module's parameters to one flat fp32 buffer (and their gradients to another),
+    packs the convolution weights into the kernels' layouts, keeps the activation workspaces, and wraps the network's backward
+    schedule (`_backward`) in the step protocol: .grad binding, weight-gradient deferral and the data-parallel reducer."""
+
+    def __init__(self, model):
+        self.model = model
+        # activation storage type: bf16, or fp32 = the parity mode of north_star ("1e-3 fp32")
+        self.dtype = getattr(model, "_storage_dtype", torch.bfloat16)
+        # deterministic statistics and weight gradients (per-workgroup rows summed in row order, slab sums): two steps on the same
+        # batch give the same bits; CHEXPERT_DET=0 keeps the fp32 atomics
+        self.det = os.environ.get("CHEXPERT_DET", "1") != "0"
+        self.flat = self.flat_grad = self.device = None
+        self.pool = {}
+        self.reducer = None          # chexpert_amd.parallel.GradReducer when data-parallel
+        self.packed_version = None
+
+    # ---- binding
+    def bound(self, dev):
+        """Whether the module's parameters still are the views of the flat buffer on dev."""
+        if self.flat is None or self.device != dev:
+            return False
+        params = list(self.model.parameters())
+        return len(params) == len(self.offsets) and \
+            all(p.data_ptr() == self.flat.data_ptr() + 4 * off for p, off in zip(params, self.offsets))
+
+    def bind_params(self, dev):
+        """The fp32 parameter masters become views of one flat buffer, their gradients views of another (grad_views)."""
+        m = self.model
+        params = list(m.parameters())
+        for p in params:
+            if p.dtype != torch.float32:
+                raise RuntimeError("parameters must be fp32 masters (bf16 is the kernels' storage type)")
+        for b in m.buffers():
+            if b.device != dev:
+                raise RuntimeError("module buffers are on %s, input on %s -- call model.to(device)" % (b.device, dev))
+        self.flat, self.offsets = flatten(params, dev)
+        self.params = params
+        self.flat_grad = torch.zeros_like(self.flat)
+        self.grad_views = [self.flat_grad[off:off + p.numel()].view(p.shape) for p, off in zip(params, self.offsets)]
+        self.off_of = {id(p): off for p, off in zip(params, self.offsets)}
+        self.device = dev
+        self.pool = {}
+
+    def plan_packing(self, convs, stem=None, stem_layout=False, stem8=None):
+        """Descriptor table of the weight packing (CxPackDesc, one launch packs them all): `stem` in the forward layout only (the
+        7x7 stride-2 stem kernel's own layout when stem_layout), then every conv of `convs` in the forward (w_fwd) and transposed
+        (w_bwd) layouts -- a grouped conv as one convolution per group --, then the region of `stem8`, a 3-input-channel stem that
+        _pack_stem8 pads to 8 channels and packs itself (at stem_off)."""
+        descs, cur = [], 0
+        self.wf, self.wb = {}, {}
+
+        def add(conv, transpose=False, stem=False):
+            nonlocal cur
+            O, I, kh, kw = conv.weight.shape
+            src = self.off_of[id(conv.weight)]
+            gr = getattr(conv, "groups", 1)
+            if gr > 1:
+                # the filters of group g are rows [g O/G, (g+1) O/G) of the (O, I/G, kh, kw) weight -- contiguous --; the entry is
+                # the list of the groups' (offset, size)
+                og, n = O // gr, (O // gr) * I * kh * kw
+                ent = []
+                for g in range(gr):
+                    descs.append(CxPackDesc(src + g * n, cur, og, I, kh, kw, int(transpose), 0))
+                    ent.append((cur, n))
+                    cur += (n + 7) // 8 * 8
+                return ent
+            n = (49 * O * 4 if self.dtype == torch.float32 else 7 * O * 32) if stem else O * I * kh * kw
+            descs.append(CxPackDesc(src, cur, O, I, kh, kw, int(transpose), int(stem)))
+            off = cur
+            cur += (n + 7) // 8 * 8
+            return (off, n)
+        if stem is not None:
+            self.wf[id(stem)] = add(stem, stem=stem_layout)
+        for conv in convs:
+            self.wf[id(conv)] = add(conv)
+            self.wb[id(conv)] = add(conv, transpose=True)
+        if stem8 is not None:
+            self.stem_off = cur
+            cur += 9 * stem8.out_channels * 8
+        self.packed = torch.empty(cur, dtype=self.dtype, device=self.device)
+        arr = (CxPackDesc * len(descs))(*descs)
+        self.desc_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+        self.n_desc = len(descs)
+        self.packed_version = None
+
+    def pack(self, train):
+        # training: parameters change every step (possibly through the fused optimiser, which does not bump tensor versions) ->
+        # always repack (one launch); eval: only when a version moved
+        ver = None if train else sum(p._version for p in self.params)
+        if ver is not None and ver == self.packed_version:
+            return
+        ops.pack_weights_table(self.flat, self.packed, self.desc_dev, self.n_desc)
+        self._pack_stem8()
+        self.packed_version = ver
+
+    def _pack_stem8(self):
+        """Packs the stem8 region of plan_packing (networks with a 3-to-8-channel stem)."""
+
+    def w_fwd(self, conv, group=None):
+        off, n = self.wf[id(conv)] if group is None else self.wf[id(conv)][group]
+        return self.packed[off:off + n]
+
+    def w_bwd(self, conv, group=None):
+        off, n = self.wb[id(conv)] if group is None else self.wb[id(conv)][group]
+        return self.packed[off:off + n]
+
+    def grad_of(self, p):
+        """p's gradient in the flat gradient buffer (1-D view)."""
+        off = self.off_of[id(p)]
+        return self.flat_grad[off:off + p.numel()]
+
+    @staticmethod
+    def _v(ws, slot, n=None):
+        off, m = slot
+        return ws.vec[off:off + (m if n is None else n)]
+
+    # ---- workspaces
+    def acquire(self, B, H, W):
+        lst = self.pool.setdefault((B, H, W), [])
+        return lst.pop() if lst else self._new_workspace(B, H, W)
+
+    def release(self, ws):
+        lst = self.pool.setdefault(ws.key, [])
+        if len(lst) < 2:
+            lst.append(ws)
+
+    # ---- backward
+    def _defer_wgrad(self):
+        """Whether a backward pass defers the ordered slab sums of its weight gradients to one table-driven launch at its end."""
+        return self.det
+
+    def backward(self, ws, dlogits, dx=None):
+        """The backward pass of the forward that filled `ws`, from d loss / d logits; dx: None, or an fp32 (B,3,H,W) buffer that also
+        receives the input gradient (cx_stem_input_grad).  Gradients accumulate into the parameters' .grad, which are views of
+        the flat gradient buffer (bound here when some .grad is None)."""
+        ops.set_det_wgrad(self.det)            # reproducible weight-gradient sums with the deterministic statistics
+        # the ordered slab sums run as one table-driven launch at the end of the pass (ops.wgrad_defer_*); a data-parallel run
+        # flushes them before each gradient bucket leaves (GradReducer.pre_launch)
+        deferred = self._defer_wgrad() and ops.wgrad_defer_begin(self.device)
+        try:
+            fresh = any(p.grad is None for p in self.params)
+            if fresh:
+                self.flat_grad.zero_()
+            elif not all(p.grad.data_ptr() == gv.data_ptr() for p, gv in zip(self.params, self.grad_views)):
+                raise RuntimeError("parameter .grad tensors were replaced; call zero_grad(set_to_none=True) first")
+            red = self.reducer
+            if red is not None:
+                red.begin()
+            done = (lambda p: red.ready(self.off_of[id(p)])) if red is not None else (lambda p: None)
+            self._backward(ws, dlogits, dx, done)
+            if red is not None:
+                red.finish()
+            if fresh:
+                for p, gv in zip(self.params, self.grad_views):
+                    p.grad = gv
+            if deferred:
+                ops.wgrad_defer_flush(self.device)
+        finally:
+            if deferred:
+                ops.wgrad_defer_abort(self.device)
+
+    def _pre_bucket(self):
+        # the deferred weight-gradient slab sums (ops.wgrad_defer_*) run before each bucket leaves, so that the bucket is final
+        ops.wgrad_defer_flush(self.device, keep=True)
+
+    def enable_data_parallel(self, bucket_bytes=16 << 20, group=None):
+        """Average gradients across ranks inside backward (bucketed all-reduce overlapped with the remaining backward kernels).
+        Call after the first bind (i.e. after one forward)."""
+        from ..parallel import GradReducer
+        if self.flat_grad is None:
+            raise RuntimeError("bind the engine first (run one forward)")
+        self.reducer = GradReducer(self.flat_grad, bucket_bytes, group)
+        self.reducer.pre_launch = self._pre_bucket

@@ -27,8 +27,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .._lib import CxPackDesc, check, lib, ptr, stream_ptr
-from ._autograd import check_input_grad, input_grad_buffer, params_untouched, wants_autograd
+from .._lib import check, lib, ptr, stream_ptr
+from ._fused import FusedEngine, FusedNet, _Vec, flatten
 
 
 # --------------------------------------------------------------------------------------------- parameter containers
@@ -130,6 +130,13 @@ class AAConv2d(nn.Module):
             why.append("out_channels-dv = %d convolution channels are not a multiple of 8" % (self.out_channels - dv))
         return "; ".join(why)
 
+    def check_supported(self, branch_aligned=True):
+        """Raises NotImplementedError naming what unsupported() finds."""
+        why = self.unsupported(branch_aligned)
+        if why:
+            raise NotImplementedError("AAConv2d(dk=%d, dv=%d, nh=%d, relative=%s): %s (the HIP attention kernels cover dk/nh and "
+                                      "dv/nh = 1 .. 64 with dv <= 104)" % (self.dk, self.dv, self.nh, self.relative, why))
+
     def rel_tables(self):
         return (self.key_rel_h, self.key_rel_w) if self.relative else (self._rel0_h, self._rel0_w)
 
@@ -177,19 +184,6 @@ class _Transition(nn.Sequential):
 
 
 # --------------------------------------------------------------------------------------------- workspace
-class _Vec:
-    """Carves fp32 vectors out of one flat tensor (16-byte aligned)."""
-
-    def __init__(self):
-        self.n = 0
-        self.slots = []
-
-    def take(self, n):
-        off = self.n
-        self.n += (n + 3) // 4 * 4
-        return (off, n)
-
-
 class _Workspace:
     """Activation buffers + coefficient vectors for one (B,H,W); owned by one in-flight forward."""
 
@@ -284,9 +278,8 @@ class _Workspace:
 
 
 # --------------------------------------------------------------------------------------------- engine
-class _Engine:
-    """Host-side schedule: binds the module's parameters to flat buffers, packs weights, and issues the
-    kernel sequence of forward and backward on the current stream."""
+class _Engine(FusedEngine):
+    """Host-side schedule: issues the kernel sequence of forward and backward on the current stream."""
     SLAB = 1 << 22               # floats per half of the statistic-row scratch (rows x channels of the largest producer)
     EW_ROWS = 2048               # workgroups (= rows) of the element-wise statistic producers in deterministic mode
 
@@ -305,7 +298,7 @@ class _Engine:
         return ws.v(slots[0]), ws.v(slots[1]), self.stat_replicas, slots[0][1]
 
     def __init__(self, model):
-        self.model = model
+        super().__init__(model)
         f = model.features
         self.growth = model.growth_rate
         self.mid = getattr(model, "_mid", None) or model.bn_size * model.growth_rate
@@ -322,20 +315,12 @@ class _Engine:
                 # DenseNet-BC rounds it up, and pads between the two branches of an attention-augmented transition)
                 c = getattr(f, "denseblock%d" % (len(self.blocks) + 1)).denselayer1.norm1.num_features
         self.c_final = c
-        self.flat = None
-        self.flat_grad = None
-        self.device = None
-        self.n_classes = None
-        self.pool = {}
-        self.reducer = None          # chexpert_amd.parallel.GradReducer when data-parallel
         self.side = None             # side stream for the weight-gradient kernels of the dense layers
-        self.dtype = getattr(model, "_storage_dtype", torch.bfloat16)
         self.stat_replicas = 16      # legacy (atomic) statistics: copies of every conv-produced vector (memory-side contention)
         # Deterministic statistics: per-workgroup rows summed in a fixed order instead of fp32 atomics (bit-identical activations,
         # losses and gradients from run to run); CHEXPERT_DET=0 brings the atomics back.  The AA transitions feed a block's first
         # channels from two kernels -- conv branch and attention out-projection: their statistic rows are reduced one after the
         # other, see _aa_forward.
-        self.det = os.environ.get("CHEXPERT_DET", "1") != "0"
         self.drop_rate = float(getattr(model, "drop_rate", 0.0))
         self.drop_seed = None        # device int64: the dropout kernels' seed, advanced once per training forward (graph-replayable)
         # two dense layers per fused 1x1 backward pass (_pair_backward): "0" never (default: measured in round 4, the pass saves
@@ -381,95 +366,23 @@ class _Engine:
 
     # ---- parameter binding
     def bind(self, dev):
-        m = self.model
-        params = [p for _, p in m.named_parameters()]
-        n_classes = m.classifier.out_features
-        ok = (self.flat is not None and self.device == dev and self.n_classes == n_classes
-              and len(params) == len(self.offsets)
-              and all(p.data_ptr() == self.flat.data_ptr() + 4 * off for p, off in zip(params, self.offsets)))
-        if ok:
+        if self.bound(dev):
             return
+        m = self.model
         if m.classifier.in_features != self.c_final:
             raise RuntimeError("classifier.in_features must be %d" % self.c_final)
-        offs, total = [], 0
-        for p in params:
-            if p.dtype != torch.float32:
-                raise RuntimeError("parameters must be fp32 masters (bf16 is the kernels' storage type)")
-            offs.append(total)
-            total += (p.numel() + 3) // 4 * 4
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        for p, off in zip(params, offs):
-            flat[off:off + p.numel()].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + p.numel()].view(p.shape)
-        for b in m.buffers():
-            if b.device != dev:
-                raise RuntimeError("module buffers are on %s, input on %s -- call model.to(device)" % (b.device, dev))
-        self.flat, self.offsets, self.params = flat, offs, params
-        self.flat_grad = torch.zeros_like(flat)
-        self.grad_views = [self.flat_grad[off:off + p.numel()].view(p.shape) for p, off in zip(params, offs)]
-        self.off_of = {id(p): off for p, off in zip(params, offs)}
-        self.device, self.n_classes = dev, n_classes
-        self.pool = {}
+        self.bind_params(dev)
+        self.n_classes = m.classifier.out_features
         # packing table: every conv weight, forward layout (+ transposed layout for input gradients)
-        descs, cur = [], 0
-        self.wf, self.wb = {}, {}
-
-        def add(conv, transpose=False, stem=False):
-            nonlocal cur
-            O, I, kh, kw = conv.weight.shape
-            f32 = self.dtype == torch.float32
-            n = (49 * O * 4 if f32 else 7 * O * 32) if stem else O * I * kh * kw
-            d = CxPackDesc(self.off_of[id(conv.weight)], cur, O, I, kh, kw, int(transpose), int(stem))
-            descs.append(d)
-            off = cur
-            cur += (n + 7) // 8 * 8
-            return (off, n)
         f = m.features
-        self.wf[id(f.conv0)] = add(f.conv0, stem=not self.cifar)
-        for mod in f.modules():
-            if isinstance(mod, nn.Conv2d) and mod is not f.conv0:
-                self.wf[id(mod)] = add(mod)
-                self.wb[id(mod)] = add(mod, transpose=True)
-        self.packed = torch.empty(cur, dtype=self.dtype, device=dev)
+        self.plan_packing([mod for mod in f.modules() if isinstance(mod, nn.Conv2d) and mod is not f.conv0], stem=f.conv0,
+                          stem_layout=not self.cifar)
         # CIFAR stem: norm0 + relu0 write the first channels of block 1's buffer through a 1x1 identity convolution (BN + ReLU in
         # its prologue, the block's statistic rows from its epilogue); its backward is the same convolution with the mask epilogue
         self.eye = torch.eye(self.c_init, dtype=self.dtype, device=dev).reshape(-1) if self.cifar else None
-        arr = (CxPackDesc * len(descs))(*descs)
-        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        self.desc_dev = host.to(dev)
-        self.n_desc = len(descs)
-        self.packed_version = None
 
-    def pack(self, train):
-        # training: parameters change every step (possibly through the fused optimiser, which does not
-        # bump tensor versions) -> always repack (one launch); eval: only when a version moved
-        ver = None if train else sum(p._version for p in self.params)
-        if ver is not None and ver == self.packed_version:
-            return
-        ops.pack_weights_table(self.flat, self.packed, self.desc_dev, self.n_desc)
-        self.packed_version = ver
-
-    def w_fwd(self, conv):
-        off, n = self.wf[id(conv)]
-        return self.packed[off:off + n]
-
-    def w_bwd(self, conv):
-        off, n = self.wb[id(conv)]
-        return self.packed[off:off + n]
-
-    def grad_of(self, p):
-        off = self.off_of[id(p)]
-        return self.flat_grad[off:off + p.numel()]
-
-    # ---- workspaces
-    def acquire(self, B, H, W):
-        lst = self.pool.setdefault((B, H, W), [])
-        return lst.pop() if lst else _Workspace(self, B, H, W, self.device)
-
-    def release(self, ws):
-        lst = self.pool.setdefault(ws.key, [])
-        if len(lst) < 2:
-            lst.append(ws)
+    def _new_workspace(self, B, H, W):
+        return _Workspace(self, B, H, W, self.device)
 
     # ---- forward
     def _bn(self, ws, stats, count, bn, out_slots, C_, train, mean_slot=None, rstd_slot=None):
@@ -711,41 +624,21 @@ class _Engine:
                         ops.conv_wgrad(dyc, y1, dw, kh=3, kw=3, pad=1, x_prologue=ops.PRO_AFFINE_RELU, pa=pa, pb=pb)
 
     # ---- backward
-    def backward(self, ws, dlogits, dx=None):
-        """dx: None, or an fp32 (B,3,H,W) buffer that also receives the input gradient (cx_stem_input_grad)"""
-        self._w2_items = []
-        ops.set_det_wgrad(self.det)            # reproducible weight-gradient sums with the deterministic statistics
-        # the ordered sums of the weight-gradient slabs run as ONE table-driven launch at the end of the pass (ops.wgrad_defer_*);
-        # a data-parallel run flushes them before each gradient bucket leaves (GradReducer.pre_launch)
-        deferred = os.environ.get("CHEXPERT_WGRAD_DEFER", "1") != "0" and ops.wgrad_defer_begin(self.device)
-        try:
-            self._backward(ws, dlogits, dx)
-            if deferred:
-                ops.wgrad_defer_flush(self.device)
-        finally:
-            if deferred:
-                ops.wgrad_defer_abort(self.device)
+    def _defer_wgrad(self):
+        return os.environ.get("CHEXPERT_WGRAD_DEFER", "1") != "0"
 
-    def _backward(self, ws, dlogits, dx=None):
+    def _backward(self, ws, dlogits, dx, done):
+        self._w2_items = []
         m, f, s = self.model, self.model.features, self.slots
-        R = self.stat_replicas
         B = ws.B
         dev = self.device
         ws.alloc_backward(self, dev)
         z0, zn = self.bwd_zero
         ws.vec[z0:z0 + zn].zero_()
-        fresh = any(p.grad is None for p in self.params)
-        if fresh:
-            self.flat_grad.zero_()
-        elif not all(p.grad.data_ptr() == gv.data_ptr() for p, gv in zip(self.params, self.grad_views)):
-            raise RuntimeError("parameter .grad tensors were replaced; call zero_grad(set_to_none=True) first")
         nb = len(self.blocks)
         G = self.grad_of
         v = ws.v
         red = self.reducer
-        if red is not None:
-            red.begin()
-        done = (lambda p: red.ready(self.off_of[id(p)])) if red is not None else (lambda p: None)
         # head
         bi = nb - 1
         c0, n_layers = self.blocks[bi]
@@ -989,11 +882,6 @@ class _Engine:
         main.wait_stream(side)
         if side is main and os.environ.get("CHEXPERT_W2_SIDE", "0") == "1":
             main.wait_stream(self.side)
-        if red is not None:
-            red.finish()
-        if fresh:
-            for p, gv in zip(self.params, self.grad_views):
-                p.grad = gv
 
     def _pair_backward(self, ws, bi, li, dz2_a, dz2_b, slice_q, done):
         """Backward of dense layers li (a) and li - 1 (b) of block bi with ONE pass of the fused 1x1 backward over the channels
@@ -1080,41 +968,9 @@ class _Engine:
         coef1(lb, sb_red(rows), 0, cin_b, slice_q(bi, li - 2))
         done(lb.norm1.weight)
 
-    def enable_data_parallel(self, bucket_bytes=16 << 20, group=None):
-        """Average gradients across ranks inside backward (bucketed all-reduce overlapped with the
-        remaining backward kernels).  Call after the first bind (i.e. after one forward) or it binds now."""
-        from ..parallel import GradReducer
-        if self.flat_grad is None:
-            raise RuntimeError("bind the engine first (run one forward)")
-        self.reducer = GradReducer(self.flat_grad, bucket_bytes, group)
-        # the deferred weight-gradient slab sums (ops.wgrad_defer_*) run before each bucket leaves, so that the bucket is final
-        self.reducer.pre_launch = lambda: (self._flush_w2(), ops.wgrad_defer_flush(self.device, keep=True))
-
-
-class _Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, anchor, model):
-        eng = model._engine
-        if not model.training:
-            raise NotImplementedError("autograd through the fused DenseNet needs train() mode (batch-statistic BatchNorm "
-                                      "backward); for Grad-CAM use chexpert_amd.gradcam.grad_cam")
-        ws = eng.forward(x, True)
-        ctx.model, ctx.ws, ctx.x_meta = model, ws, (tuple(x.shape), x.dtype, x.device)
-        return ws.logits.clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        eng, ws = ctx.model._engine, ctx.ws
-        if ws is None:
-            raise RuntimeError("backward through the fused DenseNet can only run once per forward")
-        shape, dtype, dev = ctx.x_meta
-        dx = input_grad_buffer(shape, dev) if ctx.needs_input_grad[0] else None
-        frozen = not any(p.requires_grad for p in ctx.model.parameters())
-        with params_untouched(eng.params, eng.flat_grad) if frozen else contextlib.nullcontext():
-            eng.backward(ws, dlogits.contiguous().float(), dx=dx)
-        eng.release(ws)
-        ctx.ws = None
-        return (dx.to(dtype) if dx is not None else None), None, None
+    def _pre_bucket(self):
+        self._flush_w2()
+        super()._pre_bucket()
 
 
 # --------------------------------------------------------------------------------------------- channel-padded twin
@@ -1221,54 +1077,31 @@ class _TwinNet(nn.Module):
         raise RuntimeError("parameter holder of the channel-padded schedule")
 
 
-class _PaddedEngine:
+class _PaddedEngine(FusedEngine):
     """Engine of a network with unaligned widths: binds the REAL parameters to a flat buffer (what optimisers and state_dict see),
     runs the channel-padded twin on an inner _Engine and moves parameters / running statistics / gradients between the two flat
     layouts with one table-driven launch each (cx_chan_map_table)."""
 
     def __init__(self, model):
-        self.model = model
+        super().__init__(model)
         self.twin = _TwinNet(model)
-        object.__setattr__(self.twin, "_storage_dtype", getattr(model, "_storage_dtype", torch.bfloat16))
+        object.__setattr__(self.twin, "_storage_dtype", self.dtype)
         self.inner = _Engine(self.twin)
-        self.dtype = self.inner.dtype
         self.c_final = model.classifier.in_features
-        self.flat = self.flat_grad = self.device = None
-        self.reducer = None
-        self.packed_version = None
 
     def bind(self, dev):
-        m = self.model
-        params = [p for _, p in m.named_parameters()]
-        if (self.flat is not None and self.device == dev and
-                all(p.data_ptr() == self.flat.data_ptr() + 4 * off for p, off in zip(params, self.offsets)) and
-                all(b.data_ptr() == self.stat.data_ptr() + 4 * off for b, off in zip(self.rbufs, self.boffs))):
+        if self.bound(dev) and all(b.data_ptr() == self.stat.data_ptr() + 4 * off for b, off in zip(self.rbufs, self.boffs)):
             return
         if self.twin.classifier.weight.device != dev:
             self.twin.to(dev)
         self.inner.bind(dev)
-
-        def flatten(tensors):
-            offs, total = [], 0
-            for t in tensors:
-                offs.append(total)
-                total += (t.numel() + 3) // 4 * 4
-            flat = torch.zeros(total, dtype=torch.float32, device=dev)
-            for t, off in zip(tensors, offs):
-                flat[off:off + t.numel()].copy_(t.data.reshape(-1))
-                t.data = flat[off:off + t.numel()].view(t.shape)
-            return flat, offs
-        self.flat, self.offsets = flatten(params)
-        self.params = params
-        self.flat_grad = torch.zeros_like(self.flat)
-        self.grad_views = [self.flat_grad[off:off + p.numel()].view(p.shape) for p, off in zip(params, self.offsets)]
-        self.off_of = {id(p): off for p, off in zip(params, self.offsets)}
+        self.bind_params(dev)
         # running statistics of both networks in flat buffers of their own
         bn_pairs = [(r, t) for r, t, _, _ in self.twin.pairs if isinstance(r, nn.BatchNorm2d)]
         self.rbufs = [b for r, _ in bn_pairs for b in (r.running_mean, r.running_var)]
         tbufs = [b for _, t in bn_pairs for b in (t.running_mean, t.running_var)]
-        self.stat, self.boffs = flatten(self.rbufs)
-        self.tstat, tboffs = flatten(tbufs)
+        self.stat, self.boffs = flatten(self.rbufs, dev)
+        self.tstat, tboffs = flatten(tbufs, dev)
         in_ = self.inner
         from .._lib import CxChanMapDesc
         pd, sd = [], []
@@ -1296,7 +1129,7 @@ class _PaddedEngine:
             arr = (CxChanMapDesc * len(descs))(*descs)
             return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev), len(descs)
         self.ptab, self.stab = table(pd), table(sd)
-        self.device, self.n_classes = dev, m.classifier.out_features
+        self.n_classes = self.model.classifier.out_features
 
     def _map(self, real, padded, tab, direction, accumulate=0):
         check(lib().cx_chan_map_table(ptr(real), ptr(padded), ptr(tab[0]), tab[1], direction, accumulate, stream_ptr()), "cx_chan_map_table")
@@ -1339,7 +1172,7 @@ class _PaddedEngine:
 
 
 # --------------------------------------------------------------------------------------------- module
-class DenseNet(nn.Module):
+class DenseNet(FusedNet):
     """Signature of /root/reference/models/attn_aug_conv.py:452-453 (torchvision DenseNet + attn_params)."""
 
     def __init__(self, growth_rate=32, block_config=(6, 12, 24, 16), num_init_features=64, bn_size=4, drop_rate=0,
@@ -1389,8 +1222,6 @@ class DenseNet(nn.Module):
                 nn.init.constant_(mod.bias, 0)
             elif isinstance(mod, nn.Linear):
                 nn.init.constant_(mod.bias, 0)
-        self._nbt_pending = 0
-        self._engine = None
 
     # the engine is rebuilt lazily (the classifier may be replaced after construction, chexpert.py:464)
     def _eng(self):
@@ -1398,69 +1229,15 @@ class DenseNet(nn.Module):
         if padded and len(self.block_config) == 4:
             raise NotImplementedError("ImageNet-stem DenseNets need growth and stem widths that are multiples of 8")
         for mod in self.modules():
-            why = mod.unsupported(branch_aligned=not padded) if isinstance(mod, AAConv2d) else ""
-            if why:
-                raise NotImplementedError("AAConv2d(dk=%d, dv=%d, nh=%d, relative=%s): %s (the HIP attention kernels cover dk/nh and "
-                                          "dv/nh = 1 .. 64 with dv <= 104)" % (mod.dk, mod.dv, mod.nh, mod.relative, why))
+            if isinstance(mod, AAConv2d):
+                mod.check_supported(branch_aligned=not padded)
         if self._engine is None or self._engine.c_final != self.classifier.in_features or \
                 self._engine.dtype != getattr(self, "_storage_dtype", torch.bfloat16):
             object.__setattr__(self, "_engine", _PaddedEngine(self) if padded else _Engine(self))
         return self._engine
 
-    def storage_dtype(self, dtype):
-        """Storage type of the activations inside the fused schedule: torch.bfloat16 (default: bf16 tensors, fp32 accumulation
-        and statistics) or torch.float32 -- the parity mode of north_star ("1e-3 fp32"): the same schedule on fp32 tensors with
-        the exact f32 MFMA (csrc/conv_f32.hip).  Parameters are fp32 masters either way.  Returns self."""
-        dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}.get(dtype, dtype)
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError("storage dtype must be bf16 or fp32")
-        object.__setattr__(self, "_storage_dtype", dtype)
-        return self
-
-    def _flush_nbt(self):
-        if self._nbt_pending:
-            for mod in self.modules():
-                if isinstance(mod, nn.BatchNorm2d) and mod.num_batches_tracked is not None:
-                    mod.num_batches_tracked += self._nbt_pending
-            self._nbt_pending = 0
-
-    def state_dict(self, *args, **kwargs):
-        self._flush_nbt()
-        return super().state_dict(*args, **kwargs)
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("chexpert_amd.DenseNet runs on the GPU only (hand-written HIP kernels); there is no CPU "
-                               "fallback -- move the model and the input to cuda")
-        eng = self._eng()
-        if self.training and wants_autograd(self, x):
-            return _Fn.apply(x, self.classifier.weight, self)
-        if not self.training:
-            from ..gradcam import hooked_eval_forward, hooks_registered
-            if hooks_registered(self):                     # Grad-CAM hook protocol of the reference (chexpert.py:271-272)
-                return hooked_eval_forward(self, x)
-        ws = eng.forward(x, self.training)
-        out = ws.logits.clone()
-        eng.release(ws)
-        return out
-
-    # fused training step helpers (bench / trainer fast path; same arithmetic as chexpert.py:159-163)
-    def forward_backward(self, x, target, input_grad=None):
-        """logits = model(x); loss = BCEWithLogits(logits, target).sum(1).mean(0); loss.backward().
-        Returns (loss, logits) as device tensors without a host sync.  input_grad: None, or a preallocated fp32 (B,3,H,W) tensor that
-        also receives d loss / d x (what x.grad would hold), still without a host sync."""
-        eng = self._eng()
-        if input_grad is not None:
-            check_input_grad(input_grad, x)
-        ws = eng.forward(x, self.training)
-        B, n = ws.logits.shape
-        loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
-        ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
-        eng.backward(ws, dl, dx=input_grad)
-        logits = ws.logits.clone()
-        eng.release(ws)
-        return loss, logits
+    def _anchor(self):
+        return self.classifier.weight
 
 
 def densenet121(pretrained=False, **kwargs):

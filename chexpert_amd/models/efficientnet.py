@@ -15,19 +15,16 @@ DropConnect (efficientnet.py:44-51, :100-101) and the classifier Dropout (:169-1
 per-element keep masks drawn on the GPU by `cx_dropout_mask_dev` from (model.drop_seed, device-side count of training forwards, block) -- reproducible and
 independent of torch's RNG; the parity tests feed the drawn masks (`engine.last_masks`) to the oracle.
 """
-import contextlib
 import math
 import os
-from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import _lib as L
 from .. import ops
-from .._lib import CxPackDesc, check, lib, ptr, stream_ptr
-from ._autograd import check_input_grad, input_grad_buffer, params_untouched, wants_autograd
+from .._lib import check, lib, ptr, stream_ptr
+from ._fused import FusedEngine, FusedNet, _BN
 from .densenet import BatchNorm2dParams, Conv2dParams, PoolMarker, _FusedOnly
 
 SCALING_PARAMS = {  # width, depth, resolution, dropout (efficientnet.py:13-21)
@@ -89,25 +86,6 @@ def same_pad(h_in, k, stride):
     return math.ceil(max((h_out - 1) * stride - h_in + (k - 1) + 1, 0) / 2)
 
 
-class _BN:
-    def __init__(self, V, C, fz, bz):
-        self.C = C
-        self.sum, self.sq = fz.take(C), fz.take(C)
-        self.S1, self.S2 = bz.take(C), bz.take(C)
-        self.sc, self.sh, self.mean, self.rstd = (V.take(C) for _ in range(4))
-        self.pa, self.pb, self.pc = (V.take(C) for _ in range(3))
-
-
-class _Region:
-    def __init__(self, base=0):
-        self.n = base
-
-    def take(self, n):
-        off = self.n
-        self.n += (n + 3) // 4 * 4
-        return (off, n)
-
-
 class _LibF32:
     """The C ABI with the `_f32` twin of an entry point where one exists (the fp32 storage mode)."""
 
@@ -118,108 +96,39 @@ class _LibF32:
         return getattr(self._l, name + "_f32", None) or getattr(self._l, name)
 
 
-class _Engine:
+class _Engine(FusedEngine):
+    # (fp32 storage: generic f32-MFMA convolutions, the storage-typed depthwise / squeeze-excite / Swish kernels of csrc/effnet.hip,
+    # no tiled fast paths; deterministic mode: one owner per squeeze-excite sum)
     def __init__(self, model):
-        self.model = model
-        # activation storage type: bf16, or fp32 = north_star's "1e-3 fp32" parity mode (generic f32-MFMA convolutions, the
-        # storage-typed depthwise / squeeze-excite / Swish kernels of csrc/effnet.hip; no tiled fast paths)
-        self.dtype = getattr(model, "_storage_dtype", torch.bfloat16)
-        # deterministic statistics and weight gradients (statistic rows summed in row order, slab sums, one owner per squeeze-excite
-        # sum): two steps on the same batch give the same bits; CHEXPERT_DET=0 keeps the fp32 atomics
-
-        self.det = os.environ.get("CHEXPERT_DET", "1") != "0"
-        self.flat = None
-        self.device = None
-        self.pool = {}
-        self.reducer = None
+        super().__init__(model)
         self.mb = [b for rep in model.blocks for b in rep]
         self.mb_names = ["blocks.%d.%d" % (si, bi) for si, rep in enumerate(model.blocks) for bi, _ in enumerate(rep)]
         self.last_masks = {}         # name -> mask / keep of the most recent train-mode forward (tests, reproducibility)
         self.bns = [model.stem[1]] + [m for b in self.mb for m in b if isinstance(m, nn.BatchNorm2d)] + [model.head[1]]
-        tmp = [_Region(0) for _ in range(3)]
-        for bn in self.bns:
-            _BN(tmp[2], bn.num_features, tmp[0], tmp[1])
-        nf, nb = tmp[0].n, tmp[1].n
-        self.fz, self.bz, self.rest = _Region(0), _Region(nf), _Region(nf + nb)
-        self.bn = {id(bn): _BN(self.rest, bn.num_features, self.fz, self.bz) for bn in self.bns}
-        self.fwd_zero, self.bwd_zero = (0, nf), (nf, nb)
-        cmax = max(bn.num_features for bn in self.bns)
-        self.ones = self.rest.take(cmax)
-        self.vec_size = self.rest.n
+        self.bn, rest, self.fwd_zero, self.bwd_zero = _BN.plan(self.bns)
+        self.ones = rest.take(max(bn.num_features for bn in self.bns))
+        self.vec_size = rest.n
 
     # ---- binding
     def bind(self, dev):
-        m = self.model
-        params = [p for _, p in m.named_parameters()]
-        ok = (self.flat is not None and self.device == dev and len(params) == len(self.offsets)
-              and all(p.data_ptr() == self.flat.data_ptr() + 4 * off for p, off in zip(params, self.offsets)))
-        if ok:
+        if self.bound(dev):
             return
-        offs, total = [], 0
-        for p in params:
-            offs.append(total)
-            total += (p.numel() + 3) // 4 * 4
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        for p, off in zip(params, offs):
-            flat[off:off + p.numel()].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + p.numel()].view(p.shape)
-        for b in m.buffers():
-            if b.device != dev:
-                raise RuntimeError("module buffers are on %s, input on %s -- call model.to(device)" % (b.device, dev))
-        self.flat, self.offsets, self.params = flat, offs, params
-        self.flat_grad = torch.zeros_like(flat)
-        self.grad_views = [self.flat_grad[off:off + p.numel()].view(p.shape) for p, off in zip(params, offs)]
-        self.off_of = {id(p): off for p, off in zip(params, offs)}
-        self.device = dev
+        m = self.model
+        self.bind_params(dev)
         self.n_classes = m.head[6].out_features
-        self.pool = {}
-        descs, cur = [], 0
-        self.wf, self.wb = {}, {}
+        # (the 3-channel stem is padded to 8 input channels and packed by _pack_stem8)
+        self.plan_packing([mod for b in self.mb + [m.head] for mod in b if isinstance(mod, nn.Conv2d) and mod.groups == 1],
+                          stem8=m.stem[0])
 
-        def add(conv, transpose=False):
-            nonlocal cur
-            O, I, kh, kw = conv.weight.shape
-            descs.append(CxPackDesc(self.off_of[id(conv.weight)], cur, O, I, kh, kw, int(transpose), 0))
-            off, n = cur, O * I * kh * kw
-            cur += (n + 7) // 8 * 8
-            return (off, n)
-        for b in self.mb + [m.head]:
-            for mod in b:
-                if isinstance(mod, nn.Conv2d) and mod.groups == 1:
-                    self.wf[id(mod)] = add(mod)
-                    self.wb[id(mod)] = add(mod, transpose=True)
-        self.stem_off = cur
-        cur += 9 * m.stem[0].out_channels * 8
-        self.packed = torch.empty(cur, dtype=self.dtype, device=dev)
-        arr = (CxPackDesc * len(descs))(*descs)
-        self.desc_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        self.n_desc = len(descs)
-
-    def pack(self):
-        ops.pack_weights_table(self.flat, self.packed, self.desc_dev, self.n_desc)
+    def _pack_stem8(self):
         w8 = F.pad(self.model.stem[0].weight.detach(), (0, 0, 0, 0, 0, 5)).contiguous()       # (O,3,3,3) -> (O,8,3,3)
         if self.dtype == torch.float32:         # [tap][O][I] fp32: a 3 K-element layout copy
             self.packed[self.stem_off:self.stem_off + w8.numel()].copy_(w8.permute(2, 3, 0, 1).reshape(-1))
         else:
             ops.pack_weights(w8, out=self.packed[self.stem_off:])
 
-    def w_fwd(self, conv):
-        off, n = self.wf[id(conv)]
-        return self.packed[off:off + n]
-
-    def w_bwd(self, conv):
-        off, n = self.wb[id(conv)]
-        return self.packed[off:off + n]
-
-    def G(self, p):
-        off = self.off_of[id(p)]
-        return self.flat_grad[off:off + p.numel()]
-
     # ---- workspace
-    def acquire(self, B, H, W):
-        lst = self.pool.setdefault((B, H, W), [])
-        if lst:
-            return lst.pop()
+    def _new_workspace(self, B, H, W):
         dev, bf, f32 = self.device, self.dtype, torch.float32
         e = lambda *s, dtype=bf: torch.empty(*s, dtype=dtype, device=dev)
         m = self.model
@@ -255,16 +164,6 @@ class _Engine:
         ws.bwd = None
         return ws
 
-    def release(self, ws):
-        lst = self.pool.setdefault(ws.key, [])
-        if len(lst) < 2:
-            lst.append(ws)
-
-    @staticmethod
-    def _v(ws, slot, n=None):
-        off, m = slot
-        return ws.vec[off:off + (m if n is None else n)]
-
     SLAB = 1 << 22               # floats per half of the statistic-row scratch
     ROWS = 2048                  # most statistic rows an element-wise / depthwise producer writes
 
@@ -299,7 +198,7 @@ class _Engine:
             raise RuntimeError("expected a (B,3,H,W) float input or a (B,1,H,W) uint8 image")
         B, _, H, W = x.shape
         self.bind(x.device)
-        self.pack()
+        self.pack(train)
         ws = self.acquire(B, H, W)
         self.last_masks = {}
         self.n_forward = getattr(self, "n_forward", 0) + 1
@@ -426,20 +325,8 @@ class _Engine:
         bw["gdc"] = torch.empty(max(t["out"].numel() for t in ws.blk), dtype=bf, device=dev)     # DropConnect-masked gradient
         ws.bwd = bw
 
-    def backward(self, ws, dlogits, dx=None):
-        """dx: None, or an fp32 (B,3,H,W) buffer that also receives the input gradient (cx_stem_input_grad)"""
-        ops.set_det_wgrad(self.det)            # reproducible weight-gradient sums with the deterministic statistics
-        deferred = self.det and ops.wgrad_defer_begin(self.device)
-        try:
-            self._backward(ws, dlogits, dx)
-            if deferred:
-                ops.wgrad_defer_flush(self.device)
-        finally:
-            if deferred:
-                ops.wgrad_defer_abort(self.device)
-
-    def _backward(self, ws, dlogits, dx=None):
-        m, v, G, lb = self.model, self._v, self.G, (_LibF32(lib()) if self.dtype == torch.float32 else lib())
+    def _backward(self, ws, dlogits, dx, done):
+        m, v, G, lb = self.model, self._v, self.grad_of, (_LibF32(lib()) if self.dtype == torch.float32 else lib())
         det = self.det
         B = ws.B
         sp = stream_ptr()
@@ -448,15 +335,6 @@ class _Engine:
         if not det:
             z0, zn = self.bwd_zero
             ws.vec[z0:z0 + zn].zero_()
-        fresh = any(p.grad is None for p in self.params)
-        if fresh:
-            self.flat_grad.zero_()
-        elif not all(p.grad.data_ptr() == gv.data_ptr() for p, gv in zip(self.params, self.grad_views)):
-            raise RuntimeError("parameter .grad tensors were replaced; call zero_grad(set_to_none=True) first")
-        red = self.reducer
-        if red is not None:
-            red.begin()
-        done = (lambda p: red.ready(self.off_of[id(p)])) if red is not None else (lambda p: None)
 
         def bn_bwd(S, bn, count):
             """BatchNorm backward coefficients of `bn` from the sums its producer has just written (deterministic mode: the rows of
@@ -577,46 +455,9 @@ class _Engine:
         G(m.stem[0].weight).view(c0, 3, 3, 3).add_(dw8[:, :3])
         if dx is not None:
             ops.stem_input_grad(dzs, ws.ys, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.stem[0].weight, dx, stride=2, pad=ws.stem_pad)
-        if red is not None:
-            red.finish()
-        if fresh:
-            for p, gv in zip(self.params, self.grad_views):
-                p.grad = gv
-
-    def enable_data_parallel(self, bucket_bytes=16 << 20, group=None):
-        from ..parallel import GradReducer
-        if self.flat_grad is None:
-            raise RuntimeError("bind the engine first (run one forward)")
-        self.reducer = GradReducer(self.flat_grad, bucket_bytes, group)
-        # the deferred weight-gradient slab sums (ops.wgrad_defer_*) run before each bucket leaves, so that the bucket is final
-        self.reducer.pre_launch = lambda: ops.wgrad_defer_flush(self.device, keep=True)
 
 
-class _Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, anchor, model):
-        if not model.training:
-            raise NotImplementedError("autograd through the fused EfficientNet needs train() mode")
-        ws = model._eng().forward(x, True)
-        ctx.model, ctx.ws, ctx.x_meta = model, ws, (tuple(x.shape), x.dtype, x.device)
-        return ws.logits.clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        eng, ws = ctx.model._eng(), ctx.ws
-        if ws is None:
-            raise RuntimeError("backward through the fused EfficientNet can only run once per forward")
-        shape, dtype, dev = ctx.x_meta
-        dx = input_grad_buffer(shape, dev) if ctx.needs_input_grad[0] else None
-        frozen = not any(p.requires_grad for p in ctx.model.parameters())
-        with params_untouched(eng.params, eng.flat_grad) if frozen else contextlib.nullcontext():
-            eng.backward(ws, dlogits.contiguous().float(), dx=dx)
-        eng.release(ws)
-        ctx.ws = None
-        return (dx.to(dtype) if dx is not None else None), None, None
-
-
-class EfficientNet(nn.Module):
+class EfficientNet(FusedNet):
     def __init__(self, model_name, n_classes):
         super().__init__()
         assert model_name in SCALING_PARAMS.keys(), "Invalid model name."
@@ -640,8 +481,6 @@ class EfficientNet(nn.Module):
             if isinstance(mod, nn.Linear):
                 nn.init.kaiming_uniform_(mod.weight, a=math.sqrt(5), mode="fan_in", nonlinearity="linear")
                 nn.init.constant_(mod.bias, 0)
-        self._nbt_pending = 0
-        self._engine = None
         self.drop_seed = 0           # seed of the Dropout / DropConnect masks (with the forward counter and the block index)
 
     def _eng(self):
@@ -649,50 +488,8 @@ class EfficientNet(nn.Module):
             object.__setattr__(self, "_engine", _Engine(self))
         return self._engine
 
-    def storage_dtype(self, dtype):
-        """torch.bfloat16 (default) or torch.float32: the fp32 parity mode (same method as DenseNet.storage_dtype)."""
-        dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}.get(dtype, dtype)
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError("storage dtype must be bf16 or fp32")
-        object.__setattr__(self, "_storage_dtype", dtype)
-        return self
-
-    def state_dict(self, *args, **kwargs):
-        if self._nbt_pending:
-            for mod in self.modules():
-                if isinstance(mod, nn.BatchNorm2d):
-                    mod.num_batches_tracked += self._nbt_pending
-            self._nbt_pending = 0
-        return super().state_dict(*args, **kwargs)
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("chexpert_amd EfficientNet runs on the GPU only (hand-written HIP kernels); there is no CPU fallback")
-        eng = self._eng()
-        if self.training and wants_autograd(self, x):
-            return _Fn.apply(x, self.head[6].weight, self)
-        if not self.training:
-            from ..gradcam import hooked_eval_forward, hooks_registered
-            if hooks_registered(self):                     # Grad-CAM hook protocol of the reference (chexpert.py:271-272)
-                return hooked_eval_forward(self, x)
-        ws = eng.forward(x, self.training)
-        out = ws.logits.clone()
-        eng.release(ws)
-        return out
-
-    def forward_backward(self, x, target, input_grad=None):
-        eng = self._eng()
-        if input_grad is not None:
-            check_input_grad(input_grad, x)
-        ws = eng.forward(x, self.training)
-        B, n = ws.logits.shape
-        loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
-        ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
-        eng.backward(ws, dl, dx=input_grad)
-        logits = ws.logits.clone()
-        eng.release(ws)
-        return loss, logits
+    def _anchor(self):
+        return self.head[6].weight
 
 
 def construct_model(model_name, n_classes):

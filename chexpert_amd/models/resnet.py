@@ -13,16 +13,15 @@ BatchNorm outputs are never stored; backward uses the two-tensor affine form of 
 prologues of the input- and weight-gradient kernels, and the input gradient of the strided convs is the
 same implicit GEMM walking only the source positions that lie on the stride grid (`tstride`).
 """
-import contextlib
-from collections import OrderedDict
+import os
 
 import torch
 import torch.nn as nn
 
 from .. import ops
-from .._lib import CxPackDesc, check, lib, ptr, stream_ptr
-from ._autograd import check_input_grad, input_grad_buffer, params_untouched, wants_autograd
-from .densenet import AAConv2d, BatchNorm2dParams, Conv2dParams, PoolMarker, ReLUMarker, _Vec
+from .._lib import check, lib, ptr, stream_ptr
+from ._fused import FusedEngine, FusedNet, _BN
+from .densenet import AAConv2d, BatchNorm2dParams, Conv2dParams, PoolMarker, ReLUMarker
 
 
 class Bottleneck(nn.Module):
@@ -94,55 +93,25 @@ class BasicBlock(nn.Module):
         raise RuntimeError("chexpert_amd: call the parent ResNet / WideResNet (fused HIP schedule)")
 
 
-class _BN:
-    """Vector slots of one BatchNorm."""
-
-    def __init__(self, V, C, fz, bz):
-        self.C = C
-        self.sum, self.sq = fz.take(C), fz.take(C)                    # zeroed every forward
-        self.S1, self.S2 = bz.take(C), bz.take(C)                     # zeroed every backward
-        self.sc, self.sh, self.mean, self.rstd = (V.take(C) for _ in range(4))
-        self.pa, self.pb, self.pc = (V.take(C) for _ in range(3))
-
-
-class _Region(_Vec):
-    def __init__(self, base=0):
-        super().__init__()
-        self.n = base
-
-
-class _Engine:
+class _Engine(FusedEngine):
     SLAB = 1 << 22               # floats per statistic-row scratch (rows x channels of the largest producer)
     EW_ROWS = 2048
 
     def __init__(self, model):
-        import os
-        self.model = model
-        # deterministic statistics (per-workgroup rows summed in row order, as in the DenseNet engine); the attention-augmented
-        # bottlenecks feed bn2 from two kernels (conv branch + out-projection) and stay on the atomic path
-        # (attention-augmented blocks feed one BatchNorm from two kernels: their statistic rows are reduced per channel range,
-        # _aa_fwd_stats; the two input-gradient branches stack their rows, _stacked)
-        self.det = os.environ.get("CHEXPERT_DET", "1") != "0"
+        super().__init__(model)
+        # (deterministic statistics: attention-augmented blocks feed one BatchNorm from two kernels: their statistic rows are reduced
+        # per channel range, _aa_fwd; the two input-gradient branches stack their rows, _stacked)
         self.join_fuse = os.environ.get("CHEXPERT_JOIN_FUSE", "1") != "0"      # residual-join backward in the conv1 input gradient's epilogue
         # Bottleneck networks in bf16: the residual stream is kept as two planes (bf16 hi + int8 lo = 16 significant bits, common.h
         # cx_join2) and the forward join of an identity block runs in the prologue of the NEXT block's conv1 (CX_PRO_JOIN)
         self.stream_lo = os.environ.get("CHEXPERT_STREAM_LO", "1") != "0"
         self.fwd_join_fuse = os.environ.get("CHEXPERT_FWD_JOIN_FUSE", "1") != "0"
-        # activation storage type: bf16, or fp32 = the parity mode of north_star ("1e-3 fp32"): the same schedule on fp32 tensors
-        # through the generic f32-MFMA convolutions (csrc/conv_f32.hip) and the templated element-wise kernels
-        self.dtype = getattr(model, "_storage_dtype", torch.bfloat16)
+        # fp32 storage: the same schedule on fp32 tensors through the generic f32-MFMA convolutions (csrc/conv_f32.hip) and the
+        # templated element-wise kernels
         if self.dtype != torch.bfloat16 and isinstance(model, WideResNet):
             raise NotImplementedError("the fp32 storage mode covers the ImageNet-stem ResNets (resnet152 / aaresnet152 of "
                                       "chexpert.py:482-494); the 3-channel CIFAR stem is packed for bf16")
-        self.flat = None
-        self.device = None
-        self.pool = {}
-        self.reducer = None
-        # geometry: list of (module, inplanes, planes, stride, has_downsample)
-        self.blocks = []
-        for L in model._stages():
-            for blk in L:
-                self.blocks.append(blk)
+        self.blocks = [blk for L in model._stages() for blk in L]
         self.basic = model.block is BasicBlock                 # two 3x3 convolutions per block (attn_aug_conv.py:107-156)
         self.two_plane = self.stream_lo and not (model.block is BasicBlock) and self.dtype == torch.bfloat16
         # Where the stream keeps its lo plane: on every output that feeds an identity join (round 5; 46 of resnet152's 50 joins --
@@ -165,25 +134,12 @@ class _Engine:
         self.fuse_fwd = [self.two_plane and self.fwd_join_fuse and long_id[i] and i + 1 < n for i in range(n)]
         self.cifar = isinstance(model, WideResNet)              # 3x3 stride-1 stem, no max-pool, three stages (:311-404)
         # vector plan: [fwd-zero region | bwd-zero region | rest]
-        nfz = sum(2 * bn.num_features for bn in self._all_bns()) + 64
-        nbz = nfz
-        self.fz, self.bz, self.rest = _Region(0), _Region(0), _Region(0)
-        fz_tmp, bz_tmp, rest_tmp = _Region(0), _Region(0), _Region(0)
-        # two-pass: first sizes, then offsets
-        self.bn = {}
-        for bn in self._all_bns():
-            self.bn[id(bn)] = _BN(rest_tmp, bn.num_features, fz_tmp, bz_tmp)
-        nf, nb = fz_tmp.n, bz_tmp.n
-        self.fz, self.bz, self.rest = _Region(0), _Region(nf), _Region(nf + nb)
-        self.bn = {}
-        for bn in self._all_bns():
-            self.bn[id(bn)] = _BN(self.rest, bn.num_features, self.fz, self.bz)
-        self.fwd_zero, self.bwd_zero = (0, nf), (nf, nb)
+        self.bn, rest, self.fwd_zero, self.bwd_zero = _BN.plan(list(self._all_bns()))
         cmax = 2048
-        self.join = [[self.rest.take(self._last_bn(b).num_features) for _ in range(3)] for b in self.blocks]
-        self.ones, self.zeros = self.rest.take(cmax), self.rest.take(cmax)
-        self.scratch = [self.rest.take(cmax) for _ in range(2)]
-        self.vec_size = self.rest.n
+        self.join = [[rest.take(self._last_bn(b).num_features) for _ in range(3)] for b in self.blocks]
+        self.ones, self.zeros = rest.take(cmax), rest.take(cmax)
+        self.scratch = [rest.take(cmax) for _ in range(2)]
+        self.vec_size = rest.n
 
     @staticmethod
     def _cin(b):
@@ -205,101 +161,33 @@ class _Engine:
             if b.downsample is not None:
                 yield b.downsample[1]
 
-    # ---- binding / packing (same scheme as the DenseNet engine)
+    # ---- binding / packing
     def bind(self, dev):
+        if self.bound(dev):
+            return
         m = self.model
-        params = [p for _, p in m.named_parameters()]
-        ok = (self.flat is not None and self.device == dev and len(params) == len(self.offsets)
-              and all(p.data_ptr() == self.flat.data_ptr() + 4 * off for p, off in zip(params, self.offsets)))
-        if ok:
-            return
-        offs, total = [], 0
-        for p in params:
-            if p.dtype != torch.float32:
-                raise RuntimeError("parameters must be fp32 masters")
-            offs.append(total)
-            total += (p.numel() + 3) // 4 * 4
-        flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        for p, off in zip(params, offs):
-            flat[off:off + p.numel()].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + p.numel()].view(p.shape)
-        for b in m.buffers():
-            if b.device != dev:
-                raise RuntimeError("module buffers are on %s, input on %s -- call model.to(device)" % (b.device, dev))
-        self.flat, self.offsets, self.params = flat, offs, params
-        self.flat_grad = torch.zeros_like(flat)
-        self.grad_views = [self.flat_grad[off:off + p.numel()].view(p.shape) for p, off in zip(params, offs)]
-        self.off_of = {id(p): off for p, off in zip(params, offs)}
-        self.device = dev
+        c_last = self._last_bn(self.blocks[-1]).num_features
+        if m.fc.in_features != c_last:
+            raise RuntimeError("fc.in_features must match the last stage (%d channels)" % c_last)
+        self.bind_params(dev)
         self.n_classes = m.fc.out_features
-        self.pool = {}
-        descs, cur = [], 0
-        self.wf, self.wb = {}, {}
-
-        def add(conv, transpose=False, stem=False):
-            nonlocal cur
-            O, I, kh, kw = conv.weight.shape
-            gr = getattr(conv, "groups", 1)
-            if gr > 1:
-                # grouped convolution: the filters of group g are rows [g O/G, (g+1) O/G) of the (O, I/G, kh, kw) weight -- contiguous --
-                # and are packed as a convolution of their own; the entry is the list of the groups' (offset, size)
-                og, n = O // gr, (O // gr) * I * kh * kw
-                ent = []
-                for g_ in range(gr):
-                    descs.append(CxPackDesc(self.off_of[id(conv.weight)] + g_ * n, cur, og, I, kh, kw, int(transpose), 0))
-                    ent.append((cur, n))
-                    cur += (n + 7) // 8 * 8
-                return ent
-            n = ((49 * O * 4) if self.dtype == torch.float32 else 7 * O * 32) if stem else O * I * kh * kw
-            descs.append(CxPackDesc(self.off_of[id(conv.weight)], cur, O, I, kh, kw, int(transpose), int(stem)))
-            off = cur
-            cur += (n + 7) // 8 * 8
-            return (off, n)
-        if self.cifar:                          # 3 input channels padded to 8 for the implicit GEMM (packed in pack())
-            self.stem_off = cur
-            cur += 9 * m.conv1.out_channels * 8
+        # (the CIFAR stem's 3 input channels are padded to 8 for the implicit GEMM: packed by _pack_stem8)
+        convs = [mod for mod in m.modules() if isinstance(mod, nn.Conv2d) and mod is not m.conv1]
+        if self.cifar:
+            self.plan_packing(convs, stem8=m.conv1)
         else:
-            self.wf[id(m.conv1)] = add(m.conv1, stem=True)
-        for mod in m.modules():
-            if isinstance(mod, nn.Conv2d) and mod is not m.conv1:
-                self.wf[id(mod)] = add(mod)
-                self.wb[id(mod)] = add(mod, transpose=True)
-        self.packed = torch.empty(cur, dtype=self.dtype, device=dev)
-        arr = (CxPackDesc * len(descs))(*descs)
-        self.desc_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        self.n_desc = len(descs)
-        self.packed_version = None
+            self.plan_packing(convs, stem=m.conv1, stem_layout=True)
 
-    def pack(self, train):
-        ver = None if train else sum(p._version for p in self.params)
-        if ver is not None and ver == self.packed_version:
-            return
-        ops.pack_weights_table(self.flat, self.packed, self.desc_dev, self.n_desc)
+    def _pack_stem8(self):
         if self.cifar:
             w8 = torch.nn.functional.pad(self.model.conv1.weight.detach(), (0, 0, 0, 0, 0, 5)).contiguous()   # (O,3,3,3) -> (O,8,3,3)
             ops.pack_weights(w8, out=self.packed[self.stem_off:])
-        self.packed_version = ver
-
-    def w_fwd(self, conv, group=None):
-        off, n = self.wf[id(conv)] if group is None else self.wf[id(conv)][group]
-        return self.packed[off:off + n]
-
-    def w_bwd(self, conv, group=None):
-        off, n = self.wb[id(conv)] if group is None else self.wb[id(conv)][group]
-        return self.packed[off:off + n]
-
-    def G(self, p):
-        off = self.off_of[id(p)]
-        return self.flat_grad[off:off + p.numel()]
 
     # ---- workspace
     class WS:
         pass
 
-    def acquire(self, B, H, W):
-        lst = self.pool.setdefault((B, H, W), [])
-        if lst:
-            return lst.pop()
+    def _new_workspace(self, B, H, W):
         dev, bf = self.device, self.dtype
         e = lambda *s, dtype=bf: torch.empty(*s, dtype=dtype, device=dev)
         ws = _Engine.WS()
@@ -349,16 +237,6 @@ class _Engine:
         ws.vec[o:o + n].fill_(1.0)
         ws.bwd = None
         return ws
-
-    def release(self, ws):
-        lst = self.pool.setdefault(ws.key, [])
-        if len(lst) < 2:
-            lst.append(ws)
-
-    @staticmethod
-    def _v(ws, slot, n=None):
-        off, m = slot
-        return ws.vec[off:off + (m if n is None else n)]
 
     def _sp(self, ws, S, train):
         """Statistics arguments of a producer of BatchNorm S's input."""
@@ -576,10 +454,6 @@ class _Engine:
         bw = {}
         # one gradient buffer per block OUTPUT shape change (identity blocks accumulate in place)
         bw["g"] = [None] * len(self.blocks)
-        for bi, b in enumerate(self.blocks):
-            t = ws.blk[bi]
-            if b.downsample is not None or bi == len(self.blocks) - 1:
-                pass
         shapes = {}
         for bi, b in enumerate(self.blocks):
             sh = tuple(ws.blk[bi]["out"].shape)
@@ -597,36 +471,16 @@ class _Engine:
             bw["dQKV"] = torch.empty(max(t["QKV"].numel() for t in aa_t), dtype=bf, device=dev)
         ws.bwd = bw
 
-    def backward(self, ws, dlogits, dx=None):
-        """dx: None, or an fp32 (B,3,H,W) buffer that also receives the input gradient (cx_stem_input_grad)"""
-        ops.set_det_wgrad(self.det)            # reproducible weight-gradient sums with the deterministic statistics
-        # the ordered slab sums run as one table-driven launch at the end of the pass (ops.wgrad_defer_*); a data-parallel run
-        # flushes them before each gradient bucket leaves (GradReducer.pre_launch); the CIFAR stem keeps immediate sums (read back at once)
-        deferred = self.det and not self.cifar and ops.wgrad_defer_begin(self.device)
-        try:
-            self._backward(ws, dlogits, dx)
-            if deferred:
-                ops.wgrad_defer_flush(self.device)
-        finally:
-            if deferred:
-                ops.wgrad_defer_abort(self.device)
+    def _defer_wgrad(self):
+        return self.det and not self.cifar          # the CIFAR stem keeps immediate sums (read back at once)
 
-    def _backward(self, ws, dlogits, dx=None):
-        m, v, G = self.model, self._v, self.G
+    def _backward(self, ws, dlogits, dx, done):
+        m, v, G = self.model, self._v, self.grad_of
         B = ws.B
         self._alloc_bwd(ws)
         bw = ws.bwd
         z0, zn = self.bwd_zero
         ws.vec[z0:z0 + zn].zero_()
-        fresh = any(p.grad is None for p in self.params)
-        if fresh:
-            self.flat_grad.zero_()
-        elif not all(p.grad.data_ptr() == gv.data_ptr() for p, gv in zip(self.params, self.grad_views)):
-            raise RuntimeError("parameter .grad tensors were replaced; call zero_grad(set_to_none=True) first")
-        red = self.reducer
-        if red is not None:
-            red.begin()
-        done = (lambda p: red.ready(self.off_of[id(p)])) if red is not None else (lambda p: None)
         det = self.det
         ew = lambda C: min(self.EW_ROWS, self.SLAB // C)
 
@@ -806,16 +660,11 @@ class _Engine:
                            ga=v(ws, S0.pa), gb=v(ws, S0.pb), gc=v(ws, S0.pc))
             if dx is not None:
                 ops.stem_input_grad(bw["dz0"], ws.c0, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.conv1.weight, dx, stride=2, pad=3)
-        if red is not None:
-            red.finish()
-        if fresh:
-            for p, gv in zip(self.params, self.grad_views):
-                p.grad = gv
 
     def _basic_backward(self, ws, bi, b, t, xin, msp, srows, ew, done):
         """Backward of one BasicBlock (attn_aug_conv.py:135-156), same conventions as the bottleneck path: the block's output
         gradient is masked in place by the join ReLU, BatchNorm backward rides in the two-tensor prologues of the consumers."""
-        v, G, bw, B, det = self._v, self.G, ws.bwd, ws.B, self.det
+        v, G, bw, B, det = self._v, self.grad_of, ws.bwd, ws.B, self.det
         s_, p_, cin = b.stride, b.bn1.num_features, self._cin(b)
         ho, wo = t["hout"]
         S1, S2 = self.bn[id(b.bn1)], self.bn[id(b.bn2)]
@@ -886,103 +735,8 @@ class _Engine:
                            gc=v(ws, Sd.pc))
         done(b.conv1.weight if not isinstance(b.conv1, AAConv2d) else b.conv1.first_param())
 
-    def enable_data_parallel(self, bucket_bytes=16 << 20, group=None):
-        from ..parallel import GradReducer
-        if self.flat_grad is None:
-            raise RuntimeError("bind the engine first (run one forward)")
-        self.reducer = GradReducer(self.flat_grad, bucket_bytes, group)
-        # the deferred weight-gradient slab sums (ops.wgrad_defer_*) run before each bucket leaves, so that the bucket is final
-        self.reducer.pre_launch = lambda: ops.wgrad_defer_flush(self.device, keep=True)
 
-
-class _Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, anchor, model):
-        if not model.training:
-            raise NotImplementedError("autograd through the fused ResNet needs train() mode")
-        ws = model._eng().forward(x, True)
-        ctx.model, ctx.ws, ctx.x_meta = model, ws, (tuple(x.shape), x.dtype, x.device)
-        return ws.logits.clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        eng, ws = ctx.model._eng(), ctx.ws
-        if ws is None:
-            raise RuntimeError("backward through the fused ResNet can only run once per forward")
-        shape, dtype, dev = ctx.x_meta
-        dx = input_grad_buffer(shape, dev) if ctx.needs_input_grad[0] else None
-        frozen = not any(p.requires_grad for p in ctx.model.parameters())
-        with params_untouched(eng.params, eng.flat_grad) if frozen else contextlib.nullcontext():
-            eng.backward(ws, dlogits.contiguous().float(), dx=dx)
-        eng.release(ws)
-        ctx.ws = None
-        return (dx.to(dtype) if dx is not None else None), None, None
-
-
-class _EngineNet(nn.Module):
-    """What the BasicBlock / Bottleneck ResNet and the WideResNet share: the fused engine behind forward / autograd."""
-
-    def _eng(self):
-        for mod in self.modules():
-            why = mod.unsupported() if isinstance(mod, AAConv2d) else ""
-            if why:
-                raise NotImplementedError("AAConv2d(dk=%d, dv=%d, nh=%d): %s (the HIP attention kernels cover dk/nh and dv/nh = 1 .. 64 "
-                                          "with dv <= 104)" % (mod.dk, mod.dv, mod.nh, why))
-        if self._engine is None or self._engine.dtype != getattr(self, "_storage_dtype", torch.bfloat16):
-            object.__setattr__(self, "_engine", _Engine(self))
-        return self._engine
-
-    def storage_dtype(self, dtype):
-        """Storage type of the activations inside the fused schedule: torch.bfloat16 (default) or torch.float32 -- the parity
-        mode of north_star ("1e-3 fp32"; same method as DenseNet.storage_dtype).  Parameters are fp32 masters either way."""
-        dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}.get(dtype, dtype)
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError("storage dtype must be bf16 or fp32")
-        object.__setattr__(self, "_storage_dtype", dtype)
-        return self
-
-    def state_dict(self, *args, **kwargs):
-        if self._nbt_pending:
-            for mod in self.modules():
-                if isinstance(mod, nn.BatchNorm2d):
-                    mod.num_batches_tracked += self._nbt_pending
-            self._nbt_pending = 0
-        return super().state_dict(*args, **kwargs)
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("chexpert_amd.ResNet runs on the GPU only (hand-written HIP kernels); there is no CPU fallback")
-        eng = self._eng()
-        if self.fc.in_features != self._stages()[-1][-1].bn1.num_features * self.block.expansion:
-            raise RuntimeError("fc.in_features must match the last stage (%d channels)"
-                               % (self._stages()[-1][-1].bn1.num_features * self.block.expansion))
-        if self.training and wants_autograd(self, x):
-            return _Fn.apply(x, self.fc.weight, self)
-        if not self.training:
-            from ..gradcam import hooked_eval_forward, hooks_registered
-            if hooks_registered(self):                     # Grad-CAM hook protocol of the reference (chexpert.py:271-272)
-                return hooked_eval_forward(self, x)
-        ws = eng.forward(x, self.training)
-        out = ws.logits.clone()
-        eng.release(ws)
-        return out
-
-    def forward_backward(self, x, target, input_grad=None):
-        eng = self._eng()
-        if input_grad is not None:
-            check_input_grad(input_grad, x)
-        ws = eng.forward(x, self.training)
-        B, n = ws.logits.shape
-        loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
-        ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
-        eng.backward(ws, dl, dx=input_grad)
-        logits = ws.logits.clone()
-        eng.release(ws)
-        return loss, logits
-
-
-class ResNet(_EngineNet):
+class ResNet(FusedNet):
     """Signature of /root/reference/models/attn_aug_conv.py:218-220."""
 
     def __init__(self, block, layers, num_classes=1000, zero_init_residual=False, groups=1, width_per_group=64,
@@ -1029,8 +783,17 @@ class ResNet(_EngineNet):
                     nn.init.constant_(mod.bn3.weight, 0)
                 elif isinstance(mod, BasicBlock):
                     nn.init.constant_(mod.bn2.weight, 0)
-        self._nbt_pending = 0
-        self._engine = None
+
+    def _eng(self):
+        for mod in self.modules():
+            if isinstance(mod, AAConv2d):
+                mod.check_supported()
+        if self._engine is None or self._engine.dtype != getattr(self, "_storage_dtype", torch.bfloat16):
+            object.__setattr__(self, "_engine", _Engine(self))
+        return self._engine
+
+    def _anchor(self):
+        return self.fc.weight
 
     def _make_layer(self, planes, blocks, stride, attn_params=None, dilate=False):
         block, e = self.block, self.block.expansion
@@ -1054,7 +817,7 @@ class ResNet(_EngineNet):
         return (self.layer1, self.layer2, self.layer3, self.layer4)
 
 
-class WideResNet(_EngineNet):
+class WideResNet(FusedNet):
     """Signature and parameters of /root/reference/models/attn_aug_conv.py:311-404 (WRN-d-k on CIFAR: 3x3 stem, three stages of
     BasicBlocks, AAConv2d in stages 2-3).  The network of the CIFAR harness (models/test_model.py), on the same HIP schedule as the
     BasicBlock ResNets (3x3 stem without max-pool); attention head sizes outside the kernels' set raise when the model is run."""
@@ -1090,10 +853,7 @@ class WideResNet(_EngineNet):
                 if isinstance(mod, BasicBlock):
                     nn.init.constant_(mod.bn2.weight, 0)
 
-        self._nbt_pending = 0
-        self._engine = None
-
-    _make_layer = ResNet._make_layer
+    _eng, _anchor, _make_layer = ResNet._eng, ResNet._anchor, ResNet._make_layer
 
     def _stages(self):
         return (self.layer1, self.layer2, self.layer3)

@@ -27,7 +27,7 @@ def _nets():
 
 @pytest.mark.parametrize("i", range(5))
 def test_frozen_model_with_a_requires_grad_input_routes_into_autograd(i):
-    from chexpert_amd.models._autograd import wants_autograd
+    from chexpert_amd.models._fused import wants_autograd
     model = _nets()[i].train()
     x = torch.zeros(2, 3, 32, 32)
     assert wants_autograd(model, x)                       # parameters require grad (as before)
@@ -42,14 +42,41 @@ def test_frozen_model_with_a_requires_grad_input_routes_into_autograd(i):
 
 def test_forward_routes_through_wants_autograd():
     import inspect
-    from chexpert_amd.models import DenseNet, ResNet, construct_model
-    for cls in (DenseNet, ResNet, type(construct_model("efficientnet-b0", 5)).__mro__[1]):
-        src = inspect.getsource(cls.forward)
-        assert "wants_autograd(self, x)" in src, cls
+    from chexpert_amd.models._fused import FusedNet
+    assert "wants_autograd(self, x)" in inspect.getsource(FusedNet.forward)
+    for net in _nets():                                   # one forward / forward_backward for every network
+        assert isinstance(net, FusedNet)
+        for name in ("forward", "forward_backward"):
+            assert getattr(type(net), name) is getattr(FusedNet, name), (type(net).__name__, name)
+
+
+@pytest.mark.parametrize("i", range(5))
+def test_bind_flattens_fp32_masters(i):
+    """eng.bind: every parameter becomes a view of the flat fp32 buffer at a 16-byte aligned offset and keeps its values, the
+    gradient views alias the flat gradient buffer, and a parameter that is not fp32 is refused."""
+    model = _nets()[i]
+    before = [p.detach().clone() for p in model.parameters()]
+    eng = model._eng()
+    eng.bind(torch.device("cpu"))
+    params = list(model.parameters())
+    assert len(params) == len(eng.grad_views) == len(before)
+    base, gbase = eng.flat.data_ptr(), eng.flat_grad.data_ptr()
+    for p, g, b in zip(params, eng.grad_views, before):
+        off = p.data_ptr() - base
+        assert p.untyped_storage().data_ptr() == eng.flat.untyped_storage().data_ptr() and p.dtype == torch.float32
+        assert 0 <= off and off % 16 == 0 and off // 4 + p.numel() <= eng.flat.numel()
+        assert torch.equal(p.detach(), b)
+        assert g.untyped_storage().data_ptr() == eng.flat_grad.untyped_storage().data_ptr()
+        assert g.shape == p.shape and g.data_ptr() - gbase == off
+    model = _nets()[i]
+    p = next(model.parameters())
+    p.data = p.data.to(torch.bfloat16)
+    with pytest.raises(RuntimeError, match="fp32"):
+        model._eng().bind(torch.device("cpu"))
 
 
 def test_params_untouched_restores_every_grad():
-    from chexpert_amd.models._autograd import params_untouched
+    from chexpert_amd.models._fused import params_untouched
     flat = torch.arange(6, dtype=torch.float32)
     a, b = torch.nn.Parameter(torch.zeros(2)), torch.nn.Parameter(torch.zeros(4))
     a.grad = flat[:2]                                      # a view of the flat buffer
@@ -61,7 +88,7 @@ def test_params_untouched_restores_every_grad():
 
 
 def test_input_grad_buffer_checks():
-    from chexpert_amd.models._autograd import check_input_grad, input_grad_buffer
+    from chexpert_amd.models._fused import check_input_grad, input_grad_buffer
     x = torch.zeros(2, 3, 8, 8)
     check_input_grad(torch.zeros(2, 3, 8, 8), x)
     for bad in (torch.zeros(2, 3, 8, 8, dtype=torch.float16), torch.zeros(2, 3, 8, 9), torch.zeros(2, 3, 8, 16)[..., ::2]):
