@@ -405,6 +405,40 @@ __global__ __launch_bounds__(1024) void bn_bwd_coef_kernel(const float* S1, cons
   }
 }
 
+// Frozen (eval-mode) form of bn_bwd_coef_kernel: y = gamma * (x - m) * r + beta with the running statistics m and
+// r = 1 / sqrt(running_var + eps), so dx = gamma * r * dy and there are no batch-statistic terms.  The producer reduced
+// S1 = sum dy and S2 = sum dy * (x - mu_b) * r_b against the basis (mu_b, r_b) it read (`mean` / `rstd`), hence
+//   dgamma += sum dy * (x - m) * r = S2 * (r / r_b) + r * (mu_b - m) * S1    (exactly S2 when the basis is the running statistics)
+//   dbeta  += S1,   pa = gamma * r, pb = pc = 0,   slice coefficients (qa, qb, qc) = (1, 0, 0).
+// r is formed as bn_coef_eval_kernel forms it, so pa equals the forward's scale bit for bit.
+__global__ __launch_bounds__(1024) void bn_bwd_coef_eval_kernel(const float* S1, const float* S2, const float* mean, const float* rstd,
+                                                                const float* rmean, const float* rvar, const float* gamma, float eps,
+                                                                float* dgamma, float* dbeta, float* pa, float* pb, float* pc, int C,
+                                                                int replicas, int rstride, float* qa, float* qb, float* qc, int q_lo,
+                                                                int q_n) {
+  __shared__ float part[2][64][17];
+  const int j = threadIdx.x & 15, q = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + j;
+  const int cc = c < C ? c : C - 1;
+  float s1, s2;
+  reduce_rows16<float>(S1, S2, replicas, rstride, cc, part, s1, s2);
+  if (q != 0 || c >= C) return;
+  const float g = gamma ? gamma[c] : 1.f;
+  const float r = 1.f / sqrtf(rvar[c] + eps);
+  if (dgamma) dgamma[c] += s2 * (r / rstd[c]) + r * (mean[c] - rmean[c]) * s1;
+  if (dbeta) dbeta[c] += s1;
+  if (qa && c >= q_lo && c < q_lo + q_n) {
+    qa[c - q_lo] = 1.f;
+    qb[c - q_lo] = 0.f;
+    qc[c - q_lo] = 0.f;
+  }
+  if (pa) {
+    pa[c] = g * r;
+    pb[c] = 0.f;
+    pc[c] = 0.f;
+  }
+}
+
 __global__ void bn_bwd_slice_coef_kernel(const float* A, const float* Bc, const float* mean, const float* rstd,
                                          float* pa, float* pb, float* pc, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1676,6 +1710,19 @@ int cx_bn_bwd_coef(const float* S1, const float* S2, float count, const float* g
   if (pa && (!pb || !pc)) return CX_EINVAL;
   hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((C + 15) / 16), dim3(1024), 0, as_stream(stream), S1, S2, count, gamma, mean,
                      rstd, dgamma, dbeta, A, Bc, pa, pb, pc, C, replicas, rstride, qa, qb, qc, q_lo, q_n);
+  return launch_status();
+}
+
+int cx_bn_bwd_coef_eval(const float* S1, const float* S2, const float* mean, const float* rstd, const float* running_mean,
+                        const float* running_var, const float* gamma, float eps, float* dgamma, float* dbeta, float* pa, float* pb,
+                        float* pc, int C, int replicas, int rstride, float* qa, float* qb, float* qc, int q_lo, int q_n, void* stream) {
+  if (!S1 || !S2 || !mean || !rstd || !running_mean || !running_var || C <= 0) return CX_EINVAL;
+  if (qa && (!qb || !qc || q_lo < 0 || q_n <= 0 || q_lo + q_n > C)) return CX_EINVAL;
+  if (replicas < 1) replicas = 1;
+  if (replicas > 1 && rstride < C) return CX_EINVAL;
+  if (pa && (!pb || !pc)) return CX_EINVAL;
+  hipLaunchKernelGGL(bn_bwd_coef_eval_kernel, dim3((C + 15) / 16), dim3(1024), 0, as_stream(stream), S1, S2, mean, rstd, running_mean,
+                     running_var, gamma, eps, dgamma, dbeta, pa, pb, pc, C, replicas, rstride, qa, qb, qc, q_lo, q_n);
   return launch_status();
 }
 

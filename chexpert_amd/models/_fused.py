@@ -18,6 +18,18 @@ def wants_autograd(model, x):
     return model.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in model.parameters()))
 
 
+def wants_eval_autograd(model, x):
+    """The eval-mode twin of wants_autograd: model.forward routes an eval() forward through the autograd function (BatchNorm with
+    its running statistics, frozen: saliency maps, integrated gradients, fine-tuning with frozen BatchNorm) when grad mode is on,
+    the input or some parameter requires a gradient, and no Grad-CAM hooks are registered (those keep hooked_eval_forward)."""
+    if model.training or not torch.is_grad_enabled():
+        return False
+    if not (x.requires_grad or any(p.requires_grad for p in model.parameters())):
+        return False
+    from ..gradcam import hooks_registered
+    return not hooks_registered(model)
+
+
 def input_grad_buffer(x_shape, device):
     """fp32 (B, 3, H, W) buffer cx_stem_input_grad writes (every element)."""
     if len(x_shape) != 4 or x_shape[1] != 3:
@@ -52,17 +64,16 @@ def params_untouched(params, flat_grad):
 
 # --------------------------------------------------------------------------------------------- module side
 class _Fn(torch.autograd.Function):
-    """loss.backward() through a fused network: forward runs the engine's training forward, backward its backward pass.  `anchor`
-    is a parameter of the network, so that autograd records the call; x.grad is returned when the input needs it."""
+    """loss.backward() through a fused network: forward runs the engine's training forward -- in eval mode its recording eval
+    forward (running statistics, and what backward reads) --, backward its backward pass (in eval mode with frozen BatchNorm).
+    `anchor` is a parameter of the network, so that autograd records the call; x.grad is returned when the input needs it."""
 
     @staticmethod
     def forward(ctx, x, anchor, model):
-        if not model.training:
-            raise NotImplementedError("autograd through the fused %s needs train() mode (batch-statistic BatchNorm backward); for "
-                                      "Grad-CAM use chexpert_amd.gradcam.grad_cam" % type(model).__name__)
         eng = model._engine
-        ws = eng.forward(x, True)
+        ws = eng.forward(x, model.training, record=True)
         ctx.model, ctx.eng, ctx.ws, ctx.x_meta = model, eng, ws, (tuple(x.shape), x.dtype, x.device)
+        ctx.eval_mode = not model.training
         return ws.logits.clone()
 
     @staticmethod
@@ -70,6 +81,9 @@ class _Fn(torch.autograd.Function):
         eng, ws = ctx.eng, ctx.ws
         if ws is None:
             raise RuntimeError("backward through the fused %s can only run once per forward" % type(ctx.model).__name__)
+        if ctx.eval_mode and torch.is_grad_enabled():
+            raise RuntimeError("double backward (create_graph=True) through the fused %s is not supported: its backward runs as "
+                               "HIP kernels outside autograd" % type(ctx.model).__name__)
         shape, dtype, dev = ctx.x_meta
         dx = input_grad_buffer(shape, dev) if ctx.needs_input_grad[0] else None
         frozen = not any(p.requires_grad for p in ctx.model.parameters())
@@ -118,6 +132,8 @@ class FusedNet(nn.Module):
             from ..gradcam import hooked_eval_forward, hooks_registered
             if hooks_registered(self):                     # Grad-CAM hook protocol of the reference (chexpert.py:271-272)
                 return hooked_eval_forward(self, x)
+            if wants_eval_autograd(self, x):               # frozen-BatchNorm backward (saliency, fine-tuning with frozen BN)
+                return _Fn.apply(x, self._anchor(), self)
         ws = eng.forward(x, self.training)
         out = ws.logits.clone()
         eng.release(ws)
@@ -127,11 +143,12 @@ class FusedNet(nn.Module):
     def forward_backward(self, x, target, input_grad=None):
         """logits = model(x); loss = BCEWithLogits(logits, target).sum(1).mean(0); loss.backward().
         Returns (loss, logits) as device tensors without a host sync.  input_grad: None, or a preallocated fp32 (B,3,H,W) tensor that
-        also receives d loss / d x (what x.grad would hold), still without a host sync."""
+        also receives d loss / d x (what x.grad would hold), still without a host sync.  In eval mode this is the frozen-BatchNorm
+        step (running statistics, which stay as they are)."""
         eng = self._eng()
         if input_grad is not None:
             check_input_grad(input_grad, x)
-        ws = eng.forward(x, self.training)
+        ws = eng.forward(x, self.training, record=True)
         B, n = ws.logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
@@ -306,6 +323,24 @@ class FusedEngine:
         return self.flat_grad[off:off + p.numel()]
 
     @staticmethod
+    def recorded(ws, train, record):
+        """Marks a forward's workspace: ws.frozen (an eval forward: backward takes the frozen-BatchNorm form) and ws.recorded
+        (whether it holds everything backward reads)."""
+        ws.frozen = not train
+        ws.recorded = train or record
+
+    @staticmethod
+    def bn_bwd_coef(ws, bn, S1, S2, count, gamma, mean, rstd, dgamma, dbeta, A, Bc, pa, pb, pc, Cn, replicas=1, rstride=0, q=None, lo=0):
+        """Backward coefficients of BatchNorm `bn` over its channels [lo, lo + Cn) (gamma, mean, rstd, dgamma, dbeta, A, Bc already
+        sliced by the caller): ops.bn_bwd_coef after a training forward; after an eval forward the frozen form
+        (ops.bn_bwd_coef_eval: running statistics, no batch-statistic terms, A / Bc untouched, identity slice coefficients)."""
+        if not ws.frozen:
+            return ops.bn_bwd_coef(S1, S2, count, gamma, mean, rstd, dgamma, dbeta, A, Bc, pa, pb, pc, Cn, replicas=replicas,
+                                   rstride=rstride, q=q)
+        ops.bn_bwd_coef_eval(S1, S2, mean, rstd, bn.running_mean[lo:lo + Cn], bn.running_var[lo:lo + Cn], gamma, bn.eps, dgamma,
+                             dbeta, pa, pb, pc, Cn, replicas=replicas, rstride=rstride, q=q)
+
+    @staticmethod
     def _v(ws, slot, n=None):
         off, m = slot
         return ws.vec[off:off + (m if n is None else n)]
@@ -329,6 +364,8 @@ class FusedEngine:
         """The backward pass of the forward that filled `ws`, from d loss / d logits; dx: None, or an fp32 (B,3,H,W) buffer that also
         receives the input gradient (cx_stem_input_grad).  Gradients accumulate into the parameters' .grad, which are views of
         the flat gradient buffer (bound here when some .grad is None)."""
+        if not getattr(ws, "recorded", True):
+            raise RuntimeError("this eval forward recorded nothing for a backward: run forward(x, False, record=True)")
         ops.set_det_wgrad(self.det)            # reproducible weight-gradient sums with the deterministic statistics
         # the ordered slab sums run as one table-driven launch at the end of the pass (ops.wgrad_defer_*); a data-parallel run
         # flushes them before each gradient bucket leaves (GradReducer.pre_launch)

@@ -415,7 +415,11 @@ class _Engine(FusedEngine):
                             bn.running_mean if bn.track_running_stats else None, bn.running_var if bn.track_running_stats else None,
                             ws.v(out_slots[0])[:cin], ws.v(out_slots[1])[:cin], cin, fresh)
 
-    def forward(self, x, train):
+    def forward(self, x, train, record=False):
+        """train: batch statistics, dropout; eval: running statistics.  Every forward keeps what backward reads (block buffers,
+        bottleneck outputs, max-pool arg-max, attention log-sum-exp), so `record` changes nothing here.  An eval forward leaves each
+        block's bmr (mean / rstd) at the running statistics of the block's LAST BatchNorm consumer (transition norm, norm5; the
+        last layer's norm1 before an attention transition): the basis of the frozen backward's sums."""
         m, f, s = self.model, self.model.features, self.slots
         det = self.det and train
         u8 = x.dtype == torch.uint8             # decoded grey bytes (B,1,H,W): whitened + expanded on the GPU (cx_u8_to_nhwc4)
@@ -431,8 +435,9 @@ class _Engine(FusedEngine):
         elif H % 32 or W % 32:
             raise RuntimeError("input height/width must be multiples of 32 (got %dx%d)" % (H, W))
         self.bind(x.device)
-        self.pack(train)
+        self.pack(train or record)          # (a step that differentiates repacks, as training does: a fused optimiser bumps no version)
         ws = self.acquire(B, H, W)
+        self.recorded(ws, train, True)
         if train and not self.det:
             z0, zn = self.fwd_zero
             ws.vec[z0:z0 + zn].zero_()
@@ -670,8 +675,8 @@ class _Engine(FusedEngine):
             if li_ < 0:
                 return tuple(v(t)[:c0_] for t in s["q"]) + (0, c0_)
             return tuple(v(t) for t in s["ql"][bi_][li_]) + (c0_ + li_ * g_, g_)
-        ops.bn_bwd_coef(sred[0], sred[1], B * h * w, f.norm5.weight, v(bmean), v(brstd), G(f.norm5.weight), G(f.norm5.bias),
-                        v(A), v(Bc), None, None, None, ct, replicas=sred[2], rstride=sred[3], q=slice_q(bi, n_layers - 1))
+        self.bn_bwd_coef(ws, f.norm5, sred[0], sred[1], B * h * w, f.norm5.weight, v(bmean), v(brstd), G(f.norm5.weight), G(f.norm5.bias),
+                         v(A), v(Bc), None, None, None, ct, replicas=sred[2], rstride=sred[3], q=slice_q(bi, n_layers - 1))
         q, pv = s["q"], s["p"]
         # The 3x3 weight-gradient kernels only feed the flat gradient buffer.  Rounds 1-2 ran them on a side stream beside the
         # input-gradient chain (CHEXPERT_SERIAL_WGRAD=0 still does); since the slab sums are deferred and the fused 1x1 backward
@@ -739,7 +744,7 @@ class _Engine(FusedEngine):
                     if not fused:
                         main.wait_event(ev_)
                 dyc = ws.dyc[bi][li] if ws.dyc is not None else None
-                if self.drop_rate > 0:
+                if self.drop_rate > 0 and not ws.frozen:         # (eval mode: no dropout in the forward)
                     # the slice's deferred BatchNorm correction and the forward's keep decisions, in place on the gradient slice;
                     # the kernels below then read it with identity coefficients
                     ops.dropout_slice_bwd(gs, xs, qa, qb, qc, self.drop_rate, self.drop_seed, bi * 256 + li)
@@ -781,8 +786,8 @@ class _Engine(FusedEngine):
                         ops.conv_wgrad(gs, y1, G(layer.conv2.weight), kh=3, kw=3, pad=1, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa,
                                        gb=qb, gc=qc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]), pb=v(n2[1]))
                 pa, pb, pc = (v(t) for t in s["pl"][bi][li])
-                ops.bn_bwd_coef(red2[0], red2[1], cnt, layer.norm2.weight, v(n2[2]), v(n2[3]), G(layer.norm2.weight),
-                                G(layer.norm2.bias), None, None, pa, pb, pc, self.mid, replicas=red2[2], rstride=red2[3])
+                self.bn_bwd_coef(ws, layer.norm2, red2[0], red2[1], cnt, layer.norm2.weight, v(n2[2]), v(n2[3]), G(layer.norm2.weight),
+                                 G(layer.norm2.bias), None, None, pa, pb, pc, self.mid, replicas=red2[2], rstride=red2[3])
                 if not fused:
                     ev_p = torch.cuda.Event()
                     ev_p.record(main)
@@ -803,9 +808,9 @@ class _Engine(FusedEngine):
                 if not fused or red is not None:
                     w1_done[k] = torch.cuda.Event()
                     w1_done[k].record(side)
-                ops.bn_bwd_coef(red1[0], red1[1], cnt, layer.norm1.weight, v(bmean), v(brstd), G(layer.norm1.weight),
-                                G(layer.norm1.bias), v(A), v(Bc), None, None, None, cin, replicas=red1[2], rstride=red1[3],
-                                q=slice_q(bi, li - 1))
+                self.bn_bwd_coef(ws, layer.norm1, red1[0], red1[1], cnt, layer.norm1.weight, v(bmean), v(brstd), G(layer.norm1.weight),
+                                 G(layer.norm1.bias), v(A), v(Bc), None, None, None, cin, replicas=red1[2], rstride=red1[3],
+                                 q=slice_q(bi, li - 1))
                 if red is not None:
                     main.wait_event(w1_done[k])
                 k += 1
@@ -841,9 +846,9 @@ class _Engine(FusedEngine):
                     sred = (v(St[0]), v(St[1]), 1, 0)
                 ops.conv_wgrad(gs, pbuf, G(tr.conv.weight), mode=ops.MODE_POOL2, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa, gb=qb,
                                gc=qc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(nt[0]), pb=v(nt[1]))
-                ops.bn_bwd_coef(sred[0], sred[1], B * ph * pw, tr.norm.weight, v(pmean), v(prstd), G(tr.norm.weight),
-                                G(tr.norm.bias), v(pA), v(pB), None, None, None, cprev, replicas=sred[2], rstride=sred[3],
-                                q=slice_q(bi - 1, pn - 1))
+                self.bn_bwd_coef(ws, tr.norm, sred[0], sred[1], B * ph * pw, tr.norm.weight, v(pmean), v(prstd), G(tr.norm.weight),
+                                 G(tr.norm.bias), v(pA), v(pB), None, None, None, cprev, replicas=sred[2], rstride=sred[3],
+                                 q=slice_q(bi - 1, pn - 1))
                 done(tr.norm.weight)
             elif self.cifar:
                 # stem backward of the CIFAR form: relu0 mask + norm0 sums in the mask epilogue of the identity convolution (its
@@ -855,8 +860,8 @@ class _Engine(FusedEngine):
                                      e_scale=ws.ones[:ci], **self._sp(ws, S0, ci))
                 sred = self._sc(ws, S0, ci, rows)
                 pa, pb, pc = (v(t)[:ci] for t in pv)
-                ops.bn_bwd_coef(sred[0], sred[1], B * ws.H * ws.W, f.norm0.weight, v(n0[2]), v(n0[3]), G(f.norm0.weight),
-                                G(f.norm0.bias), None, None, pa, pb, pc, ci, replicas=sred[2], rstride=sred[3])
+                self.bn_bwd_coef(ws, f.norm0, sred[0], sred[1], B * ws.H * ws.W, f.norm0.weight, v(n0[2]), v(n0[3]), G(f.norm0.weight),
+                                 G(f.norm0.bias), None, None, pa, pb, pc, ci, replicas=sred[2], rstride=sred[3])
                 ops.conv_wgrad(ws.dz0, ws.x8, G(f.conv0.weight), kh=5, kw=5, pad=2, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=pa, gb=pb,
                                gc=pc)
                 if dx is not None:
@@ -872,9 +877,9 @@ class _Engine(FusedEngine):
                                            v(S0[0]), v(S0[1]))
                     sred = (v(S0[0]), v(S0[1]), 1, 0)
                 pa, pb, pc = (v(t)[:self.c_init] for t in pv)
-                ops.bn_bwd_coef(sred[0], sred[1], B * (ws.H // 2) * (ws.W // 2), f.norm0.weight, v(n0[2]), v(n0[3]),
-                                G(f.norm0.weight), G(f.norm0.bias), None, None, pa, pb, pc, self.c_init, replicas=sred[2],
-                                rstride=sred[3])
+                self.bn_bwd_coef(ws, f.norm0, sred[0], sred[1], B * (ws.H // 2) * (ws.W // 2), f.norm0.weight, v(n0[2]), v(n0[3]),
+                                 G(f.norm0.weight), G(f.norm0.bias), None, None, pa, pb, pc, self.c_init, replicas=sred[2],
+                                 rstride=sred[3])
                 ops.conv_wgrad(ws.dz0, ws.x4, G(f.conv0.weight), mode=ops.MODE_STEM, g_prologue=ops.PRO_AFFINE2, g2=ws.c0,
                                ga=pa, gb=pb, gc=pc)
                 if dx is not None:
@@ -922,8 +927,8 @@ class _Engine(FusedEngine):
                 ops.conv_wgrad(gs, y1, G(layer.conv2.weight), kh=3, kw=3, pad=1, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa, gb=qb,
                                gc=qc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]), pb=v(n2[1]))
             pabc = tuple(v(t) for t in s["pl"][bi][l_i])
-            ops.bn_bwd_coef(red2[0], red2[1], cnt, layer.norm2.weight, v(n2[2]), v(n2[3]), G(layer.norm2.weight),
-                            G(layer.norm2.bias), None, None, *pabc, self.mid, replicas=red2[2], rstride=red2[3])
+            self.bn_bwd_coef(ws, layer.norm2, red2[0], red2[1], cnt, layer.norm2.weight, v(n2[2]), v(n2[3]), G(layer.norm2.weight),
+                             G(layer.norm2.bias), None, None, *pabc, self.mid, replicas=red2[2], rstride=red2[3])
             return pabc
 
         def conv1_args(l_i, layer, dz2, pabc, lo, hi, stat):
@@ -937,9 +942,9 @@ class _Engine(FusedEngine):
         def coef1(layer, red1, lo, hi, q):
             if q is not None:
                 q = q[:3] + (q[3] - lo, q[4])
-            ops.bn_bwd_coef(red1[0], red1[1], cnt, layer.norm1.weight[lo:hi], v(bmean)[lo:hi], v(brstd)[lo:hi],
-                            G(layer.norm1.weight)[lo:hi], G(layer.norm1.bias)[lo:hi], v(A)[lo:hi], v(Bc)[lo:hi], None, None, None, hi - lo,
-                            replicas=red1[2], rstride=red1[3], q=q)
+            self.bn_bwd_coef(ws, layer.norm1, red1[0], red1[1], cnt, layer.norm1.weight[lo:hi], v(bmean)[lo:hi], v(brstd)[lo:hi],
+                             G(layer.norm1.weight)[lo:hi], G(layer.norm1.bias)[lo:hi], v(A)[lo:hi], v(Bc)[lo:hi], None, None, None, hi - lo,
+                             replicas=red1[2], rstride=red1[3], q=q, lo=lo)
 
         def stat_region(slots, lo, n, part, parts):
             """(producer keywords, consumer tuple-maker) for the statistics of channels [lo, lo + n) in one of `parts` regions"""
@@ -1134,13 +1139,13 @@ class _PaddedEngine(FusedEngine):
     def _map(self, real, padded, tab, direction, accumulate=0):
         check(lib().cx_chan_map_table(ptr(real), ptr(padded), ptr(tab[0]), tab[1], direction, accumulate, stream_ptr()), "cx_chan_map_table")
 
-    def forward(self, x, train):
+    def forward(self, x, train, record=False):
         self.bind(x.device)
         in_ = self.inner
         self._map(self.flat, in_.flat, self.ptab, 0)              # parameters: real -> padded
         self._map(self.stat, self.tstat, self.stab, 0)            # running statistics
         in_.packed_version = None
-        ws = in_.forward(x, train)
+        ws = in_.forward(x, train, record)
         for raa, taa in self.twin.aa_pairs:                       # AAConv2d.weights of the real module (attn_aug_conv.py:87)
             object.__setattr__(raa, "_last", taa._last)
         if train:

@@ -191,15 +191,18 @@ class _Engine(FusedEngine):
         return conv_e, bn_e, mods[i], mods[i + 1], mods[i + 3], mods[i + 4], mods[i + 5]      # dw, bn_d, se, conv_p, bn_p
 
     # ---- forward
-    def forward(self, x, train):
+    def forward(self, x, train, record=False):
+        """train: batch statistics, Dropout / DropConnect; eval: running statistics, no masks.  Every forward keeps what backward
+        reads (activations and squeeze-excite intermediates), so `record` changes nothing here."""
         m, v, lb = self.model, self._v, (_LibF32(lib()) if self.dtype == torch.float32 else lib())
         u8 = x.dtype == torch.uint8             # decoded grey bytes (B,1,H,W): whitened + expanded on the GPU (cx_u8_to_nhwc8)
         if x.dim() != 4 or x.shape[1] != (1 if u8 else 3):
             raise RuntimeError("expected a (B,3,H,W) float input or a (B,1,H,W) uint8 image")
         B, _, H, W = x.shape
         self.bind(x.device)
-        self.pack(train)
+        self.pack(train or record)          # (a step that differentiates repacks, as training does: a fused optimiser bumps no version)
         ws = self.acquire(B, H, W)
+        self.recorded(ws, train, True)
         self.last_masks = {}
         self.n_forward = getattr(self, "n_forward", 0) + 1
         ws.step = self.n_forward
@@ -340,11 +343,11 @@ class _Engine(FusedEngine):
             """BatchNorm backward coefficients of `bn` from the sums its producer has just written (deterministic mode: the rows of
             the scratch pair, counted by cx_last_stat_rows)."""
             if det:
-                ops.bn_bwd_coef(ws.slab[0], ws.slab[1], count, bn.weight, v(ws, S.mean), v(ws, S.rstd), G(bn.weight), G(bn.bias), None, None,
-                                v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), S.C, replicas=lib().cx_last_stat_rows(), rstride=S.C)
+                self.bn_bwd_coef(ws, bn, ws.slab[0], ws.slab[1], count, bn.weight, v(ws, S.mean), v(ws, S.rstd), G(bn.weight), G(bn.bias),
+                                 None, None, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), S.C, replicas=lib().cx_last_stat_rows(), rstride=S.C)
             else:
-                ops.bn_bwd_coef(v(ws, S.S1), v(ws, S.S2), count, bn.weight, v(ws, S.mean), v(ws, S.rstd), G(bn.weight), G(bn.bias), None, None,
-                                v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), S.C)
+                self.bn_bwd_coef(ws, bn, v(ws, S.S1), v(ws, S.S2), count, bn.weight, v(ws, S.mean), v(ws, S.rstd), G(bn.weight), G(bn.bias),
+                                 None, None, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), S.C)
 
         def ssp(S):      # (S1, S2, stat_rows) of an element-wise / depthwise producer of S's backward sums
             return (ptr(ws.slab[0]), ptr(ws.slab[1]), self._rows_cap(S.C)) if det else (ptr(v(ws, S.S1)), ptr(v(ws, S.S2)), 0)

@@ -313,7 +313,9 @@ class _Engine(FusedEngine):
         return kw
 
     # ---- forward
-    def forward(self, x, train):
+    def forward(self, x, train, record=False):
+        """train: batch statistics (and running-statistic updates); eval: running statistics.  record (eval): also keep what
+        backward reads -- the join ReLU sign bits, which an eval forward without a backward skips."""
         m, v = self.model, self._v
         u8 = x.dtype == torch.uint8             # decoded grey bytes (B,1,H,W): whitened + expanded on the GPU (cx_u8_to_nhwc4)
         if x.dim() != 4 or x.shape[1] != (1 if u8 else 3):
@@ -323,8 +325,9 @@ class _Engine(FusedEngine):
         if H % mult or W % mult:
             raise RuntimeError("input height/width must be multiples of %d (got %dx%d)" % (mult, H, W))
         self.bind(x.device)
-        self.pack(train)
+        self.pack(train or record)          # (a step that differentiates repacks, as training does: a fused optimiser bumps no version)
         ws = self.acquire(B, H, W)
+        self.recorded(ws, train, record)
         if train and not self.det:
             z0, zn = self.fwd_zero
             ws.vec[z0:z0 + zn].zero_()
@@ -356,7 +359,7 @@ class _Engine(FusedEngine):
             cin_ = self._cin(b)
             hi, wi = t["hin"]
             ho, wo = t["hout"]
-            mk = t["mask"] if train else None
+            mk = t["mask"] if ws.recorded else None
             if self.basic:
                 # attn_aug_conv.py:135-156: conv3x3(stride) - bn1 - relu - conv3x3 - bn2, + identity | downsample(x), relu
                 S1, S2 = self.bn[id(b.bn1)], self.bn[id(b.bn2)]
@@ -532,13 +535,13 @@ class _Engine(FusedEngine):
                                    v(ws, Sd.rstd) if Sd else None, g, v(ws, S3.S1), v(ws, S3.S2), v(ws, Sd.S2) if Sd else None,
                                    mask=t["mask"])
             r3 = srows(S3, rows)
-            ops.bn_bwd_coef(r3[0], r3[1], cnt_o, b.bn3.weight, v(ws, S3.mean), v(ws, S3.rstd), G(b.bn3.weight),
-                            G(b.bn3.bias), None, None, v(ws, S3.pa), v(ws, S3.pb), v(ws, S3.pc), S3.C, replicas=r3[2], rstride=r3[3])
+            self.bn_bwd_coef(ws, b.bn3, r3[0], r3[1], cnt_o, b.bn3.weight, v(ws, S3.mean), v(ws, S3.rstd), G(b.bn3.weight),
+                             G(b.bn3.bias), None, None, v(ws, S3.pa), v(ws, S3.pb), v(ws, S3.pc), S3.C, replicas=r3[2], rstride=r3[3])
             if Sd is not None and det:       # the downsample BatchNorm shares S1 with bn3: reduce it before the rows are re-used
                 bnd = b.downsample[1]
                 rd = srows(S3, rows, ws.slab[2])
-                ops.bn_bwd_coef(rd[0], rd[1], cnt_o, bnd.weight, v(ws, Sd.mean), v(ws, Sd.rstd), G(bnd.weight), G(bnd.bias), None, None,
-                                v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc), Sd.C, replicas=rd[2], rstride=rd[3])
+                self.bn_bwd_coef(ws, bnd, rd[0], rd[1], cnt_o, bnd.weight, v(ws, Sd.mean), v(ws, Sd.rstd), G(bnd.weight), G(bnd.bias),
+                                 None, None, v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc), Sd.C, replicas=rd[2], rstride=rd[3])
             dz2 = bw["dz2"][:B * ho * wo * p_].view(B, ho, wo, p_)
             rows = ops.conv_gemm(g, self.w_bwd(b.conv3), dz2, N=p_, prologue=ops.PRO_AFFINE2, x2=t["y3"], pa=v(ws, S3.pa),
                                  pb=v(ws, S3.pb), pc=v(ws, S3.pc), epilogue=ops.EPI_MASK, ex=t["y2"], e_sc=v(ws, S2.sc),
@@ -546,8 +549,8 @@ class _Engine(FusedEngine):
             r2 = srows(S2, rows)
             ops.conv_wgrad(g, t["y2"], G(b.conv3.weight), g_prologue=ops.PRO_AFFINE2, g2=t["y3"], ga=v(ws, S3.pa), gb=v(ws, S3.pb),
                            gc=v(ws, S3.pc), x_prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S2.sc), pb=v(ws, S2.sh))
-            ops.bn_bwd_coef(r2[0], r2[1], cnt_o, b.bn2.weight, v(ws, S2.mean), v(ws, S2.rstd), G(b.bn2.weight),
-                            G(b.bn2.bias), None, None, v(ws, S2.pa), v(ws, S2.pb), v(ws, S2.pc), S2.C, replicas=r2[2], rstride=r2[3])
+            self.bn_bwd_coef(ws, b.bn2, r2[0], r2[1], cnt_o, b.bn2.weight, v(ws, S2.mean), v(ws, S2.rstd), G(b.bn2.weight),
+                             G(b.bn2.bias), None, None, v(ws, S2.pa), v(ws, S2.pb), v(ws, S2.pc), S2.C, replicas=r2[2], rstride=r2[3])
             dz1 = bw["dz1"][:B * hi * wi * p_].view(B, hi, wi, p_)
             mask1 = dict(epilogue=ops.EPI_MASK, ex=t["y1"], e_sc=v(ws, S1.sc), e_sh=v(ws, S1.sh), e_mu=v(ws, S1.mean),
                          e_r=v(ws, S1.rstd), e_scale=ones(p_), **msp(S1))
@@ -593,8 +596,8 @@ class _Engine(FusedEngine):
                                    ga=v(ws, S2.pa)[c_], gb=v(ws, S2.pb)[c_], gc=v(ws, S2.pc)[c_], x_prologue=ops.PRO_AFFINE_RELU,
                                    pa=v(ws, S1.sc)[c_], pb=v(ws, S1.sh)[c_])
             r1 = srows(S1, rows)
-            ops.bn_bwd_coef(r1[0], r1[1], cnt_i, b.bn1.weight, v(ws, S1.mean), v(ws, S1.rstd), G(b.bn1.weight),
-                            G(b.bn1.bias), None, None, v(ws, S1.pa), v(ws, S1.pb), v(ws, S1.pc), S1.C, replicas=r1[2], rstride=r1[3])
+            self.bn_bwd_coef(ws, b.bn1, r1[0], r1[1], cnt_i, b.bn1.weight, v(ws, S1.mean), v(ws, S1.rstd), G(b.bn1.weight),
+                             G(b.bn1.bias), None, None, v(ws, S1.pa), v(ws, S1.pb), v(ws, S1.pc), S1.C, replicas=r1[2], rstride=r1[3])
             gx = (bw["g"][bi - 1] if bi > 0 else bw["g_in0"]) if Sd is not None or bi == 0 else g
             identity = Sd is None
             if identity and gx is not g:
@@ -616,8 +619,8 @@ class _Engine(FusedEngine):
             if Sd is not None:
                 bnd, convd = b.downsample[1], b.downsample[0]
                 if not det:
-                    ops.bn_bwd_coef(v(ws, S3.S1), v(ws, Sd.S2), cnt_o, bnd.weight, v(ws, Sd.mean), v(ws, Sd.rstd), G(bnd.weight),
-                                    G(bnd.bias), None, None, v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc), Sd.C)
+                    self.bn_bwd_coef(ws, bnd, v(ws, S3.S1), v(ws, Sd.S2), cnt_o, bnd.weight, v(ws, Sd.mean), v(ws, Sd.rstd), G(bnd.weight),
+                                     G(bnd.bias), None, None, v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc), Sd.C)
                 ops.conv_gemm(g, self.w_bwd(convd), gx, N=cin, tstride=s_, prologue=ops.PRO_AFFINE2, x2=t["yd"], pa=v(ws, Sd.pa),
                               pb=v(ws, Sd.pb), pc=v(ws, Sd.pc), accumulate=True)
                 ops.conv_wgrad(g, xin, G(convd.weight), stride=s_, g_prologue=ops.PRO_AFFINE2, g2=t["yd"], ga=v(ws, Sd.pa),
@@ -636,8 +639,8 @@ class _Engine(FusedEngine):
                 ops.relu_bwd_stats(gx, ws.pool0, ws.c0, v(ws, S0.mean), v(ws, S0.rstd), None, None, None, bw["dz0"], v(ws, S0.S1),
                                    v(ws, S0.S2), None)
             r0 = srows(S0, rows)
-            ops.bn_bwd_coef(r0[0], r0[1], cnt0, m.bn1.weight, v(ws, S0.mean), v(ws, S0.rstd), G(m.bn1.weight), G(m.bn1.bias), None, None,
-                            v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), c0, replicas=r0[2], rstride=r0[3])
+            self.bn_bwd_coef(ws, m.bn1, r0[0], r0[1], cnt0, m.bn1.weight, v(ws, S0.mean), v(ws, S0.rstd), G(m.bn1.weight), G(m.bn1.bias),
+                             None, None, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), c0, replicas=r0[2], rstride=r0[3])
             dw8 = torch.zeros(c0, 8, 3, 3, dtype=torch.float32, device=self.device)       # 3 input channels padded to 8
             ops.conv_wgrad(bw["dz0"], ws.x8, dw8, kh=3, kw=3, stride=1, pad=1, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=v(ws, S0.pa),
                            gb=v(ws, S0.pb), gc=v(ws, S0.pc))
@@ -653,9 +656,9 @@ class _Engine(FusedEngine):
                 ops.bnrelu_maxpool_bwd(ws.c0, v(ws, S0.sc), v(ws, S0.sh), v(ws, S0.mean), v(ws, S0.rstd), ws.amax, gx, gx, ones(64),
                                        zeros(64), zeros(64), bw["dz0"], v(ws, S0.S1), v(ws, S0.S2))
             r0 = srows(S0, rows)
-            ops.bn_bwd_coef(r0[0], r0[1], B * (ws.H // 2) * (ws.W // 2), m.bn1.weight, v(ws, S0.mean), v(ws, S0.rstd),
-                            G(m.bn1.weight), G(m.bn1.bias), None, None, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), 64, replicas=r0[2],
-                            rstride=r0[3])
+            self.bn_bwd_coef(ws, m.bn1, r0[0], r0[1], B * (ws.H // 2) * (ws.W // 2), m.bn1.weight, v(ws, S0.mean), v(ws, S0.rstd),
+                             G(m.bn1.weight), G(m.bn1.bias), None, None, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), 64, replicas=r0[2],
+                             rstride=r0[3])
             ops.conv_wgrad(bw["dz0"], ws.x4, G(m.conv1.weight), mode=ops.MODE_STEM, g_prologue=ops.PRO_AFFINE2, g2=ws.c0,
                            ga=v(ws, S0.pa), gb=v(ws, S0.pb), gc=v(ws, S0.pc))
             if dx is not None:
@@ -682,13 +685,13 @@ class _Engine(FusedEngine):
                                v(ws, Sd.rstd) if Sd else None, g, v(ws, S2.S1), v(ws, S2.S2), v(ws, Sd.S2) if Sd else None,
                                mask=t["mask"])
         r2 = srows(S2, rows)
-        ops.bn_bwd_coef(r2[0], r2[1], cnt, b.bn2.weight, v(ws, S2.mean), v(ws, S2.rstd), G(b.bn2.weight), G(b.bn2.bias), None, None,
-                        v(ws, S2.pa), v(ws, S2.pb), v(ws, S2.pc), S2.C, replicas=r2[2], rstride=r2[3])
+        self.bn_bwd_coef(ws, b.bn2, r2[0], r2[1], cnt, b.bn2.weight, v(ws, S2.mean), v(ws, S2.rstd), G(b.bn2.weight), G(b.bn2.bias),
+                         None, None, v(ws, S2.pa), v(ws, S2.pb), v(ws, S2.pc), S2.C, replicas=r2[2], rstride=r2[3])
         if Sd is not None:                   # the downsample BatchNorm shares S1 (sum of the masked gradient) with bn2
             bnd = b.downsample[1]
             rd = srows(S2, rows, ws.slab[2]) if det else (v(ws, S2.S1), v(ws, Sd.S2), 1, 0)
-            ops.bn_bwd_coef(rd[0], rd[1], cnt, bnd.weight, v(ws, Sd.mean), v(ws, Sd.rstd), G(bnd.weight), G(bnd.bias), None, None,
-                            v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc), Sd.C, replicas=rd[2], rstride=rd[3])
+            self.bn_bwd_coef(ws, bnd, rd[0], rd[1], cnt, bnd.weight, v(ws, Sd.mean), v(ws, Sd.rstd), G(bnd.weight), G(bnd.bias), None, None,
+                             v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc), Sd.C, replicas=rd[2], rstride=rd[3])
         dz1 = bw["dz1"][:cnt * p_].view(B, ho, wo, p_)
         rows = ops.conv_gemm(g, self.w_bwd(b.conv2), dz1, N=p_, kh=3, kw=3, pad=1, prologue=ops.PRO_AFFINE2, x2=t["y2"], pa=v(ws, S2.pa),
                              pb=v(ws, S2.pb), pc=v(ws, S2.pc), epilogue=ops.EPI_MASK, ex=t["y1"], e_sc=v(ws, S1.sc), e_sh=v(ws, S1.sh),
@@ -696,8 +699,8 @@ class _Engine(FusedEngine):
         r1 = srows(S1, rows)
         ops.conv_wgrad(g, t["y1"], G(b.conv2.weight), kh=3, kw=3, stride=1, pad=1, g_prologue=ops.PRO_AFFINE2, g2=t["y2"],
                        ga=v(ws, S2.pa), gb=v(ws, S2.pb), gc=v(ws, S2.pc), x_prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S1.sc), pb=v(ws, S1.sh))
-        ops.bn_bwd_coef(r1[0], r1[1], cnt, b.bn1.weight, v(ws, S1.mean), v(ws, S1.rstd), G(b.bn1.weight), G(b.bn1.bias), None, None,
-                        v(ws, S1.pa), v(ws, S1.pb), v(ws, S1.pc), S1.C, replicas=r1[2], rstride=r1[3])
+        self.bn_bwd_coef(ws, b.bn1, r1[0], r1[1], cnt, b.bn1.weight, v(ws, S1.mean), v(ws, S1.rstd), G(b.bn1.weight), G(b.bn1.bias),
+                         None, None, v(ws, S1.pa), v(ws, S1.pb), v(ws, S1.pc), S1.C, replicas=r1[2], rstride=r1[3])
         gx = (bw["g"][bi - 1] if bi > 0 else bw["g_in0"]) if Sd is not None or bi == 0 else g
         identity = Sd is None
         if identity and gx is not g:

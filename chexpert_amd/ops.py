@@ -441,6 +441,16 @@ def bn_bwd_coef(S1, S2, count, gamma, mean, rstd, dgamma, dbeta, A, Bc, pa, pb, 
                                stream_ptr()), "cx_bn_bwd_coef")
 
 
+def bn_bwd_coef_eval(S1, S2, mean, rstd, rmean, rvar, gamma, eps, dgamma, dbeta, pa, pb, pc, Cn, replicas=1, rstride=0, q=None):
+    """cx_bn_bwd_coef_eval: the frozen (running-statistic) form of bn_bwd_coef.  (mean, rstd) is the basis the producer reduced S2
+    against, (rmean, rvar) the BatchNorm's running statistics; q = (qa, qb, qc, q_lo, q_n): also write the identity slice
+    coefficients (1, 0, 0) of channels [q_lo, q_lo + q_n)."""
+    qa, qb, qc, q_lo, q_n = q if q is not None else (None, None, None, 0, 0)
+    check(lib().cx_bn_bwd_coef_eval(ptr(S1), ptr(S2), ptr(mean), ptr(rstd), ptr(rmean), ptr(rvar), ptr(gamma), float(eps), ptr(dgamma),
+                                    ptr(dbeta), ptr(pa), ptr(pb), ptr(pc), Cn, replicas, rstride, ptr(qa), ptr(qb), ptr(qc), q_lo, q_n,
+                                    stream_ptr()), "cx_bn_bwd_coef_eval")
+
+
 def bn_bwd_slice_coef(A, Bc, mean, rstd, pa, pb, pc, Cn):
     check(lib().cx_bn_bwd_slice_coef(ptr(A), ptr(Bc), ptr(mean), ptr(rstd), ptr(pa), ptr(pb), ptr(pc), Cn, stream_ptr()),
           "cx_bn_bwd_slice_coef")

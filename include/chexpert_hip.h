@@ -311,6 +311,16 @@ int cx_bn_bwd_coef(const float* S1, const float* S2, float count, const float* g
                    /* optional: the cx_bn_bwd_slice_coef vectors of channels [q_lo, q_lo + q_n) from the A / B this call has just
                       completed (their last consumer), qa/qb/qc of q_n floats, or NULL                                   */
                    float* qa, float* qb, float* qc, int q_lo, int q_n, void* stream);   /* S1/S2 replicated as above */
+/* Frozen (eval-mode) form of cx_bn_bwd_coef: BatchNorm with the running statistics m = running_mean, r = 1/sqrt(running_var+eps)
+ * has dx = gamma*r*dy and no batch-statistic terms.  S1 = sum dy and S2 = sum dy*(x-mean)*rstd were reduced by the producer
+ * against the basis (mean, rstd) it read, which may differ from (m, r) (a dense-block channel's consumers share one basis):
+ *   dgamma += S2*(r/rstd) + r*(mean-m)*S1,  dbeta += S1;
+ *   pa = gamma*r, pb = pc = 0 (if pa is non-NULL);  qa/qb/qc of channels [q_lo, q_lo+q_n) = 1, 0, 0 (if qa is non-NULL).
+ * gamma may be NULL (1).  Deterministic: the rows are summed in a fixed order, no atomics.                                      */
+int cx_bn_bwd_coef_eval(const float* S1, const float* S2, const float* mean, const float* rstd, const float* running_mean,
+                        const float* running_var, const float* gamma, float eps, float* dgamma, float* dbeta, float* pa, float* pb,
+                        float* pc, int C, int replicas, int rstride, float* qa, float* qb, float* qc, int q_lo, int q_n,
+                        void* stream);
 /* AFFINE2 vectors that apply the deferred correction to a gradient slice:
  *   dY_true = G*1 + x*(-r*Bc) + (mean*r*Bc - A)                                                   */
 int cx_bn_bwd_slice_coef(const float* A, const float* Bc, const float* mean, const float* rstd, float* pa,
