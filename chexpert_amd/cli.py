@@ -10,6 +10,9 @@
   --fused_optimizer     one-kernel optimiser on the flat parameter buffer; with --graph the whole step (forward, loss, backward,
                         optimiser, scheduler) is captured once as a hipGraph and replayed per minibatch
   --jitter              brightness / contrast jitter +-0.25 of the uint8 image on the GPU (the reference's `_data_aug` rows)
+  --affine              random rotation / translation / scale / shear of the uint8 image on the GPU (training only; it runs before
+                        --jitter: geometric first, photometric second), ranges as torchvision's RandomAffine:
+                        --affine_degrees 10, --affine_translate 0.05, --affine_scale 0.9 1.1, --affine_shear 0
 
 Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N chexpert.py --train ...`; every rank holds a
 replica and a shard of each minibatch stream (per-rank BatchNorm statistics, averaged gradients: DDP semantics), the
@@ -65,6 +68,11 @@ def build_parser():
     p.add_argument("--fused_optimizer", action="store_true", help="one-kernel optimiser on the flat parameter buffer")
     p.add_argument("--graph", action="store_true", help="capture the training step as a hipGraph (needs --fused_optimizer)")
     p.add_argument("--jitter", action="store_true", help="brightness / contrast jitter +-0.25 on the uint8 image (GPU)")
+    p.add_argument("--affine", action="store_true", help="random affine warp of the uint8 image (GPU, training only)")
+    p.add_argument("--affine_degrees", type=float, default=10.0, help="rotation uniform in +-degrees")
+    p.add_argument("--affine_translate", type=float, default=0.05, help="translation uniform in +-fraction of the image size, per axis")
+    p.add_argument("--affine_scale", type=float, nargs=2, default=[0.9, 1.1], metavar=("LO", "HI"), help="scale uniform in [LO, HI]")
+    p.add_argument("--affine_shear", type=float, default=0.0, help="shear along x uniform in +-degrees")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -95,6 +103,15 @@ def batches(ds, indices, batch_size, drop_last):
             return
         items = [ds[i] for i in idx]
         yield torch.stack([it[0] for it in items]), torch.stack([it[1] for it in items]), torch.tensor(idx)
+
+
+def make_affine(args, rank, device):
+    """The geometric augmentation of the training loop (chexpert_amd/augment.py), or None: only --train with --affine warps --
+    validation, --evaluate and --visualize see the images as the loader decoded them."""
+    if not (args.affine and args.train):
+        return None
+    from .augment import RandomAffine
+    return RandomAffine(args.affine_degrees, args.affine_translate, args.affine_scale, args.affine_shear, rank, device)
 
 
 def make_model(args, device):
@@ -303,6 +320,7 @@ def main(argv=None):
         return ops.u8_jitter(x_u8, (0.75 + 0.5 * u[0]).to(device), (0.75 + 0.5 * u[1]).to(device),
                              (u[2] > 0.5).to(torch.int32).to(device))
 
+    affine = make_affine(args, rank, device)
     if args.train:
         fused = args.fused_optimizer
         gstep = None
@@ -320,6 +338,8 @@ def main(argv=None):
             # partial minibatch runs as an eager step (the hipGraph is captured on the full batch's shapes)
             for x, t, _ in train_loader.batches(idx, drop_last=False):
                 args.step += 1
+                if affine is not None:                      # geometric first, photometric second
+                    x = affine(x, args.step)
                 if args.jitter:
                     x = jitter(x, args.step)
                 if args.graph and fused and (gstep is not None or x.shape[0] == args.batch_size):

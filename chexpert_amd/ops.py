@@ -403,6 +403,20 @@ def u8_jitter(x, brightness, contrast, order, out=None):
     return out
 
 
+def u8_affine(x, mat, fill=0, out=None):
+    """Random-affine warp of decoded grey bytes (B,1,H,W) / (B,H,W) uint8 on the GPU (cx_u8_affine: bilinear, taps outside the image
+    read `fill`); mat: fp32 (B,6) inverse maps in pixel units about the image centre (chexpert_amd.augment.affine_matrices)."""
+    require_cuda(x, mat, out)
+    assert x.dtype == torch.uint8 and x.is_contiguous() and x.dim() in (3, 4) and (x.dim() == 3 or x.shape[1] == 1)
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    assert mat.dtype == torch.float32 and mat.is_contiguous() and tuple(mat.shape) == (B, 6)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.uint8 and out.shape == x.shape and out.is_contiguous()
+    check(lib().cx_u8_affine(ptr(x), ptr(out), B, H, W, ptr(mat), int(fill), stream_ptr()), "cx_u8_affine")
+    return out
+
+
 def nchw3_to_nhwc4(x, out=None):
     require_cuda(x)
     B, Cc, H, W = x.shape

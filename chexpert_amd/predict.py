@@ -3,7 +3,10 @@
 the eval-mode HIP path of chexpert_amd.models; reading / cropping is chexpert_amd.data (mode 'test').
 
   python predict.py <data.csv> <predictions.csv> --restore_path <checkpoint.pt | folder> [--model densenet121|resnet152]
-                    [--batch_size 16] [--resize N] [--mini_data N] [--cuda 0]
+                    [--batch_size 16] [--resize N] [--mini_data N] [--cuda 0] [--tta K]
+
+--tta K averages the probabilities of K forwards per image: the image as decoded, and K - 1 random affine warps of it on the GPU
+(chexpert_amd/augment.py, cx_u8_affine).
 """
 import argparse
 import os
@@ -23,20 +26,41 @@ def build_parser():
     p.add_argument("--batch_size", type=int, default=16)
     p.add_argument("--resize", type=int)
     p.add_argument("--mini_data", type=int)
+    p.add_argument("--tta", type=int, default=1, help="test-time augmentation: mean probability over K forwards (the image + K-1 affine warps)")
+    p.add_argument("--tta_seed", type=int, default=0)
     return p
 
 
 @torch.no_grad()
-def predict(model, dataset, batch_size, device):
-    """DataFrame indexed by study ('.../patient64541/study1') with one probability column per finding (predict.py:33-52)."""
+def predict(model, dataset, batch_size, device, tta=1, tta_seed=0):
+    """DataFrame indexed by study ('.../patient64541/study1') with one probability column per finding (predict.py:33-52).
+
+    tta = K > 1 (test-time augmentation): per image the mean of K sigmoid probabilities, then the max over a study's views as
+    before.  Draw 0 is the batch as decoded; draws 1 .. K-1 warp the uint8 batch with ops.u8_affine (fill 0) and matrices from
+    augment.affine_matrices at half the ranges of the training defaults -- rotation +-5 degrees, translation +-0.025 of the size,
+    scale 0.95 .. 1.05, no shear (augment.TTA_RANGES) -- seeded by augment.tta_seed_of(tta_seed, draw, number of the minibatch):
+    two calls agree bit for bit.  tta = 1 is the plain path."""
     import pandas as pd
     from .data import extract_patient_ids
+    if tta < 1:
+        raise ValueError("tta must be >= 1")
     model.eval()
     probs, studies = [], []
     for k in range(0, len(dataset), batch_size):
         items = [dataset[i] for i in range(k, min(k + batch_size, len(dataset)))]
         x = torch.stack([it[0] for it in items]).to(device)
-        probs.append(torch.sigmoid(model(x).float()).cpu())
+        if tta == 1:
+            probs.append(torch.sigmoid(model(x).float()).cpu())
+        else:
+            from . import augment, ops
+            if x.dtype != torch.uint8:
+                raise RuntimeError("test-time augmentation warps the decoded uint8 images (got %s)" % x.dtype)
+            p = torch.sigmoid(model(x).float())
+            for draw in range(1, tta):
+                mat = augment.affine_matrices(augment.tta_seed_of(tta_seed, draw, k // batch_size), x.shape[0], x.shape[-2], x.shape[-1],
+                                              **augment.TTA_RANGES)
+                p = p + torch.sigmoid(model(ops.u8_affine(x, mat.to(device))).float())
+            probs.append((p / tta).cpu())
         studies += list(extract_patient_ids(dataset, [it[2] for it in items]))
     df = pd.DataFrame(torch.cat(probs).numpy(), index=studies, columns=list(dataset.attr_names))
     df.index.name = "Study"
@@ -69,7 +93,7 @@ def main(argv=None):
     frames = []
     for f in files:
         model.load_state_dict(torch.load(f, map_location=device)["state_dict"])
-        frames.append(predict(model, ds, args.batch_size, device))
+        frames.append(predict(model, ds, args.batch_size, device, tta=args.tta, tta_seed=args.tta_seed))
     df = frames[0] if len(frames) == 1 else sum(frames[1:], frames[0]) / float(len(frames))      # mean over checkpoints
     df.to_csv(args.output_path)
     return df

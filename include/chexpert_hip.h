@@ -617,6 +617,16 @@ int cx_cam_norm_upsample(const float* cam, float* out, int B, int h, int w, int 
  * first) drawn by the caller.  HW % 16 == 0, HW <= 150 KiB (the image is parked in LDS between the two passes).               */
 int cx_u8_jitter(const uint8_t* x, uint8_t* y, int B, int HW, const float* brightness, const float* contrast, const int* order,
                  void* stream);
+/* Random-affine warp of the decoded grey images x, y: (B, H, W) uint8, distinct buffers (the geometric half of augmentation; the
+ * caller draws the matrices).  mat[b] is the INVERSE map of image b (output pixel -> source position), row-major 2x3, in pixel
+ * units about the image centre.  fp32 throughout, for output pixel (i, j):
+ *   xo = j + 0.5 - W/2, yo = i + 0.5 - H/2
+ *   u  = m0*xo + m1*yo + m2 + W/2 - 0.5,  v = m3*xo + m4*yo + m5 + H/2 - 0.5
+ *   u0 = floor(u), v0 = floor(v), fu = u - u0, fv = v - v0;  p(r, c) = x[b][r][c] inside the image, else `fill` (0..255)
+ *   top = p(v0,u0)*(1-fu) + p(v0,u0+1)*fu, bot likewise on row v0+1;  y[b][i][j] = uint8(floor(top*(1-fv) + bot*fv + 0.5))
+ * The identity (1,0,0, 0,1,0) returns x bit for bit.  One writer per output byte, no atomics: bit-reproducible.
+ * W % 4 == 0, H and W <= 1024, else CX_ESHAPE; y and mat 4-byte aligned.  Additive entry point of ABI 10 (no struct changed).   */
+int cx_u8_affine(const uint8_t* x, uint8_t* y, int B, int H, int W, const float* mat /* device, [B][6] */, int fill, void* stream);
 
 /* ---- fp32 storage mode (CX_DT_F32): the element-wise kernels of the DenseNet path with fp32 activation tensors (same arguments,
  * `const void*` tensors are fp32, pitches in elements), the fp32 weight table ([tap][O][I] fp32; descriptors with stem = 1 give
