@@ -5,8 +5,7 @@ Why: a DenseNet121 step is ~900 kernel launches; enqueued one by one through cty
 becomes the floor once the GPU side of the step is faster than that.  A replay costs ~10-20 us of host time (one
 `hipGraphLaunch`).  Shapes are static: the caller copies each minibatch into `x` / `target` (device tensors owned by this
 object) and calls `replay()`.  Learning rate and step count live in device memory (`optim._Flat.hyper`), so the optimiser and
-the scheduler advance inside the graph.  Two-stream sections of backward (weight gradients on the side stream) are captured
-as forks/joins of the graph.
+the scheduler advance inside the graph.
 """
 import torch
 

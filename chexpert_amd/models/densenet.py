@@ -17,12 +17,9 @@ as one schedule of fused kernels over NHWC bf16 buffers:
     share xhat, so they are accumulated as two per-channel coefficients and applied once by the
     channel's producer; the gradient buffer only receives gamma*rstd*dz contributions.
 """
-import contextlib
-import ctypes as C
-import math
+import os
 from collections import OrderedDict
 
-import os
 import torch
 import torch.nn as nn
 
@@ -260,10 +257,10 @@ class _Workspace:
         self.gbuf = [torch.empty_like(b) for b in self.buf]
         h, w = self.hw[0]
         self.dz2 = [torch.empty(B, h, w, eng.mid, dtype=bf, device=dev) for _ in range(2)]
-        # dense copies of the layers' corrected output-gradient slices (CxConv.pro_out of the 3x3 input-gradient kernel): one per
-        # layer, so that the weight-gradient kernels on the side stream never wait for -- or hold up -- the main chain
+        # dense copies of the layers' corrected output-gradient slices (CxConv.pro_out of the 3x3 input-gradient kernel, a bf16
+        # kernel): one per layer, a block's batched 3x3 weight gradient reads them all after the block's last layer
         self.dyc = None
-        if bf == torch.bfloat16 and os.environ.get("CHEXPERT_DENSE_DY", "1") != "0":
+        if bf == torch.bfloat16:
             self.dyc = [[torch.empty(B, hh, ww, eng.growth, dtype=bf, device=dev) for _ in range(nl)]
                         for (hh, ww), nl in zip(self.hw, eng.model.block_config)]
         if len(self.buf) > 1:
@@ -283,19 +280,28 @@ class _Engine(FusedEngine):
     SLAB = 1 << 22               # floats per half of the statistic-row scratch (rows x channels of the largest producer)
     EW_ROWS = 2048               # workgroups (= rows) of the element-wise statistic producers in deterministic mode
 
-    # statistics plumbing: producer kwargs / consumer (sum, sq, replicas, rstride) for the two modes
-    def _sp(self, ws, slots, C, sub=None):
+    # statistics plumbing for the two modes: keywords of a convolution producer (_sp), (sum, sq, stat_rows) of an element-wise
+    # producer (_ew), (sum, sq, replicas, rstride) for the consumer (_sc).  copies=False: atomic sums held once, not stat_replicas
+    # times (what the stem convolution and the element-wise kernels of backward add into)
+    def _sp(self, ws, slots, C, sub=None, copies=True):
         if self.det:
             return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // C, stat_rstride=C)
         a, b = slots
+        if not copies:
+            return dict(stat_sum=ws.v(a), stat_sq=ws.v(b))
         if sub is not None:
             a, b = (a[0] + sub[0], sub[1]), (b[0] + sub[0], sub[1])
         return dict(stat_sum=ws.v(a), stat_sq=ws.v(b), stat_replicas=self.stat_replicas, stat_rstride=slots[0][1])
 
-    def _sc(self, ws, slots, C, rows):
+    def _ew(self, ws, slots, C, rows=None):
+        if self.det:
+            return ws.slab[0], ws.slab[1], rows or min(self.EW_ROWS, self.SLAB // C)
+        return ws.v(slots[0]), ws.v(slots[1]), 0
+
+    def _sc(self, ws, slots, C, rows, copies=True):
         if self.det:
             return ws.slab[0], ws.slab[1], rows, C
-        return ws.v(slots[0]), ws.v(slots[1]), self.stat_replicas, slots[0][1]
+        return ws.v(slots[0]), ws.v(slots[1]), self.stat_replicas if copies else 1, slots[0][1] if copies else 0
 
     def __init__(self, model):
         super().__init__(model)
@@ -315,7 +321,6 @@ class _Engine(FusedEngine):
                 # DenseNet-BC rounds it up, and pads between the two branches of an attention-augmented transition)
                 c = getattr(f, "denseblock%d" % (len(self.blocks) + 1)).denselayer1.norm1.num_features
         self.c_final = c
-        self.side = None             # side stream for the weight-gradient kernels of the dense layers
         self.stat_replicas = 16      # legacy (atomic) statistics: copies of every conv-produced vector (memory-side contention)
         # Deterministic statistics: per-workgroup rows summed in a fixed order instead of fp32 atomics (bit-identical activations,
         # losses and gradients from run to run); CHEXPERT_DET=0 brings the atomics back.  The AA transitions feed a block's first
@@ -328,8 +333,7 @@ class _Engine(FusedEngine):
         # time, and the two extra small launches per pair give it back -- 27.27 vs 27.22 ms per step, interleaved A/B on one box,
         # profiles/r04_pair_bwd.txt), "1" where the kernels alone gain (see _backward), "all" wherever two layers remain (tests)
         self.pair_bwd = os.environ.get("CHEXPERT_PAIR_BWD", "0")
-        self.w2_batch = os.environ.get("CHEXPERT_W2_BATCH", "1") != "0"      # a block's 3x3 weight gradients in one launch (small maps)
-        self._w2_items = []
+        self._w2_items = []          # a block's 3x3 weight gradients, collected for one launch (_flush_w2)
         self._plan_vectors()
 
     # ---- coefficient-vector layout
@@ -354,8 +358,7 @@ class _Engine(FusedEngine):
         s["St"] = [[V.take(c + n * self.growth) for _ in range(2)] for c, n in self.blocks]
         s["AB"] = [[V.take(c + n * self.growth) for _ in range(2)] for c, n in self.blocks]
         self.bwd_zero = (b0, V.n - b0)
-        # per-layer AFFINE2 vectors (the weight-gradient kernels of layer l run on a side stream while the
-        # main stream already prepares layer l-1, so these cannot be shared scratch)
+        # per-layer AFFINE2 vectors (the two-layer pass of _pair_backward holds both its layers' norm2 vectors at once)
         s["ql"] = [[[V.take(self.growth) for _ in range(3)] for _ in range(n)] for _, n in self.blocks]
         s["pl"] = [[[V.take(self.mid) for _ in range(3)] for _ in range(n)] for _, n in self.blocks]
         s["q"] = [V.take(max(self.mid, self.c_init, max(c for c, _ in self.blocks))) for _ in range(3)]   # slice AFFINE2
@@ -441,36 +444,24 @@ class _Engine(FusedEngine):
         if train and not self.det:
             z0, zn = self.fwd_zero
             ws.vec[z0:z0 + zn].zero_()
-        sp = (lambda slots, C, sub=None: self._sp(ws, slots, C, sub)) if train else (lambda slots, C, sub=None: {})
+        sp = (lambda slots, C, sub=None, **k: self._sp(ws, slots, C, sub, **k)) if train else (lambda *a, **k: {})
+        ci = self.c_init
         if self.cifar:
             self._cifar_stem(ws, x, train, sp)
-            fresh = (ws.slab[0], ws.slab[1], self._stem_rows, self.c_init, 0, self.c_init) if det else None
-        elif u8:
-            ops.u8_to_nhwc4(x.contiguous(), ws.x4)
+            rows = self._stem_rows
         else:
-            ops.nchw3_to_nhwc4(x.contiguous().float(), ws.x4)
-        # stem: conv0 -> norm0 -> relu0 -> pool0 (attn_aug_conv.py:460-465)
-        if self.cifar:
-            pass
-        elif det:
-            rows = ops.conv_gemm(ws.x4, self.w_fwd(f.conv0), ws.c0, N=self.c_init, mode=ops.MODE_STEM, **sp(None, self.c_init))
-            st0 = (ws.slab[0], ws.slab[1], rows, self.c_init)
-        else:
-            ops.conv_gemm(ws.x4, self.w_fwd(f.conv0), ws.c0, N=self.c_init, mode=ops.MODE_STEM,
-                          stat_sum=ws.v(s["st0"][0]) if train else None, stat_sq=ws.v(s["st0"][1]) if train else None)
-            st0 = (ws.v(s["st0"][0]), ws.v(s["st0"][1]), 1, 0)
-        if not self.cifar:
-            self._bn(ws, st0, B * (H // 2) * (W // 2), f.norm0, s["n0"][:2], self.c_init, train, s["n0"][2], s["n0"][3])
-            fresh = None                         # (sum rows, sq rows, rows, rstride, first channel, channels) of the newest slice
-        if self.cifar:
-            pass
-        elif det:
-            rows = ops.bnrelu_maxpool_fwd(ws.c0, ws.v(s["n0"][0]), ws.v(s["n0"][1]), ws.buf[0][..., :self.c_init], ws.amax,
-                                          ws.slab[0], ws.slab[1], stat_rows=min(self.EW_ROWS, self.SLAB // self.c_init))
-            fresh = (ws.slab[0], ws.slab[1], rows, self.c_init, 0, self.c_init)
-        else:
-            ops.bnrelu_maxpool_fwd(ws.c0, ws.v(s["n0"][0]), ws.v(s["n0"][1]), ws.buf[0][..., :self.c_init], ws.amax,
-                                   ws.v(s["bst"][0][0]) if train else None, ws.v(s["bst"][0][1]) if train else None)
+            if u8:
+                ops.u8_to_nhwc4(x.contiguous(), ws.x4)
+            else:
+                ops.nchw3_to_nhwc4(x.contiguous().float(), ws.x4)
+            # stem: conv0 -> norm0 -> relu0 -> pool0 (attn_aug_conv.py:460-465)
+            rows = ops.conv_gemm(ws.x4, self.w_fwd(f.conv0), ws.c0, N=ci, mode=ops.MODE_STEM, **sp(s["st0"], ci, copies=False))
+            st0 = self._sc(ws, s["st0"], ci, rows, copies=False) if train else None
+            self._bn(ws, st0, B * (H // 2) * (W // 2), f.norm0, s["n0"][:2], ci, train, s["n0"][2], s["n0"][3])
+            rows = ops.bnrelu_maxpool_fwd(ws.c0, ws.v(s["n0"][0]), ws.v(s["n0"][1]), ws.buf[0][..., :ci], ws.amax,
+                                          *(self._ew(ws, s["bst"][0], ci) if train else (None, None, 0)))
+        # (sum rows, sq rows, rows, rstride, first channel, channels) of the newest slice
+        fresh = (ws.slab[0], ws.slab[1], rows, ci, 0, ci) if det else None
         nb = len(self.blocks)
         g_ = self.growth
         drop = train and self.drop_rate > 0
@@ -585,9 +576,11 @@ class _Engine(FusedEngine):
             ops.aa_outproj_fwd(T.O, aa.out_proj.weight, nxt[..., cc:cout], st((nsum[0] + cc, aa.dv)), st((nsq[0] + cc, aa.dv)))
         return fresh
 
-    def _aa_backward(self, ws, bi, aa, qa, qb, qc, G):
+    def _aa_backward(self, ws, bi, aa, done):
         """Backward of the AA transition feeding block bi (from block bi-1); qa/qb/qc apply the deferred BN correction
         to the gradient slice [0, c0) of block bi."""
+        G = self.grad_of
+        qa, qb, qc = self._slice_q(ws, bi, -1)[:3]            # written by layer 0's norm1 coefficient launch
         buf, gbuf, pbuf, pg, T = ws.buf[bi], ws.gbuf[bi], ws.buf[bi - 1], ws.gbuf[bi - 1], ws.aa[bi - 1]
         cc = aa.conv.out_channels
         c0 = cc + aa.dv                          # (the block's entry width in the reference's networks; the padded twin's is wider)
@@ -608,328 +601,256 @@ class _Engine(FusedEngine):
         ops.conv_wgrad(gs_c, T.A, G(aa.conv.weight), kh=3, kw=3, stride=2, pad=1, g_prologue=ops.PRO_AFFINE2, g2=xs_c, ga=qa[:cc],
                        gb=qb[:cc], gc=qc[:cc])
         ops.in_relu_bwd(T.dA, pbuf, T.coef[0], T.coef[1], T.S[0], T.S[1], pg)       # S: one owner per (image, channel), plain stores
+        done(aa.first_param())
 
     def _flush_w2(self):
         """Launch the collected 3x3 weight gradients of the current block (one batched launch per 24 layers; per layer when the
         library declines the shape or the slab workspace)."""
         items, self._w2_items = self._w2_items, []
-        if not items:
-            return
-        # CHEXPERT_W2_SIDE=1 (experiment): the batch on the side stream, beside the next block's input-gradient chain; backward joins
-        # the streams at its end (the reducer-driven flush stays on the main stream: the bucket must be final)
-        side = self.side if (os.environ.get("CHEXPERT_W2_SIDE", "0") == "1" and self.reducer is None and self.side is not None) else None
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-        ctx = torch.cuda.stream(side) if side is not None else contextlib.nullcontext()
-        with ctx:
-            for i in range(0, len(items), ops.L.WGRAD_BATCH_MAX):
-                part = items[i:i + ops.L.WGRAD_BATCH_MAX]
-                if not ops.conv3x3_wgrad_batch(part):
-                    for dyc, y1, pa, pb, dw in part:
-                        ops.conv_wgrad(dyc, y1, dw, kh=3, kw=3, pad=1, x_prologue=ops.PRO_AFFINE_RELU, pa=pa, pb=pb)
+        for i in range(0, len(items), ops.L.WGRAD_BATCH_MAX):
+            part = items[i:i + ops.L.WGRAD_BATCH_MAX]
+            if not ops.conv3x3_wgrad_batch(part):
+                for dyc, y1, pa, pb, dw in part:
+                    ops.conv_wgrad(dyc, y1, dw, kh=3, kw=3, pad=1, x_prologue=ops.PRO_AFFINE_RELU, pa=pa, pb=pb)
 
     # ---- backward
-    def _defer_wgrad(self):
-        return os.environ.get("CHEXPERT_WGRAD_DEFER", "1") != "0"
-
     def _backward(self, ws, dlogits, dx, done):
+        """Head, then the blocks from last to first: a block's layers from last to first, its batched 3x3 weight gradients, its
+        entry (transition or stem).  Everything is issued on the current stream.  The weight-gradient kernels only feed the flat
+        gradient buffer, but beside the input-gradient chain on a second stream they were no faster (30.37 vs 30.31 ms per step,
+        interleaved A/B on one box), and on one stream each 3x3 weight gradient reads the DENSE corrected slice its own layer's
+        input-gradient kernel leaves behind (CxConv.pro_out: 30.0 ms)."""
         self._w2_items = []
-        m, f, s = self.model, self.model.features, self.slots
-        B = ws.B
-        dev = self.device
-        ws.alloc_backward(self, dev)
+        ws.alloc_backward(self, self.device)
         z0, zn = self.bwd_zero
         ws.vec[z0:z0 + zn].zero_()
-        nb = len(self.blocks)
-        G = self.grad_of
-        v = ws.v
-        red = self.reducer
-        # head
-        bi = nb - 1
-        c0, n_layers = self.blocks[bi]
-        ct = c0 + n_layers * self.growth
-        nt, (bmean, brstd), (A, Bc) = s["nt"][bi], s["bmr"][bi], s["AB"][bi]
-        dpooled = torch.empty(B, ct, dtype=torch.float32, device=dev)
-        ops.head_bwd(dlogits, ws.pooled, m.classifier.weight, G(m.classifier.weight), G(m.classifier.bias) if
-                     m.classifier.bias is not None else None, dpooled)
-        St = s["St"][bi]
-        det = self.det
-        ew_rows = lambda C: min(self.EW_ROWS, self.SLAB // C)
-        if det:
-            if B * ct > self.SLAB:
-                raise RuntimeError("batch too large for the statistic-row scratch (B*C = %d > %d)" % (B * ct, self.SLAB))
-            rows = ops.gap_relu_bn_bwd(dpooled, ws.buf[bi], v(nt[0]), v(nt[1]), v(bmean), v(brstd), v(nt[0]), ws.gbuf[bi], ws.slab[0],
-                                       ws.slab[1], stat_rows=self.SLAB // ct)
-            sred = (ws.slab[0], ws.slab[1], rows, ct)
-        else:
-            ops.gap_relu_bn_bwd(dpooled, ws.buf[bi], v(nt[0]), v(nt[1]), v(bmean), v(brstd), v(nt[0]), ws.gbuf[bi], v(St[0]),
-                                v(St[1]))
-            sred = (v(St[0]), v(St[1]), 1, 0)
-        h, w = ws.hw[bi]
-        g_ = self.growth
-
-        def slice_q(bi_, li_):
-            """(qa, qb, qc, first channel, channels) of the slice layer li_ of block bi_ produced (li_ = -1: the block's first
-            c0 channels): emitted by the coefficient kernel of the slice's LAST consumer, whose A / B update completes them."""
-            c0_, _ = self.blocks[bi_]
-            if li_ < 0:
-                return tuple(v(t)[:c0_] for t in s["q"]) + (0, c0_)
-            return tuple(v(t) for t in s["ql"][bi_][li_]) + (c0_ + li_ * g_, g_)
-        self.bn_bwd_coef(ws, f.norm5, sred[0], sred[1], B * h * w, f.norm5.weight, v(bmean), v(brstd), G(f.norm5.weight), G(f.norm5.bias),
-                         v(A), v(Bc), None, None, None, ct, replicas=sred[2], rstride=sred[3], q=slice_q(bi, n_layers - 1))
-        q, pv = s["q"], s["p"]
-        # The 3x3 weight-gradient kernels only feed the flat gradient buffer.  Rounds 1-2 ran them on a side stream beside the
-        # input-gradient chain (CHEXPERT_SERIAL_WGRAD=0 still does); since the slab sums are deferred and the fused 1x1 backward
-        # runs near the copy rate, one stream is as fast (30.31 vs 30.37 ms, interleaved A/B on one box) and lets the weight
-        # gradient read the DENSE corrected slice its own layer's input-gradient kernel leaves behind (CxConv.pro_out:
-        # 30.0 ms) -- on two streams that dependency pushes it beside the bandwidth-bound 1x1 backward and costs 0.5 ms.
-        main = torch.cuda.current_stream()
-        if self.side is None:
-            self.side = torch.cuda.Stream(device=dev)
-        side = main if os.environ.get("CHEXPERT_SERIAL_WGRAD", "1") == "1" else self.side
-        side.wait_stream(main)
-        w1_done = {}
-        k = 0
-        for bi in range(nb - 1, -1, -1):
+        self._head_backward(ws, dlogits)
+        # input gradient + weight gradient of conv1 in one pass over dz2 / y1 / the buffer slice (conv1x1_bwd.hip: 6-37 % less kernel
+        # time than the two separate kernels, whole step 37.6 vs 39.0 ms): a bf16 kernel for 128 bottleneck channels -- the fp32
+        # parity mode and the channel-padded CIFAR twin run the two kernels one after the other
+        fused = self.dtype == torch.bfloat16 and self.mid == 128
+        k = 0                                # the dz2 buffers alternate (the two-layer pass holds both)
+        for bi in range(len(self.blocks) - 1, -1, -1):
             c0, n_layers = self.blocks[bi]
-            buf, gbuf = ws.buf[bi], ws.gbuf[bi]
             h, w = ws.hw[bi]
-            cnt = B * h * w
-            (bmean, brstd), (A, Bc) = s["bmr"][bi], s["AB"][bi]
-            block = getattr(f, "denseblock%d" % (bi + 1))
-            dz2s = [d.view(-1)[:B * h * w * self.mid].view(B, h, w, self.mid) for d in ws.dz2]
-            sub = lambda slot, a, n: (slot[0] + a, n)
-            if bi != nb - 1 and isinstance(getattr(f, "transition%d" % (bi + 1)).conv, AAConv2d):
-                # an AA transition normalises per instance (its backward is complete in cx_in_relu_bwd): no BatchNorm consumer
-                # follows the block, so nobody has emitted the slice coefficients of its last layer -- A = B = 0 there
-                cl = c0 + (n_layers - 1) * self.growth
-                ops.bn_bwd_slice_coef(v(sub(A, cl, self.growth)), v(sub(Bc, cl, self.growth)), v(sub(bmean, cl, self.growth)),
-                                      v(sub(brstd, cl, self.growth)), *(v(t) for t in s["ql"][bi][n_layers - 1]), self.growth)
-            w2_pending = None
-            dense_dy_lag = os.environ.get("CHEXPERT_DENSE_DY", "1") == "2" and red is None     # (a reducer needs every gradient of a layer enqueued before done())
-            # (the maps the strip weight-gradient kernel serves: 40x40 and smaller at 320x320; the 80x80 maps keep the ring kernel)
-            batch_w2 = (self.w2_batch and side is main and self.dtype == torch.bfloat16 and self.growth == 32 and self.mid == 128
-                        and (w < 56 or h * w < 3136))
-            fused = os.environ.get("CHEXPERT_1X1_BWD", "fused") != "split" and self.dtype == torch.bfloat16 and self.mid == 128
+            cnt = ws.B * h * w
+            dz2s = [d.view(-1)[:cnt * self.mid].view(ws.B, h, w, self.mid) for d in ws.dz2]
+            if self._aa_transition(bi + 1) is not None:
+                self._last_slice_coef(ws, bi)
+            # a block's 3x3 weight gradients leave the input-gradient chain and run as ONE launch after the block
+            # (cx_conv3x3_wgrad_batch) on the maps the strip weight-gradient kernel serves: 40x40 and smaller at 320x320; the 80x80
+            # maps keep the ring kernel, layer by layer
+            batch_w2 = fused and self.growth == 32 and (w < 56 or h * w < 3136)
             # two layers per pass over the channels both read (cx_conv1x1_dgrad_wgrad_pair_ws), where the x / dX traffic it saves
             # outweighs the second read of the later layer's dZ by its 32-channel slice launch (measured crossover at B = 256:
             # >= 288 shared channels on the 40x40 maps, >= 736 on the 20x20 maps, never on 10x10; scratch/bench_pair.py)
             pair_min = 1 << 30
-            if self.pair_bwd != "0" and fused and side is main and self.growth == 32 and not dense_dy_lag and not self.drop_rate:
+            if self.pair_bwd != "0" and fused and self.growth == 32 and not self.drop_rate:
                 pair_min = 0 if self.pair_bwd == "all" else 288 if cnt >= 300000 else 736 if cnt >= 80000 else 1 << 30
-            li = n_layers
-            while li > 0:
-                li -= 1
-                layer = getattr(block, "denselayer%d" % (li + 1))
-                cin = c0 + li * self.growth
-                g_ = self.growth
-                if li >= 1 and cin - g_ >= pair_min:
-                    self._pair_backward(ws, bi, li, dz2s[k & 1], dz2s[(k + 1) & 1], slice_q, done)
-                    k += 2
-                    li -= 1
+            li = n_layers - 1
+            while li >= 0:
+                if li >= 1 and c0 + (li - 1) * self.growth >= pair_min:
+                    self._pair_backward(ws, bi, li, dz2s[k & 1], dz2s[(k + 1) & 1], batch_w2, done)
+                    k, li = k + 2, li - 2
                     continue
-                n1, n2 = s["n1"][bi][li], s["n2"][bi][li]
-                y1 = ws.y1[bi][li]
-                qa, qb, qc = (v(t) for t in s["ql"][bi][li])      # written by the previous coefficient launch (slice_q)
-                ev_q = torch.cuda.Event()
-                ev_q.record(main)
-                gs, xs = gbuf[..., cin:cin + g_], buf[..., cin:cin + g_]
-                S2 = s["S2"][bi][li]
                 dz2 = dz2s[k & 1]
-                if k - 2 in w1_done:
-                    # split mode: the side stream's conv1 weight gradient of two layers ago has finished reading this dz2 buffer.
-                    # (In the fused mode nothing on the side stream reads dz2: no cross-stream edge on the main chain -- in the
-                    # replayed graph each such edge was a ~10 us stall of the main queue, 58 per step)
-                    ev_ = w1_done.pop(k - 2)
-                    if not fused:
-                        main.wait_event(ev_)
-                dyc = ws.dyc[bi][li] if ws.dyc is not None else None
-                if self.drop_rate > 0 and not ws.frozen:         # (eval mode: no dropout in the forward)
-                    # the slice's deferred BatchNorm correction and the forward's keep decisions, in place on the gradient slice;
-                    # the kernels below then read it with identity coefficients
-                    ops.dropout_slice_bwd(gs, xs, qa, qb, qc, self.drop_rate, self.drop_seed, bi * 256 + li)
-                    qa, qb, qc = ws.ones[:g_], ws.zeros[:g_], ws.zeros[:g_]
-                    # the side stream's conv2 weight gradient reads `gs` AFTER this in-place rewrite: the event it waits on is taken
-                    # here, not before it (a separate side stream -- CHEXPERT_SERIAL_WGRAD=0 -- could otherwise read the slice
-                    # before or while it is rewritten)
-                    ev_q = torch.cuda.Event()
-                    ev_q.record(main)
-                rows = ops.conv_gemm(gs, self.w_bwd(layer.conv2), dz2, N=self.mid, kh=3, kw=3, pad=1, prologue=ops.PRO_AFFINE2, x2=xs,
-                                     pa=qa, pb=qb, pc=qc, epilogue=ops.EPI_MASK, ex=y1, e_sc=v(n2[0]), e_sh=v(n2[1]), e_mu=v(n2[2]),
-                                     e_r=v(n2[3]), e_scale=ws.ones[:self.mid], pro_out=dyc, **self._sp(ws, S2, self.mid))
-                red2 = self._sc(ws, S2, self.mid, rows)
-                if dyc is not None and ops.last_pro_out():
-                    # the input-gradient kernel left the corrected slice as a dense (M, 32) tensor: the weight gradient reads 64
-                    # contiguous bytes per pixel instead of two 64-byte pieces of the block buffers' rows (half of every line wasted)
-                    def w2_launch(dyc=dyc, y1=y1, wgt=layer.conv2.weight, n2=n2):
-                        with torch.cuda.stream(side):
-                            ops.conv_wgrad(dyc, y1, G(wgt), kh=3, kw=3, pad=1, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]), pb=v(n2[1]))
-                    if batch_w2:
-                        # small maps: the block's 3x3 weight gradients leave the input-gradient chain and run as ONE launch after
-                        # the block (cx_conv3x3_wgrad_batch); a data-parallel run flushes them before a gradient bucket leaves
-                        self._w2_items.append((dyc, y1, v(n2[0]), v(n2[1]), G(layer.conv2.weight)))
-                    elif dense_dy_lag:
-                        # one layer behind: it then runs beside the NEXT layer's 3x3 input gradient (as the strided form does beside
-                        # its own), not beside the bandwidth-bound fused 1x1 backward
-                        if w2_pending is not None:
-                            side.wait_event(ev_q)
-                            w2_pending()
-                        w2_pending = w2_launch
-                    else:
-                        ev_d = torch.cuda.Event()
-                        ev_d.record(main)
-                        side.wait_event(ev_d)
-                        w2_launch()
-                else:
-                    side.wait_event(ev_q)
-                    with torch.cuda.stream(side):
-                        ops.conv_wgrad(gs, y1, G(layer.conv2.weight), kh=3, kw=3, pad=1, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa,
-                                       gb=qb, gc=qc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]), pb=v(n2[1]))
-                pa, pb, pc = (v(t) for t in s["pl"][bi][li])
-                self.bn_bwd_coef(ws, layer.norm2, red2[0], red2[1], cnt, layer.norm2.weight, v(n2[2]), v(n2[3]), G(layer.norm2.weight),
-                                 G(layer.norm2.bias), None, None, pa, pb, pc, self.mid, replicas=red2[2], rstride=red2[3])
-                if not fused:
-                    ev_p = torch.cuda.Event()
-                    ev_p.record(main)
-                S1 = s["S1"][bi][li]
-                # input gradient + weight gradient of conv1 in one pass over dz2 / y1 / the buffer slice (conv1x1_bwd.hip);
-                # (6-37 % less kernel time than the two separate kernels; whole step 37.6 vs 39.0 ms);
-                # CHEXPERT_1X1_BWD=split keeps them, with the weight gradient on the side stream
-                rows = ops.conv_gemm(dz2, self.w_bwd(layer.conv1), gbuf[..., :cin], N=cin, prologue=ops.PRO_AFFINE2, x2=y1, pa=pa,
-                                     pb=pb, pc=pc, epilogue=ops.EPI_MASK, ex=buf[..., :cin], e_sc=v(n1[0]), e_sh=v(n1[1]),
-                                     e_mu=v(bmean)[:cin], e_r=v(brstd)[:cin], e_scale=v(n1[0]), accumulate=True,
-                                     fused_dw=G(layer.conv1.weight) if fused else None, **self._sp(ws, S1, cin))
-                red1 = self._sc(ws, S1, cin, rows)
-                if not fused:
-                    side.wait_event(ev_p)
-                    with torch.cuda.stream(side):
-                        ops.conv_wgrad(dz2, buf[..., :cin], G(layer.conv1.weight), g_prologue=ops.PRO_AFFINE2, g2=y1, ga=pa, gb=pb,
-                                       gc=pc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n1[0]), pb=v(n1[1]))
-                if not fused or red is not None:
-                    w1_done[k] = torch.cuda.Event()
-                    w1_done[k].record(side)
-                self.bn_bwd_coef(ws, layer.norm1, red1[0], red1[1], cnt, layer.norm1.weight, v(bmean), v(brstd), G(layer.norm1.weight),
-                                 G(layer.norm1.bias), v(A), v(Bc), None, None, None, cin, replicas=red1[2], rstride=red1[3],
-                                 q=slice_q(bi, li - 1))
-                if red is not None:
-                    main.wait_event(w1_done[k])
-                k += 1
-                done(layer.norm1.weight)      # every gradient from this layer to the end of the buffer is final
-            if w2_pending is not None:
-                ev_d = torch.cuda.Event()
-                ev_d.record(main)
-                side.wait_event(ev_d)
-                w2_pending()
+                self._layer_conv1(ws, bi, li, dz2, self._layer_front(ws, bi, li, dz2, batch_w2), fused, done)
+                k, li = k + 1, li - 1
             self._flush_w2()
             # the block's first c0 channels were produced by the previous transition (or the stem)
-            qa, qb, qc = (v(t)[:c0] for t in q)               # written by layer 0's norm1 coefficient launch
-            gs, xs = gbuf[..., :c0], buf[..., :c0]
-            if bi > 0 and isinstance(getattr(f, "transition%d" % bi).conv, AAConv2d):
-                aa = getattr(f, "transition%d" % bi).conv
-                self._aa_backward(ws, bi, aa, qa, qb, qc, G)
-                done(aa.first_param())
+            aa = self._aa_transition(bi)
+            if aa is not None:
+                self._aa_backward(ws, bi, aa, done)
             elif bi > 0:
-                pc0, pn = self.blocks[bi - 1]
-                cprev = pc0 + pn * self.growth
-                tr = getattr(f, "transition%d" % bi)
-                pbuf, pg = ws.buf[bi - 1], ws.gbuf[bi - 1]
-                ph, pw = ws.hw[bi - 1]
-                nt, (pmean, prstd), (pA, pB), St = s["nt"][bi - 1], s["bmr"][bi - 1], s["AB"][bi - 1], s["St"][bi - 1]
-                dpool = ws.dpool[:B * h * w * cprev].view(B, h, w, cprev)
-                ops.conv_gemm(gs, self.w_bwd(tr.conv), dpool, N=cprev, prologue=ops.PRO_AFFINE2, x2=xs, pa=qa, pb=qb, pc=qc)
-                if det:
-                    rows = ops.unpool2_mask(dpool, pbuf, v(nt[0]), v(nt[1]), v(pmean), v(prstd), v(nt[0]), pg, ws.slab[0], ws.slab[1],
-                                            stat_rows=ew_rows(cprev))
-                    sred = (ws.slab[0], ws.slab[1], rows, cprev)
-                else:
-                    ops.unpool2_mask(dpool, pbuf, v(nt[0]), v(nt[1]), v(pmean), v(prstd), v(nt[0]), pg, v(St[0]), v(St[1]))
-                    sred = (v(St[0]), v(St[1]), 1, 0)
-                ops.conv_wgrad(gs, pbuf, G(tr.conv.weight), mode=ops.MODE_POOL2, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa, gb=qb,
-                               gc=qc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(nt[0]), pb=v(nt[1]))
-                self.bn_bwd_coef(ws, tr.norm, sred[0], sred[1], B * ph * pw, tr.norm.weight, v(pmean), v(prstd), G(tr.norm.weight),
-                                 G(tr.norm.bias), v(pA), v(pB), None, None, None, cprev, replicas=sred[2], rstride=sred[3],
-                                 q=slice_q(bi - 1, pn - 1))
-                done(tr.norm.weight)
+                self._transition_backward(ws, bi, done)
             elif self.cifar:
-                # stem backward of the CIFAR form: relu0 mask + norm0 sums in the mask epilogue of the identity convolution (its
-                # two-tensor prologue applies the deferred BatchNorm correction to the gradient slice), then conv0's weight gradient
-                n0, S0 = s["n0"], s["S0"]
-                ci = self.c_init
-                rows = ops.conv_gemm(gs, self.eye, ws.dz0, N=ci, prologue=ops.PRO_AFFINE2, x2=xs, pa=qa, pb=qb, pc=qc,
-                                     epilogue=ops.EPI_MASK, ex=ws.c0, e_sc=v(n0[0]), e_sh=v(n0[1]), e_mu=v(n0[2]), e_r=v(n0[3]),
-                                     e_scale=ws.ones[:ci], **self._sp(ws, S0, ci))
-                sred = self._sc(ws, S0, ci, rows)
-                pa, pb, pc = (v(t)[:ci] for t in pv)
-                self.bn_bwd_coef(ws, f.norm0, sred[0], sred[1], B * ws.H * ws.W, f.norm0.weight, v(n0[2]), v(n0[3]), G(f.norm0.weight),
-                                 G(f.norm0.bias), None, None, pa, pb, pc, ci, replicas=sred[2], rstride=sred[3])
-                ops.conv_wgrad(ws.dz0, ws.x8, G(f.conv0.weight), kh=5, kw=5, pad=2, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=pa, gb=pb,
-                               gc=pc)
-                if dx is not None:
-                    ops.stem_input_grad(ws.dz0, ws.c0, pa, pb, pc, f.conv0.weight, dx, stride=1, pad=2)
+                self._cifar_stem_backward(ws, dx)
             else:
-                n0, S0 = s["n0"], s["S0"]
-                if det:
-                    rows = ops.bnrelu_maxpool_bwd(ws.c0, v(n0[0]), v(n0[1]), v(n0[2]), v(n0[3]), ws.amax, gs, xs, qa, qb, qc, ws.dz0,
-                                                  ws.slab[0], ws.slab[1], stat_rows=ew_rows(self.c_init))
-                    sred = (ws.slab[0], ws.slab[1], rows, self.c_init)
-                else:
-                    ops.bnrelu_maxpool_bwd(ws.c0, v(n0[0]), v(n0[1]), v(n0[2]), v(n0[3]), ws.amax, gs, xs, qa, qb, qc, ws.dz0,
-                                           v(S0[0]), v(S0[1]))
-                    sred = (v(S0[0]), v(S0[1]), 1, 0)
-                pa, pb, pc = (v(t)[:self.c_init] for t in pv)
-                self.bn_bwd_coef(ws, f.norm0, sred[0], sred[1], B * (ws.H // 2) * (ws.W // 2), f.norm0.weight, v(n0[2]), v(n0[3]),
-                                 G(f.norm0.weight), G(f.norm0.bias), None, None, pa, pb, pc, self.c_init, replicas=sred[2],
-                                 rstride=sred[3])
-                ops.conv_wgrad(ws.dz0, ws.x4, G(f.conv0.weight), mode=ops.MODE_STEM, g_prologue=ops.PRO_AFFINE2, g2=ws.c0,
-                               ga=pa, gb=pb, gc=pc)
-                if dx is not None:
-                    ops.stem_input_grad(ws.dz0, ws.c0, pa, pb, pc, f.conv0.weight, dx, stride=2, pad=3)
-        main.wait_stream(side)
-        if side is main and os.environ.get("CHEXPERT_W2_SIDE", "0") == "1":
-            main.wait_stream(self.side)
+                self._stem_backward(ws, dx)
 
-    def _pair_backward(self, ws, bi, li, dz2_a, dz2_b, slice_q, done):
+    def _aa_transition(self, t):
+        """The AAConv2d of transition t (the one that feeds block t, 0-based); None for a BatchNorm transition, the stem (t = 0) and
+        the head (t = number of blocks)."""
+        tr = getattr(self.model.features, "transition%d" % t, None)
+        return tr.conv if tr is not None and isinstance(tr.conv, AAConv2d) else None
+
+    def _layer(self, bi, li):
+        return getattr(getattr(self.model.features, "denseblock%d" % (bi + 1)), "denselayer%d" % (li + 1))
+
+    def _slice_q(self, ws, bi, li):
+        """(qa, qb, qc, first channel, channels) of the slice layer li of block bi produced (li = -1: the block's first c0
+        channels): emitted by the coefficient kernel of the slice's LAST consumer, whose A / B update completes them."""
+        c0, _ = self.blocks[bi]
+        if li < 0:
+            return tuple(ws.v(t)[:c0] for t in self.slots["q"]) + (0, c0)
+        return tuple(ws.v(t) for t in self.slots["ql"][bi][li]) + (c0 + li * self.growth, self.growth)
+
+    def _head_backward(self, ws, dlogits):
+        """classifier -> global average pool -> ReLU -> norm5, into the last block's gradient buffer."""
+        m, f, s, v, G = self.model, self.model.features, self.slots, ws.v, self.grad_of
+        bi = len(self.blocks) - 1
+        c0, n_layers = self.blocks[bi]
+        ct = c0 + n_layers * self.growth
+        nt, (bmean, brstd), (A, Bc), St = s["nt"][bi], s["bmr"][bi], s["AB"][bi], s["St"][bi]
+        B = ws.B
+        h, w = ws.hw[bi]
+        dpooled = torch.empty(B, ct, dtype=torch.float32, device=self.device)
+        ops.head_bwd(dlogits, ws.pooled, m.classifier.weight, G(m.classifier.weight), G(m.classifier.bias) if
+                     m.classifier.bias is not None else None, dpooled)
+        if self.det and B * ct > self.SLAB:
+            raise RuntimeError("batch too large for the statistic-row scratch (B*C = %d > %d)" % (B * ct, self.SLAB))
+        rows = ops.gap_relu_bn_bwd(dpooled, ws.buf[bi], v(nt[0]), v(nt[1]), v(bmean), v(brstd), v(nt[0]), ws.gbuf[bi],
+                                   *self._ew(ws, St, ct, self.SLAB // ct))
+        sred = self._sc(ws, St, ct, rows, copies=False)
+        self.bn_bwd_coef(ws, f.norm5, sred[0], sred[1], B * h * w, f.norm5.weight, v(bmean), v(brstd), G(f.norm5.weight), G(f.norm5.bias),
+                         v(A), v(Bc), None, None, None, ct, replicas=sred[2], rstride=sred[3], q=self._slice_q(ws, bi, n_layers - 1))
+
+    def _last_slice_coef(self, ws, bi):
+        """Block bi feeds an AA transition, which normalises per instance (its backward is complete in cx_in_relu_bwd): no BatchNorm
+        consumer follows the block, so nobody has emitted the slice coefficients of its last layer -- A = B = 0 there."""
+        s, g_ = self.slots, self.growth
+        c0, n_layers = self.blocks[bi]
+        cl = c0 + (n_layers - 1) * g_
+        (bmean, brstd), (A, Bc) = s["bmr"][bi], s["AB"][bi]
+        ops.bn_bwd_slice_coef(*(ws.v((t[0] + cl, g_)) for t in (A, Bc, bmean, brstd)), *(ws.v(t) for t in s["ql"][bi][n_layers - 1]), g_)
+
+    def _layer_front(self, ws, bi, li, dz2, batch_w2):
+        """Layer li of block bi from its gradient slice down to dz2, the gradient at norm2's output: (the dropout backward,) the 3x3
+        input gradient with relu2's mask and norm2's sums in its epilogue, the 3x3 weight gradient -- queued for the block's batched
+        launch when batch_w2 --, norm2's coefficients.  Returns (pa, pb, pc), which apply norm2's correction to dz2."""
+        s, v, G, g_ = self.slots, ws.v, self.grad_of, self.growth
+        layer = self._layer(bi, li)
+        h, w = ws.hw[bi]
+        cin = self.blocks[bi][0] + li * g_
+        n2, y1, S2 = s["n2"][bi][li], ws.y1[bi][li], s["S2"][bi][li]
+        qa, qb, qc = (v(t) for t in s["ql"][bi][li])      # written by the previous coefficient launch (_slice_q)
+        gs, xs = ws.gbuf[bi][..., cin:cin + g_], ws.buf[bi][..., cin:cin + g_]
+        if self.drop_rate > 0 and not ws.frozen:         # (eval mode: no dropout in the forward)
+            # the slice's deferred BatchNorm correction and the forward's keep decisions, in place on the gradient slice; the
+            # kernels below then read it with identity coefficients
+            ops.dropout_slice_bwd(gs, xs, qa, qb, qc, self.drop_rate, self.drop_seed, bi * 256 + li)
+            qa, qb, qc = ws.ones[:g_], ws.zeros[:g_], ws.zeros[:g_]
+        dyc = ws.dyc[bi][li] if ws.dyc is not None else None
+        rows = ops.conv_gemm(gs, self.w_bwd(layer.conv2), dz2, N=self.mid, kh=3, kw=3, pad=1, prologue=ops.PRO_AFFINE2, x2=xs,
+                             pa=qa, pb=qb, pc=qc, epilogue=ops.EPI_MASK, ex=y1, e_sc=v(n2[0]), e_sh=v(n2[1]), e_mu=v(n2[2]),
+                             e_r=v(n2[3]), e_scale=ws.ones[:self.mid], pro_out=dyc, **self._sp(ws, S2, self.mid))
+        red2 = self._sc(ws, S2, self.mid, rows)
+        dw = G(layer.conv2.weight)
+        if dyc is None or not ops.last_pro_out():
+            # (fp32 mode, or a kernel without the side output) the slice as it lies in the block buffers, corrected on the fly
+            ops.conv_wgrad(gs, y1, dw, kh=3, kw=3, pad=1, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa, gb=qb, gc=qc,
+                           x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]), pb=v(n2[1]))
+        elif batch_w2:
+            self._w2_items.append((dyc, y1, v(n2[0]), v(n2[1]), dw))
+        else:
+            # the input-gradient kernel left the corrected slice as a dense (M, 32) tensor: the weight gradient reads 64 contiguous
+            # bytes per pixel instead of two 64-byte pieces of the block buffers' rows (half of every line wasted)
+            ops.conv_wgrad(dyc, y1, dw, kh=3, kw=3, pad=1, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]), pb=v(n2[1]))
+        pabc = tuple(v(t) for t in s["pl"][bi][li])
+        self.bn_bwd_coef(ws, layer.norm2, red2[0], red2[1], ws.B * h * w, layer.norm2.weight, v(n2[2]), v(n2[3]), G(layer.norm2.weight),
+                         G(layer.norm2.bias), None, None, *pabc, self.mid, replicas=red2[2], rstride=red2[3])
+        return pabc
+
+    def _layer_conv1(self, ws, bi, li, dz2, pabc, fused, done):
+        """Layer li of block bi from dz2 into the gradient buffer's channels [0, cin): conv1's input gradient with relu1's mask and
+        norm1's sums in its epilogue and conv1's weight gradient -- one kernel when `fused`, else two --, norm1's coefficients."""
+        s, v, G = self.slots, ws.v, self.grad_of
+        layer = self._layer(bi, li)
+        h, w = ws.hw[bi]
+        buf, gbuf, y1 = ws.buf[bi], ws.gbuf[bi], ws.y1[bi][li]
+        cin = self.blocks[bi][0] + li * self.growth
+        n1, S1, (bmean, brstd), (A, Bc) = s["n1"][bi][li], s["S1"][bi][li], s["bmr"][bi], s["AB"][bi]
+        pa, pb, pc = pabc
+        rows = ops.conv_gemm(dz2, self.w_bwd(layer.conv1), gbuf[..., :cin], N=cin, prologue=ops.PRO_AFFINE2, x2=y1, pa=pa,
+                             pb=pb, pc=pc, epilogue=ops.EPI_MASK, ex=buf[..., :cin], e_sc=v(n1[0]), e_sh=v(n1[1]),
+                             e_mu=v(bmean)[:cin], e_r=v(brstd)[:cin], e_scale=v(n1[0]), accumulate=True,
+                             fused_dw=G(layer.conv1.weight) if fused else None, **self._sp(ws, S1, cin))
+        red1 = self._sc(ws, S1, cin, rows)
+        if not fused:
+            ops.conv_wgrad(dz2, buf[..., :cin], G(layer.conv1.weight), g_prologue=ops.PRO_AFFINE2, g2=y1, ga=pa, gb=pb,
+                           gc=pc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n1[0]), pb=v(n1[1]))
+        self.bn_bwd_coef(ws, layer.norm1, red1[0], red1[1], ws.B * h * w, layer.norm1.weight, v(bmean), v(brstd), G(layer.norm1.weight),
+                         G(layer.norm1.bias), v(A), v(Bc), None, None, None, cin, replicas=red1[2], rstride=red1[3],
+                         q=self._slice_q(ws, bi, li - 1))
+        done(layer.norm1.weight)      # every gradient from this layer to the end of the buffer is final
+
+    def _transition_backward(self, ws, bi, done):
+        """BatchNorm transition feeding block bi: conv (on the pooled map) -> 2x2 average un-pooling with the ReLU mask and the
+        norm's sums -> the norm's coefficients, into the gradient buffer of block bi - 1."""
+        s, v, G = self.slots, ws.v, self.grad_of
+        qa, qb, qc, _, c0 = self._slice_q(ws, bi, -1)         # written by layer 0's norm1 coefficient launch
+        gs, xs = ws.gbuf[bi][..., :c0], ws.buf[bi][..., :c0]
+        B, (h, w), (ph, pw) = ws.B, ws.hw[bi], ws.hw[bi - 1]
+        pc0, pn = self.blocks[bi - 1]
+        cprev = pc0 + pn * self.growth
+        tr = getattr(self.model.features, "transition%d" % bi)
+        pbuf, pg = ws.buf[bi - 1], ws.gbuf[bi - 1]
+        nt, (pmean, prstd), (pA, pB), St = s["nt"][bi - 1], s["bmr"][bi - 1], s["AB"][bi - 1], s["St"][bi - 1]
+        dpool = ws.dpool[:B * h * w * cprev].view(B, h, w, cprev)
+        ops.conv_gemm(gs, self.w_bwd(tr.conv), dpool, N=cprev, prologue=ops.PRO_AFFINE2, x2=xs, pa=qa, pb=qb, pc=qc)
+        rows = ops.unpool2_mask(dpool, pbuf, v(nt[0]), v(nt[1]), v(pmean), v(prstd), v(nt[0]), pg, *self._ew(ws, St, cprev))
+        sred = self._sc(ws, St, cprev, rows, copies=False)
+        ops.conv_wgrad(gs, pbuf, G(tr.conv.weight), mode=ops.MODE_POOL2, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa, gb=qb,
+                       gc=qc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(nt[0]), pb=v(nt[1]))
+        self.bn_bwd_coef(ws, tr.norm, sred[0], sred[1], B * ph * pw, tr.norm.weight, v(pmean), v(prstd), G(tr.norm.weight),
+                         G(tr.norm.bias), v(pA), v(pB), None, None, None, cprev, replicas=sred[2], rstride=sred[3],
+                         q=self._slice_q(ws, bi - 1, pn - 1))
+        done(tr.norm.weight)
+
+    def _stem_backward(self, ws, dx):
+        """ImageNet stem: max-pool / ReLU / norm0 backward in one kernel, norm0's coefficients, conv0's weight (and input) gradient."""
+        f, s, v, G = self.model.features, self.slots, ws.v, self.grad_of
+        ci = self.c_init
+        qa, qb, qc = self._slice_q(ws, 0, -1)[:3]
+        gs, xs = ws.gbuf[0][..., :ci], ws.buf[0][..., :ci]
+        n0, S0 = s["n0"], s["S0"]
+        rows = ops.bnrelu_maxpool_bwd(ws.c0, v(n0[0]), v(n0[1]), v(n0[2]), v(n0[3]), ws.amax, gs, xs, qa, qb, qc, ws.dz0,
+                                      *self._ew(ws, S0, ci))
+        sred = self._sc(ws, S0, ci, rows, copies=False)
+        pa, pb, pc = (v(t)[:ci] for t in s["p"])
+        self.bn_bwd_coef(ws, f.norm0, sred[0], sred[1], ws.B * (ws.H // 2) * (ws.W // 2), f.norm0.weight, v(n0[2]), v(n0[3]),
+                         G(f.norm0.weight), G(f.norm0.bias), None, None, pa, pb, pc, ci, replicas=sred[2], rstride=sred[3])
+        ops.conv_wgrad(ws.dz0, ws.x4, G(f.conv0.weight), mode=ops.MODE_STEM, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=pa, gb=pb,
+                       gc=pc)
+        if dx is not None:
+            ops.stem_input_grad(ws.dz0, ws.c0, pa, pb, pc, f.conv0.weight, dx, stride=2, pad=3)
+
+    def _cifar_stem_backward(self, ws, dx):
+        """Stem of the CIFAR form: relu0 mask + norm0 sums in the mask epilogue of the identity convolution (its two-tensor prologue
+        applies the deferred BatchNorm correction to the gradient slice), then conv0's weight (and input) gradient."""
+        f, s, v, G = self.model.features, self.slots, ws.v, self.grad_of
+        ci = self.c_init
+        qa, qb, qc = self._slice_q(ws, 0, -1)[:3]
+        gs, xs = ws.gbuf[0][..., :ci], ws.buf[0][..., :ci]
+        n0, S0 = s["n0"], s["S0"]
+        rows = ops.conv_gemm(gs, self.eye, ws.dz0, N=ci, prologue=ops.PRO_AFFINE2, x2=xs, pa=qa, pb=qb, pc=qc,
+                             epilogue=ops.EPI_MASK, ex=ws.c0, e_sc=v(n0[0]), e_sh=v(n0[1]), e_mu=v(n0[2]), e_r=v(n0[3]),
+                             e_scale=ws.ones[:ci], **self._sp(ws, S0, ci))
+        sred = self._sc(ws, S0, ci, rows)
+        pa, pb, pc = (v(t)[:ci] for t in s["p"])
+        self.bn_bwd_coef(ws, f.norm0, sred[0], sred[1], ws.B * ws.H * ws.W, f.norm0.weight, v(n0[2]), v(n0[3]), G(f.norm0.weight),
+                         G(f.norm0.bias), None, None, pa, pb, pc, ci, replicas=sred[2], rstride=sred[3])
+        ops.conv_wgrad(ws.dz0, ws.x8, G(f.conv0.weight), kh=5, kw=5, pad=2, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=pa, gb=pb,
+                       gc=pc)
+        if dx is not None:
+            ops.stem_input_grad(ws.dz0, ws.c0, pa, pb, pc, f.conv0.weight, dx, stride=1, pad=2)
+
+    def _pair_backward(self, ws, bi, li, dz2_a, dz2_b, batch_w2, done):
         """Backward of dense layers li (a) and li - 1 (b) of block bi with ONE pass of the fused 1x1 backward over the channels
         [0, cin_b) both read.  Order: a's 3x3 input gradient -> a's 1x1 backward on its 32 newest channels alone (they are layer
         b's output slice: b's gradient depends on them) -> the slice's coefficients -> b's 3x3 input gradient -> the pair pass ->
         both norm1 coefficient launches (a's first: the A / B accumulators then see the same additions in the same order as in
         the layer-by-layer schedule).  Per channel every sum has the same terms as layer by layer, in another fp32 order."""
-        m, f, s, v = self.model, self.model.features, self.slots, ws.v
+        s, v = self.slots, ws.v
         g_ = self.growth
-        c0, n_layers = self.blocks[bi]
+        c0 = self.blocks[bi][0]
         buf, gbuf = ws.buf[bi], ws.gbuf[bi]
         h, w = ws.hw[bi]
         cnt = ws.B * h * w
         (bmean, brstd), (A, Bc) = s["bmr"][bi], s["AB"][bi]
-        block = getattr(f, "denseblock%d" % (bi + 1))
         G = self.grad_of
-        la, lb = getattr(block, "denselayer%d" % (li + 1)), getattr(block, "denselayer%d" % li)
+        la, lb = self._layer(bi, li), self._layer(bi, li - 1)
         cin_a, cin_b = c0 + li * g_, c0 + (li - 1) * g_
-
-        def front(l_i, layer, dz2):
-            """3x3 input gradient of the layer + norm2 coefficients (and its 3x3 weight gradient, batched or at once)"""
-            cin = c0 + l_i * g_
-            n2, y1, S2 = s["n2"][bi][l_i], ws.y1[bi][l_i], s["S2"][bi][l_i]
-            qa, qb, qc = (v(t) for t in s["ql"][bi][l_i])
-            gs, xs = gbuf[..., cin:cin + g_], buf[..., cin:cin + g_]
-            dyc = ws.dyc[bi][l_i] if ws.dyc is not None else None
-            rows = ops.conv_gemm(gs, self.w_bwd(layer.conv2), dz2, N=self.mid, kh=3, kw=3, pad=1, prologue=ops.PRO_AFFINE2, x2=xs,
-                                 pa=qa, pb=qb, pc=qc, epilogue=ops.EPI_MASK, ex=y1, e_sc=v(n2[0]), e_sh=v(n2[1]), e_mu=v(n2[2]),
-                                 e_r=v(n2[3]), e_scale=ws.ones[:self.mid], pro_out=dyc, **self._sp(ws, S2, self.mid))
-            red2 = self._sc(ws, S2, self.mid, rows)
-            if dyc is not None and ops.last_pro_out():
-                if (self.w2_batch and (w < 56 or h * w < 3136)):
-                    self._w2_items.append((dyc, y1, v(n2[0]), v(n2[1]), G(layer.conv2.weight)))
-                else:
-                    ops.conv_wgrad(dyc, y1, G(layer.conv2.weight), kh=3, kw=3, pad=1, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]),
-                                   pb=v(n2[1]))
-            else:
-                ops.conv_wgrad(gs, y1, G(layer.conv2.weight), kh=3, kw=3, pad=1, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa, gb=qb,
-                               gc=qc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]), pb=v(n2[1]))
-            pabc = tuple(v(t) for t in s["pl"][bi][l_i])
-            self.bn_bwd_coef(ws, layer.norm2, red2[0], red2[1], cnt, layer.norm2.weight, v(n2[2]), v(n2[3]), G(layer.norm2.weight),
-                             G(layer.norm2.bias), None, None, *pabc, self.mid, replicas=red2[2], rstride=red2[3])
-            return pabc
 
         def conv1_args(l_i, layer, dz2, pabc, lo, hi, stat):
             """conv_gemm arguments of the layer's fused 1x1 backward restricted to its input channels [lo, hi)"""
@@ -957,20 +878,20 @@ class _Engine(FusedEngine):
                     lambda rows: (sa, sb, self.stat_replicas, slots[0][1]))
 
         S1a, S1b = s["S1"][bi][li], s["S1"][bi][li - 1]
-        pa_ = front(li, la, dz2_a)
+        pa_ = self._layer_front(ws, bi, li, dz2_a, batch_w2)
         # layer a on slice li - 1 alone
         st_kw, st_red = stat_region(S1a, cin_b, g_, 0, 1)
         x_, w_, y_, kw_ = conv1_args(li, la, dz2_a, pa_, cin_b, cin_a, st_kw)
         rows = ops.conv_gemm(x_, w_, y_, fused_dw=G(la.conv1.weight).view(self.mid, cin_a)[:, cin_b:], **kw_)
-        coef1(la, st_red(rows), cin_b, cin_a, slice_q(bi, li - 1))
-        pb_ = front(li - 1, lb, dz2_b)
+        coef1(la, st_red(rows), cin_b, cin_a, self._slice_q(ws, bi, li - 1))
+        pb_ = self._layer_front(ws, bi, li - 1, dz2_b, batch_w2)
         # both layers on [0, cin_b)
         sa_kw, sa_red = stat_region(S1a, 0, cin_b, 0, 2)
         sb_kw, sb_red = stat_region(S1b, 0, cin_b, 1, 2)
         rows = ops.conv1x1_bwd_pair(conv1_args(li, la, dz2_a, pa_, 0, cin_b, sa_kw), conv1_args(li - 1, lb, dz2_b, pb_, 0, cin_b, sb_kw),
                                     G(la.conv1.weight).view(self.mid, cin_a)[:, :cin_b], G(lb.conv1.weight).view(self.mid, cin_b))
         coef1(la, sa_red(rows), 0, cin_b, None)
-        coef1(lb, sb_red(rows), 0, cin_b, slice_q(bi, li - 2))
+        coef1(lb, sb_red(rows), 0, cin_b, self._slice_q(ws, bi, li - 2))
         done(lb.norm1.weight)
 
     def _pre_bucket(self):

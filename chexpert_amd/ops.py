@@ -23,7 +23,7 @@ def _nhwc(t):
 
 
 # Workspace of the reproducible weight-gradient sums (CxWgrad.scratch): one slab buffer per (device, stream) -- kernels on one stream
-# are serialised, the weight-gradient kernels of the side stream run beside those of the main stream.  The engines whose statistics
+# are serialised, those of two streams are not.  The engines whose statistics
 # are deterministic (plain DenseNet / ResNet) switch it on for their backward pass (set_det_wgrad), which makes the whole training
 # step bit-reproducible; measured cost +1.3 % on DenseNet121 bs=256 (1.3 GB of slab traffic per step), none on ResNet152.
 # CHEXPERT_DET_WGRAD=0 keeps the fp32 atomics everywhere.  A launch whose splits x |dW| exceed the buffer falls back to atomics.

@@ -19,7 +19,7 @@ set -e
 if [[ $PART == *A* ]]; then
 timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
 timeout -k 10 300 python bench.py --full --dtype fp32 --steps 3 --warmup 1 --no-other-configs > $O/bench_fp32.json 2>> $O/bench.err
-CHEXPERT_SERIAL_WGRAD=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --no-cpu-baseline --no-other-configs --no-graph --steps 10 --warmup 3 > $O/bench_prof.json 2>> $O/bench.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --no-cpu-baseline --no-other-configs --no-graph --steps 10 --warmup 3 > $O/bench_prof.json 2>> $O/bench.err
 cp $(ls $O/stats/*/*_kernel_stats.csv) $O/kernel_stats.csv
 python scratch/kstats.py $O/stats 13 40 > $O/kstats_densenet121.txt; rm -rf $O/stats
 fi
@@ -40,7 +40,7 @@ if [[ $PART == *B* ]]; then
 for spec in "aadensenet121 128 320" "resnet152 128 320" "efficientnet-b4 64 380"; do
   set -- $spec
   timeout -k 10 300 python bench.py --full --model $1 --batch $2 --size $3 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_$1.json 2>> $O/bench.err
-  CHEXPERT_SERIAL_WGRAD=1 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --model $1 --batch $2 --size $3 --no-cpu-baseline --no-graph --steps 4 --warmup 1 > /dev/null 2>> $O/bench.err
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --model $1 --batch $2 --size $3 --no-cpu-baseline --no-graph --steps 4 --warmup 1 > /dev/null 2>> $O/bench.err
   python scratch/kstats.py $O/stats 5 30 > $O/kstats_$1.txt; rm -rf $O/stats
   pmc $1 bf16 $2 $3
 done
