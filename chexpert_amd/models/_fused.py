@@ -340,6 +340,29 @@ class FusedEngine:
         ops.bn_bwd_coef_eval(S1, S2, mean, rstd, bn.running_mean[lo:lo + Cn], bn.running_var[lo:lo + Cn], gamma, bn.eps, dgamma,
                              dbeta, pa, pb, pc, Cn, replicas=replicas, rstride=rstride, q=q)
 
+    # ---- BatchNorm coefficients of an engine that keeps its _BN slots in `self.bn` ({id(bn): _BN}) and, in deterministic mode,
+    # its statistic rows in ws.slab[0] / ws.slab[1] (ResNet, EfficientNet)
+    def _bn_coef(self, ws, bn, count, train, rows=None):
+        """Forward coefficients of `bn` (scale, shift, mean, rstd) from the sums of `count` values per channel its producer has
+        just written (`rows` statistic rows in deterministic mode), with the running-statistic update; eval: from the running
+        statistics."""
+        S, v = self.bn[id(bn)], self._v
+        if train:
+            mom = bn.momentum if bn.momentum is not None else 0.1
+            ssum, ssq, reps, rstride = (ws.slab[0], ws.slab[1], rows, S.C) if self.det else (v(ws, S.sum), v(ws, S.sq), 1, 0)
+            ops.bn_coef(ssum, ssq, count, bn.weight, bn.bias, bn.eps, mom, bn.running_mean, bn.running_var,
+                        v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), S.C, replicas=reps, rstride=rstride)
+        else:
+            ops.bn_coef_eval(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, v(ws, S.sc), v(ws, S.sh), v(ws, S.mean),
+                             v(ws, S.rstd), S.C)
+
+    def _bn_bwd(self, ws, bn, r, count):
+        """Backward coefficients pa / pb / pc of `bn` and its dgamma / dbeta from the backward sums r = (S1, S2, replicas, rstride)
+        over `count` values per channel; everything else follows from bn's slot."""
+        S, v, G = self.bn[id(bn)], self._v, self.grad_of
+        self.bn_bwd_coef(ws, bn, r[0], r[1], count, bn.weight, v(ws, S.mean), v(ws, S.rstd), G(bn.weight), G(bn.bias), None, None,
+                         v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), S.C, replicas=r[2], rstride=r[3])
+
     @staticmethod
     def _v(ws, slot, n=None):
         off, m = slot

@@ -169,16 +169,6 @@ class _Engine(FusedEngine):
     def _rows_cap(self, C):
         return min(self.ROWS, self.SLAB // C)
 
-    def _bn_coef(self, ws, bn, count, train, rows=None):
-        S, v = self.bn[id(bn)], self._v
-        if train:
-            ssum, ssq, reps, rstride = (ws.slab[0], ws.slab[1], rows, S.C) if self.det else (v(ws, S.sum), v(ws, S.sq), 1, 0)
-            ops.bn_coef(ssum, ssq, count, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean, bn.running_var,
-                        v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), S.C, replicas=reps, rstride=rstride)
-        else:
-            ops.bn_coef_eval(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, v(ws, S.sc), v(ws, S.sh), v(ws, S.mean),
-                             v(ws, S.rstd), S.C)
-
     @staticmethod
     def _parts(b):
         mods = list(b)
@@ -334,12 +324,7 @@ class _Engine(FusedEngine):
         def bn_bwd(S, bn, count):
             """BatchNorm backward coefficients of `bn` from the sums its producer has just written (deterministic mode: the rows of
             the scratch pair, counted by cx_last_stat_rows)."""
-            if det:
-                self.bn_bwd_coef(ws, bn, ws.slab[0], ws.slab[1], count, bn.weight, v(ws, S.mean), v(ws, S.rstd), G(bn.weight), G(bn.bias),
-                                 None, None, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), S.C, replicas=lib().cx_last_stat_rows(), rstride=S.C)
-            else:
-                self.bn_bwd_coef(ws, bn, v(ws, S.S1), v(ws, S.S2), count, bn.weight, v(ws, S.mean), v(ws, S.rstd), G(bn.weight), G(bn.bias),
-                                 None, None, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), S.C)
+            self._bn_bwd(ws, bn, (ws.slab[0], ws.slab[1], lib().cx_last_stat_rows(), S.C) if det else (v(ws, S.S1), v(ws, S.S2), 1, 0), count)
 
         def ssp(S):      # (S1, S2, stat_rows) of an element-wise / depthwise producer of S's backward sums
             return (ptr(ws.slab[0]), ptr(ws.slab[1]), self._rows_cap(S.C)) if det else (ptr(v(ws, S.S1)), ptr(v(ws, S.S2)), 0)

@@ -94,13 +94,17 @@ class BasicBlock(nn.Module):
 
 
 class _Engine(FusedEngine):
+    """Host-side schedule.  `forward` drives `_stem_forward` / `_cifar_stem_forward`, then per block `_bottleneck_forward` or
+    `_basic_forward` (both end in `_join_forward`, with `_down_forward` for a downsample block), then the head; `_backward` drives
+    `_head_backward`, per block `_bottleneck_backward` / `_basic_backward` (both begin with `_join_backward` and share
+    `_aa_backward_front`, `_gx` and `_down_backward`), then `_stem_backward` / `_cifar_stem_backward`.  What one block hands to the
+    next is passed explicitly: `pending` (a forward join deferred to the next conv1's prologue) and `join_rows` (a join backward
+    that ran in the epilogue of the block above)."""
     SLAB = 1 << 22               # floats per statistic-row scratch (rows x channels of the largest producer)
     EW_ROWS = 2048
 
     def __init__(self, model):
         super().__init__(model)
-        # (deterministic statistics: attention-augmented blocks feed one BatchNorm from two kernels: their statistic rows are reduced
-        # per channel range, _aa_fwd; the two input-gradient branches stack their rows, _stacked)
         self.join_fuse = os.environ.get("CHEXPERT_JOIN_FUSE", "1") != "0"      # residual-join backward in the conv1 input gradient's epilogue
         # Bottleneck networks in bf16: the residual stream is kept as two planes (bf16 hi + int8 lo = 16 significant bits, common.h
         # cx_join2) and the forward join of an identity block runs in the prologue of the NEXT block's conv1 (CX_PRO_JOIN)
@@ -114,24 +118,17 @@ class _Engine(FusedEngine):
         self.blocks = [blk for L in model._stages() for blk in L]
         self.basic = model.block is BasicBlock                 # two 3x3 convolutions per block (attn_aug_conv.py:107-156)
         self.two_plane = self.stream_lo and not (model.block is BasicBlock) and self.dtype == torch.bfloat16
-        # Where the stream keeps its lo plane: on every output that feeds an identity join (round 5; 46 of resnet152's 50 joins --
-        # the four downsample blocks' outputs start a stage and are rounded once).  Round 4 kept it only through the long stages
-        # (layer2 / layer3: 42 joins) and measured 8.3e-3 on the reference fixture's train logits at 128 images; on every identity
-        # join it is 6.9e-3 for +0.36 ms of the 54.2 ms step (profiles/r05_resnet_margin.txt): kept, the 1e-2 bound then has 30 %
-        # of room instead of 17 %.  The FUSED form (the join in the prologue of the next conv1) stays with the long stages: it does
-        # not pay on layer1 (N = 64 on a 256-wide tile) nor layer4 (MFMA-bound) -- scratch/bench_join.py.
-        # keep_lo[bi]: block bi's output has a lo plane;  fuse_fwd[bi]: its join runs in the prologue of block bi + 1's conv1.
+        # keep_lo[bi]: block bi's output has a lo plane -- every output that feeds an identity join (46 of resnet152's 50 joins; the
+        # four downsample blocks' outputs start a stage and are rounded once).  Keeping it only through the long stages measured
+        # 8.3e-3 on the reference fixture's train logits at 128 images, on every identity join 6.9e-3 for +0.36 ms of the 54.2 ms
+        # step (profiles/r05_resnet_margin.txt): the 1e-2 bound then has 30 % of room instead of 17 %.
+        # fuse_fwd[bi]: block bi's join runs in the prologue of block bi + 1's conv1.  That form stays with the stages of >= 6
+        # blocks: it does not pay on layer1 (N = 64 on a 256-wide tile) nor layer4 (MFMA-bound) -- scratch/bench_join.py.
         n = len(self.blocks)
-        stage_len = []
-        for L in model._stages():
-            stage_len += [len(L)] * len(L)
+        stage_len = [len(L) for L in model._stages() for _ in L]
         ident = [b.downsample is None for b in self.blocks]
-        long_id = [ident[i] and stage_len[i] >= 6 for i in range(n)]
-        # (CHEXPERT_STREAM_LO_MIN=<blocks>: the stage length from which the lo plane is kept, for measurements -- 1 = on every identity join)
-        lo_min = int(os.environ.get("CHEXPERT_STREAM_LO_MIN", "1"))
-        lo_id = [ident[i] and stage_len[i] >= lo_min for i in range(n)]
-        self.keep_lo = [self.two_plane and i + 1 < n and lo_id[i + 1] for i in range(n)]
-        self.fuse_fwd = [self.two_plane and self.fwd_join_fuse and long_id[i] and i + 1 < n for i in range(n)]
+        self.keep_lo = [self.two_plane and i + 1 < n and ident[i + 1] for i in range(n)]
+        self.fuse_fwd = [self.two_plane and self.fwd_join_fuse and ident[i] and stage_len[i] >= 6 and i + 1 < n for i in range(n)]
         self.cifar = isinstance(model, WideResNet)              # 3x3 stride-1 stem, no max-pool, three stages (:311-404)
         # vector plan: [fwd-zero region | bwd-zero region | rest]
         self.bn, rest, self.fwd_zero, self.bwd_zero = _BN.plan(list(self._all_bns()))
@@ -238,13 +235,34 @@ class _Engine(FusedEngine):
         ws.bwd = None
         return ws
 
-    def _sp(self, ws, S, train):
-        """Statistics arguments of a producer of BatchNorm S's input."""
-        if not train:
+    # ---- statistics plumbing for the two modes (deterministic: rows in ws.slab; CHEXPERT_DET=0: atomic sums in the _BN slots), named
+    # as in the DenseNet engine: keywords of a convolution producer (_sp), (S1, S2, stat_rows) of an element-wise producer (_ew),
+    # (S1, S2, replicas, rstride) for the consumer (_sc)
+    def _sp(self, ws, S, bwd=False, after=0):
+        """Statistics keywords of a convolution that produces BatchNorm S's forward sums (none in an eval forward), or with `bwd`
+        its backward sums S1 / S2 in a mask epilogue.  after: the rows of a first producer of the same sums -- this one's rows go
+        behind them, so one reduction over both adds them (deterministic mode)."""
+        if ws.frozen and not bwd:
             return {}
         if self.det:
-            return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // S.C, stat_rstride=S.C)
-        return dict(stat_sum=self._v(ws, S.sum), stat_sq=self._v(ws, S.sq))
+            s, q = (ws.slab[0][after * S.C:], ws.slab[1][after * S.C:]) if after else (ws.slab[0], ws.slab[1])
+            return dict(stat_sum=s, stat_sq=q, stat_det=True, stat_replicas=self.SLAB // S.C - after, stat_rstride=S.C)
+        a, b = (S.S1, S.S2) if bwd else (S.sum, S.sq)
+        return dict(stat_sum=self._v(ws, a), stat_sq=self._v(ws, b))
+
+    def _ew(self, ws, S):
+        if self.det:
+            return ws.slab[0], ws.slab[1], min(self.EW_ROWS, self.SLAB // S.C)
+        return self._v(ws, S.S1), self._v(ws, S.S2), 0
+
+    def _sc(self, ws, S, rows):
+        if self.det:
+            return ws.slab[0], ws.slab[1], rows, S.C
+        return self._v(ws, S.S1), self._v(ws, S.S2), 1, 0
+
+    def _down_s2(self, ws, Sd):
+        """Where a join backward leaves S2 of the downsample BatchNorm Sd; its S1 is the last BatchNorm's (the same masked gradient)."""
+        return ws.slab[2] if self.det else self._v(ws, Sd.S2)
 
     @staticmethod
     def _stat_slice(kw, c_):
@@ -256,16 +274,37 @@ class _Engine(FusedEngine):
                 kw[k] = kw[k][c_.start:]
         return kw
 
-    def _bn_coef(self, ws, bn, count, train, rows=None):
-        S, v = self.bn[id(bn)], self._v
-        if train:
-            mom = bn.momentum if bn.momentum is not None else 0.1
-            ssum, ssq, reps, rstride = (ws.slab[0], ws.slab[1], rows, S.C) if self.det else (v(ws, S.sum), v(ws, S.sq), 1, 0)
-            ops.bn_coef(ssum, ssq, count, bn.weight, bn.bias, bn.eps, mom, bn.running_mean, bn.running_var,
-                        v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), S.C, replicas=reps, rstride=rstride)
-        else:
-            ops.bn_coef_eval(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, v(ws, S.sc), v(ws, S.sh), v(ws, S.mean),
-                             v(ws, S.rstd), S.C)
+    # ---- BatchNorm in the operand prologues / epilogues of the convolutions.  c_: the channel range of one group of a grouped
+    # convolution or of an AAConv2d branch (None: all channels)
+    @staticmethod
+    def _ch(t, c_):
+        return t if c_ is None else t[..., c_]
+
+    def _pro_bnrelu(self, ws, S, c_=None):
+        """forward: relu(bn_S(.)) of the operand"""
+        return dict(prologue=ops.PRO_AFFINE_RELU, pa=self._ch(self._v(ws, S.sc), c_), pb=self._ch(self._v(ws, S.sh), c_))
+
+    def _x_bnrelu(self, ws, S, c_=None):
+        """weight gradient: relu(bn_S(.)) of the activation operand"""
+        return dict(x_prologue=ops.PRO_AFFINE_RELU, pa=self._ch(self._v(ws, S.sc), c_), pb=self._ch(self._v(ws, S.sh), c_))
+
+    def _pro_bnbwd(self, ws, y, S, c_=None):
+        """input gradient: BatchNorm S's backward of the gradient operand, dY = dz * pa + y * pb + pc"""
+        ch, v = self._ch, self._v
+        return dict(prologue=ops.PRO_AFFINE2, x2=ch(y, c_), pa=ch(v(ws, S.pa), c_), pb=ch(v(ws, S.pb), c_), pc=ch(v(ws, S.pc), c_))
+
+    def _g_bnbwd(self, ws, y, S, c_=None):
+        """weight gradient: the same of its gradient operand"""
+        ch, v = self._ch, self._v
+        return dict(g_prologue=ops.PRO_AFFINE2, g2=ch(y, c_), ga=ch(v(ws, S.pa), c_), gb=ch(v(ws, S.pb), c_), gc=ch(v(ws, S.pc), c_))
+
+    def _mask(self, ws, y, S, c_=None, after=0):
+        """input gradient: the epilogue that masks with [relu(bn_S(y)) > 0] and produces BatchNorm S's backward sums (_sp)"""
+        ch, v = self._ch, self._v
+        kw = self._sp(ws, S, bwd=True, after=after)
+        return dict(epilogue=ops.EPI_MASK, ex=ch(y, c_), e_sc=ch(v(ws, S.sc), c_), e_sh=ch(v(ws, S.sh), c_), e_mu=ch(v(ws, S.mean), c_),
+                    e_r=ch(v(ws, S.rstd), c_), e_scale=v(ws, self.ones, S.C if c_ is None else c_.stop - c_.start),
+                    **(kw if c_ is None else self._stat_slice(kw, c_)))
 
     def _bn_coef_part(self, ws, bn, count, rows, lo, n):
         """_bn_coef for channels [lo, lo + n) of `bn` from `rows` statistic rows of pitch n (deterministic mode: an AAConv2d's
@@ -276,10 +315,11 @@ class _Engine(FusedEngine):
         ops.bn_coef(ws.slab[0], ws.slab[1], count, c(bn.weight), c(bn.bias), bn.eps, mom, c(bn.running_mean), c(bn.running_var),
                     c(v(ws, S.sc)), c(v(ws, S.sh)), c(v(ws, S.mean)), c(v(ws, S.rstd)), n, replicas=rows, rstride=n)
 
-    def _aa_fwd(self, ws, aa, xin, yout, qkv_t, bn, S, stride, count, train, pro):
-        """AAConv2d forward (attn_aug_conv.py:65-97) into `yout` = [conv branch | attention], with the statistics of the BatchNorm
-        that follows.  Returns True when the coefficients of `bn` have been computed here (deterministic training mode)."""
-        v = self._v
+    # ---- forward
+    def _aa_fwd(self, ws, aa, xin, yout, qkv_t, bn, stride, count, pro):
+        """AAConv2d forward (attn_aug_conv.py:65-97) into `yout` = [conv branch | attention], and the coefficients of the BatchNorm
+        `bn` that follows (deterministic training mode: the statistic rows of the two kernels are reduced per channel range)."""
+        v, S, train = self._v, self.bn[id(bn)], not ws.frozen
         p_ = yout.shape[3]
         cc = p_ - aa.dv
         det = train and self.det
@@ -299,20 +339,10 @@ class _Engine(FusedEngine):
             rows = ops.aa_outproj_fwd(qkv_t["O"], aa.out_proj.weight, yout[..., cc:], ws.slab[0], ws.slab[1],
                                       stat_rows=min(self.EW_ROWS, self.SLAB // aa.dv), stat_rstride=aa.dv)
             self._bn_coef_part(ws, bn, count, rows, cc, aa.dv)
-            return True
-        ops.aa_outproj_fwd(qkv_t["O"], aa.out_proj.weight, yout[..., cc:], sub(st(S.sum), cc, aa.dv), sub(st(S.sq), cc, aa.dv))
-        return False
+        else:
+            ops.aa_outproj_fwd(qkv_t["O"], aa.out_proj.weight, yout[..., cc:], sub(st(S.sum), cc, aa.dv), sub(st(S.sq), cc, aa.dv))
+            self._bn_coef(ws, bn, count, train)
 
-    def _stacked(self, ws, kw, rows, C):
-        """Mask-epilogue arguments for a SECOND producer of the same backward sums (deterministic mode): its statistic rows go
-        behind the `rows` rows of the first one, so one reduction over rows + rows2 adds both."""
-        if not self.det:
-            return kw
-        kw = dict(kw)
-        kw.update(stat_sum=ws.slab[0][rows * C:], stat_sq=ws.slab[1][rows * C:], stat_replicas=self.SLAB // C - rows)
-        return kw
-
-    # ---- forward
     def forward(self, x, train, record=False):
         """train: batch statistics (and running-statistic updates); eval: running statistics.  record (eval): also keep what
         backward reads -- the join ReLU sign bits, which an eval forward without a backward skips."""
@@ -331,122 +361,131 @@ class _Engine(FusedEngine):
         if train and not self.det:
             z0, zn = self.fwd_zero
             ws.vec[z0:z0 + zn].zero_()
-        st = (lambda s: v(ws, s)) if train else (lambda s: None)
-        sp = lambda S_: self._sp(ws, S_, train)
-        S0 = self.bn[id(m.bn1)]
-        if self.cifar:
-            # attn_aug_conv.py:341-343, :391-393: 3x3 stride-1 stem, BatchNorm, ReLU -- no max-pool
-            if u8:
-                raise RuntimeError("the CIFAR stem takes (B,3,H,W) float images")
-            c0 = m.conv1.out_channels
-            check(lib().cx_nchw3_to_nhwc8(ptr(x.contiguous().float()), ptr(ws.x8), B, H, W, stream_ptr()), "cx_nchw3_to_nhwc8")
-            rows = ops.conv_gemm(ws.x8, self.packed[self.stem_off:], ws.c0, N=c0, kh=3, kw=3, stride=1, pad=1, **sp(S0))
-            self._bn_coef(ws, m.bn1, B * H * W, train, rows)
-            ops.affine2_relu(ws.c0, ws.c0, v(ws, S0.sc), v(ws, self.zeros, c0), v(ws, S0.sh), ws.pool0)
-        else:
-            if u8:
-                ops.u8_to_nhwc4(x.contiguous(), ws.x4)
-            else:
-                ops.nchw3_to_nhwc4(x.contiguous().float(), ws.x4)
-            rows = ops.conv_gemm(ws.x4, self.w_fwd(m.conv1), ws.c0, N=64, mode=ops.MODE_STEM, **sp(S0))
-            self._bn_coef(ws, m.bn1, B * (H // 2) * (W // 2), train, rows)
-            ops.bnrelu_maxpool_fwd(ws.c0, v(ws, S0.sc), v(ws, S0.sh), ws.pool0, ws.amax, None, None)
-        xin, xin_lo, pending = ws.pool0, None, None
-        for bi, b in enumerate(self.blocks):
-            t = ws.blk[bi]
-            s_, p_ = b.stride, b.bn1.num_features
-            o_ = self._last_bn(b).num_features
-            cin_ = self._cin(b)
-            hi, wi = t["hin"]
-            ho, wo = t["hout"]
-            mk = t["mask"] if ws.recorded else None
+        xin = self._cifar_stem_forward(ws, x) if self.cifar else self._stem_forward(ws, x)
+        xin_lo, pending = None, None
+        for bi in range(len(self.blocks)):
             if self.basic:
-                # attn_aug_conv.py:135-156: conv3x3(stride) - bn1 - relu - conv3x3 - bn2, + identity | downsample(x), relu
-                S1, S2 = self.bn[id(b.bn1)], self.bn[id(b.bn2)]
-                coef_done = False
-                if isinstance(b.conv1, AAConv2d):
-                    # attn_aug_conv.py:124-131, :65-97: the first 3x3 is attention-augmented (conv branch || attention, on the raw input)
-                    coef_done = self._aa_fwd(ws, b.conv1, xin, t["y1"], t, b.bn1, S1, s_, B * ho * wo, train, {})
-                    rows = None
-                else:
-                    rows = ops.conv_gemm(xin, self.w_fwd(b.conv1), t["y1"], N=p_, kh=3, kw=3, stride=s_, pad=1, **sp(S1))
-                if not coef_done:
-                    self._bn_coef(ws, b.bn1, B * ho * wo, train, rows)
-                rows = ops.conv_gemm(t["y1"], self.w_fwd(b.conv2), t["y2"], N=p_, kh=3, kw=3, stride=1, pad=1,
-                                     prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S1.sc), pb=v(ws, S1.sh), **sp(S2))
-                self._bn_coef(ws, b.bn2, B * ho * wo, train, rows)
-                ja, jb, jc = (v(ws, sl) for sl in self.join[bi])
-                if b.downsample is not None:
-                    Sd = self.bn[id(b.downsample[1])]
-                    rows = ops.conv_gemm(xin, self.w_fwd(b.downsample[0]), t["yd"], N=p_, stride=s_, **sp(Sd))
-                    self._bn_coef(ws, b.downsample[1], B * ho * wo, train, rows)
-                    torch.add(v(ws, S2.sh), v(ws, Sd.sh), out=jc)
-                    ops.affine2_relu(t["y2"], t["yd"], v(ws, S2.sc), v(ws, Sd.sc), jc, t["out"], mk)
-                else:
-                    ops.affine2_relu(t["y2"], xin, v(ws, S2.sc), v(ws, self.ones, p_), v(ws, S2.sh), t["out"], mk)
-                xin = t["out"]
-                continue
-            S1, S2, S3 = self.bn[id(b.bn1)], self.bn[id(b.bn2)], self.bn[id(b.bn3)]
-            if pending is not None:
-                # attn_aug_conv.py:202-211 of the block below + :188 of this one: out = relu(bn3(y3) + identity) is computed in this
-                # conv1's prologue (hi plane = its operand) and leaves as hi / lo / sign-bit side outputs -- no pass of its own
-                tp, Sp, mkp = pending
-                rows = ops.conv_gemm(tp["y3"], self.w_fwd(b.conv1), t["y1"], N=p_, prologue=ops.PRO_JOIN, x2=tp["id_hi"], x3=tp["id_lo"],
-                                     pa=v(ws, Sp.sc), pb=v(ws, self.ones, cin_), pc=v(ws, Sp.sh), pro_out=tp["out"], po_lo=tp.get("out_lo"),
-                                     po_mask=mkp, **sp(S1))
-                pending = None
+                xin = self._basic_forward(ws, bi, xin)
             else:
-                rows = ops.conv_gemm(xin, self.w_fwd(b.conv1), t["y1"], N=p_, **sp(S1))
-            self._bn_coef(ws, b.bn1, B * hi * wi, train, rows)
-            coef_done = False
-            if isinstance(b.conv2, AAConv2d):
-                # attn_aug_conv.py:65-97: 3x3 conv branch || multi-head attention over the stride-s grid, concatenated on channels
-                coef_done = self._aa_fwd(ws, b.conv2, t["y1"], t["y2"], t, b.bn2, S2, s_, B * ho * wo, train,
-                                         dict(prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S1.sc), pb=v(ws, S1.sh)))
-                rows = None
-            else:
-                d_ = b.conv2.dilation[0]              # > 1 under replace_stride_with_dilation: padding = dilation, stride 1
-                gr = b.conv2.groups
-                if gr == 1:
-                    rows = ops.conv_gemm(t["y1"], self.w_fwd(b.conv2), t["y2"], N=p_, kh=3, kw=3, stride=s_, pad=d_, dil=d_,
-                                         prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S1.sc), pb=v(ws, S1.sh), **sp(S2))
-                else:
-                    # conv3x3(width, width, stride, groups, dilation) (attn_aug_conv.py:183): one launch per group on its channel
-                    # slice of y1 / y2; the statistic rows of the groups sit side by side at the pitch of the whole BatchNorm
-                    kg = p_ // gr
-                    for g_ in range(gr):
-                        c_ = slice(g_ * kg, (g_ + 1) * kg)
-                        rows = ops.conv_gemm(t["y1"][..., c_], self.w_fwd(b.conv2, g_), t["y2"][..., c_], N=kg, kh=3, kw=3, stride=s_,
-                                             pad=d_, dil=d_, prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S1.sc)[c_], pb=v(ws, S1.sh)[c_],
-                                             **self._stat_slice(sp(S2), c_))
-            if not coef_done:
-                self._bn_coef(ws, b.bn2, B * ho * wo, train, rows)
-            rows = ops.conv_gemm(t["y2"], self.w_fwd(b.conv3), t["y3"], N=o_, prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S2.sc),
-                                 pb=v(ws, S2.sh), **sp(S3))
-            self._bn_coef(ws, b.bn3, B * ho * wo, train, rows)
-            ja, jb, jc = (v(ws, sl) for sl in self.join[bi])
-            lo_out = t.get("out_lo")
-            if b.downsample is not None:
-                Sd = self.bn[id(b.downsample[1])]
-                rows = ops.conv_gemm(xin, self.w_fwd(b.downsample[0]), t["yd"], N=o_, stride=s_, **sp(Sd))
-                self._bn_coef(ws, b.downsample[1], B * ho * wo, train, rows)
-                torch.add(v(ws, S3.sh), v(ws, Sd.sh), out=jc)
-                if lo_out is not None:       # both operands are raw convolution outputs; the stream starts here with 16 significant bits
-                    ops.join_fwd(t["y3"], t["yd"], None, v(ws, S3.sc), v(ws, Sd.sc), jc, t["out"], lo_out, mk)
-                else:
-                    ops.affine2_relu(t["y3"], t["yd"], v(ws, S3.sc), v(ws, Sd.sc), jc, t["out"], mk)
-            elif self.fuse_fwd[bi] and (o_) % 64 == 0 and t["out"].numel() * 2 < (1 << 32):
-                t["id_hi"], t["id_lo"] = xin, xin_lo                           # joined in the prologue of the next block's conv1
-                pending = (t, S3, mk)
-            elif lo_out is not None or xin_lo is not None:
-                ops.join_fwd(t["y3"], xin, xin_lo, v(ws, S3.sc), v(ws, self.ones, o_), v(ws, S3.sh), t["out"], lo_out, mk)
-            else:
-                ops.affine2_relu(t["y3"], xin, v(ws, S3.sc), v(ws, self.ones, o_), v(ws, S3.sh), t["out"], mk)
-            xin, xin_lo = t["out"], lo_out
+                xin, xin_lo, pending = self._bottleneck_forward(ws, bi, xin, xin_lo, pending)
         ops.head_fwd(xin, v(ws, self.ones), v(ws, self.zeros), m.fc.weight, m.fc.bias, ws.pooled, ws.logits)
         if train:
             m._nbt_pending += 1
         return ws
+
+    def _stem_forward(self, ws, x):
+        """7x7 stride-2 convolution, BatchNorm + ReLU + 3x3 stride-2 max-pool in one kernel"""
+        m, v = self.model, self._v
+        S0 = self.bn[id(m.bn1)]
+        if x.dtype == torch.uint8:
+            ops.u8_to_nhwc4(x.contiguous(), ws.x4)
+        else:
+            ops.nchw3_to_nhwc4(x.contiguous().float(), ws.x4)
+        rows = ops.conv_gemm(ws.x4, self.w_fwd(m.conv1), ws.c0, N=64, mode=ops.MODE_STEM, **self._sp(ws, S0))
+        self._bn_coef(ws, m.bn1, ws.B * (ws.H // 2) * (ws.W // 2), not ws.frozen, rows)
+        ops.bnrelu_maxpool_fwd(ws.c0, v(ws, S0.sc), v(ws, S0.sh), ws.pool0, ws.amax, None, None)
+        return ws.pool0
+
+    def _cifar_stem_forward(self, ws, x):
+        """attn_aug_conv.py:341-343, :391-393: 3x3 stride-1 stem, BatchNorm, ReLU -- no max-pool"""
+        m, v = self.model, self._v
+        if x.dtype == torch.uint8:
+            raise RuntimeError("the CIFAR stem takes (B,3,H,W) float images")
+        S0, c0 = self.bn[id(m.bn1)], m.conv1.out_channels
+        check(lib().cx_nchw3_to_nhwc8(ptr(x.contiguous().float()), ptr(ws.x8), ws.B, ws.H, ws.W, stream_ptr()), "cx_nchw3_to_nhwc8")
+        rows = ops.conv_gemm(ws.x8, self.packed[self.stem_off:], ws.c0, N=c0, kh=3, kw=3, stride=1, pad=1, **self._sp(ws, S0))
+        self._bn_coef(ws, m.bn1, ws.B * ws.H * ws.W, not ws.frozen, rows)
+        ops.affine2_relu(ws.c0, ws.c0, v(ws, S0.sc), v(ws, self.zeros, c0), v(ws, S0.sh), ws.pool0)
+        return ws.pool0
+
+    def _basic_forward(self, ws, bi, xin):
+        """attn_aug_conv.py:135-156: conv3x3(stride) - bn1 - relu - conv3x3 - bn2, + identity | downsample(x), relu.  Returns the
+        block's output."""
+        b, t, train = self.blocks[bi], ws.blk[bi], not ws.frozen
+        ho, wo = t["hout"]
+        p_, cnt = b.bn1.num_features, ws.B * ho * wo
+        S1, S2 = self.bn[id(b.bn1)], self.bn[id(b.bn2)]
+        if isinstance(b.conv1, AAConv2d):
+            # attn_aug_conv.py:124-131, :65-97: the first 3x3 is attention-augmented (conv branch || attention, on the raw input)
+            self._aa_fwd(ws, b.conv1, xin, t["y1"], t, b.bn1, b.stride, cnt, {})
+        else:
+            rows = ops.conv_gemm(xin, self.w_fwd(b.conv1), t["y1"], N=p_, kh=3, kw=3, stride=b.stride, pad=1, **self._sp(ws, S1))
+            self._bn_coef(ws, b.bn1, cnt, train, rows)
+        rows = ops.conv_gemm(t["y1"], self.w_fwd(b.conv2), t["y2"], N=p_, kh=3, kw=3, stride=1, pad=1, **self._pro_bnrelu(ws, S1),
+                             **self._sp(ws, S2))
+        self._bn_coef(ws, b.bn2, cnt, train, rows)
+        self._join_forward(ws, bi, xin, None)
+        return t["out"]
+
+    def _bottleneck_forward(self, ws, bi, xin, xin_lo, pending):
+        """attn_aug_conv.py:186-211 with the stride on conv2.  xin / xin_lo: the planes of the block's input; pending: the join of
+        the block below when it was left to this conv1's prologue (_join_forward).  Returns (out, out_lo, pending of this block)."""
+        v, b, t, train = self._v, self.blocks[bi], ws.blk[bi], not ws.frozen
+        s_, p_ = b.stride, b.bn1.num_features
+        (hi, wi), (ho, wo) = t["hin"], t["hout"]
+        cnt = ws.B * ho * wo
+        S1, S2, S3 = self.bn[id(b.bn1)], self.bn[id(b.bn2)], self.bn[id(b.bn3)]
+        if pending is not None:
+            # attn_aug_conv.py:202-211 of the block below + :188 of this one: out = relu(bn3(y3) + identity) is computed in this
+            # conv1's prologue (hi plane = its operand) and leaves as hi / lo / sign-bit side outputs -- no pass of its own
+            tp, Sp, mkp = pending
+            rows = ops.conv_gemm(tp["y3"], self.w_fwd(b.conv1), t["y1"], N=p_, prologue=ops.PRO_JOIN, x2=tp["id_hi"], x3=tp["id_lo"],
+                                 pa=v(ws, Sp.sc), pb=v(ws, self.ones, self._cin(b)), pc=v(ws, Sp.sh), pro_out=tp["out"],
+                                 po_lo=tp.get("out_lo"), po_mask=mkp, **self._sp(ws, S1))
+        else:
+            rows = ops.conv_gemm(xin, self.w_fwd(b.conv1), t["y1"], N=p_, **self._sp(ws, S1))
+        self._bn_coef(ws, b.bn1, ws.B * hi * wi, train, rows)
+        if isinstance(b.conv2, AAConv2d):
+            # attn_aug_conv.py:65-97: 3x3 conv branch || multi-head attention over the stride-s grid, concatenated on channels
+            self._aa_fwd(ws, b.conv2, t["y1"], t["y2"], t, b.bn2, s_, cnt, self._pro_bnrelu(ws, S1))
+        else:
+            # conv3x3(width, width, stride, groups, dilation) (attn_aug_conv.py:183): one launch per group on its channel slice of
+            # y1 / y2; the statistic rows of the groups sit side by side at the pitch of the whole BatchNorm
+            d_, gr = b.conv2.dilation[0], b.conv2.groups          # d > 1 under replace_stride_with_dilation: padding = dilation, stride 1
+            kg = p_ // gr
+            for g_ in range(gr):
+                c_, wg = (slice(g_ * kg, (g_ + 1) * kg), g_) if gr > 1 else (None, None)
+                kw = self._sp(ws, S2)
+                rows = ops.conv_gemm(self._ch(t["y1"], c_), self.w_fwd(b.conv2, wg), self._ch(t["y2"], c_), N=kg, kh=3, kw=3, stride=s_,
+                                     pad=d_, dil=d_, **self._pro_bnrelu(ws, S1, c_), **(kw if c_ is None else self._stat_slice(kw, c_)))
+            self._bn_coef(ws, b.bn2, cnt, train, rows)
+        rows = ops.conv_gemm(t["y2"], self.w_fwd(b.conv3), t["y3"], N=S3.C, **self._pro_bnrelu(ws, S2), **self._sp(ws, S3))
+        self._bn_coef(ws, b.bn3, cnt, train, rows)
+        return t["out"], t.get("out_lo"), self._join_forward(ws, bi, xin, xin_lo)
+
+    def _down_forward(self, ws, b, t, xin):
+        """the 1x1 stride-s convolution of a downsample block and the coefficients of its BatchNorm, whose slot is returned"""
+        ho, wo = t["hout"]
+        Sd = self.bn[id(b.downsample[1])]
+        rows = ops.conv_gemm(xin, self.w_fwd(b.downsample[0]), t["yd"], N=Sd.C, stride=b.stride, **self._sp(ws, Sd))
+        self._bn_coef(ws, b.downsample[1], ws.B * ho * wo, not ws.frozen, rows)
+        return Sd
+
+    def _join_forward(self, ws, bi, xin, xin_lo):
+        """The residual join of block bi, out = relu(bn_last(y) + (bn_d(downsample(x)) | x)), on the last convolution's raw output
+        y.  An identity join of fuse_fwd is not computed here: it is returned as `pending` = (t, slot of bn_last, mask) for the next
+        block's conv1 (else None).  A lo plane is read / written where the stream has one (keep_lo)."""
+        v, b, t = self._v, self.blocks[bi], ws.blk[bi]
+        S = self.bn[id(self._last_bn(b))]
+        y, ones = t["y2" if self.basic else "y3"], v(ws, self.ones, S.C)
+        mk = t["mask"] if ws.recorded else None
+        lo_out = t.get("out_lo")
+        if b.downsample is not None:
+            Sd = self._down_forward(ws, b, t, xin)
+            jc = v(ws, self.join[bi][2])
+            torch.add(v(ws, S.sh), v(ws, Sd.sh), out=jc)
+            if lo_out is not None:       # both operands are raw convolution outputs; the stream starts here with 16 significant bits
+                ops.join_fwd(y, t["yd"], None, v(ws, S.sc), v(ws, Sd.sc), jc, t["out"], lo_out, mk)
+            else:
+                ops.affine2_relu(y, t["yd"], v(ws, S.sc), v(ws, Sd.sc), jc, t["out"], mk)
+        elif self.fuse_fwd[bi] and S.C % 64 == 0 and t["out"].numel() * 2 < (1 << 32):
+            t["id_hi"], t["id_lo"] = xin, xin_lo
+            return t, S, mk
+        elif lo_out is not None or xin_lo is not None:
+            ops.join_fwd(y, xin, xin_lo, v(ws, S.sc), ones, v(ws, S.sh), t["out"], lo_out, mk)
+        else:
+            ops.affine2_relu(y, xin, v(ws, S.sc), ones, v(ws, S.sh), t["out"], mk)
+        return None
 
     # ---- backward
     def _alloc_bwd(self, ws):
@@ -478,265 +517,211 @@ class _Engine(FusedEngine):
         return self.det and not self.cifar          # the CIFAR stem keeps immediate sums (read back at once)
 
     def _backward(self, ws, dlogits, dx, done):
-        m, v, G = self.model, self._v, self.grad_of
-        B = ws.B
         self._alloc_bwd(ws)
-        bw = ws.bwd
         z0, zn = self.bwd_zero
         ws.vec[z0:z0 + zn].zero_()
-        det = self.det
-        ew = lambda C: min(self.EW_ROWS, self.SLAB // C)
-
-        def msp(S_):         # statistics arguments of a mask-epilogue producer of BatchNorm S_'s backward sums
-            if det:
-                return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // S_.C, stat_rstride=S_.C)
-            return dict(stat_sum=v(ws, S_.S1), stat_sq=v(ws, S_.S2))
-
-        def srows(S_, rows, second=None):      # (S1, S2, replicas, rstride) for cx_bn_bwd_coef
-            if det:
-                return ws.slab[0], (ws.slab[1] if second is None else second), rows, S_.C
-            return v(ws, S_.S1), v(ws, S_.S2), 1, 0
-        ones = lambda n: v(ws, self.ones, n)
-        zeros = lambda n: v(ws, self.zeros, n)
-        last = ws.blk[-1]["out"]
-        dpooled = torch.empty(B, last.shape[3], dtype=torch.float32, device=self.device)
-        ops.head_bwd(dlogits, ws.pooled, m.fc.weight, G(m.fc.weight), G(m.fc.bias) if m.fc.bias is not None else None, dpooled)
-        g = bw["g"][-1]
-        Cl = last.shape[3]
-        ops.gap_relu_bn_bwd(dpooled, last, ones(Cl), zeros(Cl), zeros(Cl), ones(Cl), ones(Cl), g, v(ws, self.scratch[0], Cl),
-                            v(ws, self.scratch[1], Cl))
+        self._head_backward(ws, dlogits)
         join_rows = None        # statistic rows of a join backward that ran in the epilogue of the block above (CX_EPI_JOIN)
         for bi in range(len(self.blocks) - 1, -1, -1):
-            b, t = self.blocks[bi], ws.blk[bi]
-            s_, p_ = b.stride, b.bn1.num_features
-            o_ = self._last_bn(b).num_features
-            hi, wi = t["hin"]
-            ho, wo = t["hout"]
-            cin = self._cin(b)
-            xin = ws.blk[bi - 1]["out"] if bi > 0 else ws.pool0
             if self.basic:
-                self._basic_backward(ws, bi, b, t, xin, msp, srows, ew, done)
-                continue
-            S1, S2, S3 = self.bn[id(b.bn1)], self.bn[id(b.bn2)], self.bn[id(b.bn3)]
-            Sd = self.bn[id(b.downsample[1])] if b.downsample is not None else None
-            g = bw["g"][bi]
-            # residual join backward: dz = dOut * [out > 0] (in place), statistics for bn3 (and the downsample BN)
-            cnt_o, cnt_i = B * ho * wo, B * hi * wi
-            if join_rows is not None:
-                # the conv1 input gradient of the block above finished dOut and ran this join in its epilogue (CX_EPI_JOIN)
-                rows, join_rows = join_rows, None
-            elif det:
-                rows = ops.relu_bwd_stats(g, t["out"], t["y3"], v(ws, S3.mean), v(ws, S3.rstd), t["yd"], v(ws, Sd.mean) if Sd else None,
-                                          v(ws, Sd.rstd) if Sd else None, g, ws.slab[0], ws.slab[1], ws.slab[2] if Sd else None,
-                                          stat_rows=ew(S3.C), mask=t["mask"])
+                self._basic_backward(ws, bi, done)
             else:
-                rows = None
-                ops.relu_bwd_stats(g, t["out"], t["y3"], v(ws, S3.mean), v(ws, S3.rstd), t["yd"], v(ws, Sd.mean) if Sd else None,
-                                   v(ws, Sd.rstd) if Sd else None, g, v(ws, S3.S1), v(ws, S3.S2), v(ws, Sd.S2) if Sd else None,
-                                   mask=t["mask"])
-            r3 = srows(S3, rows)
-            self.bn_bwd_coef(ws, b.bn3, r3[0], r3[1], cnt_o, b.bn3.weight, v(ws, S3.mean), v(ws, S3.rstd), G(b.bn3.weight),
-                             G(b.bn3.bias), None, None, v(ws, S3.pa), v(ws, S3.pb), v(ws, S3.pc), S3.C, replicas=r3[2], rstride=r3[3])
-            if Sd is not None and det:       # the downsample BatchNorm shares S1 with bn3: reduce it before the rows are re-used
-                bnd = b.downsample[1]
-                rd = srows(S3, rows, ws.slab[2])
-                self.bn_bwd_coef(ws, bnd, rd[0], rd[1], cnt_o, bnd.weight, v(ws, Sd.mean), v(ws, Sd.rstd), G(bnd.weight), G(bnd.bias),
-                                 None, None, v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc), Sd.C, replicas=rd[2], rstride=rd[3])
-            dz2 = bw["dz2"][:B * ho * wo * p_].view(B, ho, wo, p_)
-            rows = ops.conv_gemm(g, self.w_bwd(b.conv3), dz2, N=p_, prologue=ops.PRO_AFFINE2, x2=t["y3"], pa=v(ws, S3.pa),
-                                 pb=v(ws, S3.pb), pc=v(ws, S3.pc), epilogue=ops.EPI_MASK, ex=t["y2"], e_sc=v(ws, S2.sc),
-                                 e_sh=v(ws, S2.sh), e_mu=v(ws, S2.mean), e_r=v(ws, S2.rstd), e_scale=ones(p_), **msp(S2))
-            r2 = srows(S2, rows)
-            ops.conv_wgrad(g, t["y2"], G(b.conv3.weight), g_prologue=ops.PRO_AFFINE2, g2=t["y3"], ga=v(ws, S3.pa), gb=v(ws, S3.pb),
-                           gc=v(ws, S3.pc), x_prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S2.sc), pb=v(ws, S2.sh))
-            self.bn_bwd_coef(ws, b.bn2, r2[0], r2[1], cnt_o, b.bn2.weight, v(ws, S2.mean), v(ws, S2.rstd), G(b.bn2.weight),
-                             G(b.bn2.bias), None, None, v(ws, S2.pa), v(ws, S2.pb), v(ws, S2.pc), S2.C, replicas=r2[2], rstride=r2[3])
-            dz1 = bw["dz1"][:B * hi * wi * p_].view(B, hi, wi, p_)
-            mask1 = dict(epilogue=ops.EPI_MASK, ex=t["y1"], e_sc=v(ws, S1.sc), e_sh=v(ws, S1.sh), e_mu=v(ws, S1.mean),
-                         e_r=v(ws, S1.rstd), e_scale=ones(p_), **msp(S1))
-            if isinstance(b.conv2, AAConv2d):
-                aa = b.conv2
-                cc = p_ - aa.dv
-                qa, qb, qc = v(ws, S2.pa), v(ws, S2.pb), v(ws, S2.pc)          # BN2 backward as dY2 = dz2*pa + y2*pb + pc
-                gs_c, ys_c, gs_a, ys_a = dz2[..., :cc], t["y2"][..., :cc], dz2[..., cc:], t["y2"][..., cc:]
-                dO = bw["dO"][:t["O"].numel()].view(t["O"].shape)
-                dQ32 = bw["dQKV32"][:t["QKV"].numel()].view(t["QKV"].shape)
-                dQ = bw["dQKV"][:t["QKV"].numel()].view(t["QKV"].shape)
-                ops.aa_outproj_bwd(gs_a, ys_a, qa[cc:], qb[cc:], qc[cc:], t["O"], aa.out_proj.weight, dO, G(aa.out_proj.weight))
-                ops.aa_attention_bwd(t["QKV"], *aa.rel_tables(), t["O"], dO, t["LSE"], dQ32, *aa.rel_grads(G), aa.nh, aa.dk, aa.dv)
-                if self.dtype == torch.float32:
-                    dQ = dQ32
-                else:
-                    ops.f32_to_bf16(dQ32, dQ)
-                # both branches end in the same bn1 + ReLU mask: the conv branch writes dz1, the attention branch adds to it
-                rows = ops.conv_gemm(gs_c, self.w_bwd(aa.conv), dz1, N=p_, kh=3, kw=3, pad=1, tstride=s_, prologue=ops.PRO_AFFINE2, x2=ys_c,
-                                     pa=qa[:cc], pb=qb[:cc], pc=qc[:cc], **mask1)
-                rows2 = ops.conv_gemm(dQ, self.w_bwd(aa.in_proj_qkv), dz1, N=p_, tstride=s_, accumulate=True,
-                                      **self._stacked(ws, mask1, rows or 0, S1.C))
-                rows = (rows or 0) + (rows2 or 0) if det else None
-                ops.conv_wgrad(gs_c, t["y1"], G(aa.conv.weight), kh=3, kw=3, stride=s_, pad=1, g_prologue=ops.PRO_AFFINE2, g2=ys_c,
-                               ga=qa[:cc], gb=qb[:cc], gc=qc[:cc], x_prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S1.sc), pb=v(ws, S1.sh))
-                ops.conv_wgrad(dQ, t["y1"], G(aa.in_proj_qkv.weight), stride=s_, x_prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S1.sc),
-                               pb=v(ws, S1.sh))
-            else:
-                d_ = b.conv2.dilation[0]              # (a dilated conv2 has stride 1: its input gradient's padding is d (2d - d))
-                gr = b.conv2.groups
-                kg = p_ // gr
-                for g_ in range(gr):
-                    c_ = slice(g_ * kg, (g_ + 1) * kg) if gr > 1 else slice(0, p_)
-                    m1 = mask1 if gr == 1 else dict(epilogue=ops.EPI_MASK, ex=t["y1"][..., c_], e_sc=v(ws, S1.sc)[c_], e_sh=v(ws, S1.sh)[c_],
-                                                    e_mu=v(ws, S1.mean)[c_], e_r=v(ws, S1.rstd)[c_], e_scale=ones(kg),
-                                                    **self._stat_slice(msp(S1), c_))
-                    rows = ops.conv_gemm(dz2[..., c_], self.w_bwd(b.conv2, g_ if gr > 1 else None), dz1[..., c_], N=kg, kh=3, kw=3, pad=d_,
-                                         dil=d_, tstride=s_, prologue=ops.PRO_AFFINE2, x2=t["y2"][..., c_], pa=v(ws, S2.pa)[c_],
-                                         pb=v(ws, S2.pb)[c_], pc=v(ws, S2.pc)[c_], **m1)
-                    n_w = kg * kg * 9
-                    ops.conv_wgrad(dz2[..., c_], t["y1"][..., c_], G(b.conv2.weight)[g_ * n_w:(g_ + 1) * n_w] if gr > 1 else G(b.conv2.weight),
-                                   kh=3, kw=3, stride=s_, pad=d_, dil=d_, g_prologue=ops.PRO_AFFINE2, g2=t["y2"][..., c_],
-                                   ga=v(ws, S2.pa)[c_], gb=v(ws, S2.pb)[c_], gc=v(ws, S2.pc)[c_], x_prologue=ops.PRO_AFFINE_RELU,
-                                   pa=v(ws, S1.sc)[c_], pb=v(ws, S1.sh)[c_])
-            r1 = srows(S1, rows)
-            self.bn_bwd_coef(ws, b.bn1, r1[0], r1[1], cnt_i, b.bn1.weight, v(ws, S1.mean), v(ws, S1.rstd), G(b.bn1.weight),
-                             G(b.bn1.bias), None, None, v(ws, S1.pa), v(ws, S1.pb), v(ws, S1.pc), S1.C, replicas=r1[2], rstride=r1[3])
-            gx = (bw["g"][bi - 1] if bi > 0 else bw["g_in0"]) if Sd is not None or bi == 0 else g
-            identity = Sd is None
-            if identity and gx is not g:
-                gx.copy_(g)                      # first block of layer1 never is an identity block; defensive
-            prev = self.blocks[bi - 1] if bi > 0 else None
-            if (self.join_fuse and det and identity and prev is not None and prev.downsample is None and cin % 128 == 0
-                    and self.dtype == torch.bfloat16):
-                # dOut of the block below is complete with this launch (identity path already in gx): its join backward -- ReLU
-                # mask from the forward's sign bits, bn3 sums -- runs in the epilogue instead of a pass of its own over gx
-                tp, Sp = ws.blk[bi - 1], self.bn[id(prev.bn3)]
-                join_rows = ops.conv_gemm(dz1, self.w_bwd(b.conv1), gx, N=cin, prologue=ops.PRO_AFFINE2, x2=t["y1"], pa=v(ws, S1.pa),
-                                          pb=v(ws, S1.pb), pc=v(ws, S1.pc), accumulate=True, epilogue=ops.EPI_JOIN, ex=tp["y3"],
-                                          e_mu=v(ws, Sp.mean), e_r=v(ws, Sp.rstd), emask=tp["mask"], **msp(Sp))
-            else:
-                ops.conv_gemm(dz1, self.w_bwd(b.conv1), gx, N=cin, prologue=ops.PRO_AFFINE2, x2=t["y1"], pa=v(ws, S1.pa), pb=v(ws, S1.pb),
-                              pc=v(ws, S1.pc), accumulate=identity)
-            ops.conv_wgrad(dz1, xin, G(b.conv1.weight), g_prologue=ops.PRO_AFFINE2, g2=t["y1"], ga=v(ws, S1.pa), gb=v(ws, S1.pb),
-                           gc=v(ws, S1.pc))
-            if Sd is not None:
-                bnd, convd = b.downsample[1], b.downsample[0]
-                if not det:
-                    self.bn_bwd_coef(ws, bnd, v(ws, S3.S1), v(ws, Sd.S2), cnt_o, bnd.weight, v(ws, Sd.mean), v(ws, Sd.rstd), G(bnd.weight),
-                                     G(bnd.bias), None, None, v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc), Sd.C)
-                ops.conv_gemm(g, self.w_bwd(convd), gx, N=cin, tstride=s_, prologue=ops.PRO_AFFINE2, x2=t["yd"], pa=v(ws, Sd.pa),
-                              pb=v(ws, Sd.pb), pc=v(ws, Sd.pc), accumulate=True)
-                ops.conv_wgrad(g, xin, G(convd.weight), stride=s_, g_prologue=ops.PRO_AFFINE2, g2=t["yd"], ga=v(ws, Sd.pa),
-                               gb=v(ws, Sd.pb), gc=v(ws, Sd.pc))
-            done(b.conv1.weight)
-        # stem
-        S0 = self.bn[id(m.bn1)]
-        gx = bw["g_in0"]
+                join_rows = self._bottleneck_backward(ws, bi, join_rows, done)
         if self.cifar:
-            c0, cnt0 = m.conv1.out_channels, B * ws.H * ws.W
-            if det:
-                rows = ops.relu_bwd_stats(gx, ws.pool0, ws.c0, v(ws, S0.mean), v(ws, S0.rstd), None, None, None, bw["dz0"], ws.slab[0],
-                                          ws.slab[1], None, stat_rows=ew(c0))
-            else:
-                rows = None
-                ops.relu_bwd_stats(gx, ws.pool0, ws.c0, v(ws, S0.mean), v(ws, S0.rstd), None, None, None, bw["dz0"], v(ws, S0.S1),
-                                   v(ws, S0.S2), None)
-            r0 = srows(S0, rows)
-            self.bn_bwd_coef(ws, m.bn1, r0[0], r0[1], cnt0, m.bn1.weight, v(ws, S0.mean), v(ws, S0.rstd), G(m.bn1.weight), G(m.bn1.bias),
-                             None, None, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), c0, replicas=r0[2], rstride=r0[3])
-            dw8 = torch.zeros(c0, 8, 3, 3, dtype=torch.float32, device=self.device)       # 3 input channels padded to 8
-            ops.conv_wgrad(bw["dz0"], ws.x8, dw8, kh=3, kw=3, stride=1, pad=1, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=v(ws, S0.pa),
-                           gb=v(ws, S0.pb), gc=v(ws, S0.pc))
-            G(m.conv1.weight).view(c0, 3, 3, 3).add_(dw8[:, :3])
-            if dx is not None:
-                ops.stem_input_grad(bw["dz0"], ws.c0, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.conv1.weight, dx, stride=1, pad=1)
+            self._cifar_stem_backward(ws, dx)
         else:
-            if det:
-                rows = ops.bnrelu_maxpool_bwd(ws.c0, v(ws, S0.sc), v(ws, S0.sh), v(ws, S0.mean), v(ws, S0.rstd), ws.amax, gx, gx, ones(64),
-                                              zeros(64), zeros(64), bw["dz0"], ws.slab[0], ws.slab[1], stat_rows=ew(64))
-            else:
-                rows = None
-                ops.bnrelu_maxpool_bwd(ws.c0, v(ws, S0.sc), v(ws, S0.sh), v(ws, S0.mean), v(ws, S0.rstd), ws.amax, gx, gx, ones(64),
-                                       zeros(64), zeros(64), bw["dz0"], v(ws, S0.S1), v(ws, S0.S2))
-            r0 = srows(S0, rows)
-            self.bn_bwd_coef(ws, m.bn1, r0[0], r0[1], B * (ws.H // 2) * (ws.W // 2), m.bn1.weight, v(ws, S0.mean), v(ws, S0.rstd),
-                             G(m.bn1.weight), G(m.bn1.bias), None, None, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), 64, replicas=r0[2],
-                             rstride=r0[3])
-            ops.conv_wgrad(bw["dz0"], ws.x4, G(m.conv1.weight), mode=ops.MODE_STEM, g_prologue=ops.PRO_AFFINE2, g2=ws.c0,
-                           ga=v(ws, S0.pa), gb=v(ws, S0.pb), gc=v(ws, S0.pc))
-            if dx is not None:
-                ops.stem_input_grad(bw["dz0"], ws.c0, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.conv1.weight, dx, stride=2, pad=3)
+            self._stem_backward(ws, dx)
 
-    def _basic_backward(self, ws, bi, b, t, xin, msp, srows, ew, done):
-        """Backward of one BasicBlock (attn_aug_conv.py:135-156), same conventions as the bottleneck path: the block's output
-        gradient is masked in place by the join ReLU, BatchNorm backward rides in the two-tensor prologues of the consumers."""
-        v, G, bw, B, det = self._v, self.grad_of, ws.bwd, ws.B, self.det
+    def _head_backward(self, ws, dlogits):
+        m, v, G = self.model, self._v, self.grad_of
+        last = ws.blk[-1]["out"]
+        Cl = last.shape[3]
+        dpooled = torch.empty(ws.B, Cl, dtype=torch.float32, device=self.device)
+        ops.head_bwd(dlogits, ws.pooled, m.fc.weight, G(m.fc.weight), G(m.fc.bias) if m.fc.bias is not None else None, dpooled)
+        ones, zeros = v(ws, self.ones, Cl), v(ws, self.zeros, Cl)
+        ops.gap_relu_bn_bwd(dpooled, last, ones, zeros, zeros, ones, ones, ws.bwd["g"][-1], v(ws, self.scratch[0], Cl),
+                            v(ws, self.scratch[1], Cl))
+
+    def _join_backward(self, ws, bi, rows=None):
+        """Residual join backward of block bi: dz = dOut * [out > 0] in place in the block's gradient buffer g, with the backward
+        sums of the last BatchNorm and S2 of the downsample BatchNorm, then their coefficients.  rows: the pass already ran, in the
+        epilogue of the block above's conv1 input gradient (CX_EPI_JOIN), and left that many statistic rows."""
+        v, b, t, g = self._v, self.blocks[bi], ws.blk[bi], ws.bwd["g"][bi]
+        bn = self._last_bn(b)
+        S, Sd = self.bn[id(bn)], self.bn[id(b.downsample[1])] if b.downsample is not None else None
+        if rows is None:
+            s1, s2, n_rows = self._ew(ws, S)
+            rows = ops.relu_bwd_stats(g, t["out"], t["y2" if self.basic else "y3"], v(ws, S.mean), v(ws, S.rstd), t["yd"],
+                                      v(ws, Sd.mean) if Sd else None, v(ws, Sd.rstd) if Sd else None, g, s1, s2,
+                                      self._down_s2(ws, Sd) if Sd else None, stat_rows=n_rows, mask=t["mask"])
+        ho, wo = t["hout"]
+        self._bn_bwd(ws, bn, self._sc(ws, S, rows), ws.B * ho * wo)
+        if Sd is not None and (self.det or self.basic):       # (deterministic: before the next producer re-uses the rows)
+            self._down_bn_bwd(ws, b, t, rows)
+
+    def _down_bn_bwd(self, ws, b, t, rows):
+        """coefficients of the downsample BatchNorm, which shares S1 with the block's last BatchNorm (_down_s2)"""
+        ho, wo = t["hout"]
+        s1, _, reps, rstride = self._sc(ws, self.bn[id(self._last_bn(b))], rows)
+        self._bn_bwd(ws, b.downsample[1], (s1, self._down_s2(ws, self.bn[id(b.downsample[1])]), reps, rstride), ws.B * ho * wo)
+
+    def _gx(self, ws, bi):
+        """Where block bi's input gradient goes, and whether it is added there: an identity block's convolutions accumulate into
+        the block's own gradient buffer g (which holds the identity path already), a downsample block writes the buffer of the block
+        below."""
+        bw, g, identity = ws.bwd, ws.bwd["g"][bi], self.blocks[bi].downsample is None
+        gx = (bw["g"][bi - 1] if bi > 0 else bw["g_in0"]) if not identity or bi == 0 else g
+        if identity and gx is not g:
+            gx.copy_(g)                      # first block of layer1 never is an identity block; defensive
+        return gx, identity
+
+    def _aa_backward_front(self, ws, aa, t, dz, y, S):
+        """Backward of an AAConv2d's attention branch down to its projection: out-projection (with BatchNorm S's backward of the
+        gradient dz of [conv branch | attention] in its prologue), attention, dQKV in the storage type.  Returns dQKV and the
+        channel range of the conv branch."""
+        v, G, bw = self._v, self.grad_of, ws.bwd
+        cc = dz.shape[3] - aa.dv
+        dO = bw["dO"][:t["O"].numel()].view(t["O"].shape)
+        dQ32 = bw["dQKV32"][:t["QKV"].numel()].view(t["QKV"].shape)
+        dQ = bw["dQKV"][:t["QKV"].numel()].view(t["QKV"].shape)
+        ops.aa_outproj_bwd(dz[..., cc:], y[..., cc:], v(ws, S.pa)[cc:], v(ws, S.pb)[cc:], v(ws, S.pc)[cc:], t["O"], aa.out_proj.weight, dO,
+                           G(aa.out_proj.weight))
+        ops.aa_attention_bwd(t["QKV"], *aa.rel_tables(), t["O"], dO, t["LSE"], dQ32, *aa.rel_grads(G), aa.nh, aa.dk, aa.dv)
+        if self.dtype == torch.float32:
+            dQ = dQ32
+        else:
+            ops.f32_to_bf16(dQ32, dQ)
+        return dQ, slice(0, cc)
+
+    def _down_backward(self, ws, b, t, g, gx, xin):
+        """input and weight gradient of a downsample block's 1x1 stride-s convolution, BatchNorm backward in the prologues"""
+        Sd, convd = self.bn[id(b.downsample[1])], b.downsample[0]
+        if not (self.det or self.basic):         # (a Bottleneck's atomic sums: nothing re-uses them, the coefficients waited until here)
+            self._down_bn_bwd(ws, b, t, None)
+        ops.conv_gemm(g, self.w_bwd(convd), gx, N=self._cin(b), tstride=b.stride, **self._pro_bnbwd(ws, t["yd"], Sd), accumulate=True)
+        ops.conv_wgrad(g, xin, self.grad_of(convd.weight), stride=b.stride, **self._g_bnbwd(ws, t["yd"], Sd))
+
+    def _bottleneck_backward(self, ws, bi, join_rows, done):
+        """Backward of one Bottleneck: the block's output gradient is masked in place by the join ReLU, BatchNorm backward rides in
+        the two-tensor prologues of the consumers.  join_rows: see _join_backward; returns the same for the block below."""
+        G, bw, B = self.grad_of, ws.bwd, ws.B
+        b, t = self.blocks[bi], ws.blk[bi]
+        p_, cin = b.bn1.num_features, self._cin(b)
+        (hi, wi), (ho, wo) = t["hin"], t["hout"]
+        xin = ws.blk[bi - 1]["out"] if bi > 0 else ws.pool0
+        S1, S2, S3 = self.bn[id(b.bn1)], self.bn[id(b.bn2)], self.bn[id(b.bn3)]
+        g = bw["g"][bi]
+        self._join_backward(ws, bi, join_rows)
+        dz2 = bw["dz2"][:B * ho * wo * p_].view(B, ho, wo, p_)
+        rows = ops.conv_gemm(g, self.w_bwd(b.conv3), dz2, N=p_, **self._pro_bnbwd(ws, t["y3"], S3), **self._mask(ws, t["y2"], S2))
+        ops.conv_wgrad(g, t["y2"], G(b.conv3.weight), **self._g_bnbwd(ws, t["y3"], S3), **self._x_bnrelu(ws, S2))
+        self._bn_bwd(ws, b.bn2, self._sc(ws, S2, rows), B * ho * wo)
+        dz1 = bw["dz1"][:B * hi * wi * p_].view(B, hi, wi, p_)
+        rows = self._conv2_backward(ws, b, t, dz2, dz1)
+        self._bn_bwd(ws, b.bn1, self._sc(ws, S1, rows), B * hi * wi)
+        gx, identity = self._gx(ws, bi)
+        prev = self.blocks[bi - 1] if bi > 0 else None
+        join_rows = None
+        if (self.join_fuse and self.det and identity and prev is not None and prev.downsample is None and cin % 128 == 0
+                and self.dtype == torch.bfloat16):
+            # dOut of the block below is complete with this launch (identity path already in gx): its join backward -- ReLU
+            # mask from the forward's sign bits, bn3 sums -- runs in the epilogue instead of a pass of its own over gx
+            tp, Sp = ws.blk[bi - 1], self.bn[id(prev.bn3)]
+            join_rows = ops.conv_gemm(dz1, self.w_bwd(b.conv1), gx, N=cin, **self._pro_bnbwd(ws, t["y1"], S1), accumulate=True,
+                                      epilogue=ops.EPI_JOIN, ex=tp["y3"], e_mu=self._v(ws, Sp.mean), e_r=self._v(ws, Sp.rstd),
+                                      emask=tp["mask"], **self._sp(ws, Sp, bwd=True))
+        else:
+            ops.conv_gemm(dz1, self.w_bwd(b.conv1), gx, N=cin, **self._pro_bnbwd(ws, t["y1"], S1), accumulate=identity)
+        ops.conv_wgrad(dz1, xin, G(b.conv1.weight), **self._g_bnbwd(ws, t["y1"], S1))
+        if not identity:
+            self._down_backward(ws, b, t, g, gx, xin)
+        done(b.conv1.weight)
+        return join_rows
+
+    def _conv2_backward(self, ws, b, t, dz2, dz1):
+        """Input gradient dz1 (through bn1's ReLU mask, with bn1's backward sums) and weight gradients of a Bottleneck's conv2 from
+        dz2: the AAConv2d, or the 3x3 as one launch per group.  Returns the statistic rows."""
+        G, s_, p_ = self.grad_of, b.stride, b.bn1.num_features
+        S1, S2 = self.bn[id(b.bn1)], self.bn[id(b.bn2)]
+        if isinstance(b.conv2, AAConv2d):
+            aa = b.conv2
+            dQ, c_ = self._aa_backward_front(ws, aa, t, dz2, t["y2"], S2)
+            # both branches end in the same bn1 + ReLU mask: the conv branch writes dz1, the attention branch adds to it
+            rows = ops.conv_gemm(dz2[..., c_], self.w_bwd(aa.conv), dz1, N=p_, kh=3, kw=3, pad=1, tstride=s_,
+                                 **self._pro_bnbwd(ws, t["y2"], S2, c_), **self._mask(ws, t["y1"], S1))
+            rows2 = ops.conv_gemm(dQ, self.w_bwd(aa.in_proj_qkv), dz1, N=p_, tstride=s_, accumulate=True,
+                                  **self._mask(ws, t["y1"], S1, after=(rows or 0) if self.det else 0))
+            ops.conv_wgrad(dz2[..., c_], t["y1"], G(aa.conv.weight), kh=3, kw=3, stride=s_, pad=1, **self._g_bnbwd(ws, t["y2"], S2, c_),
+                           **self._x_bnrelu(ws, S1))
+            ops.conv_wgrad(dQ, t["y1"], G(aa.in_proj_qkv.weight), stride=s_, **self._x_bnrelu(ws, S1))
+            return (rows or 0) + (rows2 or 0)
+        d_, gr = b.conv2.dilation[0], b.conv2.groups      # (a dilated conv2 has stride 1: its input gradient's padding is d (2d - d))
+        kg, ch = p_ // gr, self._ch
+        n_w = kg * kg * 9
+        for g_ in range(gr):
+            c_, wg = (slice(g_ * kg, (g_ + 1) * kg), g_) if gr > 1 else (None, None)
+            rows = ops.conv_gemm(ch(dz2, c_), self.w_bwd(b.conv2, wg), ch(dz1, c_), N=kg, kh=3, kw=3, pad=d_, dil=d_, tstride=s_,
+                                 **self._pro_bnbwd(ws, t["y2"], S2, c_), **self._mask(ws, t["y1"], S1, c_))
+            ops.conv_wgrad(ch(dz2, c_), ch(t["y1"], c_), G(b.conv2.weight)[g_ * n_w:(g_ + 1) * n_w], kh=3, kw=3, stride=s_, pad=d_, dil=d_,
+                           **self._g_bnbwd(ws, t["y2"], S2, c_), **self._x_bnrelu(ws, S1, c_))
+        return rows
+
+    def _basic_backward(self, ws, bi, done):
+        """Backward of one BasicBlock (attn_aug_conv.py:135-156), same conventions as the bottleneck path."""
+        G, bw, B = self.grad_of, ws.bwd, ws.B
+        b, t = self.blocks[bi], ws.blk[bi]
         s_, p_, cin = b.stride, b.bn1.num_features, self._cin(b)
         ho, wo = t["hout"]
+        xin = ws.blk[bi - 1]["out"] if bi > 0 else ws.pool0
         S1, S2 = self.bn[id(b.bn1)], self.bn[id(b.bn2)]
-        Sd = self.bn[id(b.downsample[1])] if b.downsample is not None else None
         g = bw["g"][bi]
-        cnt = B * ho * wo
-        ones = v(ws, self.ones, p_)
-        if det:
-            rows = ops.relu_bwd_stats(g, t["out"], t["y2"], v(ws, S2.mean), v(ws, S2.rstd), t["yd"], v(ws, Sd.mean) if Sd else None,
-                                      v(ws, Sd.rstd) if Sd else None, g, ws.slab[0], ws.slab[1], ws.slab[2] if Sd else None,
-                                      stat_rows=ew(S2.C), mask=t["mask"])
-        else:
-            rows = None
-            ops.relu_bwd_stats(g, t["out"], t["y2"], v(ws, S2.mean), v(ws, S2.rstd), t["yd"], v(ws, Sd.mean) if Sd else None,
-                               v(ws, Sd.rstd) if Sd else None, g, v(ws, S2.S1), v(ws, S2.S2), v(ws, Sd.S2) if Sd else None,
-                               mask=t["mask"])
-        r2 = srows(S2, rows)
-        self.bn_bwd_coef(ws, b.bn2, r2[0], r2[1], cnt, b.bn2.weight, v(ws, S2.mean), v(ws, S2.rstd), G(b.bn2.weight), G(b.bn2.bias),
-                         None, None, v(ws, S2.pa), v(ws, S2.pb), v(ws, S2.pc), S2.C, replicas=r2[2], rstride=r2[3])
-        if Sd is not None:                   # the downsample BatchNorm shares S1 (sum of the masked gradient) with bn2
-            bnd = b.downsample[1]
-            rd = srows(S2, rows, ws.slab[2]) if det else (v(ws, S2.S1), v(ws, Sd.S2), 1, 0)
-            self.bn_bwd_coef(ws, bnd, rd[0], rd[1], cnt, bnd.weight, v(ws, Sd.mean), v(ws, Sd.rstd), G(bnd.weight), G(bnd.bias), None, None,
-                             v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc), Sd.C, replicas=rd[2], rstride=rd[3])
-        dz1 = bw["dz1"][:cnt * p_].view(B, ho, wo, p_)
-        rows = ops.conv_gemm(g, self.w_bwd(b.conv2), dz1, N=p_, kh=3, kw=3, pad=1, prologue=ops.PRO_AFFINE2, x2=t["y2"], pa=v(ws, S2.pa),
-                             pb=v(ws, S2.pb), pc=v(ws, S2.pc), epilogue=ops.EPI_MASK, ex=t["y1"], e_sc=v(ws, S1.sc), e_sh=v(ws, S1.sh),
-                             e_mu=v(ws, S1.mean), e_r=v(ws, S1.rstd), e_scale=ones, **msp(S1))
-        r1 = srows(S1, rows)
-        ops.conv_wgrad(g, t["y1"], G(b.conv2.weight), kh=3, kw=3, stride=1, pad=1, g_prologue=ops.PRO_AFFINE2, g2=t["y2"],
-                       ga=v(ws, S2.pa), gb=v(ws, S2.pb), gc=v(ws, S2.pc), x_prologue=ops.PRO_AFFINE_RELU, pa=v(ws, S1.sc), pb=v(ws, S1.sh))
-        self.bn_bwd_coef(ws, b.bn1, r1[0], r1[1], cnt, b.bn1.weight, v(ws, S1.mean), v(ws, S1.rstd), G(b.bn1.weight), G(b.bn1.bias),
-                         None, None, v(ws, S1.pa), v(ws, S1.pb), v(ws, S1.pc), S1.C, replicas=r1[2], rstride=r1[3])
-        gx = (bw["g"][bi - 1] if bi > 0 else bw["g_in0"]) if Sd is not None or bi == 0 else g
-        identity = Sd is None
-        if identity and gx is not g:
-            gx.copy_(g)
+        self._join_backward(ws, bi)
+        dz1 = bw["dz1"][:B * ho * wo * p_].view(B, ho, wo, p_)
+        rows = ops.conv_gemm(g, self.w_bwd(b.conv2), dz1, N=p_, kh=3, kw=3, pad=1, **self._pro_bnbwd(ws, t["y2"], S2),
+                             **self._mask(ws, t["y1"], S1))
+        ops.conv_wgrad(g, t["y1"], G(b.conv2.weight), kh=3, kw=3, stride=1, pad=1, **self._g_bnbwd(ws, t["y2"], S2), **self._x_bnrelu(ws, S1))
+        self._bn_bwd(ws, b.bn1, self._sc(ws, S1, rows), B * ho * wo)
+        gx, identity = self._gx(ws, bi)
         if isinstance(b.conv1, AAConv2d):
             aa = b.conv1
-            cc = p_ - aa.dv
-            qa, qb, qc = v(ws, S1.pa), v(ws, S1.pb), v(ws, S1.pc)              # BN1 backward as dY1 = dz1*pa + y1*pb + pc
-            gs_c, ys_c, gs_a, ys_a = dz1[..., :cc], t["y1"][..., :cc], dz1[..., cc:], t["y1"][..., cc:]
-            dO = bw["dO"][:t["O"].numel()].view(t["O"].shape)
-            dQ32 = bw["dQKV32"][:t["QKV"].numel()].view(t["QKV"].shape)
-            dQ = bw["dQKV"][:t["QKV"].numel()].view(t["QKV"].shape)
-            ops.aa_outproj_bwd(gs_a, ys_a, qa[cc:], qb[cc:], qc[cc:], t["O"], aa.out_proj.weight, dO, G(aa.out_proj.weight))
-            ops.aa_attention_bwd(t["QKV"], *aa.rel_tables(), t["O"], dO, t["LSE"], dQ32, *aa.rel_grads(G), aa.nh, aa.dk, aa.dv)
-            if self.dtype == torch.float32:
-                dQ = dQ32
-            else:
-                ops.f32_to_bf16(dQ32, dQ)
-            ops.conv_gemm(gs_c, self.w_bwd(aa.conv), gx, N=cin, kh=3, kw=3, pad=1, tstride=s_, prologue=ops.PRO_AFFINE2, x2=ys_c,
-                          pa=qa[:cc], pb=qb[:cc], pc=qc[:cc], accumulate=identity)
+            dQ, c_ = self._aa_backward_front(ws, aa, t, dz1, t["y1"], S1)
+            ops.conv_gemm(dz1[..., c_], self.w_bwd(aa.conv), gx, N=cin, kh=3, kw=3, pad=1, tstride=s_, **self._pro_bnbwd(ws, t["y1"], S1, c_),
+                          accumulate=identity)
             ops.conv_gemm(dQ, self.w_bwd(aa.in_proj_qkv), gx, N=cin, tstride=s_, accumulate=True)
-            ops.conv_wgrad(gs_c, xin, G(aa.conv.weight), kh=3, kw=3, stride=s_, pad=1, g_prologue=ops.PRO_AFFINE2, g2=ys_c, ga=qa[:cc],
-                           gb=qb[:cc], gc=qc[:cc])
+            ops.conv_wgrad(dz1[..., c_], xin, G(aa.conv.weight), kh=3, kw=3, stride=s_, pad=1, **self._g_bnbwd(ws, t["y1"], S1, c_))
             ops.conv_wgrad(dQ, xin, G(aa.in_proj_qkv.weight), stride=s_)
         else:
-            ops.conv_gemm(dz1, self.w_bwd(b.conv1), gx, N=cin, kh=3, kw=3, pad=1, tstride=s_, prologue=ops.PRO_AFFINE2, x2=t["y1"],
-                          pa=v(ws, S1.pa), pb=v(ws, S1.pb), pc=v(ws, S1.pc), accumulate=identity)
-            ops.conv_wgrad(dz1, xin, G(b.conv1.weight), kh=3, kw=3, stride=s_, pad=1, g_prologue=ops.PRO_AFFINE2, g2=t["y1"],
-                           ga=v(ws, S1.pa), gb=v(ws, S1.pb), gc=v(ws, S1.pc))
-        if Sd is not None:
-            convd = b.downsample[0]
-            ops.conv_gemm(g, self.w_bwd(convd), gx, N=cin, tstride=s_, prologue=ops.PRO_AFFINE2, x2=t["yd"], pa=v(ws, Sd.pa),
-                          pb=v(ws, Sd.pb), pc=v(ws, Sd.pc), accumulate=True)
-            ops.conv_wgrad(g, xin, G(convd.weight), stride=s_, g_prologue=ops.PRO_AFFINE2, g2=t["yd"], ga=v(ws, Sd.pa), gb=v(ws, Sd.pb),
-                           gc=v(ws, Sd.pc))
+            ops.conv_gemm(dz1, self.w_bwd(b.conv1), gx, N=cin, kh=3, kw=3, pad=1, tstride=s_, **self._pro_bnbwd(ws, t["y1"], S1),
+                          accumulate=identity)
+            ops.conv_wgrad(dz1, xin, G(b.conv1.weight), kh=3, kw=3, stride=s_, pad=1, **self._g_bnbwd(ws, t["y1"], S1))
+        if not identity:
+            self._down_backward(ws, b, t, g, gx, xin)
         done(b.conv1.weight if not isinstance(b.conv1, AAConv2d) else b.conv1.first_param())
+
+    def _stem_backward(self, ws, dx):
+        """max-pool + ReLU + BatchNorm backward in one kernel, weight gradient of the 7x7 convolution, input gradient when asked"""
+        m, v, G = self.model, self._v, self.grad_of
+        S0, gx, dz0 = self.bn[id(m.bn1)], ws.bwd["g_in0"], ws.bwd["dz0"]
+        s1, s2, n_rows = self._ew(ws, S0)
+        rows = ops.bnrelu_maxpool_bwd(ws.c0, v(ws, S0.sc), v(ws, S0.sh), v(ws, S0.mean), v(ws, S0.rstd), ws.amax, gx, gx, v(ws, self.ones, 64),
+                                      v(ws, self.zeros, 64), v(ws, self.zeros, 64), dz0, s1, s2, stat_rows=n_rows)
+        self._bn_bwd(ws, m.bn1, self._sc(ws, S0, rows), ws.B * (ws.H // 2) * (ws.W // 2))
+        ops.conv_wgrad(dz0, ws.x4, G(m.conv1.weight), mode=ops.MODE_STEM, **self._g_bnbwd(ws, ws.c0, S0))
+        if dx is not None:
+            ops.stem_input_grad(dz0, ws.c0, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.conv1.weight, dx, stride=2, pad=3)
+
+    def _cifar_stem_backward(self, ws, dx):
+        m, v, G = self.model, self._v, self.grad_of
+        S0, gx, dz0 = self.bn[id(m.bn1)], ws.bwd["g_in0"], ws.bwd["dz0"]
+        c0 = m.conv1.out_channels
+        s1, s2, n_rows = self._ew(ws, S0)
+        rows = ops.relu_bwd_stats(gx, ws.pool0, ws.c0, v(ws, S0.mean), v(ws, S0.rstd), None, None, None, dz0, s1, s2, None, stat_rows=n_rows)
+        self._bn_bwd(ws, m.bn1, self._sc(ws, S0, rows), ws.B * ws.H * ws.W)
+        dw8 = torch.zeros(c0, 8, 3, 3, dtype=torch.float32, device=self.device)       # 3 input channels padded to 8
+        ops.conv_wgrad(dz0, ws.x8, dw8, kh=3, kw=3, stride=1, pad=1, **self._g_bnbwd(ws, ws.c0, S0))
+        G(m.conv1.weight).view(c0, 3, 3, 3).add_(dw8[:, :3])
+        if dx is not None:
+            ops.stem_input_grad(dz0, ws.c0, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.conv1.weight, dx, stride=1, pad=1)
 
 
 class ResNet(FusedNet):

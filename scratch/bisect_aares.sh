@@ -10,6 +10,4 @@ run() {
 run CHEXPERT_STREAM_LO=1 CHEXPERT_FWD_JOIN_FUSE=1
 run CHEXPERT_STREAM_LO=0
 run CHEXPERT_STREAM_LO=1 CHEXPERT_FWD_JOIN_FUSE=0
-run CHEXPERT_STREAM_LO_MIN=1
-run CHEXPERT_STREAM_LO_MIN=1 CHEXPERT_FWD_JOIN_FUSE=0
 cat $O
