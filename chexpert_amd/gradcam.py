@@ -9,7 +9,7 @@ the normalised, bilinearly up-sampled maps.  `hooks` / `cls_idx` are accepted fo
 """
 import torch
 
-from . import _lib as L
+from . import ops
 
 
 def _targets(model, eng, ws, dev):
@@ -47,7 +47,6 @@ class _HookedLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        from . import ops
         lin, pooled = ctx.linear, ctx.pooled
         dl = dlogits.contiguous().float()
         dw = torch.zeros_like(lin.weight)
@@ -71,15 +70,11 @@ def hooked_eval_forward(model, x):
         feat = torch.empty(B, C, h, w, dtype=torch.float32, device=x.device)
         if buf.dtype != torch.bfloat16:
             raise NotImplementedError("hooks are served from the bf16 engine")
-
-        def fill(relu):
-            L.check(L.lib().cx_affine_to_f32_nchw(L.ptr(buf), L.ptr(sc), L.ptr(sh), int(relu), L.ptr(feat), B, h, w, C, buf.stride(2),
-                                                  L.stream_ptr()), "cx_affine_to_f32_nchw")
-        fill(False)
+        ops.affine_to_f32_nchw(buf, sc, sh, False, feat)
         for hook in list(hooked._forward_hooks.values()):
             hook(hooked, (None,), feat)
-        if relu_after:
-            fill(True)                       # F.relu(features, inplace=True) of the reference mutates the hooked tensor (:514)
+        if relu_after:                       # F.relu(features, inplace=True) of the reference mutates the hooked tensor (:514)
+            ops.affine_to_f32_nchw(buf, sc, sh, True, feat)
         logits, pooled = ws.logits.clone(), ws.pooled.clone()
     finally:
         eng.release(ws)
@@ -120,11 +115,9 @@ def grad_cam(model, x, hooks=None, cls_idx=None):
         n_cls = ws.logits.shape[1]
         wts = (ws.pooled.sum(0) / n_cls).contiguous()
         cam = torch.empty(B, h * w, dtype=torch.float32, device=dev)
-        L.check(L.lib().cx_gradcam_map(L.ptr(buf), L.ptr(sc), L.ptr(sh), L.ptr(wts), L.ptr(cam), B, h * w, C, buf.stride(2), inner,
-                                        L.stream_ptr()), "cx_gradcam_map")
+        ops.gradcam_map(buf, sc, sh, wts, cam, inner)
         out = torch.empty(B, 1, x.shape[2], x.shape[3], dtype=torch.float32, device=dev)
-        L.check(L.lib().cx_cam_norm_upsample(L.ptr(cam), L.ptr(out), B, h, w, x.shape[2], x.shape[3], L.stream_ptr()),
-                "cx_cam_norm_upsample")
+        ops.cam_norm_upsample(cam, out, h, w)
     finally:
         eng.release(ws)
         model.train(was_training)

@@ -24,7 +24,6 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .._lib import check, lib, ptr, stream_ptr
 from ._fused import FusedEngine, FusedNet, _Vec, flatten
 
 
@@ -534,8 +533,7 @@ class _Engine(FusedEngine):
         convolution that writes block 1's first channels and leaves their statistic rows."""
         f, s = self.model.features, self.slots
         B, H, W = ws.B, ws.H, ws.W
-        name = "cx_nchw3_to_nhwc8" if self.dtype == torch.bfloat16 else "cx_nchw3_to_nhwc8_f32"
-        check(getattr(lib(), name)(ptr(x.contiguous().float()), ptr(ws.x8), B, H, W, stream_ptr()), name)
+        ops.nchw3_to_nhwc8(x.contiguous().float(), ws.x8)
         rows = ops.conv_gemm(ws.x8, self.w_fwd(f.conv0), ws.c0, N=self.c_init, kh=5, kw=5, pad=2, **sp(None, self.c_init))
         st0 = (ws.slab[0], ws.slab[1], rows, self.c_init) if train else None
         self._bn(ws, st0, B * H * W, f.norm0, s["n0"][:2], self.c_init, train, s["n0"][2], s["n0"][3])
@@ -1058,7 +1056,7 @@ class _PaddedEngine(FusedEngine):
         self.n_classes = self.model.classifier.out_features
 
     def _map(self, real, padded, tab, direction, accumulate=0):
-        check(lib().cx_chan_map_table(ptr(real), ptr(padded), ptr(tab[0]), tab[1], direction, accumulate, stream_ptr()), "cx_chan_map_table")
+        ops.chan_map_table(real, padded, tab[0], tab[1], direction, accumulate)
 
     def forward(self, x, train, record=False):
         self.bind(x.device)

@@ -22,7 +22,6 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .._lib import check, lib, ptr, stream_ptr
 from ._fused import FusedEngine, FusedNet, _BN
 from .densenet import BatchNorm2dParams, Conv2dParams, PoolMarker, _FusedOnly
 
@@ -85,17 +84,8 @@ def same_pad(h_in, k, stride):
     return math.ceil(max((h_out - 1) * stride - h_in + (k - 1) + 1, 0) / 2)
 
 
-class _LibF32:
-    """The C ABI with the `_f32` twin of an entry point where one exists (the fp32 storage mode)."""
-
-    def __init__(self, l):
-        self._l = l
-
-    def __getattr__(self, name):
-        return getattr(self._l, name + "_f32", None) or getattr(self._l, name)
-
-
 class _Engine(FusedEngine):
+    # forward / _backward are drivers over per-block methods (stem, MBConv block, head), as in the DenseNet and ResNet engines
     # (fp32 storage: generic f32-MFMA convolutions, the storage-typed depthwise / squeeze-excite / Swish kernels of csrc/effnet.hip,
     # no tiled fast paths; deterministic mode: one owner per squeeze-excite sum)
     def __init__(self, model):
@@ -103,6 +93,8 @@ class _Engine(FusedEngine):
         self.mb = [b for rep in model.blocks for b in rep]
         self.mb_names = ["blocks.%d.%d" % (si, bi) for si, rep in enumerate(model.blocks) for bi, _ in enumerate(rep)]
         self.last_masks = {}         # name -> mask / keep of the most recent train-mode forward (tests, reproducibility)
+        self.n_forward = 0           # forwards so far (ws.step)
+        self.step_dev = None         # device-side count of the training forwards: what the Dropout / DropConnect masks are drawn from
         self.bns = [model.stem[1]] + [m for b in self.mb for m in b if isinstance(m, nn.BatchNorm2d)] + [model.head[1]]
         self.bn, rest, self.fwd_zero, self.bwd_zero = _BN.plan(self.bns)
         self.ones = rest.take(max(bn.num_features for bn in self.bns))
@@ -160,14 +152,11 @@ class _Engine(FusedEngine):
         ws.slab = torch.empty(2, self.SLAB, dtype=f32, device=dev) if self.det else None
         o, n = self.ones
         ws.vec[o:o + n].fill_(1.0)
-        ws.bwd = None
+        ws.bwd = ws.dw8 = None
         return ws
 
     SLAB = 1 << 22               # floats per half of the statistic-row scratch
     ROWS = 2048                  # most statistic rows an element-wise / depthwise producer writes
-
-    def _rows_cap(self, C):
-        return min(self.ROWS, self.SLAB // C)
 
     @staticmethod
     def _parts(b):
@@ -179,11 +168,48 @@ class _Engine(FusedEngine):
             i = 3
         return conv_e, bn_e, mods[i], mods[i + 1], mods[i + 3], mods[i + 4], mods[i + 5]      # dw, bn_d, se, conv_p, bn_p
 
+    # ---- statistics plumbing for the two modes (deterministic: rows in ws.slab; CHEXPERT_DET=0: atomic sums in the _BN slots), named
+    # as in the ResNet engine: keywords of a convolution producer (_sp), (S1, S2, stat_rows) of an element-wise / depthwise producer
+    # (_ew), (S1, S2, replicas, rstride) for the consumer (_sc); _rows is the row scratch of the per-(image, channel) sums
+    def _sp(self, ws, S):
+        """Statistics keywords of a convolution that produces BatchNorm S's forward sums (none in an eval forward)."""
+        if ws.frozen:
+            return dict(stat_sum=None, stat_sq=None)
+        if self.det:
+            return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // S.C, stat_rstride=S.C)
+        return dict(stat_sum=self._v(ws, S.sum), stat_sq=self._v(ws, S.sq))
+
+    def _ew(self, ws, S, bwd=False):
+        """Where an element-wise / depthwise producer leaves BatchNorm S's forward sums (nowhere in an eval forward) or, with `bwd`,
+        its backward sums S1 / S2."""
+        if ws.frozen and not bwd:
+            return None, None, 0
+        if self.det:
+            return ws.slab[0], ws.slab[1], min(self.ROWS, self.SLAB // S.C)
+        a, b = (S.S1, S.S2) if bwd else (S.sum, S.sq)
+        return self._v(ws, a), self._v(ws, b), 0
+
+    def _sc(self, ws, S, rows):
+        if self.det:
+            return ws.slab[0], ws.slab[1], rows, S.C
+        return self._v(ws, S.S1), self._v(ws, S.S2), 1, 0
+
+    def _rows(self, ws):
+        """(free between a coefficient launch and the next statistics producer)"""
+        return ws.slab[0] if self.det else None
+
+    def _pro_bnbwd(self, ws, y, S):
+        """input gradient: BatchNorm S's backward of the gradient operand, dY = dz * pa + y * pb + pc"""
+        return dict(prologue=ops.PRO_AFFINE2, x2=y, pa=self._v(ws, S.pa), pb=self._v(ws, S.pb), pc=self._v(ws, S.pc))
+
+    def _g_bnbwd(self, ws, y, S):
+        """weight gradient: the same of its gradient operand"""
+        return dict(g_prologue=ops.PRO_AFFINE2, g2=y, ga=self._v(ws, S.pa), gb=self._v(ws, S.pb), gc=self._v(ws, S.pc))
+
     # ---- forward
     def forward(self, x, train, record=False):
         """train: batch statistics, Dropout / DropConnect; eval: running statistics, no masks.  Every forward keeps what backward
         reads (activations and squeeze-excite intermediates), so `record` changes nothing here."""
-        m, v, lb = self.model, self._v, (_LibF32(lib()) if self.dtype == torch.float32 else lib())
         u8 = x.dtype == torch.uint8             # decoded grey bytes (B,1,H,W): whitened + expanded on the GPU (cx_u8_to_nhwc8)
         if x.dim() != 4 or x.shape[1] != (1 if u8 else 3):
             raise RuntimeError("expected a (B,3,H,W) float input or a (B,1,H,W) uint8 image")
@@ -193,97 +219,90 @@ class _Engine(FusedEngine):
         ws = self.acquire(B, H, W)
         self.recorded(ws, train, True)
         self.last_masks = {}
-        self.n_forward = getattr(self, "n_forward", 0) + 1
+        self.n_forward += 1
         ws.step = self.n_forward
         if train:
             # the masks' step counter lives in device memory and is bumped by a kernel: a captured step (graph.py) draws new
             # Dropout / DropConnect masks at every replay, and the eager step draws the same ones
-            if getattr(self, "step_dev", None) is None or self.step_dev.device != x.device:
+            if self.step_dev is None or self.step_dev.device != x.device:
                 self.step_dev = torch.zeros(1, dtype=torch.int64, device=x.device)
-            check(lb.cx_counter_add(ptr(self.step_dev), 1, stream_ptr()), "cx_counter_add")
-        det = self.det and train
-        if train and not det:
-            z0, zn = self.fwd_zero
-            ws.vec[z0:z0 + zn].zero_()
-        st = (lambda s: v(ws, s)) if train else (lambda s: None)
-        # statistics arguments of a convolution feeding BatchNorm S_, of a depthwise producer (sum, sq, stat_rows)
-        csp = (lambda S_: dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // S_.C, stat_rstride=S_.C)) \
-            if det else (lambda S_: dict(stat_sum=st(S_.sum), stat_sq=st(S_.sq)))
-        dsp = (lambda S_: (ptr(ws.slab[0]), ptr(ws.slab[1]), self._rows_cap(S_.C))) if det else \
-            (lambda S_: (ptr(st(S_.sum)), ptr(st(S_.sq)), 0))
-        sp = stream_ptr()
-        # row scratch of the per-(image, channel) sums (free between a coefficient launch and the next statistics producer)
-        rsc = (ptr(ws.slab[0]), self.SLAB) if self.det else (None, 0)
-        S0 = self.bn[id(m.stem[1])]
+            ops.counter_add(self.step_dev)
+            if not self.det:
+                z0, zn = self.fwd_zero
+                ws.vec[z0:z0 + zn].zero_()
         if u8:
-            check(lb.cx_u8_to_nhwc8(ptr(x.contiguous()), ptr(ws.x8), B * H * W, 0.5330, 0.0349, sp), "cx_u8_to_nhwc8")
+            ops.u8_to_nhwc8(x.contiguous(), ws.x8)
         else:
-            check(lb.cx_nchw3_to_nhwc8(ptr(x.contiguous().float()), ptr(ws.x8), B, H, W, sp), "cx_nchw3_to_nhwc8")
-        c0 = m.stem[0].out_channels
-        rows = ops.conv_gemm(ws.x8, self.packed[self.stem_off:], ws.ys, N=c0, kh=3, kw=3, stride=2, pad=ws.stem_pad, **csp(S0))
-        hs, wsz = ws.ys.shape[1:3]
-        self._bn_coef(ws, m.stem[1], B * hs * wsz, train, rows)
-        check(lb.cx_scale_act_bc(ptr(ws.ys), ptr(v(ws, S0.sc)), ptr(v(ws, S0.sh)), None, ptr(ws.x0), B, hs * wsz, c0, sp), "cx_scale_act_bc")
-        xin = ws.x0
-        for bi, b in enumerate(self.mb):
-            c, t = b.cfg, ws.blk[bi]
-            conv_e, bn_e, dw, bn_d, se, conv_p, bn_p = self._parts(b)
-            (hi, wi), (ho, wo) = t["hin"], t["hout"]
-            Sd, Sp = self.bn[id(bn_d)], self.bn[id(bn_p)]
-            if conv_e is not None:
-                Se = self.bn[id(bn_e)]
-                rows = ops.conv_gemm(xin, self.w_fwd(conv_e), t["ye"], N=c["ce"], **csp(Se))
-                self._bn_coef(ws, bn_e, B * hi * wi, train, rows)
-                xdw, sc, sh = t["ye"], v(ws, Se.sc), v(ws, Se.sh)
-            else:
-                xdw, sc, sh = xin, None, None
-            d1, d2, dcap = dsp(Sd)
-            check(lb.cx_dwconv_fwd(ptr(xdw), ptr(dw.weight), ptr(sc), ptr(sh), ptr(t["yd"]), d1, d2, B, hi, wi,
-                                   c["ce"], c["k"], c["stride"], t["pad"], dcap, sp), "cx_dwconv_fwd")
-            self._bn_coef(ws, bn_d, B * ho * wo, train, lib().cx_last_stat_rows() if det else None)
-            # squeeze + excite (efficientnet.py:69-73) in two launches: the excitation kernel adds the pool's split rows itself
-            check(lb.cx_gap_se_fwd(ptr(t["yd"]), ptr(v(ws, Sd.sc)), ptr(v(ws, Sd.sh)), ptr(t["pooled"]), ptr(se[1].weight), ptr(se[1].bias),
-                                   ptr(se[3].weight), ptr(se[3].bias), ptr(t["h1"]), ptr(t["s"]), B, ho * wo, c["ce"], t["R"], 2, *rsc, sp),
-                  "cx_gap_se_fwd")
-            check(lb.cx_scale_act_bc(ptr(t["yd"]), ptr(v(ws, Sd.sc)), ptr(v(ws, Sd.sh)), ptr(t["s"]), ptr(t["u"]), B, ho * wo, c["ce"], sp),
-                  "cx_scale_act_bc")
-            rows = ops.conv_gemm(t["u"], self.w_fwd(conv_p), t["yp"], N=c["cout"], **csp(Sp))
-            self._bn_coef(ws, bn_p, B * ho * wo, train, rows)
-            # DropConnect (efficientnet.py:44-51, :100-101): train mode only, on blocks with a skip; the per-image mask / keep
-            # probability is drawn by cx_dropout_mask from the model's step counter (reproducible, independent of torch's RNG)
-            p_dc = list(b)[-1].p if (train and c["skip"] and isinstance(list(b)[-1], DropMarker)) else 0.0
-            t["dc"] = None
-            if p_dc > 0.0:
-                t["dc"] = torch.empty(B, dtype=torch.float32, device=self.device)
-                check(lb.cx_dropout_mask_dev(ptr(t["dc"]), B, 1.0 - p_dc, self._seed_base(bi), ptr(self.step_dev), sp), "cx_dropout_mask_dev")
-                self.last_masks[self.mb_names[bi]] = t["dc"]
-            check(lb.cx_affine2_out(ptr(t["yp"]), ptr(xin) if c["skip"] else None, ptr(v(ws, Sp.sc)), ptr(v(ws, self.ones)),
-                                    ptr(v(ws, Sp.sh)), ptr(t["dc"]), ho * wo, ptr(t["out"]), B * ho * wo, c["cout"], sp), "cx_affine2_out")
-            xin = t["out"]
+            ops.nchw3_to_nhwc8(x.contiguous().float(), ws.x8)
+        xin = self._stem_forward(ws, train)
+        for bi in range(len(self.mb)):
+            xin = self._mbconv_forward(ws, bi, xin, train)
+        self._head_forward(ws, xin, train)
+        if train:
+            self.model._nbt_pending += 1
+        return ws
+
+    def _stem_forward(self, ws, train):
+        """3x3 stride-2 convolution of the 8-channel image, BatchNorm, Swish"""
+        m, v = self.model, self._v
+        S0, c0 = self.bn[id(m.stem[1])], m.stem[0].out_channels
+        rows = ops.conv_gemm(ws.x8, self.packed[self.stem_off:], ws.ys, N=c0, kh=3, kw=3, stride=2, pad=ws.stem_pad, **self._sp(ws, S0))
+        self._bn_coef(ws, m.stem[1], ws.ys.numel() // c0, train, rows)
+        ops.scale_act_bc(ws.ys, v(ws, S0.sc), v(ws, S0.sh), None, ws.x0)
+        return ws.x0
+
+    def _mbconv_forward(self, ws, bi, xin, train):
+        """efficientnet.py:76-110: expand 1x1 (unless expand_ratio == 1), depthwise k x k with the expansion's BatchNorm + Swish
+        applied on load, squeeze-excite, project 1x1, BatchNorm (+ DropConnect-ed skip).  Returns the block's output."""
+        b, t, v = self.mb[bi], ws.blk[bi], self._v
+        c, cnt = b.cfg, ws.B * t["hout"][0] * t["hout"][1]
+        conv_e, bn_e, dw, bn_d, se, conv_p, bn_p = self._parts(b)
+        Sd, Sp = self.bn[id(bn_d)], self.bn[id(bn_p)]
+        xdw, sc, sh = xin, None, None
+        if conv_e is not None:
+            Se = self.bn[id(bn_e)]
+            rows = ops.conv_gemm(xin, self.w_fwd(conv_e), t["ye"], N=c["ce"], **self._sp(ws, Se))
+            self._bn_coef(ws, bn_e, ws.B * t["hin"][0] * t["hin"][1], train, rows)
+            xdw, sc, sh = t["ye"], v(ws, Se.sc), v(ws, Se.sh)
+        s1, s2, cap = self._ew(ws, Sd)
+        rows = ops.dwconv_fwd(xdw, dw.weight, sc, sh, t["yd"], s1, s2, k=c["k"], stride=c["stride"], pad=t["pad"], stat_rows=cap)
+        self._bn_coef(ws, bn_d, cnt, train, rows)
+        # squeeze + excite (efficientnet.py:69-73) in two launches: the excitation kernel adds the pool's split rows itself
+        sc, sh = v(ws, Sd.sc), v(ws, Sd.sh)
+        ops.gap_se_fwd(t["yd"], sc, sh, t["pooled"], se[1].weight, se[1].bias, se[3].weight, se[3].bias, t["h1"], t["s"], rows=self._rows(ws))
+        ops.scale_act_bc(t["yd"], sc, sh, t["s"], t["u"])
+        rows = ops.conv_gemm(t["u"], self.w_fwd(conv_p), t["yp"], N=c["cout"], **self._sp(ws, Sp))
+        self._bn_coef(ws, bn_p, cnt, train, rows)
+        # DropConnect (efficientnet.py:44-51, :100-101): train mode only, on blocks with a skip; the per-image mask / keep
+        # probability is drawn by cx_dropout_mask_dev from the model's step counter (reproducible, independent of torch's RNG)
+        last = list(b)[-1]
+        p_dc = last.p if (train and c["skip"] and isinstance(last, DropMarker)) else 0.0
+        t["dc"] = None
+        if p_dc > 0.0:
+            t["dc"] = torch.empty(ws.B, dtype=torch.float32, device=self.device)
+            ops.dropout_mask_dev(t["dc"], 1.0 - p_dc, self._seed_base(bi), self.step_dev)
+            self.last_masks[self.mb_names[bi]] = t["dc"]
+        ops.affine2_out(t["yp"], xin if c["skip"] else None, v(ws, Sp.sc), v(ws, self.ones), v(ws, Sp.sh), t["dc"], t["out"])
+        return t["out"]
+
+    def _head_forward(self, ws, xin, train):
+        """1x1 convolution to 1280 channels, BatchNorm, Swish + global average pool in one kernel, Dropout, classifier"""
+        m, v, B = self.model, self._v, ws.B
         Sh = self.bn[id(m.head[1])]
-        hl, wl = ws.hw_last
-        rows = ops.conv_gemm(xin, self.w_fwd(m.head[0]), ws.yh, N=1280, **csp(Sh))
-        self._bn_coef(ws, m.head[1], B * hl * wl, train, rows)
-        check(lb.cx_gap_affine_act(ptr(ws.yh), ptr(v(ws, Sh.sc)), ptr(v(ws, Sh.sh)), ptr(ws.pooled), B, hl * wl, 1280, 2, *rsc, sp),
-              "cx_gap_affine_act")
+        rows = ops.conv_gemm(xin, self.w_fwd(m.head[0]), ws.yh, N=1280, **self._sp(ws, Sh))
+        self._bn_coef(ws, m.head[1], B * ws.hw_last[0] * ws.hw_last[1], train, rows)
+        ops.gap_affine_act(ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.pooled, act=2, rows=self._rows(ws))
         # Dropout in front of the classifier (efficientnet.py:169-171), train mode only
         p_do = m.head[5].p if train else 0.0
-        ws.drop = None
-        fc_in = ws.pooled
+        ws.drop, ws.fc_in = None, ws.pooled
         if p_do > 0.0:
             ws.drop = torch.empty(B, 1280, dtype=torch.float32, device=self.device)
-            check(lb.cx_dropout_mask_dev(ptr(ws.drop), B * 1280, 1.0 - p_do, self._seed_base(len(self.mb)), ptr(self.step_dev), sp),
-                  "cx_dropout_mask_dev")
+            ops.dropout_mask_dev(ws.drop, 1.0 - p_do, self._seed_base(len(self.mb)), self.step_dev)
             ws.pooled_d = torch.empty_like(ws.pooled)
-            check(lb.cx_mul_f32(ptr(ws.pooled), ptr(ws.drop), ptr(ws.pooled_d), B * 1280, sp), "cx_mul_f32")
-            fc_in = ws.pooled_d
+            ops.mul_f32(ws.pooled, ws.drop, ws.pooled_d)
+            ws.fc_in = ws.pooled_d
             self.last_masks["head"] = ws.drop
-        ws.fc_in = fc_in
-        check(lb.cx_linear_fwd(ptr(fc_in), ptr(m.head[6].weight), ptr(m.head[6].bias), ptr(ws.logits), B, 1280, self.n_classes, sp),
-              "cx_linear_fwd")
-        if train:
-            m._nbt_pending += 1
-        return ws
+        ops.linear_fwd(ws.fc_in, m.head[6].weight, m.head[6].bias, ws.logits)
 
     def _seed_base(self, idx):
         """Host part of the 64-bit seed of the mask of block `idx`: (model seed, block); the kernel adds the device-side count of
@@ -311,119 +330,100 @@ class _Engine(FusedEngine):
         ws.bwd = bw
 
     def _backward(self, ws, dlogits, dx, done):
-        m, v, G, lb = self.model, self._v, self.grad_of, (_LibF32(lib()) if self.dtype == torch.float32 else lib())
-        det = self.det
-        B = ws.B
-        sp = stream_ptr()
         self._alloc_bwd(ws)
-        bw = ws.bwd
-        if not det:
+        if not self.det:
             z0, zn = self.bwd_zero
             ws.vec[z0:z0 + zn].zero_()
+        g = self._head_backward(ws, dlogits, done)
+        for bi in range(len(self.mb) - 1, -1, -1):
+            g = self._mbconv_backward(ws, bi, g, done)
+        self._stem_backward(ws, g, dx)
 
-        def bn_bwd(S, bn, count):
-            """BatchNorm backward coefficients of `bn` from the sums its producer has just written (deterministic mode: the rows of
-            the scratch pair, counted by cx_last_stat_rows)."""
-            self._bn_bwd(ws, bn, (ws.slab[0], ws.slab[1], lib().cx_last_stat_rows(), S.C) if det else (v(ws, S.S1), v(ws, S.S2), 1, 0), count)
-
-        def ssp(S):      # (S1, S2, stat_rows) of an element-wise / depthwise producer of S's backward sums
-            return (ptr(ws.slab[0]), ptr(ws.slab[1]), self._rows_cap(S.C)) if det else (ptr(v(ws, S.S1)), ptr(v(ws, S.S2)), 0)
-
-        def dw_wgrad(*args):
-            """cx_dwconv_wgrad with the slab workspace of ops (deferred sums when backward defers them)."""
-            wsb, arena, dfr = ops._wgrad_ws(self.device)
-            check(lb.cx_dwconv_wgrad(*args, ptr(wsb), 0 if wsb is None else wsb.numel(), sp), "cx_dwconv_wgrad")
-            ops._wgrad_used(arena, dfr)
-        # ---- head
+    def _head_backward(self, ws, dlogits, done):
+        """Returns the gradient of the last block's output."""
+        m, v, G, B = self.model, self._v, self.grad_of, ws.B
         fc, Sh = m.head[6], self.bn[id(m.head[1])]
-        hl, wl = ws.hw_last
         dpool = torch.empty(B, 1280, dtype=torch.float32, device=self.device)
         ops.head_bwd(dlogits, ws.fc_in, fc.weight, G(fc.weight), G(fc.bias), dpool)
         if ws.drop is not None:
-            check(lb.cx_mul_f32(ptr(dpool), ptr(ws.drop), ptr(dpool), B * 1280, sp), "cx_mul_f32")
-        dzh = bw["dze"][:ws.yh.numel()].view(ws.yh.shape)
-        check(lb.cx_se_act_bwd(None, ptr(ws.yh), ptr(v(ws, Sh.sc)), ptr(v(ws, Sh.sh)), ptr(v(ws, Sh.mean)), ptr(v(ws, Sh.rstd)), None,
-                               ptr(dpool), ptr(dzh), *ssp(Sh)[:2], B, hl * wl, 1280, ssp(Sh)[2], sp), "cx_se_act_bwd")
-        bn_bwd(Sh, m.head[1], B * hl * wl)
-        g = bw["g"][-1]
-        xlast = ws.blk[-1]["out"]
-        ops.conv_gemm(dzh, self.w_bwd(m.head[0]), g, N=xlast.shape[3], prologue=ops.PRO_AFFINE2, x2=ws.yh, pa=v(ws, Sh.pa), pb=v(ws, Sh.pb),
-                      pc=v(ws, Sh.pc))
-        ops.conv_wgrad(dzh, xlast, G(m.head[0].weight), g_prologue=ops.PRO_AFFINE2, g2=ws.yh, ga=v(ws, Sh.pa), gb=v(ws, Sh.pb),
-                       gc=v(ws, Sh.pc))
+            ops.mul_f32(dpool, ws.drop, dpool)
+        dzh = ws.bwd["dze"][:ws.yh.numel()].view(ws.yh.shape)
+        rows = ops.se_act_bwd(None, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), v(ws, Sh.mean), v(ws, Sh.rstd), None, dpool, dzh,
+                              *self._ew(ws, Sh, bwd=True))
+        self._bn_bwd(ws, m.head[1], self._sc(ws, Sh, rows), B * ws.hw_last[0] * ws.hw_last[1])
+        g, xlast = ws.bwd["g"][-1], ws.blk[-1]["out"]
+        ops.conv_gemm(dzh, self.w_bwd(m.head[0]), g, N=xlast.shape[3], **self._pro_bnbwd(ws, ws.yh, Sh))
+        ops.conv_wgrad(dzh, xlast, G(m.head[0].weight), **self._g_bnbwd(ws, ws.yh, Sh))
         done(m.head[0].weight)
-        # ---- blocks
-        for bi in range(len(self.mb) - 1, -1, -1):
-            b, t = self.mb[bi], ws.blk[bi]
-            c = b.cfg
-            conv_e, bn_e, dw, bn_d, se, conv_p, bn_p = self._parts(b)
-            (hi, wi), (ho, wo) = t["hin"], t["hout"]
-            Sd, Sp = self.bn[id(bn_d)], self.bn[id(bn_p)]
-            xin = ws.blk[bi - 1]["out"] if bi > 0 else ws.x0
-            g = bw["g"][bi]
-            gin = g if c["skip"] else (bw["g"][bi - 1] if bi > 0 else bw["g0"])       # skip: dx accumulates into g itself
-            ce, rows_o = c["ce"], B * ho * wo
-            gsk = g                                   # gradient of the block output: the skip path takes it as it is
-            if t.get("dc") is not None:               # the branch sees it through the DropConnect mask
-                gb = bw["gdc"][:g.numel()].view(g.shape)
-                check(lb.cx_scale_rows(ptr(g), ptr(t["dc"]), ho * wo, ptr(gb), rows_o, c["cout"], sp), "cx_scale_rows")
-                g = gb
-            check(lb.cx_bn_lin_bwd_stats(ptr(g), ptr(t["yp"]), ptr(v(ws, Sp.mean)), ptr(v(ws, Sp.rstd)), *ssp(Sp)[:2],
-                                         rows_o, c["cout"], ssp(Sp)[2], sp), "cx_bn_lin_bwd_stats")
-            bn_bwd(Sp, bn_p, rows_o)
-            du = bw["du"][:rows_o * ce].view(B, ho, wo, ce)
-            dzd = bw["dzd"][:rows_o * ce].view(B, ho, wo, ce)
-            ops.conv_gemm(g, self.w_bwd(conv_p), du, N=ce, prologue=ops.PRO_AFFINE2, x2=t["yp"], pa=v(ws, Sp.pa), pb=v(ws, Sp.pb),
-                          pc=v(ws, Sp.pc))
-            ops.conv_wgrad(g, t["u"], G(conv_p.weight), g_prologue=ops.PRO_AFFINE2, g2=t["yp"], ga=v(ws, Sp.pa), gb=v(ws, Sp.pb),
-                           gc=v(ws, Sp.pc))
-            ds = torch.empty(B, ce, dtype=torch.float32, device=self.device)
-            dpl = torch.empty(B, ce, dtype=torch.float32, device=self.device)
-            # ds[b][c] = sum_hw du * swish(bn(yd)) and the two FCs' backward (efficientnet.py:69-73): the reduce kernel's split rows go
-            # straight into the first FC pass (cx_se_bwd_fused: no launch of their own)
-            wsb, arena, dfr = ops._wgrad_ws(self.device)
-            check(lb.cx_se_bwd_fused(ptr(du), ptr(t["yd"]), ptr(v(ws, Sd.sc)), ptr(v(ws, Sd.sh)), ptr(ds), ptr(t["s"]), ptr(t["h1"]),
-                                     ptr(t["pooled"]), ptr(se[1].weight), ptr(se[3].weight), ptr(G(se[1].weight)), ptr(G(se[1].bias)),
-                                     ptr(G(se[3].weight)), ptr(G(se[3].bias)), ptr(dpl), B, ho * wo, ce, t["R"],
-                                     *((ptr(ws.slab[0]), self.SLAB) if det else (None, 0)), ptr(wsb), 0 if wsb is None else wsb.numel(), sp),
-                  "cx_se_bwd_fused")
-            ops._wgrad_used(arena, dfr)
-            check(lb.cx_se_act_bwd(ptr(du), ptr(t["yd"]), ptr(v(ws, Sd.sc)), ptr(v(ws, Sd.sh)), ptr(v(ws, Sd.mean)), ptr(v(ws, Sd.rstd)),
-                                   ptr(t["s"]), ptr(dpl), ptr(dzd), *ssp(Sd)[:2], B, ho * wo, ce, ssp(Sd)[2], sp), "cx_se_act_bwd")
-            bn_bwd(Sd, bn_d, rows_o)
-            dargs = (ptr(dzd), ptr(t["yd"]), ptr(v(ws, Sd.pa)), ptr(v(ws, Sd.pb)), ptr(v(ws, Sd.pc)))
-            if conv_e is not None:
-                Se = self.bn[id(bn_e)]
-                dze = bw["dze"][:B * hi * wi * ce].view(B, hi, wi, ce)
-                check(lb.cx_dwconv_dgrad(*dargs, ptr(dw.weight), ptr(t["ye"]), ptr(v(ws, Se.sc)), ptr(v(ws, Se.sh)), ptr(v(ws, Se.mean)),
-                                         ptr(v(ws, Se.rstd)), ptr(dze), *ssp(Se)[:2], B, hi, wi, ce, c["k"],
-                                         c["stride"], t["pad"], 0, ssp(Se)[2], sp), "cx_dwconv_dgrad")
-                bn_bwd(Se, bn_e, B * hi * wi)           # (before the next producer re-uses the statistic rows)
-                dw_wgrad(*dargs, ptr(t["ye"]), ptr(v(ws, Se.sc)), ptr(v(ws, Se.sh)), ptr(G(dw.weight)), B, hi, wi, ce, c["k"],
-                         c["stride"], t["pad"])
-                ops.conv_gemm(dze, self.w_bwd(conv_e), gin, N=c["cin"], prologue=ops.PRO_AFFINE2, x2=t["ye"], pa=v(ws, Se.pa),
-                              pb=v(ws, Se.pb), pc=v(ws, Se.pc), accumulate=c["skip"])
-                ops.conv_wgrad(dze, xin, G(conv_e.weight), g_prologue=ops.PRO_AFFINE2, g2=t["ye"], ga=v(ws, Se.pa), gb=v(ws, Se.pb),
-                               gc=v(ws, Se.pc))
-            else:
-                check(lb.cx_dwconv_dgrad(*dargs, ptr(dw.weight), ptr(xin), None, None, None, None, ptr(gin), None, None, B, hi, wi, ce,
-                                         c["k"], c["stride"], t["pad"], int(c["skip"]), 0, sp), "cx_dwconv_dgrad")
-                dw_wgrad(*dargs, ptr(xin), None, None, ptr(G(dw.weight)), B, hi, wi, ce, c["k"], c["stride"], t["pad"])
-            done(list(b.parameters())[0])
-        # ---- stem: x0 = swish(bn(ys))
-        S0 = self.bn[id(m.stem[1])]
-        hs, wsz = ws.ys.shape[1:3]
-        c0 = m.stem[0].out_channels
-        dzs = bw["dze"][:ws.ys.numel()].view(ws.ys.shape)
-        check(lb.cx_se_act_bwd(ptr(bw["g0"]), ptr(ws.ys), ptr(v(ws, S0.sc)), ptr(v(ws, S0.sh)), ptr(v(ws, S0.mean)), ptr(v(ws, S0.rstd)), None,
-                               None, ptr(dzs), *ssp(S0)[:2], B, hs * wsz, c0, ssp(S0)[2], sp), "cx_se_act_bwd")
-        bn_bwd(S0, m.stem[1], B * hs * wsz)
+        return g
+
+    def _mbconv_backward(self, ws, bi, g, done):
+        """Backward of block bi from the gradient g of its output.  Returns the gradient of its input."""
+        b, t, bw, v, G, B = self.mb[bi], ws.blk[bi], ws.bwd, self._v, self.grad_of, ws.B
+        c, ce = b.cfg, b.cfg["ce"]
+        conv_e, bn_e, dw, bn_d, se, conv_p, bn_p = self._parts(b)
+        (hi, wi), (ho, wo) = t["hin"], t["hout"]
+        Sd, Sp = self.bn[id(bn_d)], self.bn[id(bn_p)]
+        xin = ws.blk[bi - 1]["out"] if bi > 0 else ws.x0
+        gin = g if c["skip"] else (bw["g"][bi - 1] if bi > 0 else bw["g0"])       # skip: dx accumulates into g itself
+        if t.get("dc") is not None:               # the skip path takes g as it is, the branch sees it through the DropConnect mask
+            gb = bw["gdc"][:g.numel()].view(g.shape)
+            ops.scale_rows(g, t["dc"], gb)
+            g = gb
+        rows = ops.bn_lin_bwd_stats(g, t["yp"], v(ws, Sp.mean), v(ws, Sp.rstd), *self._ew(ws, Sp, bwd=True))
+        self._bn_bwd(ws, bn_p, self._sc(ws, Sp, rows), B * ho * wo)
+        du = bw["du"][:B * ho * wo * ce].view(B, ho, wo, ce)
+        dzd = bw["dzd"][:B * ho * wo * ce].view(B, ho, wo, ce)
+        ops.conv_gemm(g, self.w_bwd(conv_p), du, N=ce, **self._pro_bnbwd(ws, t["yp"], Sp))
+        ops.conv_wgrad(g, t["u"], G(conv_p.weight), **self._g_bnbwd(ws, t["yp"], Sp))
+        self._se_backward(ws, bi, du, dzd)
+        dY = (dzd, t["yd"], v(ws, Sd.pa), v(ws, Sd.pb), v(ws, Sd.pc))           # gradient of the depthwise output: pa*dzd + pb*yd + pc
+        geo = dict(k=c["k"], stride=c["stride"], pad=t["pad"])
+        if conv_e is not None:
+            Se = self.bn[id(bn_e)]
+            dze = bw["dze"][:B * hi * wi * ce].view(B, hi, wi, ce)
+            s1, s2, cap = self._ew(ws, Se, bwd=True)
+            rows = ops.dwconv_dgrad(*dY, dw.weight, t["ye"], v(ws, Se.sc), v(ws, Se.sh), v(ws, Se.mean), v(ws, Se.rstd), dze, s1, s2,
+                                    stat_rows=cap, **geo)
+            self._bn_bwd(ws, bn_e, self._sc(ws, Se, rows), B * hi * wi)       # (before the next producer re-uses the statistic rows)
+            ops.dwconv_wgrad(*dY, t["ye"], v(ws, Se.sc), v(ws, Se.sh), G(dw.weight), **geo)
+            ops.conv_gemm(dze, self.w_bwd(conv_e), gin, N=c["cin"], accumulate=c["skip"], **self._pro_bnbwd(ws, t["ye"], Se))
+            ops.conv_wgrad(dze, xin, G(conv_e.weight), **self._g_bnbwd(ws, t["ye"], Se))
+        else:                                     # expand_ratio == 1: the depthwise convolution reads the block input itself
+            ops.dwconv_dgrad(*dY, dw.weight, xin, None, None, None, None, gin, None, None, accumulate=c["skip"], **geo)
+            ops.dwconv_wgrad(*dY, xin, None, None, G(dw.weight), **geo)
+        done(list(b.parameters())[0])
+        return gin
+
+    def _se_backward(self, ws, bi, du, dzd):
+        """From du, the gradient of u = swish(bn(yd)) * s: the squeeze-excite backward (efficientnet.py:69-73) and dzd, the gradient
+        of bn_d's output, with bn_d's coefficients.  ds[b][c] = sum_hw du * swish(bn(yd)) and the two FCs' backward are one call: the
+        reduce kernel's split rows go straight into the first FC pass (cx_se_bwd_fused: no launch of their own)."""
+        t, v, G = ws.blk[bi], self._v, self.grad_of
+        _, _, _, bn_d, se, _, _ = self._parts(self.mb[bi])
+        Sd = self.bn[id(bn_d)]
+        B, ho, wo, ce = du.shape
+        sc, sh = v(ws, Sd.sc), v(ws, Sd.sh)
+        ds = torch.empty(B, ce, dtype=torch.float32, device=self.device)
+        dpl = torch.empty(B, ce, dtype=torch.float32, device=self.device)
+        ops.se_bwd_fused(du, t["yd"], sc, sh, ds, t["s"], t["h1"], t["pooled"], se[1].weight, se[3].weight, G(se[1].weight),
+                         G(se[1].bias), G(se[3].weight), G(se[3].bias), dpl, rows=self._rows(ws))
+        rows = ops.se_act_bwd(du, t["yd"], sc, sh, v(ws, Sd.mean), v(ws, Sd.rstd), t["s"], dpl, dzd, *self._ew(ws, Sd, bwd=True))
+        self._bn_bwd(ws, bn_d, self._sc(ws, Sd, rows), B * ho * wo)
+
+    def _stem_backward(self, ws, g, dx):
+        """x0 = swish(bn(ys)) from its gradient g; the stem's weight gradient and, into dx when given, the input gradient"""
+        m, v, G = self.model, self._v, self.grad_of
+        S0, c0 = self.bn[id(m.stem[1])], m.stem[0].out_channels
+        dzs = ws.bwd["dze"][:ws.ys.numel()].view(ws.ys.shape)
+        rows = ops.se_act_bwd(g, ws.ys, v(ws, S0.sc), v(ws, S0.sh), v(ws, S0.mean), v(ws, S0.rstd), None, None, dzs,
+                              *self._ew(ws, S0, bwd=True))
+        self._bn_bwd(ws, m.stem[1], self._sc(ws, S0, rows), ws.ys.numel() // c0)
         # (persistent: its address is part of the deferred slab-sum table, which must not change from step to step)
-        if getattr(ws, "dw8", None) is None:
+        if ws.dw8 is None:
             ws.dw8 = torch.empty(c0, 8, 3, 3, dtype=torch.float32, device=self.device)
         dw8 = ws.dw8.zero_()
-        ops.conv_wgrad(dzs, ws.x8, dw8, kh=3, kw=3, stride=2, pad=ws.stem_pad, g_prologue=ops.PRO_AFFINE2, g2=ws.ys, ga=v(ws, S0.pa),
-                       gb=v(ws, S0.pb), gc=v(ws, S0.pc))
+        ops.conv_wgrad(dzs, ws.x8, dw8, kh=3, kw=3, stride=2, pad=ws.stem_pad, **self._g_bnbwd(ws, ws.ys, S0))
         ops.wgrad_defer_flush(self.device)       # the stem gradient is read back right here: run the deferred slab sums now
         G(m.stem[0].weight).view(c0, 3, 3, 3).add_(dw8[:, :3])
         if dx is not None:

@@ -19,7 +19,6 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .._lib import check, lib, ptr, stream_ptr
 from ._fused import FusedEngine, FusedNet, _BN
 from .densenet import AAConv2d, BatchNorm2dParams, Conv2dParams, PoolMarker, ReLUMarker
 
@@ -392,7 +391,7 @@ class _Engine(FusedEngine):
         if x.dtype == torch.uint8:
             raise RuntimeError("the CIFAR stem takes (B,3,H,W) float images")
         S0, c0 = self.bn[id(m.bn1)], m.conv1.out_channels
-        check(lib().cx_nchw3_to_nhwc8(ptr(x.contiguous().float()), ptr(ws.x8), ws.B, ws.H, ws.W, stream_ptr()), "cx_nchw3_to_nhwc8")
+        ops.nchw3_to_nhwc8(x.contiguous().float(), ws.x8)
         rows = ops.conv_gemm(ws.x8, self.packed[self.stem_off:], ws.c0, N=c0, kh=3, kw=3, stride=1, pad=1, **self._sp(ws, S0))
         self._bn_coef(ws, m.bn1, ws.B * ws.H * ws.W, not ws.frozen, rows)
         ops.affine2_relu(ws.c0, ws.c0, v(ws, S0.sc), v(ws, self.zeros, c0), v(ws, S0.sh), ws.pool0)

@@ -1,4 +1,5 @@
-"""Thin tensor-level wrappers over the C ABI (one call = one kernel launch on the current stream).
+"""Thin tensor-level wrappers over the C ABI (one call = one kernel launch on the current stream).  Every launch of the package goes
+through here: `lib()` is named in this module and in `_lib.py` only.
 
 Tensors: activations are torch.bfloat16 NHWC views (B,H,W,C) whose channel pitch may exceed C (a
 slice of a dense-block buffer); statistics / coefficient vectors / parameter gradients are fp32.
@@ -20,6 +21,20 @@ def _nhwc(t):
     sb, sh, sw, sc = t.stride()
     assert sc == 1 and sh == W * sw and sb == H * sh, "NHWC slice must be dense in (B,H,W) with a channel pitch"
     return B, H, W, Cc, sw
+
+
+def _dense(t, like=None):
+    """_nhwc for a kernel that takes no pitch: (B,H,W,C) of a dense NHWC tensor (of `like`'s shape and storage type)."""
+    B, H, W, Cc, ld = _nhwc(t)
+    assert ld == Cc, "this kernel takes dense NHWC tensors (no channel pitch)"
+    assert like is None or (t.shape == like.shape and t.dtype == like.dtype), "NHWC operands of one launch share shape and storage type"
+    return B, H, W, Cc
+
+
+def _f32(*tensors, n=0):
+    """Statistics, coefficients, parameters and their gradients: contiguous fp32 of at least n elements (None: not given)."""
+    for t in tensors:
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n), "expected a contiguous fp32 tensor"
 
 
 # Workspace of the reproducible weight-gradient sums (CxWgrad.scratch): one slab buffer per (device, stream) -- kernels on one stream
@@ -427,6 +442,31 @@ def nchw3_to_nhwc4(x, out=None):
     return out
 
 
+def u8_to_nhwc8(x, out, mean=0.5330, std=0.0349):
+    """cx_u8_to_nhwc8: uint8 grey images (B,1,H,W) -> whitened (B,H,W,8) in out's storage type (3 equal channels + 5 zeros)."""
+    require_cuda(x, out)
+    B, H, W, Cc = _dense(out)
+    assert x.dtype == torch.uint8 and x.is_contiguous() and tuple(x.shape) == (B, 1, H, W) and Cc == 8
+    check(_fn("cx_u8_to_nhwc8", out)(ptr(x), ptr(out), B * H * W, mean, std, stream_ptr()), "cx_u8_to_nhwc8")
+
+
+def nchw3_to_nhwc8(x, out):
+    """cx_nchw3_to_nhwc8: fp32 (B,3,H,W) -> (B,H,W,8) in out's storage type (the 3 channels + 5 zeros)."""
+    require_cuda(x, out)
+    B, H, W, Cc = _dense(out)
+    assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (B, 3, H, W) and Cc == 8
+    check(_fn("cx_nchw3_to_nhwc8", out)(ptr(x), ptr(out), B, H, W, stream_ptr()), "cx_nchw3_to_nhwc8")
+
+
+def chan_map_table(real, padded, table, n_desc, direction, accumulate=0):
+    """cx_chan_map_table: copies (direction 0: real -> padded, 1: padded -> real, `accumulate`: added) between the flat fp32 buffers
+    of a network and of its channel-padded twin, as the n_desc CxChanMapDesc of `table` (uint8 bytes on the device) say."""
+    require_cuda(real, padded, table)
+    _f32(real, padded)
+    assert table.dtype == torch.uint8 and table.is_contiguous() and table.numel() == n_desc * C.sizeof(L.CxChanMapDesc)
+    check(lib().cx_chan_map_table(ptr(real), ptr(padded), ptr(table), n_desc, direction, accumulate, stream_ptr()), "cx_chan_map_table")
+
+
 def bn_coef(s, q, count, gamma, beta, eps, momentum, rmean, rvar, scale, shift, mean, rstd, Cn=None, replicas=1, rstride=0):
     Cn = Cn if Cn is not None else s.numel()
     check(lib().cx_bn_coef(ptr(s), ptr(q), float(count), ptr(gamma), ptr(beta), eps, momentum, ptr(rmean), ptr(rvar),
@@ -717,3 +757,219 @@ def in_relu_bwd(da, x, sc, sh, S1, S2, gout):
 
 def f32_to_bf16(x, y):
     check(lib().cx_f32_to_bf16(ptr(x), ptr(y), x.numel(), stream_ptr()), "cx_f32_to_bf16")
+
+
+# ---- EfficientNet pieces (csrc/dwconv.hip, csrc/effnet.hip): depthwise convolution, squeeze-excite, Swish glue.  None of these
+# kernels takes a pitch: every NHWC operand is dense.  stat_rows > 0: deterministic statistic rows (the count written is returned),
+# 0: fp32 atomics into [C] vectors.  rows: the optional row scratch of the per-(image, channel) sums (None: atomics).
+def _out_hw(H, W, k, stride, pad):
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def dwconv_fwd(x, w, sc, sh, y, stat_sum, stat_sq, *, k, stride, pad, stat_rows=0):
+    """cx_dwconv_fwd: y = depthwise k x k convolution (w fp32 (C,1,k,k)) of swish(x*sc + sh) (sc None: of x) + the sums of y."""
+    require_cuda(x, w, y)
+    B, H, W, Cc = _dense(x)
+    assert _dense(y) == (B, *_out_hw(H, W, k, stride, pad), Cc) and y.dtype == x.dtype
+    _f32(sc, sh, stat_sum, stat_sq, n=Cc)
+    _f32(w, n=Cc * k * k)
+    check(_fn("cx_dwconv_fwd", x)(ptr(x), ptr(w), ptr(sc), ptr(sh), ptr(y), ptr(stat_sum), ptr(stat_sq), B, H, W, Cc, k, stride, pad,
+                                  stat_rows, stream_ptr()), "cx_dwconv_fwd")
+    return lib().cx_last_stat_rows() if stat_rows else None
+
+
+def dwconv_dgrad(g, g2, ga, gb, gc, w, x, sc, sh, mean, rstd, dz, S1, S2, *, k, stride, pad, accumulate=False, stat_rows=0):
+    """cx_dwconv_dgrad: dY = g*ga + g2*gb + gc; dz (+)= (sum_taps dY w) * swish'(x*sc + sh) with the BatchNorm backward sums S1 / S2
+    of dz (sc None: dz is the plain input gradient, no sums)."""
+    require_cuda(g, g2, w, x, dz)
+    B, H, W, Cc = _dense(x)
+    assert _dense(g) == (B, *_out_hw(H, W, k, stride, pad), Cc) and g.dtype == x.dtype
+    _dense(g2, g)
+    _dense(dz, x)
+    _f32(ga, gb, gc, sc, sh, mean, rstd, S1, S2, n=Cc)
+    _f32(w, n=Cc * k * k)
+    check(_fn("cx_dwconv_dgrad", x)(ptr(g), ptr(g2), ptr(ga), ptr(gb), ptr(gc), ptr(w), ptr(x), ptr(sc), ptr(sh), ptr(mean), ptr(rstd),
+                                    ptr(dz), ptr(S1), ptr(S2), B, H, W, Cc, k, stride, pad, int(accumulate), stat_rows, stream_ptr()),
+          "cx_dwconv_dgrad")
+    return lib().cx_last_stat_rows() if stat_rows else None
+
+
+def dwconv_wgrad(g, g2, ga, gb, gc, x, sc, sh, dw, *, k, stride, pad):
+    """cx_dwconv_wgrad: dw (fp32 (C,1,k,k)) += the depthwise weight gradient at dY = g*ga + g2*gb + gc and the input
+    swish(x*sc + sh) (sc None: x), through the slab workspace (reproducible, deferrable) when it is on."""
+    require_cuda(g, g2, x, dw)
+    B, H, W, Cc = _dense(x)
+    assert _dense(g) == (B, *_out_hw(H, W, k, stride, pad), Cc) and g.dtype == x.dtype
+    _dense(g2, g)
+    _f32(ga, gb, gc, sc, sh, n=Cc)
+    _f32(dw, n=Cc * k * k)
+    ws, arena, dfr = _wgrad_ws(dw.device)
+    check(_fn("cx_dwconv_wgrad", x)(ptr(g), ptr(g2), ptr(ga), ptr(gb), ptr(gc), ptr(x), ptr(sc), ptr(sh), ptr(dw), B, H, W, Cc, k, stride,
+                                    pad, ptr(ws), 0 if ws is None else ws.numel(), stream_ptr()), "cx_dwconv_wgrad")
+    _wgrad_used(arena, dfr)
+
+
+def gap_se_fwd(x, sc, sh, pooled, w1, b1, w2, b2, h1, s, *, act=2, rows=None):
+    """cx_gap_se_fwd: pooled = mean_hw act(x*sc + sh) (act 0 none / 1 ReLU / 2 Swish), h1 = W1 pooled + b1,
+    s = sigmoid(W2 swish(h1) + b2): squeeze + excitation in two launches."""
+    require_cuda(x, pooled, w1, w2, h1, s)
+    B, H, W, Cc = _dense(x)
+    R = h1.shape[1]
+    assert tuple(pooled.shape) == tuple(s.shape) == (B, Cc) and tuple(h1.shape) == (B, R)
+    _f32(sc, sh, b2, n=Cc)
+    _f32(pooled, s, rows, n=B * Cc)
+    _f32(w1, w2, n=R * Cc)
+    _f32(b1, h1, n=R)
+    check(_fn("cx_gap_se_fwd", x)(ptr(x), ptr(sc), ptr(sh), ptr(pooled), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(h1), ptr(s), B, H * W, Cc,
+                                  R, act, ptr(rows), 0 if rows is None else rows.numel(), stream_ptr()), "cx_gap_se_fwd")
+
+
+def scale_act_bc(x, sc, sh, s, u):
+    """cx_scale_act_bc: u = swish(x*sc + sh) * s[b][c] (s None: no squeeze-excite scaling)."""
+    require_cuda(x, s, u)
+    B, H, W, Cc = _dense(x)
+    _dense(u, x)
+    _f32(sc, sh, n=Cc)
+    _f32(s, n=B * Cc)
+    check(_fn("cx_scale_act_bc", x)(ptr(x), ptr(sc), ptr(sh), ptr(s), ptr(u), B, H * W, Cc, stream_ptr()), "cx_scale_act_bc")
+
+
+def gap_affine_act(x, sc, sh, pooled, *, act, rows=None):
+    """cx_gap_affine_act: pooled[b][c] = mean_hw act(x*sc + sh) (act as gap_se_fwd)."""
+    require_cuda(x, pooled)
+    B, H, W, Cc = _dense(x)
+    _f32(sc, sh, n=Cc)
+    _f32(pooled, rows, n=B * Cc)
+    check(_fn("cx_gap_affine_act", x)(ptr(x), ptr(sc), ptr(sh), ptr(pooled), B, H * W, Cc, act, ptr(rows),
+                                      0 if rows is None else rows.numel(), stream_ptr()), "cx_gap_affine_act")
+
+
+def se_bwd_fused(du, x, sc, sh, ds, s, h1, pooled, w1, w2, dw1, db1, dw2, db2, dpooled, *, rows=None):
+    """cx_se_bwd_fused: ds[b][c] = sum_hw du * swish(x*sc + sh) and the backward of the two squeeze-excite FCs (their gradients
+    added into dw1 / db1 / dw2 / db2 through the slab workspace when it is on; dpooled written)."""
+    require_cuda(du, x, ds, s, h1, pooled, w1, w2, dw1, db1, dw2, db2, dpooled)
+    B, H, W, Cc = _dense(x)
+    _dense(du, x)
+    R = h1.shape[1]
+    assert tuple(s.shape) == tuple(pooled.shape) == tuple(ds.shape) == tuple(dpooled.shape) == (B, Cc) and tuple(h1.shape) == (B, R)
+    _f32(sc, sh, db2, n=Cc)
+    _f32(ds, s, pooled, dpooled, rows, n=B * Cc)
+    _f32(w1, w2, dw1, dw2, n=R * Cc)
+    _f32(h1, db1, n=R)
+    ws, arena, dfr = _wgrad_ws(dw1.device)
+    check(_fn("cx_se_bwd_fused", x)(ptr(du), ptr(x), ptr(sc), ptr(sh), ptr(ds), ptr(s), ptr(h1), ptr(pooled), ptr(w1), ptr(w2), ptr(dw1),
+                                    ptr(db1), ptr(dw2), ptr(db2), ptr(dpooled), B, H * W, Cc, R, ptr(rows),
+                                    0 if rows is None else rows.numel(), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr()),
+          "cx_se_bwd_fused")
+    _wgrad_used(arena, dfr)
+
+
+def se_act_bwd(du, x, sc, sh, mean, rstd, s, dpooled, dz, S1, S2, stat_rows=0):
+    """cx_se_act_bwd: dz = (du*s[b][c] + dpooled[b][c]/HW) * swish'(x*sc + sh) (du or dpooled / s may be None) with the BatchNorm
+    backward sums S1 / S2 of dz."""
+    require_cuda(du, x, s, dpooled, dz)
+    B, H, W, Cc = _dense(x)
+    _dense(dz, x)
+    if du is not None:
+        _dense(du, x)
+    _f32(sc, sh, mean, rstd, S1, S2, n=Cc)
+    _f32(s, dpooled, n=B * Cc)
+    check(_fn("cx_se_act_bwd", x)(ptr(du), ptr(x), ptr(sc), ptr(sh), ptr(mean), ptr(rstd), ptr(s), ptr(dpooled), ptr(dz), ptr(S1), ptr(S2),
+                                  B, H * W, Cc, stat_rows, stream_ptr()), "cx_se_act_bwd")
+    return lib().cx_last_stat_rows() if stat_rows else None
+
+
+def bn_lin_bwd_stats(g, y, mean, rstd, S1, S2, stat_rows=0):
+    """cx_bn_lin_bwd_stats: the backward sums S1 = sum g, S2 = sum g * (y - mean) * rstd of a BatchNorm without activation."""
+    require_cuda(g, y)
+    B, H, W, Cc = _dense(g)
+    _dense(y, g)
+    _f32(mean, rstd, S1, S2, n=Cc)
+    check(_fn("cx_bn_lin_bwd_stats", g)(ptr(g), ptr(y), ptr(mean), ptr(rstd), ptr(S1), ptr(S2), B * H * W, Cc, stat_rows, stream_ptr()),
+          "cx_bn_lin_bwd_stats")
+    return lib().cx_last_stat_rows() if stat_rows else None
+
+
+def affine2_out(a, b, pa, pb, pc, sample_scale, out):
+    """cx_affine2_out: out = s * (a*pa + pc) + b*pb; b (the skip input) and s = sample_scale[image] (DropConnect) may be None."""
+    require_cuda(a, b, sample_scale, out)
+    B, H, W, Cc = _dense(a)
+    _dense(out, a)
+    if b is not None:
+        _dense(b, a)
+    _f32(pa, pb, pc, n=Cc)
+    _f32(sample_scale, n=B)
+    check(_fn("cx_affine2_out", a)(ptr(a), ptr(b), ptr(pa), ptr(pb), ptr(pc), ptr(sample_scale), H * W, ptr(out), B * H * W, Cc,
+                                   stream_ptr()), "cx_affine2_out")
+
+
+def scale_rows(g, sample_scale, out):
+    """cx_scale_rows: out = sample_scale[image] * g: the gradient that enters a DropConnect-ed branch."""
+    require_cuda(g, sample_scale, out)
+    B, H, W, Cc = _dense(g)
+    _dense(out, g)
+    _f32(sample_scale, n=B)
+    check(_fn("cx_scale_rows", g)(ptr(g), ptr(sample_scale), H * W, ptr(out), B * H * W, Cc, stream_ptr()), "cx_scale_rows")
+
+
+def dropout_mask_dev(out, keep_prob, base, step):
+    """cx_dropout_mask_dev: out[i] in {0, 1/keep_prob}, a counter-based Bernoulli mask whose seed is base + step[0] * 1000003 (step:
+    the int64 device counter counter_add bumps)."""
+    require_cuda(out, step)
+    _f32(out)
+    assert step.dtype == torch.int64 and step.numel() == 1
+    check(lib().cx_dropout_mask_dev(ptr(out), out.numel(), keep_prob, base, ptr(step), stream_ptr()), "cx_dropout_mask_dev")
+
+
+def counter_add(counter, inc=1):
+    """cx_counter_add: counter[0] += inc on the device (one int64)."""
+    require_cuda(counter)
+    assert counter.dtype == torch.int64 and counter.numel() == 1
+    check(lib().cx_counter_add(ptr(counter), inc, stream_ptr()), "cx_counter_add")
+
+
+def mul_f32(a, b, out):
+    """cx_mul_f32: out = a * b, element-wise on fp32 (out may be a)."""
+    require_cuda(a, b, out)
+    _f32(a, b, out, n=a.numel())
+    check(lib().cx_mul_f32(ptr(a), ptr(b), ptr(out), a.numel(), stream_ptr()), "cx_mul_f32")
+
+
+def linear_fwd(x, w, bias, y):
+    """cx_linear_fwd: y (B,N) = x (B,C) W^T + bias, all fp32."""
+    require_cuda(x, w, bias, y)
+    (B, Cc), N = x.shape, y.shape[1]
+    assert y.shape[0] == B and tuple(w.shape) == (N, Cc) and bias.numel() == N
+    _f32(x, w, bias, y)
+    check(lib().cx_linear_fwd(ptr(x), ptr(w), ptr(bias), ptr(y), B, Cc, N, stream_ptr()), "cx_linear_fwd")
+
+
+# ---- Grad-CAM (csrc/gradcam.hip) on a bf16 NHWC feature map that may be a channel slice
+def affine_to_f32_nchw(x, scale, shift, relu, out):
+    """cx_affine_to_f32_nchw: out (B,C,H,W) fp32 = act(x*scale + shift) (scale / shift None: identity; relu: ReLU)."""
+    require_cuda(x, scale, shift, out)
+    B, H, W, Cc, ldx = _nhwc(x)
+    _f32(scale, shift, n=Cc)
+    _f32(out)
+    assert tuple(out.shape) == (B, Cc, H, W)
+    check(_fn("cx_affine_to_f32_nchw", x)(ptr(x), ptr(scale), ptr(shift), int(relu), ptr(out), B, H, W, Cc, ldx, stream_ptr()),
+          "cx_affine_to_f32_nchw")
+
+
+def gradcam_map(x, scale, shift, w, cam, inner_relu):
+    """cx_gradcam_map: cam (B,HW) = relu(sum_c w[c] * f(x*scale + shift)), f = ReLU when inner_relu else the identity."""
+    require_cuda(x, scale, shift, w, cam)
+    B, H, W, Cc, ldx = _nhwc(x)
+    _f32(scale, shift, w, n=Cc)
+    _f32(cam, n=B * H * W)
+    check(_fn("cx_gradcam_map", x)(ptr(x), ptr(scale), ptr(shift), ptr(w), ptr(cam), B, H * W, Cc, ldx, inner_relu, stream_ptr()),
+          "cx_gradcam_map")
+
+
+def cam_norm_upsample(cam, out, h, w):
+    """cx_cam_norm_upsample: out (B,1,H,W) = the h x w maps cam (B,h*w) scaled to [0, 1] per image and up-sampled bilinearly."""
+    require_cuda(cam, out)
+    B, _, H, W = out.shape
+    assert tuple(cam.shape) == (B, h * w) and out.shape[1] == 1
+    _f32(cam, out)
+    check(lib().cx_cam_norm_upsample(ptr(cam), ptr(out), B, h, w, H, W, stream_ptr()), "cx_cam_norm_upsample")

@@ -1,7 +1,11 @@
-"""Call trace of the ResNet / WideResNet / EfficientNet engines on the CPU, without the library: every function of chexpert_amd.ops
-and the `lib` / `ptr` / `stream_ptr` / `check` names of models/resnet.py and models/efficientnet.py are replaced by recorders, so
-`eng.forward` / `eng.backward` run on CPU tensors and leave the list of calls they would have issued.  A host-side refactor of an
-engine is right when this list is EQUAL before and after, for every configuration below.
+"""Call trace of the DenseNet / ResNet / WideResNet / EfficientNet engines and of Grad-CAM on the CPU, without the library: the
+functions of chexpert_amd.ops and the `lib` / `ptr` / `stream_ptr` / `check` names of the modules that use them are replaced by
+recorders, so `eng.forward` / `eng.backward` run on CPU tensors and leave the list of calls they would have issued.  A host-side
+refactor of an engine is right when this list is EQUAL before and after, for every configuration below.
+
+The wrappers of ops named in REAL run for real (on the recorders' `lib`): what they log is the C call they make, so a tree whose
+engine calls `lib.cx_*` itself and a tree that goes through those wrappers leave the same list.  The library stand-in knows the
+names of `_lib.SIGNATURES` and no other, as the library does.
 
     python scratch/record_calls.py [TREE] [--dump DIR]
 
@@ -22,6 +26,10 @@ from torch.overrides import TorchFunctionMode
 
 ROWS = 7
 SWITCHES = ("CHEXPERT_DET", "CHEXPERT_JOIN_FUSE", "CHEXPERT_FWD_JOIN_FUSE", "CHEXPERT_STREAM_LO")
+# functions of ops that run for real: the helpers every wrapper uses, and the wrappers of the entry points the engines once called raw
+REAL = {"_nhwc", "_fn", "_dense", "_f32", "_out_hw", "dwconv_fwd", "dwconv_dgrad", "dwconv_wgrad", "gap_se_fwd", "scale_act_bc", "gap_affine_act",
+        "se_bwd_fused", "se_act_bwd", "bn_lin_bwd_stats", "affine2_out", "scale_rows", "dropout_mask_dev", "counter_add", "mul_f32",
+        "linear_fwd", "u8_to_nhwc8", "nchw3_to_nhwc8", "chan_map_table", "affine_to_f32_nchw", "gradcam_map", "cam_norm_upsample"}
 
 
 class Trace:
@@ -72,8 +80,17 @@ def _recorder(name, ret=ROWS, sig=None):
 
 
 class _Lib:
+    def __init__(self, names):
+        self._names = names
+
     def __getattr__(self, name):
+        if name not in self._names:
+            raise AttributeError(name)
         return _recorder("lib." + name, ROWS if name == "cx_last_stat_rows" else 0)
+
+
+class _OnGpu(torch.Tensor):
+    is_cuda = True
 
 
 class _Reducer:
@@ -93,15 +110,22 @@ def patch(pkg):
     ops = pkg.ops
     special = {"_wgrad_ws": (None, None, False), "wgrad_defer_begin": True, "kernel_hint": 0}
     for name, fn in list(vars(ops).items()):
-        if callable(fn) and getattr(fn, "__module__", None) == ops.__name__ and not isinstance(fn, type):
+        if callable(fn) and getattr(fn, "__module__", None) == ops.__name__ and not isinstance(fn, type) and name not in REAL:
             setattr(ops, name, _recorder("ops." + name, special.get(name, ROWS), inspect.signature(fn)))
-    from chexpert_amd.models import efficientnet, resnet
-    for mod in (resnet, efficientnet):
-        mod.lib, mod.ptr, mod.stream_ptr, mod.check = (lambda: _Lib()), (lambda t: None if t is None else _Ptr(t)), (lambda: 0), \
-            (lambda rc, what: None)
+    from chexpert_amd import _lib, gradcam
+    from chexpert_amd.models import densenet, efficientnet, resnet
+    the_lib = _Lib(set(_lib.SIGNATURES))
+    stand_ins = dict(lib=lambda: the_lib, ptr=lambda t: None if t is None else _Ptr(t), stream_ptr=lambda: 0, check=lambda rc, what: None,
+                     require_cuda=lambda *tensors: None)
+    for mod in (ops, densenet, resnet, efficientnet):
+        for name, f in stand_ins.items():
+            if hasattr(mod, name):
+                setattr(mod, name, f)
+    if hasattr(gradcam, "L"):                  # (a tree whose Grad-CAM calls the library through its `_lib as L`)
+        gradcam.L = type("L", (), {k: staticmethod(f) for k, f in stand_ins.items()})
 
 
-def run(name, make, x, *, train=True, dx=False, reducer=False, fp32=False, env=None, steps=2):
+def run(name, make, x, *, train=True, dx=False, reducer=False, fp32=False, env=None, steps=2, eval_first=False, hooked=False, cam=False):
     global TRACE
     for k in SWITCHES:
         os.environ.pop(k, None)
@@ -116,6 +140,17 @@ def run(name, make, x, *, train=True, dx=False, reducer=False, fp32=False, env=N
     if reducer:
         eng.reducer = _Reducer()
     with _TensorWrites():
+        if eval_first:                         # a plain eval forward before the training steps (its workspace is the one they take)
+            eng.release(eng.forward(x, False))
+        if hooked:                             # Grad-CAM's hook protocol: the eval forward and the feature-map launches
+            from chexpert_amd.gradcam import hooked_eval_forward
+            with torch.no_grad():
+                hooked_eval_forward(model, x)
+            steps = 0
+        if cam:                                # grad_cam itself (it insists on a GPU tensor: a CPU one that says it is)
+            from chexpert_amd.gradcam import grad_cam
+            grad_cam(model, x.as_subclass(_OnGpu))
+            steps = 0
         for _ in range(steps):                 # the second step takes the pooled workspace and its backward buffers
             ws = eng.forward(x, train, record=True)
             dl = torch.ones(ws.logits.shape, dtype=torch.float32)
@@ -128,7 +163,7 @@ def run(name, make, x, *, train=True, dx=False, reducer=False, fp32=False, env=N
 
 
 def main():
-    from chexpert_amd.models import BasicBlock, Bottleneck, ResNet, WideResNet
+    from chexpert_amd.models import BasicBlock, Bottleneck, DenseNet, ResNet, WideResNet
     from chexpert_amd.models.efficientnet import construct_model
     x64, x32 = torch.randn(2, 3, 64, 64), torch.randn(2, 3, 32, 32)
     u8 = torch.randint(0, 255, (2, 1, 64, 64), dtype=torch.uint8)
@@ -171,6 +206,22 @@ def main():
         run("efficientnet_b0_frozen_" + tag, eff, x64, train=False, **kw)
         run("efficientnet_b0_dx_reducer_" + tag, eff, x64, dx=True, reducer=True, **kw)
     run("efficientnet_b0_fp32_det", eff, x64, fp32=True)
+    run("efficientnet_b0_u8_det", eff, u8)
+    run("efficientnet_b0_fp32_atomic", eff, x64, fp32=True, env=atomic)
+    run("efficientnet_b0_fp32_after_eval_det", eff, x64, fp32=True, eval_first=True)
+    run("efficientnet_b0_dx_det", eff, x64, dx=True)
+    run("efficientnet_b0_dx_atomic", eff, x64, dx=True, env=atomic)
+    for tag, kw in (("det", {}), ("atomic", dict(env=atomic))):
+        run("efficientnet_b1_" + tag, lambda: construct_model("efficientnet-b1", 5), x64, **kw)
+    bc = lambda: DenseNet(12, (2, 2, 2), 24, num_classes=5)          # growth 12: the channel-padded twin with the CIFAR stem
+    run("densenet_bc_padded_det", bc, x32)
+    run("densenet_bc_padded_fp32_det", bc, x32, fp32=True)
+    run("gradcam_hooks_efficientnet_b0", eff, x64, train=False, hooked=True)
+    run("gradcam_maps_efficientnet_b0", eff, x64, train=False, cam=True)
+    run("gradcam_maps_bottleneck", bott(), x64, train=False, cam=True)
+    run("gradcam_maps_densenet", lambda: DenseNet(32, (2, 2, 2, 2), 64, num_classes=5), x64, train=False, cam=True)
+    run("gradcam_hooks_bottleneck", bott(), x64, train=False, hooked=True)
+    run("gradcam_hooks_densenet", lambda: DenseNet(32, (2, 2, 2, 2), 64, num_classes=5), x64, train=False, hooked=True)
 
 
 if __name__ == "__main__":

@@ -61,6 +61,26 @@ def test_product_library_never_reads_the_environment():
                     assert before.rfind("#ifdef CX_DIAG_TIMING") > before.rfind("#endif"), "%s: %s outside CX_DIAG_TIMING" % (f, name)
 
 
+def test_only_ops_and_the_binding_touch_the_library():
+    """`ops.py` is the one tensor-level layer over the C ABI: no other module of the package names `lib` (imported, called or as
+    `_lib.lib`), so every launch passes a wrapper's shape / dtype / pitch checks."""
+    import ast
+    pkg = os.path.join(ROOT, "chexpert_amd")
+    seen = []
+    for d, _, files in os.walk(pkg):
+        for f in sorted(files):
+            if not f.endswith(".py"):
+                continue
+            path = os.path.join(d, f)
+            rel = os.path.relpath(path, pkg)
+            for node in ast.walk(ast.parse(open(path).read(), path)):
+                names = [node.id] if isinstance(node, ast.Name) else [node.attr] if isinstance(node, ast.Attribute) else \
+                    [a.name for a in node.names] if isinstance(node, ast.ImportFrom) else []
+                if "lib" in names:
+                    seen.append(rel)
+    assert set(seen) == {"ops.py", "_lib.py"}, "the library is reached outside ops.py / _lib.py: %s" % sorted(set(seen))
+
+
 def test_validation_codes_without_launching():
     """Argument validation happens before any launch, so it can be exercised without a GPU."""
     from chexpert_amd import _lib
