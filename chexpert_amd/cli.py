@@ -13,6 +13,11 @@
   --affine              random rotation / translation / scale / shear of the uint8 image on the GPU (training only; it runs before
                         --jitter: geometric first, photometric second), ranges as torchvision's RandomAffine:
                         --affine_degrees 10, --affine_translate 0.05, --affine_scale 0.9 1.1, --affine_shear 0
+  --uncertain POLICY    what an uncertain (-1) training label becomes: ones (the reference's U-Ones, default), zeros, ignore (it stays
+                        -1 and the loss skips it), ones_lsr / zeros_lsr (label smoothing: uniform in [0.55, 0.85] / [0, 0.3])
+  --pos_weight W        `auto` or n_classes floats: BCEWithLogitsLoss's pos_weight, inside the fused step too; auto = per class
+                        (non-ignored negatives) / (positives) of the training labels, clamped to [1/16, 16]
+  --synthetic_uncertain F   that fraction of the synthetic training labels is uncertain (the policy above then applies)
 
 Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N chexpert.py --train ...`; every rank holds a
 replica and a shard of each minibatch stream (per-rank BatchNorm statistics, averaged gradients: DDP semantics), the
@@ -33,6 +38,7 @@ import torch.nn as nn
 from . import metrics as M
 from . import parallel as P
 from . import synth
+from .data import UNCERTAIN_POLICIES, apply_uncertain
 
 ATTR_NAMES = ["Atelectasis", "Cardiomegaly", "Consolidation", "Edema", "Pleural Effusion"]     # dataset.py:25
 
@@ -73,6 +79,9 @@ def build_parser():
     p.add_argument("--affine_translate", type=float, default=0.05, help="translation uniform in +-fraction of the image size, per axis")
     p.add_argument("--affine_scale", type=float, nargs=2, default=[0.9, 1.1], metavar=("LO", "HI"), help="scale uniform in [LO, HI]")
     p.add_argument("--affine_shear", type=float, default=0.0, help="shear along x uniform in +-degrees")
+    p.add_argument("--uncertain", default="ones", choices=list(UNCERTAIN_POLICIES), help="policy for the uncertain (-1) training labels")
+    p.add_argument("--pos_weight", nargs="+", default=None, metavar="W", help="`auto` or n_classes floats: positive-term weights of the loss")
+    p.add_argument("--synthetic_uncertain", type=float, default=0.0, metavar="F", help="fraction of the synthetic training labels marked uncertain")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -83,11 +92,17 @@ def build_parser():
 
 class SyntheticXrays(torch.utils.data.Dataset):
     """Decoded grey bytes (1,S,S) uint8 U{0..255} -- what PIL hands the reference's transform chain (chexpert.py:67-72) after
-    resize / centre-crop -- with Bernoulli(0.3) U-Ones-like labels (dataset.py:139-142)."""
+    resize / centre-crop -- with Bernoulli(0.3) U-Ones-like labels (dataset.py:139-142).  uncertain_frac > 0: a second hash draw,
+    independent of the labels', marks that fraction of them uncertain (-1), and the policy `uncertain` (data.apply_uncertain)
+    then says what they become; 0 leaves the labels as they were, bit for bit."""
 
-    def __init__(self, n, size, n_classes, seed):
+    def __init__(self, n, size, n_classes, seed, uncertain_frac=0.0, uncertain="ones"):
         self.n, self.size, self.n_classes, self.seed = n, size, n_classes, seed
         self.targets = synth.targets(seed + 1, n, n_classes)
+        if uncertain_frac > 0:
+            lab = self.targets.numpy().copy()
+            lab[synth.uniform01(seed * 7919 + 104729, n * n_classes).reshape(n, n_classes) < uncertain_frac] = -1.0
+            self.targets = torch.from_numpy(apply_uncertain(lab, uncertain, seed))
 
     def __len__(self):
         return self.n
@@ -112,6 +127,28 @@ def make_affine(args, rank, device):
         return None
     from .augment import RandomAffine
     return RandomAffine(args.affine_degrees, args.affine_translate, args.affine_scale, args.affine_shear, rank, device)
+
+
+def resolve_pos_weight(spec, targets, n_classes):
+    """--pos_weight as a list of n_classes floats, or None.  `auto`: per class (non-ignored negatives) / (positives) of the training
+    targets on the host, soft labels counted by their value (t to the positives, 1 - t to the negatives), clamped to [1/16, 16]
+    (a class without positives gets 16)."""
+    if spec is None:
+        return None
+    spec = [spec] if isinstance(spec, str) else list(spec)
+    if len(spec) == 1 and str(spec[0]) == "auto":
+        t = np.asarray(targets, dtype=np.float64)
+        live = t >= 0
+        pos = np.where(live, t, 0.0).sum(0)
+        neg = np.where(live, 1.0 - t, 0.0).sum(0)
+        w = np.where(pos > 0, neg / np.maximum(pos, 1e-300), 16.0)
+        return [float(v) for v in np.clip(w, 1.0 / 16, 16.0)]
+    w = [float(v) for v in spec]
+    if len(w) != n_classes:
+        raise ValueError("--pos_weight takes `auto` or %d floats (got %d)" % (n_classes, len(w)))
+    if not all(np.isfinite(v) and v > 0 for v in w):
+        raise ValueError("--pos_weight takes finite weights > 0 (got %s)" % w)
+    return w
 
 
 def make_model(args, device):
@@ -167,6 +204,9 @@ def evaluate(model, ds, indices, batch_size, device):
     model.eval()
     outs, tgts, losses, ids = [], [], [], []
     loss_fn = nn.BCEWithLogitsLoss(reduction="none")
+    if bool((ds.targets < 0).any()):               # ignored labels in this table: their element losses are 0 (cx_bce_masked_fwd_bwd)
+        from .loss import MaskedBCE
+        loss_fn = MaskedBCE().elementwise
     for x, t, idx in batches(ds, indices, batch_size, False):
         o = model(x.to(device))
         losses.append(loss_fn(o, t.to(device)))
@@ -253,6 +293,10 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.load_config:
         args.__dict__.update(json.load(open(args.load_config)))
+    if not 0.0 <= args.synthetic_uncertain <= 1.0:
+        raise ValueError("--synthetic_uncertain takes a fraction in [0, 1] (got %r)" % args.synthetic_uncertain)
+    if args.synthetic_uncertain > 0 and not args.synthetic:
+        raise ValueError("--synthetic_uncertain marks labels of the synthetic set: pass --synthetic N with it")
     rank, world, local = P.dist_info()
     if world > 1:
         # the process group comes first, before anything touches the GPU; one rank per GPU over RCCL ("nccl"), or ranks sharing
@@ -268,7 +312,8 @@ def main(argv=None):
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
         cfg_path = os.path.join(args.output_dir, "config.json")
-        if not os.path.exists(cfg_path):
+        new_cfg = not os.path.exists(cfg_path)
+        if new_cfg:
             json.dump(args.__dict__, open(cfg_path, "w"), indent=4)
     # datasets and the training loader come BEFORE the first GPU call: its worker processes are forked from a process that has
     # not initialised the GPU runtime and never touch the card (chexpert_amd/loader.py)
@@ -276,18 +321,24 @@ def main(argv=None):
     device = torch.device("cuda:%d" % (args.cuda or 0))
     if args.synthetic:
         n_valid = max(args.batch_size, args.synthetic // 5)
-        train_ds = SyntheticXrays(args.mini_data or args.synthetic, size, args.n_classes, 7)
+        train_ds = SyntheticXrays(args.mini_data or args.synthetic, size, args.n_classes, 7, args.synthetic_uncertain, args.uncertain)
         valid_ds = SyntheticXrays(n_valid, size, args.n_classes, 11)
     else:                                  # chexpert.py:64-79 over the extracted CheXpert-v1.0-small folder (uint8 to the GPU)
         from .data import ChexpertCSV
         if not args.data_path:
             raise RuntimeError("pass --data_path <folder holding CheXpert-v1.0-small> or --synthetic N (no download here)")
-        train_ds = ChexpertCSV(args.data_path, "train", args.resize, mini_data=args.mini_data)
+        train_ds = ChexpertCSV(args.data_path, "train", args.resize, mini_data=args.mini_data, uncertain=args.uncertain, seed=args.seed)
         # (under torch.distributed.run the ranks of a node share one table: --cache_decoded is then the node's budget)
         if args.cache_decoded > 0 and not train_ds.enable_decoded_cache(int(args.cache_decoded * 2 ** 30),
                                                                          node_shared=int(os.environ.get("WORLD_SIZE", "1")) > 1):
             print("decoded-image cache off: %d images of %d^2 bytes exceed --cache_decoded %.1f GB" % (len(train_ds), train_ds.crop, args.cache_decoded))
         valid_ds = ChexpertCSV(args.data_path, "valid", args.resize, mini_data=args.mini_data)
+    pos_weight = resolve_pos_weight(args.pos_weight, train_ds.targets, args.n_classes)
+    if pos_weight is not None and rank == 0 and new_cfg:       # the resolved vector goes beside the flags that asked for it: a config
+        # kept from an earlier run (restore into its output_dir) stays whole, as that run wrote it
+        cfg = json.load(open(cfg_path))
+        cfg["pos_weight_resolved"] = pos_weight
+        json.dump(cfg, open(cfg_path, "w"), indent=4)
     train_loader = None
     if args.train:
         from .loader import RingLoader
@@ -302,6 +353,11 @@ def main(argv=None):
     if args.restore and os.path.isfile(args.restore):
         restore(args, model, optimizer, scheduler, device)
     loss_fn = nn.BCEWithLogitsLoss(reduction="none")
+    masked_loss = None
+    if args.uncertain == "ignore" or pos_weight is not None:
+        from .loss import MaskedBCE
+        model.set_loss(ignore_negative=args.uncertain == "ignore", pos_weight=pos_weight)      # the fused step's loss
+        masked_loss = MaskedBCE(model.loss_pos_weight, ignore_negative=args.uncertain == "ignore")   # the autograd route's
     if rank == 0:
         print("Loaded %s (number of parameters: %s; weights trained to step %d)" % (
             model._get_name(), format(sum(p.numel() for p in model.parameters()), ","), args.step))
@@ -364,7 +420,7 @@ def main(argv=None):
                         optimizer.scheduler_step()
                 else:
                     out = model(x)
-                    loss = loss_fn(out, t).sum(1).mean(0)                     # chexpert.py:160
+                    loss = masked_loss(out, t) if masked_loss is not None else loss_fn(out, t).sum(1).mean(0)   # chexpert.py:160
                     optimizer.zero_grad()
                     loss.backward()
                     optimizer.step()

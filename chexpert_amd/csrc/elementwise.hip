@@ -1,6 +1,7 @@
 // HBM-bound glue kernels of the DenseNet hot path: layout conversion, weight packing, BatchNorm
 // coefficient bookkeeping, stem pooling, head, loss, un-pooling and the fused optimisers.
 // All activation traffic is 16 B per lane along the channel axis (NHWC bf16).
+#include <type_traits>
 #include <vector>
 #include "common.h"
 
@@ -649,6 +650,43 @@ __global__ void bce_kernel(const float* __restrict__ logits, const float* __rest
     __syncthreads();
   }
   if (threadIdx.x == 0 && loss) *loss = red[0] * invB;
+}
+
+// bce_kernel with ignored elements (target < 0: no loss, no gradient; the divisor stays B) and, when WEIGHTED, a per-class positive
+// weight (torch's BCEWithLogitsLoss(pos_weight)).  One workgroup, fixed tree, no atomics.  Unweighted, a live element runs
+// bce_kernel's expressions and the sum its fp32 tree, so targets without negatives give bce_kernel's bits.  Weighted, the sum runs
+// in double: weights up to 16 on logits of +-8 take the batch sum of 256 x 14 elements past 1e4, where an fp32 add rounds to 5e-4.
+template <bool WEIGHTED>
+__global__ void bce_masked_kernel(const float* __restrict__ logits, const float* __restrict__ target, const float* __restrict__ pos_weight,
+                                  float* loss, float* loss_elem, float* dlogits, float grad_scale, int B, int n) {
+  using Acc = typename std::conditional<WEIGHTED, double, float>::type;
+  __shared__ Acc red[256];
+  Acc acc = 0;
+  const float invB = 1.f / B;
+  for (int i = threadIdx.x; i < B * n; i += blockDim.x) {
+    const float x = logits[i], t = target[i];
+    float l = 0.f, d = 0.f;
+    if (t >= 0.f) {
+      if (WEIGHTED) {
+        const float w = 1.f + (pos_weight[i % n] - 1.f) * t;
+        l = (1.f - t) * x + w * (log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f));
+        d = ((1.f - t) - w * (1.f / (1.f + expf(x)))) * invB * grad_scale;      // 1 - sigmoid(x) = sigmoid(-x), without the cancellation
+      } else {
+        l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+        d = (1.f / (1.f + expf(-x)) - t) * invB * grad_scale;
+      }
+    }
+    acc += l;
+    if (loss_elem) loss_elem[i] = l;
+    if (dlogits) dlogits[i] = d;
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && loss) *loss = WEIGHTED ? (float)(red[0] / B) : (float)red[0] * invB;
 }
 
 // one wave per sample: row maximum and sum of exponentials by DPP-free shuffles, loss = mean_b (logsumexp - logit[target]);
@@ -1773,6 +1811,18 @@ int cx_bce_fwd_bwd(const float* logits, const float* target, float* loss, float*
   if (!logits || !target || B <= 0 || n_classes <= 0) return CX_EINVAL;
   hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(256), 0, as_stream(stream), logits, target, loss, loss_elem, dlogits, grad_scale, B,
                      n_classes);
+  return launch_status();
+}
+
+int cx_bce_masked_fwd_bwd(const float* logits, const float* target, const float* pos_weight, float* loss, float* loss_elem,
+                          float* dlogits, float grad_scale, int B, int n_classes, void* stream) {
+  if (!logits || !target || B <= 0 || n_classes <= 0) return CX_EINVAL;
+  if (pos_weight)
+    hipLaunchKernelGGL(bce_masked_kernel<true>, dim3(1), dim3(256), 0, as_stream(stream), logits, target, pos_weight, loss, loss_elem,
+                       dlogits, grad_scale, B, n_classes);
+  else
+    hipLaunchKernelGGL(bce_masked_kernel<false>, dim3(1), dim3(256), 0, as_stream(stream), logits, target, pos_weight, loss, loss_elem,
+                       dlogits, grad_scale, B, n_classes);
   return launch_status();
 }
 

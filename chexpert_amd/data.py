@@ -4,6 +4,7 @@
 the models' input kernels (cx_u8_to_nhwc4 / cx_u8_to_nhwc8), so a batch crosses PCIe at one byte per pixel.
 
 Labels follow dataset.py:134-153 (U-Ones): training rows get blanks -> 0 and uncertain (-1) -> 1 on the five competition findings;
+`uncertain=` selects the other policies of the dataset's paper (apply_uncertain: zeros, ignore, the two label-smoothed ones);
 the validation file is used as it is; `test` mode reads a bare csv of paths with zero labels (dataset.py:33-37).  Nothing is
 downloaded here (no network): a missing data folder raises.
 """
@@ -15,6 +16,31 @@ from PIL import Image
 
 ATTR_NAMES = ["Atelectasis", "Cardiomegaly", "Consolidation", "Edema", "Pleural Effusion"]      # dataset.py:26
 DIR_NAME = "CheXpert-v1.0-small"                                                                  # dataset.py:18-19
+
+
+UNCERTAIN_POLICIES = ("ones", "zeros", "ignore", "ones_lsr", "zeros_lsr")
+_LSR_RANGE = {"ones_lsr": (0.55, 0.85), "zeros_lsr": (0.0, 0.3)}          # the label-smoothed U-Ones / U-Zeros variants
+
+
+def apply_uncertain(labels, policy, seed=0):
+    """What an uncertain label (-1) becomes under `policy` (dataset.py:119, :141 "setup options for uncertain labels"), on a float
+    (N, C) numpy table whose blanks are already 0: 'ones' -> 1 (the reference's hard-wired U-Ones), 'zeros' -> 0, 'ignore' -> it
+    stays -1 (the loss skips it: FusedNet.set_loss / MaskedBCE), 'ones_lsr' / 'zeros_lsr' -> a value uniform in [0.55, 0.85] /
+    [0, 0.3], drawn once from synth.uniform01 keyed by (seed, row, class).  Returns a new float32 table."""
+    if policy not in UNCERTAIN_POLICIES:
+        raise ValueError("uncertain policy must be one of %s (got %r)" % (", ".join(UNCERTAIN_POLICIES), policy))
+    lab = np.array(labels, dtype=np.float32)
+    unc = lab == -1
+    if policy == "ones":
+        lab[unc] = 1.0
+    elif policy == "zeros":
+        lab[unc] = 0.0
+    elif policy != "ignore":
+        from . import synth
+        lo, hi = _LSR_RANGE[policy]
+        u = synth.uniform01(seed, lab.size).reshape(lab.shape)            # element (row, class) reads counter row * C + class
+        lab[unc] = (lo + (hi - lo) * u[unc]).astype(np.float32)
+    return lab
 
 
 def resize_center_crop(img, resize, crop):
@@ -40,12 +66,16 @@ def resize_center_crop(img, resize, crop):
 
 class ChexpertCSV(torch.utils.data.Dataset):
     """mode 'train' / 'valid' / 'vis': `root` holds the extracted CheXpert-v1.0-small folder; 'test': `root` is a csv of image paths.
-    Items are (uint8 (1,S,S), float32 labels (5,), row index in the source table) like the reference's (img, attr, idx)."""
+    Items are (uint8 (1,S,S), float32 labels (5,), row index in the source table) like the reference's (img, attr, idx).
+    uncertain / seed: the policy for the -1 labels of the training table (apply_uncertain) and the seed of its label-smoothing draws."""
     attr_names = ATTR_NAMES
 
-    def __init__(self, root, mode="train", resize=None, data_filter=None, mini_data=None):
+    def __init__(self, root, mode="train", resize=None, data_filter=None, mini_data=None, uncertain="ones", seed=0):
         import pandas as pd
         assert mode in ("train", "valid", "test", "vis")
+        if uncertain not in UNCERTAIN_POLICIES:
+            raise ValueError("uncertain policy must be one of %s (got %r)" % (", ".join(UNCERTAIN_POLICIES), uncertain))
+        self.uncertain = uncertain         # acts on the training table only
         self.mode, self.resize, self.crop = mode, resize, (resize or 320)
         root = os.path.expanduser(root)
         if mode == "test":
@@ -61,7 +91,10 @@ class ChexpertCSV(torch.utils.data.Dataset):
             self.csv_path = os.path.join(folder, "train.csv" if mode == "train" else "valid.csv")      # (also part of the decoded-cache key)
             df = pd.read_csv(self.csv_path, keep_default_na=True)
             if mode == "train":
-                df[self.attr_names] = df[self.attr_names].fillna(0).replace(-1, 1)            # U-Ones
+                if uncertain == "ones":
+                    df[self.attr_names] = df[self.attr_names].fillna(0).replace(-1, 1)        # U-Ones
+                else:                      # on the whole table, before any filter: a draw belongs to its row of the file
+                    df[self.attr_names] = apply_uncertain(df[self.attr_names].fillna(0).values, uncertain, seed)
                 for k, v in (data_filter or {}).items():
                     df = df[df[k] == v]
         if mini_data is not None:

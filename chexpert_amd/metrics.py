@@ -45,16 +45,25 @@ def precision_recall_curve(y_true, score):
 
 
 def compute_metrics(outputs, targets, losses):
-    """Same dictionary layout as chexpert.py:130-146 (lists per class, json-serialisable)."""
+    """Same dictionary layout as chexpert.py:130-146 (lists per class, json-serialisable).  A row whose target is negative (an
+    uncertain label kept as -1) is left out of that class's curves and of that class's mean loss."""
     outputs, targets, losses = (np.asarray(t, dtype=np.float64) for t in (outputs, targets, losses))
+    if not (targets < 0).any():
+        mean_loss = losses.mean(0).tolist()
+    else:
+        mean_loss = [float(losses[targets[:, i] >= 0, i].mean()) if (targets[:, i] >= 0).any() else float("nan")
+                     for i in range(outputs.shape[1])]
     fpr, tpr, aucs, precision, recall = {}, {}, {}, {}, {}
     for i in range(outputs.shape[1]):
-        f, t, _ = roc_curve(targets[:, i], outputs[:, i])
+        keep = targets[:, i] >= 0
+        if len(keep) and not keep.any():                  # a class with every label ignored has no curve
+            aucs[i], fpr[i], tpr[i], precision[i], recall[i] = float("nan"), [], [], [], []
+            continue
+        f, t, _ = roc_curve(targets[keep, i], outputs[keep, i])
         aucs[i] = auc(f, t)
-        p, r, _ = precision_recall_curve(targets[:, i], outputs[:, i])
+        p, r, _ = precision_recall_curve(targets[keep, i], outputs[keep, i])
         fpr[i], tpr[i], precision[i], recall[i] = f.tolist(), t.tolist(), p.tolist(), r.tolist()
-    return {"fpr": fpr, "tpr": tpr, "aucs": aucs, "precision": precision, "recall": recall,
-            "loss": dict(enumerate(losses.mean(0).tolist()))}
+    return {"fpr": fpr, "tpr": tpr, "aucs": aucs, "precision": precision, "recall": recall, "loss": dict(enumerate(mean_loss))}
 
 
 def mean_auc(metrics):

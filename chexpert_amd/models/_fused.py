@@ -102,6 +102,35 @@ class FusedNet(nn.Module):
         super().__init__()
         self._nbt_pending = 0            # training forwards not yet counted in the BatchNorms' num_batches_tracked
         self._engine = None
+        # set_loss(): plain tensors / flags, not buffers (the state_dict keys stay what they are)
+        self.loss_ignore_negative, self.loss_pos_weight, self._pos_weight_store = False, None, None
+
+    def set_loss(self, ignore_negative=False, pos_weight=None):
+        """The loss of forward_backward.  ignore_negative: a target < 0 (an uncertain label kept as -1, the U-Ignore policy) adds no
+        loss and no gradient; the divisor stays the batch size.  pos_weight: None, or n_classes positive-term weights as in torch's
+        BCEWithLogitsLoss(pos_weight).  Either option routes the step through cx_bce_masked_fwd_bwd, which skips every target < 0:
+        the weighted loss has no arithmetic for a negative target, so pos_weight implies the skipping, and ignore_negative decides
+        between the two kernels only when there are no weights.  set_loss() puts the plain loss back, to which a negative target
+        is a number like any other.  The weights live in one fp32 tensor (`loss_pos_weight`), neither buffer nor parameter, so
+        state_dict() is what it was.  Returns self.
+
+        Choose the loss BEFORE a step is captured (GraphedTrainStep, SegmentedTrainStep): a captured step replays the kernel and
+        the weight storage it was captured with.  What a replay does see is a change of the weights' VALUES -- in place
+        (`model.loss_pos_weight.mul_(2)`) or by set_loss(pos_weight=...) with the same number of weights and the same options,
+        which copies into the held storage.  A switch between the plain and the masked loss, from no weights to weights or
+        back, or to another number of weights (new storage) needs a new capture."""
+        if pos_weight is not None:
+            dev = next(self.parameters()).device
+            if dev.type != "cuda":
+                raise RuntimeError("set_loss(pos_weight=...) holds the weights on the parameters' device: call model.to(device) first")
+            w = torch.as_tensor(pos_weight, dtype=torch.float32).reshape(-1)
+            held = self._pos_weight_store
+            if held is None or held.numel() != w.numel() or held.device != dev:
+                held = self._pos_weight_store = torch.empty(w.numel(), dtype=torch.float32, device=dev)
+            held.copy_(w)
+        self.loss_pos_weight = self._pos_weight_store if pos_weight is not None else None
+        self.loss_ignore_negative = bool(ignore_negative)
+        return self
 
     def storage_dtype(self, dtype):
         """Storage type of the activations inside the fused schedule: torch.bfloat16 (default: bf16 tensors, fp32 accumulation
@@ -144,7 +173,8 @@ class FusedNet(nn.Module):
         """logits = model(x); loss = BCEWithLogits(logits, target).sum(1).mean(0); loss.backward().
         Returns (loss, logits) as device tensors without a host sync.  input_grad: None, or a preallocated fp32 (B,3,H,W) tensor that
         also receives d loss / d x (what x.grad would hold), still without a host sync.  In eval mode this is the frozen-BatchNorm
-        step (running statistics, which stay as they are)."""
+        step (running statistics, which stay as they are).  After set_loss(...) the loss ignores targets < 0 and / or weights the
+        positive term per class (same reduction, same divisor)."""
         eng = self._eng()
         if input_grad is not None:
             check_input_grad(input_grad, x)
@@ -152,7 +182,10 @@ class FusedNet(nn.Module):
         B, n = ws.logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
-        ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
+        if self.loss_ignore_negative or self.loss_pos_weight is not None:      # set_loss(): ignored labels / class weights
+            ops.bce_masked_fwd_bwd(ws.logits, target, self.loss_pos_weight, loss, None, dl)
+        else:
+            ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
         eng.backward(ws, dl, dx=input_grad)
         logits = ws.logits.clone()
         eng.release(ws)

@@ -560,6 +560,21 @@ def bce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):
                                stream_ptr()), "cx_bce_fwd_bwd")
 
 
+def bce_masked_fwd_bwd(logits, target, pos_weight, loss, loss_elem, dlogits, grad_scale=1.0):
+    """bce_fwd_bwd in which a target < 0 is ignored (no loss, no gradient; the divisor stays B) and pos_weight (fp32 (n,), or None)
+    weights the positive term per class as torch's BCEWithLogitsLoss(pos_weight) does.  loss, loss_elem and dlogits are optional."""
+    require_cuda(logits, target, pos_weight, loss, loss_elem, dlogits)
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    B, n = logits.shape
+    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (B, n) and target.device == logits.device
+    assert pos_weight is None or (tuple(pos_weight.shape) == (n,) and pos_weight.device == logits.device)
+    _f32(pos_weight, n=n)
+    _f32(loss, n=1)
+    _f32(loss_elem, dlogits, n=B * n)
+    check(lib().cx_bce_masked_fwd_bwd(ptr(logits), ptr(target), ptr(pos_weight), ptr(loss), ptr(loss_elem), ptr(dlogits), grad_scale,
+                                      B, n, stream_ptr()), "cx_bce_masked_fwd_bwd")
+
+
 def softmax_ce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):
     """CrossEntropyLoss forward + gradient in one launch (fp32 logits [B, n], int64 class indices [B])."""
     B, n = logits.shape

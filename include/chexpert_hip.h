@@ -346,6 +346,18 @@ int cx_head_fwd(const void* x, const float* scale, const float* shift, const flo
  * (chexpert.py:160, :530)                                                                         */
 int cx_bce_fwd_bwd(const float* logits, const float* target, float* loss, float* loss_elem, float* dlogits,
                    float grad_scale, int B, int n_classes, void* stream);
+/* cx_bce_fwd_bwd with ignored labels and class weights: the uncertainty policies the reference asks for (dataset.py:119, :141
+ * "setup options for uncertain labels") and torch's BCEWithLogitsLoss(pos_weight).  Per element, x = logits[b][c], t = target[b][c],
+ * p = pos_weight ? pos_weight[c] : 1:
+ *   t < 0   ignored: loss_elem = 0, dlogits = 0, nothing added to loss
+ *   else    w = 1 + (p-1) t;  l = (1-t) x + w (log1p(exp(-|x|)) + max(-x, 0));  dl/dx = (1-t) - w (1 - sigmoid(x))
+ * loss = sum l / B (the divisor stays the batch size, whatever is ignored: .sum(1).mean(0) over the masked element losses),
+ * dlogits = dl/dx / B * grad_scale.  Soft targets in [0,1] are valid.  pos_weight: fp32 [n_classes] on the device, or NULL; with
+ * NULL a live element runs cx_bce_fwd_bwd's expressions, so targets without negatives give its loss, loss_elem and dlogits bit for
+ * bit.  loss, loss_elem and dlogits are optional.  One workgroup, fixed tree, no atomics: bit-reproducible.  Additive entry point
+ * of ABI 10 (no struct changed).                                                                                               */
+int cx_bce_masked_fwd_bwd(const float* logits, const float* target, const float* pos_weight, float* loss, float* loss_elem,
+                          float* dlogits, float grad_scale, int B, int n_classes, void* stream);
 /* loss = CrossEntropyLoss(logits, target) (mean over the batch of logsumexp - logit[target]);
  * dlogits = (softmax - onehot)/B * grad_scale; loss_elem (optional) = the per-sample terms
  * (models/test_model.py:118, :143, :331: the CIFAR harness criterion)                              */
