@@ -189,6 +189,8 @@ SIGNATURES = {
     "cx_linear_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "cx_gradcam_map": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "cx_cam_norm_upsample": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "cx_class_cam": [_vp] * 6 + [_i] * 9 + [_vp],
+    "cx_class_cam_f32": [_vp] * 6 + [_i] * 9 + [_vp],
     "cx_fill_f32": [_vp, _f, _sz, _vp],
     "cx_copy_stream": [_vp, _vp, _sz, _vp],
     "cx_affine_to_f32_nchw": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],

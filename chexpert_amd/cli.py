@@ -17,6 +17,8 @@
                         -1 and the loss skips it), ones_lsr / zeros_lsr (label smoothing: uniform in [0.55, 0.85] / [0, 0.3])
   --pos_weight W        `auto` or n_classes floats: BCEWithLogitsLoss's pos_weight, inside the fused step too; auto = per class
                         (non-ignored negatives) / (positives) of the training labels, clamped to [1/16, 16]
+  --cam_classes [C ...] with --visualize: class-specific maps (gradcam.class_cam) of the 'vis' subset for these class indices (no value
+                        or `all`: every class): vis/class_cam_lowres.npy (N, K, h, w) and one vis/classcam_<ident>_step_<N>.png per image
   --synthetic_uncertain F   that fraction of the synthetic training labels is uncertain (the policy above then applies)
 
 Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N chexpert.py --train ...`; every rank holds a
@@ -82,6 +84,8 @@ def build_parser():
     p.add_argument("--uncertain", default="ones", choices=list(UNCERTAIN_POLICIES), help="policy for the uncertain (-1) training labels")
     p.add_argument("--pos_weight", nargs="+", default=None, metavar="W", help="`auto` or n_classes floats: positive-term weights of the loss")
     p.add_argument("--synthetic_uncertain", type=float, default=0.0, metavar="F", help="fraction of the synthetic training labels marked uncertain")
+    p.add_argument("--cam_classes", nargs="*", default=None, metavar="CLASS",
+                   help="with --visualize: class-specific maps (gradcam.class_cam) of these class indices; no value or `all` = every class")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -149,6 +153,22 @@ def resolve_pos_weight(spec, targets, n_classes):
     if not all(np.isfinite(v) and v > 0 for v in w):
         raise ValueError("--pos_weight takes finite weights > 0 (got %s)" % w)
     return w
+
+
+def resolve_cam_classes(spec, n_classes):
+    """--cam_classes as a list of class indices, or None when the flag is absent.  No value or `all`: every class."""
+    if spec is None:
+        return None
+    spec = [str(s) for s in spec]
+    if not spec or spec == ["all"]:
+        return list(range(n_classes))
+    try:
+        classes = [int(s) for s in spec]
+    except ValueError:
+        raise ValueError("--cam_classes takes class indices, `all` or no value (got %s)" % spec)
+    if not all(0 <= c < n_classes for c in classes):
+        raise ValueError("--cam_classes takes indices in [0, %d) (got %s)" % (n_classes, classes))
+    return classes
 
 
 def make_model(args, device):
@@ -297,6 +317,9 @@ def main(argv=None):
         raise ValueError("--synthetic_uncertain takes a fraction in [0, 1] (got %r)" % args.synthetic_uncertain)
     if args.synthetic_uncertain > 0 and not args.synthetic:
         raise ValueError("--synthetic_uncertain marks labels of the synthetic set: pass --synthetic N with it")
+    cam_classes = resolve_cam_classes(getattr(args, "cam_classes", None), args.n_classes)
+    if cam_classes is not None and not args.visualize:
+        raise ValueError("--cam_classes draws class maps over the 'vis' subset: pass --visualize with it")
     rank, world, local = P.dist_info()
     if world > 1:
         # the process group comes first, before anything touches the GPU; one rank per GPU over RCCL ("nccl"), or ranks sharing
@@ -463,12 +486,12 @@ def main(argv=None):
         # chexpert.py:556-563: Grad-CAM grids over the 'vis' subset (three examples per finding category), and for the
         # attention-augmented models the attention-map grids of the stored softmax weights
         from . import vis
-        from .gradcam import grad_cam
+        from .gradcam import class_cam, grad_cam
         names = ATTR_NAMES[:args.n_classes] if args.n_classes <= len(ATTR_NAMES) else ["class %d" % i for i in range(args.n_classes)]
         groups = vis.select_vis_subset(valid_ds.targets, names)
         flat = sorted({i for g in groups[1] for i in g})
         pos = {i: k for k, i in enumerate(flat)}
-        imgs, labels, scores, masks = [], [], [], []
+        imgs, labels, scores, masks, class_maps = [], [], [], [], []
         model.eval()
         attn_layers = [m for m in model.modules() if type(m).__name__ == "AAConv2d"]
         for x, tg, idx in batches(valid_ds, flat, args.batch_size, False):
@@ -476,6 +499,8 @@ def main(argv=None):
             with torch.no_grad():
                 scores.append(model(xd).float().cpu())
             masks.append(grad_cam(model, xd).float().cpu())
+            if cam_classes is not None:         # the raw low-resolution relu(M): up-sampled maps of 14 classes would be hundreds of MB
+                class_maps.append(class_cam(model, xd, cam_classes, normalize=False, upsample=False)[0].cpu())
             imgs.append(x.float().div(255.0)[:, 0] if x.dtype == torch.uint8 else (x.float()[:, 0] * vis.STD + vis.MEAN))
             labels.append(tg)
             if attn_layers:
@@ -489,6 +514,12 @@ def main(argv=None):
                               groups, args.output_dir, getattr(args, "step", 0))
         np.save(os.path.join(args.output_dir, "vis", "grad_cam.npy"), cam.numpy())
         print("grad-cam maps:", tuple(cam.shape), "figures:", len(files))
+        if cam_classes is not None:
+            class_maps = torch.cat(class_maps)
+            files = vis.visualize_classes(imgs.numpy(), labels.numpy(), scores.numpy(), class_maps.numpy(), ["synthetic/%d" % i for i in flat],
+                                          names, cam_classes, args.output_dir, getattr(args, "step", 0))
+            np.save(os.path.join(args.output_dir, "vis", "class_cam_lowres.npy"), class_maps.numpy())
+            print("class maps:", tuple(class_maps.shape), "figures:", len(files))
     if args.plot_roc and rank == 0:
         files = [f for f in os.listdir(args.output_dir) if f.startswith("eval_results") and f.endswith(".json")]
         if not files:

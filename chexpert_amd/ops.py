@@ -981,6 +981,41 @@ def gradcam_map(x, scale, shift, w, cam, inner_relu):
           "cx_gradcam_map")
 
 
+CAM_ACT_NONE, CAM_ACT_RELU, CAM_ACT_SWISH = 0, 1, 2
+
+
+def class_cam(x, scale, shift, w, cam, *, act, relu=True, cls=None):
+    """cx_class_cam: cam (B,K,H*W) fp32 = post(1/(H*W) * sum_f w[cls(b,k), f] * act(x*scale + shift)), all K classes in one launch that
+    reads x once.  x: bf16 or fp32-mode NHWC view (channel pitch allowed); scale / shift: fp32 (C) or both None (identity);
+    act: CAM_ACT_*; w: fp32 (n_classes, C) with unit column stride; post = ReLU when `relu`.
+    cls: None -- map k is class k, K = n_classes; a list / tuple of K class indices -- the same classes for every image, range-checked
+    here (ValueError) before anything is launched; an int32 device tensor (B, K) -- one row of classes per image, NOT checked (that
+    would be a host sync): the kernel clamps every entry into [0, n_classes)."""
+    require_cuda(x, scale, shift, w, cam)
+    B, H, W, Cc, ldx = _nhwc(x)
+    assert (scale is None) == (shift is None), "scale and shift come together"
+    _f32(scale, shift, n=Cc)
+    assert act in (CAM_ACT_NONE, CAM_ACT_RELU, CAM_ACT_SWISH), "act is one of ops.CAM_ACT_*"
+    assert w.dtype == torch.float32 and w.dim() == 2 and w.shape[1] == Cc and w.stride(1) == 1, "w: fp32 (n_classes, C) rows"
+    n_classes, ldw = w.shape[0], w.stride(0)
+    assert cam.dtype == torch.float32 and cam.is_contiguous() and cam.dim() == 3 and cam.shape[0] == B and cam.shape[2] == H * W, \
+        "cam: contiguous fp32 (B, K, H*W)"
+    K = cam.shape[1]
+    if isinstance(cls, (list, tuple)):
+        if len(cls) != K or K < 1:
+            raise ValueError("class_cam: %d class indices for %d maps per image" % (len(cls), K))
+        if not all(isinstance(c, int) and 0 <= c < n_classes for c in cls):
+            raise ValueError("class_cam: class indices must be ints in [0, %d) (got %s)" % (n_classes, list(cls)))
+        cls = torch.tensor(list(cls), dtype=torch.int32).repeat(B, 1).to(x.device)
+    if cls is not None:
+        require_cuda(cls)
+        assert cls.dtype == torch.int32 and cls.is_contiguous() and tuple(cls.shape) == (B, K), "cls: contiguous int32 (B, K)"
+    else:
+        assert K == n_classes, "without a class table the maps are those of all n_classes classes"
+    check(_fn("cx_class_cam", x)(ptr(x), ptr(scale), ptr(shift), ptr(w), ptr(cls), ptr(cam), B, H * W, Cc, ldx, n_classes, ldw, K,
+                                 act, int(bool(relu)), stream_ptr()), "cx_class_cam")
+
+
 def cam_norm_upsample(cam, out, h, w):
     """cx_cam_norm_upsample: out (B,1,H,W) = the h x w maps cam (B,h*w) scaled to [0, 1] per image and up-sampled bilinearly."""
     require_cuda(cam, out)

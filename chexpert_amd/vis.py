@@ -111,3 +111,36 @@ def vis_attn(x, idents, idxs, attn_layers, out_dir, batch_element=0, window=30):
         plt.close(fig)
         written.append(path)
     return written
+
+
+def visualize_classes(imgs, labels, logits, cams, idents, attr_names, classes, out_dir, step):
+    """Per-finding localisation figures (gradcam.class_cam): imgs (N,H,W) in [0,1], labels (N,C), logits (N,C), cams (N,K,h,w) the maps
+    of the K classes `classes` (indices into attr_names) at any resolution -- each is scaled to its own range and stretched over
+    the image for display.  One figure per image, vis/classcam_<ident>_step_<step>.png: the radiograph, then one overlay per class
+    titled with the class name, its label and its sigmoid probability (plotting conventions of `_row`)."""
+    plt = _plt()
+    os.makedirs(os.path.join(out_dir, "vis"), exist_ok=True)
+    probs = 1.0 / (1.0 + np.exp(-np.asarray(logits, dtype=np.float64)))
+    cams = np.asarray(cams, dtype=np.float64)
+    K = len(classes)
+    assert cams.ndim == 4 and cams.shape[1] == K, "cams: (N, K, h, w) with one map per requested class"
+    H, W = imgs.shape[1], imgs.shape[2]
+    written = []
+    for i in range(len(imgs)):
+        fig, axs = plt.subplots(1, K + 1, figsize=((K + 1) * max(W, 128) / 100, 1.3 * max(H, 128) / 100), dpi=100, frameon=False, squeeze=False)
+        axs = axs[0]
+        axs[0].set_title("%s\nOriginal image" % idents[i], fontsize=10)
+        axs[0].imshow(imgs[i], cmap="gray")
+        for k, c in enumerate(classes):
+            m = cams[i, k]
+            m = (m - m.min()) / (m.max() - m.min() + 1e-5)
+            axs[k + 1].set_title("%s\nlabel %g, prob. %.4f" % (attr_names[c], float(labels[i][c]), probs[i][c]), fontsize=10)
+            axs[k + 1].imshow(imgs[i], cmap="gray")
+            axs[k + 1].imshow(m, cmap="jet", alpha=0.5, extent=(-0.5, W - 0.5, H - 0.5, -0.5), interpolation="bilinear")
+        for ax in axs:
+            ax.axis("off")
+        path = os.path.join(out_dir, "vis", "classcam_%s_step_%d.png" % (str(idents[i]).replace("/", "_").replace(" ", "_"), step))
+        plt.savefig(path, dpi=100)
+        plt.close(fig)
+        written.append(path)
+    return written

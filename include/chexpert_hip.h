@@ -619,6 +619,27 @@ int cx_gradcam_map(const void* x, const float* scale, const float* shift, const 
                    int ldx, int inner_relu, void* stream);
 int cx_cam_norm_upsample(const float* cam, float* out, int B, int h, int w, int H, int W, void* stream);
 
+/* Class-specific maps at the tensor the network pools globally, A = act(x*scale + shift), for K classes in one pass over x:
+ *   cam[b][k][p] = post((1/HW) * sum_f w[cls(b,k)][f] * A[b][p][f]),   post = relu when `relu` else the identity.
+ * With the final Linear y = bias + W mean_p A this is Grad-CAM taken at A (alpha[c][f] = mean_p dy_c/dA[f][p] = W[c][f]/HW exactly, no
+ * backward pass), and sum_p of the signed map (relu = 0) is y[b][c] - bias[c].
+ *   x      (B, HW, C) NHWC, pixel pitch ldx >= C elements, bf16 (the _f32 twin: fp32); C % 8 == 0, ldx % 8 == 0, C <= 4096
+ *   scale / shift   fp32 [C], or both NULL for the identity;   act: CX_CAM_ACT_*
+ *   w      fp32 (n_classes, C), 16-byte aligned, row pitch ldw >= C, ldw % 4 == 0
+ *   cls    NULL: class k of the map is row k of w and K == n_classes; else int32 (B, K) on the device, the row of w for map (b, k)
+ *          (one class list repeated for every image, or one class per image with K = 1).  The library cannot range-check device
+ *          memory: an entry outside [0, n_classes) is CLAMPED into the range inside the kernel (callers that hold the indices on the
+ *          host check them there).
+ *   cam    fp32 (B, K, HW)
+ * x is read once whatever K is.  fp32 sums in a fixed order, one writer per element, no atomics: bit-reproducible, and a class gives
+ * the same bits wherever it stands in cls.  CX_ESHAPE ("unsupported shape") before anything is launched for NULL x / w / cam, K < 1,
+ * C % 8, C > 4096, a bad pitch, or cls == NULL with K != n_classes.  Additive entry points of ABI 10 (no struct changed).        */
+enum { CX_CAM_ACT_NONE = 0, CX_CAM_ACT_RELU = 1, CX_CAM_ACT_SWISH = 2 };
+int cx_class_cam(const void* x, const float* scale, const float* shift, const float* w, const int* cls, float* cam, int B, int HW, int C,
+                 int ldx, int n_classes, int ldw, int K, int act, int relu, void* stream);
+int cx_class_cam_f32(const void* x, const float* scale, const float* shift, const float* w, const int* cls, float* cam, int B, int HW,
+                     int C, int ldx, int n_classes, int ldw, int K, int act, int relu, void* stream);
+
 /* stat_rows (cx_bnrelu_maxpool_fwd / _bwd, cx_gap_relu_bn_bwd, cx_unpool2_mask, cx_relu_bwd_stats): 0 = the statistics are added to the single
  * copy S1 / S2 [C] with atomics; > 0 = deterministic rows: the launch uses at most stat_rows workgroups (cx_gap_relu_bn_bwd: one row
  * per image, B <= stat_rows) and plain-stores row r at S[r*C + c]; cx_last_stat_rows() gives the row count for the consumer.   */
