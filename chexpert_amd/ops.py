@@ -951,10 +951,10 @@ def mul_f32(a, b, out):
 
 
 def linear_fwd(x, w, bias, y):
-    """cx_linear_fwd: y (B,N) = x (B,C) W^T + bias, all fp32."""
+    """cx_linear_fwd: y (B,N) = x (B,C) W^T + bias, all fp32 (bias None: no bias)."""
     require_cuda(x, w, bias, y)
     (B, Cc), N = x.shape, y.shape[1]
-    assert y.shape[0] == B and tuple(w.shape) == (N, Cc) and bias.numel() == N
+    assert y.shape[0] == B and tuple(w.shape) == (N, Cc) and (bias is None or bias.numel() == N)
     _f32(x, w, bias, y)
     check(lib().cx_linear_fwd(ptr(x), ptr(w), ptr(bias), ptr(y), B, Cc, N, stream_ptr()), "cx_linear_fwd")
 
