@@ -20,6 +20,11 @@
   --cam_classes [C ...] with --visualize: class-specific maps (gradcam.class_cam) of the 'vis' subset for these class indices (no value
                         or `all`: every class): vis/class_cam_lowres.npy (N, K, h, w) and one vis/classcam_<ident>_step_<N>.png per image
   --synthetic_uncertain F   that fraction of the synthetic training labels is uncertain (the policy above then applies)
+  --clip_grad_norm X    clip the gradient to global L2 norm X inside the fused optimiser step (needs --fused_optimizer, as the next three)
+  --skip_nonfinite      drop the update of a minibatch whose gradient norm is inf or NaN (it still counts for the schedule)
+  --ema_decay D         exponential moving average of the weights, written by the optimiser kernel; evaluation and the checkpoint's
+                        `ema_state_dict` use it.  --no_ema_warmup: constant decay instead of min(D, (1 + step) / (10 + step))
+  --use_ema             --evaluate_single_model / --evaluate_ensemble / --visualize load `ema_state_dict` from the checkpoint
 
 Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N chexpert.py --train ...`; every rank holds a
 replica and a shard of each minibatch stream (per-rank BatchNorm statistics, averaged gradients: DDP semantics), the
@@ -86,6 +91,11 @@ def build_parser():
     p.add_argument("--synthetic_uncertain", type=float, default=0.0, metavar="F", help="fraction of the synthetic training labels marked uncertain")
     p.add_argument("--cam_classes", nargs="*", default=None, metavar="CLASS",
                    help="with --visualize: class-specific maps (gradcam.class_cam) of these class indices; no value or `all` = every class")
+    p.add_argument("--clip_grad_norm", type=float, default=None, metavar="X", help="global-norm gradient clipping in the fused optimiser step")
+    p.add_argument("--skip_nonfinite", action="store_true", help="drop the update of a minibatch whose gradient is not finite")
+    p.add_argument("--ema_decay", type=float, default=None, metavar="D", help="exponential moving average of the weights, decay D in (0, 1)")
+    p.add_argument("--no_ema_warmup", action="store_true", help="constant EMA decay (default: min(D, (1 + step) / (10 + step)))")
+    p.add_argument("--use_ema", action="store_true", help="evaluate / visualise with the checkpoint's ema_state_dict")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -171,19 +181,51 @@ def resolve_cam_classes(spec, n_classes):
     return classes
 
 
+def optimizer_options(args):
+    """--clip_grad_norm / --skip_nonfinite / --ema_decay / --no_ema_warmup as keyword arguments of the fused optimisers ({}: all off)."""
+    clip, skip, ema = getattr(args, "clip_grad_norm", None), getattr(args, "skip_nonfinite", False), getattr(args, "ema_decay", None)
+    no_warm, use_ema = getattr(args, "no_ema_warmup", False), getattr(args, "use_ema", False)
+    for flag, on in (("--clip_grad_norm", clip is not None), ("--skip_nonfinite", skip), ("--ema_decay", ema is not None),
+                     ("--no_ema_warmup", no_warm)):
+        if on and not args.fused_optimizer:
+            raise ValueError("%s works inside the fused optimiser step: pass --fused_optimizer with it" % flag)
+    if clip is not None and not clip > 0:
+        raise ValueError("--clip_grad_norm takes a norm > 0 (got %r)" % clip)
+    if ema is not None and not 0.0 < ema < 1.0:
+        raise ValueError("--ema_decay takes a decay in (0, 1) (got %r)" % ema)
+    if no_warm and ema is None:
+        raise ValueError("--no_ema_warmup changes the decay of --ema_decay: pass --ema_decay D with it")
+    if use_ema and args.train:
+        raise ValueError("--use_ema picks the weights of --evaluate_single_model / --evaluate_ensemble / --visualize; training "
+                         "evaluates with the average whenever --ema_decay is given")
+    if clip is None and not skip and ema is None:
+        return {}
+    return {"max_grad_norm": clip, "skip_nonfinite": bool(skip), "ema_decay": ema, "ema_warmup": not no_warm}
+
+
+def model_weights(ck, args, path=""):
+    """The state dict a checkpoint is read for: the live weights, or with --use_ema (outside training) their average."""
+    if getattr(args, "use_ema", False) and not args.train:
+        if "ema_state_dict" not in ck:
+            raise RuntimeError("--use_ema: checkpoint %s holds no ema_state_dict (it was not trained with --ema_decay)" % path)
+        return ck["ema_state_dict"]
+    return ck["state_dict"]
+
+
 def make_model(args, device):
     """Model zoo and optimiser wiring of chexpert.py:461-502."""
     from . import optim as O
     from .models import densenet121
     name = args.model
     fused = args.fused_optimizer
+    ex = optimizer_options(args)
     sched = None
     if name == "densenet121":
         model = densenet121(pretrained=args.pretrained)
         model.classifier = nn.Linear(model.classifier.in_features, args.n_classes)
         nn.init.constant_(model.classifier.bias, 0)
         model = model.storage_dtype(args.dtype).to(device)
-        opt = O.FusedAdam(model, lr=args.lr) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)
+        opt = O.FusedAdam(model, lr=args.lr, **ex) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)
         return model, opt, None
     if name in ("aadensenet121", "densenet121_attn_aug"):      # chexpert.py:474-480 (README row name accepted too)
         from .models import DenseNet
@@ -192,7 +234,7 @@ def make_model(args, device):
                          attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
         model = model.storage_dtype(args.dtype).to(device)
         if fused:
-            return model, O.FusedSGDNesterov(model, lr=args.lr), "fused"
+            return model, O.FusedSGDNesterov(model, lr=args.lr, **ex), "fused"
         opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, nesterov=True)
         return model, opt, torch.optim.lr_scheduler.MultiStepLR(opt, [40000, 60000])
     if name == "resnet152":                                   # chexpert.py:481-486
@@ -200,12 +242,12 @@ def make_model(args, device):
         model = resnet152(pretrained=args.pretrained)
         model.fc = nn.Linear(model.fc.in_features, args.n_classes)
         model = model.storage_dtype(args.dtype).to(device)
-        return model, (O.FusedAdam(model, lr=args.lr) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
+        return model, (O.FusedAdam(model, lr=args.lr, **ex) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
     if "efficientnet" in name:                                # chexpert.py:496-500
         from .models import construct_model
         model = construct_model(name, n_classes=args.n_classes).storage_dtype(args.dtype).to(device)
         if fused:
-            return model, O.FusedRMSprop(model, lr=args.lr, decay=args.lr_decay_factor), "fused"
+            return model, O.FusedRMSprop(model, lr=args.lr, decay=args.lr_decay_factor, **ex), "fused"
         opt = torch.optim.RMSprop(model.parameters(), lr=args.lr, momentum=0.9, eps=0.001)
         return model, opt, torch.optim.lr_scheduler.ExponentialLR(opt, args.lr_decay_factor)
     if name == "aaresnet152":                                 # chexpert.py:486-494
@@ -214,7 +256,7 @@ def make_model(args, device):
         model = ResNet(Bottleneck, [3, 8, 36, 3], num_classes=args.n_classes,
                        attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
         model = model.storage_dtype(args.dtype).to(device)
-        return model, (O.FusedAdam(model, lr=args.lr) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
+        return model, (O.FusedAdam(model, lr=args.lr, **ex) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
     raise RuntimeError("Model architecture not supported.")
 
 
@@ -276,7 +318,7 @@ def save_checkpoint(ckpt, optim_state, sched_state, args, max_records=10):
 def restore(args, model, optimizer, scheduler, device):
     """chexpert.py:504-518: model weights + step from the file; when training also `optim_<name>` / `sched_<name>` beside it."""
     ck = torch.load(args.restore, map_location=device)
-    model.load_state_dict(ck["state_dict"])
+    model.load_state_dict(model_weights(ck, args, args.restore))
     args.step = ck["global_step"]
     if args.train:
         d, b = os.path.dirname(args.restore), os.path.basename(args.restore)
@@ -317,6 +359,7 @@ def main(argv=None):
         raise ValueError("--synthetic_uncertain takes a fraction in [0, 1] (got %r)" % args.synthetic_uncertain)
     if args.synthetic_uncertain > 0 and not args.synthetic:
         raise ValueError("--synthetic_uncertain marks labels of the synthetic set: pass --synthetic N with it")
+    ex = optimizer_options(args)
     cam_classes = resolve_cam_classes(getattr(args, "cam_classes", None), args.n_classes)
     if cam_classes is not None and not args.visualize:
         raise ValueError("--cam_classes draws class maps over the 'vis' subset: pass --visualize with it")
@@ -385,8 +428,15 @@ def main(argv=None):
         print("Loaded %s (number of parameters: %s; weights trained to step %d)" % (
             model._get_name(), format(sum(p.numel() for p in model.parameters()), ","), args.step))
 
+    def averaged():
+        """The weights an evaluation during training sees: the EMA where --ema_decay keeps one (and a step has bound it)."""
+        import contextlib
+        on = ex.get("ema_decay") is not None and args.train and model._eng().flat is not None
+        return optimizer.ema_weights() if on else contextlib.nullcontext()
+
     def run_eval(tag):
-        res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world))
+        with averaged():
+            res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world))
         if rank == 0:
             print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
             json.dump(res, open(os.path.join(args.output_dir, tag + ".json"), "w"), indent=4)
@@ -450,16 +500,27 @@ def main(argv=None):
                     if scheduler and args.step >= args.lr_warmup_steps:
                         scheduler.step()
                 if args.step % args.log_interval == 0 and rank == 0:
-                    print(json.dumps({"step": args.step, "train_loss": round(loss.item(), 5)}), flush=True)
+                    line = {"step": args.step, "train_loss": round(loss.item(), 5)}
+                    if ex.get("max_grad_norm") is not None or ex.get("skip_nonfinite"):      # (loss.item() has synchronised already)
+                        line["grad_norm"] = round(optimizer.grad_norm(), 5)
+                        if optimizer.skipped_steps():
+                            line["skipped"] = optimizer.skipped_steps()
+                    print(json.dumps(line), flush=True)
                 if args.step % args.eval_interval == 0:
-                    res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world))
+                    ema_sd = None
+                    with averaged():
+                        res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world))
+                        if ex.get("ema_decay") is not None and rank == 0:
+                            ema_sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
                     if rank == 0:
                         if gstep is not None:
                             optimizer.sync_from_device()
                         sched_state = scheduler.state_dict() if scheduler is not None and scheduler != "fused" else None
-                        save_checkpoint({"global_step": args.step, "eval_loss": float(np.sum(list(res["loss"].values()))),
-                                         "avg_auc": M.mean_auc(res), "state_dict": model.state_dict()},
-                                        optimizer.state_dict(), sched_state, args)
+                        ckpt = {"global_step": args.step, "eval_loss": float(np.sum(list(res["loss"].values()))),
+                                "avg_auc": M.mean_auc(res), "state_dict": model.state_dict()}
+                        if ema_sd is not None:        # beside the live weights, which restore continues from
+                            ckpt["ema_state_dict"] = ema_sd
+                        save_checkpoint(ckpt, optimizer.state_dict(), sched_state, args)
                     model.train()
             torch.cuda.synchronize()
             if rank == 0:        # input pipeline + step, end to end (the figure to hold against bench.py's device-resident rate)
@@ -474,7 +535,7 @@ def main(argv=None):
         assert args.restore and os.path.isdir(args.restore), "Restore argument must be directory with saved checkpoints"
         outs, losses = [], []
         for c in sorted(f for f in os.listdir(args.restore) if f.startswith("checkpoint") and f.endswith(".pt")):
-            model.load_state_dict(torch.load(os.path.join(args.restore, c), map_location=device)["state_dict"])
+            model.load_state_dict(model_weights(torch.load(os.path.join(args.restore, c), map_location=device), args, c))
             o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world)
             outs.append(o)
             losses.append(l)

@@ -675,6 +675,72 @@ def optim_tick(hyper):
     check(lib().cx_optim_tick(ptr(hyper), stream_ptr()), "cx_optim_tick")
 
 
+# ---- global-norm clipping, non-finite skip and weight EMA inside the optimiser launch (csrc/optim_ex.hip)
+def grad_norm_partials(n):
+    """Floats of workspace `grad_norm` needs for n gradients (the grid of its first launch: a function of n alone)."""
+    return lib().cx_grad_norm_partials(n)
+
+
+def grad_norm(g, workspace, clip, grad_scale=1.0, max_norm=0.0, skip_nonfinite=False):
+    """clip = float[4] {norm of grad_scale * g, clip coefficient, nonfinite, skipped steps} on the device; two launches, no atomics,
+    the same bits on every call.  max_norm <= 0: coefficient 1.  `clip[3]` is a running count: zero `clip` once."""
+    require_cuda(g, workspace, clip)
+    _f32(g, workspace)
+    _f32(clip, n=4)
+    check(lib().cx_grad_norm(ptr(g), g.numel(), grad_scale, max_norm, int(bool(skip_nonfinite)), ptr(workspace), workspace.numel(),
+                             ptr(clip), stream_ptr()), "cx_grad_norm")
+
+
+def _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, *bufs):
+    n = p.numel()
+    require_cuda(p, clip, ema, *bufs)
+    _f32(p, ema, *bufs, n=n)
+    _f32(clip, n=4)
+    return ptr(clip), ptr(ema), (0.0 if ema is None else float(ema_decay)), int(bool(ema_warmup)), int(bool(skip_nonfinite)), stream_ptr()
+
+
+def adam_step_ex(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
+                 ema_warmup=True, skip_nonfinite=False):
+    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, m, v)
+    check(lib().cx_adam_step_ex(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                                *tail), "cx_adam_step_ex")
+
+
+def sgd_nesterov_step_ex(p, g, buf, lr, momentum, weight_decay, first_step, step, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
+                         ema_warmup=True, skip_nonfinite=False):
+    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, buf)
+    check(lib().cx_sgd_nesterov_step_ex(ptr(p), ptr(g), ptr(buf), p.numel(), lr, momentum, weight_decay, int(first_step), step,
+                                        grad_scale, *tail), "cx_sgd_nesterov_step_ex")
+
+
+def rmsprop_step_ex(p, g, sq, buf, lr, alpha, eps, momentum, weight_decay, step, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
+                    ema_warmup=True, skip_nonfinite=False):
+    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, sq, buf)
+    check(lib().cx_rmsprop_step_ex(ptr(p), ptr(g), ptr(sq), ptr(buf), p.numel(), lr, alpha, eps, momentum, weight_decay, step,
+                                   grad_scale, *tail), "cx_rmsprop_step_ex")
+
+
+def adam_step_dev_ex(p, g, m, v, hyper, beta1, beta2, eps, weight_decay, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
+                     ema_warmup=True, skip_nonfinite=False):
+    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, m, v)
+    check(lib().cx_adam_step_dev_ex(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(hyper), beta1, beta2, eps, weight_decay,
+                                    grad_scale, *tail), "cx_adam_step_dev_ex")
+
+
+def sgd_nesterov_step_dev_ex(p, g, buf, hyper, momentum, weight_decay, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
+                             ema_warmup=True, skip_nonfinite=False):
+    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, buf)
+    check(lib().cx_sgd_nesterov_step_dev_ex(ptr(p), ptr(g), ptr(buf), p.numel(), ptr(hyper), momentum, weight_decay, grad_scale,
+                                            *tail), "cx_sgd_nesterov_step_dev_ex")
+
+
+def rmsprop_step_dev_ex(p, g, sq, buf, hyper, alpha, eps, momentum, weight_decay, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
+                        ema_warmup=True, skip_nonfinite=False):
+    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, sq, buf)
+    check(lib().cx_rmsprop_step_dev_ex(ptr(p), ptr(g), ptr(sq), ptr(buf), p.numel(), ptr(hyper), alpha, eps, momentum, weight_decay,
+                                       grad_scale, *tail), "cx_rmsprop_step_dev_ex")
+
+
 def bf16_to_f32_nchw(x, out=None):
     B, H, W, Cc, ldx = _nhwc(x)
     if out is None:

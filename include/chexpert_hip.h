@@ -455,6 +455,40 @@ int cx_rmsprop_step_dev(float* p, const float* g, float* sq, float* buf, size_t 
                         float momentum, float weight_decay, float grad_scale, void* stream);
 int cx_optim_tick(float* hyper, void* stream);
 
+/* Global-norm gradient clipping, non-finite skip and weight EMA inside the optimiser launch (optim_ex.hip).
+ * cx_grad_norm: two launches, no atomics.  Launch 1: cx_grad_norm_partials(n) workgroups (a function of n alone), each sums
+ * (grad_scale * g)^2 over a fixed contiguous range (16-byte loads, n % 4 scalar tail) and plain-stores one partial to `workspace`
+ * (>= cx_grad_norm_partials(n) floats).  Launch 2: one workgroup sums the partials in a fixed order and writes
+ * clip = float[4] {norm, coef, nonfinite, skipped}: norm = sqrt(sum); coef = min(1, max_norm / (norm + 1e-6))
+ * (torch.nn.utils.clip_grad_norm_), 1 when max_norm <= 0; nonfinite = 1 when the sum is inf or NaN; skipped += 1 when nonfinite and
+ * skip_nonfinite (the caller zeroes clip once).  g 16-byte aligned (CX_EALIGN), any n; n == 0: norm 0, coef 1.                       */
+int cx_grad_norm_partials(size_t n);
+int cx_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, int skip_nonfinite, float* workspace,
+                 size_t workspace_floats, float* clip, void* stream);
+/* The six steps above with: the gradient that enters the update = grad_scale * clip[1] * g (clip null: grad_scale * g); nothing
+ * written (p, states, ema keep their bits) when skip_nonfinite and clip[2] != 0; ema (null: none) = d * ema + (1 - d) * p_new in the
+ * same pass, d = ema_decay or, with ema_warmup, min(ema_decay, (1 + t) / (10 + t)), t = the 1-based number of this step (`step`,
+ * or hyper[1] + 1).  clip and ema null: the call is forwarded to the plain entry point (same kernel, same bits).  cx_optim_tick is unchanged: a skipped step is still a
+ * minibatch for the schedule and for Adam's bias correction.                                                                      */
+int cx_adam_step_ex(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, int step, float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup,
+                    int skip_nonfinite, void* stream);
+int cx_sgd_nesterov_step_ex(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay,
+                            int first_step, int step, float grad_scale, const float* clip, float* ema, float ema_decay,
+                            int ema_warmup, int skip_nonfinite, void* stream);
+int cx_rmsprop_step_ex(float* p, const float* g, float* sq, float* buf, size_t n, float lr, float alpha, float eps, float momentum,
+                       float weight_decay, int step, float grad_scale, const float* clip, float* ema, float ema_decay,
+                       int ema_warmup, int skip_nonfinite, void* stream);
+int cx_adam_step_dev_ex(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float beta1, float beta2,
+                        float eps, float weight_decay, float grad_scale, const float* clip, float* ema, float ema_decay,
+                        int ema_warmup, int skip_nonfinite, void* stream);
+int cx_sgd_nesterov_step_dev_ex(float* p, const float* g, float* buf, size_t n, const float* hyper, float momentum,
+                                float weight_decay, float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup,
+                                int skip_nonfinite, void* stream);
+int cx_rmsprop_step_dev_ex(float* p, const float* g, float* sq, float* buf, size_t n, const float* hyper, float alpha, float eps,
+                           float momentum, float weight_decay, float grad_scale, const float* clip, float* ema, float ema_decay,
+                           int ema_warmup, int skip_nonfinite, void* stream);
+
 /* ---- attention-augmented convolution (AAConv2d, models/attn_aug_conv.py:19-100) --------------------
  * qkv: bf16 (B, H*W, ldq) output of in_proj_qkv (channels [q dk | k dk | v dv], head-major), ldq % 4 == 0.
  * Head widths dkh = dk/nh and dvh = dv/nh of 1 .. 64 with dv <= 104: dkh = 20 with dvh <= 13 runs the row / generic kernels
