@@ -14,6 +14,33 @@ Convention (kernel, `affine_matrices` and `affine_reference` alike).  mat[b] = (
     p(r, c) = x[b][r][c] inside the image, else `fill`
     top = p(v0,u0)*(1-fu) + p(v0,u0+1)*fu ;  bot likewise on row v0+1
     y[b][i][j] = uint8(floor(top*(1-fv) + bot*fv + 0.5))
+
+Contrast equalisation (CLAHE: `cx_u8_clahe_lut` + `cx_u8_clahe_apply`, chexpert_amd/csrc/clahe.hip; `ops.u8_clahe`) lives here too:
+deterministic preprocessing rather than augmentation, so it runs in every mode, as the first step on the uint8 batch, before the
+warp.  Its structure is OpenCV's `createCLAHE(clipLimit, tileGridSize)`, but it is NOT bit-equal to OpenCV, which rounds the tables
+and the interpolation in float and anchors on pixel indices: the definition below is integer arithmetic throughout (kernel and
+`clahe_reference` agree bit for bit), and tables sit at tile centres with pixel centres at half-integers.
+
+x: uint8 (B, H, W) or (B, 1, H, W); grid (GY, GX), each 1..16, dividing (H, W); tile th = H / GY, tw = W / GX, area = th * tw; clip
+limit c >= 0 (`//` is floor division):
+
+    L = 0 if c == 0 else min(area, max(1, floor(c * area / 256)))          clip count (`clahe_clip_count`); 0 = no clipping
+
+    table of tile (b, gy, gx), 256 bytes:
+      hist[v] = number of pixels of the tile with value v
+      if L > 0:  excess = sum(max(hist[v] - L, 0));  hist[v] = min(hist[v], L);  q, r = divmod(excess, 256)
+                 hist[v] += q for every v
+                 if r > 0: step = max(1, 256 // r); for v = 0, step, 2*step, ... < 256, while r > 0: hist[v] += 1, r -= 1
+      cdf[v] = hist[0] + ... + hist[v];   lut[v] = (cdf[v] * 255 + area // 2) // area
+
+    output pixel (i, j) with value v = x[b][i][j]:
+      ay = 2*i + 1 - th;  gy0 = ay // (2*th)  (-1 in the top half tile);  wy = ay - gy0 * 2*th  (in [0, 2*th));  gy1 = gy0 + 1
+      then gy0 and gy1 are clamped to [0, GY-1];  ax, gx0, wx, gx1 likewise with j, tw, GX
+      num = (2*th - wy) * ((2*tw - wx) * lut[gy0][gx0][v] + wx * lut[gy0][gx1][v])
+          +       wy    * ((2*tw - wx) * lut[gy1][gx0][v] + wx * lut[gy1][gx1][v])
+      y[b][i][j] = (num + 2*th*tw) // (4*th*tw)
+
+GY = GX = 1 with c = 0 is plain global histogram equalisation.
 """
 import math
 
@@ -103,3 +130,114 @@ class RandomAffine:
         B, H, W = x_u8.shape[0], x_u8.shape[-2], x_u8.shape[-1]
         mat = affine_matrices(step_seed(step, self.rank), B, H, W, **self.ranges)
         return ops.u8_affine(x_u8, mat.to(self.device), self.fill)
+
+
+def clahe_clip_count(clip_limit, th, tw):
+    """The integer clip level per histogram bin of a th x tw tile for clip limit c (a multiple of the mean bin height area / 256, as
+    OpenCV's clipLimit): 0 for c == 0 (no clipping), else min(area, max(1, floor(c * area / 256)))."""
+    c, area = float(clip_limit), int(th) * int(tw)
+    if not (c >= 0.0 and math.isfinite(c)):
+        raise ValueError("the CLAHE clip limit is a finite number >= 0 (got %r)" % (clip_limit,))
+    if c == 0.0:
+        return 0
+    return min(area, max(1, int(math.floor(c * area / 256.0))))
+
+
+def check_clahe_grid(grid, H, W):
+    """(GY, GX) as ints if the grid is one the kernels take for an H x W image, else ValueError with the reason."""
+    if len(grid) != 2:
+        raise ValueError("the CLAHE grid is two numbers GY GX (got %r)" % (grid,))
+    GY, GX = int(grid[0]), int(grid[1])
+    if not (1 <= GY <= 16 and 1 <= GX <= 16):
+        raise ValueError("the CLAHE grid takes 1..16 tiles per axis (got %d x %d)" % (GY, GX))
+    if H % GY or W % GX:
+        raise ValueError("the CLAHE grid %d x %d does not divide the %d x %d image" % (GY, GX, H, W))
+    if W % 4 or H > 1024 or W > 1024:
+        raise ValueError("CLAHE takes images up to 1024 x 1024 whose width is a multiple of 4 (got %d x %d)" % (H, W))
+    return GY, GX
+
+
+def clahe_tables_reference(img, grid, clip_count):
+    """The tables of the definition in the module docstring in numpy integers on the CPU, and the redistribution residual r of
+    every tile: (lut (B, GY, GX, 256) uint8, r (B, GY, GX) int64; r = 0 where nothing is clipped)."""
+    import numpy as np
+    x = np.asarray(img.cpu() if isinstance(img, torch.Tensor) else img)
+    H, W = x.shape[-2], x.shape[-1]
+    GY, GX = check_clahe_grid(grid, H, W)
+    x = x.reshape(-1, H, W)
+    B, th, tw = x.shape[0], H // GY, W // GX
+    area, L = th * tw, int(clip_count)
+    if not 0 <= L <= area:
+        raise ValueError("clip count %d outside [0, %d]" % (L, area))
+    tiles = x.reshape(B, GY, th, GX, tw).transpose(0, 1, 3, 2, 4).reshape(B * GY * GX, area)
+    lut = np.empty((B * GY * GX, 256), np.uint8)
+    res = np.zeros(B * GY * GX, np.int64)
+    for n, tile in enumerate(tiles):
+        hist = np.bincount(tile, minlength=256).astype(np.int64)
+        if L > 0:
+            excess = int(np.maximum(hist - L, 0).sum())
+            hist = np.minimum(hist, L)
+            q, r = divmod(excess, 256)
+            hist += q
+            res[n] = r
+            if r > 0:
+                step = max(1, 256 // r)
+                for v in range(0, 256, step):
+                    if r == 0:
+                        break
+                    hist[v] += 1
+                    r -= 1
+        lut[n] = (np.cumsum(hist) * 255 + area // 2) // area
+    return torch.from_numpy(lut.reshape(B, GY, GX, 256)), torch.from_numpy(res.reshape(B, GY, GX))
+
+
+def clahe_apply_reference(img, lut):
+    """The interpolation of the definition in the module docstring in numpy integers on the CPU: img uint8 (B,1,H,W) / (B,H,W),
+    lut (B, GY, GX, 256) uint8; returns img's shape, uint8."""
+    import numpy as np
+    x = np.asarray(img.cpu() if isinstance(img, torch.Tensor) else img)
+    t = np.asarray(lut.cpu() if isinstance(lut, torch.Tensor) else lut).astype(np.int64)
+    shape, H, W = x.shape, x.shape[-2], x.shape[-1]
+    x = x.reshape(-1, H, W)
+    B, GY, GX = t.shape[0], t.shape[1], t.shape[2]
+    th, tw = H // GY, W // GX
+
+    def axis(n, t_, G):
+        a = 2 * np.arange(n, dtype=np.int64) + 1 - t_
+        g0 = a // (2 * t_)                                   # floor division: -1 in the first half tile
+        w = a - g0 * 2 * t_
+        return np.clip(g0, 0, G - 1), np.clip(g0 + 1, 0, G - 1), w
+
+    gy0, gy1, wy = (v.reshape(1, H, 1) for v in axis(H, th, GY))
+    gx0, gx1, wx = (v.reshape(1, 1, W) for v in axis(W, tw, GX))
+    b = np.arange(B).reshape(B, 1, 1)
+    v = x.astype(np.int64)
+    num = (2 * th - wy) * ((2 * tw - wx) * t[b, gy0, gx0, v] + wx * t[b, gy0, gx1, v]) \
+        + wy * ((2 * tw - wx) * t[b, gy1, gx0, v] + wx * t[b, gy1, gx1, v])
+    assert int(num.max()) < 2 ** 31
+    return torch.from_numpy(((num + 2 * th * tw) // (4 * th * tw)).astype(np.uint8).reshape(shape))
+
+
+def clahe_reference(img, grid=(8, 8), clip_limit=2.0, return_lut=False):
+    """The definition in the module docstring in numpy integers on the CPU: img uint8 (B,1,H,W) / (B,H,W); returns the same shape,
+    uint8, and with `return_lut` the (B, GY, GX, 256) uint8 tables too.  Like OpenCV's createCLAHE in structure, not bit-equal to it
+    (integer rounding, tile-centre / pixel-centre anchoring).  Used by the tests and by nothing else."""
+    H, W = img.shape[-2], img.shape[-1]
+    GY, GX = check_clahe_grid(grid, H, W)
+    lut, _ = clahe_tables_reference(img, (GY, GX), clahe_clip_count(clip_limit, H // GY, W // GX))
+    out = clahe_apply_reference(img, lut)
+    return (out, lut) if return_lut else out
+
+
+class Clahe:
+    """The --clahe step: equalises a uint8 batch on the GPU (ops.u8_clahe: two launches).  No random draw: every mode runs it."""
+
+    def __init__(self, grid=(8, 8), clip_limit=2.0):
+        self.grid, self.clip_limit = (int(grid[0]), int(grid[1])), float(clip_limit)
+        clahe_clip_count(self.clip_limit, 1, 1)              # (validates the limit)
+
+    def __call__(self, x_u8, out=None):
+        from . import ops
+        if x_u8.dtype != torch.uint8:
+            raise RuntimeError("CLAHE equalises the decoded uint8 images (got %s)" % x_u8.dtype)
+        return ops.u8_clahe(x_u8, self.grid, self.clip_limit, out)

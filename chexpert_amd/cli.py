@@ -13,6 +13,11 @@
   --affine              random rotation / translation / scale / shear of the uint8 image on the GPU (training only; it runs before
                         --jitter: geometric first, photometric second), ranges as torchvision's RandomAffine:
                         --affine_degrees 10, --affine_translate 0.05, --affine_scale 0.9 1.1, --affine_shear 0
+  --clahe               contrast-limited adaptive histogram equalisation of the uint8 image on the GPU (chexpert_amd/augment.py):
+                        deterministic preprocessing, so it runs in EVERY mode (training, its evaluations, --evaluate_single_model,
+                        --evaluate_ensemble, --visualize), as the first step on the uint8 batch, before --affine and --jitter;
+                        --clahe_grid 8 8 tiles (each 1..16, dividing the crop size), --clahe_clip 2.0 (0: no clipping).  It sits behind
+                        the loader: --cache_decoded does not depend on these settings
   --uncertain POLICY    what an uncertain (-1) training label becomes: ones (the reference's U-Ones, default), zeros, ignore (it stays
                         -1 and the loss skips it), ones_lsr / zeros_lsr (label smoothing: uniform in [0.55, 0.85] / [0, 0.3])
   --pos_weight W        `auto` or n_classes floats: BCEWithLogitsLoss's pos_weight, inside the fused step too; auto = per class
@@ -86,6 +91,9 @@ def build_parser():
     p.add_argument("--affine_translate", type=float, default=0.05, help="translation uniform in +-fraction of the image size, per axis")
     p.add_argument("--affine_scale", type=float, nargs=2, default=[0.9, 1.1], metavar=("LO", "HI"), help="scale uniform in [LO, HI]")
     p.add_argument("--affine_shear", type=float, default=0.0, help="shear along x uniform in +-degrees")
+    p.add_argument("--clahe", action="store_true", help="CLAHE contrast equalisation of the uint8 image (GPU, every mode)")
+    p.add_argument("--clahe_grid", type=int, nargs=2, default=[8, 8], metavar=("GY", "GX"), help="tiles per axis, each 1..16, dividing the crop size")
+    p.add_argument("--clahe_clip", type=float, default=2.0, metavar="C", help="clip limit in multiples of the mean bin height (0: no clipping)")
     p.add_argument("--uncertain", default="ones", choices=list(UNCERTAIN_POLICIES), help="policy for the uncertain (-1) training labels")
     p.add_argument("--pos_weight", nargs="+", default=None, metavar="W", help="`auto` or n_classes floats: positive-term weights of the loss")
     p.add_argument("--synthetic_uncertain", type=float, default=0.0, metavar="F", help="fraction of the synthetic training labels marked uncertain")
@@ -132,6 +140,32 @@ def batches(ds, indices, batch_size, drop_last):
             return
         items = [ds[i] for i in idx]
         yield torch.stack([it[0] for it in items]), torch.stack([it[1] for it in items]), torch.tensor(idx)
+
+
+def parse_args(argv=None):
+    """The command line, --load_config applied, and what can be refused before anything is built refused here (parser.error): a
+    --clahe grid that does not divide the crop size is an argument error, not a kernel status."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.load_config:
+        args.__dict__.update(json.load(open(args.load_config)))
+    if getattr(args, "clahe", False):
+        from .augment import check_clahe_grid, clahe_clip_count
+        size = args.resize or 320
+        try:
+            check_clahe_grid(args.clahe_grid, size, size)
+            clahe_clip_count(args.clahe_clip, 1, 1)
+        except ValueError as e:
+            parser.error("--clahe: %s" % e)
+    return args
+
+
+def make_clahe(args):
+    """The equalisation step (chexpert_amd/augment.py), or None without --clahe: then nothing is launched or allocated for it."""
+    if not getattr(args, "clahe", False):
+        return None
+    from .augment import Clahe
+    return Clahe(args.clahe_grid, args.clahe_clip)
 
 
 def make_affine(args, rank, device):
@@ -261,8 +295,9 @@ def make_model(args, device):
 
 
 @torch.no_grad()
-def evaluate(model, ds, indices, batch_size, device):
-    """chexpert.py:198-211 on this rank's slice of the validation set; returns logits, targets, per-element losses, indices."""
+def evaluate(model, ds, indices, batch_size, device, pre=None):
+    """chexpert.py:198-211 on this rank's slice of the validation set; returns logits, targets, per-element losses, indices.
+    `pre`: the deterministic preprocessing of the uint8 batch on the GPU (--clahe), or None."""
     model.eval()
     outs, tgts, losses, ids = [], [], [], []
     loss_fn = nn.BCEWithLogitsLoss(reduction="none")
@@ -270,7 +305,7 @@ def evaluate(model, ds, indices, batch_size, device):
         from .loss import MaskedBCE
         loss_fn = MaskedBCE().elementwise
     for x, t, idx in batches(ds, indices, batch_size, False):
-        o = model(x.to(device))
+        o = model(x.to(device) if pre is None else pre(x.to(device)))
         losses.append(loss_fn(o, t.to(device)))
         outs.append(o)
         tgts.append(t.to(device))
@@ -281,10 +316,10 @@ def evaluate(model, ds, indices, batch_size, device):
     return torch.cat(outs), torch.cat(tgts), torch.cat(losses), torch.cat(ids)
 
 
-def evaluate_sharded(model, ds, batch_size, device, rank, world):
+def evaluate_sharded(model, ds, batch_size, device, rank, world, pre=None):
     """Every rank forwards indices rank::world; the (N,5) logits / targets / losses are gathered and put back in dataset order."""
     idx = list(range(len(ds)))[rank::world]
-    o, t, l, i = evaluate(model, ds, idx, batch_size, device)
+    o, t, l, i = evaluate(model, ds, idx, batch_size, device, pre)
     o, t, l, i = (P.gather_rows(v) for v in (o, t, l, i))
     order = torch.argsort(i)
     return o[order].cpu(), t[order].cpu(), l[order].cpu()
@@ -352,9 +387,7 @@ def plot_roc(res, args, name):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    if args.load_config:
-        args.__dict__.update(json.load(open(args.load_config)))
+    args = parse_args(argv)
     if not 0.0 <= args.synthetic_uncertain <= 1.0:
         raise ValueError("--synthetic_uncertain takes a fraction in [0, 1] (got %r)" % args.synthetic_uncertain)
     if args.synthetic_uncertain > 0 and not args.synthetic:
@@ -428,6 +461,8 @@ def main(argv=None):
         print("Loaded %s (number of parameters: %s; weights trained to step %d)" % (
             model._get_name(), format(sum(p.numel() for p in model.parameters()), ","), args.step))
 
+    clahe = make_clahe(args)
+
     def averaged():
         """The weights an evaluation during training sees: the EMA where --ema_decay keeps one (and a step has bound it)."""
         import contextlib
@@ -436,7 +471,7 @@ def main(argv=None):
 
     def run_eval(tag):
         with averaged():
-            res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world))
+            res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe))
         if rank == 0:
             print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
             json.dump(res, open(os.path.join(args.output_dir, tag + ".json"), "w"), indent=4)
@@ -467,6 +502,8 @@ def main(argv=None):
             # partial minibatch runs as an eager step (the hipGraph is captured on the full batch's shapes)
             for x, t, _ in train_loader.batches(idx, drop_last=False):
                 args.step += 1
+                if clahe is not None:                       # deterministic preprocessing first, then the random steps
+                    x = clahe(x)
                 if affine is not None:                      # geometric first, photometric second
                     x = affine(x, args.step)
                 if args.jitter:
@@ -509,7 +546,7 @@ def main(argv=None):
                 if args.step % args.eval_interval == 0:
                     ema_sd = None
                     with averaged():
-                        res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world))
+                        res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe))
                         if ex.get("ema_decay") is not None and rank == 0:
                             ema_sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
                     if rank == 0:
@@ -536,7 +573,7 @@ def main(argv=None):
         outs, losses = [], []
         for c in sorted(f for f in os.listdir(args.restore) if f.startswith("checkpoint") and f.endswith(".pt")):
             model.load_state_dict(model_weights(torch.load(os.path.join(args.restore, c), map_location=device), args, c))
-            o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world)
+            o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe)
             outs.append(o)
             losses.append(l)
         res = M.compute_metrics(torch.stack(outs, 2).mean(2), tg, torch.stack(losses, 2).mean(2))   # mean of logits, chexpert.py:233
@@ -557,6 +594,9 @@ def main(argv=None):
         attn_layers = [m for m in model.modules() if type(m).__name__ == "AAConv2d"]
         for x, tg, idx in batches(valid_ds, flat, args.batch_size, False):
             xd = x.to(device)
+            if clahe is not None:                # the figures show what the network saw
+                xd = clahe(xd)
+                x = xd.cpu()
             with torch.no_grad():
                 scores.append(model(xd).float().cpu())
             masks.append(grad_cam(model, xd).float().cpu())

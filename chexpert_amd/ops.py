@@ -432,6 +432,47 @@ def u8_affine(x, mat, fill=0, out=None):
     return out
 
 
+def _u8_images(x):
+    assert x.dtype == torch.uint8 and x.is_contiguous() and x.dim() in (3, 4) and (x.dim() == 3 or x.shape[1] == 1)
+    return x.shape[0], x.shape[-2], x.shape[-1]
+
+
+def u8_clahe_lut(x, grid, clip_count):
+    """Stage 1 of CLAHE (cx_u8_clahe_lut): the (B, GY, GX, 256) uint8 equalisation tables of decoded grey bytes (B,1,H,W) / (B,H,W)
+    uint8 on the GPU; grid = (GY, GX), clip_count = the integer clip level per bin (chexpert_amd.augment.clahe_clip_count; 0: none)."""
+    require_cuda(x)
+    B, H, W = _u8_images(x)
+    GY, GX = int(grid[0]), int(grid[1])
+    lut = torch.empty(B, max(GY, 0), max(GX, 0), 256, dtype=torch.uint8, device=x.device)
+    check(lib().cx_u8_clahe_lut(ptr(x), ptr(lut), B, H, W, GY, GX, int(clip_count), stream_ptr()), "cx_u8_clahe_lut")
+    return lut
+
+
+def u8_clahe_apply(x, lut, out=None):
+    """Stage 2 of CLAHE (cx_u8_clahe_apply): every pixel through the bilinear blend of the four tables around it; lut: (B, GY, GX, 256)
+    uint8 as u8_clahe_lut returns it.  `out` must not be x."""
+    require_cuda(x, lut, out)
+    B, H, W = _u8_images(x)
+    assert lut.dtype == torch.uint8 and lut.is_contiguous() and lut.dim() == 4 and lut.shape[0] == B and lut.shape[3] == 256
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.uint8 and out.shape == x.shape and out.is_contiguous()
+    check(lib().cx_u8_clahe_apply(ptr(x), ptr(lut), ptr(out), B, H, W, lut.shape[1], lut.shape[2], stream_ptr()), "cx_u8_clahe_apply")
+    return out
+
+
+def u8_clahe(x, grid=(8, 8), clip_limit=2.0, out=None):
+    """Contrast-limited adaptive histogram equalisation of decoded grey bytes on the GPU: both stages (two launches).  The structure
+    is OpenCV's createCLAHE(clipLimit, tileGridSize); the arithmetic is the integer definition of chexpert_amd/augment.py, not
+    bit-equal to OpenCV's float rounding."""
+    from .augment import clahe_clip_count
+    B, H, W = _u8_images(x)
+    GY, GX = int(grid[0]), int(grid[1])
+    if GY < 1 or GX < 1 or H % GY or W % GX:
+        raise RuntimeError("u8_clahe: grid %s does not divide a %d x %d image (unsupported shape)" % ((GY, GX), H, W))
+    return u8_clahe_apply(x, u8_clahe_lut(x, (GY, GX), clahe_clip_count(clip_limit, H // GY, W // GX)), out)
+
+
 def nchw3_to_nhwc4(x, out=None):
     require_cuda(x)
     B, Cc, H, W = x.shape

@@ -4,9 +4,11 @@ the eval-mode HIP path of chexpert_amd.models; reading / cropping is chexpert_am
 
   python predict.py <data.csv> <predictions.csv> --restore_path <checkpoint.pt | folder> [--model densenet121|resnet152]
                     [--batch_size 16] [--resize N] [--mini_data N] [--cuda 0] [--tta K]
+                    [--clahe [--clahe_grid GY GX] [--clahe_clip C]]
 
 --tta K averages the probabilities of K forwards per image: the image as decoded, and K - 1 random affine warps of it on the GPU
-(chexpert_amd/augment.py, cx_u8_affine).
+(chexpert_amd/augment.py, cx_u8_affine).  --clahe equalises every uint8 batch on the GPU first (ops.u8_clahe, as the training command
+line's flag of the same name: a model trained with it is evaluated with it), before the forward and before each draw's warp.
 """
 import argparse
 import os
@@ -28,18 +30,38 @@ def build_parser():
     p.add_argument("--mini_data", type=int)
     p.add_argument("--tta", type=int, default=1, help="test-time augmentation: mean probability over K forwards (the image + K-1 affine warps)")
     p.add_argument("--tta_seed", type=int, default=0)
+    p.add_argument("--clahe", action="store_true", help="CLAHE contrast equalisation of the uint8 image (GPU), as chexpert.py --clahe")
+    p.add_argument("--clahe_grid", type=int, nargs=2, default=[8, 8], metavar=("GY", "GX"), help="tiles per axis, each 1..16, dividing the crop size")
+    p.add_argument("--clahe_clip", type=float, default=2.0, metavar="C", help="clip limit in multiples of the mean bin height (0: no clipping)")
     return p
 
 
+def parse_args(argv=None):
+    """The command line; a --clahe grid that does not divide the crop size is refused here (parser.error)."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.clahe:
+        from .augment import check_clahe_grid, clahe_clip_count
+        size = args.resize or 320
+        try:
+            check_clahe_grid(args.clahe_grid, size, size)
+            clahe_clip_count(args.clahe_clip, 1, 1)
+        except ValueError as e:
+            parser.error("--clahe: %s" % e)
+    return args
+
+
 @torch.no_grad()
-def predict(model, dataset, batch_size, device, tta=1, tta_seed=0):
+def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None):
     """DataFrame indexed by study ('.../patient64541/study1') with one probability column per finding (predict.py:33-52).
 
     tta = K > 1 (test-time augmentation): per image the mean of K sigmoid probabilities, then the max over a study's views as
     before.  Draw 0 is the batch as decoded; draws 1 .. K-1 warp the uint8 batch with ops.u8_affine (fill 0) and matrices from
     augment.affine_matrices at half the ranges of the training defaults -- rotation +-5 degrees, translation +-0.025 of the size,
     scale 0.95 .. 1.05, no shear (augment.TTA_RANGES) -- seeded by augment.tta_seed_of(tta_seed, draw, number of the minibatch):
-    two calls agree bit for bit.  tta = 1 is the plain path."""
+    two calls agree bit for bit.  tta = 1 is the plain path.
+
+    clahe: an augment.Clahe (or None): the uint8 batch is equalised once on the GPU, before the forward and before each draw's warp."""
     import pandas as pd
     from .data import extract_patient_ids
     if tta < 1:
@@ -49,6 +71,8 @@ def predict(model, dataset, batch_size, device, tta=1, tta_seed=0):
     for k in range(0, len(dataset), batch_size):
         items = [dataset[i] for i in range(k, min(k + batch_size, len(dataset)))]
         x = torch.stack([it[0] for it in items]).to(device)
+        if clahe is not None:
+            x = clahe(x)
         if tta == 1:
             probs.append(torch.sigmoid(model(x).float()).cpu())
         else:
@@ -71,7 +95,7 @@ def main(argv=None):
     import pandas as pd
     from .data import ChexpertCSV
     from .models import densenet121, resnet152
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("predict runs on the GPU only (there is no CPU path)")
     device = torch.device("cuda:%d" % args.cuda)
@@ -91,9 +115,13 @@ def main(argv=None):
     else:
         files = [args.restore_path]
     frames = []
+    clahe = None
+    if args.clahe:
+        from .augment import Clahe
+        clahe = Clahe(args.clahe_grid, args.clahe_clip)
     for f in files:
         model.load_state_dict(torch.load(f, map_location=device)["state_dict"])
-        frames.append(predict(model, ds, args.batch_size, device, tta=args.tta, tta_seed=args.tta_seed))
+        frames.append(predict(model, ds, args.batch_size, device, tta=args.tta, tta_seed=args.tta_seed, clahe=clahe))
     df = frames[0] if len(frames) == 1 else sum(frames[1:], frames[0]) / float(len(frames))      # mean over checkpoints
     df.to_csv(args.output_path)
     return df

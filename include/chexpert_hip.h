@@ -694,6 +694,28 @@ int cx_u8_jitter(const uint8_t* x, uint8_t* y, int B, int HW, const float* brigh
  * The identity (1,0,0, 0,1,0) returns x bit for bit.  One writer per output byte, no atomics: bit-reproducible.
  * W % 4 == 0, H and W <= 1024, else CX_ESHAPE; y and mat 4-byte aligned.  Additive entry point of ABI 10 (no struct changed).   */
 int cx_u8_affine(const uint8_t* x, uint8_t* y, int B, int H, int W, const float* mat /* device, [B][6] */, int fill, void* stream);
+/* Contrast-limited adaptive histogram equalisation (CLAHE) of the decoded grey images x: (B, H, W) uint8, in two stages (clahe.hip).
+ * The structure is OpenCV's createCLAHE (per-tile clipped histogram -> table, bilinear blend of the four surrounding tables), but
+ * NOT bit-equal to it: everything here is integer arithmetic, and tables sit at tile centres with pixel centres at half-integers.
+ * Grid (GY, GX), each 1..16, tile th = H / GY by tw = W / GX, area = th * tw.
+ * cx_u8_clahe_lut writes lut: (B, GY, GX, 256) uint8.  clip_count L in [0, area] is computed by the caller
+ * (L = 0 if c == 0 else min(area, max(1, floor(c * area / 256))) for a clip limit c; 0 = no clipping).  Table of tile (b, gy, gx):
+ *   hist[v] = number of pixels of the tile with value v
+ *   L > 0:  excess = sum max(hist[v] - L, 0);  hist[v] = min(hist[v], L);  q, r = divmod(excess, 256);  hist[v] += q for every v;
+ *           r > 0: step = max(1, 256 / r), and hist[v] += 1 for v = 0, step, 2 step, ... < 256 while r-- > 0
+ *   cdf[v] = hist[0] + ... + hist[v];   lut[v] = (cdf[v] * 255 + area / 2) / area
+ * cx_u8_clahe_apply writes y (a buffer other than x) from x and the tables.  For pixel (i, j) with value v = x[b][i][j]:
+ *   ay = 2 i + 1 - th;  gy0 = floor(ay / (2 th)) (-1 in the top half tile);  wy = ay - gy0 * 2 th;  gy1 = gy0 + 1; both clamped to
+ *   [0, GY - 1];  ax, gx0, wx, gx1 likewise with j, tw, GX
+ *   num = (2 th - wy) * ((2 tw - wx) * lut[gy0][gx0][v] + wx * lut[gy0][gx1][v])
+ *       +       wy    * ((2 tw - wx) * lut[gy1][gx0][v] + wx * lut[gy1][gx1][v])
+ *   y[b][i][j] = (num + 2 th tw) / (4 th tw)                                  (num < 2^31 at the size limits)
+ * GY = GX = 1 with L = 0 is plain global histogram equalisation.  Integer LDS adds inside a workgroup, nothing added in device
+ * memory, one writer per output byte: bit-reproducible.
+ * CX_ESHAPE: H % GY, W % GX, W % 4, H or W > 1024, a grid value outside 1..16.  CX_EINVAL: a null pointer, B <= 0, x == y,
+ * clip_count outside [0, area].  CX_EALIGN: lut or y not 4-byte aligned (x may have any alignment).  Additive entry points of ABI 10. */
+int cx_u8_clahe_lut(const uint8_t* x, uint8_t* lut, int B, int H, int W, int GY, int GX, int clip_count, void* stream);
+int cx_u8_clahe_apply(const uint8_t* x, const uint8_t* lut, uint8_t* y, int B, int H, int W, int GY, int GX, void* stream);
 
 /* ---- fp32 storage mode (CX_DT_F32): the element-wise kernels of the DenseNet path with fp32 activation tensors (same arguments,
  * `const void*` tensors are fp32, pitches in elements), the fp32 weight table ([tap][O][I] fp32; descriptors with stem = 1 give
