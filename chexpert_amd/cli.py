@@ -22,6 +22,11 @@
                         -1 and the loss skips it), ones_lsr / zeros_lsr (label smoothing: uniform in [0.55, 0.85] / [0, 0.3])
   --pos_weight W        `auto` or n_classes floats: BCEWithLogitsLoss's pos_weight, inside the fused step too; auto = per class
                         (non-ignored negatives) / (positives) of the training labels, clamped to [1/16, 16]
+  --loss {bce,aucm}     aucm: the AUC min-max-margin loss (Yuan et al., ICCV 2021; FusedNet.set_loss(kind="aucm"), loss.AUCMLoss) instead of
+                        the cross-entropy, its auxiliary scalars trained beside the network: --aucm_margin M (default 1.0), --aucm_prior `auto`
+                        (the default) or n_classes positive rates in (0, 1); auto = per class positives / non-ignored labels of the
+                        training table, a label >= 0.5 being a positive; --aucm_lr_aux R, the rate of the auxiliary scalars (default:
+                        --lr).  Not with --pos_weight, and on one GPU only.  Evaluation keeps reporting cross-entropy element losses
   --cam_classes [C ...] with --visualize: class-specific maps (gradcam.class_cam) of the 'vis' subset for these class indices (no value
                         or `all`: every class): vis/class_cam_lowres.npy (N, K, h, w) and one vis/classcam_<ident>_step_<N>.png per image
   --synthetic_uncertain F   that fraction of the synthetic training labels is uncertain (the policy above then applies)
@@ -96,6 +101,10 @@ def build_parser():
     p.add_argument("--clahe_clip", type=float, default=2.0, metavar="C", help="clip limit in multiples of the mean bin height (0: no clipping)")
     p.add_argument("--uncertain", default="ones", choices=list(UNCERTAIN_POLICIES), help="policy for the uncertain (-1) training labels")
     p.add_argument("--pos_weight", nargs="+", default=None, metavar="W", help="`auto` or n_classes floats: positive-term weights of the loss")
+    p.add_argument("--loss", default="bce", choices=["bce", "aucm"], help="training loss: cross-entropy, or the AUC min-max-margin loss")
+    p.add_argument("--aucm_margin", type=float, default=None, metavar="M", help="margin of --loss aucm (> 0; default 1.0)")
+    p.add_argument("--aucm_prior", nargs="+", default=None, metavar="P", help="`auto` (default) or n_classes positive rates in (0, 1) for --loss aucm")
+    p.add_argument("--aucm_lr_aux", type=float, default=None, metavar="R", help="rate of the auxiliary scalars of --loss aucm (default: --lr)")
     p.add_argument("--synthetic_uncertain", type=float, default=0.0, metavar="F", help="fraction of the synthetic training labels marked uncertain")
     p.add_argument("--cam_classes", nargs="*", default=None, metavar="CLASS",
                    help="with --visualize: class-specific maps (gradcam.class_cam) of these class indices; no value or `all` = every class")
@@ -197,6 +206,62 @@ def resolve_pos_weight(spec, targets, n_classes):
     if not all(np.isfinite(v) and v > 0 for v in w):
         raise ValueError("--pos_weight takes finite weights > 0 (got %s)" % w)
     return w
+
+
+def class_names(n_classes):
+    return ATTR_NAMES[:n_classes] if n_classes <= len(ATTR_NAMES) else ["class %d" % i for i in range(n_classes)]
+
+
+def resolve_aucm_prior(spec, targets, n_classes):
+    """--aucm_prior as a list of n_classes floats in (0, 1).  None or `auto`: per class positives / live labels of the training
+    targets on the host, with the loss's own split: live is t >= 0, positive is t >= 0.5 (a soft label falls on the side it came
+    from).  A class whose prior is not inside (0, 1) -- no positive, no negative or no live label at all -- is refused by name: the
+    loss weighs its two sides by p and 1 - p."""
+    names = class_names(n_classes)
+    spec = ["auto"] if spec is None else [spec] if isinstance(spec, str) else [str(v) for v in spec]
+    if spec == ["auto"]:
+        t = np.asarray(targets, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != n_classes:
+            raise ValueError("--aucm_prior auto needs the (N, %d) training targets (got shape %s)" % (n_classes, t.shape))
+        live, pos = (t >= 0).sum(0), (t >= 0.5).sum(0)
+        for c in range(n_classes):
+            if live[c] == 0 or pos[c] == 0 or pos[c] == live[c]:
+                raise ValueError("--aucm_prior auto: class %d (%s) has %d positives among %d non-ignored training labels; the AUC-margin "
+                                 "loss needs a prior inside (0, 1), i.e. both positives and negatives" % (c, names[c], pos[c], live[c]))
+        return [float(v) for v in pos / live]
+    try:
+        pr = [float(v) for v in spec]
+    except ValueError:
+        raise ValueError("--aucm_prior takes `auto` or %d floats (got %s)" % (n_classes, spec))
+    if len(pr) != n_classes:
+        raise ValueError("--aucm_prior takes `auto` or %d floats (got %d)" % (n_classes, len(pr)))
+    for c, v in enumerate(pr):
+        if not 0.0 < v < 1.0:
+            raise ValueError("--aucm_prior: class %d (%s) has prior %r; it must be inside (0, 1)" % (c, names[c], v))
+    return pr
+
+
+def aucm_options(args, world=1):
+    """--loss / --aucm_* checked before anything runs: None for the cross-entropy, else {"margin", "lr_aux"} (the prior needs the
+    training table: resolve_aucm_prior)."""
+    loss = getattr(args, "loss", "bce")
+    margin, prior, lr_aux = getattr(args, "aucm_margin", None), getattr(args, "aucm_prior", None), getattr(args, "aucm_lr_aux", None)
+    if loss != "aucm":
+        if prior is not None or lr_aux is not None or margin is not None:
+            raise ValueError("--aucm_margin / --aucm_prior / --aucm_lr_aux belong to --loss aucm: pass it with them")
+        return None
+    margin = 1.0 if margin is None else margin
+    if args.pos_weight is not None:
+        raise ValueError("--loss aucm cannot be combined with --pos_weight: the class prior is this loss's weighting")
+    if not margin > 0:
+        raise ValueError("--aucm_margin takes a margin > 0 (got %r)" % margin)
+    lr_aux = args.lr if lr_aux is None else lr_aux
+    if not lr_aux > 0:
+        raise ValueError("--aucm_lr_aux takes a rate > 0 (got %r)" % lr_aux)
+    if world > 1:
+        from .models._fused import AUCM_DATA_PARALLEL
+        raise RuntimeError("--loss aucm: " + AUCM_DATA_PARALLEL % world)
+    return {"margin": float(margin), "lr_aux": float(lr_aux)}
 
 
 def resolve_cam_classes(spec, n_classes):
@@ -351,7 +416,8 @@ def save_checkpoint(ckpt, optim_state, sched_state, args, max_records=10):
 
 
 def restore(args, model, optimizer, scheduler, device):
-    """chexpert.py:504-518: model weights + step from the file; when training also `optim_<name>` / `sched_<name>` beside it."""
+    """chexpert.py:504-518: model weights + step from the file; when training also `optim_<name>` / `sched_<name>` beside it.
+    Returns the checkpoint's `loss_state` entry (FusedNet.loss_state() of a --loss aucm run), or None."""
     ck = torch.load(args.restore, map_location=device)
     model.load_state_dict(model_weights(ck, args, args.restore))
     args.step = ck["global_step"]
@@ -360,6 +426,7 @@ def restore(args, model, optimizer, scheduler, device):
         optimizer.load_state_dict(torch.load(os.path.join(d, "optim_" + b), map_location=device))
         if scheduler is not None and scheduler != "fused":
             scheduler.load_state_dict(torch.load(os.path.join(d, "sched_" + b), map_location=device))
+    return ck.get("loss_state")
 
 
 def plot_roc(res, args, name):
@@ -397,6 +464,7 @@ def main(argv=None):
     if cam_classes is not None and not args.visualize:
         raise ValueError("--cam_classes draws class maps over the 'vis' subset: pass --visualize with it")
     rank, world, local = P.dist_info()
+    aucm = aucm_options(args, world)
     if world > 1:
         # the process group comes first, before anything touches the GPU; one rank per GPU over RCCL ("nccl"), or ranks sharing
         # a device over gloo when the box has fewer GPUs than ranks (tests)
@@ -438,6 +506,12 @@ def main(argv=None):
         cfg = json.load(open(cfg_path))
         cfg["pos_weight_resolved"] = pos_weight
         json.dump(cfg, open(cfg_path, "w"), indent=4)
+    if aucm is not None:
+        aucm["prior"] = resolve_aucm_prior(args.aucm_prior, train_ds.targets, args.n_classes)
+        if rank == 0 and new_cfg:
+            cfg = json.load(open(cfg_path))
+            cfg["aucm_prior_resolved"] = aucm["prior"]
+            json.dump(cfg, open(cfg_path, "w"), indent=4)
     train_loader = None
     if args.train:
         from .loader import RingLoader
@@ -449,14 +523,37 @@ def main(argv=None):
         torch.manual_seed(args.seed)
         np.random.seed(args.seed)
     model, optimizer, scheduler = make_model(args, device)
+    restored_loss = None
     if args.restore and os.path.isfile(args.restore):
-        restore(args, model, optimizer, scheduler, device)
+        restored_loss = restore(args, model, optimizer, scheduler, device)
     loss_fn = nn.BCEWithLogitsLoss(reduction="none")
     masked_loss = None
     if args.uncertain == "ignore" or pos_weight is not None:
         from .loss import MaskedBCE
         model.set_loss(ignore_negative=args.uncertain == "ignore", pos_weight=pos_weight)      # the fused step's loss
         masked_loss = MaskedBCE(model.loss_pos_weight, ignore_negative=args.uncertain == "ignore")   # the autograd route's
+    aucm_loss = aucm_opt = None
+    if aucm is not None:
+        # the fused step's loss; a restored checkpoint brings its auxiliary scalars, the flags of this run keep the last word on
+        # prior, margin and rate (set_loss on a model that holds the loss already leaves loss_aux as it is)
+        if restored_loss is not None and restored_loss.get("kind") == "aucm":
+            model.load_loss_state(restored_loss)
+        model.set_loss(kind="aucm", **aucm)
+        if args.train and not args.fused_optimizer:
+            # the autograd route: the loss module's a, b, alpha under plain SGD at the auxiliary rate, then alpha >= 0 -- the update
+            # of the fused step; they start from, and a checkpoint reads them back through, model.loss_aux
+            from .loss import AUCMLoss
+            aucm_loss = AUCMLoss(aucm["prior"], aucm["margin"]).to(device)
+            with torch.no_grad():
+                for p_, row in zip((aucm_loss.a, aucm_loss.b, aucm_loss.alpha), model.loss_aux):
+                    p_.copy_(row)
+            aucm_opt = torch.optim.SGD(aucm_loss.parameters(), lr=aucm["lr_aux"])
+
+    def sync_loss_aux():
+        """Autograd route: model.loss_aux (what loss_state() and a checkpoint read) follows the loss module's parameters."""
+        if aucm_loss is not None:
+            with torch.no_grad():
+                model.loss_aux.copy_(torch.stack([aucm_loss.a, aucm_loss.b, aucm_loss.alpha]))
     if rank == 0:
         print("Loaded %s (number of parameters: %s; weights trained to step %d)" % (
             model._get_name(), format(sum(p.numel() for p in model.parameters()), ","), args.step))
@@ -530,10 +627,17 @@ def main(argv=None):
                         optimizer.scheduler_step()
                 else:
                     out = model(x)
-                    loss = masked_loss(out, t) if masked_loss is not None else loss_fn(out, t).sum(1).mean(0)   # chexpert.py:160
+                    if aucm_loss is not None:
+                        loss = aucm_loss(out, t)
+                        aucm_opt.zero_grad()
+                    else:
+                        loss = masked_loss(out, t) if masked_loss is not None else loss_fn(out, t).sum(1).mean(0)   # chexpert.py:160
                     optimizer.zero_grad()
                     loss.backward()
                     optimizer.step()
+                    if aucm_loss is not None:
+                        aucm_opt.step()
+                        aucm_loss.clamp_()
                     if scheduler and args.step >= args.lr_warmup_steps:
                         scheduler.step()
                 if args.step % args.log_interval == 0 and rank == 0:
@@ -557,8 +661,12 @@ def main(argv=None):
                                 "avg_auc": M.mean_auc(res), "state_dict": model.state_dict()}
                         if ema_sd is not None:        # beside the live weights, which restore continues from
                             ckpt["ema_state_dict"] = ema_sd
+                        if aucm is not None:          # the auxiliary scalars are trained state: restore continues from them
+                            sync_loss_aux()
+                            ckpt["loss_state"] = model.loss_state()
                         save_checkpoint(ckpt, optimizer.state_dict(), sched_state, args)
                     model.train()
+            sync_loss_aux()      # (also current when no checkpoint followed the last step)
             torch.cuda.synchronize()
             if rank == 0:        # input pipeline + step, end to end (the figure to hold against bench.py's device-resident rate)
                 print(json.dumps({"epoch": epoch, "images_per_sec": round(len(idx) * world / (time.perf_counter() - t_epoch), 1),
@@ -585,7 +693,7 @@ def main(argv=None):
         # attention-augmented models the attention-map grids of the stored softmax weights
         from . import vis
         from .gradcam import class_cam, grad_cam
-        names = ATTR_NAMES[:args.n_classes] if args.n_classes <= len(ATTR_NAMES) else ["class %d" % i for i in range(args.n_classes)]
+        names = class_names(args.n_classes)
         groups = vis.select_vis_subset(valid_ds.targets, names)
         flat = sorted({i for g in groups[1] for i in g})
         pos = {i: k for k, i in enumerate(flat)}

@@ -10,6 +10,11 @@ the scheduler advance inside the graph.
 import torch
 
 
+def _step_state(model):
+    """What a training step changes beside the parameters: the module buffers and the state of the model's loss."""
+    return list(model.buffers()) + list(getattr(model, "loss_step_state", lambda: [])())
+
+
 class GraphedTrainStep:
     def __init__(self, model, optimizer, x, target, warmup_steps=0, warmup_iters=2):
         if not x.is_cuda:
@@ -25,7 +30,8 @@ class GraphedTrainStep:
         model.train()
         # construction is free of side effects on the model: the warm-up steps below really run (they update BatchNorm running
         # statistics), so the module buffers and the num_batches_tracked bookkeeping are put back afterwards
-        saved = [(b, b.detach().clone()) for b in model.buffers()]
+        # (so are the auxiliary scalars of set_loss(kind="aucm"), which a train-mode step updates: loss_step_state)
+        saved = [(b, b.detach().clone()) for b in _step_state(model)]
         nbt = getattr(model, "_nbt_pending", 0)
         # eager warm-up on a side stream: binds the engine, allocates the workspaces, sets kernel attributes, creates the
         # optimiser state -- none of which may happen during capture
@@ -99,7 +105,7 @@ class SegmentedTrainStep:
         self.model, self.opt, self.red = model, optimizer, red
         self.x, self.target = x.clone(), target.clone()
         model.train()
-        saved = [(b, b.detach().clone()) for b in model.buffers()]
+        saved = [(b, b.detach().clone()) for b in _step_state(model)]
         nbt = getattr(model, "_nbt_pending", 0)
         s = torch.cuda.Stream(device=x.device)
         s.wait_stream(torch.cuda.current_stream())

@@ -1,17 +1,19 @@
 """The training loss with uncertain-label handling outside the fused step: `loss = MaskedBCE(w)(model(x), t); loss.backward()` and
 the element losses of an evaluation run the arithmetic of `FusedNet.set_loss` (cx_bce_masked_fwd_bwd, csrc/elementwise.hip), so
-the autograd route and the fused step agree bit for bit.  Device tensors only: there is no CPU path."""
+the autograd route and the fused step agree bit for bit.  AUCMLoss is the same for `FusedNet.set_loss(kind="aucm")`: the AUC
+min-max-margin loss (cx_aucm_fwd_bwd, csrc/aucm.hip) with its auxiliary scalars as parameters.  Device tensors only: there is no
+CPU path."""
 import torch
 import torch.nn as nn
 
 from . import ops
 
 
-def _operands(logits, target):
+def _operands(logits, target, who="MaskedBCE", kernel="cx_bce_masked_fwd_bwd"):
     if not logits.is_cuda:
-        raise RuntimeError("MaskedBCE runs on the GPU only (cx_bce_masked_fwd_bwd); there is no CPU fallback")
+        raise RuntimeError("%s runs on the GPU only (%s); there is no CPU fallback" % (who, kernel))
     if logits.dim() != 2 or tuple(target.shape) != tuple(logits.shape):
-        raise RuntimeError("MaskedBCE takes (B, n) logits and targets of one shape (got %s and %s)" % (tuple(logits.shape), tuple(target.shape)))
+        raise RuntimeError("%s takes (B, n) logits and targets of one shape (got %s and %s)" % (who, tuple(logits.shape), tuple(target.shape)))
     return logits.detach().contiguous().float(), target.detach().contiguous().float()
 
 
@@ -72,3 +74,68 @@ class MaskedBCE(nn.Module):
         else:
             ops.bce_fwd_bwd(x, t, None, out, None)
         return out
+
+
+class _AUCMFn(torch.autograd.Function):
+    """loss, d loss / d logits and the three auxiliary gradients in one launch; backward scales the stored gradients."""
+
+    @staticmethod
+    def forward(ctx, logits, target, a, b, alpha, prior, margin):
+        x, t = _operands(logits, target, "AUCMLoss", "cx_aucm_fwd_bwd")
+        aux = torch.stack([a.detach(), b.detach(), alpha.detach()]).float().contiguous()
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        dl, daux = torch.empty_like(x), torch.empty_like(aux)
+        ops.aucm_fwd_bwd(x, t, prior, aux, margin, loss, None, dl, daux)
+        ctx.save_for_backward(dl, daux)
+        ctx.in_dtype = logits.dtype
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dl, daux = ctx.saved_tensors
+        # alpha is the dual variable: the saddle point is a minimum in (w, a, b) and a maximum in alpha, so its gradient leaves
+        # negated and the optimiser that descends on every parameter ascends on alpha
+        return (dl * grad_output).to(ctx.in_dtype), None, daux[0] * grad_output, daux[1] * grad_output, -daux[2] * grad_output, None, None
+
+
+class AUCMLoss(nn.Module):
+    """The AUC min-max-margin loss (Yuan et al., "Large-scale Robust Deep AUC Maximization", ICCV 2021) of (B, n) logits, summed
+    over the classes: the loss of FusedNet.set_loss(kind="aucm") for the autograd route, by the same kernel, so `loss.backward()`
+    leaves the fused step's d loss / d logits bit for bit.  prior: n class positive rates in (0, 1); margin > 0.  A target < 0 is
+    ignored, a target >= 0.5 counts as a positive, the rest as negatives.
+
+    The auxiliary scalars a, b, alpha are nn.Parameters of THIS module (shape (n,), zero at first): hand them to an optimiser
+    beside the network's.  The problem is a saddle point -- minimise over the network, a and b, maximise over alpha >= 0 -- so
+    backward returns alpha's gradient NEGATED: `alpha.grad` is -d loss / d alpha, and a descending optimiser ascends on alpha.
+    Call clamp_() after each optimiser step to keep alpha >= 0 (plain SGD with rate lr_aux followed by clamp_() is the update
+    FusedNet.forward_backward makes).  There are no element losses: elementwise() raises."""
+
+    def __init__(self, prior, margin=1.0):
+        super().__init__()
+        p = torch.as_tensor(prior, dtype=torch.float32).detach().reshape(-1).cpu()
+        if p.numel() < 1 or not bool(((p > 0) & (p < 1)).all()):
+            raise ValueError("AUCMLoss takes class priors in (0, 1) (got %s)" % p.tolist())
+        if not float(margin) > 0:
+            raise ValueError("AUCMLoss takes a margin > 0 (got %r)" % (margin,))
+        self.margin = float(margin)
+        self.prior = p                       # a plain attribute, moved by hand like MaskedBCE.pos_weight
+        self.a, self.b, self.alpha = (nn.Parameter(torch.zeros(p.numel())) for _ in range(3))
+
+    def forward(self, logits, target):
+        if self.prior.device != logits.device:
+            self.prior = self.prior.to(logits.device)
+        if self.a.device != logits.device:
+            raise RuntimeError("AUCMLoss: a, b and alpha are on %s, the logits on %s -- call loss.to(device)" % (self.a.device, logits.device))
+        if logits.dim() == 2 and logits.shape[1] != self.prior.numel():
+            raise RuntimeError("AUCMLoss holds %d classes, the logits have %d" % (self.prior.numel(), logits.shape[1]))
+        return _AUCMFn.apply(logits, target, self.a, self.b, self.alpha, self.prior, self.margin)
+
+    @torch.no_grad()
+    def clamp_(self):
+        """alpha >= 0, after an optimiser step.  Returns self."""
+        self.alpha.clamp_(min=0)
+        return self
+
+    def elementwise(self, logits, target):
+        raise RuntimeError("AUCMLoss has no element losses: it is a function of each class's whole batch column (its positives "
+                           "against its negatives), not a sum over elements -- evaluate with MaskedBCE.elementwise or BCEWithLogitsLoss")

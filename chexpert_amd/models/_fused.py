@@ -62,6 +62,19 @@ def params_untouched(params, flat_grad):
             p.grad = g
 
 
+AUCM_DATA_PARALLEL = ("the AUC-margin loss (kind='aucm') is not supported data-parallel (world size %d): each rank would update its "
+                      "auxiliary scalars a, b, alpha from its own shard, and averaging their gradients needs a collective of its "
+                      "own at a new cut of the segmented step, which has not been built -- train on one GPU, or use the "
+                      "cross-entropy")
+
+
+def check_aucm_single_process(reducer):
+    """Raises when gradients are averaged over more than one rank (`reducer`: the engine's GradReducer, or None)."""
+    world = getattr(reducer, "world", 1) if reducer is not None else 1
+    if world > 1:
+        raise RuntimeError(AUCM_DATA_PARALLEL % world)
+
+
 # --------------------------------------------------------------------------------------------- module side
 class _Fn(torch.autograd.Function):
     """loss.backward() through a fused network: forward runs the engine's training forward -- in eval mode its recording eval
@@ -104,8 +117,13 @@ class FusedNet(nn.Module):
         self._engine = None
         # set_loss(): plain tensors / flags, not buffers (the state_dict keys stay what they are)
         self.loss_ignore_negative, self.loss_pos_weight, self._pos_weight_store = False, None, None
+        # set_loss(kind="aucm"): the auxiliary scalars (3, n), the class priors (n,), the one-float rate of their update (device
+        # tensors the kernels read) and the margin (a host float, passed by value)
+        self.loss_kind, self.loss_margin = "bce", 1.0
+        self.loss_aux = self.loss_prior = self.loss_lr_aux = self._loss_daux = None
+        self._aucm_store = None
 
-    def set_loss(self, ignore_negative=False, pos_weight=None):
+    def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None):
         """The loss of forward_backward.  ignore_negative: a target < 0 (an uncertain label kept as -1, the U-Ignore policy) adds no
         loss and no gradient; the divisor stays the batch size.  pos_weight: None, or n_classes positive-term weights as in torch's
         BCEWithLogitsLoss(pos_weight).  Either option routes the step through cx_bce_masked_fwd_bwd, which skips every target < 0:
@@ -118,7 +136,33 @@ class FusedNet(nn.Module):
         the weight storage it was captured with.  What a replay does see is a change of the weights' VALUES -- in place
         (`model.loss_pos_weight.mul_(2)`) or by set_loss(pos_weight=...) with the same number of weights and the same options,
         which copies into the held storage.  A switch between the plain and the masked loss, from no weights to weights or
-        back, or to another number of weights (new storage) needs a new capture."""
+        back, or to another number of weights (new storage) needs a new capture.
+
+        kind="aucm" replaces the cross-entropy by the AUC min-max-margin loss (Yuan et al., ICCV 2021; cx_aucm_fwd_bwd): a
+        squared-hinge surrogate of the per-class AUROC with three auxiliary scalars per class, which forward_backward trains
+        beside the network (descent on a and b, ascent on alpha >= 0, rate lr_aux, after the backward pass of a train-mode step).
+        prior: n_classes positive rates in (0, 1); margin > 0; lr_aux > 0.  It skips every target < 0 (ignore_negative has nothing
+        left to decide), counts a target >= 0.5 as a positive, and cannot be combined with pos_weight (ValueError).  The state is
+        plain tensors again: `loss_aux` (3, n) = rows a, b, alpha, zero at first; `loss_prior` (n,); `loss_lr_aux` (one float);
+        loss_state() / load_loss_state() carry them to a checkpoint and back.  The storage rule is the one of the weights:
+        set_loss(kind="aucm", ...) on a model that already holds the loss for the same number of classes copies prior and lr_aux
+        into the held storage and leaves `loss_aux` as trained, so a captured step sees the new values (as it sees
+        `model.loss_lr_aux.fill_(r)`); coming from another kind, or with another number of classes, `loss_aux` starts at zero.  A
+        change of kind or of the margin (passed by value) needs a new capture.  The data-parallel step is not supported: the
+        auxiliary gradients would need a collective of their own (forward_backward raises when the engine averages gradients over
+        more than one rank)."""
+        if kind not in ("bce", "aucm"):
+            raise ValueError("set_loss(kind=...) takes 'bce' or 'aucm' (got %r)" % (kind,))
+        if kind == "bce" and (prior is not None or lr_aux is not None or margin != 1.0):
+            raise ValueError("set_loss: prior, margin and lr_aux belong to kind='aucm'")
+        if kind == "aucm":
+            if pos_weight is not None:
+                raise ValueError("set_loss(kind='aucm') cannot be combined with pos_weight: the class prior is this loss's weighting")
+            self._set_aucm(prior, margin, lr_aux)
+            self.loss_pos_weight, self.loss_ignore_negative, self.loss_kind = None, True, "aucm"
+            return self
+        self.loss_kind = "bce"
+        self.loss_aux = self.loss_prior = self.loss_lr_aux = self._loss_daux = None      # (the storage itself is kept)
         if pos_weight is not None:
             dev = next(self.parameters()).device
             if dev.type != "cuda":
@@ -131,6 +175,72 @@ class FusedNet(nn.Module):
         self.loss_pos_weight = self._pos_weight_store if pos_weight is not None else None
         self.loss_ignore_negative = bool(ignore_negative)
         return self
+
+    def _n_classes(self):
+        """Width of the final Linear layer (the classifier of every family)."""
+        return [m for m in self.modules() if isinstance(m, nn.Linear)][-1].out_features
+
+    def _set_aucm(self, prior, margin, lr_aux):
+        """Checks the operands of set_loss(kind="aucm") (ValueError; nothing is changed when one is refused) and puts them into the
+        held device storage, which is made anew -- with loss_aux = 0 -- when there is none for this number of classes."""
+        n = self._n_classes()
+        if prior is None:
+            raise ValueError("set_loss(kind='aucm') needs prior: the %d class positive rates" % n)
+        p = torch.as_tensor(prior, dtype=torch.float32).detach().reshape(-1).cpu()
+        if p.numel() != n:
+            raise ValueError("set_loss(kind='aucm') takes one prior per class: %d (got %d)" % (n, p.numel()))
+        if not bool(((p > 0) & (p < 1)).all()):
+            raise ValueError("set_loss(kind='aucm') takes priors in (0, 1) (got %s)" % p.tolist())
+        if not float(margin) > 0:
+            raise ValueError("set_loss(kind='aucm') takes a margin > 0 (got %r)" % (margin,))
+        if lr_aux is None or not float(lr_aux) > 0:
+            raise ValueError("set_loss(kind='aucm') needs lr_aux > 0, the rate of the auxiliary scalars (got %r)" % (lr_aux,))
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("set_loss(kind='aucm') holds its state on the parameters' device: call model.to(device) first")
+        held = self._aucm_store
+        fresh = held is None or held["prior"].numel() != n or held["prior"].device != dev
+        if fresh:
+            held = self._aucm_store = {"aux": torch.zeros(3, n, dtype=torch.float32, device=dev),
+                                       "daux": torch.zeros(3, n, dtype=torch.float32, device=dev),
+                                       "prior": torch.empty(n, dtype=torch.float32, device=dev),
+                                       "lr_aux": torch.empty(1, dtype=torch.float32, device=dev)}
+        elif self.loss_kind != "aucm":
+            held["aux"].zero_()
+        held["prior"].copy_(p)
+        held["lr_aux"].fill_(float(lr_aux))
+        self.loss_aux, self._loss_daux, self.loss_prior, self.loss_lr_aux = held["aux"], held["daux"], held["prior"], held["lr_aux"]
+        self.loss_margin = float(margin)
+
+    def loss_state(self):
+        """What set_loss(kind=...) holds beyond the model's state_dict, as CPU tensors and floats: {kind, aux, prior, margin, lr_aux}
+        (aux, prior and lr_aux are None for kind 'bce').  A checkpoint keeps it beside the weights."""
+        if self.loss_kind != "aucm":
+            return {"kind": self.loss_kind, "aux": None, "prior": None, "margin": float(self.loss_margin), "lr_aux": None}
+        return {"kind": "aucm", "aux": self.loss_aux.detach().cpu().clone(), "prior": self.loss_prior.detach().cpu().clone(),
+                "margin": float(self.loss_margin), "lr_aux": float(self.loss_lr_aux.item())}
+
+    def load_loss_state(self, d):
+        """Restores loss_state(): for kind 'aucm' the loss is set with the stored prior, margin and rate, and the auxiliary scalars
+        are copied in (into the held storage when there is one for this number of classes).  Kind 'bce' leaves the options of
+        the cross-entropy (ignore_negative, pos_weight) as they are.  Returns self."""
+        if d["kind"] != "aucm":
+            if d["kind"] != "bce":
+                raise ValueError("load_loss_state: unknown loss kind %r" % (d["kind"],))
+            if self.loss_kind != "bce":
+                self.set_loss()
+            return self
+        aux = torch.as_tensor(d["aux"], dtype=torch.float32)
+        if tuple(aux.shape) != (3, self._n_classes()):
+            raise ValueError("load_loss_state: aux must be (3, %d) (got %s)" % (self._n_classes(), tuple(aux.shape)))
+        self.set_loss(kind="aucm", prior=d["prior"], margin=d["margin"], lr_aux=d["lr_aux"])
+        self.loss_aux.copy_(aux)
+        return self
+
+    def loss_step_state(self):
+        """The tensors beyond parameters and buffers that a train-mode forward_backward changes (a graph capture's warm-up steps
+        really run: it puts them back)."""
+        return [self.loss_aux] if self.loss_kind == "aucm" else []
 
     def storage_dtype(self, dtype):
         """Storage type of the activations inside the fused schedule: torch.bfloat16 (default: bf16 tensors, fp32 accumulation
@@ -174,19 +284,27 @@ class FusedNet(nn.Module):
         Returns (loss, logits) as device tensors without a host sync.  input_grad: None, or a preallocated fp32 (B,3,H,W) tensor that
         also receives d loss / d x (what x.grad would hold), still without a host sync.  In eval mode this is the frozen-BatchNorm
         step (running statistics, which stay as they are).  After set_loss(...) the loss ignores targets < 0 and / or weights the
-        positive term per class (same reduction, same divisor)."""
+        positive term per class (same reduction, same divisor).  After set_loss(kind="aucm", ...) the loss is the AUC-margin loss,
+        and a train-mode step ends with the update of its auxiliary scalars (`loss_aux`), from the gradients of this step; the
+        eval-mode step computes the gradients and leaves `loss_aux` alone."""
         eng = self._eng()
         if input_grad is not None:
             check_input_grad(input_grad, x)
+        if self.loss_kind == "aucm":
+            check_aucm_single_process(eng.reducer)
         ws = eng.forward(x, self.training, record=True)
         B, n = ws.logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
-        if self.loss_ignore_negative or self.loss_pos_weight is not None:      # set_loss(): ignored labels / class weights
+        if self.loss_kind == "aucm":                                           # set_loss(kind="aucm"): one launch, as the others
+            ops.aucm_fwd_bwd(ws.logits, target, self.loss_prior, self.loss_aux, self.loss_margin, loss, None, dl, self._loss_daux)
+        elif self.loss_ignore_negative or self.loss_pos_weight is not None:    # set_loss(): ignored labels / class weights
             ops.bce_masked_fwd_bwd(ws.logits, target, self.loss_pos_weight, loss, None, dl)
         else:
             ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
         eng.backward(ws, dl, dx=input_grad)
+        if self.loss_kind == "aucm" and self.training:                         # from this step's gradients; eval leaves them alone
+            ops.aucm_aux_step(self.loss_aux, self._loss_daux, self.loss_lr_aux)
         logits = ws.logits.clone()
         eng.release(ws)
         return loss, logits

@@ -616,6 +616,36 @@ def bce_masked_fwd_bwd(logits, target, pos_weight, loss, loss_elem, dlogits, gra
                                       B, n, stream_ptr()), "cx_bce_masked_fwd_bwd")
 
 
+def aucm_fwd_bwd(logits, target, prior, aux, margin, loss, loss_class, dlogits, daux, grad_scale=1.0):
+    """The AUC min-max-margin loss of the (B, n) logits with its gradients in one launch (cx_aucm_fwd_bwd): prior fp32 (n,) in (0, 1),
+    aux fp32 (3, n) = rows a, b, alpha, margin > 0; a target < 0 is ignored, t >= 0.5 is a positive.  loss (1,), loss_class (n,),
+    dlogits (B, n) and daux (3, n) are optional; grad_scale multiplies dlogits alone."""
+    require_cuda(logits, target, prior, aux, loss, loss_class, dlogits, daux)
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    B, n = logits.shape
+    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (B, n) and target.device == logits.device
+    assert tuple(prior.shape) == (n,) and tuple(aux.shape) == (3, n) and (daux is None or tuple(daux.shape) == (3, n))
+    assert all(t is None or t.device == logits.device for t in (prior, aux, loss, loss_class, dlogits, daux))
+    _f32(prior, loss_class, n=n)
+    _f32(aux, daux, n=3 * n)
+    _f32(loss, n=1)
+    _f32(dlogits, n=B * n)
+    assert dlogits is None or tuple(dlogits.shape) == (B, n)
+    check(lib().cx_aucm_fwd_bwd(ptr(logits), ptr(target), ptr(prior), ptr(aux), float(margin), ptr(loss), ptr(loss_class), ptr(dlogits),
+                                ptr(daux), grad_scale, B, n, stream_ptr()), "cx_aucm_fwd_bwd")
+
+
+def aucm_aux_step(aux, daux, lr_aux):
+    """a -= lr da, b -= lr db, alpha = max(0, alpha + lr dalpha) on the (3, n) auxiliary scalars of aucm_fwd_bwd; lr_aux is a one-float
+    DEVICE tensor, read by the kernel (a captured step sees a changed rate)."""
+    require_cuda(aux, daux, lr_aux)
+    assert aux.dim() == 2 and aux.shape[0] == 3 and tuple(daux.shape) == tuple(aux.shape) and lr_aux.numel() == 1
+    assert daux.device == aux.device and lr_aux.device == aux.device
+    _f32(aux, daux, n=aux.numel())
+    _f32(lr_aux, n=1)
+    check(lib().cx_aucm_aux_step(ptr(aux), ptr(daux), ptr(lr_aux), aux.shape[1], stream_ptr()), "cx_aucm_aux_step")
+
+
 def softmax_ce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):
     """CrossEntropyLoss forward + gradient in one launch (fp32 logits [B, n], int64 class indices [B])."""
     B, n = logits.shape

@@ -358,6 +358,25 @@ int cx_bce_fwd_bwd(const float* logits, const float* target, float* loss, float*
  * of ABI 10 (no struct changed).                                                                                               */
 int cx_bce_masked_fwd_bwd(const float* logits, const float* target, const float* pos_weight, float* loss, float* loss_elem,
                           float* dlogits, float grad_scale, int B, int n_classes, void* stream);
+/* AUC min-max-margin loss (Yuan et al., ICCV 2021) with its gradients, one launch (aucm.hip).  Per class c, over the batch rows i, with
+ * x = logits[i][c], y = sigmoid(x), t = target[i][c], p = prior[c] in (0, 1), m = margin > 0, (a, b, alpha) = aux[0][c], aux[1][c],
+ * aux[2][c]; a row is live when t >= 0 (t < 0 is ignored as in cx_bce_masked_fwd_bwd), positive (P) when live and t >= 0.5, negative
+ * (N) when live and t < 0.5, L = number of live rows:
+ *   inner      = p (1-p) m + sum(p y N - (1-p) y P) / L
+ *   loss_c     = (1-p) sum((y-a)^2 P) / L + p sum((y-b)^2 N) / L + 2 alpha inner - p (1-p) alpha^2
+ *   dloss/dx_i = y (1-y) / L [P (1-p) (2 (y-a) - 2 alpha) + N p (2 (y-b) + 2 alpha)]              (0 for an ignored row)
+ *   dloss/da   = -(1-p) sum(2 (y-a) P) / L,  dloss/db = -p sum(2 (y-b) N) / L,  dloss/dalpha = 2 inner - 2 p (1-p) alpha
+ * and loss = sum_c loss_c.  A class without a live row adds nothing: loss_c = 0 and its three auxiliary gradients are 0, so the
+ * update below leaves its scalars alone.  prior: fp32 [n_classes]; aux, daux: fp32 (3, n_classes); loss: one float; loss_class:
+ * [n_classes] (the loss_c); dlogits: (B, n_classes) = dloss/dx * grad_scale (grad_scale touches nothing else).  loss, loss_class,
+ * dlogits and daux may each be NULL.  One workgroup; the per-class sums run in double over a fixed tree, no atomics: bit-reproducible.
+ * Any B >= 1 and n_classes >= 1.  CX_EINVAL before anything is launched: NULL logits / target / prior / aux, B < 1, n_classes < 1,
+ * margin <= 0.  Additive entry points of ABI 10 (no struct changed).                                                             */
+int cx_aucm_fwd_bwd(const float* logits, const float* target, const float* prior, const float* aux, float margin, float* loss,
+                    float* loss_class, float* dlogits, float* daux, float grad_scale, int B, int n_classes, void* stream);
+/* primal descent on a and b, dual ascent on alpha, from the gradients of the same step: a -= lr da, b -= lr db,
+ * alpha = max(0, alpha + lr dalpha), lr = *lr_aux_dev (a device float: a captured step sees a changed rate).                      */
+int cx_aucm_aux_step(float* aux, const float* daux, const float* lr_aux_dev, int n_classes, void* stream);
 /* loss = CrossEntropyLoss(logits, target) (mean over the batch of logsumexp - logit[target]);
  * dlogits = (softmax - onehot)/B * grad_scale; loss_elem (optional) = the per-sample terms
  * (models/test_model.py:118, :143, :331: the CIFAR harness criterion)                              */
