@@ -35,6 +35,11 @@
   --ema_decay D         exponential moving average of the weights, written by the optimiser kernel; evaluation and the checkpoint's
                         `ema_state_dict` use it.  --no_ema_warmup: constant decay instead of min(D, (1 + step) / (10 + step))
   --use_ema             --evaluate_single_model / --evaluate_ensemble / --visualize load `ema_state_dict` from the checkpoint
+  --bootstrap B         B > 0: every eval_results_<tag>.json gets an auc_ci_<tag>.json beside it (rank 0): AUROC per class and for the mean
+                        with its (1 - A) percentile bootstrap interval over B replicates, computed on the GPU (metrics.bootstrap_auc);
+                        --bootstrap_seed S (default: --seed), --bootstrap_unit image|study|patient (what is resampled; study and
+                        patient need the real data's paths), --bootstrap_alpha A (default 0.05).  0 (default): nothing is computed,
+                        allocated or written
 
 Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N chexpert.py --train ...`; every rank holds a
 replica and a shard of each minibatch stream (per-rank BatchNorm statistics, averaged gradients: DDP semantics), the
@@ -57,6 +62,7 @@ from . import parallel as P
 from . import synth
 from .data import UNCERTAIN_POLICIES, apply_uncertain
 
+BOOTSTRAP_UNITS = ("image", "study", "patient")
 ATTR_NAMES = ["Atelectasis", "Cardiomegaly", "Consolidation", "Edema", "Pleural Effusion"]     # dataset.py:25
 
 
@@ -113,6 +119,10 @@ def build_parser():
     p.add_argument("--ema_decay", type=float, default=None, metavar="D", help="exponential moving average of the weights, decay D in (0, 1)")
     p.add_argument("--no_ema_warmup", action="store_true", help="constant EMA decay (default: min(D, (1 + step) / (10 + step)))")
     p.add_argument("--use_ema", action="store_true", help="evaluate / visualise with the checkpoint's ema_state_dict")
+    p.add_argument("--bootstrap", type=int, default=0, metavar="B", help="bootstrap replicates of the AUROC intervals written beside every eval_results file (0: none)")
+    p.add_argument("--bootstrap_seed", type=int, default=None, metavar="S", help="seed of the bootstrap draws (default: --seed)")
+    p.add_argument("--bootstrap_unit", default="image", choices=list(BOOTSTRAP_UNITS), help="what the bootstrap resamples")
+    p.add_argument("--bootstrap_alpha", type=float, default=0.05, metavar="A", help="the intervals cover 1 - A (default 0.05)")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -166,7 +176,55 @@ def parse_args(argv=None):
             clahe_clip_count(args.clahe_clip, 1, 1)
         except ValueError as e:
             parser.error("--clahe: %s" % e)
+    boot, alpha, unit = getattr(args, "bootstrap", 0), getattr(args, "bootstrap_alpha", 0.05), getattr(args, "bootstrap_unit", "image")
+    if boot < 0:
+        parser.error("--bootstrap takes a number of replicates >= 0 (got %r)" % boot)
+    if not 0.0 < alpha < 1.0:
+        parser.error("--bootstrap_alpha takes a level inside (0, 1) (got %r)" % alpha)
+    if unit not in BOOTSTRAP_UNITS:
+        parser.error("--bootstrap_unit takes one of %s (got %r)" % (", ".join(BOOTSTRAP_UNITS), unit))
+    if boot > 0 and unit != "image" and getattr(args, "synthetic", 0):
+        parser.error("--bootstrap_unit %s groups the images by their file paths; --synthetic images have none (use image)" % unit)
     return args
+
+
+def auc_ci_name(tag):
+    """File name of the intervals that go with <tag>.json: eval_results_step_5 -> auc_ci_step_5.json.  It must not start with
+    `eval_results`: --plot_roc reads every file with that prefix as a compute_metrics dictionary."""
+    return "auc_ci_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ".json"
+
+
+def bootstrap_groups(args, ds):
+    """One resampling-unit id per validation row, or None for --bootstrap_unit image: the study ('.../patientN/studyK', what
+    data.extract_patient_ids returns) or the patient (that without its last path component)."""
+    unit = getattr(args, "bootstrap_unit", "image")
+    if unit == "image":
+        return None
+    if not hasattr(ds, "data"):
+        raise ValueError("--bootstrap_unit %s groups the images by their file paths; this dataset has none (use image)" % unit)
+    from .data import extract_patient_ids
+    ids = [str(v) for v in extract_patient_ids(ds, ds.data.index)]
+    return np.array(ids if unit == "study" else [v.rsplit("/", 1)[0] for v in ids])
+
+
+def write_auc_ci(args, tag, outputs, targets, groups=None):
+    """With --bootstrap B > 0: AUROC intervals of the evaluation that wrote <tag>.json, into auc_ci_<...>.json beside it, and one
+    `AUC [lo, hi]` line per class and for the mean.  Returns the path, or None (B = 0: nothing computed, allocated or written)."""
+    n_boot = getattr(args, "bootstrap", 0)
+    if n_boot <= 0:
+        return None
+    seed = getattr(args, "bootstrap_seed", None)
+    ci = M.bootstrap_auc(outputs, targets, n_boot=n_boot, seed=args.seed if seed is None else seed, groups=groups,
+                         alpha=getattr(args, "bootstrap_alpha", 0.05), device="cuda:%d" % (args.cuda or 0))
+    ci["unit"] = getattr(args, "bootstrap_unit", "image")
+    names = class_names(len(ci["aucs"]))
+    print("AUC with %g %% bootstrap intervals (%d replicates over %d %s units):" % (100 * (1 - ci["alpha"]), n_boot, ci["n_units"], ci["unit"]))
+    for c, name in enumerate(names):
+        print("  %-18s %.4f [%.4f, %.4f]" % (name, ci["aucs"][c], ci["lo"][c], ci["hi"][c]))
+    print("  %-18s %.4f [%.4f, %.4f]" % ("mean", ci["mean_auc"]["point"], ci["mean_auc"]["lo"], ci["mean_auc"]["hi"]))
+    path = os.path.join(args.output_dir, auc_ci_name(tag))
+    json.dump(ci, open(path, "w"), indent=4)
+    return path
 
 
 def make_clahe(args):
@@ -566,12 +624,16 @@ def main(argv=None):
         on = ex.get("ema_decay") is not None and args.train and model._eng().flat is not None
         return optimizer.ema_weights() if on else contextlib.nullcontext()
 
+    boot_groups = bootstrap_groups(args, valid_ds) if getattr(args, "bootstrap", 0) > 0 else None
+
     def run_eval(tag):
         with averaged():
-            res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe))
+            o, t, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe)
+        res = M.compute_metrics(o, t, l)
         if rank == 0:
             print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
             json.dump(res, open(os.path.join(args.output_dir, tag + ".json"), "w"), indent=4)
+            write_auc_ci(args, tag, o, t, boot_groups)
         return res
 
     def jitter(x_u8, step):
@@ -684,10 +746,12 @@ def main(argv=None):
             o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe)
             outs.append(o)
             losses.append(l)
-        res = M.compute_metrics(torch.stack(outs, 2).mean(2), tg, torch.stack(losses, 2).mean(2))   # mean of logits, chexpert.py:233
+        mean_out = torch.stack(outs, 2).mean(2)                                                      # mean of logits, chexpert.py:233
+        res = M.compute_metrics(mean_out, tg, torch.stack(losses, 2).mean(2))
         if rank == 0:
             json.dump(res, open(os.path.join(args.output_dir, "eval_results_ensemble.json"), "w"), indent=4)
             print("AUC:\n", pprint.pformat(res["aucs"]))
+            write_auc_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
     if args.visualize and rank == 0:
         # chexpert.py:556-563: Grad-CAM grids over the 'vis' subset (three examples per finding category), and for the
         # attention-augmented models the attention-map grids of the stored softmax weights

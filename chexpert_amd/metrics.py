@@ -69,3 +69,276 @@ def compute_metrics(outputs, targets, losses):
 def mean_auc(metrics):
     v = np.array(list(metrics["aucs"].values()), dtype=np.float64)
     return float(np.nanmean(v)) if np.any(~np.isnan(v)) else float("nan")
+
+
+# ---- bootstrap confidence intervals of the AUROC (chexpert_amd/csrc/bootstrap.hip) ------------------------------------------------
+# Rows are grouped into U resampling units (an image by default, or a study / a patient); replicate b draws U units with replacement
+# and weighs every row by the number of times its unit was drawn.  The weighted AUROC is exact in integers:
+#   num2 = sum over positives i of w_i * (LT_i + LE_i),  LT_i / LE_i = the negative weight with a score < / <= that of i
+#   AUROC = num2 / (2 W+ W-): the trapezoid area of the materialised resample, ties counted half; W+ = 0 or W- = 0: NaN (degenerate)
+# The `*_reference` functions are the numpy statement the kernels are held to bit for bit; `bootstrap_auc` itself runs on the GPU only.
+_M64 = (1 << 64) - 1
+BOOT_MAX_UNITS = 1 << 24
+BOOT_TABLE_BYTES = 256 << 20          # budget of the count table: replicates are processed in chunks that stay under it
+
+
+def splitmix64(seed, k):
+    """The draw hash: the splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 * (k + 1) mod 2^64 (what effnet.hip uses for dropout), on
+    Python ints."""
+    z = (seed + 0x9E3779B97F4A7C15 * (k + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def bootstrap_draws(n_units, b, seed):
+    """The n_units unit indices replicate b draws: unit = ((splitmix64(seed, b * U + j) >> 32) * U) >> 32, in uint64 numpy arithmetic
+    (which wraps mod 2^64 as the definition asks).  The multiply-shift favours some units by at most U / 2^32 in probability."""
+    U = int(n_units)
+    with np.errstate(over="ignore"):
+        k = np.uint64((int(b) * U) & _M64) + np.arange(U, dtype=np.uint64)
+        z = np.uint64(int(seed) & _M64) + np.uint64(0x9E3779B97F4A7C15) * (k + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+        return (((z >> np.uint64(32)) * np.uint64(U)) >> np.uint64(32)).astype(np.int64)
+
+
+def bootstrap_counts_reference(n_units, n_rep, seed, first=0):
+    """Statement of cx_boot_counts: (n_rep, n_units) uint32, row r = how often each unit is drawn by replicate first + r."""
+    U = int(n_units)
+    if not 1 <= U <= BOOT_MAX_UNITS:
+        raise ValueError("bootstrap: %d resampling units (1 .. 2^24 are supported)" % U)
+    out = np.zeros((int(n_rep), U), dtype=np.uint32)
+    for r in range(int(n_rep)):
+        out[r] = np.bincount(bootstrap_draws(U, first + r, seed), minlength=U)
+    return out
+
+
+def _as_scores(a):
+    if hasattr(a, "detach"):                    # a torch tensor: numpy has no bfloat16 (the conversion to fp32 keeps its order and ties)
+        a = a.detach().cpu()
+        a = (a.float() if str(a.dtype) in ("torch.bfloat16", "torch.float16") else a).numpy()
+    return np.asarray(a)
+
+
+def _units_of(n_rows, groups):
+    if groups is None:
+        return np.arange(n_rows, dtype=np.int64), n_rows
+    g = np.asarray(groups)
+    if g.shape != (n_rows,):
+        raise ValueError("bootstrap: groups holds %s ids for %d rows" % (g.shape, n_rows))
+    ids, inv = np.unique(g, return_inverse=True)
+    return inv.reshape(-1).astype(np.int64), int(len(ids))
+
+
+def bootstrap_plan(outputs, targets, groups=None):
+    """What cx_boot_auc reads, built once per call on the host (N log N): for every class the kept rows (target >= 0) in two orders,
+    both ascending in score (compared in the dtype given): `hi` with the negatives of a tie group before its positives, `lo` with the
+    positives first.  An entry is the row's unit index with the label (target > 0.5) in bit 31.
+    groups: one hashable id per row (data.extract_patient_ids output works); the units are the distinct ids.  None: every row its own.
+    Returns {"order": int32 (for class c: hi then lo, lens[c] entries each, from offs[c]), "offs": int64 (C), "lens": int32 (C),
+    "units": int64 (N) unit index of every row, "n_units": U}."""
+    s, t = _as_scores(outputs), np.asarray(_as_scores(targets), dtype=np.float64)
+    if s.ndim != 2 or s.shape != t.shape:
+        raise ValueError("bootstrap: outputs %s and targets %s must be (N, C) arrays of one shape" % (s.shape, t.shape))
+    if np.isnan(s).any():
+        raise ValueError("bootstrap: the scores hold NaN")
+    units, U = _units_of(s.shape[0], groups)
+    if not 1 <= U <= BOOT_MAX_UNITS:
+        raise ValueError("bootstrap: %d resampling units (1 .. 2^24 are supported)" % U)
+    parts, offs, lens, at = [], [], [], 0
+    for c in range(s.shape[1]):
+        keep = np.nonzero(t[:, c] >= 0)[0]
+        pos = t[keep, c] > 0.5
+        rank = np.unique(s[keep, c], return_inverse=True)[1].reshape(-1)
+        entry = (units[keep] | (pos.astype(np.int64) << 31)).astype(np.uint32).view(np.int32)
+        parts += [entry[np.lexsort((pos, rank))], entry[np.lexsort((~pos, rank))]]
+        offs.append(at)
+        lens.append(len(keep))
+        at += 2 * len(keep)
+    order = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+    return {"order": order.astype(np.int32), "offs": np.asarray(offs, dtype=np.int64), "lens": np.asarray(lens, dtype=np.int32),
+            "units": units, "n_units": U}
+
+
+def bootstrap_scan_reference(counts, order, offs, lens, n_units):
+    """Statement of cx_boot_auc in uint64 numpy: (num2, wpos, wneg), each (n_rep, C) uint64, num2 = S(hi) + S(lo) with
+    S(order) = sum_t p_t * (sum_{t' < t} q_t'), p / q the count of the entry's unit at a positive / negative entry; unit indices are
+    clamped to n_units - 1 as the kernel clamps them."""
+    counts = np.asarray(counts).astype(np.uint64)
+    order = np.asarray(order, dtype=np.int32)
+    R, C = counts.shape[0], len(lens)
+    num2, wpos, wneg = (np.zeros((R, C), dtype=np.uint64) for _ in range(3))
+    for c in range(C):
+        n, o = int(lens[c]), int(offs[c])
+        for k in range(2):
+            e = order[o + k * n:o + (k + 1) * n]
+            w = counts[:, np.minimum(e & 0x7fffffff, n_units - 1)]
+            p, q = np.where(e < 0, w, np.uint64(0)), np.where(e < 0, np.uint64(0), w)
+            excl = np.cumsum(q, axis=1, dtype=np.uint64) - q
+            num2[:, c] += (p * excl).sum(1, dtype=np.uint64)
+            if k == 0:
+                wpos[:, c], wneg[:, c] = p.sum(1, dtype=np.uint64), q.sum(1, dtype=np.uint64)
+    return num2, wpos, wneg
+
+
+def _definition_parts(s, t, units, counts):
+    """(num2, wpos, wneg), each (R, C) int64, straight from the definition (no `hi` / `lo` orders): the rows of a class sorted by score,
+    the negative weight accumulated along them, LE_i read at the end and LT_i before the start of row i's tie group."""
+    counts = np.asarray(counts).astype(np.int64)
+    R, C = counts.shape[0], s.shape[1]
+    num2, wpos, wneg = (np.zeros((R, C), dtype=np.int64) for _ in range(3))
+    for c in range(C):
+        keep = np.nonzero(t[:, c] >= 0)[0]
+        if not len(keep):
+            continue
+        vals, rank = np.unique(s[keep, c], return_inverse=True)
+        rank = rank.reshape(-1)
+        by = np.argsort(rank, kind="mergesort")
+        pos, r = (t[keep, c] > 0.5)[by], rank[by]
+        w = counts[:, units[keep][by]]
+        cneg = np.concatenate([np.zeros((R, 1), dtype=np.int64), np.cumsum(np.where(pos, 0, w), axis=1)], axis=1)
+        start = np.searchsorted(r, np.arange(len(vals)), side="left")      # first sorted row of every tie group
+        end = np.searchsorted(r, np.arange(len(vals)), side="right")
+        num2[:, c] = (np.where(pos, w, 0) * (cneg[:, start[r]] + cneg[:, end[r]])).sum(1)
+        wpos[:, c], wneg[:, c] = np.where(pos, w, 0).sum(1), cneg[:, -1]
+    return num2, wpos, wneg
+
+
+def _auc_of(num2, wpos, wneg):
+    """float64 num2 / (2 W+ W-): both operands are exact (below 2^53 for U <= 2^24), so this is the correctly rounded quotient."""
+    num2, den = np.asarray(num2).astype(np.float64), 2.0 * np.asarray(wpos).astype(np.float64) * np.asarray(wneg).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, num2 / np.where(den > 0, den, 1.0), np.nan)
+
+
+def _interval(v, alpha):
+    """(lo, hi, se, n_degenerate) of one column of replicates: percentiles and the ddof-1 deviation over the non-degenerate ones."""
+    ok = v[~np.isnan(v)]
+    lo, hi = (float(np.percentile(ok, 100.0 * q)) for q in (alpha / 2, 1 - alpha / 2)) if len(ok) else (float("nan"), float("nan"))
+    return lo, hi, float(np.std(ok, ddof=1)) if len(ok) > 1 else float("nan"), int(len(v) - len(ok))
+
+
+def _row_mean(a):
+    """Mean over the classes, NaN where any class is (np.mean propagates it)."""
+    return a.mean(axis=1) if a.shape[1] else np.full(a.shape[0], np.nan)
+
+
+def _summarise(point, rep, n_boot, seed, alpha, n_units, return_replicates):
+    C = rep.shape[1]
+    cols = [_interval(rep[:, c], alpha) for c in range(C)]
+    m = _interval(_row_mean(rep), alpha)
+    out = {"aucs": {c: float(point[c]) for c in range(C)}, "lo": {c: cols[c][0] for c in range(C)}, "hi": {c: cols[c][1] for c in range(C)},
+           "se": {c: cols[c][2] for c in range(C)}, "n_degenerate": {c: cols[c][3] for c in range(C)},
+           "mean_auc": {"point": float(_row_mean(point[None])[0]), "lo": m[0], "hi": m[1], "se": m[2]},
+           "n_boot": int(n_boot), "seed": int(seed), "alpha": float(alpha), "n_units": int(n_units)}
+    if return_replicates:
+        out["replicates"] = rep
+    return out
+
+
+def _p_two_sided(d):
+    ok = d[~np.isnan(d)]
+    if not len(ok):
+        return float("nan")
+    return float(min(1.0, 2.0 * min((np.sum(ok <= 0) + 1.0) / (len(ok) + 1.0), (np.sum(ok >= 0) + 1.0) / (len(ok) + 1.0))))
+
+
+def _summarise_diff(point_a, point_b, rep_a, rep_b, n_boot, seed, alpha, n_units, return_replicates):
+    C = rep_a.shape[1]
+    d = rep_a - rep_b                                         # NaN where either model's replicate is degenerate
+    cols = [_interval(d[:, c], alpha) for c in range(C)]
+    dm = _row_mean(rep_a) - _row_mean(rep_b)
+    m = _interval(dm, alpha)
+    out = {"delta": {c: float(point_a[c] - point_b[c]) for c in range(C)}, "lo": {c: cols[c][0] for c in range(C)},
+           "hi": {c: cols[c][1] for c in range(C)}, "p": {c: _p_two_sided(d[:, c]) for c in range(C)},
+           "n_degenerate": {c: cols[c][3] for c in range(C)},
+           "mean_auc": {"delta": float(_row_mean(point_a[None])[0] - _row_mean(point_b[None])[0]), "lo": m[0], "hi": m[1],
+                        "p": _p_two_sided(dm)},
+           "n_boot": int(n_boot), "seed": int(seed), "alpha": float(alpha), "n_units": int(n_units)}
+    if return_replicates:
+        out["replicates"] = d
+    return out
+
+
+def _check_boot(n_boot, alpha):
+    if int(n_boot) < 1:
+        raise ValueError("bootstrap: n_boot must be >= 1 (got %r)" % n_boot)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("bootstrap: alpha must be inside (0, 1) (got %r)" % alpha)
+
+
+def _replicates_gpu(plans, n_boot, seed, device, chunk):
+    """[(point (C), replicates (n_boot, C))] per plan, all plans over ONE count table per chunk of replicates (the paired comparison)."""
+    import torch
+
+    from . import ops
+    U = plans[0]["n_units"]
+    assert all(p["n_units"] == U for p in plans)
+    if chunk is None:
+        chunk = max(1, BOOT_TABLE_BYTES // (4 * U))
+    chunk = max(1, min(int(chunk), int(n_boot)))
+    orders = [torch.from_numpy(p["order"]).to(device) for p in plans]
+    table = torch.empty(chunk, U, dtype=torch.int32, device=device)
+    ones = torch.ones(1, U, dtype=torch.int32, device=device)
+    points = [_auc_of(*(v.cpu().numpy() for v in ops.boot_auc(ones, o, p["offs"], p["lens"], U)))[0] for p, o in zip(plans, orders)]
+    reps = [[] for _ in plans]
+    for first in range(0, int(n_boot), chunk):
+        counts = ops.boot_counts(U, min(chunk, int(n_boot) - first), seed, first=first, out=table)
+        for k, (p, o) in enumerate(zip(plans, orders)):
+            reps[k].append(_auc_of(*(v.cpu().numpy() for v in ops.boot_auc(counts, o, p["offs"], p["lens"], U))))
+    return [(pt, np.concatenate(r)) for pt, r in zip(points, reps)]
+
+
+def _replicates_reference(outputs, targets, groups, n_boot, seed):
+    s, t = _as_scores(outputs), np.asarray(_as_scores(targets), dtype=np.float64)
+    units, U = _units_of(s.shape[0], groups)
+    point = _auc_of(*_definition_parts(s, t, units, np.ones((1, U), dtype=np.int64)))[0]
+    reps = []
+    for first in range(0, int(n_boot), 64):                       # (chunks only bound the host memory: a row depends on its index alone)
+        counts = bootstrap_counts_reference(U, min(64, int(n_boot) - first), seed, first=first)
+        reps.append(_auc_of(*_definition_parts(s, t, units, counts)))
+    return point, np.concatenate(reps), U
+
+
+def bootstrap_auc(outputs, targets, n_boot=1000, seed=0, groups=None, alpha=0.05, device="cuda", chunk=None, return_replicates=False):
+    """AUROC per class with its (1 - alpha) non-parametric percentile bootstrap interval, on the GPU (cx_boot_counts + cx_boot_auc; no
+    CPU fallback).  outputs / targets: (N, C) scores and labels as compute_metrics takes them (target < 0: the row is left out of that
+    class); groups: one id per row to resample by study or patient instead of by image.  Replicates run in chunks whose count table
+    stays under 256 MB (`chunk`: replicates per chunk); the result does not depend on the chunking.  The point estimate goes through
+    the same kernel with a row of ones as counts.  Returns a json-serialisable dict, int class keys as in compute_metrics:
+      aucs; lo, hi: np.percentile at 100 alpha/2 and 100 (1 - alpha/2) over the non-degenerate replicates; se: their std (ddof 1);
+      n_degenerate: replicates without a positive or without a negative; mean_auc: {point, lo, hi, se} of the per-replicate mean over
+      the classes (NaN where any class is degenerate); n_boot, seed, alpha, n_units.
+    return_replicates: also "replicates", the (n_boot, C) float64 array (not json-serialisable)."""
+    _check_boot(n_boot, alpha)
+    plan = bootstrap_plan(outputs, targets, groups)
+    (point, rep), = _replicates_gpu([plan], n_boot, seed, device, chunk)
+    return _summarise(point, rep, n_boot, seed, alpha, plan["n_units"], return_replicates)
+
+
+def bootstrap_auc_reference(outputs, targets, n_boot=1000, seed=0, groups=None, alpha=0.05, return_replicates=False):
+    """The numpy statement of bootstrap_auc (host, integers from the definition; for the tests and as the timing yardstick)."""
+    _check_boot(n_boot, alpha)
+    point, rep, U = _replicates_reference(outputs, targets, groups, n_boot, seed)
+    return _summarise(point, rep, n_boot, seed, alpha, U, return_replicates)
+
+
+def bootstrap_auc_diff(outputs_a, outputs_b, targets, n_boot=1000, seed=0, groups=None, alpha=0.05, device="cuda", chunk=None,
+                       return_replicates=False):
+    """Paired bootstrap of the AUROC difference of two models on the same rows (one count table, two plans).  Per class and under
+    "mean_auc" for the mean over the classes: delta (a - b), lo, hi (percentiles of the replicate differences) and p, two-sided:
+    2 min((#{d* <= 0} + 1) / (B' + 1), (#{d* >= 0} + 1) / (B' + 1)) capped at 1, B' = the replicates degenerate in neither model."""
+    _check_boot(n_boot, alpha)
+    pa, pb = bootstrap_plan(outputs_a, targets, groups), bootstrap_plan(outputs_b, targets, groups)
+    (point_a, rep_a), (point_b, rep_b) = _replicates_gpu([pa, pb], n_boot, seed, device, chunk)
+    return _summarise_diff(point_a, point_b, rep_a, rep_b, n_boot, seed, alpha, pa["n_units"], return_replicates)
+
+
+def bootstrap_auc_diff_reference(outputs_a, outputs_b, targets, n_boot=1000, seed=0, groups=None, alpha=0.05, return_replicates=False):
+    """The numpy statement of bootstrap_auc_diff."""
+    _check_boot(n_boot, alpha)
+    point_a, rep_a, U = _replicates_reference(outputs_a, targets, groups, n_boot, seed)
+    point_b, rep_b, _ = _replicates_reference(outputs_b, targets, groups, n_boot, seed)
+    return _summarise_diff(point_a, point_b, rep_a, rep_b, n_boot, seed, alpha, U, return_replicates)

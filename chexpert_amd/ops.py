@@ -1160,3 +1160,49 @@ def cam_norm_upsample(cam, out, h, w):
     assert tuple(cam.shape) == (B, h * w) and out.shape[1] == 1
     _f32(cam, out)
     check(lib().cx_cam_norm_upsample(ptr(cam), ptr(out), B, h, w, H, W, stream_ptr()), "cx_cam_norm_upsample")
+
+
+# ---- bootstrap of the AUROC (bootstrap.hip) ----
+BOOT_TILE, BOOT_MAX_TILES, BOOT_MAX_UNITS = 8192, 8, 1 << 24      # CX_BOOT_TILE, CX_BOOT_MAX_TILES, CX_BOOT_MAX_UNITS of the header
+
+
+def boot_counts(n_units, n_rep, seed, first=0, out=None, device="cuda"):
+    """cx_boot_counts: rows first .. first + n_rep - 1 of the bootstrap count table as an (n_rep, n_units) int32 tensor on the GPU
+    (the kernel's uint32; a count is at most n_units <= 2^24): element [r, u] is the number of the n_units draws of replicate
+    first + r that hit unit u.  A row depends on (seed, first + r, n_units) only.  `out`: a contiguous int32 (>= n_rep, n_units)
+    tensor whose first n_rep rows are written and returned.  Up to BOOT_MAX_TILES * BOOT_TILE units a workgroup counts a tile of
+    BOOT_TILE units in LDS; above that the hits are added in device memory."""
+    n_units, n_rep, first = int(n_units), int(n_rep), int(first)
+    if out is None:
+        out = torch.empty(max(n_rep, 0), max(n_units, 0), dtype=torch.int32, device=device)
+    require_cuda(out)
+    assert out.dtype == torch.int32 and out.dim() == 2 and out.is_contiguous() and out.shape[0] >= n_rep and out.shape[1] == n_units, \
+        "out: contiguous int32 (>= n_rep, n_units)"
+    check(lib().cx_boot_counts(ptr(out), out.stride(0) if out.shape[0] else n_units, n_units, first, n_rep, int(seed) & (2 ** 64 - 1),
+                               stream_ptr()), "cx_boot_counts")
+    return out[:n_rep]
+
+
+def boot_auc(counts, order, offs, lens, n_units):
+    """cx_boot_auc: the integer parts of the weighted AUROC of every (replicate, class).  counts: int32 (n_rep, >= n_units) on the GPU
+    with unit row stride, read as uint32 (rows of boot_counts, or any non-negative weights whose row sum is < 2^32); order: int32
+    device tensor holding, for class c, the `hi` then the `lo` order of its kept rows (lens[c] entries each, from offs[c]; an entry =
+    unit index | label << 31; metrics.bootstrap_plan builds them); offs / lens: host sequences of C ints.  Returns int64 tensors
+    (n_rep, C): num2, wpos, wneg with AUROC = num2 / (2 * wpos * wneg); a class with lens[c] == 0 gives zeros."""
+    require_cuda(counts, order)
+    assert counts.dtype == torch.int32 and counts.dim() == 2 and counts.stride(1) == 1 and counts.shape[1] >= n_units, \
+        "counts: int32 (n_rep, >= n_units) rows"
+    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), "order: contiguous int32"
+    offs, lens = [int(v) for v in offs], [int(v) for v in lens]
+    n_cls, n_rep = len(lens), counts.shape[0]
+    if len(offs) != n_cls or any(n < 0 or o < 0 or o + 2 * n > order.numel() for o, n in zip(offs, lens)):
+        raise ValueError("boot_auc: offsets %s / lengths %s do not fit an order array of %d entries" % (offs, lens, order.numel()))
+    num2 = torch.empty(n_rep, n_cls, dtype=torch.int64, device=counts.device)
+    wpos = torch.empty(n_rep, n_cls, dtype=torch.int32, device=counts.device)
+    wneg = torch.empty_like(wpos)
+    if n_rep == 0:
+        return num2, wpos.long(), wneg.long()
+    ld = counts.stride(0) if n_rep > 1 else counts.shape[1]
+    check(lib().cx_boot_auc(ptr(counts), ld, n_rep, ptr(order), (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens), n_cls, ptr(num2),
+                            ptr(wpos), ptr(wneg), int(n_units), stream_ptr()), "cx_boot_auc")
+    return num2, wpos.long() & 0xffffffff, wneg.long() & 0xffffffff      # the kernel's uint32 sums

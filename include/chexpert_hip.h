@@ -736,6 +736,35 @@ int cx_u8_affine(const uint8_t* x, uint8_t* y, int B, int H, int W, const float*
 int cx_u8_clahe_lut(const uint8_t* x, uint8_t* lut, int B, int H, int W, int GY, int GX, int clip_count, void* stream);
 int cx_u8_clahe_apply(const uint8_t* x, const uint8_t* lut, uint8_t* y, int B, int H, int W, int GY, int GX, void* stream);
 
+/* Non-parametric bootstrap of the AUROC (bootstrap.hip; chexpert_amd/metrics.py: bootstrap_auc, and the numpy statement of both entry
+ * points, bootstrap_counts_reference / bootstrap_scan_reference).  Integer arithmetic throughout, held to that statement bit for bit.
+ * Rows are grouped into U resampling units (an image, a study, a patient); replicate b draws U units with replacement.  Draw j of
+ * replicate b is the splitmix64 finaliser that effnet.hip uses for dropout, scaled by a multiply-shift:
+ *   k = b * U + j (uint64);  z = seed + 0x9E3779B97F4A7C15 * (k + 1);  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31);  unit = ((z >> 32) * U) >> 32        (all mod 2^64)
+ * (the multiply-shift favours some units by at most U / 2^32 in probability: 0.4 % of 1 / U at U = 2^24, 5e-6 of it at U = 20 000).
+ * cx_boot_counts writes rows first .. first + n_rep - 1 of the count table into counts[0 .. n_rep) (row pitch ld >= U dwords):
+ * counts[r][u] = number of the U draws of replicate first + r that hit unit u; a row sums to U and depends on (seed, first + r, U)
+ * only, not on how the replicates are cut into calls.  U <= CX_BOOT_MAX_TILES * CX_BOOT_TILE: one workgroup per (replicate, tile of
+ * CX_BOOT_TILE units) counts in LDS and stores the tile; above, the rows are zeroed and the hits added in device memory.  Integer adds
+ * commute: the same bits on every run.
+ * cx_boot_auc: for class c the caller lists the kept rows (target >= 0) twice, both times ascending in score: `hi` with the negatives
+ * of a tie group before its positives, `lo` with the positives first.  An entry is the row's unit index with the label (1 = positive)
+ * in bit 31.  order (device) holds, for class c, hi then lo, len[c] entries each, from order[offs[c]]; offs and len are HOST arrays of C
+ * elements, checked here (len[c] may be 0 and differ by class).  With w = counts[r][unit], p = w at a positive entry, q = w at a
+ * negative one and S(order) = sum_t p_t * (sum_{t' < t} q_t'):
+ *   num2[r][c] = S(hi) + S(lo) = sum over positives i of w_i * (LT_i + LE_i),   LT_i / LE_i = the negative weight with a score < / <= that of i
+ *   wpos[r][c] = sum p,  wneg[r][c] = sum q;   AUROC = num2 / (2 * wpos * wneg) (formed by the caller in float64: exact operands below
+ *   2^53 for U <= 2^24, so the quotient is correctly rounded), the trapezoid area with ties counted half; wpos == 0 or wneg == 0: no AUROC.
+ * Outputs are (n_rep, C) row-major, one writer per element.  Unit indices >= U are CLAMPED to U - 1 inside the kernel, never trusted.
+ * Requirement: the sum of a count row is < 2^32 (cx_boot_counts: U).  One wave per (replicate, class); no LDS, no atomics.
+ * CX_EINVAL: a null pointer, n_rep < 1, first < 0, C < 1, a negative len[c] or offs[c].  CX_ESHAPE: U outside [1, CX_BOOT_MAX_UNITS],
+ * ld < U.  CX_EALIGN: counts / order / wpos / wneg not 4-byte, num2 not 8-byte aligned.  Additive entry points of ABI 10.          */
+enum { CX_BOOT_TILE = 8192, CX_BOOT_MAX_TILES = 8, CX_BOOT_MAX_UNITS = 1 << 24 };
+int cx_boot_counts(uint32_t* counts, int ld, int U, int first, int n_rep, uint64_t seed, void* stream);
+int cx_boot_auc(const uint32_t* counts, int ld, int n_rep, const int32_t* order /* device */, const int64_t* offs /* host, [C] */,
+                const int32_t* len /* host, [C] */, int C, uint64_t* num2, uint32_t* wpos, uint32_t* wneg, int U, void* stream);
+
 /* ---- fp32 storage mode (CX_DT_F32): the element-wise kernels of the DenseNet path with fp32 activation tensors (same arguments,
  * `const void*` tensors are fp32, pitches in elements), the fp32 weight table ([tap][O][I] fp32; descriptors with stem = 1 give
  * [49][O][4]) and the fp32 image layouts.  cx_conv_gemm / cx_conv_wgrad take CxConv.dtype / CxWgrad.dtype = CX_DT_F32.          */
