@@ -29,6 +29,13 @@
                         --lr).  Not with --pos_weight, and on one GPU only.  Evaluation keeps reporting cross-entropy element losses
   --cam_classes [C ...] with --visualize: class-specific maps (gradcam.class_cam) of the 'vis' subset for these class indices (no value
                         or `all`: every class): vis/class_cam_lowres.npy (N, K, h, w) and one vis/classcam_<ident>_step_<N>.png per image
+  --saliency METHOD     with --visualize: full-resolution, class-specific pixel attributions (chexpert_amd/saliency.py) of the 'vis' subset:
+                        grad (|d logit / d x|), smoothgrad, smoothgrad_sq or ig (integrated gradients, signed).  --saliency_classes
+                        [C ...] (as --cam_classes; default all), --saliency_steps M (path steps of ig, default 32; noise samples of
+                        smoothgrad, default 16), --saliency_sigma S (noise in whitened units; default 0.15 of the uint8 range),
+                        --saliency_baseline mean|black (ig; default mean), --saliency_chunk R (rows per pass).  Writes
+                        vis/saliency_<method>.npy (N, K, H, W) fp16, every map divided by its largest magnitude, those magnitudes in
+                        vis/saliency_<method>_scale.npy (N, K) fp32, and one vis/saliency_<method>_<ident>_step_<N>.png per image
   --synthetic_uncertain F   that fraction of the synthetic training labels is uncertain (the policy above then applies)
   --clip_grad_norm X    clip the gradient to global L2 norm X inside the fused optimiser step (needs --fused_optimizer, as the next three)
   --skip_nonfinite      drop the update of a minibatch whose gradient norm is inf or NaN (it still counts for the schedule)
@@ -114,6 +121,12 @@ def build_parser():
     p.add_argument("--synthetic_uncertain", type=float, default=0.0, metavar="F", help="fraction of the synthetic training labels marked uncertain")
     p.add_argument("--cam_classes", nargs="*", default=None, metavar="CLASS",
                    help="with --visualize: class-specific maps (gradcam.class_cam) of these class indices; no value or `all` = every class")
+    p.add_argument("--saliency", default=None, choices=list(SALIENCY_METHODS), help="with --visualize: pixel attribution maps of the 'vis' subset")
+    p.add_argument("--saliency_classes", nargs="*", default=None, metavar="CLASS", help="class indices of --saliency; no value or `all` = every class (default)")
+    p.add_argument("--saliency_steps", type=int, default=None, metavar="M", help="path steps of ig (default 32) / noise samples of smoothgrad (default 16)")
+    p.add_argument("--saliency_sigma", type=float, default=None, metavar="S", help="noise of smoothgrad in whitened units (default: 0.15 of the uint8 range)")
+    p.add_argument("--saliency_baseline", default=None, choices=["mean", "black"], help="baseline of ig: the dataset mean grey (default) or black")
+    p.add_argument("--saliency_chunk", type=int, default=None, metavar="R", help="rows per forward + backward pass of --saliency")
     p.add_argument("--clip_grad_norm", type=float, default=None, metavar="X", help="global-norm gradient clipping in the fused optimiser step")
     p.add_argument("--skip_nonfinite", action="store_true", help="drop the update of a minibatch whose gradient is not finite")
     p.add_argument("--ema_decay", type=float, default=None, metavar="D", help="exponential moving average of the weights, decay D in (0, 1)")
@@ -338,6 +351,53 @@ def resolve_cam_classes(spec, n_classes):
     return classes
 
 
+SALIENCY_METHODS = ("grad", "smoothgrad", "smoothgrad_sq", "ig")
+
+
+def resolve_saliency(args):
+    """--saliency and its options as a dictionary {method, classes, steps, sigma, baseline, chunk}, or None when no --saliency* flag
+    is given.  Refused here (ValueError), before anything is built: an option without --saliency, --saliency without --visualize, class
+    indices out of range, steps or chunk <= 0, a negative sigma, an option that the method does not take."""
+    method = getattr(args, "saliency", None)
+    opts = {k: getattr(args, "saliency_" + k, None) for k in ("classes", "steps", "sigma", "baseline", "chunk")}
+    given = [k for k, v in opts.items() if v is not None]
+    if method is None:
+        if given:
+            raise ValueError("--saliency_%s belongs to --saliency METHOD: pass it too" % given[0])
+        return None
+    if method not in SALIENCY_METHODS:
+        raise ValueError("--saliency takes one of %s (got %r)" % (", ".join(SALIENCY_METHODS), method))
+    if not args.visualize:
+        raise ValueError("--saliency draws attribution maps over the 'vis' subset: pass --visualize with it")
+    try:
+        classes = resolve_cam_classes(opts["classes"] if opts["classes"] is not None else [], args.n_classes)
+    except ValueError as e:
+        raise ValueError(str(e).replace("--cam_classes", "--saliency_classes")) from None
+    steps = opts["steps"]
+    if steps is not None and (method == "grad" or steps <= 0):
+        raise ValueError("--saliency_steps takes a number >= 1 of path steps (ig) or noise samples (smoothgrad) (got %r with %s)" % (steps, method))
+    if opts["sigma"] is not None and (not method.startswith("smoothgrad") or not opts["sigma"] >= 0):
+        raise ValueError("--saliency_sigma is the noise >= 0 of smoothgrad / smoothgrad_sq (got %r with %s)" % (opts["sigma"], method))
+    if opts["baseline"] is not None and method != "ig":
+        raise ValueError("--saliency_baseline belongs to --saliency ig (got it with %s)" % method)
+    if opts["chunk"] is not None and opts["chunk"] <= 0:
+        raise ValueError("--saliency_chunk takes a number of rows >= 1 (got %r)" % opts["chunk"])
+    return {"method": method, "classes": classes, "steps": steps if steps is not None else (32 if method == "ig" else 16),
+            "sigma": opts["sigma"], "baseline": opts["baseline"] or "mean", "chunk": opts["chunk"]}
+
+
+def saliency_maps(model, x, sal):
+    """The (B,K,H,W) maps of --saliency for a whitened (B,3,H,W) batch on the GPU: grad, smoothgrad and smoothgrad_sq as the sum of
+    the channels' magnitudes, ig signed (the sum over the channels, whose pixel sum is the completeness identity's left side)."""
+    from . import saliency as S
+    m, cl, ch = sal["method"], sal["classes"], sal["chunk"]
+    if m == "grad":
+        return S.input_gradient(model, x, cl, channels="abs")
+    if m == "ig":
+        return S.integrated_gradients(model, x, cl, steps=sal["steps"], baseline=None if sal["baseline"] == "mean" else "black", chunk=ch)[0]
+    return S.smoothgrad(model, x, cl, samples=sal["steps"], sigma=sal["sigma"], squared=m == "smoothgrad_sq", chunk=ch)
+
+
 def optimizer_options(args):
     """--clip_grad_norm / --skip_nonfinite / --ema_decay / --no_ema_warmup as keyword arguments of the fused optimisers ({}: all off)."""
     clip, skip, ema = getattr(args, "clip_grad_norm", None), getattr(args, "skip_nonfinite", False), getattr(args, "ema_decay", None)
@@ -521,6 +581,7 @@ def main(argv=None):
     cam_classes = resolve_cam_classes(getattr(args, "cam_classes", None), args.n_classes)
     if cam_classes is not None and not args.visualize:
         raise ValueError("--cam_classes draws class maps over the 'vis' subset: pass --visualize with it")
+    sal = resolve_saliency(args)
     rank, world, local = P.dist_info()
     aucm = aucm_options(args, world)
     if world > 1:
@@ -761,7 +822,7 @@ def main(argv=None):
         groups = vis.select_vis_subset(valid_ds.targets, names)
         flat = sorted({i for g in groups[1] for i in g})
         pos = {i: k for k, i in enumerate(flat)}
-        imgs, labels, scores, masks, class_maps = [], [], [], [], []
+        imgs, labels, scores, masks, class_maps, sal_maps = [], [], [], [], [], []
         model.eval()
         attn_layers = [m for m in model.modules() if type(m).__name__ == "AAConv2d"]
         for x, tg, idx in batches(valid_ds, flat, args.batch_size, False):
@@ -774,6 +835,9 @@ def main(argv=None):
             masks.append(grad_cam(model, xd).float().cpu())
             if cam_classes is not None:         # the raw low-resolution relu(M): up-sampled maps of 14 classes would be hundreds of MB
                 class_maps.append(class_cam(model, xd, cam_classes, normalize=False, upsample=False)[0].cpu())
+            if sal is not None:                 # float interface: whitened, three identical channels (as the attention figures below)
+                xf = ((xd.float().div(255.0) - vis.MEAN) / vis.STD).expand(-1, 3, -1, -1) if xd.dtype == torch.uint8 else xd.float()
+                sal_maps.append(saliency_maps(model, xf.contiguous(), sal).cpu())
             imgs.append(x.float().div(255.0)[:, 0] if x.dtype == torch.uint8 else (x.float()[:, 0] * vis.STD + vis.MEAN))
             labels.append(tg)
             if attn_layers:
@@ -793,6 +857,17 @@ def main(argv=None):
                                           names, cam_classes, args.output_dir, getattr(args, "step", 0))
             np.save(os.path.join(args.output_dir, "vis", "class_cam_lowres.npy"), class_maps.numpy())
             print("class maps:", tuple(class_maps.shape), "figures:", len(files))
+        if sal is not None:
+            sal_maps = torch.cat(sal_maps)
+            files = vis.visualize_saliency(imgs.numpy(), labels.numpy(), scores.numpy(), sal_maps.numpy(), ["synthetic/%d" % i for i in flat],
+                                           names, sal["classes"], sal["method"], args.output_dir, getattr(args, "step", 0),
+                                           signed=sal["method"] == "ig")
+            # fp16 on disk: every map divided by its largest magnitude (gradients of a logit per pixel are far below fp16's range)
+            scale = sal_maps.abs().amax((2, 3))
+            np.save(os.path.join(args.output_dir, "vis", "saliency_%s.npy" % sal["method"]),
+                    (sal_maps / scale.clamp_min(1e-30)[:, :, None, None]).numpy().astype(np.float16))
+            np.save(os.path.join(args.output_dir, "vis", "saliency_%s_scale.npy" % sal["method"]), scale.numpy())
+            print("saliency (%s) maps:" % sal["method"], tuple(sal_maps.shape), "figures:", len(files))
     if args.plot_roc and rank == 0:
         files = [f for f in os.listdir(args.output_dir) if f.startswith("eval_results") and f.endswith(".json")]
         if not files:

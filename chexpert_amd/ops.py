@@ -1206,3 +1206,87 @@ def boot_auc(counts, order, offs, lens, n_units):
     check(lib().cx_boot_auc(ptr(counts), ld, n_rep, ptr(order), (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens), n_cls, ptr(num2),
                             ptr(wpos), ptr(wneg), int(n_units), stream_ptr()), "cx_boot_auc")
     return num2, wpos.long() & 0xffffffff, wneg.long() & 0xffffffff      # the kernel's uint32 sums
+
+
+# ---- pixel attribution maps (saliency.hip; chexpert_amd/saliency.py composes them and states them in numpy) ----
+SAL_MODES = {"none": 0, "sum": 1, "abs": 2, "max": 3}      # CX_SAL_NONE .. CX_SAL_MAX of the header
+SAL_PARTIALS = 128                                          # CX_SAL_PARTIALS
+
+
+def _sal_images(t, what):
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4 and t.shape[1] == 3, "%s: contiguous fp32 (.,3,H,W)" % what
+    return t.shape[0], t.shape[2], t.shape[3]
+
+
+def _sal_table(t, dtype, n, what):
+    assert t.dtype == dtype and t.is_contiguous() and t.numel() == n, "%s: contiguous %s of %d entries" % (what, dtype, n)
+
+
+def _sal_base(base, x):
+    """(full baseline or None, the three per-channel constants) of a baseline given as a (B,3,H,W) tensor or as three floats."""
+    if isinstance(base, torch.Tensor):
+        assert base.shape == x.shape, "a full baseline has the input's shape"
+        _sal_images(base, "base")
+        return base, (0.0, 0.0, 0.0)
+    b = tuple(float(v) for v in base)
+    assert len(b) == 3, "a constant baseline is three floats, one per channel"
+    return None, b
+
+
+def sal_points(x, base, img, alpha, out=None, *, sigma=None, seed=0, first_row=0):
+    """cx_sal_points: out (R,3,H,W) = base[img[r]] + alpha[r] * (x[img[r]] - base[img[r]]) [+ sigma[img[r]] * n(seed, first_row + r, .)],
+    every product and sum rounded on its own.  x: fp32 (B,3,H,W); base: a tensor of x's shape or three per-channel floats; img int32 (R,),
+    alpha fp32 (R,), sigma None or fp32 (B,), all on the device."""
+    require_cuda(x, img, alpha, sigma, out)
+    B, H, W = _sal_images(x, "x")
+    R = img.numel()
+    _sal_table(img, torch.int32, R, "img")
+    _sal_table(alpha, torch.float32, R, "alpha")
+    if sigma is not None:
+        _sal_table(sigma, torch.float32, B, "sigma")
+    full, const = _sal_base(base, x)
+    require_cuda(full)
+    if out is None:
+        out = torch.empty(R, 3, H, W, dtype=torch.float32, device=x.device)
+    assert _sal_images(out, "out") == (R, H, W)
+    check(lib().cx_sal_points(ptr(x), ptr(full), const[0], const[1], const[2], ptr(img), ptr(alpha), ptr(sigma), int(seed) & (2 ** 64 - 1),
+                              int(first_row) & (2 ** 64 - 1), ptr(out), B, R, H, W, stream_ptr()), "cx_sal_points")
+    return out
+
+
+def sal_accumulate(g, slot, w, acc, *, square=False, accumulate=True):
+    """cx_sal_accumulate: acc (P,3,H,W) = (acc if accumulate else 0) + sum over the rows r with slot[r] == p, in ascending order, of
+    w[r] * (g[r]^2 if square else g[r]).  g: fp32 (R,3,H,W); slot int32 (R,), w fp32 (R,) on the device."""
+    require_cuda(g, slot, w, acc)
+    R, H, W = _sal_images(g, "g")
+    P, Ha, Wa = _sal_images(acc, "acc")
+    assert (Ha, Wa) == (H, W), "acc and g share H and W"
+    _sal_table(slot, torch.int32, R, "slot")
+    _sal_table(w, torch.float32, R, "w")
+    check(lib().cx_sal_accumulate(ptr(g), ptr(slot), ptr(w), ptr(acc), R, P, H, W, int(bool(square)), int(bool(accumulate)), stream_ptr()),
+          "cx_sal_accumulate")
+    return acc
+
+
+def sal_finish(acc, x=None, base=(0.0, 0.0, 0.0), img_of=None, *, times_input=False, channels="none", total=False):
+    """cx_sal_finish: a = acc * (x[img_of[p]] - base[img_of[p]]) with times_input, else acc; the map (P,3,H,W) for channels "none",
+    else (P,H,W): "sum" (a0 + a1) + a2, "abs" (|a0| + |a1|) + |a2|, "max" the largest |a_c|.  Returns (map, total): total is None, or
+    with total=True the float64 (P,) sums of a over each plane."""
+    require_cuda(acc, x, img_of)
+    if channels not in SAL_MODES:
+        raise ValueError("sal_finish: channels is one of %s (got %r)" % (", ".join(SAL_MODES), channels))
+    P, H, W = _sal_images(acc, "acc")
+    B, full, const = 0, None, (0.0, 0.0, 0.0)
+    if times_input:
+        B, Hx, Wx = _sal_images(x, "x")
+        assert (Hx, Wx) == (H, W), "acc and x share H and W"
+        _sal_table(img_of, torch.int32, P, "img_of")
+        full, const = _sal_base(base, x)
+        require_cuda(full)
+    out = torch.empty((P, 3, H, W) if channels == "none" else (P, H, W), dtype=torch.float32, device=acc.device)
+    tot = torch.empty(P, dtype=torch.float64, device=acc.device) if total else None
+    part = torch.empty(P * SAL_PARTIALS, dtype=torch.float64, device=acc.device) if total else None
+    check(lib().cx_sal_finish(ptr(acc), ptr(x) if times_input else None, ptr(full), const[0], const[1], const[2],
+                              ptr(img_of) if times_input else None, ptr(out), ptr(tot), ptr(part), P, B, H, W, int(bool(times_input)),
+                              SAL_MODES[channels], stream_ptr()), "cx_sal_finish")
+    return out, tot

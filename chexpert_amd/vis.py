@@ -144,3 +144,42 @@ def visualize_classes(imgs, labels, logits, cams, idents, attr_names, classes, o
         plt.close(fig)
         written.append(path)
     return written
+
+
+def visualize_saliency(imgs, labels, logits, maps, idents, attr_names, classes, method, out_dir, step, signed=False):
+    """Pixel attribution figures (chexpert_amd.saliency): imgs (N,H,W) in [0,1], labels (N,C), logits (N,C), maps (N,K,H,W) the
+    full-resolution maps of the K classes `classes` (indices into attr_names).  One figure per image,
+    vis/saliency_<method>_<ident>_step_<step>.png: the radiograph, then one overlay per class titled as in `visualize_classes`.
+    The display scaling happens here, on the host, per map: its 99.5th percentile of |map| is the end of the colour range (a single
+    hot pixel does not flatten the rest); signed maps (integrated gradients) get a symmetric diverging colour map around zero,
+    unsigned ones a sequential one from zero."""
+    plt = _plt()
+    os.makedirs(os.path.join(out_dir, "vis"), exist_ok=True)
+    probs = 1.0 / (1.0 + np.exp(-np.asarray(logits, dtype=np.float64)))
+    maps = np.asarray(maps, dtype=np.float64)
+    K = len(classes)
+    assert maps.ndim == 4 and maps.shape[1] == K and maps.shape[2:] == imgs.shape[1:], "maps: (N, K, H, W), one map per requested class"
+    H, W = imgs.shape[1], imgs.shape[2]
+    written = []
+    for i in range(len(imgs)):
+        fig, axs = plt.subplots(1, K + 1, figsize=((K + 1) * max(W, 128) / 100, 1.3 * max(H, 128) / 100), dpi=100, frameon=False, squeeze=False)
+        axs = axs[0]
+        axs[0].set_title("%s\nOriginal image" % idents[i], fontsize=10)
+        axs[0].imshow(imgs[i], cmap="gray")
+        for k, c in enumerate(classes):
+            m = maps[i, k]
+            top = float(np.percentile(np.abs(m), 99.5))
+            top = top if top > 0 else (float(np.abs(m).max()) or 1.0)
+            axs[k + 1].set_title("%s\nlabel %g, prob. %.4f" % (attr_names[c], float(labels[i][c]), probs[i][c]), fontsize=10)
+            axs[k + 1].imshow(imgs[i], cmap="gray")
+            if signed:
+                axs[k + 1].imshow(m, cmap="seismic", vmin=-top, vmax=top, alpha=0.6)
+            else:
+                axs[k + 1].imshow(np.abs(m), cmap="inferno", vmin=0.0, vmax=top, alpha=0.6)
+        for ax in axs:
+            ax.axis("off")
+        path = os.path.join(out_dir, "vis", "saliency_%s_%s_step_%d.png" % (method, str(idents[i]).replace("/", "_").replace(" ", "_"), step))
+        plt.savefig(path, dpi=100)
+        plt.close(fig)
+        written.append(path)
+    return written

@@ -765,6 +765,41 @@ int cx_boot_counts(uint32_t* counts, int ld, int U, int first, int n_rep, uint64
 int cx_boot_auc(const uint32_t* counts, int ld, int n_rep, const int32_t* order /* device */, const int64_t* offs /* host, [C] */,
                 const int32_t* len /* host, [C] */, int C, uint64_t* num2, uint32_t* wpos, uint32_t* wneg, int U, void* stream);
 
+/* Pixel attribution maps (saliency.hip; chexpert_amd/saliency.py: input_gradient, smoothgrad, integrated_gradients, and the numpy
+ * statement of the three entry points, points_reference / accumulate_reference / finish_reference): the glue around the eval-mode
+ * forward + backward with dx.  fp32 NCHW, N = 3 * H * W floats per row; every product and every sum below is rounded to fp32 on its
+ * own (nothing is contracted into a fused multiply-add), so the results are those of the numpy statement bit for bit -- the noise
+ * term excepted, whose logf / cospif are the device's.  One writer per output element, no atomics: the same bits on every run.
+ * cx_sal_points writes out (R,3,H,W), the rows the network is evaluated at.  With b = img[r] (device table, clamped into [0, B)) and
+ * base[b][e] = the full baseline (B,3,H,W), or, base == NULL, the constant base0 / base1 / base2 of e's channel:
+ *   d = x[b][e] - base[b][e];   v = base[b][e] + alpha[r] * d;
+ *   out[r][e] = v                                                     (sigma == NULL)
+ *   out[r][e] = v + sigma[b] * n(seed, (first_row + r) * N + e)       (sigma: device table, one fp32 per image)
+ * Baseline 0 and alpha 1 give x exactly.  n(seed, k) is one standard normal per hash, so a row's noise depends on (seed, first_row + r)
+ * only and not on how the rows are cut into calls.  With z = the splitmix64 hash of cx_boot_counts above (z = seed + 0x9E37... * (k + 1), ...):
+ *   u1 = ((z >> 40) + 1) * 2^-24;   u2 = ((z >> 8) & 0xFFFFFF) * 2^-24;   n = sqrtf(-2 * logf(u1)) * cospif(2 * u2)       (|n| <= 5.77)
+ * cx_sal_accumulate folds the input gradients g (R,3,H,W) of a pass into acc (P,3,H,W).  Per element of plane p: a = acc (accumulate
+ * != 0) or 0; for r = 0 .. R - 1 in this order, where slot[r] == p: t = g[r] (square == 0) or g[r] * g[r]; a = a + w[r] * t; acc = a.
+ * slot (int32) and w (fp32) are device tables of R entries; a slot outside [0, P) belongs to no plane.
+ * cx_sal_finish turns the sums into maps.  a[p][c] = acc[p][c] (times_input == 0) or acc[p][c] * (x[b][c] - base[b][c]) with
+ * b = img_of[p] (device table, clamped into [0, B)) and the baseline as above.  mode CX_SAL_NONE: out (P,3,H,W) = a; the others give
+ * out (P,H,W): CX_SAL_SUM (a0 + a1) + a2, CX_SAL_ABS (|a0| + |a1|) + |a2|, CX_SAL_MAX max(max(|a0|, |a1|), |a2|).  total != NULL:
+ * total[p] (double) = the sum of a over the 3 H W elements of plane p (the left side of the completeness identity of integrated
+ * gradients), accumulated in double in two fixed stages: CX_SAL_PARTIALS workgroup sums per plane into partial (P * CX_SAL_PARTIALS
+ * doubles, the caller's), then their sum in ascending order.
+ * Any H, W >= 1 (one float4 per lane where N % 4 == 0 -- finish: H W % 4 == 0 -- and the tensors are 16-byte aligned, one float
+ * otherwise).  CX_EINVAL before anything is launched: a null pointer (base, sigma, total always may be null; x, img_of when
+ * times_input == 0; partial when total is), B, R, P, H or W <= 0, an output that aliases an input, total without partial.
+ * CX_ESHAPE: H * W >= 2^29, R or P > 65535, an unknown mode.  CX_EALIGN: a pointer that is not 4-byte (total, partial: 8-byte) aligned.
+ * Additive entry points of ABI 10.                                                                                              */
+enum { CX_SAL_NONE = 0, CX_SAL_SUM = 1, CX_SAL_ABS = 2, CX_SAL_MAX = 3, CX_SAL_PARTIALS = 128 };
+int cx_sal_points(const float* x, const float* base, float base0, float base1, float base2, const int32_t* img, const float* alpha,
+                  const float* sigma, uint64_t seed, uint64_t first_row, float* out, int B, int R, int H, int W, void* stream);
+int cx_sal_accumulate(const float* g, const int32_t* slot, const float* w, float* acc, int R, int P, int H, int W, int square,
+                      int accumulate, void* stream);
+int cx_sal_finish(const float* acc, const float* x, const float* base, float base0, float base1, float base2, const int32_t* img_of,
+                  float* out, double* total, double* partial, int P, int B, int H, int W, int times_input, int mode, void* stream);
+
 /* ---- fp32 storage mode (CX_DT_F32): the element-wise kernels of the DenseNet path with fp32 activation tensors (same arguments,
  * `const void*` tensors are fp32, pitches in elements), the fp32 weight table ([tap][O][I] fp32; descriptors with stem = 1 give
  * [49][O][4]) and the fp32 image layouts.  cx_conv_gemm / cx_conv_wgrad take CxConv.dtype / CxWgrad.dtype = CX_DT_F32.          */
