@@ -102,6 +102,8 @@ SIGNATURES = {
     "cx_u8_to_nhwc4_f32": [_vp, _vp, _sz, _f, _f, _vp],
     "cx_u8_jitter": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "cx_u8_affine": [_vp, _vp, _i, _i, _i, _vp, _i, _vp],
+    "cx_u8_mix": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
+    "cx_target_mix": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "cx_u8_clahe_lut": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "cx_u8_clahe_apply": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "cx_bn_coef_eval": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp],

@@ -41,6 +41,23 @@ limit c >= 0 (`//` is floor division):
       y[b][i][j] = (num + 2*th*tw) // (4*th*tw)
 
 GY = GX = 1 with c = 0 is plain global histogram equalisation.
+
+Sample mixing (Mixup, CutMix, random erasing: `cx_u8_mix` + `cx_target_mix`, chexpert_amd/csrc/mix.hip; `ops.u8_mix`,
+`ops.target_mix`) is the LAST step on the uint8 batch: the per-sample transforms above come first and the collated batch is mixed
+afterwards, as timm does.  A plan is four int32 arrays, perm (B,), lam_q (B,), box (B, 4) = y0 y1 x0 x1 and tw_q (B,); `mix_plan` and
+`erase_plan` draw one, `mix_reference` / `target_mix_reference` state what the kernels make of it (bit for bit, `//`-free integers
+and separately rounded fp32):
+
+    p = clamp(perm[b], -1, B-1);  q = clamp(lam_q[b], 0, 65536);  y0, y1 clamped to [0, H];  x0, x1 clamped to [0, W]
+    pixel (i, j), a = x[b][i][j]:   outside rows [y0, y1) x columns [x0, x1):  y = a
+                                    inside:  o = fill if p < 0 else x[p][i][j];  y = (q*a + (65536 - q)*o + 32768) >> 16
+    targets, w_q = clamp(tw_q[b], 0, 65536), w = w_q / 65536 (w and 1 - w exact in fp32):
+      p < 0 or w_q == 65536:            out[b][c] = t[b][c]
+      else t[b][c] < 0 or t[p][c] < 0:  out[b][c] = -1          (a label the loss ignores stays ignored)
+      else:                             out[b][c] = fl(fl(w * t[b][c]) + fl((1 - w) * t[p][c]))
+
+Mixup: box = the image, lam_q = tw_q = round(65536 lambda).  CutMix: a partial box, lam_q = 0, tw_q = the share of the row's own
+pixels.  Erasing: perm = -1, lam_q = 0, tw_q = 65536 (labels do not change).
 """
 import math
 
@@ -58,6 +75,17 @@ def step_seed(step, rank=0):
     another offset: a run is reproducible, the ranks draw different transforms, and the warp does not share its numbers with the
     jitter of the same step."""
     return int(step) * 7919 + 4001 + int(rank)
+
+
+def mix_seed(step, rank=0):
+    """step_seed's sibling for the --mixup / --cutmix plan of minibatch `step`: an offset of its own, so the mix shares no numbers
+    with the erase, the warp or the jitter of the same step (the offsets stay below the 7919 between two steps)."""
+    return int(step) * 7919 + 2003 + int(rank)
+
+
+def erase_seed(step, rank=0):
+    """step_seed's sibling for the --erase_prob plan of minibatch `step`."""
+    return int(step) * 7919 + 6007 + int(rank)
 
 
 def tta_seed_of(tta_seed, draw, batch):
@@ -241,3 +269,197 @@ class Clahe:
         if x_u8.dtype != torch.uint8:
             raise RuntimeError("CLAHE equalises the decoded uint8 images (got %s)" % x_u8.dtype)
         return ops.u8_clahe(x_u8, self.grid, self.clip_limit, out)
+
+
+# ---- sample mixing: Mixup, CutMix, random erasing ----------------------------------------------------------------------------------
+MIX_ONE = 65536              # lambda = 1 in the 16-bit fixed point of lam_q / tw_q
+ERASE_FILL = 136             # the dataset mean 0.5330 in grey levels
+
+
+def _identity_plan(B):
+    import numpy as np
+    return {"perm": np.arange(B, dtype=np.int32), "lam_q": np.full(B, MIX_ONE, np.int32), "box": np.zeros((B, 4), np.int32),
+            "tw_q": np.full(B, MIX_ONE, np.int32)}
+
+
+def mix_plan(seed, B, H, W, mixup_alpha=0.0, cutmix_alpha=0.0, prob=1.0, switch_prob=0.5, mode="batch"):
+    """The Mixup / CutMix plan of one minibatch as int32 numpy arrays {perm (B,), lam_q (B,), box (B,4), tw_q (B,)}, with the
+    semantics of timm's `Mixup`: with probability 1 - prob nothing is mixed; with both alphas > 0 CutMix is chosen with probability
+    switch_prob; mode "batch" draws once for the minibatch, "elem" once per row.  A pure function of its arguments:
+      perm     argsort (stable) of synth.uniform(seed, (B,)); fixed points are allowed (a row mixed with itself is unchanged)
+      lambda   Beta(alpha, alpha) from numpy.random.RandomState(seed mod 2^32) (the legacy stream, which NumPy keeps frozen): n draws
+               at mixup_alpha where it is > 0, then n at cutmix_alpha where it is > 0 (n = 1 or B)
+      u        counters B .. B + 4n - 1 of the same synth.uniform stream, in [0, 1): rows `apply`, `switch`, `cy`, `cx`
+      a draw is mixed where u_apply < prob, and is a CutMix where only cutmix_alpha > 0, or both are and u_switch < switch_prob
+      Mixup    lam_q = tw_q = floor(65536 lambda + 0.5), box = the image
+      CutMix   timm's rand_bbox: r = sqrt(1 - lambda), cut = int(H r) x int(W r) about the centre (int(u_cy H), int(u_cx W)), clipped
+               to the image; lam_q = 0; tw_q = ((HW - area) * 131072 + HW) // (2 HW), the share of the row's own pixels rounded half
+               up to 16 bits
+    B = 0, both alphas 0, prob = 0, or no draw that is mixed give the identity plan (perm = 0..B-1, lam_q = tw_q = 65536, empty boxes)."""
+    import numpy as np
+    B, H, W = int(B), int(H), int(W)
+    ma, ca = float(mixup_alpha), float(cutmix_alpha)
+    if mode not in ("batch", "elem"):
+        raise ValueError("mix_plan: mode is batch or elem (got %r)" % (mode,))
+    if ma < 0 or ca < 0 or not (0.0 <= float(prob) <= 1.0 and 0.0 <= float(switch_prob) <= 1.0):
+        raise ValueError("mix_plan: alphas >= 0 and probabilities in [0, 1] (got %r, %r, %r, %r)" % (mixup_alpha, cutmix_alpha, prob, switch_prob))
+    plan = _identity_plan(B)
+    if B == 0 or (ma == 0 and ca == 0):
+        return plan
+    n = 1 if mode == "batch" else B
+    plan["perm"] = np.argsort(synth.uniform(seed, (B,)).numpy(), kind="stable").astype(np.int32)
+    rs = np.random.RandomState(int(seed) % (1 << 32))
+    lam_mix = rs.beta(ma, ma, n) if ma > 0 else np.ones(n)
+    lam_cut = rs.beta(ca, ca, n) if ca > 0 else np.ones(n)
+    u = synth.uniform(seed, (B + 4 * n,), 0.0, 1.0, dtype=torch.float64).numpy()[B:].reshape(4, n)
+    apply = u[0] < float(prob)
+    if not apply.any():
+        return _identity_plan(B)
+    cut = np.full(n, ma == 0) if (ma == 0 or ca == 0) else u[1] < float(switch_prob)
+    lam_q = np.full(n, MIX_ONE, np.int64)
+    tw_q = np.full(n, MIX_ONE, np.int64)
+    box = np.zeros((n, 4), np.int64)
+    for k in range(n):
+        if not apply[k]:
+            continue
+        if cut[k]:
+            r = math.sqrt(max(0.0, 1.0 - float(lam_cut[k])))
+            ch, cw = int(H * r), int(W * r)
+            cy, cx = int(u[2, k] * H), int(u[3, k] * W)
+            y0, y1 = min(max(cy - ch // 2, 0), H), min(max(cy + ch // 2, 0), H)
+            x0, x1 = min(max(cx - cw // 2, 0), W), min(max(cx + cw // 2, 0), W)
+            area = (y1 - y0) * (x1 - x0)
+            box[k] = (y0, y1, x0, x1)
+            lam_q[k] = 0
+            tw_q[k] = ((H * W - area) * 131072 + H * W) // (2 * H * W)
+        else:
+            lam_q[k] = tw_q[k] = min(max(int(math.floor(65536.0 * float(lam_mix[k]) + 0.5)), 0), MIX_ONE)
+            box[k] = (0, H, 0, W)
+    rows = np.zeros(B, np.int64) if n == 1 else np.arange(B)
+    plan["lam_q"], plan["tw_q"], plan["box"] = lam_q[rows].astype(np.int32), tw_q[rows].astype(np.int32), box[rows].astype(np.int32)
+    return plan
+
+
+def erase_plan(seed, B, H, W, prob=0.25, area=(0.02, 1.0 / 3.0), aspect=(0.3, 3.3), attempts=10):
+    """The random-erasing plan of one minibatch (same arrays as mix_plan), drawn as torchvision's `RandomErasing.get_params`: a row
+    is erased where u < prob; then up to `attempts` tries of an area fraction uniform in `area` and an aspect ratio log-uniform in
+    `aspect`, h = int(round(sqrt(A r))), w = int(round(sqrt(A / r))) with A the fraction times H W; the first try with h < H and
+    w < W is taken, top uniform in [0, H - h], left uniform in [0, W - w] (none fits: the row stays).  The numbers are
+    synth.uniform(seed, (B, 1 + 4 * attempts)) in [0, 1).  Erased rows get perm = -1 (the kernel writes `fill`) and their box; the
+    others keep perm = b and an empty box; lam_q = 0 and tw_q = 65536 everywhere: labels do not change."""
+    import numpy as np
+    B, H, W, attempts = int(B), int(H), int(W), int(attempts)
+    if not 0.0 <= float(prob) <= 1.0:
+        raise ValueError("erase_plan: prob in [0, 1] (got %r)" % (prob,))
+    plan = _identity_plan(B)
+    plan["lam_q"][:] = 0
+    if B == 0 or float(prob) == 0.0:
+        return plan
+    u = synth.uniform(seed, (B, 1 + 4 * attempts), 0.0, 1.0, dtype=torch.float64).numpy()
+    la0, la1 = math.log(float(aspect[0])), math.log(float(aspect[1]))
+    for b in range(B):
+        if not u[b, 0] < float(prob):
+            continue
+        for k in range(attempts):
+            ua, ur, ut, ul = u[b, 1 + 4 * k:5 + 4 * k]
+            A = H * W * (float(area[0]) + ua * (float(area[1]) - float(area[0])))
+            r = math.exp(la0 + ur * (la1 - la0))
+            h, w = int(round(math.sqrt(A * r))), int(round(math.sqrt(A / r)))
+            if not (h < H and w < W):
+                continue
+            top, left = int(ut * (H - h + 1)), int(ul * (W - w + 1))
+            plan["perm"][b] = -1
+            plan["box"][b] = (top, top + h, left, left + w)
+            break
+    return plan
+
+
+def _np(v):
+    import numpy as np
+    return np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
+
+
+def mix_reference(x, perm, lam_q, box, fill=0):
+    """cx_u8_mix's definition (module docstring) in numpy int64 on the CPU, clamps included: x uint8 (B,1,H,W) / (B,H,W); returns the
+    same shape, uint8 (a torch tensor).  Used by the tests and by nothing else."""
+    import numpy as np
+    xs = _np(x)
+    shape, H, W = xs.shape, xs.shape[-2], xs.shape[-1]
+    a = xs.reshape(-1, H, W).astype(np.int64)
+    B = a.shape[0]
+    p = np.clip(_np(perm).astype(np.int64).reshape(B), -1, B - 1)
+    q = np.clip(_np(lam_q).astype(np.int64).reshape(B), 0, MIX_ONE).reshape(B, 1, 1)
+    bx = _np(box).astype(np.int64).reshape(B, 4)
+    y0, y1 = np.clip(bx[:, 0], 0, H).reshape(B, 1, 1), np.clip(bx[:, 1], 0, H).reshape(B, 1, 1)
+    x0, x1 = np.clip(bx[:, 2], 0, W).reshape(B, 1, 1), np.clip(bx[:, 3], 0, W).reshape(B, 1, 1)
+    i, j = np.arange(H).reshape(1, H, 1), np.arange(W).reshape(1, 1, W)
+    inside = (i >= y0) & (i < y1) & (j >= x0) & (j < x1)
+    o = np.where((p < 0).reshape(B, 1, 1), np.int64(fill), a[np.maximum(p, 0)])
+    m = (q * a + (MIX_ONE - q) * o + 32768) >> 16
+    return torch.from_numpy(np.where(inside, m, a).astype(np.uint8).reshape(shape))
+
+
+def target_mix_reference(t, perm, tw_q):
+    """cx_target_mix's definition (module docstring) in numpy float32 on the CPU, every product and sum rounded on its own: t (B, n);
+    returns (B, n) float32 (a torch tensor).  Used by the tests and by nothing else."""
+    import numpy as np
+    tt = _np(t).astype(np.float32)
+    B = tt.shape[0]
+    p = np.clip(_np(perm).astype(np.int64).reshape(B), -1, B - 1)
+    wq = np.clip(_np(tw_q).astype(np.int64).reshape(B), 0, MIX_ONE)
+    w = (wq.astype(np.float32) * np.float32(2.0 ** -16)).reshape(B, 1)
+    oth = tt[np.maximum(p, 0)]
+    blend = (w * tt).astype(np.float32) + ((np.float32(1.0) - w) * oth).astype(np.float32)
+    out = np.where((tt < 0) | (oth < 0), np.float32(-1.0), blend.astype(np.float32))
+    keep = ((p < 0) | (wq == MIX_ONE)).reshape(B, 1)
+    return torch.from_numpy(np.where(keep, tt, out).astype(np.float32))
+
+
+def _plan_to(plan, device):
+    """A plan's four arrays on `device` through ONE copy: int32 views (perm, lam_q, tw_q, box) of a (7 B,) buffer."""
+    import numpy as np
+    B = len(plan["perm"])
+    flat = np.concatenate([plan["perm"], plan["lam_q"], plan["tw_q"], plan["box"].reshape(-1)]).astype(np.int32)
+    d = torch.from_numpy(flat).to(device)
+    return d[:B], d[B:2 * B], d[2 * B:3 * B], d[3 * B:].view(B, 4)
+
+
+class SampleMix:
+    """The --mixup / --cutmix / --erase_prob step of the training loop, the last one on the uint8 batch: (x_u8, t, step) -> (x, t)
+    on the GPU, its plans drawn from (step, rank).  Mixing is ops.u8_mix + ops.target_mix; erasing a second ops.u8_mix (labels do not
+    change).  Build it with `make_sample_mix`, which returns None when everything is off."""
+
+    def __init__(self, mixup_alpha=0.0, cutmix_alpha=0.0, prob=1.0, switch_prob=0.5, mode="batch", erase_prob=0.0, erase_fill=ERASE_FILL,
+                 rank=0, device=None):
+        self.mix = {"mixup_alpha": float(mixup_alpha), "cutmix_alpha": float(cutmix_alpha), "prob": float(prob),
+                    "switch_prob": float(switch_prob), "mode": mode}
+        self.mixing = (self.mix["mixup_alpha"] > 0 or self.mix["cutmix_alpha"] > 0) and self.mix["prob"] > 0
+        self.erase_prob, self.erase_fill = float(erase_prob), int(erase_fill)
+        self.rank, self.device = rank, device
+        mix_plan(0, 0, 1, 1, **self.mix)                     # (validates the settings)
+        erase_plan(0, 0, 1, 1, prob=self.erase_prob)
+        if not 0 <= self.erase_fill <= 255:
+            raise ValueError("the erase fill is a grey level 0..255 (got %r)" % (erase_fill,))
+
+    def __call__(self, x_u8, t, step):
+        from . import ops
+        if x_u8.dtype != torch.uint8:
+            raise RuntimeError("the sample mix works on the decoded uint8 images (got %s)" % x_u8.dtype)
+        B, H, W = x_u8.shape[0], x_u8.shape[-2], x_u8.shape[-1]
+        device = x_u8.device if self.device is None else self.device
+        if self.mixing:
+            perm, lam_q, tw_q, box = _plan_to(mix_plan(mix_seed(step, self.rank), B, H, W, **self.mix), device)
+            x_u8 = ops.u8_mix(x_u8, perm, lam_q, box, 0)
+            t = ops.target_mix(t, perm, tw_q)
+        if self.erase_prob > 0:
+            perm, lam_q, _, box = _plan_to(erase_plan(erase_seed(step, self.rank), B, H, W, prob=self.erase_prob), device)
+            x_u8 = ops.u8_mix(x_u8, perm, lam_q, box, self.erase_fill)
+        return x_u8, t
+
+
+def make_sample_mix(mixup_alpha=0.0, cutmix_alpha=0.0, prob=1.0, switch_prob=0.5, mode="batch", erase_prob=0.0, erase_fill=ERASE_FILL,
+                    rank=0, device=None):
+    """A SampleMix, or None with everything off (no alpha > 0 or mix probability 0, and erase probability 0): then nothing is
+    launched or allocated."""
+    sm = SampleMix(mixup_alpha, cutmix_alpha, prob, switch_prob, mode, erase_prob, erase_fill, rank, device)
+    return sm if (sm.mixing or sm.erase_prob > 0) else None

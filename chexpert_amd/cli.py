@@ -18,6 +18,17 @@
                         --evaluate_ensemble, --visualize), as the first step on the uint8 batch, before --affine and --jitter;
                         --clahe_grid 8 8 tiles (each 1..16, dividing the crop size), --clahe_clip 2.0 (0: no clipping).  It sits behind
                         the loader: --cache_decoded does not depend on these settings
+  --mixup ALPHA         sample-mixing regularisation of the uint8 batch and its targets on the GPU (chexpert_amd/augment.py: SampleMix;
+  --cutmix ALPHA        training only), the LAST step on the batch, after --clahe, --affine and --jitter (per-sample transforms first,
+                        then the collated batch is mixed, as timm does): Mixup blends every image with a partner of the minibatch at
+                        lambda ~ Beta(ALPHA, ALPHA), CutMix pastes a box of the partner (area share 1 - lambda); the targets are blended
+                        by the same share, a label the loss ignores (-1) stays ignored.  0 (default): off.  With both, CutMix is chosen
+                        with --mix_switch_prob P (default 0.5); --mix_prob P: the probability that a minibatch is mixed at all (default
+                        1.0); --mix_mode batch|elem: one draw per minibatch (default) or per image.  Not with --loss aucm (it thresholds
+                        the targets at 0.5).  Each data-parallel rank mixes its own shard with its own seed
+  --erase_prob P        random erasing (Cutout) of the uint8 batch on the GPU, after the mix: each image with probability P gets one
+                        rectangle (area 2 % .. 1/3 of the image, aspect 0.3 .. 3.3, as torchvision's RandomErasing) overwritten with the
+                        grey level --erase_fill V (default 136, the dataset mean); labels do not change.  0 (default): off
   --uncertain POLICY    what an uncertain (-1) training label becomes: ones (the reference's U-Ones, default), zeros, ignore (it stays
                         -1 and the loss skips it), ones_lsr / zeros_lsr (label smoothing: uniform in [0.55, 0.85] / [0, 0.3])
   --pos_weight W        `auto` or n_classes floats: BCEWithLogitsLoss's pos_weight, inside the fused step too; auto = per class
@@ -112,6 +123,13 @@ def build_parser():
     p.add_argument("--clahe", action="store_true", help="CLAHE contrast equalisation of the uint8 image (GPU, every mode)")
     p.add_argument("--clahe_grid", type=int, nargs=2, default=[8, 8], metavar=("GY", "GX"), help="tiles per axis, each 1..16, dividing the crop size")
     p.add_argument("--clahe_clip", type=float, default=2.0, metavar="C", help="clip limit in multiples of the mean bin height (0: no clipping)")
+    p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA", help="Mixup of the uint8 batch at lambda ~ Beta(ALPHA, ALPHA) (GPU, training only; 0: off)")
+    p.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA", help="CutMix of the uint8 batch at lambda ~ Beta(ALPHA, ALPHA) (GPU, training only; 0: off)")
+    p.add_argument("--mix_prob", type=float, default=1.0, metavar="P", help="probability that a minibatch (--mix_mode elem: an image) is mixed")
+    p.add_argument("--mix_switch_prob", type=float, default=0.5, metavar="P", help="probability of CutMix where --mixup and --cutmix are both on")
+    p.add_argument("--mix_mode", default="batch", choices=["batch", "elem"], help="one lambda / box per minibatch, or per image")
+    p.add_argument("--erase_prob", type=float, default=0.0, metavar="P", help="random erasing of the uint8 batch: probability per image (GPU, training only; 0: off)")
+    p.add_argument("--erase_fill", type=int, default=136, metavar="V", help="grey level 0..255 an erased rectangle gets (default: the dataset mean)")
     p.add_argument("--uncertain", default="ones", choices=list(UNCERTAIN_POLICIES), help="policy for the uncertain (-1) training labels")
     p.add_argument("--pos_weight", nargs="+", default=None, metavar="W", help="`auto` or n_classes floats: positive-term weights of the loss")
     p.add_argument("--loss", default="bce", choices=["bce", "aucm"], help="training loss: cross-entropy, or the AUC min-max-margin loss")
@@ -176,7 +194,8 @@ def batches(ds, indices, batch_size, drop_last):
 
 def parse_args(argv=None):
     """The command line, --load_config applied, and what can be refused before anything is built refused here (parser.error): a
-    --clahe grid that does not divide the crop size is an argument error, not a kernel status."""
+    --clahe grid that does not divide the crop size is an argument error, not a kernel status; so are the ranges of the sample-mixing
+    flags and their combination with --loss aucm."""
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.load_config:
@@ -189,6 +208,21 @@ def parse_args(argv=None):
             clahe_clip_count(args.clahe_clip, 1, 1)
         except ValueError as e:
             parser.error("--clahe: %s" % e)
+    for name in ("mixup", "cutmix"):
+        v = getattr(args, name, 0.0)
+        if not (v >= 0.0 and np.isfinite(v)):
+            parser.error("--%s takes a Beta parameter >= 0 (got %r)" % (name, v))
+    for name, dflt in (("mix_prob", 1.0), ("mix_switch_prob", 0.5), ("erase_prob", 0.0)):
+        v = getattr(args, name, dflt)
+        if not 0.0 <= v <= 1.0:
+            parser.error("--%s takes a probability in [0, 1] (got %r)" % (name, v))
+    if not 0 <= getattr(args, "erase_fill", 136) <= 255:
+        parser.error("--erase_fill takes a grey level 0..255 (got %r)" % args.erase_fill)
+    if getattr(args, "mix_mode", "batch") not in ("batch", "elem"):
+        parser.error("--mix_mode takes batch or elem (got %r)" % args.mix_mode)
+    if (getattr(args, "mixup", 0.0) > 0 or getattr(args, "cutmix", 0.0) > 0) and getattr(args, "loss", "bce") == "aucm":
+        parser.error("--mixup / --cutmix cannot be combined with --loss aucm: that loss thresholds the targets at 0.5, a blended "
+                     "label has no meaning there (--erase_prob leaves the labels alone and is allowed)")
     boot, alpha, unit = getattr(args, "bootstrap", 0), getattr(args, "bootstrap_alpha", 0.05), getattr(args, "bootstrap_unit", "image")
     if boot < 0:
         parser.error("--bootstrap takes a number of replicates >= 0 (got %r)" % boot)
@@ -255,6 +289,17 @@ def make_affine(args, rank, device):
         return None
     from .augment import RandomAffine
     return RandomAffine(args.affine_degrees, args.affine_translate, args.affine_scale, args.affine_shear, rank, device)
+
+
+def make_mix(args, rank, device):
+    """The sample-mixing step of the training loop (chexpert_amd/augment.py: SampleMix), or None: only --train with --mixup,
+    --cutmix or --erase_prob mixes -- validation, --evaluate, --visualize and predict never do."""
+    if not args.train:
+        return None
+    from .augment import make_sample_mix
+    return make_sample_mix(getattr(args, "mixup", 0.0), getattr(args, "cutmix", 0.0), getattr(args, "mix_prob", 1.0),
+                           getattr(args, "mix_switch_prob", 0.5), getattr(args, "mix_mode", "batch"), getattr(args, "erase_prob", 0.0),
+                           getattr(args, "erase_fill", 136), rank, device)
 
 
 def resolve_pos_weight(spec, targets, n_classes):
@@ -705,6 +750,7 @@ def main(argv=None):
                              (u[2] > 0.5).to(torch.int32).to(device))
 
     affine = make_affine(args, rank, device)
+    mix = make_mix(args, rank, device)
     if args.train:
         fused = args.fused_optimizer
         gstep = None
@@ -728,6 +774,8 @@ def main(argv=None):
                     x = affine(x, args.step)
                 if args.jitter:
                     x = jitter(x, args.step)
+                if mix is not None:                         # per-sample transforms first, then the collated batch is mixed
+                    x, t = mix(x, t, args.step)
                 if args.graph and fused and (gstep is not None or x.shape[0] == args.batch_size):
                     if gstep is None:                       # captured on the first full minibatch's shapes
                         # (data-parallel: graph segments cut at the gradient buckets, the all-reduces enqueued between them)

@@ -432,6 +432,41 @@ def u8_affine(x, mat, fill=0, out=None):
     return out
 
 
+def _plan_i32(v, shape, name):
+    assert v.dtype == torch.int32 and v.is_contiguous() and tuple(v.shape) == shape, "%s: int32 %s expected" % (name, shape)
+
+
+def u8_mix(x, perm, lam_q, box, fill=0, out=None):
+    """Mixup / CutMix / random erasing of decoded grey bytes (B,1,H,W) / (B,H,W) uint8 on the GPU (cx_u8_mix, integers throughout):
+    inside row b's box (y0 y1 x0 x1, clamped to the image) y = (q*x[b] + (65536 - q)*o + 32768) >> 16 with q = lam_q[b] and
+    o = x[perm[b]], or `fill` where perm[b] < 0; outside it y = x[b].  perm, lam_q: int32 (B,), box: int32 (B,4)
+    (chexpert_amd.augment.mix_plan / erase_plan).  `out` must not be x."""
+    require_cuda(x, perm, lam_q, box, out)
+    assert x.dtype == torch.uint8 and x.is_contiguous() and x.dim() in (3, 4) and (x.dim() == 3 or x.shape[1] == 1)
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    _plan_i32(perm, (B,), "perm"), _plan_i32(lam_q, (B,), "lam_q"), _plan_i32(box, (B, 4), "box")
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.uint8 and out.shape == x.shape and out.is_contiguous()
+    check(lib().cx_u8_mix(ptr(x), ptr(out), B, H, W, ptr(perm), ptr(lam_q), ptr(box), int(fill), stream_ptr()), "cx_u8_mix")
+    return out
+
+
+def target_mix(t, perm, tw_q, out=None):
+    """The targets that go with u8_mix (cx_target_mix): t fp32 (B, n); out[b] = w*t[b] + (1 - w)*t[perm[b]] with w = tw_q[b] / 65536,
+    every product and sum rounded on its own; -1 where either label is < 0 (ignored stays ignored); t[b] where perm[b] < 0 or
+    tw_q[b] == 65536.  perm, tw_q: int32 (B,).  `out` must not be t."""
+    require_cuda(t, perm, tw_q, out)
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2
+    B, n = t.shape
+    _plan_i32(perm, (B,), "perm"), _plan_i32(tw_q, (B,), "tw_q")
+    if out is None:
+        out = torch.empty_like(t)
+    assert out.dtype == torch.float32 and out.shape == t.shape and out.is_contiguous()
+    check(lib().cx_target_mix(ptr(t), ptr(out), B, n, ptr(perm), ptr(tw_q), stream_ptr()), "cx_target_mix")
+    return out
+
+
 def _u8_images(x):
     assert x.dtype == torch.uint8 and x.is_contiguous() and x.dim() in (3, 4) and (x.dim() == 3 or x.shape[1] == 1)
     return x.shape[0], x.shape[-2], x.shape[-1]

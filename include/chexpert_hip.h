@@ -713,6 +713,29 @@ int cx_u8_jitter(const uint8_t* x, uint8_t* y, int B, int HW, const float* brigh
  * The identity (1,0,0, 0,1,0) returns x bit for bit.  One writer per output byte, no atomics: bit-reproducible.
  * W % 4 == 0, H and W <= 1024, else CX_ESHAPE; y and mat 4-byte aligned.  Additive entry point of ABI 10 (no struct changed).   */
 int cx_u8_affine(const uint8_t* x, uint8_t* y, int B, int H, int W, const float* mat /* device, [B][6] */, int fill, void* stream);
+/* Sample mixing of the decoded grey images x, y: (B, H, W) uint8, distinct buffers (mix.hip): Mixup, CutMix and random erasing
+ * through one primitive; the caller draws the plan (chexpert_amd/augment.py: mix_plan, erase_plan).  Integer arithmetic throughout.
+ * Per row b: p = perm[b] clamped to [-1, B-1], q = lam_q[b] clamped to [0, 65536], the box (y0 y1 x0 x1) clamped to the image: rows
+ * [y0, y1), columns [x0, x1).  For pixel (i, j) with a = x[b][i][j]:
+ *   outside the box   y[b][i][j] = a
+ *   inside the box    o = (p < 0) ? fill : x[p][i][j];   y[b][i][j] = (q*a + (65536 - q)*o + 32768) >> 16
+ * i.e. round-half-up of lambda*a + (1 - lambda)*o with lambda = q / 65536 (the sum is below 2^24: exact).  Mixup: box = the whole
+ * image, any q.  CutMix: a partial box, q = 0.  Erasing: p = -1, q = 0.  Because of the clamps no load leaves the batch whatever
+ * the parameter arrays hold; a row (or band of rows) the box does not touch is copied without reading the partner.  One writer per
+ * output byte, no atomics: bit-reproducible.  x == y is CX_EINVAL (a partner row may be read after it was written), as are a null
+ * pointer, B, H or W <= 0 and fill outside 0..255.  W % 4 == 0, H and W <= 1024, else CX_ESHAPE; x, y, perm, lam_q and box 4-byte
+ * aligned, else CX_EALIGN (16 bytes per lane where W % 16 == 0 and x, y are 16-byte aligned).  Additive entry point of ABI 10.   */
+int cx_u8_mix(const uint8_t* x, uint8_t* y, int B, int H, int W, const int* perm /* device, [B] */, const int* lam_q /* device, [B] */,
+              const int* box /* device, [B][4]: y0 y1 x0 x1 */, int fill, void* stream);
+/* The targets that go with cx_u8_mix: t, out (B, n) fp32, distinct buffers.  Every product and sum is rounded to fp32 on its own
+ * (nothing is contracted into a fused multiply-add).  p = perm[b] clamped to [-1, B-1], w_q = tw_q[b] clamped to [0, 65536],
+ * w = w_q / 65536 (w and 1 - w are exact in fp32):
+ *   p < 0 or w_q == 65536            out[b][c] = t[b][c]
+ *   else t[b][c] < 0 or t[p][c] < 0  out[b][c] = -1      (a label the loss ignores stays ignored)
+ *   else                             out[b][c] = w * t[b][c] + (1 - w) * t[p][c]
+ * CX_EINVAL: a null pointer, out == t, B or n <= 0.  CX_EALIGN: a pointer that is not 4-byte aligned.  Additive entry point of ABI 10. */
+int cx_target_mix(const float* t, float* out, int B, int n, const int* perm /* device, [B] */, const int* tw_q /* device, [B] */,
+                  void* stream);
 /* Contrast-limited adaptive histogram equalisation (CLAHE) of the decoded grey images x: (B, H, W) uint8, in two stages (clahe.hip).
  * The structure is OpenCV's createCLAHE (per-tile clipped histogram -> table, bilinear blend of the four surrounding tables), but
  * NOT bit-equal to it: everything here is integer arithmetic, and tables sit at tile centres with pixel centres at half-integers.
