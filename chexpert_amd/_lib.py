@@ -207,6 +207,8 @@ SIGNATURES = {
     "cx_class_cam_f32": [_vp] * 6 + [_i] * 9 + [_vp],
     "cx_boot_counts": [_vp, _i, _i, _i, _i, C.c_uint64, _vp],
     "cx_boot_auc": [_vp, _i, _i, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _i, _vp],
+    "cx_boot_sweep": [_vp, _i, _i, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
+                      _vp, _vp, _vp, _vp, _i, _vp],
     "cx_sal_points": [_vp, _vp, _f, _f, _f, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _i, _i, _i, _i, _vp],
     "cx_sal_accumulate": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "cx_sal_finish": [_vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

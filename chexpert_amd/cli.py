@@ -58,6 +58,10 @@
                         --bootstrap_seed S (default: --seed), --bootstrap_unit image|study|patient (what is resampled; study and
                         patient need the real data's paths), --bootstrap_alpha A (default 0.05).  0 (default): nothing is computed,
                         allocated or written
+  --bootstrap_metrics M [M ...]   with --bootstrap B > 0: a metrics_ci_<tag>.json beside every auc_ci_<tag>.json, with the same seed, unit and
+                        level: the interval of every named metric over the same kind of resamples (metrics.bootstrap_metrics): auroc, ap
+                        (average precision), sens@S (sensitivity at specificity >= S), spec@S (specificity at sensitivity >= S), S inside
+                        (0, 1) with at most 6 decimals, at most 8 operating points.  Not given (default): nothing more is computed or written
 
 Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N chexpert.py --train ...`; every rank holds a
 replica and a shard of each minibatch stream (per-rank BatchNorm statistics, averaged gradients: DDP semantics), the
@@ -154,6 +158,8 @@ def build_parser():
     p.add_argument("--bootstrap_seed", type=int, default=None, metavar="S", help="seed of the bootstrap draws (default: --seed)")
     p.add_argument("--bootstrap_unit", default="image", choices=list(BOOTSTRAP_UNITS), help="what the bootstrap resamples")
     p.add_argument("--bootstrap_alpha", type=float, default=0.05, metavar="A", help="the intervals cover 1 - A (default 0.05)")
+    p.add_argument("--bootstrap_metrics", nargs="+", default=None, metavar="M",
+                   help="with --bootstrap: intervals of these metrics (auroc, ap, sens@S, spec@S) into metrics_ci_<tag>.json")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -232,6 +238,14 @@ def parse_args(argv=None):
         parser.error("--bootstrap_unit takes one of %s (got %r)" % (", ".join(BOOTSTRAP_UNITS), unit))
     if boot > 0 and unit != "image" and getattr(args, "synthetic", 0):
         parser.error("--bootstrap_unit %s groups the images by their file paths; --synthetic images have none (use image)" % unit)
+    names = getattr(args, "bootstrap_metrics", None)
+    if names is not None:
+        if boot <= 0:
+            parser.error("--bootstrap_metrics needs --bootstrap B > 0 (the number of replicates)")
+        try:
+            M.parse_boot_metrics(names)
+        except ValueError as e:
+            parser.error("--bootstrap_metrics: %s" % e)
     return args
 
 
@@ -270,6 +284,29 @@ def write_auc_ci(args, tag, outputs, targets, groups=None):
         print("  %-18s %.4f [%.4f, %.4f]" % (name, ci["aucs"][c], ci["lo"][c], ci["hi"][c]))
     print("  %-18s %.4f [%.4f, %.4f]" % ("mean", ci["mean_auc"]["point"], ci["mean_auc"]["lo"], ci["mean_auc"]["hi"]))
     path = os.path.join(args.output_dir, auc_ci_name(tag))
+    json.dump(ci, open(path, "w"), indent=4)
+    return path
+
+
+def metrics_ci_name(tag):
+    """File name of the metric intervals that go with <tag>.json: eval_results_step_5 -> metrics_ci_step_5.json (the rule of auc_ci_name:
+    not the prefix `eval_results`)."""
+    return "metrics_ci_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ".json"
+
+
+def write_metrics_ci(args, tag, outputs, targets, groups=None):
+    """With --bootstrap B > 0 and --bootstrap_metrics: the intervals of the named metrics of the evaluation that wrote <tag>.json, into
+    metrics_ci_<...>.json beside it ({name: summary}), and one line per metric.  Returns the path, or None (nothing computed or written)."""
+    n_boot, names = getattr(args, "bootstrap", 0), getattr(args, "bootstrap_metrics", None)
+    if n_boot <= 0 or not names:
+        return None
+    seed = getattr(args, "bootstrap_seed", None)
+    ci = M.bootstrap_metrics(outputs, targets, metrics=names, n_boot=n_boot, seed=args.seed if seed is None else seed, groups=groups,
+                             alpha=getattr(args, "bootstrap_alpha", 0.05), device="cuda:%d" % (args.cuda or 0))
+    for name, r in ci.items():
+        r["unit"] = getattr(args, "bootstrap_unit", "image")
+        print("%s, mean over the classes: %.4f [%.4f, %.4f]" % (name, r["mean_auc"]["point"], r["mean_auc"]["lo"], r["mean_auc"]["hi"]))
+    path = os.path.join(args.output_dir, metrics_ci_name(tag))
     json.dump(ci, open(path, "w"), indent=4)
     return path
 
@@ -740,6 +777,7 @@ def main(argv=None):
             print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
             json.dump(res, open(os.path.join(args.output_dir, tag + ".json"), "w"), indent=4)
             write_auc_ci(args, tag, o, t, boot_groups)
+            write_metrics_ci(args, tag, o, t, boot_groups)
         return res
 
     def jitter(x_u8, step):
@@ -861,6 +899,7 @@ def main(argv=None):
             json.dump(res, open(os.path.join(args.output_dir, "eval_results_ensemble.json"), "w"), indent=4)
             print("AUC:\n", pprint.pformat(res["aucs"]))
             write_auc_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
+            write_metrics_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
     if args.visualize and rank == 0:
         # chexpert.py:556-563: Grad-CAM grids over the 'vis' subset (three examples per finding category), and for the
         # attention-augmented models the attention-map grids of the stored softmax weights

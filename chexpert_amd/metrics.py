@@ -5,6 +5,8 @@ Here the ROC / PR curves are built directly (descending score sweep with tie gro
 sklearn's `_binary_clf_curve` does) and the AUROC is the trapezoid area.  Host-side numpy: this runs once
 per evaluation on (N, 5) arrays and is not on the GPU hot path.
 """
+import re
+
 import numpy as np
 
 
@@ -342,3 +344,278 @@ def bootstrap_auc_diff_reference(outputs_a, outputs_b, targets, n_boot=1000, see
     point_a, rep_a, U = _replicates_reference(outputs_a, targets, groups, n_boot, seed)
     point_b, rep_b, _ = _replicates_reference(outputs_b, targets, groups, n_boot, seed)
     return _summarise_diff(point_a, point_b, rep_a, rep_b, n_boot, seed, alpha, U, return_replicates)
+
+
+# ---- bootstrap of the metrics that need the whole threshold sweep (chexpert_amd/csrc/bootstrap.hip, cx_boot_sweep) ----------------
+# For one replicate and one class: the kept rows (target >= 0) weigh w = counts[unit(row)], a row is positive iff target > 0.5.  The
+# distinct scores are swept from high to low; after tie group g, tp_g / fp_g = the positive / negative weight with a score >= the
+# group's, W+ / W- the totals.  The operating points of the resample are (tp_g, fp_g) at the group ends, plus (0, 0); nothing is
+# interpolated:
+#   AP      = apnum / (W+ 2^32),  apnum = sum_g (tp_g - tp_{g-1}) * floor((tp_g << 32) / (tp_g + fp_g))  (uint64; a term with
+#             tp_g = tp_{g-1} is 0 and does not divide): the step sum of sklearn's average_precision_score, below the exact value by
+#             less than 2^-32.  NaN iff W+ = 0
+#   sens@S  = max{tp_g : fp_g 10^6 <= (10^6 - s) W-} / W+,  s = round(S 10^6): the sensitivity at specificity >= S
+#   spec@S  = 1 - min{fp_g : tp_g 10^6 >= s W+} / W-: the specificity at sensitivity >= S.  Both NaN iff W+ = 0 or W- = 0
+# A tie group without weight in a replicate repeats the previous (tp, fp), so the group ends are a property of the scores alone.
+BOOT_MAX_POINTS, BOOT_SENS, BOOT_SPEC, BOOT_PPM = 8, 0, 1, 10 ** 6
+_METRIC_POINT = re.compile(r"(sens|spec)@(\d*\.\d+|\d+)\Z")
+
+
+def parse_boot_metrics(names):
+    """Strict parse of metric names: "auroc", "ap", "sens@S", "spec@S" with S a plain decimal inside (0, 1) of at most 6 decimals.
+    Returns (names as a tuple, points): points lists (BOOT_SENS | BOOT_SPEC, s = S in millionths) of the operating points in the order
+    named.  ValueError: an unknown or repeated name, an S outside (0, 1) or finer than 10^-6, more than BOOT_MAX_POINTS points, none."""
+    if isinstance(names, str):
+        names = (names,)
+    names, points = tuple(names), []
+    if not names:
+        raise ValueError("bootstrap: no metric named")
+    for name in names:
+        if not isinstance(name, str):
+            raise ValueError("bootstrap: a metric name is a string (got %r)" % (name,))
+        if names.count(name) > 1:
+            raise ValueError("bootstrap: metric %r is named twice" % name)
+        if name in ("auroc", "ap"):
+            continue
+        m = _METRIC_POINT.match(name)
+        if not m:
+            raise ValueError("bootstrap: unknown metric %r (auroc, ap, sens@S, spec@S with S a decimal inside (0, 1))" % name)
+        frac = m.group(2).partition(".")[2]
+        if len(frac) > 6:
+            raise ValueError("bootstrap: %r has more than 6 decimals" % name)
+        ppm = int(m.group(2).partition(".")[0] or "0") * BOOT_PPM + int((frac + "000000")[:6])
+        if not 1 <= ppm <= BOOT_PPM - 1:
+            raise ValueError("bootstrap: %r asks for a value outside (0, 1)" % name)
+        points.append((BOOT_SENS if m.group(1) == "sens" else BOOT_SPEC, ppm))
+    if len(points) > BOOT_MAX_POINTS:
+        raise ValueError("bootstrap: %d operating points (at most %d in one call)" % (len(points), BOOT_MAX_POINTS))
+    return names, points
+
+
+def bootstrap_sweep_plan(outputs, targets, groups=None):
+    """What cx_boot_sweep reads, built once per call on the host: for every class the kept rows (target >= 0) ONCE, descending in score
+    (compared in the dtype given).  An entry is the row's unit index with the label (target > 0.5) in bit 31 and bit 30 set on the last
+    entry of its tie group (free: U <= 2^24).  Inside a tie group the positives come first, then the row index ascends: the order there
+    is immaterial, this one makes the plan deterministic.  Returns {"order": int32, "offs": int64 (C), "lens": int32 (C), "units",
+    "n_units"} as bootstrap_plan does, with lens[c] entries for class c from offs[c]."""
+    s, t = _as_scores(outputs), np.asarray(_as_scores(targets), dtype=np.float64)
+    if s.ndim != 2 or s.shape != t.shape:
+        raise ValueError("bootstrap: outputs %s and targets %s must be (N, C) arrays of one shape" % (s.shape, t.shape))
+    if np.isnan(s).any():
+        raise ValueError("bootstrap: the scores hold NaN")
+    units, U = _units_of(s.shape[0], groups)
+    if not 1 <= U <= BOOT_MAX_UNITS:
+        raise ValueError("bootstrap: %d resampling units (1 .. 2^24 are supported)" % U)
+    parts, offs, lens, at = [], [], [], 0
+    for c in range(s.shape[1]):
+        keep = np.nonzero(t[:, c] >= 0)[0]
+        pos = t[keep, c] > 0.5
+        rank = np.unique(s[keep, c], return_inverse=True)[1].reshape(-1)
+        by = np.lexsort((keep, ~pos, -rank))                     # descending score; positives first; ascending row
+        entry = units[keep][by] | (pos[by].astype(np.int64) << 31)
+        if len(by):
+            r = rank[by]
+            entry |= np.r_[r[1:] != r[:-1], True].astype(np.int64) << 30
+        parts.append(entry.astype(np.uint32).view(np.int32))
+        offs.append(at)
+        lens.append(len(keep))
+        at += len(keep)
+    order = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+    return {"order": order.astype(np.int32), "offs": np.asarray(offs, dtype=np.int64), "lens": np.asarray(lens, dtype=np.int32),
+            "units": units, "n_units": U}
+
+
+def _check_points(points):
+    points = [(int(k), int(v)) for k, v in points]
+    if len(points) > BOOT_MAX_POINTS or any(k not in (BOOT_SENS, BOOT_SPEC) or not 1 <= v <= BOOT_PPM - 1 for k, v in points):
+        raise ValueError("bootstrap: at most %d operating points (BOOT_SENS | BOOT_SPEC, 1 .. 999999 millionths), got %s"
+                         % (BOOT_MAX_POINTS, points))
+    return points
+
+
+def bootstrap_sweep_reference(counts, order, offs, lens, n_units, points=()):
+    """Statement of cx_boot_sweep in uint64 numpy, vectorised over the replicates: (apnum, wpos, wneg, pts), (n_rep, C) and
+    (n_rep, C, P) uint64.  Unit indices are clamped to n_units - 1 as the kernel clamps them; every comparison is in uint64."""
+    counts = np.asarray(counts).astype(np.uint64)
+    order = np.asarray(order, dtype=np.int32)
+    points = _check_points(points)
+    R, C, u64 = counts.shape[0], len(lens), np.uint64
+    apnum, wpos, wneg = (np.zeros((R, C), dtype=u64) for _ in range(3))
+    pts = np.zeros((R, C, len(points)), dtype=u64)
+    for c in range(C):
+        e = order[int(offs[c]):int(offs[c]) + int(lens[c])]
+        w = counts[:, np.minimum(e & 0x3fffffff, n_units - 1)]
+        tp = np.cumsum(np.where(e < 0, w, u64(0)), axis=1, dtype=u64)
+        fp = np.cumsum(np.where(e < 0, u64(0), w), axis=1, dtype=u64)
+        if len(e):
+            wpos[:, c], wneg[:, c] = tp[:, -1], fp[:, -1]
+        ends = np.nonzero(e & 0x40000000)[0]
+        tp, fp = tp[:, ends], fp[:, ends]                        # the operating points of the resample (without (0, 0))
+        step = tp - np.concatenate([np.zeros((R, 1), dtype=u64), tp[:, :-1]], axis=1)
+        live = (step > 0) & (tp + fp > 0)
+        quot = (tp << u64(32)) // np.where(live, tp + fp, u64(1))
+        apnum[:, c] = np.where(live, step * quot, u64(0)).sum(1, dtype=u64)
+        for k, (kind, ppm) in enumerate(points):
+            if kind == BOOT_SENS:
+                ok = fp * u64(BOOT_PPM) <= u64(BOOT_PPM - ppm) * wneg[:, c:c + 1]
+                pts[:, c, k] = np.where(ok, tp, u64(0)).max(axis=1, initial=u64(0))               # (0, 0) always qualifies
+            else:
+                ok = tp * u64(BOOT_PPM) >= u64(ppm) * wpos[:, c:c + 1]
+                least = np.where(ok, fp, u64(0xffffffff)).min(axis=1, initial=u64(0xffffffff))
+                pts[:, c, k] = np.where(wpos[:, c] == 0, u64(0), least)                           # (0, 0) qualifies iff W+ = 0
+    return apnum, wpos, wneg, pts
+
+
+def _sweep_definition_parts(s, t, units, counts, points=()):
+    """(apnum, wpos, wneg, pts) straight from the definition, in Python integers (object arrays): no prepared order, no running sums, no
+    group-end marks.  For every distinct score v of a class, tp / fp are the weights of the kept positives / negatives scoring >= v;
+    the thresholds whose group has no weight in a replicate are dropped before anything else is formed."""
+    counts = np.asarray(counts).astype(np.int64)
+    points = _check_points(points)
+    R, C = counts.shape[0], s.shape[1]
+    apnum, wpos, wneg = (np.zeros((R, C), dtype=object) for _ in range(3))
+    pts = np.zeros((R, C, len(points)), dtype=object)
+    for c in range(C):
+        keep = np.nonzero(t[:, c] >= 0)[0]
+        sc, pos = s[keep, c], t[keep, c] > 0.5
+        vals = np.unique(sc)[::-1]
+        at_least = (sc[None, :] >= vals[:, None]).astype(np.int64)               # (thresholds, rows)
+        in_group = (sc[None, :] == vals[:, None]).astype(np.int64)
+        for r in range(R):
+            w = counts[r, units[keep]]
+            tps, fps = at_least @ np.where(pos, w, 0), at_least @ np.where(pos, 0, w)
+            present = (in_group @ w) > 0
+            curve = [(0, 0)] + [(int(a), int(b)) for a, b in zip(tps[present], fps[present])]
+            Wp, Wn = int(np.where(pos, w, 0).sum()), int(np.where(pos, 0, w).sum())
+            wpos[r, c], wneg[r, c] = Wp, Wn
+            apnum[r, c] = sum((a - a0) * ((a << 32) // (a + b)) for (a0, _), (a, b) in zip(curve[:-1], curve[1:]) if a != a0)
+            for k, (kind, ppm) in enumerate(points):
+                if kind == BOOT_SENS:
+                    pts[r, c, k] = max(a for a, b in curve if b * BOOT_PPM <= (BOOT_PPM - ppm) * Wn)
+                else:
+                    pts[r, c, k] = min(b for a, b in curve if a * BOOT_PPM >= ppm * Wp)
+    return apnum, wpos, wneg, pts
+
+
+def _sweep_values(names, points, apnum, wpos, wneg, pts):
+    """{name: (n_rep, C) float64} of the sweep's metrics from its integers.  float64(apnum) rounds once (apnum may need 64 bits), W+ 2^32
+    is exact and the quotient rounds once; the operating points are quotients of exact operands, 1 - x rounds once more."""
+    ap = np.asarray(apnum).astype(np.uint64).astype(np.float64)
+    p, q = np.asarray(wpos).astype(np.float64), np.asarray(wneg).astype(np.float64)
+    both = (p > 0) & (q > 0)
+    out, k = {}, 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for name in names:
+            if name == "ap":
+                out[name] = np.where(p > 0, ap / (np.where(p > 0, p, 1.0) * 2.0 ** 32), np.nan)
+            elif name != "auroc":
+                v = np.asarray(pts)[:, :, k].astype(np.float64)
+                out[name] = np.where(both, v / np.where(both, p, 1.0) if points[k][0] == BOOT_SENS else 1.0 - v / np.where(both, q, 1.0), np.nan)
+                k += 1
+    return out
+
+
+def _summarise_metric(*args):
+    s = _summarise(*args)
+    return {"point": s.pop("aucs"), **s}
+
+
+def _metric_replicates_gpu(models, targets, names, points, n_boot, seed, groups, device, chunk):
+    """[{name: (point (C), replicates (n_boot, C))}] per model, every model and every metric over ONE count table per chunk of
+    replicates; the point estimate goes through the same kernels with a row of ones."""
+    import torch
+
+    from . import ops
+    auc = [bootstrap_plan(o, targets, groups) if "auroc" in names else None for o in models]
+    swp = [bootstrap_sweep_plan(o, targets, groups) if len(names) > ("auroc" in names) else None for o in models]
+    U = (auc[0] or swp[0])["n_units"]
+    if chunk is None:
+        chunk = max(1, BOOT_TABLE_BYTES // (4 * U))
+    chunk = max(1, min(int(chunk), int(n_boot)))
+    dev_order = [[None if p is None else torch.from_numpy(p["order"]).to(device) for p in (a, s)] for a, s in zip(auc, swp)]
+
+    def evaluate(counts, k):
+        out = {}
+        if auc[k] is not None:
+            out["auroc"] = _auc_of(*(v.cpu().numpy() for v in ops.boot_auc(counts, dev_order[k][0], auc[k]["offs"], auc[k]["lens"], U)))
+        if swp[k] is not None:
+            got = ops.boot_sweep(counts, dev_order[k][1], swp[k]["offs"], swp[k]["lens"], U, points)
+            apnum, wpos, wneg, pts = (v.cpu().numpy() for v in got)
+            out.update(_sweep_values(names, points, apnum.view(np.uint64), wpos, wneg, pts))
+        return out
+
+    table = torch.empty(chunk, U, dtype=torch.int32, device=device)
+    ones = torch.ones(1, U, dtype=torch.int32, device=device)
+    point = [evaluate(ones, k) for k in range(len(models))]
+    reps = [{name: [] for name in names} for _ in models]
+    for first in range(0, int(n_boot), chunk):
+        counts = ops.boot_counts(U, min(chunk, int(n_boot) - first), seed, first=first, out=table)
+        for k in range(len(models)):
+            for name, v in evaluate(counts, k).items():
+                reps[k][name].append(v)
+    return [{name: (point[k][name][0], np.concatenate(reps[k][name])) for name in names} for k in range(len(models))], U
+
+
+def _metric_replicates_reference(outputs, targets, names, points, n_boot, seed, groups):
+    """{name: (point, replicates)} on the host: the AUROC as bootstrap_auc_reference forms it, the sweep's metrics through the numpy
+    statement of the kernel over the prepared plan."""
+    out, U = {}, None
+    if "auroc" in names:
+        point, rep, U = _replicates_reference(outputs, targets, groups, n_boot, seed)
+        out["auroc"] = (point, rep)
+    if len(names) > ("auroc" in names):
+        plan = bootstrap_sweep_plan(outputs, targets, groups)
+        U = plan["n_units"]
+
+        def values(counts):
+            return _sweep_values(names, points, *bootstrap_sweep_reference(counts, plan["order"], plan["offs"], plan["lens"], U, points))
+        point, reps = values(np.ones((1, U), dtype=np.uint32)), []
+        for first in range(0, int(n_boot), 64):
+            reps.append(values(bootstrap_counts_reference(U, min(64, int(n_boot) - first), seed, first=first)))
+        out.update({name: (point[name][0], np.concatenate([r[name] for r in reps])) for name in point})
+    return {name: out[name] for name in names}, U
+
+
+def bootstrap_metrics(outputs, targets, metrics=("auroc", "ap"), n_boot=1000, seed=0, groups=None, alpha=0.05, device="cuda", chunk=None,
+                      return_replicates=False):
+    """Percentile bootstrap intervals of several evaluation metrics over the SAME resamples, on the GPU (cx_boot_counts, cx_boot_auc,
+    cx_boot_sweep; no CPU fallback).  metrics: "auroc", "ap" (average precision, the step sum), "sens@S" (sensitivity at specificity
+    >= S) and "spec@S" (specificity at sensitivity >= S), S a decimal inside (0, 1) with at most 6 decimals, at most 8 operating
+    points in one call.  The other arguments are those of bootstrap_auc.  Returns {name: summary}; a summary has the keys of
+    bootstrap_auc's result with "point" in place of "aucs" ("mean_auc" is the metric's mean over the classes), and the "auroc"
+    summary carries the numbers of bootstrap_auc with the same arguments, bit for bit."""
+    _check_boot(n_boot, alpha)
+    names, points = parse_boot_metrics(metrics)
+    (res,), U = _metric_replicates_gpu([outputs], targets, names, points, n_boot, seed, groups, device, chunk)
+    return {name: _summarise_metric(*res[name], n_boot, seed, alpha, U, return_replicates) for name in names}
+
+
+def bootstrap_metrics_reference(outputs, targets, metrics=("auroc", "ap"), n_boot=1000, seed=0, groups=None, alpha=0.05,
+                                return_replicates=False):
+    """The numpy statement of bootstrap_metrics (host; for the tests and as the timing yardstick)."""
+    _check_boot(n_boot, alpha)
+    names, points = parse_boot_metrics(metrics)
+    res, U = _metric_replicates_reference(outputs, targets, names, points, n_boot, seed, groups)
+    return {name: _summarise_metric(*res[name], n_boot, seed, alpha, U, return_replicates) for name in names}
+
+
+def bootstrap_metrics_diff(outputs_a, outputs_b, targets, metrics=("auroc", "ap"), n_boot=1000, seed=0, groups=None, alpha=0.05,
+                           device="cuda", chunk=None, return_replicates=False):
+    """Paired bootstrap of the difference a - b of every named metric between two models on the same rows (one count table, two plans
+    per kernel).  Returns {name: what bootstrap_auc_diff returns for the AUROC}."""
+    _check_boot(n_boot, alpha)
+    names, points = parse_boot_metrics(metrics)
+    (a, b), U = _metric_replicates_gpu([outputs_a, outputs_b], targets, names, points, n_boot, seed, groups, device, chunk)
+    return {name: _summarise_diff(a[name][0], b[name][0], a[name][1], b[name][1], n_boot, seed, alpha, U, return_replicates)
+            for name in names}
+
+
+def bootstrap_metrics_diff_reference(outputs_a, outputs_b, targets, metrics=("auroc", "ap"), n_boot=1000, seed=0, groups=None, alpha=0.05,
+                                     return_replicates=False):
+    """The numpy statement of bootstrap_metrics_diff."""
+    _check_boot(n_boot, alpha)
+    names, points = parse_boot_metrics(metrics)
+    a, U = _metric_replicates_reference(outputs_a, targets, names, points, n_boot, seed, groups)
+    b, _ = _metric_replicates_reference(outputs_b, targets, names, points, n_boot, seed, groups)
+    return {name: _summarise_diff(a[name][0], b[name][0], a[name][1], b[name][1], n_boot, seed, alpha, U, return_replicates)
+            for name in names}

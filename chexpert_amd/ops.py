@@ -1243,6 +1243,42 @@ def boot_auc(counts, order, offs, lens, n_units):
     return num2, wpos.long() & 0xffffffff, wneg.long() & 0xffffffff      # the kernel's uint32 sums
 
 
+BOOT_MAX_POINTS, BOOT_SENS, BOOT_SPEC = 8, 0, 1                    # CX_BOOT_MAX_POINTS, CX_BOOT_SENS, CX_BOOT_SPEC of the header
+
+
+def boot_sweep(counts, order, offs, lens, n_units, points=()):
+    """cx_boot_sweep: the integer parts of the average precision and of fixed operating points of every (replicate, class).  counts: as
+    boot_auc takes them; order: int32 device tensor holding, for class c, its kept rows once, descending in score (lens[c] entries from
+    offs[c]; an entry = unit index | label << 31 | end of its tie group << 30; metrics.bootstrap_sweep_plan builds them); points: up to
+    BOOT_MAX_POINTS pairs (BOOT_SENS or BOOT_SPEC, value in millionths 1 .. 999 999).  Returns int64 tensors apnum, wpos, wneg
+    (n_rep, C) and pts (n_rep, C, len(points)): AP = apnum / (wpos * 2^32) with apnum the kernel's uint64 (read it as such: .numpy()
+    .view(np.uint64); it passes 2^63 only when wpos does 2^31); sens@ = pts / wpos, spec@ = 1 - pts / wneg."""
+    require_cuda(counts, order)
+    assert counts.dtype == torch.int32 and counts.dim() == 2 and counts.stride(1) == 1 and counts.shape[1] >= n_units, \
+        "counts: int32 (n_rep, >= n_units) rows"
+    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), "order: contiguous int32"
+    offs, lens = [int(v) for v in offs], [int(v) for v in lens]
+    points = [(int(k), int(v)) for k, v in points]
+    n_cls, n_rep, n_pts = len(lens), counts.shape[0], len(points)
+    if len(offs) != n_cls or any(n < 0 or o < 0 or o + n > order.numel() for o, n in zip(offs, lens)):
+        raise ValueError("boot_sweep: offsets %s / lengths %s do not fit an order array of %d entries" % (offs, lens, order.numel()))
+    if n_pts > BOOT_MAX_POINTS or any(k not in (BOOT_SENS, BOOT_SPEC) or not 1 <= v <= 999999 for k, v in points):
+        raise ValueError("boot_sweep: at most %d operating points (BOOT_SENS | BOOT_SPEC, 1 .. 999999 millionths), got %s"
+                         % (BOOT_MAX_POINTS, points))
+    apnum = torch.empty(n_rep, n_cls, dtype=torch.int64, device=counts.device)
+    wpos = torch.empty(n_rep, n_cls, dtype=torch.int32, device=counts.device)
+    wneg = torch.empty_like(wpos)
+    pts = torch.empty(n_rep, n_cls, n_pts, dtype=torch.int32, device=counts.device)
+    if n_rep == 0:
+        return apnum, wpos.long(), wneg.long(), pts.long()
+    ld = counts.stride(0) if n_rep > 1 else counts.shape[1]
+    check(lib().cx_boot_sweep(ptr(counts), ld, n_rep, ptr(order), (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens), n_cls,
+                              (C.c_int32 * max(n_pts, 1))(*[k for k, _ in points]), (C.c_int32 * max(n_pts, 1))(*[v for _, v in points]),
+                              n_pts, ptr(apnum), ptr(wpos), ptr(wneg), ptr(pts) if n_pts else None, int(n_units), stream_ptr()),
+          "cx_boot_sweep")
+    return apnum, wpos.long() & 0xffffffff, wneg.long() & 0xffffffff, pts.long() & 0xffffffff      # the kernel's unsigned values
+
+
 # ---- pixel attribution maps (saliency.hip; chexpert_amd/saliency.py composes them and states them in numpy) ----
 SAL_MODES = {"none": 0, "sum": 1, "abs": 2, "max": 3}      # CX_SAL_NONE .. CX_SAL_MAX of the header
 SAL_PARTIALS = 128                                          # CX_SAL_PARTIALS

@@ -788,6 +788,34 @@ int cx_boot_counts(uint32_t* counts, int ld, int U, int first, int n_rep, uint64
 int cx_boot_auc(const uint32_t* counts, int ld, int n_rep, const int32_t* order /* device */, const int64_t* offs /* host, [C] */,
                 const int32_t* len /* host, [C] */, int C, uint64_t* num2, uint32_t* wpos, uint32_t* wneg, int U, void* stream);
 
+/* The threshold sweep of the same bootstrap (bootstrap.hip; chexpert_amd/metrics.py: bootstrap_metrics, and the numpy statement
+ * bootstrap_sweep_reference, held bit for bit): average precision and fixed operating points of every (replicate, class), in integers.
+ * For class c the caller lists the kept rows ONCE, descending in score (metrics.bootstrap_sweep_plan): an entry is the row's unit index
+ * with the label in bit 31 and bit 30 set on the LAST entry of its tie group (the order inside a group is immaterial).  order (device)
+ * holds len[c] entries for class c from order[offs[c]]; offs and len are HOST arrays.  With w = counts[r][unit], tp_g / fp_g = the
+ * positive / negative weight up to and including the marked entry g, tp_0 = fp_0 = 0, W+ / W- the totals:
+ *   apnum[r][c] = sum over marked g of (tp_g - tp_{g-1}) * floor((tp_g << 32) / (tp_g + fp_g))      (uint64; a term with tp_g = tp_{g-1} is 0
+ *                 and does not divide);  AP = apnum / (W+ * 2^32), the step sum of the precision-recall curve, below the exact value
+ *                 by less than 2^-32 (every floor loses less than 2^-32 of its step's weight); W+ = 0: no AP
+ *   wpos[r][c] = W+,  wneg[r][c] = W-
+ *   pts[r][c][k], for operating point k with s = pt_ppm[k] millionths (1 .. 999 999), over the marked entries and the point (0, 0):
+ *     pt_type[k] == CX_BOOT_SENS: max{tp_g : fp_g * 10^6 <= (10^6 - s) * W-}    sensitivity at specificity >= s = pts / W+
+ *     pt_type[k] == CX_BOOT_SPEC: min{fp_g : tp_g * 10^6 >= s * W+}              specificity at sensitivity >= s = 1 - pts / W-
+ *     (uint64 comparisons; both values need W+ > 0 and W- > 0; the set of the minimum is never empty: the last entry is marked, and
+ *     with W+ = 0 the point (0, 0) qualifies).
+ * pt_type / pt_ppm are HOST arrays of P <= CX_BOOT_MAX_POINTS entries; P = 0 (pt_type, pt_ppm, pts may then be NULL) computes apnum,
+ * wpos and wneg only and reads the entries once instead of twice: W+ and W- of the conditions come from a first pass of the kernel over
+ * the same entries, never from the caller.  Outputs are row-major (n_rep, C) and (n_rep, C, P), one writer per element.  Unit indices
+ * >= U are CLAMPED to U - 1.  Requirement: the sum of a count row is < 2^32, which also keeps apnum below 2^64.  One wave per
+ * (replicate, class); no LDS, no atomics.
+ * CX_EINVAL: a null pointer, n_rep < 1, C < 1, a negative len[c] or offs[c], a pt_type that is neither constant, a pt_ppm outside
+ * [1, 999 999].  CX_ESHAPE: P outside [0, CX_BOOT_MAX_POINTS], U outside [1, CX_BOOT_MAX_UNITS], ld < U.  CX_EALIGN: counts / order /
+ * wpos / wneg / pts not 4-byte, apnum not 8-byte aligned.  Additive entry point of ABI 10.                                          */
+enum { CX_BOOT_MAX_POINTS = 8, CX_BOOT_SENS = 0, CX_BOOT_SPEC = 1 };
+int cx_boot_sweep(const uint32_t* counts, int ld, int n_rep, const int32_t* order /* device */, const int64_t* offs /* host, [C] */,
+                  const int32_t* len /* host, [C] */, int C, const int32_t* pt_type /* host, [P] */, const int32_t* pt_ppm /* host, [P] */,
+                  int P, uint64_t* apnum, uint32_t* wpos, uint32_t* wneg, uint32_t* pts, int U, void* stream);
+
 /* Pixel attribution maps (saliency.hip; chexpert_amd/saliency.py: input_gradient, smoothgrad, integrated_gradients, and the numpy
  * statement of the three entry points, points_reference / accumulate_reference / finish_reference): the glue around the eval-mode
  * forward + backward with dx.  fp32 NCHW, N = 3 * H * W floats per row; every product and every sum below is rounded to fp32 on its
