@@ -38,16 +38,25 @@ __device__ __forceinline__ int wrapq(int v, int q) { return v >= q ? v - q : v; 
 // step index / steps per image by multiply-high; spi == 1 (a whole image per step: small maps) has no 32-bit magic number (2^32)
 __device__ __forceinline__ int div_spi(const RingGeo& g, int v) { return g.spi == 1 ? v : (int)__umulhi((unsigned)v, g.mSpi); }
 
+// Per-lane statistic sums -> sums over the 32 lanes of each wave half, 16 values at once: lane l of a half ends with the sum of
+// v[l & 15].  The tree over lanes is balanced and in lane order (pairs, quads, 8, 16, 32 lanes -- what a butterfly of one value over
+// quad_perm / row mirrors / xor 16 gives, and what the statistic rows and golden fixtures were recorded with), but each level
+// passes on only the half of the values its lane still answers for: 15 exchanges for 16 values instead of 80.
 template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float half_sum(float v) {      // sum over the 32 lanes of each wave half
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);
-  v = dpp_add<0x140>(v);
-  return v + __shfl_xor(v, 16);
+__device__ __forceinline__ float dpp_get(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
+template <int XOR>
+__device__ __forceinline__ float swz_xor(float v) { return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (XOR << 10) | 0x1F)); }
+__device__ __forceinline__ float half_sum16(const float (&v)[16], int lane) {
+  const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
+  float a[8], b[4], c[2];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) a[k] = (b0 ? v[2 * k + 1] : v[2 * k]) + dpp_get<0xB1>(b0 ? v[2 * k] : v[2 * k + 1]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) b[k] = (b1 ? a[2 * k + 1] : a[2 * k]) + dpp_get<0x4E>(b1 ? a[2 * k] : a[2 * k + 1]);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) c[k] = (b2 ? b[2 * k + 1] : b[2 * k]) + swz_xor<4>(b2 ? b[2 * k] : b[2 * k + 1]);
+  const float d = (b3 ? c[1] : c[0]) + swz_xor<8>(b3 ? c[0] : c[1]);
+  return d + swz_xor<16>(d);
 }
 
 #ifdef CX_RING_STAMPS
@@ -62,8 +71,26 @@ __device__ __forceinline__ unsigned long long rstamp() {
   return t;
 }
 #define RSTAMP(i) { const unsigned long long t_ = rstamp(); st_acc[i] += t_ - st_prev; st_prev = t_; }
+// outside the step loop: [0] kernel entry -> end of the one-time setup, [1] from there -> first MFMA of the first step, [2] end of the
+// last step -> kernel end, [3] whole kernel in s_memtime ticks, [4] whole kernel in s_memrealtime ticks (100 MHz): [3] / [4] x 100 MHz
+// is the clock the other figures count in
+__device__ unsigned long long ring_pro_stamps[1024 * 8];
+__device__ unsigned long long ring_fwd_pro_stamps[1024 * 8];
+#define PSTAMP_BEGIN unsigned long long ps_acc[3] = {0, 0, 0}; const unsigned long long ps_rt0 = __builtin_amdgcn_s_memrealtime(), ps_t0 = rstamp(); \
+  unsigned long long ps_prev = ps_t0; bool ps_first = true;
+#define PSTAMP(i) { const unsigned long long t_ = rstamp(); ps_acc[i] = t_ - ps_prev; ps_prev = t_; }
+#define PSTAMP_FIRST_MFMA if (ps_first) { PSTAMP(1) ps_first = false; }
+#define PSTAMP_MARK ps_prev = rstamp();
+#define PSTAMP_END(arr) { PSTAMP(2) const unsigned long long rt_ = __builtin_amdgcn_s_memrealtime(); \
+  if (threadIdx.x == 0 && blockIdx.x < 1024) { for (int i = 0; i < 3; ++i) arr[blockIdx.x * 8 + i] = ps_acc[i]; \
+    arr[blockIdx.x * 8 + 3] = ps_prev - ps_t0; arr[blockIdx.x * 8 + 4] = rt_ - ps_rt0; } }
 #else
 #define RSTAMP(i)
+#define PSTAMP_BEGIN
+#define PSTAMP(i)
+#define PSTAMP_FIRST_MFMA
+#define PSTAMP_MARK
+#define PSTAMP_END(arr)
 #endif
 template <int NCH, int DEPTH>
 __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __restrict__ x, int ldx, const float* __restrict__ sc,
@@ -77,15 +104,25 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lrow = lane & 31, lh = lane >> 5;
   const int P = g.P, R = g.R, Q = g.Q, W = g.W, H = g.H, Wt = g.Wt, ntx = g.ntx;       // W: image width, Wt = P - 2: column-tile width
+  PSTAMP_BEGIN
 
-  // ---- one-time setup: weights [tap][n][k] -> LDS rows of 272 B, ring zeroed (pad columns stay zero), coefficients
-  for (int i = tid; i < W_ROWS * 16; i += NT) {
-    const int row = i >> 4, c = i & 15;
-    *reinterpret_cast<uint4*>(wl + row * XP + c * 16) = *reinterpret_cast<const uint4*>(wpk + (size_t)row * 128 + c * 8);
+  // ---- prologue order (it matters on the small maps, where a workgroup has one or two steps to amortise it): everything whose
+  // address does not depend on LDS contents -- the BN coefficients, the whole first window, the nine weight slices -- is requested
+  // before anything is consumed, so the launch no longer pays a chain of dependent global round trips (weights chunk by chunk,
+  // coefficients, window row yc-1, row yc, step rows) before its first MFMA.  (As compiled the weight requests follow the wait for
+  // the first row: two round trips, profiles/ring_prologue_stamps.txt.)  The ring is not zeroed: the first window of an image writes
+  // every ring pixel that is read (halo columns and rows outside the image are staged as zeros, the two mirror pixels with ring
+  // pixels 0 and 1), and the step's own barrier is the first one.
+  // weights [tap][n][k] -> LDS rows of 272 B: all of a thread's loads are requested first of all, stored after the other requests
+  static_assert((W_ROWS * 16) % NT == 0, "whole weight chunks per thread");
+  constexpr int WCH = W_ROWS * 16 / NT;
+  uint4 wv[WCH];
+#pragma unroll
+  for (int j = 0; j < WCH; ++j) {
+    const int i = tid + NT * j;
+    wv[j] = *reinterpret_cast<const uint4*>(wpk + (size_t)(i >> 4) * 128 + (i & 15) * 8);
   }
-  for (int i = tid; i < (Q + 2) * (XP / 16); i += NT) reinterpret_cast<uint4*>(ring)[i] = make_uint4(0, 0, 0, 0);
-  __syncthreads();
-
+  __builtin_amdgcn_sched_barrier(0);
   const int total_steps = g.B * g.spi;
   const int u0 = blockIdx.x * g.steps_per_wg;
   const int u1 = min(total_steps, u0 + g.steps_per_wg);
@@ -95,6 +132,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __r
   // step is one image row and shorter than an HBM round trip under load)
   uint4 pre[DEPTH][NCH];
   bool pv[DEPTH][NCH];
+  constexpr int HN = NCH < 3 ? NCH : 3;
+  uint4 hal[HN];              // window rows yc-1, yc of an image restart (live between their request and their staging only)
+  bool hv[HN];
   int base_row = 0;           // image row held by ring slot 0: slot(y) = (y - base_row) mod (R+2)
   // chunk slot i of this thread: chunk id tid + NT*i -> (row inside the group of new rows, pixel, 16-B channel chunk).  NT and
   // 16*W are multiples of 16, so the channel chunk is tid & 15 for every slot: its BN scale/shift stay in registers
@@ -109,10 +149,6 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __r
   float csc[8], csh[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { csc[j] = sc[cc8 * 8 + j]; csh[j] = sh[cc8 * 8 + j]; }
-  // retire these loads here: a load still pending at the loop header makes every first use inside the loop a vmcnt(0), which
-  // drains the DEPTH row sets in flight each step
-#pragma unroll
-  for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(csc[j]), "v"(csh[j]));
   // rows [y0, y0+n) of column tile bv = image * ntx + tile -> registers (ring position p of a row is image column x0 - 1 + p);
   // unconditional loads on clamped addresses, validity applied when staged
   // A chunk's byte offset inside the row group is a constant of the thread (voff); the group's own offset is wave-uniform.  Chunks
@@ -123,22 +159,25 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __r
 #pragma unroll
   for (int i = 0; i < NCH; ++i) voff[i] = ((uint32_t)(crow[i] * W + cpx[i]) * (uint32_t)ldx + (uint32_t)cc8 * 8u) * 2u;
   const char* __restrict__ xb = reinterpret_cast<const char*>(x);
-  auto issue_rows = [&](uint4 (&pre)[NCH], bool (&pv)[NCH], int bv, int y0, int n) __attribute__((always_inline)) {
+  // (ns: chunk slots that can hold a row < n -- NCH for the R rows of a step, fewer for the two halo rows of a restart)
+  auto issue_rows = [&](auto& pre, auto& pv, int bv, int y0, int n, int ns) __attribute__((always_inline)) {
+    constexpr int NS = (int)(sizeof(pv) / sizeof(pv[0]));
     const int b = bv >> g.ntx_shift, x0 = (bv - (b << g.ntx_shift)) * Wt - 1;
     const uint32_t sbase = (uint32_t)((b * H + y0) * W + x0) * (uint32_t)ldx * 2u;      // (wraps for y0 = -1 / x0 = -1: only valid chunks use it)
     const uint32_t r_lo = (uint32_t)max(-y0, 0), r_n = (uint32_t)max(min(n, H - y0), 0) - r_lo;      // rows  [r_lo, r_lo + r_n)
     const uint32_t c_lo = (uint32_t)max(-x0, 0), c_n = (uint32_t)max(W - x0, 0) - c_lo;              // pixels [c_lo, c_lo + c_n)
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
+    for (int i = 0; i < NS; ++i) {
       pv[i] = ((uint32_t)crow[i] - r_lo) < r_n && ((uint32_t)cpx[i] - c_lo) < c_n;
-      pre[i] = *reinterpret_cast<const uint4*>(xb + (size_t)(pv[i] ? sbase + voff[i] : 0u));
+      if (i < ns) pre[i] = *reinterpret_cast<const uint4*>(xb + (size_t)(pv[i] ? sbase + voff[i] : 0u));
     }
   };
-  auto write_rows = [&](uint4 (&pre)[NCH], bool (&pv)[NCH], int y0, int n) __attribute__((always_inline)) {
+  auto write_rows = [&](auto& pre, auto& pv, int y0, int n, int P) __attribute__((always_inline)) {
+    constexpr int NS = (int)(sizeof(pv) / sizeof(pv[0]));
     int slot_y0 = (y0 - base_row) % (R + 2);          // wave-uniform
     if (slot_y0 < 0) slot_y0 += R + 2;
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
+    for (int i = 0; i < NS; ++i) {
       if (crow[i] < n) {
         int slot = slot_y0 + crow[i];                   // crow <= R: one conditional subtract wraps it
         if (slot >= R + 2) slot -= R + 2;
@@ -156,8 +195,66 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __r
   auto issue_step = [&](uint4 (&pre)[NCH], bool (&pv)[NCH], int v) __attribute__((always_inline)) {
     const int bv = div_spi(g, v), sv = v - bv * g.spi;
     const bool ok = v < ulim && sv != 0;
-    issue_rows(pre, pv, ok ? bv : 0, ok ? sv * R + 1 : 0, ok ? R : 0);
+    issue_rows(pre, pv, ok ? bv : 0, ok ? sv * R + 1 : 0, ok ? R : 0, NCH);
   };
+  // Restart of an image (or of the part of it in this workgroup's range): the window rows yc-1, yc (one group of two rows in hal),
+  // the R new rows of the first step and the row groups of the next DEPTH-1 steps are requested in one burst, then the two window
+  // rows are staged (the R rows by the step itself).  Where the two rows need more than hal's HN chunk slots (column tiles wider
+  // than 46 pixels) there are two bursts: the window rows in the step's own register sets, then the step rows.
+  const bool halo2 = 2 * chunks_per_row <= HN * NT;
+  const int halo_ns = (2 * chunks_per_row + NT - 1) / NT;
+  auto issue_refill = [&](int ui, int b, int yc) __attribute__((always_inline)) {
+    issue_rows(pre[0], pv[0], b, yc + 1, R, NCH);
+#pragma unroll
+    for (int d = 1; d < DEPTH; ++d) issue_step(pre[d], pv[d], ui + d);
+  };
+  auto restart_issue = [&](int ui) __attribute__((always_inline)) {
+    const int b = div_spi(g, ui), yc = (ui - b * g.spi) * R;
+    if (halo2) {
+      issue_rows(hal, hv, b, yc - 1, 2, halo_ns);
+      issue_refill(ui, b, yc);
+    } else if constexpr (DEPTH == 1) {
+      issue_rows(pre[0], pv[0], b, yc - 1, 2, NCH);     // (NCH = 7 holds two rows of any tile the ring has room for)
+    } else {
+      issue_rows(pre[1], pv[1], b, yc - 1, 1, NCH);
+      issue_rows(pre[0], pv[0], b, yc, 1, NCH);
+    }
+  };
+  auto restart_stage = [&](int ui) __attribute__((always_inline)) {
+    const int b = div_spi(g, ui), yc = (ui - b * g.spi) * R;
+    base_row = yc - 1;
+    // (row count and pitch through an opaque copy: the per-slot masks and ring addresses of a restart are otherwise hoisted out of
+    // every loop as invariants and held -- spilled -- across the step loop)
+    int n1 = 1, n2 = 2, Pq = P;
+    asm volatile("" : "+s"(n1), "+s"(n2), "+s"(Pq));
+    if (halo2) {
+      write_rows(hal, hv, yc - 1, n2, Pq);
+    } else {
+      if constexpr (DEPTH == 1) {
+        write_rows(pre[0], pv[0], yc - 1, n2, Pq);
+      } else {
+        write_rows(pre[1], pv[1], yc - 1, n1, Pq);
+        write_rows(pre[0], pv[0], yc, n1, Pq);
+      }
+      issue_refill(ui, b, yc);
+    }
+  };
+
+  // The range is walked from a per-workgroup offset and wraps (two passes): with every workgroup starting at row 0 of its
+  // own image, all 256 read addresses that differ by multiples of the image size at the same moment.
+  const int rot = u1 - u0 > 1 ? (int)((blockIdx.x * 37u) % (unsigned)(u1 - u0)) : 0;
+  restart_issue(u0 + rot);                            // the first window goes out with the weights
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int j = 0; j < WCH; ++j) {
+    const int i = tid + NT * j;
+    *reinterpret_cast<uint4*>(wl + (i >> 4) * XP + (i & 15) * 16) = wv[j];
+  }
+  // retire the coefficient loads here: a load still pending at the loop header makes every first use inside the loop a vmcnt(0),
+  // which drains the DEPTH row sets in flight each step
+#pragma unroll
+  for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(csc[j]), "v"(csh[j]));
+  PSTAMP(0)
 
   float s1[2][8], s2[2][8];
 #pragma unroll
@@ -177,12 +274,13 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __r
     const int bv = div_spi(g, u), yc = (u - bv * g.spi) * R;
     const int b = bv >> g.ntx_shift, x0 = (bv - (b << g.ntx_shift)) * Wt;
     RSTAMP(0)                                          // (between steps: restart of an image, loop overhead)
-    write_rows(cur, cv, yc + 1, R);
+    write_rows(cur, cv, yc + 1, R, P);
     RSTAMP(1)
     __syncthreads();                                   // the window of this step is complete
     RSTAMP(2)
     issue_step(cur, cv, u + DEPTH);                    // in flight under the MFMAs of this and the next DEPTH-1 steps
     RSTAMP(3)
+    PSTAMP_FIRST_MFMA
     int slot0 = (yc - 1 - base_row) % (R + 2);
     if (slot0 < 0) slot0 += R + 2;
     const int ws = slot0 * P;
@@ -257,27 +355,18 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __r
 #endif
   };
 
-  // One image (or the part of it in this workgroup's range) at a time: the window rows yc-1, yc of its first step are built
-  // synchronously and the pipeline is refilled outside the step loop.
-  // The range is walked from a per-workgroup offset and wraps (two passes): with every workgroup starting at row 0 of its
-  // own image, all 256 read addresses that differ by multiples of the image size at the same moment.
-  const int rot = u1 - u0 > 1 ? (int)((blockIdx.x * 37u) % (unsigned)(u1 - u0)) : 0;
+  // One image (or the part of it in this workgroup's range) at a time: its first window is rebuilt and the pipeline refilled
+  // outside the step loop.
+  bool first = true;
 #pragma unroll 1
   for (int pass = 0; pass < 2; ++pass) {
   ulim = pass == 0 ? u1 : u0 + rot;
   for (int ui = pass == 0 ? u0 + rot : u0; ui < ulim;) {
-    const int b = div_spi(g, ui), yc = (ui - b * g.spi) * R;
+    const int b = div_spi(g, ui);
     const int ue = min(ulim, (b + 1) * g.spi);
-    base_row = yc - 1;
-    auto sync_rows = [&](int y0) __attribute__((always_inline)) {
-      issue_rows(pre[0], pv[0], b, y0, 1);
-      write_rows(pre[0], pv[0], y0, 1);
-    };
-    sync_rows(yc - 1);
-    sync_rows(yc);
-    issue_rows(pre[0], pv[0], b, yc + 1, R);
-#pragma unroll
-    for (int d = 1; d < DEPTH; ++d) issue_step(pre[d], pv[d], ui + d);
+    if (!first) restart_issue(ui);
+    first = false;
+    restart_stage(ui);
     for (int u = ui; u < ue; u += DEPTH) {
       step(u, std::integral_constant<int, 0>());
       if (DEPTH > 1) { if (u + 1 >= ue) break; step(u + 1, std::integral_constant<int, 1 % DEPTH>()); }
@@ -286,6 +375,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __r
     ui = ue;
   }
   }
+  PSTAMP_MARK
 
 #ifdef CX_RING_STAMPS
   if (tid == 0 && blockIdx.x < 1024) {
@@ -294,23 +384,23 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_fwd_kernel(const bf16* __r
   }
 #endif
   if (stat_sum) {
-    float* scratch = reinterpret_cast<float*>(wl);               // the weight slices are no longer read
-    wg_stat_begin<NT / 64>(scratch, 32, tid, NT);
-    float t1 = 0.f, t2 = 0.f;
+    // the weight slices are no longer read (every wave is past the last step's barrier).  A wave stores all 32 channels of its two
+    // scratch rows itself, so the rows need no zeroing and no barrier ahead of the stores.
+    float* scratch = reinterpret_cast<float*>(wl);
+    float f1[16], f2[16];
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float a = half_sum(s1[cc][j]);
-        const float c = half_sum(s2[cc][j]);
-        if (lrow == 8 * cc + j) { t1 = a; t2 = c; }
-      }
+      for (int j = 0; j < 8; ++j) { f1[8 * cc + j] = s1[cc][j]; f2[8 * cc + j] = s2[cc][j]; }
+    const float t1 = half_sum16(f1, lane), t2 = half_sum16(f2, lane);      // lanes lrow < 16: the sums of value 8*cc + j = lrow
     if (lrow < 16) {
       const int n = 8 * (2 * (lrow >> 3) + lh) + (lrow & 7);
-      wg_stat_put(scratch, 32, wave, n, t1, t2);
+      scratch[(wave * 2) * 32 + n] = t1;
+      scratch[(wave * 2 + 1) * 32 + n] = t2;
     }
     wg_stat_end<NT / 64>(scratch, 32, tid, NT, stat_sum, stat_sq, stat_det, (int)blockIdx.x, stat_replicas, stat_rstride, 0, 32);
   }
+  PSTAMP_END(ring_fwd_pro_stamps)
 }
 
 template <int NCH, int DEPTH>
@@ -359,28 +449,32 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_dgrad_kernel(
   const int lrow = lane & 31, lh = lane >> 5;
   const int h2 = wave & 1;                                     // this wave's half of the output channels
   const int P = g.P, R = g.R, Q = g.Q, W = g.W, H = g.H;
+  PSTAMP_BEGIN
 
-  for (int i = tid; i < DW_ROWS * 4; i += NT) {
-    const int row = i >> 2, c = i & 3;
-    *reinterpret_cast<uint4*>(wl + row * GP + c * 16) = *reinterpret_cast<const uint4*>(wpk + (size_t)row * 32 + c * 8);
+  // ---- prologue order as in the forward kernel: the coefficient vectors, the whole first window and the nine weight slices are
+  // requested in one burst, then consumed; no barrier before the one of the first step.  Only the ring pixels that no staging writes
+  // are zeroed (the pad columns of every slot and the first mirror pixel); a restart writes all the others.
+  // weights -> LDS rows of 80 B: all of a thread's loads are requested first of all, stored after the other requests
+  static_assert((DW_ROWS * 4) % NT == 0, "whole weight chunks per thread");
+  constexpr int WCH = DW_ROWS * 4 / NT;
+  uint4 wv[WCH];
+#pragma unroll
+  for (int j = 0; j < WCH; ++j) {
+    const int i = tid + NT * j;
+    wv[j] = *reinterpret_cast<const uint4*>(wpk + (size_t)(i >> 2) * 32 + (i & 3) * 8);
   }
-  for (int i = tid; i < (Q + 2) * (GP / 16); i += NT) reinterpret_cast<uint4*>(ring)[i] = make_uint4(0, 0, 0, 0);
-  if (tid < 128) {
-    ecoef[tid] = e_sc[tid]; ecoef[128 + tid] = e_sh[tid]; ecoef[256 + tid] = e_mu[tid]; ecoef[384 + tid] = e_r[tid];
-    ecoef[512 + tid] = e_scale[tid];
-  }
-  if (tid < 32) { ecoef[640 + tid] = ga[tid]; ecoef[672 + tid] = gb[tid]; ecoef[704 + tid] = gc[tid]; }
-  __syncthreads();
-
+  __builtin_amdgcn_sched_barrier(0);
   const int total_steps = g.B * g.spi;
   const int u0 = blockIdx.x * g.steps_per_wg;
   const int u1 = min(total_steps, u0 + g.steps_per_wg);
   const int cpr = W * 4;
 
   // new gradient rows: chunk slot i of this thread = chunk id tid + NT*i -> (row, pixel); the channel chunk is tid & 3 for
-  // every slot (NT and 4*W are multiples of 4), so its AFFINE2 coefficients stay in registers
+  // every slot (NT and 4*W are multiples of 4), so one LDS address holds its AFFINE2 coefficients
   uint4 pg[NCH], pg2[NCH];
   bool gv[NCH];
+  uint4 hg[NCH], hg2[NCH];    // window rows yc-1, yc of an image restart (live between their request and their staging only)
+  bool hgv[NCH];
   int base_row = 0;
   int crow[NCH], cpx[NCH];
   const int cc4 = tid & 3;
@@ -390,7 +484,13 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_dgrad_kernel(
     crow[i] = cid / cpr;
     cpx[i] = (cid - crow[i] * cpr) >> 2;
   }
-  const float* kco = ecoef + 640 + cc4 * 8;          // ga | gb | gc of this thread's channel chunk (LDS)
+  float* kco = ecoef + 640 + cc4 * 8;                // ga | gb | gc of this thread's channel chunk (LDS)
+  float ev[5], kv[3][8];
+  if (tid < 128) { ev[0] = e_sc[tid]; ev[1] = e_sh[tid]; ev[2] = e_mu[tid]; ev[3] = e_r[tid]; ev[4] = e_scale[tid]; }
+  // every thread fetches the 24 AFFINE2 coefficients of its channel chunk and stores them itself (128 threads write the same values
+  // to the same words): its own stores are visible to its own staging without a barrier
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { kv[0][j] = ga[cc4 * 8 + j]; kv[1][j] = gb[cc4 * 8 + j]; kv[2][j] = gc[cc4 * 8 + j]; }
 
   // (chunk offsets inside the row group are constants of the thread, the group's offset is wave-uniform; rows outside the image
   // read offset 0 and are zeroed when staged -- see the forward kernel)
@@ -402,7 +502,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_dgrad_kernel(
   }
   const char* __restrict__ gslb = reinterpret_cast<const char*>(gsl);
   const char* __restrict__ g2b = reinterpret_cast<const char*>(g2);
-  auto issue_rows = [&](int b, int y0, int n) __attribute__((always_inline)) {
+  auto issue_rows = [&](uint4 (&pg)[NCH], uint4 (&pg2)[NCH], bool (&gv)[NCH], int b, int y0, int n) __attribute__((always_inline)) {
     const uint32_t row0 = (uint32_t)((b * H + y0) * W);
     const uint32_t sg = row0 * (uint32_t)ldg * 2u, sg2 = row0 * (uint32_t)ldg2 * 2u;
     const uint32_t r_lo = (uint32_t)max(-y0, 0), r_n = (uint32_t)max(min(n, H - y0), 0) - r_lo;
@@ -413,7 +513,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_dgrad_kernel(
       pg2[i] = *reinterpret_cast<const uint4*>(g2b + (size_t)(gv[i] ? sg2 + vog2[i] : 0u));
     }
   };
-  auto write_rows = [&](int b, int y0, int n) __attribute__((always_inline)) {
+  auto write_rows = [&](uint4 (&pg)[NCH], uint4 (&pg2)[NCH], bool (&gv)[NCH], int b, int y0, int n, int P) __attribute__((always_inline)) {
     int slot_y0 = (y0 - base_row) % (R + 2);
     if (slot_y0 < 0) slot_y0 += R + 2;
 #pragma unroll
@@ -433,6 +533,55 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_dgrad_kernel(
       }
     }
   };
+  // Restart of an image: the window rows yc-1, yc and the R new rows of its first step go out in one burst, then the two window
+  // rows are staged (the R rows by the step itself).  Where two rows do not fit the chunk slots (R = 1: maps wider than 128
+  // pixels) there are two bursts: the window rows one each in hg / pg, then the step rows.
+  const bool halo2 = 2 * cpr <= NCH * NT;
+  auto restart_issue = [&](int b, int yc) __attribute__((always_inline)) {
+    if (halo2) {
+      issue_rows(hg, hg2, hgv, b, yc - 1, 2);
+      issue_rows(pg, pg2, gv, b, yc + 1, R);
+    } else {
+      issue_rows(hg, hg2, hgv, b, yc - 1, 1);
+      issue_rows(pg, pg2, gv, b, yc, 1);
+    }
+  };
+  auto restart_stage = [&](int b, int yc) __attribute__((always_inline)) {
+    base_row = yc - 1;
+    int n1 = 1, n2 = 2, Pq = P;                        // (opaque copies: see the forward kernel)
+    asm volatile("" : "+s"(n1), "+s"(n2), "+s"(Pq));
+    if (halo2) {
+      write_rows(hg, hg2, hgv, b, yc - 1, n2, Pq);
+    } else {
+      write_rows(hg, hg2, hgv, b, yc - 1, n1, Pq);
+      write_rows(pg, pg2, gv, b, yc, n1, Pq);
+      issue_rows(pg, pg2, gv, b, yc + 1, R);
+    }
+  };
+
+  {
+    const int b0 = div_spi(g, u0);
+    restart_issue(b0, (u0 - b0 * g.spi) * R);         // the first window goes out with the weights
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  // coefficient vectors and weights -> LDS, pad pixels zeroed
+#pragma unroll
+  for (int j = 0; j < WCH; ++j) {
+    const int i = tid + NT * j;
+    *reinterpret_cast<uint4*>(wl + (i >> 2) * GP + (i & 3) * 16) = wv[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { kco[j] = kv[0][j]; kco[32 + j] = kv[1][j]; kco[64 + j] = kv[2][j]; }
+  if (tid < 128) {
+    ecoef[tid] = ev[0]; ecoef[128 + tid] = ev[1]; ecoef[256 + tid] = ev[2]; ecoef[384 + tid] = ev[3]; ecoef[512 + tid] = ev[4];
+  }
+  // ring pixels outside every staging: pad columns 0 and P-1 of the R+2 slots, mirror pixel Q (pixel Q+1 mirrors a staged one)
+  for (int i = tid; i < (2 * (R + 2) + 1) * 4; i += NT) {
+    const int k = i >> 2;
+    const int pos = k == 2 * (R + 2) ? Q : (k >> 1) * P + (k & 1) * (P - 1);
+    *reinterpret_cast<uint4*>(ring + pos * GP + (i & 3) * 16) = make_uint4(0, 0, 0, 0);
+  }
+  PSTAMP(0)
 
   float s1[2][2][8], s2[2][2][8];
 #pragma unroll
@@ -450,21 +599,18 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_dgrad_kernel(
   for (int u = u0; u < u1; ++u) {
     const int b = div_spi(g, u), yc = (u - b * g.spi) * R;
     if (u == u0 || yc == 0) {
-      base_row = yc - 1;
-      issue_rows(b, yc - 1, 1);
-      write_rows(b, yc - 1, 1);
-      issue_rows(b, yc, 1);
-      write_rows(b, yc, 1);
-      issue_rows(b, yc + 1, R);
+      if (u != u0) restart_issue(b, yc);
+      restart_stage(b, yc);
     }
     RSTAMP(0)
-    write_rows(b, yc + 1, R);
+    write_rows(pg, pg2, gv, b, yc + 1, R, P);
     RSTAMP(1)
     __syncthreads();                                   // the window of this step is complete
     RSTAMP(2)
     const bool next_cont = (u + 1 < u1) && (div_spi(g, u + 1) == b);
-    if (next_cont) issue_rows(b, yc + R + 1, R);
+    if (next_cont) issue_rows(pg, pg2, gv, b, yc + R + 1, R);
     RSTAMP(3)
+    PSTAMP_FIRST_MFMA
     int slot0 = (yc - 1 - base_row) % (R + 2);
     if (slot0 < 0) slot0 += R + 2;
     const int ws = slot0 * P;
@@ -575,6 +721,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_dgrad_kernel(
     __syncthreads();                                   // every wave is done with the oldest rows of the ring
     RSTAMP(6)
   }
+  PSTAMP_MARK
 #ifdef CX_RING_STAMPS
   if (tid == 0 && blockIdx.x < 1024) {
     for (int i = 0; i < 7; ++i) ring_stamps[blockIdx.x * 8 + i] = st_acc[i];
@@ -583,26 +730,28 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_ring_dgrad_kernel(
 #endif
 
   {
-    float* scratch = reinterpret_cast<float*>(wl);               // the weight slices are no longer read (ecoef stays)
-    wg_stat_begin<NT / 64>(scratch, 128, tid, NT);
+    // the weight slices are no longer read (every wave is past the last step's barrier; ecoef stays).  A wave stores the 64 channels
+    // of its half and zeros for the other half itself, so its two scratch rows need no zeroing pass and no barrier ahead of the stores.
+    float* scratch = reinterpret_cast<float*>(wl);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      float t1 = 0.f, t2 = 0.f;
+      float f1[16], f2[16];
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float a = half_sum(s1[j][cc][e]);
-          const float c = half_sum(s2[j][cc][e]);
-          if (lrow == 8 * cc + e) { t1 = a; t2 = c; }
-        }
+        for (int e = 0; e < 8; ++e) { f1[8 * cc + e] = s1[j][cc][e]; f2[8 * cc + e] = s2[j][cc][e]; }
+      const float t1 = half_sum16(f1, lane), t2 = half_sum16(f2, lane);    // lanes lrow < 16: the sums of value 8*cc + e = lrow
       if (lrow < 16) {
         const int n = (2 * h2 + j) * 32 + 8 * (2 * (lrow >> 3) + lh) + (lrow & 7);
-        wg_stat_put(scratch, 128, wave, n, t1, ecoef[384 + n] * (t2 - ecoef[256 + n] * t1));
+        scratch[(wave * 2) * 128 + n] = t1;
+        scratch[(wave * 2 + 1) * 128 + n] = ecoef[384 + n] * (t2 - ecoef[256 + n] * t1);
+        scratch[(wave * 2) * 128 + (n ^ 64)] = 0.f;
+        scratch[(wave * 2 + 1) * 128 + (n ^ 64)] = 0.f;
       }
     }
     wg_stat_end<NT / 64>(scratch, 128, tid, NT, S1, S2, stat_det, (int)blockIdx.x, stat_replicas, stat_rstride, 0, 128);
   }
+  PSTAMP_END(ring_pro_stamps)
 }
 
 template <int NCH>
@@ -982,5 +1131,9 @@ extern "C" int dbg_ring_stamps(unsigned long long* host, int n_words) {
 }
 extern "C" int dbg_ring_fwd_stamps(unsigned long long* host, int n_words) {
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ring_fwd_stamps), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
+}
+extern "C" int dbg_ring_pro_stamps(unsigned long long* host, int n_words, int fwd) {
+  return fwd ? (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ring_fwd_pro_stamps), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost)
+             : (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ring_pro_stamps), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
 }
 #endif

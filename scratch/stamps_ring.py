@@ -1,13 +1,24 @@
-"""Phase shares of the 3x3 input-gradient ring kernel (diagnostic build -DCX_RING_STAMPS, scratch/libstamp_ring.so):
-python scratch/stamps_ring.py   (copies the diagnostic library over the product one in ITS snapshot only)"""
+"""Phase shares of the 3x3 forward and input-gradient ring kernels (diagnostic build -DCX_RING_STAMPS, scratch/libstamp_ring.so):
+python scratch/stamps_ring.py [library]   (copies the diagnostic library over the product one in ITS snapshot only)
+Per map size: the step loop's phases (clocks per step) and, outside the loop, setup / setup end -> first MFMA / last step -> kernel end
+(clocks per launch, median over workgroups) with the clock they count in (s_memtime ticks per 100 MHz s_memrealtime tick)."""
 import ctypes, os, shutil, sys, numpy as np, torch
 sys.path.insert(0, '.')
 from chexpert_amd import _lib
-shutil.copy("scratch/libstamp_ring.so", _lib.LIB_PATH)
+shutil.copy(sys.argv[1] if len(sys.argv) > 1 else "scratch/libstamp_ring.so", _lib.LIB_PATH)
 from chexpert_amd import ops
 dev = torch.device('cuda:0'); bf = torch.bfloat16; B = 256
 names = ["restart", "wait+stage", "barrier1", "issue", "items:multiply", "items:epilogue", "barrier2"]
-for hw, ctot in ((80, 256), (40, 512), (20, 1024)):
+def outside(fwd):
+    host = (ctypes.c_ulonglong * (1024 * 8))()
+    ctypes.CDLL(_lib.LIB_PATH).dbg_ring_pro_stamps(host, 1024 * 8, fwd)
+    a = np.frombuffer(host, dtype=np.uint64).reshape(1024, 8).astype(np.float64)[:256]
+    a = a[a[:, 4] > 0]
+    m = np.median(a, 0)
+    mhz = np.median(a[:, 3] / a[:, 4]) * 100.0
+    return "   outside the loop, clocks per launch at %.0f MHz: setup %.0f (%.2f us), setup -> first MFMA %.0f (%.2f us), last step -> end %.0f (%.2f us), kernel %.0f (%.2f us)" % (
+        mhz, m[0], m[0] / mhz, m[1], m[1] / mhz, m[2], m[2] / mhz, m[3], m[3] / mhz)
+for hw, ctot in ((80, 256), (40, 512), (20, 1024), (10, 1024)):
     z1 = (torch.randn(B, hw, hw, 128, device=dev) * 0.5).to(bf)
     buf = (torch.randn(B, hw, hw, ctot, device=dev) * 0.5).to(bf)
     gbuf = (torch.randn(B, hw, hw, ctot, device=dev) * 0.5).to(bf)
@@ -36,6 +47,7 @@ for hw, ctot in ((80, 256), (40, 512), (20, 1024)):
     fn = ["between steps", "wait+stage", "barrier1", "issue", "sub-tiles:multiply", "sub-tiles:epilogue", "barrier2"]
     print("%dx%d FORWARD (%s, %.1f us): steps/wg %.0f, core clocks per step %.0f: " % (hw, hw, kname, e0.elapsed_time(e1) * 1e3, np.median(a[:, 7]), med.sum()) +
           ", ".join("%s %.0f" % (nm, v) for nm, v in zip(fn, med)), flush=True)
+    print(outside(1), flush=True)
     for _ in range(3): d()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -49,3 +61,4 @@ for hw, ctot in ((80, 256), (40, 512), (20, 1024)):
     med = np.median(per, 0)
     print("%dx%d (%s, %.1f us): steps/wg %.0f, core clocks per step %.0f: " % (hw, hw, _lib.lib().cx_last_kernel().decode(), e0.elapsed_time(e1) * 1e3, np.median(a[:, 7]), med.sum()) +
           ", ".join("%s %.0f" % (nm, v) for nm, v in zip(names, med)), flush=True)
+    print(outside(0), flush=True)
