@@ -38,6 +38,14 @@
                         (the default) or n_classes positive rates in (0, 1); auto = per class positives / non-ignored labels of the
                         training table, a label >= 0.5 being a positive; --aucm_lr_aux R, the rate of the auxiliary scalars (default:
                         --lr).  Not with --pos_weight, and on one GPU only.  Evaluation keeps reporting cross-entropy element losses
+  --loss {focal,asl}    the focal loss (Lin et al., ICCV 2017) / the asymmetric loss (Ridnik et al., ICCV 2021) instead of the cross-entropy,
+                        inside the fused step (FusedNet.set_loss(kind="focal" | "asl"), cx_asl_fwd_bwd) and, without --fused_optimizer,
+                        through loss.FocalLoss / loss.AsymmetricLoss: --focal_gamma G (default 2), --focal_alpha A (in (0, 1); default
+                        none); --asl_gamma_pos GP (default 0), --asl_gamma_neg GN (default 4), --asl_clip M (in [0, 1); default 0.05).
+                        Both skip an ignored (-1) label and take soft labels, so they combine with --uncertain, --pos_weight (also
+                        auto), --mixup / --cutmix / --erase_prob, --fused_optimizer --graph and more than one rank.  The evaluation
+                        loss in eval_results stays the (masked) cross-entropy, so it can be compared across training losses; the
+                        checkpoint carries the loss's four numbers (`loss_state`), which --restore puts back
   --cam_classes [C ...] with --visualize: class-specific maps (gradcam.class_cam) of the 'vis' subset for these class indices (no value
                         or `all`: every class): vis/class_cam_lowres.npy (N, K, h, w) and one vis/classcam_<ident>_step_<N>.png per image
   --saliency METHOD     with --visualize: full-resolution, class-specific pixel attributions (chexpert_amd/saliency.py) of the 'vis' subset:
@@ -136,7 +144,14 @@ def build_parser():
     p.add_argument("--erase_fill", type=int, default=136, metavar="V", help="grey level 0..255 an erased rectangle gets (default: the dataset mean)")
     p.add_argument("--uncertain", default="ones", choices=list(UNCERTAIN_POLICIES), help="policy for the uncertain (-1) training labels")
     p.add_argument("--pos_weight", nargs="+", default=None, metavar="W", help="`auto` or n_classes floats: positive-term weights of the loss")
-    p.add_argument("--loss", default="bce", choices=["bce", "aucm"], help="training loss: cross-entropy, or the AUC min-max-margin loss")
+    p.add_argument("--loss", default="bce", choices=["bce", "aucm", "focal", "asl"],
+                   help="training loss: cross-entropy, the AUC min-max-margin loss, the focal loss or the asymmetric loss (the evaluation "
+                        "loss written to eval_results stays the cross-entropy, comparable across training losses)")
+    p.add_argument("--focal_gamma", type=float, default=None, metavar="G", help="focusing exponent of --loss focal (>= 0; default 2)")
+    p.add_argument("--focal_alpha", type=float, default=None, metavar="A", help="class balance of --loss focal, in (0, 1) (default: none)")
+    p.add_argument("--asl_gamma_pos", type=float, default=None, metavar="GP", help="positives' exponent of --loss asl (>= 0; default 0)")
+    p.add_argument("--asl_gamma_neg", type=float, default=None, metavar="GN", help="negatives' exponent of --loss asl (>= 0; default 4)")
+    p.add_argument("--asl_clip", type=float, default=None, metavar="M", help="probability shift of the negatives of --loss asl, in [0, 1) (default 0.05)")
     p.add_argument("--aucm_margin", type=float, default=None, metavar="M", help="margin of --loss aucm (> 0; default 1.0)")
     p.add_argument("--aucm_prior", nargs="+", default=None, metavar="P", help="`auto` (default) or n_classes positive rates in (0, 1) for --loss aucm")
     p.add_argument("--aucm_lr_aux", type=float, default=None, metavar="R", help="rate of the auxiliary scalars of --loss aucm (default: --lr)")
@@ -417,6 +432,34 @@ def aucm_options(args, world=1):
     return {"margin": float(margin), "lr_aux": float(lr_aux)}
 
 
+def focus_options(args):
+    """--loss focal|asl and their flags checked before anything runs: None for the other losses, else the keywords of
+    FusedNet.set_loss (kind and the numbers; the weights come from --pos_weight)."""
+    loss = getattr(args, "loss", "bce")
+    fg, fa = getattr(args, "focal_gamma", None), getattr(args, "focal_alpha", None)
+    gp, gn, m = getattr(args, "asl_gamma_pos", None), getattr(args, "asl_gamma_neg", None), getattr(args, "asl_clip", None)
+    if loss != "focal" and (fg is not None or fa is not None):
+        raise ValueError("--focal_gamma / --focal_alpha belong to --loss focal: pass it with them")
+    if loss != "asl" and (gp is not None or gn is not None or m is not None):
+        raise ValueError("--asl_gamma_pos / --asl_gamma_neg / --asl_clip belong to --loss asl: pass it with them")
+    if loss == "focal":
+        fg = 2.0 if fg is None else fg
+        if not (fg >= 0 and np.isfinite(fg)):
+            raise ValueError("--focal_gamma takes a finite exponent >= 0 (got %r)" % fg)
+        if fa is not None and not 0 < fa < 1:
+            raise ValueError("--focal_alpha takes a class balance inside (0, 1) (got %r)" % fa)
+        return {"kind": "focal", "gamma": float(fg), "alpha": None if fa is None else float(fa)}
+    if loss == "asl":
+        gp, gn, m = 0.0 if gp is None else gp, 4.0 if gn is None else gn, 0.05 if m is None else m
+        for name, v in (("--asl_gamma_pos", gp), ("--asl_gamma_neg", gn)):
+            if not (v >= 0 and np.isfinite(v)):
+                raise ValueError("%s takes a finite exponent >= 0 (got %r)" % (name, v))
+        if not 0 <= m < 1:
+            raise ValueError("--asl_clip takes a probability shift in [0, 1) (got %r)" % m)
+        return {"kind": "asl", "gamma_pos": float(gp), "gamma_neg": float(gn), "clip": float(m)}
+    return None
+
+
 def resolve_cam_classes(spec, n_classes):
     """--cam_classes as a list of class indices, or None when the flag is absent.  No value or `all`: every class."""
     if spec is None:
@@ -617,7 +660,7 @@ def save_checkpoint(ckpt, optim_state, sched_state, args, max_records=10):
 
 def restore(args, model, optimizer, scheduler, device):
     """chexpert.py:504-518: model weights + step from the file; when training also `optim_<name>` / `sched_<name>` beside it.
-    Returns the checkpoint's `loss_state` entry (FusedNet.loss_state() of a --loss aucm run), or None."""
+    Returns the checkpoint's `loss_state` entry (FusedNet.loss_state() of a --loss aucm, focal or asl run), or None."""
     ck = torch.load(args.restore, map_location=device)
     model.load_state_dict(model_weights(ck, args, args.restore))
     args.step = ck["global_step"]
@@ -666,6 +709,7 @@ def main(argv=None):
     sal = resolve_saliency(args)
     rank, world, local = P.dist_info()
     aucm = aucm_options(args, world)
+    focus = focus_options(args)
     if world > 1:
         # the process group comes first, before anything touches the GPU; one rank per GPU over RCCL ("nccl"), or ranks sharing
         # a device over gloo when the box has fewer GPUs than ranks (tests)
@@ -729,7 +773,26 @@ def main(argv=None):
         restored_loss = restore(args, model, optimizer, scheduler, device)
     loss_fn = nn.BCEWithLogitsLoss(reduction="none")
     masked_loss = None
-    if args.uncertain == "ignore" or pos_weight is not None:
+    if focus is not None:
+        # the fused step's loss and, by the same kernel, the autograd route's; a restored checkpoint of the same kind brings its four
+        # numbers (loss_focus: a schedule may have moved them), one of another kind is refused
+        from .loss import AsymmetricLoss, FocalLoss
+        model.set_loss(pos_weight=pos_weight, **focus)
+        if restored_loss is not None:
+            if restored_loss.get("kind") != focus["kind"]:
+                if train_loader is not None:
+                    train_loader.close()
+                raise ValueError("--restore: the checkpoint was trained with --loss %s, this run asks for --loss %s"
+                                 % (restored_loss.get("kind"), focus["kind"]))
+            model.load_loss_state(restored_loss)
+        crit = (FocalLoss if focus["kind"] == "focal" else AsymmetricLoss)(pos_weight=model.loss_pos_weight,
+                                                                           **{k: v for k, v in focus.items() if k != "kind"})
+        crit.focus = model.loss_focus                    # one storage: the module reads what the model holds
+        masked_loss = crit
+    elif args.train and restored_loss is not None and restored_loss.get("kind") in ("focal", "asl"):
+        train_loader.close()
+        raise ValueError("--restore: the checkpoint was trained with --loss %s: pass it (and its flags) to go on training" % restored_loss["kind"])
+    elif args.uncertain == "ignore" or pos_weight is not None:
         from .loss import MaskedBCE
         model.set_loss(ignore_negative=args.uncertain == "ignore", pos_weight=pos_weight)      # the fused step's loss
         masked_loss = MaskedBCE(model.loss_pos_weight, ignore_negative=args.uncertain == "ignore")   # the autograd route's
@@ -872,6 +935,8 @@ def main(argv=None):
                             ckpt["ema_state_dict"] = ema_sd
                         if aucm is not None:          # the auxiliary scalars are trained state: restore continues from them
                             sync_loss_aux()
+                            ckpt["loss_state"] = model.loss_state()
+                        elif focus is not None:       # the loss's four numbers: restore checks the kind and puts them back
                             ckpt["loss_state"] = model.loss_state()
                         save_checkpoint(ckpt, optimizer.state_dict(), sched_state, args)
                     model.train()

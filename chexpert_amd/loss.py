@@ -1,8 +1,9 @@
 """The training loss with uncertain-label handling outside the fused step: `loss = MaskedBCE(w)(model(x), t); loss.backward()` and
 the element losses of an evaluation run the arithmetic of `FusedNet.set_loss` (cx_bce_masked_fwd_bwd, csrc/elementwise.hip), so
 the autograd route and the fused step agree bit for bit.  AUCMLoss is the same for `FusedNet.set_loss(kind="aucm")`: the AUC
-min-max-margin loss (cx_aucm_fwd_bwd, csrc/aucm.hip) with its auxiliary scalars as parameters.  Device tensors only: there is no
-CPU path."""
+min-max-margin loss (cx_aucm_fwd_bwd, csrc/aucm.hip) with its auxiliary scalars as parameters.  FocalLoss and AsymmetricLoss are
+the same for `FusedNet.set_loss(kind="focal" | "asl")` (cx_asl_fwd_bwd, csrc/focal.hip).  Device tensors only: there is no CPU
+path."""
 import torch
 import torch.nn as nn
 
@@ -139,3 +140,85 @@ class AUCMLoss(nn.Module):
     def elementwise(self, logits, target):
         raise RuntimeError("AUCMLoss has no element losses: it is a function of each class's whole batch column (its positives "
                            "against its negatives), not a sum over elements -- evaluate with MaskedBCE.elementwise or BCEWithLogitsLoss")
+
+
+class _FocusFn(torch.autograd.Function):
+    """loss and d loss / d logits in one launch (cx_asl_fwd_bwd); backward scales the stored gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, target, pos_weight, focus, who):
+        x, t = _operands(logits, target, who, "cx_asl_fwd_bwd")
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        dl = torch.empty_like(x)
+        ops.asl_fwd_bwd(x, t, pos_weight, focus, loss, None, dl)
+        ctx.save_for_backward(dl)
+        ctx.in_dtype = logits.dtype
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dl, = ctx.saved_tensors
+        return (dl * grad_output).to(ctx.in_dtype), None, None, None, None
+
+
+class _FocusLoss(nn.Module):
+    """What FocalLoss and AsymmetricLoss share: the four numbers [gamma+, gamma-, clip, alpha or -1] the kernel reads from the device
+    (`focus`, a plain attribute like `pos_weight`, moved by hand), the autograd route and the element losses."""
+
+    def __init__(self, focus, pos_weight):
+        super().__init__()
+        gp, gn, m, al = (float(v) for v in focus)
+        who = type(self).__name__
+        if not (0 <= gp < float("inf") and 0 <= gn < float("inf")):
+            raise ValueError("%s takes finite exponents >= 0 (got %r, %r)" % (who, gp, gn))
+        if not 0 <= m < 1:
+            raise ValueError("%s takes a clip in [0, 1) (got %r)" % (who, m))
+        self.focus = torch.tensor([gp, gn, m, al], dtype=torch.float32)
+        self.pos_weight = None if pos_weight is None else torch.as_tensor(pos_weight, dtype=torch.float32).detach().reshape(-1)
+        if self.pos_weight is not None and not bool(((self.pos_weight > 0) & torch.isfinite(self.pos_weight)).all()):
+            raise ValueError("%s takes finite pos_weight > 0 (got %s)" % (who, self.pos_weight.tolist()))
+
+    def _held(self, device):
+        if self.focus.device != device:
+            self.focus = self.focus.to(device)
+        if self.pos_weight is not None and self.pos_weight.device != device:
+            self.pos_weight = self.pos_weight.to(device)
+        return self.pos_weight, self.focus
+
+    def forward(self, logits, target):
+        _operands(logits, target, type(self).__name__, "cx_asl_fwd_bwd")      # (refuses a CPU tensor before anything is moved)
+        w, focus = self._held(logits.device)
+        return _FocusFn.apply(logits, target, w, focus, type(self).__name__)
+
+    @torch.no_grad()
+    def elementwise(self, logits, target):
+        """The (B, n) element losses (0 where ignored, and for a hard negative at or below the clip), outside autograd."""
+        x, t = _operands(logits, target, type(self).__name__, "cx_asl_fwd_bwd")
+        w, focus = self._held(x.device)
+        out = torch.empty_like(x)
+        ops.asl_fwd_bwd(x, t, w, focus, None, out, None)
+        return out
+
+
+class FocalLoss(_FocusLoss):
+    """The focal loss (Lin et al., "Focal Loss for Dense Object Detection", ICCV 2017) of (B, n) logits: torchvision's
+    sigmoid_focal_loss(alpha, gamma) summed over the classes and averaged over the batch, a target < 0 ignored (the divisor stays the
+    batch size), soft targets valid, pos_weight on the positive term -- the loss of FusedNet.set_loss(kind="focal") for the autograd
+    route, by the same kernel, so `loss.backward()` leaves the fused step's d loss / d logits bit for bit.  gamma >= 0; alpha None
+    (no class balance) or in (0, 1).  The focusing weight is differentiated, not detached."""
+
+    def __init__(self, gamma=2.0, alpha=None, pos_weight=None):
+        if alpha is not None and not 0 < float(alpha) < 1:
+            raise ValueError("FocalLoss takes alpha None or in (0, 1) (got %r)" % (alpha,))
+        super().__init__([gamma, gamma, 0.0, -1.0 if alpha is None else alpha], pos_weight)
+
+
+class AsymmetricLoss(_FocusLoss):
+    """The asymmetric loss (Ridnik et al., "Asymmetric Loss for Multi-Label Classification", ICCV 2021) of (B, n) logits, timm's
+    AsymmetricLossMultiLabel (its blended form for soft targets) summed over the classes and averaged over the batch: positives
+    -(1 - p)^gamma_pos log p, negatives -p_m^gamma_neg log(1 - p_m) with p_m = max(p - clip, 0), so a hard negative with p <= clip
+    adds no loss and no gradient.  A target < 0 is ignored; pos_weight weights the positive term.  The loss of
+    FusedNet.set_loss(kind="asl") for the autograd route, by the same kernel, bit for bit."""
+
+    def __init__(self, gamma_pos=0.0, gamma_neg=4.0, clip=0.05, pos_weight=None):
+        super().__init__([gamma_pos, gamma_neg, clip, -1.0], pos_weight)

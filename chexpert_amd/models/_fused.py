@@ -122,8 +122,11 @@ class FusedNet(nn.Module):
         self.loss_kind, self.loss_margin = "bce", 1.0
         self.loss_aux = self.loss_prior = self.loss_lr_aux = self._loss_daux = None
         self._aucm_store = None
+        # set_loss(kind="focal" | "asl"): [gamma+, gamma-, clip, alpha or -1], one fp32 device tensor the kernel reads
+        self.loss_focus = self._focus_store = None
 
-    def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None):
+    def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
+                 alpha=None, gamma_pos=None, gamma_neg=None, clip=None):
         """The loss of forward_backward.  ignore_negative: a target < 0 (an uncertain label kept as -1, the U-Ignore policy) adds no
         loss and no gradient; the divisor stays the batch size.  pos_weight: None, or n_classes positive-term weights as in torch's
         BCEWithLogitsLoss(pos_weight).  Either option routes the step through cx_bce_masked_fwd_bwd, which skips every target < 0:
@@ -150,30 +153,95 @@ class FusedNet(nn.Module):
         `model.loss_lr_aux.fill_(r)`); coming from another kind, or with another number of classes, `loss_aux` starts at zero.  A
         change of kind or of the margin (passed by value) needs a new capture.  The data-parallel step is not supported: the
         auxiliary gradients would need a collective of their own (forward_backward raises when the engine averages gradients over
-        more than one rank)."""
-        if kind not in ("bce", "aucm"):
-            raise ValueError("set_loss(kind=...) takes 'bce' or 'aucm' (got %r)" % (kind,))
-        if kind == "bce" and (prior is not None or lr_aux is not None or margin != 1.0):
+        more than one rank).
+
+        kind="focal" (gamma=2.0, alpha=None) and kind="asl" (gamma_pos=0.0, gamma_neg=4.0, clip=0.05) replace the cross-entropy by
+        the focal loss (Lin et al., ICCV 2017) and the asymmetric loss (Ridnik et al., ICCV 2021), one kernel for both
+        (cx_asl_fwd_bwd; the definition stands in include/chexpert_hip.h): the cross-entropy term of every element is multiplied by
+        (1 - p_t)^gamma, with its own exponent for positives and negatives and the negatives' probability shifted down by clip, below
+        which a hard negative adds nothing at all.  The focusing weight is part of the derivative (it is not detached).  gamma,
+        gamma_pos, gamma_neg >= 0; clip in [0, 1); alpha None or in (0, 1), the positives' share of the class balance a = alpha t +
+        (1 - alpha)(1 - t).  Both kinds skip every target < 0, take soft targets, and accept pos_weight (the held storage above).
+        The four numbers live in one fp32 device tensor, `loss_focus` = [gamma+, gamma-, clip, alpha or -1], neither buffer nor
+        parameter; a repeated call copies into the held storage.  For a captured step the rule of the weights holds: a change of
+        kind, or from no pos_weight to weights or back, needs a new capture; a change of VALUES -- `model.loss_focus[1] = 2`, or
+        set_loss with the same kind and new numbers -- is seen by the next replay, so a gamma schedule needs none.  The
+        data-parallel step needs nothing new (the sum over elements is averaged over the ranks like the cross-entropy's).  An
+        operand out of range, or a keyword of another kind, is a ValueError that changes nothing."""
+        if kind not in ("bce", "aucm", "focal", "asl"):
+            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal' or 'asl' (got %r)" % (kind,))
+        if kind != "aucm" and (prior is not None or lr_aux is not None or margin != 1.0):
             raise ValueError("set_loss: prior, margin and lr_aux belong to kind='aucm'")
+        if kind != "focal" and (gamma is not None or alpha is not None):
+            raise ValueError("set_loss: gamma and alpha belong to kind='focal'")
+        if kind != "asl" and (gamma_pos is not None or gamma_neg is not None or clip is not None):
+            raise ValueError("set_loss: gamma_pos, gamma_neg and clip belong to kind='asl'")
         if kind == "aucm":
             if pos_weight is not None:
                 raise ValueError("set_loss(kind='aucm') cannot be combined with pos_weight: the class prior is this loss's weighting")
             self._set_aucm(prior, margin, lr_aux)
-            self.loss_pos_weight, self.loss_ignore_negative, self.loss_kind = None, True, "aucm"
+            self.loss_pos_weight, self.loss_ignore_negative, self.loss_kind, self.loss_focus = None, True, "aucm", None
             return self
+        if kind == "focal":
+            g = 2.0 if gamma is None else gamma
+            if alpha is not None and not 0 < float(alpha) < 1:
+                raise ValueError("set_loss(kind='focal') takes alpha None or in (0, 1) (got %r)" % (alpha,))
+            return self._set_focus("focal", [g, g, 0.0, -1.0 if alpha is None else alpha], pos_weight)
+        if kind == "asl":
+            return self._set_focus("asl", [0.0 if gamma_pos is None else gamma_pos, 4.0 if gamma_neg is None else gamma_neg,
+                                           0.05 if clip is None else clip, -1.0], pos_weight)
         self.loss_kind = "bce"
-        self.loss_aux = self.loss_prior = self.loss_lr_aux = self._loss_daux = None      # (the storage itself is kept)
-        if pos_weight is not None:
-            dev = next(self.parameters()).device
-            if dev.type != "cuda":
-                raise RuntimeError("set_loss(pos_weight=...) holds the weights on the parameters' device: call model.to(device) first")
-            w = torch.as_tensor(pos_weight, dtype=torch.float32).reshape(-1)
-            held = self._pos_weight_store
-            if held is None or held.numel() != w.numel() or held.device != dev:
-                held = self._pos_weight_store = torch.empty(w.numel(), dtype=torch.float32, device=dev)
-            held.copy_(w)
-        self.loss_pos_weight = self._pos_weight_store if pos_weight is not None else None
+        self.loss_aux = self.loss_prior = self.loss_lr_aux = self._loss_daux = self.loss_focus = None      # (the storage itself is kept)
+        self.loss_pos_weight = self._hold_pos_weight(pos_weight)
         self.loss_ignore_negative = bool(ignore_negative)
+        return self
+
+    def _hold_pos_weight(self, pos_weight):
+        """pos_weight copied into the held device storage (made anew for another number of weights or another device); None: None."""
+        if pos_weight is None:
+            return None
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("set_loss(pos_weight=...) holds the weights on the parameters' device: call model.to(device) first")
+        w = torch.as_tensor(pos_weight, dtype=torch.float32).reshape(-1)
+        held = self._pos_weight_store
+        if held is None or held.numel() != w.numel() or held.device != dev:
+            held = self._pos_weight_store = torch.empty(w.numel(), dtype=torch.float32, device=dev)
+        held.copy_(w)
+        return held
+
+    def _set_focus(self, kind, focus, pos_weight):
+        """Checks the four numbers [gamma+, gamma-, clip, alpha or a negative number for none] and the weights of
+        set_loss(kind="focal" | "asl") (ValueError; nothing is changed when one is refused) and copies them into the held device
+        storage.  Returns self."""
+        try:
+            gp, gn, m, al = (float(v) for v in focus)
+        except (TypeError, ValueError):
+            raise ValueError("set_loss(kind=%r) takes numbers (got %r)" % (kind, focus))
+        names = ("gamma", "gamma") if kind == "focal" else ("gamma_pos", "gamma_neg")
+        for name, v in zip(names, (gp, gn)):
+            if not (v >= 0 and v < float("inf")):
+                raise ValueError("set_loss(kind=%r) takes a finite %s >= 0 (got %r)" % (kind, name, v))
+        if not 0 <= m < 1:
+            raise ValueError("set_loss(kind=%r) takes a clip in [0, 1) (got %r)" % (kind, m))
+        if not (al < 0 or 0 < al < 1):            # (NaN fails both)
+            raise ValueError("set_loss(kind=%r) takes alpha None or in (0, 1) (got %r)" % (kind, al))
+        al = -1.0 if al < 0 else al
+        if pos_weight is not None:
+            w = torch.as_tensor(pos_weight, dtype=torch.float32).detach().reshape(-1).cpu()
+            n = self._n_classes()
+            if w.numel() != n or not bool(((w > 0) & torch.isfinite(w)).all()):
+                raise ValueError("set_loss(kind=%r) takes %d finite pos_weight > 0 (got %s)" % (kind, n, w.tolist()))
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("set_loss(kind=%r) holds its state on the parameters' device: call model.to(device) first" % kind)
+        held = self._focus_store
+        if held is None or held.device != dev:
+            held = self._focus_store = torch.empty(4, dtype=torch.float32, device=dev)
+        held.copy_(torch.tensor([gp, gn, m, al], dtype=torch.float32))
+        self.loss_pos_weight = self._hold_pos_weight(pos_weight)
+        self.loss_aux = self.loss_prior = self.loss_lr_aux = self._loss_daux = None
+        self.loss_kind, self.loss_ignore_negative, self.loss_focus = kind, True, held
         return self
 
     def _n_classes(self):
@@ -214,7 +282,11 @@ class FusedNet(nn.Module):
 
     def loss_state(self):
         """What set_loss(kind=...) holds beyond the model's state_dict, as CPU tensors and floats: {kind, aux, prior, margin, lr_aux}
-        (aux, prior and lr_aux are None for kind 'bce').  A checkpoint keeps it beside the weights."""
+        (aux, prior and lr_aux are None for kind 'bce').  Kinds 'focal' and 'asl' add `focus`, the four numbers of `loss_focus`.  A
+        checkpoint keeps it beside the weights."""
+        if self.loss_kind in ("focal", "asl"):
+            return {"kind": self.loss_kind, "focus": self.loss_focus.detach().cpu().clone(), "aux": None, "prior": None,
+                    "margin": float(self.loss_margin), "lr_aux": None}
         if self.loss_kind != "aucm":
             return {"kind": self.loss_kind, "aux": None, "prior": None, "margin": float(self.loss_margin), "lr_aux": None}
         return {"kind": "aucm", "aux": self.loss_aux.detach().cpu().clone(), "prior": self.loss_prior.detach().cpu().clone(),
@@ -223,7 +295,14 @@ class FusedNet(nn.Module):
     def load_loss_state(self, d):
         """Restores loss_state(): for kind 'aucm' the loss is set with the stored prior, margin and rate, and the auxiliary scalars
         are copied in (into the held storage when there is one for this number of classes).  Kind 'bce' leaves the options of
-        the cross-entropy (ignore_negative, pos_weight) as they are.  Returns self."""
+        the cross-entropy (ignore_negative, pos_weight) as they are.  Kinds 'focal' and 'asl' set the loss with the stored `focus`
+        (checked like set_loss's operands) and keep the pos_weight the model holds.  Returns self."""
+        if d["kind"] in ("focal", "asl"):
+            focus = d.get("focus")
+            if focus is None or torch.as_tensor(focus).numel() != 4:
+                raise ValueError("load_loss_state: kind %r needs focus, four numbers (got %r)" % (d["kind"], focus))
+            w = self.loss_pos_weight.clone() if self.loss_pos_weight is not None else None
+            return self._set_focus(d["kind"], torch.as_tensor(focus, dtype=torch.float32).reshape(-1).tolist(), w)
         if d["kind"] != "aucm":
             if d["kind"] != "bce":
                 raise ValueError("load_loss_state: unknown loss kind %r" % (d["kind"],))
@@ -239,7 +318,7 @@ class FusedNet(nn.Module):
 
     def loss_step_state(self):
         """The tensors beyond parameters and buffers that a train-mode forward_backward changes (a graph capture's warm-up steps
-        really run: it puts them back)."""
+        really run: it puts them back).  The focal and asymmetric losses change nothing per step."""
         return [self.loss_aux] if self.loss_kind == "aucm" else []
 
     def storage_dtype(self, dtype):
@@ -286,7 +365,8 @@ class FusedNet(nn.Module):
         step (running statistics, which stay as they are).  After set_loss(...) the loss ignores targets < 0 and / or weights the
         positive term per class (same reduction, same divisor).  After set_loss(kind="aucm", ...) the loss is the AUC-margin loss,
         and a train-mode step ends with the update of its auxiliary scalars (`loss_aux`), from the gradients of this step; the
-        eval-mode step computes the gradients and leaves `loss_aux` alone."""
+        eval-mode step computes the gradients and leaves `loss_aux` alone.  After set_loss(kind="focal" | "asl") the loss is the
+        focal / asymmetric loss (ops.asl_fwd_bwd), in either mode."""
         eng = self._eng()
         if input_grad is not None:
             check_input_grad(input_grad, x)
@@ -298,6 +378,8 @@ class FusedNet(nn.Module):
         dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
         if self.loss_kind == "aucm":                                           # set_loss(kind="aucm"): one launch, as the others
             ops.aucm_fwd_bwd(ws.logits, target, self.loss_prior, self.loss_aux, self.loss_margin, loss, None, dl, self._loss_daux)
+        elif self.loss_kind in ("focal", "asl"):                               # set_loss(kind="focal" | "asl"): one launch again
+            ops.asl_fwd_bwd(ws.logits, target, self.loss_pos_weight, self.loss_focus, loss, None, dl)
         elif self.loss_ignore_negative or self.loss_pos_weight is not None:    # set_loss(): ignored labels / class weights
             ops.bce_masked_fwd_bwd(ws.logits, target, self.loss_pos_weight, loss, None, dl)
         else:

@@ -681,6 +681,27 @@ def aucm_aux_step(aux, daux, lr_aux):
     check(lib().cx_aucm_aux_step(ptr(aux), ptr(daux), ptr(lr_aux), aux.shape[1], stream_ptr()), "cx_aucm_aux_step")
 
 
+def asl_fwd_bwd(logits, target, pos_weight, focus, loss, loss_elem, dlogits, grad_scale=1.0):
+    """The focal / asymmetric loss of the (B, n) logits with d loss / d logits in one launch (cx_asl_fwd_bwd): focus is a four-float
+    DEVICE tensor [gamma+, gamma-, clip, alpha or -1], read by the kernel (a captured step sees a changed value); a target < 0 is
+    ignored, pos_weight (fp32 (n,), or None) weights the positive term.  loss (1,), loss_elem and dlogits (B, n) are optional;
+    grad_scale multiplies dlogits alone."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    B, n = logits.shape
+    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (B, n) and target.device == logits.device
+    assert pos_weight is None or tuple(pos_weight.shape) == (n,)
+    assert focus is not None and tuple(focus.shape) == (4,)
+    assert all(t is None or t.device == logits.device for t in (pos_weight, focus, loss, loss_elem, dlogits))
+    assert all(t is None or tuple(t.shape) == (B, n) for t in (loss_elem, dlogits))
+    _f32(pos_weight, n=n)
+    _f32(focus, n=4)
+    _f32(loss, n=1)
+    _f32(loss_elem, dlogits, n=B * n)
+    require_cuda(logits, target, pos_weight, focus, loss, loss_elem, dlogits)
+    check(lib().cx_asl_fwd_bwd(ptr(logits), ptr(target), ptr(pos_weight), ptr(focus), ptr(loss), ptr(loss_elem), ptr(dlogits), grad_scale,
+                               B, n, stream_ptr()), "cx_asl_fwd_bwd")
+
+
 def softmax_ce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):
     """CrossEntropyLoss forward + gradient in one launch (fp32 logits [B, n], int64 class indices [B])."""
     B, n = logits.shape

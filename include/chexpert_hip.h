@@ -377,6 +377,23 @@ int cx_aucm_fwd_bwd(const float* logits, const float* target, const float* prior
 /* primal descent on a and b, dual ascent on alpha, from the gradients of the same step: a -= lr da, b -= lr db,
  * alpha = max(0, alpha + lr dalpha), lr = *lr_aux_dev (a device float: a captured step sees a changed rate).                      */
 int cx_aucm_aux_step(float* aux, const float* daux, const float* lr_aux_dev, int n_classes, void* stream);
+/* Focal loss (Lin et al., ICCV 2017) and asymmetric loss (Ridnik et al., ICCV 2021) with d loss / d logits, one launch (focal.hip).
+ * focus: FOUR floats ON THE DEVICE, [gamma+ >= 0, gamma- >= 0, clip m in [0, 1), alpha in (0, 1) or a negative number for "none"];
+ * the kernel reads them from memory, so a captured step sees a change made in place.  Per element, x = logits[b][c],
+ * t = target[b][c], w = pos_weight ? pos_weight[c] : 1, p = sigmoid(x), q = sigmoid(-x), p_m = max(p - m, 0), p_n = min(q + m, 1):
+ *   t < 0   ignored: loss_elem = 0, dlogits = 0, nothing added to loss (as in cx_bce_masked_fwd_bwd)
+ *   else    C = -(w t log p + (1-t) log p_n);  u = t q + (1-t) p_m;  g = gamma+ t + gamma- (1-t);  f = g == 0 ? 1 : u^g;
+ *           a = alpha < 0 ? 1 : alpha t + (1-alpha)(1-t);  l = a f C
+ * loss = sum l / B (the divisor stays the batch size), dlogits = dl/dx / B * grad_scale with the exact derivative (f is not
+ * detached; d p_m / dx = p q where p > m, 0 elsewhere).  A hard negative at or below the clip (t == 0, p <= m) gives l = 0 and
+ * dl/dx = 0 exactly, whatever gamma- is (u = 0: the derivative of 0^g is taken as 0).  Soft targets in [0, 1] are valid.  gamma+ =
+ * gamma- and m = 0 is the focal loss (torchvision's sigmoid_focal_loss summed over the classes and averaged over the batch), all
+ * zero and no alpha the (weighted, masked) cross-entropy.  pos_weight: fp32 [n_classes] on the device, or NULL.  loss (one float),
+ * loss_elem and dlogits (B, n_classes) may each be NULL.  One workgroup, the sum in double over a fixed tree, no atomics:
+ * bit-reproducible.  CX_EINVAL before anything is launched: NULL logits / target / focus, B < 1, n_classes < 1.  The values of
+ * focus are the caller's to keep in range.  Additive entry point of ABI 10 (no struct changed).                                  */
+int cx_asl_fwd_bwd(const float* logits, const float* target, const float* pos_weight, const float* focus, float* loss,
+                   float* loss_elem, float* dlogits, float grad_scale, int B, int n_classes, void* stream);
 /* loss = CrossEntropyLoss(logits, target) (mean over the batch of logsumexp - logit[target]);
  * dlogits = (softmax - onehot)/B * grad_scale; loss_elem (optional) = the per-sample terms
  * (models/test_model.py:118, :143, :331: the CIFAR harness criterion)                              */
