@@ -149,6 +149,11 @@ SIGNATURES = {
     "cx_adam_step_dev_ex": [_vp, _vp, _vp, _vp, _sz, _vp, _f, _f, _f, _f, _f, _vp, _vp, _f, _i, _i, _vp],
     "cx_sgd_nesterov_step_dev_ex": [_vp, _vp, _vp, _sz, _vp, _f, _f, _f, _vp, _vp, _f, _i, _i, _vp],
     "cx_rmsprop_step_dev_ex": [_vp, _vp, _vp, _vp, _sz, _vp, _f, _f, _f, _f, _f, _vp, _vp, _f, _i, _i, _vp],
+    "cx_optim_item_vec4": [],
+    "cx_grad_norm_items": [_vp, _sz, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp],
+    "cx_adam_step_items": [_vp, _vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _f, _i, _f, _f, _f, _f, _vp, _vp, _f, _i, _i, _vp],
+    "cx_sgd_nesterov_step_items": [_vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _f, _i, _f, _f, _vp, _vp, _f, _i, _i, _vp],
+    "cx_rmsprop_step_items": [_vp, _vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _f, _i, _f, _f, _f, _f, _vp, _vp, _f, _i, _i, _vp],
     "cx_aa_attention_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "cx_aa_attention_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "cx_aa_attention_weights": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],

@@ -61,6 +61,13 @@
   --ema_decay D         exponential moving average of the weights, written by the optimiser kernel; evaluation and the checkpoint's
                         `ema_state_dict` use it.  --no_ema_warmup: constant decay instead of min(D, (1 + step) / (10 + step))
   --use_ema             --evaluate_single_model / --evaluate_ensemble / --visualize load `ema_state_dict` from the checkpoint
+  --weight_decay W      weight decay of the fused optimiser (needs --fused_optimizer, as the next five); L2 (g += W p) unless
+                        --decoupled_decay: p <- p (1 - lr W) ahead of the update (AdamW's rule, for all three optimisers)
+  --no_decay_norm_bias  no weight decay on 1-D parameters (BatchNorm weights and biases, every bias)
+  --head_lr_mult M / --backbone_lr_mult M   learning-rate multiplier of the classifier (the last nn.Linear) / of everything else
+  --freeze_backbone_steps N   the classifier trains alone for the first N minibatches, then the backbone is thawed (-1: for the whole
+                        run, a linear probe).  The backward pass still fills every gradient and BatchNorm running statistics keep
+                        moving; the optimiser kernels skip the frozen tensors.  Works with --graph (the group table lives on the device)
   --bootstrap B         B > 0: every eval_results_<tag>.json gets an auc_ci_<tag>.json beside it (rank 0): AUROC per class and for the mean
                         with its (1 - A) percentile bootstrap interval over B replicates, computed on the GPU (metrics.bootstrap_auc);
                         --bootstrap_seed S (default: --seed), --bootstrap_unit image|study|patient (what is resampled; study and
@@ -169,6 +176,13 @@ def build_parser():
     p.add_argument("--ema_decay", type=float, default=None, metavar="D", help="exponential moving average of the weights, decay D in (0, 1)")
     p.add_argument("--no_ema_warmup", action="store_true", help="constant EMA decay (default: min(D, (1 + step) / (10 + step)))")
     p.add_argument("--use_ema", action="store_true", help="evaluate / visualise with the checkpoint's ema_state_dict")
+    p.add_argument("--weight_decay", type=float, default=None, metavar="W", help="weight decay of the fused optimiser (>= 0)")
+    p.add_argument("--decoupled_decay", action="store_true", help="decay the weights directly (AdamW's rule) instead of through the gradient")
+    p.add_argument("--no_decay_norm_bias", action="store_true", help="no weight decay on 1-D parameters (BatchNorm, biases)")
+    p.add_argument("--head_lr_mult", type=float, default=None, metavar="M", help="learning-rate multiplier of the classifier (the last nn.Linear)")
+    p.add_argument("--backbone_lr_mult", type=float, default=None, metavar="M", help="learning-rate multiplier of everything but the classifier")
+    p.add_argument("--freeze_backbone_steps", type=int, default=0, metavar="N",
+                   help="train the classifier alone for the first N minibatches (-1: the whole run)")
     p.add_argument("--bootstrap", type=int, default=0, metavar="B", help="bootstrap replicates of the AUROC intervals written beside every eval_results file (0: none)")
     p.add_argument("--bootstrap_seed", type=int, default=None, metavar="S", help="seed of the bootstrap draws (default: --seed)")
     p.add_argument("--bootstrap_unit", default="image", choices=list(BOOTSTRAP_UNITS), help="what the bootstrap resamples")
@@ -545,6 +559,59 @@ def optimizer_options(args):
     return {"max_grad_norm": clip, "skip_nonfinite": bool(skip), "ema_decay": ema, "ema_warmup": not no_warm}
 
 
+def group_options(args):
+    """--weight_decay / --decoupled_decay / --no_decay_norm_bias / --head_lr_mult / --backbone_lr_mult / --freeze_backbone_steps,
+    validated: ({} when all are off, else the keyword arguments of optim.finetune_groups under "finetune" (None: no groups
+    needed) plus "weight_decay" and "decoupled" for the optimiser's constructor and "freeze_steps")."""
+    import math
+    wd, dec = getattr(args, "weight_decay", None), getattr(args, "decoupled_decay", False)
+    nd = getattr(args, "no_decay_norm_bias", False)
+    hm, bm = getattr(args, "head_lr_mult", None), getattr(args, "backbone_lr_mult", None)
+    fz = getattr(args, "freeze_backbone_steps", 0)
+    for flag, on in (("--weight_decay", wd is not None), ("--decoupled_decay", dec), ("--no_decay_norm_bias", nd),
+                     ("--head_lr_mult", hm is not None), ("--backbone_lr_mult", bm is not None), ("--freeze_backbone_steps", fz != 0)):
+        if on and not args.fused_optimizer:
+            raise ValueError("%s works inside the fused optimiser step: pass --fused_optimizer with it" % flag)
+    if wd is not None and not (math.isfinite(wd) and wd >= 0):
+        raise ValueError("--weight_decay takes a finite decay >= 0 (got %r)" % wd)
+    for flag, v in (("--head_lr_mult", hm), ("--backbone_lr_mult", bm)):
+        if v is not None and not (math.isfinite(v) and v >= 0):
+            raise ValueError("%s takes a finite multiplier >= 0 (got %r)" % (flag, v))
+    if fz < -1:
+        raise ValueError("--freeze_backbone_steps takes a number of minibatches >= 0, or -1 for the whole run (got %r)" % fz)
+    if (dec or nd) and not wd:
+        raise ValueError("%s changes how --weight_decay is applied: pass --weight_decay W > 0 with it"
+                         % ("--decoupled_decay" if dec else "--no_decay_norm_bias"))
+    if wd is None and not dec and not nd and hm is None and bm is None and fz == 0:
+        return {}
+    finetune = None
+    if nd or hm is not None or bm is not None or fz != 0:
+        finetune = {"weight_decay": wd or 0.0, "no_decay_norm_bias": bool(nd), "head_lr_mult": 1.0 if hm is None else hm,
+                    "backbone_lr_mult": 1.0 if bm is None else bm, "freeze_backbone": fz != 0}
+    return {"weight_decay": wd or 0.0, "decoupled": bool(dec), "finetune": finetune, "freeze_steps": fz}
+
+
+def fused_optimizer_kwargs(args, model):
+    """Keyword arguments of the fused optimiser's constructor for the clip / skip / EMA and the parameter-group flags."""
+    from . import optim as O
+    kw = dict(optimizer_options(args))
+    go = group_options(args)
+    if go:
+        kw["weight_decay"] = go["weight_decay"]
+        if go["decoupled"]:
+            kw["decoupled"] = True
+        if go["finetune"] is not None:
+            kw["groups"] = O.finetune_groups(model, **go["finetune"])
+    return kw
+
+
+def thaw_backbone(optimizer):
+    """--freeze_backbone_steps N, after minibatch N: the backbone's rows of the group table are rewritten on the device."""
+    for i, name in enumerate(optimizer.group_names):
+        if name.startswith("backbone"):
+            optimizer.set_group(i, frozen=False)
+
+
 def model_weights(ck, args, path=""):
     """The state dict a checkpoint is read for: the live weights, or with --use_ema (outside training) their average."""
     if getattr(args, "use_ema", False) and not args.train:
@@ -560,14 +627,18 @@ def make_model(args, device):
     from .models import densenet121
     name = args.model
     fused = args.fused_optimizer
-    ex = optimizer_options(args)
+    optimizer_options(args)                                  # validated before a model is built
+    group_options(args)
     sched = None
+
+    def ex():                                                # the constructor's keyword arguments, once `model` exists
+        return fused_optimizer_kwargs(args, model)
     if name == "densenet121":
         model = densenet121(pretrained=args.pretrained)
         model.classifier = nn.Linear(model.classifier.in_features, args.n_classes)
         nn.init.constant_(model.classifier.bias, 0)
         model = model.storage_dtype(args.dtype).to(device)
-        opt = O.FusedAdam(model, lr=args.lr, **ex) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)
+        opt = O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)
         return model, opt, None
     if name in ("aadensenet121", "densenet121_attn_aug"):      # chexpert.py:474-480 (README row name accepted too)
         from .models import DenseNet
@@ -576,7 +647,7 @@ def make_model(args, device):
                          attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
         model = model.storage_dtype(args.dtype).to(device)
         if fused:
-            return model, O.FusedSGDNesterov(model, lr=args.lr, **ex), "fused"
+            return model, O.FusedSGDNesterov(model, lr=args.lr, **ex()), "fused"
         opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, nesterov=True)
         return model, opt, torch.optim.lr_scheduler.MultiStepLR(opt, [40000, 60000])
     if name == "resnet152":                                   # chexpert.py:481-486
@@ -584,12 +655,12 @@ def make_model(args, device):
         model = resnet152(pretrained=args.pretrained)
         model.fc = nn.Linear(model.fc.in_features, args.n_classes)
         model = model.storage_dtype(args.dtype).to(device)
-        return model, (O.FusedAdam(model, lr=args.lr, **ex) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
+        return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
     if "efficientnet" in name:                                # chexpert.py:496-500
         from .models import construct_model
         model = construct_model(name, n_classes=args.n_classes).storage_dtype(args.dtype).to(device)
         if fused:
-            return model, O.FusedRMSprop(model, lr=args.lr, decay=args.lr_decay_factor, **ex), "fused"
+            return model, O.FusedRMSprop(model, lr=args.lr, decay=args.lr_decay_factor, **ex()), "fused"
         opt = torch.optim.RMSprop(model.parameters(), lr=args.lr, momentum=0.9, eps=0.001)
         return model, opt, torch.optim.lr_scheduler.ExponentialLR(opt, args.lr_decay_factor)
     if name == "aaresnet152":                                 # chexpert.py:486-494
@@ -598,7 +669,7 @@ def make_model(args, device):
         model = ResNet(Bottleneck, [3, 8, 36, 3], num_classes=args.n_classes,
                        attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
         model = model.storage_dtype(args.dtype).to(device)
-        return model, (O.FusedAdam(model, lr=args.lr, **ex) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
+        return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
     raise RuntimeError("Model architecture not supported.")
 
 
@@ -703,6 +774,7 @@ def main(argv=None):
     if args.synthetic_uncertain > 0 and not args.synthetic:
         raise ValueError("--synthetic_uncertain marks labels of the synthetic set: pass --synthetic N with it")
     ex = optimizer_options(args)
+    groups_on = group_options(args)
     cam_classes = resolve_cam_classes(getattr(args, "cam_classes", None), args.n_classes)
     if cam_classes is not None and not args.visualize:
         raise ValueError("--cam_classes draws class maps over the 'vis' subset: pass --visualize with it")
@@ -912,6 +984,8 @@ def main(argv=None):
                         aucm_loss.clamp_()
                     if scheduler and args.step >= args.lr_warmup_steps:
                         scheduler.step()
+                if groups_on.get("freeze_steps", 0) > 0 and args.step == groups_on["freeze_steps"]:
+                    thaw_backbone(optimizer)                # every rank alike: the table is the same on all of them, no collective
                 if args.step % args.log_interval == 0 and rank == 0:
                     line = {"step": args.step, "train_loss": round(loss.item(), 5)}
                     if ex.get("max_grad_norm") is not None or ex.get("skip_nonfinite"):      # (loss.item() has synchronised already)

@@ -868,6 +868,69 @@ def rmsprop_step_dev_ex(p, g, sq, buf, hyper, alpha, eps, momentum, weight_decay
                                        grad_scale, *tail), "cx_rmsprop_step_dev_ex")
 
 
+# ---- parameter groups: per-tensor item table and per-group rows walked by the optimiser kernels (csrc/optim_groups.hip)
+def optim_item_vec4():
+    """Longest work item of the grouped optimiser kernels, in 16-byte units (a constant of the library)."""
+    return lib().cx_optim_item_vec4()
+
+
+def _group_tables(p, items, groups, *bufs):
+    """Checks of one grouped launch; returns (n, items pointer, item count, groups pointer, group count)."""
+    n = p.numel()
+    require_cuda(p, items, groups, *bufs)
+    _f32(p, *bufs, n=n)
+    _f32(groups)
+    assert items.dtype == torch.int32 and items.is_contiguous() and items.dim() == 2 and items.shape[1] == 4, \
+        "items: an int32 tensor (n_items, 4) {start4, len4, group, tensor}"
+    assert groups.dim() == 2 and groups.shape[1] == 4, "groups: a float tensor (G, 4) {lr_mult, weight_decay, frozen, t0}"
+    return n, ptr(items), items.shape[0], ptr(groups), groups.shape[0]
+
+
+def grad_norm_items(g, items, groups, partials, group_sq, group_norm, clip, grad_scale=1.0, max_norm=0.0, skip_nonfinite=False):
+    """The segmented `grad_norm`: clip = {norm over the groups with frozen == 0, coefficient, nonfinite, skipped}, group_norm[k] the
+    norm of every group (frozen ones too).  Two launches, no atomics, the same bits on every call.  partials: n_items floats."""
+    n, pi, ni, pg, ng = _group_tables(g, items, groups)
+    require_cuda(partials, group_sq, group_norm, clip)
+    _f32(partials, n=ni)
+    _f32(group_sq, group_norm, n=ng)
+    _f32(clip, n=4)
+    check(lib().cx_grad_norm_items(ptr(g), n, pi, ni, pg, ng, grad_scale, max_norm, int(bool(skip_nonfinite)), ptr(partials),
+                                   ptr(group_sq), ptr(group_norm), ptr(clip), stream_ptr()), "cx_grad_norm_items")
+
+
+def _items_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite):
+    require_cuda(clip)
+    _f32(clip, n=4)
+    return ptr(clip), ptr(ema), (0.0 if ema is None else float(ema_decay)), int(bool(ema_warmup)), int(bool(skip_nonfinite)), stream_ptr()
+
+
+def adam_step_items(p, g, m, v, items, groups, decoupled, beta1, beta2, eps, hyper=None, lr=0.0, step=0, grad_scale=1.0, clip=None,
+                    ema=None, ema_decay=0.0, ema_warmup=True, skip_nonfinite=False):
+    """Adam over the item table.  hyper (device float[8]) given: lr and the step come from it; else `lr` and the 1-based `step`."""
+    n, pi, ni, pg, ng = _group_tables(p, items, groups, g, m, v, ema)
+    check(lib().cx_adam_step_items(ptr(p), ptr(g), ptr(m), ptr(v), n, pi, ni, pg, ng, int(bool(decoupled)), ptr(hyper), lr, int(step),
+                                   beta1, beta2, eps, grad_scale, *_items_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)),
+          "cx_adam_step_items")
+
+
+def sgd_nesterov_step_items(p, g, buf, items, groups, decoupled, momentum, hyper=None, lr=0.0, step=0, grad_scale=1.0, clip=None,
+                            ema=None, ema_decay=0.0, ema_warmup=True, skip_nonfinite=False):
+    """SGD with Nesterov momentum over the item table (`buf` starts as zeros: there is no first-step switch)."""
+    n, pi, ni, pg, ng = _group_tables(p, items, groups, g, buf, ema)
+    check(lib().cx_sgd_nesterov_step_items(ptr(p), ptr(g), ptr(buf), n, pi, ni, pg, ng, int(bool(decoupled)), ptr(hyper), lr, int(step),
+                                           momentum, grad_scale, *_items_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)),
+          "cx_sgd_nesterov_step_items")
+
+
+def rmsprop_step_items(p, g, sq, buf, items, groups, decoupled, alpha, eps, momentum, hyper=None, lr=0.0, step=0, grad_scale=1.0,
+                       clip=None, ema=None, ema_decay=0.0, ema_warmup=True, skip_nonfinite=False):
+    """RMSprop with momentum over the item table."""
+    n, pi, ni, pg, ng = _group_tables(p, items, groups, g, sq, buf, ema)
+    check(lib().cx_rmsprop_step_items(ptr(p), ptr(g), ptr(sq), ptr(buf), n, pi, ni, pg, ng, int(bool(decoupled)), ptr(hyper), lr,
+                                      int(step), alpha, eps, momentum, grad_scale,
+                                      *_items_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)), "cx_rmsprop_step_items")
+
+
 def bf16_to_f32_nchw(x, out=None):
     B, H, W, Cc, ldx = _nhwc(x)
     if out is None:

@@ -6,10 +6,94 @@ RMSprop(momentum=0.9, eps=1e-3)), with the schedulers of :480 (MultiStepLR[40000
 (ExponentialLR(gamma)) folded in as `scheduler_step()`.
 """
 import contextlib
+import math
 
 import torch
 
 from . import ops
+
+MAX_GROUPS = 256
+
+
+def item_table(numels, group_of, vec4=None):
+    """The work items of the grouped kernels (csrc/optim_groups.hip) for tensors of `numels` floats laid out as `_fused.flatten`
+    lays them out (each at a multiple of 4 floats, zero-padded to one), tensor k in group group_of[k]: a list of
+    (start4, len4, group, tensor) in 16-byte units.  Every tensor, padding included, is cut into consecutive items of at most
+    `vec4` units (default: the library's constant); items come in buffer order and none crosses a tensor.  A function of the
+    shapes and the group assignment alone."""
+    V = int(ops.optim_item_vec4() if vec4 is None else vec4)
+    if V < 1:
+        raise ValueError("an item holds at least one 16-byte unit")
+    items, at = [], 0
+    for k, (n, grp) in enumerate(zip(numels, group_of)):
+        left = (int(n) + 3) // 4
+        while left > 0:
+            take = min(left, V)
+            items.append((at, take, int(grp), k))
+            at += take
+            left -= take
+    return items
+
+
+def reference_step(kind, p, g, state, lr, t, lr_mult=1.0, weight_decay=0.0, frozen=False, t0=0, decoupled=False,
+                   betas=(0.9, 0.999), eps=None, momentum=0.9, alpha=0.99):
+    """float64 restatement of one grouped step for the tensors of ONE group (what cx_*_step_items computes per element, and what
+    torch.optim.Adam / AdamW / SGD(nesterov) / RMSprop compute for a param_group): returns the new p, updates `state` (a list of
+    two tensors shaped like p, zeros before the first step) in place.  t is the 1-based number of the minibatch, t0 the number of
+    minibatches the group sat out before its first step (torch keeps one step count per parameter and starts it when the
+    parameter first has a gradient): Adam's bias corrections use t - t0.  frozen: nothing changes.
+    decoupled: p <- p * (1 - lr_g * wd) first, then the rule without decay (AdamW's order); else g <- g + wd * p."""
+    if frozen:
+        return p
+    p, g = p.double(), g.double()
+    lr_g = float(lr) * float(lr_mult)
+    if decoupled:
+        p = p * (1.0 - lr_g * weight_decay)
+    elif weight_decay != 0:
+        g = g + weight_decay * p
+    if kind == "adam":
+        tg = t - t0
+        e = 1e-8 if eps is None else eps
+        state[0] = betas[0] * state[0] + (1 - betas[0]) * g
+        state[1] = betas[1] * state[1] + (1 - betas[1]) * g * g
+        return p - lr_g / (1 - betas[0] ** tg) * (state[0] / (state[1].sqrt() / math.sqrt(1 - betas[1] ** tg) + e))
+    if kind == "sgd_nesterov":
+        state[0] = momentum * state[0] + g                  # zeros before the group's first step: the buffer starts as g
+        return p - lr_g * (g + momentum * state[0])
+    if kind == "rmsprop":
+        e = 1e-3 if eps is None else eps
+        state[0] = alpha * state[0] + (1 - alpha) * g * g
+        state[1] = momentum * state[1] + g / (state[0].sqrt() + e)
+        return p - lr_g * state[1]
+    raise ValueError("unknown optimiser kind %r" % (kind,))
+
+
+def finetune_groups(model, weight_decay=0.0, no_decay_norm_bias=False, head_lr_mult=1.0, backbone_lr_mult=1.0, freeze_backbone=False):
+    """The `groups` list of a fine-tuning run: the head (the last nn.Linear in named_modules() order: `classifier` of DenseNet, `fc`
+    of ResNet, the final layer of EfficientNet's head) against everything else, each split once more when no_decay_norm_bias
+    exempts every 1-D parameter (BatchNorm weights and biases, all biases) from weight decay.  Dicts carry a "name": "backbone",
+    "backbone_no_decay", "head", "head_no_decay"; an empty group is left out."""
+    head = None
+    for _, mod in model.named_modules():
+        if isinstance(mod, torch.nn.Linear):
+            head = mod
+    if head is None:
+        raise ValueError("finetune_groups: the model has no nn.Linear to call its head")
+    head_ids = {id(q) for q in head.parameters()}
+    parts = {"backbone": [], "backbone_no_decay": [], "head": [], "head_no_decay": []}
+    for q in model.parameters():
+        key = "head" if id(q) in head_ids else "backbone"
+        if no_decay_norm_bias and q.dim() <= 1:
+            key += "_no_decay"
+        parts[key].append(q)
+    out = []
+    for key, params in parts.items():
+        if params:
+            is_head = key.startswith("head")
+            out.append({"name": key, "params": params, "lr_mult": float(head_lr_mult if is_head else backbone_lr_mult),
+                        "weight_decay": 0.0 if key.endswith("_no_decay") else float(weight_decay),
+                        "frozen": bool(freeze_backbone) and not is_head})
+    return out
 
 
 class _Flat:
@@ -21,10 +105,23 @@ class _Flat:
       ema_warmup      decay = min(ema_decay, (1 + t) / (10 + t)) at step t, so the average forgets its start quickly
 
     With any of them on the step is `cx_grad_norm` (when clipping or skipping) + the `_ex` update.  The scheduler and Adam's bias
-    correction count minibatches, skipped ones included."""
-    NSTATE = 0
+    correction count minibatches, skipped ones included.
 
-    def __init__(self, model, lr, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True):
+    Parameter groups (`groups`, `decoupled`; both off by default, and then nothing here runs):
+
+      groups      list of {"params": iterable of the model's Parameters, "lr_mult": 1.0, "weight_decay": <the constructor's>,
+                  "frozen": False, "name": optional}.  Dict j is group j + 1; parameters named in no dict form group 0 (the
+                  constructor's weight_decay, lr_mult 1).  A frozen group is skipped by the kernels: no byte of its parameters,
+                  states or EMA is written, and its gradient counts neither for the clip norm nor as non-finite.
+      decoupled   weight decay as p <- p * (1 - lr_g * wd_g) ahead of the rule (AdamW's order) instead of g += wd_g * p
+
+    The step is then `cx_grad_norm_items` (when clipping or skipping) + `cx_*_step_items`, walking a per-tensor item table and
+    the group rows {lr_mult, weight_decay, frozen, t0} in device memory (`set_group` rewrites a row, between graph replays too)."""
+    NSTATE = 0
+    KIND = None
+
+    def __init__(self, model, lr, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True, weight_decay=0.0,
+                 decoupled=False, groups=None):
         self.model = model
         self.lr = float(lr)
         self.base_lr = float(lr)
@@ -41,6 +138,112 @@ class _Flat:
         self.ema_warmup = bool(ema_warmup)
         self._ws = self._clip = self._ema = None
         self._pending_ex = None
+        self.decoupled = bool(decoupled)
+        self._grouped = groups is not None or self.decoupled
+        self._items = self._gtab = self._gpart = self._gsq = self._gnorm = None
+        if self._grouped:
+            self._init_groups(groups or [], float(weight_decay))
+
+    # ---- parameter groups
+    def _init_groups(self, groups, weight_decay):
+        named = list(self.model.named_parameters())
+        name_of = {id(q): n for n, q in named}
+        if 1 + len(groups) > MAX_GROUPS:
+            raise ValueError("at most %d parameter groups (got %d dicts + the default group)" % (MAX_GROUPS, len(groups)))
+        self._group_of = {}                                 # id(parameter) -> group
+        self.group_names = ["default"]
+        self._grows = [[1.0, weight_decay, 0.0, 0.0]]       # {lr_mult, weight_decay, frozen, t0}, the host copy of the device table
+        for j, d in enumerate(groups):
+            extra = set(d) - {"params", "lr_mult", "weight_decay", "frozen", "name"}
+            if "params" not in d or extra:
+                raise ValueError("group %d: a dict with 'params' and optionally lr_mult, weight_decay, frozen, name (got %s)" % (j, sorted(d)))
+            lr_mult, wd = float(d.get("lr_mult", 1.0)), float(d.get("weight_decay", weight_decay))
+            if not (math.isfinite(lr_mult) and lr_mult >= 0.0):
+                raise ValueError("group %d: lr_mult must be finite and >= 0 (got %r)" % (j, d.get("lr_mult")))
+            if not math.isfinite(wd):
+                raise ValueError("group %d: weight_decay must be finite (got %r)" % (j, d.get("weight_decay")))
+            for q in d["params"]:
+                if id(q) not in name_of:
+                    raise ValueError("group %d names a parameter that is not the model's" % j)
+                if id(q) in self._group_of:
+                    raise ValueError("parameter %s appears twice in the groups" % name_of[id(q)])
+                self._group_of[id(q)] = j + 1
+            self.group_names.append(str(d.get("name", "group%d" % (j + 1))))
+            self._grows.append([lr_mult, wd, 1.0 if d.get("frozen", False) else 0.0, 0.0])
+        self._gparams = [[] for _ in self._grows]           # parameter names of each group, in the model's order
+        for n, q in named:
+            self._gparams[self._group_of.get(id(q), 0)].append(n)
+        self._frozen_at = [0] * len(self._grows)            # steps done when the group was frozen
+
+    def _group_bufs(self, eng):
+        dev = eng.flat.device
+        if self._items is not None and self._items.device == dev and self._gnumel == eng.flat.numel():
+            return
+        if len(eng.params) != sum(len(v) for v in self._gparams):
+            raise RuntimeError("the engine holds %d parameters, the groups were built over %d" % (len(eng.params), sum(len(v) for v in self._gparams)))
+        items = item_table([q.numel() for q in eng.params], [self._group_of.get(id(q), 0) for q in eng.params])
+        # the kernels trust the table: check it against the buffer it will walk
+        tensor_start = {}
+        for it in items:
+            tensor_start.setdefault(it[3], it[0])
+        if any(4 * tensor_start[k] != off for k, off in enumerate(eng.offsets)) or \
+                (items and 4 * (items[-1][0] + items[-1][1]) != eng.flat.numel()) or (not items and eng.flat.numel()):
+            raise RuntimeError("the item table does not match the layout of the flat parameter buffer")
+        self._items = torch.tensor(items, dtype=torch.int32).reshape(-1, 4).to(dev)
+        self._gtab = torch.tensor(self._grows, dtype=torch.float32).to(dev)
+        self._gpart = torch.zeros(max(1, len(items)), dtype=torch.float32, device=dev)
+        self._gsq = torch.zeros(len(self._grows), dtype=torch.float32, device=dev)
+        self._gnorm = torch.zeros(len(self._grows), dtype=torch.float32, device=dev)
+        self._gnumel = eng.flat.numel()
+
+    def set_group(self, i, lr_mult=None, weight_decay=None, frozen=None):
+        """Rewrites row i of the group table (None: keep) with one small host-to-device copy on the current stream, so the next
+        step -- a replay of a captured one included -- sees it.  Freezing notes the steps done; thawing adds the steps the group
+        sat out to its t0 (for a group frozen from the start: t0 = the steps done), so that Adam's bias corrections count the
+        group's own steps, as torch does for a parameter whose gradient was None until then.  Thawing reads the device step count
+        (`sync_from_device`: synchronises)."""
+        if not self._grouped:
+            raise RuntimeError("set_group() needs an optimiser built with groups (or decoupled=True)")
+        row = self._grows[i]
+        if lr_mult is not None:
+            if not (math.isfinite(float(lr_mult)) and float(lr_mult) >= 0.0):
+                raise ValueError("lr_mult must be finite and >= 0 (got %r)" % (lr_mult,))
+            row[0] = float(lr_mult)
+        if weight_decay is not None:
+            if not math.isfinite(float(weight_decay)):
+                raise ValueError("weight_decay must be finite (got %r)" % (weight_decay,))
+            row[1] = float(weight_decay)
+        if frozen is not None and bool(frozen) != (row[2] != 0.0):
+            self.sync_from_device()
+            if frozen:
+                self._frozen_at[i] = self.step_count
+            else:
+                row[3] += float(self.step_count - self._frozen_at[i])
+            row[2] = 1.0 if frozen else 0.0
+        if self._gtab is not None:
+            self._gtab[i].copy_(torch.tensor(row, dtype=torch.float32))
+
+    def group_grad_norms(self):
+        """L2 norm of the (unscaled) gradient of every group at the most recent step, frozen groups included.  Reads the device:
+        synchronises."""
+        if not self._grouped:
+            raise RuntimeError("group_grad_norms() needs an optimiser built with groups")
+        self._clip_host()
+        return [0.0] * len(self._grows) if self._gnorm is None else [float(v) for v in self._gnorm.cpu()]
+
+    def _step_items(self, grad_scale, dev, **rule):
+        """One grouped step: the segmented norm when clipping or skipping is on, then the rule over the item table."""
+        p, g, st = self._bufs(self.NSTATE)
+        if self._norm_on():
+            ops.grad_norm_items(g, self._items, self._gtab, self._gpart, self._gsq, self._gnorm, self._clip, grad_scale,
+                                self.max_grad_norm or 0.0, self.skip_nonfinite)
+        where = {"hyper": self.hyper()} if dev else {"lr": self.lr, "step": self.step_count + 1}
+        getattr(ops, self.KIND + "_step_items")(p, g, *st, self._items, self._gtab, self.decoupled, grad_scale=grad_scale,
+                                                clip=self._clip if self._norm_on() else None, ema=self._ema,
+                                                ema_decay=self.ema_decay or 0.0, ema_warmup=self.ema_warmup,
+                                                skip_nonfinite=self.skip_nonfinite, **where, **rule)
+        if not dev:
+            self.step_count += 1
 
     def _norm_on(self):
         return self.max_grad_norm is not None or self.skip_nonfinite
@@ -71,6 +274,8 @@ class _Flat:
                 self._clip[3] = float(pend.get("skipped", 0))
                 if self._ema is not None and pend.get("ema") is not None:
                     self._ema.copy_(pend["ema"])
+        if self._grouped:
+            self._group_bufs(eng)
         return eng.flat, eng.flat_grad, self._state
 
     def _ex_args(self, g, grad_scale):
@@ -150,11 +355,16 @@ class _Flat:
                        "ema_warmup": self.ema_warmup,
                        "skipped": int(self._clip[3]) if self._clip is not None else int(pend.get("skipped", 0)),
                        "ema": self._ema.detach().cpu().clone() if self._ema is not None else pend.get("ema")})
+        if self._grouped:
+            sd["groups"] = {"rows": [list(r) for r in self._grows], "decoupled": self.decoupled, "names": list(self.group_names),
+                            "params": [list(v) for v in self._gparams], "frozen_at": list(self._frozen_at)}
         return sd
 
     def load_state_dict(self, sd):
         if sd.get("kind") != type(self).__name__:
             raise RuntimeError("optimizer checkpoint was written by %s, this is %s" % (sd.get("kind"), type(self).__name__))
+        if "groups" in sd:                             # (a checkpoint written without groups leaves them as constructed)
+            self._load_groups(sd["groups"])
         self.lr, self.base_lr, self.step_count, self.sched_steps = sd["lr"], sd["base_lr"], sd["step_count"], sd["sched_steps"]
         self._pending_state = sd["state"]              # copied into the flat-buffer state once the engine is bound
         self._hyper = None
@@ -163,6 +373,29 @@ class _Flat:
             self.ema_decay, self.ema_warmup = sd["ema_decay"], bool(sd["ema_warmup"])
             self._pending_ex = {"skipped": int(sd.get("skipped", 0)), "ema": sd.get("ema")}
             self._ws = self._clip = self._ema = None
+
+    def _load_groups(self, gs):
+        if not self._grouped:
+            raise RuntimeError("the optimizer checkpoint was written with parameter groups: build the optimiser with the same groups "
+                               "(decoupled=%r) before loading it" % bool(gs["decoupled"]))
+        mine = {n: k for k, names in enumerate(self._gparams) for n in names}
+        theirs = {n: k for k, names in enumerate(gs["params"]) for n in names}
+        for n, k in mine.items():
+            if theirs.get(n) != k:
+                raise RuntimeError("the optimizer checkpoint partitions the parameters differently: %s is in group %s there, in group "
+                                   "%d here" % (n, theirs.get(n, "none"), k))
+        for n in theirs:
+            if n not in mine:
+                raise RuntimeError("the optimizer checkpoint partitions the parameters differently: %s is not a parameter here" % n)
+        if len(gs["rows"]) != len(self._grows):
+            raise RuntimeError("the optimizer checkpoint has %d parameter groups, this optimiser %d" % (len(gs["rows"]), len(self._grows)))
+        if bool(gs["decoupled"]) != self.decoupled:
+            raise RuntimeError("the optimizer checkpoint was written with decoupled=%r, this optimiser has decoupled=%r"
+                               % (bool(gs["decoupled"]), self.decoupled))
+        self._grows = [[float(v) for v in r] for r in gs["rows"]]
+        self._frozen_at = [int(v) for v in gs.get("frozen_at", [0] * len(self._grows))]
+        if self._gtab is not None:
+            self._gtab.copy_(torch.tensor(self._grows, dtype=torch.float32))
 
     def sync_from_device(self):
         if getattr(self, "_hyper", None) is not None:
@@ -176,12 +409,18 @@ class _Flat:
 
 class FusedAdam(_Flat):
     NSTATE = 2
+    KIND = "adam"
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **options):
-        super().__init__(model, lr, **options)
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, groups=None, **options):
+        super().__init__(model, lr, weight_decay=weight_decay, decoupled=decoupled, groups=groups, **options)
         self.betas, self.eps, self.wd = betas, eps, weight_decay
 
+    def _rule(self):
+        return {"beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps}
+
     def step(self, grad_scale=1.0):
+        if self._grouped:
+            return self._step_items(grad_scale, False, **self._rule())
         p, g, (m, v) = self._bufs(2)
         self.step_count += 1
         if self._ex_on():
@@ -191,6 +430,8 @@ class FusedAdam(_Flat):
         ops.adam_step(p, g, m, v, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, grad_scale)
 
     def step_dev(self, grad_scale=1.0):
+        if self._grouped:
+            return self._step_items(grad_scale, True, **self._rule())
         p, g, (m, v) = self._bufs(2)
         if self._ex_on():
             ops.adam_step_dev_ex(p, g, m, v, self.hyper(), self.betas[0], self.betas[1], self.eps, self.wd, grad_scale,
@@ -201,14 +442,18 @@ class FusedAdam(_Flat):
 
 class FusedSGDNesterov(_Flat):
     NSTATE = 1
+    KIND = "sgd_nesterov"
 
-    def __init__(self, model, lr, momentum=0.9, weight_decay=0.0, milestones=(40000, 60000), gamma=0.1, **options):
-        super().__init__(model, lr, **options)
+    def __init__(self, model, lr, momentum=0.9, weight_decay=0.0, milestones=(40000, 60000), gamma=0.1, decoupled=False, groups=None,
+                 **options):
+        super().__init__(model, lr, weight_decay=weight_decay, decoupled=decoupled, groups=groups, **options)
         self.momentum, self.wd, self.milestones, self.gamma = momentum, weight_decay, tuple(milestones), gamma
         ms = (tuple(milestones) + (1 << 30, 1 << 30))[:2]
         self._sched = (2, gamma, ms)
 
     def step_dev(self, grad_scale=1.0):
+        if self._grouped:
+            return self._step_items(grad_scale, True, momentum=self.momentum)
         p, g, (buf,) = self._bufs(1)
         if self._ex_on():
             ops.sgd_nesterov_step_dev_ex(p, g, buf, self.hyper(), self.momentum, self.wd, grad_scale, **self._ex_args(g, grad_scale))
@@ -216,6 +461,8 @@ class FusedSGDNesterov(_Flat):
         ops.sgd_nesterov_step_dev(p, g, buf, self.hyper(), self.momentum, self.wd, grad_scale)
 
     def step(self, grad_scale=1.0):
+        if self._grouped:
+            return self._step_items(grad_scale, False, momentum=self.momentum)
         p, g, (buf,) = self._bufs(1)
         if self._ex_on():
             ops.sgd_nesterov_step_ex(p, g, buf, self.lr, self.momentum, self.wd, self.step_count == 0, self.step_count + 1, grad_scale,
@@ -231,13 +478,20 @@ class FusedSGDNesterov(_Flat):
 
 class FusedRMSprop(_Flat):
     NSTATE = 2
+    KIND = "rmsprop"
 
-    def __init__(self, model, lr, alpha=0.99, eps=1e-3, momentum=0.9, weight_decay=0.0, decay=0.97, **options):
-        super().__init__(model, lr, **options)
+    def __init__(self, model, lr, alpha=0.99, eps=1e-3, momentum=0.9, weight_decay=0.0, decay=0.97, decoupled=False, groups=None,
+                 **options):
+        super().__init__(model, lr, weight_decay=weight_decay, decoupled=decoupled, groups=groups, **options)
         self.alpha, self.eps, self.momentum, self.wd, self.decay = alpha, eps, momentum, weight_decay, decay
         self._sched = (1, decay, (0, 0))
 
+    def _rule(self):
+        return {"alpha": self.alpha, "eps": self.eps, "momentum": self.momentum}
+
     def step_dev(self, grad_scale=1.0):
+        if self._grouped:
+            return self._step_items(grad_scale, True, **self._rule())
         p, g, (sq, buf) = self._bufs(2)
         if self._ex_on():
             ops.rmsprop_step_dev_ex(p, g, sq, buf, self.hyper(), self.alpha, self.eps, self.momentum, self.wd, grad_scale,
@@ -246,6 +500,8 @@ class FusedRMSprop(_Flat):
         ops.rmsprop_step_dev(p, g, sq, buf, self.hyper(), self.alpha, self.eps, self.momentum, self.wd, grad_scale)
 
     def step(self, grad_scale=1.0):
+        if self._grouped:
+            return self._step_items(grad_scale, False, **self._rule())
         p, g, (sq, buf) = self._bufs(2)
         if self._ex_on():
             ops.rmsprop_step_ex(p, g, sq, buf, self.lr, self.alpha, self.eps, self.momentum, self.wd, self.step_count + 1, grad_scale,

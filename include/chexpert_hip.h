@@ -525,6 +525,45 @@ int cx_rmsprop_step_dev_ex(float* p, const float* g, float* sq, float* buf, size
                            float momentum, float weight_decay, float grad_scale, const float* clip, float* ema, float ema_decay,
                            int ema_warmup, int skip_nonfinite, void* stream);
 
+/* Parameter groups for the fused optimisers (optim_groups.hip): per-group learning-rate multiplier, weight decay (L2 or decoupled),
+ * frozen groups and a per-group step count.  The flat buffers hold every parameter tensor at a multiple of 4 floats, zero-padded
+ * to a multiple of 4 (n % 4 == 0), and are walked through two tables in device memory:
+ *   items  = uint32[n_items][4] {start4, len4, group, tensor}: a run of len4 16-byte units from unit start4, all of one tensor,
+ *            len4 <= cx_optim_item_vec4() (a constant); items in buffer order, covering every unit exactly once.  The kernels
+ *            trust the table: start4 + len4 <= n / 4 and group < n_groups are the caller's to guarantee.
+ *   groups = float[n_groups][4] {lr_mult, weight_decay, frozen, t0}, 1 <= n_groups <= 256.  Read by the kernels at every launch,
+ *            so a captured hipGraph sees a row rewritten between two replays.
+ * cx_grad_norm_items: two launches, no atomics.  Launch 1 plain-stores one partial sum of (grad_scale * g)^2 per item to
+ * `partials` (n_items floats).  Launch 2, one workgroup: group_sq[k] = the partials of group k added one by one in item order,
+ * group_norm[k] = sqrt(group_sq[k]) (frozen groups too); then the group_sq of the groups with frozen == 0 added in group order give
+ * clip = {norm, coef, nonfinite, skipped} exactly as cx_grad_norm defines them.  A non-finite value in a frozen group shows in that
+ * group's group_norm only.
+ * cx_*_step_items: hyper null -> `lr` and the 1-based `step` are the host's; else lr = hyper[0], step = hyper[1] + 1 (the arguments
+ * are ignored).  Per item of group k: frozen != 0 -> skipped, no byte of p, the states or ema written; lr_k = lr * lr_mult;
+ * decoupled == 0: g += weight_decay_k * p (the L2 form of the plain steps); decoupled != 0: p <- p * (1 - lr_k * weight_decay_k)
+ * first, then the rule without decay (torch.optim.AdamW's order).  Adam's bias corrections use step - t0_k, the group's own step
+ * count; SGD and RMSprop do not read t0.  The SGD momentum buffer must start as zeros (momentum * 0 + g is the first step's
+ * buffer).  clip / ema / ema_decay / ema_warmup / skip_nonfinite as in the *_ex steps (the EMA's warm-up counts `step`, not
+ * step - t0).  Padding floats stay 0 under every rule.
+ * CX_EINVAL before any launch: a null pointer (clip and ema may be null; buf of RMSprop when momentum == 0), n_groups outside
+ * [1, 256], n % 4 != 0, n_items == 0 with n > 0, step < 1 without hyper, ema_decay outside [0, 1].  CX_EALIGN: a buffer or table
+ * that is not 16-byte aligned.                                                                                                     */
+int cx_optim_item_vec4(void);
+int cx_grad_norm_items(const float* g, size_t n, const uint32_t* items, int n_items, const float* groups, int n_groups,
+                       float grad_scale, float max_norm, int skip_nonfinite, float* partials, float* group_sq, float* group_norm,
+                       float* clip, void* stream);
+int cx_adam_step_items(float* p, const float* g, float* m, float* v, size_t n, const uint32_t* items, int n_items, const float* groups,
+                       int n_groups, int decoupled, const float* hyper, float lr, int step, float beta1, float beta2, float eps,
+                       float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup, int skip_nonfinite,
+                       void* stream);
+int cx_sgd_nesterov_step_items(float* p, const float* g, float* buf, size_t n, const uint32_t* items, int n_items, const float* groups,
+                               int n_groups, int decoupled, const float* hyper, float lr, int step, float momentum, float grad_scale,
+                               const float* clip, float* ema, float ema_decay, int ema_warmup, int skip_nonfinite, void* stream);
+int cx_rmsprop_step_items(float* p, const float* g, float* sq, float* buf, size_t n, const uint32_t* items, int n_items,
+                          const float* groups, int n_groups, int decoupled, const float* hyper, float lr, int step, float alpha, float eps,
+                          float momentum, float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup,
+                          int skip_nonfinite, void* stream);
+
 /* ---- attention-augmented convolution (AAConv2d, models/attn_aug_conv.py:19-100) --------------------
  * qkv: bf16 (B, H*W, ldq) output of in_proj_qkv (channels [q dk | k dk | v dv], head-major), ldq % 4 == 0.
  * Head widths dkh = dk/nh and dvh = dv/nh of 1 .. 64 with dv <= 104: dkh = 20 with dvh <= 13 runs the row / generic kernels
