@@ -1,0 +1,658 @@
+// The fused optimisers over the engine's flat fp32 buffers: Adam, SGD with Nesterov momentum and RMSprop, each update rule stated
+// once, in three kernel families.
+//
+//   cx_*_step[_dev]       the plain one-kernel update.  `_dev`: the learning rate and the step count live in device memory
+//                         (hyper = {lr, steps_done, sched_kind, gamma, warmup_steps, milestone0, milestone1, base_lr}), so a captured
+//                         hipGraph can be replayed while both change; cx_optim_tick advances them
+//   cx_grad_norm          two launches, no atomics: per-workgroup partial sums of (grad_scale * g)^2 over fixed contiguous ranges, then
+//                         ONE workgroup that sums the partials and writes clip[4] = {norm, coef, nonfinite, skipped} to device memory
+//   cx_*_step[_dev]_ex    the plain update with the gradient multiplied by clip[1], nothing written at all when clip[2] says the
+//                         gradient was not finite and skipping is on, and ema = d * ema + (1 - d) * p_new written by the thread that
+//                         computed p_new; with clip and ema both null the call IS the plain entry point (its kernel, its bits)
+//   cx_grad_norm_items    the segmented form of cx_grad_norm: one partial per item, then ONE workgroup that sums the partials per group
+//                         in item order, the unfrozen groups in group order, and writes clip[4] as cx_grad_norm does.  No atomics.
+//   cx_*_step_items       parameter groups (per-group learning-rate multiplier, weight decay (L2 or decoupled), frozen groups, a
+//                         per-group step count): a workgroup takes slices of items, reads the item's group row once per slice and
+//                         streams it with 16-byte loads and stores; an item of a frozen group is skipped: no byte written
+//
+// The grouped kernels walk a table of work items instead of the flat index range.  The flat buffers hold every parameter tensor at
+// an offset that is a multiple of 4 floats, zero-padded to a multiple of 4:
+//
+//   item  = uint32[4] {start4, len4, group, tensor}   a run of len4 16-byte units from unit start4, all of ONE tensor
+//                                                      (len4 <= cx_optim_item_vec4(); items in buffer order, covering every unit once)
+//   group = float[4]  {lr_mult, weight_decay, frozen, t0}   one row per group, 1 <= G <= 256, in DEVICE memory: a captured hipGraph
+//                                                      of the training step sees a row that was rewritten between two replays
+//
+// The cut into items never changes what is computed for an element: every element sees the same expressions on the same values
+// whatever item it falls in (tests/test_optim_groups_gpu.py: one group against five, bit for bit).
+//
+// Nothing here reads a gradient on the host, so a captured hipGraph of the training step replays all of it.
+#include <math.h>
+#include "common.h"
+
+namespace {
+
+constexpr int THREADS = 256;             // 4 waves; one pass of a workgroup covers 256 16-byte units (4 KiB of each buffer)
+constexpr int MAX_BLOCKS = 2048;         // 256 CUs x 8 workgroups
+constexpr int GN_MIN_VEC = 1024;         // 16-byte loads per workgroup before a second workgroup is worth its launch (16 KB)
+// Longest item, in 16-byte units.  A constant: the table (and with it the summation tree of the norm) is a function of the parameter
+// shapes and the group assignment alone, never of the device or of occupancy.  Chosen from profiles/optim_groups_bench.txt: the
+// second launch of the norm adds the partials one by one, so its time grows with the number of items and wants them long ...
+constexpr int OG_ITEM_VEC4 = 8192;
+// ... while the steps want many small pieces to spread over the workgroups (DenseNet121 is 530 items of this length), so a step
+// hands out slices of items: OG_SLOT_VEC4 units (16 KiB of each buffer), OG_ITEM_VEC4 / OG_SLOT_VEC4 slots per item.
+constexpr int OG_SLOT_VEC4 = 1024;
+constexpr int OG_SLOTS = OG_ITEM_VEC4 / OG_SLOT_VEC4;
+constexpr int OG_MAX_GROUPS = 256;
+
+struct Item {
+  uint32_t start4, len4, group, tensor;
+};
+
+inline int blocks_for(long long work) { return work < 1 ? 1 : work > MAX_BLOCKS ? MAX_BLOCKS : (int)work; }
+
+// The grid of cx_grad_norm is a function of n alone (never of the device or of occupancy), so the summation tree, and with it every
+// bit of the norm, is the same on every run and on every rank of a data-parallel job.
+inline int gn_blocks(size_t n) { return n == 0 ? 0 : blocks_for((long long)(((n >> 2) + GN_MIN_VEC - 1) / GN_MIN_VEC)); }
+
+// ---- the norms ------------------------------------------------------------------------------------------------------------------
+// Thread t takes the 16-byte units lo + t, lo + t + 256, ... < hi of g into four accumulators, one per component (fused
+// multiply-adds), and joins them as (a0 + a1) + (a2 + a3).  Coalesced: a wave reads 1 KiB per instruction.  g is read with plain
+// loads: the step that follows reads it again, out of the caches where it still fits.
+__device__ __forceinline__ float sq_units(const float* __restrict__ g, size_t lo, size_t hi, float gscale) {
+  const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 4
+  for (size_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+    const f32x4 v = g4[i];
+    const float x0 = v[0] * gscale, x1 = v[1] * gscale, x2 = v[2] * gscale, x3 = v[3] * gscale;
+    a0 = fmaf(x0, x0, a0);
+    a1 = fmaf(x1, x1, a1);
+    a2 = fmaf(x2, x2, a2);
+    a3 = fmaf(x3, x3, a3);
+  }
+  return (a0 + a1) + (a2 + a3);
+}
+
+// wave fold (6 shuffle levels, lane 0 ends with the sum of the wave), then the 4 wave sums in wave order; valid in thread 0.  A
+// caller that folds again puts a __syncthreads() between the two: wave_sum is written anew.
+__device__ __forceinline__ float block_fold(float v) {
+  __shared__ float wave_sum[THREADS / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+}
+
+// One thread, the sum of squares in hand.  clip = {norm, coef, nonfinite, skipped}: coef is torch.nn.utils.clip_grad_norm_'s
+// clamp(max_norm / (norm + 1e-6), max = 1) (1 when max_norm <= 0: clipping off, the norm is still reported); `skipped` counts the
+// steps that the kernels below will drop (a float: exact up to 2^24).
+__device__ __forceinline__ void write_clip(float sum, float max_norm, int skip_nonfinite, float* __restrict__ clip) {
+  const float norm = sqrtf(sum);
+  const bool nonfinite = !(sum < INFINITY);                 // inf or NaN (the sum of squares is never negative)
+  float coef = 1.f;
+  if (max_norm > 0.f) {
+    const float c = max_norm / (norm + 1e-6f);
+    coef = c > 1.f ? 1.f : c;                               // NaN stays NaN, as torch.clamp leaves it
+  }
+  clip[0] = norm;
+  clip[1] = coef;
+  clip[2] = nonfinite ? 1.f : 0.f;
+  if (nonfinite && skip_nonfinite) clip[3] += 1.f;
+}
+
+// cx_grad_norm, launch 1.  Workgroup b owns the 16-byte units [b * per, min((b + 1) * per, n / 4)), per = ceil((n / 4) / gridDim.x).
+// The n % 4 trailing floats go to threads 0..2 of the last workgroup.
+__global__ __launch_bounds__(THREADS) void grad_sq_partial_kernel(const float* __restrict__ g, size_t n, float gscale,
+                                                                   float* __restrict__ part) {
+  const size_t n4 = n >> 2;
+  const size_t per = (n4 + gridDim.x - 1) / gridDim.x;
+  const size_t lo = (size_t)blockIdx.x * per;
+  const size_t hi = lo + per < n4 ? lo + per : n4;
+  float acc = sq_units(g, lo, hi, gscale);
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x < (n & 3)) {
+    const float x = g[(n4 << 2) + threadIdx.x] * gscale;
+    acc = fmaf(x, x, acc);
+  }
+  const float s = block_fold(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// cx_grad_norm, launch 2: one workgroup.  Thread t sums partials [t * per, (t + 1) * per) in index order (per = ceil(nparts / 256)
+// <= 8), the 256 sums are folded as above.
+__global__ __launch_bounds__(THREADS) void grad_norm_final_kernel(const float* __restrict__ part, int nparts, float max_norm,
+                                                                   int skip_nonfinite, float* __restrict__ clip) {
+  const int per = (nparts + THREADS - 1) / THREADS;
+  const int lo = threadIdx.x * per;
+  const int hi = lo + per < nparts ? lo + per : nparts;
+  float acc = 0.f;
+  for (int i = lo; i < hi; ++i) acc += part[i];
+  const float sum = block_fold(acc);
+  if (threadIdx.x == 0) write_clip(sum, max_norm, skip_nonfinite, clip);
+}
+
+// cx_grad_norm_items, launch 1.  Workgroup b takes items b, b + gridDim.x, ...; the units of an item are summed and folded as a
+// range of grad_sq_partial_kernel is.  One plain store per item.
+__global__ __launch_bounds__(THREADS) void item_sq_partial_kernel(const float* __restrict__ g, const Item* __restrict__ items,
+                                                                   int n_items, float gscale, float* __restrict__ part) {
+  for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
+    const Item item = items[it];
+    const float s = block_fold(sq_units(g, item.start4, (size_t)item.start4 + item.len4, gscale));
+    if (threadIdx.x == 0) part[it] = s;
+    __syncthreads();
+  }
+}
+
+// cx_grad_norm_items, launch 2: one workgroup.  Thread q < G owns group q: it adds the partials of the group's items one by one in
+// item order, writes group_sq[q] and group_norm[q] -- for a frozen group too.  The items pass through LDS 256 at a time; every thread
+// reads the same four (group, partial) pairs per step (16-byte broadcasts) and adds either the partial or +0 (exact: the sum is never
+// negative), so the only instruction on the dependent chain is the addition itself.  Thread 0 then adds group_sq of the groups with
+// frozen == 0 in group order.  A partial of another group is selected away, never multiplied by zero: an inf or NaN in a frozen
+// group reaches that group's group_norm and nothing else.
+__global__ __launch_bounds__(THREADS) void group_norm_final_kernel(const float* __restrict__ part, const Item* __restrict__ items,
+                                                                    int n_items, const float* __restrict__ groups, int n_groups,
+                                                                    float max_norm, int skip_nonfinite, float* __restrict__ group_sq,
+                                                                    float* __restrict__ group_norm, float* __restrict__ clip) {
+  __shared__ __attribute__((aligned(16))) float s_part[THREADS];
+  __shared__ __attribute__((aligned(16))) uint32_t s_group[THREADS];
+  __shared__ float s_sq[OG_MAX_GROUPS];
+  const uint32_t q = threadIdx.x;
+  float acc = 0.f;
+  for (int base = 0; base < n_items; base += THREADS) {
+    const int cnt = n_items - base < THREADS ? n_items - base : THREADS;
+    const bool have = (int)threadIdx.x < cnt;
+    s_part[threadIdx.x] = have ? part[base + threadIdx.x] : 0.f;
+    s_group[threadIdx.x] = have ? items[base + threadIdx.x].group : 0xffffffffu;      // matches no group
+    __syncthreads();
+    if (q < (uint32_t)n_groups) {
+#pragma unroll 4
+      for (int j = 0; j < cnt; j += 4) {
+        const uint4 gq = *reinterpret_cast<const uint4*>(&s_group[j]);
+        const f32x4 pv = *reinterpret_cast<const f32x4*>(&s_part[j]);
+        acc += gq.x == q ? pv[0] : 0.f;
+        acc += gq.y == q ? pv[1] : 0.f;
+        acc += gq.z == q ? pv[2] : 0.f;
+        acc += gq.w == q ? pv[3] : 0.f;
+      }
+    }
+    __syncthreads();
+  }
+  if (q < (uint32_t)n_groups) {
+    s_sq[q] = acc;
+    group_sq[q] = acc;
+    group_norm[q] = sqrtf(acc);
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  float sum = 0.f;
+  for (int k = 0; k < n_groups; ++k)
+    if (groups[4 * k + 2] == 0.f) sum += s_sq[k];
+  write_clip(sum, max_norm, skip_nonfinite, clip);
+}
+
+// ---- the update rules -----------------------------------------------------------------------------------------------------------
+// A rule holds its state pointers (s0, s1) and the constants of the optimiser.  begin(lr, t) takes what a launch, or a group row,
+// fixes: the learning rate and the 1-based step number; update() is the rule on values in registers, the gradient already scaled
+// and decayed; has_s0() / has_s1() say whether the step reads a state at all (SGD's first step does not read buf, RMSprop
+// without momentum never touches its buf).
+struct AdamRule {
+  float *s0, *s1;                 // m, v
+  float b1, b2, eps;
+  float bc1, bc2_sqrt;            // host_bc: the bias corrections are the host's powf (cx_adam_step[_ex]); else begin() computes them
+  bool host_bc;
+  float step_size;
+  __device__ __forceinline__ bool has_s0() const { return true; }
+  __device__ __forceinline__ bool has_s1() const { return true; }
+  __device__ __forceinline__ void begin(float lr, float t) {
+    if (!host_bc) {
+      bc1 = 1.f - powf(b1, t);
+      bc2_sqrt = sqrtf(1.f - powf(b2, t));
+    }
+    step_size = lr / bc1;
+  }
+  __device__ __forceinline__ float update(float gi, float pi, float& mi, float& vi) const {
+    mi = b1 * mi + (1.f - b1) * gi;
+    vi = b2 * vi + (1.f - b2) * gi * gi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    return pi - step_size * (mi / denom);
+  }
+};
+
+struct SgdRule {
+  float *s0, *s1;                 // buf, unused
+  float mom;
+  // The flat steps: 1 on the first step (buf is not read: it becomes g), 0 after it, -1: the first step is t == 1 (`hyper` form).
+  // The grouped steps: 0 always.  There the momentum buffer starts as zeros and a frozen item never writes it, so momentum * 0 + g
+  // IS g on the first step of a group, whenever that is.
+  int first;
+  float lr;
+  __device__ __forceinline__ bool has_s0() const { return !first; }
+  __device__ __forceinline__ bool has_s1() const { return false; }
+  __device__ __forceinline__ void begin(float lr_, float t) {
+    lr = lr_;
+    if (first < 0) first = t == 1.f;
+  }
+  __device__ __forceinline__ float update(float gi, float pi, float& bi, float&) const {
+    bi = first ? gi : mom * bi + gi;
+    return pi - lr * (gi + mom * bi);
+  }
+};
+
+struct RmsRule {
+  float *s0, *s1;                 // sq, buf (may be null when mom == 0)
+  float alpha, eps, mom;
+  float lr;
+  __device__ __forceinline__ bool has_s0() const { return true; }
+  __device__ __forceinline__ bool has_s1() const { return mom > 0.f; }
+  __device__ __forceinline__ void begin(float lr_, float) { lr = lr_; }
+  __device__ __forceinline__ float update(float gi, float pi, float& si, float& bi) const {
+    si = alpha * si + (1.f - alpha) * gi * gi;
+    const float avg = sqrtf(si) + eps;
+    if (mom > 0.f) {
+      bi = mom * bi + gi / avg;
+      return pi - lr * bi;
+    }
+    return pi - lr * gi / avg;
+  }
+};
+
+// Weight decay ahead of the rule.  L2: g += wd * p.  Decoupled: p <- p * keep, keep = 1 - lr * wd, and the rule without decay
+// (torch.optim.AdamW's order).
+__device__ __forceinline__ void decay(float& gi, float& pi, bool decoupled, float wd, float keep) {
+  if (decoupled)
+    pi = pi * keep;
+  else if (wd != 0.f)
+    gi += wd * pi;
+}
+
+// ---- clip, skip and EMA: what the *_ex and the grouped steps share --------------------------------------------------------------
+struct Tail {
+  const float* clip;
+  float* ema;
+  float ema_decay;
+  int ema_warmup;
+  int skip_nonfinite;
+};
+
+// What a launch fixes before its loop.  `hyper` null: lr and the 1-based step number t are the host's arguments; else hyper[0] and
+// hyper[1] + 1 (cx_optim_tick's table).  gs = grad_scale * clip[1] (clip null: grad_scale * 1); d = the EMA's decay at step t.
+struct Launch {
+  float lr, t, gs, d, omd;
+};
+
+// false: clip[2] says the gradient was not finite and skipping is on.  The whole grid takes the same side: nothing is written.
+__device__ __forceinline__ bool begin_launch(const Tail& x, const float* __restrict__ hyper, float lr, int step, float gscale,
+                                             Launch& q) {
+  if (x.clip && x.skip_nonfinite && x.clip[2] != 0.f) return false;
+  q.lr = hyper ? hyper[0] : lr;
+  q.t = hyper ? hyper[1] + 1.f : (float)step;
+  q.gs = gscale * (x.clip ? x.clip[1] : 1.f);
+  q.d = x.ema_decay;
+  if (x.ema && x.ema_warmup) q.d = fminf(q.d, (1.f + q.t) / (10.f + q.t));
+  q.omd = 1.f - q.d;
+  return true;
+}
+
+// CX_EINVAL / CX_EALIGN before any launch.  units16: the kernel moves ema in 16-byte units.
+int check_tail(const float* hyper, int step, const float* ema, float ema_decay, bool units16) {
+  if (ema && !(ema_decay >= 0.f && ema_decay <= 1.f)) return CX_EINVAL;
+  if (!hyper && step < 1) return CX_EINVAL;
+  if (units16 && !aligned16(ema)) return CX_EALIGN;
+  return 0;
+}
+
+// ---- the flat steps -------------------------------------------------------------------------------------------------------------
+// Adam and SGD (RMSprop: below).  One kernel per rule and per TAIL serves the host-lr and the `hyper` form.  TAIL false is the plain step: no clip, no skip, no EMA
+// (x is not read).  Same source is not same bits: under -ffp-contract=fast what the compiler fuses into one rounding and what it
+// packs two by two (v_pk_mul_f32) and adds unfused differs between the two instantiations, which is why the
+// *_ex entry points hand a call without clip and without ema to the plain kernel.
+template <class Rule, bool TAIL>
+__global__ __launch_bounds__(THREADS) void step_kernel(Rule r, float* __restrict__ p, const float* __restrict__ g, size_t n,
+                                                        const float* __restrict__ hyper, float lr, int step, float wd, float gscale,
+                                                        Tail x_) {
+  const Tail x = TAIL ? x_ : Tail{nullptr, nullptr, 0.f, 0, 0};
+  Launch q;
+  if (!begin_launch(x, hyper, lr, step, gscale, q)) return;
+  r.begin(q.lr, q.t);
+  const bool has_s1 = r.has_s1();
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float e = x.ema ? x.ema[i] : 0.f;                          // ahead of the stores: every load of the element is in flight at once
+    float gi = g[i] * q.gs, pi = p[i];
+    decay(gi, pi, false, wd, 1.f);
+    // a state that is not read gets a placeholder, which update() ignores.  For s0 it is gi and not a constant: that keeps the
+    // decay above in the block that feeds this choice, where the compiler packs g * gs with wd * p and adds them unfused, as these
+    // kernels always have (with 0.f here it fuses wd * p into the sum: another last bit whenever wd != 0)
+    float a = r.has_s0() ? r.s0[i] : gi, b = has_s1 ? r.s1[i] : 0.f;
+    const float pn = r.update(gi, pi, a, b);
+    r.s0[i] = a;
+    if (has_s1) r.s1[i] = b;
+    p[i] = pn;
+    if (x.ema) x.ema[i] = q.d * e + q.omd * pn;
+  }
+}
+
+// clip and ema both null: the plain kernel (and `step`, which only the tail reads, goes unchecked)
+template <class Rule>
+int launch_step(const Rule& r, float* p, const float* g, size_t n, const float* hyper, float lr, int step, float wd, float gscale,
+                const Tail& x, void* stream) {
+  const dim3 grid(blocks_for((long long)((n + THREADS - 1) / THREADS)));
+  if (!x.clip && !x.ema) {
+    hipLaunchKernelGGL((step_kernel<Rule, false>), grid, dim3(THREADS), 0, as_stream(stream), r, p, g, n, hyper, lr, step, wd, gscale, x);
+    return launch_status();
+  }
+  if (const int e = check_tail(hyper, step, x.ema, x.ema_decay, false)) return e;
+  hipLaunchKernelGGL((step_kernel<Rule, true>), grid, dim3(THREADS), 0, as_stream(stream), r, p, g, n, hyper, lr, step, wd, gscale, x);
+  return launch_status();
+}
+
+// ---- the flat RMSprop steps -----------------------------------------------------------------------------------------------------
+// Stated separately from step_kernel, on memory: buf is read after sq is stored (and not at all without momentum).  With every load
+// of the element ahead of its stores, as step_kernel has them, the same bits came 4 % slower at ResNet152's size
+// (profiles/optim_refactor_bench.txt).  RmsRule::update is this rule on registers, for the grouped steps.
+__device__ __forceinline__ float rmsprop_flat(float* sq, float* buf, size_t i, float gi, const float pi, float lr, float alpha,
+                                              float eps, float mom, float wd) {
+  if (wd != 0.f) gi += wd * pi;
+  const float si = alpha * sq[i] + (1.f - alpha) * gi * gi;
+  sq[i] = si;
+  const float avg = sqrtf(si) + eps;
+  if (mom > 0.f) {
+    const float bi = mom * buf[i] + gi / avg;
+    buf[i] = bi;
+    return pi - lr * bi;
+  }
+  return pi - lr * gi / avg;
+}
+
+// plain: `hyper` null or not are two kernels, as they always were
+__global__ void rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq, float* __restrict__ buf,
+                               size_t n, float lr, float alpha, float eps, float mom, float wd, float gscale) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    p[i] = rmsprop_flat(sq, buf, i, g[i] * gscale, p[i], lr, alpha, eps, mom, wd);
+}
+__global__ void rmsprop_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq, float* __restrict__ buf,
+                                   size_t n, const float* __restrict__ hyper, float alpha, float eps, float mom, float wd, float gscale) {
+  const float lr = hyper[0];
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    p[i] = rmsprop_flat(sq, buf, i, g[i] * gscale, p[i], lr, alpha, eps, mom, wd);
+}
+// clip, skip and EMA
+__global__ __launch_bounds__(THREADS) void rmsprop_ex_kernel(float* __restrict__ p, const float* __restrict__ g, float* sq, float* buf,
+                                                              size_t n, const float* __restrict__ hyper, float lr, int step, float alpha,
+                                                              float eps, float mom, float wd, float gscale, Tail x) {
+  Launch q;
+  if (!begin_launch(x, hyper, lr, step, gscale, q)) return;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float e = x.ema ? x.ema[i] : 0.f;
+    const float pn = rmsprop_flat(sq, buf, i, g[i] * q.gs, p[i], q.lr, alpha, eps, mom, wd);
+    p[i] = pn;
+    if (x.ema) x.ema[i] = q.d * e + q.omd * pn;
+  }
+}
+
+int launch_rmsprop(float* p, const float* g, float* sq, float* buf, size_t n, const float* hyper, float lr, int step, float alpha,
+                   float eps, float mom, float wd, float gscale, const Tail& x, void* stream) {
+  const dim3 grid(blocks_for((long long)((n + THREADS - 1) / THREADS)));
+  if (x.clip || x.ema) {
+    if (const int e = check_tail(hyper, step, x.ema, x.ema_decay, false)) return e;
+    hipLaunchKernelGGL(rmsprop_ex_kernel, grid, dim3(THREADS), 0, as_stream(stream), p, g, sq, buf, n, hyper, lr, step, alpha, eps, mom,
+                       wd, gscale, x);
+  } else if (hyper) {
+    hipLaunchKernelGGL(rmsprop_dev_kernel, grid, dim3(THREADS), 0, as_stream(stream), p, g, sq, buf, n, hyper, alpha, eps, mom, wd, gscale);
+  } else {
+    hipLaunchKernelGGL(rmsprop_kernel, grid, dim3(THREADS), 0, as_stream(stream), p, g, sq, buf, n, lr, alpha, eps, mom, wd, gscale);
+  }
+  return launch_status();
+}
+
+// ---- the grouped steps ----------------------------------------------------------------------------------------------------------
+// begin() takes what the group row fixes: lr_g = lr * lr_mult and the group's own 1-based step t_g = t - t0.
+template <class Rule>
+__global__ __launch_bounds__(THREADS) void step_items_kernel(Rule r, float* __restrict__ p, const float* __restrict__ g,
+                                                              const Item* __restrict__ items, int n_items,
+                                                              const float* __restrict__ groups, int decoupled,
+                                                              const float* __restrict__ hyper, float lr, int step, float gscale,
+                                                              Tail x) {
+  Launch q;
+  if (!begin_launch(x, hyper, lr, step, gscale, q)) return;
+  f32x4* __restrict__ p4 = reinterpret_cast<f32x4*>(p);
+  const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g);
+  f32x4* s04 = reinterpret_cast<f32x4*>(r.s0);
+  f32x4* s14 = reinterpret_cast<f32x4*>(r.s1);
+  f32x4* e4 = reinterpret_cast<f32x4*>(x.ema);
+  const bool has_s1 = r.has_s1();
+  // slot s = slice s / n_items of item s % n_items (slice-major: with the slice as the fast index a grid of 2048 = 256 * OG_SLOTS
+  // workgroups would give workgroup b the slice b % OG_SLOTS of every item it meets, and the short items have only slice 0 --
+  // measured 4x slower); a slice past the end of a short item is empty
+  for (long long s = blockIdx.x; s < (long long)n_items * OG_SLOTS; s += gridDim.x) {
+    const Item item = items[s % n_items];
+    const uint32_t first = (uint32_t)(s / n_items) * OG_SLOT_VEC4;
+    if (first >= item.len4) continue;
+    const float* __restrict__ row = groups + 4 * (size_t)item.group;
+    const float lr_mult = row[0], wd = row[1], frozen = row[2], t0 = row[3];
+    if (frozen != 0.f) continue;                                     // uniform over the workgroup
+    const float lr_g = q.lr * lr_mult;
+    r.begin(lr_g, q.t - t0);
+    const float keep = 1.f - lr_g * wd;
+    const uint32_t last = first + OG_SLOT_VEC4 < item.len4 ? first + OG_SLOT_VEC4 : item.len4;
+    const size_t lo = (size_t)item.start4 + first, hi = (size_t)item.start4 + last;
+    for (size_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+      // every load of the unit ahead of its stores
+      const f32x4 gv = g4[i];
+      f32x4 pv = p4[i];
+      f32x4 av = s04[i];
+      f32x4 bv = has_s1 ? s14[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 ev = e4 ? e4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float gi = gv[c] * q.gs, pi = pv[c];
+        float a = av[c], b = bv[c];
+        decay(gi, pi, decoupled, wd, keep);
+        const float pn = r.update(gi, pi, a, b);
+        av[c] = a;
+        bv[c] = b;
+        pv[c] = pn;
+        ev[c] = q.d * ev[c] + q.omd * pn;
+      }
+      p4[i] = pv;
+      s04[i] = av;
+      if (has_s1) s14[i] = bv;
+      if (e4) e4[i] = ev;
+    }
+  }
+}
+
+int check_tables(size_t n, const void* items, int n_items, const void* groups, int n_groups) {
+  if (!items || !groups || n_items < 0) return CX_EINVAL;
+  if (n_groups < 1 || n_groups > OG_MAX_GROUPS) return CX_EINVAL;
+  if ((n & 3) != 0) return CX_EINVAL;                       // the flat buffers are whole 16-byte units
+  if (n > 0 && n_items == 0) return CX_EINVAL;
+  if (!aligned16(items) || !aligned16(groups)) return CX_EALIGN;
+  return 0;
+}
+
+template <class Rule>
+int launch_step_items(const Rule& r, float* p, const float* g, size_t n, const uint32_t* items, int n_items, const float* groups,
+                      int n_groups, int decoupled, const float* hyper, float lr, int step, float gscale, const Tail& x, void* stream) {
+  if (!p || !g || !r.s0) return CX_EINVAL;
+  if (const int e = check_tables(n, items, n_items, groups, n_groups)) return e;
+  if (const int e = check_tail(hyper, step, x.ema, x.ema_decay, true)) return e;
+  if (!aligned16(p) || !aligned16(g) || !aligned16(r.s0) || !aligned16(r.s1)) return CX_EALIGN;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(step_items_kernel<Rule>, dim3(blocks_for((long long)n_items * OG_SLOTS)), dim3(THREADS), 0, as_stream(stream), r, p,
+                     g, reinterpret_cast<const Item*>(items), n_items, groups, decoupled ? 1 : 0, hyper, lr, step, gscale, x);
+  return launch_status();
+}
+
+// ---- cx_optim_tick applies the reference's schedulers (chexpert.py:165: stepped once per minibatch from lr_warmup_steps on; :480
+// MultiStepLR, :500 ExponentialLR)
+__global__ void optim_tick_kernel(float* hyper) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float step = hyper[1] + 1.f;
+  hyper[1] = step;
+  const int kind = (int)hyper[2];
+  // chexpert.py:157-165: `args.step += 1` opens the minibatch, `if scheduler and args.step >= args.lr_warmup_steps:
+  // scheduler.step()` closes it -> after minibatch number `step` the scheduler has been stepped k times
+  const float warm = hyper[4];
+  if (step < warm) return;
+  const float k = step - fmaxf(warm, 1.f) + 1.f;
+  if (kind == 1) hyper[0] *= hyper[3];                                                   // ExponentialLR
+  if (kind == 2) hyper[0] = hyper[7] * powf(hyper[3], (k >= hyper[5] ? 1.f : 0.f) + (k >= hyper[6] ? 1.f : 0.f));   // MultiStepLR
+}
+
+}  // namespace
+
+
+extern "C" {
+
+int cx_optim_tick(float* hyper, void* stream) {
+  if (!hyper) return CX_EINVAL;
+  hipLaunchKernelGGL(optim_tick_kernel, dim3(1), dim3(64), 0, as_stream(stream), hyper);
+  return launch_status();
+}
+
+int cx_grad_norm_partials(size_t n) { return gn_blocks(n); }
+
+int cx_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, int skip_nonfinite, float* workspace,
+                 size_t workspace_floats, float* clip, void* stream) {
+  if (!clip || (n && (!g || !workspace))) return CX_EINVAL;
+  const int blocks = gn_blocks(n);
+  if (workspace_floats < (size_t)blocks) return CX_EINVAL;
+  if (n && !aligned16(g)) return CX_EALIGN;
+  if (blocks)
+    hipLaunchKernelGGL(grad_sq_partial_kernel, dim3(blocks), dim3(THREADS), 0, as_stream(stream), g, n, grad_scale, workspace);
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(THREADS), 0, as_stream(stream), workspace, blocks, max_norm, skip_nonfinite,
+                     clip);
+  return launch_status();
+}
+
+int cx_optim_item_vec4(void) { return OG_ITEM_VEC4; }
+
+int cx_grad_norm_items(const float* g, size_t n, const uint32_t* items, int n_items, const float* groups, int n_groups,
+                       float grad_scale, float max_norm, int skip_nonfinite, float* partials, float* group_sq, float* group_norm,
+                       float* clip, void* stream) {
+  if (!clip || !group_sq || !group_norm || (n && (!g || !partials))) return CX_EINVAL;
+  if (const int e = check_tables(n, items, n_items, groups, n_groups)) return e;
+  if (n && !aligned16(g)) return CX_EALIGN;
+  const Item* tab = reinterpret_cast<const Item*>(items);
+  if (n == 0) n_items = 0;
+  if (n_items)
+    hipLaunchKernelGGL(item_sq_partial_kernel, dim3(blocks_for(n_items)), dim3(THREADS), 0, as_stream(stream), g, tab, n_items, grad_scale,
+                       partials);
+  hipLaunchKernelGGL(group_norm_final_kernel, dim3(1), dim3(THREADS), 0, as_stream(stream), partials, tab, n_items, groups, n_groups,
+                     max_norm, skip_nonfinite, group_sq, group_norm, clip);
+  return launch_status();
+}
+
+// ---- Adam.  The host-lr form takes its bias corrections from the host's powf.
+int cx_adam_step_ex(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, int step, float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup,
+                    int skip_nonfinite, void* stream) {
+  if (!p || !g || !m || !v || step < 1) return CX_EINVAL;
+  const float bc1 = 1.f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  const AdamRule r = {m, v, beta1, beta2, eps, bc1, bc2s, true, 0.f};
+  return launch_step(r, p, g, n, nullptr, lr, step, weight_decay, grad_scale, {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+int cx_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                 float weight_decay, int step, float grad_scale, void* stream) {
+  return cx_adam_step_ex(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, nullptr, 0.f, 0, 0, stream);
+}
+
+int cx_adam_step_dev_ex(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float beta1, float beta2,
+                        float eps, float weight_decay, float grad_scale, const float* clip, float* ema, float ema_decay,
+                        int ema_warmup, int skip_nonfinite, void* stream) {
+  if (!p || !g || !m || !v || !hyper) return CX_EINVAL;
+  const AdamRule r = {m, v, beta1, beta2, eps, 1.f, 1.f, false, 0.f};
+  return launch_step(r, p, g, n, hyper, 0.f, 0, weight_decay, grad_scale, {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+int cx_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float beta1, float beta2, float eps,
+                     float weight_decay, float grad_scale, void* stream) {
+  return cx_adam_step_dev_ex(p, g, m, v, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr, nullptr, 0.f, 0, 0, stream);
+}
+
+int cx_adam_step_items(float* p, const float* g, float* m, float* v, size_t n, const uint32_t* items, int n_items, const float* groups,
+                       int n_groups, int decoupled, const float* hyper, float lr, int step, float beta1, float beta2, float eps,
+                       float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup, int skip_nonfinite,
+                       void* stream) {
+  if (!v) return CX_EINVAL;
+  const AdamRule r = {m, v, beta1, beta2, eps, 1.f, 1.f, false, 0.f};
+  return launch_step_items(r, p, g, n, items, n_items, groups, n_groups, decoupled, hyper, lr, step, grad_scale,
+                           {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+// ---- SGD with Nesterov momentum
+int cx_sgd_nesterov_step_ex(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay,
+                            int first_step, int step, float grad_scale, const float* clip, float* ema, float ema_decay,
+                            int ema_warmup, int skip_nonfinite, void* stream) {
+  if (!p || !g || !buf) return CX_EINVAL;
+  const SgdRule r = {buf, nullptr, momentum, first_step ? 1 : 0, 0.f};
+  return launch_step(r, p, g, n, nullptr, lr, step, weight_decay, grad_scale, {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+int cx_sgd_nesterov_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay,
+                         int first_step, float grad_scale, void* stream) {
+  return cx_sgd_nesterov_step_ex(p, g, buf, n, lr, momentum, weight_decay, first_step, 0, grad_scale, nullptr, nullptr, 0.f, 0, 0, stream);
+}
+
+int cx_sgd_nesterov_step_dev_ex(float* p, const float* g, float* buf, size_t n, const float* hyper, float momentum,
+                                float weight_decay, float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup,
+                                int skip_nonfinite, void* stream) {
+  if (!p || !g || !buf || !hyper) return CX_EINVAL;
+  const SgdRule r = {buf, nullptr, momentum, -1, 0.f};
+  return launch_step(r, p, g, n, hyper, 0.f, 0, weight_decay, grad_scale, {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+int cx_sgd_nesterov_step_dev(float* p, const float* g, float* buf, size_t n, const float* hyper, float momentum, float weight_decay,
+                             float grad_scale, void* stream) {
+  return cx_sgd_nesterov_step_dev_ex(p, g, buf, n, hyper, momentum, weight_decay, grad_scale, nullptr, nullptr, 0.f, 0, 0, stream);
+}
+
+int cx_sgd_nesterov_step_items(float* p, const float* g, float* buf, size_t n, const uint32_t* items, int n_items, const float* groups,
+                               int n_groups, int decoupled, const float* hyper, float lr, int step, float momentum, float grad_scale,
+                               const float* clip, float* ema, float ema_decay, int ema_warmup, int skip_nonfinite, void* stream) {
+  const SgdRule r = {buf, nullptr, momentum, 0, 0.f};
+  return launch_step_items(r, p, g, n, items, n_items, groups, n_groups, decoupled, hyper, lr, step, grad_scale,
+                           {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+// ---- RMSprop.  momentum == 0: buf is never touched and may be null.
+int cx_rmsprop_step_ex(float* p, const float* g, float* sq, float* buf, size_t n, float lr, float alpha, float eps, float momentum,
+                       float weight_decay, int step, float grad_scale, const float* clip, float* ema, float ema_decay,
+                       int ema_warmup, int skip_nonfinite, void* stream) {
+  if (!p || !g || !sq || (momentum > 0.f && !buf)) return CX_EINVAL;
+  return launch_rmsprop(p, g, sq, buf, n, nullptr, lr, step, alpha, eps, momentum, weight_decay, grad_scale,
+                        {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+int cx_rmsprop_step(float* p, const float* g, float* sq, float* buf, size_t n, float lr, float alpha, float eps, float momentum,
+                    float weight_decay, float grad_scale, void* stream) {
+  return cx_rmsprop_step_ex(p, g, sq, buf, n, lr, alpha, eps, momentum, weight_decay, 0, grad_scale, nullptr, nullptr, 0.f, 0, 0, stream);
+}
+
+int cx_rmsprop_step_dev_ex(float* p, const float* g, float* sq, float* buf, size_t n, const float* hyper, float alpha, float eps,
+                           float momentum, float weight_decay, float grad_scale, const float* clip, float* ema, float ema_decay,
+                           int ema_warmup, int skip_nonfinite, void* stream) {
+  if (!p || !g || !sq || !hyper || (momentum > 0.f && !buf)) return CX_EINVAL;
+  return launch_rmsprop(p, g, sq, buf, n, hyper, 0.f, 0, alpha, eps, momentum, weight_decay, grad_scale,
+                        {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+int cx_rmsprop_step_dev(float* p, const float* g, float* sq, float* buf, size_t n, const float* hyper, float alpha, float eps,
+                        float momentum, float weight_decay, float grad_scale, void* stream) {
+  return cx_rmsprop_step_dev_ex(p, g, sq, buf, n, hyper, alpha, eps, momentum, weight_decay, grad_scale, nullptr, nullptr, 0.f, 0, 0, stream);
+}
+
+int cx_rmsprop_step_items(float* p, const float* g, float* sq, float* buf, size_t n, const uint32_t* items, int n_items,
+                          const float* groups, int n_groups, int decoupled, const float* hyper, float lr, int step, float alpha, float eps,
+                          float momentum, float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup,
+                          int skip_nonfinite, void* stream) {
+  if (momentum > 0.f && !buf) return CX_EINVAL;
+  const RmsRule r = {sq, buf, alpha, eps, momentum, 0.f};
+  return launch_step_items(r, p, g, n, items, n_items, groups, n_groups, decoupled, hyper, lr, step, grad_scale,
+                           {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+}  // extern "C"

@@ -802,7 +802,7 @@ def optim_tick(hyper):
     check(lib().cx_optim_tick(ptr(hyper), stream_ptr()), "cx_optim_tick")
 
 
-# ---- global-norm clipping, non-finite skip and weight EMA inside the optimiser launch (csrc/optim_ex.hip)
+# ---- global-norm clipping, non-finite skip and weight EMA inside the optimiser launch (csrc/optim.hip)
 def grad_norm_partials(n):
     """Floats of workspace `grad_norm` needs for n gradients (the grid of its first launch: a function of n alone)."""
     return lib().cx_grad_norm_partials(n)
@@ -818,57 +818,57 @@ def grad_norm(g, workspace, clip, grad_scale=1.0, max_norm=0.0, skip_nonfinite=F
                              ptr(clip), stream_ptr()), "cx_grad_norm")
 
 
-def _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, *bufs):
-    n = p.numel()
-    require_cuda(p, clip, ema, *bufs)
-    _f32(p, ema, *bufs, n=n)
+def _optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite, *bufs, n=0):
+    """Checks `bufs` (n floats each) and clip; the trailing arguments every `_ex` and `_items` entry point takes."""
+    require_cuda(clip, ema, *bufs)
+    _f32(ema, *bufs, n=n)
     _f32(clip, n=4)
     return ptr(clip), ptr(ema), (0.0 if ema is None else float(ema_decay)), int(bool(ema_warmup)), int(bool(skip_nonfinite)), stream_ptr()
 
 
 def adam_step_ex(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
                  ema_warmup=True, skip_nonfinite=False):
-    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, m, v)
+    tail = _optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite, p, g, m, v, n=p.numel())
     check(lib().cx_adam_step_ex(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                                 *tail), "cx_adam_step_ex")
 
 
 def sgd_nesterov_step_ex(p, g, buf, lr, momentum, weight_decay, first_step, step, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
                          ema_warmup=True, skip_nonfinite=False):
-    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, buf)
+    tail = _optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite, p, g, buf, n=p.numel())
     check(lib().cx_sgd_nesterov_step_ex(ptr(p), ptr(g), ptr(buf), p.numel(), lr, momentum, weight_decay, int(first_step), step,
                                         grad_scale, *tail), "cx_sgd_nesterov_step_ex")
 
 
 def rmsprop_step_ex(p, g, sq, buf, lr, alpha, eps, momentum, weight_decay, step, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
                     ema_warmup=True, skip_nonfinite=False):
-    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, sq, buf)
+    tail = _optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite, p, g, sq, buf, n=p.numel())
     check(lib().cx_rmsprop_step_ex(ptr(p), ptr(g), ptr(sq), ptr(buf), p.numel(), lr, alpha, eps, momentum, weight_decay, step,
                                    grad_scale, *tail), "cx_rmsprop_step_ex")
 
 
 def adam_step_dev_ex(p, g, m, v, hyper, beta1, beta2, eps, weight_decay, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
                      ema_warmup=True, skip_nonfinite=False):
-    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, m, v)
+    tail = _optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite, p, g, m, v, n=p.numel())
     check(lib().cx_adam_step_dev_ex(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(hyper), beta1, beta2, eps, weight_decay,
                                     grad_scale, *tail), "cx_adam_step_dev_ex")
 
 
 def sgd_nesterov_step_dev_ex(p, g, buf, hyper, momentum, weight_decay, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
                              ema_warmup=True, skip_nonfinite=False):
-    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, buf)
+    tail = _optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite, p, g, buf, n=p.numel())
     check(lib().cx_sgd_nesterov_step_dev_ex(ptr(p), ptr(g), ptr(buf), p.numel(), ptr(hyper), momentum, weight_decay, grad_scale,
                                             *tail), "cx_sgd_nesterov_step_dev_ex")
 
 
 def rmsprop_step_dev_ex(p, g, sq, buf, hyper, alpha, eps, momentum, weight_decay, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0,
                         ema_warmup=True, skip_nonfinite=False):
-    tail = _ex_tail(p, clip, ema, ema_decay, ema_warmup, skip_nonfinite, g, sq, buf)
+    tail = _optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite, p, g, sq, buf, n=p.numel())
     check(lib().cx_rmsprop_step_dev_ex(ptr(p), ptr(g), ptr(sq), ptr(buf), p.numel(), ptr(hyper), alpha, eps, momentum, weight_decay,
                                        grad_scale, *tail), "cx_rmsprop_step_dev_ex")
 
 
-# ---- parameter groups: per-tensor item table and per-group rows walked by the optimiser kernels (csrc/optim_groups.hip)
+# ---- parameter groups: per-tensor item table and per-group rows walked by the optimiser kernels (csrc/optim.hip)
 def optim_item_vec4():
     """Longest work item of the grouped optimiser kernels, in 16-byte units (a constant of the library)."""
     return lib().cx_optim_item_vec4()
@@ -898,18 +898,12 @@ def grad_norm_items(g, items, groups, partials, group_sq, group_norm, clip, grad
                                    ptr(group_sq), ptr(group_norm), ptr(clip), stream_ptr()), "cx_grad_norm_items")
 
 
-def _items_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite):
-    require_cuda(clip)
-    _f32(clip, n=4)
-    return ptr(clip), ptr(ema), (0.0 if ema is None else float(ema_decay)), int(bool(ema_warmup)), int(bool(skip_nonfinite)), stream_ptr()
-
-
 def adam_step_items(p, g, m, v, items, groups, decoupled, beta1, beta2, eps, hyper=None, lr=0.0, step=0, grad_scale=1.0, clip=None,
                     ema=None, ema_decay=0.0, ema_warmup=True, skip_nonfinite=False):
     """Adam over the item table.  hyper (device float[8]) given: lr and the step come from it; else `lr` and the 1-based `step`."""
     n, pi, ni, pg, ng = _group_tables(p, items, groups, g, m, v, ema)
     check(lib().cx_adam_step_items(ptr(p), ptr(g), ptr(m), ptr(v), n, pi, ni, pg, ng, int(bool(decoupled)), ptr(hyper), lr, int(step),
-                                   beta1, beta2, eps, grad_scale, *_items_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)),
+                                   beta1, beta2, eps, grad_scale, *_optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)),
           "cx_adam_step_items")
 
 
@@ -918,7 +912,7 @@ def sgd_nesterov_step_items(p, g, buf, items, groups, decoupled, momentum, hyper
     """SGD with Nesterov momentum over the item table (`buf` starts as zeros: there is no first-step switch)."""
     n, pi, ni, pg, ng = _group_tables(p, items, groups, g, buf, ema)
     check(lib().cx_sgd_nesterov_step_items(ptr(p), ptr(g), ptr(buf), n, pi, ni, pg, ng, int(bool(decoupled)), ptr(hyper), lr, int(step),
-                                           momentum, grad_scale, *_items_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)),
+                                           momentum, grad_scale, *_optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)),
           "cx_sgd_nesterov_step_items")
 
 
@@ -928,7 +922,7 @@ def rmsprop_step_items(p, g, sq, buf, items, groups, decoupled, alpha, eps, mome
     n, pi, ni, pg, ng = _group_tables(p, items, groups, g, sq, buf, ema)
     check(lib().cx_rmsprop_step_items(ptr(p), ptr(g), ptr(sq), ptr(buf), n, pi, ni, pg, ng, int(bool(decoupled)), ptr(hyper), lr,
                                       int(step), alpha, eps, momentum, grad_scale,
-                                      *_items_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)), "cx_rmsprop_step_items")
+                                      *_optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)), "cx_rmsprop_step_items")
 
 
 def bf16_to_f32_nchw(x, out=None):

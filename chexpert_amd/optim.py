@@ -16,7 +16,7 @@ MAX_GROUPS = 256
 
 
 def item_table(numels, group_of, vec4=None):
-    """The work items of the grouped kernels (csrc/optim_groups.hip) for tensors of `numels` floats laid out as `_fused.flatten`
+    """The work items of the grouped kernels (csrc/optim.hip) for tensors of `numels` floats laid out as `_fused.flatten`
     lays them out (each at a multiple of 4 floats, zero-padded to one), tensor k in group group_of[k]: a list of
     (start4, len4, group, tensor) in 16-byte units.  Every tensor, padding included, is cut into consecutive items of at most
     `vec4` units (default: the library's constant); items come in buffer order and none crosses a tensor.  A function of the
@@ -119,15 +119,20 @@ class _Flat:
     the group rows {lr_mult, weight_decay, frozen, t0} in device memory (`set_group` rewrites a row, between graph replays too)."""
     NSTATE = 0
     KIND = None
+    SCHED = (0, 1.0, (0, 0))        # (kind, gamma, milestones): 0 none, 1 ExponentialLR, 2 MultiStepLR
+    # what the host-lr entry point of each family takes beside the rule's own arguments, by the family's suffix
+    HOST_ARGS = {"": ("lr",), "_ex": ("lr", "step"), "_items": ("lr", "step")}
 
     def __init__(self, model, lr, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True, weight_decay=0.0,
                  decoupled=False, groups=None):
         self.model = model
         self.lr = float(lr)
         self.base_lr = float(lr)
+        self.wd = float(weight_decay)                       # the ungrouped steps' decay; with groups: group 0's row
         self.step_count = 0
         self.sched_steps = 0
-        self._state = None
+        self._state = self._pending_state = self._hyper = None
+        self._sched = self.SCHED
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be > 0 (got %r)" % (max_grad_norm,))
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
@@ -142,7 +147,7 @@ class _Flat:
         self._grouped = groups is not None or self.decoupled
         self._items = self._gtab = self._gpart = self._gsq = self._gnorm = None
         if self._grouped:
-            self._init_groups(groups or [], float(weight_decay))
+            self._init_groups(groups or [], self.wd)
 
     # ---- parameter groups
     def _init_groups(self, groups, weight_decay):
@@ -231,19 +236,41 @@ class _Flat:
         self._clip_host()
         return [0.0] * len(self._grows) if self._gnorm is None else [float(v) for v in self._gnorm.cpu()]
 
-    def _step_items(self, grad_scale, dev, **rule):
-        """One grouped step: the segmented norm when clipping or skipping is on, then the rule over the item table."""
+    # ---- the step
+    def _step(self, grad_scale, dev):
+        """One step through the family the options select: grouped -> `_items`, clip / skip / EMA on -> `_ex`, else the plain entry
+        point; `dev`: the learning rate and the step count are the device's (`hyper()`), else the host's.  The norm goes first when
+        clipping or skipping is on."""
         p, g, st = self._bufs(self.NSTATE)
-        if self._norm_on():
-            ops.grad_norm_items(g, self._items, self._gtab, self._gpart, self._gsq, self._gnorm, self._clip, grad_scale,
-                                self.max_grad_norm or 0.0, self.skip_nonfinite)
-        where = {"hyper": self.hyper()} if dev else {"lr": self.lr, "step": self.step_count + 1}
-        getattr(ops, self.KIND + "_step_items")(p, g, *st, self._items, self._gtab, self.decoupled, grad_scale=grad_scale,
-                                                clip=self._clip if self._norm_on() else None, ema=self._ema,
-                                                ema_decay=self.ema_decay or 0.0, ema_warmup=self.ema_warmup,
-                                                skip_nonfinite=self.skip_nonfinite, **where, **rule)
-        if not dev:
+        family = "_items" if self._grouped else "_ex" if self._ex_on() else ""
+        args = {"grad_scale": grad_scale}
+        if self._grouped:
+            args.update(items=self._items, groups=self._gtab, decoupled=self.decoupled)
+        else:
+            args.update(weight_decay=self.wd)
+        if family:
+            if self._grouped and self._norm_on():
+                ops.grad_norm_items(g, self._items, self._gtab, self._gpart, self._gsq, self._gnorm, self._clip, grad_scale,
+                                    self.max_grad_norm or 0.0, self.skip_nonfinite)
+            elif self._norm_on():
+                ops.grad_norm(g, self._ws, self._clip, grad_scale, self.max_grad_norm or 0.0, self.skip_nonfinite)
+            args.update(clip=self._clip if self._norm_on() else None, ema=self._ema, ema_decay=self.ema_decay or 0.0,
+                        ema_warmup=self.ema_warmup, skip_nonfinite=self.skip_nonfinite)
+        if dev:
+            args.update(hyper=self.hyper())
+        else:
+            host = {"lr": self.lr, "first_step": self.step_count == 0, "step": self.step_count + 1}
+            args.update({k: host[k] for k in self.HOST_ARGS[family]})
+        name = self.KIND + ("_step_dev" if dev and not self._grouped else "_step") + family
+        getattr(ops, name)(p, g, *st, **self._rule(), **args)
+        if not dev:                                         # (the device's count is cx_optim_tick's: `tick()`)
             self.step_count += 1
+
+    def step(self, grad_scale=1.0):
+        self._step(grad_scale, False)
+
+    def step_dev(self, grad_scale=1.0):
+        self._step(grad_scale, True)
 
     def _norm_on(self):
         return self.max_grad_norm is not None or self.skip_nonfinite
@@ -257,11 +284,10 @@ class _Flat:
             raise RuntimeError("run a forward pass first (parameters are bound to the flat buffer lazily)")
         if self._state is None or self._state[0].numel() != eng.flat.numel() or self._state[0].device != eng.flat.device:
             self._state = [torch.zeros_like(eng.flat) for _ in range(n)]
-            pend = getattr(self, "_pending_state", None)
+            pend, self._pending_state = self._pending_state, None
             if pend is not None:
                 for dst, src in zip(self._state, pend):
                     dst.copy_(src)
-                self._pending_state = None
         if self._ex_on() and (self._clip is None or self._clip.device != eng.flat.device
                               or (self._ema is not None and self._ema.numel() != eng.flat.numel())):
             # beside the states, so that nothing is allocated while a graph is being captured
@@ -277,13 +303,6 @@ class _Flat:
         if self._grouped:
             self._group_bufs(eng)
         return eng.flat, eng.flat_grad, self._state
-
-    def _ex_args(self, g, grad_scale):
-        """Launches the norm when clipping or skipping is on; keyword arguments of the `_ex` update that follows."""
-        if self._norm_on():
-            ops.grad_norm(g, self._ws, self._clip, grad_scale, self.max_grad_norm or 0.0, self.skip_nonfinite)
-        return {"clip": self._clip if self._norm_on() else None, "ema": self._ema, "ema_decay": self.ema_decay or 0.0,
-                "ema_warmup": self.ema_warmup, "skip_nonfinite": self.skip_nonfinite}
 
     def _clip_host(self):
         if not self._norm_on():
@@ -327,14 +346,12 @@ class _Flat:
         self.model.zero_grad(set_to_none=set_to_none)
 
     # ---- device-resident hyper-parameters (graph replay: chexpert_amd/graph.py)
-    SCHED = (0, 1.0, (0, 0))        # (kind, gamma, milestones): 0 none, 1 ExponentialLR, 2 MultiStepLR
-
     def hyper(self, warmup_steps=0):
         """float[8] on the device: {lr, steps_done, sched_kind, gamma, lr_warmup_steps, milestone0, milestone1, base_lr}
         (include/chexpert_hip.h, cx_optim_tick).  Created from the host-side state on first use; from then on the device
         copy is the truth for `step_dev()` / `tick()` and `sync_from_device()` reads it back."""
-        if getattr(self, "_hyper", None) is None:
-            kind, gamma, ms = self.SCHED if not hasattr(self, "_sched") else self._sched
+        if self._hyper is None:
+            kind, gamma, ms = self._sched
             eng = self.model._eng()
             self._hyper = torch.tensor([self.lr, float(self.step_count), float(kind), float(gamma), float(warmup_steps),
                                         float(ms[0]), float(ms[1]), self.base_lr], dtype=torch.float32, device=eng.flat.device)
@@ -398,7 +415,7 @@ class _Flat:
             self._gtab.copy_(torch.tensor(self._grows, dtype=torch.float32))
 
     def sync_from_device(self):
-        if getattr(self, "_hyper", None) is not None:
+        if self._hyper is not None:
             h = self._hyper.cpu()
             self.lr, self.step_count = float(h[0]), int(h[1])
             # cx_optim_tick steps the scheduler inside the graph: after minibatch number `step` it has been stepped
@@ -410,66 +427,31 @@ class _Flat:
 class FusedAdam(_Flat):
     NSTATE = 2
     KIND = "adam"
+    HOST_ARGS = dict(_Flat.HOST_ARGS, **{"": ("lr", "step")})              # the host's powf makes the bias corrections
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, groups=None, **options):
         super().__init__(model, lr, weight_decay=weight_decay, decoupled=decoupled, groups=groups, **options)
-        self.betas, self.eps, self.wd = betas, eps, weight_decay
+        self.betas, self.eps = betas, eps
 
     def _rule(self):
         return {"beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps}
-
-    def step(self, grad_scale=1.0):
-        if self._grouped:
-            return self._step_items(grad_scale, False, **self._rule())
-        p, g, (m, v) = self._bufs(2)
-        self.step_count += 1
-        if self._ex_on():
-            ops.adam_step_ex(p, g, m, v, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, grad_scale,
-                             **self._ex_args(g, grad_scale))
-            return
-        ops.adam_step(p, g, m, v, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, grad_scale)
-
-    def step_dev(self, grad_scale=1.0):
-        if self._grouped:
-            return self._step_items(grad_scale, True, **self._rule())
-        p, g, (m, v) = self._bufs(2)
-        if self._ex_on():
-            ops.adam_step_dev_ex(p, g, m, v, self.hyper(), self.betas[0], self.betas[1], self.eps, self.wd, grad_scale,
-                                 **self._ex_args(g, grad_scale))
-            return
-        ops.adam_step_dev(p, g, m, v, self.hyper(), self.betas[0], self.betas[1], self.eps, self.wd, grad_scale)
 
 
 class FusedSGDNesterov(_Flat):
     NSTATE = 1
     KIND = "sgd_nesterov"
+    # on its first step the momentum buffer becomes the gradient (the grouped kernels start from a zeroed buffer instead)
+    HOST_ARGS = dict(_Flat.HOST_ARGS, **{"": ("lr", "first_step"), "_ex": ("lr", "first_step", "step")})
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=0.0, milestones=(40000, 60000), gamma=0.1, decoupled=False, groups=None,
                  **options):
         super().__init__(model, lr, weight_decay=weight_decay, decoupled=decoupled, groups=groups, **options)
-        self.momentum, self.wd, self.milestones, self.gamma = momentum, weight_decay, tuple(milestones), gamma
+        self.momentum, self.milestones, self.gamma = momentum, tuple(milestones), gamma
         ms = (tuple(milestones) + (1 << 30, 1 << 30))[:2]
         self._sched = (2, gamma, ms)
 
-    def step_dev(self, grad_scale=1.0):
-        if self._grouped:
-            return self._step_items(grad_scale, True, momentum=self.momentum)
-        p, g, (buf,) = self._bufs(1)
-        if self._ex_on():
-            ops.sgd_nesterov_step_dev_ex(p, g, buf, self.hyper(), self.momentum, self.wd, grad_scale, **self._ex_args(g, grad_scale))
-            return
-        ops.sgd_nesterov_step_dev(p, g, buf, self.hyper(), self.momentum, self.wd, grad_scale)
-
-    def step(self, grad_scale=1.0):
-        if self._grouped:
-            return self._step_items(grad_scale, False, momentum=self.momentum)
-        p, g, (buf,) = self._bufs(1)
-        if self._ex_on():
-            ops.sgd_nesterov_step_ex(p, g, buf, self.lr, self.momentum, self.wd, self.step_count == 0, self.step_count + 1, grad_scale,
-                                     **self._ex_args(g, grad_scale))
-        else:
-            ops.sgd_nesterov_step(p, g, buf, self.lr, self.momentum, self.wd, self.step_count == 0, grad_scale)
-        self.step_count += 1
+    def _rule(self):
+        return {"momentum": self.momentum}
 
     def scheduler_step(self):
         self.sched_steps += 1
@@ -483,32 +465,11 @@ class FusedRMSprop(_Flat):
     def __init__(self, model, lr, alpha=0.99, eps=1e-3, momentum=0.9, weight_decay=0.0, decay=0.97, decoupled=False, groups=None,
                  **options):
         super().__init__(model, lr, weight_decay=weight_decay, decoupled=decoupled, groups=groups, **options)
-        self.alpha, self.eps, self.momentum, self.wd, self.decay = alpha, eps, momentum, weight_decay, decay
+        self.alpha, self.eps, self.momentum, self.decay = alpha, eps, momentum, decay
         self._sched = (1, decay, (0, 0))
 
     def _rule(self):
         return {"alpha": self.alpha, "eps": self.eps, "momentum": self.momentum}
-
-    def step_dev(self, grad_scale=1.0):
-        if self._grouped:
-            return self._step_items(grad_scale, True, **self._rule())
-        p, g, (sq, buf) = self._bufs(2)
-        if self._ex_on():
-            ops.rmsprop_step_dev_ex(p, g, sq, buf, self.hyper(), self.alpha, self.eps, self.momentum, self.wd, grad_scale,
-                                    **self._ex_args(g, grad_scale))
-            return
-        ops.rmsprop_step_dev(p, g, sq, buf, self.hyper(), self.alpha, self.eps, self.momentum, self.wd, grad_scale)
-
-    def step(self, grad_scale=1.0):
-        if self._grouped:
-            return self._step_items(grad_scale, False, **self._rule())
-        p, g, (sq, buf) = self._bufs(2)
-        if self._ex_on():
-            ops.rmsprop_step_ex(p, g, sq, buf, self.lr, self.alpha, self.eps, self.momentum, self.wd, self.step_count + 1, grad_scale,
-                                **self._ex_args(g, grad_scale))
-        else:
-            ops.rmsprop_step(p, g, sq, buf, self.lr, self.alpha, self.eps, self.momentum, self.wd, grad_scale)
-        self.step_count += 1
 
     def scheduler_step(self):
         self.sched_steps += 1

@@ -491,7 +491,7 @@ int cx_rmsprop_step_dev(float* p, const float* g, float* sq, float* buf, size_t 
                         float momentum, float weight_decay, float grad_scale, void* stream);
 int cx_optim_tick(float* hyper, void* stream);
 
-/* Global-norm gradient clipping, non-finite skip and weight EMA inside the optimiser launch (optim_ex.hip).
+/* Global-norm gradient clipping, non-finite skip and weight EMA inside the optimiser launch (optim.hip).
  * cx_grad_norm: two launches, no atomics.  Launch 1: cx_grad_norm_partials(n) workgroups (a function of n alone), each sums
  * (grad_scale * g)^2 over a fixed contiguous range (16-byte loads, n % 4 scalar tail) and plain-stores one partial to `workspace`
  * (>= cx_grad_norm_partials(n) floats).  Launch 2: one workgroup sums the partials in a fixed order and writes
@@ -525,7 +525,7 @@ int cx_rmsprop_step_dev_ex(float* p, const float* g, float* sq, float* buf, size
                            float momentum, float weight_decay, float grad_scale, const float* clip, float* ema, float ema_decay,
                            int ema_warmup, int skip_nonfinite, void* stream);
 
-/* Parameter groups for the fused optimisers (optim_groups.hip): per-group learning-rate multiplier, weight decay (L2 or decoupled),
+/* Parameter groups for the fused optimisers (optim.hip): per-group learning-rate multiplier, weight decay (L2 or decoupled),
  * frozen groups and a per-group step count.  The flat buffers hold every parameter tensor at a multiple of 4 floats, zero-padded
  * to a multiple of 4 (n % 4 == 0), and are walked through two tables in device memory:
  *   items  = uint32[n_items][4] {start4, len4, group, tensor}: a run of len4 16-byte units from unit start4, all of one tensor,

@@ -1,4 +1,4 @@
-"""Micro-benchmark of the grouped optimiser launches (csrc/optim_groups.hip) on the flat fp32 buffers of DenseNet121 and ResNet152 with
+"""Micro-benchmark of the grouped optimiser launches (csrc/optim.hip) on the flat fp32 buffers of DenseNet121 and ResNet152 with
 their real tensor lists: cx_grad_norm_items and cx_*_step_items (device form, clip + EMA on) for 1, 3 and 64 groups and a sweep of
 the item length, next to the ungrouped cx_*_step_dev, cx_*_step_dev_ex and cx_grad_norm at the same n, measured in the same run
 (before and after the grouped launches).  Every launch is timed by its own pair of events; median and 10th / 90th percentile of

@@ -1,4 +1,4 @@
-"""GPU: global-norm gradient clipping, non-finite skip and weight EMA inside the optimiser launch (csrc/optim_ex.hip:
+"""GPU: global-norm gradient clipping, non-finite skip and weight EMA inside the optimiser launch (csrc/optim.hip:
 cx_grad_norm, cx_*_step_ex, cx_*_step_dev_ex) and their wiring in chexpert_amd.optim, against torch.optim +
 torch.nn.utils.clip_grad_norm_ on the CPU and float64 restatements."""
 import math
@@ -133,14 +133,17 @@ def plain_hyper(dev, lr=1e-2):
     return torch.tensor([lr, 0, 0, 1.0, 0, 0, 0, lr], dtype=torch.float32, device=dev)
 
 
-@pytest.mark.parametrize("form", ["host", "dev"])
-@pytest.mark.parametrize("kind", KINDS)
-def test_clipping_matches_clip_grad_norm(dev, kind, form):
+# Each of the three checks below runs at n = 10007 (the test of its name) and, as `_small_n`, at n = 3: less than one 16-byte unit
+# and less than a wave (the scalar tail of the norm carries the whole sum), and n = 257: one element past a workgroup (a second
+# workgroup with a single live lane).  Same bounds.
+SMALL_N = [3, 257]
+
+
+def check_clipping_matches_clip_grad_norm(dev, kind, form, n):
     """Three steps, gradients one vector scaled by 1, 10 and 0.5, max_norm = 2 x the norm of the first: unclipped, clipped, unclipped.
     CPU: clip_grad_norm_(max_norm) then torch.optim's step (oracle.step.make_optimizer)."""
     from chexpert_amd import ops
     from oracle import step as ostep
-    n = 10007
     p0, g0 = rnd(620, (n,)), rnd(621, (n,))
     max_norm = 2.0 * g0.double().norm().item()
     pc = p0.clone().requires_grad_(True)
@@ -171,9 +174,19 @@ def test_clipping_matches_clip_grad_norm(dev, kind, form):
 
 @pytest.mark.parametrize("form", ["host", "dev"])
 @pytest.mark.parametrize("kind", KINDS)
-def test_ex_step_without_options_gives_the_plain_bits(dev, kind, form):
+def test_clipping_matches_clip_grad_norm(dev, kind, form):
+    check_clipping_matches_clip_grad_norm(dev, kind, form, 10007)
+
+
+@pytest.mark.parametrize("n", SMALL_N)
+@pytest.mark.parametrize("form", ["host", "dev"])
+@pytest.mark.parametrize("kind", KINDS)
+def test_clipping_matches_clip_grad_norm_small_n(dev, kind, form, n):
+    check_clipping_matches_clip_grad_norm(dev, kind, form, n)
+
+
+def check_ex_step_without_options_gives_the_plain_bits(dev, kind, form, n):
     from chexpert_amd import ops
-    n = 10007
     p0 = rnd(630, (n,)).to(dev)
     pa, pb = p0.clone(), p0.clone()
     sa = [torch.zeros(n, device=dev) for _ in range(2)]
@@ -189,12 +202,22 @@ def test_ex_step_without_options_gives_the_plain_bits(dev, kind, form):
 
 
 @pytest.mark.parametrize("form", ["host", "dev"])
-@pytest.mark.parametrize("warmup", [True, False])
 @pytest.mark.parametrize("kind", KINDS)
-def test_ema_follows_the_parameters(dev, kind, warmup, form):
+def test_ex_step_without_options_gives_the_plain_bits(dev, kind, form):
+    check_ex_step_without_options_gives_the_plain_bits(dev, kind, form, 10007)
+
+
+@pytest.mark.parametrize("n", SMALL_N)
+@pytest.mark.parametrize("form", ["host", "dev"])
+@pytest.mark.parametrize("kind", KINDS)
+def test_ex_step_without_options_gives_the_plain_bits_small_n(dev, kind, form, n):
+    check_ex_step_without_options_gives_the_plain_bits(dev, kind, form, n)
+
+
+def check_ema_follows_the_parameters(dev, kind, warmup, form, n):
     """ema = d * ema + (1 - d) * p_new with the p the device produced at each step, restated in float64."""
     from chexpert_amd import ops
-    n, d0 = 10007, 0.9
+    d0 = 0.9
     p = rnd(640, (n,)).to(dev)
     ema = p.clone()
     want = p.cpu().double()
@@ -208,6 +231,21 @@ def test_ema_follows_the_parameters(dev, kind, warmup, form):
         want = d * want + (1.0 - d) * p.cpu().double()
     close(ema.cpu(), want, rel=1e-6, what="%s ema" % kind)
     assert not torch.equal(ema, p)
+
+
+@pytest.mark.parametrize("form", ["host", "dev"])
+@pytest.mark.parametrize("warmup", [True, False])
+@pytest.mark.parametrize("kind", KINDS)
+def test_ema_follows_the_parameters(dev, kind, warmup, form):
+    check_ema_follows_the_parameters(dev, kind, warmup, form, 10007)
+
+
+@pytest.mark.parametrize("n", SMALL_N)
+@pytest.mark.parametrize("form", ["host", "dev"])
+@pytest.mark.parametrize("warmup", [True, False])
+@pytest.mark.parametrize("kind", KINDS)
+def test_ema_follows_the_parameters_small_n(dev, kind, warmup, form, n):
+    check_ema_follows_the_parameters(dev, kind, warmup, form, n)
 
 
 def lr_after(kind, lr, lr0, step, warm, gamma, ms):

@@ -304,8 +304,8 @@ def test_header_declares_the_entry_points_and_the_makefile_lists_the_source():
         assert re.search(r"\bint %s\(" % name, header), name
     mk = open(os.path.join(ROOT, "chexpert_amd", "csrc", "Makefile")).read()
     srcs = re.search(r"^SRCS = (.*)$", mk, re.M).group(1).split()
-    assert "optim_groups.hip" in srcs and "optim_ex.hip" in srcs and "elementwise.hip" in srcs
-    assert os.path.exists(os.path.join(ROOT, "chexpert_amd", "csrc", "optim_groups.hip"))
+    assert "optim.hip" in srcs and "elementwise.hip" in srcs
+    assert os.path.exists(os.path.join(ROOT, "chexpert_amd", "csrc", "optim.hip"))
 
 
 # ---------------------------------------------------------------------------------------- the float64 restatement against torch.optim

@@ -1,4 +1,4 @@
-"""GPU: parameter groups of the fused optimisers (csrc/optim_groups.hip: cx_grad_norm_items, cx_*_step_items) and their wiring in
+"""GPU: parameter groups of the fused optimisers (csrc/optim.hip: cx_grad_norm_items, cx_*_step_items) and their wiring in
 chexpert_amd.optim, on a synthetic layout of ten tensors (about 30 V floats, V = cx_optim_item_vec4()): against torch.optim built
 with the same param_groups on the CPU, the float64 restatement optim.reference_step where torch has no such rule, and bit for bit
 where the feature promises bits (partition independence, frozen groups, skipped steps, the captured step, groups=None)."""
