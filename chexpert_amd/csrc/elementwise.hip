@@ -1,7 +1,6 @@
 // HBM-bound glue kernels of the DenseNet hot path: layout conversion, weight packing, BatchNorm
 // coefficient bookkeeping, stem pooling, head, loss, un-pooling and the fused optimisers.
 // All activation traffic is 16 B per lane along the channel axis (NHWC bf16).
-#include <type_traits>
 #include <vector>
 #include "common.h"
 
@@ -628,103 +627,6 @@ __global__ void linear_kernel(const float* __restrict__ pooled, const float* __r
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
     if (lane == 0) logits[(size_t)b * n_classes + k] = acc + (bias ? bias[k] : 0.f);
-  }
-}
-
-__global__ void bce_kernel(const float* __restrict__ logits, const float* __restrict__ target, float* loss, float* loss_elem,
-                           float* dlogits, float grad_scale, int B, int n) {
-  __shared__ float red[256];
-  float acc = 0.f;
-  const float invB = 1.f / B;
-  for (int i = threadIdx.x; i < B * n; i += blockDim.x) {
-    const float x = logits[i], t = target[i];
-    const float l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-    acc += l;
-    if (loss_elem) loss_elem[i] = l;
-    if (dlogits) dlogits[i] = (1.f / (1.f + expf(-x)) - t) * invB * grad_scale;
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && loss) *loss = red[0] * invB;
-}
-
-// bce_kernel with ignored elements (target < 0: no loss, no gradient; the divisor stays B) and, when WEIGHTED, a per-class positive
-// weight (torch's BCEWithLogitsLoss(pos_weight)).  One workgroup, fixed tree, no atomics.  Unweighted, a live element runs
-// bce_kernel's expressions and the sum its fp32 tree, so targets without negatives give bce_kernel's bits.  Weighted, the sum runs
-// in double: weights up to 16 on logits of +-8 take the batch sum of 256 x 14 elements past 1e4, where an fp32 add rounds to 5e-4.
-template <bool WEIGHTED>
-__global__ void bce_masked_kernel(const float* __restrict__ logits, const float* __restrict__ target, const float* __restrict__ pos_weight,
-                                  float* loss, float* loss_elem, float* dlogits, float grad_scale, int B, int n) {
-  using Acc = typename std::conditional<WEIGHTED, double, float>::type;
-  __shared__ Acc red[256];
-  Acc acc = 0;
-  const float invB = 1.f / B;
-  for (int i = threadIdx.x; i < B * n; i += blockDim.x) {
-    const float x = logits[i], t = target[i];
-    float l = 0.f, d = 0.f;
-    if (t >= 0.f) {
-      if (WEIGHTED) {
-        const float w = 1.f + (pos_weight[i % n] - 1.f) * t;
-        l = (1.f - t) * x + w * (log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f));
-        d = ((1.f - t) - w * (1.f / (1.f + expf(x)))) * invB * grad_scale;      // 1 - sigmoid(x) = sigmoid(-x), without the cancellation
-      } else {
-        l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-        d = (1.f / (1.f + expf(-x)) - t) * invB * grad_scale;
-      }
-    }
-    acc += l;
-    if (loss_elem) loss_elem[i] = l;
-    if (dlogits) dlogits[i] = d;
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && loss) *loss = WEIGHTED ? (float)(red[0] / B) : (float)red[0] * invB;
-}
-
-// one wave per sample: row maximum and sum of exponentials by DPP-free shuffles, loss = mean_b (logsumexp - logit[target]);
-// the per-sample terms are summed by ONE workgroup in sample order (bit-reproducible)
-__global__ void softmax_ce_kernel(const float* __restrict__ logits, const long long* __restrict__ target, float* loss, float* loss_elem,
-                                  float* dlogits, float grad_scale, int B, int n) {
-  __shared__ float red[256];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const float invB = 1.f / B;
-  float acc = 0.f;                                       // lane 0 of each wave: its samples' losses
-  for (int b = wave; b < B; b += nw) {
-    const float* row = logits + (size_t)b * n;
-    float m = -INFINITY;
-    for (int i = lane; i < n; i += 64) m = fmaxf(m, row[i]);
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float se = 0.f;
-    for (int i = lane; i < n; i += 64) se += expf(row[i] - m);
-    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
-    const int t = (int)target[b];
-    const float l = (t >= 0 && t < n) ? m + logf(se) - row[t] : 0.f;
-    if (lane == 0) {
-      acc += l;
-      if (loss_elem) loss_elem[b] = l;
-    }
-    if (dlogits) {
-      const float inv = 1.f / se;
-      // a target outside [0, n) contributes no loss and no gradient (nn.CrossEntropyLoss raises on it; the host wrapper checks the
-      // target tensor's type and placement, its values stay on the device)
-      const float live = (t >= 0 && t < n) ? invB * grad_scale : 0.f;
-      for (int i = lane; i < n; i += 64) dlogits[(size_t)b * n + i] = (expf(row[i] - m) * inv - (i == t ? 1.f : 0.f)) * live;
-    }
-  }
-  red[threadIdx.x] = lane == 0 ? acc : 0.f;
-  __syncthreads();
-  if (threadIdx.x == 0 && loss) {
-    float s = 0.f;
-    for (int w = 0; w < nw; ++w) s += red[w * 64];
-    *loss = s * invB;
   }
 }
 
@@ -1689,34 +1591,6 @@ int cx_head_fwd(const void* x, const float* scale, const float* shift, const flo
 }
 int cx_head_fwd_f32(const void* x, const float* scale, const float* shift, const float* w, const float* bias, float* pooled, float* logits, int B, int HW, int C, int ldx, int n_classes, void* stream) {
   return head_fwd_t<float>(x, scale, shift, w, bias, pooled, logits, B, HW, C, ldx, n_classes, stream);
-}
-
-int cx_bce_fwd_bwd(const float* logits, const float* target, float* loss, float* loss_elem, float* dlogits, float grad_scale,
-                   int B, int n_classes, void* stream) {
-  if (!logits || !target || B <= 0 || n_classes <= 0) return CX_EINVAL;
-  hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(256), 0, as_stream(stream), logits, target, loss, loss_elem, dlogits, grad_scale, B,
-                     n_classes);
-  return launch_status();
-}
-
-int cx_bce_masked_fwd_bwd(const float* logits, const float* target, const float* pos_weight, float* loss, float* loss_elem,
-                          float* dlogits, float grad_scale, int B, int n_classes, void* stream) {
-  if (!logits || !target || B <= 0 || n_classes <= 0) return CX_EINVAL;
-  if (pos_weight)
-    hipLaunchKernelGGL(bce_masked_kernel<true>, dim3(1), dim3(256), 0, as_stream(stream), logits, target, pos_weight, loss, loss_elem,
-                       dlogits, grad_scale, B, n_classes);
-  else
-    hipLaunchKernelGGL(bce_masked_kernel<false>, dim3(1), dim3(256), 0, as_stream(stream), logits, target, pos_weight, loss, loss_elem,
-                       dlogits, grad_scale, B, n_classes);
-  return launch_status();
-}
-
-int cx_softmax_ce_fwd_bwd(const float* logits, const int64_t* target, float* loss, float* loss_elem, float* dlogits, float grad_scale,
-                          int B, int n_classes, void* stream) {
-  if (!logits || !target || B <= 0 || n_classes <= 0) return CX_EINVAL;
-  hipLaunchKernelGGL(softmax_ce_kernel, dim3(1), dim3(256), 0, as_stream(stream), logits, (const long long*)target, loss, loss_elem,
-                     dlogits, grad_scale, B, n_classes);
-  return launch_status();
 }
 
 int cx_head_bwd(const float* dlogits, const float* pooled, const float* w, float* dw, float* db, float* dpooled, int B, int C,

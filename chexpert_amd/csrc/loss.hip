@@ -1,0 +1,387 @@
+// The training losses on the (B, n) logits of a step, each with d loss / d logits in one launch of ONE workgroup: the operand is
+// B x n floats (256 x 14 at the largest), so the launch is latency, not throughput, and one workgroup keeps every sum in a fixed
+// order without a second launch or an atomic.  Three families:
+//
+//   cx_bce_fwd_bwd, cx_bce_masked_fwd_bwd, cx_asl_fwd_bwd   sums over elements: one skeleton (elem_loss_kernel) over a per-element
+//                                                           term, four terms (plain, masked and weighted BCE, focal / asymmetric)
+//   cx_softmax_ce_fwd_bwd                                   one wave per sample, its own final sum
+//   cx_aucm_fwd_bwd, cx_aucm_aux_step                       a function of each class's whole batch column: column trees, two passes
+#include "common.h"
+
+#include <climits>
+
+namespace {
+
+constexpr int NT = 256;       // workgroup width
+
+// sigmoid(x) and 1 - sigmoid(x) = sigmoid(-x), the second without the cancellation
+__device__ __forceinline__ void sigmoid_pair(const float x, float& p, float& q) {
+  p = 1.f / (1.f + expf(-x));
+  q = 1.f / (1.f + expf(x));
+}
+
+// ---- the element-wise terms -----------------------------------------------------------------------------------------------------
+// A term holds what a launch fixes (the per-class weights, the focus numbers, read from memory once per thread), names the type its
+// sum runs in (Acc) and states the arithmetic of one element: (x, t, class index k) -> the loss l and d = d loss / d x, the latter
+// already times invB * grad_scale.  mean() is the final divide of the folded sum.  The expressions of a term are its own: two terms
+// that look alike do not share a rounded sub-expression.
+
+// BCEWithLogitsLoss summed over the classes and averaged over the batch.  A negative target is a number like any other.
+struct BceTerm {
+  using Acc = float;
+  __device__ BceTerm(const float*, const float*) {}
+  __device__ __forceinline__ void operator()(float x, float t, int k, float invB, float grad_scale, float& l, float& d) const {
+    l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+    d = (1.f / (1.f + expf(-x)) - t) * invB * grad_scale;
+  }
+  __device__ static float mean(float sum, int B, float invB) { return sum * invB; }
+};
+
+// BceTerm with ignored elements (target < 0: no loss, no gradient; the divisor stays B) and, in WeightedBceTerm, a per-class positive
+// weight (torch's BCEWithLogitsLoss(pos_weight)).  One workgroup, fixed tree, no atomics.  Unweighted, a live element runs
+// BceTerm's expressions and the sum its fp32 tree, so targets without negatives give cx_bce_fwd_bwd's bits.  Weighted, the sum runs
+// in double: weights up to 16 on logits of +-8 take the batch sum of 256 x 14 elements past 1e4, where an fp32 add rounds to 5e-4.
+struct MaskedBceTerm : BceTerm {
+  using BceTerm::BceTerm;
+  __device__ __forceinline__ void operator()(float x, float t, int k, float invB, float grad_scale, float& l, float& d) const {
+    l = d = 0.f;
+    if (t >= 0.f) BceTerm::operator()(x, t, k, invB, grad_scale, l, d);
+  }
+};
+
+struct WeightedBceTerm {
+  using Acc = double;
+  const float* __restrict__ pos_weight;
+  __device__ WeightedBceTerm(const float* pos_weight, const float*) : pos_weight(pos_weight) {}
+  __device__ __forceinline__ void operator()(float x, float t, int k, float invB, float grad_scale, float& l, float& d) const {
+    l = d = 0.f;
+    if (t >= 0.f) {
+      const float w = 1.f + (pos_weight[k] - 1.f) * t;
+      l = (1.f - t) * x + w * (log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f));
+      float p, q;
+      sigmoid_pair(x, p, q);
+      d = ((1.f - t) - w * q) * invB * grad_scale;
+    }
+  }
+  __device__ static float mean(double sum, int B, float invB) { return (float)(sum / B); }
+};
+
+// Focal loss (Lin et al., ICCV 2017) and asymmetric loss (Ridnik et al., "Asymmetric Loss for Multi-Label Classification", ICCV 2021)
+// on the (B, n) logits of a training step, with d loss / d logits, in one launch (include/chexpert_hip.h, cx_asl_fwd_bwd).  One
+// term serves both: the focal loss is the asymmetric one with equal exponents and no clip.
+//
+// The shape is the masked BCE's (elem_loss_kernel): one workgroup, a grid-stride loop over the B x n elements, a fixed tree over
+// LDS, no atomics, every output optional.  The sum runs in double, for the reason the weighted BCE gives.  The four
+// hyper-parameters are READ FROM MEMORY (focus[4] = gamma+, gamma-, clip, alpha or a negative number for "no alpha"), so a captured
+// step sees a change made in place.
+//
+// Numerics.  With e = log1p(exp(-|x|)):  softplus(x) = max(x, 0) + e = -log q  and  softplus(-x) = max(-x, 0) + e = -log p, so
+// neither logarithm is taken of a rounded probability; q = 1 / (1 + exp(x)) is never 1 - p.  The focusing weight u^g is
+// exp(g log u), and log u is one of those softplus values wherever u is p or q themselves (hard targets without a clip, hard
+// positives always): q^g of a confident positive is exp(-g softplus(x)), to a relative error of g |ln q| 2^-24.  With a clip m > 0 the
+// shifted negative probability p_n = min(q + m, 1) is at least m; its logarithm is log1p(-(p - m)) while p - m < 1/2 (p - m is
+// exact near the clip, so the loss keeps its relative accuracy as it goes to 0 there) and log(q + m) beyond.
+//
+// The clip is stated piecewise.  A hard negative at or below it (u = 0) gives loss 0 and gradient 0 exactly; the product
+// g u^(g-1) u' is never formed (it is inf * 0 there for g < 1).  Above the clip u > 0 and g u^(g-1) u' = g f u' / u is finite.
+struct AslTerm {
+  using Acc = double;
+  const float* __restrict__ pos_weight;
+  float gp, gn, m, alpha;
+  __device__ AslTerm(const float* pos_weight, const float* focus)
+      : pos_weight(pos_weight), gp(focus[0]), gn(focus[1]), m(focus[2]), alpha(focus[3]) {}
+  __device__ __forceinline__ void operator()(float x, float t, int k, float invB, float grad_scale, float& l, float& d) const {
+    l = d = 0.f;
+    if (t >= 0.f) {
+      const float w = pos_weight ? pos_weight[k] : 1.f;
+      const float e = log1pf(expf(-fabsf(x)));
+      const float sp = fmaxf(x, 0.f) + e, sn = fmaxf(-x, 0.f) + e;      // -log q, -log p
+      float p, q;
+      sigmoid_pair(x, p, q);
+      const float omt = 1.f - t;
+      const bool above = p > m;                                          // p_m = p - m there, 0 (and constant) elsewhere
+      const float pm = above ? p - m : 0.f;
+      float lpn, dneg;                                                   // log p_n;  d(-log p_n)/dx = p q / p_n above the clip
+      if (m == 0.f) {
+        lpn = -sp;
+        dneg = p;
+      } else if (above) {
+        lpn = pm < 0.5f ? log1pf(-pm) : logf(q + m);
+        dneg = p * q / fminf(q + m, 1.f);
+      } else {
+        lpn = 0.f;
+        dneg = 0.f;
+      }
+      const float C = w * t * sn - omt * lpn;
+      const float dC = omt * dneg - w * t * q;
+      const float u = t * q + omt * pm;                                  // 1 - p_t;  u' = p q ((1 - t) [p > m] - t)
+      const float g = gp * t + gn * omt;
+      float f = 1.f, df = 0.f;
+      if (g != 0.f) {
+        if (u > 0.f) {
+          float lu, ratio;                                               // log u, u' / u
+          if (t == 1.f) {
+            lu = -sp;
+            ratio = -p;
+          } else if (t == 0.f && m == 0.f) {
+            lu = -sn;
+            ratio = q;
+          } else {
+            lu = logf(u);
+            ratio = p * q * ((above ? omt : 0.f) - t) / u;
+          }
+          f = expf(g * lu);
+          df = g * f * ratio;
+        } else {
+          f = 0.f;                                                       // 0^g, g > 0: the hard threshold; its derivative is taken as 0
+        }
+      }
+      const float a = alpha < 0.f ? 1.f : alpha * t + (1.f - alpha) * omt;
+      l = a * f * C;
+      d = a * (df * C + f * dC) * invB * grad_scale;
+    }
+  }
+  __device__ static float mean(double sum, int B, float invB) { return (float)(sum / B); }
+};
+
+// ---- the element-wise skeleton --------------------------------------------------------------------------------------------------
+// One workgroup: thread t takes elements t, t + 256, ... of the B x n, adds their losses in Term::Acc, and the 256 sums are folded
+// by a fixed tree over LDS.  loss (one float), loss_elem and dlogits (B x n) are each written when given.  The stride and the tree
+// are stated on blockDim.x (256 at every launch), not on NT: with the constant the compiler unrolls the tree and packs the two
+// products of the weighted BCE's loss into one v_pk_mul_f32 ahead of the contraction, which costs that loss its fused multiply-add
+// (a last-bit change of loss and loss_elem on soft targets).
+template <typename Term>
+__global__ __launch_bounds__(NT) void elem_loss_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                       const float* __restrict__ pos_weight, const float* __restrict__ focus,
+                                                       float* loss, float* loss_elem, float* dlogits, float grad_scale, int B, int n) {
+  using Acc = typename Term::Acc;
+  __shared__ Acc red[NT];
+  const Term term(pos_weight, focus);
+  const float invB = 1.f / B;
+  Acc acc = 0;
+  for (int i = threadIdx.x; i < B * n; i += blockDim.x) {
+    float l, d;
+    term(logits[i], target[i], i % n, invB, grad_scale, l, d);
+    acc += l;
+    if (loss_elem) loss_elem[i] = l;
+    if (dlogits) dlogits[i] = d;
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && loss) *loss = Term::mean(red[0], B, invB);
+}
+
+template <typename Term>
+int launch_elem_loss(const float* logits, const float* target, const float* pos_weight, const float* focus, float* loss,
+                     float* loss_elem, float* dlogits, float grad_scale, int B, int n, void* stream) {
+  hipLaunchKernelGGL(elem_loss_kernel<Term>, dim3(1), dim3(NT), 0, as_stream(stream), logits, target, pos_weight, focus, loss, loss_elem,
+                     dlogits, grad_scale, B, n);
+  return launch_status();
+}
+
+// ---- softmax cross-entropy ------------------------------------------------------------------------------------------------------
+// one wave per sample: row maximum and sum of exponentials by DPP-free shuffles, loss = mean_b (logsumexp - logit[target]);
+// the per-sample terms are summed by ONE workgroup in sample order (bit-reproducible)
+__global__ void softmax_ce_kernel(const float* __restrict__ logits, const long long* __restrict__ target, float* loss, float* loss_elem,
+                                  float* dlogits, float grad_scale, int B, int n) {
+  __shared__ float red[256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const float invB = 1.f / B;
+  float acc = 0.f;                                       // lane 0 of each wave: its samples' losses
+  for (int b = wave; b < B; b += nw) {
+    const float* row = logits + (size_t)b * n;
+    float m = -INFINITY;
+    for (int i = lane; i < n; i += 64) m = fmaxf(m, row[i]);
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    float se = 0.f;
+    for (int i = lane; i < n; i += 64) se += expf(row[i] - m);
+    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+    const int t = (int)target[b];
+    const float l = (t >= 0 && t < n) ? m + logf(se) - row[t] : 0.f;
+    if (lane == 0) {
+      acc += l;
+      if (loss_elem) loss_elem[b] = l;
+    }
+    if (dlogits) {
+      const float inv = 1.f / se;
+      // a target outside [0, n) contributes no loss and no gradient (nn.CrossEntropyLoss raises on it; the host wrapper checks the
+      // target tensor's type and placement, its values stay on the device)
+      const float live = (t >= 0 && t < n) ? invB * grad_scale : 0.f;
+      for (int i = lane; i < n; i += 64) dlogits[(size_t)b * n + i] = (expf(row[i] - m) * inv - (i == t ? 1.f : 0.f)) * live;
+    }
+  }
+  red[threadIdx.x] = lane == 0 ? acc : 0.f;
+  __syncthreads();
+  if (threadIdx.x == 0 && loss) {
+    float s = 0.f;
+    for (int w = 0; w < nw; ++w) s += red[w * 64];
+    *loss = s * invB;
+  }
+}
+
+// ---- AUC margin -----------------------------------------------------------------------------------------------------------------
+// AUC min-max-margin loss (Yuan et al., "Large-scale Robust Deep AUC Maximization", ICCV 2021) on the (B, n) logits of a training
+// step, with the gradients of the logits and of the three auxiliary scalars per class (include/chexpert_hip.h, cx_aucm_fwd_bwd),
+// and the primal-descent / dual-ascent update of those scalars (cx_aucm_aux_step).
+//
+// One workgroup, like the BCE kernels it stands beside: the operand is B x n floats (256 x 14 at the largest), so the launch is
+// latency, not throughput, and one workgroup keeps every sum in a fixed order without a second launch or an atomic.
+// Thread (r, c) = (tid / CW, tid % CW), CW the power of two that covers min(n, 256): column c is a class, the 256 / CW threads of a
+// column stride over the rows.  The work is five sums per class -- (y-a)^2 and (y-a) over the positives, (y-b)^2 and (y-b) over the
+// negatives, and p y N - (1-p) y P over both -- plus the count of live rows.  They run in double, for the reason the weighted BCE
+// gives: 1e3 terms of order 1 added in fp32 round at 1e-4, which is the whole loss tolerance.  Each column is folded by a fixed
+// tree over r through LDS; the thread r = 0 then holds the class's totals, writes its loss term and auxiliary gradients and leaves
+// the row count in LDS for the second pass, in which the same threads write d loss / d logits (it needs L, so it cannot be fused
+// into the first).  Classes beyond CW (n > 256) are taken in further sweeps of the same code.  The class terms are added to the
+// loss by thread 0 in class order.  No atomics anywhere: two runs give the same bits.
+constexpr int NSUM = 5;       // double sums per class
+
+__global__ __launch_bounds__(NT) void aucm_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                  const float* __restrict__ prior, const float* __restrict__ aux, float margin,
+                                                  float* loss, float* loss_class, float* dlogits, float* daux, float grad_scale, int B,
+                                                  int n, int CW) {
+  __shared__ double red[NSUM][NT];
+  __shared__ int cnt[NT];
+  __shared__ double cls[NT];           // loss terms of this sweep's classes
+  const int tid = threadIdx.x, c = tid % CW, r = tid / CW, R = NT / CW;
+  double total = 0.0;                  // thread 0: the loss so far
+  for (int c0 = 0; c0 < n; c0 += CW) {
+    const int k = c0 + c;
+    const bool on = k < n;
+    double p = 0.5, a = 0.0, b = 0.0, al = 0.0;
+    if (on) { p = prior[k]; a = aux[k]; b = aux[n + k]; al = aux[2 * n + k]; }
+    double s[NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    int live = 0;
+    if (on) {
+      for (int i = r; i < B; i += R) {
+        const float t = target[(size_t)i * n + k];
+        if (t >= 0.f) {
+          float yf, omy;
+          sigmoid_pair(logits[(size_t)i * n + k], yf, omy);
+          const double y = yf;
+          ++live;
+          if (t >= 0.5f) {
+            const double d = y - a;
+            s[0] += d * d;
+            s[1] += d;
+            s[4] -= (1.0 - p) * y;
+          } else {
+            const double d = y - b;
+            s[2] += d * d;
+            s[3] += d;
+            s[4] += p * y;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NSUM; ++j) red[j][tid] = s[j];
+    cnt[tid] = live;
+    __syncthreads();
+    for (int h = R / 2; h > 0; h >>= 1) {
+      if (r < h) {
+#pragma unroll
+        for (int j = 0; j < NSUM; ++j) red[j][tid] += red[j][tid + h * CW];
+        cnt[tid] += cnt[tid + h * CW];
+      }
+      __syncthreads();
+    }
+    if (r == 0) {
+      double lc = 0.0;
+      if (on) {
+        const int nl = cnt[c];
+        double da = 0.0, db = 0.0, dal = 0.0;
+        if (nl > 0) {                  // a class without a live row adds nothing and moves nothing
+          const double L = nl, q = p * (1.0 - p), inner = q * margin + red[4][c] / L;
+          lc = ((1.0 - p) * red[0][c] + p * red[2][c]) / L + 2.0 * al * inner - q * al * al;
+          da = -(1.0 - p) * 2.0 * red[1][c] / L;
+          db = -p * 2.0 * red[3][c] / L;
+          dal = 2.0 * inner - 2.0 * q * al;
+        }
+        if (loss_class) loss_class[k] = (float)lc;
+        if (daux) { daux[k] = (float)da; daux[n + k] = (float)db; daux[2 * n + k] = (float)dal; }
+      }
+      cls[c] = lc;
+    }
+    __syncthreads();
+    if (tid == 0)
+      for (int j = 0; j < CW && c0 + j < n; ++j) total += cls[j];
+    if (dlogits && on) {
+      const int nl = cnt[c];
+      const float invL = nl > 0 ? 1.f / (float)nl : 0.f;
+      const float pf = (float)p, af = (float)a, bf = (float)b, alf = (float)al;
+      for (int i = r; i < B; i += R) {
+        const float t = target[(size_t)i * n + k];
+        float d = 0.f;
+        if (t >= 0.f) {
+          float y, omy;
+          sigmoid_pair(logits[(size_t)i * n + k], y, omy);
+          const float g = t >= 0.5f ? (1.f - pf) * (2.f * (y - af) - 2.f * alf) : pf * (2.f * (y - bf) + 2.f * alf);
+          d = y * omy * invL * g * grad_scale;
+        }
+        dlogits[(size_t)i * n + k] = d;
+      }
+    }
+    __syncthreads();                   // red / cnt / cls are rewritten by the next sweep
+  }
+  if (tid == 0 && loss) *loss = (float)total;
+}
+
+__global__ void aucm_aux_step_kernel(float* __restrict__ aux, const float* __restrict__ daux, const float* __restrict__ lr_aux, int n) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const float lr = *lr_aux;
+  aux[k] = aux[k] - lr * daux[k];
+  aux[n + k] = aux[n + k] - lr * daux[n + k];
+  aux[2 * n + k] = fmaxf(aux[2 * n + k] + lr * daux[2 * n + k], 0.f);
+}
+
+}  // namespace
+
+int cx_bce_fwd_bwd(const float* logits, const float* target, float* loss, float* loss_elem, float* dlogits, float grad_scale,
+                   int B, int n_classes, void* stream) {
+  if (!logits || !target || B <= 0 || n_classes <= 0) return CX_EINVAL;
+  return launch_elem_loss<BceTerm>(logits, target, nullptr, nullptr, loss, loss_elem, dlogits, grad_scale, B, n_classes, stream);
+}
+
+int cx_bce_masked_fwd_bwd(const float* logits, const float* target, const float* pos_weight, float* loss, float* loss_elem,
+                          float* dlogits, float grad_scale, int B, int n_classes, void* stream) {
+  if (!logits || !target || B <= 0 || n_classes <= 0) return CX_EINVAL;
+  return (pos_weight ? launch_elem_loss<WeightedBceTerm> : launch_elem_loss<MaskedBceTerm>)(
+      logits, target, pos_weight, nullptr, loss, loss_elem, dlogits, grad_scale, B, n_classes, stream);
+}
+
+int cx_asl_fwd_bwd(const float* logits, const float* target, const float* pos_weight, const float* focus, float* loss, float* loss_elem,
+                   float* dlogits, float grad_scale, int B, int n_classes, void* stream) {
+  if (!logits || !target || !focus || B < 1 || n_classes < 1 || (long long)B * n_classes > INT_MAX - NT) return CX_EINVAL;
+  return launch_elem_loss<AslTerm>(logits, target, pos_weight, focus, loss, loss_elem, dlogits, grad_scale, B, n_classes, stream);
+}
+
+int cx_softmax_ce_fwd_bwd(const float* logits, const int64_t* target, float* loss, float* loss_elem, float* dlogits, float grad_scale,
+                          int B, int n_classes, void* stream) {
+  if (!logits || !target || B <= 0 || n_classes <= 0) return CX_EINVAL;
+  hipLaunchKernelGGL(softmax_ce_kernel, dim3(1), dim3(256), 0, as_stream(stream), logits, (const long long*)target, loss, loss_elem,
+                     dlogits, grad_scale, B, n_classes);
+  return launch_status();
+}
+
+int cx_aucm_fwd_bwd(const float* logits, const float* target, const float* prior, const float* aux, float margin, float* loss,
+                    float* loss_class, float* dlogits, float* daux, float grad_scale, int B, int n_classes, void* stream) {
+  if (!logits || !target || !prior || !aux || B < 1 || n_classes < 1 || !(margin > 0.f)) return CX_EINVAL;
+  int CW = 1;
+  while (CW < n_classes && CW < NT) CW <<= 1;
+  hipLaunchKernelGGL(aucm_kernel, dim3(1), dim3(NT), 0, as_stream(stream), logits, target, prior, aux, margin, loss, loss_class, dlogits,
+                     daux, grad_scale, B, n_classes, CW);
+  return launch_status();
+}
+
+int cx_aucm_aux_step(float* aux, const float* daux, const float* lr_aux_dev, int n_classes, void* stream) {
+  if (!aux || !daux || !lr_aux_dev || n_classes < 1) return CX_EINVAL;
+  hipLaunchKernelGGL(aucm_aux_step_kernel, dim3((n_classes + NT - 1) / NT), dim3(NT), 0, as_stream(stream), aux, daux, lr_aux_dev,
+                     n_classes);
+  return launch_status();
+}

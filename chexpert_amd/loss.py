@@ -1,16 +1,190 @@
-"""The training loss with uncertain-label handling outside the fused step: `loss = MaskedBCE(w)(model(x), t); loss.backward()` and
-the element losses of an evaluation run the arithmetic of `FusedNet.set_loss` (cx_bce_masked_fwd_bwd, csrc/elementwise.hip), so
-the autograd route and the fused step agree bit for bit.  AUCMLoss is the same for `FusedNet.set_loss(kind="aucm")`: the AUC
-min-max-margin loss (cx_aucm_fwd_bwd, csrc/aucm.hip) with its auxiliary scalars as parameters.  FocalLoss and AsymmetricLoss are
-the same for `FusedNet.set_loss(kind="focal" | "asl")` (cx_asl_fwd_bwd, csrc/focal.hip).  Device tensors only: there is no CPU
-path."""
+"""The loss of a training step, stated once for its two routes.  `Loss` is what `FusedNet.set_loss` holds: the kind, its numbers and
+the device tensors the kernels of csrc/loss.hip read, with the one rule that picks the kernel (`Loss.launch`).  The modules below are
+the same losses outside the fused step -- `loss = MaskedBCE(w)(model(x), t); loss.backward()` and the element losses of an
+evaluation -- over the same `launch`, so the autograd route and the fused step run one kernel and agree bit for bit: MaskedBCE for
+the cross-entropy with uncertain-label handling (cx_bce_fwd_bwd / cx_bce_masked_fwd_bwd), AUCMLoss for kind "aucm" (cx_aucm_fwd_bwd),
+with its auxiliary scalars as parameters, FocalLoss and AsymmetricLoss for kinds "focal" and "asl" (cx_asl_fwd_bwd).  Device
+tensors only: there is no CPU path."""
 import torch
 import torch.nn as nn
 
 from . import ops
 
+KERNEL = {"bce": "cx_bce_masked_fwd_bwd", "aucm": "cx_aucm_fwd_bwd", "focal": "cx_asl_fwd_bwd", "asl": "cx_asl_fwd_bwd"}
 
-def _operands(logits, target, who="MaskedBCE", kernel="cx_bce_masked_fwd_bwd"):
+
+# ------------------------------------------------------------------------------------------------ the range checks, each once
+# `who` is the caller as its user wrote it (set_loss(kind='asl'), FocalLoss, ...); a refusal is a ValueError in its name.
+def check_focus(who, gamma_pos, gamma_neg, clip, alpha, names=("gamma_pos", "gamma_neg")):
+    """The four numbers of the focal / asymmetric loss as the kernel reads them: [gamma+, gamma-, clip, alpha or -1]."""
+    try:
+        gp, gn, m, al = (float(v) for v in (gamma_pos, gamma_neg, clip, -1.0 if alpha is None else alpha))
+    except (TypeError, ValueError):
+        raise ValueError("%s takes numbers (got %r)" % (who, (gamma_pos, gamma_neg, clip, alpha)))
+    for name, v in zip(names, (gp, gn)):
+        if not 0 <= v < float("inf"):
+            raise ValueError("%s takes a finite %s >= 0 (got %r)" % (who, name, v))
+    if not 0 <= m < 1:
+        raise ValueError("%s takes a clip in [0, 1) (got %r)" % (who, m))
+    if alpha is not None and not 0 < al < 1:          # (NaN fails it)
+        raise ValueError("%s takes alpha None or in (0, 1) (got %r)" % (who, alpha))
+    return [gp, gn, m, al]
+
+
+def check_pos_weight(who, pos_weight, n=None):
+    """None, or the positive-term weights as an fp32 vector (on the device they came on): finite, > 0, and n of them where n is given."""
+    if pos_weight is None:
+        return None
+    w = torch.as_tensor(pos_weight, dtype=torch.float32).detach().reshape(-1)
+    if (n is not None and w.numel() != n) or not bool(((w > 0) & torch.isfinite(w)).all()):
+        raise ValueError("%s takes %sfinite pos_weight > 0 (got %s)" % (who, "" if n is None else "%d " % n, w.tolist()))
+    return w
+
+
+def check_prior(who, prior, margin, n=None):
+    """The class positive rates of the AUC-margin loss as a CPU fp32 vector: in (0, 1), n of them where n is given; margin > 0."""
+    if prior is None:
+        raise ValueError("%s needs prior: the class positive rates" % who)
+    p = torch.as_tensor(prior, dtype=torch.float32).detach().reshape(-1).cpu()
+    if p.numel() < 1 or (n is not None and p.numel() != n):
+        raise ValueError("%s takes one prior per class%s (got %d)" % (who, "" if n is None else ": %d" % n, p.numel()))
+    if not bool(((p > 0) & (p < 1)).all()):
+        raise ValueError("%s takes priors in (0, 1) (got %s)" % (who, p.tolist()))
+    if not float(margin) > 0:
+        raise ValueError("%s takes a margin > 0 (got %r)" % (who, margin))
+    return p
+
+
+# ------------------------------------------------------------------------------------------------ the loss of a step
+class Loss:
+    """The loss of a step: `kind` ('bce', 'aucm', 'focal', 'asl'), `ignore_negative`, `margin` (a host float, passed by value) and
+    the fp32 device tensors the kernels read -- `pos_weight` (n,), `focus` (4,) = [gamma+, gamma-, clip, alpha or -1], `aux` and
+    `daux` (3, n) = rows a, b, alpha and their gradients, `prior` (n,), `lr_aux` (1,) --, None where the kind has none.  Plain
+    tensors, neither buffers nor parameters.  Behind them stands held storage (`_held`, by name) that outlives a change of kind: a
+    repeated set() with the same sizes copies into it, so a captured step, which replays the storage it was captured with, sees the
+    new values.  FusedNet keeps one (set / state / load_state are its set_loss / loss_state / load_loss_state); a loss module makes
+    one per call from its own attributes."""
+
+    def __init__(self, kind="bce", ignore_negative=False, margin=1.0, pos_weight=None, focus=None, aux=None, daux=None, prior=None,
+                 lr_aux=None):
+        self.kind, self.ignore_negative, self.margin = kind, ignore_negative, margin
+        self.pos_weight, self.focus, self.aux, self.daux, self.prior, self.lr_aux = pos_weight, focus, aux, daux, prior, lr_aux
+        self._held = {}
+
+    def launch(self, logits, target, loss, loss_elem, dlogits):
+        """The loss (1,), the element losses (B, n) and d loss / d logits (B, n), each where given, in one launch.  The kernel is
+        the kind's; for 'bce' the masked one when ignore_negative is set or there are weights (it skips every target < 0: the
+        weighted loss has no arithmetic for a negative target), else the plain one, to which a negative target is a number."""
+        if self.kind == "aucm":
+            if loss_elem is not None:
+                raise RuntimeError("the AUC-margin loss has no element losses")
+            ops.aucm_fwd_bwd(logits, target, self.prior, self.aux, self.margin, loss, None, dlogits, self.daux)
+        elif self.kind in ("focal", "asl"):
+            ops.asl_fwd_bwd(logits, target, self.pos_weight, self.focus, loss, loss_elem, dlogits)
+        elif self.ignore_negative or self.pos_weight is not None:
+            ops.bce_masked_fwd_bwd(logits, target, self.pos_weight, loss, loss_elem, dlogits)
+        else:
+            ops.bce_fwd_bwd(logits, target, loss, loss_elem, dlogits)
+
+    def _hold(self, name, values, dev, keep=False):
+        """`values` copied into the held storage `name`, which is made anew for another shape or another device; with `keep`,
+        storage that is already there stays as it is.  None: None (the storage is kept for the next time)."""
+        if values is None:
+            return None
+        v = torch.as_tensor(values, dtype=torch.float32)
+        held = self._held.get(name)
+        fresh = held is None or held.shape != v.shape or held.device != dev
+        if fresh:
+            held = self._held[name] = torch.empty(v.shape, dtype=torch.float32, device=dev)
+        if fresh or not keep:
+            held.copy_(v)
+        return held
+
+    def _put(self, who, dev, kind, ignore_negative, pos_weight=None, focus=None, prior=None, margin=None, lr_aux=None):
+        """The one place that writes the state, after every check: each field is assigned, to None where `kind` has none, so nothing
+        of the previous kind is left over.  `aux` starts at zero coming from another kind and stays as trained coming from 'aucm';
+        the margin stays what the last 'aucm' made it."""
+        if dev.type != "cuda" and (kind != "bce" or pos_weight is not None):
+            raise RuntimeError("%s holds its state on the parameters' device: call model.to(device) first" % who)
+        zeros = None if prior is None else torch.zeros(3, prior.numel())
+        self.aux = self._hold("aux", zeros, dev, keep=self.kind == "aucm")
+        self.daux = self._hold("daux", zeros, dev, keep=True)
+        self.pos_weight, self.focus = self._hold("pos_weight", pos_weight, dev), self._hold("focus", focus, dev)
+        self.prior, self.lr_aux = self._hold("prior", prior, dev), self._hold("lr_aux", None if lr_aux is None else [lr_aux], dev)
+        self.kind, self.ignore_negative = kind, ignore_negative
+        if margin is not None:
+            self.margin = float(margin)
+
+    def set(self, dev, n, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
+            alpha=None, gamma_pos=None, gamma_neg=None, clip=None):
+        """FusedNet.set_loss for a model of n classes with its parameters on dev.  A refused call changes nothing."""
+        if kind not in KERNEL:
+            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal' or 'asl' (got %r)" % (kind,))
+        if kind != "aucm" and (prior is not None or lr_aux is not None or margin != 1.0):
+            raise ValueError("set_loss: prior, margin and lr_aux belong to kind='aucm'")
+        if kind != "focal" and (gamma is not None or alpha is not None):
+            raise ValueError("set_loss: gamma and alpha belong to kind='focal'")
+        if kind != "asl" and (gamma_pos is not None or gamma_neg is not None or clip is not None):
+            raise ValueError("set_loss: gamma_pos, gamma_neg and clip belong to kind='asl'")
+        who = "set_loss(kind=%r)" % kind
+        if kind == "bce":
+            w = None if pos_weight is None else torch.as_tensor(pos_weight, dtype=torch.float32).reshape(-1)
+            self._put("set_loss(pos_weight=...)", dev, kind, bool(ignore_negative), w)
+        elif kind == "aucm":
+            if pos_weight is not None:
+                raise ValueError("%s cannot be combined with pos_weight: the class prior is this loss's weighting" % who)
+            p = check_prior(who, prior, margin, n)
+            if lr_aux is None or not float(lr_aux) > 0:
+                raise ValueError("%s needs lr_aux > 0, the rate of the auxiliary scalars (got %r)" % (who, lr_aux))
+            self._put(who, dev, kind, True, prior=p, margin=margin, lr_aux=float(lr_aux))
+        else:
+            if kind == "focal":
+                g = 2.0 if gamma is None else gamma
+                focus = check_focus(who, g, g, 0.0, alpha, ("gamma", "gamma"))
+            else:
+                focus = check_focus(who, 0.0 if gamma_pos is None else gamma_pos, 4.0 if gamma_neg is None else gamma_neg,
+                                    0.05 if clip is None else clip, None)
+            self._put(who, dev, kind, True, check_pos_weight(who, pos_weight, n), focus)
+
+    def step_state(self):
+        """FusedNet.loss_step_state: the tensors a train-mode step changes."""
+        return [self.aux] if self.kind == "aucm" else []
+
+    def state(self):
+        """FusedNet.loss_state: CPU tensors and floats."""
+        def cpu(t):
+            return None if t is None else t.detach().cpu().clone()
+        d = {"kind": self.kind, "aux": cpu(self.aux), "prior": cpu(self.prior), "margin": float(self.margin),
+             "lr_aux": None if self.lr_aux is None else float(self.lr_aux.item())}
+        if self.focus is not None:
+            d["focus"] = cpu(self.focus)
+        return d
+
+    def load_state(self, d, dev, n):
+        """FusedNet.load_loss_state."""
+        kind = d["kind"]
+        if kind in ("focal", "asl"):
+            focus = d.get("focus")
+            if focus is None or torch.as_tensor(focus).numel() != 4:
+                raise ValueError("load_loss_state: kind %r needs focus, four numbers (got %r)" % (kind, focus))
+            gp, gn, m, al = torch.as_tensor(focus, dtype=torch.float32).reshape(-1).tolist()
+            who = "load_loss_state(kind=%r)" % kind
+            focus = check_focus(who, gp, gn, m, None if al < 0 else al)
+            self._put(who, dev, kind, True, check_pos_weight(who, self.pos_weight, n), focus)      # (the held weights stay)
+        elif kind == "aucm":
+            aux = torch.as_tensor(d["aux"], dtype=torch.float32)
+            if tuple(aux.shape) != (3, n):
+                raise ValueError("load_loss_state: aux must be (3, %d) (got %s)" % (n, tuple(aux.shape)))
+            self.set(dev, n, kind="aucm", prior=d["prior"], margin=d["margin"], lr_aux=d["lr_aux"])
+            self.aux.copy_(aux)
+        elif kind != "bce":
+            raise ValueError("load_loss_state: unknown loss kind %r" % (kind,))
+        elif self.kind != "bce":               # (a model that holds the cross-entropy keeps its options)
+            self.set(dev, n)
+
+
+# ------------------------------------------------------------------------------------------------ the autograd route
+def _operands(logits, target, who, kernel):
     if not logits.is_cuda:
         raise RuntimeError("%s runs on the GPU only (%s); there is no CPU fallback" % (who, kernel))
     if logits.dim() != 2 or tuple(target.shape) != tuple(logits.shape):
@@ -18,88 +192,79 @@ def _operands(logits, target, who="MaskedBCE", kernel="cx_bce_masked_fwd_bwd"):
     return logits.detach().contiguous().float(), target.detach().contiguous().float()
 
 
-class _MaskedBCEFn(torch.autograd.Function):
-    """loss and d loss / d logits in one launch; backward scales the stored gradient."""
+class _LossFn(torch.autograd.Function):
+    """loss and d loss / d logits in one launch (Loss.launch); backward scales the stored gradient.  `aux`: nothing, or the a, b, alpha
+    of an AUCMLoss, which autograd records; their gradients are the three rows of state.daux, from the same launch."""
 
     @staticmethod
-    def forward(ctx, logits, target, pos_weight, masked):
-        x, t = _operands(logits, target)
+    def forward(ctx, logits, target, state, who, *aux):
+        x, t = _operands(logits, target, who, KERNEL[state.kind])
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty_like(x)
-        if masked:
-            ops.bce_masked_fwd_bwd(x, t, pos_weight, loss, None, dl)
-        else:
-            ops.bce_fwd_bwd(x, t, loss, None, dl)
-        ctx.save_for_backward(dl)
+        state.launch(x, t, loss, None, dl)
+        ctx.save_for_backward(dl, *([state.daux] if aux else []))
         ctx.in_dtype = logits.dtype
         return loss[0]
 
     @staticmethod
     def backward(ctx, grad_output):
-        dl, = ctx.saved_tensors
-        return (dl * grad_output).to(ctx.in_dtype), None, None, None
+        dl, *daux = ctx.saved_tensors
+        grads = ((dl * grad_output).to(ctx.in_dtype), None, None, None)
+        if daux:
+            # alpha is the dual variable: the saddle point is a minimum in (w, a, b) and a maximum in alpha, so its gradient leaves
+            # negated and the optimiser that descends on every parameter ascends on alpha
+            grads += (daux[0][0] * grad_output, daux[0][1] * grad_output, -daux[0][2] * grad_output)
+        return grads
 
 
-class MaskedBCE(nn.Module):
+class _LossModule(nn.Module):
+    """What the loss modules share.  A subclass keeps its operands as plain attributes -- moved by hand to the logits' device
+    (`.to` of the module leaves them), never in a state_dict -- and states them as a Loss in `_state(device)`."""
+    _aux = ()                  # names of the parameters autograd records
+
+    def _on(self, device, *names):
+        for name in names:
+            t = getattr(self, name)
+            if t is not None and t.device != device:
+                setattr(self, name, t.to(device))
+
+    def forward(self, logits, target):
+        who = type(self).__name__
+        _operands(logits, target, who, KERNEL[self.kind])                  # (refuses a CPU tensor before anything is moved)
+        return _LossFn.apply(logits, target, self._state(logits), who, *(getattr(self, name) for name in self._aux))
+
+    @torch.no_grad()
+    def elementwise(self, logits, target):
+        """The (B, n) element losses (0 where ignored, and for a hard negative at or below the clip), outside autograd."""
+        x, t = _operands(logits, target, type(self).__name__, KERNEL[self.kind])
+        out = torch.empty_like(x)
+        self._state(x).launch(x, t, None, out, None)
+        return out
+
+
+class MaskedBCE(_LossModule):
     """BCEWithLogitsLoss(pos_weight)(logits, target) summed over the classes and averaged over the batch (chexpert.py:160), in which
     a target < 0 is ignored (no loss, no gradient; the divisor stays the batch size).  The two options select the kernel exactly
     as FusedNet.set_loss does: with ignore_negative or a pos_weight it is cx_bce_masked_fwd_bwd, which skips every target < 0 (the
     weighted loss has no arithmetic for a negative target, so pos_weight implies the skipping); with neither it is the plain
     cx_bce_fwd_bwd, to which a negative target is a number like any other, as it is to torch's BCEWithLogitsLoss."""
+    kind = "bce"
 
     def __init__(self, pos_weight=None, ignore_negative=True):
         super().__init__()
         self.ignore_negative = bool(ignore_negative)
-        # a plain attribute like FusedNet.set_loss's: moved by hand (`.to` of the module leaves it), never in a state_dict
         self.pos_weight = None if pos_weight is None else torch.as_tensor(pos_weight, dtype=torch.float32).reshape(-1)
 
     @property
     def masked(self):
         return self.ignore_negative or self.pos_weight is not None
 
-    def _weight(self, device):
-        if self.pos_weight is not None and self.pos_weight.device != device:
-            self.pos_weight = self.pos_weight.to(device)
-        return self.pos_weight
-
-    def forward(self, logits, target):
-        return _MaskedBCEFn.apply(logits, target, self._weight(logits.device), self.masked)
-
-    @torch.no_grad()
-    def elementwise(self, logits, target):
-        """The (B, n) element losses (0 where ignored), outside autograd."""
-        x, t = _operands(logits, target)
-        out = torch.empty_like(x)
-        if self.masked:
-            ops.bce_masked_fwd_bwd(x, t, self._weight(x.device), None, out, None)
-        else:
-            ops.bce_fwd_bwd(x, t, None, out, None)
-        return out
+    def _state(self, logits):
+        self._on(logits.device, "pos_weight")
+        return Loss("bce", self.ignore_negative, pos_weight=self.pos_weight)
 
 
-class _AUCMFn(torch.autograd.Function):
-    """loss, d loss / d logits and the three auxiliary gradients in one launch; backward scales the stored gradients."""
-
-    @staticmethod
-    def forward(ctx, logits, target, a, b, alpha, prior, margin):
-        x, t = _operands(logits, target, "AUCMLoss", "cx_aucm_fwd_bwd")
-        aux = torch.stack([a.detach(), b.detach(), alpha.detach()]).float().contiguous()
-        loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        dl, daux = torch.empty_like(x), torch.empty_like(aux)
-        ops.aucm_fwd_bwd(x, t, prior, aux, margin, loss, None, dl, daux)
-        ctx.save_for_backward(dl, daux)
-        ctx.in_dtype = logits.dtype
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        dl, daux = ctx.saved_tensors
-        # alpha is the dual variable: the saddle point is a minimum in (w, a, b) and a maximum in alpha, so its gradient leaves
-        # negated and the optimiser that descends on every parameter ascends on alpha
-        return (dl * grad_output).to(ctx.in_dtype), None, daux[0] * grad_output, daux[1] * grad_output, -daux[2] * grad_output, None, None
-
-
-class AUCMLoss(nn.Module):
+class AUCMLoss(_LossModule):
     """The AUC min-max-margin loss (Yuan et al., "Large-scale Robust Deep AUC Maximization", ICCV 2021) of (B, n) logits, summed
     over the classes: the loss of FusedNet.set_loss(kind="aucm") for the autograd route, by the same kernel, so `loss.backward()`
     leaves the fused step's d loss / d logits bit for bit.  prior: n class positive rates in (0, 1); margin > 0.  A target < 0 is
@@ -110,26 +275,22 @@ class AUCMLoss(nn.Module):
     backward returns alpha's gradient NEGATED: `alpha.grad` is -d loss / d alpha, and a descending optimiser ascends on alpha.
     Call clamp_() after each optimiser step to keep alpha >= 0 (plain SGD with rate lr_aux followed by clamp_() is the update
     FusedNet.forward_backward makes).  There are no element losses: elementwise() raises."""
+    kind, _aux = "aucm", ("a", "b", "alpha")
 
     def __init__(self, prior, margin=1.0):
         super().__init__()
-        p = torch.as_tensor(prior, dtype=torch.float32).detach().reshape(-1).cpu()
-        if p.numel() < 1 or not bool(((p > 0) & (p < 1)).all()):
-            raise ValueError("AUCMLoss takes class priors in (0, 1) (got %s)" % p.tolist())
-        if not float(margin) > 0:
-            raise ValueError("AUCMLoss takes a margin > 0 (got %r)" % (margin,))
+        self.prior = check_prior("AUCMLoss", prior, margin)
         self.margin = float(margin)
-        self.prior = p                       # a plain attribute, moved by hand like MaskedBCE.pos_weight
-        self.a, self.b, self.alpha = (nn.Parameter(torch.zeros(p.numel())) for _ in range(3))
+        self.a, self.b, self.alpha = (nn.Parameter(torch.zeros(self.prior.numel())) for _ in range(3))
 
-    def forward(self, logits, target):
-        if self.prior.device != logits.device:
-            self.prior = self.prior.to(logits.device)
+    def _state(self, logits):
+        self._on(logits.device, "prior")
         if self.a.device != logits.device:
             raise RuntimeError("AUCMLoss: a, b and alpha are on %s, the logits on %s -- call loss.to(device)" % (self.a.device, logits.device))
-        if logits.dim() == 2 and logits.shape[1] != self.prior.numel():
+        if logits.shape[1] != self.prior.numel():
             raise RuntimeError("AUCMLoss holds %d classes, the logits have %d" % (self.prior.numel(), logits.shape[1]))
-        return _AUCMFn.apply(logits, target, self.a, self.b, self.alpha, self.prior, self.margin)
+        aux = torch.stack([self.a.detach(), self.b.detach(), self.alpha.detach()]).float().contiguous()
+        return Loss("aucm", True, self.margin, prior=self.prior, aux=aux, daux=torch.empty_like(aux))
 
     @torch.no_grad()
     def clamp_(self):
@@ -142,62 +303,18 @@ class AUCMLoss(nn.Module):
                            "against its negatives), not a sum over elements -- evaluate with MaskedBCE.elementwise or BCEWithLogitsLoss")
 
 
-class _FocusFn(torch.autograd.Function):
-    """loss and d loss / d logits in one launch (cx_asl_fwd_bwd); backward scales the stored gradient."""
-
-    @staticmethod
-    def forward(ctx, logits, target, pos_weight, focus, who):
-        x, t = _operands(logits, target, who, "cx_asl_fwd_bwd")
-        loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        dl = torch.empty_like(x)
-        ops.asl_fwd_bwd(x, t, pos_weight, focus, loss, None, dl)
-        ctx.save_for_backward(dl)
-        ctx.in_dtype = logits.dtype
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        dl, = ctx.saved_tensors
-        return (dl * grad_output).to(ctx.in_dtype), None, None, None, None
-
-
-class _FocusLoss(nn.Module):
+class _FocusLoss(_LossModule):
     """What FocalLoss and AsymmetricLoss share: the four numbers [gamma+, gamma-, clip, alpha or -1] the kernel reads from the device
-    (`focus`, a plain attribute like `pos_weight`, moved by hand), the autograd route and the element losses."""
+    (`focus`) and the positive-term weights (`pos_weight`)."""
 
     def __init__(self, focus, pos_weight):
         super().__init__()
-        gp, gn, m, al = (float(v) for v in focus)
-        who = type(self).__name__
-        if not (0 <= gp < float("inf") and 0 <= gn < float("inf")):
-            raise ValueError("%s takes finite exponents >= 0 (got %r, %r)" % (who, gp, gn))
-        if not 0 <= m < 1:
-            raise ValueError("%s takes a clip in [0, 1) (got %r)" % (who, m))
-        self.focus = torch.tensor([gp, gn, m, al], dtype=torch.float32)
-        self.pos_weight = None if pos_weight is None else torch.as_tensor(pos_weight, dtype=torch.float32).detach().reshape(-1)
-        if self.pos_weight is not None and not bool(((self.pos_weight > 0) & torch.isfinite(self.pos_weight)).all()):
-            raise ValueError("%s takes finite pos_weight > 0 (got %s)" % (who, self.pos_weight.tolist()))
+        self.focus = torch.tensor(focus, dtype=torch.float32)
+        self.pos_weight = check_pos_weight(type(self).__name__, pos_weight)
 
-    def _held(self, device):
-        if self.focus.device != device:
-            self.focus = self.focus.to(device)
-        if self.pos_weight is not None and self.pos_weight.device != device:
-            self.pos_weight = self.pos_weight.to(device)
-        return self.pos_weight, self.focus
-
-    def forward(self, logits, target):
-        _operands(logits, target, type(self).__name__, "cx_asl_fwd_bwd")      # (refuses a CPU tensor before anything is moved)
-        w, focus = self._held(logits.device)
-        return _FocusFn.apply(logits, target, w, focus, type(self).__name__)
-
-    @torch.no_grad()
-    def elementwise(self, logits, target):
-        """The (B, n) element losses (0 where ignored, and for a hard negative at or below the clip), outside autograd."""
-        x, t = _operands(logits, target, type(self).__name__, "cx_asl_fwd_bwd")
-        w, focus = self._held(x.device)
-        out = torch.empty_like(x)
-        ops.asl_fwd_bwd(x, t, w, focus, None, out, None)
-        return out
+    def _state(self, logits):
+        self._on(logits.device, "focus", "pos_weight")
+        return Loss(self.kind, True, pos_weight=self.pos_weight, focus=self.focus)
 
 
 class FocalLoss(_FocusLoss):
@@ -206,11 +323,10 @@ class FocalLoss(_FocusLoss):
     batch size), soft targets valid, pos_weight on the positive term -- the loss of FusedNet.set_loss(kind="focal") for the autograd
     route, by the same kernel, so `loss.backward()` leaves the fused step's d loss / d logits bit for bit.  gamma >= 0; alpha None
     (no class balance) or in (0, 1).  The focusing weight is differentiated, not detached."""
+    kind = "focal"
 
     def __init__(self, gamma=2.0, alpha=None, pos_weight=None):
-        if alpha is not None and not 0 < float(alpha) < 1:
-            raise ValueError("FocalLoss takes alpha None or in (0, 1) (got %r)" % (alpha,))
-        super().__init__([gamma, gamma, 0.0, -1.0 if alpha is None else alpha], pos_weight)
+        super().__init__(check_focus("FocalLoss", gamma, gamma, 0.0, alpha, ("gamma", "gamma")), pos_weight)
 
 
 class AsymmetricLoss(_FocusLoss):
@@ -219,6 +335,7 @@ class AsymmetricLoss(_FocusLoss):
     -(1 - p)^gamma_pos log p, negatives -p_m^gamma_neg log(1 - p_m) with p_m = max(p - clip, 0), so a hard negative with p <= clip
     adds no loss and no gradient.  A target < 0 is ignored; pos_weight weights the positive term.  The loss of
     FusedNet.set_loss(kind="asl") for the autograd route, by the same kernel, bit for bit."""
+    kind = "asl"
 
     def __init__(self, gamma_pos=0.0, gamma_neg=4.0, clip=0.05, pos_weight=None):
-        super().__init__([gamma_pos, gamma_neg, clip, -1.0], pos_weight)
+        super().__init__(check_focus("AsymmetricLoss", gamma_pos, gamma_neg, clip, None), pos_weight)

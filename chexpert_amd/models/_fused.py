@@ -9,6 +9,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import CxPackDesc
+from ..loss import Loss
 
 
 # --------------------------------------------------------------------------------------------- input gradient (x.grad)
@@ -115,15 +116,9 @@ class FusedNet(nn.Module):
         super().__init__()
         self._nbt_pending = 0            # training forwards not yet counted in the BatchNorms' num_batches_tracked
         self._engine = None
-        # set_loss(): plain tensors / flags, not buffers (the state_dict keys stay what they are)
-        self.loss_ignore_negative, self.loss_pos_weight, self._pos_weight_store = False, None, None
-        # set_loss(kind="aucm"): the auxiliary scalars (3, n), the class priors (n,), the one-float rate of their update (device
-        # tensors the kernels read) and the margin (a host float, passed by value)
-        self.loss_kind, self.loss_margin = "bce", 1.0
-        self.loss_aux = self.loss_prior = self.loss_lr_aux = self._loss_daux = None
-        self._aucm_store = None
-        # set_loss(kind="focal" | "asl"): [gamma+, gamma-, clip, alpha or -1], one fp32 device tensor the kernel reads
-        self.loss_focus = self._focus_store = None
+        # set_loss(): plain tensors / flags, not buffers (the state_dict keys stay what they are); read through loss_kind,
+        # loss_pos_weight, ... below
+        self._loss = Loss()
 
     def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
                  alpha=None, gamma_pos=None, gamma_neg=None, clip=None):
@@ -168,158 +163,32 @@ class FusedNet(nn.Module):
         set_loss with the same kind and new numbers -- is seen by the next replay, so a gamma schedule needs none.  The
         data-parallel step needs nothing new (the sum over elements is averaged over the ranks like the cross-entropy's).  An
         operand out of range, or a keyword of another kind, is a ValueError that changes nothing."""
-        if kind not in ("bce", "aucm", "focal", "asl"):
-            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal' or 'asl' (got %r)" % (kind,))
-        if kind != "aucm" and (prior is not None or lr_aux is not None or margin != 1.0):
-            raise ValueError("set_loss: prior, margin and lr_aux belong to kind='aucm'")
-        if kind != "focal" and (gamma is not None or alpha is not None):
-            raise ValueError("set_loss: gamma and alpha belong to kind='focal'")
-        if kind != "asl" and (gamma_pos is not None or gamma_neg is not None or clip is not None):
-            raise ValueError("set_loss: gamma_pos, gamma_neg and clip belong to kind='asl'")
-        if kind == "aucm":
-            if pos_weight is not None:
-                raise ValueError("set_loss(kind='aucm') cannot be combined with pos_weight: the class prior is this loss's weighting")
-            self._set_aucm(prior, margin, lr_aux)
-            self.loss_pos_weight, self.loss_ignore_negative, self.loss_kind, self.loss_focus = None, True, "aucm", None
-            return self
-        if kind == "focal":
-            g = 2.0 if gamma is None else gamma
-            if alpha is not None and not 0 < float(alpha) < 1:
-                raise ValueError("set_loss(kind='focal') takes alpha None or in (0, 1) (got %r)" % (alpha,))
-            return self._set_focus("focal", [g, g, 0.0, -1.0 if alpha is None else alpha], pos_weight)
-        if kind == "asl":
-            return self._set_focus("asl", [0.0 if gamma_pos is None else gamma_pos, 4.0 if gamma_neg is None else gamma_neg,
-                                           0.05 if clip is None else clip, -1.0], pos_weight)
-        self.loss_kind = "bce"
-        self.loss_aux = self.loss_prior = self.loss_lr_aux = self._loss_daux = self.loss_focus = None      # (the storage itself is kept)
-        self.loss_pos_weight = self._hold_pos_weight(pos_weight)
-        self.loss_ignore_negative = bool(ignore_negative)
-        return self
-
-    def _hold_pos_weight(self, pos_weight):
-        """pos_weight copied into the held device storage (made anew for another number of weights or another device); None: None."""
-        if pos_weight is None:
-            return None
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("set_loss(pos_weight=...) holds the weights on the parameters' device: call model.to(device) first")
-        w = torch.as_tensor(pos_weight, dtype=torch.float32).reshape(-1)
-        held = self._pos_weight_store
-        if held is None or held.numel() != w.numel() or held.device != dev:
-            held = self._pos_weight_store = torch.empty(w.numel(), dtype=torch.float32, device=dev)
-        held.copy_(w)
-        return held
-
-    def _set_focus(self, kind, focus, pos_weight):
-        """Checks the four numbers [gamma+, gamma-, clip, alpha or a negative number for none] and the weights of
-        set_loss(kind="focal" | "asl") (ValueError; nothing is changed when one is refused) and copies them into the held device
-        storage.  Returns self."""
-        try:
-            gp, gn, m, al = (float(v) for v in focus)
-        except (TypeError, ValueError):
-            raise ValueError("set_loss(kind=%r) takes numbers (got %r)" % (kind, focus))
-        names = ("gamma", "gamma") if kind == "focal" else ("gamma_pos", "gamma_neg")
-        for name, v in zip(names, (gp, gn)):
-            if not (v >= 0 and v < float("inf")):
-                raise ValueError("set_loss(kind=%r) takes a finite %s >= 0 (got %r)" % (kind, name, v))
-        if not 0 <= m < 1:
-            raise ValueError("set_loss(kind=%r) takes a clip in [0, 1) (got %r)" % (kind, m))
-        if not (al < 0 or 0 < al < 1):            # (NaN fails both)
-            raise ValueError("set_loss(kind=%r) takes alpha None or in (0, 1) (got %r)" % (kind, al))
-        al = -1.0 if al < 0 else al
-        if pos_weight is not None:
-            w = torch.as_tensor(pos_weight, dtype=torch.float32).detach().reshape(-1).cpu()
-            n = self._n_classes()
-            if w.numel() != n or not bool(((w > 0) & torch.isfinite(w)).all()):
-                raise ValueError("set_loss(kind=%r) takes %d finite pos_weight > 0 (got %s)" % (kind, n, w.tolist()))
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("set_loss(kind=%r) holds its state on the parameters' device: call model.to(device) first" % kind)
-        held = self._focus_store
-        if held is None or held.device != dev:
-            held = self._focus_store = torch.empty(4, dtype=torch.float32, device=dev)
-        held.copy_(torch.tensor([gp, gn, m, al], dtype=torch.float32))
-        self.loss_pos_weight = self._hold_pos_weight(pos_weight)
-        self.loss_aux = self.loss_prior = self.loss_lr_aux = self._loss_daux = None
-        self.loss_kind, self.loss_ignore_negative, self.loss_focus = kind, True, held
+        self._loss.set(next(self.parameters()).device, self._n_classes(), ignore_negative, pos_weight, kind=kind, prior=prior,
+                       margin=margin, lr_aux=lr_aux, gamma=gamma, alpha=alpha, gamma_pos=gamma_pos, gamma_neg=gamma_neg, clip=clip)
         return self
 
     def _n_classes(self):
         """Width of the final Linear layer (the classifier of every family)."""
         return [m for m in self.modules() if isinstance(m, nn.Linear)][-1].out_features
 
-    def _set_aucm(self, prior, margin, lr_aux):
-        """Checks the operands of set_loss(kind="aucm") (ValueError; nothing is changed when one is refused) and puts them into the
-        held device storage, which is made anew -- with loss_aux = 0 -- when there is none for this number of classes."""
-        n = self._n_classes()
-        if prior is None:
-            raise ValueError("set_loss(kind='aucm') needs prior: the %d class positive rates" % n)
-        p = torch.as_tensor(prior, dtype=torch.float32).detach().reshape(-1).cpu()
-        if p.numel() != n:
-            raise ValueError("set_loss(kind='aucm') takes one prior per class: %d (got %d)" % (n, p.numel()))
-        if not bool(((p > 0) & (p < 1)).all()):
-            raise ValueError("set_loss(kind='aucm') takes priors in (0, 1) (got %s)" % p.tolist())
-        if not float(margin) > 0:
-            raise ValueError("set_loss(kind='aucm') takes a margin > 0 (got %r)" % (margin,))
-        if lr_aux is None or not float(lr_aux) > 0:
-            raise ValueError("set_loss(kind='aucm') needs lr_aux > 0, the rate of the auxiliary scalars (got %r)" % (lr_aux,))
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("set_loss(kind='aucm') holds its state on the parameters' device: call model.to(device) first")
-        held = self._aucm_store
-        fresh = held is None or held["prior"].numel() != n or held["prior"].device != dev
-        if fresh:
-            held = self._aucm_store = {"aux": torch.zeros(3, n, dtype=torch.float32, device=dev),
-                                       "daux": torch.zeros(3, n, dtype=torch.float32, device=dev),
-                                       "prior": torch.empty(n, dtype=torch.float32, device=dev),
-                                       "lr_aux": torch.empty(1, dtype=torch.float32, device=dev)}
-        elif self.loss_kind != "aucm":
-            held["aux"].zero_()
-        held["prior"].copy_(p)
-        held["lr_aux"].fill_(float(lr_aux))
-        self.loss_aux, self._loss_daux, self.loss_prior, self.loss_lr_aux = held["aux"], held["daux"], held["prior"], held["lr_aux"]
-        self.loss_margin = float(margin)
-
     def loss_state(self):
         """What set_loss(kind=...) holds beyond the model's state_dict, as CPU tensors and floats: {kind, aux, prior, margin, lr_aux}
         (aux, prior and lr_aux are None for kind 'bce').  Kinds 'focal' and 'asl' add `focus`, the four numbers of `loss_focus`.  A
         checkpoint keeps it beside the weights."""
-        if self.loss_kind in ("focal", "asl"):
-            return {"kind": self.loss_kind, "focus": self.loss_focus.detach().cpu().clone(), "aux": None, "prior": None,
-                    "margin": float(self.loss_margin), "lr_aux": None}
-        if self.loss_kind != "aucm":
-            return {"kind": self.loss_kind, "aux": None, "prior": None, "margin": float(self.loss_margin), "lr_aux": None}
-        return {"kind": "aucm", "aux": self.loss_aux.detach().cpu().clone(), "prior": self.loss_prior.detach().cpu().clone(),
-                "margin": float(self.loss_margin), "lr_aux": float(self.loss_lr_aux.item())}
+        return self._loss.state()
 
     def load_loss_state(self, d):
         """Restores loss_state(): for kind 'aucm' the loss is set with the stored prior, margin and rate, and the auxiliary scalars
         are copied in (into the held storage when there is one for this number of classes).  Kind 'bce' leaves the options of
         the cross-entropy (ignore_negative, pos_weight) as they are.  Kinds 'focal' and 'asl' set the loss with the stored `focus`
         (checked like set_loss's operands) and keep the pos_weight the model holds.  Returns self."""
-        if d["kind"] in ("focal", "asl"):
-            focus = d.get("focus")
-            if focus is None or torch.as_tensor(focus).numel() != 4:
-                raise ValueError("load_loss_state: kind %r needs focus, four numbers (got %r)" % (d["kind"], focus))
-            w = self.loss_pos_weight.clone() if self.loss_pos_weight is not None else None
-            return self._set_focus(d["kind"], torch.as_tensor(focus, dtype=torch.float32).reshape(-1).tolist(), w)
-        if d["kind"] != "aucm":
-            if d["kind"] != "bce":
-                raise ValueError("load_loss_state: unknown loss kind %r" % (d["kind"],))
-            if self.loss_kind != "bce":
-                self.set_loss()
-            return self
-        aux = torch.as_tensor(d["aux"], dtype=torch.float32)
-        if tuple(aux.shape) != (3, self._n_classes()):
-            raise ValueError("load_loss_state: aux must be (3, %d) (got %s)" % (self._n_classes(), tuple(aux.shape)))
-        self.set_loss(kind="aucm", prior=d["prior"], margin=d["margin"], lr_aux=d["lr_aux"])
-        self.loss_aux.copy_(aux)
+        self._loss.load_state(d, next(self.parameters()).device, self._n_classes())
         return self
 
     def loss_step_state(self):
         """The tensors beyond parameters and buffers that a train-mode forward_backward changes (a graph capture's warm-up steps
         really run: it puts them back).  The focal and asymmetric losses change nothing per step."""
-        return [self.loss_aux] if self.loss_kind == "aucm" else []
+        return self._loss.step_state()
 
     def storage_dtype(self, dtype):
         """Storage type of the activations inside the fused schedule: torch.bfloat16 (default: bf16 tensors, fp32 accumulation
@@ -370,26 +239,25 @@ class FusedNet(nn.Module):
         eng = self._eng()
         if input_grad is not None:
             check_input_grad(input_grad, x)
-        if self.loss_kind == "aucm":
+        L = self._loss
+        if L.kind == "aucm":
             check_aucm_single_process(eng.reducer)
         ws = eng.forward(x, self.training, record=True)
         B, n = ws.logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
-        if self.loss_kind == "aucm":                                           # set_loss(kind="aucm"): one launch, as the others
-            ops.aucm_fwd_bwd(ws.logits, target, self.loss_prior, self.loss_aux, self.loss_margin, loss, None, dl, self._loss_daux)
-        elif self.loss_kind in ("focal", "asl"):                               # set_loss(kind="focal" | "asl"): one launch again
-            ops.asl_fwd_bwd(ws.logits, target, self.loss_pos_weight, self.loss_focus, loss, None, dl)
-        elif self.loss_ignore_negative or self.loss_pos_weight is not None:    # set_loss(): ignored labels / class weights
-            ops.bce_masked_fwd_bwd(ws.logits, target, self.loss_pos_weight, loss, None, dl)
-        else:
-            ops.bce_fwd_bwd(ws.logits, target, loss, None, dl)
+        L.launch(ws.logits, target, loss, None, dl)                            # one launch, whatever set_loss chose
         eng.backward(ws, dl, dx=input_grad)
-        if self.loss_kind == "aucm" and self.training:                         # from this step's gradients; eval leaves them alone
-            ops.aucm_aux_step(self.loss_aux, self._loss_daux, self.loss_lr_aux)
+        if L.kind == "aucm" and self.training:                                 # from this step's gradients; eval leaves them alone
+            ops.aucm_aux_step(L.aux, L.daux, L.lr_aux)
         logits = ws.logits.clone()
         eng.release(ws)
         return loss, logits
+
+
+# what set_loss holds, readable on the model (read-only: set_loss writes; a tensor may be written in place)
+for _name in ("kind", "ignore_negative", "pos_weight", "margin", "aux", "prior", "lr_aux", "focus", "daux"):
+    setattr(FusedNet, ("_loss_" if _name == "daux" else "loss_") + _name, property(lambda self, _name=_name: getattr(self._loss, _name)))
 
 
 # --------------------------------------------------------------------------------------------- engine side

@@ -636,17 +636,26 @@ def bce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):
                                stream_ptr()), "cx_bce_fwd_bwd")
 
 
+def _loss_operands(logits, target, vectors=(), loss=None, outputs=()):
+    """The operands the loss wrappers share (AssertionError): contiguous fp32 (B, n) logits and targets, optional per-class `vectors`
+    (n,), an optional one-float `loss` and optional (B, n) `outputs`, every one on the logits' device.  Returns (B, n).  Where
+    require_cuda stands beside it is each wrapper's own: it decides which of the two errors a call that earns both gets."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    B, n = logits.shape
+    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (B, n)
+    assert all(v is None or tuple(v.shape) == (n,) for v in vectors)
+    assert all(o is None or tuple(o.shape) == (B, n) for o in outputs)
+    assert all(t is None or t.device == logits.device for t in (target, loss, *vectors, *outputs))
+    _f32(loss, n=1)
+    _f32(*vectors, *outputs)
+    return B, n
+
+
 def bce_masked_fwd_bwd(logits, target, pos_weight, loss, loss_elem, dlogits, grad_scale=1.0):
     """bce_fwd_bwd in which a target < 0 is ignored (no loss, no gradient; the divisor stays B) and pos_weight (fp32 (n,), or None)
     weights the positive term per class as torch's BCEWithLogitsLoss(pos_weight) does.  loss, loss_elem and dlogits are optional."""
     require_cuda(logits, target, pos_weight, loss, loss_elem, dlogits)
-    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
-    B, n = logits.shape
-    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (B, n) and target.device == logits.device
-    assert pos_weight is None or (tuple(pos_weight.shape) == (n,) and pos_weight.device == logits.device)
-    _f32(pos_weight, n=n)
-    _f32(loss, n=1)
-    _f32(loss_elem, dlogits, n=B * n)
+    B, n = _loss_operands(logits, target, (pos_weight,), loss, (loss_elem, dlogits))
     check(lib().cx_bce_masked_fwd_bwd(ptr(logits), ptr(target), ptr(pos_weight), ptr(loss), ptr(loss_elem), ptr(dlogits), grad_scale,
                                       B, n, stream_ptr()), "cx_bce_masked_fwd_bwd")
 
@@ -656,16 +665,11 @@ def aucm_fwd_bwd(logits, target, prior, aux, margin, loss, loss_class, dlogits, 
     aux fp32 (3, n) = rows a, b, alpha, margin > 0; a target < 0 is ignored, t >= 0.5 is a positive.  loss (1,), loss_class (n,),
     dlogits (B, n) and daux (3, n) are optional; grad_scale multiplies dlogits alone."""
     require_cuda(logits, target, prior, aux, loss, loss_class, dlogits, daux)
-    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
-    B, n = logits.shape
-    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (B, n) and target.device == logits.device
-    assert tuple(prior.shape) == (n,) and tuple(aux.shape) == (3, n) and (daux is None or tuple(daux.shape) == (3, n))
-    assert all(t is None or t.device == logits.device for t in (prior, aux, loss, loss_class, dlogits, daux))
-    _f32(prior, loss_class, n=n)
-    _f32(aux, daux, n=3 * n)
-    _f32(loss, n=1)
-    _f32(dlogits, n=B * n)
-    assert dlogits is None or tuple(dlogits.shape) == (B, n)
+    assert prior is not None
+    B, n = _loss_operands(logits, target, (prior, loss_class), loss, (dlogits,))
+    assert tuple(aux.shape) == (3, n) and (daux is None or tuple(daux.shape) == (3, n))
+    assert aux.device == logits.device and (daux is None or daux.device == logits.device)
+    _f32(aux, daux)
     check(lib().cx_aucm_fwd_bwd(ptr(logits), ptr(target), ptr(prior), ptr(aux), float(margin), ptr(loss), ptr(loss_class), ptr(dlogits),
                                 ptr(daux), grad_scale, B, n, stream_ptr()), "cx_aucm_fwd_bwd")
 
@@ -686,17 +690,9 @@ def asl_fwd_bwd(logits, target, pos_weight, focus, loss, loss_elem, dlogits, gra
     DEVICE tensor [gamma+, gamma-, clip, alpha or -1], read by the kernel (a captured step sees a changed value); a target < 0 is
     ignored, pos_weight (fp32 (n,), or None) weights the positive term.  loss (1,), loss_elem and dlogits (B, n) are optional;
     grad_scale multiplies dlogits alone."""
-    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
-    B, n = logits.shape
-    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (B, n) and target.device == logits.device
-    assert pos_weight is None or tuple(pos_weight.shape) == (n,)
-    assert focus is not None and tuple(focus.shape) == (4,)
-    assert all(t is None or t.device == logits.device for t in (pos_weight, focus, loss, loss_elem, dlogits))
-    assert all(t is None or tuple(t.shape) == (B, n) for t in (loss_elem, dlogits))
-    _f32(pos_weight, n=n)
-    _f32(focus, n=4)
-    _f32(loss, n=1)
-    _f32(loss_elem, dlogits, n=B * n)
+    B, n = _loss_operands(logits, target, (pos_weight,), loss, (loss_elem, dlogits))
+    assert focus is not None and tuple(focus.shape) == (4,) and focus.device == logits.device
+    _f32(focus)
     require_cuda(logits, target, pos_weight, focus, loss, loss_elem, dlogits)
     check(lib().cx_asl_fwd_bwd(ptr(logits), ptr(target), ptr(pos_weight), ptr(focus), ptr(loss), ptr(loss_elem), ptr(dlogits), grad_scale,
                                B, n, stream_ptr()), "cx_asl_fwd_bwd")

@@ -358,7 +358,7 @@ int cx_bce_fwd_bwd(const float* logits, const float* target, float* loss, float*
  * of ABI 10 (no struct changed).                                                                                               */
 int cx_bce_masked_fwd_bwd(const float* logits, const float* target, const float* pos_weight, float* loss, float* loss_elem,
                           float* dlogits, float grad_scale, int B, int n_classes, void* stream);
-/* AUC min-max-margin loss (Yuan et al., ICCV 2021) with its gradients, one launch (aucm.hip).  Per class c, over the batch rows i, with
+/* AUC min-max-margin loss (Yuan et al., ICCV 2021) with its gradients, one launch (loss.hip).  Per class c, over the batch rows i, with
  * x = logits[i][c], y = sigmoid(x), t = target[i][c], p = prior[c] in (0, 1), m = margin > 0, (a, b, alpha) = aux[0][c], aux[1][c],
  * aux[2][c]; a row is live when t >= 0 (t < 0 is ignored as in cx_bce_masked_fwd_bwd), positive (P) when live and t >= 0.5, negative
  * (N) when live and t < 0.5, L = number of live rows:
@@ -377,7 +377,7 @@ int cx_aucm_fwd_bwd(const float* logits, const float* target, const float* prior
 /* primal descent on a and b, dual ascent on alpha, from the gradients of the same step: a -= lr da, b -= lr db,
  * alpha = max(0, alpha + lr dalpha), lr = *lr_aux_dev (a device float: a captured step sees a changed rate).                      */
 int cx_aucm_aux_step(float* aux, const float* daux, const float* lr_aux_dev, int n_classes, void* stream);
-/* Focal loss (Lin et al., ICCV 2017) and asymmetric loss (Ridnik et al., ICCV 2021) with d loss / d logits, one launch (focal.hip).
+/* Focal loss (Lin et al., ICCV 2017) and asymmetric loss (Ridnik et al., ICCV 2021) with d loss / d logits, one launch (loss.hip).
  * focus: FOUR floats ON THE DEVICE, [gamma+ >= 0, gamma- >= 0, clip m in [0, 1), alpha in (0, 1) or a negative number for "none"];
  * the kernel reads them from memory, so a captured step sees a change made in place.  Per element, x = logits[b][c],
  * t = target[b][c], w = pos_weight ? pos_weight[c] : 1, p = sigmoid(x), q = sigmoid(-x), p_m = max(p - m, 0), p_n = min(q + m, 1):

@@ -94,7 +94,7 @@ def test_aucm_symbols_match_the_header():
         assert hasattr(_lib.lib(), name)
     assert _lib.lib().cx_abi_version() == 10                           # additive entry points
     mk = open(os.path.join(ROOT, "chexpert_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^SRCS\s*=.*\baucm\.hip\b", mk, flags=re.M)
+    assert re.search(r"^SRCS\s*=.*\bloss\.hip\b", mk, flags=re.M)
 
 
 def test_entry_points_validate_without_launching():

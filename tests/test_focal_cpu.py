@@ -154,7 +154,7 @@ def test_asl_symbol_matches_the_header():
     assert hasattr(_lib.lib(), "cx_asl_fwd_bwd")
     assert _lib.lib().cx_abi_version() == 10                           # an additive entry point
     mk = open(os.path.join(ROOT, "chexpert_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^SRCS\s*=.*\bfocal\.hip\b", mk, flags=re.M)
+    assert re.search(r"^SRCS\s*=.*\bloss\.hip\b", mk, flags=re.M)
     assert "cx_asl_fwd_bwd" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
 
 

@@ -321,6 +321,68 @@ def test_eval_mode_step_with_input_grad(dev):
     assert torch.equal(lb.detach(), loss.reshape(())) and torch.equal(xb.grad, buf)
 
 
+def test_set_loss_walk_leaves_nothing_of_the_previous_kind(dev):
+    """set_loss walked across the kinds, twice: plain -> ignore_negative -> pos_weight -> focal(pos_weight) -> aucm -> asl (no
+    weights) -> pos_weight only -> plain.  After every move the public attributes are the documented ones (None where the kind
+    has none; the margin is passed by value to 'aucm' alone and stays what the last 'aucm' made it), the step's loss and
+    d loss / d logits are those of the matching loss module on the same logits, bit for bit, and the held storage of a second visit
+    is that of the first."""
+    from chexpert_amd.loss import AsymmetricLoss, AUCMLoss, FocalLoss, MaskedBCE
+    model, S = _net("densenet", dev)
+    B, n = 2, 5
+    x = synth.xray_batch(1700, B, S).to(dev)
+    t = _targets(1710, B, n, ignored=0.3).to(dev)
+    assert (t < 0).any() and (t >= 0).any()
+    w1, w2, w3 = (synth.uniform(1720 + i, (n,), 0.5, 8.0) for i in range(3))
+    prior = synth.uniform(1730, (n,), 0.1, 0.9)
+    zeros = torch.zeros(3, n)
+    f32 = lambda *v: torch.tensor(v, dtype=torch.float32)                                                     # noqa: E731
+    # (name, set_loss keywords, the loss module, then what the model must hold: ignore_negative, pos_weight, aux, prior, lr_aux, focus)
+    walk = [("bce", {}, lambda: MaskedBCE(ignore_negative=False), False, None, None, None, None, None),
+            ("bce", dict(ignore_negative=True), lambda: MaskedBCE(), True, None, None, None, None, None),
+            ("bce", dict(pos_weight=w1), lambda: MaskedBCE(w1, ignore_negative=False), False, w1, None, None, None, None),
+            ("focal", dict(kind="focal", gamma=1.5, alpha=0.25, pos_weight=w2), lambda: FocalLoss(1.5, 0.25, pos_weight=w2),
+             True, w2, None, None, None, f32(1.5, 1.5, 0.0, 0.25)),
+            ("aucm", dict(kind="aucm", prior=prior, margin=0.7, lr_aux=0.05), lambda: AUCMLoss(prior, 0.7).to(dev),
+             True, None, zeros, prior, f32(0.05), None),
+            ("asl", dict(kind="asl"), lambda: AsymmetricLoss(), True, None, None, None, None, f32(0.0, 4.0, 0.05, -1.0)),
+            ("bce", dict(pos_weight=w3), lambda: MaskedBCE(w3, ignore_negative=False), False, w3, None, None, None, None),
+            ("bce", {}, lambda: MaskedBCE(ignore_negative=False), False, None, None, None, None, None)]
+    eng, seen, ptrs = model._eng(), [], {}
+    backward = eng.backward
+
+    def spy(ws, dl, dx=None):                                           # d loss / d logits, as the step hands it to the backward pass
+        seen.append(dl.clone())
+        return backward(ws, dl, dx=dx)
+    eng.backward = spy
+    margin = 1.0
+    for visit in range(2):
+        for kind, kw, make, ign, w, aux, pr, lr, focus in walk:
+            assert model.set_loss(**kw) is model
+            margin = kw.get("margin", margin)
+            assert (model.loss_kind, model.loss_ignore_negative, model.loss_margin) == (kind, ign, margin), (visit, kw)
+            for name, want in (("loss_pos_weight", w), ("loss_aux", aux), ("loss_prior", pr), ("loss_lr_aux", lr), ("loss_focus", focus),
+                               ("_loss_daux", aux)):
+                got = getattr(model, name)
+                assert (got is None) == (want is None), (visit, kw, name)
+                if got is not None:
+                    assert got.is_cuda and got.dtype == torch.float32 and tuple(got.shape) == tuple(want.shape), (visit, kw, name)
+                    assert name == "_loss_daux" or torch.equal(got.cpu(), want), (visit, kw, name)
+                    assert ptrs.setdefault(name, got.data_ptr()) == got.data_ptr(), (visit, kw, name)
+            assert model.loss_state()["kind"] == kind and model.loss_step_state() == ([model.loss_aux] if kind == "aucm" else [])
+            model.zero_grad(set_to_none=True)
+            loss, logits = model.forward_backward(x, t)
+            crit = make()
+            xl = logits.clone().requires_grad_(True)
+            lm = crit(xl, t)
+            lm.backward()
+            assert torch.equal(lm.detach(), loss.reshape(())) and torch.equal(xl.grad, seen[-1]), (visit, kw)
+            assert math.isfinite(loss.item()) and float(seen[-1].abs().max()) > 0
+            if kind == "aucm":                                          # the train-mode step has moved the scalars: a later kind must not see them
+                assert float(model.loss_aux.abs().max()) > 0
+    assert len(seen) == 2 * len(walk) and set(ptrs) == {"loss_pos_weight", "loss_aux", "loss_prior", "loss_lr_aux", "loss_focus", "_loss_daux"}
+
+
 def _eager_dev_step(model, opt, x, t):
     """The step GraphedTrainStep captures, launched one by one (the command line's partial-minibatch step)."""
     opt.zero_grad()
