@@ -15,8 +15,7 @@ from . import ops
 def _targets(model, eng, ws, dev):
     """(hooked module, final Linear, feature buffer, scale, shift, ReLU'd-in-place-after-the-hook?) of the reference's hook pairs."""
     if hasattr(model, "features"):                               # DenseNet: norm5 output, ReLU'd in place by the model (:514)
-        nt = eng.slots["nt"][len(eng.blocks) - 1]
-        return model.features.norm5, model.classifier, ws.buf[-1], ws.v(nt[0]), ws.v(nt[1]), True
+        return (model.features.norm5, model.classifier) + eng.norm5_operands(ws) + (True,)
     if hasattr(model, "_stages"):                                # ResNet / WideResNet: output of the last stage (already post-ReLU)
         return model._stages()[-1], model.fc, ws.blk[-1]["out"], None, None, False
     if hasattr(model, "head"):                                   # EfficientNet: head[1] BatchNorm output, before Swish
@@ -99,9 +98,7 @@ def grad_cam(model, x, hooks=None, cls_idx=None):
     try:
         dev = x.device
         if hasattr(model, "features"):                               # DenseNet: relu(norm5(block-4 buffer))
-            buf = ws.buf[-1]
-            nt = eng.slots["nt"][len(eng.blocks) - 1]
-            sc, sh, inner = ws.v(nt[0]), ws.v(nt[1]), 1
+            (buf, sc, sh), inner = eng.norm5_operands(ws), 1
         elif hasattr(model, "_stages"):                              # ResNet: output of the last stage (post-ReLU, no BN in between)
             buf = ws.blk[-1]["out"]
             C_ = buf.shape[3]
@@ -142,8 +139,7 @@ def cam_source(model):
 def _cam_operands(model, eng, ws):
     """(feature buffer, scale, shift) of A = act(buffer * scale + shift) in the workspace of an eval forward."""
     if hasattr(model, "features"):
-        nt = eng.slots["nt"][len(eng.blocks) - 1]
-        return ws.buf[-1], ws.v(nt[0]), ws.v(nt[1])
+        return eng.norm5_operands(ws)
     if hasattr(model, "_stages"):
         return ws.blk[-1]["out"], None, None
     S = eng.bn[id(model.head[1])]

@@ -441,6 +441,14 @@ class FusedEngine:
         ops.bn_bwd_coef_eval(S1, S2, mean, rstd, bn.running_mean[lo:lo + Cn], bn.running_var[lo:lo + Cn], gamma, bn.eps, dgamma,
                              dbeta, pa, pb, pc, Cn, replicas=replicas, rstride=rstride, q=q)
 
+    @staticmethod
+    def _bn_train(bn):
+        """(gamma, beta, eps, momentum, running mean, running var) of a training BatchNorm as the coefficient kernels take them:
+        momentum None counts as 0.1, the running buffers are None when the module tracks none."""
+        track = bn.track_running_stats
+        return (bn.weight, bn.bias, bn.eps, bn.momentum if bn.momentum is not None else 0.1,
+                bn.running_mean if track else None, bn.running_var if track else None)
+
     # ---- BatchNorm coefficients of an engine that keeps its _BN slots in `self.bn` ({id(bn): _BN}) and, in deterministic mode,
     # its statistic rows in ws.slab[0] / ws.slab[1] (ResNet, EfficientNet)
     def _bn_coef(self, ws, bn, count, train, rows=None):
@@ -449,10 +457,9 @@ class FusedEngine:
         statistics."""
         S, v = self.bn[id(bn)], self._v
         if train:
-            mom = bn.momentum if bn.momentum is not None else 0.1
             ssum, ssq, reps, rstride = (ws.slab[0], ws.slab[1], rows, S.C) if self.det else (v(ws, S.sum), v(ws, S.sq), 1, 0)
-            ops.bn_coef(ssum, ssq, count, bn.weight, bn.bias, bn.eps, mom, bn.running_mean, bn.running_var,
-                        v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), S.C, replicas=reps, rstride=rstride)
+            ops.bn_coef(ssum, ssq, count, *self._bn_train(bn), v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), S.C,
+                        replicas=reps, rstride=rstride)
         else:
             ops.bn_coef_eval(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, v(ws, S.sc), v(ws, S.sh), v(ws, S.mean),
                              v(ws, S.rstd), S.C)
@@ -468,6 +475,30 @@ class FusedEngine:
     def _v(ws, slot, n=None):
         off, m = slot
         return ws.vec[off:off + (m if n is None else n)]
+
+    # ---- operand keywords of the convolutions around a BatchNorm whose record S names its vectors (sc, sh, pa, pb, pc: a _BN,
+    # or an engine's own record with these fields); c_: the channel range of a grouped convolution
+    @staticmethod
+    def _ch(t, c_):
+        return t if c_ is None else t[..., c_]
+
+    def _pro_bnrelu(self, ws, S, c_=None):
+        """forward: relu(bn_S(.)) of the operand"""
+        return dict(prologue=ops.PRO_AFFINE_RELU, pa=self._ch(self._v(ws, S.sc), c_), pb=self._ch(self._v(ws, S.sh), c_))
+
+    def _x_bnrelu(self, ws, S, c_=None):
+        """weight gradient: relu(bn_S(.)) of the activation operand"""
+        return dict(x_prologue=ops.PRO_AFFINE_RELU, pa=self._ch(self._v(ws, S.sc), c_), pb=self._ch(self._v(ws, S.sh), c_))
+
+    def _pro_bnbwd(self, ws, y, S, c_=None):
+        """input gradient: BatchNorm S's backward of the gradient operand, dY = dz * pa + y * pb + pc"""
+        ch, v = self._ch, self._v
+        return dict(prologue=ops.PRO_AFFINE2, x2=ch(y, c_), pa=ch(v(ws, S.pa), c_), pb=ch(v(ws, S.pb), c_), pc=ch(v(ws, S.pc), c_))
+
+    def _g_bnbwd(self, ws, y, S, c_=None):
+        """weight gradient: the same of its gradient operand"""
+        ch, v = self._ch, self._v
+        return dict(g_prologue=ops.PRO_AFFINE2, g2=ch(y, c_), ga=ch(v(ws, S.pa), c_), gb=ch(v(ws, S.pb), c_), gc=ch(v(ws, S.pc), c_))
 
     # ---- workspaces
     def acquire(self, B, H, W):

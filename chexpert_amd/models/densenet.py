@@ -243,10 +243,6 @@ class _Workspace:
         # coefficient kernel that follows on the same stream sums them in row order
         self.slab = torch.empty(2, eng.SLAB, dtype=torch.float32, device=dev) if eng.det else None
 
-    def v(self, slot):
-        off, n = slot
-        return self.vec[off:off + n]
-
     def alloc_backward(self, eng, dev):
         if self.dz0 is not None:
             return
@@ -274,33 +270,86 @@ class _Workspace:
 
 
 # --------------------------------------------------------------------------------------------- engine
+class _Slots:
+    """A record of named vector slots.  C: the channels of the BatchNorm it serves; such a record carries the field names of a
+    `_fused._BN` as far as it has them (sum, sq, S1, S2, sc, sh, mean, rstd, pa, pb, pc), so the operand helpers take either."""
+
+    def __init__(self, C=None, **slots):
+        self.C = C
+        self.__dict__.update(slots)
+
+
 class _Engine(FusedEngine):
     """Host-side schedule: issues the kernel sequence of forward and backward on the current stream."""
     SLAB = 1 << 22               # floats per half of the statistic-row scratch (rows x channels of the largest producer)
     EW_ROWS = 2048               # workgroups (= rows) of the element-wise statistic producers in deterministic mode
 
-    # statistics plumbing for the two modes: keywords of a convolution producer (_sp), (sum, sq, stat_rows) of an element-wise
-    # producer (_ew), (sum, sq, replicas, rstride) for the consumer (_sc).  copies=False: atomic sums held once, not stat_replicas
-    # times (what the stem convolution and the element-wise kernels of backward add into)
-    def _sp(self, ws, slots, C, sub=None, copies=True):
-        if self.det:
-            return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // C, stat_rstride=C)
-        a, b = slots
-        if not copies:
-            return dict(stat_sum=ws.v(a), stat_sq=ws.v(b))
+    # ---- statistics plumbing for the two modes (deterministic: rows in ws.slab; CHEXPERT_DET=0: atomic sums in the records), named
+    # as in the ResNet engine: keywords of a convolution producer (_sp), (sum, sq, stat_rows) of an element-wise producer (_ew),
+    # (sum, sq, replicas, rstride) for the consumer (_sc).  S: the record of the sums -- its forward sum / sq, with `bwd` its S1 / S2.
+    # DenseNet's own: the sums a convolution produces are held stat_replicas times (copies=False: once -- what the stem
+    # convolution and the element-wise kernels add into), and a producer may write the channel range sub = (first, channels) of S
+    @staticmethod
+    def _sums(S, bwd, sub=None):
+        """(slot, slot, pitch of the copies) of S's forward sum / sq or backward S1 / S2, the slots cut to the channel range sub"""
+        a, b = (S.S1, S.S2) if bwd else (S.sum, S.sq)
         if sub is not None:
-            a, b = (a[0] + sub[0], sub[1]), (b[0] + sub[0], sub[1])
-        return dict(stat_sum=ws.v(a), stat_sq=ws.v(b), stat_replicas=self.stat_replicas, stat_rstride=slots[0][1])
+            return (a[0] + sub[0], sub[1]), (b[0] + sub[0], sub[1]), a[1]
+        return a, b, a[1]
 
-    def _ew(self, ws, slots, C, rows=None):
-        if self.det:
-            return ws.slab[0], ws.slab[1], rows or min(self.EW_ROWS, self.SLAB // C)
-        return ws.v(slots[0]), ws.v(slots[1]), 0
+    def _ew_rows(self, C):
+        return min(self.EW_ROWS, self.SLAB // C)
 
-    def _sc(self, ws, slots, C, rows, copies=True):
+    def _sp(self, ws, S, bwd=False, sub=None, copies=True):
+        if ws.frozen and not bwd:
+            return {}
         if self.det:
-            return ws.slab[0], ws.slab[1], rows, C
-        return ws.v(slots[0]), ws.v(slots[1]), self.stat_replicas if copies else 1, slots[0][1] if copies else 0
+            C = S.C if sub is None else sub[1]
+            return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // C, stat_rstride=C)
+        a, b, pitch = self._sums(S, bwd, sub)
+        if not copies:
+            return dict(stat_sum=self._v(ws, a), stat_sq=self._v(ws, b))
+        return dict(stat_sum=self._v(ws, a), stat_sq=self._v(ws, b), stat_replicas=self.stat_replicas, stat_rstride=pitch)
+
+    def _ew(self, ws, S, bwd=False, sub=None, rows=None):
+        if ws.frozen and not bwd:
+            return None, None, 0
+        if self.det:
+            return ws.slab[0], ws.slab[1], rows or self._ew_rows(S.C if sub is None else sub[1])
+        a, b, _ = self._sums(S, bwd, sub)
+        return self._v(ws, a), self._v(ws, b), 0
+
+    def _sc(self, ws, S, rows, bwd=False, copies=True):
+        if self.det:
+            return ws.slab[0], ws.slab[1], rows, S.C
+        a, b, pitch = self._sums(S, bwd)
+        return self._v(ws, a), self._v(ws, b), self.stat_replicas if copies else 1, pitch if copies else 0
+
+    def _fresh(self, ws, rows, lo, n):
+        """The pending statistic rows of a block buffer's newest channels [lo, lo + n), as cx_bn_coef_moments takes them: the next
+        BatchNorm over the buffer reduces them (deterministic training forward; None otherwise)."""
+        return (ws.slab[0], ws.slab[1], rows, n, lo, n) if self.det and not ws.frozen else None
+
+    # ---- operand keywords that are DenseNet's own (FusedEngine has those of a BatchNorm record)
+    @staticmethod
+    def _pro_slice(xs, q):
+        """input gradient: the deferred BatchNorm correction of a gradient slice, dY = dy * qa + x * qb + qc (q: _slice_q)"""
+        return dict(prologue=ops.PRO_AFFINE2, x2=xs, pa=q[0], pb=q[1], pc=q[2])
+
+    @staticmethod
+    def _g_slice(xs, q):
+        """weight gradient: the same of its gradient operand"""
+        return dict(g_prologue=ops.PRO_AFFINE2, g2=xs, ga=q[0], gb=q[1], gc=q[2])
+
+    def _mask(self, ws, y, S, by_sc=False, c_=None, stat=None):
+        """input gradient: the epilogue that masks with [relu(bn_S(y)) > 0] and produces BatchNorm S's backward sums.  The masked
+        gradient is scaled by one (conv2's form: norm2, norm0) or, by_sc, by S's scale (conv1's form: a norm1, whose mean / rstd
+        are the block's and whose gain the shared xhat terms leave out).  c_: a range of S's channels; stat: the statistics
+        keywords, where they are not _sp's (the regions of _pair_backward)."""
+        ch, v = self._ch, self._v
+        return dict(epilogue=ops.EPI_MASK, ex=ch(y, c_), e_sc=ch(v(ws, S.sc), c_), e_sh=ch(v(ws, S.sh), c_), e_mu=ch(v(ws, S.mean), c_),
+                    e_r=ch(v(ws, S.rstd), c_), e_scale=ch(v(ws, S.sc), c_) if by_sc else ws.ones[:S.C],
+                    **(self._sp(ws, S, bwd=True) if stat is None else stat))
 
     def __init__(self, model):
         super().__init__(model)
@@ -337,34 +386,57 @@ class _Engine(FusedEngine):
 
     # ---- coefficient-vector layout
     def _plan_vectors(self):
-        V = _Vec()
-        s = {}
-        R = self.stat_replicas
-        take_r = lambda n: (V.take(n * R)[0], n)      # R copies, n floats apart: the conv kernels spread their atomics over them
-        s["st0"] = [V.take(self.c_init) for _ in range(2)]                # conv0 output sum, sq
-        s["bst"] = [[take_r(c + n * self.growth) for _ in range(2)] for c, n in self.blocks]
-        s["yst"] = [[[take_r(self.mid) for _ in range(2)] for _ in range(n)] for _, n in self.blocks]
+        """Carves the coefficient vector into self.plan: .stem (conv0's sum / sq, norm0's sc / sh / mean / rstd and backward sums
+        S1 / S2), .blocks -- per block its replicated sums (sum, sq), its channels' mean / rstd, the exit norm's (transition norm,
+        norm5) sc / sh and backward sums S1 / S2, the accumulators A / Bc of the deferred BatchNorm terms, and .layers --, per
+        layer .n1 (sc, sh, replicated backward sums S1 / S2; mean / rstd are the block's, cut to the layer's input channels), .n2
+        (sc, sh, mean, rstd, the bottleneck output's replicated sum / sq, replicated S1 / S2, pa / pb / pc) and the slice triple
+        qa / qb / qc of the layer's output channels; .q and .p: the shared triples of a block's first channels and of norm0
+        (the stem's pa / pb / pc are .p cut to its channels).  The takes keep one order, whatever record files them: the
+        layout is [sums zeroed every forward | forward coefficients | sums zeroed every backward | backward coefficients]."""
+        V, R, g_, mid, ci = _Vec(), self.stat_replicas, self.growth, self.mid, self.c_init
+        self._spans = []
+
+        def take(n, copies=1):
+            """(copies > 1: that many copies, n floats apart -- the conv kernels spread their atomics over them)"""
+            self._spans.append(V.take(n * copies))
+            return (self._spans[-1][0], n)
+        per_block = lambda n_of, k, copies=1: [[take(n_of(c, n), copies) for _ in range(k)] for c, n in self.blocks]
+        per_layer = lambda n_of, k, copies=1: [[[take(n_of(c, i), copies) for _ in range(k)] for i in range(n)] for c, n in self.blocks]
+        ct, cin, mid_, g__ = (lambda c, n: c + n * g_), (lambda c, i: c + i * g_), (lambda c, i: mid), (lambda c, i: g_)
+        st0 = [take(ci) for _ in range(2)]
+        bst, yst = per_block(ct, 2, R), per_layer(mid_, 2, R)
         self.fwd_zero = (0, V.n)                                           # zeroed at the start of each forward
-        s["n0"] = [V.take(self.c_init) for _ in range(4)]                  # sc, sh, mean, rstd
-        s["bmr"] = [[V.take(c + n * self.growth) for _ in range(2)] for c, n in self.blocks]     # block mean, rstd
-        s["n1"] = [[[V.take(c + i * self.growth) for _ in range(2)] for i in range(n)] for c, n in self.blocks]
-        s["n2"] = [[[V.take(self.mid) for _ in range(4)] for _ in range(n)] for _, n in self.blocks]
-        s["nt"] = [[V.take(c + n * self.growth) for _ in range(2)] for c, n in self.blocks]      # transition / norm5 sc, sh
+        n0 = [take(ci) for _ in range(4)]
+        bmr, n1, n2, nt = per_block(ct, 2), per_layer(cin, 2), per_layer(mid_, 4), per_block(ct, 2)
         b0 = V.n
-        s["S0"] = [V.take(self.c_init) for _ in range(2)]
-        s["S1"] = [[[take_r(c + i * self.growth) for _ in range(2)] for i in range(n)] for c, n in self.blocks]
-        s["S2"] = [[[take_r(self.mid) for _ in range(2)] for _ in range(n)] for _, n in self.blocks]
-        s["St"] = [[V.take(c + n * self.growth) for _ in range(2)] for c, n in self.blocks]
-        s["AB"] = [[V.take(c + n * self.growth) for _ in range(2)] for c, n in self.blocks]
+        S0 = [take(ci) for _ in range(2)]
+        S1, S2, St, AB = per_layer(cin, 2, R), per_layer(mid_, 2, R), per_block(ct, 2), per_block(ct, 2)
         self.bwd_zero = (b0, V.n - b0)
         # per-layer AFFINE2 vectors (the two-layer pass of _pair_backward holds both its layers' norm2 vectors at once)
-        s["ql"] = [[[V.take(self.growth) for _ in range(3)] for _ in range(n)] for _, n in self.blocks]
-        s["pl"] = [[[V.take(self.mid) for _ in range(3)] for _ in range(n)] for _, n in self.blocks]
-        s["q"] = [V.take(max(self.mid, self.c_init, max(c for c, _ in self.blocks))) for _ in range(3)]   # slice AFFINE2
-        s["p"] = [V.take(max(self.mid, self.c_init)) for _ in range(3)]                                   # norm2 AFFINE2
-        s["dpooled"] = V.take(0)
-        self.slots = s
+        ql, pl = per_layer(g__, 3), per_layer(mid_, 3)
+        q = [take(max(mid, ci, max(c for c, _ in self.blocks))) for _ in range(3)]         # slice AFFINE2
+        p = [take(max(mid, ci)) for _ in range(3)]                                         # norm2 AFFINE2
+        names = lambda keys, *lists: dict(zip(keys.split(), (t for l in lists for t in l)))
+        blocks = []
+        for bi, (c, n) in enumerate(self.blocks):
+            layers = [_Slots(n1=_Slots(cin(c, i), mean=(bmr[bi][0][0], cin(c, i)), rstd=(bmr[bi][1][0], cin(c, i)),
+                                       **names("sc sh S1 S2", n1[bi][i], S1[bi][i])),
+                             n2=_Slots(mid, **names("sc sh mean rstd sum sq S1 S2 pa pb pc", n2[bi][i], yst[bi][i], S2[bi][i], pl[bi][i])),
+                             **names("qa qb qc", ql[bi][i])) for i in range(n)]
+            blocks.append(_Slots(ct(c, n), layers=layers, **names("sum sq mean rstd sc sh S1 S2 A Bc", bst[bi], bmr[bi], nt[bi], St[bi], AB[bi])))
+        stem = _Slots(ci, **names("sum sq sc sh mean rstd S1 S2 pa pb pc", st0, n0, S0, [(t[0], ci) for t in p]))
+        self.plan = _Slots(stem=stem, blocks=blocks, q=_Slots(**names("qa qb qc", q)), p=_Slots(**names("pa pb pc", p)), dpooled=take(0))
         self.vec_size = V.n
+
+    def vector_slots(self):
+        """Every (offset, length) span of the coefficient vector that the plan handed out (a replicated sum: all its copies)."""
+        return iter(self._spans)
+
+    def norm5_operands(self, ws):
+        """(last block buffer, norm5 scale, norm5 shift) of a workspace: relu(buffer * scale + shift) is what the head pools."""
+        last = self.plan.blocks[-1]
+        return ws.buf[-1], self._v(ws, last.sc), self._v(ws, last.sh)
 
     # ---- parameter binding
     def bind(self, dev):
@@ -386,44 +458,47 @@ class _Engine(FusedEngine):
     def _new_workspace(self, B, H, W):
         return _Workspace(self, B, H, W, self.device)
 
-    # ---- forward
-    def _bn(self, ws, stats, count, bn, out_slots, C_, train, mean_slot=None, rstd_slot=None):
-        """scale/shift (+mean/rstd) of one BatchNorm over C_ channels; stats = (sum, sq, replicas, rstride) of its input."""
-        sc, sh = ws.v(out_slots[0])[:C_], ws.v(out_slots[1])[:C_]
-        mean = ws.v(mean_slot)[:C_] if mean_slot is not None else None
-        rstd = ws.v(rstd_slot)[:C_] if rstd_slot is not None else None
-        if train:
-            mom = bn.momentum if bn.momentum is not None else 0.1
-            ssum, ssq, reps, rstride = stats
-            ops.bn_coef(ssum, ssq, count, bn.weight, bn.bias, bn.eps, mom,
-                        bn.running_mean if bn.track_running_stats else None,
-                        bn.running_var if bn.track_running_stats else None, sc, sh, mean, rstd, C_, replicas=reps, rstride=rstride)
-        else:
-            ops.bn_coef_eval(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, sc, sh, mean, rstd, C_)
+    def _aa_transition(self, t):
+        """The AAConv2d of transition t (the one that feeds block t, 0-based); None for a BatchNorm transition, the stem (t = 0) and
+        the head (t = number of blocks)."""
+        tr = getattr(self.model.features, "transition%d" % t, None)
+        return tr.conv if tr is not None and isinstance(tr.conv, AAConv2d) else None
 
-    def _bn_block(self, ws, bi, cin, count, bn, out_slots, train, fresh):
-        """BatchNorm over channels [0, cin) of block buffer bi (norm1 of a dense layer, a transition norm, norm5).  Batch moments
-        of a buffer channel exist once (bmean / brstd): deterministic mode reduces only the `fresh` channels -- those the
-        previous launch produced -- from their statistic rows; the atomic mode re-reads the replicated block sums."""
-        s = self.slots
-        bmean, brstd = s["bmr"][bi]
-        if not train:
-            return self._bn(ws, None, count, bn, out_slots, cin, False, bmean, brstd)
-        if not self.det:
-            bsum, bsq = s["bst"][bi]
-            return self._bn(ws, (ws.v(bsum), ws.v(bsq), self.stat_replicas, bsum[1]), count, bn, out_slots, cin, True, bmean, brstd)
-        mom = bn.momentum if bn.momentum is not None else 0.1
-        ops.bn_coef_moments(ws.v(bmean)[:cin], ws.v(brstd)[:cin], count, bn.weight, bn.bias, bn.eps, mom,
-                            bn.running_mean if bn.track_running_stats else None, bn.running_var if bn.track_running_stats else None,
-                            ws.v(out_slots[0])[:cin], ws.v(out_slots[1])[:cin], cin, fresh)
+    def _layer(self, bi, li):
+        return getattr(getattr(self.model.features, "denseblock%d" % (bi + 1)), "denselayer%d" % (li + 1))
+
+    @staticmethod
+    def _count(buf):
+        """values per channel of an NHWC buffer"""
+        return buf.shape[0] * buf.shape[1] * buf.shape[2]
+
+    # ---- forward
+    def _bn(self, ws, S, bn, count, stats):
+        """scale / shift / mean / rstd of BatchNorm `bn` into its record S; stats = (sum, sq, replicas, rstride) of its input (_sc),
+        which an eval forward does not read."""
+        v = self._v
+        out = v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), S.C
+        if ws.frozen:
+            ops.bn_coef_eval(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, *out)
+        else:
+            ops.bn_coef(stats[0], stats[1], count, *self._bn_train(bn), *out, replicas=stats[2], rstride=stats[3])
+
+    def _bn_block(self, ws, blk, S, bn, count, fresh):
+        """BatchNorm over the first S.C channels of the buffer of block `blk` (S: the .n1 of a dense layer, or blk itself for its
+        transition norm / norm5).  Batch moments of a buffer channel exist once (blk.mean / rstd): deterministic mode reduces only
+        the `fresh` channels -- those the previous launch produced -- from their statistic rows; the atomic mode re-reads the
+        replicated block sums."""
+        v = self._v
+        if ws.frozen or not self.det:
+            return self._bn(ws, S, bn, count, (v(ws, blk.sum), v(ws, blk.sq), self.stat_replicas, blk.sum[1]))
+        ops.bn_coef_moments(v(ws, S.mean), v(ws, S.rstd), count, *self._bn_train(bn), v(ws, S.sc), v(ws, S.sh), S.C, fresh)
 
     def forward(self, x, train, record=False):
         """train: batch statistics, dropout; eval: running statistics.  Every forward keeps what backward reads (block buffers,
         bottleneck outputs, max-pool arg-max, attention log-sum-exp), so `record` changes nothing here.  An eval forward leaves each
-        block's bmr (mean / rstd) at the running statistics of the block's LAST BatchNorm consumer (transition norm, norm5; the
-        last layer's norm1 before an attention transition): the basis of the frozen backward's sums."""
-        m, f, s = self.model, self.model.features, self.slots
-        det = self.det and train
+        block's mean / rstd at the running statistics of the block's LAST BatchNorm consumer (transition norm, norm5; the last
+        layer's norm1 before an attention transition): the basis of the frozen backward's sums.
+        `fresh`, the pending statistic rows of the newest slice (_fresh), goes from each step to the next."""
         u8 = x.dtype == torch.uint8             # decoded grey bytes (B,1,H,W): whitened + expanded on the GPU (cx_u8_to_nhwc4)
         if x.dim() != 4 or x.shape[1] != (1 if u8 else 3):
             raise RuntimeError("expected a (B,3,H,W) float input or a (B,1,H,W) uint8 image")
@@ -443,28 +518,9 @@ class _Engine(FusedEngine):
         if train and not self.det:
             z0, zn = self.fwd_zero
             ws.vec[z0:z0 + zn].zero_()
-        sp = (lambda slots, C, sub=None, **k: self._sp(ws, slots, C, sub, **k)) if train else (lambda *a, **k: {})
-        ci = self.c_init
-        if self.cifar:
-            self._cifar_stem(ws, x, train, sp)
-            rows = self._stem_rows
-        else:
-            if u8:
-                ops.u8_to_nhwc4(x.contiguous(), ws.x4)
-            else:
-                ops.nchw3_to_nhwc4(x.contiguous().float(), ws.x4)
-            # stem: conv0 -> norm0 -> relu0 -> pool0 (attn_aug_conv.py:460-465)
-            rows = ops.conv_gemm(ws.x4, self.w_fwd(f.conv0), ws.c0, N=ci, mode=ops.MODE_STEM, **sp(s["st0"], ci, copies=False))
-            st0 = self._sc(ws, s["st0"], ci, rows, copies=False) if train else None
-            self._bn(ws, st0, B * (H // 2) * (W // 2), f.norm0, s["n0"][:2], ci, train, s["n0"][2], s["n0"][3])
-            rows = ops.bnrelu_maxpool_fwd(ws.c0, ws.v(s["n0"][0]), ws.v(s["n0"][1]), ws.buf[0][..., :ci], ws.amax,
-                                          *(self._ew(ws, s["bst"][0], ci) if train else (None, None, 0)))
-        # (sum rows, sq rows, rows, rstride, first channel, channels) of the newest slice
-        fresh = (ws.slab[0], ws.slab[1], rows, ci, 0, ci) if det else None
-        nb = len(self.blocks)
-        g_ = self.growth
-        drop = train and self.drop_rate > 0
-        if drop:
+        rows = self._cifar_stem_forward(ws, x) if self.cifar else self._stem_forward(ws, x)
+        fresh = self._fresh(ws, rows, 0, self.c_init)
+        if train and self.drop_rate > 0:
             if not self.det:
                 raise RuntimeError("drop_rate > 0 uses the deterministic statistic rows (unset CHEXPERT_DET=0)")
             if self.drop_seed is None:
@@ -472,144 +528,113 @@ class _Engine(FusedEngine):
                 self.drop_seed = torch.tensor([(torch.initial_seed() + (rank << 40)) & 0x7fffffffffffffff], dtype=torch.int64,
                                               device=x.device)
             self.drop_seed.add_(1)
-        for bi, (c0, n_layers) in enumerate(self.blocks):
-            buf = ws.buf[bi]
-            h, w = ws.hw[bi]
-            cnt = B * h * w
-            block = getattr(f, "denseblock%d" % (bi + 1))
+        last = len(self.blocks) - 1
+        for bi, (_, n_layers) in enumerate(self.blocks):
             for li in range(n_layers):
-                layer = getattr(block, "denselayer%d" % (li + 1))
-                cin = c0 + li * g_
-                n1, n2 = s["n1"][bi][li], s["n2"][bi][li]
-                self._bn_block(ws, bi, cin, cnt, layer.norm1, n1, train, fresh)
-                yst = s["yst"][bi][li]
-                y1 = ws.y1[bi][li]
-                rows = ops.conv_gemm(buf[..., :cin], self.w_fwd(layer.conv1), y1, N=self.mid, prologue=ops.PRO_AFFINE_RELU,
-                                     pa=ws.v(n1[0]), pb=ws.v(n1[1]), **sp(yst, self.mid))
-                self._bn(ws, self._sc(ws, yst, self.mid, rows) if train else None, cnt, layer.norm2, n2[:2], self.mid, train, n2[2],
-                         n2[3])
-                rows = ops.conv_gemm(y1, self.w_fwd(layer.conv2), buf[..., cin:cin + g_], N=g_, kh=3, kw=3, pad=1,
-                                     prologue=ops.PRO_AFFINE_RELU, pa=ws.v(n2[0]), pb=ws.v(n2[1]),
-                                     **({} if drop else sp(s["bst"][bi], g_, (cin, g_))))
-                if drop:
-                    # dropout on the new slice, in place; its statistic rows are those of the dropped-out values (what every later
-                    # BatchNorm of the block sees)
-                    rows = ops.dropout_slice_fwd(buf[..., cin:cin + g_], self.drop_rate, self.drop_seed, bi * 256 + li, ws.slab[0],
-                                                 ws.slab[1], stat_rows=min(self.EW_ROWS, self.SLAB // g_))
-                if det:
-                    fresh = (ws.slab[0], ws.slab[1], rows, g_, cin, g_)
-            ct = c0 + n_layers * g_
-            nt = s["nt"][bi]
-            if bi != nb - 1 and isinstance(getattr(f, "transition%d" % (bi + 1)).conv, AAConv2d):
-                # block statistics are still needed by backward (mean / rstd of the buffer channels)
-                bmean, brstd = s["bmr"][bi]
-                if train and det:          # no BatchNorm consumes the block: finish the moments of its last slice here
-                    ops.bn_coef_moments(ws.v(bmean)[:ct], ws.v(brstd)[:ct], cnt, None, None, 1e-5, 0.0, None, None, None, None, ct, fresh)
-                elif train:
-                    bsum, bsq = s["bst"][bi]
-                    ops.bn_coef(ws.v(bsum), ws.v(bsq), cnt, None, None, 1e-5, 0.0, None, None, None, None, ws.v(bmean), ws.v(brstd), ct,
-                                replicas=self.stat_replicas, rstride=bsum[1])
-                st = (lambda a: ws.v(a)) if train else (lambda a: None)
-                fresh = self._aa_forward(ws, bi, getattr(f, "transition%d" % (bi + 1)).conv, st, det)
-            elif bi != nb - 1:
-                tr = getattr(f, "transition%d" % (bi + 1))
-                self._bn_block(ws, bi, ct, cnt, tr.norm, nt, train, fresh)
-                cn = self.blocks[bi + 1][0]          # channels the transition produces (ct // 2 in the reference's networks)
-                rows = ops.conv_gemm(buf, self.w_fwd(tr.conv), ws.buf[bi + 1][..., :cn], N=cn, mode=ops.MODE_POOL2,
-                                     prologue=ops.PRO_AFFINE_RELU, pa=ws.v(nt[0]), pb=ws.v(nt[1]),
-                                     **sp(s["bst"][bi + 1], cn, (0, cn)))
-                if det:
-                    fresh = (ws.slab[0], ws.slab[1], rows, cn, 0, cn)
+                fresh = self._layer_forward(ws, bi, li, fresh)
+            if bi == last:
+                self._head_forward(ws, bi, fresh)
+            elif self._aa_transition(bi + 1) is not None:
+                fresh = self._aa_forward(ws, bi, fresh)
             else:
-                self._bn_block(ws, bi, ct, cnt, f.norm5, nt, train, fresh)
-                ops.head_fwd(buf, ws.v(nt[0]), ws.v(nt[1]), m.classifier.weight, m.classifier.bias, ws.pooled, ws.logits)
+                fresh = self._transition_forward(ws, bi, fresh)
         if train:
-            m._nbt_pending += 1
+            self.model._nbt_pending += 1
         return ws
 
-    def _cifar_stem(self, ws, x, train, sp):
+    def _stem_forward(self, ws, x):
+        """conv0 -> norm0 -> relu0 -> pool0 of the ImageNet form (attn_aug_conv.py:460-465) into block 1's first channels.  Returns
+        their statistic rows."""
+        f, S, ci = self.model.features, self.plan.stem, self.c_init
+        if x.dtype == torch.uint8:
+            ops.u8_to_nhwc4(x.contiguous(), ws.x4)
+        else:
+            ops.nchw3_to_nhwc4(x.contiguous().float(), ws.x4)
+        rows = ops.conv_gemm(ws.x4, self.w_fwd(f.conv0), ws.c0, N=ci, mode=ops.MODE_STEM, **self._sp(ws, S, copies=False))
+        self._bn(ws, S, f.norm0, self._count(ws.c0), self._sc(ws, S, rows, copies=False))
+        return ops.bnrelu_maxpool_fwd(ws.c0, self._v(ws, S.sc), self._v(ws, S.sh), ws.buf[0][..., :ci], ws.amax,
+                                      *self._ew(ws, self.plan.blocks[0], rows=self._ew_rows(ci)))
+
+    def _cifar_stem_forward(self, ws, x):
         """conv0 (5x5, stride 1, pad 2) -> norm0 -> relu0 of the CIFAR form (attn_aug_conv.py:469-474).  The image is held with 8
         channels (3 + zeros), conv0 runs on the generic implicit GEMM; norm0 + relu0 ride in the prologue of a 1x1 identity
-        convolution that writes block 1's first channels and leaves their statistic rows."""
-        f, s = self.model.features, self.slots
-        B, H, W = ws.B, ws.H, ws.W
+        convolution that writes block 1's first channels.  Returns their statistic rows."""
+        f, S, ci = self.model.features, self.plan.stem, self.c_init
         ops.nchw3_to_nhwc8(x.contiguous().float(), ws.x8)
-        rows = ops.conv_gemm(ws.x8, self.w_fwd(f.conv0), ws.c0, N=self.c_init, kh=5, kw=5, pad=2, **sp(None, self.c_init))
-        st0 = (ws.slab[0], ws.slab[1], rows, self.c_init) if train else None
-        self._bn(ws, st0, B * H * W, f.norm0, s["n0"][:2], self.c_init, train, s["n0"][2], s["n0"][3])
-        self._stem_rows = ops.conv_gemm(ws.c0, self.eye, ws.buf[0][..., :self.c_init], N=self.c_init, prologue=ops.PRO_AFFINE_RELU,
-                                        pa=ws.v(s["n0"][0]), pb=ws.v(s["n0"][1]), **sp(None, self.c_init))
+        rows = ops.conv_gemm(ws.x8, self.w_fwd(f.conv0), ws.c0, N=ci, kh=5, kw=5, pad=2, **self._sp(ws, S))
+        self._bn(ws, S, f.norm0, self._count(ws.c0), self._sc(ws, S, rows))
+        return ops.conv_gemm(ws.c0, self.eye, ws.buf[0][..., :ci], N=ci, **self._pro_bnrelu(ws, S), **self._sp(ws, S))
 
-    def _aa_forward(self, ws, bi, aa, st, det=False):
-        """InstanceNorm -> ReLU -> AAConv2d(3x3, stride 2) from block buffer bi into the first channels of buffer bi+1.  Returns the
+    def _layer_forward(self, ws, bi, li, fresh):
+        """Dense layer li of block bi: norm1's coefficients, conv1 into the bottleneck buffer, norm2's coefficients, conv2 into the
+        layer's slice of the block buffer (and the dropout on it).  Returns the slice's pending statistic rows."""
+        blk, layer, g_ = self.plan.blocks[bi], self._layer(bi, li), self.growth
+        L = blk.layers[li]
+        buf, y1, cin = ws.buf[bi], ws.y1[bi][li], L.n1.C
+        cnt = self._count(buf)
+        drop = self.drop_rate > 0 and not ws.frozen
+        self._bn_block(ws, blk, L.n1, layer.norm1, cnt, fresh)
+        rows = ops.conv_gemm(buf[..., :cin], self.w_fwd(layer.conv1), y1, N=self.mid, **self._pro_bnrelu(ws, L.n1), **self._sp(ws, L.n2))
+        self._bn(ws, L.n2, layer.norm2, cnt, self._sc(ws, L.n2, rows))
+        rows = ops.conv_gemm(y1, self.w_fwd(layer.conv2), buf[..., cin:cin + g_], N=g_, kh=3, kw=3, pad=1, **self._pro_bnrelu(ws, L.n2),
+                             **({} if drop else self._sp(ws, blk, sub=(cin, g_))))
+        if drop:
+            # dropout on the new slice, in place; its statistic rows are those of the dropped-out values (what every later
+            # BatchNorm of the block sees)
+            rows = ops.dropout_slice_fwd(buf[..., cin:cin + g_], self.drop_rate, self.drop_seed, bi * 256 + li,
+                                         *self._ew(ws, blk, sub=(cin, g_)))
+        return self._fresh(ws, rows, cin, g_)
+
+    def _transition_forward(self, ws, bi, fresh):
+        """BatchNorm transition after block bi: the norm's coefficients, then ReLU -> 2x2 average pool -> 1x1 convolution (in that
+        order: they commute) into the first channels of block bi + 1.  Returns their pending statistic rows."""
+        blk, nxt, tr = self.plan.blocks[bi], self.plan.blocks[bi + 1], getattr(self.model.features, "transition%d" % (bi + 1))
+        cn = self.blocks[bi + 1][0]          # channels the transition produces (half the block's in the reference's networks)
+        self._bn_block(ws, blk, blk, tr.norm, self._count(ws.buf[bi]), fresh)
+        rows = ops.conv_gemm(ws.buf[bi], self.w_fwd(tr.conv), ws.buf[bi + 1][..., :cn], N=cn, mode=ops.MODE_POOL2,
+                             **self._pro_bnrelu(ws, blk), **self._sp(ws, nxt, sub=(0, cn)))
+        return self._fresh(ws, rows, 0, cn)
+
+    def _head_forward(self, ws, bi, fresh):
+        """norm5's coefficients; ReLU -> global average pool -> classifier in one kernel."""
+        m, blk = self.model, self.plan.blocks[bi]
+        self._bn_block(ws, blk, blk, m.features.norm5, self._count(ws.buf[bi]), fresh)
+        ops.head_fwd(ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), m.classifier.weight, m.classifier.bias, ws.pooled, ws.logits)
+
+    def _aa_forward(self, ws, bi, fresh):
+        """InstanceNorm -> ReLU -> AAConv2d(3x3, stride 2) from block buffer bi into the first channels of buffer bi+1.  No BatchNorm
+        consumes block bi, whose mean / rstd backward still reads: the moments of its last slice are finished here.  Returns the
         pending statistic rows of the attention channels (deterministic mode), which the next norm1 reduces."""
-        s = self.slots
-        buf, nxt, T = ws.buf[bi], ws.buf[bi + 1], ws.aa[bi]
+        v, blk, nxt, aa = self._v, self.plan.blocks[bi], self.plan.blocks[bi + 1], self._aa_transition(bi + 1)
+        buf, nbuf, T = ws.buf[bi], ws.buf[bi + 1], ws.aa[bi]
         B, h, w, ct = buf.shape
+        det = self.det and not ws.frozen
+        none = (None, None, 1e-5, 0.0, None, None)              # no gain, shift or running statistics: moments only
+        if det:
+            ops.bn_coef_moments(v(ws, blk.mean), v(ws, blk.rstd), B * h * w, *none, None, None, ct, fresh)
+        elif not ws.frozen:
+            ops.bn_coef(v(ws, blk.sum), v(ws, blk.sq), B * h * w, *none, None, None, v(ws, blk.mean), v(ws, blk.rstd), ct,
+                        replicas=self.stat_replicas, rstride=blk.sum[1])
         cc = aa.conv.out_channels                               # convolution branch, then the attention channels
         cout = cc + aa.dv                                       # (= ct // 2 in the reference's networks)
         ops.stats_bc(buf, T.stat[0], T.stat[1])                 # one owner per (image, channel): plain stores
-        ops.bn_coef(T.stat[0], T.stat[1], h * w, None, None, 1e-5, 0.0, None, None, T.coef[0], T.coef[1], None, None, B * ct)
+        ops.bn_coef(T.stat[0], T.stat[1], h * w, *none, T.coef[0], T.coef[1], None, None, B * ct)
         ops.affine_relu_bc(buf, T.coef[0], T.coef[1], T.A)
-        nsum, nsq = s["bst"][bi + 1]
-        fresh = None
         if det:
             # the block's first channels come from two kernels: the conv branch's rows become moments at once (they share the
             # scratch pair with the out-projection's rows), the attention channels' rows stay pending for the next norm1
-            rows = ops.conv_gemm(T.A, self.w_fwd(aa.conv), nxt[..., :cc], N=cc, kh=3, kw=3, stride=2, pad=1, **self._sp(ws, None, cc))
-            nmean, nrstd = s["bmr"][bi + 1]
-            ops.bn_coef_moments(ws.v(nmean)[:cc], ws.v(nrstd)[:cc], B * (h // 2) * (w // 2), None, None, 1e-5, 0.0, None, None, None, None, cc,
-                                (ws.slab[0], ws.slab[1], rows, cc, 0, cc))
+            rows = ops.conv_gemm(T.A, self.w_fwd(aa.conv), nbuf[..., :cc], N=cc, kh=3, kw=3, stride=2, pad=1, **self._sp(ws, nxt, sub=(0, cc)))
+            ops.bn_coef_moments(v(ws, nxt.mean, cc), v(ws, nxt.rstd, cc), B * (h // 2) * (w // 2), *none, None, None, cc,
+                                self._fresh(ws, rows, 0, cc))
         else:
-            ops.conv_gemm(T.A, self.w_fwd(aa.conv), nxt[..., :cc], N=cc, kh=3, kw=3, stride=2, pad=1,
-                          stat_sum=st((nsum[0], cc)), stat_sq=st((nsq[0], cc)))
+            ssum, ssq, _ = self._ew(ws, nxt, sub=(0, cc))
+            ops.conv_gemm(T.A, self.w_fwd(aa.conv), nbuf[..., :cc], N=cc, kh=3, kw=3, stride=2, pad=1, stat_sum=ssum, stat_sq=ssq)
         ops.conv_gemm(T.A, self.w_fwd(aa.in_proj_qkv), T.QKV, N=2 * aa.dk + aa.dv, stride=2)
         ops.aa_attention_fwd(T.QKV, *aa.rel_tables(), T.O, T.LSE, aa.nh, aa.dk, aa.dv)
         object.__setattr__(aa, "_last", (T.QKV, T.LSE))
-        if det:
-            rows = ops.aa_outproj_fwd(T.O, aa.out_proj.weight, nxt[..., cc:cout], ws.slab[0], ws.slab[1],
-                                      stat_rows=min(self.EW_ROWS, self.SLAB // aa.dv), stat_rstride=aa.dv)
-            fresh = (ws.slab[0], ws.slab[1], rows, aa.dv, cc, aa.dv)
-        else:
-            ops.aa_outproj_fwd(T.O, aa.out_proj.weight, nxt[..., cc:cout], st((nsum[0] + cc, aa.dv)), st((nsq[0] + cc, aa.dv)))
-        return fresh
-
-    def _aa_backward(self, ws, bi, aa, done):
-        """Backward of the AA transition feeding block bi (from block bi-1); qa/qb/qc apply the deferred BN correction
-        to the gradient slice [0, c0) of block bi."""
-        G = self.grad_of
-        qa, qb, qc = self._slice_q(ws, bi, -1)[:3]            # written by layer 0's norm1 coefficient launch
-        buf, gbuf, pbuf, pg, T = ws.buf[bi], ws.gbuf[bi], ws.buf[bi - 1], ws.gbuf[bi - 1], ws.aa[bi - 1]
-        cc = aa.conv.out_channels
-        c0 = cc + aa.dv                          # (the block's entry width in the reference's networks; the padded twin's is wider)
-        Cp = pbuf.shape[3]
-        gs_c, xs_c, gs_a, xs_a = gbuf[..., :cc], buf[..., :cc], gbuf[..., cc:c0], buf[..., cc:c0]
-        ops.aa_outproj_bwd(gs_a, xs_a, qa[cc:c0], qb[cc:c0], qc[cc:c0], T.O, aa.out_proj.weight, T.dO, G(aa.out_proj.weight))
-        ops.aa_attention_bwd(T.QKV, *aa.rel_tables(), T.O, T.dO, T.LSE, T.dQKV32, *aa.rel_grads(G), aa.nh, aa.dk, aa.dv)
-        if self.dtype == torch.float32:         # fp32 storage mode: the fp32 gradient is the convolution operand as it is
-            T.dQKV = T.dQKV32
-        else:
-            ops.f32_to_bf16(T.dQKV32, T.dQKV)
-        # (the 3x3 branch reaches every pixel and stores; the 1x1 branch only reaches the even-even ones: accumulating, its
-        # other parity classes are nothing to do)
-        ops.conv_gemm(gs_c, self.w_bwd(aa.conv), T.dA, N=Cp, kh=3, kw=3, pad=1, tstride=2, prologue=ops.PRO_AFFINE2, x2=xs_c,
-                      pa=qa[:cc], pb=qb[:cc], pc=qc[:cc])
-        ops.conv_gemm(T.dQKV, self.w_bwd(aa.in_proj_qkv), T.dA, N=Cp, tstride=2, accumulate=True)
-        ops.conv_wgrad(T.dQKV, T.A, G(aa.in_proj_qkv.weight), stride=2)
-        ops.conv_wgrad(gs_c, T.A, G(aa.conv.weight), kh=3, kw=3, stride=2, pad=1, g_prologue=ops.PRO_AFFINE2, g2=xs_c, ga=qa[:cc],
-                       gb=qb[:cc], gc=qc[:cc])
-        ops.in_relu_bwd(T.dA, pbuf, T.coef[0], T.coef[1], T.S[0], T.S[1], pg)       # S: one owner per (image, channel), plain stores
-        done(aa.first_param())
-
-    def _flush_w2(self):
-        """Launch the collected 3x3 weight gradients of the current block (one batched launch per 24 layers; per layer when the
-        library declines the shape or the slab workspace)."""
-        items, self._w2_items = self._w2_items, []
-        for i in range(0, len(items), ops.L.WGRAD_BATCH_MAX):
-            part = items[i:i + ops.L.WGRAD_BATCH_MAX]
-            if not ops.conv3x3_wgrad_batch(part):
-                for dyc, y1, pa, pb, dw in part:
-                    ops.conv_wgrad(dyc, y1, dw, kh=3, kw=3, pad=1, x_prologue=ops.PRO_AFFINE_RELU, pa=pa, pb=pb)
+        rows = ops.aa_outproj_fwd(T.O, aa.out_proj.weight, nbuf[..., cc:cout], *self._ew(ws, nxt, sub=(cc, aa.dv)),
+                                  stat_rstride=aa.dv if det else 0)
+        return self._fresh(ws, rows, cc, aa.dv)
 
     # ---- backward
     def _backward(self, ws, dlogits, dx, done):
@@ -652,13 +677,13 @@ class _Engine(FusedEngine):
                     k, li = k + 2, li - 2
                     continue
                 dz2 = dz2s[k & 1]
-                self._layer_conv1(ws, bi, li, dz2, self._layer_front(ws, bi, li, dz2, batch_w2), fused, done)
+                self._layer_front(ws, bi, li, dz2, batch_w2)
+                self._layer_conv1(ws, bi, li, dz2, fused, done)
                 k, li = k + 1, li - 1
             self._flush_w2()
             # the block's first c0 channels were produced by the previous transition (or the stem)
-            aa = self._aa_transition(bi)
-            if aa is not None:
-                self._aa_backward(ws, bi, aa, done)
+            if self._aa_transition(bi) is not None:
+                self._aa_backward(ws, bi, done)
             elif bi > 0:
                 self._transition_backward(ws, bi, done)
             elif self.cifar:
@@ -666,172 +691,174 @@ class _Engine(FusedEngine):
             else:
                 self._stem_backward(ws, dx)
 
-    def _aa_transition(self, t):
-        """The AAConv2d of transition t (the one that feeds block t, 0-based); None for a BatchNorm transition, the stem (t = 0) and
-        the head (t = number of blocks)."""
-        tr = getattr(self.model.features, "transition%d" % t, None)
-        return tr.conv if tr is not None and isinstance(tr.conv, AAConv2d) else None
-
-    def _layer(self, bi, li):
-        return getattr(getattr(self.model.features, "denseblock%d" % (bi + 1)), "denselayer%d" % (li + 1))
-
     def _slice_q(self, ws, bi, li):
         """(qa, qb, qc, first channel, channels) of the slice layer li of block bi produced (li = -1: the block's first c0
         channels): emitted by the coefficient kernel of the slice's LAST consumer, whose A / B update completes them."""
         c0, _ = self.blocks[bi]
-        if li < 0:
-            return tuple(ws.v(t)[:c0] for t in self.slots["q"]) + (0, c0)
-        return tuple(ws.v(t) for t in self.slots["ql"][bi][li]) + (c0 + li * self.growth, self.growth)
+        Q, n = (self.plan.q, c0) if li < 0 else (self.plan.blocks[bi].layers[li], None)
+        return tuple(self._v(ws, t, n) for t in (Q.qa, Q.qb, Q.qc)) + ((0, c0) if li < 0 else (c0 + li * self.growth, self.growth))
+
+    def _norm_bwd(self, ws, bn, S, r, count, acc=None, q=None, c_=None):
+        """Backward coefficients of BatchNorm `bn` (record S) and its dgamma / dbeta from the backward sums r = (S1, S2, replicas,
+        rstride) over `count` values per channel.  A norm2 / norm0 gets its own pa / pb / pc.  A norm over a block buffer (norm1,
+        transition norm, norm5) names the block's record as `acc`: its terms go to the block's accumulators A / Bc, over the
+        block's mean / rstd, and q (_slice_q) asks for the coefficients of the slice this norm is the last consumer of.  c_: the
+        range of the norm's channels that r covers (_pair_backward)."""
+        v, G, M = self._v, self.grad_of, acc or S
+        lo, n = (0, S.C) if c_ is None else (c_.start, c_.stop - c_.start)
+        ch = lambda t: self._ch(t, c_)
+        out = (ch(v(ws, acc.A)), ch(v(ws, acc.Bc)), None, None, None) if acc is not None else \
+            (None, None, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc))
+        if q is not None and c_ is not None:
+            q = q[:3] + (q[3] - lo, q[4])
+        self.bn_bwd_coef(ws, bn, r[0], r[1], count, ch(bn.weight), ch(v(ws, M.mean)), ch(v(ws, M.rstd)), ch(G(bn.weight)), ch(G(bn.bias)),
+                         *out, n, replicas=r[2], rstride=r[3], q=q, lo=lo)
 
     def _head_backward(self, ws, dlogits):
         """classifier -> global average pool -> ReLU -> norm5, into the last block's gradient buffer."""
-        m, f, s, v, G = self.model, self.model.features, self.slots, ws.v, self.grad_of
+        m, v, G = self.model, self._v, self.grad_of
         bi = len(self.blocks) - 1
-        c0, n_layers = self.blocks[bi]
-        ct = c0 + n_layers * self.growth
-        nt, (bmean, brstd), (A, Bc), St = s["nt"][bi], s["bmr"][bi], s["AB"][bi], s["St"][bi]
-        B = ws.B
-        h, w = ws.hw[bi]
-        dpooled = torch.empty(B, ct, dtype=torch.float32, device=self.device)
+        blk, ct = self.plan.blocks[bi], self.plan.blocks[bi].C
+        dpooled = torch.empty(ws.B, ct, dtype=torch.float32, device=self.device)
         ops.head_bwd(dlogits, ws.pooled, m.classifier.weight, G(m.classifier.weight), G(m.classifier.bias) if
                      m.classifier.bias is not None else None, dpooled)
-        if self.det and B * ct > self.SLAB:
-            raise RuntimeError("batch too large for the statistic-row scratch (B*C = %d > %d)" % (B * ct, self.SLAB))
-        rows = ops.gap_relu_bn_bwd(dpooled, ws.buf[bi], v(nt[0]), v(nt[1]), v(bmean), v(brstd), v(nt[0]), ws.gbuf[bi],
-                                   *self._ew(ws, St, ct, self.SLAB // ct))
-        sred = self._sc(ws, St, ct, rows, copies=False)
-        self.bn_bwd_coef(ws, f.norm5, sred[0], sred[1], B * h * w, f.norm5.weight, v(bmean), v(brstd), G(f.norm5.weight), G(f.norm5.bias),
-                         v(A), v(Bc), None, None, None, ct, replicas=sred[2], rstride=sred[3], q=self._slice_q(ws, bi, n_layers - 1))
+        if self.det and ws.B * ct > self.SLAB:
+            raise RuntimeError("batch too large for the statistic-row scratch (B*C = %d > %d)" % (ws.B * ct, self.SLAB))
+        rows = ops.gap_relu_bn_bwd(dpooled, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
+                                   ws.gbuf[bi], *self._ew(ws, blk, bwd=True, rows=self.SLAB // ct))
+        self._norm_bwd(ws, m.features.norm5, blk, self._sc(ws, blk, rows, bwd=True, copies=False), self._count(ws.buf[bi]), acc=blk,
+                       q=self._slice_q(ws, bi, self.blocks[bi][1] - 1))
 
     def _last_slice_coef(self, ws, bi):
         """Block bi feeds an AA transition, which normalises per instance (its backward is complete in cx_in_relu_bwd): no BatchNorm
         consumer follows the block, so nobody has emitted the slice coefficients of its last layer -- A = B = 0 there."""
-        s, g_ = self.slots, self.growth
-        c0, n_layers = self.blocks[bi]
-        cl = c0 + (n_layers - 1) * g_
-        (bmean, brstd), (A, Bc) = s["bmr"][bi], s["AB"][bi]
-        ops.bn_bwd_slice_coef(*(ws.v((t[0] + cl, g_)) for t in (A, Bc, bmean, brstd)), *(ws.v(t) for t in s["ql"][bi][n_layers - 1]), g_)
+        blk, g_ = self.plan.blocks[bi], self.growth
+        cl = blk.C - g_
+        ops.bn_bwd_slice_coef(*(self._v(ws, (t[0] + cl, g_)) for t in (blk.A, blk.Bc, blk.mean, blk.rstd)),
+                              *self._slice_q(ws, bi, self.blocks[bi][1] - 1)[:3], g_)
 
     def _layer_front(self, ws, bi, li, dz2, batch_w2):
         """Layer li of block bi from its gradient slice down to dz2, the gradient at norm2's output: (the dropout backward,) the 3x3
         input gradient with relu2's mask and norm2's sums in its epilogue, the 3x3 weight gradient -- queued for the block's batched
-        launch when batch_w2 --, norm2's coefficients.  Returns (pa, pb, pc), which apply norm2's correction to dz2."""
-        s, v, G, g_ = self.slots, ws.v, self.grad_of, self.growth
-        layer = self._layer(bi, li)
-        h, w = ws.hw[bi]
-        cin = self.blocks[bi][0] + li * g_
-        n2, y1, S2 = s["n2"][bi][li], ws.y1[bi][li], s["S2"][bi][li]
-        qa, qb, qc = (v(t) for t in s["ql"][bi][li])      # written by the previous coefficient launch (_slice_q)
+        launch when batch_w2 --, norm2's coefficients pa / pb / pc, which apply norm2's correction to dz2."""
+        G, g_ = self.grad_of, self.growth
+        layer, n2 = self._layer(bi, li), self.plan.blocks[bi].layers[li].n2
+        y1 = ws.y1[bi][li]
+        q = self._slice_q(ws, bi, li)                     # written by the previous coefficient launch
+        cin = q[3]
         gs, xs = ws.gbuf[bi][..., cin:cin + g_], ws.buf[bi][..., cin:cin + g_]
         if self.drop_rate > 0 and not ws.frozen:         # (eval mode: no dropout in the forward)
             # the slice's deferred BatchNorm correction and the forward's keep decisions, in place on the gradient slice; the
             # kernels below then read it with identity coefficients
-            ops.dropout_slice_bwd(gs, xs, qa, qb, qc, self.drop_rate, self.drop_seed, bi * 256 + li)
-            qa, qb, qc = ws.ones[:g_], ws.zeros[:g_], ws.zeros[:g_]
+            ops.dropout_slice_bwd(gs, xs, *q[:3], self.drop_rate, self.drop_seed, bi * 256 + li)
+            q = ws.ones[:g_], ws.zeros[:g_], ws.zeros[:g_]
         dyc = ws.dyc[bi][li] if ws.dyc is not None else None
-        rows = ops.conv_gemm(gs, self.w_bwd(layer.conv2), dz2, N=self.mid, kh=3, kw=3, pad=1, prologue=ops.PRO_AFFINE2, x2=xs,
-                             pa=qa, pb=qb, pc=qc, epilogue=ops.EPI_MASK, ex=y1, e_sc=v(n2[0]), e_sh=v(n2[1]), e_mu=v(n2[2]),
-                             e_r=v(n2[3]), e_scale=ws.ones[:self.mid], pro_out=dyc, **self._sp(ws, S2, self.mid))
-        red2 = self._sc(ws, S2, self.mid, rows)
-        dw = G(layer.conv2.weight)
+        rows = ops.conv_gemm(gs, self.w_bwd(layer.conv2), dz2, N=self.mid, kh=3, kw=3, pad=1, pro_out=dyc, **self._pro_slice(xs, q),
+                             **self._mask(ws, y1, n2))
+        red2 = self._sc(ws, n2, rows, bwd=True)
+        dw, x_n2 = G(layer.conv2.weight), self._x_bnrelu(ws, n2)
         if dyc is None or not ops.last_pro_out():
             # (fp32 mode, or a kernel without the side output) the slice as it lies in the block buffers, corrected on the fly
-            ops.conv_wgrad(gs, y1, dw, kh=3, kw=3, pad=1, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa, gb=qb, gc=qc,
-                           x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]), pb=v(n2[1]))
+            ops.conv_wgrad(gs, y1, dw, kh=3, kw=3, pad=1, **self._g_slice(xs, q), **x_n2)
         elif batch_w2:
-            self._w2_items.append((dyc, y1, v(n2[0]), v(n2[1]), dw))
+            self._w2_items.append(((dyc, y1, x_n2["pa"], x_n2["pb"], dw), x_n2))
         else:
             # the input-gradient kernel left the corrected slice as a dense (M, 32) tensor: the weight gradient reads 64 contiguous
             # bytes per pixel instead of two 64-byte pieces of the block buffers' rows (half of every line wasted)
-            ops.conv_wgrad(dyc, y1, dw, kh=3, kw=3, pad=1, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n2[0]), pb=v(n2[1]))
-        pabc = tuple(v(t) for t in s["pl"][bi][li])
-        self.bn_bwd_coef(ws, layer.norm2, red2[0], red2[1], ws.B * h * w, layer.norm2.weight, v(n2[2]), v(n2[3]), G(layer.norm2.weight),
-                         G(layer.norm2.bias), None, None, *pabc, self.mid, replicas=red2[2], rstride=red2[3])
-        return pabc
+            ops.conv_wgrad(dyc, y1, dw, kh=3, kw=3, pad=1, **x_n2)
+        self._norm_bwd(ws, layer.norm2, n2, red2, self._count(y1))
 
-    def _layer_conv1(self, ws, bi, li, dz2, pabc, fused, done):
+    def _flush_w2(self):
+        """Launch the collected 3x3 weight gradients of the current block (one batched launch per 24 layers; per layer when the
+        library declines the shape or the slab workspace)."""
+        items, self._w2_items = self._w2_items, []
+        for i in range(0, len(items), ops.L.WGRAD_BATCH_MAX):
+            part = items[i:i + ops.L.WGRAD_BATCH_MAX]
+            if not ops.conv3x3_wgrad_batch([item for item, _ in part]):
+                for (dyc, y1, _, _, dw), x_n2 in part:
+                    ops.conv_wgrad(dyc, y1, dw, kh=3, kw=3, pad=1, **x_n2)
+
+    def _layer_conv1(self, ws, bi, li, dz2, fused, done):
         """Layer li of block bi from dz2 into the gradient buffer's channels [0, cin): conv1's input gradient with relu1's mask and
         norm1's sums in its epilogue and conv1's weight gradient -- one kernel when `fused`, else two --, norm1's coefficients."""
-        s, v, G = self.slots, ws.v, self.grad_of
-        layer = self._layer(bi, li)
-        h, w = ws.hw[bi]
-        buf, gbuf, y1 = ws.buf[bi], ws.gbuf[bi], ws.y1[bi][li]
-        cin = self.blocks[bi][0] + li * self.growth
-        n1, S1, (bmean, brstd), (A, Bc) = s["n1"][bi][li], s["S1"][bi][li], s["bmr"][bi], s["AB"][bi]
-        pa, pb, pc = pabc
-        rows = ops.conv_gemm(dz2, self.w_bwd(layer.conv1), gbuf[..., :cin], N=cin, prologue=ops.PRO_AFFINE2, x2=y1, pa=pa,
-                             pb=pb, pc=pc, epilogue=ops.EPI_MASK, ex=buf[..., :cin], e_sc=v(n1[0]), e_sh=v(n1[1]),
-                             e_mu=v(bmean)[:cin], e_r=v(brstd)[:cin], e_scale=v(n1[0]), accumulate=True,
-                             fused_dw=G(layer.conv1.weight) if fused else None, **self._sp(ws, S1, cin))
-        red1 = self._sc(ws, S1, cin, rows)
+        G, blk, layer = self.grad_of, self.plan.blocks[bi], self._layer(bi, li)
+        L = blk.layers[li]
+        y1, cin = ws.y1[bi][li], L.n1.C
+        x = ws.buf[bi][..., :cin]
+        rows = ops.conv_gemm(dz2, self.w_bwd(layer.conv1), ws.gbuf[bi][..., :cin], N=cin, accumulate=True,
+                             fused_dw=G(layer.conv1.weight) if fused else None, **self._pro_bnbwd(ws, y1, L.n2),
+                             **self._mask(ws, x, L.n1, by_sc=True))
         if not fused:
-            ops.conv_wgrad(dz2, buf[..., :cin], G(layer.conv1.weight), g_prologue=ops.PRO_AFFINE2, g2=y1, ga=pa, gb=pb,
-                           gc=pc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(n1[0]), pb=v(n1[1]))
-        self.bn_bwd_coef(ws, layer.norm1, red1[0], red1[1], ws.B * h * w, layer.norm1.weight, v(bmean), v(brstd), G(layer.norm1.weight),
-                         G(layer.norm1.bias), v(A), v(Bc), None, None, None, cin, replicas=red1[2], rstride=red1[3],
-                         q=self._slice_q(ws, bi, li - 1))
+            ops.conv_wgrad(dz2, x, G(layer.conv1.weight), **self._g_bnbwd(ws, y1, L.n2), **self._x_bnrelu(ws, L.n1))
+        self._norm_bwd(ws, layer.norm1, L.n1, self._sc(ws, L.n1, rows, bwd=True), self._count(x), acc=blk, q=self._slice_q(ws, bi, li - 1))
         done(layer.norm1.weight)      # every gradient from this layer to the end of the buffer is final
 
     def _transition_backward(self, ws, bi, done):
         """BatchNorm transition feeding block bi: conv (on the pooled map) -> 2x2 average un-pooling with the ReLU mask and the
         norm's sums -> the norm's coefficients, into the gradient buffer of block bi - 1."""
-        s, v, G = self.slots, ws.v, self.grad_of
-        qa, qb, qc, _, c0 = self._slice_q(ws, bi, -1)         # written by layer 0's norm1 coefficient launch
+        v, G, prev = self._v, self.grad_of, self.plan.blocks[bi - 1]
+        q = self._slice_q(ws, bi, -1)                         # written by layer 0's norm1 coefficient launch
+        c0, cprev = q[4], prev.C
         gs, xs = ws.gbuf[bi][..., :c0], ws.buf[bi][..., :c0]
-        B, (h, w), (ph, pw) = ws.B, ws.hw[bi], ws.hw[bi - 1]
-        pc0, pn = self.blocks[bi - 1]
-        cprev = pc0 + pn * self.growth
+        B, (h, w) = ws.B, ws.hw[bi]
         tr = getattr(self.model.features, "transition%d" % bi)
         pbuf, pg = ws.buf[bi - 1], ws.gbuf[bi - 1]
-        nt, (pmean, prstd), (pA, pB), St = s["nt"][bi - 1], s["bmr"][bi - 1], s["AB"][bi - 1], s["St"][bi - 1]
         dpool = ws.dpool[:B * h * w * cprev].view(B, h, w, cprev)
-        ops.conv_gemm(gs, self.w_bwd(tr.conv), dpool, N=cprev, prologue=ops.PRO_AFFINE2, x2=xs, pa=qa, pb=qb, pc=qc)
-        rows = ops.unpool2_mask(dpool, pbuf, v(nt[0]), v(nt[1]), v(pmean), v(prstd), v(nt[0]), pg, *self._ew(ws, St, cprev))
-        sred = self._sc(ws, St, cprev, rows, copies=False)
-        ops.conv_wgrad(gs, pbuf, G(tr.conv.weight), mode=ops.MODE_POOL2, g_prologue=ops.PRO_AFFINE2, g2=xs, ga=qa, gb=qb,
-                       gc=qc, x_prologue=ops.PRO_AFFINE_RELU, pa=v(nt[0]), pb=v(nt[1]))
-        self.bn_bwd_coef(ws, tr.norm, sred[0], sred[1], B * ph * pw, tr.norm.weight, v(pmean), v(prstd), G(tr.norm.weight),
-                         G(tr.norm.bias), v(pA), v(pB), None, None, None, cprev, replicas=sred[2], rstride=sred[3],
-                         q=self._slice_q(ws, bi - 1, pn - 1))
+        ops.conv_gemm(gs, self.w_bwd(tr.conv), dpool, N=cprev, **self._pro_slice(xs, q))
+        rows = ops.unpool2_mask(dpool, pbuf, v(ws, prev.sc), v(ws, prev.sh), v(ws, prev.mean), v(ws, prev.rstd), v(ws, prev.sc), pg,
+                                *self._ew(ws, prev, bwd=True))
+        sred = self._sc(ws, prev, rows, bwd=True, copies=False)
+        ops.conv_wgrad(gs, pbuf, G(tr.conv.weight), mode=ops.MODE_POOL2, **self._g_slice(xs, q), **self._x_bnrelu(ws, prev))
+        self._norm_bwd(ws, tr.norm, prev, sred, self._count(pbuf), acc=prev, q=self._slice_q(ws, bi - 1, self.blocks[bi - 1][1] - 1))
         done(tr.norm.weight)
 
     def _stem_backward(self, ws, dx):
         """ImageNet stem: max-pool / ReLU / norm0 backward in one kernel, norm0's coefficients, conv0's weight (and input) gradient."""
-        f, s, v, G = self.model.features, self.slots, ws.v, self.grad_of
-        ci = self.c_init
-        qa, qb, qc = self._slice_q(ws, 0, -1)[:3]
+        f, v, G, S, ci = self.model.features, self._v, self.grad_of, self.plan.stem, self.c_init
         gs, xs = ws.gbuf[0][..., :ci], ws.buf[0][..., :ci]
-        n0, S0 = s["n0"], s["S0"]
-        rows = ops.bnrelu_maxpool_bwd(ws.c0, v(n0[0]), v(n0[1]), v(n0[2]), v(n0[3]), ws.amax, gs, xs, qa, qb, qc, ws.dz0,
-                                      *self._ew(ws, S0, ci))
-        sred = self._sc(ws, S0, ci, rows, copies=False)
-        pa, pb, pc = (v(t)[:ci] for t in s["p"])
-        self.bn_bwd_coef(ws, f.norm0, sred[0], sred[1], ws.B * (ws.H // 2) * (ws.W // 2), f.norm0.weight, v(n0[2]), v(n0[3]),
-                         G(f.norm0.weight), G(f.norm0.bias), None, None, pa, pb, pc, ci, replicas=sred[2], rstride=sred[3])
-        ops.conv_wgrad(ws.dz0, ws.x4, G(f.conv0.weight), mode=ops.MODE_STEM, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=pa, gb=pb,
-                       gc=pc)
+        rows = ops.bnrelu_maxpool_bwd(ws.c0, v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), ws.amax, gs, xs,
+                                      *self._slice_q(ws, 0, -1)[:3], ws.dz0, *self._ew(ws, S, bwd=True))
+        self._norm_bwd(ws, f.norm0, S, self._sc(ws, S, rows, bwd=True, copies=False), self._count(ws.c0))
+        ops.conv_wgrad(ws.dz0, ws.x4, G(f.conv0.weight), mode=ops.MODE_STEM, **self._g_bnbwd(ws, ws.c0, S))
         if dx is not None:
-            ops.stem_input_grad(ws.dz0, ws.c0, pa, pb, pc, f.conv0.weight, dx, stride=2, pad=3)
+            ops.stem_input_grad(ws.dz0, ws.c0, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), f.conv0.weight, dx, stride=2, pad=3)
 
     def _cifar_stem_backward(self, ws, dx):
         """Stem of the CIFAR form: relu0 mask + norm0 sums in the mask epilogue of the identity convolution (its two-tensor prologue
         applies the deferred BatchNorm correction to the gradient slice), then conv0's weight (and input) gradient."""
-        f, s, v, G = self.model.features, self.slots, ws.v, self.grad_of
-        ci = self.c_init
-        qa, qb, qc = self._slice_q(ws, 0, -1)[:3]
+        f, v, G, S, ci = self.model.features, self._v, self.grad_of, self.plan.stem, self.c_init
         gs, xs = ws.gbuf[0][..., :ci], ws.buf[0][..., :ci]
-        n0, S0 = s["n0"], s["S0"]
-        rows = ops.conv_gemm(gs, self.eye, ws.dz0, N=ci, prologue=ops.PRO_AFFINE2, x2=xs, pa=qa, pb=qb, pc=qc,
-                             epilogue=ops.EPI_MASK, ex=ws.c0, e_sc=v(n0[0]), e_sh=v(n0[1]), e_mu=v(n0[2]), e_r=v(n0[3]),
-                             e_scale=ws.ones[:ci], **self._sp(ws, S0, ci))
-        sred = self._sc(ws, S0, ci, rows)
-        pa, pb, pc = (v(t)[:ci] for t in s["p"])
-        self.bn_bwd_coef(ws, f.norm0, sred[0], sred[1], ws.B * ws.H * ws.W, f.norm0.weight, v(n0[2]), v(n0[3]), G(f.norm0.weight),
-                         G(f.norm0.bias), None, None, pa, pb, pc, ci, replicas=sred[2], rstride=sred[3])
-        ops.conv_wgrad(ws.dz0, ws.x8, G(f.conv0.weight), kh=5, kw=5, pad=2, g_prologue=ops.PRO_AFFINE2, g2=ws.c0, ga=pa, gb=pb,
-                       gc=pc)
+        rows = ops.conv_gemm(gs, self.eye, ws.dz0, N=ci, **self._pro_slice(xs, self._slice_q(ws, 0, -1)), **self._mask(ws, ws.c0, S))
+        self._norm_bwd(ws, f.norm0, S, self._sc(ws, S, rows, bwd=True), self._count(ws.c0))
+        ops.conv_wgrad(ws.dz0, ws.x8, G(f.conv0.weight), kh=5, kw=5, pad=2, **self._g_bnbwd(ws, ws.c0, S))
         if dx is not None:
-            ops.stem_input_grad(ws.dz0, ws.c0, pa, pb, pc, f.conv0.weight, dx, stride=1, pad=2)
+            ops.stem_input_grad(ws.dz0, ws.c0, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), f.conv0.weight, dx, stride=1, pad=2)
+
+    def _aa_backward(self, ws, bi, done):
+        """Backward of the AA transition feeding block bi (from block bi-1); qa/qb/qc apply the deferred BN correction
+        to the gradient slice [0, c0) of block bi."""
+        G, aa = self.grad_of, self._aa_transition(bi)
+        q = self._slice_q(ws, bi, -1)[:3]                     # written by layer 0's norm1 coefficient launch
+        buf, gbuf, pbuf, pg, T = ws.buf[bi], ws.gbuf[bi], ws.buf[bi - 1], ws.gbuf[bi - 1], ws.aa[bi - 1]
+        cc = aa.conv.out_channels
+        c0 = cc + aa.dv                          # (the block's entry width in the reference's networks; the padded twin's is wider)
+        Cp = pbuf.shape[3]
+        gs_c, xs_c, gs_a, xs_a = gbuf[..., :cc], buf[..., :cc], gbuf[..., cc:c0], buf[..., cc:c0]
+        q_c = [t[:cc] for t in q]
+        ops.aa_outproj_bwd(gs_a, xs_a, *(t[cc:c0] for t in q), T.O, aa.out_proj.weight, T.dO, G(aa.out_proj.weight))
+        ops.aa_attention_bwd(T.QKV, *aa.rel_tables(), T.O, T.dO, T.LSE, T.dQKV32, *aa.rel_grads(G), aa.nh, aa.dk, aa.dv)
+        if self.dtype == torch.float32:         # fp32 storage mode: the fp32 gradient is the convolution operand as it is
+            T.dQKV = T.dQKV32
+        else:
+            ops.f32_to_bf16(T.dQKV32, T.dQKV)
+        # (the 3x3 branch reaches every pixel and stores; the 1x1 branch only reaches the even-even ones: accumulating, its
+        # other parity classes are nothing to do)
+        ops.conv_gemm(gs_c, self.w_bwd(aa.conv), T.dA, N=Cp, kh=3, kw=3, pad=1, tstride=2, **self._pro_slice(xs_c, q_c))
+        ops.conv_gemm(T.dQKV, self.w_bwd(aa.in_proj_qkv), T.dA, N=Cp, tstride=2, accumulate=True)
+        ops.conv_wgrad(T.dQKV, T.A, G(aa.in_proj_qkv.weight), stride=2)
+        ops.conv_wgrad(gs_c, T.A, G(aa.conv.weight), kh=3, kw=3, stride=2, pad=1, **self._g_slice(xs_c, q_c))
+        ops.in_relu_bwd(T.dA, pbuf, T.coef[0], T.coef[1], T.S[0], T.S[1], pg)       # S: one owner per (image, channel), plain stores
+        done(aa.first_param())
 
     def _pair_backward(self, ws, bi, li, dz2_a, dz2_b, batch_w2, done):
         """Backward of dense layers li (a) and li - 1 (b) of block bi with ONE pass of the fused 1x1 backward over the channels
@@ -839,57 +866,41 @@ class _Engine(FusedEngine):
         b's output slice: b's gradient depends on them) -> the slice's coefficients -> b's 3x3 input gradient -> the pair pass ->
         both norm1 coefficient launches (a's first: the A / B accumulators then see the same additions in the same order as in
         the layer-by-layer schedule).  Per channel every sum has the same terms as layer by layer, in another fp32 order."""
-        s, v = self.slots, ws.v
-        g_ = self.growth
-        c0 = self.blocks[bi][0]
-        buf, gbuf = ws.buf[bi], ws.gbuf[bi]
-        h, w = ws.hw[bi]
-        cnt = ws.B * h * w
-        (bmean, brstd), (A, Bc) = s["bmr"][bi], s["AB"][bi]
-        G = self.grad_of
-        la, lb = self._layer(bi, li), self._layer(bi, li - 1)
-        cin_a, cin_b = c0 + li * g_, c0 + (li - 1) * g_
+        v, G, blk = self._v, self.grad_of, self.plan.blocks[bi]
+        buf, gbuf, cnt = ws.buf[bi], ws.gbuf[bi], self._count(ws.buf[bi])
+        la, lb, La, Lb = self._layer(bi, li), self._layer(bi, li - 1), blk.layers[li], blk.layers[li - 1]
+        cin_a, cin_b = La.n1.C, Lb.n1.C
 
-        def conv1_args(l_i, layer, dz2, pabc, lo, hi, stat):
+        def conv1_args(l_i, layer, dz2, lo, hi, stat):
             """conv_gemm arguments of the layer's fused 1x1 backward restricted to its input channels [lo, hi)"""
-            n1 = s["n1"][bi][l_i]
-            kw = dict(N=hi - lo, prologue=ops.PRO_AFFINE2, x2=ws.y1[bi][l_i], pa=pabc[0], pb=pabc[1], pc=pabc[2], epilogue=ops.EPI_MASK,
-                      ex=buf[..., lo:hi], e_sc=v(n1[0])[lo:hi], e_sh=v(n1[1])[lo:hi], e_mu=v(bmean)[lo:hi], e_r=v(brstd)[lo:hi],
-                      e_scale=v(n1[0])[lo:hi], accumulate=True, **stat)
+            L = blk.layers[l_i]
+            kw = dict(N=hi - lo, accumulate=True, **self._pro_bnbwd(ws, ws.y1[bi][l_i], L.n2),
+                      **self._mask(ws, buf, L.n1, by_sc=True, c_=slice(lo, hi), stat=stat))
             return dz2, self.w_bwd(layer.conv1)[lo * self.mid:hi * self.mid], gbuf[..., lo:hi], kw
 
-        def coef1(layer, red1, lo, hi, q):
-            if q is not None:
-                q = q[:3] + (q[3] - lo, q[4])
-            self.bn_bwd_coef(ws, layer.norm1, red1[0], red1[1], cnt, layer.norm1.weight[lo:hi], v(bmean)[lo:hi], v(brstd)[lo:hi],
-                             G(layer.norm1.weight)[lo:hi], G(layer.norm1.bias)[lo:hi], v(A)[lo:hi], v(Bc)[lo:hi], None, None, None, hi - lo,
-                             replicas=red1[2], rstride=red1[3], q=q, lo=lo)
-
-        def stat_region(slots, lo, n, part, parts):
-            """(producer keywords, consumer tuple-maker) for the statistics of channels [lo, lo + n) in one of `parts` regions"""
+        def stat_region(S, lo, n, part, parts):
+            """(producer keywords, consumer tuple-maker) for the backward sums of S's channels [lo, lo + n) in one of `parts` regions"""
             if self.det:
                 per = self.SLAB // parts
                 a, b_ = ws.slab[0][part * per:(part + 1) * per], ws.slab[1][part * per:(part + 1) * per]
                 return (dict(stat_sum=a, stat_sq=b_, stat_det=True, stat_replicas=per // n, stat_rstride=n), lambda rows: (a, b_, rows, n))
-            sa, sb = v(slots[0])[lo:], v(slots[1])[lo:]
-            return (dict(stat_sum=sa, stat_sq=sb, stat_replicas=self.stat_replicas, stat_rstride=slots[0][1]),
-                    lambda rows: (sa, sb, self.stat_replicas, slots[0][1]))
+            sa, sb, R, rstride = v(ws, S.S1)[lo:], v(ws, S.S2)[lo:], self.stat_replicas, S.S1[1]
+            return dict(stat_sum=sa, stat_sq=sb, stat_replicas=R, stat_rstride=rstride), lambda rows: (sa, sb, R, rstride)
 
-        S1a, S1b = s["S1"][bi][li], s["S1"][bi][li - 1]
-        pa_ = self._layer_front(ws, bi, li, dz2_a, batch_w2)
+        self._layer_front(ws, bi, li, dz2_a, batch_w2)
         # layer a on slice li - 1 alone
-        st_kw, st_red = stat_region(S1a, cin_b, g_, 0, 1)
-        x_, w_, y_, kw_ = conv1_args(li, la, dz2_a, pa_, cin_b, cin_a, st_kw)
+        st_kw, st_red = stat_region(La.n1, cin_b, self.growth, 0, 1)
+        x_, w_, y_, kw_ = conv1_args(li, la, dz2_a, cin_b, cin_a, st_kw)
         rows = ops.conv_gemm(x_, w_, y_, fused_dw=G(la.conv1.weight).view(self.mid, cin_a)[:, cin_b:], **kw_)
-        coef1(la, st_red(rows), cin_b, cin_a, self._slice_q(ws, bi, li - 1))
-        pb_ = self._layer_front(ws, bi, li - 1, dz2_b, batch_w2)
+        self._norm_bwd(ws, la.norm1, La.n1, st_red(rows), cnt, acc=blk, q=self._slice_q(ws, bi, li - 1), c_=slice(cin_b, cin_a))
+        self._layer_front(ws, bi, li - 1, dz2_b, batch_w2)
         # both layers on [0, cin_b)
-        sa_kw, sa_red = stat_region(S1a, 0, cin_b, 0, 2)
-        sb_kw, sb_red = stat_region(S1b, 0, cin_b, 1, 2)
-        rows = ops.conv1x1_bwd_pair(conv1_args(li, la, dz2_a, pa_, 0, cin_b, sa_kw), conv1_args(li - 1, lb, dz2_b, pb_, 0, cin_b, sb_kw),
+        sa_kw, sa_red = stat_region(La.n1, 0, cin_b, 0, 2)
+        sb_kw, sb_red = stat_region(Lb.n1, 0, cin_b, 1, 2)
+        rows = ops.conv1x1_bwd_pair(conv1_args(li, la, dz2_a, 0, cin_b, sa_kw), conv1_args(li - 1, lb, dz2_b, 0, cin_b, sb_kw),
                                     G(la.conv1.weight).view(self.mid, cin_a)[:, :cin_b], G(lb.conv1.weight).view(self.mid, cin_b))
-        coef1(la, sa_red(rows), 0, cin_b, None)
-        coef1(lb, sb_red(rows), 0, cin_b, self._slice_q(ws, bi, li - 2))
+        self._norm_bwd(ws, la.norm1, La.n1, sa_red(rows), cnt, acc=blk, c_=slice(0, cin_b))
+        self._norm_bwd(ws, lb.norm1, Lb.n1, sb_red(rows), cnt, acc=blk, q=self._slice_q(ws, bi, li - 2), c_=slice(0, cin_b))
         done(lb.norm1.weight)
 
     def _pre_bucket(self):

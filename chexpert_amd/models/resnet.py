@@ -273,30 +273,8 @@ class _Engine(FusedEngine):
                 kw[k] = kw[k][c_.start:]
         return kw
 
-    # ---- BatchNorm in the operand prologues / epilogues of the convolutions.  c_: the channel range of one group of a grouped
-    # convolution or of an AAConv2d branch (None: all channels)
-    @staticmethod
-    def _ch(t, c_):
-        return t if c_ is None else t[..., c_]
-
-    def _pro_bnrelu(self, ws, S, c_=None):
-        """forward: relu(bn_S(.)) of the operand"""
-        return dict(prologue=ops.PRO_AFFINE_RELU, pa=self._ch(self._v(ws, S.sc), c_), pb=self._ch(self._v(ws, S.sh), c_))
-
-    def _x_bnrelu(self, ws, S, c_=None):
-        """weight gradient: relu(bn_S(.)) of the activation operand"""
-        return dict(x_prologue=ops.PRO_AFFINE_RELU, pa=self._ch(self._v(ws, S.sc), c_), pb=self._ch(self._v(ws, S.sh), c_))
-
-    def _pro_bnbwd(self, ws, y, S, c_=None):
-        """input gradient: BatchNorm S's backward of the gradient operand, dY = dz * pa + y * pb + pc"""
-        ch, v = self._ch, self._v
-        return dict(prologue=ops.PRO_AFFINE2, x2=ch(y, c_), pa=ch(v(ws, S.pa), c_), pb=ch(v(ws, S.pb), c_), pc=ch(v(ws, S.pc), c_))
-
-    def _g_bnbwd(self, ws, y, S, c_=None):
-        """weight gradient: the same of its gradient operand"""
-        ch, v = self._ch, self._v
-        return dict(g_prologue=ops.PRO_AFFINE2, g2=ch(y, c_), ga=ch(v(ws, S.pa), c_), gb=ch(v(ws, S.pb), c_), gc=ch(v(ws, S.pc), c_))
-
+    # ---- BatchNorm in the epilogue of an input-gradient convolution (the prologue keywords are FusedEngine's).  c_: the channel
+    # range of one group of a grouped convolution or of an AAConv2d branch (None: all channels)
     def _mask(self, ws, y, S, c_=None, after=0):
         """input gradient: the epilogue that masks with [relu(bn_S(y)) > 0] and produces BatchNorm S's backward sums (_sp)"""
         ch, v = self._ch, self._v

@@ -21,9 +21,7 @@ model = model.to(dev).eval()
 eng = model._eng()
 with torch.no_grad():
     ws = eng.forward(synth.xray_batch(5, B, S).to(dev), False)
-buf = ws.buf[-1]
-nt = eng.slots["nt"][len(eng.blocks) - 1]
-sc, sh = ws.v(nt[0]), ws.v(nt[1])
+buf, sc, sh = eng.norm5_operands(ws)
 Bb, h, w, C = buf.shape
 W = model.classifier.weight.detach().contiguous().clone()
 cam = torch.empty(B, K, h * w, device=dev)

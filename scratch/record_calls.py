@@ -8,9 +8,12 @@ engine calls `lib.cx_*` itself and a tree that goes through those wrappers leave
 names of `_lib.SIGNATURES` and no other, as the library does.
 
     python scratch/record_calls.py [TREE] [--dump DIR]
+    python scratch/record_calls.py [TREE] --time
 
 TREE: the checkout to import chexpert_amd from (default: this one), so the script can be pointed at a checkout of another commit.
 Prints one line per configuration: name, number of calls, sha256 of the list.  --dump writes each list to DIR/<name>.txt (diff them).
+--time runs no configuration: it prints the median host time of one DenseNet121 step (forward + backward under the recorders, 20
+steps after 3) -- what the engine's Python costs per step, to compare two trees.
 
 What a call logs: the function's name and its arguments; a tensor as (index of its storage by first appearance, storage offset,
 shape, strides, dtype), anything else by repr.  Calls made directly on tensors are logged too when they write: `zero_`, `fill_`,
@@ -25,7 +28,7 @@ import torch
 from torch.overrides import TorchFunctionMode
 
 ROWS = 7
-SWITCHES = ("CHEXPERT_DET", "CHEXPERT_JOIN_FUSE", "CHEXPERT_FWD_JOIN_FUSE", "CHEXPERT_STREAM_LO")
+SWITCHES = ("CHEXPERT_DET", "CHEXPERT_JOIN_FUSE", "CHEXPERT_FWD_JOIN_FUSE", "CHEXPERT_STREAM_LO", "CHEXPERT_PAIR_BWD")
 # functions of ops that run for real: the helpers every wrapper uses, and the wrappers of the entry points the engines once called raw
 REAL = {"_nhwc", "_fn", "_dense", "_f32", "_out_hw", "dwconv_fwd", "dwconv_dgrad", "dwconv_wgrad", "gap_se_fwd", "scale_act_bc", "gap_affine_act",
         "se_bwd_fused", "se_act_bwd", "bn_lin_bwd_stats", "affine2_out", "scale_rows", "dropout_mask_dev", "counter_add", "mul_f32",
@@ -216,6 +219,38 @@ def main():
     bc = lambda: DenseNet(12, (2, 2, 2), 24, num_classes=5)          # growth 12: the channel-padded twin with the CIFAR stem
     run("densenet_bc_padded_det", bc, x32)
     run("densenet_bc_padded_fp32_det", bc, x32, fp32=True)
+    dense = lambda cfg=(2, 2, 2, 2), **kw: (lambda: DenseNet(32, cfg, 64, num_classes=5, **kw))
+    run("densenet_det", dense(), x64)
+    run("densenet_atomic", dense(), x64, env=atomic)
+    run("densenet_fp32_det", dense(), x64, fp32=True)
+    run("densenet_fp32_atomic", dense(), x64, fp32=True, env=atomic)
+    run("densenet_frozen_det", dense(), x64, train=False)
+    run("densenet_frozen_atomic", dense(), x64, train=False, env=atomic)
+    run("densenet_dx_det", dense(), x64, dx=True)
+    run("densenet_dx_frozen_atomic", dense(), x64, dx=True, train=False, env=atomic)
+    run("densenet_u8_det", dense(), u8)
+    run("densenet_reducer_det", dense(), x64, reducer=True)
+    run("densenet_reducer_atomic", dense(), x64, reducer=True, env=atomic)
+    run("densenet_after_eval_det", dense(), x64, eval_first=True)
+    run("densenet_drop_det", dense(drop_rate=0.25), x64)
+    run("densenet_drop_frozen_det", dense(drop_rate=0.25), x64, train=False)
+    run("densenet121_det", dense((6, 12, 24, 16)), x64)
+    run("densenet121_pair_all_det", dense((6, 12, 24, 16)), x64, env={"CHEXPERT_PAIR_BWD": "all"})
+    run("densenet121_pair_all_atomic", dense((6, 12, 24, 16)), x64, env={"CHEXPERT_PAIR_BWD": "all", **atomic})
+    run("densenet4352_pair_all_det", dense((4, 3, 5, 2)), x64, env={"CHEXPERT_PAIR_BWD": "all"})      # odd layer counts
+    run("densenet4352_pair_1_det", dense((4, 3, 5, 2)), x64, env={"CHEXPERT_PAIR_BWD": "1"})
+    apv = lambda S, v: dict(ap(S), v=v)        # (a share of attention channels that leaves these narrow transitions some)
+    run("densenet_aa_det", dense(attn_params=apv(64, .25)), x64)
+    run("densenet_aa_atomic", dense(attn_params=apv(64, .25)), x64, env=atomic)
+    run("densenet_aa_fp32_det", dense(attn_params=apv(64, .25)), x64, fp32=True)
+    run("densenet_aa_frozen_det", dense(attn_params=apv(64, .25)), x64, train=False)
+    run("densenet_aa_dx_det", dense(attn_params=apv(64, .25)), x64, dx=True)
+    bc3 = lambda **kw: (lambda: DenseNet(12, (3, 3, 3), 24, num_classes=5, **kw))
+    run("densenet_bc333_det", bc3(), x32)
+    run("densenet_bc333_fp32_det", bc3(), x32, fp32=True)
+    run("densenet_bc333_drop_det", bc3(drop_rate=0.2), x32)
+    run("densenet_bc333_aa_det", bc3(attn_params=apv(32, .7)), x32)
+    run("densenet_bc333_dx_frozen_det", bc3(), x32, dx=True, train=False)
     run("gradcam_hooks_efficientnet_b0", eff, x64, train=False, hooked=True)
     run("gradcam_maps_efficientnet_b0", eff, x64, train=False, cam=True)
     run("gradcam_maps_bottleneck", bott(), x64, train=False, cam=True)
@@ -224,9 +259,34 @@ def main():
     run("gradcam_hooks_densenet", lambda: DenseNet(32, (2, 2, 2, 2), 64, num_classes=5), x64, train=False, hooked=True)
 
 
+def time_steps(steps=20, warmup=3):
+    """Median host seconds of one DenseNet121 step (B = 2, 64x64) under the recorders."""
+    global TRACE
+    import time
+    from chexpert_amd.models import DenseNet
+    for k in SWITCHES:
+        os.environ.pop(k, None)
+    torch.manual_seed(0)
+    model = DenseNet(32, (6, 12, 24, 16), 64, num_classes=5).train()
+    eng = model._eng()
+    x, times = torch.randn(2, 3, 64, 64), []
+    for i in range(warmup + steps):
+        TRACE = Trace()                        # (a fresh list per step: the log does not grow)
+        t0 = time.perf_counter()
+        ws = eng.forward(x, True, record=True)
+        eng.backward(ws, torch.ones(ws.logits.shape, dtype=torch.float32))
+        eng.release(ws)
+        times.append(time.perf_counter() - t0)
+    times = sorted(times[warmup:])
+    print("densenet121 host step: median %.2f ms of %d" % (1e3 * times[len(times) // 2], steps), flush=True)
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
     DUMP = None
+    TIME = "--time" in argv
+    if TIME:
+        argv.remove("--time")
     if "--dump" in argv:
         i = argv.index("--dump")
         DUMP = argv[i + 1]
@@ -238,4 +298,4 @@ if __name__ == "__main__":
     assert os.path.abspath(chexpert_amd.__file__).startswith(os.path.abspath(tree)), chexpert_amd.__file__
     import chexpert_amd.ops
     patch(chexpert_amd)
-    main()
+    time_steps() if TIME else main()
