@@ -215,6 +215,8 @@ SIGNATURES = {
     "cx_boot_auc": [_vp, _i, _i, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _i, _vp],
     "cx_boot_sweep": [_vp, _i, _i, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                       _vp, _vp, _vp, _vp, _i, _vp],
+    "cx_calib_fit": [_vp, _vp, _i, _i, _i, _i, C.c_double, _i, _vp, _vp],
+    "cx_boot_calib": [_vp, _i, _i, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
     "cx_sal_points": [_vp, _vp, _f, _f, _f, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _i, _i, _i, _i, _vp],
     "cx_sal_accumulate": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "cx_sal_finish": [_vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

@@ -77,6 +77,15 @@
                         level: the interval of every named metric over the same kind of resamples (metrics.bootstrap_metrics): auroc, ap
                         (average precision), sens@S (sensitivity at specificity >= S), spec@S (specificity at sensitivity >= S), S inside
                         (0, 1) with at most 6 decimals, at most 8 operating points.  Not given (default): nothing more is computed or written
+  --calibrate temperature|platt   every eval_results_<tag>.json gets a calibration_<tag>.json beside it (rank 0): the per-class map
+                        p = sigmoid(a z + b) fitted on the GPU on that evaluation's logits (temperature: b = 0), ECE / MCE / Brier score
+                        before and after it, the reliability curves and, with --bootstrap B, the intervals of all six (same seed, unit
+                        and level as the AUROC intervals; conditional on the fit), plus reliability_<tag>.png.  --calibrate_smooth: Platt's
+                        smoothed targets (the cure for a separable class); --calibration_bins M (1 .. 64, default 15),
+                        --calibration_binning width|mass (equal-width bins of [0, 1) or equal-mass bins of the scores)
+  --calibration_from FILE   apply the fit stored in FILE (a calibration_<tag>.json, e.g. of another split) instead of fitting; exclusive with
+                        --calibrate.  Before / after measured on the split the map was fitted on is optimistic: fit on one split, report
+                        on another.  --calibration_bins alone applies no map and reports the uncalibrated metrics only
 
 Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N chexpert.py --train ...`; every rank holds a
 replica and a shard of each minibatch stream (per-rank BatchNorm statistics, averaged gradients: DDP semantics), the
@@ -189,6 +198,16 @@ def build_parser():
     p.add_argument("--bootstrap_alpha", type=float, default=0.05, metavar="A", help="the intervals cover 1 - A (default 0.05)")
     p.add_argument("--bootstrap_metrics", nargs="+", default=None, metavar="M",
                    help="with --bootstrap: intervals of these metrics (auroc, ap, sens@S, spec@S) into metrics_ci_<tag>.json")
+    p.add_argument("--calibrate", default=None, choices=["temperature", "platt"],
+                   help="fit a per-class calibration map on every evaluation's logits and write calibration_<tag>.json beside its results "
+                        "(before / after on the fitting split itself is optimistic)")
+    p.add_argument("--calibrate_smooth", action="store_true", help="with --calibrate: Platt's smoothed targets")
+    p.add_argument("--calibration_from", default=None, metavar="FILE",
+                   help="apply the fit stored in FILE (e.g. fitted on another split) instead of fitting; exclusive with --calibrate, whose "
+                        "before / after on the fitting split itself is optimistic")
+    p.add_argument("--calibration_bins", type=int, default=None, metavar="M",
+                   help="bins of ECE / MCE and of the reliability diagram (1 .. 64, default 15); alone: the uncalibrated metrics only")
+    p.add_argument("--calibration_binning", default="width", choices=["width", "mass"], help="equal-width or equal-mass bins")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -275,6 +294,19 @@ def parse_args(argv=None):
             M.parse_boot_metrics(names)
         except ValueError as e:
             parser.error("--bootstrap_metrics: %s" % e)
+    fit, stored, bins = getattr(args, "calibrate", None), getattr(args, "calibration_from", None), getattr(args, "calibration_bins", None)
+    if fit is not None and stored is not None:
+        parser.error("--calibrate fits a map and --calibration_from applies a stored one: give one of the two")
+    if fit is not None and fit not in ("temperature", "platt"):
+        parser.error("--calibrate takes temperature or platt (got %r)" % fit)
+    if getattr(args, "calibrate_smooth", False) and fit is None:
+        parser.error("--calibrate_smooth needs --calibrate (the smoothed targets belong to the fit)")
+    if bins is not None and not 1 <= bins <= 64:
+        parser.error("--calibration_bins takes 1 .. 64 bins (got %r)" % bins)
+    if getattr(args, "calibration_binning", "width") not in ("width", "mass"):
+        parser.error("--calibration_binning takes width or mass (got %r)" % args.calibration_binning)
+    if stored is not None and not os.path.isfile(stored):
+        parser.error("--calibration_from: no file %s" % stored)
     return args
 
 
@@ -337,6 +369,50 @@ def write_metrics_ci(args, tag, outputs, targets, groups=None):
         print("%s, mean over the classes: %.4f [%.4f, %.4f]" % (name, r["mean_auc"]["point"], r["mean_auc"]["lo"], r["mean_auc"]["hi"]))
     path = os.path.join(args.output_dir, metrics_ci_name(tag))
     json.dump(ci, open(path, "w"), indent=4)
+    return path
+
+
+def calibration_name(tag, stem="calibration", ext=".json"):
+    """File name of the calibration report that goes with <tag>.json: eval_results_step_5 -> calibration_step_5.json (the rule of
+    auc_ci_name: not the prefix `eval_results`); stem "reliability", ext ".png": the figure beside it."""
+    return stem + "_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ext
+
+
+def write_calibration(args, tag, outputs, targets, groups=None):
+    """With --calibrate, --calibration_from or --calibration_bins: the calibration report of the evaluation that wrote <tag>.json, into
+    calibration_<...>.json beside it -- the fit (fitted here or loaded), ECE / MCE / Brier and the reliability curves before and, where
+    a map is applied, after it, with intervals under --bootstrap B -- and the figure reliability_<...>.png.  Returns the json's path, or
+    None (none of the flags: nothing computed or written)."""
+    method, stored, bins = getattr(args, "calibrate", None), getattr(args, "calibration_from", None), getattr(args, "calibration_bins", None)
+    if method is None and stored is None and bins is None:
+        return None
+    from . import calibration as K
+    from . import vis
+    device, seed = "cuda:%d" % (args.cuda or 0), getattr(args, "bootstrap_seed", None)
+    kw = dict(bins=15 if bins is None else bins, binning=getattr(args, "calibration_binning", "width"), n_boot=getattr(args, "bootstrap", 0),
+              seed=args.seed if seed is None else seed, groups=groups, alpha=getattr(args, "bootstrap_alpha", 0.05), device=device)
+    fit = None
+    if method is not None:
+        fit = K.fit_calibration(outputs, targets, method=method, smooth=getattr(args, "calibrate_smooth", False), device=device)
+    elif stored is not None:
+        fit = K.load_calibration(stored)
+    report = {"fit": fit, "fitted_here": method is not None, "unit": getattr(args, "bootstrap_unit", "image")}
+    before = K.calibration_metrics(outputs, targets, None, **kw)
+    report.update({"ece_before": before["ece"], "mce_before": before["mce"], "brier_before": before["brier"],
+                   "reliability_before": before["reliability"]})
+    after = None
+    if fit is not None:
+        after = K.calibration_metrics(outputs, targets, fit, **kw)
+        report.update({"ece_after": after["ece"], "mce_after": after["mce"], "brier_after": after["brier"],
+                       "reliability_after": after["reliability"]})
+    for name in ("ece", "mce", "brier"):
+        vals = [np.nanmean(list(r[name]["point"].values())) if r is not None and len(r[name]["point"]) else float("nan") for r in (before, after)]
+        print("%s, mean over the classes: %.4f%s" % (name, vals[0], "" if after is None else " -> %.4f after the map" % vals[1]))
+    path = os.path.join(args.output_dir, calibration_name(tag))
+    json.dump(report, open(path, "w"), indent=4)
+    vis.reliability_diagram(before["reliability"], class_names(len(before["ece"]["point"])),
+                            os.path.join(args.output_dir, calibration_name(tag, "reliability", ".png")),
+                            after=None if after is None else after["reliability"])
     return path
 
 
@@ -913,6 +989,7 @@ def main(argv=None):
             json.dump(res, open(os.path.join(args.output_dir, tag + ".json"), "w"), indent=4)
             write_auc_ci(args, tag, o, t, boot_groups)
             write_metrics_ci(args, tag, o, t, boot_groups)
+            write_calibration(args, tag, o, t, boot_groups)
         return res
 
     def jitter(x_u8, step):
@@ -1039,6 +1116,7 @@ def main(argv=None):
             print("AUC:\n", pprint.pformat(res["aucs"]))
             write_auc_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
             write_metrics_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
+            write_calibration(args, "eval_results_ensemble", mean_out, tg, boot_groups)
     if args.visualize and rank == 0:
         # chexpert.py:556-563: Grad-CAM grids over the 'vis' subset (three examples per finding category), and for the
         # attention-augmented models the attention-map grids of the stored softmax weights

@@ -1353,6 +1353,65 @@ def boot_sweep(counts, order, offs, lens, n_units, points=()):
     return apnum, wpos.long() & 0xffffffff, wneg.long() & 0xffffffff, pts.long() & 0xffffffff      # the kernel's unsigned values
 
 
+# ---- calibration (calib.hip; chexpert_amd/calibration.py composes them and states them in numpy) ----
+CALIB_METHODS = {"temperature": 0, "platt": 1}                     # CX_CALIB_TEMPERATURE, CX_CALIB_PLATT of the header
+CALIB_MAX_ITER, CALIB_MAX_BINS = 1000, 64                          # CX_CALIB_MAX_ITER, CX_CALIB_MAX_BINS
+
+
+def calib_fit(logits, targets, method="temperature", smooth=False, g_tol=1e-10, max_iter=100):
+    """cx_calib_fit: the per-class calibration map u = a z + b of (N, C) logits against (N, C) targets (target < 0: the row is left
+    out of the class; positive iff target > 0.5), every class in one launch.  Returns a float64 (C, 8) tensor on the GPU: a, b,
+    nll_before, nll_after, gmax, lambda_min, iterations, status (0 converged, 1 iteration cap, 2 degenerate, 3 flat; 2 / 3 return the
+    identity).  ValueError before any launch: an unknown method, max_iter outside 1 .. CALIB_MAX_ITER, g_tol negative or NaN."""
+    require_cuda(logits, targets)
+    if method not in CALIB_METHODS:
+        raise ValueError("calib_fit: method %r (one of %s)" % (method, sorted(CALIB_METHODS)))
+    if not 1 <= int(max_iter) <= CALIB_MAX_ITER:
+        raise ValueError("calib_fit: max_iter must be inside 1 .. %d (got %r)" % (CALIB_MAX_ITER, max_iter))
+    if not float(g_tol) >= 0.0:
+        raise ValueError("calib_fit: g_tol must be >= 0 (got %r)" % (g_tol,))
+    assert logits.dim() == 2 and logits.shape == targets.shape, "logits / targets: (N, C) of one shape"
+    n, n_cls = logits.shape
+    z, t = logits.float().t().contiguous(), targets.float().t().contiguous()      # class-major (C, N)
+    out = torch.tensor([1.0, 0.0, float("nan"), float("nan"), float("nan"), float("nan"), 0.0, 2.0], dtype=torch.float64,
+                       device=logits.device).repeat(n_cls, 1)                     # what a class without rows is (N == 0: no launch)
+    check(lib().cx_calib_fit(ptr(z), ptr(t), n_cls, n, CALIB_METHODS[method], int(bool(smooth)), float(g_tol), int(max_iter), ptr(out),
+                             stream_ptr()), "cx_calib_fit")
+    return out
+
+
+def boot_calib(counts, order, conf, offs, lens, n_units, bins):
+    """cx_boot_calib: the integer bin sums behind ECE / MCE / Brier of every (replicate, class).  counts: as boot_auc takes them; order:
+    int32 device tensor holding lens[c] entries for class c from offs[c] (an entry = unit index | bin << 24 | label << 31); conf: int32
+    device tensor parallel to order, the fixed-point confidences read as uint32 (calibration.calibration_plan builds both); bins: M in
+    1 .. CALIB_MAX_BINS.  Returns int64 tensors wsum, wpos, csum (n_rep, C, M) and bnum (n_rep, C); csum and bnum hold the kernel's
+    uint64 (read them as such: .numpy().view(np.uint64)).  ValueError before any launch: offsets / lengths that do not fit the order
+    array, a conf of another length, bins outside 1 .. CALIB_MAX_BINS."""
+    require_cuda(counts, order, conf)
+    assert counts.dtype == torch.int32 and counts.dim() == 2 and counts.stride(1) == 1 and counts.shape[1] >= n_units, \
+        "counts: int32 (n_rep, >= n_units) rows"
+    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), "order: contiguous int32"
+    assert conf.dtype == torch.int32 and conf.dim() == 1 and conf.is_contiguous(), "conf: contiguous int32"
+    offs, lens, bins = [int(v) for v in offs], [int(v) for v in lens], int(bins)
+    n_cls, n_rep = len(lens), counts.shape[0]
+    if len(offs) != n_cls or any(n < 0 or o < 0 or o + n > order.numel() for o, n in zip(offs, lens)):
+        raise ValueError("boot_calib: offsets %s / lengths %s do not fit an order array of %d entries" % (offs, lens, order.numel()))
+    if conf.numel() != order.numel():
+        raise ValueError("boot_calib: %d confidences for %d entries" % (conf.numel(), order.numel()))
+    if not 1 <= bins <= CALIB_MAX_BINS:
+        raise ValueError("boot_calib: %d bins (1 .. %d are supported)" % (bins, CALIB_MAX_BINS))
+    wsum = torch.empty(n_rep, n_cls, bins, dtype=torch.int32, device=counts.device)
+    wpos = torch.empty_like(wsum)
+    csum = torch.empty(n_rep, n_cls, bins, dtype=torch.int64, device=counts.device)
+    bnum = torch.empty(n_rep, n_cls, dtype=torch.int64, device=counts.device)
+    if n_rep == 0 or n_cls == 0:
+        return wsum.long(), wpos.long(), csum, bnum
+    ld = counts.stride(0) if n_rep > 1 else counts.shape[1]
+    check(lib().cx_boot_calib(ptr(counts), ld, n_rep, ptr(order), ptr(conf), (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens), n_cls,
+                              bins, ptr(wsum), ptr(wpos), ptr(csum), ptr(bnum), int(n_units), stream_ptr()), "cx_boot_calib")
+    return wsum.long() & 0xffffffff, wpos.long() & 0xffffffff, csum, bnum      # the kernel's unsigned values
+
+
 # ---- pixel attribution maps (saliency.hip; chexpert_amd/saliency.py composes them and states them in numpy) ----
 SAL_MODES = {"none": 0, "sum": 1, "abs": 2, "max": 3}      # CX_SAL_NONE .. CX_SAL_MAX of the header
 SAL_PARTIALS = 128                                          # CX_SAL_PARTIALS

@@ -4,11 +4,13 @@ the eval-mode HIP path of chexpert_amd.models; reading / cropping is chexpert_am
 
   python predict.py <data.csv> <predictions.csv> --restore_path <checkpoint.pt | folder> [--model densenet121|resnet152]
                     [--batch_size 16] [--resize N] [--mini_data N] [--cuda 0] [--tta K]
-                    [--clahe [--clahe_grid GY GX] [--clahe_clip C]]
+                    [--clahe [--clahe_grid GY GX] [--clahe_clip C]] [--calibration FILE]
 
 --tta K averages the probabilities of K forwards per image: the image as decoded, and K - 1 random affine warps of it on the GPU
 (chexpert_amd/augment.py, cx_u8_affine).  --clahe equalises every uint8 batch on the GPU first (ops.u8_clahe, as the training command
 line's flag of the same name: a model trained with it is evaluated with it), before the forward and before each draw's warp.
+--calibration FILE applies the per-class map stored in a calibration_<tag>.json of the training command line (chexpert_amd/calibration.py):
+the probabilities are sigmoid(a z + b), under --tta before the mean over the K forwards.  Without the flag the output is unchanged.
 """
 import argparse
 import os
@@ -33,6 +35,8 @@ def build_parser():
     p.add_argument("--clahe", action="store_true", help="CLAHE contrast equalisation of the uint8 image (GPU), as chexpert.py --clahe")
     p.add_argument("--clahe_grid", type=int, nargs=2, default=[8, 8], metavar=("GY", "GX"), help="tiles per axis, each 1..16, dividing the crop size")
     p.add_argument("--clahe_clip", type=float, default=2.0, metavar="C", help="clip limit in multiples of the mean bin height (0: no clipping)")
+    p.add_argument("--calibration", default=None, metavar="FILE",
+                   help="a calibration_<tag>.json written by chexpert.py --calibrate: the probabilities become sigmoid(a z + b)")
     return p
 
 
@@ -48,11 +52,25 @@ def parse_args(argv=None):
             clahe_clip_count(args.clahe_clip, 1, 1)
         except ValueError as e:
             parser.error("--clahe: %s" % e)
+    if args.calibration is not None and not os.path.isfile(args.calibration):
+        parser.error("--calibration: no file %s" % args.calibration)
     return args
 
 
+def probabilities(logits, cal=None):
+    """The probabilities of a batch of logits: sigmoid(z) in fp32, or, with a fit (calibration.fit_calibration's dict, or what
+    calibration.load_calibration reads), sigmoid(a z + b) with the per-class a, b rounded to fp32.  The identity map (a = 1, b = 0)
+    gives the bits of the plain path: 1 * z + 0 is z."""
+    z = logits.float()
+    if cal is None:
+        return torch.sigmoid(z)
+    from .calibration import _map_of
+    a, b = (torch.from_numpy(v.astype(np.float32)).to(z.device) for v in _map_of(cal, z.shape[-1]))
+    return torch.sigmoid(z * a + b)
+
+
 @torch.no_grad()
-def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None):
+def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None, cal=None):
     """DataFrame indexed by study ('.../patient64541/study1') with one probability column per finding (predict.py:33-52).
 
     tta = K > 1 (test-time augmentation): per image the mean of K sigmoid probabilities, then the max over a study's views as
@@ -61,7 +79,8 @@ def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None):
     scale 0.95 .. 1.05, no shear (augment.TTA_RANGES) -- seeded by augment.tta_seed_of(tta_seed, draw, number of the minibatch):
     two calls agree bit for bit.  tta = 1 is the plain path.
 
-    clahe: an augment.Clahe (or None): the uint8 batch is equalised once on the GPU, before the forward and before each draw's warp."""
+    clahe: an augment.Clahe (or None): the uint8 batch is equalised once on the GPU, before the forward and before each draw's warp.
+    cal: a calibration fit (or None): every forward's probabilities are sigmoid(a z + b) (`probabilities`), before the mean over the draws."""
     import pandas as pd
     from .data import extract_patient_ids
     if tta < 1:
@@ -74,16 +93,16 @@ def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None):
         if clahe is not None:
             x = clahe(x)
         if tta == 1:
-            probs.append(torch.sigmoid(model(x).float()).cpu())
+            probs.append(probabilities(model(x), cal).cpu())
         else:
             from . import augment, ops
             if x.dtype != torch.uint8:
                 raise RuntimeError("test-time augmentation warps the decoded uint8 images (got %s)" % x.dtype)
-            p = torch.sigmoid(model(x).float())
+            p = probabilities(model(x), cal)
             for draw in range(1, tta):
                 mat = augment.affine_matrices(augment.tta_seed_of(tta_seed, draw, k // batch_size), x.shape[0], x.shape[-2], x.shape[-1],
                                               **augment.TTA_RANGES)
-                p = p + torch.sigmoid(model(ops.u8_affine(x, mat.to(device))).float())
+                p = p + probabilities(model(ops.u8_affine(x, mat.to(device))), cal)
             probs.append((p / tta).cpu())
         studies += list(extract_patient_ids(dataset, [it[2] for it in items]))
     df = pd.DataFrame(torch.cat(probs).numpy(), index=studies, columns=list(dataset.attr_names))
@@ -119,9 +138,13 @@ def main(argv=None):
     if args.clahe:
         from .augment import Clahe
         clahe = Clahe(args.clahe_grid, args.clahe_clip)
+    cal = None
+    if args.calibration is not None:
+        from .calibration import load_calibration
+        cal = load_calibration(args.calibration)
     for f in files:
         model.load_state_dict(torch.load(f, map_location=device)["state_dict"])
-        frames.append(predict(model, ds, args.batch_size, device, tta=args.tta, tta_seed=args.tta_seed, clahe=clahe))
+        frames.append(predict(model, ds, args.batch_size, device, tta=args.tta, tta_seed=args.tta_seed, clahe=clahe, cal=cal))
     df = frames[0] if len(frames) == 1 else sum(frames[1:], frames[0]) / float(len(frames))      # mean over checkpoints
     df.to_csv(args.output_path)
     return df

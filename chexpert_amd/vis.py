@@ -183,3 +183,42 @@ def visualize_saliency(imgs, labels, logits, maps, idents, attr_names, classes, 
         plt.close(fig)
         written.append(path)
     return written
+
+
+def reliability_diagram(reliability, attr_names, out_path, after=None):
+    """Reliability diagram of calibration.calibration_metrics' "reliability" entry: one panel per class with the diagonal, the curve
+    fraction positive against mean confidence over the non-empty bins (`reliability`: before the map; `after`, optional: with it), and
+    under it the bin weights of `reliability` as a bar strip at the bins' mean confidence.  Class keys may be ints or, after a json
+    round trip, strings.  Writes out_path (png) and returns it."""
+    plt = _plt()
+
+    def curve(rel, c):
+        get = lambda d: np.asarray(d[c] if c in d else d[str(c)], dtype=np.float64)
+        return get(rel["mean_conf"]), get(rel["frac_pos"]), get(rel["weight"])
+    C = len(reliability["weight"])
+    fig, axs = plt.subplots(2, max(C, 1), figsize=(3.0 * max(C, 1), 3.8), dpi=100, squeeze=False, sharex=True,
+                            gridspec_kw={"height_ratios": [4, 1]})
+    for c in range(C):
+        top, strip = axs[0][c], axs[1][c]
+        top.plot([0, 1], [0, 1], color="0.6", linestyle="--", linewidth=1)
+        x, y, w = curve(reliability, c)
+        ok = w > 0
+        top.plot(x[ok], y[ok], marker="o", markersize=3, linewidth=1, label="before" if after is not None else None)
+        if after is not None:
+            xa, ya, wa = curve(after, c)
+            top.plot(xa[wa > 0], ya[wa > 0], marker="s", markersize=3, linewidth=1, label="after")
+            top.legend(fontsize=7, loc="upper left")
+        top.set_xlim(0, 1)
+        top.set_ylim(0, 1)
+        top.set_title(attr_names[c] if c < len(attr_names) else "class %d" % c, fontsize=9)
+        if c == 0:
+            top.set_ylabel("fraction positive", fontsize=8)
+            strip.set_ylabel("weight", fontsize=8)
+        strip.bar(x[ok], w[ok], width=1.0 / max(int(reliability["bins"]), 1) * 0.8, color="0.4")
+        strip.set_xlabel("mean confidence", fontsize=8)
+        for ax in (top, strip):
+            ax.tick_params(labelsize=7)
+    fig.tight_layout()
+    plt.savefig(out_path, dpi=100)
+    plt.close(fig)
+    return out_path

@@ -872,6 +872,45 @@ int cx_boot_sweep(const uint32_t* counts, int ld, int n_rep, const int32_t* orde
                   const int32_t* len /* host, [C] */, int C, const int32_t* pt_type /* host, [P] */, const int32_t* pt_ppm /* host, [P] */,
                   int P, uint64_t* apnum, uint32_t* wpos, uint32_t* wneg, uint32_t* pts, int U, void* stream);
 
+/* Calibration of the predicted probabilities (calib.hip; chexpert_amd/calibration.py: fit_calibration, calibration_metrics, and the
+ * numpy statements fit_calibration_reference / calibration_sums_reference).
+ * cx_calib_fit fits, for every class c on its own, the map u = a_c z + b_c, p = sigmoid(u) (method CX_CALIB_PLATT; with
+ * CX_CALIB_TEMPERATURE b_c = 0 and only a_c = 1 / T_c is fitted).  logits and targets are fp32 (C, N), class-major and contiguous; a
+ * row with target < 0 is left out of its class, a row is positive iff target > 0.5.  The objective is the mean over the kept rows of
+ * softplus(u) - t u in fp64, softplus(u) = max(u, 0) + log1p(exp(-|u|)), t the 0 / 1 label or, smooth != 0, Platt's targets
+ * (N+ + 1) / (N+ + 2) and 1 / (N- + 2).  Damped Newton from the identity (a = 1, b = 0): gradient g and Hessian H of the mean loss,
+ * step d = (H + 1e-12 I)^-1 g, the step halved while the loss rises (above L (1 + 1e-12), the rounding of the sum), at most 40
+ * halvings; it stops when max |g| <= g_tol or after max_iter iterations.  out is fp64 (C, 8): a, b, nll_before, nll_after, gmax,
+ * lambda_min, iterations, status.  status 0: converged; 1: iteration cap, parameters kept; 2: degenerate (no kept row, no positive or
+ * no negative), the identity is returned; 3: flat -- the smallest eigenvalue of the last Hessian is below 1e-8 (separable or nearly
+ * separable data), the identity is returned (smooth is the cure).  With status 2 / 3 nll_after is the loss of the identity; with
+ * status 2 gmax and lambda_min are NaN, and both losses are NaN when no row is kept.  One 256-thread workgroup per class, fp64 sums
+ * reduced in one fixed order, no atomics: the same bits on every run.  Every loop is bounded by max_iter.  N == 0 or C == 0 returns 0
+ * without launching (out is left untouched).
+ * CX_EINVAL before anything is launched: C < 0, N < 0, an unknown method, max_iter outside [1, CX_CALIB_MAX_ITER], g_tol negative or
+ * NaN, a null pointer.  CX_EALIGN: logits / targets not 4-byte, out not 8-byte aligned.
+ * cx_boot_calib: the bin sums of every (replicate, class) over a count table as cx_boot_sweep reads it (counts, ld, n_rep; the sum of a
+ * count row is < 2^32).  order (device) holds len[c] entries for class c from order[offs[c]] (offs, len: HOST arrays): an entry is the
+ * row's unit index in bits 0-23, its bin in bits 24-29 and its label in bit 31; conf (device, parallel to order) holds the row's
+ * fixed-point confidence P = min(floor(p 2^32), 2^32 - 1).  With w = counts[r][unit], per bin b < M:
+ *   wsum[r][c][b] = sum w,  wpos[r][c][b] = sum w over the positives (uint32),  csum[r][c][b] = sum w P (uint64)
+ *   bnum[r][c]    = sum w umulhi(d, d),  d = 2^32 - 1 - P at a positive and P at a negative (uint64)
+ * so that, formed by the caller in float64 with G_b = |wpos_b 2^32 - csum_b| and W = sum_b wsum_b: ECE = sum_b G_b / (W 2^32),
+ * MCE = max over wsum_b > 0 of G_b / (wsum_b 2^32), Brier = bnum / (W 2^32) (below the exact value by less than 2^-31).
+ * Outputs are row-major (n_rep, C, M) and (n_rep, C), one writer per element; a class with len[c] == 0 gives zeros.  Unit indices
+ * >= U are CLAMPED to U - 1 and bins >= M to M - 1.  The entries may come in any order; listed ascending in bin (calibration_plan)
+ * a lane adds to its wave's LDS accumulators once per bin instead of once per entry.  One wave per (replicate, class); integer LDS
+ * atomics only (integer adds commute: the same bits on every run).
+ * CX_EINVAL: a null pointer, n_rep < 1, C < 1, a negative len[c] or offs[c].  CX_ESHAPE: M outside [1, CX_CALIB_MAX_BINS], U outside
+ * [1, CX_BOOT_MAX_UNITS], ld < U.  CX_EALIGN: counts / order / conf / wsum / wpos not 4-byte, csum / bnum not 8-byte aligned.
+ * Additive entry points of ABI 10.                                                                                              */
+enum { CX_CALIB_TEMPERATURE = 0, CX_CALIB_PLATT = 1, CX_CALIB_MAX_ITER = 1000, CX_CALIB_MAX_BINS = 64 };
+int cx_calib_fit(const float* logits, const float* targets, int C, int N, int method, int smooth, double g_tol, int max_iter, double* out,
+                 void* stream);
+int cx_boot_calib(const uint32_t* counts, int ld, int n_rep, const int32_t* order /* device */, const uint32_t* conf /* device */,
+                  const int64_t* offs /* host, [C] */, const int32_t* len /* host, [C] */, int C, int M, uint32_t* wsum, uint32_t* wpos,
+                  uint64_t* csum, uint64_t* bnum, int U, void* stream);
+
 /* Pixel attribution maps (saliency.hip; chexpert_amd/saliency.py: input_gradient, smoothgrad, integrated_gradients, and the numpy
  * statement of the three entry points, points_reference / accumulate_reference / finish_reference): the glue around the eval-mode
  * forward + backward with dx.  fp32 NCHW, N = 3 * H * W floats per row; every product and every sum below is rounded to fp32 on its
