@@ -118,6 +118,8 @@ SIGNATURES = {
     "cx_aucm_fwd_bwd": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _i, _i, _vp],
     "cx_aucm_aux_step": [_vp, _vp, _vp, _i, _vp],
     "cx_asl_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp],
+    "cx_mc3_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp],
+    "cx_mc3_collapse": [_vp, _vp, _vp, _i, _i, _vp],
     "cx_softmax_ce_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp],
     "cx_head_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "cx_gap_relu_bn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

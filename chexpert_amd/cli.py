@@ -30,7 +30,19 @@
                         rectangle (area 2 % .. 1/3 of the image, aspect 0.3 .. 3.3, as torchvision's RandomErasing) overwritten with the
                         grey level --erase_fill V (default 136, the dataset mean); labels do not change.  0 (default): off
   --uncertain POLICY    what an uncertain (-1) training label becomes: ones (the reference's U-Ones, default), zeros, ignore (it stays
-                        -1 and the loss skips it), ones_lsr / zeros_lsr (label smoothing: uniform in [0.55, 0.85] / [0, 0.3])
+                        -1 and the loss skips it), ones_lsr / zeros_lsr (label smoothing: uniform in [0.55, 0.85] / [0, 0.3]),
+                        multiclass (the paper's U-MultiClass: it stays -1 and is a class of its own).  multiclass is a different
+                        model, not a different table: every model family gets a head of 3 x n_classes outputs (negative, positive,
+                        uncertain per finding; --n_classes stays the number of findings) and trains a three-way softmax cross-entropy
+                        per finding, inside the fused step (FusedNet.set_loss(kind="multiclass"), cx_mc3_fwd_bwd) and, without
+                        --fused_optimizer, through loss.MultiClassUncertain.  Evaluation drops the uncertain output right after the
+                        forward (loss.collapse_multiclass: z = z_positive - z_negative, sigmoid(z) = p1 / (p0 + p1)), so the evaluation
+                        loss (cross-entropy on z), AUROC, --bootstrap*, --calibrate*, --plot_roc, --evaluate_ensemble and the
+                        eval_results files see (N, n_classes) logits as always.  The checkpoint carries `loss_state`; --restore
+                        refuses a checkpoint of the other head, both ways (evaluating a multiclass checkpoint needs the flag too).
+                        Works with --fused_optimizer --graph, --erase_prob and more than one rank.  Not with --loss other than bce,
+                        --pos_weight, --mixup / --cutmix (no soft-target form) or --visualize (the class indices of the CAM and
+                        saliency tools are head outputs)
   --pos_weight W        `auto` or n_classes floats: BCEWithLogitsLoss's pos_weight, inside the fused step too; auto = per class
                         (non-ignored negatives) / (positives) of the training labels, clamped to [1/16, 16]
   --loss {bce,aucm}     aucm: the AUC min-max-margin loss (Yuan et al., ICCV 2021; FusedNet.set_loss(kind="aucm"), loss.AUCMLoss) instead of
@@ -550,6 +562,43 @@ def focus_options(args):
     return None
 
 
+def multiclass_options(args):
+    """--uncertain multiclass checked before anything runs: whether the run trains (or evaluates) the three-way softmax head.  What
+    has no meaning for it is refused by naming both flags."""
+    if getattr(args, "uncertain", "ones") != "multiclass":
+        return False
+    loss, soft = getattr(args, "loss", "bce"), "the three-way softmax has no soft-target form (--erase_prob leaves the labels alone and is allowed)"
+    refused = [("--loss %s" % loss, loss != "bce", "the three-way softmax is this policy's loss"),
+               ("--pos_weight", getattr(args, "pos_weight", None) is not None, "it weights the positive term of a sigmoid loss"),
+               ("--mixup", getattr(args, "mixup", 0.0) > 0, soft), ("--cutmix", getattr(args, "cutmix", 0.0) > 0, soft),
+               ("--visualize", bool(getattr(args, "visualize", False)),
+                "the class indices of the CAM and saliency tools are head outputs, three per finding")]
+    for flag, on, why in refused:
+        if on:
+            raise ValueError("--uncertain multiclass cannot be combined with %s: %s" % (flag, why))
+    return True
+
+
+def head_width(args):
+    """Outputs of the classifier: --n_classes findings, three logits each under --uncertain multiclass."""
+    return args.n_classes * (3 if getattr(args, "uncertain", "ones") == "multiclass" else 1)
+
+
+def checkpoint_loss_kind(ck):
+    """The loss kind a checkpoint was trained with ('bce' where it carries no loss_state)."""
+    return (ck.get("loss_state") or {}).get("kind", "bce")
+
+
+def check_checkpoint_head(ck, multiclass, path):
+    """A checkpoint of a --uncertain multiclass run has a head of three outputs per finding, every other one a head of one: the two do
+    not load into each other, and the refusal says so before load_state_dict fails on a shape."""
+    kind = checkpoint_loss_kind(ck)
+    if (kind == "multiclass") != multiclass:
+        raise ValueError("--restore %s: the checkpoint was trained %s --uncertain multiclass (loss kind %r), this run is %s it: the heads "
+                         "differ (three outputs per finding against one)" % (path, "with" if kind == "multiclass" else "without", kind,
+                                                                             "with" if multiclass else "without"))
+
+
 def resolve_cam_classes(spec, n_classes):
     """--cam_classes as a list of class indices, or None when the flag is absent.  No value or `all`: every class."""
     if spec is None:
@@ -706,12 +755,13 @@ def make_model(args, device):
     optimizer_options(args)                                  # validated before a model is built
     group_options(args)
     sched = None
+    n_out = head_width(args)                                 # (three logits per finding under --uncertain multiclass)
 
     def ex():                                                # the constructor's keyword arguments, once `model` exists
         return fused_optimizer_kwargs(args, model)
     if name == "densenet121":
         model = densenet121(pretrained=args.pretrained)
-        model.classifier = nn.Linear(model.classifier.in_features, args.n_classes)
+        model.classifier = nn.Linear(model.classifier.in_features, n_out)
         nn.init.constant_(model.classifier.bias, 0)
         model = model.storage_dtype(args.dtype).to(device)
         opt = O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)
@@ -719,7 +769,7 @@ def make_model(args, device):
     if name in ("aadensenet121", "densenet121_attn_aug"):      # chexpert.py:474-480 (README row name accepted too)
         from .models import DenseNet
         size = args.resize or 320
-        model = DenseNet(32, (6, 12, 24, 16), 64, num_classes=args.n_classes,
+        model = DenseNet(32, (6, 12, 24, 16), 64, num_classes=n_out,
                          attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
         model = model.storage_dtype(args.dtype).to(device)
         if fused:
@@ -729,12 +779,12 @@ def make_model(args, device):
     if name == "resnet152":                                   # chexpert.py:481-486
         from .models import resnet152
         model = resnet152(pretrained=args.pretrained)
-        model.fc = nn.Linear(model.fc.in_features, args.n_classes)
+        model.fc = nn.Linear(model.fc.in_features, n_out)
         model = model.storage_dtype(args.dtype).to(device)
         return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
     if "efficientnet" in name:                                # chexpert.py:496-500
         from .models import construct_model
-        model = construct_model(name, n_classes=args.n_classes).storage_dtype(args.dtype).to(device)
+        model = construct_model(name, n_classes=n_out).storage_dtype(args.dtype).to(device)
         if fused:
             return model, O.FusedRMSprop(model, lr=args.lr, decay=args.lr_decay_factor, **ex()), "fused"
         opt = torch.optim.RMSprop(model.parameters(), lr=args.lr, momentum=0.9, eps=0.001)
@@ -742,7 +792,7 @@ def make_model(args, device):
     if name == "aaresnet152":                                 # chexpert.py:486-494
         from .models import Bottleneck, ResNet
         size = args.resize or 320
-        model = ResNet(Bottleneck, [3, 8, 36, 3], num_classes=args.n_classes,
+        model = ResNet(Bottleneck, [3, 8, 36, 3], num_classes=n_out,
                        attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
         model = model.storage_dtype(args.dtype).to(device)
         return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
@@ -750,17 +800,23 @@ def make_model(args, device):
 
 
 @torch.no_grad()
-def evaluate(model, ds, indices, batch_size, device, pre=None):
+def evaluate(model, ds, indices, batch_size, device, pre=None, collapse=False):
     """chexpert.py:198-211 on this rank's slice of the validation set; returns logits, targets, per-element losses, indices.
-    `pre`: the deterministic preprocessing of the uint8 batch on the GPU (--clahe), or None."""
+    `pre`: the deterministic preprocessing of the uint8 batch on the GPU (--clahe), or None.  `collapse`: the model has the three-way
+    head of --uncertain multiclass; its logits become binary ones right after the forward (loss.collapse_multiclass), so everything
+    from the element losses on sees (N, n_classes)."""
     model.eval()
     outs, tgts, losses, ids = [], [], [], []
     loss_fn = nn.BCEWithLogitsLoss(reduction="none")
     if bool((ds.targets < 0).any()):               # ignored labels in this table: their element losses are 0 (cx_bce_masked_fwd_bwd)
         from .loss import MaskedBCE
         loss_fn = MaskedBCE().elementwise
+    if collapse:
+        from .loss import collapse_multiclass
     for x, t, idx in batches(ds, indices, batch_size, False):
         o = model(x.to(device) if pre is None else pre(x.to(device)))
+        if collapse:
+            o = collapse_multiclass(o)
         losses.append(loss_fn(o, t.to(device)))
         outs.append(o)
         tgts.append(t.to(device))
@@ -771,10 +827,10 @@ def evaluate(model, ds, indices, batch_size, device, pre=None):
     return torch.cat(outs), torch.cat(tgts), torch.cat(losses), torch.cat(ids)
 
 
-def evaluate_sharded(model, ds, batch_size, device, rank, world, pre=None):
+def evaluate_sharded(model, ds, batch_size, device, rank, world, pre=None, collapse=False):
     """Every rank forwards indices rank::world; the (N,5) logits / targets / losses are gathered and put back in dataset order."""
     idx = list(range(len(ds)))[rank::world]
-    o, t, l, i = evaluate(model, ds, idx, batch_size, device, pre)
+    o, t, l, i = evaluate(model, ds, idx, batch_size, device, pre, collapse)
     o, t, l, i = (P.gather_rows(v) for v in (o, t, l, i))
     order = torch.argsort(i)
     return o[order].cpu(), t[order].cpu(), l[order].cpu()
@@ -805,10 +861,12 @@ def save_checkpoint(ckpt, optim_state, sched_state, args, max_records=10):
         torch.save(ckpt, os.path.join(d, "best_checkpoints", "checkpoint_%d.pt" % file_id))
 
 
-def restore(args, model, optimizer, scheduler, device):
+def restore(args, model, optimizer, scheduler, device, multiclass=False):
     """chexpert.py:504-518: model weights + step from the file; when training also `optim_<name>` / `sched_<name>` beside it.
-    Returns the checkpoint's `loss_state` entry (FusedNet.loss_state() of a --loss aucm, focal or asl run), or None."""
+    Returns the checkpoint's `loss_state` entry (FusedNet.loss_state() of a --loss aucm, focal or asl or --uncertain multiclass run),
+    or None.  A checkpoint whose head is not this run's (`multiclass`) is refused (ValueError) before anything is loaded."""
     ck = torch.load(args.restore, map_location=device)
+    check_checkpoint_head(ck, multiclass, args.restore)
     model.load_state_dict(model_weights(ck, args, args.restore))
     args.step = ck["global_step"]
     if args.train:
@@ -858,6 +916,7 @@ def main(argv=None):
     rank, world, local = P.dist_info()
     aucm = aucm_options(args, world)
     focus = focus_options(args)
+    multiclass = multiclass_options(args)
     if world > 1:
         # the process group comes first, before anything touches the GPU; one rank per GPU over RCCL ("nccl"), or ranks sharing
         # a device over gloo when the box has fewer GPUs than ranks (tests)
@@ -918,7 +977,12 @@ def main(argv=None):
     model, optimizer, scheduler = make_model(args, device)
     restored_loss = None
     if args.restore and os.path.isfile(args.restore):
-        restored_loss = restore(args, model, optimizer, scheduler, device)
+        try:
+            restored_loss = restore(args, model, optimizer, scheduler, device, multiclass)
+        except ValueError:
+            if train_loader is not None:
+                train_loader.close()
+            raise
     loss_fn = nn.BCEWithLogitsLoss(reduction="none")
     masked_loss = None
     if focus is not None:
@@ -940,6 +1004,14 @@ def main(argv=None):
     elif args.train and restored_loss is not None and restored_loss.get("kind") in ("focal", "asl"):
         train_loader.close()
         raise ValueError("--restore: the checkpoint was trained with --loss %s: pass it (and its flags) to go on training" % restored_loss["kind"])
+    elif multiclass:
+        # the fused step's loss and, by the same kernel, the autograd route's; a restored checkpoint brings its class weights
+        from .loss import MultiClassUncertain
+        model.set_loss(kind="multiclass")
+        if restored_loss is not None:
+            model.load_loss_state(restored_loss)
+        masked_loss = MultiClassUncertain()
+        masked_loss.class_weight = model.loss_class_weight      # one storage: the module reads what the model holds
     elif args.uncertain == "ignore" or pos_weight is not None:
         from .loss import MaskedBCE
         model.set_loss(ignore_negative=args.uncertain == "ignore", pos_weight=pos_weight)      # the fused step's loss
@@ -982,7 +1054,7 @@ def main(argv=None):
 
     def run_eval(tag):
         with averaged():
-            o, t, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe)
+            o, t, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, multiclass)
         res = M.compute_metrics(o, t, l)
         if rank == 0:
             print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
@@ -1073,7 +1145,7 @@ def main(argv=None):
                 if args.step % args.eval_interval == 0:
                     ema_sd = None
                     with averaged():
-                        res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe))
+                        res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, multiclass))
                         if ex.get("ema_decay") is not None and rank == 0:
                             ema_sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
                     if rank == 0:
@@ -1087,7 +1159,7 @@ def main(argv=None):
                         if aucm is not None:          # the auxiliary scalars are trained state: restore continues from them
                             sync_loss_aux()
                             ckpt["loss_state"] = model.loss_state()
-                        elif focus is not None:       # the loss's four numbers: restore checks the kind and puts them back
+                        elif focus is not None or multiclass:      # the loss's numbers: restore checks the kind and puts them back
                             ckpt["loss_state"] = model.loss_state()
                         save_checkpoint(ckpt, optimizer.state_dict(), sched_state, args)
                     model.train()
@@ -1105,8 +1177,10 @@ def main(argv=None):
         assert args.restore and os.path.isdir(args.restore), "Restore argument must be directory with saved checkpoints"
         outs, losses = [], []
         for c in sorted(f for f in os.listdir(args.restore) if f.startswith("checkpoint") and f.endswith(".pt")):
-            model.load_state_dict(model_weights(torch.load(os.path.join(args.restore, c), map_location=device), args, c))
-            o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe)
+            ck = torch.load(os.path.join(args.restore, c), map_location=device)
+            check_checkpoint_head(ck, multiclass, c)
+            model.load_state_dict(model_weights(ck, args, c))
+            o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, multiclass)
             outs.append(o)
             losses.append(l)
         mean_out = torch.stack(outs, 2).mean(2)                                                      # mean of logits, chexpert.py:233

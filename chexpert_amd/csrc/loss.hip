@@ -4,6 +4,8 @@
 //
 //   cx_bce_fwd_bwd, cx_bce_masked_fwd_bwd, cx_asl_fwd_bwd   sums over elements: one skeleton (elem_loss_kernel) over a per-element
 //                                                           term, four terms (plain, masked and weighted BCE, focal / asymmetric)
+//   cx_mc3_fwd_bwd, cx_mc3_collapse                         the same sum over elements of THREE logits each (U-MultiClass), in the
+//                                                           skeleton's sibling mc3_loss_kernel; the collapse to binary logits
 //   cx_softmax_ce_fwd_bwd                                   one wave per sample, its own final sum
 //   cx_aucm_fwd_bwd, cx_aucm_aux_step                       a function of each class's whole batch column: column trees, two passes
 #include "common.h"
@@ -183,6 +185,79 @@ int launch_elem_loss(const float* logits, const float* target, const float* pos_
   return launch_status();
 }
 
+// ---- three-way softmax over every finding (U-MultiClass) -----------------------------------------------------------------------
+// The U-MultiClass policy of the data set's paper (Irvin et al., "CheXpert", AAAI 2019): every finding owns three logits -- negative,
+// positive, uncertain -- and the loss is the softmax cross-entropy over them (include/chexpert_hip.h, cx_mc3_fwd_bwd).  Finding k of
+// row b reads logits[b][3k .. 3k+2]; its class comes from the (B, n) target table the sigmoid losses read: 2 where t < 0, 1 where
+// t >= 0.5 (the "positive" of aucm_kernel), else 0.  Nothing is ignored.
+//
+// Numerics.  m = max z, e_j = exp(z_j - m), s = (e0 + e1) + e2, and r = the sum of the two exponentials that are not the target's, in
+// index order.  Where the target's logit is the maximum (e_c = 1, s = 1 + r) the loss is log1p(r), else (m - z_c) + log(s); the
+// target's gradient is -r / s, never e_c / s - 1, and r is never s - e_c: a confident correct element (r ~ 1e-4) keeps every digit
+// where m + log(s) - z_c keeps three.
+__device__ __forceinline__ int mc3_class(const float t) { return t < 0.f ? 2 : (t >= 0.5f ? 1 : 0); }
+
+__device__ __forceinline__ void mc3_softmax(const float z0, const float z1, const float z2, float& m, float& e0, float& e1, float& e2,
+                                            float& s) {
+  m = fmaxf(fmaxf(z0, z1), z2);
+  e0 = expf(z0 - m);
+  e1 = expf(z1 - m);
+  e2 = expf(z2 - m);
+  s = (e0 + e1) + e2;
+}
+
+// The sibling of elem_loss_kernel for an element of three logits: one workgroup, thread t takes triples t, t + 256, ... of the B x n,
+// the sum in double (class weights take it where the weighted BCE's goes), the same fixed tree over LDS, stride and tree stated on
+// blockDim.x.  class_weight: (n, 3) or null; the term and its three gradients are multiplied by w[k][c], with 1.f where there is no
+// table, so a table of ones gives the bits of the call without one.
+__global__ __launch_bounds__(NT) void mc3_loss_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                      const float* __restrict__ class_weight, float* loss, float* loss_elem,
+                                                      float* dlogits, float grad_scale, int B, int n) {
+  __shared__ double red[NT];
+  const float invB = 1.f / B;
+  double acc = 0;
+  for (int i = threadIdx.x; i < B * n; i += blockDim.x) {
+    const size_t o = (size_t)i * 3;
+    const float z0 = logits[o], z1 = logits[o + 1], z2 = logits[o + 2];
+    const int c = mc3_class(target[i]);
+    const float w = class_weight ? class_weight[(i % n) * 3 + c] : 1.f;
+    float m, e0, e1, e2, s;
+    mc3_softmax(z0, z1, z2, m, e0, e1, e2, s);
+    const float zc = c == 0 ? z0 : (c == 1 ? z1 : z2);
+    const float r = c == 0 ? e1 + e2 : (c == 1 ? e0 + e2 : e0 + e1);
+    const float l = w * (zc == m ? log1pf(r) : (m - zc) + logf(s));
+    acc += l;
+    if (loss_elem) loss_elem[i] = l;
+    if (dlogits) {
+      dlogits[o] = w * ((c == 0 ? -r : e0) / s) * invB * grad_scale;
+      dlogits[o + 1] = w * ((c == 1 ? -r : e1) / s) * invB * grad_scale;
+      dlogits[o + 2] = w * ((c == 2 ? -r : e2) / s) * invB * grad_scale;
+    }
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = blockDim.x / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && loss) *loss = (float)(red[0] / B);
+}
+
+// What the three logits of a finding become at test time: z = z1 - z0, whose sigmoid is p1 / (p0 + p1), the softmax over the two
+// classes that are left when "uncertain" is dropped, and p_unc = e2 / s.  One thread per (b, k), no reduction.
+__global__ __launch_bounds__(NT) void mc3_collapse_kernel(const float* __restrict__ logits, float* __restrict__ z,
+                                                          float* __restrict__ p_unc, long long total) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const float z0 = logits[i * 3], z1 = logits[i * 3 + 1], z2 = logits[i * 3 + 2];
+  z[i] = z1 - z0;
+  if (p_unc) {
+    float m, e0, e1, e2, s;
+    mc3_softmax(z0, z1, z2, m, e0, e1, e2, s);
+    p_unc[i] = e2 / s;
+  }
+}
+
 // ---- softmax cross-entropy ------------------------------------------------------------------------------------------------------
 // one wave per sample: row maximum and sum of exponentials by DPP-free shuffles, loss = mean_b (logsumexp - logit[target]);
 // the per-sample terms are summed by ONE workgroup in sample order (bit-reproducible)
@@ -359,6 +434,21 @@ int cx_asl_fwd_bwd(const float* logits, const float* target, const float* pos_we
                    float* dlogits, float grad_scale, int B, int n_classes, void* stream) {
   if (!logits || !target || !focus || B < 1 || n_classes < 1 || (long long)B * n_classes > INT_MAX - NT) return CX_EINVAL;
   return launch_elem_loss<AslTerm>(logits, target, pos_weight, focus, loss, loss_elem, dlogits, grad_scale, B, n_classes, stream);
+}
+
+int cx_mc3_fwd_bwd(const float* logits, const float* target, const float* class_weight, float* loss, float* loss_elem, float* dlogits,
+                   float grad_scale, int B, int n, void* stream) {
+  if (!logits || !target || B < 1 || n < 1 || (long long)B * n > INT_MAX - NT) return CX_EINVAL;
+  hipLaunchKernelGGL(mc3_loss_kernel, dim3(1), dim3(NT), 0, as_stream(stream), logits, target, class_weight, loss, loss_elem, dlogits,
+                     grad_scale, B, n);
+  return launch_status();
+}
+
+int cx_mc3_collapse(const float* logits, float* z, float* p_unc, int B, int n, void* stream) {
+  if (!logits || !z || B < 1 || n < 1 || (long long)B * n > INT_MAX - NT) return CX_EINVAL;
+  const long long total = (long long)B * n;
+  hipLaunchKernelGGL(mc3_collapse_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, as_stream(stream), logits, z, p_unc, total);
+  return launch_status();
 }
 
 int cx_softmax_ce_fwd_bwd(const float* logits, const int64_t* target, float* loss, float* loss_elem, float* dlogits, float grad_scale,

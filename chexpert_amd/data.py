@@ -4,7 +4,8 @@
 the models' input kernels (cx_u8_to_nhwc4 / cx_u8_to_nhwc8), so a batch crosses PCIe at one byte per pixel.
 
 Labels follow dataset.py:134-153 (U-Ones): training rows get blanks -> 0 and uncertain (-1) -> 1 on the five competition findings;
-`uncertain=` selects the other policies of the dataset's paper (apply_uncertain: zeros, ignore, the two label-smoothed ones);
+`uncertain=` selects the other policies of the dataset's paper (apply_uncertain: zeros, ignore, the two label-smoothed ones, and
+multiclass, whose table is that of ignore);
 the validation file is used as it is; `test` mode reads a bare csv of paths with zero labels (dataset.py:33-37).  Nothing is
 downloaded here (no network): a missing data folder raises.
 """
@@ -18,7 +19,7 @@ ATTR_NAMES = ["Atelectasis", "Cardiomegaly", "Consolidation", "Edema", "Pleural 
 DIR_NAME = "CheXpert-v1.0-small"                                                                  # dataset.py:18-19
 
 
-UNCERTAIN_POLICIES = ("ones", "zeros", "ignore", "ones_lsr", "zeros_lsr")
+UNCERTAIN_POLICIES = ("ones", "zeros", "ignore", "ones_lsr", "zeros_lsr", "multiclass")
 _LSR_RANGE = {"ones_lsr": (0.55, 0.85), "zeros_lsr": (0.0, 0.3)}          # the label-smoothed U-Ones / U-Zeros variants
 
 
@@ -26,7 +27,9 @@ def apply_uncertain(labels, policy, seed=0):
     """What an uncertain label (-1) becomes under `policy` (dataset.py:119, :141 "setup options for uncertain labels"), on a float
     (N, C) numpy table whose blanks are already 0: 'ones' -> 1 (the reference's hard-wired U-Ones), 'zeros' -> 0, 'ignore' -> it
     stays -1 (the loss skips it: FusedNet.set_loss / MaskedBCE), 'ones_lsr' / 'zeros_lsr' -> a value uniform in [0.55, 0.85] /
-    [0, 0.3], drawn once from synth.uniform01 keyed by (seed, row, class).  Returns a new float32 table."""
+    [0, 0.3], drawn once from synth.uniform01 keyed by (seed, row, class), 'multiclass' -> it stays -1, as under 'ignore': the
+    U-MultiClass policy is a different model, not a different table (a three-way softmax per finding, in which -1 is the class
+    "uncertain": FusedNet.set_loss(kind="multiclass") / loss.MultiClassUncertain).  Returns a new float32 table."""
     if policy not in UNCERTAIN_POLICIES:
         raise ValueError("uncertain policy must be one of %s (got %r)" % (", ".join(UNCERTAIN_POLICIES), policy))
     lab = np.array(labels, dtype=np.float32)
@@ -35,7 +38,7 @@ def apply_uncertain(labels, policy, seed=0):
         lab[unc] = 1.0
     elif policy == "zeros":
         lab[unc] = 0.0
-    elif policy != "ignore":
+    elif policy not in ("ignore", "multiclass"):
         from . import synth
         lo, hi = _LSR_RANGE[policy]
         u = synth.uniform01(seed, lab.size).reshape(lab.shape)            # element (row, class) reads counter row * C + class

@@ -3,14 +3,17 @@ the device tensors the kernels of csrc/loss.hip read, with the one rule that pic
 the same losses outside the fused step -- `loss = MaskedBCE(w)(model(x), t); loss.backward()` and the element losses of an
 evaluation -- over the same `launch`, so the autograd route and the fused step run one kernel and agree bit for bit: MaskedBCE for
 the cross-entropy with uncertain-label handling (cx_bce_fwd_bwd / cx_bce_masked_fwd_bwd), AUCMLoss for kind "aucm" (cx_aucm_fwd_bwd),
-with its auxiliary scalars as parameters, FocalLoss and AsymmetricLoss for kinds "focal" and "asl" (cx_asl_fwd_bwd).  Device
-tensors only: there is no CPU path."""
+with its auxiliary scalars as parameters, FocalLoss and AsymmetricLoss for kinds "focal" and "asl" (cx_asl_fwd_bwd),
+MultiClassUncertain for kind "multiclass" (cx_mc3_fwd_bwd), the three-way softmax of the U-MultiClass policy, whose logits are (B, 3n)
+and which `collapse_multiclass` turns into binary ones (cx_mc3_collapse).  Device tensors only: there is no CPU path."""
 import torch
 import torch.nn as nn
 
 from . import ops
 
-KERNEL = {"bce": "cx_bce_masked_fwd_bwd", "aucm": "cx_aucm_fwd_bwd", "focal": "cx_asl_fwd_bwd", "asl": "cx_asl_fwd_bwd"}
+KERNEL = {"bce": "cx_bce_masked_fwd_bwd", "aucm": "cx_aucm_fwd_bwd", "focal": "cx_asl_fwd_bwd", "asl": "cx_asl_fwd_bwd",
+          "multiclass": "cx_mc3_fwd_bwd"}
+WIDTH = {"multiclass": 3}          # logits per target element, where it is not 1
 
 
 # ------------------------------------------------------------------------------------------------ the range checks, each once
@@ -41,6 +44,19 @@ def check_pos_weight(who, pos_weight, n=None):
     return w
 
 
+def check_class_weight(who, class_weight, n=None):
+    """None, or the weights of the three-way softmax as an fp32 (n, 3) table (on the device they came on), row k = the weights of
+    finding k's classes negative, positive, uncertain: finite, > 0, and n rows where n is given."""
+    if class_weight is None:
+        return None
+    w = torch.as_tensor(class_weight, dtype=torch.float32).detach()
+    shaped = w.dim() == 2 and w.shape[1] == 3 and w.shape[0] >= 1 and (n is None or w.shape[0] == n)
+    if not shaped or not bool(((w > 0) & torch.isfinite(w)).all()):
+        raise ValueError("%s takes finite class_weight > 0 of shape (%s, 3) (got shape %s: %s)"
+                         % (who, "n" if n is None else n, tuple(w.shape), w.tolist()))
+    return w
+
+
 def check_prior(who, prior, margin, n=None):
     """The class positive rates of the AUC-margin loss as a CPU fp32 vector: in (0, 1), n of them where n is given; margin > 0."""
     if prior is None:
@@ -57,28 +73,33 @@ def check_prior(who, prior, margin, n=None):
 
 # ------------------------------------------------------------------------------------------------ the loss of a step
 class Loss:
-    """The loss of a step: `kind` ('bce', 'aucm', 'focal', 'asl'), `ignore_negative`, `margin` (a host float, passed by value) and
-    the fp32 device tensors the kernels read -- `pos_weight` (n,), `focus` (4,) = [gamma+, gamma-, clip, alpha or -1], `aux` and
-    `daux` (3, n) = rows a, b, alpha and their gradients, `prior` (n,), `lr_aux` (1,) --, None where the kind has none.  Plain
+    """The loss of a step: `kind` ('bce', 'aucm', 'focal', 'asl', 'multiclass'), `ignore_negative`, `margin` (a host float, passed by
+    value) and the fp32 device tensors the kernels read -- `pos_weight` (n,), `focus` (4,) = [gamma+, gamma-, clip, alpha or -1],
+    `aux` and `daux` (3, n) = rows a, b, alpha and their gradients, `prior` (n,), `lr_aux` (1,), `class_weight` (n, 3) = the weights
+    of kind 'multiclass', whose head has 3n outputs --, None where the kind has none.  Plain
     tensors, neither buffers nor parameters.  Behind them stands held storage (`_held`, by name) that outlives a change of kind: a
     repeated set() with the same sizes copies into it, so a captured step, which replays the storage it was captured with, sees the
     new values.  FusedNet keeps one (set / state / load_state are its set_loss / loss_state / load_loss_state); a loss module makes
     one per call from its own attributes."""
 
     def __init__(self, kind="bce", ignore_negative=False, margin=1.0, pos_weight=None, focus=None, aux=None, daux=None, prior=None,
-                 lr_aux=None):
+                 lr_aux=None, class_weight=None):
         self.kind, self.ignore_negative, self.margin = kind, ignore_negative, margin
         self.pos_weight, self.focus, self.aux, self.daux, self.prior, self.lr_aux = pos_weight, focus, aux, daux, prior, lr_aux
+        self.class_weight = class_weight
         self._held = {}
 
     def launch(self, logits, target, loss, loss_elem, dlogits):
         """The loss (1,), the element losses (B, n) and d loss / d logits (B, n), each where given, in one launch.  The kernel is
         the kind's; for 'bce' the masked one when ignore_negative is set or there are weights (it skips every target < 0: the
-        weighted loss has no arithmetic for a negative target), else the plain one, to which a negative target is a number."""
+        weighted loss has no arithmetic for a negative target), else the plain one, to which a negative target is a number.  Kind
+        'multiclass' takes (B, 3n) logits and dlogits beside the (B, n) target and element losses."""
         if self.kind == "aucm":
             if loss_elem is not None:
                 raise RuntimeError("the AUC-margin loss has no element losses")
             ops.aucm_fwd_bwd(logits, target, self.prior, self.aux, self.margin, loss, None, dlogits, self.daux)
+        elif self.kind == "multiclass":
+            ops.mc3_fwd_bwd(logits, target, self.class_weight, loss, loss_elem, dlogits)
         elif self.kind in ("focal", "asl"):
             ops.asl_fwd_bwd(logits, target, self.pos_weight, self.focus, loss, loss_elem, dlogits)
         elif self.ignore_negative or self.pos_weight is not None:
@@ -100,7 +121,8 @@ class Loss:
             held.copy_(v)
         return held
 
-    def _put(self, who, dev, kind, ignore_negative, pos_weight=None, focus=None, prior=None, margin=None, lr_aux=None):
+    def _put(self, who, dev, kind, ignore_negative, pos_weight=None, focus=None, prior=None, margin=None, lr_aux=None,
+             class_weight=None):
         """The one place that writes the state, after every check: each field is assigned, to None where `kind` has none, so nothing
         of the previous kind is left over.  `aux` starts at zero coming from another kind and stays as trained coming from 'aucm';
         the margin stays what the last 'aucm' made it."""
@@ -111,15 +133,18 @@ class Loss:
         self.daux = self._hold("daux", zeros, dev, keep=True)
         self.pos_weight, self.focus = self._hold("pos_weight", pos_weight, dev), self._hold("focus", focus, dev)
         self.prior, self.lr_aux = self._hold("prior", prior, dev), self._hold("lr_aux", None if lr_aux is None else [lr_aux], dev)
+        self.class_weight = self._hold("class_weight", class_weight, dev)
         self.kind, self.ignore_negative = kind, ignore_negative
         if margin is not None:
             self.margin = float(margin)
 
     def set(self, dev, n, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
-            alpha=None, gamma_pos=None, gamma_neg=None, clip=None):
-        """FusedNet.set_loss for a model of n classes with its parameters on dev.  A refused call changes nothing."""
+            alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None):
+        """FusedNet.set_loss for a model whose head has n outputs, with its parameters on dev.  A refused call changes nothing."""
         if kind not in KERNEL:
-            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal' or 'asl' (got %r)" % (kind,))
+            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal', 'asl' or 'multiclass' (got %r)" % (kind,))
+        if kind != "multiclass" and class_weight is not None:
+            raise ValueError("set_loss: class_weight belongs to kind='multiclass'")
         if kind != "aucm" and (prior is not None or lr_aux is not None or margin != 1.0):
             raise ValueError("set_loss: prior, margin and lr_aux belong to kind='aucm'")
         if kind != "focal" and (gamma is not None or alpha is not None):
@@ -137,6 +162,13 @@ class Loss:
             if lr_aux is None or not float(lr_aux) > 0:
                 raise ValueError("%s needs lr_aux > 0, the rate of the auxiliary scalars (got %r)" % (who, lr_aux))
             self._put(who, dev, kind, True, prior=p, margin=margin, lr_aux=float(lr_aux))
+        elif kind == "multiclass":
+            if pos_weight is not None or ignore_negative:
+                raise ValueError("%s cannot be combined with pos_weight or ignore_negative: an uncertain label is a class of its "
+                                 "own there, and class_weight is this loss's weighting" % who)
+            if n % 3:
+                raise ValueError("%s needs a head of three outputs per finding (negative, positive, uncertain); this head has %d" % (who, n))
+            self._put(who, dev, kind, False, class_weight=check_class_weight(who, class_weight, n // 3))
         else:
             if kind == "focal":
                 g = 2.0 if gamma is None else gamma
@@ -158,6 +190,8 @@ class Loss:
              "lr_aux": None if self.lr_aux is None else float(self.lr_aux.item())}
         if self.focus is not None:
             d["focus"] = cpu(self.focus)
+        if self.kind == "multiclass":
+            d["class_weight"] = cpu(self.class_weight)
         return d
 
     def load_state(self, d, dev, n):
@@ -177,6 +211,8 @@ class Loss:
                 raise ValueError("load_loss_state: aux must be (3, %d) (got %s)" % (n, tuple(aux.shape)))
             self.set(dev, n, kind="aucm", prior=d["prior"], margin=d["margin"], lr_aux=d["lr_aux"])
             self.aux.copy_(aux)
+        elif kind == "multiclass":
+            self.set(dev, n, kind="multiclass", class_weight=d.get("class_weight"))
         elif kind != "bce":
             raise ValueError("load_loss_state: unknown loss kind %r" % (kind,))
         elif self.kind != "bce":               # (a model that holds the cross-entropy keeps its options)
@@ -184,11 +220,14 @@ class Loss:
 
 
 # ------------------------------------------------------------------------------------------------ the autograd route
-def _operands(logits, target, who, kernel):
+def _operands(logits, target, who, kind):
+    """The contiguous fp32 logits and targets of a loss module: (B, n) both, or (B, 3n) against (B, n) for kind 'multiclass'."""
+    width = WIDTH.get(kind, 1)
     if not logits.is_cuda:
-        raise RuntimeError("%s runs on the GPU only (%s); there is no CPU fallback" % (who, kernel))
-    if logits.dim() != 2 or tuple(target.shape) != tuple(logits.shape):
-        raise RuntimeError("%s takes (B, n) logits and targets of one shape (got %s and %s)" % (who, tuple(logits.shape), tuple(target.shape)))
+        raise RuntimeError("%s runs on the GPU only (%s); there is no CPU fallback" % (who, KERNEL[kind]))
+    if logits.dim() != 2 or logits.shape[1] % width or tuple(target.shape) != (logits.shape[0], logits.shape[1] // width):
+        raise RuntimeError("%s takes %s (got %s and %s)" % (who, "(B, n) logits and targets of one shape" if width == 1 else
+                                                            "(B, %dn) logits and (B, n) targets" % width, tuple(logits.shape), tuple(target.shape)))
     return logits.detach().contiguous().float(), target.detach().contiguous().float()
 
 
@@ -198,7 +237,7 @@ class _LossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, state, who, *aux):
-        x, t = _operands(logits, target, who, KERNEL[state.kind])
+        x, t = _operands(logits, target, who, state.kind)
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty_like(x)
         state.launch(x, t, loss, None, dl)
@@ -230,14 +269,14 @@ class _LossModule(nn.Module):
 
     def forward(self, logits, target):
         who = type(self).__name__
-        _operands(logits, target, who, KERNEL[self.kind])                  # (refuses a CPU tensor before anything is moved)
+        _operands(logits, target, who, self.kind)                          # (refuses a CPU tensor before anything is moved)
         return _LossFn.apply(logits, target, self._state(logits), who, *(getattr(self, name) for name in self._aux))
 
     @torch.no_grad()
     def elementwise(self, logits, target):
         """The (B, n) element losses (0 where ignored, and for a hard negative at or below the clip), outside autograd."""
-        x, t = _operands(logits, target, type(self).__name__, KERNEL[self.kind])
-        out = torch.empty_like(x)
+        x, t = _operands(logits, target, type(self).__name__, self.kind)
+        out = torch.empty(t.shape, dtype=torch.float32, device=x.device)
         self._state(x).launch(x, t, None, out, None)
         return out
 
@@ -339,3 +378,42 @@ class AsymmetricLoss(_FocusLoss):
 
     def __init__(self, gamma_pos=0.0, gamma_neg=4.0, clip=0.05, pos_weight=None):
         super().__init__(check_focus("AsymmetricLoss", gamma_pos, gamma_neg, clip, None), pos_weight)
+
+
+class MultiClassUncertain(_LossModule):
+    """The U-MultiClass policy of the data set's paper (Irvin et al., "CheXpert", AAAI 2019) as a loss: every finding has three logits
+    -- negative, positive, uncertain, columns 3k, 3k + 1, 3k + 2 of the (B, 3n) logits -- and the loss is the softmax cross-entropy
+    over them, summed over the findings and averaged over the batch.  The (B, n) target is the table the other losses read: class 2
+    where t < 0 (an uncertain label kept as -1), 1 where t >= 0.5, else 0; nothing is ignored and there is no soft-target form.
+    class_weight: None, or a finite (n, 3) table > 0 whose entry [k][c] multiplies the terms of finding k with class c.  The loss of
+    FusedNet.set_loss(kind="multiclass") for the autograd route, by the same kernel, bit for bit.  elementwise() gives the (B, n)
+    terms; collapse_multiclass() the binary logits an evaluation reads."""
+    kind = "multiclass"
+
+    def __init__(self, class_weight=None):
+        super().__init__()
+        self.class_weight = check_class_weight("MultiClassUncertain", class_weight)
+
+    def _state(self, logits):
+        self._on(logits.device, "class_weight")
+        if self.class_weight is not None and logits.shape[1] != 3 * self.class_weight.shape[0]:
+            raise RuntimeError("MultiClassUncertain holds %d findings, the logits have %d columns" % (self.class_weight.shape[0], logits.shape[1]))
+        return Loss("multiclass", False, class_weight=self.class_weight)
+
+
+@torch.no_grad()
+def collapse_multiclass(logits, return_uncertain=False):
+    """The binary logits of (B, 3n) three-way logits (cx_mc3_collapse): z (B, n) = z_positive - z_negative in fp32, so that sigmoid(z)
+    is the paper's test-time probability, the softmax over negative and positive with "uncertain" dropped; everything that takes
+    (B, n) logits -- evaluation losses, AUROC, bootstrap, calibration, ensembles -- takes z.  return_uncertain: (z, p_unc) with
+    p_unc (B, n) the softmax probability of "uncertain"."""
+    if not logits.is_cuda:
+        raise RuntimeError("collapse_multiclass runs on the GPU only (cx_mc3_collapse); there is no CPU fallback")
+    if logits.dim() != 2 or logits.shape[1] == 0 or logits.shape[1] % 3:
+        raise RuntimeError("collapse_multiclass takes (B, 3n) logits (got %s)" % (tuple(logits.shape),))
+    x = logits.detach().contiguous().float()
+    z = torch.empty(x.shape[0], x.shape[1] // 3, dtype=torch.float32, device=x.device)
+    p = torch.empty_like(z) if return_uncertain else None
+    if x.shape[0]:
+        ops.mc3_collapse(x, z, p)
+    return (z, p) if return_uncertain else z

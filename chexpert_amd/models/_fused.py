@@ -121,7 +121,7 @@ class FusedNet(nn.Module):
         self._loss = Loss()
 
     def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
-                 alpha=None, gamma_pos=None, gamma_neg=None, clip=None):
+                 alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None):
         """The loss of forward_backward.  ignore_negative: a target < 0 (an uncertain label kept as -1, the U-Ignore policy) adds no
         loss and no gradient; the divisor stays the batch size.  pos_weight: None, or n_classes positive-term weights as in torch's
         BCEWithLogitsLoss(pos_weight).  Either option routes the step through cx_bce_masked_fwd_bwd, which skips every target < 0:
@@ -162,9 +162,22 @@ class FusedNet(nn.Module):
         kind, or from no pos_weight to weights or back, needs a new capture; a change of VALUES -- `model.loss_focus[1] = 2`, or
         set_loss with the same kind and new numbers -- is seen by the next replay, so a gamma schedule needs none.  The
         data-parallel step needs nothing new (the sum over elements is averaged over the ranks like the cross-entropy's).  An
-        operand out of range, or a keyword of another kind, is a ValueError that changes nothing."""
+        operand out of range, or a keyword of another kind, is a ValueError that changes nothing.
+
+        kind="multiclass" (class_weight=None) is the U-MultiClass policy of the data set's paper (Irvin et al., AAAI 2019), a different
+        model rather than a different label table: the head has THREE outputs per finding -- columns 3k, 3k + 1, 3k + 2 are finding
+        k's negative, positive and uncertain logit -- and the loss is the softmax cross-entropy over each triple, summed over the
+        findings and averaged over the batch (cx_mc3_fwd_bwd; the arithmetic stands in include/chexpert_hip.h).  The target stays the
+        (B, n) table: class 2 where t < 0 (an uncertain label kept as -1), 1 where t >= 0.5, else 0; nothing is ignored and there is
+        no soft-target form.  The head width must be a multiple of 3; pos_weight and ignore_negative=True are refused.
+        class_weight: None, or a finite (n, 3) table > 0 whose entry [k][c] multiplies the terms of finding k with class c; it lives
+        in one fp32 tensor, `loss_class_weight`, neither buffer nor parameter, under the storage rule of the weights: a repeated call
+        with the same shape copies into the held storage, which a captured step's replay sees (as it sees an in-place change);
+        from no weights to weights or back needs a new capture.  Nothing changes per step, and the data-parallel step needs nothing
+        new.  At test time loss.collapse_multiclass(logits) gives the binary (B, n) logits z = z_positive - z_negative."""
         self._loss.set(next(self.parameters()).device, self._n_classes(), ignore_negative, pos_weight, kind=kind, prior=prior,
-                       margin=margin, lr_aux=lr_aux, gamma=gamma, alpha=alpha, gamma_pos=gamma_pos, gamma_neg=gamma_neg, clip=clip)
+                       margin=margin, lr_aux=lr_aux, gamma=gamma, alpha=alpha, gamma_pos=gamma_pos, gamma_neg=gamma_neg, clip=clip,
+                       class_weight=class_weight)
         return self
 
     def _n_classes(self):
@@ -173,15 +186,16 @@ class FusedNet(nn.Module):
 
     def loss_state(self):
         """What set_loss(kind=...) holds beyond the model's state_dict, as CPU tensors and floats: {kind, aux, prior, margin, lr_aux}
-        (aux, prior and lr_aux are None for kind 'bce').  Kinds 'focal' and 'asl' add `focus`, the four numbers of `loss_focus`.  A
-        checkpoint keeps it beside the weights."""
+        (aux, prior and lr_aux are None for kind 'bce').  Kinds 'focal' and 'asl' add `focus`, the four numbers of `loss_focus`, kind
+        'multiclass' adds `class_weight` (the (n, 3) table, or None).  A checkpoint keeps it beside the weights."""
         return self._loss.state()
 
     def load_loss_state(self, d):
         """Restores loss_state(): for kind 'aucm' the loss is set with the stored prior, margin and rate, and the auxiliary scalars
         are copied in (into the held storage when there is one for this number of classes).  Kind 'bce' leaves the options of
         the cross-entropy (ignore_negative, pos_weight) as they are.  Kinds 'focal' and 'asl' set the loss with the stored `focus`
-        (checked like set_loss's operands) and keep the pos_weight the model holds.  Returns self."""
+        (checked like set_loss's operands) and keep the pos_weight the model holds.  Kind 'multiclass' sets the loss with the stored
+        `class_weight`.  Returns self."""
         self._loss.load_state(d, next(self.parameters()).device, self._n_classes())
         return self
 
@@ -235,7 +249,8 @@ class FusedNet(nn.Module):
         positive term per class (same reduction, same divisor).  After set_loss(kind="aucm", ...) the loss is the AUC-margin loss,
         and a train-mode step ends with the update of its auxiliary scalars (`loss_aux`), from the gradients of this step; the
         eval-mode step computes the gradients and leaves `loss_aux` alone.  After set_loss(kind="focal" | "asl") the loss is the
-        focal / asymmetric loss (ops.asl_fwd_bwd), in either mode."""
+        focal / asymmetric loss (ops.asl_fwd_bwd), in either mode.  After set_loss(kind="multiclass") the logits are (B, 3n) against
+        the (B, n) target and the loss is the three-way softmax cross-entropy per finding (ops.mc3_fwd_bwd), in either mode."""
         eng = self._eng()
         if input_grad is not None:
             check_input_grad(input_grad, x)
@@ -256,7 +271,7 @@ class FusedNet(nn.Module):
 
 
 # what set_loss holds, readable on the model (read-only: set_loss writes; a tensor may be written in place)
-for _name in ("kind", "ignore_negative", "pos_weight", "margin", "aux", "prior", "lr_aux", "focus", "daux"):
+for _name in ("kind", "ignore_negative", "pos_weight", "margin", "aux", "prior", "lr_aux", "focus", "class_weight", "daux"):
     setattr(FusedNet, ("_loss_" if _name == "daux" else "loss_") + _name, property(lambda self, _name=_name: getattr(self._loss, _name)))
 
 

@@ -698,6 +698,43 @@ def asl_fwd_bwd(logits, target, pos_weight, focus, loss, loss_elem, dlogits, gra
                                B, n, stream_ptr()), "cx_asl_fwd_bwd")
 
 
+def _mc3_logits(logits):
+    """The (B, 3n) logits of the three-way softmax (AssertionError): contiguous fp32, three outputs per finding.  Returns (B, n)."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    assert logits.shape[0] >= 1 and logits.shape[1] >= 3 and logits.shape[1] % 3 == 0
+    return logits.shape[0], logits.shape[1] // 3
+
+
+def mc3_fwd_bwd(logits, target, class_weight, loss, loss_elem, dlogits, grad_scale=1.0):
+    """The three-way softmax cross-entropy of U-MultiClass with d loss / d logits in one launch (cx_mc3_fwd_bwd): logits (B, 3n), finding
+    k owning columns 3k (negative), 3k + 1 (positive), 3k + 2 (uncertain); target the (B, n) table, class 2 where t < 0, 1 where
+    t >= 0.5, else 0; class_weight fp32 (n, 3) or None.  loss (1,), loss_elem (B, n) and dlogits (B, 3n) are optional; grad_scale
+    multiplies dlogits alone."""
+    B, n = _mc3_logits(logits)
+    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (B, n)
+    assert class_weight is None or tuple(class_weight.shape) == (n, 3)
+    assert loss_elem is None or tuple(loss_elem.shape) == (B, n)
+    assert dlogits is None or tuple(dlogits.shape) == (B, 3 * n)
+    assert all(t is None or t.device == logits.device for t in (target, class_weight, loss, loss_elem, dlogits))
+    _f32(loss, n=1)
+    _f32(class_weight, loss_elem, dlogits)
+    require_cuda(logits, target, class_weight, loss, loss_elem, dlogits)
+    check(lib().cx_mc3_fwd_bwd(ptr(logits), ptr(target), ptr(class_weight), ptr(loss), ptr(loss_elem), ptr(dlogits), grad_scale, B, n,
+                               stream_ptr()), "cx_mc3_fwd_bwd")
+
+
+def mc3_collapse(logits, z, p_unc=None):
+    """The binary logits of (B, 3n) three-way logits (cx_mc3_collapse): z (B, n) = z1 - z0, whose sigmoid is p1 / (p0 + p1), and, where
+    given, p_unc (B, n), the softmax probability of "uncertain".  Returns z."""
+    B, n = _mc3_logits(logits)
+    assert z is not None and tuple(z.shape) == (B, n) and (p_unc is None or tuple(p_unc.shape) == (B, n))
+    assert all(t is None or t.device == logits.device for t in (z, p_unc))
+    _f32(z, p_unc)
+    require_cuda(logits, z, p_unc)
+    check(lib().cx_mc3_collapse(ptr(logits), ptr(z), ptr(p_unc), B, n, stream_ptr()), "cx_mc3_collapse")
+    return z
+
+
 def softmax_ce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):
     """CrossEntropyLoss forward + gradient in one launch (fp32 logits [B, n], int64 class indices [B])."""
     B, n = logits.shape

@@ -11,6 +11,11 @@ the eval-mode HIP path of chexpert_amd.models; reading / cropping is chexpert_am
 line's flag of the same name: a model trained with it is evaluated with it), before the forward and before each draw's warp.
 --calibration FILE applies the per-class map stored in a calibration_<tag>.json of the training command line (chexpert_amd/calibration.py):
 the probabilities are sigmoid(a z + b), under --tta before the mean over the K forwards.  Without the flag the output is unchanged.
+
+A checkpoint of a `--uncertain multiclass` run (three logits per finding: negative, positive, uncertain) is recognised by its
+classifier's row count: n rows build the usual head, 3n rows the wide one, whose logits are collapsed on the GPU right after every
+forward (loss.collapse_multiclass: z = z_positive - z_negative, sigmoid(z) = p1 / (p0 + p1)); --calibration and --tta then act on z.
+Any other count is an error, and the checkpoints of a folder must agree.
 """
 import argparse
 import os
@@ -69,8 +74,18 @@ def probabilities(logits, cal=None):
     return torch.sigmoid(z * a + b)
 
 
+def head_is_multiclass(state_dict, key, n, path=""):
+    """Whether the classifier `key` of a checkpoint's state_dict is the three-way head of a --uncertain multiclass run: False for n
+    rows, True for 3n; any other count is a ValueError that names both."""
+    rows = int(state_dict[key].shape[0])
+    if rows not in (n, 3 * n):
+        raise ValueError("checkpoint %s: %s has %d rows; the %d findings need %d (one logit each) or %d (three each: a --uncertain "
+                         "multiclass run)" % (path, key, rows, n, n, 3 * n))
+    return rows == 3 * n
+
+
 @torch.no_grad()
-def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None, cal=None):
+def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None, cal=None, collapse=False):
     """DataFrame indexed by study ('.../patient64541/study1') with one probability column per finding (predict.py:33-52).
 
     tta = K > 1 (test-time augmentation): per image the mean of K sigmoid probabilities, then the max over a study's views as
@@ -80,12 +95,20 @@ def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None, c
     two calls agree bit for bit.  tta = 1 is the plain path.
 
     clahe: an augment.Clahe (or None): the uint8 batch is equalised once on the GPU, before the forward and before each draw's warp.
-    cal: a calibration fit (or None): every forward's probabilities are sigmoid(a z + b) (`probabilities`), before the mean over the draws."""
+    cal: a calibration fit (or None): every forward's probabilities are sigmoid(a z + b) (`probabilities`), before the mean over the draws.
+    collapse: the model has the three-way head of a --uncertain multiclass run; every forward's (B, 3n) logits become the binary
+    z = z_positive - z_negative (loss.collapse_multiclass) before `probabilities`."""
     import pandas as pd
     from .data import extract_patient_ids
     if tta < 1:
         raise ValueError("tta must be >= 1")
     model.eval()
+    forward = model
+    if collapse:
+        from .loss import collapse_multiclass
+
+        def forward(xb):
+            return collapse_multiclass(model(xb))
     probs, studies = [], []
     for k in range(0, len(dataset), batch_size):
         items = [dataset[i] for i in range(k, min(k + batch_size, len(dataset)))]
@@ -93,16 +116,16 @@ def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None, c
         if clahe is not None:
             x = clahe(x)
         if tta == 1:
-            probs.append(probabilities(model(x), cal).cpu())
+            probs.append(probabilities(forward(x), cal).cpu())
         else:
             from . import augment, ops
             if x.dtype != torch.uint8:
                 raise RuntimeError("test-time augmentation warps the decoded uint8 images (got %s)" % x.dtype)
-            p = probabilities(model(x), cal)
+            p = probabilities(forward(x), cal)
             for draw in range(1, tta):
                 mat = augment.affine_matrices(augment.tta_seed_of(tta_seed, draw, k // batch_size), x.shape[0], x.shape[-2], x.shape[-1],
                                               **augment.TTA_RANGES)
-                p = p + probabilities(model(ops.u8_affine(x, mat.to(device))), cal)
+                p = p + probabilities(forward(ops.u8_affine(x, mat.to(device))), cal)
             probs.append((p / tta).cpu())
         studies += list(extract_patient_ids(dataset, [it[2] for it in items]))
     df = pd.DataFrame(torch.cat(probs).numpy(), index=studies, columns=list(dataset.attr_names))
@@ -120,13 +143,16 @@ def main(argv=None):
     device = torch.device("cuda:%d" % args.cuda)
     ds = ChexpertCSV(args.data_path, "test", args.resize, mini_data=args.mini_data)
     n = len(ds.attr_names)
-    if args.model == "densenet121":
-        model = densenet121(pretrained=False)
-        model.classifier = nn.Linear(model.classifier.in_features, n)
-    else:
-        model = resnet152(pretrained=False)
-        model.fc = nn.Linear(model.fc.in_features, n)
-    model = model.to(device)
+    key = "classifier.weight" if args.model == "densenet121" else "fc.weight"
+
+    def build(width):
+        if args.model == "densenet121":
+            net = densenet121(pretrained=False)
+            net.classifier = nn.Linear(net.classifier.in_features, width)
+        else:
+            net = resnet152(pretrained=False)
+            net.fc = nn.Linear(net.fc.in_features, width)
+        return net.to(device)
     if os.path.isdir(args.restore_path):
         files = sorted(os.path.join(args.restore_path, f) for f in os.listdir(args.restore_path)
                        if f.startswith("checkpoint") and f.endswith(".pt"))
@@ -142,9 +168,17 @@ def main(argv=None):
     if args.calibration is not None:
         from .calibration import load_calibration
         cal = load_calibration(args.calibration)
+    model = wide = None
     for f in files:
-        model.load_state_dict(torch.load(f, map_location=device)["state_dict"])
-        frames.append(predict(model, ds, args.batch_size, device, tta=args.tta, tta_seed=args.tta_seed, clahe=clahe, cal=cal))
+        sd = torch.load(f, map_location=device)["state_dict"]
+        w = head_is_multiclass(sd, key, n, f)
+        if model is None:                   # the first checkpoint's head decides; the others of a folder must agree
+            model, wide = build(n * (3 if w else 1)), w
+        elif w != wide:
+            raise ValueError("the checkpoints of %s disagree: %s has %d logits per finding, %s has %d" % (args.restore_path, files[0],
+                                                                                                       3 if wide else 1, f, 3 if w else 1))
+        model.load_state_dict(sd)
+        frames.append(predict(model, ds, args.batch_size, device, tta=args.tta, tta_seed=args.tta_seed, clahe=clahe, cal=cal, collapse=wide))
     df = frames[0] if len(frames) == 1 else sum(frames[1:], frames[0]) / float(len(frames))      # mean over checkpoints
     df.to_csv(args.output_path)
     return df

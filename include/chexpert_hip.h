@@ -394,6 +394,28 @@ int cx_aucm_aux_step(float* aux, const float* daux, const float* lr_aux_dev, int
  * focus are the caller's to keep in range.  Additive entry point of ABI 10 (no struct changed).                                  */
 int cx_asl_fwd_bwd(const float* logits, const float* target, const float* pos_weight, const float* focus, float* loss,
                    float* loss_elem, float* dlogits, float grad_scale, int B, int n_classes, void* stream);
+/* U-MultiClass (Irvin et al., "CheXpert", AAAI 2019): a three-way softmax cross-entropy per finding, with d loss / d logits, one launch
+ * (loss.hip).  The head has 3n outputs; finding k of row b owns logits[b][3k + 0] (negative), [3k + 1] (positive) and [3k + 2]
+ * (uncertain).  target: the (B, n) fp32 table of the sigmoid losses; the class of element (b, k) is c = 2 if t < 0, 1 if t >= 0.5,
+ * else 0.  Nothing is ignored and there is no soft-target form.  Per element, with (z0, z1, z2) its three logits:
+ *   m = max(z0, z1, z2);  e_j = expf(z_j - m);  s = (e0 + e1) + e2
+ *   r = the sum of the two e_j with j != c, added in index order (never s - e_c)
+ *   l = z_c == m ? log1pf(r) : (m - z_c) + logf(s)                                   = -log softmax_c
+ *   dl/dz_j = e_j / s for j != c,  -r / s for j == c (never e_c / s - 1)
+ * so a confident correct element keeps its digits (elements whose target logit leads by 4 .. 12: within 7e-7 of their float64 values
+ * in an fp32 model of this statement, where m + logf(s) - z_c is off by 4e-3 .. 1.3e-2).  class_weight: fp32 (n, 3) on the device,
+ * or NULL: l and its three gradients are multiplied by w[k][c]; a table of ones gives the bits of NULL.  loss = sum w l / B (sum over
+ * the findings, mean over the batch: the reduction and divisor of cx_bce_fwd_bwd; weights do not change the divisor), loss_elem (B, n)
+ * = w l, dlogits (B, 3n) = w dl/dz / B * grad_scale.  loss, loss_elem and dlogits may each be NULL.  One workgroup, the sum in double
+ * over a fixed tree, no atomics: bit-reproducible.  CX_EINVAL before anything is launched: NULL logits / target, B < 1, n < 1,
+ * B * n > INT_MAX - 256.  Additive entry points of ABI 10 (no struct changed).                                                     */
+int cx_mc3_fwd_bwd(const float* logits, const float* target, const float* class_weight, float* loss, float* loss_elem,
+                   float* dlogits, float grad_scale, int B, int n, void* stream);
+/* The test-time form of those logits: z[b][k] = z1 - z0 (one fp32 subtraction), so that sigmoid(z) = p1 / (p0 + p1), the softmax
+ * over the two classes left when "uncertain" is dropped -- everything that takes binary (B, n) logits takes z --, and, where p_unc is
+ * given, p_unc[b][k] = e2 / s with m, e, s as above.  One thread per (b, k), no reduction; any B * n <= INT_MAX - 256 (a whole
+ * validation table in one call).  CX_EINVAL before anything is launched: NULL logits / z, B < 1, n < 1, the size cap.            */
+int cx_mc3_collapse(const float* logits, float* z, float* p_unc, int B, int n, void* stream);
 /* loss = CrossEntropyLoss(logits, target) (mean over the batch of logsumexp - logit[target]);
  * dlogits = (softmax - onehot)/B * grad_scale; loss_elem (optional) = the per-sample terms
  * (models/test_model.py:118, :143, :331: the CIFAR harness criterion)                              */
