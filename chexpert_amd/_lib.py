@@ -184,6 +184,11 @@ SIGNATURES = {
     "cx_dwconv_dgrad_f32": [_vp] * 14 + [_i] * 9 + [_vp],
     "cx_dwconv_wgrad": [_vp] * 9 + [_i] * 7 + [_vp, C.c_int64, _vp],
     "cx_dwconv_wgrad_f32": [_vp] * 9 + [_i] * 7 + [_vp, C.c_int64, _vp],
+    "cx_pool_head_fwd": [_vp] * 6 + [_i] * 6 + [_vp],
+    "cx_pool_head_fwd_f32": [_vp] * 6 + [_i] * 6 + [_vp],
+    "cx_pool_head_bwd": [_vp] * 13 + [_i] * 8 + [_vp],
+    "cx_pool_head_bwd_f32": [_vp] * 13 + [_i] * 8 + [_vp],
+    "cx_pool_p_grad": [_vp] * 5 + [_i, _i, _vp],
     "cx_gap_affine_act": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_int64, _vp],
     "cx_gap_affine_act_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_int64, _vp],
     "cx_se_fwd": [_vp] * 7 + [_i, _i, _i, _vp],

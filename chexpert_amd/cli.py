@@ -58,6 +58,12 @@
                         auto), --mixup / --cutmix / --erase_prob, --fused_optimizer --graph and more than one rank.  The evaluation
                         loss in eval_results stays the (masked) cross-entropy, so it can be compared across training losses; the
                         checkpoint carries the loss's four numbers (`loss_state`), which --restore puts back
+  --pool KIND           the global pooling in front of the classifier (FusedNet.set_pool, csrc/pool_head.hip): avg (default), max, lse
+                        (log-sum-exp, --pool_r R: sharpness, default 10) or gem (generalised mean, --pool_p P: start of the trained
+                        exponent in [1, 16], default 3); every --model, with --fused_optimizer --graph and more than one rank.  The
+                        checkpoint of another pooling than the average carries `pool_state`; --restore, --evaluate_*, --visualize and predict.py read the kind from it, a
+                        --pool that names another kind is refused.  Grad-CAM and --cam_classes assume the average: --visualize on
+                        another pooling draws the --saliency figures only
   --cam_classes [C ...] with --visualize: class-specific maps (gradcam.class_cam) of the 'vis' subset for these class indices (no value
                         or `all`: every class): vis/class_cam_lowres.npy (N, K, h, w) and one vis/classcam_<ident>_step_<N>.png per image
   --saliency METHOD     with --visualize: full-resolution, class-specific pixel attributions (chexpert_amd/saliency.py) of the 'vis' subset:
@@ -220,6 +226,11 @@ def build_parser():
     p.add_argument("--calibration_bins", type=int, default=None, metavar="M",
                    help="bins of ECE / MCE and of the reliability diagram (1 .. 64, default 15); alone: the uncalibrated metrics only")
     p.add_argument("--calibration_binning", default="width", choices=["width", "mass"], help="equal-width or equal-mass bins")
+    p.add_argument("--pool", default=None, choices=["avg", "max", "lse", "gem"],
+                   help="global pooling in front of the classifier (FusedNet.set_pool; default: the checkpoint's, else the average): the "
+                        "maximum, log-sum-exp with sharpness --pool_r, or the generalised mean with the trained exponent --pool_p")
+    p.add_argument("--pool_r", type=float, default=None, metavar="R", help="with --pool lse: the sharpness r > 0 (default 10)")
+    p.add_argument("--pool_p", type=float, default=None, metavar="P", help="with --pool gem: the exponent's start in [1, 16] (default 3)")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -319,6 +330,13 @@ def parse_args(argv=None):
         parser.error("--calibration_binning takes width or mass (got %r)" % args.calibration_binning)
     if stored is not None and not os.path.isfile(stored):
         parser.error("--calibration_from: no file %s" % stored)
+    try:
+        pool = resolve_pool(args)
+    except ValueError as e:
+        parser.error(str(e))
+    why = visualize_needs_avg(args, pool["kind"] if pool else "avg")
+    if why:
+        parser.error(why)
     return args
 
 
@@ -599,6 +617,72 @@ def check_checkpoint_head(ck, multiclass, path):
                                                                              "with" if multiclass else "without"))
 
 
+def resolve_pool(args):
+    """--pool / --pool_r / --pool_p checked before anything runs: None when --pool is absent (the checkpoint's pooling, else the
+    average), or the keywords of FusedNet.set_pool.  --pool_r belongs to lse and --pool_p to gem (ValueError otherwise)."""
+    from .pooling import DEFAULT_P, DEFAULT_R, check_pool
+    kind, r, p = getattr(args, "pool", None), getattr(args, "pool_r", None), getattr(args, "pool_p", None)
+    if r is not None and kind != "lse":
+        raise ValueError("--pool_r is the sharpness of --pool lse: pass --pool lse with it")
+    if p is not None and kind != "gem":
+        raise ValueError("--pool_p is the exponent of --pool gem: pass --pool gem with it")
+    if kind is None:
+        return None
+    try:
+        kind, r, p = check_pool(kind, DEFAULT_R if r is None else r, DEFAULT_P if p is None else p)
+    except ValueError as e:
+        raise ValueError("--pool: %s" % e)
+    return {"kind": kind, "r": r, "p": p}
+
+
+def pool_for_checkpoint(pool, ck_pool):
+    """The keywords of set_pool for a model that takes a checkpoint's weights: the checkpoint's `pool_state` (none: the average, a
+    checkpoint from before the flag) decides the kind, and a --pool flag (`pool`: resolve_pool's dict, or None) that names another
+    kind is refused -- before load_state_dict would fail on `pool_p` / `pool_r`.  r and p then come with the weights."""
+    ck_kind = (ck_pool or {}).get("kind", "avg")
+    if pool is not None and pool["kind"] != ck_kind:
+        raise ValueError("--pool %s contradicts the checkpoint, which was trained with --pool %s: drop the flag, or pass the "
+                         "checkpoint's" % (pool["kind"], ck_kind))
+    out = {"kind": ck_kind}
+    if ck_kind == "lse":
+        out["r"] = (ck_pool or {}).get("r") or (pool or {}).get("r") or 10.0
+    if ck_kind == "gem" and pool is not None:
+        out["p"] = pool["p"]
+    return out
+
+
+def restore_pool(args, pool):
+    """What make_model hands set_pool: --pool without --restore; with --restore the pool_state of the checkpoint file (of the first
+    checkpoint of a folder), checked against the flag (pool_for_checkpoint)."""
+    path = args.restore
+    if path and os.path.isdir(path):
+        files = sorted(f for f in os.listdir(path) if f.startswith("checkpoint") and f.endswith(".pt"))
+        path = os.path.join(path, files[0]) if files else None
+    if not path or not os.path.isfile(path):
+        return {k: v for k, v in (pool or {"kind": "avg"}).items() if v is not None}
+    return pool_for_checkpoint(pool, torch.load(path, map_location="cpu").get("pool_state"))
+
+
+def check_checkpoint_pool(ck, model, path):
+    """A checkpoint whose pooling is not the model's is refused (ValueError) before load_state_dict."""
+    kind = (ck.get("pool_state") or {}).get("kind", "avg")
+    if kind != model.pool_kind:
+        raise ValueError("checkpoint %s was trained with --pool %s, the model was built with --pool %s" % (path, kind, model.pool_kind))
+
+
+def visualize_needs_avg(args, kind):
+    """Why --visualize cannot draw what was asked for on a model that pools with `kind` (None: it can).  Grad-CAM and the class
+    maps read the head as an average; the saliency maps (--saliency) work with every pooling, and are then the only figures."""
+    if kind == "avg" or not getattr(args, "visualize", False):
+        return None
+    if getattr(args, "cam_classes", None) is not None:
+        return "--cam_classes draws class activation maps, which assume the average pool: not with --pool %s" % kind
+    if getattr(args, "saliency", None) is None:
+        return ("--visualize draws Grad-CAM maps, which assume the average pool: with --pool %s pass --saliency (pixel attribution works "
+                "with every pooling)" % kind)
+    return None
+
+
 def resolve_cam_classes(spec, n_classes):
     """--cam_classes as a list of class indices, or None when the flag is absent.  No value or `all`: every class."""
     if spec is None:
@@ -746,8 +830,9 @@ def model_weights(ck, args, path=""):
     return ck["state_dict"]
 
 
-def make_model(args, device):
-    """Model zoo and optimiser wiring of chexpert.py:461-502."""
+def make_model(args, device, pool=None):
+    """Model zoo and optimiser wiring of chexpert.py:461-502.  pool: the keywords of FusedNet.set_pool (None: the average), applied
+    before the optimiser is built -- GeM's exponent is one of its parameters."""
     from . import optim as O
     from .models import densenet121
     name = args.model
@@ -756,6 +841,7 @@ def make_model(args, device):
     group_options(args)
     sched = None
     n_out = head_width(args)                                 # (three logits per finding under --uncertain multiclass)
+    pool = pool or {}
 
     def ex():                                                # the constructor's keyword arguments, once `model` exists
         return fused_optimizer_kwargs(args, model)
@@ -763,7 +849,7 @@ def make_model(args, device):
         model = densenet121(pretrained=args.pretrained)
         model.classifier = nn.Linear(model.classifier.in_features, n_out)
         nn.init.constant_(model.classifier.bias, 0)
-        model = model.storage_dtype(args.dtype).to(device)
+        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool)
         opt = O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)
         return model, opt, None
     if name in ("aadensenet121", "densenet121_attn_aug"):      # chexpert.py:474-480 (README row name accepted too)
@@ -771,7 +857,7 @@ def make_model(args, device):
         size = args.resize or 320
         model = DenseNet(32, (6, 12, 24, 16), 64, num_classes=n_out,
                          attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
-        model = model.storage_dtype(args.dtype).to(device)
+        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool)
         if fused:
             return model, O.FusedSGDNesterov(model, lr=args.lr, **ex()), "fused"
         opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, nesterov=True)
@@ -780,11 +866,11 @@ def make_model(args, device):
         from .models import resnet152
         model = resnet152(pretrained=args.pretrained)
         model.fc = nn.Linear(model.fc.in_features, n_out)
-        model = model.storage_dtype(args.dtype).to(device)
+        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool)
         return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
     if "efficientnet" in name:                                # chexpert.py:496-500
         from .models import construct_model
-        model = construct_model(name, n_classes=n_out).storage_dtype(args.dtype).to(device)
+        model = construct_model(name, n_classes=n_out).storage_dtype(args.dtype).to(device).set_pool(**pool)
         if fused:
             return model, O.FusedRMSprop(model, lr=args.lr, decay=args.lr_decay_factor, **ex()), "fused"
         opt = torch.optim.RMSprop(model.parameters(), lr=args.lr, momentum=0.9, eps=0.001)
@@ -794,7 +880,7 @@ def make_model(args, device):
         size = args.resize or 320
         model = ResNet(Bottleneck, [3, 8, 36, 3], num_classes=n_out,
                        attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
-        model = model.storage_dtype(args.dtype).to(device)
+        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool)
         return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
     raise RuntimeError("Model architecture not supported.")
 
@@ -867,6 +953,7 @@ def restore(args, model, optimizer, scheduler, device, multiclass=False):
     or None.  A checkpoint whose head is not this run's (`multiclass`) is refused (ValueError) before anything is loaded."""
     ck = torch.load(args.restore, map_location=device)
     check_checkpoint_head(ck, multiclass, args.restore)
+    check_checkpoint_pool(ck, model, args.restore)
     model.load_state_dict(model_weights(ck, args, args.restore))
     args.step = ck["global_step"]
     if args.train:
@@ -917,6 +1004,7 @@ def main(argv=None):
     aucm = aucm_options(args, world)
     focus = focus_options(args)
     multiclass = multiclass_options(args)
+    pool = resolve_pool(args)
     if world > 1:
         # the process group comes first, before anything touches the GPU; one rank per GPU over RCCL ("nccl"), or ranks sharing
         # a device over gloo when the box has fewer GPUs than ranks (tests)
@@ -974,7 +1062,16 @@ def main(argv=None):
     if args.seed:
         torch.manual_seed(args.seed)
         np.random.seed(args.seed)
-    model, optimizer, scheduler = make_model(args, device)
+    try:
+        pool = restore_pool(args, pool)        # the checkpoint's pooling; a --pool flag that contradicts it is refused here
+        why = visualize_needs_avg(args, pool["kind"])
+        if why:
+            raise ValueError(why)
+    except ValueError:
+        if train_loader is not None:
+            train_loader.close()
+        raise
+    model, optimizer, scheduler = make_model(args, device, pool)
     restored_loss = None
     if args.restore and os.path.isfile(args.restore):
         try:
@@ -1154,6 +1251,8 @@ def main(argv=None):
                         sched_state = scheduler.state_dict() if scheduler is not None and scheduler != "fused" else None
                         ckpt = {"global_step": args.step, "eval_loss": float(np.sum(list(res["loss"].values()))),
                                 "avg_auc": M.mean_auc(res), "state_dict": model.state_dict()}
+                        if model.pool_kind != "avg":  # (a checkpoint without it is the average's: the keys of before)
+                            ckpt["pool_state"] = model.pool_state()
                         if ema_sd is not None:        # beside the live weights, which restore continues from
                             ckpt["ema_state_dict"] = ema_sd
                         if aucm is not None:          # the auxiliary scalars are trained state: restore continues from them
@@ -1179,6 +1278,7 @@ def main(argv=None):
         for c in sorted(f for f in os.listdir(args.restore) if f.startswith("checkpoint") and f.endswith(".pt")):
             ck = torch.load(os.path.join(args.restore, c), map_location=device)
             check_checkpoint_head(ck, multiclass, c)
+            check_checkpoint_pool(ck, model, c)
             model.load_state_dict(model_weights(ck, args, c))
             o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, multiclass)
             outs.append(o)
@@ -1203,6 +1303,7 @@ def main(argv=None):
         imgs, labels, scores, masks, class_maps, sal_maps = [], [], [], [], [], []
         model.eval()
         attn_layers = [m for m in model.modules() if type(m).__name__ == "AAConv2d"]
+        avg_pool = model.pool_kind == "avg"
         for x, tg, idx in batches(valid_ds, flat, args.batch_size, False):
             xd = x.to(device)
             if clahe is not None:                # the figures show what the network saw
@@ -1210,7 +1311,8 @@ def main(argv=None):
                 x = xd.cpu()
             with torch.no_grad():
                 scores.append(model(xd).float().cpu())
-            masks.append(grad_cam(model, xd).float().cpu())
+            if avg_pool:                         # (another pooling: the saliency maps are the figures, visualize_needs_avg)
+                masks.append(grad_cam(model, xd).float().cpu())
             if cam_classes is not None:         # the raw low-resolution relu(M): up-sampled maps of 14 classes would be hundreds of MB
                 class_maps.append(class_cam(model, xd, cam_classes, normalize=False, upsample=False)[0].cpu())
             if sal is not None:                 # float interface: whitened, three identical channels (as the attention figures below)
@@ -1222,13 +1324,14 @@ def main(argv=None):
                 xn = (x.float().div(255.0) - vis.MEAN) / vis.STD if x.dtype == torch.uint8 else x.float()
                 for k in range(len(x)):
                     vis.vis_attn(xn, ["synthetic/%d" % int(i) for i in idx], idx, attn_layers, args.output_dir, k)
-        imgs, labels, scores, masks = torch.cat(imgs), torch.cat(labels), torch.cat(scores), torch.cat(masks)
-        cam = masks
+        imgs, labels, scores = torch.cat(imgs), torch.cat(labels), torch.cat(scores)
         groups = (groups[0], [[pos[i] for i in g] for g in groups[1]])
-        files = vis.visualize(imgs.numpy(), labels.numpy(), scores.numpy(), masks[:, 0].numpy(), ["synthetic/%d" % i for i in flat], names,
-                              groups, args.output_dir, getattr(args, "step", 0))
-        np.save(os.path.join(args.output_dir, "vis", "grad_cam.npy"), cam.numpy())
-        print("grad-cam maps:", tuple(cam.shape), "figures:", len(files))
+        if avg_pool:
+            cam = masks = torch.cat(masks)
+            files = vis.visualize(imgs.numpy(), labels.numpy(), scores.numpy(), masks[:, 0].numpy(), ["synthetic/%d" % i for i in flat], names,
+                                  groups, args.output_dir, getattr(args, "step", 0))
+            np.save(os.path.join(args.output_dir, "vis", "grad_cam.npy"), cam.numpy())
+            print("grad-cam maps:", tuple(cam.shape), "figures:", len(files))
         if cam_classes is not None:
             class_maps = torch.cat(class_maps)
             files = vis.visualize_classes(imgs.numpy(), labels.numpy(), scores.numpy(), class_maps.numpy(), ["synthetic/%d" % i for i in flat],

@@ -24,6 +24,13 @@ def _targets(model, eng, ws, dev):
     raise RuntimeError("unknown model family")
 
 
+def _require_avg(model, what):
+    """NotImplementedError naming set_pool for a model that pools with anything but the average."""
+    check = getattr(model, "require_avg_pool", None)
+    if check is not None:
+        check(what)
+
+
 def hooks_registered(model):
     try:
         eng = model._eng()
@@ -60,7 +67,9 @@ class _HookedLinear(torch.autograd.Function):
 def hooked_eval_forward(model, x):
     """Eval forward through the HIP engine that honours `register_forward_hook` on the reference's Grad-CAM targets and
     `register_backward_hook` on the final Linear (chexpert.py:271-272 with the hook pairs of :468, :484, :498), so the
-    reference's own `grad_cam(model, x, hooks)` works against the drop-in."""
+    reference's own `grad_cam(model, x, hooks)` works against the drop-in.  The hooks' arithmetic is that of the average pool: a model
+    with another pooling (set_pool) is refused."""
+    _require_avg(model, "the Grad-CAM hook path (hooked_eval_forward)")
     eng = model._eng()
     ws = eng.forward(x, False)
     try:
@@ -91,6 +100,7 @@ def grad_cam(model, x, hooks=None, cls_idx=None):
     docstring); for class-specific maps use `class_cam`."""
     if not x.is_cuda:
         raise RuntimeError("grad_cam runs on the GPU only")
+    _require_avg(model, "grad_cam")
     was_training = model.training
     model.eval()
     eng = model._eng()
@@ -191,6 +201,7 @@ def class_cam(model, x, classes=None, *, relu=True, normalize=True, upsample=Tru
     the raw M (relu=False) or relu(M).  relu=False with normalize scales the signed map the same way.  Both storage types, all three
     families; registered Grad-CAM hooks are ignored (the hooked path is never taken); model.training and the running statistics are
     left as they were."""
+    _require_avg(model, "class_cam")          # M is Grad-CAM only when the pool is the mean
     act, lin = cam_source(model)
     kind, K, payload = _cam_classes(classes, lin.out_features)
     if upsample and not normalize:

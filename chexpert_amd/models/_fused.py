@@ -119,6 +119,8 @@ class FusedNet(nn.Module):
         # set_loss(): plain tensors / flags, not buffers (the state_dict keys stay what they are); read through loss_kind,
         # loss_pos_weight, ... below
         self._loss = Loss()
+        self._pool_kind = "avg"          # set_pool(): "gem" adds the parameter pool_p, "lse" the buffer pool_r
+        self._pool_locked = False        # a fused optimiser has been built over the parameters
 
     def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
                  alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None):
@@ -180,6 +182,74 @@ class FusedNet(nn.Module):
                        class_weight=class_weight)
         return self
 
+    # ---- the global pooling in front of the classifier
+    def set_pool(self, kind="avg", r=10.0, p=3.0):
+        """The global pooling of the head: "avg" (the default: the kernels of the average head, untouched), "max", "lse" (log-sum-exp
+        with sharpness r > 0) or "gem" (generalised mean with the trained exponent p in [1, 16]); the definitions stand in
+        chexpert_amd/pooling.py.  "gem" registers the parameter `pool_p` (shape (1,), trained with the network: its gradient lives in
+        the flat gradient buffer, behind every other parameter's), "lse" registers the buffer `pool_r` (one fp32 value in device
+        memory, not trained; a captured step sees `model.pool_r.fill_(5.0)`).  An "avg" or "max" model keeps exactly the state_dict
+        keys it had.  Call it BEFORE the engine binds the parameters -- before the first forward, and before a fused optimiser is
+        built over the model's parameters --: afterwards it raises RuntimeError.  An invalid kind, r <= 0 or p outside [1, 16] is a
+        ValueError that changes nothing.  class_cam, the Grad-CAM hook path and the channel-padded CIFAR DenseNet-BC assume the
+        average and refuse another kind.  Returns self."""
+        from ..pooling import check_pool
+        kind, r, p = check_pool(kind, r, p)
+        if self._pool_bound():
+            raise RuntimeError("set_pool() must be called before the engine has bound the parameters (before the first forward and "
+                               "before a fused optimiser is built): the pooling parameter is part of the flat parameter buffer")
+        dev = next(self.parameters()).device
+        self._parameters.pop("pool_p", None)
+        self._buffers.pop("pool_r", None)
+        self._pool_kind = kind
+        if kind == "gem":
+            self.register_parameter("pool_p", nn.Parameter(torch.full((1,), p, dtype=torch.float32, device=dev)))
+        elif kind == "lse":
+            self.register_buffer("pool_r", torch.full((1,), r, dtype=torch.float32, device=dev))
+        return self
+
+    def _pool_bound(self):
+        """Whether the parameter list is fixed: the engine has bound the parameters to its flat buffer (the engine flag), or a fused
+        optimiser has been built over them."""
+        return self._pool_locked or (self._engine is not None and getattr(self._engine, "flat", None) is not None)
+
+    @property
+    def pool_kind(self):
+        return self._pool_kind
+
+    def pool_param(self):
+        """The device tensor the pooling kernels read: r for "lse", p for "gem", None otherwise."""
+        return {"lse": self._buffers.get("pool_r"), "gem": self._parameters.get("pool_p")}.get(self._pool_kind)
+
+    def pool_state(self):
+        """What a checkpoint keeps beside the state_dict to rebuild the head: {kind, r} (r None unless kind is "lse"; GeM's p is a
+        parameter and travels in the state_dict)."""
+        return {"kind": self._pool_kind, "r": float(self.pool_r.item()) if self._pool_kind == "lse" else None}
+
+    def load_pool_state(self, d):
+        """Restores pool_state() (None or {}: the average) -- before load_state_dict, which then finds `pool_p` / `pool_r`.  Returns
+        self."""
+        d = d or {}
+        kind = d.get("kind", "avg")
+        return self.set_pool(kind, r=d["r"]) if kind == "lse" and d.get("r") is not None else self.set_pool(kind)
+
+    def require_avg_pool(self, what):
+        """class_cam, the Grad-CAM hooks and the channel-padded twin read the head as an average."""
+        if self._pool_kind != "avg":
+            raise NotImplementedError("%s assumes the global average pool: this model pools with set_pool(%r)" % (what, self._pool_kind))
+
+    def named_parameters(self, prefix="", recurse=True, remove_duplicate=True):
+        """nn.Module's order with `pool_p` moved to the end: backward produces the gradients from the end of the flat buffer to its
+        start (the head first), and the data-parallel reducer cuts its buckets in that order."""
+        held, pp = None, self._parameters.get("pool_p")
+        for name, q in super().named_parameters(prefix=prefix, recurse=recurse, remove_duplicate=remove_duplicate):
+            if pp is not None and q is pp:
+                held = (name, q)
+            else:
+                yield name, q
+        if held is not None:
+            yield held
+
     def _n_classes(self):
         """Width of the final Linear layer (the classifier of every family)."""
         return [m for m in self.modules() if isinstance(m, nn.Linear)][-1].out_features
@@ -232,6 +302,7 @@ class FusedNet(nn.Module):
         if not self.training:
             from ..gradcam import hooked_eval_forward, hooks_registered
             if hooks_registered(self):                     # Grad-CAM hook protocol of the reference (chexpert.py:271-272)
+                self.require_avg_pool("the Grad-CAM hook path (hooked_eval_forward)")
                 return hooked_eval_forward(self, x)
             if wants_eval_autograd(self, x):               # frozen-BatchNorm backward (saliency, fine-tuning with frozen BN)
                 return _Fn.apply(x, self._anchor(), self)
@@ -514,6 +585,28 @@ class FusedEngine:
         """weight gradient: the same of its gradient operand"""
         ch, v = self._ch, self._v
         return dict(g_prologue=ops.PRO_AFFINE2, g2=ch(y, c_), ga=ch(v(ws, S.pa), c_), gb=ch(v(ws, S.pb), c_), gc=ch(v(ws, S.pc), c_))
+
+    # ---- the head's pooling when it is not the average (FusedNet.set_pool): pool_head_fwd + linear_fwd on the way up, head_bwd,
+    # pool_p_grad (gem) and pool_head_bwd on the way back; the engines keep their own average calls
+    def pool_kind(self):
+        return getattr(self.model, "pool_kind", "avg")
+
+    def _pool_fwd(self, ws, x, sc, sh, act):
+        """ws.pooled = pool act(x*sc + sh) of the last feature map (ws.pool_aux: GeM's T, which pool_p_grad reads; LSE's offset, which its backward reads)."""
+        m, kind = self.model, self.pool_kind()
+        if kind != "max" and getattr(ws, "pool_aux", None) is None:
+            ws.pool_aux = torch.empty_like(ws.pooled)
+        ops.pool_head_fwd(x, sc, sh, ws.pooled, ws.pool_aux if kind != "max" else None, m.pool_param(), act=act, kind=kind)
+
+    def _pool_bwd(self, ws, dpooled, x, sc, sh, mean, rstd, e_scale, g, S1, S2, stat_rows, act, done):
+        """The pooling's backward from dpooled (the gradient of ws.pooled): pool_p's gradient first (reported to the reducer: it is
+        the last parameter of the flat buffer), then g / S1 / S2 as the average's backward leaves them.  Returns the statistic rows."""
+        m, kind = self.model, self.pool_kind()
+        if kind == "gem":
+            ops.pool_p_grad(dpooled, ws.pooled, ws.pool_aux, m.pool_p, self.grad_of(m.pool_p))
+            done(m.pool_p)
+        return ops.pool_head_bwd(dpooled, ws.pooled, ws.pool_aux if kind != "max" else None, m.pool_param(), x, sc, sh, mean, rstd,
+                                 e_scale, g, S1, S2, act=act, kind=kind, stat_rows=stat_rows)
 
     # ---- workspaces
     def acquire(self, B, H, W):

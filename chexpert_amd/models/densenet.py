@@ -596,9 +596,13 @@ class _Engine(FusedEngine):
         return self._fresh(ws, rows, 0, cn)
 
     def _head_forward(self, ws, bi, fresh):
-        """norm5's coefficients; ReLU -> global average pool -> classifier in one kernel."""
+        """norm5's coefficients; ReLU -> global average pool -> classifier in one kernel.  Another pooling (set_pool): its kernel,
+        then the classifier."""
         m, blk = self.model, self.plan.blocks[bi]
         self._bn_block(ws, blk, blk, m.features.norm5, self._count(ws.buf[bi]), fresh)
+        if self.pool_kind() != "avg":
+            self._pool_fwd(ws, ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), ops.POOL_ACT_RELU)
+            return ops.linear_fwd(ws.pooled, m.classifier.weight, m.classifier.bias, ws.logits)
         ops.head_fwd(ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), m.classifier.weight, m.classifier.bias, ws.pooled, ws.logits)
 
     def _aa_forward(self, ws, bi, fresh):
@@ -647,7 +651,7 @@ class _Engine(FusedEngine):
         ws.alloc_backward(self, self.device)
         z0, zn = self.bwd_zero
         ws.vec[z0:z0 + zn].zero_()
-        self._head_backward(ws, dlogits)
+        self._head_backward(ws, dlogits, done)
         # input gradient + weight gradient of conv1 in one pass over dz2 / y1 / the buffer slice (conv1x1_bwd.hip: 6-37 % less kernel
         # time than the two separate kernels, whole step 37.6 vs 39.0 ms): a bf16 kernel for 128 bottleneck channels -- the fp32
         # parity mode and the channel-padded CIFAR twin run the two kernels one after the other
@@ -714,8 +718,8 @@ class _Engine(FusedEngine):
         self.bn_bwd_coef(ws, bn, r[0], r[1], count, ch(bn.weight), ch(v(ws, M.mean)), ch(v(ws, M.rstd)), ch(G(bn.weight)), ch(G(bn.bias)),
                          *out, n, replicas=r[2], rstride=r[3], q=q, lo=lo)
 
-    def _head_backward(self, ws, dlogits):
-        """classifier -> global average pool -> ReLU -> norm5, into the last block's gradient buffer."""
+    def _head_backward(self, ws, dlogits, done):
+        """classifier -> global pool (the average, or set_pool's) -> ReLU -> norm5, into the last block's gradient buffer."""
         m, v, G = self.model, self._v, self.grad_of
         bi = len(self.blocks) - 1
         blk, ct = self.plan.blocks[bi], self.plan.blocks[bi].C
@@ -724,8 +728,12 @@ class _Engine(FusedEngine):
                      m.classifier.bias is not None else None, dpooled)
         if self.det and ws.B * ct > self.SLAB:
             raise RuntimeError("batch too large for the statistic-row scratch (B*C = %d > %d)" % (ws.B * ct, self.SLAB))
-        rows = ops.gap_relu_bn_bwd(dpooled, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
-                                   ws.gbuf[bi], *self._ew(ws, blk, bwd=True, rows=self.SLAB // ct))
+        if self.pool_kind() != "avg":
+            rows = self._pool_bwd(ws, dpooled, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
+                                  ws.gbuf[bi], *self._ew(ws, blk, bwd=True, rows=self.SLAB // ct), ops.POOL_ACT_RELU, done)
+        else:
+            rows = ops.gap_relu_bn_bwd(dpooled, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
+                                       ws.gbuf[bi], *self._ew(ws, blk, bwd=True, rows=self.SLAB // ct))
         self._norm_bwd(ws, m.features.norm5, blk, self._sc(ws, blk, rows, bwd=True, copies=False), self._count(ws.buf[bi]), acc=blk,
                        q=self._slice_q(ws, bi, self.blocks[bi][1] - 1))
 
@@ -1166,6 +1174,8 @@ class DenseNet(FusedNet):
         for mod in self.modules():
             if isinstance(mod, AAConv2d):
                 mod.check_supported(branch_aligned=not padded)
+        if padded:
+            self.require_avg_pool("the channel-padded CIFAR DenseNet-BC schedule (_TwinNet)")
         if self._engine is None or self._engine.c_final != self.classifier.in_features or \
                 self._engine.dtype != getattr(self, "_storage_dtype", torch.bfloat16):
             object.__setattr__(self, "_engine", _PaddedEngine(self) if padded else _Engine(self))

@@ -291,7 +291,10 @@ class _Engine(FusedEngine):
         Sh = self.bn[id(m.head[1])]
         rows = ops.conv_gemm(xin, self.w_fwd(m.head[0]), ws.yh, N=1280, **self._sp(ws, Sh))
         self._bn_coef(ws, m.head[1], B * ws.hw_last[0] * ws.hw_last[1], train, rows)
-        ops.gap_affine_act(ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.pooled, act=2, rows=self._rows(ws))
+        if self.pool_kind() != "avg":               # set_pool: the pooling's kernel in the average's place
+            self._pool_fwd(ws, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ops.POOL_ACT_SWISH)
+        else:
+            ops.gap_affine_act(ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.pooled, act=2, rows=self._rows(ws))
         # Dropout in front of the classifier (efficientnet.py:169-171), train mode only
         p_do = m.head[5].p if train else 0.0
         ws.drop, ws.fc_in = None, ws.pooled
@@ -348,8 +351,12 @@ class _Engine(FusedEngine):
         if ws.drop is not None:
             ops.mul_f32(dpool, ws.drop, dpool)
         dzh = ws.bwd["dze"][:ws.yh.numel()].view(ws.yh.shape)
-        rows = ops.se_act_bwd(None, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), v(ws, Sh.mean), v(ws, Sh.rstd), None, dpool, dzh,
-                              *self._ew(ws, Sh, bwd=True))
+        if self.pool_kind() != "avg":
+            rows = self._pool_bwd(ws, dpool, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), v(ws, Sh.mean), v(ws, Sh.rstd), v(ws, self.ones, 1280), dzh,
+                                  *self._ew(ws, Sh, bwd=True), ops.POOL_ACT_SWISH, done)
+        else:
+            rows = ops.se_act_bwd(None, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), v(ws, Sh.mean), v(ws, Sh.rstd), None, dpool, dzh,
+                                  *self._ew(ws, Sh, bwd=True))
         self._bn_bwd(ws, m.head[1], self._sc(ws, Sh, rows), B * ws.hw_last[0] * ws.hw_last[1])
         g, xlast = ws.bwd["g"][-1], ws.blk[-1]["out"]
         ops.conv_gemm(dzh, self.w_bwd(m.head[0]), g, N=xlast.shape[3], **self._pro_bnbwd(ws, ws.yh, Sh))

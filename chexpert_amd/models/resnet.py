@@ -345,7 +345,11 @@ class _Engine(FusedEngine):
                 xin = self._basic_forward(ws, bi, xin)
             else:
                 xin, xin_lo, pending = self._bottleneck_forward(ws, bi, xin, xin_lo, pending)
-        ops.head_fwd(xin, v(ws, self.ones), v(ws, self.zeros), m.fc.weight, m.fc.bias, ws.pooled, ws.logits)
+        if self.pool_kind() != "avg":               # set_pool: the pooling's kernel, then the classifier
+            self._pool_fwd(ws, xin, v(ws, self.ones), v(ws, self.zeros), ops.POOL_ACT_RELU)
+            ops.linear_fwd(ws.pooled, m.fc.weight, m.fc.bias, ws.logits)
+        else:
+            ops.head_fwd(xin, v(ws, self.ones), v(ws, self.zeros), m.fc.weight, m.fc.bias, ws.pooled, ws.logits)
         if train:
             m._nbt_pending += 1
         return ws
@@ -497,7 +501,7 @@ class _Engine(FusedEngine):
         self._alloc_bwd(ws)
         z0, zn = self.bwd_zero
         ws.vec[z0:z0 + zn].zero_()
-        self._head_backward(ws, dlogits)
+        self._head_backward(ws, dlogits, done)
         join_rows = None        # statistic rows of a join backward that ran in the epilogue of the block above (CX_EPI_JOIN)
         for bi in range(len(self.blocks) - 1, -1, -1):
             if self.basic:
@@ -509,13 +513,16 @@ class _Engine(FusedEngine):
         else:
             self._stem_backward(ws, dx)
 
-    def _head_backward(self, ws, dlogits):
+    def _head_backward(self, ws, dlogits, done):
         m, v, G = self.model, self._v, self.grad_of
         last = ws.blk[-1]["out"]
         Cl = last.shape[3]
         dpooled = torch.empty(ws.B, Cl, dtype=torch.float32, device=self.device)
         ops.head_bwd(dlogits, ws.pooled, m.fc.weight, G(m.fc.weight), G(m.fc.bias) if m.fc.bias is not None else None, dpooled)
         ones, zeros = v(ws, self.ones, Cl), v(ws, self.zeros, Cl)
+        if self.pool_kind() != "avg":
+            return self._pool_bwd(ws, dpooled, last, ones, zeros, zeros, ones, ones, ws.bwd["g"][-1], v(ws, self.scratch[0], Cl),
+                                  v(ws, self.scratch[1], Cl), 0, ops.POOL_ACT_RELU, done)
         ops.gap_relu_bn_bwd(dpooled, last, ones, zeros, zeros, ones, ones, ws.bwd["g"][-1], v(ws, self.scratch[0], Cl),
                             v(ws, self.scratch[1], Cl))
 

@@ -755,6 +755,54 @@ def gap_relu_bn_bwd(dpooled, x, scale, shift, mean, rstd, e_scale, g, S1, S2, st
     return lib().cx_last_stat_rows() if stat_rows else None
 
 
+# ---- pooling heads other than the average (csrc/pool_head.hip; the definitions: include/chexpert_hip.h, pooling.py)
+POOL_KINDS = {"avg": 0, "max": 1, "lse": 2, "gem": 3}       # CX_POOL_*
+POOL_ACT_RELU, POOL_ACT_SWISH = 1, 2                        # CX_POOL_ACT_*
+
+
+def _pool_args(x, pooled, param, act, kind):
+    require_cuda(x, pooled, param)
+    B, H, W, Cc, ldx = _nhwc(x)
+    k = POOL_KINDS[kind] if isinstance(kind, str) else int(kind)
+    assert k in (1, 2, 3), "pool_head_*: kind max, lse or gem (the average has its own kernels)"
+    assert act in (POOL_ACT_RELU, POOL_ACT_SWISH)
+    assert tuple(pooled.shape) == (B, Cc) and pooled.dtype == torch.float32 and pooled.is_contiguous()
+    assert (param is None) == (k == 1), "pool_head_*: param is r for lse, p for gem, None for max"
+    assert param is None or (param.dtype == torch.float32 and param.numel() == 1)
+    return B, H * W, Cc, ldx, k
+
+
+def pool_head_fwd(x, sc, sh, pooled, aux, param, *, act, kind):
+    """cx_pool_head_fwd: pooled (B,C) fp32 = pool_p act(x*sc + sh) over the pixels of an NHWC map, pool = max / lse / gem; aux (B,C)
+    receives GeM's T / LSE's offset pooled - max; param: the one-element fp32 tensor r (lse) or p (gem), None for max."""
+    B, HW, Cc, ldx, k = _pool_args(x, pooled, param, act, kind)
+    assert k == 1 or (aux is not None and aux.shape == pooled.shape and aux.dtype == torch.float32 and aux.is_contiguous())
+    check(_fn("cx_pool_head_fwd", x)(ptr(x), ptr(sc), ptr(sh), ptr(pooled), ptr(aux), ptr(param), B, HW, Cc, ldx, act, k, stream_ptr()),
+          "cx_pool_head_fwd")
+
+
+def pool_head_bwd(dpooled, pooled, aux, param, x, sc, sh, mean, rstd, e_scale, g, S1, S2, *, act, kind, stat_rows=0):
+    """cx_pool_head_bwd: the backward of pool_head_fwd with the contract of gap_relu_bn_bwd (g = e_scale * dz, S1 / S2; stat_rows > 0:
+    one statistic row per image).  Returns the row count in rows mode."""
+    B, HW, Cc, ldx, k = _pool_args(x, pooled, param, act, kind)
+    assert tuple(dpooled.shape) == (B, Cc) and dpooled.dtype == torch.float32 and dpooled.is_contiguous()
+    assert g.dtype == x.dtype and g.shape == x.shape
+    check(_fn("cx_pool_head_bwd", x)(ptr(dpooled), ptr(pooled), ptr(aux), ptr(param), ptr(x), ptr(sc), ptr(sh), ptr(mean), ptr(rstd),
+                                     ptr(e_scale), ptr(g), ptr(S1), ptr(S2), B, HW, Cc, ldx, _nhwc(g)[4], act, k, stat_rows, stream_ptr()),
+          "cx_pool_head_bwd")
+    return lib().cx_last_stat_rows() if stat_rows else None
+
+
+def pool_p_grad(dpooled, pooled, aux, p, dp):
+    """cx_pool_p_grad: dp[0] += sum dpooled * pooled * (T - ln pooled) / q (GeM's exponent; 0 where p is clamped), in a fixed order."""
+    require_cuda(dpooled, pooled, aux, p, dp)
+    B, Cc = pooled.shape
+    for t in (dpooled, pooled, aux):
+        assert tuple(t.shape) == (B, Cc) and t.dtype == torch.float32 and t.is_contiguous()
+    assert p.dtype == dp.dtype == torch.float32 and p.numel() == dp.numel() == 1
+    check(lib().cx_pool_p_grad(ptr(dpooled), ptr(pooled), ptr(aux), ptr(p), ptr(dp), B, Cc, stream_ptr()), "cx_pool_p_grad")
+
+
 def unpool2_mask(d, x, sc, sh, mean, rstd, e_scale, g, S1, S2, stat_rows=0):
     B, H, W, Cc, ldx = _nhwc(x)
     check(_fn("cx_unpool2_mask", x)(ptr(d), ptr(x), ptr(sc), ptr(sh), ptr(mean), ptr(rstd), ptr(e_scale), ptr(g), ptr(S1), ptr(S2),

@@ -70,8 +70,9 @@ def reference_step(kind, p, g, state, lr, t, lr_mult=1.0, weight_decay=0.0, froz
 
 def finetune_groups(model, weight_decay=0.0, no_decay_norm_bias=False, head_lr_mult=1.0, backbone_lr_mult=1.0, freeze_backbone=False):
     """The `groups` list of a fine-tuning run: the head (the last nn.Linear in named_modules() order: `classifier` of DenseNet, `fc`
-    of ResNet, the final layer of EfficientNet's head) against everything else, each split once more when no_decay_norm_bias
-    exempts every 1-D parameter (BatchNorm weights and biases, all biases) from weight decay.  Dicts carry a "name": "backbone",
+    of ResNet, the final layer of EfficientNet's head; GeM's exponent `pool_p` of FusedNet.set_pool goes with it) against
+    everything else, each split once more when no_decay_norm_bias exempts every 1-D parameter (BatchNorm weights and biases, all
+    biases, `pool_p`) from weight decay.  Dicts carry a "name": "backbone",
     "backbone_no_decay", "head", "head_no_decay"; an empty group is left out."""
     head = None
     for _, mod in model.named_modules():
@@ -80,6 +81,8 @@ def finetune_groups(model, weight_decay=0.0, no_decay_norm_bias=False, head_lr_m
     if head is None:
         raise ValueError("finetune_groups: the model has no nn.Linear to call its head")
     head_ids = {id(q) for q in head.parameters()}
+    if getattr(model, "pool_p", None) is not None:          # GeM's exponent (set_pool) belongs to the head; 1-D: no decay
+        head_ids.add(id(model.pool_p))
     parts = {"backbone": [], "backbone_no_decay": [], "head": [], "head_no_decay": []}
     for q in model.parameters():
         key = "head" if id(q) in head_ids else "backbone"
@@ -126,6 +129,8 @@ class _Flat:
     def __init__(self, model, lr, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True, weight_decay=0.0,
                  decoupled=False, groups=None):
         self.model = model
+        if hasattr(model, "set_pool"):                      # the parameter list is this optimiser's from here on (FusedNet.set_pool)
+            model._pool_locked = True
         self.lr = float(lr)
         self.base_lr = float(lr)
         self.wd = float(weight_decay)                       # the ungrouped steps' decay; with groups: group 0's row

@@ -968,6 +968,48 @@ int cx_sal_accumulate(const float* g, const int32_t* slot, const float* w, float
 int cx_sal_finish(const float* acc, const float* x, const float* base, float base0, float base1, float base2, const int32_t* img_of,
                   float* out, double* total, double* partial, int P, int B, int H, int W, int times_input, int mode, void* stream);
 
+/* ---- global pooling heads other than the average (csrc/pool_head.hip; numpy statement: chexpert_amd/pooling.py).
+ * a[b][p][c] = act(x[b][p][c] * sc[c] + sh[c]) over the HW pixels p of image b; act = CX_POOL_ACT_RELU (DenseNet; ResNet with sc = 1,
+ * sh = 0) or CX_POOL_ACT_SWISH (the EfficientNet head).  The average stays with cx_head_fwd / cx_gap_relu_bn_bwd and
+ * cx_gap_affine_act / cx_se_act_bwd: CX_POOL_AVG is a name for the callers, these entries refuse it.
+ *
+ *   kind          pooled[b][c]                                                    d pooled / d a[b][p][c]
+ *   CX_POOL_MAX   max_p a                                                         1 at the FIRST maximal pixel in ascending p, else 0
+ *   CX_POOL_LSE   m + log(mean_p exp(r (a - m))) / r,  m = max_p a,  r > 0        exp(r (a - pooled)) / HW
+ *   CX_POOL_GEM   (mean_p a'^q)^(1/q),  a' = max(a, 1e-6),  q = clamp(p, 1, 16)   a'^(q-1) pooled^(1-q) / HW where a > 1e-6, else 0
+ *
+ * GeM's exponent is trained: d pooled / d p = pooled (T - ln pooled) / q with T = sum_p a'^q ln a' / sum_p a'^q, and 0 where p is
+ * clamped (p <= 1 or p >= 16).  The activation's derivative multiplies d pooled / d a: the ReLU mask x*sc + sh > 0, or swish'.
+ * LSE and GeM are computed relative to the column maximum (two walks over the column), so an activation of 1e4 stays finite
+ * with r = 10 and with p = 16.  param: the device pointer to r (LSE) or p (GeM), one fp32 value read by the kernel -- a captured step
+ * sees an in-place change --, NULL for the maximum.
+ *
+ * Forward: pooled fp32 (B, C); aux fp32 (B, C) receives T for GeM, for LSE the offset pooled - m = log(mean_p exp(r (a - m))) / r, and
+ * is not touched by the maximum (may be NULL then).  No pitch padding of x is read.
+ * Backward: the contract of cx_gap_relu_bn_bwd -- dz = dpooled * (d pooled / d a) * act', g = e_scale * dz (storage type, pitch ldg,
+ * padding untouched), S1 = sum dz, S2 = sum dz (x - mean) rstd; stat_rows == 0: fp32 atomics into S1 / S2 [C]; stat_rows > 0:
+ * exactly one row per image (row b at S[b*C + c], the row count B is what the last-stat-rows query returns, two calls give equal
+ * bits), CX_ESTATROWS below B rows with nothing written.  The maximum stores no arg-max: the backward evaluates the same fmaf and
+ * activation, which gives the forward's bits, and the first pixel that equals pooled takes the gradient.  LSE forms a - pooled as
+ * (a - m) - aux with the column maximum found again: next to a maximum of 1e4 pooled itself is rounded to 1e-3, and r times that
+ * would be the gradient's relative error.  GeM's backward does not read aux (the exponent's gradient does).
+ * cx_pool_p_grad: dp[0] += sum_{b,c} dpooled pooled (T - ln pooled) / q in a fixed order (one workgroup, no atomics).
+ * Checks, before any launch: CX_EINVAL a NULL operand (param and aux where the kind needs them), an unknown kind or act; CX_ESHAPE C % 8, a pitch % 8, a pitch below C, a size <= 0; CX_EALIGN x or g not 16-byte aligned.  Additive entry points of
+ * ABI 10.                                                                                                                       */
+enum { CX_POOL_AVG = 0, CX_POOL_MAX = 1, CX_POOL_LSE = 2, CX_POOL_GEM = 3 };
+enum { CX_POOL_ACT_RELU = 1, CX_POOL_ACT_SWISH = 2 };        /* the codes of cx_gap_affine_act's act */
+int cx_pool_head_fwd(const void* x, const float* sc, const float* sh, float* pooled, float* aux, const float* param, int B, int HW,
+                     int C, int ldx, int act, int kind, void* stream);
+int cx_pool_head_bwd(const float* dpooled, const float* pooled, const float* aux, const float* param, const void* x, const float* sc,
+                     const float* sh, const float* mean, const float* rstd, const float* e_scale, void* g, float* S1, float* S2, int B,
+                     int HW, int C, int ldx, int ldg, int act, int kind, int stat_rows, void* stream);
+int cx_pool_p_grad(const float* dpooled, const float* pooled, const float* aux, const float* p, float* dp, int B, int C, void* stream);
+int cx_pool_head_fwd_f32(const void* x, const float* sc, const float* sh, float* pooled, float* aux, const float* param, int B, int HW,
+                         int C, int ldx, int act, int kind, void* stream);
+int cx_pool_head_bwd_f32(const float* dpooled, const float* pooled, const float* aux, const float* param, const void* x,
+                         const float* sc, const float* sh, const float* mean, const float* rstd, const float* e_scale, void* g,
+                         float* S1, float* S2, int B, int HW, int C, int ldx, int ldg, int act, int kind, int stat_rows, void* stream);
+
 /* ---- fp32 storage mode (CX_DT_F32): the element-wise kernels of the DenseNet path with fp32 activation tensors (same arguments,
  * `const void*` tensors are fp32, pitches in elements), the fp32 weight table ([tap][O][I] fp32; descriptors with stem = 1 give
  * [49][O][4]) and the fp32 image layouts.  cx_conv_gemm / cx_conv_wgrad take CxConv.dtype / CxWgrad.dtype = CX_DT_F32.          */
