@@ -224,6 +224,8 @@ SIGNATURES = {
                       _vp, _vp, _vp, _vp, _i, _vp],
     "cx_calib_fit": [_vp, _vp, _i, _i, _i, _i, C.c_double, _i, _vp, _vp],
     "cx_boot_calib": [_vp, _i, _i, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
+    "cx_delong_place": [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i, _i, _vp, _i, _vp],
+    "cx_delong_gram": [_vp, _i, _i, _i, _vp, _vp],
     "cx_sal_points": [_vp, _vp, _f, _f, _f, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _i, _i, _i, _i, _vp],
     "cx_sal_accumulate": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "cx_sal_finish": [_vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

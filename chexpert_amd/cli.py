@@ -95,6 +95,12 @@
                         level: the interval of every named metric over the same kind of resamples (metrics.bootstrap_metrics): auroc, ap
                         (average precision), sens@S (sensitivity at specificity >= S), spec@S (specificity at sensitivity >= S), S inside
                         (0, 1) with at most 6 decimals, at most 8 operating points.  Not given (default): nothing more is computed or written
+  --delong              every eval_results_<tag>.json gets a delong_<tag>.json beside it (rank 0): AUROC per class and for the mean with its
+                        analytic standard error and (1 - A) normal interval, computed on the GPU (metrics.delong_auc): DeLong's variance
+                        for --bootstrap_unit image, Obuchowski's clustered extension for study / patient (which need the real data's
+                        paths); A is --bootstrap_alpha.  Deterministic, no replicates.  With --evaluate_ensemble, delong_ensemble.json
+                        also holds under "vs_members" DeLong's paired test of the ensemble against every member checkpoint
+                        (metrics.delong_auc_diff).  Not given (default): nothing is computed, allocated or written
   --calibrate temperature|platt   every eval_results_<tag>.json gets a calibration_<tag>.json beside it (rank 0): the per-class map
                         p = sigmoid(a z + b) fitted on the GPU on that evaluation's logits (temperature: b = 0), ECE / MCE / Brier score
                         before and after it, the reliability curves and, with --bootstrap B, the intervals of all six (same seed, unit
@@ -214,6 +220,8 @@ def build_parser():
     p.add_argument("--bootstrap_seed", type=int, default=None, metavar="S", help="seed of the bootstrap draws (default: --seed)")
     p.add_argument("--bootstrap_unit", default="image", choices=list(BOOTSTRAP_UNITS), help="what the bootstrap resamples")
     p.add_argument("--bootstrap_alpha", type=float, default=0.05, metavar="A", help="the intervals cover 1 - A (default 0.05)")
+    p.add_argument("--delong", action="store_true", default=False,
+                   help="DeLong / Obuchowski AUROC intervals into delong_<tag>.json beside every eval_results file; paired test under --evaluate_ensemble")
     p.add_argument("--bootstrap_metrics", nargs="+", default=None, metavar="M",
                    help="with --bootstrap: intervals of these metrics (auroc, ap, sens@S, spec@S) into metrics_ci_<tag>.json")
     p.add_argument("--calibrate", default=None, choices=["temperature", "platt"],
@@ -307,7 +315,7 @@ def parse_args(argv=None):
         parser.error("--bootstrap_alpha takes a level inside (0, 1) (got %r)" % alpha)
     if unit not in BOOTSTRAP_UNITS:
         parser.error("--bootstrap_unit takes one of %s (got %r)" % (", ".join(BOOTSTRAP_UNITS), unit))
-    if boot > 0 and unit != "image" and getattr(args, "synthetic", 0):
+    if (boot > 0 or getattr(args, "delong", False)) and unit != "image" and getattr(args, "synthetic", 0):
         parser.error("--bootstrap_unit %s groups the images by their file paths; --synthetic images have none (use image)" % unit)
     names = getattr(args, "bootstrap_metrics", None)
     if names is not None:
@@ -375,6 +383,38 @@ def write_auc_ci(args, tag, outputs, targets, groups=None):
         print("  %-18s %.4f [%.4f, %.4f]" % (name, ci["aucs"][c], ci["lo"][c], ci["hi"][c]))
     print("  %-18s %.4f [%.4f, %.4f]" % ("mean", ci["mean_auc"]["point"], ci["mean_auc"]["lo"], ci["mean_auc"]["hi"]))
     path = os.path.join(args.output_dir, auc_ci_name(tag))
+    json.dump(ci, open(path, "w"), indent=4)
+    return path
+
+
+def delong_name(tag):
+    """File name of the analytic intervals that go with <tag>.json: eval_results_step_5 -> delong_step_5.json (the rule of auc_ci_name:
+    not the prefix `eval_results`)."""
+    return "delong_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ".json"
+
+
+def write_delong(args, tag, outputs, targets, groups=None, members=None):
+    """With --delong: the DeLong (Obuchowski with grouped units) AUROC intervals of the evaluation that wrote <tag>.json, into
+    delong_<...>.json beside it, and one `AUC [lo, hi]` line per class and for the mean.  members: {checkpoint file name: that member's
+    outputs} under --evaluate_ensemble; the file then holds under "vs_members" the paired test of `outputs` against each of them, and
+    the mean-AUROC delta, z and p of each are printed.  Returns the path, or None (no --delong: nothing computed, allocated or written)."""
+    if not getattr(args, "delong", False):
+        return None
+    alpha, device = getattr(args, "bootstrap_alpha", 0.05), "cuda:%d" % (args.cuda or 0)
+    ci = M.delong_auc(outputs, targets, groups=groups, alpha=alpha, device=device)
+    ci["unit"] = getattr(args, "bootstrap_unit", "image")
+    names = class_names(len(ci["aucs"]))
+    print("AUC with %g %% %s intervals (%d %s units):" % (100 * (1 - ci["alpha"]), ci["method"], ci["n_units"], ci["unit"]))
+    for c, name in enumerate(names):
+        print("  %-18s %.4f [%.4f, %.4f]" % (name, ci["aucs"][c], ci["lo"][c], ci["hi"][c]))
+    print("  %-18s %.4f [%.4f, %.4f]" % ("mean", ci["mean_auc"]["point"], ci["mean_auc"]["lo"], ci["mean_auc"]["hi"]))
+    if members is not None:
+        ci["vs_members"] = {}
+        for name, out in members.items():
+            d = M.delong_auc_diff(outputs, out, targets, groups=groups, alpha=alpha, device=device)
+            ci["vs_members"][name] = d
+            print("  ensemble - %-24s mean AUC delta %+.4f  z %.3f  p %.4g" % (name, d["mean_auc"]["delta"], d["mean_auc"]["z"], d["mean_auc"]["p"]))
+    path = os.path.join(args.output_dir, delong_name(tag))
     json.dump(ci, open(path, "w"), indent=4)
     return path
 
@@ -1147,7 +1187,7 @@ def main(argv=None):
         on = ex.get("ema_decay") is not None and args.train and model._eng().flat is not None
         return optimizer.ema_weights() if on else contextlib.nullcontext()
 
-    boot_groups = bootstrap_groups(args, valid_ds) if getattr(args, "bootstrap", 0) > 0 else None
+    boot_groups = bootstrap_groups(args, valid_ds) if getattr(args, "bootstrap", 0) > 0 or getattr(args, "delong", False) else None
 
     def run_eval(tag):
         with averaged():
@@ -1157,6 +1197,7 @@ def main(argv=None):
             print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
             json.dump(res, open(os.path.join(args.output_dir, tag + ".json"), "w"), indent=4)
             write_auc_ci(args, tag, o, t, boot_groups)
+            write_delong(args, tag, o, t, boot_groups)
             write_metrics_ci(args, tag, o, t, boot_groups)
             write_calibration(args, tag, o, t, boot_groups)
         return res
@@ -1274,7 +1315,7 @@ def main(argv=None):
         run_eval("eval_results_step_%d" % args.step)
     if args.evaluate_ensemble:
         assert args.restore and os.path.isdir(args.restore), "Restore argument must be directory with saved checkpoints"
-        outs, losses = [], []
+        outs, losses, members = [], [], []
         for c in sorted(f for f in os.listdir(args.restore) if f.startswith("checkpoint") and f.endswith(".pt")):
             ck = torch.load(os.path.join(args.restore, c), map_location=device)
             check_checkpoint_head(ck, multiclass, c)
@@ -1283,12 +1324,14 @@ def main(argv=None):
             o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, multiclass)
             outs.append(o)
             losses.append(l)
+            members.append(c)
         mean_out = torch.stack(outs, 2).mean(2)                                                      # mean of logits, chexpert.py:233
         res = M.compute_metrics(mean_out, tg, torch.stack(losses, 2).mean(2))
         if rank == 0:
             json.dump(res, open(os.path.join(args.output_dir, "eval_results_ensemble.json"), "w"), indent=4)
             print("AUC:\n", pprint.pformat(res["aucs"]))
             write_auc_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
+            write_delong(args, "eval_results_ensemble", mean_out, tg, boot_groups, members=dict(zip(members, outs)))
             write_metrics_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
             write_calibration(args, "eval_results_ensemble", mean_out, tg, boot_groups)
     if args.visualize and rank == 0:

@@ -5,7 +5,10 @@ Here the ROC / PR curves are built directly (descending score sweep with tie gro
 sklearn's `_binary_clf_curve` does) and the AUROC is the trapezoid area.  Host-side numpy: this runs once
 per evaluation on (N, 5) arrays and is not on the GPU hot path.
 """
+import math
 import re
+from fractions import Fraction
+from statistics import NormalDist
 
 import numpy as np
 
@@ -619,3 +622,256 @@ def bootstrap_metrics_diff_reference(outputs_a, outputs_b, targets, metrics=("au
     b, _ = _metric_replicates_reference(outputs_b, targets, names, points, n_boot, seed, groups)
     return {name: _summarise_diff(a[name][0], b[name][0], a[name][1], b[name][1], n_boot, seed, alpha, U, return_replicates)
             for name in names}
+
+
+# ---- DeLong / Obuchowski variance of the AUROC and the paired test (chexpert_amd/csrc/delong.hip) ----------------------------------
+# One model, one class: the kept rows (target >= 0), M positives (target > 0.5), N negatives, scores compared in the dtype given.
+# Doubled placements, ties counted half (integers):
+#   a positive i: X2_i = 2 #{neg j : s_j < s_i} + #{neg j : s_j = s_i};  a negative j: Y2_j = 2 #{pos i : s_i > s_j} + #{pos i : s_i = s_j}
+#   num2 = sum X2 = sum Y2 (what cx_boot_auc returns for a count row of ones),  theta = num2 / (2 M N)
+# Rows are grouped into U units (one row each, or the distinct ids of `groups`).  Per class and unit u four integers -- the table of
+# cx_delong_place: X_u (sum of X2 over the unit's positives), m_u (their number), Y_u (sum of Y2 over its negatives), n_u.  With
+#   a_u = X_u / (2 N) - m_u theta,  b_u = Y_u / (2 M) - n_u theta,  I10 / I01 / I = the units with m_u > 0 / n_u > 0 / a kept row:
+#   S10 = I10 / ((I10 - 1) M) sum a_u^2,  S01 = I01 / ((I01 - 1) N) sum b_u^2,  S11 = I / (I - 1) sum a_u b_u
+#   Var(theta) = S10 / M + S01 / N + 2 S11 / (M N)                 (Obuchowski 1997; single-row units: DeLong 1988 exactly)
+#   Cov(theta_A, theta_B): the same with the cross products sum aA aB, sum bA bB and sum (aA bB + aB bA) (no factor 2 on the last)
+#   Var(delta) = Var_A + Var_B - 2 Cov,  z = delta / sqrt(Var(delta)),  p = erfc(|z| / sqrt 2)
+# The mean over the classes (different kept rows per class: DeLong's matrix does not apply) takes the cluster-robust influence form:
+#   psi_u^c = a_u^c / M^c + b_u^c / N^c,  psibar_u = mean_c psi_u^c,  Var(mean theta) = U / (U - 1) sum_u psibar_u^2
+# which for one class differs from the per-class form only in the finite-sample factors (U / (U - 1) for all three terms instead of
+# I10 / (I10 - 1), I01 / (I01 - 1), I / (I - 1)); the paired mean uses psibar_A - psibar_B.
+# Where each part is computed: a_u = (M X_u - m_u num2) / (2 M N) and b_u = (N Y_u - n_u num2) / (2 M N) have integer numerators, so every
+# sum above is a combination of the raw moment sums G[p][q] = sum_u z[p][u] z[q][u] of the table's rows (cx_delong_gram) with integer
+# coefficients.  The host forms these combinations in Python integers, the quotients as exact fractions, and rounds ONCE to float64:
+# no float sum is ever formed, so the GPU path and the numpy statement return equal floats whenever their integers agree, and identical
+# models give Var(delta) = 0 exactly.
+DELONG_MAX_ROWS = 128                 # CX_DELONG_MAX_ROWS: 4 rows per class and model, two models of 16 classes
+
+
+def delong_place_reference(order, offs, lens, n_units):
+    """Statement of cx_delong_place in int64 numpy: the (4 C, n_units) table, rows 4c .. 4c+3 = X, m, Y, n of class c, from the `hi` /
+    `lo` orders of bootstrap_plan.  In `hi` the negatives in front of a positive are its LE, in `lo` its LT (their sum is X2); for a
+    negative Y2 = (M - positives in front in lo) + (M - positives in front in hi).  Unit indices are clamped to n_units - 1."""
+    order = np.asarray(order, dtype=np.int32)
+    U = int(n_units)
+    z = np.zeros((4 * len(lens), U), dtype=np.int64)
+    for c in range(len(lens)):
+        n, o = int(lens[c]), int(offs[c])
+        for k in range(2):
+            e = order[o + k * n:o + (k + 1) * n]
+            pos = e < 0
+            u = np.minimum(e & 0x7fffffff, U - 1).astype(np.int64)
+            before = np.cumsum(pos, dtype=np.int64) - pos                  # positives in front of every entry
+            neg_before = np.arange(n, dtype=np.int64) - before
+            np.add.at(z[4 * c], u[pos], neg_before[pos])
+            np.add.at(z[4 * c + 2], u[~pos], int(pos.sum()) - before[~pos])
+            if k == 0:
+                np.add.at(z[4 * c + 1], u[pos], 1)
+                np.add.at(z[4 * c + 3], u[~pos], 1)
+    return z
+
+
+def int_gram_reference(z, n_units=None):
+    """Statement of cx_delong_gram: g[p][q] = sum_u z[p][u] z[q][u] mod 2^64 over the first n_units columns, as an int64 (Q, Q) array."""
+    z = np.ascontiguousarray(np.asarray(z, dtype=np.int64)[:, :n_units]).view(np.uint64)
+    with np.errstate(over="ignore"):
+        return np.matmul(z, z.T).view(np.int64)
+
+
+def _delong_check(alpha):
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("delong: alpha must be inside (0, 1) (got %r)" % alpha)
+
+
+def _delong_plans(models, targets, groups):
+    """The plans of the models (bootstrap_plan's errors are the input errors) after the checks that come before any launch."""
+    plans = [bootstrap_plan(o, targets, groups) for o in models]
+    n_cls, U = len(plans[0]["lens"]), plans[0]["n_units"]
+    if n_cls < 1:
+        raise ValueError("delong: the outputs hold no class")
+    if 4 * n_cls * len(plans) > DELONG_MAX_ROWS:
+        raise ValueError("delong: %d classes of %d model(s) need %d table rows (at most %d are supported)"
+                         % (n_cls, len(plans), 4 * n_cls * len(plans), DELONG_MAX_ROWS))
+    # overflow guard: X_u <= 2 L g_u with L = the longest class list and g_u the rows of unit u, so every Gram entry is at most
+    # 4 L^2 sum g_u^2; below 2^63 the int64 the kernel returns is the true integer
+    g = np.bincount(plans[0]["units"], minlength=U).astype(np.int64)
+    longest = int(max(int(v) for v in plans[0]["lens"]))
+    if 4 * longest * longest * int(np.dot(g, g)) >= 1 << 63:
+        raise ValueError("delong: 4 * %d^2 * sum of squared unit sizes (%d) reaches 2^63: the moment sums would overflow int64"
+                         % (longest, int(np.dot(g, g))))
+    return plans
+
+
+def _delong_stats(table, n_models):
+    """Per model and class (M, N, num2, I10, I01, I) as Python ints from the (4 C K, U) int64 table, a numpy array or a torch tensor
+    on the GPU (only these reductions leave it)."""
+    m, n = table[1::4], table[3::4]
+    sums, m_on, n_on, any_on = (v.tolist() for v in (table.sum(1), (m > 0).sum(1), (n > 0).sum(1), ((m + n) > 0).sum(1)))
+    n_cls = len(m_on) // n_models
+    return [[(sums[4 * r + 1], sums[4 * r + 3], sums[4 * r], m_on[r], n_on[r], any_on[r]) for r in range(k * n_cls, (k + 1) * n_cls)]
+            for k in range(n_models)]
+
+
+class _DelongFinish:
+    """The exact host finish: stats[k][c] = (M, N, num2, I10, I01, I), G = the (4 C K)^2 moment sums as nested lists of Python ints."""
+
+    def __init__(self, stats, G, n_units):
+        self.stats, self.G, self.U, self.C = stats, G, int(n_units), len(stats[0])
+
+    def _q(self, k, c, v, l, d, w):
+        """sum_u (v . rows of (k, c))_u (w . rows of (l, d))_u as an integer."""
+        G, p0, q0 = self.G, 4 * (k * self.C + c), 4 * (l * self.C + d)
+        return sum(v[i] * w[j] * G[p0 + i][q0 + j] for i in range(4) if v[i] for j in range(4) if w[j])
+
+    def _coef(self, k, c):
+        """Integer numerators of a_u, b_u (both over 2 M N) and psi_u (over 2 M^2 N^2) on the rows X, m, Y, n."""
+        M, N, S = self.stats[k][c][:3]
+        return (M, -S, 0, 0), (0, 0, N, -S), (M * N, -N * S, M * N, -M * S)
+
+    def theta(self, k, c):
+        M, N, S = self.stats[k][c][:3]
+        return Fraction(S, 2 * M * N) if M and N else None
+
+    def cov(self, k, l, c):
+        """Cov(theta_k, theta_l) of class c as a Fraction (k == l: the variance); None where it is not defined."""
+        M, N, _, I10, I01, I = self.stats[k][c]
+        if not (M and N) or I10 < 2 or I01 < 2:
+            return None
+        (ak, bk, _), (al, bl, _) = self._coef(k, c), self._coef(l, c)
+        D = (2 * M * N) ** 2
+        s10 = Fraction(I10 * self._q(k, c, ak, l, c, al), (I10 - 1) * M * D)
+        s01 = Fraction(I01 * self._q(k, c, bk, l, c, bl), (I01 - 1) * N * D)
+        s11 = Fraction(I * (self._q(k, c, ak, l, c, bl) + self._q(l, c, al, k, c, bk)), (I - 1) * D)
+        return s10 / M + s01 / N + s11 / (M * N)
+
+    def mean_cov(self, k, l):
+        """U / (U - 1) sum_u psibar_k psibar_l as a Fraction; None where a class has no positive or no negative, or U = 1."""
+        if self.U < 2 or any(not (st[0] and st[1]) for st in self.stats[k]):
+            return None
+        tot = Fraction(0)
+        for c in range(self.C):
+            Mc, Nc = self.stats[k][c][:2]
+            wc = self._coef(k, c)[2]
+            for d in range(self.C):
+                Md, Nd = self.stats[l][d][:2]
+                tot += Fraction(self._q(k, c, wc, l, d, self._coef(l, d)[2]), 4 * (Mc * Nc * Md * Nd) ** 2)
+        return tot * Fraction(self.U, (self.U - 1) * self.C * self.C)
+
+
+def _delong_se(var):
+    return math.sqrt(float(var)) if var is not None and var >= 0 else float("nan")
+
+
+def _delong_band(point, se, zq, lo, hi):
+    if math.isnan(point) or math.isnan(se):
+        return float("nan"), float("nan")
+    return min(max(point - zq * se, lo), hi), min(max(point + zq * se, lo), hi)
+
+
+def _delong_summary(fin, alpha, grouped):
+    C, zq = fin.C, NormalDist().inv_cdf(1.0 - alpha / 2.0)
+    th = [fin.theta(0, c) for c in range(C)]
+    aucs = {c: float(th[c]) if th[c] is not None else float("nan") for c in range(C)}
+    se = {c: _delong_se(fin.cov(0, 0, c)) for c in range(C)}
+    band = {c: _delong_band(aucs[c], se[c], zq, 0.0, 1.0) for c in range(C)}
+    point = float(sum(th) / C) if all(t is not None for t in th) else float("nan")
+    mse = _delong_se(fin.mean_cov(0, 0))
+    mband = _delong_band(point, mse, zq, 0.0, 1.0)
+    st = fin.stats[0]
+    return {"aucs": aucs, "se": se, "lo": {c: band[c][0] for c in range(C)}, "hi": {c: band[c][1] for c in range(C)},
+            "n_pos": {c: st[c][0] for c in range(C)}, "n_neg": {c: st[c][1] for c in range(C)},
+            "n_units_pos": {c: st[c][3] for c in range(C)}, "n_units_neg": {c: st[c][4] for c in range(C)},
+            "mean_auc": {"point": point, "se": mse, "lo": mband[0], "hi": mband[1]},
+            "alpha": float(alpha), "n_units": fin.U, "method": "obuchowski" if grouped else "delong"}
+
+
+def _delong_test(delta, var, zq):
+    """(delta, se, lo, hi, z, p, degenerate) of one difference: delta a Fraction or None, var its variance as a Fraction or None."""
+    nan = float("nan")
+    if delta is None:
+        return nan, nan, nan, nan, nan, nan, False
+    d = float(delta)
+    if var is None:
+        return d, nan, nan, nan, nan, nan, False
+    se = _delong_se(var)
+    lo, hi = _delong_band(d, se, zq, -1.0, 1.0)
+    if var <= 0:
+        return d, se, lo, hi, nan, nan, True
+    z = d / se
+    return d, se, lo, hi, z, math.erfc(abs(z) / math.sqrt(2.0)), False
+
+
+def _delong_diff_summary(fin, alpha, grouped):
+    C, zq = fin.C, NormalDist().inv_cdf(1.0 - alpha / 2.0)
+    rows = []
+    for c in range(C):
+        ta, tb = fin.theta(0, c), fin.theta(1, c)
+        va, vb, cab = fin.cov(0, 0, c), fin.cov(1, 1, c), fin.cov(0, 1, c)
+        rows.append(_delong_test(None if ta is None else ta - tb, None if va is None else va + vb - 2 * cab, zq))
+    th = [(fin.theta(0, c), fin.theta(1, c)) for c in range(C)]
+    ok = all(a is not None for a, _ in th)
+    maa, mbb, mab = fin.mean_cov(0, 0), fin.mean_cov(1, 1), fin.mean_cov(0, 1)
+    m = _delong_test(sum(a - b for a, b in th) / C if ok else None, None if maa is None else maa + mbb - 2 * mab, zq)
+    keys = ("delta", "se", "lo", "hi", "z", "p", "degenerate")
+    out = {name: {c: rows[c][i] for c in range(C)} for i, name in enumerate(keys)}
+    out["mean_auc"] = dict(zip(keys[:6], m[:6]))
+    out.update({"alpha": float(alpha), "n_units": fin.U, "method": "obuchowski" if grouped else "delong"})
+    return out
+
+
+def _delong_gpu(plans, device):
+    """_DelongFinish of the plans through cx_delong_place and cx_delong_gram: one stacked table, one Gram matrix."""
+    import torch
+
+    from . import ops
+    U, n_cls = plans[0]["n_units"], len(plans[0]["lens"])
+    table = torch.empty(4 * n_cls * len(plans), U, dtype=torch.int64, device=device)
+    for k, p in enumerate(plans):
+        ops.delong_place(torch.from_numpy(p["order"]).to(device), p["offs"], p["lens"], U, out=table[4 * n_cls * k:4 * n_cls * (k + 1)])
+    g = ops.int_gram(table, U)
+    return _DelongFinish(_delong_stats(table, len(plans)), g.cpu().tolist(), U)
+
+
+def _delong_host(plans):
+    table = np.concatenate([delong_place_reference(p["order"], p["offs"], p["lens"], p["n_units"]) for p in plans])
+    return _DelongFinish(_delong_stats(table, len(plans)), int_gram_reference(table).tolist(), plans[0]["n_units"])
+
+
+def delong_auc(outputs, targets, groups=None, alpha=0.05, device="cuda"):
+    """AUROC per class with its analytic standard error and (1 - alpha) normal interval, on the GPU (cx_delong_place + cx_delong_gram;
+    no CPU fallback): DeLong's variance (DeLong, DeLong and Clarke-Pearson 1988) for groups=None, Obuchowski's clustered extension
+    (1997) with `groups`, one id per row as bootstrap_auc takes them.  Deterministic: no seed, no replicates.  The definitions are in
+    the comment above; everything that scales with the rows is integer work on the GPU, the finish is exact on the host.  Returns a
+    json-serialisable dict, int class keys: aucs, se, lo, hi (theta -/+ z_{1-alpha/2} se, clipped to [0, 1]; the quantile from
+    statistics.NormalDist), n_pos, n_neg, n_units_pos, n_units_neg (M, N, I10, I01); mean_auc: {point, se, lo, hi} of the mean over the
+    classes, whose variance is the cluster-robust influence form U / (U - 1) sum_u psibar_u^2 -- it differs from the per-class form only
+    in the finite-sample factors; alpha, n_units, method ("delong" | "obuchowski").  A class without a positive or a negative: NaN
+    throughout (and the mean with it, as in bootstrap_auc); a class with one positive or one negative unit: se, lo, hi NaN.
+    ValueError before any launch: bootstrap_plan's input errors (shapes, NaN scores), more than 32 classes, alpha outside (0, 1), and
+    4 max_c(M_c + N_c)^2 sum_u g_u^2 >= 2^63 (g_u the rows of unit u), beyond which the moment sums could overflow."""
+    _delong_check(alpha)
+    plans = _delong_plans([outputs], targets, groups)
+    return _delong_summary(_delong_gpu(plans, device), alpha, groups is not None)
+
+
+def delong_auc_reference(outputs, targets, groups=None, alpha=0.05):
+    """The numpy statement of delong_auc (host: delong_place_reference, int_gram_reference and the same exact finish)."""
+    _delong_check(alpha)
+    return _delong_summary(_delong_host(_delong_plans([outputs], targets, groups)), alpha, groups is not None)
+
+
+def delong_auc_diff(outputs_a, outputs_b, targets, groups=None, alpha=0.05, device="cuda"):
+    """DeLong's paired test of the AUROC difference a - b of two models on the same rows (Obuchowski's with `groups`), on the GPU: both
+    models' tables stacked, one Gram matrix.  Per class: delta, se, lo, hi (delta -/+ z se, clipped to [-1, 1]), z = delta / se,
+    p = erfc(|z| / sqrt 2) and degenerate (Var(delta) <= 0, identical scores for example: z and p are NaN); mean_auc: {delta, se, lo,
+    hi, z, p} of the mean over the classes with the influence form of delong_auc on psibar_a - psibar_b; alpha, n_units, method.  At
+    most 16 classes; the other errors are those of delong_auc."""
+    _delong_check(alpha)
+    plans = _delong_plans([outputs_a, outputs_b], targets, groups)
+    return _delong_diff_summary(_delong_gpu(plans, device), alpha, groups is not None)
+
+
+def delong_auc_diff_reference(outputs_a, outputs_b, targets, groups=None, alpha=0.05):
+    """The numpy statement of delong_auc_diff."""
+    _delong_check(alpha)
+    return _delong_diff_summary(_delong_host(_delong_plans([outputs_a, outputs_b], targets, groups)), alpha, groups is not None)

@@ -1497,6 +1497,50 @@ def boot_calib(counts, order, conf, offs, lens, n_units, bins):
     return wsum.long() & 0xffffffff, wpos.long() & 0xffffffff, csum, bnum      # the kernel's unsigned values
 
 
+# ---- DeLong / Obuchowski variance of the AUROC (delong.hip; chexpert_amd/metrics.py composes them and states them in numpy) ----
+DELONG_MAX_ROWS, DELONG_WG_ENTRIES, DELONG_TILE = 128, 16384, 32    # CX_DELONG_MAX_ROWS, CX_DELONG_WG_ENTRIES, CX_DELONG_TILE of the header
+
+
+def delong_place(order, offs, lens, n_units, out=None):
+    """cx_delong_place: the unit sums of the doubled placements.  order / offs / lens: what boot_auc takes (metrics.bootstrap_plan builds
+    them).  Returns an int64 (4 C, n_units) tensor on the GPU, rows 4c .. 4c+3 = (sum of X2 over the unit's positives, their number, sum
+    of Y2 over its negatives, their number) of class c; a class with lens[c] == 0 gives zeros.  `out`: an int64 (4 C, >= n_units) tensor
+    with unit column stride whose first n_units columns are written (zeroed first) and returned; the columns behind them are left
+    untouched.  A workgroup walks DELONG_WG_ENTRIES entries of a list."""
+    require_cuda(order)
+    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), "order: contiguous int32"
+    offs, lens, n_units = [int(v) for v in offs], [int(v) for v in lens], int(n_units)
+    n_cls = len(lens)
+    if n_cls < 1 or len(offs) != n_cls or any(n < 0 or o < 0 or o + 2 * n > order.numel() for o, n in zip(offs, lens)):
+        raise ValueError("delong_place: offsets %s / lengths %s do not fit an order array of %d entries" % (offs, lens, order.numel()))
+    if not 1 <= n_units <= BOOT_MAX_UNITS:
+        raise ValueError("delong_place: %d units (1 .. 2^24 are supported)" % n_units)
+    if out is None:
+        out = torch.empty(4 * n_cls, n_units, dtype=torch.int64, device=order.device)
+    require_cuda(out)
+    assert out.dtype == torch.int64 and out.dim() == 2 and out.shape[0] == 4 * n_cls and out.shape[1] >= n_units and out.stride(1) == 1 \
+        and (out.shape[0] == 1 or out.stride(0) >= n_units), "out: int64 (4 C, >= n_units) rows"
+    check(lib().cx_delong_place(ptr(order), (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens), n_cls, n_units, ptr(out),
+                                out.stride(0), stream_ptr()), "cx_delong_place")
+    return out[:, :n_units]
+
+
+def int_gram(z, n_units):
+    """cx_delong_gram: g = z[:, :n_units] @ z[:, :n_units].T in int64 arithmetic that wraps mod 2^64.  z: int64 (Q, >= n_units) on the GPU
+    with unit column stride, Q in 1 .. DELONG_MAX_ROWS.  Returns an int64 (Q, Q) tensor, symmetric."""
+    require_cuda(z)
+    n_units = int(n_units)
+    assert z.dtype == torch.int64 and z.dim() == 2 and z.stride(1) == 1 and z.shape[1] >= n_units, "z: int64 (Q, >= n_units) rows"
+    n_rows = z.shape[0]
+    if not 1 <= n_rows <= DELONG_MAX_ROWS:
+        raise ValueError("int_gram: %d rows (1 .. %d are supported)" % (n_rows, DELONG_MAX_ROWS))
+    if not 1 <= n_units <= BOOT_MAX_UNITS:
+        raise ValueError("int_gram: %d units (1 .. 2^24 are supported)" % n_units)
+    g = torch.empty(n_rows, n_rows, dtype=torch.int64, device=z.device)
+    check(lib().cx_delong_gram(ptr(z), z.stride(0) if n_rows > 1 else z.shape[1], n_rows, n_units, ptr(g), stream_ptr()), "cx_delong_gram")
+    return g
+
+
 # ---- pixel attribution maps (saliency.hip; chexpert_amd/saliency.py composes them and states them in numpy) ----
 SAL_MODES = {"none": 0, "sum": 1, "abs": 2, "max": 3}      # CX_SAL_NONE .. CX_SAL_MAX of the header
 SAL_PARTIALS = 128                                          # CX_SAL_PARTIALS

@@ -933,6 +933,34 @@ int cx_boot_calib(const uint32_t* counts, int ld, int n_rep, const int32_t* orde
                   const int64_t* offs /* host, [C] */, const int32_t* len /* host, [C] */, int C, int M, uint32_t* wsum, uint32_t* wpos,
                   uint64_t* csum, uint64_t* bnum, int U, void* stream);
 
+/* DeLong / Obuchowski variance of the AUROC (delong.hip; chexpert_amd/metrics.py: delong_auc, delong_auc_diff, and the numpy statement
+ * of both entry points, delong_place_reference / int_gram_reference, held bit for bit).  Integer arithmetic throughout.
+ * cx_delong_place reads exactly what cx_boot_auc reads (the `hi` then the `lo` order of every class's kept rows, len[c] entries each
+ * from order[offs[c]], an entry = unit index in bits 0-30 | label << 31; offs / len are HOST arrays) and writes the unit sums of the
+ * doubled placements into z, an int64 table of 4 C rows of pitch ldz >= U (the padding is left untouched; the U columns are zeroed by
+ * the entry point itself).  With M the positives of the class, ties counted half:
+ *   a positive i:  X2_i = 2 #{neg j : s_j < s_i} + #{neg j : s_j = s_i} = (negatives in front of i in hi) + (those in front in lo)
+ *   a negative j:  Y2_j = 2 #{pos i : s_i > s_j} + #{pos i : s_i = s_j} = (M - positives in front in lo) + (M - those in front in hi)
+ *   z[4c][u] = sum of X2 over unit u's positives,  z[4c+1][u] = their number,  z[4c+2][u] = sum of Y2 over its negatives,
+ *   z[4c+3][u] = their number;  sum_u z[4c] = sum_u z[4c+2] = the num2 of cx_boot_auc for a count row of ones
+ * One 1024-thread workgroup per (class, order, chunk of CX_DELONG_WG_ENTRIES entries): a pass over the whole list that counts M and
+ * the positives in front of the chunk, then the chunk, whose exclusive prefix count of positives (the negatives in front are the
+ * position minus it) comes from wave ballots, an LDS scan of the wave totals and a running carry; every entry is added to its unit's
+ * row with 64-bit integer atomics (integer adds commute: the same bits on every run).  No workgroup waits on another.  Unit indices
+ * >= U are CLAMPED to U - 1; len[c] may be 0 and may differ by class.
+ * CX_EINVAL: a null pointer, C < 1, a negative len[c] or offs[c].  CX_ESHAPE: U outside [1, CX_BOOT_MAX_UNITS], ldz < U.  CX_EALIGN:
+ * order not 4-byte, z not 8-byte aligned.
+ * cx_delong_gram: g[p][q] = sum_{u < U} z[p][u] * z[q][u] mod 2^64 for the Q rows of z (pitch ldz >= U), g row-major Q x Q, symmetric
+ * (p <= q is computed and mirrored); the entry point zeroes g itself.  A workgroup stages tiles of CX_DELONG_TILE units x Q rows in
+ * LDS (33 KB at Q = 128), a thread keeps up to three 4 x 4 blocks of g in registers over all the tiles of its workgroup (64-bit
+ * multiply-add on the vector ALU) and adds them to g with 64-bit integer atomics at the end.
+ * CX_EINVAL: a null pointer.  CX_ESHAPE: Q outside [1, CX_DELONG_MAX_ROWS], U outside [1, CX_BOOT_MAX_UNITS], ldz < U.  CX_EALIGN: z or
+ * g not 8-byte aligned.  Additive entry points of ABI 10.                                                                          */
+enum { CX_DELONG_MAX_ROWS = 128, CX_DELONG_WG_ENTRIES = 16384, CX_DELONG_TILE = 32 };
+int cx_delong_place(const int32_t* order /* device */, const int64_t* offs /* host, [C] */, const int32_t* len /* host, [C] */, int C,
+                    int U, int64_t* z, int ldz, void* stream);
+int cx_delong_gram(const int64_t* z, int ldz, int Q, int U, int64_t* g, void* stream);
+
 /* Pixel attribution maps (saliency.hip; chexpert_amd/saliency.py: input_gradient, smoothgrad, integrated_gradients, and the numpy
  * statement of the three entry points, points_reference / accumulate_reference / finish_reference): the glue around the eval-mode
  * forward + backward with dx.  fp32 NCHW, N = 3 * H * W floats per row; every product and every sum below is rounded to fp32 on its
