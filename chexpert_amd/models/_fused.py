@@ -2,7 +2,6 @@
 autograd function), the host side of their engines (FusedEngine: flat parameter masters, weight packing, workspaces, the step
 protocol of backward) and the coefficient-vector bookkeeping (_Vec, _BN)."""
 import contextlib
-import os
 
 import torch
 import torch.nn as nn
@@ -378,23 +377,18 @@ class _Vec:
 
 
 class _BN:
-    """Vector slots of one BatchNorm."""
+    """Vector slots of one BatchNorm: forward coefficients sc / sh / mean / rstd, backward coefficients pa / pb / pc."""
 
-    def __init__(self, V, C, fz, bz):
+    def __init__(self, V, C):
         self.C = C
-        self.sum, self.sq = fz.take(C), fz.take(C)                    # zeroed every forward
-        self.S1, self.S2 = bz.take(C), bz.take(C)                     # zeroed every backward
         self.sc, self.sh, self.mean, self.rstd = (V.take(C) for _ in range(4))
         self.pa, self.pb, self.pc = (V.take(C) for _ in range(3))
 
     @staticmethod
     def plan(bns):
-        """Slots of every BatchNorm of `bns` in one vector laid out as [forward-zeroed sums | backward-zeroed sums | the rest].
-        Returns ({id(bn): _BN}, the _Vec of the rest, for more slots behind them, fwd_zero, bwd_zero)."""
-        nf = sum(2 * _up4(bn.num_features) for bn in bns)
-        fz, bz, rest = _Vec(0), _Vec(nf), _Vec(2 * nf)
-        slots = {id(bn): _BN(rest, bn.num_features, fz, bz) for bn in bns}
-        return slots, rest, (0, nf), (nf, nf)
+        """Slots of every BatchNorm of `bns` in one vector.  Returns ({id(bn): _BN}, the _Vec, for more slots behind them)."""
+        V = _Vec()
+        return {id(bn): _BN(V, bn.num_features) for bn in bns}, V
 
 
 class FusedEngine:
@@ -406,9 +400,6 @@ class FusedEngine:
         self.model = model
         # activation storage type: bf16, or fp32 = the parity mode of north_star ("1e-3 fp32")
         self.dtype = getattr(model, "_storage_dtype", torch.bfloat16)
-        # deterministic statistics and weight gradients (per-workgroup rows summed in row order, slab sums): two steps on the same
-        # batch give the same bits; CHEXPERT_DET=0 keeps the fp32 atomics
-        self.det = os.environ.get("CHEXPERT_DET", "1") != "0"
         self.flat = self.flat_grad = self.device = None
         self.pool = {}
         self.reducer = None          # chexpert_amd.parallel.GradReducer when data-parallel
@@ -535,27 +526,25 @@ class FusedEngine:
         return (bn.weight, bn.bias, bn.eps, bn.momentum if bn.momentum is not None else 0.1,
                 bn.running_mean if track else None, bn.running_var if track else None)
 
-    # ---- BatchNorm coefficients of an engine that keeps its _BN slots in `self.bn` ({id(bn): _BN}) and, in deterministic mode,
-    # its statistic rows in ws.slab[0] / ws.slab[1] (ResNet, EfficientNet)
+    # ---- BatchNorm coefficients of an engine that keeps its _BN slots in `self.bn` ({id(bn): _BN}) and its statistic rows in
+    # ws.slab[0] / ws.slab[1] (ResNet, EfficientNet)
     def _bn_coef(self, ws, bn, count, train, rows=None):
-        """Forward coefficients of `bn` (scale, shift, mean, rstd) from the sums of `count` values per channel its producer has
-        just written (`rows` statistic rows in deterministic mode), with the running-statistic update; eval: from the running
-        statistics."""
+        """Forward coefficients of `bn` (scale, shift, mean, rstd) from the `rows` statistic rows over `count` values per channel
+        its producer has just written, with the running-statistic update; eval: from the running statistics."""
         S, v = self.bn[id(bn)], self._v
         if train:
-            ssum, ssq, reps, rstride = (ws.slab[0], ws.slab[1], rows, S.C) if self.det else (v(ws, S.sum), v(ws, S.sq), 1, 0)
-            ops.bn_coef(ssum, ssq, count, *self._bn_train(bn), v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), S.C,
-                        replicas=reps, rstride=rstride)
+            ops.bn_coef(ws.slab[0], ws.slab[1], count, *self._bn_train(bn), v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), S.C,
+                        replicas=rows, rstride=S.C)
         else:
             ops.bn_coef_eval(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, v(ws, S.sc), v(ws, S.sh), v(ws, S.mean),
                              v(ws, S.rstd), S.C)
 
-    def _bn_bwd(self, ws, bn, r, count):
-        """Backward coefficients pa / pb / pc of `bn` and its dgamma / dbeta from the backward sums r = (S1, S2, replicas, rstride)
-        over `count` values per channel; everything else follows from bn's slot."""
+    def _bn_bwd(self, ws, bn, rows, count, s2=None):
+        """Backward coefficients pa / pb / pc of `bn` and its dgamma / dbeta from the `rows` statistic rows of its backward sums S1 /
+        S2 over `count` values per channel (s2: the rows of S2 where they are not ws.slab[1]); everything else follows from bn's slot."""
         S, v, G = self.bn[id(bn)], self._v, self.grad_of
-        self.bn_bwd_coef(ws, bn, r[0], r[1], count, bn.weight, v(ws, S.mean), v(ws, S.rstd), G(bn.weight), G(bn.bias), None, None,
-                         v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), S.C, replicas=r[2], rstride=r[3])
+        self.bn_bwd_coef(ws, bn, ws.slab[0], ws.slab[1] if s2 is None else s2, count, bn.weight, v(ws, S.mean), v(ws, S.rstd),
+                         G(bn.weight), G(bn.bias), None, None, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), S.C, replicas=rows, rstride=S.C)
 
     @staticmethod
     def _v(ws, slot, n=None):
@@ -621,7 +610,7 @@ class FusedEngine:
     # ---- backward
     def _defer_wgrad(self):
         """Whether a backward pass defers the ordered slab sums of its weight gradients to one table-driven launch at its end."""
-        return self.det
+        return True
 
     def backward(self, ws, dlogits, dx=None):
         """The backward pass of the forward that filled `ws`, from d loss / d logits; dx: None, or an fp32 (B,3,H,W) buffer that also
@@ -629,7 +618,7 @@ class FusedEngine:
         the flat gradient buffer (bound here when some .grad is None)."""
         if not getattr(ws, "recorded", True):
             raise RuntimeError("this eval forward recorded nothing for a backward: run forward(x, False, record=True)")
-        ops.set_det_wgrad(self.det)            # reproducible weight-gradient sums with the deterministic statistics
+        ops.set_det_wgrad(True)                # reproducible weight-gradient sums beside the ordered statistic rows
         # the ordered slab sums run as one table-driven launch at the end of the pass (ops.wgrad_defer_*); a data-parallel run
         # flushes them before each gradient bucket leaves (GradReducer.pre_launch)
         deferred = self._defer_wgrad() and ops.wgrad_defer_begin(self.device)

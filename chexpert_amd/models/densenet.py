@@ -241,7 +241,7 @@ class _Workspace:
         self.zeros = torch.zeros(max(eng.growth, 8), dtype=torch.float32, device=dev)
         # deterministic statistics (CxConv.stat_det): every producer writes per-workgroup rows into this scratch pair and the
         # coefficient kernel that follows on the same stream sums them in row order
-        self.slab = torch.empty(2, eng.SLAB, dtype=torch.float32, device=dev) if eng.det else None
+        self.slab = torch.empty(2, eng.SLAB, dtype=torch.float32, device=dev)
 
     def alloc_backward(self, eng, dev):
         if self.dz0 is not None:
@@ -272,7 +272,7 @@ class _Workspace:
 # --------------------------------------------------------------------------------------------- engine
 class _Slots:
     """A record of named vector slots.  C: the channels of the BatchNorm it serves; such a record carries the field names of a
-    `_fused._BN` as far as it has them (sum, sq, S1, S2, sc, sh, mean, rstd, pa, pb, pc), so the operand helpers take either."""
+    `_fused._BN` as far as it has them (sc, sh, mean, rstd, pa, pb, pc), so the operand helpers take either."""
 
     def __init__(self, C=None, **slots):
         self.C = C
@@ -282,53 +282,34 @@ class _Slots:
 class _Engine(FusedEngine):
     """Host-side schedule: issues the kernel sequence of forward and backward on the current stream."""
     SLAB = 1 << 22               # floats per half of the statistic-row scratch (rows x channels of the largest producer)
-    EW_ROWS = 2048               # workgroups (= rows) of the element-wise statistic producers in deterministic mode
+    EW_ROWS = 2048               # workgroups (= rows) of the element-wise statistic producers
 
-    # ---- statistics plumbing for the two modes (deterministic: rows in ws.slab; CHEXPERT_DET=0: atomic sums in the records), named
-    # as in the ResNet engine: keywords of a convolution producer (_sp), (sum, sq, stat_rows) of an element-wise producer (_ew),
-    # (sum, sq, replicas, rstride) for the consumer (_sc).  S: the record of the sums -- its forward sum / sq, with `bwd` its S1 / S2.
-    # DenseNet's own: the sums a convolution produces are held stat_replicas times (copies=False: once -- what the stem
-    # convolution and the element-wise kernels add into), and a producer may write the channel range sub = (first, channels) of S
-    @staticmethod
-    def _sums(S, bwd, sub=None):
-        """(slot, slot, pitch of the copies) of S's forward sum / sq or backward S1 / S2, the slots cut to the channel range sub"""
-        a, b = (S.S1, S.S2) if bwd else (S.sum, S.sq)
-        if sub is not None:
-            return (a[0] + sub[0], sub[1]), (b[0] + sub[0], sub[1]), a[1]
-        return a, b, a[1]
-
+    # ---- statistics plumbing: every producer of a BatchNorm's sums writes one row per workgroup into ws.slab[0] / ws.slab[1], at
+    # the pitch of the C channels it produces, and returns the number of rows; the coefficient kernel that follows sums them in row
+    # order.  Named as in the ResNet engine: keywords of a convolution producer (_sp), (sum, sq, stat_rows) of an element-wise
+    # producer (_ew), (sum, sq, replicas, rstride) for the consumer (_sc).  A forward producer has none in an eval forward (`bwd`: the
+    # backward sums S1 / S2, which the frozen backward takes too)
     def _ew_rows(self, C):
         return min(self.EW_ROWS, self.SLAB // C)
 
-    def _sp(self, ws, S, bwd=False, sub=None, copies=True):
+    def _sp(self, ws, C, bwd=False):
         if ws.frozen and not bwd:
             return {}
-        if self.det:
-            C = S.C if sub is None else sub[1]
-            return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // C, stat_rstride=C)
-        a, b, pitch = self._sums(S, bwd, sub)
-        if not copies:
-            return dict(stat_sum=self._v(ws, a), stat_sq=self._v(ws, b))
-        return dict(stat_sum=self._v(ws, a), stat_sq=self._v(ws, b), stat_replicas=self.stat_replicas, stat_rstride=pitch)
+        return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // C, stat_rstride=C)
 
-    def _ew(self, ws, S, bwd=False, sub=None, rows=None):
+    def _ew(self, ws, C, bwd=False, rows=None):
         if ws.frozen and not bwd:
             return None, None, 0
-        if self.det:
-            return ws.slab[0], ws.slab[1], rows or self._ew_rows(S.C if sub is None else sub[1])
-        a, b, _ = self._sums(S, bwd, sub)
-        return self._v(ws, a), self._v(ws, b), 0
+        return ws.slab[0], ws.slab[1], rows or self._ew_rows(C)
 
-    def _sc(self, ws, S, rows, bwd=False, copies=True):
-        if self.det:
-            return ws.slab[0], ws.slab[1], rows, S.C
-        a, b, pitch = self._sums(S, bwd)
-        return self._v(ws, a), self._v(ws, b), self.stat_replicas if copies else 1, pitch if copies else 0
+    @staticmethod
+    def _sc(ws, C, rows):
+        return ws.slab[0], ws.slab[1], rows, C
 
     def _fresh(self, ws, rows, lo, n):
         """The pending statistic rows of a block buffer's newest channels [lo, lo + n), as cx_bn_coef_moments takes them: the next
-        BatchNorm over the buffer reduces them (deterministic training forward; None otherwise)."""
-        return (ws.slab[0], ws.slab[1], rows, n, lo, n) if self.det and not ws.frozen else None
+        BatchNorm over the buffer reduces them (training forward; None otherwise)."""
+        return None if ws.frozen else (ws.slab[0], ws.slab[1], rows, n, lo, n)
 
     # ---- operand keywords that are DenseNet's own (FusedEngine has those of a BatchNorm record)
     @staticmethod
@@ -349,7 +330,7 @@ class _Engine(FusedEngine):
         ch, v = self._ch, self._v
         return dict(epilogue=ops.EPI_MASK, ex=ch(y, c_), e_sc=ch(v(ws, S.sc), c_), e_sh=ch(v(ws, S.sh), c_), e_mu=ch(v(ws, S.mean), c_),
                     e_r=ch(v(ws, S.rstd), c_), e_scale=ch(v(ws, S.sc), c_) if by_sc else ws.ones[:S.C],
-                    **(self._sp(ws, S, bwd=True) if stat is None else stat))
+                    **(self._sp(ws, S.C, bwd=True) if stat is None else stat))
 
     def __init__(self, model):
         super().__init__(model)
@@ -369,11 +350,9 @@ class _Engine(FusedEngine):
                 # DenseNet-BC rounds it up, and pads between the two branches of an attention-augmented transition)
                 c = getattr(f, "denseblock%d" % (len(self.blocks) + 1)).denselayer1.norm1.num_features
         self.c_final = c
-        self.stat_replicas = 16      # legacy (atomic) statistics: copies of every conv-produced vector (memory-side contention)
-        # Deterministic statistics: per-workgroup rows summed in a fixed order instead of fp32 atomics (bit-identical activations,
-        # losses and gradients from run to run); CHEXPERT_DET=0 brings the atomics back.  The AA transitions feed a block's first
-        # channels from two kernels -- conv branch and attention out-projection: their statistic rows are reduced one after the
-        # other, see _aa_forward.
+        # Statistics are per-workgroup rows summed in a fixed order (bit-identical activations, losses and gradients from run to
+        # run).  The AA transitions feed a block's first channels from two kernels -- conv branch and attention out-projection:
+        # their statistic rows are reduced one after the other, see _aa_forward.
         self.drop_rate = float(getattr(model, "drop_rate", 0.0))
         self.drop_seed = None        # device int64: the dropout kernels' seed, advanced once per training forward (graph-replayable)
         # two dense layers per fused 1x1 backward pass (_pair_backward): "0" never (default: measured in round 4, the pass saves
@@ -386,33 +365,27 @@ class _Engine(FusedEngine):
 
     # ---- coefficient-vector layout
     def _plan_vectors(self):
-        """Carves the coefficient vector into self.plan: .stem (conv0's sum / sq, norm0's sc / sh / mean / rstd and backward sums
-        S1 / S2), .blocks -- per block its replicated sums (sum, sq), its channels' mean / rstd, the exit norm's (transition norm,
-        norm5) sc / sh and backward sums S1 / S2, the accumulators A / Bc of the deferred BatchNorm terms, and .layers --, per
-        layer .n1 (sc, sh, replicated backward sums S1 / S2; mean / rstd are the block's, cut to the layer's input channels), .n2
-        (sc, sh, mean, rstd, the bottleneck output's replicated sum / sq, replicated S1 / S2, pa / pb / pc) and the slice triple
-        qa / qb / qc of the layer's output channels; .q and .p: the shared triples of a block's first channels and of norm0
-        (the stem's pa / pb / pc are .p cut to its channels).  The takes keep one order, whatever record files them: the
-        layout is [sums zeroed every forward | forward coefficients | sums zeroed every backward | backward coefficients]."""
-        V, R, g_, mid, ci = _Vec(), self.stat_replicas, self.growth, self.mid, self.c_init
+        """Carves the coefficient vector into self.plan: .stem (norm0's sc / sh / mean / rstd), .blocks -- per block its channels'
+        mean / rstd, the exit norm's (transition norm, norm5) sc / sh, the accumulators A / Bc of the deferred BatchNorm terms, and
+        .layers --, per layer .n1 (sc, sh; mean / rstd are the block's, cut to the layer's input channels), .n2 (sc, sh, mean, rstd,
+        pa / pb / pc) and the slice triple qa / qb / qc of the layer's output channels; .q and .p: the shared triples of a block's
+        first channels and of norm0 (the stem's pa / pb / pc are .p cut to its channels).  No sums live here: they are rows of
+        ws.slab.  The takes keep one order, whatever record files them: the layout is [forward coefficients | A / Bc, zeroed
+        every backward | backward coefficients]."""
+        V, g_, mid, ci = _Vec(), self.growth, self.mid, self.c_init
         self._spans = []
 
-        def take(n, copies=1):
-            """(copies > 1: that many copies, n floats apart -- the conv kernels spread their atomics over them)"""
-            self._spans.append(V.take(n * copies))
-            return (self._spans[-1][0], n)
-        per_block = lambda n_of, k, copies=1: [[take(n_of(c, n), copies) for _ in range(k)] for c, n in self.blocks]
-        per_layer = lambda n_of, k, copies=1: [[[take(n_of(c, i), copies) for _ in range(k)] for i in range(n)] for c, n in self.blocks]
+        def take(n):
+            self._spans.append(V.take(n))
+            return self._spans[-1]
+        per_block = lambda n_of, k: [[take(n_of(c, n)) for _ in range(k)] for c, n in self.blocks]
+        per_layer = lambda n_of, k: [[[take(n_of(c, i)) for _ in range(k)] for i in range(n)] for c, n in self.blocks]
         ct, cin, mid_, g__ = (lambda c, n: c + n * g_), (lambda c, i: c + i * g_), (lambda c, i: mid), (lambda c, i: g_)
-        st0 = [take(ci) for _ in range(2)]
-        bst, yst = per_block(ct, 2, R), per_layer(mid_, 2, R)
-        self.fwd_zero = (0, V.n)                                           # zeroed at the start of each forward
         n0 = [take(ci) for _ in range(4)]
         bmr, n1, n2, nt = per_block(ct, 2), per_layer(cin, 2), per_layer(mid_, 4), per_block(ct, 2)
         b0 = V.n
-        S0 = [take(ci) for _ in range(2)]
-        S1, S2, St, AB = per_layer(cin, 2, R), per_layer(mid_, 2, R), per_block(ct, 2), per_block(ct, 2)
-        self.bwd_zero = (b0, V.n - b0)
+        AB = per_block(ct, 2)
+        self.bwd_zero = (b0, V.n - b0)                                     # the backward accumulates into A / Bc
         # per-layer AFFINE2 vectors (the two-layer pass of _pair_backward holds both its layers' norm2 vectors at once)
         ql, pl = per_layer(g__, 3), per_layer(mid_, 3)
         q = [take(max(mid, ci, max(c for c, _ in self.blocks))) for _ in range(3)]         # slice AFFINE2
@@ -420,17 +393,16 @@ class _Engine(FusedEngine):
         names = lambda keys, *lists: dict(zip(keys.split(), (t for l in lists for t in l)))
         blocks = []
         for bi, (c, n) in enumerate(self.blocks):
-            layers = [_Slots(n1=_Slots(cin(c, i), mean=(bmr[bi][0][0], cin(c, i)), rstd=(bmr[bi][1][0], cin(c, i)),
-                                       **names("sc sh S1 S2", n1[bi][i], S1[bi][i])),
-                             n2=_Slots(mid, **names("sc sh mean rstd sum sq S1 S2 pa pb pc", n2[bi][i], yst[bi][i], S2[bi][i], pl[bi][i])),
+            layers = [_Slots(n1=_Slots(cin(c, i), mean=(bmr[bi][0][0], cin(c, i)), rstd=(bmr[bi][1][0], cin(c, i)), **names("sc sh", n1[bi][i])),
+                             n2=_Slots(mid, **names("sc sh mean rstd pa pb pc", n2[bi][i], pl[bi][i])),
                              **names("qa qb qc", ql[bi][i])) for i in range(n)]
-            blocks.append(_Slots(ct(c, n), layers=layers, **names("sum sq mean rstd sc sh S1 S2 A Bc", bst[bi], bmr[bi], nt[bi], St[bi], AB[bi])))
-        stem = _Slots(ci, **names("sum sq sc sh mean rstd S1 S2 pa pb pc", st0, n0, S0, [(t[0], ci) for t in p]))
+            blocks.append(_Slots(ct(c, n), layers=layers, **names("mean rstd sc sh A Bc", bmr[bi], nt[bi], AB[bi])))
+        stem = _Slots(ci, **names("sc sh mean rstd pa pb pc", n0, [(t[0], ci) for t in p]))
         self.plan = _Slots(stem=stem, blocks=blocks, q=_Slots(**names("qa qb qc", q)), p=_Slots(**names("pa pb pc", p)), dpooled=take(0))
         self.vec_size = V.n
 
     def vector_slots(self):
-        """Every (offset, length) span of the coefficient vector that the plan handed out (a replicated sum: all its copies)."""
+        """Every (offset, length) span of the coefficient vector that the plan handed out."""
         return iter(self._spans)
 
     def norm5_operands(self, ws):
@@ -473,24 +445,23 @@ class _Engine(FusedEngine):
         return buf.shape[0] * buf.shape[1] * buf.shape[2]
 
     # ---- forward
-    def _bn(self, ws, S, bn, count, stats):
-        """scale / shift / mean / rstd of BatchNorm `bn` into its record S; stats = (sum, sq, replicas, rstride) of its input (_sc),
-        which an eval forward does not read."""
+    def _bn(self, ws, S, bn, count, rows=None):
+        """scale / shift / mean / rstd of BatchNorm `bn` into its record S, from the `rows` statistic rows of its input; an eval
+        forward takes the running statistics."""
         v = self._v
         out = v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), S.C
         if ws.frozen:
             ops.bn_coef_eval(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, *out)
         else:
-            ops.bn_coef(stats[0], stats[1], count, *self._bn_train(bn), *out, replicas=stats[2], rstride=stats[3])
+            ops.bn_coef(ws.slab[0], ws.slab[1], count, *self._bn_train(bn), *out, replicas=rows, rstride=S.C)
 
     def _bn_block(self, ws, blk, S, bn, count, fresh):
         """BatchNorm over the first S.C channels of the buffer of block `blk` (S: the .n1 of a dense layer, or blk itself for its
-        transition norm / norm5).  Batch moments of a buffer channel exist once (blk.mean / rstd): deterministic mode reduces only
-        the `fresh` channels -- those the previous launch produced -- from their statistic rows; the atomic mode re-reads the
-        replicated block sums."""
+        transition norm / norm5).  Batch moments of a buffer channel exist once (blk.mean / rstd): only the `fresh` channels --
+        those the previous launch produced -- are reduced, from their statistic rows."""
         v = self._v
-        if ws.frozen or not self.det:
-            return self._bn(ws, S, bn, count, (v(ws, blk.sum), v(ws, blk.sq), self.stat_replicas, blk.sum[1]))
+        if ws.frozen:
+            return self._bn(ws, S, bn, count)
         ops.bn_coef_moments(v(ws, S.mean), v(ws, S.rstd), count, *self._bn_train(bn), v(ws, S.sc), v(ws, S.sh), S.C, fresh)
 
     def forward(self, x, train, record=False):
@@ -507,22 +478,15 @@ class _Engine(FusedEngine):
             mult = 1 << (len(self.blocks) - 1)
             if u8 or H % mult or W % mult:
                 raise RuntimeError("the CIFAR-stem network takes (B,3,H,W) float images with H, W multiples of %d" % mult)
-            if not self.det:
-                raise RuntimeError("the CIFAR-stem schedule uses the deterministic statistic rows (unset CHEXPERT_DET=0)")
         elif H % 32 or W % 32:
             raise RuntimeError("input height/width must be multiples of 32 (got %dx%d)" % (H, W))
         self.bind(x.device)
         self.pack(train or record)          # (a step that differentiates repacks, as training does: a fused optimiser bumps no version)
         ws = self.acquire(B, H, W)
         self.recorded(ws, train, True)
-        if train and not self.det:
-            z0, zn = self.fwd_zero
-            ws.vec[z0:z0 + zn].zero_()
         rows = self._cifar_stem_forward(ws, x) if self.cifar else self._stem_forward(ws, x)
         fresh = self._fresh(ws, rows, 0, self.c_init)
         if train and self.drop_rate > 0:
-            if not self.det:
-                raise RuntimeError("drop_rate > 0 uses the deterministic statistic rows (unset CHEXPERT_DET=0)")
             if self.drop_seed is None:
                 rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
                 self.drop_seed = torch.tensor([(torch.initial_seed() + (rank << 40)) & 0x7fffffffffffffff], dtype=torch.int64,
@@ -550,10 +514,9 @@ class _Engine(FusedEngine):
             ops.u8_to_nhwc4(x.contiguous(), ws.x4)
         else:
             ops.nchw3_to_nhwc4(x.contiguous().float(), ws.x4)
-        rows = ops.conv_gemm(ws.x4, self.w_fwd(f.conv0), ws.c0, N=ci, mode=ops.MODE_STEM, **self._sp(ws, S, copies=False))
-        self._bn(ws, S, f.norm0, self._count(ws.c0), self._sc(ws, S, rows, copies=False))
-        return ops.bnrelu_maxpool_fwd(ws.c0, self._v(ws, S.sc), self._v(ws, S.sh), ws.buf[0][..., :ci], ws.amax,
-                                      *self._ew(ws, self.plan.blocks[0], rows=self._ew_rows(ci)))
+        rows = ops.conv_gemm(ws.x4, self.w_fwd(f.conv0), ws.c0, N=ci, mode=ops.MODE_STEM, **self._sp(ws, ci))
+        self._bn(ws, S, f.norm0, self._count(ws.c0), rows)
+        return ops.bnrelu_maxpool_fwd(ws.c0, self._v(ws, S.sc), self._v(ws, S.sh), ws.buf[0][..., :ci], ws.amax, *self._ew(ws, ci))
 
     def _cifar_stem_forward(self, ws, x):
         """conv0 (5x5, stride 1, pad 2) -> norm0 -> relu0 of the CIFAR form (attn_aug_conv.py:469-474).  The image is held with 8
@@ -561,9 +524,9 @@ class _Engine(FusedEngine):
         convolution that writes block 1's first channels.  Returns their statistic rows."""
         f, S, ci = self.model.features, self.plan.stem, self.c_init
         ops.nchw3_to_nhwc8(x.contiguous().float(), ws.x8)
-        rows = ops.conv_gemm(ws.x8, self.w_fwd(f.conv0), ws.c0, N=ci, kh=5, kw=5, pad=2, **self._sp(ws, S))
-        self._bn(ws, S, f.norm0, self._count(ws.c0), self._sc(ws, S, rows))
-        return ops.conv_gemm(ws.c0, self.eye, ws.buf[0][..., :ci], N=ci, **self._pro_bnrelu(ws, S), **self._sp(ws, S))
+        rows = ops.conv_gemm(ws.x8, self.w_fwd(f.conv0), ws.c0, N=ci, kh=5, kw=5, pad=2, **self._sp(ws, ci))
+        self._bn(ws, S, f.norm0, self._count(ws.c0), rows)
+        return ops.conv_gemm(ws.c0, self.eye, ws.buf[0][..., :ci], N=ci, **self._pro_bnrelu(ws, S), **self._sp(ws, ci))
 
     def _layer_forward(self, ws, bi, li, fresh):
         """Dense layer li of block bi: norm1's coefficients, conv1 into the bottleneck buffer, norm2's coefficients, conv2 into the
@@ -574,25 +537,24 @@ class _Engine(FusedEngine):
         cnt = self._count(buf)
         drop = self.drop_rate > 0 and not ws.frozen
         self._bn_block(ws, blk, L.n1, layer.norm1, cnt, fresh)
-        rows = ops.conv_gemm(buf[..., :cin], self.w_fwd(layer.conv1), y1, N=self.mid, **self._pro_bnrelu(ws, L.n1), **self._sp(ws, L.n2))
-        self._bn(ws, L.n2, layer.norm2, cnt, self._sc(ws, L.n2, rows))
+        rows = ops.conv_gemm(buf[..., :cin], self.w_fwd(layer.conv1), y1, N=self.mid, **self._pro_bnrelu(ws, L.n1), **self._sp(ws, self.mid))
+        self._bn(ws, L.n2, layer.norm2, cnt, rows)
         rows = ops.conv_gemm(y1, self.w_fwd(layer.conv2), buf[..., cin:cin + g_], N=g_, kh=3, kw=3, pad=1, **self._pro_bnrelu(ws, L.n2),
-                             **({} if drop else self._sp(ws, blk, sub=(cin, g_))))
+                             **({} if drop else self._sp(ws, g_)))
         if drop:
             # dropout on the new slice, in place; its statistic rows are those of the dropped-out values (what every later
             # BatchNorm of the block sees)
-            rows = ops.dropout_slice_fwd(buf[..., cin:cin + g_], self.drop_rate, self.drop_seed, bi * 256 + li,
-                                         *self._ew(ws, blk, sub=(cin, g_)))
+            rows = ops.dropout_slice_fwd(buf[..., cin:cin + g_], self.drop_rate, self.drop_seed, bi * 256 + li, *self._ew(ws, g_))
         return self._fresh(ws, rows, cin, g_)
 
     def _transition_forward(self, ws, bi, fresh):
         """BatchNorm transition after block bi: the norm's coefficients, then ReLU -> 2x2 average pool -> 1x1 convolution (in that
         order: they commute) into the first channels of block bi + 1.  Returns their pending statistic rows."""
-        blk, nxt, tr = self.plan.blocks[bi], self.plan.blocks[bi + 1], getattr(self.model.features, "transition%d" % (bi + 1))
+        blk, tr = self.plan.blocks[bi], getattr(self.model.features, "transition%d" % (bi + 1))
         cn = self.blocks[bi + 1][0]          # channels the transition produces (half the block's in the reference's networks)
         self._bn_block(ws, blk, blk, tr.norm, self._count(ws.buf[bi]), fresh)
         rows = ops.conv_gemm(ws.buf[bi], self.w_fwd(tr.conv), ws.buf[bi + 1][..., :cn], N=cn, mode=ops.MODE_POOL2,
-                             **self._pro_bnrelu(ws, blk), **self._sp(ws, nxt, sub=(0, cn)))
+                             **self._pro_bnrelu(ws, blk), **self._sp(ws, cn))
         return self._fresh(ws, rows, 0, cn)
 
     def _head_forward(self, ws, bi, fresh):
@@ -608,36 +570,30 @@ class _Engine(FusedEngine):
     def _aa_forward(self, ws, bi, fresh):
         """InstanceNorm -> ReLU -> AAConv2d(3x3, stride 2) from block buffer bi into the first channels of buffer bi+1.  No BatchNorm
         consumes block bi, whose mean / rstd backward still reads: the moments of its last slice are finished here.  Returns the
-        pending statistic rows of the attention channels (deterministic mode), which the next norm1 reduces."""
+        pending statistic rows of the attention channels (a training forward), which the next norm1 reduces."""
         v, blk, nxt, aa = self._v, self.plan.blocks[bi], self.plan.blocks[bi + 1], self._aa_transition(bi + 1)
         buf, nbuf, T = ws.buf[bi], ws.buf[bi + 1], ws.aa[bi]
         B, h, w, ct = buf.shape
-        det = self.det and not ws.frozen
+        train = not ws.frozen
         none = (None, None, 1e-5, 0.0, None, None)              # no gain, shift or running statistics: moments only
-        if det:
+        if train:
             ops.bn_coef_moments(v(ws, blk.mean), v(ws, blk.rstd), B * h * w, *none, None, None, ct, fresh)
-        elif not ws.frozen:
-            ops.bn_coef(v(ws, blk.sum), v(ws, blk.sq), B * h * w, *none, None, None, v(ws, blk.mean), v(ws, blk.rstd), ct,
-                        replicas=self.stat_replicas, rstride=blk.sum[1])
         cc = aa.conv.out_channels                               # convolution branch, then the attention channels
         cout = cc + aa.dv                                       # (= ct // 2 in the reference's networks)
         ops.stats_bc(buf, T.stat[0], T.stat[1])                 # one owner per (image, channel): plain stores
         ops.bn_coef(T.stat[0], T.stat[1], h * w, *none, T.coef[0], T.coef[1], None, None, B * ct)
         ops.affine_relu_bc(buf, T.coef[0], T.coef[1], T.A)
-        if det:
-            # the block's first channels come from two kernels: the conv branch's rows become moments at once (they share the
-            # scratch pair with the out-projection's rows), the attention channels' rows stay pending for the next norm1
-            rows = ops.conv_gemm(T.A, self.w_fwd(aa.conv), nbuf[..., :cc], N=cc, kh=3, kw=3, stride=2, pad=1, **self._sp(ws, nxt, sub=(0, cc)))
+        # the block's first channels come from two kernels: the conv branch's rows become moments at once (they share the scratch
+        # pair with the out-projection's rows), the attention channels' rows stay pending for the next norm1
+        rows = ops.conv_gemm(T.A, self.w_fwd(aa.conv), nbuf[..., :cc], N=cc, kh=3, kw=3, stride=2, pad=1,
+                             **(self._sp(ws, cc) if train else dict(stat_sum=None, stat_sq=None)))
+        if train:
             ops.bn_coef_moments(v(ws, nxt.mean, cc), v(ws, nxt.rstd, cc), B * (h // 2) * (w // 2), *none, None, None, cc,
                                 self._fresh(ws, rows, 0, cc))
-        else:
-            ssum, ssq, _ = self._ew(ws, nxt, sub=(0, cc))
-            ops.conv_gemm(T.A, self.w_fwd(aa.conv), nbuf[..., :cc], N=cc, kh=3, kw=3, stride=2, pad=1, stat_sum=ssum, stat_sq=ssq)
         ops.conv_gemm(T.A, self.w_fwd(aa.in_proj_qkv), T.QKV, N=2 * aa.dk + aa.dv, stride=2)
         ops.aa_attention_fwd(T.QKV, *aa.rel_tables(), T.O, T.LSE, aa.nh, aa.dk, aa.dv)
         object.__setattr__(aa, "_last", (T.QKV, T.LSE))
-        rows = ops.aa_outproj_fwd(T.O, aa.out_proj.weight, nbuf[..., cc:cout], *self._ew(ws, nxt, sub=(cc, aa.dv)),
-                                  stat_rstride=aa.dv if det else 0)
+        rows = ops.aa_outproj_fwd(T.O, aa.out_proj.weight, nbuf[..., cc:cout], *self._ew(ws, aa.dv), stat_rstride=aa.dv if train else 0)
         return self._fresh(ws, rows, cc, aa.dv)
 
     # ---- backward
@@ -726,15 +682,15 @@ class _Engine(FusedEngine):
         dpooled = torch.empty(ws.B, ct, dtype=torch.float32, device=self.device)
         ops.head_bwd(dlogits, ws.pooled, m.classifier.weight, G(m.classifier.weight), G(m.classifier.bias) if
                      m.classifier.bias is not None else None, dpooled)
-        if self.det and ws.B * ct > self.SLAB:
+        if ws.B * ct > self.SLAB:
             raise RuntimeError("batch too large for the statistic-row scratch (B*C = %d > %d)" % (ws.B * ct, self.SLAB))
         if self.pool_kind() != "avg":
             rows = self._pool_bwd(ws, dpooled, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
-                                  ws.gbuf[bi], *self._ew(ws, blk, bwd=True, rows=self.SLAB // ct), ops.POOL_ACT_RELU, done)
+                                  ws.gbuf[bi], *self._ew(ws, ct, bwd=True, rows=self.SLAB // ct), ops.POOL_ACT_RELU, done)
         else:
             rows = ops.gap_relu_bn_bwd(dpooled, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
-                                       ws.gbuf[bi], *self._ew(ws, blk, bwd=True, rows=self.SLAB // ct))
-        self._norm_bwd(ws, m.features.norm5, blk, self._sc(ws, blk, rows, bwd=True, copies=False), self._count(ws.buf[bi]), acc=blk,
+                                       ws.gbuf[bi], *self._ew(ws, ct, bwd=True, rows=self.SLAB // ct))
+        self._norm_bwd(ws, m.features.norm5, blk, self._sc(ws, ct, rows), self._count(ws.buf[bi]), acc=blk,
                        q=self._slice_q(ws, bi, self.blocks[bi][1] - 1))
 
     def _last_slice_coef(self, ws, bi):
@@ -763,7 +719,7 @@ class _Engine(FusedEngine):
         dyc = ws.dyc[bi][li] if ws.dyc is not None else None
         rows = ops.conv_gemm(gs, self.w_bwd(layer.conv2), dz2, N=self.mid, kh=3, kw=3, pad=1, pro_out=dyc, **self._pro_slice(xs, q),
                              **self._mask(ws, y1, n2))
-        red2 = self._sc(ws, n2, rows, bwd=True)
+        red2 = self._sc(ws, self.mid, rows)
         dw, x_n2 = G(layer.conv2.weight), self._x_bnrelu(ws, n2)
         if dyc is None or not ops.last_pro_out():
             # (fp32 mode, or a kernel without the side output) the slice as it lies in the block buffers, corrected on the fly
@@ -798,7 +754,7 @@ class _Engine(FusedEngine):
                              **self._mask(ws, x, L.n1, by_sc=True))
         if not fused:
             ops.conv_wgrad(dz2, x, G(layer.conv1.weight), **self._g_bnbwd(ws, y1, L.n2), **self._x_bnrelu(ws, L.n1))
-        self._norm_bwd(ws, layer.norm1, L.n1, self._sc(ws, L.n1, rows, bwd=True), self._count(x), acc=blk, q=self._slice_q(ws, bi, li - 1))
+        self._norm_bwd(ws, layer.norm1, L.n1, self._sc(ws, cin, rows), self._count(x), acc=blk, q=self._slice_q(ws, bi, li - 1))
         done(layer.norm1.weight)      # every gradient from this layer to the end of the buffer is final
 
     def _transition_backward(self, ws, bi, done):
@@ -814,8 +770,8 @@ class _Engine(FusedEngine):
         dpool = ws.dpool[:B * h * w * cprev].view(B, h, w, cprev)
         ops.conv_gemm(gs, self.w_bwd(tr.conv), dpool, N=cprev, **self._pro_slice(xs, q))
         rows = ops.unpool2_mask(dpool, pbuf, v(ws, prev.sc), v(ws, prev.sh), v(ws, prev.mean), v(ws, prev.rstd), v(ws, prev.sc), pg,
-                                *self._ew(ws, prev, bwd=True))
-        sred = self._sc(ws, prev, rows, bwd=True, copies=False)
+                                *self._ew(ws, cprev, bwd=True))
+        sred = self._sc(ws, cprev, rows)
         ops.conv_wgrad(gs, pbuf, G(tr.conv.weight), mode=ops.MODE_POOL2, **self._g_slice(xs, q), **self._x_bnrelu(ws, prev))
         self._norm_bwd(ws, tr.norm, prev, sred, self._count(pbuf), acc=prev, q=self._slice_q(ws, bi - 1, self.blocks[bi - 1][1] - 1))
         done(tr.norm.weight)
@@ -825,8 +781,8 @@ class _Engine(FusedEngine):
         f, v, G, S, ci = self.model.features, self._v, self.grad_of, self.plan.stem, self.c_init
         gs, xs = ws.gbuf[0][..., :ci], ws.buf[0][..., :ci]
         rows = ops.bnrelu_maxpool_bwd(ws.c0, v(ws, S.sc), v(ws, S.sh), v(ws, S.mean), v(ws, S.rstd), ws.amax, gs, xs,
-                                      *self._slice_q(ws, 0, -1)[:3], ws.dz0, *self._ew(ws, S, bwd=True))
-        self._norm_bwd(ws, f.norm0, S, self._sc(ws, S, rows, bwd=True, copies=False), self._count(ws.c0))
+                                      *self._slice_q(ws, 0, -1)[:3], ws.dz0, *self._ew(ws, ci, bwd=True))
+        self._norm_bwd(ws, f.norm0, S, self._sc(ws, ci, rows), self._count(ws.c0))
         ops.conv_wgrad(ws.dz0, ws.x4, G(f.conv0.weight), mode=ops.MODE_STEM, **self._g_bnbwd(ws, ws.c0, S))
         if dx is not None:
             ops.stem_input_grad(ws.dz0, ws.c0, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), f.conv0.weight, dx, stride=2, pad=3)
@@ -837,7 +793,7 @@ class _Engine(FusedEngine):
         f, v, G, S, ci = self.model.features, self._v, self.grad_of, self.plan.stem, self.c_init
         gs, xs = ws.gbuf[0][..., :ci], ws.buf[0][..., :ci]
         rows = ops.conv_gemm(gs, self.eye, ws.dz0, N=ci, **self._pro_slice(xs, self._slice_q(ws, 0, -1)), **self._mask(ws, ws.c0, S))
-        self._norm_bwd(ws, f.norm0, S, self._sc(ws, S, rows, bwd=True), self._count(ws.c0))
+        self._norm_bwd(ws, f.norm0, S, self._sc(ws, ci, rows), self._count(ws.c0))
         ops.conv_wgrad(ws.dz0, ws.x8, G(f.conv0.weight), kh=5, kw=5, pad=2, **self._g_bnbwd(ws, ws.c0, S))
         if dx is not None:
             ops.stem_input_grad(ws.dz0, ws.c0, v(ws, S.pa), v(ws, S.pb), v(ws, S.pc), f.conv0.weight, dx, stride=1, pad=2)
@@ -886,25 +842,22 @@ class _Engine(FusedEngine):
                       **self._mask(ws, buf, L.n1, by_sc=True, c_=slice(lo, hi), stat=stat))
             return dz2, self.w_bwd(layer.conv1)[lo * self.mid:hi * self.mid], gbuf[..., lo:hi], kw
 
-        def stat_region(S, lo, n, part, parts):
-            """(producer keywords, consumer tuple-maker) for the backward sums of S's channels [lo, lo + n) in one of `parts` regions"""
-            if self.det:
-                per = self.SLAB // parts
-                a, b_ = ws.slab[0][part * per:(part + 1) * per], ws.slab[1][part * per:(part + 1) * per]
-                return (dict(stat_sum=a, stat_sq=b_, stat_det=True, stat_replicas=per // n, stat_rstride=n), lambda rows: (a, b_, rows, n))
-            sa, sb, R, rstride = v(ws, S.S1)[lo:], v(ws, S.S2)[lo:], self.stat_replicas, S.S1[1]
-            return dict(stat_sum=sa, stat_sq=sb, stat_replicas=R, stat_rstride=rstride), lambda rows: (sa, sb, R, rstride)
+        def stat_region(n, part, parts):
+            """(producer keywords, consumer tuple-maker) for the backward sums of n channels in one of `parts` regions of the rows"""
+            per = self.SLAB // parts
+            a, b_ = ws.slab[0][part * per:(part + 1) * per], ws.slab[1][part * per:(part + 1) * per]
+            return dict(stat_sum=a, stat_sq=b_, stat_det=True, stat_replicas=per // n, stat_rstride=n), lambda rows: (a, b_, rows, n)
 
         self._layer_front(ws, bi, li, dz2_a, batch_w2)
         # layer a on slice li - 1 alone
-        st_kw, st_red = stat_region(La.n1, cin_b, self.growth, 0, 1)
+        st_kw, st_red = stat_region(self.growth, 0, 1)
         x_, w_, y_, kw_ = conv1_args(li, la, dz2_a, cin_b, cin_a, st_kw)
         rows = ops.conv_gemm(x_, w_, y_, fused_dw=G(la.conv1.weight).view(self.mid, cin_a)[:, cin_b:], **kw_)
         self._norm_bwd(ws, la.norm1, La.n1, st_red(rows), cnt, acc=blk, q=self._slice_q(ws, bi, li - 1), c_=slice(cin_b, cin_a))
         self._layer_front(ws, bi, li - 1, dz2_b, batch_w2)
         # both layers on [0, cin_b)
-        sa_kw, sa_red = stat_region(La.n1, 0, cin_b, 0, 2)
-        sb_kw, sb_red = stat_region(Lb.n1, 0, cin_b, 1, 2)
+        sa_kw, sa_red = stat_region(cin_b, 0, 2)
+        sb_kw, sb_red = stat_region(cin_b, 1, 2)
         rows = ops.conv1x1_bwd_pair(conv1_args(li, la, dz2_a, 0, cin_b, sa_kw), conv1_args(li - 1, lb, dz2_b, 0, cin_b, sb_kw),
                                     G(la.conv1.weight).view(self.mid, cin_a)[:, :cin_b], G(lb.conv1.weight).view(self.mid, cin_b))
         self._norm_bwd(ws, la.norm1, La.n1, sa_red(rows), cnt, acc=blk, c_=slice(0, cin_b))

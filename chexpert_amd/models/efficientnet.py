@@ -87,7 +87,7 @@ def same_pad(h_in, k, stride):
 class _Engine(FusedEngine):
     # forward / _backward are drivers over per-block methods (stem, MBConv block, head), as in the DenseNet and ResNet engines
     # (fp32 storage: generic f32-MFMA convolutions, the storage-typed depthwise / squeeze-excite / Swish kernels of csrc/effnet.hip,
-    # no tiled fast paths; deterministic mode: one owner per squeeze-excite sum)
+    # no tiled fast paths; one owner per squeeze-excite sum)
     def __init__(self, model):
         super().__init__(model)
         self.mb = [b for rep in model.blocks for b in rep]
@@ -96,7 +96,7 @@ class _Engine(FusedEngine):
         self.n_forward = 0           # forwards so far (ws.step)
         self.step_dev = None         # device-side count of the training forwards: what the Dropout / DropConnect masks are drawn from
         self.bns = [model.stem[1]] + [m for b in self.mb for m in b if isinstance(m, nn.BatchNorm2d)] + [model.head[1]]
-        self.bn, rest, self.fwd_zero, self.bwd_zero = _BN.plan(self.bns)
+        self.bn, rest = _BN.plan(self.bns)
         self.ones = rest.take(max(bn.num_features for bn in self.bns))
         self.vec_size = rest.n
 
@@ -149,7 +149,7 @@ class _Engine(FusedEngine):
         ws.pooled = e(B, 1280, dtype=f32)
         ws.logits = e(B, self.n_classes, dtype=f32)
         ws.vec = torch.zeros(self.vec_size, dtype=f32, device=dev)
-        ws.slab = torch.empty(2, self.SLAB, dtype=f32, device=dev) if self.det else None
+        ws.slab = torch.empty(2, self.SLAB, dtype=f32, device=dev)
         o, n = self.ones
         ws.vec[o:o + n].fill_(1.0)
         ws.bwd = ws.dw8 = None
@@ -168,35 +168,23 @@ class _Engine(FusedEngine):
             i = 3
         return conv_e, bn_e, mods[i], mods[i + 1], mods[i + 3], mods[i + 4], mods[i + 5]      # dw, bn_d, se, conv_p, bn_p
 
-    # ---- statistics plumbing for the two modes (deterministic: rows in ws.slab; CHEXPERT_DET=0: atomic sums in the _BN slots), named
-    # as in the ResNet engine: keywords of a convolution producer (_sp), (S1, S2, stat_rows) of an element-wise / depthwise producer
-    # (_ew), (S1, S2, replicas, rstride) for the consumer (_sc); _rows is the row scratch of the per-(image, channel) sums
+    # ---- statistics plumbing: every producer of a BatchNorm's sums writes one row per workgroup into ws.slab[0] / ws.slab[1], at
+    # the pitch of the BatchNorm's width, and returns the number of rows; the coefficient kernel that follows (_bn_coef, _bn_bwd)
+    # sums them in row order.  Named as in the ResNet engine: keywords of a convolution producer (_sp), (S1, S2, stat_rows) of an
+    # element-wise / depthwise producer (_ew).  Between a coefficient launch and the next producer ws.slab[0] is free: the
+    # squeeze-excite and pooling kernels keep the split rows of their per-(image, channel) sums there
     def _sp(self, ws, S):
         """Statistics keywords of a convolution that produces BatchNorm S's forward sums (none in an eval forward)."""
         if ws.frozen:
             return dict(stat_sum=None, stat_sq=None)
-        if self.det:
-            return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // S.C, stat_rstride=S.C)
-        return dict(stat_sum=self._v(ws, S.sum), stat_sq=self._v(ws, S.sq))
+        return dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // S.C, stat_rstride=S.C)
 
     def _ew(self, ws, S, bwd=False):
         """Where an element-wise / depthwise producer leaves BatchNorm S's forward sums (nowhere in an eval forward) or, with `bwd`,
         its backward sums S1 / S2."""
         if ws.frozen and not bwd:
             return None, None, 0
-        if self.det:
-            return ws.slab[0], ws.slab[1], min(self.ROWS, self.SLAB // S.C)
-        a, b = (S.S1, S.S2) if bwd else (S.sum, S.sq)
-        return self._v(ws, a), self._v(ws, b), 0
-
-    def _sc(self, ws, S, rows):
-        if self.det:
-            return ws.slab[0], ws.slab[1], rows, S.C
-        return self._v(ws, S.S1), self._v(ws, S.S2), 1, 0
-
-    def _rows(self, ws):
-        """(free between a coefficient launch and the next statistics producer)"""
-        return ws.slab[0] if self.det else None
+        return ws.slab[0], ws.slab[1], min(self.ROWS, self.SLAB // S.C)
 
     def _pro_bnbwd(self, ws, y, S):
         """input gradient: BatchNorm S's backward of the gradient operand, dY = dz * pa + y * pb + pc"""
@@ -227,9 +215,6 @@ class _Engine(FusedEngine):
             if self.step_dev is None or self.step_dev.device != x.device:
                 self.step_dev = torch.zeros(1, dtype=torch.int64, device=x.device)
             ops.counter_add(self.step_dev)
-            if not self.det:
-                z0, zn = self.fwd_zero
-                ws.vec[z0:z0 + zn].zero_()
         if u8:
             ops.u8_to_nhwc8(x.contiguous(), ws.x8)
         else:
@@ -269,7 +254,7 @@ class _Engine(FusedEngine):
         self._bn_coef(ws, bn_d, cnt, train, rows)
         # squeeze + excite (efficientnet.py:69-73) in two launches: the excitation kernel adds the pool's split rows itself
         sc, sh = v(ws, Sd.sc), v(ws, Sd.sh)
-        ops.gap_se_fwd(t["yd"], sc, sh, t["pooled"], se[1].weight, se[1].bias, se[3].weight, se[3].bias, t["h1"], t["s"], rows=self._rows(ws))
+        ops.gap_se_fwd(t["yd"], sc, sh, t["pooled"], se[1].weight, se[1].bias, se[3].weight, se[3].bias, t["h1"], t["s"], rows=ws.slab[0])
         ops.scale_act_bc(t["yd"], sc, sh, t["s"], t["u"])
         rows = ops.conv_gemm(t["u"], self.w_fwd(conv_p), t["yp"], N=c["cout"], **self._sp(ws, Sp))
         self._bn_coef(ws, bn_p, cnt, train, rows)
@@ -294,7 +279,7 @@ class _Engine(FusedEngine):
         if self.pool_kind() != "avg":               # set_pool: the pooling's kernel in the average's place
             self._pool_fwd(ws, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ops.POOL_ACT_SWISH)
         else:
-            ops.gap_affine_act(ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.pooled, act=2, rows=self._rows(ws))
+            ops.gap_affine_act(ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.pooled, act=2, rows=ws.slab[0])
         # Dropout in front of the classifier (efficientnet.py:169-171), train mode only
         p_do = m.head[5].p if train else 0.0
         ws.drop, ws.fc_in = None, ws.pooled
@@ -334,9 +319,6 @@ class _Engine(FusedEngine):
 
     def _backward(self, ws, dlogits, dx, done):
         self._alloc_bwd(ws)
-        if not self.det:
-            z0, zn = self.bwd_zero
-            ws.vec[z0:z0 + zn].zero_()
         g = self._head_backward(ws, dlogits, done)
         for bi in range(len(self.mb) - 1, -1, -1):
             g = self._mbconv_backward(ws, bi, g, done)
@@ -357,7 +339,7 @@ class _Engine(FusedEngine):
         else:
             rows = ops.se_act_bwd(None, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), v(ws, Sh.mean), v(ws, Sh.rstd), None, dpool, dzh,
                                   *self._ew(ws, Sh, bwd=True))
-        self._bn_bwd(ws, m.head[1], self._sc(ws, Sh, rows), B * ws.hw_last[0] * ws.hw_last[1])
+        self._bn_bwd(ws, m.head[1], rows, B * ws.hw_last[0] * ws.hw_last[1])
         g, xlast = ws.bwd["g"][-1], ws.blk[-1]["out"]
         ops.conv_gemm(dzh, self.w_bwd(m.head[0]), g, N=xlast.shape[3], **self._pro_bnbwd(ws, ws.yh, Sh))
         ops.conv_wgrad(dzh, xlast, G(m.head[0].weight), **self._g_bnbwd(ws, ws.yh, Sh))
@@ -378,7 +360,7 @@ class _Engine(FusedEngine):
             ops.scale_rows(g, t["dc"], gb)
             g = gb
         rows = ops.bn_lin_bwd_stats(g, t["yp"], v(ws, Sp.mean), v(ws, Sp.rstd), *self._ew(ws, Sp, bwd=True))
-        self._bn_bwd(ws, bn_p, self._sc(ws, Sp, rows), B * ho * wo)
+        self._bn_bwd(ws, bn_p, rows, B * ho * wo)
         du = bw["du"][:B * ho * wo * ce].view(B, ho, wo, ce)
         dzd = bw["dzd"][:B * ho * wo * ce].view(B, ho, wo, ce)
         ops.conv_gemm(g, self.w_bwd(conv_p), du, N=ce, **self._pro_bnbwd(ws, t["yp"], Sp))
@@ -392,7 +374,7 @@ class _Engine(FusedEngine):
             s1, s2, cap = self._ew(ws, Se, bwd=True)
             rows = ops.dwconv_dgrad(*dY, dw.weight, t["ye"], v(ws, Se.sc), v(ws, Se.sh), v(ws, Se.mean), v(ws, Se.rstd), dze, s1, s2,
                                     stat_rows=cap, **geo)
-            self._bn_bwd(ws, bn_e, self._sc(ws, Se, rows), B * hi * wi)       # (before the next producer re-uses the statistic rows)
+            self._bn_bwd(ws, bn_e, rows, B * hi * wi)       # (before the next producer re-uses the statistic rows)
             ops.dwconv_wgrad(*dY, t["ye"], v(ws, Se.sc), v(ws, Se.sh), G(dw.weight), **geo)
             ops.conv_gemm(dze, self.w_bwd(conv_e), gin, N=c["cin"], accumulate=c["skip"], **self._pro_bnbwd(ws, t["ye"], Se))
             ops.conv_wgrad(dze, xin, G(conv_e.weight), **self._g_bnbwd(ws, t["ye"], Se))
@@ -414,9 +396,9 @@ class _Engine(FusedEngine):
         ds = torch.empty(B, ce, dtype=torch.float32, device=self.device)
         dpl = torch.empty(B, ce, dtype=torch.float32, device=self.device)
         ops.se_bwd_fused(du, t["yd"], sc, sh, ds, t["s"], t["h1"], t["pooled"], se[1].weight, se[3].weight, G(se[1].weight),
-                         G(se[1].bias), G(se[3].weight), G(se[3].bias), dpl, rows=self._rows(ws))
+                         G(se[1].bias), G(se[3].weight), G(se[3].bias), dpl, rows=ws.slab[0])
         rows = ops.se_act_bwd(du, t["yd"], sc, sh, v(ws, Sd.mean), v(ws, Sd.rstd), t["s"], dpl, dzd, *self._ew(ws, Sd, bwd=True))
-        self._bn_bwd(ws, bn_d, self._sc(ws, Sd, rows), B * ho * wo)
+        self._bn_bwd(ws, bn_d, rows, B * ho * wo)
 
     def _stem_backward(self, ws, g, dx):
         """x0 = swish(bn(ys)) from its gradient g; the stem's weight gradient and, into dx when given, the input gradient"""
@@ -425,7 +407,7 @@ class _Engine(FusedEngine):
         dzs = ws.bwd["dze"][:ws.ys.numel()].view(ws.ys.shape)
         rows = ops.se_act_bwd(g, ws.ys, v(ws, S0.sc), v(ws, S0.sh), v(ws, S0.mean), v(ws, S0.rstd), None, None, dzs,
                               *self._ew(ws, S0, bwd=True))
-        self._bn_bwd(ws, m.stem[1], self._sc(ws, S0, rows), ws.ys.numel() // c0)
+        self._bn_bwd(ws, m.stem[1], rows, ws.ys.numel() // c0)
         # (persistent: its address is part of the deferred slab-sum table, which must not change from step to step)
         if ws.dw8 is None:
             ws.dw8 = torch.empty(c0, 8, 3, 3, dtype=torch.float32, device=self.device)

@@ -129,8 +129,7 @@ class _Engine(FusedEngine):
         self.keep_lo = [self.two_plane and i + 1 < n and ident[i + 1] for i in range(n)]
         self.fuse_fwd = [self.two_plane and self.fwd_join_fuse and ident[i] and stage_len[i] >= 6 and i + 1 < n for i in range(n)]
         self.cifar = isinstance(model, WideResNet)              # 3x3 stride-1 stem, no max-pool, three stages (:311-404)
-        # vector plan: [fwd-zero region | bwd-zero region | rest]
-        self.bn, rest, self.fwd_zero, self.bwd_zero = _BN.plan(list(self._all_bns()))
+        self.bn, rest = _BN.plan(list(self._all_bns()))
         cmax = 2048
         self.join = [[rest.take(self._last_bn(b).num_features) for _ in range(3)] for b in self.blocks]
         self.ones, self.zeros = rest.take(cmax), rest.take(cmax)
@@ -226,7 +225,7 @@ class _Engine(FusedEngine):
             ws.blk.append(t)
             h, w = ho, wo
         ws.pooled = torch.empty(B, self.model.fc.in_features, dtype=torch.float32, device=dev)
-        ws.slab = torch.empty(3, self.SLAB, dtype=torch.float32, device=dev) if self.det else None
+        ws.slab = torch.empty(3, self.SLAB, dtype=torch.float32, device=dev)
         ws.logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=dev)
         ws.vec = torch.zeros(self.vec_size, dtype=torch.float32, device=dev)
         o, n = self.ones
@@ -234,39 +233,26 @@ class _Engine(FusedEngine):
         ws.bwd = None
         return ws
 
-    # ---- statistics plumbing for the two modes (deterministic: rows in ws.slab; CHEXPERT_DET=0: atomic sums in the _BN slots), named
-    # as in the DenseNet engine: keywords of a convolution producer (_sp), (S1, S2, stat_rows) of an element-wise producer (_ew),
-    # (S1, S2, replicas, rstride) for the consumer (_sc)
+    # ---- statistics plumbing: every producer of a BatchNorm's sums writes one row per workgroup into ws.slab[0] / ws.slab[1], at
+    # the pitch of the BatchNorm's width, and returns the number of rows; the coefficient kernel that follows (_bn_coef, _bn_bwd)
+    # sums them in row order.  Named as in the DenseNet engine: keywords of a convolution producer (_sp), (S1, S2, stat_rows) of an
+    # element-wise producer (_ew)
     def _sp(self, ws, S, bwd=False, after=0):
         """Statistics keywords of a convolution that produces BatchNorm S's forward sums (none in an eval forward), or with `bwd`
         its backward sums S1 / S2 in a mask epilogue.  after: the rows of a first producer of the same sums -- this one's rows go
-        behind them, so one reduction over both adds them (deterministic mode)."""
+        behind them, so one reduction over both adds them."""
         if ws.frozen and not bwd:
             return {}
-        if self.det:
-            s, q = (ws.slab[0][after * S.C:], ws.slab[1][after * S.C:]) if after else (ws.slab[0], ws.slab[1])
-            return dict(stat_sum=s, stat_sq=q, stat_det=True, stat_replicas=self.SLAB // S.C - after, stat_rstride=S.C)
-        a, b = (S.S1, S.S2) if bwd else (S.sum, S.sq)
-        return dict(stat_sum=self._v(ws, a), stat_sq=self._v(ws, b))
+        return dict(stat_sum=ws.slab[0][after * S.C:], stat_sq=ws.slab[1][after * S.C:], stat_det=True,
+                    stat_replicas=self.SLAB // S.C - after, stat_rstride=S.C)
 
     def _ew(self, ws, S):
-        if self.det:
-            return ws.slab[0], ws.slab[1], min(self.EW_ROWS, self.SLAB // S.C)
-        return self._v(ws, S.S1), self._v(ws, S.S2), 0
-
-    def _sc(self, ws, S, rows):
-        if self.det:
-            return ws.slab[0], ws.slab[1], rows, S.C
-        return self._v(ws, S.S1), self._v(ws, S.S2), 1, 0
-
-    def _down_s2(self, ws, Sd):
-        """Where a join backward leaves S2 of the downsample BatchNorm Sd; its S1 is the last BatchNorm's (the same masked gradient)."""
-        return ws.slab[2] if self.det else self._v(ws, Sd.S2)
+        return ws.slab[0], ws.slab[1], min(self.EW_ROWS, self.SLAB // S.C)
 
     @staticmethod
     def _stat_slice(kw, c_):
         """statistics keywords of a producer restricted to the channel range c_ of their BatchNorm (grouped convolutions): the
-        vectors / row buffers start at the range's first channel, the row pitch stays the BatchNorm's width"""
+        row buffers start at the range's first channel, the row pitch stays the BatchNorm's width"""
         kw = dict(kw)
         for k in ("stat_sum", "stat_sq"):
             if kw.get(k) is not None:
@@ -284,8 +270,8 @@ class _Engine(FusedEngine):
                     **(kw if c_ is None else self._stat_slice(kw, c_)))
 
     def _bn_coef_part(self, ws, bn, count, rows, lo, n):
-        """_bn_coef for channels [lo, lo + n) of `bn` from `rows` statistic rows of pitch n (deterministic mode: an AAConv2d's
-        conv branch and its attention out-projection each produce the rows of their own channel range)."""
+        """_bn_coef for channels [lo, lo + n) of `bn` from `rows` statistic rows of pitch n (an AAConv2d's conv branch and its
+        attention out-projection each produce the rows of their own channel range)."""
         S, v = self.bn[id(bn)], self._v
         mom = bn.momentum if bn.momentum is not None else 0.1
         c = lambda t_: t_[lo:lo + n]
@@ -295,30 +281,25 @@ class _Engine(FusedEngine):
     # ---- forward
     def _aa_fwd(self, ws, aa, xin, yout, qkv_t, bn, stride, count, pro):
         """AAConv2d forward (attn_aug_conv.py:65-97) into `yout` = [conv branch | attention], and the coefficients of the BatchNorm
-        `bn` that follows (deterministic training mode: the statistic rows of the two kernels are reduced per channel range)."""
-        v, S, train = self._v, self.bn[id(bn)], not ws.frozen
-        p_ = yout.shape[3]
-        cc = p_ - aa.dv
-        det = train and self.det
-        sub = lambda slot, lo, n: None if slot is None else slot[lo:lo + n]
-        st = (lambda s_: v(ws, s_)) if train else (lambda s_: None)
-        if det:
-            rows = ops.conv_gemm(xin, self.w_fwd(aa.conv), yout[..., :cc], N=cc, kh=3, kw=3, stride=stride, pad=1, stat_sum=ws.slab[0],
-                                 stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // cc, stat_rstride=cc, **pro)
+        `bn` that follows (training: the statistic rows of the two kernels are reduced per channel range; an eval forward produces
+        no statistics)."""
+        train = not ws.frozen
+        cc = yout.shape[3] - aa.dv
+        stat = dict(stat_sum=ws.slab[0], stat_sq=ws.slab[1], stat_det=True, stat_replicas=self.SLAB // cc, stat_rstride=cc) if train \
+            else dict(stat_sum=None, stat_sq=None)
+        rows = ops.conv_gemm(xin, self.w_fwd(aa.conv), yout[..., :cc], N=cc, kh=3, kw=3, stride=stride, pad=1, **stat, **pro)
+        if train:
             self._bn_coef_part(ws, bn, count, rows, 0, cc)
-        else:
-            ops.conv_gemm(xin, self.w_fwd(aa.conv), yout[..., :cc], N=cc, kh=3, kw=3, stride=stride, pad=1,
-                          stat_sum=sub(st(S.sum), 0, cc), stat_sq=sub(st(S.sq), 0, cc), **pro)
         ops.conv_gemm(xin, self.w_fwd(aa.in_proj_qkv), qkv_t["QKV"], N=2 * aa.dk + aa.dv, stride=stride, **pro)
         ops.aa_attention_fwd(qkv_t["QKV"], *aa.rel_tables(), qkv_t["O"], qkv_t["LSE"], aa.nh, aa.dk, aa.dv)
         object.__setattr__(aa, "_last", (qkv_t["QKV"], qkv_t["LSE"]))
-        if det:
+        if train:
             rows = ops.aa_outproj_fwd(qkv_t["O"], aa.out_proj.weight, yout[..., cc:], ws.slab[0], ws.slab[1],
                                       stat_rows=min(self.EW_ROWS, self.SLAB // aa.dv), stat_rstride=aa.dv)
             self._bn_coef_part(ws, bn, count, rows, cc, aa.dv)
         else:
-            ops.aa_outproj_fwd(qkv_t["O"], aa.out_proj.weight, yout[..., cc:], sub(st(S.sum), cc, aa.dv), sub(st(S.sq), cc, aa.dv))
-            self._bn_coef(ws, bn, count, train)
+            ops.aa_outproj_fwd(qkv_t["O"], aa.out_proj.weight, yout[..., cc:], None, None)
+            self._bn_coef(ws, bn, count, False)
 
     def forward(self, x, train, record=False):
         """train: batch statistics (and running-statistic updates); eval: running statistics.  record (eval): also keep what
@@ -335,9 +316,6 @@ class _Engine(FusedEngine):
         self.pack(train or record)          # (a step that differentiates repacks, as training does: a fused optimiser bumps no version)
         ws = self.acquire(B, H, W)
         self.recorded(ws, train, record)
-        if train and not self.det:
-            z0, zn = self.fwd_zero
-            ws.vec[z0:z0 + zn].zero_()
         xin = self._cifar_stem_forward(ws, x) if self.cifar else self._stem_forward(ws, x)
         xin_lo, pending = None, None
         for bi in range(len(self.blocks)):
@@ -495,12 +473,10 @@ class _Engine(FusedEngine):
         ws.bwd = bw
 
     def _defer_wgrad(self):
-        return self.det and not self.cifar          # the CIFAR stem keeps immediate sums (read back at once)
+        return not self.cifar          # the CIFAR stem keeps immediate sums (read back at once)
 
     def _backward(self, ws, dlogits, dx, done):
         self._alloc_bwd(ws)
-        z0, zn = self.bwd_zero
-        ws.vec[z0:z0 + zn].zero_()
         self._head_backward(ws, dlogits, done)
         join_rows = None        # statistic rows of a join backward that ran in the epilogue of the block above (CX_EPI_JOIN)
         for bi in range(len(self.blocks) - 1, -1, -1):
@@ -537,17 +513,13 @@ class _Engine(FusedEngine):
             s1, s2, n_rows = self._ew(ws, S)
             rows = ops.relu_bwd_stats(g, t["out"], t["y2" if self.basic else "y3"], v(ws, S.mean), v(ws, S.rstd), t["yd"],
                                       v(ws, Sd.mean) if Sd else None, v(ws, Sd.rstd) if Sd else None, g, s1, s2,
-                                      self._down_s2(ws, Sd) if Sd else None, stat_rows=n_rows, mask=t["mask"])
+                                      ws.slab[2] if Sd else None, stat_rows=n_rows, mask=t["mask"])
         ho, wo = t["hout"]
-        self._bn_bwd(ws, bn, self._sc(ws, S, rows), ws.B * ho * wo)
-        if Sd is not None and (self.det or self.basic):       # (deterministic: before the next producer re-uses the rows)
-            self._down_bn_bwd(ws, b, t, rows)
-
-    def _down_bn_bwd(self, ws, b, t, rows):
-        """coefficients of the downsample BatchNorm, which shares S1 with the block's last BatchNorm (_down_s2)"""
-        ho, wo = t["hout"]
-        s1, _, reps, rstride = self._sc(ws, self.bn[id(self._last_bn(b))], rows)
-        self._bn_bwd(ws, b.downsample[1], (s1, self._down_s2(ws, self.bn[id(b.downsample[1])]), reps, rstride), ws.B * ho * wo)
+        self._bn_bwd(ws, bn, rows, ws.B * ho * wo)
+        if Sd is not None:
+            # the downsample BatchNorm shares S1 with the block's last BatchNorm (the same masked gradient), its S2 rows are
+            # ws.slab[2]; its coefficients are taken here, before the next producer re-uses the rows
+            self._bn_bwd(ws, b.downsample[1], rows, ws.B * ho * wo, s2=ws.slab[2])
 
     def _gx(self, ws, bi):
         """Where block bi's input gradient goes, and whether it is added there: an identity block's convolutions accumulate into
@@ -580,8 +552,6 @@ class _Engine(FusedEngine):
     def _down_backward(self, ws, b, t, g, gx, xin):
         """input and weight gradient of a downsample block's 1x1 stride-s convolution, BatchNorm backward in the prologues"""
         Sd, convd = self.bn[id(b.downsample[1])], b.downsample[0]
-        if not (self.det or self.basic):         # (a Bottleneck's atomic sums: nothing re-uses them, the coefficients waited until here)
-            self._down_bn_bwd(ws, b, t, None)
         ops.conv_gemm(g, self.w_bwd(convd), gx, N=self._cin(b), tstride=b.stride, **self._pro_bnbwd(ws, t["yd"], Sd), accumulate=True)
         ops.conv_wgrad(g, xin, self.grad_of(convd.weight), stride=b.stride, **self._g_bnbwd(ws, t["yd"], Sd))
 
@@ -599,14 +569,14 @@ class _Engine(FusedEngine):
         dz2 = bw["dz2"][:B * ho * wo * p_].view(B, ho, wo, p_)
         rows = ops.conv_gemm(g, self.w_bwd(b.conv3), dz2, N=p_, **self._pro_bnbwd(ws, t["y3"], S3), **self._mask(ws, t["y2"], S2))
         ops.conv_wgrad(g, t["y2"], G(b.conv3.weight), **self._g_bnbwd(ws, t["y3"], S3), **self._x_bnrelu(ws, S2))
-        self._bn_bwd(ws, b.bn2, self._sc(ws, S2, rows), B * ho * wo)
+        self._bn_bwd(ws, b.bn2, rows, B * ho * wo)
         dz1 = bw["dz1"][:B * hi * wi * p_].view(B, hi, wi, p_)
         rows = self._conv2_backward(ws, b, t, dz2, dz1)
-        self._bn_bwd(ws, b.bn1, self._sc(ws, S1, rows), B * hi * wi)
+        self._bn_bwd(ws, b.bn1, rows, B * hi * wi)
         gx, identity = self._gx(ws, bi)
         prev = self.blocks[bi - 1] if bi > 0 else None
         join_rows = None
-        if (self.join_fuse and self.det and identity and prev is not None and prev.downsample is None and cin % 128 == 0
+        if (self.join_fuse and identity and prev is not None and prev.downsample is None and cin % 128 == 0
                 and self.dtype == torch.bfloat16):
             # dOut of the block below is complete with this launch (identity path already in gx): its join backward -- ReLU
             # mask from the forward's sign bits, bn3 sums -- runs in the epilogue instead of a pass of its own over gx
@@ -634,7 +604,7 @@ class _Engine(FusedEngine):
             rows = ops.conv_gemm(dz2[..., c_], self.w_bwd(aa.conv), dz1, N=p_, kh=3, kw=3, pad=1, tstride=s_,
                                  **self._pro_bnbwd(ws, t["y2"], S2, c_), **self._mask(ws, t["y1"], S1))
             rows2 = ops.conv_gemm(dQ, self.w_bwd(aa.in_proj_qkv), dz1, N=p_, tstride=s_, accumulate=True,
-                                  **self._mask(ws, t["y1"], S1, after=(rows or 0) if self.det else 0))
+                                  **self._mask(ws, t["y1"], S1, after=rows or 0))
             ops.conv_wgrad(dz2[..., c_], t["y1"], G(aa.conv.weight), kh=3, kw=3, stride=s_, pad=1, **self._g_bnbwd(ws, t["y2"], S2, c_),
                            **self._x_bnrelu(ws, S1))
             ops.conv_wgrad(dQ, t["y1"], G(aa.in_proj_qkv.weight), stride=s_, **self._x_bnrelu(ws, S1))
@@ -664,7 +634,7 @@ class _Engine(FusedEngine):
         rows = ops.conv_gemm(g, self.w_bwd(b.conv2), dz1, N=p_, kh=3, kw=3, pad=1, **self._pro_bnbwd(ws, t["y2"], S2),
                              **self._mask(ws, t["y1"], S1))
         ops.conv_wgrad(g, t["y1"], G(b.conv2.weight), kh=3, kw=3, stride=1, pad=1, **self._g_bnbwd(ws, t["y2"], S2), **self._x_bnrelu(ws, S1))
-        self._bn_bwd(ws, b.bn1, self._sc(ws, S1, rows), B * ho * wo)
+        self._bn_bwd(ws, b.bn1, rows, B * ho * wo)
         gx, identity = self._gx(ws, bi)
         if isinstance(b.conv1, AAConv2d):
             aa = b.conv1
@@ -689,7 +659,7 @@ class _Engine(FusedEngine):
         s1, s2, n_rows = self._ew(ws, S0)
         rows = ops.bnrelu_maxpool_bwd(ws.c0, v(ws, S0.sc), v(ws, S0.sh), v(ws, S0.mean), v(ws, S0.rstd), ws.amax, gx, gx, v(ws, self.ones, 64),
                                       v(ws, self.zeros, 64), v(ws, self.zeros, 64), dz0, s1, s2, stat_rows=n_rows)
-        self._bn_bwd(ws, m.bn1, self._sc(ws, S0, rows), ws.B * (ws.H // 2) * (ws.W // 2))
+        self._bn_bwd(ws, m.bn1, rows, ws.B * (ws.H // 2) * (ws.W // 2))
         ops.conv_wgrad(dz0, ws.x4, G(m.conv1.weight), mode=ops.MODE_STEM, **self._g_bnbwd(ws, ws.c0, S0))
         if dx is not None:
             ops.stem_input_grad(dz0, ws.c0, v(ws, S0.pa), v(ws, S0.pb), v(ws, S0.pc), m.conv1.weight, dx, stride=2, pad=3)
@@ -700,7 +670,7 @@ class _Engine(FusedEngine):
         c0 = m.conv1.out_channels
         s1, s2, n_rows = self._ew(ws, S0)
         rows = ops.relu_bwd_stats(gx, ws.pool0, ws.c0, v(ws, S0.mean), v(ws, S0.rstd), None, None, None, dz0, s1, s2, None, stat_rows=n_rows)
-        self._bn_bwd(ws, m.bn1, self._sc(ws, S0, rows), ws.B * ws.H * ws.W)
+        self._bn_bwd(ws, m.bn1, rows, ws.B * ws.H * ws.W)
         dw8 = torch.zeros(c0, 8, 3, 3, dtype=torch.float32, device=self.device)       # 3 input channels padded to 8
         ops.conv_wgrad(dz0, ws.x8, dw8, kh=3, kw=3, stride=1, pad=1, **self._g_bnbwd(ws, ws.c0, S0))
         G(m.conv1.weight).view(c0, 3, 3, 3).add_(dw8[:, :3])

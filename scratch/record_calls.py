@@ -7,11 +7,14 @@ The wrappers of ops named in REAL run for real (on the recorders' `lib`): what t
 engine calls `lib.cx_*` itself and a tree that goes through those wrappers leave the same list.  The library stand-in knows the
 names of `_lib.SIGNATURES` and no other, as the library does.
 
-    python scratch/record_calls.py [TREE] [--dump DIR]
+    python scratch/record_calls.py [TREE] [--dump DIR] [--rank-offsets]
     python scratch/record_calls.py [TREE] --time
 
 TREE: the checkout to import chexpert_amd from (default: this one), so the script can be pointed at a checkout of another commit.
 Prints one line per configuration: name, number of calls, sha256 of the list.  --dump writes each list to DIR/<name>.txt (diff them).
+--rank-offsets logs a tensor's storage offset as its rank among the distinct offsets seen for that storage in that list, so a monotone
+re-packing of a vector (slots dropped, the others in their order) leaves the list as it is; the offsets of `zero_` calls do not
+count (a fill of a range of slots is what such a re-packing shortens or removes): they are ranked by the offsets below them.
 --time runs no configuration: it prints the median host time of one DenseNet121 step (forward + backward under the recorders, 20
 steps after 3) -- what the engine's Python costs per step, to compare two trees.
 
@@ -19,6 +22,7 @@ What a call logs: the function's name and its arguments; a tensor as (index of i
 shape, strides, dtype), anything else by repr.  Calls made directly on tensors are logged too when they write: `zero_`, `fill_`,
 `copy_`, `add_` and `torch.add(..., out=)` (a TorchFunctionMode), and so are the reducer's `begin` / `ready(offset)` / `finish`.
 Every recorder returns ROWS where the real function returns a statistic-row count."""
+import bisect
 import hashlib
 import inspect
 import os
@@ -28,7 +32,7 @@ import torch
 from torch.overrides import TorchFunctionMode
 
 ROWS = 7
-SWITCHES = ("CHEXPERT_DET", "CHEXPERT_JOIN_FUSE", "CHEXPERT_FWD_JOIN_FUSE", "CHEXPERT_STREAM_LO", "CHEXPERT_PAIR_BWD")
+SWITCHES = ("CHEXPERT_JOIN_FUSE", "CHEXPERT_FWD_JOIN_FUSE", "CHEXPERT_STREAM_LO", "CHEXPERT_PAIR_BWD")
 # functions of ops that run for real: the helpers every wrapper uses, and the wrappers of the entry points the engines once called raw
 REAL = {"_nhwc", "_fn", "_dense", "_f32", "_out_hw", "dwconv_fwd", "dwconv_dgrad", "dwconv_wgrad", "gap_se_fwd", "scale_act_bc", "gap_affine_act",
         "se_bwd_fused", "se_act_bwd", "bn_lin_bwd_stats", "affine2_out", "scale_rows", "dropout_mask_dev", "counter_add", "mul_f32",
@@ -57,8 +61,22 @@ class Trace:
     def log(self, name, args, kwargs):
         self.calls.append((name, self.describe(args), self.describe(kwargs)))
 
+    def ranked(self):
+        """The calls with every tensor's storage offset replaced by its rank (--rank-offsets)."""
+        def walk(a, f):
+            if isinstance(a, tuple):
+                return f(a) if len(a) == 6 and a[0] == "T" else tuple(walk(x, f) for x in a)
+            return a
+        seen = {}
+        walk(tuple(c for c in self.calls if c[0] != "torch.zero_"), lambda t: seen.setdefault(t[1], set()).add(t[2]))
+        order = {sid: sorted(offs) for sid, offs in seen.items()}
+        return walk(tuple(self.calls), lambda t: t[:2] + (bisect.bisect_left(order.get(t[1], ()), t[2]),) + t[3:])
+
+    def lines(self):
+        return [repr(c) for c in (self.ranked() if RANK else self.calls)]
+
     def digest(self):
-        return hashlib.sha256("\n".join(repr(c) for c in self.calls).encode()).hexdigest()[:16]
+        return hashlib.sha256("\n".join(self.lines()).encode()).hexdigest()[:16]
 
 
 TRACE = Trace()
@@ -128,7 +146,8 @@ def patch(pkg):
         gradcam.L = type("L", (), {k: staticmethod(f) for k, f in stand_ins.items()})
 
 
-def run(name, make, x, *, train=True, dx=False, reducer=False, fp32=False, env=None, steps=2, eval_first=False, hooked=False, cam=False):
+def run(name, make, x, *, train=True, dx=False, reducer=False, fp32=False, env=None, steps=2, eval_first=False, hooked=False, cam=False,
+        pool=None):
     global TRACE
     for k in SWITCHES:
         os.environ.pop(k, None)
@@ -136,6 +155,8 @@ def run(name, make, x, *, train=True, dx=False, reducer=False, fp32=False, env=N
     TRACE = Trace()
     torch.manual_seed(0)
     model = make()
+    if pool:
+        model.set_pool(pool)
     if fp32:
         model.storage_dtype(torch.float32)
     model.train(train)
@@ -162,7 +183,7 @@ def run(name, make, x, *, train=True, dx=False, reducer=False, fp32=False, env=N
     print("%-28s %5d calls  %s" % (name, len(TRACE.calls), TRACE.digest()), flush=True)
     if DUMP:
         with open(os.path.join(DUMP, name + ".txt"), "w") as f:
-            f.writelines(repr(c) + "\n" for c in TRACE.calls)
+            f.writelines(line + "\n" for line in TRACE.lines())
 
 
 def main():
@@ -175,73 +196,55 @@ def main():
     basic = lambda **kw: (lambda: ResNet(BasicBlock, [2, 2, 1, 1], num_classes=5, **kw))
     wrn = lambda d=10, k=2, **kw: (lambda: WideResNet(BasicBlock, d, k, num_classes=5, **kw))
     eff = lambda: construct_model("efficientnet-b0", 5)
-    atomic = {"CHEXPERT_DET": "0"}
     run("bottleneck_det", bott(), x64)
-    run("bottleneck_atomic", bott(), x64, env=atomic)
     for sw in ("CHEXPERT_JOIN_FUSE", "CHEXPERT_FWD_JOIN_FUSE", "CHEXPERT_STREAM_LO"):
         run("bottleneck_%s0_det" % sw[9:].lower(), bott(), x64, env={sw: "0"})
-        run("bottleneck_%s0_atomic" % sw[9:].lower(), bott(), x64, env={sw: "0", **atomic})
     run("bottleneck_fp32_det", bott(), x64, fp32=True)
-    run("bottleneck_fp32_atomic", bott(), x64, fp32=True, env=atomic)
     run("bottleneck_frozen_det", bott(), x64, train=False)
-    run("bottleneck_frozen_atomic", bott(), x64, train=False, env=atomic)
     run("bottleneck_dx_det", bott(), x64, dx=True)
-    run("bottleneck_dx_frozen_atomic", bott(), x64, dx=True, train=False, env=atomic)
     run("bottleneck_u8_det", bott(), u8)
     run("bottleneck_reducer_det", bott(), x64, reducer=True)
-    run("bottleneck_reducer_atomic", bott(), x64, reducer=True, env=atomic)
+    run("bottleneck_lse_det", bott(), x64, pool="lse")
     for tag, kw in (("grouped", dict(groups=4, width_per_group=16)), ("dilated", dict(replace_stride_with_dilation=[False, True, True])),
                     ("wide128", dict(width_per_group=128)), ("aa", dict(attn_params=ap(64)))):
         run("bottleneck_%s_det" % tag, bott(**kw), x64)
-        run("bottleneck_%s_atomic" % tag, bott(**kw), x64, env=atomic)
     run("bottleneck_aa_fp32_det", bott(attn_params=ap(64)), x64, fp32=True)
     run("bottleneck_aa_frozen_det", bott(attn_params=ap(64)), x64, train=False)
     for tag, mk, x in (("basic", basic(), x64), ("basic_aa", basic(attn_params=ap(64)), x64), ("wrn", wrn(), x32),
                        ("wrn16_4_aa", wrn(16, 4, attn_params=ap(32)), x32)):
         run(tag + "_det", mk, x)
-        run(tag + "_atomic", mk, x, env=atomic)
         run(tag + "_dx_det", mk, x, dx=True)
-        run(tag + "_frozen_atomic", mk, x, train=False, env=atomic)
         run(tag + "_reducer_det", mk, x, reducer=True)
     run("basic_fp32_det", basic(), x64, fp32=True)
-    for tag, kw in (("det", {}), ("atomic", dict(env=atomic))):
-        run("efficientnet_b0_" + tag, eff, x64, **kw)
-        run("efficientnet_b0_frozen_" + tag, eff, x64, train=False, **kw)
-        run("efficientnet_b0_dx_reducer_" + tag, eff, x64, dx=True, reducer=True, **kw)
+    run("efficientnet_b0_det", eff, x64)
+    run("efficientnet_b0_frozen_det", eff, x64, train=False)
+    run("efficientnet_b0_dx_reducer_det", eff, x64, dx=True, reducer=True)
     run("efficientnet_b0_fp32_det", eff, x64, fp32=True)
     run("efficientnet_b0_u8_det", eff, u8)
-    run("efficientnet_b0_fp32_atomic", eff, x64, fp32=True, env=atomic)
     run("efficientnet_b0_fp32_after_eval_det", eff, x64, fp32=True, eval_first=True)
     run("efficientnet_b0_dx_det", eff, x64, dx=True)
-    run("efficientnet_b0_dx_atomic", eff, x64, dx=True, env=atomic)
-    for tag, kw in (("det", {}), ("atomic", dict(env=atomic))):
-        run("efficientnet_b1_" + tag, lambda: construct_model("efficientnet-b1", 5), x64, **kw)
+    run("efficientnet_b0_gem_det", eff, x64, pool="gem")
+    run("efficientnet_b1_det", lambda: construct_model("efficientnet-b1", 5), x64)
     bc = lambda: DenseNet(12, (2, 2, 2), 24, num_classes=5)          # growth 12: the channel-padded twin with the CIFAR stem
     run("densenet_bc_padded_det", bc, x32)
     run("densenet_bc_padded_fp32_det", bc, x32, fp32=True)
     dense = lambda cfg=(2, 2, 2, 2), **kw: (lambda: DenseNet(32, cfg, 64, num_classes=5, **kw))
     run("densenet_det", dense(), x64)
-    run("densenet_atomic", dense(), x64, env=atomic)
     run("densenet_fp32_det", dense(), x64, fp32=True)
-    run("densenet_fp32_atomic", dense(), x64, fp32=True, env=atomic)
     run("densenet_frozen_det", dense(), x64, train=False)
-    run("densenet_frozen_atomic", dense(), x64, train=False, env=atomic)
     run("densenet_dx_det", dense(), x64, dx=True)
-    run("densenet_dx_frozen_atomic", dense(), x64, dx=True, train=False, env=atomic)
     run("densenet_u8_det", dense(), u8)
     run("densenet_reducer_det", dense(), x64, reducer=True)
-    run("densenet_reducer_atomic", dense(), x64, reducer=True, env=atomic)
     run("densenet_after_eval_det", dense(), x64, eval_first=True)
+    run("densenet_max_det", dense(), x64, pool="max")
     run("densenet_drop_det", dense(drop_rate=0.25), x64)
     run("densenet_drop_frozen_det", dense(drop_rate=0.25), x64, train=False)
     run("densenet121_det", dense((6, 12, 24, 16)), x64)
     run("densenet121_pair_all_det", dense((6, 12, 24, 16)), x64, env={"CHEXPERT_PAIR_BWD": "all"})
-    run("densenet121_pair_all_atomic", dense((6, 12, 24, 16)), x64, env={"CHEXPERT_PAIR_BWD": "all", **atomic})
     run("densenet4352_pair_all_det", dense((4, 3, 5, 2)), x64, env={"CHEXPERT_PAIR_BWD": "all"})      # odd layer counts
     run("densenet4352_pair_1_det", dense((4, 3, 5, 2)), x64, env={"CHEXPERT_PAIR_BWD": "1"})
     apv = lambda S, v: dict(ap(S), v=v)        # (a share of attention channels that leaves these narrow transitions some)
     run("densenet_aa_det", dense(attn_params=apv(64, .25)), x64)
-    run("densenet_aa_atomic", dense(attn_params=apv(64, .25)), x64, env=atomic)
     run("densenet_aa_fp32_det", dense(attn_params=apv(64, .25)), x64, fp32=True)
     run("densenet_aa_frozen_det", dense(attn_params=apv(64, .25)), x64, train=False)
     run("densenet_aa_dx_det", dense(attn_params=apv(64, .25)), x64, dx=True)
@@ -284,6 +287,9 @@ def time_steps(steps=20, warmup=3):
 if __name__ == "__main__":
     argv = sys.argv[1:]
     DUMP = None
+    RANK = "--rank-offsets" in argv
+    if RANK:
+        argv.remove("--rank-offsets")
     TIME = "--time" in argv
     if TIME:
         argv.remove("--time")

@@ -116,21 +116,40 @@ def test_state_dict_surface_matches_reference_keys():
         m.features.conv0(torch.zeros(1, 3, 64, 64))                # sub-modules only hold parameters
 
 
-def test_engine_vector_plan_and_block_geometry():
-    from chexpert_amd.models import DenseNet
-    eng = DenseNet(32, (6, 12, 24, 16), 64, num_classes=5)._eng()
-    assert eng.blocks == [(64, 6), (128, 12), (256, 24), (512, 16)] and eng.c_final == 1024
-    z0, zn = eng.fwd_zero
-    b0, bn = eng.bwd_zero
-    assert z0 == 0 and zn <= b0 and b0 + bn <= eng.vec_size
-    # the layout: every later refactor of the engine is checked by the equality of its call lists, which rests on these offsets
-    slots = list(eng.vector_slots())
-    spans = sorted(s for s in slots if s[1] > 0)
-    assert (len(slots), len(spans)) == (1099, 1098)
-    assert eng.vec_size == 1719424 and eng.fwd_zero == (0, 327808) and eng.bwd_zero == (432064, 1257600)
-    # slots never overlap
+def _no_overlap(spans, vec_size):
+    spans = sorted(s for s in spans if s[1] > 0)
     for (a, n), (b, _) in zip(spans, spans[1:]):
         assert a + n <= b
+    assert spans[0][0] >= 0 and spans[-1][0] + spans[-1][1] <= vec_size
+
+
+def test_engine_vector_plan_and_block_geometry():
+    from chexpert_amd.models import Bottleneck, DenseNet, ResNet
+    from chexpert_amd.models.efficientnet import construct_model
+    eng = DenseNet(32, (6, 12, 24, 16), 64, num_classes=5)._eng()
+    assert eng.blocks == [(64, 6), (128, 12), (256, 24), (512, 16)] and eng.c_final == 1024
+    b0, bn = eng.bwd_zero
+    assert 0 <= b0 and b0 + bn <= eng.vec_size
+    assert not hasattr(eng, "fwd_zero")                # nothing is zeroed per forward: the statistics are rows of the workspace's slab
+    # the layout: every later refactor of the engine is checked by the equality of its call lists, which rests on these offsets
+    slots = list(eng.vector_slots())
+    assert (len(slots), len([s for s in slots if s[1] > 0])) == (731, 730)
+    assert eng.vec_size == 139648 and eng.bwd_zero == (104256, 5632)
+    # the zeroed region is the blocks' accumulators A / Bc and nothing else
+    assert bn == 2 * sum(c + n * 32 for c, n in eng.blocks)
+    assert (b0, b0 + bn) == (eng.plan.blocks[0].A[0], eng.plan.blocks[-1].Bc[0] + eng.plan.blocks[-1].Bc[1])
+    # slots never overlap
+    _no_overlap(slots, eng.vec_size)
+    # ResNet and EfficientNet: seven coefficient slots per BatchNorm and the engine's own behind them, no zeroed region at all
+    bn_slots = lambda e: [s for S in e.bn.values() for s in (S.sc, S.sh, S.mean, S.rstd, S.pa, S.pb, S.pc)]
+    res = ResNet(Bottleneck, [3, 4, 6, 3], num_classes=5)._eng()
+    assert len(res.bn) == 53 and res.vec_size == 239424
+    _no_overlap(bn_slots(res) + [s for j in res.join for s in j] + [res.ones, res.zeros] + res.scratch, res.vec_size)
+    eff = construct_model("efficientnet-b0", 5)._eng()
+    assert len(eff.bn) == 49 and eff.vec_size == 148336
+    _no_overlap(bn_slots(eff) + [eff.ones], eff.vec_size)
+    for e in (res, eff):
+        assert not hasattr(e, "fwd_zero") and not hasattr(e, "bwd_zero")
 
 
 _DP_WORKER = r"""

@@ -131,13 +131,12 @@ def test_smooth_regime_matches_fp32_oracle_tightly(dev, cfg, B, S):
     assert c > 0.995 and abs(n - 1) < 0.03
 
 
-@pytest.mark.parametrize("cfg,B,S,det", [((4, 3, 5, 2), 4, 64, "1"), ((6, 12, 24, 16), 2, 160, "1"), ((2, 2, 3, 2), 4, 64, "0")])
-def test_two_layers_per_pass_backward_equals_layer_by_layer(dev, monkeypatch, cfg, B, S, det):
+@pytest.mark.parametrize("cfg,B,S", [((4, 3, 5, 2), 4, 64), ((6, 12, 24, 16), 2, 160)])
+def test_two_layers_per_pass_backward_equals_layer_by_layer(dev, monkeypatch, cfg, B, S):
     """The pair schedule of the dense blocks' backward (cx_conv1x1_dgrad_wgrad_pair_ws wherever two layers remain, odd layer
     counts leave layer 0 to the single-layer kernel) against the layer-by-layer schedule on the same step: the same terms in
     every sum, another fp32 order in the channel statistics -- and reproducible bit for bit with the statistic rows."""
     from chexpert_amd.models import DenseNet
-    monkeypatch.setenv("CHEXPERT_DET", det)
     x, t = synth.xray_batch(900, B, S).to(dev), synth.targets(901, B, 5).to(dev)
     res = {}
     for mode in ("0", "all"):
@@ -152,15 +151,8 @@ def test_two_layers_per_pass_backward_equals_layer_by_layer(dev, monkeypatch, cf
             runs.append((loss.clone(), {k: p.grad.detach().clone() for k, p in model.named_parameters()}))
             model.load_state_dict(sd)
         assert model._eng().pair_bwd == mode
-        if det == "1":
-            assert all(torch.equal(runs[0][1][k], runs[1][1][k]) for k in runs[0][1]), "mode %s: not reproducible" % mode
+        assert all(torch.equal(runs[0][1][k], runs[1][1][k]) for k in runs[0][1]), "mode %s: not reproducible" % mode
         res[mode] = runs[0]
-    if det == "0":        # atomic statistic sums: the forward passes of the two models already differ in fp32 order
-        assert abs(float(res["0"][0]) - float(res["all"][0])) < 1e-2 * abs(float(res["0"][0]))
-        for k, g in res["0"][1].items():
-            if g.dim() > 1:
-                assert _cos(res["all"][1][k], g)[0] > 0.99, (k, _cos(res["all"][1][k], g))
-        return
     assert torch.equal(res["0"][0], res["all"][0])
     # the first pair differs by the fp32 order of the statistic sums alone; from the first bf16 rounding those 1e-6 differences reach
     # (the corrected slice the next 3x3 input gradient reads) on, rounding amplifies them as it amplifies any perturbation
