@@ -12,6 +12,12 @@ LIB_PATH = os.path.join(_HERE, "libchexpert_hip.so")
 PRO_NONE, PRO_AFFINE_RELU, PRO_AFFINE2, PRO_JOIN = 0, 1, 2, 3
 MODE_CONV, MODE_POOL2, MODE_STEM = 0, 1, 2
 EPI_STORE, EPI_MASK, EPI_JOIN = 0, 1, 2
+# the evaluation statistics (bootstrap.hip, calib.hip, delong.hip): the header's CX_BOOT_*, CX_CALIB_* and CX_DELONG_* values
+BOOT_TILE, BOOT_MAX_TILES, BOOT_MAX_UNITS = 8192, 8, 1 << 24
+BOOT_MAX_POINTS, BOOT_SENS, BOOT_SPEC = 8, 0, 1
+CALIB_METHODS = {"temperature": 0, "platt": 1}                     # CX_CALIB_TEMPERATURE, CX_CALIB_PLATT
+CALIB_MAX_ITER, CALIB_MAX_BINS = 1000, 64
+DELONG_MAX_ROWS, DELONG_WG_ENTRIES, DELONG_TILE = 128, 16384, 32   # 4 rows per class and model: two models of 16 classes
 
 _vp, _fp, _i32 = C.c_void_p, C.c_void_p, C.c_int32
 

@@ -33,12 +33,13 @@ GPU only.
 """
 import numpy as np
 
-from .metrics import (BOOT_MAX_UNITS, BOOT_TABLE_BYTES, _as_scores, _check_boot, _summarise_metric, _units_of,
-                      bootstrap_counts_reference)
+from ._lib import CALIB_MAX_BINS as MAX_BINS
+from ._lib import CALIB_MAX_ITER as MAX_ITER
+from ._lib import CALIB_METHODS
+from .resample import _check_boot, _check_inputs, _check_scores, _pack_lists, _replicates, _summarise_metric
 
-METHODS = ("temperature", "platt")
+METHODS = tuple(CALIB_METHODS)            # ("temperature", "platt")
 BINNINGS = ("width", "mass")
-MAX_BINS, MAX_ITER = 64, 1000
 _HALVINGS, _RIDGE, _FLAT, _SLACK = 40, 1e-12, 1e-8, 1e-12
 _FIT_COLUMNS = ("a", "b", "nll_before", "nll_after", "gmax", "lambda_min", "iterations", "status")
 
@@ -52,13 +53,10 @@ def _check_fit(method, g_tol, max_iter):
         raise ValueError("calibration: g_tol must be >= 0 (got %r)" % (g_tol,))
 
 
-def _inputs(outputs, targets):
-    s, t = _as_scores(outputs), np.asarray(_as_scores(targets), dtype=np.float64)
-    if s.ndim != 2 or s.shape != t.shape:
-        raise ValueError("calibration: outputs %s and targets %s must be (N, C) arrays of one shape" % (s.shape, t.shape))
-    if np.isnan(s).any():
-        raise ValueError("calibration: the scores hold NaN")
-    return np.asarray(s, dtype=np.float32), t
+def _inputs(outputs, targets, *groups):
+    """The checked inputs with the logits in float32: (s, t), or (s, t, units, U) when the rows' groups (or None) are given."""
+    s, *rest = _check_inputs(outputs, targets, *groups, "calibration") if groups else _check_scores(outputs, targets, "calibration")
+    return (np.asarray(s, dtype=np.float32), *rest)
 
 
 def _fit_terms(z, t, a, b, full=True):
@@ -217,12 +215,9 @@ def calibration_plan(outputs, targets, groups=None, cal=None, bins=15, binning="
     unit index in bits 0-23, its bin in bits 24-29 and its label (target > 0.5) in bit 31; `conf` holds P in parallel.
     Returns {"order": int32, "conf": uint32, "offs": int64 (C), "lens": int32 (C), "units", "n_units", "bins", "binning"}."""
     M = _check_bins(bins, binning)
-    s, t = _inputs(outputs, targets)
-    units, U = _units_of(s.shape[0], groups)
-    if not 1 <= U <= BOOT_MAX_UNITS:
-        raise ValueError("calibration: %d resampling units (1 .. 2^24 are supported)" % U)
+    s, t, units, U = _inputs(outputs, targets, groups)
     a, b = _map_of(cal, s.shape[1])
-    parts, confs, offs, lens, at = [], [], [], [], 0
+    parts, confs = [], []
     for c in range(s.shape[1]):
         keep = np.nonzero(t[:, c] >= 0)[0]
         P = fixed_point(_sigmoid64(a[c] * s[keep, c].astype(np.float64) + b[c]))
@@ -230,13 +225,9 @@ def calibration_plan(outputs, targets, groups=None, cal=None, bins=15, binning="
         entry = units[keep] | (_bins_of(P, M, binning) << 24) | ((t[keep, c] > 0.5).astype(np.int64) << 31)
         parts.append(entry[by].astype(np.uint32).view(np.int32))
         confs.append(P[by].astype(np.uint32))
-        offs.append(at)
-        lens.append(len(keep))
-        at += len(keep)
-    order = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
-    conf = np.concatenate(confs) if confs else np.zeros(0, dtype=np.uint32)
-    return {"order": order.astype(np.int32), "conf": conf.astype(np.uint32), "offs": np.asarray(offs, dtype=np.int64),
-            "lens": np.asarray(lens, dtype=np.int32), "units": units, "n_units": U, "bins": M, "binning": binning}
+    order, offs, lens = _pack_lists(parts)
+    return {"order": order, "conf": _pack_lists(confs, np.uint32)[0], "offs": offs, "lens": lens, "units": units, "n_units": U, "bins": M,
+            "binning": binning}
 
 
 def calibration_sums_reference(counts, plan, n_units=None):
@@ -267,8 +258,7 @@ def _calibration_definition(outputs, targets, counts, groups=None, cal=None, bin
     """(wsum, wpos, csum, bnum) straight from the definition, in Python integers (object arrays): no prepared plan, no sorted order, a
     loop over the rows."""
     M = _check_bins(bins, binning)
-    s, t = _inputs(outputs, targets)
-    units, U = _units_of(s.shape[0], groups)
+    s, t, units, U = _inputs(outputs, targets, groups)
     a, b = _map_of(cal, s.shape[1])
     counts = np.asarray(counts).astype(np.int64)
     R, C = counts.shape[0], s.shape[1]
@@ -331,26 +321,42 @@ def _reliability(wsum, wpos, csum, bins, binning):
 
 
 _VALUES = ("ece", "mce", "brier")
+_SUMS = ("wsum", "wpos", "csum", "bnum")
 
 
-def _result(point_sums, rep_values, plan, n_boot, seed, alpha, return_replicates):
-    point = _calibration_values(*point_sums)
-    out = {}
-    for name in _VALUES:
-        if int(n_boot) == 0:
-            out[name] = {"point": {c: float(v) for c, v in enumerate(point[name][0])}}
-        else:
-            out[name] = _summarise_metric(point[name][0], np.concatenate([r[name] for r in rep_values]), n_boot, seed, alpha,
-                                          plan["n_units"], return_replicates)
-    out["reliability"] = _reliability(*point_sums[:3], plan["bins"], plan["binning"])
-    if return_replicates and int(n_boot) > 0:
-        out["replicate_weights"] = np.concatenate([r["weight"] for r in rep_values])      # W of every (replicate, class)
-    return out
-
-
-def _check_metrics(n_boot, alpha):
+def _calibration_metrics(outputs, targets, cal, bins, binning, n_boot, seed, groups, alpha, return_replicates, device=None, chunk=None,
+                         host=False):
+    """The body of calibration_metrics and of its numpy statement: the integer sums of the point sample and of every replicate through
+    the replicate driver -- from cx_boot_calib on `device`, or, host=True, from calibration_sums_reference -- then the one forming of
+    the floats."""
     if int(n_boot) != 0:
         _check_boot(n_boot, alpha)
+    plan = calibration_plan(outputs, targets, groups, cal, bins, binning)
+    U = plan["n_units"]
+    if host:
+        def sums(counts):
+            return calibration_sums_reference(counts, plan)
+    else:
+        import torch
+
+        from . import ops
+        order = torch.from_numpy(plan["order"]).to(device)
+        conf = torch.from_numpy(plan["conf"].view(np.int32)).to(device)
+
+        def sums(counts):
+            return (v.cpu().numpy() for v in ops.boot_calib(counts, order, conf, plan["offs"], plan["lens"], U, plan["bins"]))
+    point, reps = _replicates(lambda counts: dict(zip(_SUMS, sums(counts))), U, n_boot, seed, device, chunk, host)
+    point = [point[name][None] for name in _SUMS]                 # as one-row tables again
+    values = _calibration_values(*point)
+    if reps is None:
+        out = {name: {"point": {c: float(v) for c, v in enumerate(values[name][0])}} for name in _VALUES}
+    else:
+        rep_values = _calibration_values(*(reps[name] for name in _SUMS))
+        out = {name: _summarise_metric(values[name][0], rep_values[name], n_boot, seed, alpha, U, return_replicates) for name in _VALUES}
+    out["reliability"] = _reliability(*point[:3], plan["bins"], plan["binning"])
+    if return_replicates and reps is not None:
+        out["replicate_weights"] = rep_values["weight"]             # W of every (replicate, class)
+    return out
 
 
 def calibration_metrics(outputs, targets, cal=None, bins=15, binning="width", n_boot=0, seed=0, groups=None, alpha=0.05, device="cuda",
@@ -363,42 +369,13 @@ def calibration_metrics(outputs, targets, cal=None, bins=15, binning="width", n_
     (seed, unit) they are the resamples of the AUROC intervals.  With `cal` given every interval is CONDITIONAL on the fitted
     parameters: the fit is not redrawn per replicate, so the intervals leave the fit's own sampling error out.
     return_replicates: also "replicates" per summary and "replicate_weights", the kept weight W of every (replicate, class)."""
-    import torch
-
-    from . import ops
-    _check_metrics(n_boot, alpha)
-    plan = calibration_plan(outputs, targets, groups, cal, bins, binning)
-    U, M = plan["n_units"], plan["bins"]
-    order = torch.from_numpy(plan["order"]).to(device)
-    conf = torch.from_numpy(plan["conf"].view(np.int32)).to(device)
-
-    def sums(counts):
-        return tuple(v.cpu().numpy() for v in ops.boot_calib(counts, order, conf, plan["offs"], plan["lens"], U, M))
-    point = sums(torch.ones(1, U, dtype=torch.int32, device=device))
-    reps = []
-    if int(n_boot) > 0:
-        if chunk is None:
-            chunk = max(1, BOOT_TABLE_BYTES // (4 * U))
-        chunk = max(1, min(int(chunk), int(n_boot)))
-        table = torch.empty(chunk, U, dtype=torch.int32, device=device)
-        for first in range(0, int(n_boot), chunk):
-            counts = ops.boot_counts(U, min(chunk, int(n_boot) - first), seed, first=first, out=table)
-            reps.append(_calibration_values(*sums(counts)))
-    return _result(point, reps, plan, n_boot, seed, alpha, return_replicates)
+    return _calibration_metrics(outputs, targets, cal, bins, binning, n_boot, seed, groups, alpha, return_replicates, device=device, chunk=chunk)
 
 
 def calibration_metrics_reference(outputs, targets, cal=None, bins=15, binning="width", n_boot=0, seed=0, groups=None, alpha=0.05,
                                   return_replicates=False):
     """The numpy statement of calibration_metrics (host; for the tests and as the timing yardstick)."""
-    _check_metrics(n_boot, alpha)
-    plan = calibration_plan(outputs, targets, groups, cal, bins, binning)
-    U = plan["n_units"]
-    point = calibration_sums_reference(np.ones((1, U), dtype=np.uint32), plan)
-    reps = []
-    for first in range(0, int(n_boot), 64):
-        counts = bootstrap_counts_reference(U, min(64, int(n_boot) - first), seed, first=first)
-        reps.append(_calibration_values(*calibration_sums_reference(counts, plan)))
-    return _result(point, reps, plan, n_boot, seed, alpha, return_replicates)
+    return _calibration_metrics(outputs, targets, cal, bins, binning, n_boot, seed, groups, alpha, return_replicates, host=True)
 
 
 def load_calibration(path):

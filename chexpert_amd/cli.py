@@ -348,10 +348,11 @@ def parse_args(argv=None):
     return args
 
 
-def auc_ci_name(tag):
-    """File name of the intervals that go with <tag>.json: eval_results_step_5 -> auc_ci_step_5.json.  It must not start with
-    `eval_results`: --plot_roc reads every file with that prefix as a compute_metrics dictionary."""
-    return "auc_ci_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ".json"
+def report_name(tag, stem, ext=".json"):
+    """File name of the report `stem` that goes with <tag>.json: eval_results_step_5, "auc_ci" -> auc_ci_step_5.json (stems: auc_ci,
+    delong, metrics_ci, calibration, and reliability with ext ".png" for the figure).  It must not start with `eval_results`:
+    --plot_roc reads every file with that prefix as a compute_metrics dictionary."""
+    return stem + "_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ext
 
 
 def bootstrap_groups(args, ds):
@@ -367,30 +368,35 @@ def bootstrap_groups(args, ds):
     return np.array(ids if unit == "study" else [v.rsplit("/", 1)[0] for v in ids])
 
 
+def _interval_options(args):
+    """(seed, alpha, device, unit) as the four reports below take them: --bootstrap_seed (default --seed), --bootstrap_alpha, the
+    device of --cuda and --bootstrap_unit."""
+    seed = getattr(args, "bootstrap_seed", None)
+    return (args.seed if seed is None else seed, getattr(args, "bootstrap_alpha", 0.05), "cuda:%d" % (args.cuda or 0),
+            getattr(args, "bootstrap_unit", "image"))
+
+
+def _print_auc_intervals(ci):
+    """One `AUC [lo, hi]` line per class and for the mean."""
+    for c, name in enumerate(class_names(len(ci["aucs"]))):
+        print("  %-18s %.4f [%.4f, %.4f]" % (name, ci["aucs"][c], ci["lo"][c], ci["hi"][c]))
+    print("  %-18s %.4f [%.4f, %.4f]" % ("mean", ci["mean_auc"]["point"], ci["mean_auc"]["lo"], ci["mean_auc"]["hi"]))
+
+
 def write_auc_ci(args, tag, outputs, targets, groups=None):
     """With --bootstrap B > 0: AUROC intervals of the evaluation that wrote <tag>.json, into auc_ci_<...>.json beside it, and one
     `AUC [lo, hi]` line per class and for the mean.  Returns the path, or None (B = 0: nothing computed, allocated or written)."""
     n_boot = getattr(args, "bootstrap", 0)
     if n_boot <= 0:
         return None
-    seed = getattr(args, "bootstrap_seed", None)
-    ci = M.bootstrap_auc(outputs, targets, n_boot=n_boot, seed=args.seed if seed is None else seed, groups=groups,
-                         alpha=getattr(args, "bootstrap_alpha", 0.05), device="cuda:%d" % (args.cuda or 0))
-    ci["unit"] = getattr(args, "bootstrap_unit", "image")
-    names = class_names(len(ci["aucs"]))
+    seed, alpha, device, unit = _interval_options(args)
+    ci = M.bootstrap_auc(outputs, targets, n_boot=n_boot, seed=seed, groups=groups, alpha=alpha, device=device)
+    ci["unit"] = unit
     print("AUC with %g %% bootstrap intervals (%d replicates over %d %s units):" % (100 * (1 - ci["alpha"]), n_boot, ci["n_units"], ci["unit"]))
-    for c, name in enumerate(names):
-        print("  %-18s %.4f [%.4f, %.4f]" % (name, ci["aucs"][c], ci["lo"][c], ci["hi"][c]))
-    print("  %-18s %.4f [%.4f, %.4f]" % ("mean", ci["mean_auc"]["point"], ci["mean_auc"]["lo"], ci["mean_auc"]["hi"]))
-    path = os.path.join(args.output_dir, auc_ci_name(tag))
+    _print_auc_intervals(ci)
+    path = os.path.join(args.output_dir, report_name(tag, "auc_ci"))
     json.dump(ci, open(path, "w"), indent=4)
     return path
-
-
-def delong_name(tag):
-    """File name of the analytic intervals that go with <tag>.json: eval_results_step_5 -> delong_step_5.json (the rule of auc_ci_name:
-    not the prefix `eval_results`)."""
-    return "delong_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ".json"
 
 
 def write_delong(args, tag, outputs, targets, groups=None, members=None):
@@ -400,29 +406,20 @@ def write_delong(args, tag, outputs, targets, groups=None, members=None):
     the mean-AUROC delta, z and p of each are printed.  Returns the path, or None (no --delong: nothing computed, allocated or written)."""
     if not getattr(args, "delong", False):
         return None
-    alpha, device = getattr(args, "bootstrap_alpha", 0.05), "cuda:%d" % (args.cuda or 0)
+    _, alpha, device, unit = _interval_options(args)
     ci = M.delong_auc(outputs, targets, groups=groups, alpha=alpha, device=device)
-    ci["unit"] = getattr(args, "bootstrap_unit", "image")
-    names = class_names(len(ci["aucs"]))
+    ci["unit"] = unit
     print("AUC with %g %% %s intervals (%d %s units):" % (100 * (1 - ci["alpha"]), ci["method"], ci["n_units"], ci["unit"]))
-    for c, name in enumerate(names):
-        print("  %-18s %.4f [%.4f, %.4f]" % (name, ci["aucs"][c], ci["lo"][c], ci["hi"][c]))
-    print("  %-18s %.4f [%.4f, %.4f]" % ("mean", ci["mean_auc"]["point"], ci["mean_auc"]["lo"], ci["mean_auc"]["hi"]))
+    _print_auc_intervals(ci)
     if members is not None:
         ci["vs_members"] = {}
         for name, out in members.items():
             d = M.delong_auc_diff(outputs, out, targets, groups=groups, alpha=alpha, device=device)
             ci["vs_members"][name] = d
             print("  ensemble - %-24s mean AUC delta %+.4f  z %.3f  p %.4g" % (name, d["mean_auc"]["delta"], d["mean_auc"]["z"], d["mean_auc"]["p"]))
-    path = os.path.join(args.output_dir, delong_name(tag))
+    path = os.path.join(args.output_dir, report_name(tag, "delong"))
     json.dump(ci, open(path, "w"), indent=4)
     return path
-
-
-def metrics_ci_name(tag):
-    """File name of the metric intervals that go with <tag>.json: eval_results_step_5 -> metrics_ci_step_5.json (the rule of auc_ci_name:
-    not the prefix `eval_results`)."""
-    return "metrics_ci_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ".json"
 
 
 def write_metrics_ci(args, tag, outputs, targets, groups=None):
@@ -431,21 +428,14 @@ def write_metrics_ci(args, tag, outputs, targets, groups=None):
     n_boot, names = getattr(args, "bootstrap", 0), getattr(args, "bootstrap_metrics", None)
     if n_boot <= 0 or not names:
         return None
-    seed = getattr(args, "bootstrap_seed", None)
-    ci = M.bootstrap_metrics(outputs, targets, metrics=names, n_boot=n_boot, seed=args.seed if seed is None else seed, groups=groups,
-                             alpha=getattr(args, "bootstrap_alpha", 0.05), device="cuda:%d" % (args.cuda or 0))
+    seed, alpha, device, unit = _interval_options(args)
+    ci = M.bootstrap_metrics(outputs, targets, metrics=names, n_boot=n_boot, seed=seed, groups=groups, alpha=alpha, device=device)
     for name, r in ci.items():
-        r["unit"] = getattr(args, "bootstrap_unit", "image")
+        r["unit"] = unit
         print("%s, mean over the classes: %.4f [%.4f, %.4f]" % (name, r["mean_auc"]["point"], r["mean_auc"]["lo"], r["mean_auc"]["hi"]))
-    path = os.path.join(args.output_dir, metrics_ci_name(tag))
+    path = os.path.join(args.output_dir, report_name(tag, "metrics_ci"))
     json.dump(ci, open(path, "w"), indent=4)
     return path
-
-
-def calibration_name(tag, stem="calibration", ext=".json"):
-    """File name of the calibration report that goes with <tag>.json: eval_results_step_5 -> calibration_step_5.json (the rule of
-    auc_ci_name: not the prefix `eval_results`); stem "reliability", ext ".png": the figure beside it."""
-    return stem + "_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ext
 
 
 def write_calibration(args, tag, outputs, targets, groups=None):
@@ -458,15 +448,15 @@ def write_calibration(args, tag, outputs, targets, groups=None):
         return None
     from . import calibration as K
     from . import vis
-    device, seed = "cuda:%d" % (args.cuda or 0), getattr(args, "bootstrap_seed", None)
+    seed, alpha, device, unit = _interval_options(args)
     kw = dict(bins=15 if bins is None else bins, binning=getattr(args, "calibration_binning", "width"), n_boot=getattr(args, "bootstrap", 0),
-              seed=args.seed if seed is None else seed, groups=groups, alpha=getattr(args, "bootstrap_alpha", 0.05), device=device)
+              seed=seed, groups=groups, alpha=alpha, device=device)
     fit = None
     if method is not None:
         fit = K.fit_calibration(outputs, targets, method=method, smooth=getattr(args, "calibrate_smooth", False), device=device)
     elif stored is not None:
         fit = K.load_calibration(stored)
-    report = {"fit": fit, "fitted_here": method is not None, "unit": getattr(args, "bootstrap_unit", "image")}
+    report = {"fit": fit, "fitted_here": method is not None, "unit": unit}
     before = K.calibration_metrics(outputs, targets, None, **kw)
     report.update({"ece_before": before["ece"], "mce_before": before["mce"], "brier_before": before["brier"],
                    "reliability_before": before["reliability"]})
@@ -478,10 +468,10 @@ def write_calibration(args, tag, outputs, targets, groups=None):
     for name in ("ece", "mce", "brier"):
         vals = [np.nanmean(list(r[name]["point"].values())) if r is not None and len(r[name]["point"]) else float("nan") for r in (before, after)]
         print("%s, mean over the classes: %.4f%s" % (name, vals[0], "" if after is None else " -> %.4f after the map" % vals[1]))
-    path = os.path.join(args.output_dir, calibration_name(tag))
+    path = os.path.join(args.output_dir, report_name(tag, "calibration"))
     json.dump(report, open(path, "w"), indent=4)
     vis.reliability_diagram(before["reliability"], class_names(len(before["ece"]["point"])),
-                            os.path.join(args.output_dir, calibration_name(tag, "reliability", ".png")),
+                            os.path.join(args.output_dir, report_name(tag, "reliability", ".png")),
                             after=None if after is None else after["reliability"])
     return path
 

@@ -17,14 +17,13 @@
 // Same bits every run: the only unordered operation is the integer add of the counts stage (LDS atomics, or device-memory atomics for
 // very large U), and integer adds commute -- the project's rule is about the order of FLOAT sums, of which this file has none.  Every
 // output element of the scan stage has exactly one writer.
-#include "common.h"
+#include "resample.h"
 
 namespace {
 
 constexpr int BOOT_TILE = CX_BOOT_TILE;            // units per workgroup of the LDS form: 32 KB of counters, 4 workgroups per CU
 constexpr int BOOT_MAX_TILES = CX_BOOT_MAX_TILES;  // more tiles than this per replicate: the device-memory form (a tile re-hashes all U draws)
 constexpr int BOOT_MAX_U = CX_BOOT_MAX_UNITS;
-constexpr int BOOT_CLASSES = 32;          // classes per launch of the scan stage (offsets and lengths travel as kernel arguments)
 
 __device__ __forceinline__ uint32_t boot_draw(const uint64_t seed, const uint64_t k, const uint32_t U) {
   uint64_t z = seed + 0x9E3779B97F4A7C15ull * (k + 1ull);
@@ -75,31 +74,14 @@ __global__ __launch_bounds__(256) void boot_counts_global_kernel(uint32_t* __res
 
 // ---- stage 2: one wave per (replicate, class), both orders side by side ---------------------------------------------------------------
 // A step is 64 entries of each order, one per lane, read coalesced; BOOT_STEPS steps' entries and the count-row gathers behind them
-// are requested before the first scan consumes any.  Per step and order: an inclusive wave scan of q in uint32 (DPP: four shifts inside
-// the rows of 16 lanes, then lane 15 of a row to the next row and lane 31 to the upper half), the exclusive prefix plus the running
-// carry times p added to the lane's uint64 sum, and the carry advanced by the step's total (lane 63, wave-uniform).  The two orders are
-// independent chains, which is what lets one wave own the output element: one writer, no LDS, no barrier.
-__device__ __forceinline__ uint32_t boot_wave_scan(uint32_t v) {
-#define BOOT_DPP(ctrl, rows) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rows, 0xf, false)
-  BOOT_DPP(0x111, 0xf);       // row_shr:1
-  BOOT_DPP(0x112, 0xf);       // row_shr:2
-  BOOT_DPP(0x114, 0xf);       // row_shr:4
-  BOOT_DPP(0x118, 0xf);       // row_shr:8
-  BOOT_DPP(0x142, 0xa);       // row_bcast:15 into rows 1 and 3
-  BOOT_DPP(0x143, 0xc);       // row_bcast:31 into rows 2 and 3
-#undef BOOT_DPP
-  return v;
-}
-
-struct BootPlan {
-  long long offs[BOOT_CLASSES];
-  int len[BOOT_CLASSES];
-};
-
+// are requested before the first scan consumes any.  Per step and order: an inclusive wave scan of q in uint32 (wave_scan_add of
+// resample.h), the exclusive prefix plus the running carry times p added to the lane's uint64 sum, and the carry advanced by the
+// step's total (lane 63, wave-uniform).  The two orders are independent chains, which is what lets one wave own the output element:
+// one writer, no LDS, no barrier.
 constexpr int BOOT_STEPS = 4;
 
 __global__ __launch_bounds__(256) void boot_auc_kernel(const uint32_t* __restrict__ counts, int ld, int n_rep,
-                                                       const int32_t* __restrict__ order, const BootPlan plan, int c0, int cn, int C,
+                                                       const int32_t* __restrict__ order, const ClassLists plan, int c0, int cn, int C,
                                                        uint64_t* __restrict__ num2, uint32_t* __restrict__ wpos,
                                                        uint32_t* __restrict__ wneg, int U) {
   const int lane = threadIdx.x & 63;
@@ -132,13 +114,14 @@ __global__ __launch_bounds__(256) void boot_auc_kernel(const uint32_t* __restric
       const uint32_t a = in ? wh[s] : 0u, b = in ? wl[s] : 0u;
       const uint32_t ph = eh[s] < 0 ? a : 0u, qh = eh[s] < 0 ? 0u : a;       // bit 31 = the label
       const uint32_t pl = el[s] < 0 ? b : 0u, ql = el[s] < 0 ? 0u : b;
-      const uint32_t ih = boot_wave_scan(qh), il = boot_wave_scan(ql);
+      const uint32_t ih = wave_scan_add(qh), il = wave_scan_add(ql);
       acc += (uint64_t)ph * (uint64_t)(carry_hi + ih - qh) + (uint64_t)pl * (uint64_t)(carry_lo + il - ql);
       carry_hi += (uint32_t)__builtin_amdgcn_readlane((int)ih, 63);
       carry_lo += (uint32_t)__builtin_amdgcn_readlane((int)il, 63);
       sp += ph;
     }
   }
+  // wave_sum_u64 of acc written out, interleaved with the sum of sp: as two loops the compiler schedules this kernel differently
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     acc += ((uint64_t)(uint32_t)__shfl_xor((int)(acc >> 32), d) << 32) | (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)acc, d);
@@ -173,25 +156,11 @@ constexpr int BOOT_POINTS = CX_BOOT_MAX_POINTS;
 constexpr uint64_t BOOT_PPM = 1000000ull;
 
 struct BootSweepPlan {
-  long long offs[BOOT_CLASSES];
-  int len[BOOT_CLASSES];
+  ClassLists lists;               // first: the argument layout of the kernel is that of the lists with the points behind them
   int n_pts;
   int spec[BOOT_POINTS];          // 0: sens@ (max tp under fp * 1e6 <= (1e6 - ppm) * W-), 1: spec@ (min fp under tp * 1e6 >= ppm * W+)
   int ppm[BOOT_POINTS];
 };
-
-__device__ __forceinline__ uint32_t boot_wave_xmax(uint32_t v) {      // exclusive max-scan over the wave, identity 0
-  v = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false);      // wave_shr:1 (lane 0 takes the identity)
-#define BOOT_DPP(ctrl, rows) v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rows, 0xf, false))
-  BOOT_DPP(0x111, 0xf);       // row_shr:1
-  BOOT_DPP(0x112, 0xf);       // row_shr:2
-  BOOT_DPP(0x114, 0xf);       // row_shr:4
-  BOOT_DPP(0x118, 0xf);       // row_shr:8
-  BOOT_DPP(0x142, 0xa);       // row_bcast:15 into rows 1 and 3
-  BOOT_DPP(0x143, 0xc);       // row_bcast:31 into rows 2 and 3
-#undef BOOT_DPP
-  return v;
-}
 
 // floor((tp << 32) / den) for 1 <= den, tp <= den: the dividend is exact in fp64 (32 significant bits) and the quotient is <= 2^32, so
 // the correctly rounded fp64 quotient is within 2^-21 of the true one and its integer part is the floor or one above it (one below is
@@ -213,8 +182,8 @@ __global__ __launch_bounds__(256) void boot_sweep_kernel(const uint32_t* __restr
   const long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= (long long)n_rep * cn) return;                     // the same for all lanes of a wave; no barrier follows
   const int rep = (int)(item / cn), cl = (int)(item - (long long)rep * cn);
-  const int n = plan.len[cl], P = plan.n_pts;
-  const int32_t* __restrict__ ent = order + plan.offs[cl];
+  const int n = plan.lists.len[cl], P = plan.n_pts;
+  const int32_t* __restrict__ ent = order + plan.lists.offs[cl];
   const uint32_t* __restrict__ row = counts + (size_t)rep * ld;
   // first pass (only with operating points): the totals the conditions compare against
   uint32_t Wp = 0, Wn = 0;
@@ -257,11 +226,11 @@ __global__ __launch_bounds__(256) void boot_sweep_kernel(const uint32_t* __restr
       const bool in = t0 + s * 64 + lane < n;
       const uint32_t a = in ? w[s] : 0u;
       const uint32_t p = e[s] < 0 ? a : 0u, q = e[s] < 0 ? 0u : a;                       // bit 31 = the label
-      const uint32_t ip = boot_wave_scan(p), iq = boot_wave_scan(q);
+      const uint32_t ip = wave_scan_add(p), iq = wave_scan_add(q);
       const uint32_t tp = carry_p + ip, fp = carry_q + iq;
       const bool mark = in && (e[s] & 0x40000000);                                       // bit 30 = the end of a tie group
       const uint32_t m = mark ? tp : 0u;
-      const uint32_t x = boot_wave_xmax(m);
+      const uint32_t x = wave_xscan_max(m);
       const uint32_t prev = max(carry_prev, x);
       if (mark && tp != prev) {                                  // a step of the precision-recall curve: the one place that divides
         const uint32_t den = tp + fp;
@@ -282,9 +251,7 @@ __global__ __launch_bounds__(256) void boot_sweep_kernel(const uint32_t* __restr
       carry_prev = max(carry_prev, (uint32_t)__builtin_amdgcn_readlane((int)max(x, m), 63));
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1)
-    acc += ((uint64_t)(uint32_t)__shfl_xor((int)(acc >> 32), d) << 32) | (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)acc, d);
+  acc = wave_sum_u64(acc);
 #pragma unroll
   for (int k = 0; k < BOOT_POINTS; ++k) {
     if (k < P) {
@@ -329,23 +296,16 @@ int cx_boot_counts(uint32_t* counts, int ld, int U, int first, int n_rep, uint64
 int cx_boot_auc(const uint32_t* counts, int ld, int n_rep, const int32_t* order, const int64_t* offs, const int32_t* len, int C,
                 uint64_t* num2, uint32_t* wpos, uint32_t* wneg, int U, void* stream) {
   if (!counts || !order || !offs || !len || !num2 || !wpos || !wneg || n_rep < 1 || C < 1) return CX_EINVAL;
-  if (U < 1 || U > BOOT_MAX_U || ld < U) return CX_ESHAPE;
-  for (int c = 0; c < C; ++c)
-    if (len[c] < 0 || offs[c] < 0) return CX_EINVAL;
+  if (const int rc = check_class_lists(U, ld, offs, len, C)) return rc;
   if ((((uintptr_t)counts) & 3) || (((uintptr_t)order) & 3) || (((uintptr_t)num2) & 7) || (((uintptr_t)wpos) & 3) || (((uintptr_t)wneg) & 3))
     return CX_EALIGN;
-  if (((long long)n_rep * BOOT_CLASSES + 3) / 4 > 0x7fffffffll) return CX_ESHAPE;
-  for (int c0 = 0; c0 < C; c0 += BOOT_CLASSES) {
-    const int cn = min(BOOT_CLASSES, C - c0);
-    BootPlan plan;
-    for (int c = 0; c < BOOT_CLASSES; ++c) plan.offs[c] = c < cn ? (long long)offs[c0 + c] : 0ll, plan.len[c] = c < cn ? len[c0 + c] : 0;
+  if (((long long)n_rep * CX_LIST_CLASSES + 3) / 4 > 0x7fffffffll) return CX_ESHAPE;
+  ClassLists plan;
+  return for_class_groups(offs, len, C, plan, [&](int c0, int cn) {
     const long long waves = (long long)n_rep * cn;
     hipLaunchKernelGGL(boot_auc_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, as_stream(stream), counts, ld, n_rep, order, plan,
                        c0, cn, C, num2, wpos, wneg, U);
-    const int rc = launch_status();
-    if (rc) return rc;
-  }
-  return 0;
+  });
 }
 
 int cx_boot_sweep(const uint32_t* counts, int ld, int n_rep, const int32_t* order, const int64_t* offs, const int32_t* len, int C,
@@ -354,26 +314,19 @@ int cx_boot_sweep(const uint32_t* counts, int ld, int n_rep, const int32_t* orde
   if (!counts || !order || !offs || !len || !apnum || !wpos || !wneg || n_rep < 1 || C < 1) return CX_EINVAL;
   if (P < 0 || P > BOOT_POINTS) return CX_ESHAPE;
   if (P > 0 && (!pt_type || !pt_ppm || !pts)) return CX_EINVAL;
-  if (U < 1 || U > BOOT_MAX_U || ld < U) return CX_ESHAPE;
-  for (int c = 0; c < C; ++c)
-    if (len[c] < 0 || offs[c] < 0) return CX_EINVAL;
+  if (const int rc = check_class_lists(U, ld, offs, len, C)) return rc;
   for (int k = 0; k < P; ++k)
     if ((pt_type[k] != CX_BOOT_SENS && pt_type[k] != CX_BOOT_SPEC) || pt_ppm[k] < 1 || pt_ppm[k] > 999999) return CX_EINVAL;
   if ((((uintptr_t)counts) & 3) || (((uintptr_t)order) & 3) || (((uintptr_t)apnum) & 7) || (((uintptr_t)wpos) & 3) || (((uintptr_t)wneg) & 3) ||
       (P > 0 && (((uintptr_t)pts) & 3)))
     return CX_EALIGN;
-  if (((long long)n_rep * BOOT_CLASSES + 3) / 4 > 0x7fffffffll) return CX_ESHAPE;
+  if (((long long)n_rep * CX_LIST_CLASSES + 3) / 4 > 0x7fffffffll) return CX_ESHAPE;
   BootSweepPlan plan;
   plan.n_pts = P;
   for (int k = 0; k < BOOT_POINTS; ++k) plan.spec[k] = k < P ? (pt_type[k] == CX_BOOT_SPEC) : 0, plan.ppm[k] = k < P ? pt_ppm[k] : 1;
-  for (int c0 = 0; c0 < C; c0 += BOOT_CLASSES) {
-    const int cn = min(BOOT_CLASSES, C - c0);
-    for (int c = 0; c < BOOT_CLASSES; ++c) plan.offs[c] = c < cn ? (long long)offs[c0 + c] : 0ll, plan.len[c] = c < cn ? len[c0 + c] : 0;
+  return for_class_groups(offs, len, C, plan.lists, [&](int c0, int cn) {
     const long long waves = (long long)n_rep * cn;
     hipLaunchKernelGGL(boot_sweep_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, as_stream(stream), counts, ld, n_rep, order,
                        plan, c0, cn, C, apnum, wpos, wneg, pts, U);
-    const int rc = launch_status();
-    if (rc) return rc;
-  }
-  return 0;
+  });
 }

@@ -34,7 +34,7 @@
 // same process, alternating): 5.40 ms against 5.36 ms at 20 000 rows x 14 classes x 2000 replicates (equal-mass bins: 5.39 ms), 41 us
 // against 44 us at 234 x 5 x 1000 (launch latency).  The numpy statement: 13 ms for the 1000 replicates of the small shape, 155 ms per
 // 128 replicates of the large one.
-#include "common.h"
+#include "resample.h"
 
 namespace {
 
@@ -179,18 +179,12 @@ __global__ __launch_bounds__(256) void calib_fit_kernel(const float* __restrict_
 }
 
 // ---- cx_boot_calib ----------------------------------------------------------------------------------------------------------------
-constexpr int CALIB_CLASSES = 32;         // classes per launch (offsets and lengths travel as kernel arguments)
 constexpr int CALIB_STEPS = 4;
 constexpr int CALIB_BINS = CX_CALIB_MAX_BINS;
 
-struct CalibPlan {
-  long long offs[CALIB_CLASSES];
-  int len[CALIB_CLASSES];
-};
-
 __global__ __launch_bounds__(256) void boot_calib_kernel(const uint32_t* __restrict__ counts, int ld, int n_rep,
                                                          const int32_t* __restrict__ order, const uint32_t* __restrict__ conf,
-                                                         const CalibPlan plan, int c0, int cn, int C, int M, uint32_t* __restrict__ wsum,
+                                                         const ClassLists plan, int c0, int cn, int C, int M, uint32_t* __restrict__ wsum,
                                                          uint32_t* __restrict__ wpos, uint64_t* __restrict__ csum,
                                                          uint64_t* __restrict__ bnum, int U) {
   __shared__ unsigned long long s_c[4][CALIB_BINS];
@@ -233,9 +227,7 @@ __global__ __launch_bounds__(256) void boot_calib_kernel(const uint32_t* __restr
     }
   }
   if (rw != 0u) atomicAdd(&s_w[wave][cur], rw), atomicAdd(&s_p[wave][cur], rp), atomicAdd(&s_c[wave][cur], (unsigned long long)rc);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1)
-    bn += ((uint64_t)(uint32_t)__shfl_xor((int)(bn >> 32), d) << 32) | (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)bn, d);
+  bn = wave_sum_u64(bn);
   __syncthreads();
   if (active) {
     const size_t o = (size_t)rep * C + c0 + cl;
@@ -263,22 +255,15 @@ int cx_boot_calib(const uint32_t* counts, int ld, int n_rep, const int32_t* orde
                   const int32_t* len, int C, int M, uint32_t* wsum, uint32_t* wpos, uint64_t* csum, uint64_t* bnum, int U, void* stream) {
   if (!counts || !order || !conf || !offs || !len || !wsum || !wpos || !csum || !bnum || n_rep < 1 || C < 1) return CX_EINVAL;
   if (M < 1 || M > CALIB_BINS) return CX_ESHAPE;
-  if (U < 1 || U > CX_BOOT_MAX_UNITS || ld < U) return CX_ESHAPE;
-  for (int c = 0; c < C; ++c)
-    if (len[c] < 0 || offs[c] < 0) return CX_EINVAL;
+  if (const int rc = check_class_lists(U, ld, offs, len, C)) return rc;
   if ((((uintptr_t)counts) & 3) || (((uintptr_t)order) & 3) || (((uintptr_t)conf) & 3) || (((uintptr_t)wsum) & 3) || (((uintptr_t)wpos) & 3) ||
       (((uintptr_t)csum) & 7) || (((uintptr_t)bnum) & 7))
     return CX_EALIGN;
-  if (((long long)n_rep * CALIB_CLASSES + 3) / 4 > 0x7fffffffll) return CX_ESHAPE;
-  for (int c0 = 0; c0 < C; c0 += CALIB_CLASSES) {
-    const int cn = min(CALIB_CLASSES, C - c0);
-    CalibPlan plan;
-    for (int c = 0; c < CALIB_CLASSES; ++c) plan.offs[c] = c < cn ? (long long)offs[c0 + c] : 0ll, plan.len[c] = c < cn ? len[c0 + c] : 0;
+  if (((long long)n_rep * CX_LIST_CLASSES + 3) / 4 > 0x7fffffffll) return CX_ESHAPE;
+  ClassLists plan;
+  return for_class_groups(offs, len, C, plan, [&](int c0, int cn) {
     const long long waves = (long long)n_rep * cn;
     hipLaunchKernelGGL(boot_calib_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, as_stream(stream), counts, ld, n_rep, order,
                        conf, plan, c0, cn, C, M, wsum, wpos, csum, bnum, U);
-    const int rc = launch_status();
-    if (rc) return rc;
-  }
-  return 0;
+  });
 }

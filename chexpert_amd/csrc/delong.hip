@@ -14,7 +14,7 @@
 // model, Gram 656 us (2.0e12 multiply-adds per second); at 234 x 5: 23 us and 17 us (launch latency).
 // Same bits every run: the only unordered operations are integer adds (device-memory atomics), and integer adds commute -- the
 // project's rule is about the order of FLOAT sums, of which this file has none.  No workgroup waits on another.
-#include "common.h"
+#include "resample.h"
 
 namespace {
 
@@ -27,13 +27,7 @@ constexpr int DL_STEP_ENTRIES = DL_THREADS * DL_STEPS;
 constexpr int DL_CHUNK = CX_DELONG_WG_ENTRIES;         // entries of a list that one workgroup walks
 static_assert(DL_CHUNK % DL_STEP_ENTRIES == 0, "a workgroup walks whole steps");
 static_assert(DL_STEPS * DL_WAVES == 64, "one lane per wave total in the scan of the totals");
-constexpr int DL_CLASSES = 32;                         // classes per launch (offsets and lengths travel as kernel arguments)
 constexpr int DL_MAX_U = CX_BOOT_MAX_UNITS;
-
-struct DelongPlan {
-  long long offs[DL_CLASSES];
-  int len[DL_CLASSES];
-};
 
 // rows x cols elements of a table of pitch ld, grid-stride (the padding behind the columns is not touched)
 __global__ __launch_bounds__(256) void delong_zero_kernel(u64* __restrict__ p, long long ld, int cols, long long total) {
@@ -49,7 +43,7 @@ __global__ __launch_bounds__(256) void delong_zero_kernel(u64* __restrict__ p, l
 // the chunk in steps of DL_STEP_ENTRIES entries, thread t the entries t, t + 1024, ... of the step: the number of positives in front of
 // an entry is the carry, plus the totals of the waves in front of it within the step (64 totals in LDS, scanned by every wave on its
 // own: no second hand-over), plus the ballot bits below its lane.  The negatives in front are the position minus that.
-__global__ __launch_bounds__(DL_THREADS) void delong_place_kernel(const int32_t* __restrict__ order, const DelongPlan plan, int c0,
+__global__ __launch_bounds__(DL_THREADS) void delong_place_kernel(const int32_t* __restrict__ order, const ClassLists plan, int c0,
                                                                   u64* __restrict__ z, long long ldz, int U) {
   __shared__ uint32_t tot[DL_STEPS * DL_WAVES];
   __shared__ uint32_t red[2 * DL_WAVES];
@@ -197,29 +191,22 @@ __global__ __launch_bounds__(256) void delong_gram_kernel(const u64* __restrict_
 
 int cx_delong_place(const int32_t* order, const int64_t* offs, const int32_t* len, int C, int U, int64_t* z, int ldz, void* stream) {
   if (!order || !offs || !len || !z || C < 1) return CX_EINVAL;
-  if (U < 1 || U > DL_MAX_U || ldz < U) return CX_ESHAPE;
-  for (int c = 0; c < C; ++c)
-    if (len[c] < 0 || offs[c] < 0) return CX_EINVAL;
+  if (const int rc = check_class_lists(U, ldz, offs, len, C)) return rc;
   if ((((uintptr_t)order) & 3) || (((uintptr_t)z) & 7)) return CX_EALIGN;
   const long long total = 4ll * C * U;
   const unsigned zgrid = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipLaunchKernelGGL(delong_zero_kernel, dim3(zgrid), dim3(256), 0, as_stream(stream), (u64*)z, (long long)ldz, U, total);
   int rc = launch_status();
   if (rc) return rc;
-  for (int c0 = 0; c0 < C; c0 += DL_CLASSES) {
-    const int cn = min(DL_CLASSES, C - c0);
-    DelongPlan plan;
-    for (int c = 0; c < DL_CLASSES; ++c) plan.offs[c] = c < cn ? (long long)offs[c0 + c] : 0ll, plan.len[c] = c < cn ? len[c0 + c] : 0;
+  ClassLists plan;
+  return for_class_groups(offs, len, C, plan, [&](int c0, int cn) {
     int longest = 0;
     for (int c = 0; c < cn; ++c) longest = max(longest, plan.len[c]);
-    if (longest == 0) continue;                                  // nothing to add: the rows stay zero
+    if (longest == 0) return;                                    // nothing to add: the rows stay zero
     const unsigned chunks = (unsigned)(((long long)longest + DL_CHUNK - 1) / DL_CHUNK);
     hipLaunchKernelGGL(delong_place_kernel, dim3(chunks, (unsigned)(2 * cn)), dim3(DL_THREADS), 0, as_stream(stream), order, plan, c0,
                        (u64*)z, (long long)ldz, U);
-    rc = launch_status();
-    if (rc) return rc;
-  }
-  return 0;
+  });
 }
 
 int cx_delong_gram(const int64_t* z, int ldz, int Q, int U, int64_t* g, void* stream) {

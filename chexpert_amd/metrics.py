@@ -2,8 +2,13 @@
 
 The reference calls sklearn `roc_curve` / `auc` / `precision_recall_curve` per class on raw logits.
 Here the ROC / PR curves are built directly (descending score sweep with tie groups collapsed, as
-sklearn's `_binary_clf_curve` does) and the AUROC is the trapezoid area.  Host-side numpy: this runs once
-per evaluation on (N, 5) arrays and is not on the GPU hot path.
+sklearn's `_binary_clf_curve` does) and the AUROC is the trapezoid area.  That part is host-side numpy: it runs once per
+evaluation on (N, 5) arrays.
+
+The interval estimates below it run on the GPU: percentile bootstrap intervals of the AUROC (bootstrap.hip, cx_boot_auc) and of
+the average precision and fixed operating points (cx_boot_sweep), both over the count tables of resample.py's replicate driver, and
+the analytic DeLong / Obuchowski intervals and paired test (delong.hip).  Every GPU function has a `*_reference` twin, the numpy
+statement the kernels are held to bit for bit; a pair shares one private body that differs only in where the integers come from.
 """
 import math
 import re
@@ -11,6 +16,10 @@ from fractions import Fraction
 from statistics import NormalDist
 
 import numpy as np
+
+from ._lib import BOOT_MAX_POINTS, BOOT_SENS, BOOT_SPEC, DELONG_MAX_ROWS
+from .resample import (BOOT_MAX_UNITS, _as_scores, _check_boot, _check_inputs, _pack_lists, _replicates, _summarise_diff,  # noqa: F401
+                       _summarise_metric, _units_of, bootstrap_counts_reference, bootstrap_draws, splitmix64)  # (the draws stay in reach here)
 
 
 def _binary_curve(y_true, score):
@@ -82,61 +91,7 @@ def mean_auc(metrics):
 #   num2 = sum over positives i of w_i * (LT_i + LE_i),  LT_i / LE_i = the negative weight with a score < / <= that of i
 #   AUROC = num2 / (2 W+ W-): the trapezoid area of the materialised resample, ties counted half; W+ = 0 or W- = 0: NaN (degenerate)
 # The `*_reference` functions are the numpy statement the kernels are held to bit for bit; `bootstrap_auc` itself runs on the GPU only.
-_M64 = (1 << 64) - 1
-BOOT_MAX_UNITS = 1 << 24
-BOOT_TABLE_BYTES = 256 << 20          # budget of the count table: replicates are processed in chunks that stay under it
-
-
-def splitmix64(seed, k):
-    """The draw hash: the splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 * (k + 1) mod 2^64 (what effnet.hip uses for dropout), on
-    Python ints."""
-    z = (seed + 0x9E3779B97F4A7C15 * (k + 1)) & _M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
-
-
-def bootstrap_draws(n_units, b, seed):
-    """The n_units unit indices replicate b draws: unit = ((splitmix64(seed, b * U + j) >> 32) * U) >> 32, in uint64 numpy arithmetic
-    (which wraps mod 2^64 as the definition asks).  The multiply-shift favours some units by at most U / 2^32 in probability."""
-    U = int(n_units)
-    with np.errstate(over="ignore"):
-        k = np.uint64((int(b) * U) & _M64) + np.arange(U, dtype=np.uint64)
-        z = np.uint64(int(seed) & _M64) + np.uint64(0x9E3779B97F4A7C15) * (k + np.uint64(1))
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-        return (((z >> np.uint64(32)) * np.uint64(U)) >> np.uint64(32)).astype(np.int64)
-
-
-def bootstrap_counts_reference(n_units, n_rep, seed, first=0):
-    """Statement of cx_boot_counts: (n_rep, n_units) uint32, row r = how often each unit is drawn by replicate first + r."""
-    U = int(n_units)
-    if not 1 <= U <= BOOT_MAX_UNITS:
-        raise ValueError("bootstrap: %d resampling units (1 .. 2^24 are supported)" % U)
-    out = np.zeros((int(n_rep), U), dtype=np.uint32)
-    for r in range(int(n_rep)):
-        out[r] = np.bincount(bootstrap_draws(U, first + r, seed), minlength=U)
-    return out
-
-
-def _as_scores(a):
-    if hasattr(a, "detach"):                    # a torch tensor: numpy has no bfloat16 (the conversion to fp32 keeps its order and ties)
-        a = a.detach().cpu()
-        a = (a.float() if str(a.dtype) in ("torch.bfloat16", "torch.float16") else a).numpy()
-    return np.asarray(a)
-
-
-def _units_of(n_rows, groups):
-    if groups is None:
-        return np.arange(n_rows, dtype=np.int64), n_rows
-    g = np.asarray(groups)
-    if g.shape != (n_rows,):
-        raise ValueError("bootstrap: groups holds %s ids for %d rows" % (g.shape, n_rows))
-    ids, inv = np.unique(g, return_inverse=True)
-    return inv.reshape(-1).astype(np.int64), int(len(ids))
-
-
+# The draws, the count table, the input checks and the replicate loop are resample.py's.
 def bootstrap_plan(outputs, targets, groups=None):
     """What cx_boot_auc reads, built once per call on the host (N log N): for every class the kept rows (target >= 0) in two orders,
     both ascending in score (compared in the dtype given): `hi` with the negatives of a tie group before its positives, `lo` with the
@@ -144,27 +99,16 @@ def bootstrap_plan(outputs, targets, groups=None):
     groups: one hashable id per row (data.extract_patient_ids output works); the units are the distinct ids.  None: every row its own.
     Returns {"order": int32 (for class c: hi then lo, lens[c] entries each, from offs[c]), "offs": int64 (C), "lens": int32 (C),
     "units": int64 (N) unit index of every row, "n_units": U}."""
-    s, t = _as_scores(outputs), np.asarray(_as_scores(targets), dtype=np.float64)
-    if s.ndim != 2 or s.shape != t.shape:
-        raise ValueError("bootstrap: outputs %s and targets %s must be (N, C) arrays of one shape" % (s.shape, t.shape))
-    if np.isnan(s).any():
-        raise ValueError("bootstrap: the scores hold NaN")
-    units, U = _units_of(s.shape[0], groups)
-    if not 1 <= U <= BOOT_MAX_UNITS:
-        raise ValueError("bootstrap: %d resampling units (1 .. 2^24 are supported)" % U)
-    parts, offs, lens, at = [], [], [], 0
+    s, t, units, U = _check_inputs(outputs, targets, groups, "bootstrap")
+    parts = []
     for c in range(s.shape[1]):
         keep = np.nonzero(t[:, c] >= 0)[0]
         pos = t[keep, c] > 0.5
         rank = np.unique(s[keep, c], return_inverse=True)[1].reshape(-1)
         entry = (units[keep] | (pos.astype(np.int64) << 31)).astype(np.uint32).view(np.int32)
-        parts += [entry[np.lexsort((pos, rank))], entry[np.lexsort((~pos, rank))]]
-        offs.append(at)
-        lens.append(len(keep))
-        at += 2 * len(keep)
-    order = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
-    return {"order": order.astype(np.int32), "offs": np.asarray(offs, dtype=np.int64), "lens": np.asarray(lens, dtype=np.int32),
-            "units": units, "n_units": U}
+        parts.append((entry[np.lexsort((pos, rank))], entry[np.lexsort((~pos, rank))]))
+    order, offs, lens = _pack_lists(parts)
+    return {"order": order, "offs": offs, "lens": lens, "units": units, "n_units": U}
 
 
 def bootstrap_scan_reference(counts, order, offs, lens, n_units):
@@ -218,93 +162,10 @@ def _auc_of(num2, wpos, wneg):
         return np.where(den > 0, num2 / np.where(den > 0, den, 1.0), np.nan)
 
 
-def _interval(v, alpha):
-    """(lo, hi, se, n_degenerate) of one column of replicates: percentiles and the ddof-1 deviation over the non-degenerate ones."""
-    ok = v[~np.isnan(v)]
-    lo, hi = (float(np.percentile(ok, 100.0 * q)) for q in (alpha / 2, 1 - alpha / 2)) if len(ok) else (float("nan"), float("nan"))
-    return lo, hi, float(np.std(ok, ddof=1)) if len(ok) > 1 else float("nan"), int(len(v) - len(ok))
-
-
-def _row_mean(a):
-    """Mean over the classes, NaN where any class is (np.mean propagates it)."""
-    return a.mean(axis=1) if a.shape[1] else np.full(a.shape[0], np.nan)
-
-
-def _summarise(point, rep, n_boot, seed, alpha, n_units, return_replicates):
-    C = rep.shape[1]
-    cols = [_interval(rep[:, c], alpha) for c in range(C)]
-    m = _interval(_row_mean(rep), alpha)
-    out = {"aucs": {c: float(point[c]) for c in range(C)}, "lo": {c: cols[c][0] for c in range(C)}, "hi": {c: cols[c][1] for c in range(C)},
-           "se": {c: cols[c][2] for c in range(C)}, "n_degenerate": {c: cols[c][3] for c in range(C)},
-           "mean_auc": {"point": float(_row_mean(point[None])[0]), "lo": m[0], "hi": m[1], "se": m[2]},
-           "n_boot": int(n_boot), "seed": int(seed), "alpha": float(alpha), "n_units": int(n_units)}
-    if return_replicates:
-        out["replicates"] = rep
-    return out
-
-
-def _p_two_sided(d):
-    ok = d[~np.isnan(d)]
-    if not len(ok):
-        return float("nan")
-    return float(min(1.0, 2.0 * min((np.sum(ok <= 0) + 1.0) / (len(ok) + 1.0), (np.sum(ok >= 0) + 1.0) / (len(ok) + 1.0))))
-
-
-def _summarise_diff(point_a, point_b, rep_a, rep_b, n_boot, seed, alpha, n_units, return_replicates):
-    C = rep_a.shape[1]
-    d = rep_a - rep_b                                         # NaN where either model's replicate is degenerate
-    cols = [_interval(d[:, c], alpha) for c in range(C)]
-    dm = _row_mean(rep_a) - _row_mean(rep_b)
-    m = _interval(dm, alpha)
-    out = {"delta": {c: float(point_a[c] - point_b[c]) for c in range(C)}, "lo": {c: cols[c][0] for c in range(C)},
-           "hi": {c: cols[c][1] for c in range(C)}, "p": {c: _p_two_sided(d[:, c]) for c in range(C)},
-           "n_degenerate": {c: cols[c][3] for c in range(C)},
-           "mean_auc": {"delta": float(_row_mean(point_a[None])[0] - _row_mean(point_b[None])[0]), "lo": m[0], "hi": m[1],
-                        "p": _p_two_sided(dm)},
-           "n_boot": int(n_boot), "seed": int(seed), "alpha": float(alpha), "n_units": int(n_units)}
-    if return_replicates:
-        out["replicates"] = d
-    return out
-
-
-def _check_boot(n_boot, alpha):
-    if int(n_boot) < 1:
-        raise ValueError("bootstrap: n_boot must be >= 1 (got %r)" % n_boot)
-    if not 0.0 < alpha < 1.0:
-        raise ValueError("bootstrap: alpha must be inside (0, 1) (got %r)" % alpha)
-
-
-def _replicates_gpu(plans, n_boot, seed, device, chunk):
-    """[(point (C), replicates (n_boot, C))] per plan, all plans over ONE count table per chunk of replicates (the paired comparison)."""
-    import torch
-
-    from . import ops
-    U = plans[0]["n_units"]
-    assert all(p["n_units"] == U for p in plans)
-    if chunk is None:
-        chunk = max(1, BOOT_TABLE_BYTES // (4 * U))
-    chunk = max(1, min(int(chunk), int(n_boot)))
-    orders = [torch.from_numpy(p["order"]).to(device) for p in plans]
-    table = torch.empty(chunk, U, dtype=torch.int32, device=device)
-    ones = torch.ones(1, U, dtype=torch.int32, device=device)
-    points = [_auc_of(*(v.cpu().numpy() for v in ops.boot_auc(ones, o, p["offs"], p["lens"], U)))[0] for p, o in zip(plans, orders)]
-    reps = [[] for _ in plans]
-    for first in range(0, int(n_boot), chunk):
-        counts = ops.boot_counts(U, min(chunk, int(n_boot) - first), seed, first=first, out=table)
-        for k, (p, o) in enumerate(zip(plans, orders)):
-            reps[k].append(_auc_of(*(v.cpu().numpy() for v in ops.boot_auc(counts, o, p["offs"], p["lens"], U))))
-    return [(pt, np.concatenate(r)) for pt, r in zip(points, reps)]
-
-
-def _replicates_reference(outputs, targets, groups, n_boot, seed):
-    s, t = _as_scores(outputs), np.asarray(_as_scores(targets), dtype=np.float64)
-    units, U = _units_of(s.shape[0], groups)
-    point = _auc_of(*_definition_parts(s, t, units, np.ones((1, U), dtype=np.int64)))[0]
-    reps = []
-    for first in range(0, int(n_boot), 64):                       # (chunks only bound the host memory: a row depends on its index alone)
-        counts = bootstrap_counts_reference(U, min(64, int(n_boot) - first), seed, first=first)
-        reps.append(_auc_of(*_definition_parts(s, t, units, counts)))
-    return point, np.concatenate(reps), U
+def _aucs(summaries):
+    """bootstrap_auc's result from bootstrap_metrics' for ("auroc",): the same numbers with "aucs" in place of "point"."""
+    s = summaries["auroc"]
+    return {"aucs": s.pop("point"), **s}
 
 
 def bootstrap_auc(outputs, targets, n_boot=1000, seed=0, groups=None, alpha=0.05, device="cuda", chunk=None, return_replicates=False):
@@ -317,17 +178,12 @@ def bootstrap_auc(outputs, targets, n_boot=1000, seed=0, groups=None, alpha=0.05
       n_degenerate: replicates without a positive or without a negative; mean_auc: {point, lo, hi, se} of the per-replicate mean over
       the classes (NaN where any class is degenerate); n_boot, seed, alpha, n_units.
     return_replicates: also "replicates", the (n_boot, C) float64 array (not json-serialisable)."""
-    _check_boot(n_boot, alpha)
-    plan = bootstrap_plan(outputs, targets, groups)
-    (point, rep), = _replicates_gpu([plan], n_boot, seed, device, chunk)
-    return _summarise(point, rep, n_boot, seed, alpha, plan["n_units"], return_replicates)
+    return _aucs(_bootstrap_metrics(outputs, targets, ("auroc",), n_boot, seed, groups, alpha, return_replicates, device=device, chunk=chunk))
 
 
 def bootstrap_auc_reference(outputs, targets, n_boot=1000, seed=0, groups=None, alpha=0.05, return_replicates=False):
     """The numpy statement of bootstrap_auc (host, integers from the definition; for the tests and as the timing yardstick)."""
-    _check_boot(n_boot, alpha)
-    point, rep, U = _replicates_reference(outputs, targets, groups, n_boot, seed)
-    return _summarise(point, rep, n_boot, seed, alpha, U, return_replicates)
+    return _aucs(_bootstrap_metrics(outputs, targets, ("auroc",), n_boot, seed, groups, alpha, return_replicates, host=True))
 
 
 def bootstrap_auc_diff(outputs_a, outputs_b, targets, n_boot=1000, seed=0, groups=None, alpha=0.05, device="cuda", chunk=None,
@@ -335,18 +191,13 @@ def bootstrap_auc_diff(outputs_a, outputs_b, targets, n_boot=1000, seed=0, group
     """Paired bootstrap of the AUROC difference of two models on the same rows (one count table, two plans).  Per class and under
     "mean_auc" for the mean over the classes: delta (a - b), lo, hi (percentiles of the replicate differences) and p, two-sided:
     2 min((#{d* <= 0} + 1) / (B' + 1), (#{d* >= 0} + 1) / (B' + 1)) capped at 1, B' = the replicates degenerate in neither model."""
-    _check_boot(n_boot, alpha)
-    pa, pb = bootstrap_plan(outputs_a, targets, groups), bootstrap_plan(outputs_b, targets, groups)
-    (point_a, rep_a), (point_b, rep_b) = _replicates_gpu([pa, pb], n_boot, seed, device, chunk)
-    return _summarise_diff(point_a, point_b, rep_a, rep_b, n_boot, seed, alpha, pa["n_units"], return_replicates)
+    return _bootstrap_metrics_diff(outputs_a, outputs_b, targets, ("auroc",), n_boot, seed, groups, alpha, return_replicates, device=device,
+                                   chunk=chunk)["auroc"]
 
 
 def bootstrap_auc_diff_reference(outputs_a, outputs_b, targets, n_boot=1000, seed=0, groups=None, alpha=0.05, return_replicates=False):
     """The numpy statement of bootstrap_auc_diff."""
-    _check_boot(n_boot, alpha)
-    point_a, rep_a, U = _replicates_reference(outputs_a, targets, groups, n_boot, seed)
-    point_b, rep_b, _ = _replicates_reference(outputs_b, targets, groups, n_boot, seed)
-    return _summarise_diff(point_a, point_b, rep_a, rep_b, n_boot, seed, alpha, U, return_replicates)
+    return _bootstrap_metrics_diff(outputs_a, outputs_b, targets, ("auroc",), n_boot, seed, groups, alpha, return_replicates, host=True)["auroc"]
 
 
 # ---- bootstrap of the metrics that need the whole threshold sweep (chexpert_amd/csrc/bootstrap.hip, cx_boot_sweep) ----------------
@@ -360,7 +211,7 @@ def bootstrap_auc_diff_reference(outputs_a, outputs_b, targets, n_boot=1000, see
 #   sens@S  = max{tp_g : fp_g 10^6 <= (10^6 - s) W-} / W+,  s = round(S 10^6): the sensitivity at specificity >= S
 #   spec@S  = 1 - min{fp_g : tp_g 10^6 >= s W+} / W-: the specificity at sensitivity >= S.  Both NaN iff W+ = 0 or W- = 0
 # A tie group without weight in a replicate repeats the previous (tp, fp), so the group ends are a property of the scores alone.
-BOOT_MAX_POINTS, BOOT_SENS, BOOT_SPEC, BOOT_PPM = 8, 0, 1, 10 ** 6
+BOOT_PPM = 10 ** 6
 _METRIC_POINT = re.compile(r"(sens|spec)@(\d*\.\d+|\d+)\Z")
 
 
@@ -401,15 +252,8 @@ def bootstrap_sweep_plan(outputs, targets, groups=None):
     entry of its tie group (free: U <= 2^24).  Inside a tie group the positives come first, then the row index ascends: the order there
     is immaterial, this one makes the plan deterministic.  Returns {"order": int32, "offs": int64 (C), "lens": int32 (C), "units",
     "n_units"} as bootstrap_plan does, with lens[c] entries for class c from offs[c]."""
-    s, t = _as_scores(outputs), np.asarray(_as_scores(targets), dtype=np.float64)
-    if s.ndim != 2 or s.shape != t.shape:
-        raise ValueError("bootstrap: outputs %s and targets %s must be (N, C) arrays of one shape" % (s.shape, t.shape))
-    if np.isnan(s).any():
-        raise ValueError("bootstrap: the scores hold NaN")
-    units, U = _units_of(s.shape[0], groups)
-    if not 1 <= U <= BOOT_MAX_UNITS:
-        raise ValueError("bootstrap: %d resampling units (1 .. 2^24 are supported)" % U)
-    parts, offs, lens, at = [], [], [], 0
+    s, t, units, U = _check_inputs(outputs, targets, groups, "bootstrap")
+    parts = []
     for c in range(s.shape[1]):
         keep = np.nonzero(t[:, c] >= 0)[0]
         pos = t[keep, c] > 0.5
@@ -420,12 +264,8 @@ def bootstrap_sweep_plan(outputs, targets, groups=None):
             r = rank[by]
             entry |= np.r_[r[1:] != r[:-1], True].astype(np.int64) << 30
         parts.append(entry.astype(np.uint32).view(np.int32))
-        offs.append(at)
-        lens.append(len(keep))
-        at += len(keep)
-    order = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
-    return {"order": order.astype(np.int32), "offs": np.asarray(offs, dtype=np.int64), "lens": np.asarray(lens, dtype=np.int32),
-            "units": units, "n_units": U}
+    order, offs, lens = _pack_lists(parts)
+    return {"order": order, "offs": offs, "lens": lens, "units": units, "n_units": U}
 
 
 def _check_points(points):
@@ -518,65 +358,67 @@ def _sweep_values(names, points, apnum, wpos, wneg, pts):
     return out
 
 
-def _summarise_metric(*args):
-    s = _summarise(*args)
-    return {"point": s.pop("aucs"), **s}
-
-
-def _metric_replicates_gpu(models, targets, names, points, n_boot, seed, groups, device, chunk):
-    """[{name: (point (C), replicates (n_boot, C))}] per model, every model and every metric over ONE count table per chunk of
-    replicates; the point estimate goes through the same kernels with a row of ones."""
-    import torch
-
-    from . import ops
-    auc = [bootstrap_plan(o, targets, groups) if "auroc" in names else None for o in models]
-    swp = [bootstrap_sweep_plan(o, targets, groups) if len(names) > ("auroc" in names) else None for o in models]
-    U = (auc[0] or swp[0])["n_units"]
-    if chunk is None:
-        chunk = max(1, BOOT_TABLE_BYTES // (4 * U))
-    chunk = max(1, min(int(chunk), int(n_boot)))
-    dev_order = [[None if p is None else torch.from_numpy(p["order"]).to(device) for p in (a, s)] for a, s in zip(auc, swp)]
-
-    def evaluate(counts, k):
-        out = {}
-        if auc[k] is not None:
-            out["auroc"] = _auc_of(*(v.cpu().numpy() for v in ops.boot_auc(counts, dev_order[k][0], auc[k]["offs"], auc[k]["lens"], U)))
-        if swp[k] is not None:
-            got = ops.boot_sweep(counts, dev_order[k][1], swp[k]["offs"], swp[k]["lens"], U, points)
-            apnum, wpos, wneg, pts = (v.cpu().numpy() for v in got)
-            out.update(_sweep_values(names, points, apnum.view(np.uint64), wpos, wneg, pts))
-        return out
-
-    table = torch.empty(chunk, U, dtype=torch.int32, device=device)
-    ones = torch.ones(1, U, dtype=torch.int32, device=device)
-    point = [evaluate(ones, k) for k in range(len(models))]
-    reps = [{name: [] for name in names} for _ in models]
-    for first in range(0, int(n_boot), chunk):
-        counts = ops.boot_counts(U, min(chunk, int(n_boot) - first), seed, first=first, out=table)
-        for k in range(len(models)):
-            for name, v in evaluate(counts, k).items():
-                reps[k][name].append(v)
-    return [{name: (point[k][name][0], np.concatenate(reps[k][name])) for name in names} for k in range(len(models))], U
-
-
-def _metric_replicates_reference(outputs, targets, names, points, n_boot, seed, groups):
-    """{name: (point, replicates)} on the host: the AUROC as bootstrap_auc_reference forms it, the sweep's metrics through the numpy
-    statement of the kernel over the prepared plan."""
-    out, U = {}, None
+def _evaluator(outputs, targets, groups, names, points, device=None, host=False):
+    """(evaluate, U) of one model: evaluate(counts) -> {name: (R, C) float64} of the named metrics over a count table.  On the GPU the
+    integers come from cx_boot_auc and cx_boot_sweep over the prepared plans; host=True: the AUROC's from the definition
+    (`_definition_parts`, no plan) and the sweep's from the numpy statement of the kernel over the plan."""
+    auroc = sweep = None                                         # counts -> the integer parts, where the names ask for them
     if "auroc" in names:
-        point, rep, U = _replicates_reference(outputs, targets, groups, n_boot, seed)
-        out["auroc"] = (point, rep)
+        if host:
+            s, t = _as_scores(outputs), np.asarray(_as_scores(targets), dtype=np.float64)
+            units, U = _units_of(s.shape[0], groups)
+
+            def auroc(counts):
+                return _definition_parts(s, t, units, counts)
+        else:
+            plan = bootstrap_plan(outputs, targets, groups)
+            auroc, U = _gpu_parts("boot_auc", plan, device), plan["n_units"]
     if len(names) > ("auroc" in names):
         plan = bootstrap_sweep_plan(outputs, targets, groups)
         U = plan["n_units"]
+        if host:
+            def sweep(counts):
+                return bootstrap_sweep_reference(counts, plan["order"], plan["offs"], plan["lens"], U, points)
+        else:
+            sweep = _gpu_parts("boot_sweep", plan, device, points)
 
-        def values(counts):
-            return _sweep_values(names, points, *bootstrap_sweep_reference(counts, plan["order"], plan["offs"], plan["lens"], U, points))
-        point, reps = values(np.ones((1, U), dtype=np.uint32)), []
-        for first in range(0, int(n_boot), 64):
-            reps.append(values(bootstrap_counts_reference(U, min(64, int(n_boot) - first), seed, first=first)))
-        out.update({name: (point[name][0], np.concatenate([r[name] for r in reps])) for name in point})
-    return {name: out[name] for name in names}, U
+    def evaluate(counts):
+        out = {} if auroc is None else {"auroc": _auc_of(*auroc(counts))}
+        if sweep is not None:
+            out.update(_sweep_values(names, points, *sweep(counts)))       # (apnum is read as the kernel's uint64 there)
+        return out
+    return evaluate, U
+
+
+def _gpu_parts(op, plan, device, *args):
+    """counts -> the integer parts that ops.<op> returns for the plan, as numpy arrays; the order array goes to the device once."""
+    import torch
+
+    from . import ops
+    order = torch.from_numpy(plan["order"]).to(device)
+    return lambda counts: (v.cpu().numpy() for v in getattr(ops, op)(counts, order, plan["offs"], plan["lens"], plan["n_units"], *args))
+
+
+def _bootstrap(models, targets, metrics, n_boot, seed, groups, alpha, device=None, chunk=None, host=False):
+    """(names, point, reps, U) of the named metrics of every model over ONE count table per chunk of replicates (the paired
+    comparison): point[k, name] (C) and reps[k, name] (n_boot, C) of model k."""
+    _check_boot(n_boot, alpha)
+    names, points = parse_boot_metrics(metrics)
+    evaluators, units = zip(*(_evaluator(o, targets, groups, names, points, device, host) for o in models))
+    point, reps = _replicates(lambda counts: {(k, name): v for k, evaluate in enumerate(evaluators) for name, v in evaluate(counts).items()},
+                              units[0], n_boot, seed, device, chunk, host)
+    return names, point, reps, units[0]
+
+
+def _bootstrap_metrics(outputs, targets, metrics, n_boot, seed, groups, alpha, return_replicates, **backend):
+    names, point, reps, U = _bootstrap([outputs], targets, metrics, n_boot, seed, groups, alpha, **backend)
+    return {name: _summarise_metric(point[0, name], reps[0, name], n_boot, seed, alpha, U, return_replicates) for name in names}
+
+
+def _bootstrap_metrics_diff(outputs_a, outputs_b, targets, metrics, n_boot, seed, groups, alpha, return_replicates, **backend):
+    names, point, reps, U = _bootstrap([outputs_a, outputs_b], targets, metrics, n_boot, seed, groups, alpha, **backend)
+    return {name: _summarise_diff(point[0, name], point[1, name], reps[0, name], reps[1, name], n_boot, seed, alpha, U, return_replicates)
+            for name in names}
 
 
 def bootstrap_metrics(outputs, targets, metrics=("auroc", "ap"), n_boot=1000, seed=0, groups=None, alpha=0.05, device="cuda", chunk=None,
@@ -587,41 +429,27 @@ def bootstrap_metrics(outputs, targets, metrics=("auroc", "ap"), n_boot=1000, se
     points in one call.  The other arguments are those of bootstrap_auc.  Returns {name: summary}; a summary has the keys of
     bootstrap_auc's result with "point" in place of "aucs" ("mean_auc" is the metric's mean over the classes), and the "auroc"
     summary carries the numbers of bootstrap_auc with the same arguments, bit for bit."""
-    _check_boot(n_boot, alpha)
-    names, points = parse_boot_metrics(metrics)
-    (res,), U = _metric_replicates_gpu([outputs], targets, names, points, n_boot, seed, groups, device, chunk)
-    return {name: _summarise_metric(*res[name], n_boot, seed, alpha, U, return_replicates) for name in names}
+    return _bootstrap_metrics(outputs, targets, metrics, n_boot, seed, groups, alpha, return_replicates, device=device, chunk=chunk)
 
 
 def bootstrap_metrics_reference(outputs, targets, metrics=("auroc", "ap"), n_boot=1000, seed=0, groups=None, alpha=0.05,
                                 return_replicates=False):
     """The numpy statement of bootstrap_metrics (host; for the tests and as the timing yardstick)."""
-    _check_boot(n_boot, alpha)
-    names, points = parse_boot_metrics(metrics)
-    res, U = _metric_replicates_reference(outputs, targets, names, points, n_boot, seed, groups)
-    return {name: _summarise_metric(*res[name], n_boot, seed, alpha, U, return_replicates) for name in names}
+    return _bootstrap_metrics(outputs, targets, metrics, n_boot, seed, groups, alpha, return_replicates, host=True)
 
 
 def bootstrap_metrics_diff(outputs_a, outputs_b, targets, metrics=("auroc", "ap"), n_boot=1000, seed=0, groups=None, alpha=0.05,
                            device="cuda", chunk=None, return_replicates=False):
     """Paired bootstrap of the difference a - b of every named metric between two models on the same rows (one count table, two plans
     per kernel).  Returns {name: what bootstrap_auc_diff returns for the AUROC}."""
-    _check_boot(n_boot, alpha)
-    names, points = parse_boot_metrics(metrics)
-    (a, b), U = _metric_replicates_gpu([outputs_a, outputs_b], targets, names, points, n_boot, seed, groups, device, chunk)
-    return {name: _summarise_diff(a[name][0], b[name][0], a[name][1], b[name][1], n_boot, seed, alpha, U, return_replicates)
-            for name in names}
+    return _bootstrap_metrics_diff(outputs_a, outputs_b, targets, metrics, n_boot, seed, groups, alpha, return_replicates, device=device,
+                                   chunk=chunk)
 
 
 def bootstrap_metrics_diff_reference(outputs_a, outputs_b, targets, metrics=("auroc", "ap"), n_boot=1000, seed=0, groups=None, alpha=0.05,
                                      return_replicates=False):
     """The numpy statement of bootstrap_metrics_diff."""
-    _check_boot(n_boot, alpha)
-    names, points = parse_boot_metrics(metrics)
-    a, U = _metric_replicates_reference(outputs_a, targets, names, points, n_boot, seed, groups)
-    b, _ = _metric_replicates_reference(outputs_b, targets, names, points, n_boot, seed, groups)
-    return {name: _summarise_diff(a[name][0], b[name][0], a[name][1], b[name][1], n_boot, seed, alpha, U, return_replicates)
-            for name in names}
+    return _bootstrap_metrics_diff(outputs_a, outputs_b, targets, metrics, n_boot, seed, groups, alpha, return_replicates, host=True)
 
 
 # ---- DeLong / Obuchowski variance of the AUROC and the paired test (chexpert_amd/csrc/delong.hip) ----------------------------------
@@ -645,9 +473,6 @@ def bootstrap_metrics_diff_reference(outputs_a, outputs_b, targets, metrics=("au
 # coefficients.  The host forms these combinations in Python integers, the quotients as exact fractions, and rounds ONCE to float64:
 # no float sum is ever formed, so the GPU path and the numpy statement return equal floats whenever their integers agree, and identical
 # models give Var(delta) = 0 exactly.
-DELONG_MAX_ROWS = 128                 # CX_DELONG_MAX_ROWS: 4 rows per class and model, two models of 16 classes
-
-
 def delong_place_reference(order, offs, lens, n_units):
     """Statement of cx_delong_place in int64 numpy: the (4 C, n_units) table, rows 4c .. 4c+3 = X, m, Y, n of class c, from the `hi` /
     `lo` orders of bootstrap_plan.  In `hi` the negatives in front of a positive are its LE, in `lo` its LT (their sum is X2); for a
@@ -819,22 +644,24 @@ def _delong_diff_summary(fin, alpha, grouped):
     return out
 
 
-def _delong_gpu(plans, device):
-    """_DelongFinish of the plans through cx_delong_place and cx_delong_gram: one stacked table, one Gram matrix."""
-    import torch
-
-    from . import ops
+def _delong(summary, models, targets, groups, alpha, device=None, host=False):
+    """summary (_delong_summary | _delong_diff_summary) of the exact finish over one stacked table and one Gram matrix of the models:
+    through cx_delong_place and cx_delong_gram on `device`, or, host=True, through their numpy statements."""
+    _delong_check(alpha)
+    plans = _delong_plans(models, targets, groups)
     U, n_cls = plans[0]["n_units"], len(plans[0]["lens"])
-    table = torch.empty(4 * n_cls * len(plans), U, dtype=torch.int64, device=device)
-    for k, p in enumerate(plans):
-        ops.delong_place(torch.from_numpy(p["order"]).to(device), p["offs"], p["lens"], U, out=table[4 * n_cls * k:4 * n_cls * (k + 1)])
-    g = ops.int_gram(table, U)
-    return _DelongFinish(_delong_stats(table, len(plans)), g.cpu().tolist(), U)
+    if host:
+        table = np.concatenate([delong_place_reference(p["order"], p["offs"], p["lens"], U) for p in plans])
+        gram = int_gram_reference(table)
+    else:
+        import torch
 
-
-def _delong_host(plans):
-    table = np.concatenate([delong_place_reference(p["order"], p["offs"], p["lens"], p["n_units"]) for p in plans])
-    return _DelongFinish(_delong_stats(table, len(plans)), int_gram_reference(table).tolist(), plans[0]["n_units"])
+        from . import ops
+        table = torch.empty(4 * n_cls * len(plans), U, dtype=torch.int64, device=device)
+        for k, p in enumerate(plans):
+            ops.delong_place(torch.from_numpy(p["order"]).to(device), p["offs"], p["lens"], U, out=table[4 * n_cls * k:4 * n_cls * (k + 1)])
+        gram = ops.int_gram(table, U).cpu()
+    return summary(_DelongFinish(_delong_stats(table, len(plans)), gram.tolist(), U), alpha, groups is not None)
 
 
 def delong_auc(outputs, targets, groups=None, alpha=0.05, device="cuda"):
@@ -849,15 +676,12 @@ def delong_auc(outputs, targets, groups=None, alpha=0.05, device="cuda"):
     throughout (and the mean with it, as in bootstrap_auc); a class with one positive or one negative unit: se, lo, hi NaN.
     ValueError before any launch: bootstrap_plan's input errors (shapes, NaN scores), more than 32 classes, alpha outside (0, 1), and
     4 max_c(M_c + N_c)^2 sum_u g_u^2 >= 2^63 (g_u the rows of unit u), beyond which the moment sums could overflow."""
-    _delong_check(alpha)
-    plans = _delong_plans([outputs], targets, groups)
-    return _delong_summary(_delong_gpu(plans, device), alpha, groups is not None)
+    return _delong(_delong_summary, [outputs], targets, groups, alpha, device)
 
 
 def delong_auc_reference(outputs, targets, groups=None, alpha=0.05):
     """The numpy statement of delong_auc (host: delong_place_reference, int_gram_reference and the same exact finish)."""
-    _delong_check(alpha)
-    return _delong_summary(_delong_host(_delong_plans([outputs], targets, groups)), alpha, groups is not None)
+    return _delong(_delong_summary, [outputs], targets, groups, alpha, host=True)
 
 
 def delong_auc_diff(outputs_a, outputs_b, targets, groups=None, alpha=0.05, device="cuda"):
@@ -866,12 +690,9 @@ def delong_auc_diff(outputs_a, outputs_b, targets, groups=None, alpha=0.05, devi
     p = erfc(|z| / sqrt 2) and degenerate (Var(delta) <= 0, identical scores for example: z and p are NaN); mean_auc: {delta, se, lo,
     hi, z, p} of the mean over the classes with the influence form of delong_auc on psibar_a - psibar_b; alpha, n_units, method.  At
     most 16 classes; the other errors are those of delong_auc."""
-    _delong_check(alpha)
-    plans = _delong_plans([outputs_a, outputs_b], targets, groups)
-    return _delong_diff_summary(_delong_gpu(plans, device), alpha, groups is not None)
+    return _delong(_delong_diff_summary, [outputs_a, outputs_b], targets, groups, alpha, device)
 
 
 def delong_auc_diff_reference(outputs_a, outputs_b, targets, groups=None, alpha=0.05):
     """The numpy statement of delong_auc_diff."""
-    _delong_check(alpha)
-    return _delong_diff_summary(_delong_host(_delong_plans([outputs_a, outputs_b], targets, groups)), alpha, groups is not None)
+    return _delong(_delong_diff_summary, [outputs_a, outputs_b], targets, groups, alpha, host=True)

@@ -9,8 +9,9 @@ import os
 import torch
 
 from . import _lib as L
-from ._lib import (EPI_JOIN, EPI_MASK, EPI_STORE, MODE_CONV, MODE_POOL2, MODE_STEM, PRO_AFFINE2, PRO_AFFINE_RELU, PRO_JOIN, PRO_NONE,
-                   CxConv, CxWgrad, check, lib, ptr, require_cuda, stream_ptr)
+from ._lib import (BOOT_MAX_POINTS, BOOT_MAX_TILES, BOOT_MAX_UNITS, BOOT_SENS, BOOT_SPEC, BOOT_TILE, CALIB_MAX_BINS, CALIB_MAX_ITER,
+                   CALIB_METHODS, DELONG_MAX_ROWS, DELONG_TILE, DELONG_WG_ENTRIES, EPI_JOIN, EPI_MASK, EPI_STORE, MODE_CONV, MODE_POOL2,
+                   MODE_STEM, PRO_AFFINE2, PRO_AFFINE_RELU, PRO_JOIN, PRO_NONE, CxConv, CxWgrad, check, lib, ptr, require_cuda, stream_ptr)
 import ctypes as C
 
 
@@ -1356,8 +1357,22 @@ def cam_norm_upsample(cam, out, h, w):
     check(lib().cx_cam_norm_upsample(ptr(cam), ptr(out), B, h, w, H, W, stream_ptr()), "cx_cam_norm_upsample")
 
 
-# ---- bootstrap of the AUROC (bootstrap.hip) ----
-BOOT_TILE, BOOT_MAX_TILES, BOOT_MAX_UNITS = 8192, 8, 1 << 24      # CX_BOOT_TILE, CX_BOOT_MAX_TILES, CX_BOOT_MAX_UNITS of the header
+# ---- evaluation statistics over per-class entry lists (bootstrap.hip, calib.hip, delong.hip; the header's constants are in _lib.py) ----
+def _class_lists(what, counts, order, offs, lens, n_units, per_class=1, min_classes=0):
+    """What boot_auc, boot_sweep, boot_calib and delong_place check alike: counts (None: the kernel reads no table) is int32
+    (n_rep, >= n_units) on the GPU with unit row stride, order a contiguous int32 device tensor, and class c's per_class lists of
+    lens[c] entries from offs[c] lie inside it (ValueError in `what`'s name otherwise).  Returns (ld, n_rep, n_cls, offs, lens): the
+    row pitch to pass for counts and the two host sequences as the ctypes arrays the entry points take."""
+    require_cuda(counts, order)
+    assert counts is None or (counts.dtype == torch.int32 and counts.dim() == 2 and counts.stride(1) == 1 and counts.shape[1] >= n_units), \
+        "counts: int32 (n_rep, >= n_units) rows"
+    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), "order: contiguous int32"
+    offs, lens = [int(v) for v in offs], [int(v) for v in lens]
+    n_cls, n_rep = len(lens), 0 if counts is None else counts.shape[0]
+    if n_cls < min_classes or len(offs) != n_cls or any(n < 0 or o < 0 or o + per_class * n > order.numel() for o, n in zip(offs, lens)):
+        raise ValueError("%s: offsets %s / lengths %s do not fit an order array of %d entries" % (what, offs, lens, order.numel()))
+    ld = 0 if counts is None else counts.stride(0) if n_rep > 1 else counts.shape[1]
+    return ld, n_rep, n_cls, (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens)
 
 
 def boot_counts(n_units, n_rep, seed, first=0, out=None, device="cuda"):
@@ -1383,26 +1398,15 @@ def boot_auc(counts, order, offs, lens, n_units):
     device tensor holding, for class c, the `hi` then the `lo` order of its kept rows (lens[c] entries each, from offs[c]; an entry =
     unit index | label << 31; metrics.bootstrap_plan builds them); offs / lens: host sequences of C ints.  Returns int64 tensors
     (n_rep, C): num2, wpos, wneg with AUROC = num2 / (2 * wpos * wneg); a class with lens[c] == 0 gives zeros."""
-    require_cuda(counts, order)
-    assert counts.dtype == torch.int32 and counts.dim() == 2 and counts.stride(1) == 1 and counts.shape[1] >= n_units, \
-        "counts: int32 (n_rep, >= n_units) rows"
-    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), "order: contiguous int32"
-    offs, lens = [int(v) for v in offs], [int(v) for v in lens]
-    n_cls, n_rep = len(lens), counts.shape[0]
-    if len(offs) != n_cls or any(n < 0 or o < 0 or o + 2 * n > order.numel() for o, n in zip(offs, lens)):
-        raise ValueError("boot_auc: offsets %s / lengths %s do not fit an order array of %d entries" % (offs, lens, order.numel()))
+    ld, n_rep, n_cls, offs, lens = _class_lists("boot_auc", counts, order, offs, lens, n_units, per_class=2)
     num2 = torch.empty(n_rep, n_cls, dtype=torch.int64, device=counts.device)
     wpos = torch.empty(n_rep, n_cls, dtype=torch.int32, device=counts.device)
     wneg = torch.empty_like(wpos)
     if n_rep == 0:
         return num2, wpos.long(), wneg.long()
-    ld = counts.stride(0) if n_rep > 1 else counts.shape[1]
-    check(lib().cx_boot_auc(ptr(counts), ld, n_rep, ptr(order), (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens), n_cls, ptr(num2),
-                            ptr(wpos), ptr(wneg), int(n_units), stream_ptr()), "cx_boot_auc")
+    check(lib().cx_boot_auc(ptr(counts), ld, n_rep, ptr(order), offs, lens, n_cls, ptr(num2), ptr(wpos), ptr(wneg), int(n_units),
+                            stream_ptr()), "cx_boot_auc")
     return num2, wpos.long() & 0xffffffff, wneg.long() & 0xffffffff      # the kernel's uint32 sums
-
-
-BOOT_MAX_POINTS, BOOT_SENS, BOOT_SPEC = 8, 0, 1                    # CX_BOOT_MAX_POINTS, CX_BOOT_SENS, CX_BOOT_SPEC of the header
 
 
 def boot_sweep(counts, order, offs, lens, n_units, points=()):
@@ -1412,15 +1416,9 @@ def boot_sweep(counts, order, offs, lens, n_units, points=()):
     BOOT_MAX_POINTS pairs (BOOT_SENS or BOOT_SPEC, value in millionths 1 .. 999 999).  Returns int64 tensors apnum, wpos, wneg
     (n_rep, C) and pts (n_rep, C, len(points)): AP = apnum / (wpos * 2^32) with apnum the kernel's uint64 (read it as such: .numpy()
     .view(np.uint64); it passes 2^63 only when wpos does 2^31); sens@ = pts / wpos, spec@ = 1 - pts / wneg."""
-    require_cuda(counts, order)
-    assert counts.dtype == torch.int32 and counts.dim() == 2 and counts.stride(1) == 1 and counts.shape[1] >= n_units, \
-        "counts: int32 (n_rep, >= n_units) rows"
-    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), "order: contiguous int32"
-    offs, lens = [int(v) for v in offs], [int(v) for v in lens]
     points = [(int(k), int(v)) for k, v in points]
-    n_cls, n_rep, n_pts = len(lens), counts.shape[0], len(points)
-    if len(offs) != n_cls or any(n < 0 or o < 0 or o + n > order.numel() for o, n in zip(offs, lens)):
-        raise ValueError("boot_sweep: offsets %s / lengths %s do not fit an order array of %d entries" % (offs, lens, order.numel()))
+    n_pts = len(points)
+    ld, n_rep, n_cls, offs, lens = _class_lists("boot_sweep", counts, order, offs, lens, n_units)
     if n_pts > BOOT_MAX_POINTS or any(k not in (BOOT_SENS, BOOT_SPEC) or not 1 <= v <= 999999 for k, v in points):
         raise ValueError("boot_sweep: at most %d operating points (BOOT_SENS | BOOT_SPEC, 1 .. 999999 millionths), got %s"
                          % (BOOT_MAX_POINTS, points))
@@ -1430,19 +1428,13 @@ def boot_sweep(counts, order, offs, lens, n_units, points=()):
     pts = torch.empty(n_rep, n_cls, n_pts, dtype=torch.int32, device=counts.device)
     if n_rep == 0:
         return apnum, wpos.long(), wneg.long(), pts.long()
-    ld = counts.stride(0) if n_rep > 1 else counts.shape[1]
-    check(lib().cx_boot_sweep(ptr(counts), ld, n_rep, ptr(order), (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens), n_cls,
-                              (C.c_int32 * max(n_pts, 1))(*[k for k, _ in points]), (C.c_int32 * max(n_pts, 1))(*[v for _, v in points]),
-                              n_pts, ptr(apnum), ptr(wpos), ptr(wneg), ptr(pts) if n_pts else None, int(n_units), stream_ptr()),
-          "cx_boot_sweep")
+    check(lib().cx_boot_sweep(ptr(counts), ld, n_rep, ptr(order), offs, lens, n_cls, (C.c_int32 * max(n_pts, 1))(*[k for k, _ in points]),
+                              (C.c_int32 * max(n_pts, 1))(*[v for _, v in points]), n_pts, ptr(apnum), ptr(wpos), ptr(wneg),
+                              ptr(pts) if n_pts else None, int(n_units), stream_ptr()), "cx_boot_sweep")
     return apnum, wpos.long() & 0xffffffff, wneg.long() & 0xffffffff, pts.long() & 0xffffffff      # the kernel's unsigned values
 
 
 # ---- calibration (calib.hip; chexpert_amd/calibration.py composes them and states them in numpy) ----
-CALIB_METHODS = {"temperature": 0, "platt": 1}                     # CX_CALIB_TEMPERATURE, CX_CALIB_PLATT of the header
-CALIB_MAX_ITER, CALIB_MAX_BINS = 1000, 64                          # CX_CALIB_MAX_ITER, CX_CALIB_MAX_BINS
-
-
 def calib_fit(logits, targets, method="temperature", smooth=False, g_tol=1e-10, max_iter=100):
     """cx_calib_fit: the per-class calibration map u = a z + b of (N, C) logits against (N, C) targets (target < 0: the row is left
     out of the class; positive iff target > 0.5), every class in one launch.  Returns a float64 (C, 8) tensor on the GPU: a, b,
@@ -1472,15 +1464,10 @@ def boot_calib(counts, order, conf, offs, lens, n_units, bins):
     1 .. CALIB_MAX_BINS.  Returns int64 tensors wsum, wpos, csum (n_rep, C, M) and bnum (n_rep, C); csum and bnum hold the kernel's
     uint64 (read them as such: .numpy().view(np.uint64)).  ValueError before any launch: offsets / lengths that do not fit the order
     array, a conf of another length, bins outside 1 .. CALIB_MAX_BINS."""
-    require_cuda(counts, order, conf)
-    assert counts.dtype == torch.int32 and counts.dim() == 2 and counts.stride(1) == 1 and counts.shape[1] >= n_units, \
-        "counts: int32 (n_rep, >= n_units) rows"
-    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), "order: contiguous int32"
+    require_cuda(conf)
     assert conf.dtype == torch.int32 and conf.dim() == 1 and conf.is_contiguous(), "conf: contiguous int32"
-    offs, lens, bins = [int(v) for v in offs], [int(v) for v in lens], int(bins)
-    n_cls, n_rep = len(lens), counts.shape[0]
-    if len(offs) != n_cls or any(n < 0 or o < 0 or o + n > order.numel() for o, n in zip(offs, lens)):
-        raise ValueError("boot_calib: offsets %s / lengths %s do not fit an order array of %d entries" % (offs, lens, order.numel()))
+    bins = int(bins)
+    ld, n_rep, n_cls, offs, lens = _class_lists("boot_calib", counts, order, offs, lens, n_units)
     if conf.numel() != order.numel():
         raise ValueError("boot_calib: %d confidences for %d entries" % (conf.numel(), order.numel()))
     if not 1 <= bins <= CALIB_MAX_BINS:
@@ -1491,28 +1478,20 @@ def boot_calib(counts, order, conf, offs, lens, n_units, bins):
     bnum = torch.empty(n_rep, n_cls, dtype=torch.int64, device=counts.device)
     if n_rep == 0 or n_cls == 0:
         return wsum.long(), wpos.long(), csum, bnum
-    ld = counts.stride(0) if n_rep > 1 else counts.shape[1]
-    check(lib().cx_boot_calib(ptr(counts), ld, n_rep, ptr(order), ptr(conf), (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens), n_cls,
-                              bins, ptr(wsum), ptr(wpos), ptr(csum), ptr(bnum), int(n_units), stream_ptr()), "cx_boot_calib")
+    check(lib().cx_boot_calib(ptr(counts), ld, n_rep, ptr(order), ptr(conf), offs, lens, n_cls, bins, ptr(wsum), ptr(wpos), ptr(csum),
+                              ptr(bnum), int(n_units), stream_ptr()), "cx_boot_calib")
     return wsum.long() & 0xffffffff, wpos.long() & 0xffffffff, csum, bnum      # the kernel's unsigned values
 
 
 # ---- DeLong / Obuchowski variance of the AUROC (delong.hip; chexpert_amd/metrics.py composes them and states them in numpy) ----
-DELONG_MAX_ROWS, DELONG_WG_ENTRIES, DELONG_TILE = 128, 16384, 32    # CX_DELONG_MAX_ROWS, CX_DELONG_WG_ENTRIES, CX_DELONG_TILE of the header
-
-
 def delong_place(order, offs, lens, n_units, out=None):
     """cx_delong_place: the unit sums of the doubled placements.  order / offs / lens: what boot_auc takes (metrics.bootstrap_plan builds
     them).  Returns an int64 (4 C, n_units) tensor on the GPU, rows 4c .. 4c+3 = (sum of X2 over the unit's positives, their number, sum
     of Y2 over its negatives, their number) of class c; a class with lens[c] == 0 gives zeros.  `out`: an int64 (4 C, >= n_units) tensor
     with unit column stride whose first n_units columns are written (zeroed first) and returned; the columns behind them are left
     untouched.  A workgroup walks DELONG_WG_ENTRIES entries of a list."""
-    require_cuda(order)
-    assert order.dtype == torch.int32 and order.dim() == 1 and order.is_contiguous(), "order: contiguous int32"
-    offs, lens, n_units = [int(v) for v in offs], [int(v) for v in lens], int(n_units)
-    n_cls = len(lens)
-    if n_cls < 1 or len(offs) != n_cls or any(n < 0 or o < 0 or o + 2 * n > order.numel() for o, n in zip(offs, lens)):
-        raise ValueError("delong_place: offsets %s / lengths %s do not fit an order array of %d entries" % (offs, lens, order.numel()))
+    n_units = int(n_units)
+    _, _, n_cls, offs, lens = _class_lists("delong_place", None, order, offs, lens, n_units, per_class=2, min_classes=1)
     if not 1 <= n_units <= BOOT_MAX_UNITS:
         raise ValueError("delong_place: %d units (1 .. 2^24 are supported)" % n_units)
     if out is None:
@@ -1520,8 +1499,7 @@ def delong_place(order, offs, lens, n_units, out=None):
     require_cuda(out)
     assert out.dtype == torch.int64 and out.dim() == 2 and out.shape[0] == 4 * n_cls and out.shape[1] >= n_units and out.stride(1) == 1 \
         and (out.shape[0] == 1 or out.stride(0) >= n_units), "out: int64 (4 C, >= n_units) rows"
-    check(lib().cx_delong_place(ptr(order), (C.c_int64 * n_cls)(*offs), (C.c_int32 * n_cls)(*lens), n_cls, n_units, ptr(out),
-                                out.stride(0), stream_ptr()), "cx_delong_place")
+    check(lib().cx_delong_place(ptr(order), offs, lens, n_cls, n_units, ptr(out), out.stride(0), stream_ptr()), "cx_delong_place")
     return out[:, :n_units]
 
 

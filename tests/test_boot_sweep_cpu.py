@@ -299,7 +299,7 @@ def test_command_line_file_name_and_nothing_without_the_flag(tmp_path):
 
     from chexpert_amd import cli
     for tag, want in (("eval_results_step_300", "metrics_ci_step_300.json"), ("eval_results_ensemble", "metrics_ci_ensemble.json")):
-        assert cli.metrics_ci_name(tag) == want and want != cli.auc_ci_name(tag)
+        assert cli.report_name(tag, "metrics_ci") == want and want != cli.report_name(tag, "auc_ci")
         assert not fnmatch.fnmatch(want, "eval_results*") and not want.startswith("eval_results")      # --plot_roc globs that prefix
     s, t = _case(20, 5, 1)
     # without the option, and without --bootstrap, nothing is computed (no GPU is touched: this test runs without one) or written

@@ -223,7 +223,7 @@ def test_command_line_file_name_groups_and_nothing_without_the_flag(tmp_path):
 
     from chexpert_amd import cli
     for tag, want in (("eval_results_step_300", "auc_ci_step_300.json"), ("eval_results_ensemble", "auc_ci_ensemble.json")):
-        assert cli.auc_ci_name(tag) == want
+        assert cli.report_name(tag, "auc_ci") == want
         assert not fnmatch.fnmatch(want, "eval_results*") and not want.startswith("eval_results")      # --plot_roc globs that prefix
     # --bootstrap 0: nothing is computed (no GPU is touched: this test runs without one) and nothing is written
     a = cli.parse_args(["--evaluate", "--output_dir", str(tmp_path)])

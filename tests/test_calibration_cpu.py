@@ -207,8 +207,8 @@ def test_cli_flags_parse_and_the_exclusive_pair_errors(tmp_path, capsys):
         with pytest.raises(SystemExit):
             cli.parse_args(bad)
     capsys.readouterr()
-    assert cli.calibration_name("eval_results_step_5") == "calibration_step_5.json"
-    assert not cli.calibration_name("eval_results_ensemble", "reliability", ".png").startswith("eval_results")
+    assert cli.report_name("eval_results_step_5", "calibration") == "calibration_step_5.json"
+    assert not cli.report_name("eval_results_ensemble", "reliability", ".png").startswith("eval_results")
     # nothing asked for: nothing computed or written
     assert cli.write_calibration(d, "eval_results_step_0", None, None) is None
     # the json round trip (string class keys) gives the same calibrated logits

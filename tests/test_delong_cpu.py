@@ -242,7 +242,7 @@ def test_command_line_flag_config_round_trip_and_file_name(tmp_path):
     b = cli.parse_args(["--load_config", str(path)])
     assert b.delong is True and b.bootstrap_unit == "patient" and b.bootstrap_alpha == 0.1
     for tag, want in (("eval_results_step_300", "delong_step_300.json"), ("eval_results_ensemble", "delong_ensemble.json")):
-        assert cli.delong_name(tag) == want
+        assert cli.report_name(tag, "delong") == want
         assert not fnmatch.fnmatch(want, "eval_results*") and not want.startswith("eval_results")      # --plot_roc globs that prefix
     # without --delong: nothing is computed (no GPU is touched: this test runs without one) and nothing is written
     a = cli.parse_args(["--evaluate_single_model", "--output_dir", str(tmp_path / "out")])
