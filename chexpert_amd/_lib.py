@@ -195,6 +195,11 @@ SIGNATURES = {
     "cx_pool_head_bwd": [_vp] * 13 + [_i] * 8 + [_vp],
     "cx_pool_head_bwd_f32": [_vp] * 13 + [_i] * 8 + [_vp],
     "cx_pool_p_grad": [_vp] * 5 + [_i, _i, _vp],
+    "cx_csra_head_fwd": [_vp] * 10 + [_i] * 6 + [_vp],
+    "cx_csra_head_fwd_f32": [_vp] * 10 + [_i] * 6 + [_vp],
+    "cx_csra_head_bwd": [_vp] * 18 + [C.c_longlong] + [_i] * 8 + [_vp],
+    "cx_csra_head_bwd_f32": [_vp] * 18 + [C.c_longlong] + [_i] * 8 + [_vp],
+    "cx_csra_bwd_scratch": [_i] * 4,
     "cx_gap_affine_act": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_int64, _vp],
     "cx_gap_affine_act_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_int64, _vp],
     "cx_se_fwd": [_vp] * 7 + [_i, _i, _i, _vp],
@@ -260,7 +265,8 @@ def lib():
         for name, args in SIGNATURES.items():
             fn = getattr(l, name)
             fn.argtypes = args
-            fn.restype = C.c_char_p if name in ("cx_error_string", "cx_last_kernel") else C.c_int
+            fn.restype = C.c_char_p if name in ("cx_error_string", "cx_last_kernel") else \
+                C.c_longlong if name == "cx_csra_bwd_scratch" else C.c_int
         if l.cx_abi_version() != 10:
             raise RuntimeError("chexpert_amd: ABI version mismatch")
         _lib = l

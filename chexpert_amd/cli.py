@@ -64,6 +64,15 @@
                         checkpoint of another pooling than the average carries `pool_state`; --restore, --evaluate_*, --visualize and predict.py read the kind from it, a
                         --pool that names another kind is refused.  Grad-CAM and --cam_classes assume the average: --visualize on
                         another pooling draws the --saliency figures only
+  --head KIND           the head of the network (FusedNet.set_head, csrc/csra_head.hip): linear (default: activation, pool, classifier) or
+                        csra, class-specific residual attention: the classifier at every pixel, the score map pooled per class by its
+                        mean plus --csra_lambda L (default 0.1) times its softmax-weighted mean at temperature --csra_T T (default 1);
+                        every --model, with --fused_optimizer --graph and more than one rank; it stands on the average pool (not
+                        with --pool max / lse / gem).  The checkpoint of a csra run carries `head_state`; --restore, --evaluate_*,
+                        --visualize and predict.py read the head from it, and --head linear is then refused.  A checkpoint of a
+                        linear-head run may be restored into --head csra (the keys are equal: fine-tuning).  --visualize
+                        --cam_classes on a csra model writes vis/csra_maps_lowres.npy (N, 2, K, h, w): the scores and the attention
+                        of the requested classes (heads.class_maps)
   --cam_classes [C ...] with --visualize: class-specific maps (gradcam.class_cam) of the 'vis' subset for these class indices (no value
                         or `all`: every class): vis/class_cam_lowres.npy (N, K, h, w) and one vis/classcam_<ident>_step_<N>.png per image
   --saliency METHOD     with --visualize: full-resolution, class-specific pixel attributions (chexpert_amd/saliency.py) of the 'vis' subset:
@@ -239,6 +248,11 @@ def build_parser():
                         "maximum, log-sum-exp with sharpness --pool_r, or the generalised mean with the trained exponent --pool_p")
     p.add_argument("--pool_r", type=float, default=None, metavar="R", help="with --pool lse: the sharpness r > 0 (default 10)")
     p.add_argument("--pool_p", type=float, default=None, metavar="P", help="with --pool gem: the exponent's start in [1, 16] (default 3)")
+    p.add_argument("--head", default=None, choices=["linear", "csra"],
+                   help="head of the network (FusedNet.set_head; default: the checkpoint's, else linear): csra applies the classifier at "
+                        "every pixel and pools the score map per class (class-specific residual attention)")
+    p.add_argument("--csra_lambda", type=float, default=None, metavar="L", help="with --head csra: the attention term's weight >= 0 (default 0.1)")
+    p.add_argument("--csra_T", type=float, default=None, metavar="T", help="with --head csra: the softmax temperature > 0 (default 1)")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -343,6 +357,13 @@ def parse_args(argv=None):
     except ValueError as e:
         parser.error(str(e))
     why = visualize_needs_avg(args, pool["kind"] if pool else "avg")
+    if why:
+        parser.error(why)
+    try:
+        head = resolve_head(args, pool)
+    except ValueError as e:
+        parser.error(str(e))
+    why = visualize_needs_linear(args, head["kind"] if head else "linear")
     if why:
         parser.error(why)
     return args
@@ -700,6 +721,74 @@ def check_checkpoint_pool(ck, model, path):
         raise ValueError("checkpoint %s was trained with --pool %s, the model was built with --pool %s" % (path, kind, model.pool_kind))
 
 
+def resolve_head(args, pool=None):
+    """--head / --csra_lambda / --csra_T checked before anything runs: None when --head is absent (the checkpoint's head, else linear),
+    or the keywords of FusedNet.set_head (lam / T None where the flag is absent: the checkpoint's, else the defaults).  The two numbers
+    belong to --head csra, which stands on the average pool (`pool`: resolve_pool's dict); ValueError otherwise."""
+    from .heads import DEFAULT_LAMBDA, DEFAULT_T, check_head
+    kind, lam, T = getattr(args, "head", None), getattr(args, "csra_lambda", None), getattr(args, "csra_T", None)
+    if (lam is not None or T is not None) and kind != "csra":
+        raise ValueError("--csra_lambda and --csra_T belong to --head csra: pass --head csra with them")
+    if kind is None:
+        return None
+    try:
+        check_head(kind, DEFAULT_LAMBDA if lam is None else lam, DEFAULT_T if T is None else T)
+    except ValueError as e:
+        raise ValueError("--head: %s" % e)
+    if kind == "csra" and pool is not None and pool["kind"] != "avg":
+        raise ValueError("--head csra stands on the average pool: not with --pool %s" % pool["kind"])
+    return {"kind": kind, "lam": lam, "T": T}
+
+
+def head_for_checkpoint(head, ck_head):
+    """The keywords of set_head for a model that takes a checkpoint's weights.  The checkpoint's `head_state` (none: linear) names its
+    head; --head linear on a csra checkpoint is refused.  --head csra on a linear checkpoint is the fine-tuning case (the keys are
+    equal; lambda and T come from the command line).  On a csra checkpoint lambda and T are the checkpoint's unless the flags give them."""
+    from .heads import DEFAULT_LAMBDA, DEFAULT_T
+    ck_head = ck_head or {}
+    ck_kind = ck_head.get("kind", "linear")
+    if head is not None and head["kind"] != ck_kind and ck_kind != "linear":
+        raise ValueError("--head %s contradicts the checkpoint, which was trained with --head %s: drop the flag, or pass the "
+                         "checkpoint's" % (head["kind"], ck_kind))
+    kind = head["kind"] if head is not None else ck_kind
+    if kind != "csra":
+        return {"kind": kind}
+    pick = lambda key, default: next(v for v in ((head or {}).get(key), ck_head.get(key), default) if v is not None)     # noqa: E731
+    return {"kind": "csra", "lam": pick("lam", DEFAULT_LAMBDA), "T": pick("T", DEFAULT_T)}
+
+
+def restore_head(args, head, pool_kind="avg"):
+    """What make_model hands set_head: --head without --restore; with --restore the head_state of the checkpoint file (of the first
+    checkpoint of a folder), checked against the flag (head_for_checkpoint) and against the pooling."""
+    path = args.restore
+    if path and os.path.isdir(path):
+        files = sorted(f for f in os.listdir(path) if f.startswith("checkpoint") and f.endswith(".pt"))
+        path = os.path.join(path, files[0]) if files else None
+    ck_head = torch.load(path, map_location="cpu").get("head_state") if path and os.path.isfile(path) else None
+    out = head_for_checkpoint(head, ck_head)
+    if out["kind"] == "csra" and pool_kind != "avg":
+        raise ValueError("--head csra stands on the average pool: the checkpoint pools with --pool %s" % pool_kind)
+    return out
+
+
+def check_checkpoint_head_kind(ck, model, path):
+    """A csra checkpoint is refused by a linear-head model (ValueError); a linear checkpoint loads into either (the keys are equal)."""
+    kind = (ck.get("head_state") or {}).get("kind", "linear")
+    if kind != "linear" and kind != model.head_kind:
+        raise ValueError("checkpoint %s was trained with --head %s, the model was built with --head %s" % (path, kind, model.head_kind))
+
+
+def visualize_needs_linear(args, kind):
+    """Why --visualize cannot draw what was asked for on a model with head `kind` (None: it can).  Grad-CAM reads the head as pool +
+    classifier; a csra model has its own maps (--cam_classes: heads.class_maps) and the saliency maps."""
+    if kind == "linear" or not getattr(args, "visualize", False):
+        return None
+    if getattr(args, "cam_classes", None) is None and getattr(args, "saliency", None) is None:
+        return ("--visualize draws Grad-CAM maps, which assume the linear head: with --head %s pass --cam_classes (its score and "
+                "attention maps) or --saliency" % kind)
+    return None
+
+
 def visualize_needs_avg(args, kind):
     """Why --visualize cannot draw what was asked for on a model that pools with `kind` (None: it can).  Grad-CAM and the class
     maps read the head as an average; the saliency maps (--saliency) work with every pooling, and are then the only figures."""
@@ -860,9 +949,9 @@ def model_weights(ck, args, path=""):
     return ck["state_dict"]
 
 
-def make_model(args, device, pool=None):
+def make_model(args, device, pool=None, head=None):
     """Model zoo and optimiser wiring of chexpert.py:461-502.  pool: the keywords of FusedNet.set_pool (None: the average), applied
-    before the optimiser is built -- GeM's exponent is one of its parameters."""
+    before the optimiser is built -- GeM's exponent is one of its parameters.  head: the keywords of FusedNet.set_head (None: linear)."""
     from . import optim as O
     from .models import densenet121
     name = args.model
@@ -871,7 +960,7 @@ def make_model(args, device, pool=None):
     group_options(args)
     sched = None
     n_out = head_width(args)                                 # (three logits per finding under --uncertain multiclass)
-    pool = pool or {}
+    pool, head = pool or {}, head or {}
 
     def ex():                                                # the constructor's keyword arguments, once `model` exists
         return fused_optimizer_kwargs(args, model)
@@ -879,7 +968,7 @@ def make_model(args, device, pool=None):
         model = densenet121(pretrained=args.pretrained)
         model.classifier = nn.Linear(model.classifier.in_features, n_out)
         nn.init.constant_(model.classifier.bias, 0)
-        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool)
+        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
         opt = O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)
         return model, opt, None
     if name in ("aadensenet121", "densenet121_attn_aug"):      # chexpert.py:474-480 (README row name accepted too)
@@ -887,7 +976,7 @@ def make_model(args, device, pool=None):
         size = args.resize or 320
         model = DenseNet(32, (6, 12, 24, 16), 64, num_classes=n_out,
                          attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
-        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool)
+        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
         if fused:
             return model, O.FusedSGDNesterov(model, lr=args.lr, **ex()), "fused"
         opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, nesterov=True)
@@ -896,11 +985,11 @@ def make_model(args, device, pool=None):
         from .models import resnet152
         model = resnet152(pretrained=args.pretrained)
         model.fc = nn.Linear(model.fc.in_features, n_out)
-        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool)
+        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
         return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
     if "efficientnet" in name:                                # chexpert.py:496-500
         from .models import construct_model
-        model = construct_model(name, n_classes=n_out).storage_dtype(args.dtype).to(device).set_pool(**pool)
+        model = construct_model(name, n_classes=n_out).storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
         if fused:
             return model, O.FusedRMSprop(model, lr=args.lr, decay=args.lr_decay_factor, **ex()), "fused"
         opt = torch.optim.RMSprop(model.parameters(), lr=args.lr, momentum=0.9, eps=0.001)
@@ -910,7 +999,7 @@ def make_model(args, device, pool=None):
         size = args.resize or 320
         model = ResNet(Bottleneck, [3, 8, 36, 3], num_classes=n_out,
                        attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
-        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool)
+        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
         return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
     raise RuntimeError("Model architecture not supported.")
 
@@ -984,6 +1073,7 @@ def restore(args, model, optimizer, scheduler, device, multiclass=False):
     ck = torch.load(args.restore, map_location=device)
     check_checkpoint_head(ck, multiclass, args.restore)
     check_checkpoint_pool(ck, model, args.restore)
+    check_checkpoint_head_kind(ck, model, args.restore)
     model.load_state_dict(model_weights(ck, args, args.restore))
     args.step = ck["global_step"]
     if args.train:
@@ -1035,6 +1125,7 @@ def main(argv=None):
     focus = focus_options(args)
     multiclass = multiclass_options(args)
     pool = resolve_pool(args)
+    head = resolve_head(args, pool)
     if world > 1:
         # the process group comes first, before anything touches the GPU; one rank per GPU over RCCL ("nccl"), or ranks sharing
         # a device over gloo when the box has fewer GPUs than ranks (tests)
@@ -1097,11 +1188,15 @@ def main(argv=None):
         why = visualize_needs_avg(args, pool["kind"])
         if why:
             raise ValueError(why)
+        head = restore_head(args, head, pool["kind"])      # the checkpoint's head; --head linear on a csra checkpoint is refused here
+        why = visualize_needs_linear(args, head["kind"])
+        if why:
+            raise ValueError(why)
     except ValueError:
         if train_loader is not None:
             train_loader.close()
         raise
-    model, optimizer, scheduler = make_model(args, device, pool)
+    model, optimizer, scheduler = make_model(args, device, pool, head)
     restored_loss = None
     if args.restore and os.path.isfile(args.restore):
         try:
@@ -1284,6 +1379,8 @@ def main(argv=None):
                                 "avg_auc": M.mean_auc(res), "state_dict": model.state_dict()}
                         if model.pool_kind != "avg":  # (a checkpoint without it is the average's: the keys of before)
                             ckpt["pool_state"] = model.pool_state()
+                        if model.head_kind != "linear":
+                            ckpt["head_state"] = model.head_state()
                         if ema_sd is not None:        # beside the live weights, which restore continues from
                             ckpt["ema_state_dict"] = ema_sd
                         if aucm is not None:          # the auxiliary scalars are trained state: restore continues from them
@@ -1310,6 +1407,7 @@ def main(argv=None):
             ck = torch.load(os.path.join(args.restore, c), map_location=device)
             check_checkpoint_head(ck, multiclass, c)
             check_checkpoint_pool(ck, model, c)
+            check_checkpoint_head_kind(ck, model, c)
             model.load_state_dict(model_weights(ck, args, c))
             o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, multiclass)
             outs.append(o)
@@ -1336,7 +1434,9 @@ def main(argv=None):
         imgs, labels, scores, masks, class_maps, sal_maps = [], [], [], [], [], []
         model.eval()
         attn_layers = [m for m in model.modules() if type(m).__name__ == "AAConv2d"]
-        avg_pool = model.pool_kind == "avg"
+        csra = model.head_kind == "csra"       # (its figures: the score and attention maps of --cam_classes, and the saliency maps)
+        avg_pool = model.pool_kind == "avg" and not csra
+        csra_maps = []
         for x, tg, idx in batches(valid_ds, flat, args.batch_size, False):
             xd = x.to(device)
             if clahe is not None:                # the figures show what the network saw
@@ -1346,7 +1446,11 @@ def main(argv=None):
                 scores.append(model(xd).float().cpu())
             if avg_pool:                         # (another pooling: the saliency maps are the figures, visualize_needs_avg)
                 masks.append(grad_cam(model, xd).float().cpu())
-            if cam_classes is not None:         # the raw low-resolution relu(M): up-sampled maps of 14 classes would be hundreds of MB
+            if cam_classes is not None and csra:
+                from .heads import class_maps as head_maps
+                sc_map, at_map, _ = head_maps(model, xd)
+                csra_maps.append(torch.stack([sc_map[:, cam_classes], at_map[:, cam_classes]], 1).cpu())
+            elif cam_classes is not None:       # the raw low-resolution relu(M): up-sampled maps of 14 classes would be hundreds of MB
                 class_maps.append(class_cam(model, xd, cam_classes, normalize=False, upsample=False)[0].cpu())
             if sal is not None:                 # float interface: whitened, three identical channels (as the attention figures below)
                 xf = ((xd.float().div(255.0) - vis.MEAN) / vis.STD).expand(-1, 3, -1, -1) if xd.dtype == torch.uint8 else xd.float()
@@ -1365,7 +1469,12 @@ def main(argv=None):
                                   groups, args.output_dir, getattr(args, "step", 0))
             np.save(os.path.join(args.output_dir, "vis", "grad_cam.npy"), cam.numpy())
             print("grad-cam maps:", tuple(cam.shape), "figures:", len(files))
-        if cam_classes is not None:
+        if cam_classes is not None and csra:
+            csra_maps = torch.cat(csra_maps)
+            os.makedirs(os.path.join(args.output_dir, "vis"), exist_ok=True)
+            np.save(os.path.join(args.output_dir, "vis", "csra_maps_lowres.npy"), csra_maps.numpy())
+            print("csra score / attention maps:", tuple(csra_maps.shape))
+        elif cam_classes is not None:
             class_maps = torch.cat(class_maps)
             files = vis.visualize_classes(imgs.numpy(), labels.numpy(), scores.numpy(), class_maps.numpy(), ["synthetic/%d" % i for i in flat],
                                           names, cam_classes, args.output_dir, getattr(args, "step", 0))

@@ -120,6 +120,7 @@ class FusedNet(nn.Module):
         self._loss = Loss()
         self._pool_kind = "avg"          # set_pool(): "gem" adds the parameter pool_p, "lse" the buffer pool_r
         self._pool_locked = False        # a fused optimiser has been built over the parameters
+        self._head_kind = "linear"       # set_head(): "csra" adds the buffer head_attn = [lambda, T]
 
     def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
                  alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None):
@@ -194,6 +195,8 @@ class FusedNet(nn.Module):
         average and refuse another kind.  Returns self."""
         from ..pooling import check_pool
         kind, r, p = check_pool(kind, r, p)
+        if kind != "avg" and self._head_kind == "csra":
+            raise ValueError("set_pool(%r): the csra head (set_head) pools its score map itself and stands on the average pool" % (kind,))
         if self._pool_bound():
             raise RuntimeError("set_pool() must be called before the engine has bound the parameters (before the first forward and "
                                "before a fused optimiser is built): the pooling parameter is part of the flat parameter buffer")
@@ -233,9 +236,61 @@ class FusedNet(nn.Module):
         return self.set_pool(kind, r=d["r"]) if kind == "lse" and d.get("r") is not None else self.set_pool(kind)
 
     def require_avg_pool(self, what):
-        """class_cam, the Grad-CAM hooks and the channel-padded twin read the head as an average."""
+        """class_cam, the Grad-CAM hooks and the channel-padded twin read the head as an average in front of the classifier."""
         if self._pool_kind != "avg":
             raise NotImplementedError("%s assumes the global average pool: this model pools with set_pool(%r)" % (what, self._pool_kind))
+        if self._head_kind != "linear":
+            raise NotImplementedError("%s assumes the linear head: this model has set_head(%r) (its maps: heads.class_maps)"
+                                      % (what, self._head_kind))
+
+    # ---- the head: activation -> pool -> classifier ("linear"), or the classifier at every pixel, pooled per class ("csra")
+    def set_head(self, kind="linear", lam=0.1, T=1.0):
+        """The head of the network: "linear" (the default: activation, global pool, classifier; the kernels it always ran, untouched)
+        or "csra", class-specific residual attention (Zhu & Wu, ICCV 2021): the classifier is applied at every pixel of the last
+        feature map and the score map s is pooled per class, logit = bias + mean_p s + lam * sum_p softmax_p(T s) s; the definition
+        stands in chexpert_amd/heads.py.  It is the same nn.Linear under the same state_dict keys, and lam = 0 is the linear head as
+        a function, so a checkpoint of a linear-head model loads into a csra model.  "csra" registers the buffer `head_attn`, an fp32
+        (2,) device tensor [lam, T] that the kernels read (not trained, not part of the state_dict: head_state() carries it; a
+        captured step sees `model.head_attn[0] = 0.2`).  Call it BEFORE the engine binds the parameters -- before the first forward,
+        and before a fused optimiser is built --: afterwards it raises RuntimeError.  An invalid kind, lam < 0, T <= 0 or a
+        non-finite value is a ValueError that changes nothing, as is "csra" on a model whose set_pool is not the average, or with
+        more than 64 outputs.  class_cam, the Grad-CAM hook path and the channel-padded CIFAR DenseNet-BC refuse a csra model;
+        heads.class_maps gives its score and attention maps.  Returns self."""
+        from ..heads import MAX_CLASSES, check_head
+        kind, lam, T = check_head(kind, lam, T)
+        if kind == "csra" and self._pool_kind != "avg":
+            raise ValueError("set_head('csra') stands on the average pool: this model pools with set_pool(%r)" % (self._pool_kind,))
+        if kind == "csra" and self._n_classes() > MAX_CLASSES:
+            raise ValueError("set_head('csra') takes at most %d outputs (this classifier has %d)" % (MAX_CLASSES, self._n_classes()))
+        if self._pool_bound():
+            raise RuntimeError("set_head() must be called before the engine has bound the parameters (before the first forward and "
+                               "before a fused optimiser is built): a bound engine has chosen its head kernels")
+        dev = next(self.parameters()).device
+        self._buffers.pop("head_attn", None)
+        self._non_persistent_buffers_set.discard("head_attn")
+        self._head_kind = kind
+        if kind == "csra":
+            self.register_buffer("head_attn", torch.tensor([lam, T], dtype=torch.float32, device=dev), persistent=False)
+        return self
+
+    @property
+    def head_kind(self):
+        return self._head_kind
+
+    def head_state(self):
+        """What a checkpoint keeps beside the state_dict to rebuild the head: {kind, lam, T} (lam and T None for "linear")."""
+        if self._head_kind != "csra":
+            return {"kind": self._head_kind, "lam": None, "T": None}
+        lam, T = (float(v) for v in self.head_attn.tolist())
+        return {"kind": "csra", "lam": lam, "T": T}
+
+    def load_head_state(self, d):
+        """Restores head_state() (None or {}: the linear head).  Returns self."""
+        d = d or {}
+        kind = d.get("kind", "linear")
+        if kind == "csra" and d.get("lam") is not None and d.get("T") is not None:
+            return self.set_head(kind, lam=d["lam"], T=d["T"])
+        return self.set_head(kind)
 
     def named_parameters(self, prefix="", recurse=True, remove_duplicate=True):
         """nn.Module's order with `pool_p` moved to the end: backward produces the gradients from the end of the flat buffer to its
@@ -596,6 +651,34 @@ class FusedEngine:
             done(m.pool_p)
         return ops.pool_head_bwd(dpooled, ws.pooled, ws.pool_aux if kind != "max" else None, m.pool_param(), x, sc, sh, mean, rstd,
                                  e_scale, g, S1, S2, act=act, kind=kind, stat_rows=stat_rows)
+
+    # ---- the csra head (FusedNet.set_head): csra_head_fwd in the place of pool + classifier, csra_head_bwd in the place of head_bwd +
+    # the pool's backward; g / S1 / S2 leave as the average's backward leaves them
+    def head_kind(self):
+        return getattr(self.model, "head_kind", "linear")
+
+    def _csra_fwd(self, ws, x, sc, sh, m, fc, act):
+        """ws.logits from the last feature map x; ws.csra_s (the score map) and ws.csra_stat stay for the way back and for class_maps."""
+        B, H, W, _ = x.shape
+        n = fc.out_features
+        if getattr(ws, "csra_s", None) is None:
+            ws.csra_s = torch.empty(B, n, H * W, dtype=torch.float32, device=self.device)
+            ws.csra_stat = torch.empty(B, n, ops.CSRA_STAT, dtype=torch.float32, device=self.device)
+            ws.csra_scratch = None
+        ws.csra_hw = (H, W)
+        ops.csra_head_fwd(x, sc, sh, m, fc.weight, fc.bias, self.model.head_attn, ws.logits, ws.csra_s, ws.csra_stat, act=act)
+
+    def _csra_bwd(self, ws, dlogits, x, sc, sh, m, mean, rstd, e_scale, g, S1, S2, stat_rows, fc, act, done):
+        """The head's backward from dlogits: the classifier's gradients (added where head_bwd adds them, reported to the reducer),
+        g / S1 / S2.  Returns the statistic rows."""
+        G = self.grad_of
+        B, H, W, C = x.shape
+        if ws.csra_scratch is None:
+            ws.csra_scratch = torch.empty(ops.csra_bwd_scratch(B, H * W, C, fc.out_features), dtype=torch.float32, device=self.device)
+        rows = ops.csra_head_bwd(dlogits, ws.csra_s, ws.csra_stat, self.model.head_attn, x, sc, sh, m, mean, rstd, e_scale, fc.weight, g, S1,
+                                 S2, G(fc.weight), G(fc.bias) if fc.bias is not None else None, ws.csra_scratch, act=act, stat_rows=stat_rows)
+        done(fc.weight)
+        return rows
 
     # ---- workspaces
     def acquire(self, B, H, W):

@@ -804,6 +804,57 @@ def pool_p_grad(dpooled, pooled, aux, p, dp):
     check(lib().cx_pool_p_grad(ptr(dpooled), ptr(pooled), ptr(aux), ptr(p), ptr(dp), B, Cc, stream_ptr()), "cx_pool_p_grad")
 
 
+# ---- class-specific residual attention head (csrc/csra_head.hip; the definition: include/chexpert_hip.h, heads.py)
+CSRA_MAX_CLASSES = 64                                       # CX_CSRA_MAX_CLASSES
+CSRA_STAT = 4                                               # floats per (image, class) the forward leaves for the way back
+
+
+def _csra_args(x, m, w, attn, act):
+    require_cuda(x, m, w, attn)
+    B, H, W, Cc, ldx = _nhwc(x)
+    n = w.shape[0]
+    assert act in (POOL_ACT_RELU, POOL_ACT_SWISH)
+    assert tuple(w.shape) == (n, Cc) and w.dtype == torch.float32 and w.is_contiguous()
+    assert attn.dtype == torch.float32 and attn.numel() == 2 and attn.is_contiguous(), "csra_head_*: attn is the fp32 device tensor [lambda, T]"
+    assert m is None or (tuple(m.shape) == (B, Cc) and m.dtype == torch.float32 and m.is_contiguous())
+    return B, H * W, Cc, ldx, n
+
+
+def csra_bwd_scratch(B, HW, Cc, n):
+    """cx_csra_bwd_scratch: the floats of scratch csra_head_bwd needs at this shape."""
+    r = lib().cx_csra_bwd_scratch(B, HW, Cc, n)
+    if r < 0:
+        check(int(r), "cx_csra_bwd_scratch")
+    return int(r)
+
+
+def csra_head_fwd(x, sc, sh, m, w, bias, attn, logits, s, stat, *, act):
+    """cx_csra_head_fwd: s (B,n,HW) fp32 = the classifier w (n,C) at every pixel of act(x*sc + sh) * m (m (B,C) fp32 or None), logits
+    (B,n) = bias + mean_p s + lambda * softmax_p(T s) . s with attn = [lambda, T] in device memory; stat (B,n,4) is what the backward
+    reads."""
+    B, HW, Cc, ldx, n = _csra_args(x, m, w, attn, act)
+    for t, shape in ((logits, (B, n)), (s, (B, n, HW)), (stat, (B, n, CSRA_STAT))):
+        assert tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous()
+    check(_fn("cx_csra_head_fwd", x)(ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(w), ptr(bias), ptr(attn), ptr(logits), ptr(s), ptr(stat), B, HW, Cc,
+                                     ldx, n, act, stream_ptr()), "cx_csra_head_fwd")
+
+
+def csra_head_bwd(dlogits, s, stat, attn, x, sc, sh, m, mean, rstd, e_scale, w, g, S1, S2, dw, db, scratch, *, act, stat_rows=0):
+    """cx_csra_head_bwd: the backward of csra_head_fwd with the contract of gap_relu_bn_bwd (g = e_scale * dz, S1 / S2; stat_rows > 0:
+    one statistic row per image); dw (n,C) and db (n,; or None) are added to, in a fixed order through `scratch` (fp32, at least
+    csra_bwd_scratch floats).  Returns the row count in rows mode."""
+    B, HW, Cc, ldx, n = _csra_args(x, m, w, attn, act)
+    require_cuda(dlogits, s, stat, g, dw, db, scratch)
+    assert tuple(dlogits.shape) == (B, n) and dlogits.dtype == torch.float32 and dlogits.is_contiguous()
+    assert g.dtype == x.dtype and g.shape == x.shape
+    assert dw.numel() == n * Cc and dw.dtype == torch.float32 and dw.is_contiguous() and (db is None or db.numel() == n)
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous()
+    check(_fn("cx_csra_head_bwd", x)(ptr(dlogits), ptr(s), ptr(stat), ptr(attn), ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(mean), ptr(rstd),
+                                     ptr(e_scale), ptr(w), ptr(g), ptr(S1), ptr(S2), ptr(dw), ptr(db), ptr(scratch), scratch.numel(), B, HW,
+                                     Cc, ldx, _nhwc(g)[4], n, act, stat_rows, stream_ptr()), "cx_csra_head_bwd")
+    return lib().cx_last_stat_rows() if stat_rows else None
+
+
 def unpool2_mask(d, x, sc, sh, mean, rstd, e_scale, g, S1, S2, stat_rows=0):
     B, H, W, Cc, ldx = _nhwc(x)
     check(_fn("cx_unpool2_mask", x)(ptr(d), ptr(x), ptr(sc), ptr(sh), ptr(mean), ptr(rstd), ptr(e_scale), ptr(g), ptr(S1), ptr(S2),

@@ -16,7 +16,8 @@ A checkpoint of a `--uncertain multiclass` run (three logits per finding: negati
 classifier's row count: n rows build the usual head, 3n rows the wide one, whose logits are collapsed on the GPU right after every
 forward (loss.collapse_multiclass: z = z_positive - z_negative, sigmoid(z) = p1 / (p0 + p1)); --calibration and --tta then act on z.
 Any other count is an error, and the checkpoints of a folder must agree.  The pooling of the head (chexpert.py --pool) is read from
-the checkpoint's `pool_state` (none: the average); the checkpoints of a folder must agree on it too.
+the checkpoint's `pool_state` (none: the average); the checkpoints of a folder must agree on it too.  The head (chexpert.py --head) is
+read from the checkpoint's `head_state` (none: linear) in the same way.
 """
 import argparse
 import os
@@ -146,14 +147,14 @@ def main(argv=None):
     n = len(ds.attr_names)
     key = "classifier.weight" if args.model == "densenet121" else "fc.weight"
 
-    def build(width, pool_state):
+    def build(width, pool_state, head_state):
         if args.model == "densenet121":
             net = densenet121(pretrained=False)
             net.classifier = nn.Linear(net.classifier.in_features, width)
         else:
             net = resnet152(pretrained=False)
             net.fc = nn.Linear(net.fc.in_features, width)
-        return net.to(device).load_pool_state(pool_state)
+        return net.to(device).load_pool_state(pool_state).load_head_state(head_state)
     if os.path.isdir(args.restore_path):
         files = sorted(os.path.join(args.restore_path, f) for f in os.listdir(args.restore_path)
                        if f.startswith("checkpoint") and f.endswith(".pt"))
@@ -173,9 +174,13 @@ def main(argv=None):
     for f in files:
         ck = torch.load(f, map_location=device)
         sd, pool_kind = ck["state_dict"], (ck.get("pool_state") or {}).get("kind", "avg")
+        head_kind = (ck.get("head_state") or {}).get("kind", "linear")
         w = head_is_multiclass(sd, key, n, f)
         if model is None:                   # the first checkpoint's head decides; the others of a folder must agree
-            model, wide = build(n * (3 if w else 1), ck.get("pool_state")), w
+            model, wide = build(n * (3 if w else 1), ck.get("pool_state"), ck.get("head_state")), w
+        elif head_kind != model.head_kind:
+            raise ValueError("the checkpoints of %s disagree: %s has the %s head, %s the %s head" % (args.restore_path, files[0], model.head_kind,
+                                                                                                f, head_kind))
         elif pool_kind != model.pool_kind:
             raise ValueError("the checkpoints of %s disagree: %s pools with %s, %s with %s" % (args.restore_path, files[0], model.pool_kind,
                                                                                           f, pool_kind))

@@ -1038,6 +1038,51 @@ int cx_pool_head_bwd_f32(const float* dpooled, const float* pooled, const float*
                          const float* sc, const float* sh, const float* mean, const float* rstd, const float* e_scale, void* g,
                          float* S1, float* S2, int B, int HW, int C, int ldx, int ldg, int act, int kind, int stat_rows, void* stream);
 
+/* ---- class-specific residual attention head (csrc/csra_head.hip; FusedNet.set_head("csra"); chexpert_amd/heads.py states the same
+ * in numpy float64).  The classifier is applied at every pixel and the score map is pooled per class (CSRA; Zhu & Wu, ICCV 2021).
+ * For image b, a[b,p,c] = act(x[b,p,c] sc[c] + sh[c]) m[b,c], act = CX_POOL_ACT_RELU or CX_POOL_ACT_SWISH, m the optional
+ * per-(image, channel) multiplier (the EfficientNet head's Dropout mask; NULL: 1), W (n, C), bias (n,) or NULL, lam_T = the device
+ * pointer to [lambda, T] (lambda >= 0, T > 0; read by the kernels, so a captured step sees a changed value):
+ *
+ *   s[b,k,p]   = sum_c W[k,c] a[b,p,c]                     (no bias: the softmax does not see it)
+ *   w[b,k,p]   = softmax over p of T s[b,k,p]              (relative to max_p s: a score of 1e4 stays finite)
+ *   att[b,k]   = sum_p w[b,k,p] s[b,k,p]
+ *   logit[b,k] = bias[k] + mean_p s[b,k,p] + lambda att[b,k]
+ *
+ *   ds[b,k,p]  = dlogit[b,k] (1/HW + lambda w[b,k,p] (1 + T (s[b,k,p] - att[b,k])))
+ *   da[b,p,c]  = m[b,c] sum_k ds[b,k,p] W[k,c],   dz = da act'(z),   g = e_scale dz,   S1 = sum dz,   S2 = sum dz (x - mean) rstd
+ *   dW[k,c]   += sum_{b,p} ds[b,k,p] a[b,p,c],    db[k] += sum_b dlogit[b,k]
+ *
+ * lambda = 0 is the average head (cx_head_fwd) as a function; the scores are not divided by |W_k| and the bias is kept, one head,
+ * no T = infinity branch.  All sums are fp32 on the VALU: the activated operand is not rounded to bf16.
+ *
+ * cx_csra_head_fwd: x (B, HW, ldx) in the storage type, padding never read; logits (B, n), s (B, n, HW) fp32 and stat (B, n, 4) fp32
+ * = [max_p s, 1 / sum_p exp(T (s - max)), att - max, 0], which the backward reads.
+ * cx_csra_head_bwd: the contract of cx_gap_relu_bn_bwd / cx_pool_head_bwd: g in the storage type at pitch ldg, padding untouched;
+ * stat_rows == 0: fp32 atomics into S1 / S2 (C each); stat_rows > 0: row b of S1 / S2 = the sums of image b, plain stores,
+ * cx_last_stat_rows() returns B, CX_ESTATROWS with nothing written below B rows.  dW (n, C) and db (n,; may be NULL) are ADDED to,
+ * like cx_head_bwd's, from per-group partial sums in `scratch` added in a fixed order: no atomics on dW / db, and in rows mode two
+ * calls on the same inputs give equal bits in every output.  scratch: scratch_len floats, at least cx_csra_bwd_scratch(B, HW, C, n)
+ * (= B HW n' + groups n C with n' = n rounded up to 16 / 32 / 64 and groups <= 128); a smaller one is CX_EUNSUPPORTED (there is no
+ * other path).  The contents of scratch are undefined afterwards.
+ * Checks, before any launch: CX_EINVAL a NULL operand (m, bias, db may be NULL) or an unknown act; CX_ESHAPE n < 1, a size <= 0, C or
+ * a pitch % 8 (bf16 storage) / % 4 (fp32 storage), a pitch below C; CX_EUNSUPPORTED n > CX_CSRA_MAX_CLASSES or the scratch too
+ * small; CX_EALIGN x, g or scratch not 16-byte aligned.  Additive entry points of ABI 10.                                       */
+#define CX_CSRA_MAX_CLASSES 64
+int cx_csra_head_fwd(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, const float* lam_T,
+                     float* logits, float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream);
+int cx_csra_head_bwd(const float* dlogits, const float* s, const float* stat, const float* lam_T, const void* x, const float* sc,
+                     const float* sh, const float* m, const float* mean, const float* rstd, const float* e_scale, const float* W, void* g,
+                     float* S1, float* S2, float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg,
+                     int n, int act, int stat_rows, void* stream);
+int cx_csra_head_fwd_f32(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias,
+                         const float* lam_T, float* logits, float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream);
+int cx_csra_head_bwd_f32(const float* dlogits, const float* s, const float* stat, const float* lam_T, const void* x, const float* sc,
+                         const float* sh, const float* m, const float* mean, const float* rstd, const float* e_scale, const float* W, void* g,
+                         float* S1, float* S2, float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx,
+                         int ldg, int n, int act, int stat_rows, void* stream);
+long long cx_csra_bwd_scratch(int B, int HW, int C, int n);      /* floats; CX_ESHAPE / CX_EUNSUPPORTED as above */
+
 /* ---- fp32 storage mode (CX_DT_F32): the element-wise kernels of the DenseNet path with fp32 activation tensors (same arguments,
  * `const void*` tensors are fp32, pitches in elements), the fp32 weight table ([tap][O][I] fp32; descriptors with stem = 1 give
  * [49][O][4]) and the fp32 image layouts.  cx_conv_gemm / cx_conv_wgrad take CxConv.dtype / CxWgrad.dtype = CX_DT_F32.          */
