@@ -53,13 +53,13 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* tile, int pitch, int k0, i
   return cx_join_tr(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base)), __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + 4 * pitch)));
 }
 
-// BC = buffer channels per workgroup: 64 (256 threads, two workgroups per CU) or 128 (512 threads, one per CU: dZ is re-read by
-// half as many channel tiles, for the layers with many input channels)
-template <int PRO, bool ACC, int BC>
-__global__ __launch_bounds__(BC * 4, BC == 64 ? 2 : 1) void pw_bwd_kernel(const CxConv p, float* __restrict__ dw, const int M,
-                                                                         const int c_tiles, const int tiles_per_split,
-                                                                         float* __restrict__ slab, const int dw_ld) {
-  constexpr int NT = BC * 4;
+// BC = buffer channels per workgroup: 64 (256 threads, two workgroups per CU).  Slices of fewer than 32 channels take this kernel;
+// wider ones take pw_bwd2_kernel below.
+template <int PRO, bool ACC>
+__global__ __launch_bounds__(256, 2) void pw_bwd_kernel(const CxConv p, float* __restrict__ dw, const int M,
+                                                       const int c_tiles, const int tiles_per_split,
+                                                       float* __restrict__ slab, const int dw_ld) {
+  constexpr int BC = 64, NT = 256;
   constexpr int W_BYTES = BC * PITCH;
   constexpr int COEF_BYTES = (5 * BC + 3 * KD) * 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -111,8 +111,8 @@ __global__ __launch_bounds__(BC * 4, BC == 64 ? 2 : 1) void pw_bwd_kernel(const 
 
   // input gradient: wave = (pixel sub-tile pw, 64-channel half ch); weight gradient: two 32x32 tiles of dW per wave
   const int pw = wave & 3, ch = wave >> 2;
-  const int wn_[2] = {BC == 64 ? (wave >> 1) * 2 : (wave & 3), BC == 64 ? (wave >> 1) * 2 + 1 : (wave & 3)};      // n sub-tiles
-  const int wc_[2] = {BC == 64 ? (wave & 1) : (wave >> 2) * 2, BC == 64 ? (wave & 1) : (wave >> 2) * 2 + 1};      // c sub-tiles
+  const int wn_[2] = {(wave >> 1) * 2, (wave >> 1) * 2 + 1};    // n sub-tiles
+  const int wc_[2] = {wave & 1, wave & 1};                      // c sub-tiles
   f32x16 accw[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -222,20 +222,11 @@ __global__ __launch_bounds__(BC * 4, BC == 64 ? 2 : 1) void pw_bwd_kernel(const 
     // ---- weight gradient: dW[n][c] += sum over the 128 pixels of the tile (k = pixel, transposing LDS reads)
 #pragma unroll
     for (int kk = 0; kk < BM / 16; ++kk) {
-      if (BC == 64) {                               // one c sub-tile, two n sub-tiles
-        const bf16x8 bfr = tr_frag(Xh + wc_[0] * XH_BYTES, XH_PITCH, kk * 16, 0, lane);
+      const bf16x8 bfr = tr_frag(Xh + wc_[0] * XH_BYTES, XH_PITCH, kk * 16, 0, lane);    // one c sub-tile, two n sub-tiles
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const bf16x8 af = tr_frag(At, PITCH, kk * 16, wn_[i] * 32, lane);
-          accw[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, accw[i], 0, 0, 0);
-        }
-      } else {                                      // one n sub-tile, two c sub-tiles
-        const bf16x8 af = tr_frag(At, PITCH, kk * 16, wn_[0] * 32, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const bf16x8 bfr = tr_frag(Xh + wc_[i] * XH_BYTES, XH_PITCH, kk * 16, 0, lane);
-          accw[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, accw[i], 0, 0, 0);
-        }
+      for (int i = 0; i < 2; ++i) {
+        const bf16x8 af = tr_frag(At, PITCH, kk * 16, wn_[i] * 32, lane);
+        accw[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, accw[i], 0, 0, 0);
       }
     }
     __syncthreads();                              // both LDS tiles free for the next pixel tile
@@ -893,12 +884,13 @@ int launch_bwd2(const CxConv& p, float* dw, const int dw_ld, float* scratch, lon
   return slab ? cx_dw_reduce_ld(dw, slab, total, splits, p.N, dw_ld, st) : 0;
 }
 
-template <int PRO, bool ACC, int BC>
+template <int PRO, bool ACC>
 int launch_bwd_bc(const CxConv& p, float* dw, const int dw_ld, float* scratch, long long scratch_floats, hipStream_t st) {
+  constexpr int BC = 64;
   const long long M = (long long)p.B * p.Ho * p.Wo;
   const int m_tiles = (int)((M + BM - 1) / BM);
   const int c_tiles = (p.N + BC - 1) / BC;
-  int splits = (BC == 64 ? 1024 : 512) / c_tiles;    // ~4 (2) workgroups per CU in the grid
+  int splits = 1024 / c_tiles;                       // ~4 workgroups per CU in the grid
   if (splits < 1) splits = 1;
   if (splits > m_tiles) splits = m_tiles;
   const int tps = (m_tiles + splits - 1) / splits;
@@ -907,14 +899,13 @@ int launch_bwd_bc(const CxConv& p, float* dw, const int dw_ld, float* scratch, l
   if (const int e = stat_rows_check(p, splits)) return e;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_bwd_kernel<PRO, ACC, BC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_bwd_kernel<PRO, ACC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr = true;
   }
   const size_t total = (size_t)KD * p.N;
   float* slab = dw_slab(scratch, scratch_floats, splits, (long long)total);
-  CX_KTAG("pw_bwd_kernel<%d, %s, %d>", PRO, ACC ? "true" : "false", BC);
-  hipLaunchKernelGGL((pw_bwd_kernel<PRO, ACC, BC>), dim3(c_tiles * splits), dim3(BC * 4), smem, st, p, dw, (int)M, c_tiles, tps, slab, dw_ld);
+  CX_KTAG("pw_bwd_kernel<%d, %s, 64>", PRO, ACC ? "true" : "false");      // (the tag bench.py and profiles/ key this kernel by)
+  hipLaunchKernelGGL((pw_bwd_kernel<PRO, ACC>), dim3(c_tiles * splits), dim3(256), smem, st, p, dw, (int)M, c_tiles, tps, slab, dw_ld);
   if (const int e = launch_status()) return e;
   return slab ? cx_dw_reduce_ld(dw, slab, total, splits, p.N, dw_ld, st) : 0;
 }
@@ -923,10 +914,8 @@ template <int PRO, bool ACC>
 int launch_bwd(const CxConv& p, float* dw, const int dw_ld, float* scratch, long long scratch_floats, hipStream_t st) {
   static const int force = cx_diag_int("CX_PW_BWD_BC", 0);
   const bool wide = force ? force == 128 : p.N >= 32;   // measured crossover (round 2: the v2 kernel also wins on the 64- and 96-channel layers)
-  static const int v1 = cx_diag_int("CX_PW_BWD_V1", 0);   // diagnostic: the round-1 kernel
-  if (wide && !v1) return launch_bwd2<PRO, ACC>(p, dw, dw_ld, scratch, scratch_floats, st);
-  return wide ? launch_bwd_bc<PRO, ACC, 128>(p, dw, dw_ld, scratch, scratch_floats, st)
-              : launch_bwd_bc<PRO, ACC, 64>(p, dw, dw_ld, scratch, scratch_floats, st);
+  return wide ? launch_bwd2<PRO, ACC>(p, dw, dw_ld, scratch, scratch_floats, st)
+              : launch_bwd_bc<PRO, ACC>(p, dw, dw_ld, scratch, scratch_floats, st);
 }
 
 }  // namespace

@@ -1,12 +1,13 @@
 // Forward of the dense-layer bottleneck 1x1 convolution, K <= 256 input channels (round 4):
 //   Y[m][0:128] = relu(X[m][0:K]*scale + shift) . W^T   (+ per-channel sum / sum of squares of the values as stored)
-// torchvision `_DenseLayer.norm1 -> relu1 -> conv1` as restated at /root/reference/models/attn_aug_conv.py:13 (forward).
+// torchvision `_DenseLayer.norm1 -> relu1 -> conv1` as restated at models/attn_aug_conv.py:13 (forward).
 //
-// Why a second kernel.  conv1x1_fwd.hip feeds the MFMA's B operand straight from global memory: a lane loads 16 bytes of ITS
-// pixel, so one wave-instruction touches 16-byte pieces of 32 different pixels and every 128-byte line is completed by four
-// instructions; its stores are 32-byte pieces likewise.  Measured (scratch/segbench.hip, profiles/r04_segbench.txt), a bare
-// stream in that shape runs at 3.3-4.2 TB/s against 4.9-5.0 TB/s when a wave-instruction covers whole rows -- and the kernel sat at
-// 3.2 TB/s.  Here every global access is a whole row: a workgroup (512 threads, one per CU) walks 64-pixel tiles; the tile's
+// Every global access covers a whole row.  The layer is a stream (K <= 256 against 128 outputs), and the shape of the accesses
+// sets its speed: feeding the MFMA's B operand straight from global memory (a lane loads 16 bytes of ITS pixel, so one
+// wave-instruction touches 16-byte pieces of 32 different pixels, every 128-byte line is completed by four instructions, and the
+// stores are 32-byte pieces likewise) is a fragmentary shape.  Measured (scratch/segbench.hip, profiles/r04_segbench.txt), a bare
+// stream in that shape runs at 3.3-4.2 TB/s against 4.9-5.0 TB/s when a wave-instruction covers whole rows -- and a kernel built
+// that way sat at 3.2 TB/s.  So here a workgroup (512 threads, one per CU) walks 64-pixel tiles; the tile's
 // activations are requested two tiles ahead in the staging shape (consecutive lanes = consecutive 16-byte chunks of a pixel row),
 // normalised on the way into a double-buffered LDS image, multiplied from there (weights resident in LDS), and the output tile goes
 // back through LDS to leave as whole 256-byte rows.  Two barriers per tile; statistics as per-lane registers reduced once per
@@ -228,11 +229,9 @@ int launch_fwd2_n(const CxConv& p, hipStream_t st) {
 
 }  // namespace
 
-// Called by cx_conv_gemm (through cx_try_pw_fwd) after its argument validation; *handled = false leaves the call to the older kernels.
+// Called by cx_conv_gemm after its argument validation; *handled = false leaves the call to the kernels tried after this one.
 int cx_try_pw_fwd2(const CxConv& p, hipStream_t st, bool* handled) {
   *handled = false;
-  static const int on = cx_diag_int("CX_PW_FWD2", 1);            // diagnostic builds: 0 = conv1x1_fwd.hip
-  if (!on) return 0;
   if (p.mode != CX_MODE_CONV || p.kh != 1 || p.kw != 1 || p.stride != 1 || p.pad != 0 || p.tstride > 1) return 0;
   // (K > 256 in the same design, K walked in 128-channel chunks, was measured in three forms and not kept: profiles/r04_pw_fwd3_rejected.txt)
   if (p.epilogue != CX_EPI_STORE || p.accumulate || p.N != NO || (p.K % 32) || p.K < 32 || p.K > 256) return 0;

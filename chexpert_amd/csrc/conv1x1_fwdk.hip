@@ -1,4 +1,4 @@
-// Bottleneck 1x1 forward for K > 256 (weights do not fit LDS, see conv1x1_fwd.hip): Y[m][0:128] = relu(X[m][0:K]*sc + sh) . W^T.
+// Bottleneck 1x1 forward for K > 256 (weights do not fit LDS, see conv1x1_fwd2.hip): Y[m][0:128] = relu(X[m][0:K]*sc + sh) . W^T.
 //
 // On the small maps of dense blocks 3-4 the generic kernel is latency bound: a workgroup walks K in 32-channel steps and
 // every step waits for loads issued one step earlier (31 dependent round trips at K = 992, ~3 us each).  Same tile
@@ -169,14 +169,14 @@ __global__ __launch_bounds__(256, 2) void pw_fwdk_kernel(const CxConv p, const i
   }
 }
 
-// Pipelined form: the same tile with BK = 64 channels per step and the operands of the next D steps in flight in D register sets
+// Pipelined form: the same tile with BK = 64 channels per step and the operands of the next D = 2 steps in flight in D register sets
 // (4 + 4 sixteen-byte loads per thread and step).  The single-set kernel above overlaps one step's loads with one step's MFMAs
 // (~0.25 us against 2-3 us of load latency under load): a workgroup spends most of a step waiting.  Here a step's loads have D
 // steps of time; the loop body is unrolled D-fold so every register set is indexed statically and the wait counts are exact
 // (loads beyond the last step are harmless re-reads of it: unconditional requests, see DESIGN.md lesson 15).
-template <int PRO, int D>
+template <int PRO>
 __global__ __launch_bounds__(256, 2) void pw_fwdp_kernel(const CxConv p, const int M) {
-  constexpr int BK = 64;
+  constexpr int BK = 64, D = 2;
   constexpr int PITCH = BK * 2 + 16;                 // 144 B
   constexpr int CPR = BK / 8;                        // 8 chunks per row
   constexpr int RPP = 256 / CPR;                     // 32 rows per pass
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void pw_fwdp_kernel(const CxConv p, const i
   }
 }
 
-template <int PRO, int D>
+template <int PRO>
 int launch_fwdp(const CxConv& p, hipStream_t st) {
   const long long M = (long long)p.B * p.Ho * p.Wo;
   const int m_tiles = (int)((M + BM - 1) / BM);
@@ -348,13 +348,13 @@ int launch_fwdp(const CxConv& p, hipStream_t st) {
   const size_t smem = (size_t)2 * p.K * 4 + (stage > epi ? stage : epi) + 2 * BN * 4;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_fwdp_kernel<PRO, D>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_fwdp_kernel<PRO>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     attr = true;
   }
   if (smem > 80 * 1024) return CX_ESHAPE;
   if (const int e = stat_rows_check(p, m_tiles)) return e;
-  CX_KTAG("pw_fwdp_kernel<%d, %d>", PRO, D);
-  hipLaunchKernelGGL((pw_fwdp_kernel<PRO, D>), dim3(m_tiles), dim3(256), smem, st, p, (int)M);
+  CX_KTAG("pw_fwdp_kernel<%d, 2>", PRO);              // (the tag bench.py and profiles/ key this kernel by)
+  hipLaunchKernelGGL((pw_fwdp_kernel<PRO>), dim3(m_tiles), dim3(256), smem, st, p, (int)M);
   return launch_status();
 }
 
@@ -379,7 +379,7 @@ int launch_fwdk(const CxConv& p, hipStream_t st) {
 
 }  // namespace
 
-// Called by cx_conv_gemm after its argument validation and after cx_try_pw_fwd; *handled = false -> generic kernel.
+// Called by cx_conv_gemm after its argument validation and after cx_try_pw_fwd2; *handled = false -> generic kernel.
 int cx_try_pw_fwdk(const CxConv& p, hipStream_t st, bool* handled) {
   *handled = false;
   if (p.mode != CX_MODE_CONV || p.kh != 1 || p.kw != 1 || p.stride != 1 || p.pad != 0 || p.tstride > 1) return 0;
@@ -390,13 +390,8 @@ int cx_try_pw_fwdk(const CxConv& p, hipStream_t st, bool* handled) {
   *handled = true;
   // measured at bs = 256 (scratch/bench_pw.py fwd, one box): two sets in flight 85 -> 75 us at K = 992 on 20x20 maps, 55 -> 50 at
   // K = 512, nothing below that and nothing on 10x10 maps (one tile per CU there: the step is bound by its barrier-separated
-  // stage / MFMA phases with one wave per SIMD, not by load latency); three and four sets are no better than two
-  static const int pipe = cx_diag_int("CX_FWDK_PIPE", 2);     // 0: the single-set kernel
-  if (pipe == 2 && p.K % 32 == 0 && p.K >= 512)
-    return p.prologue == CX_PRO_AFFINE_RELU ? launch_fwdp<CX_PRO_AFFINE_RELU, 2>(p, st) : launch_fwdp<CX_PRO_NONE, 2>(p, st);
-  if (pipe == 3 && p.K % 32 == 0 && p.K >= 192)
-    return p.prologue == CX_PRO_AFFINE_RELU ? launch_fwdp<CX_PRO_AFFINE_RELU, 3>(p, st) : launch_fwdp<CX_PRO_NONE, 3>(p, st);
-  if (pipe == 4 && p.K % 32 == 0 && p.K >= 256)
-    return p.prologue == CX_PRO_AFFINE_RELU ? launch_fwdp<CX_PRO_AFFINE_RELU, 4>(p, st) : launch_fwdp<CX_PRO_NONE, 4>(p, st);
+  // stage / MFMA phases with one wave per SIMD, not by load latency); three and four sets were no better than two
+  if (p.K % 32 == 0 && p.K >= 512)
+    return p.prologue == CX_PRO_AFFINE_RELU ? launch_fwdp<CX_PRO_AFFINE_RELU>(p, st) : launch_fwdp<CX_PRO_NONE>(p, st);
   return p.prologue == CX_PRO_AFFINE_RELU ? launch_fwdk<128, CX_PRO_AFFINE_RELU>(p, st) : launch_fwdk<128, CX_PRO_NONE>(p, st);
 }

@@ -413,7 +413,7 @@ int cx_try_strip_fwd(const CxConv& p, hipStream_t st, bool* handled);     // con
 int cx_try_ring_dgrad(const CxConv& p, hipStream_t st, bool* handled);    // conv3x3_ring.hip
 int cx_try_strip_dgrad(const CxConv& p, hipStream_t st, bool* handled);
 int cx_try_pw_dgrad(const CxConv& p, hipStream_t st, bool* handled);        // conv1x1_dgrad.hip
-int cx_try_pw_fwd(const CxConv& p, hipStream_t st, bool* handled);          // conv1x1_fwd.hip
+int cx_try_pw_fwd2(const CxConv& p, hipStream_t st, bool* handled);         // conv1x1_fwd2.hip
 int cx_try_pw_fwdk(const CxConv& p, hipStream_t st, bool* handled);         // conv1x1_fwdk.hip
 int cx_try_pw_xs(const CxConv& p, hipStream_t st, bool* handled);           // conv1x1_xs.hip
 int cx_try_stem_fwd(const CxConv& p, hipStream_t st, bool* handled);        // conv_stem.hip
@@ -518,7 +518,7 @@ extern "C" int cx_conv_gemm(const CxConv* pp, void* stream) {
       if (handled) return rc;
       rc = cx_try_pw_dgrad(p, st, &handled);
       if (handled) return rc;
-      rc = cx_try_pw_fwd(p, st, &handled);
+      rc = cx_try_pw_fwd2(p, st, &handled);
       if (handled) return rc;
       rc = cx_try_pw_fwdk(p, st, &handled);
       if (handled) return rc;

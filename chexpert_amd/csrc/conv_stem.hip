@@ -1,5 +1,5 @@
 // Stem convolution (7x7, stride 2, pad 3, 3 -> 64 channels; features.conv0 / conv1 of the reference nets) on the (B,H,W,4) bf16
-// image, persistent and LDS-free on the activation side like conv1x1_fwd.hip.
+// image, persistent and LDS-free on the activation side.
 //
 // K is organised as 7 row-taps x 32 (= 8 input pixels x 4 channels of the row window that starts at column 2*ox - 4; the
 // weights are packed [ky][64][32] with zeros for the pad pixel and the pad channel, cx_pack_weights(stem = 1)).  With the MFMA

@@ -44,7 +44,7 @@ struct DwGeo {
 };
 
 // ---------------------------------------------------------------------------------------------------------------- forward
-template <int K, int S, int TH, int NCQ, bool PIPE_>
+template <int K, int S, int TH, int NCQ>
 __global__ __launch_bounds__(256) void dw_fwd_tile_kernel(const bf16* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ sc, const float* __restrict__ sh,
                                                           bf16* __restrict__ y, float* g1, float* g2, const DwGeo g) {
@@ -74,49 +74,14 @@ __global__ __launch_bounds__(256) void dw_fwd_tile_kernel(const bf16* __restrict
   }
   const int ntiles = g.B * g.tiles_y * g.tiles_x;
   constexpr int NCHUNK = IH * IW * NCQ;
-  // PIPE_ (experiment, CX_DW_PIPE=1): the NEXT tile's source vectors are requested right after the current tile has been staged, so
-  // they travel under its stencil (one tile in registers, at most 8 vectors per thread).  Measured on the B4 shapes: no gain -- the
-  // counters show the kernel waiting on LDS issue (SQ_WAIT_INST_LDS = 70 % of the issue stalls), not on memory.
-  constexpr int NLD = (NCHUNK + 255) / 256;
-  constexpr bool PIPE = PIPE_ && S == 1 && NLD <= 8;
-  U128 pre[PIPE ? NLD : 1];
-  unsigned pre_ok = 0;
-  auto issue = [&](int t) {
-    const int b = t / (g.tiles_y * g.tiles_x), r_ = t - b * g.tiles_y * g.tiles_x;
-    const int ty = r_ / g.tiles_x, tx = r_ - ty * g.tiles_x;
-    const int iy0 = ty * TH * S - PAD, ix0 = tx * TW * S - PAD;
-    pre_ok = 0;
-#pragma unroll
-    for (int u = 0; u < (PIPE ? NLD : 0); ++u) {
-      const int i = u * 256 + tid, p = (i < NCHUNK ? i : tid) / NCQ;
-      const int pr = p / IW, pc = p - pr * IW, iy = iy0 + pr, ix = ix0 + pc;
-      pre_ok |= (cok && iy >= 0 && iy < H && ix >= 0 && ix < W ? 1u : 0u) << u;
-      const int iyc = min(max(iy, 0), H - 1), ixc = min(max(ix, 0), W - 1);
-      pre[u].u = *reinterpret_cast<const uint4*>(x + ((size_t)(b * H + iyc) * W + ixc) * C + ccl);
-    }
-  };
-  if constexpr (PIPE) {
-    if ((int)blockIdx.x < ntiles) issue(blockIdx.x);
-  }
+  // (requesting the NEXT tile's source vectors right after the current tile has been staged, so that they travel under its stencil,
+  // was measured on the B4 shapes: no gain -- the counters show the kernel waiting on LDS issue (SQ_WAIT_INST_LDS = 70 % of the issue
+  // stalls), not on memory)
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int b = t / (g.tiles_y * g.tiles_x), r_ = t - b * g.tiles_y * g.tiles_x;
     const int ty = r_ / g.tiles_x, tx = r_ - ty * g.tiles_x;
     const int oy0 = ty * TH, ox0 = tx * TW, iy0 = oy0 * S - PAD, ix0 = ox0 * S - PAD;
     __syncthreads();                                  // the previous tile has been read (first time: weights staged)
-    if constexpr (PIPE) {
-#pragma unroll
-      for (int u = 0; u < NLD; ++u) {
-        const int i = u * 256 + tid, p = i / NCQ;
-        U128 o;
-        o.u = affine_swish8(pre[u].u, fsc, fsh, act);
-        const unsigned keep = (pre_ok >> u) & 1u ? 0xffffffffu : 0u;
-        o.u.x &= keep; o.u.y &= keep; o.u.z &= keep; o.u.w &= keep;
-        if (i < NCHUNK) *reinterpret_cast<uint4*>(tile + (size_t)p * PP + cq * 16) = o.u;
-      }
-      __syncthreads();
-      const int tn = t + (int)gridDim.x;
-      issue(tn < ntiles ? tn : t);                    // unconditional request (the last tile re-requests itself)
-    } else {
     for (int base = 0; base < NCHUNK; base += 1024) {
       U128 v[4];
       bool ok[4];
@@ -139,7 +104,6 @@ __global__ __launch_bounds__(256) void dw_fwd_tile_kernel(const bf16* __restrict
       }
     }
     __syncthreads();
-    }
     float acc[4][8];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -583,15 +547,8 @@ int launch_cfg(int which, const DwArgs& a, DwGeo g, hipStream_t st) {
   if (which == 0) {
     size_t smem = fwd_smem<K, S, TH, NCQ>();
     if (g.det && smem < 256 * 16 * 4) smem = 256 * 16 * 4;
-    static const bool pipe = cx_diag_int("CX_DW_PIPE", 0) == 1;    // measured: no gain (LDS-issue bound, not latency bound)
-    static bool attr_np = false;
-    if (pipe) {
-      allow_smem(&dw_fwd_tile_kernel<K, S, TH, NCQ, true>, smem, &attr[0]);
-      hipLaunchKernelGGL((dw_fwd_tile_kernel<K, S, TH, NCQ, true>), grid, dim3(256), smem, st, a.x, a.w, a.sc, a.sh, a.y, a.s1, a.s2, g);
-    } else {
-      allow_smem(&dw_fwd_tile_kernel<K, S, TH, NCQ, false>, smem, &attr_np);
-      hipLaunchKernelGGL((dw_fwd_tile_kernel<K, S, TH, NCQ, false>), grid, dim3(256), smem, st, a.x, a.w, a.sc, a.sh, a.y, a.s1, a.s2, g);
-    }
+    allow_smem(&dw_fwd_tile_kernel<K, S, TH, NCQ>, smem, &attr[0]);
+    hipLaunchKernelGGL((dw_fwd_tile_kernel<K, S, TH, NCQ>), grid, dim3(256), smem, st, a.x, a.w, a.sc, a.sh, a.y, a.s1, a.s2, g);
   } else if (which == 1) {
     size_t smem = dgrad_smem<K, S, TH, NCQ>();
     if (g.det && smem < 256 * 16 * 4) smem = 256 * 16 * 4;
