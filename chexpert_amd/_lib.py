@@ -200,6 +200,11 @@ SIGNATURES = {
     "cx_csra_head_bwd": [_vp] * 18 + [C.c_longlong] + [_i] * 8 + [_vp],
     "cx_csra_head_bwd_f32": [_vp] * 18 + [C.c_longlong] + [_i] * 8 + [_vp],
     "cx_csra_bwd_scratch": [_i] * 4,
+    "cx_pcam_head_fwd": [_vp] * 9 + [_i] * 6 + [_vp],
+    "cx_pcam_head_fwd_f32": [_vp] * 9 + [_i] * 6 + [_vp],
+    "cx_pcam_head_bwd": [_vp] * 17 + [C.c_longlong] + [_i] * 8 + [_vp],
+    "cx_pcam_head_bwd_f32": [_vp] * 17 + [C.c_longlong] + [_i] * 8 + [_vp],
+    "cx_pcam_bwd_scratch": [_i] * 4,
     "cx_gap_affine_act": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_int64, _vp],
     "cx_gap_affine_act_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_int64, _vp],
     "cx_se_fwd": [_vp] * 7 + [_i, _i, _i, _vp],
@@ -266,7 +271,7 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = C.c_char_p if name in ("cx_error_string", "cx_last_kernel") else \
-                C.c_longlong if name == "cx_csra_bwd_scratch" else C.c_int
+                C.c_longlong if name in ("cx_csra_bwd_scratch", "cx_pcam_bwd_scratch") else C.c_int
         if l.cx_abi_version() != 10:
             raise RuntimeError("chexpert_amd: ABI version mismatch")
         _lib = l

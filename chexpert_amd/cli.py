@@ -72,7 +72,13 @@
                         --visualize and predict.py read the head from it, and --head linear is then refused.  A checkpoint of a
                         linear-head run may be restored into --head csra (the keys are equal: fine-tuning).  --visualize
                         --cam_classes on a csra model writes vis/csra_maps_lowres.npy (N, 2, K, h, w): the scores and the attention
-                        of the requested classes (heads.class_maps)
+                        of the requested classes (heads.class_maps).
+                        pcam is probabilistic-CAM pooling (Ye et al. 2020): the classifier at every pixel, each per-pixel logit turned
+                        into a probability, the map pooled per class with those probabilities as weights; no hyper-parameter
+                        (--csra_lambda / --csra_T are refused), the average pool only, checkpoints and --restore as for csra.  A
+                        linear-head checkpoint may be restored into --head pcam (the keys are equal), but the function changes, unlike
+                        csra at lambda 0.  --visualize --cam_classes on a pcam model writes vis/pcam_maps_lowres.npy (N, 2, K, h, w),
+                        the probability maps P in [0, 1] and the pooling weights, and one vis/pcam_<ident>_step_<N>.png per image
   --cam_classes [C ...] with --visualize: class-specific maps (gradcam.class_cam) of the 'vis' subset for these class indices (no value
                         or `all`: every class): vis/class_cam_lowres.npy (N, K, h, w) and one vis/classcam_<ident>_step_<N>.png per image
   --saliency METHOD     with --visualize: full-resolution, class-specific pixel attributions (chexpert_amd/saliency.py) of the 'vis' subset:
@@ -248,9 +254,10 @@ def build_parser():
                         "maximum, log-sum-exp with sharpness --pool_r, or the generalised mean with the trained exponent --pool_p")
     p.add_argument("--pool_r", type=float, default=None, metavar="R", help="with --pool lse: the sharpness r > 0 (default 10)")
     p.add_argument("--pool_p", type=float, default=None, metavar="P", help="with --pool gem: the exponent's start in [1, 16] (default 3)")
-    p.add_argument("--head", default=None, choices=["linear", "csra"],
+    p.add_argument("--head", default=None, choices=["linear", "csra", "pcam"],
                    help="head of the network (FusedNet.set_head; default: the checkpoint's, else linear): csra applies the classifier at "
-                        "every pixel and pools the score map per class (class-specific residual attention)")
+                        "every pixel and pools the score map per class (class-specific residual attention); pcam pools it with the "
+                        "per-pixel probabilities as weights (probabilistic-CAM pooling) and gives per-class probability maps")
     p.add_argument("--csra_lambda", type=float, default=None, metavar="L", help="with --head csra: the attention term's weight >= 0 (default 0.1)")
     p.add_argument("--csra_T", type=float, default=None, metavar="T", help="with --head csra: the softmax temperature > 0 (default 1)")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
@@ -735,15 +742,17 @@ def resolve_head(args, pool=None):
         check_head(kind, DEFAULT_LAMBDA if lam is None else lam, DEFAULT_T if T is None else T)
     except ValueError as e:
         raise ValueError("--head: %s" % e)
-    if kind == "csra" and pool is not None and pool["kind"] != "avg":
-        raise ValueError("--head csra stands on the average pool: not with --pool %s" % pool["kind"])
+    if kind != "linear" and pool is not None and pool["kind"] != "avg":
+        raise ValueError("--head %s stands on the average pool: not with --pool %s" % (kind, pool["kind"]))
     return {"kind": kind, "lam": lam, "T": T}
 
 
 def head_for_checkpoint(head, ck_head):
     """The keywords of set_head for a model that takes a checkpoint's weights.  The checkpoint's `head_state` (none: linear) names its
     head; --head linear on a csra checkpoint is refused.  --head csra on a linear checkpoint is the fine-tuning case (the keys are
-    equal; lambda and T come from the command line).  On a csra checkpoint lambda and T are the checkpoint's unless the flags give them."""
+    equal; lambda and T come from the command line).  On a csra checkpoint lambda and T are the checkpoint's unless the flags give them.
+    --head pcam on a linear checkpoint is allowed in the same way (the keys are equal; the function changes); every other
+    contradiction -- linear or csra on a pcam checkpoint, pcam on a csra one -- is refused."""
     from .heads import DEFAULT_LAMBDA, DEFAULT_T
     ck_head = ck_head or {}
     ck_kind = ck_head.get("kind", "linear")
@@ -766,13 +775,17 @@ def restore_head(args, head, pool_kind="avg"):
         path = os.path.join(path, files[0]) if files else None
     ck_head = torch.load(path, map_location="cpu").get("head_state") if path and os.path.isfile(path) else None
     out = head_for_checkpoint(head, ck_head)
-    if out["kind"] == "csra" and pool_kind != "avg":
-        raise ValueError("--head csra stands on the average pool: the checkpoint pools with --pool %s" % pool_kind)
+    if out["kind"] != "linear" and pool_kind != "avg":
+        raise ValueError("--head %s stands on the average pool: the checkpoint pools with --pool %s" % (out["kind"], pool_kind))
+    if out["kind"] == "pcam" and path and os.path.isfile(path) and (ck_head or {}).get("kind", "linear") == "linear":
+        print("--head pcam on a linear-head checkpoint: the weights load (the keys are equal), but the head computes another function "
+              "of them (unlike --head csra at lambda 0): the first losses are not the checkpoint's")
     return out
 
 
 def check_checkpoint_head_kind(ck, model, path):
-    """A csra checkpoint is refused by a linear-head model (ValueError); a linear checkpoint loads into either (the keys are equal)."""
+    """A csra or pcam checkpoint is refused by a model with another head (ValueError); a linear checkpoint loads into every head (the
+    keys are equal)."""
     kind = (ck.get("head_state") or {}).get("kind", "linear")
     if kind != "linear" and kind != model.head_kind:
         raise ValueError("checkpoint %s was trained with --head %s, the model was built with --head %s" % (path, kind, model.head_kind))
@@ -780,7 +793,7 @@ def check_checkpoint_head_kind(ck, model, path):
 
 def visualize_needs_linear(args, kind):
     """Why --visualize cannot draw what was asked for on a model with head `kind` (None: it can).  Grad-CAM reads the head as pool +
-    classifier; a csra model has its own maps (--cam_classes: heads.class_maps) and the saliency maps."""
+    classifier; a csra or pcam model has its own maps (--cam_classes: heads.class_maps) and the saliency maps."""
     if kind == "linear" or not getattr(args, "visualize", False):
         return None
     if getattr(args, "cam_classes", None) is None and getattr(args, "saliency", None) is None:
@@ -1435,8 +1448,9 @@ def main(argv=None):
         model.eval()
         attn_layers = [m for m in model.modules() if type(m).__name__ == "AAConv2d"]
         csra = model.head_kind == "csra"       # (its figures: the score and attention maps of --cam_classes, and the saliency maps)
-        avg_pool = model.pool_kind == "avg" and not csra
-        csra_maps = []
+        pcam = model.head_kind == "pcam"       # (its figures: the probability maps of --cam_classes, and the saliency maps)
+        avg_pool = model.pool_kind == "avg" and not csra and not pcam
+        csra_maps, pcam_up = [], []
         for x, tg, idx in batches(valid_ds, flat, args.batch_size, False):
             xd = x.to(device)
             if clahe is not None:                # the figures show what the network saw
@@ -1446,10 +1460,16 @@ def main(argv=None):
                 scores.append(model(xd).float().cpu())
             if avg_pool:                         # (another pooling: the saliency maps are the figures, visualize_needs_avg)
                 masks.append(grad_cam(model, xd).float().cpu())
-            if cam_classes is not None and csra:
+            if cam_classes is not None and (csra or pcam):
                 from .heads import class_maps as head_maps
                 sc_map, at_map, _ = head_maps(model, xd)
                 csra_maps.append(torch.stack([sc_map[:, cam_classes], at_map[:, cam_classes]], 1).cpu())
+                if pcam:                        # the overlays: P of the requested classes, scaled per map and up-sampled on the GPU
+                    from . import ops
+                    pm = sc_map[:, cam_classes].contiguous()
+                    up = torch.empty(pm.shape[0] * pm.shape[1], 1, xd.shape[2], xd.shape[3], dtype=torch.float32, device=device)
+                    ops.cam_norm_upsample(pm.view(up.shape[0], -1), up, pm.shape[2], pm.shape[3])
+                    pcam_up.append(up.view(pm.shape[0], pm.shape[1], xd.shape[2], xd.shape[3]).half().cpu())
             elif cam_classes is not None:       # the raw low-resolution relu(M): up-sampled maps of 14 classes would be hundreds of MB
                 class_maps.append(class_cam(model, xd, cam_classes, normalize=False, upsample=False)[0].cpu())
             if sal is not None:                 # float interface: whitened, three identical channels (as the attention figures below)
@@ -1469,7 +1489,14 @@ def main(argv=None):
                                   groups, args.output_dir, getattr(args, "step", 0))
             np.save(os.path.join(args.output_dir, "vis", "grad_cam.npy"), cam.numpy())
             print("grad-cam maps:", tuple(cam.shape), "figures:", len(files))
-        if cam_classes is not None and csra:
+        if cam_classes is not None and pcam:
+            csra_maps = torch.cat(csra_maps)
+            files = vis.visualize_classes(imgs.numpy(), labels.numpy(), scores.numpy(), torch.cat(pcam_up).float().numpy(),
+                                          ["synthetic/%d" % i for i in flat], names, cam_classes, args.output_dir, getattr(args, "step", 0),
+                                          prefix="pcam")
+            np.save(os.path.join(args.output_dir, "vis", "pcam_maps_lowres.npy"), csra_maps.numpy())
+            print("pcam probability / weight maps:", tuple(csra_maps.shape), "figures:", len(files))
+        elif cam_classes is not None and csra:
             csra_maps = torch.cat(csra_maps)
             os.makedirs(os.path.join(args.output_dir, "vis"), exist_ok=True)
             np.save(os.path.join(args.output_dir, "vis", "csra_maps_lowres.npy"), csra_maps.numpy())

@@ -15,6 +15,12 @@
 // Every sum of one (image, channel) is formed by one thread in ascending pixel order; the weight gradient leaves as one partial per
 // group of images, which csra_reduce_kernel adds in ascending group order (and db in ascending image order): no atomics on dW / db,
 // two calls give equal bits.
+//
+// Probabilistic-CAM pooling head (PCAM; Ye et al. 2020), FusedNet.set_head("pcam"): the same score map, pooled per class with the
+// per-pixel probabilities sigmoid(s + bias) as weights.  Forward: csra_score_kernel as it is, then pcam_stat_kernel, one wave per
+// (image, class).  Backward: pcam_ds_kernel, one workgroup per image, writes ds and dl_eff = dlogit (1 + r) (the bias sits inside
+// the sigmoid, so db is not the sum of dlogit), then csra_bwd_kernel and csra_reduce_kernel unchanged, the reduce reading dl_eff.  What the stat kernel leaves is
+// relative to the row's largest u = s + bias, as csra's is to max_p s.
 #include <limits.h>
 #include <math.h>
 #include "common.h"
@@ -259,6 +265,79 @@ __global__ __launch_bounds__(256) void csra_reduce_kernel(const float* __restric
   }
 }
 
+// sigmoid(u), sigmoid(-u) and log sigmoid(u) from one exp(-|u|): nothing cancels and nothing overflows
+struct PcSig { float p, q, l; };
+__device__ __forceinline__ PcSig pc_sig(float u) {
+  const float t = expf(-fabsf(u)), inv = 1.f / (1.f + t), hi = inv, lo = t * inv;
+  PcSig r;
+  r.p = u >= 0.f ? hi : lo;
+  r.q = u >= 0.f ? lo : hi;
+  r.l = fminf(u, 0.f) - log1pf(t);
+  return r;
+}
+
+// One wave per (image, class).  u = s + bias, L = log sigmoid(u), w = exp(L - max L) / sum, logit = sum w u.  stat = [max_p u,
+// 1 / sum_p exp(L - max L), logit - max u, bias]: relative to the largest u of the row (L is monotone in u, so max L = L(max u), which
+// the way back recomputes from stat[0]); the bias rides along because the way back has the csra argument list, which has none.
+__global__ __launch_bounds__(256) void pcam_stat_kernel(const float* __restrict__ s, const float* __restrict__ bias, float* __restrict__ logits,
+                                                        float* __restrict__ stat, size_t BN, int n, int HW) {
+  const int lane = threadIdx.x & 63;
+  const size_t idx = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (idx >= BN) return;                                      // (whole waves leave; no barrier below)
+  const float* row = s + idx * HW;
+  const float bk = bias ? bias[idx % n] : 0.f;
+  float mx = -INFINITY;
+  for (int p = lane; p < HW; p += 64) mx = fmaxf(mx, row[p] + bk);
+  mx = cs_wave_max(mx);
+  const float lmx = pc_sig(mx).l;
+  float z = 0.f, t = 0.f;
+  for (int p = lane; p < HW; p += 64) {
+    const float u = row[p] + bk, e = expf(pc_sig(u).l - lmx);
+    z += e;
+    t += e * (u - mx);
+  }
+  z = cs_wave_sum(z);
+  t = cs_wave_sum(t);
+  if (lane == 0) {
+    const float off = t / z;                                  // logit - max u <= 0
+    logits[idx] = mx + off;
+    float* st = stat + idx * CS_STAT;
+    st[0] = mx; st[1] = 1.f / z; st[2] = off; st[3] = bk;
+  }
+}
+
+// One workgroup per image.  ds[(b HW + p) NT + k] = dlogit[b,k] w (1 + q (u - logit)), q = sigmoid(-u), 0 for k >= n, and
+// dl_eff[b,k] = dlogit[b,k] (1 + r), r = sum_p w q (u - logit).  A thread keeps one class (256 % NT == 0) and walks its pixels in
+// ascending order; the 256 / NT partial sums of a class are added in ascending thread order: a fixed order, no atomics.
+__global__ __launch_bounds__(256) void pcam_ds_kernel(const float* __restrict__ dl, const float* __restrict__ s, const float* __restrict__ stat,
+                                                      float* __restrict__ ds, float* __restrict__ dleff, int n, int HW, int NT) {
+  __shared__ float red[256];
+  const size_t b = blockIdx.x;
+  const int k = threadIdx.x % NT, per = 256 / NT;
+  float r = 0.f;
+  if (k < n) {
+    const size_t bk = b * n + k;
+    const float* st = stat + bk * CS_STAT;
+    const float mx = st[0], rz = st[1], off = st[2], bias = st[3], d = dl[bk], lmx = pc_sig(mx).l;
+    for (int p = threadIdx.x / NT; p < HW; p += per) {
+      const float u = s[bk * HW + p] + bias;
+      const PcSig g = pc_sig(u);
+      const float w = expf(g.l - lmx) * rz, t = g.q * ((u - mx) - off);
+      r = fmaf(w, t, r);
+      ds[(b * HW + p) * NT + k] = d * w * (1.f + t);
+    }
+  } else {
+    for (int p = threadIdx.x / NT; p < HW; p += per) ds[(b * HW + p) * NT + k] = 0.f;
+  }
+  red[threadIdx.x] = r;
+  __syncthreads();                                            // (every thread of the workgroup arrives)
+  if (threadIdx.x < n) {
+    float v = 0.f;
+    for (int j = 0; j < per; ++j) v += red[j * NT + threadIdx.x];
+    dleff[b * n + threadIdx.x] = dl[b * n + threadIdx.x] * (1.f + v);
+  }
+}
+
 bool known_act(int act) { return act == CX_POOL_ACT_RELU || act == CX_POOL_ACT_SWISH; }
 template <typename T> bool shape_ok(int B, int HW, int C, int ld) {
   const int q = sizeof(T) == 2 ? 8 : 4;
@@ -283,6 +362,20 @@ int csra_fwd_t(const void* x, const float* sc, const float* sh, const float* m, 
   hipLaunchKernelGGL((csra_score_kernel<T>), dim3((rows + per - 1) / per), dim3(CS_THREADS), 0, as_stream(stream), (const T*)x, sc, sh, m, W, s,
                      rows, HW, C, ldx, n, act);
   hipLaunchKernelGGL(csra_stat_kernel, dim3((BN + 3) / 4), dim3(256), 0, as_stream(stream), s, bias, lam_T, logits, stat, BN, n, HW);
+  return launch_status();
+}
+
+template <typename T>
+int pcam_fwd_t(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, float* logits, float* s,
+               float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
+  if (!x || !sc || !sh || !W || !logits || !s || !stat || !known_act(act)) return CX_EINVAL;
+  if (n < 1 || !shape_ok<T>(B, HW, C, ldx)) return CX_ESHAPE;
+  if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
+  if (!aligned16(x)) return CX_EALIGN;
+  const size_t rows = (size_t)B * HW, per = CS_WAVES * CS_PT, BN = (size_t)B * n;
+  hipLaunchKernelGGL((csra_score_kernel<T>), dim3((rows + per - 1) / per), dim3(CS_THREADS), 0, as_stream(stream), (const T*)x, sc, sh, m, W, s,
+                     rows, HW, C, ldx, n, act);
+  hipLaunchKernelGGL(pcam_stat_kernel, dim3((BN + 3) / 4), dim3(256), 0, as_stream(stream), s, bias, logits, stat, BN, n, HW);
   return launch_status();
 }
 
@@ -324,6 +417,37 @@ int csra_bwd_t(const float* dlogits, const float* s, const float* stat, const fl
   return launch_status();
 }
 
+// csra_bwd_t with pcam_ds_kernel in the place of csra_ds_kernel; scratch = ds | the weight-gradient partials | dl_eff (B n)
+template <typename T>
+int pcam_bwd_t(const float* dlogits, const float* s, const float* stat, const void* x, const float* sc, const float* sh, const float* m,
+               const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1, float* S2,
+               float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n, int act,
+               int stat_rows, void* stream) {
+  if (!dlogits || !s || !stat || !x || !sc || !sh || !mean || !rstd || !e_scale || !W || !g || !S1 || !S2 || !dW || !scratch || !known_act(act))
+    return CX_EINVAL;
+  if (n < 1 || !shape_ok<T>(B, HW, C, ldx) || !shape_ok<T>(B, HW, C, ldg)) return CX_ESHAPE;
+  if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
+  const long long base = scratch_floats(B, HW, C, n);
+  if (scratch_len < base + (long long)B * n) return CX_EUNSUPPORTED;           // refused, no other path
+  if (!aligned16(x) || !aligned16(g) || !aligned16(scratch)) return CX_EALIGN;
+  if (stat_rows > 0) { if (stat_rows < B) return CX_ESTATROWS; cx_tl_stat_rows = B; }
+  const int NT = nt_of(n), GB = group_size(B), groups = (B + GB - 1) / GB, det = stat_rows > 0 ? 1 : 0;
+  const size_t total = (size_t)B * HW * NT, nC = (size_t)n * C;
+  float* ds = scratch;
+  float* part = scratch + total;
+  float* dleff = scratch + base;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(pcam_ds_kernel, dim3(B), dim3(256), 0, st, dlogits, s, stat, ds, dleff, n, HW, NT);
+  if (NT == 16)
+    launch_bwd<T, 16, 4>(ds, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB, groups, st);
+  else if (NT == 32)
+    launch_bwd<T, 32, 2>(ds, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB, groups, st);
+  else
+    launch_bwd<T, 64, 1>(ds, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB, groups, st);
+  hipLaunchKernelGGL(csra_reduce_kernel, dim3((nC + n + 255) / 256), dim3(256), 0, st, part, dleff, dW, db, groups, B, n, nC);
+  return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -354,6 +478,34 @@ long long cx_csra_bwd_scratch(int B, int HW, int C, int n) {
   if (B <= 0 || HW <= 0 || C <= 0 || n < 1) return CX_ESHAPE;
   if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
   return scratch_floats(B, HW, C, n);
+}
+
+int cx_pcam_head_fwd(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, float* logits,
+                     float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
+  return pcam_fwd_t<bf16>(x, sc, sh, m, W, bias, logits, s, stat, B, HW, C, ldx, n, act, stream);
+}
+int cx_pcam_head_fwd_f32(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, float* logits,
+                         float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
+  return pcam_fwd_t<float>(x, sc, sh, m, W, bias, logits, s, stat, B, HW, C, ldx, n, act, stream);
+}
+int cx_pcam_head_bwd(const float* dlogits, const float* s, const float* stat, const void* x, const float* sc, const float* sh, const float* m,
+                     const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1, float* S2, float* dW,
+                     float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n, int act, int stat_rows,
+                     void* stream) {
+  return pcam_bwd_t<bf16>(dlogits, s, stat, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx, ldg, n,
+                          act, stat_rows, stream);
+}
+int cx_pcam_head_bwd_f32(const float* dlogits, const float* s, const float* stat, const void* x, const float* sc, const float* sh,
+                         const float* m, const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1,
+                         float* S2, float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n,
+                         int act, int stat_rows, void* stream) {
+  return pcam_bwd_t<float>(dlogits, s, stat, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx, ldg,
+                           n, act, stat_rows, stream);
+}
+long long cx_pcam_bwd_scratch(int B, int HW, int C, int n) {
+  if (B <= 0 || HW <= 0 || C <= 0 || n < 1) return CX_ESHAPE;
+  if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
+  return scratch_floats(B, HW, C, n) + (long long)B * n;
 }
 
 }  // extern "C"

@@ -120,7 +120,7 @@ class FusedNet(nn.Module):
         self._loss = Loss()
         self._pool_kind = "avg"          # set_pool(): "gem" adds the parameter pool_p, "lse" the buffer pool_r
         self._pool_locked = False        # a fused optimiser has been built over the parameters
-        self._head_kind = "linear"       # set_head(): "csra" adds the buffer head_attn = [lambda, T]
+        self._head_kind = "linear"       # set_head(): "csra" adds the buffer head_attn = [lambda, T]; "pcam" adds nothing
 
     def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
                  alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None):
@@ -195,8 +195,9 @@ class FusedNet(nn.Module):
         average and refuse another kind.  Returns self."""
         from ..pooling import check_pool
         kind, r, p = check_pool(kind, r, p)
-        if kind != "avg" and self._head_kind == "csra":
-            raise ValueError("set_pool(%r): the csra head (set_head) pools its score map itself and stands on the average pool" % (kind,))
+        if kind != "avg" and self._head_kind in ("csra", "pcam"):
+            raise ValueError("set_pool(%r): the %s head (set_head) pools its score map itself and stands on the average pool"
+                             % (kind, self._head_kind))
         if self._pool_bound():
             raise RuntimeError("set_pool() must be called before the engine has bound the parameters (before the first forward and "
                                "before a fused optimiser is built): the pooling parameter is part of the flat parameter buffer")
@@ -255,13 +256,18 @@ class FusedNet(nn.Module):
         and before a fused optimiser is built --: afterwards it raises RuntimeError.  An invalid kind, lam < 0, T <= 0 or a
         non-finite value is a ValueError that changes nothing, as is "csra" on a model whose set_pool is not the average, or with
         more than 64 outputs.  class_cam, the Grad-CAM hook path and the channel-padded CIFAR DenseNet-BC refuse a csra model;
-        heads.class_maps gives its score and attention maps.  Returns self."""
+        heads.class_maps gives its score and attention maps.
+        "pcam" is probabilistic-CAM pooling (Ye et al. 2020): the same score map, pooled per class with the per-pixel probabilities
+        sigmoid(s + bias) as weights, logit = sum_p w (s + bias), w = sigmoid(s + bias) / sum_p sigmoid(s + bias).  It has no
+        hyper-parameter (lam and T are validated and unused), registers no buffer and adds no state_dict key; the ordering rule, the
+        average pool, the 64 outputs and the refusals are csra's; a linear checkpoint loads, but the function changes.
+        heads.class_maps gives its probability maps and pooling weights.  Returns self."""
         from ..heads import MAX_CLASSES, check_head
         kind, lam, T = check_head(kind, lam, T)
-        if kind == "csra" and self._pool_kind != "avg":
-            raise ValueError("set_head('csra') stands on the average pool: this model pools with set_pool(%r)" % (self._pool_kind,))
-        if kind == "csra" and self._n_classes() > MAX_CLASSES:
-            raise ValueError("set_head('csra') takes at most %d outputs (this classifier has %d)" % (MAX_CLASSES, self._n_classes()))
+        if kind != "linear" and self._pool_kind != "avg":
+            raise ValueError("set_head(%r) stands on the average pool: this model pools with set_pool(%r)" % (kind, self._pool_kind))
+        if kind != "linear" and self._n_classes() > MAX_CLASSES:
+            raise ValueError("set_head(%r) takes at most %d outputs (this classifier has %d)" % (kind, MAX_CLASSES, self._n_classes()))
         if self._pool_bound():
             raise RuntimeError("set_head() must be called before the engine has bound the parameters (before the first forward and "
                                "before a fused optimiser is built): a bound engine has chosen its head kernels")
@@ -278,7 +284,7 @@ class FusedNet(nn.Module):
         return self._head_kind
 
     def head_state(self):
-        """What a checkpoint keeps beside the state_dict to rebuild the head: {kind, lam, T} (lam and T None for "linear")."""
+        """What a checkpoint keeps beside the state_dict to rebuild the head: {kind, lam, T} (lam and T None unless kind is "csra")."""
         if self._head_kind != "csra":
             return {"kind": self._head_kind, "lam": None, "T": None}
         lam, T = (float(v) for v in self.head_attn.tolist())
@@ -657,28 +663,54 @@ class FusedEngine:
     def head_kind(self):
         return getattr(self.model, "head_kind", "linear")
 
-    def _csra_fwd(self, ws, x, sc, sh, m, fc, act):
-        """ws.logits from the last feature map x; ws.csra_s (the score map) and ws.csra_stat stay for the way back and for class_maps."""
+    def _map_slots(self, ws, x, n):
+        """The workspace slots of a head that pools a per-pixel score map: ws.csra_s (the score map) and ws.csra_stat stay for the way
+        back and for class_maps; ws.csra_scratch is allocated by the first backward."""
         B, H, W, _ = x.shape
-        n = fc.out_features
         if getattr(ws, "csra_s", None) is None:
             ws.csra_s = torch.empty(B, n, H * W, dtype=torch.float32, device=self.device)
             ws.csra_stat = torch.empty(B, n, ops.CSRA_STAT, dtype=torch.float32, device=self.device)
             ws.csra_scratch = None
         ws.csra_hw = (H, W)
+
+    def _map_scratch(self, ws, x, n, size):
+        B, H, W, C = x.shape
+        if ws.csra_scratch is None:
+            ws.csra_scratch = torch.empty(size(B, H * W, C, n), dtype=torch.float32, device=self.device)
+        return ws.csra_scratch
+
+    def _csra_fwd(self, ws, x, sc, sh, m, fc, act):
+        """ws.logits from the last feature map x."""
+        self._map_slots(ws, x, fc.out_features)
         ops.csra_head_fwd(x, sc, sh, m, fc.weight, fc.bias, self.model.head_attn, ws.logits, ws.csra_s, ws.csra_stat, act=act)
 
     def _csra_bwd(self, ws, dlogits, x, sc, sh, m, mean, rstd, e_scale, g, S1, S2, stat_rows, fc, act, done):
         """The head's backward from dlogits: the classifier's gradients (added where head_bwd adds them, reported to the reducer),
         g / S1 / S2.  Returns the statistic rows."""
         G = self.grad_of
-        B, H, W, C = x.shape
-        if ws.csra_scratch is None:
-            ws.csra_scratch = torch.empty(ops.csra_bwd_scratch(B, H * W, C, fc.out_features), dtype=torch.float32, device=self.device)
+        scratch = self._map_scratch(ws, x, fc.out_features, ops.csra_bwd_scratch)
         rows = ops.csra_head_bwd(dlogits, ws.csra_s, ws.csra_stat, self.model.head_attn, x, sc, sh, m, mean, rstd, e_scale, fc.weight, g, S1,
-                                 S2, G(fc.weight), G(fc.bias) if fc.bias is not None else None, ws.csra_scratch, act=act, stat_rows=stat_rows)
+                                 S2, G(fc.weight), G(fc.bias) if fc.bias is not None else None, scratch, act=act, stat_rows=stat_rows)
         done(fc.weight)
         return rows
+
+    def _pcam_fwd(self, ws, x, sc, sh, m, fc, act):
+        """_csra_fwd for set_head("pcam"): the same workspace slots, no [lambda, T]."""
+        self._map_slots(ws, x, fc.out_features)
+        ops.pcam_head_fwd(x, sc, sh, m, fc.weight, fc.bias, ws.logits, ws.csra_s, ws.csra_stat, act=act)
+
+    def _pcam_bwd(self, ws, dlogits, x, sc, sh, m, mean, rstd, e_scale, g, S1, S2, stat_rows, fc, act, done):
+        """_csra_bwd for set_head("pcam"): the bias gradient is the kernel's sum_b dlogit (1 + r).  Returns the statistic rows."""
+        G = self.grad_of
+        scratch = self._map_scratch(ws, x, fc.out_features, ops.pcam_bwd_scratch)
+        rows = ops.pcam_head_bwd(dlogits, ws.csra_s, ws.csra_stat, x, sc, sh, m, mean, rstd, e_scale, fc.weight, g, S1, S2, G(fc.weight),
+                                 G(fc.bias) if fc.bias is not None else None, scratch, act=act, stat_rows=stat_rows)
+        done(fc.weight)
+        return rows
+
+    def _map_head(self):
+        """(forward, backward) of a head that pools a per-pixel score map, None for the linear head."""
+        return {"csra": (self._csra_fwd, self._csra_bwd), "pcam": (self._pcam_fwd, self._pcam_bwd)}.get(self.head_kind())
 
     # ---- workspaces
     def acquire(self, B, H, W):

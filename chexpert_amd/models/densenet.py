@@ -562,8 +562,8 @@ class _Engine(FusedEngine):
         then the classifier."""
         m, blk = self.model, self.plan.blocks[bi]
         self._bn_block(ws, blk, blk, m.features.norm5, self._count(ws.buf[bi]), fresh)
-        if self.head_kind() == "csra":              # set_head: the classifier at every pixel, pooled per class
-            return self._csra_fwd(ws, ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), None, m.classifier, ops.POOL_ACT_RELU)
+        if self.head_kind() in ("csra", "pcam"):    # set_head: the classifier at every pixel, pooled per class
+            return self._map_head()[0](ws, ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), None, m.classifier, ops.POOL_ACT_RELU)
         if self.pool_kind() != "avg":
             self._pool_fwd(ws, ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), ops.POOL_ACT_RELU)
             return ops.linear_fwd(ws.pooled, m.classifier.weight, m.classifier.bias, ws.logits)
@@ -681,7 +681,7 @@ class _Engine(FusedEngine):
         m, v, G = self.model, self._v, self.grad_of
         bi = len(self.blocks) - 1
         blk, ct = self.plan.blocks[bi], self.plan.blocks[bi].C
-        csra = self.head_kind() == "csra"
+        csra = self.head_kind() in ("csra", "pcam")
         if not csra:
             dpooled = torch.empty(ws.B, ct, dtype=torch.float32, device=self.device)
             ops.head_bwd(dlogits, ws.pooled, m.classifier.weight, G(m.classifier.weight), G(m.classifier.bias) if
@@ -689,7 +689,7 @@ class _Engine(FusedEngine):
         if ws.B * ct > self.SLAB:
             raise RuntimeError("batch too large for the statistic-row scratch (B*C = %d > %d)" % (ws.B * ct, self.SLAB))
         if csra:
-            rows = self._csra_bwd(ws, dlogits, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), None, v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
+            rows = self._map_head()[1](ws, dlogits, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), None, v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
                                   ws.gbuf[bi], *self._ew(ws, ct, bwd=True, rows=self.SLAB // ct), m.classifier, ops.POOL_ACT_RELU, done)
         elif self.pool_kind() != "avg":
             rows = self._pool_bwd(ws, dpooled, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),

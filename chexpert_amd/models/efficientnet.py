@@ -276,14 +276,14 @@ class _Engine(FusedEngine):
         Sh = self.bn[id(m.head[1])]
         rows = ops.conv_gemm(xin, self.w_fwd(m.head[0]), ws.yh, N=1280, **self._sp(ws, Sh))
         self._bn_coef(ws, m.head[1], B * ws.hw_last[0] * ws.hw_last[1], train, rows)
-        if self.head_kind() == "csra":              # set_head: Swish, Dropout mask and classifier at every pixel, pooled per class
+        if self.head_kind() in ("csra", "pcam"):    # set_head: Swish, Dropout mask and classifier at every pixel, pooled per class
             p_do = m.head[5].p if train else 0.0
             ws.drop = None
             if p_do > 0.0:
                 ws.drop = torch.empty(B, 1280, dtype=torch.float32, device=self.device)
                 ops.dropout_mask_dev(ws.drop, 1.0 - p_do, self._seed_base(len(self.mb)), self.step_dev)
                 self.last_masks["head"] = ws.drop
-            return self._csra_fwd(ws, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.drop, m.head[6], ops.POOL_ACT_SWISH)
+            return self._map_head()[0](ws, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.drop, m.head[6], ops.POOL_ACT_SWISH)
         if self.pool_kind() != "avg":               # set_pool: the pooling's kernel in the average's place
             self._pool_fwd(ws, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ops.POOL_ACT_SWISH)
         else:
@@ -336,7 +336,7 @@ class _Engine(FusedEngine):
         """Returns the gradient of the last block's output."""
         m, v, G, B = self.model, self._v, self.grad_of, ws.B
         fc, Sh = m.head[6], self.bn[id(m.head[1])]
-        csra = self.head_kind() == "csra"
+        csra = self.head_kind() in ("csra", "pcam")
         if not csra:
             dpool = torch.empty(B, 1280, dtype=torch.float32, device=self.device)
             ops.head_bwd(dlogits, ws.fc_in, fc.weight, G(fc.weight), G(fc.bias), dpool)
@@ -344,7 +344,7 @@ class _Engine(FusedEngine):
                 ops.mul_f32(dpool, ws.drop, dpool)
         dzh = ws.bwd["dze"][:ws.yh.numel()].view(ws.yh.shape)
         if csra:
-            rows = self._csra_bwd(ws, dlogits, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.drop, v(ws, Sh.mean), v(ws, Sh.rstd), v(ws, self.ones, 1280),
+            rows = self._map_head()[1](ws, dlogits, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.drop, v(ws, Sh.mean), v(ws, Sh.rstd), v(ws, self.ones, 1280),
                                   dzh, *self._ew(ws, Sh, bwd=True), fc, ops.POOL_ACT_SWISH, done)
         elif self.pool_kind() != "avg":
             rows = self._pool_bwd(ws, dpool, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), v(ws, Sh.mean), v(ws, Sh.rstd), v(ws, self.ones, 1280), dzh,

@@ -323,8 +323,8 @@ class _Engine(FusedEngine):
                 xin = self._basic_forward(ws, bi, xin)
             else:
                 xin, xin_lo, pending = self._bottleneck_forward(ws, bi, xin, xin_lo, pending)
-        if self.head_kind() == "csra":              # set_head: the classifier at every pixel, pooled per class
-            self._csra_fwd(ws, xin, v(ws, self.ones), v(ws, self.zeros), None, m.fc, ops.POOL_ACT_RELU)
+        if self.head_kind() in ("csra", "pcam"):    # set_head: the classifier at every pixel, pooled per class
+            self._map_head()[0](ws, xin, v(ws, self.ones), v(ws, self.zeros), None, m.fc, ops.POOL_ACT_RELU)
         elif self.pool_kind() != "avg":             # set_pool: the pooling's kernel, then the classifier
             self._pool_fwd(ws, xin, v(ws, self.ones), v(ws, self.zeros), ops.POOL_ACT_RELU)
             ops.linear_fwd(ws.pooled, m.fc.weight, m.fc.bias, ws.logits)
@@ -496,8 +496,8 @@ class _Engine(FusedEngine):
         last = ws.blk[-1]["out"]
         Cl = last.shape[3]
         ones, zeros = v(ws, self.ones, Cl), v(ws, self.zeros, Cl)
-        if self.head_kind() == "csra":
-            return self._csra_bwd(ws, dlogits, last, ones, zeros, None, zeros, ones, ones, ws.bwd["g"][-1], v(ws, self.scratch[0], Cl),
+        if self.head_kind() in ("csra", "pcam"):
+            return self._map_head()[1](ws, dlogits, last, ones, zeros, None, zeros, ones, ones, ws.bwd["g"][-1], v(ws, self.scratch[0], Cl),
                                   v(ws, self.scratch[1], Cl), 0, m.fc, ops.POOL_ACT_RELU, done)
         dpooled = torch.empty(ws.B, Cl, dtype=torch.float32, device=self.device)
         ops.head_bwd(dlogits, ws.pooled, m.fc.weight, G(m.fc.weight), G(m.fc.bias) if m.fc.bias is not None else None, dpooled)

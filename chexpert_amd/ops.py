@@ -855,6 +855,51 @@ def csra_head_bwd(dlogits, s, stat, attn, x, sc, sh, m, mean, rstd, e_scale, w, 
     return lib().cx_last_stat_rows() if stat_rows else None
 
 
+# ---- probabilistic-CAM pooling head (csrc/csra_head.hip): the csra operands without [lambda, T]
+def _pcam_args(x, m, w, act):
+    require_cuda(x, m, w)
+    B, H, W, Cc, ldx = _nhwc(x)
+    n = w.shape[0]
+    assert act in (POOL_ACT_RELU, POOL_ACT_SWISH)
+    assert tuple(w.shape) == (n, Cc) and w.dtype == torch.float32 and w.is_contiguous()
+    assert m is None or (tuple(m.shape) == (B, Cc) and m.dtype == torch.float32 and m.is_contiguous())
+    return B, H * W, Cc, ldx, n
+
+
+def pcam_bwd_scratch(B, HW, Cc, n):
+    """cx_pcam_bwd_scratch: the floats of scratch pcam_head_bwd needs at this shape (csra_bwd_scratch + B n)."""
+    r = lib().cx_pcam_bwd_scratch(B, HW, Cc, n)
+    if r < 0:
+        check(int(r), "cx_pcam_bwd_scratch")
+    return int(r)
+
+
+def pcam_head_fwd(x, sc, sh, m, w, bias, logits, s, stat, *, act):
+    """cx_pcam_head_fwd: s (B,n,HW) fp32 = the classifier w (n,C) at every pixel of act(x*sc + sh) * m (csra_head_fwd's score map),
+    logits (B,n) = sum_p w_p (s_p + bias) with w_p = sigmoid(s_p + bias) / sum_q sigmoid(s_q + bias); stat (B,n,4) is what the
+    backward reads."""
+    B, HW, Cc, ldx, n = _pcam_args(x, m, w, act)
+    for t, shape in ((logits, (B, n)), (s, (B, n, HW)), (stat, (B, n, CSRA_STAT))):
+        assert tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous()
+    check(_fn("cx_pcam_head_fwd", x)(ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(w), ptr(bias), ptr(logits), ptr(s), ptr(stat), B, HW, Cc, ldx, n, act,
+                                     stream_ptr()), "cx_pcam_head_fwd")
+
+
+def pcam_head_bwd(dlogits, s, stat, x, sc, sh, m, mean, rstd, e_scale, w, g, S1, S2, dw, db, scratch, *, act, stat_rows=0):
+    """cx_pcam_head_bwd: the backward of pcam_head_fwd with the contract of csra_head_bwd; `scratch` holds at least pcam_bwd_scratch
+    floats.  Returns the row count in rows mode."""
+    B, HW, Cc, ldx, n = _pcam_args(x, m, w, act)
+    require_cuda(dlogits, s, stat, g, dw, db, scratch)
+    assert tuple(dlogits.shape) == (B, n) and dlogits.dtype == torch.float32 and dlogits.is_contiguous()
+    assert g.dtype == x.dtype and g.shape == x.shape
+    assert dw.numel() == n * Cc and dw.dtype == torch.float32 and dw.is_contiguous() and (db is None or db.numel() == n)
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous()
+    check(_fn("cx_pcam_head_bwd", x)(ptr(dlogits), ptr(s), ptr(stat), ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(mean), ptr(rstd), ptr(e_scale),
+                                     ptr(w), ptr(g), ptr(S1), ptr(S2), ptr(dw), ptr(db), ptr(scratch), scratch.numel(), B, HW, Cc, ldx,
+                                     _nhwc(g)[4], n, act, stat_rows, stream_ptr()), "cx_pcam_head_bwd")
+    return lib().cx_last_stat_rows() if stat_rows else None
+
+
 def unpool2_mask(d, x, sc, sh, mean, rstd, e_scale, g, S1, S2, stat_rows=0):
     B, H, W, Cc, ldx = _nhwc(x)
     check(_fn("cx_unpool2_mask", x)(ptr(d), ptr(x), ptr(sc), ptr(sh), ptr(mean), ptr(rstd), ptr(e_scale), ptr(g), ptr(S1), ptr(S2),

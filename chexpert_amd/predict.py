@@ -17,7 +17,7 @@ classifier's row count: n rows build the usual head, 3n rows the wide one, whose
 forward (loss.collapse_multiclass: z = z_positive - z_negative, sigmoid(z) = p1 / (p0 + p1)); --calibration and --tta then act on z.
 Any other count is an error, and the checkpoints of a folder must agree.  The pooling of the head (chexpert.py --pool) is read from
 the checkpoint's `pool_state` (none: the average); the checkpoints of a folder must agree on it too.  The head (chexpert.py --head) is
-read from the checkpoint's `head_state` (none: linear) in the same way.
+read from the checkpoint's `head_state` (none: linear; csra or pcam) in the same way.
 """
 import argparse
 import os

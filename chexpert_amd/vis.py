@@ -113,11 +113,12 @@ def vis_attn(x, idents, idxs, attn_layers, out_dir, batch_element=0, window=30):
     return written
 
 
-def visualize_classes(imgs, labels, logits, cams, idents, attr_names, classes, out_dir, step):
+def visualize_classes(imgs, labels, logits, cams, idents, attr_names, classes, out_dir, step, prefix="classcam"):
     """Per-finding localisation figures (gradcam.class_cam): imgs (N,H,W) in [0,1], labels (N,C), logits (N,C), cams (N,K,h,w) the maps
     of the K classes `classes` (indices into attr_names) at any resolution -- each is scaled to its own range and stretched over
     the image for display.  One figure per image, vis/classcam_<ident>_step_<step>.png: the radiograph, then one overlay per class
-    titled with the class name, its label and its sigmoid probability (plotting conventions of `_row`)."""
+    titled with the class name, its label and its sigmoid probability (plotting conventions of `_row`).  `prefix` replaces
+    `classcam` in the file name (the pcam head's probability maps: "pcam")."""
     plt = _plt()
     os.makedirs(os.path.join(out_dir, "vis"), exist_ok=True)
     probs = 1.0 / (1.0 + np.exp(-np.asarray(logits, dtype=np.float64)))
@@ -139,7 +140,7 @@ def visualize_classes(imgs, labels, logits, cams, idents, attr_names, classes, o
             axs[k + 1].imshow(m, cmap="jet", alpha=0.5, extent=(-0.5, W - 0.5, H - 0.5, -0.5), interpolation="bilinear")
         for ax in axs:
             ax.axis("off")
-        path = os.path.join(out_dir, "vis", "classcam_%s_step_%d.png" % (str(idents[i]).replace("/", "_").replace(" ", "_"), step))
+        path = os.path.join(out_dir, "vis", "%s_%s_step_%d.png" % (prefix, str(idents[i]).replace("/", "_").replace(" ", "_"), step))
         plt.savefig(path, dpi=100)
         plt.close(fig)
         written.append(path)

@@ -1083,6 +1083,47 @@ int cx_csra_head_bwd_f32(const float* dlogits, const float* s, const float* stat
                          int ldg, int n, int act, int stat_rows, void* stream);
 long long cx_csra_bwd_scratch(int B, int HW, int C, int n);      /* floats; CX_ESHAPE / CX_EUNSUPPORTED as above */
 
+/* ---- probabilistic-CAM pooling head (csrc/csra_head.hip; FusedNet.set_head("pcam"); chexpert_amd/heads.py states the same in numpy
+ * float64).  PCAM (Ye et al., "Weakly Supervised Lesion Localization With Probabilistic-CAM Pooling", 2020): the classifier at every
+ * pixel, each per-pixel logit turned into a probability, the map pooled per class with those probabilities as weights.  a, W, bias
+ * and m are those of the csra head above; sigma is the logistic function:
+ *
+ *   s[b,k,p]   = sum_c W[k,c] a[b,p,c]                     (csra's score map: the same kernel, the same bits)
+ *   u[b,k,p]   = s[b,k,p] + bias[k]                        (bias NULL: 0)
+ *   w[b,k,p]   = sigma(u[b,k,p]) / sum_q sigma(u[b,k,q])   evaluated as softmax over p of log sigma(u), relative to its maximum
+ *   logit[b,k] = sum_p w[b,k,p] u[b,k,p]
+ *   P[b,k,p]   = sigma(u[b,k,p])                           the probability map
+ *
+ *   q[b,k,p]   = sigma(-u[b,k,p])
+ *   ds[b,k,p]  = dlogit[b,k] w[b,k,p] (1 + q[b,k,p] (u[b,k,p] - logit[b,k]))
+ *   r[b,k]     = sum_p w[b,k,p] q[b,k,p] (u[b,k,p] - logit[b,k])
+ *   db[k]     += sum_b dlogit[b,k] (1 + r[b,k])            (the bias is inside sigma: not csra's sum_b dlogit)
+ *   da, dz, g = e_scale dz, S1, S2, dW: the csra lines with this ds
+ *
+ * One nn.Linear is shared by all classes' maps, the gradient flows through w, and there is no hyper-parameter, hence no lam_T.
+ * sigma(u), sigma(-u) and log sigma(u) are formed from one exp(-|u|); scores of +-1e4 stay finite.
+ *
+ * cx_pcam_head_fwd: the arguments of cx_csra_head_fwd without lam_T.  stat (B, n, 4) fp32 = [max_p u, 1 / sum_p exp(log sigma(u) -
+ * log sigma(max_p u)), logit - max_p u, bias[k]]: relative to the largest u of the row, so that a score of 1e4 beside ordinary ones
+ * costs nothing in u - logit = (u - max u) - stat[2] or in w; the bias rides along for the way back, whose argument list has none.
+ * cx_pcam_head_bwd: the arguments and the contract of cx_csra_head_bwd without lam_T (g, S1 / S2 atomic or one row per image,
+ * CX_ESTATROWS; dW and db ADDED to in a fixed order, no atomics, equal bits over two calls).  scratch: at least
+ * cx_pcam_bwd_scratch(B, HW, C, n) = cx_csra_bwd_scratch(B, HW, C, n) + B n floats (the last B n hold dlogit (1 + r)); a shorter one
+ * is CX_EUNSUPPORTED with nothing written.  The checks are those of the csra entry points.  Additive entry points of ABI 10.     */
+int cx_pcam_head_fwd(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, float* logits,
+                     float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream);
+int cx_pcam_head_bwd(const float* dlogits, const float* s, const float* stat, const void* x, const float* sc, const float* sh, const float* m,
+                     const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1, float* S2, float* dW,
+                     float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n, int act, int stat_rows,
+                     void* stream);
+int cx_pcam_head_fwd_f32(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, float* logits,
+                         float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream);
+int cx_pcam_head_bwd_f32(const float* dlogits, const float* s, const float* stat, const void* x, const float* sc, const float* sh,
+                         const float* m, const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1,
+                         float* S2, float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n,
+                         int act, int stat_rows, void* stream);
+long long cx_pcam_bwd_scratch(int B, int HW, int C, int n);      /* floats; CX_ESHAPE / CX_EUNSUPPORTED as above */
+
 /* ---- fp32 storage mode (CX_DT_F32): the element-wise kernels of the DenseNet path with fp32 activation tensors (same arguments,
  * `const void*` tensors are fp32, pitches in elements), the fp32 weight table ([tap][O][I] fp32; descriptors with stem = 1 give
  * [49][O][4]) and the fp32 image layouts.  cx_conv_gemm / cx_conv_wgrad take CxConv.dtype / CxWgrad.dtype = CX_DT_F32.          */
