@@ -265,12 +265,14 @@ int launch_f32(const CxConv& p, hipStream_t st) {
 
 // ------------------------------------------------------------------------------------------------ weight gradient
 // Workgroup = (tap, 64 output channels n, 64 input channels c, pixel range); 16 pixels per step: G[16][64 n] and A[16][64 c] in
-// LDS (pitch 65), wave (wn, wc) owns one 32 x 32 tile of dW, 8 MFMAs per step; fp32 atomics into OIHW at the end.
+// LDS (pitch 65), wave (wn, wc) owns one 32 x 32 tile of dW, 8 MFMAs per step; at the end the tile of every pixel range goes to its
+// own slab of the caller's workspace (cx_dw_reduce adds the slabs in range order: the same bits every run, as in the bf16 kernels)
+// or, without a workspace, into OIHW through fp32 atomics.
 constexpr int WP = 65;
 
 template <int GPRO, int XPRO, int MODE>
 __global__ __launch_bounds__(256) void wgrad_f32_kernel(const CxWgrad p, const int M, const int n_tiles, const int c_tiles,
-                                                        const int px_per_split, const int dw_k) {
+                                                        const int px_per_split, const int dw_k, float* __restrict__ slab) {
   constexpr int NSRC = (MODE == CX_MODE_POOL2) ? 4 : 1;
   __shared__ float Gt[16 * WP], Xt[16 * WP];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -370,7 +372,7 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const CxWgrad p, const i
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int n = n0 + wn * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (n < p.N) atomicAdd(p.dw + ((size_t)n * dw_k + c) * taps + tap, acc[r]);
+      if (n < p.N) dw_out(p.dw, slab, (size_t)p.N * dw_k * taps, split, ((size_t)n * dw_k + c) * taps + tap, acc[r]);
     }
   }
 }
@@ -386,10 +388,15 @@ int launch_wgrad_f32(const CxWgrad& p, hipStream_t st, int dw_k) {
   long long pps = (M + splits - 1) / splits;
   pps = (pps + 15) / 16 * 16;
   splits = (M + pps - 1) / pps;
+  // every workgroup stores its whole (tap, 64 n, 64 c) tile, an empty pixel range zeros: each (range, element) is written once.
+  // (dw_slab also sets the figure cx_last_slab_floats() reports -- 0 on the atomic route, not the previous launch's)
+  const size_t wtotal = (size_t)p.N * dw_k * taps;
+  float* slab = dw_slab(p.scratch, p.scratch_floats, splits, (long long)wtotal);
   CX_KTAG("wgrad_f32_kernel<%d, %d, %d>", GPRO, XPRO, MODE);
   hipLaunchKernelGGL((wgrad_f32_kernel<GPRO, XPRO, MODE>), dim3((unsigned)(base * splits)), dim3(256), 0, st, p, (int)M, n_tiles, c_tiles,
-                     (int)pps, dw_k);
-  return launch_status();
+                     (int)pps, dw_k, slab);
+  if (const int e = launch_status()) return e;
+  return slab ? cx_dw_reduce(p.dw, slab, wtotal, (int)splits, st) : 0;
 }
 
 }  // namespace

@@ -81,6 +81,7 @@ class _WgradArena:
         self.buf = torch.empty(self.START, dtype=torch.float32, device=device)
         self.off = 0
         self.need = 0
+        self.spilled = False           # a launch of the pass found less than MIN_FREE left and ran its sum at once
         self.tables = {}
         self.active = False
 
@@ -100,11 +101,11 @@ def wgrad_defer_begin(device):
     if WGRAD_SCRATCH_FLOATS <= 0:
         return False
     a = _arena(device)
-    if a.need > a.buf.numel():                       # the previous pass did not fit
+    if a.spilled or a.need > a.buf.numel():          # the previous pass did not fit (a spill can leave need <= numel: MIN_FREE)
         a.buf = None
         a.buf = torch.empty(int(a.need * 1.05) + a.MIN_FREE, dtype=torch.float32, device=device)
         a.tables.clear()
-    a.off, a.need, a.active = 0, 0, True
+    a.off, a.need, a.spilled, a.active = 0, 0, False, True
     lib().cx_wgrad_defer(1)
     return True
 
@@ -116,6 +117,7 @@ def _wgrad_ws(device):
         if a.buf.numel() - a.off >= a.MIN_FREE:
             return a.buf[a.off:], a, True
         lib().cx_wgrad_defer(0)                      # this launch sums at once from the per-stream scratch
+        a.spilled = True
         return wgrad_scratch(device), a, False
     return wgrad_scratch(device), None, False
 
