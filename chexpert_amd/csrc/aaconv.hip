@@ -816,6 +816,21 @@ inline int grid_for(size_t n, int block, int cap) {
 
 inline size_t attn_lds_floats(int H, int W, int dvh) { return (size_t)DKH * (2 * H - 1 + 2 * W - 1) + (size_t)AQ * (H + W + 2) + TK * (DKH + dvh); }
 
+// Every dv/nh the generic kernels are instantiated for (1 .. MAXDV).  The forward and the backward launcher expand their dispatch
+// switch from this one list, and the backward's case raises the LDS limit of the instance it launches, so the set of instances
+// that can be launched and the set that may ask for more than 64 KB are the same set by construction.
+#define AA_DVH_LIST(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
+constexpr size_t AA_LDS_DEFAULT = 64 * 1024;       // dynamic LDS a kernel may ask for without hipFuncSetAttribute
+constexpr size_t AA_LDS_BWD_Q = 160 * 1024;        // what the query side of the backward is allowed (the CU's LDS)
+
+template <typename T> constexpr const char* aa_tname() { return std::is_same<T, bf16>::value ? "bf16" : "f32"; }
+
+// the contract every launcher states for qkv: rows of ldq elements holding [q dk | k dk | v dv], read in chunks of four elements
+// (8 bytes of bf16, 16 bytes of fp32: V4<T>::ld), so the pitch is a multiple of four elements
+inline bool aa_qkv_shape(int B, int H, int W, int nh, int dk, int dv, int ldq) {
+  return B > 0 && H > 0 && W > 0 && nh > 0 && dk > 0 && dv >= 0 && dk % nh == 0 && dv % nh == 0 && ldq % 4 == 0 && ldq >= 2 * dk + dv;
+}
+
 }  // namespace
 
 // ---- launchers, templated on the storage type (bf16 / the fp32 parity mode)
@@ -826,7 +841,7 @@ template <typename T>
 int aa_attention_fwd_t(const void* qkv, const float* rel_h, const float* rel_w, float* o, float* lse, int B, int H, int W, int nh,
                         int dk, int dv, int ldq, void* stream) {
   if (!qkv || !rel_h || !rel_w || !o || !lse) return CX_EINVAL;
-  if (nh <= 0 || dv % nh || (ldq % 4)) return CX_ESHAPE;
+  if (!aa_qkv_shape(B, H, W, nh, dk, dv, ldq)) return CX_ESHAPE;
   hipStream_t st = as_stream(stream);
   if (dk != nh * DKH || dv / nh > MAXDV)            // other head widths: aaconv_heads.hip (CX_ESHAPE beyond dk/nh, dv/nh <= 64, dv <= 104)
     return cx_aa_heads_fwd(!std::is_same<T, bf16>::value, qkv, rel_h, rel_w, o, lse, B, H, W, nh, dk, dv, ldq, st);
@@ -839,26 +854,19 @@ int aa_attention_fwd_t(const void* qkv, const float* rel_h, const float* rel_w, 
     if (handled) return rc;
   }
   const size_t smem = attn_lds_floats(H, W, dvh) * 4;
-  if (smem > 64 * 1024) return CX_ESHAPE;
+  if (smem > AA_LDS_DEFAULT) return CX_ESHAPE;          // no instance asks for more than the default limit: no attribute to raise
   dim3 grid((H * W + AQ - 1) / AQ, B * nh);
-#define LAUNCH(D) hipLaunchKernelGGL((aa_attn_fwd_kernel<T, D>), grid, dim3(AQ), smem, st, (const T*)qkv, rel_h, rel_w, o, lse, g)
+  // (5, 7, 10, 11, 12: value ratios the reference's configurations do not use; generic kernels only)
+#define AA_CASE(D)                                                                                                            \
+    case D:                                                                                                                   \
+      hipLaunchKernelGGL((aa_attn_fwd_kernel<T, D>), grid, dim3(AQ), smem, st, (const T*)qkv, rel_h, rel_w, o, lse, g);       \
+      break;
   switch (dvh) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    case 5: LAUNCH(5); break;          // (5, 7, 10, 11, 12: value ratios the reference's configurations do not use; generic kernels only)
-    case 6: LAUNCH(6); break;
-    case 7: LAUNCH(7); break;
-    case 8: LAUNCH(8); break;
-    case 9: LAUNCH(9); break;
-    case 10: LAUNCH(10); break;
-    case 11: LAUNCH(11); break;
-    case 12: LAUNCH(12); break;
-    case 13: LAUNCH(13); break;
+    AA_DVH_LIST(AA_CASE)
     default: return CX_EUNSUPPORTED;
   }
-#undef LAUNCH
+#undef AA_CASE
+  CX_KTAG("aa_fwd<%s,%d>", aa_tname<T>(), dvh);
   return launch_status();
 }
 
@@ -866,14 +874,15 @@ template <typename T>
 int aa_attention_weights_t(const void* qkv, const float* rel_h, const float* rel_w, const float* lse, float* weights, int B, int H,
                             int W, int nh, int dk, int dv, int ldq, void* stream) {
   if (!qkv || !rel_h || !rel_w || !lse || !weights) return CX_EINVAL;
-  if (nh <= 0 || dv % nh || (ldq % 4)) return CX_ESHAPE;
+  if (!aa_qkv_shape(B, H, W, nh, dk, dv, ldq)) return CX_ESHAPE;
   if (dk != nh * DKH)
     return cx_aa_heads_weights(!std::is_same<T, bf16>::value, qkv, rel_h, rel_w, lse, weights, B, H, W, nh, dk, dv, ldq, as_stream(stream));
   AAGeo g{B, H, W, nh, dk, dv, ldq};
   const size_t smem = attn_lds_floats(H, W, 0) * 4;
-  if (smem > 64 * 1024) return CX_ESHAPE;
+  if (smem > AA_LDS_DEFAULT) return CX_ESHAPE;
   hipLaunchKernelGGL(aa_attn_weights_kernel<T>, dim3((H * W + AQ - 1) / AQ, B * nh), dim3(AQ), smem, as_stream(stream),
                      (const T*)qkv, rel_h, rel_w, lse, weights, g);
+  CX_KTAG("aa_weights<%s>", aa_tname<T>());
   return launch_status();
 }
 
@@ -882,7 +891,7 @@ int aa_attention_bwd_t(const void* qkv, const float* rel_h, const float* rel_w, 
                         float* dqkv, float* d_rel_h, float* d_rel_w, int B, int H, int W, int nh, int dk, int dv, int ldq,
                         float* scratch, int64_t scratch_floats, void* stream) {
   if (!qkv || !rel_h || !rel_w || !o || !d_o || !lse || !dqkv || !d_rel_h || !d_rel_w) return CX_EINVAL;
-  if (nh <= 0 || dk % nh || dv % nh || (ldq % 4)) return CX_ESHAPE;
+  if (!aa_qkv_shape(B, H, W, nh, dk, dv, ldq)) return CX_ESHAPE;
   hipStream_t st = as_stream(stream);
   // Reproducible relative-table gradients: every query-side workgroup plain-stores its two partial tables into the caller's
   // workspace (one slab per workgroup: 128 queries of one (image, head)) and the slabs are added in workgroup order afterwards.
@@ -909,20 +918,7 @@ int aa_attention_bwd_t(const void* qkv, const float* rel_h, const float* rel_w, 
   const size_t smem_q = (attn_lds_floats(H, W, dvh) + (size_t)DKH * (2 * H - 1 + 2 * W - 1) + (size_t)AQ * (W + 1) + (size_t)AQ * (H + 1) +
                          (size_t)AQ * (DKH + 1)) * 4;
   const size_t smem_k = ((size_t)DKH * (2 * H - 1 + 2 * W - 1) + TK * (DKH + dvh + 2)) * 4;
-  if (smem_q > 160 * 1024) return CX_ESHAPE;
   dim3 grid((H * W + AQ - 1) / AQ, B * nh);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, 13>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
   bool row_q = false;
   {
     const int rc = !std::is_same<T, bf16>::value ? 0 : cx_try_aa_row(1, qkv, rel_h, rel_w, const_cast<float*>(o), d_o, const_cast<float*>(lse), dqkv, d_rel_h, d_rel_w, slab_h,
@@ -930,27 +926,24 @@ int aa_attention_bwd_t(const void* qkv, const float* rel_h, const float* rel_w, 
     if (row_q && rc) return rc;          // dq, dk, dv and the table partials all done there
   }
   if (!row_q) {
-#define LAUNCH(D)                                                                                                              \
-    hipLaunchKernelGGL((aa_attn_bwd_q_kernel<T, D>), grid, dim3(AQ), smem_q, st, (const T*)qkv, rel_h, rel_w, o, d_o, lse, dqkv, \
-                       d_rel_h, d_rel_w, slab_h, slab_w, g);                                                                  \
-    hipLaunchKernelGGL((aa_attn_bwd_k_kernel<T, D>), grid, dim3(AQ), smem_k, st, (const T*)qkv, rel_h, rel_w, o, d_o, lse, dqkv, g)
+    if (smem_q > AA_LDS_BWD_Q || smem_k > AA_LDS_DEFAULT) return CX_ESHAPE;
+    // smem_q passes the 64 KB default from H + W = 35 on: the case that launches an instance is also what raises that instance's
+    // limit, once (a host-side attribute: nothing is queued on the stream)
+#define AA_CASE(D)                                                                                                             \
+    case D: {                                                                                                                  \
+      static const bool attr = ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_kernel<T, D>),          \
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)AA_LDS_BWD_Q), true); \
+      (void)attr;                                                                                                              \
+      hipLaunchKernelGGL((aa_attn_bwd_q_kernel<T, D>), grid, dim3(AQ), smem_q, st, (const T*)qkv, rel_h, rel_w, o, d_o, lse, dqkv, \
+                         d_rel_h, d_rel_w, slab_h, slab_w, g);                                                                 \
+      hipLaunchKernelGGL((aa_attn_bwd_k_kernel<T, D>), grid, dim3(AQ), smem_k, st, (const T*)qkv, rel_h, rel_w, o, d_o, lse, dqkv, g); \
+    } break;
     switch (dvh) {
-      case 1: LAUNCH(1); break;
-      case 2: LAUNCH(2); break;
-      case 3: LAUNCH(3); break;
-      case 4: LAUNCH(4); break;
-      case 5: LAUNCH(5); break;
-      case 6: LAUNCH(6); break;
-      case 7: LAUNCH(7); break;
-      case 8: LAUNCH(8); break;
-      case 9: LAUNCH(9); break;
-      case 10: LAUNCH(10); break;
-      case 11: LAUNCH(11); break;
-      case 12: LAUNCH(12); break;
-      case 13: LAUNCH(13); break;
+      AA_DVH_LIST(AA_CASE)
       default: return CX_EUNSUPPORTED;
     }
-#undef LAUNCH
+#undef AA_CASE
+    CX_KTAG("aa_bwd<%s,%d>", aa_tname<T>(), dvh);
     if (const int e = launch_status()) return e;
   }
   if (slab_h) {

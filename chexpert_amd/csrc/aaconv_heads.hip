@@ -466,6 +466,8 @@ inline size_t bwdk_floats(int KC, int VC, int H, int W) {
 }
 
 // dynamic LDS above the 64 KB default, once per kernel instantiation (a host-side attribute: nothing is queued on the stream)
+template <typename T> constexpr const char* tname() { return std::is_same<T, bf16>::value ? "bf16" : "f32"; }
+
 template <typename K>
 inline void allow_lds(K* kern) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
@@ -478,6 +480,7 @@ int launch_fwd(const HGeo& g, const T* qkv, const float* rel_h, const float* rel
   const size_t smem = fwd_floats(KC, VC, g.H, g.W) * 4;
   if (smem > LDS_MAX) return CX_ESHAPE;
   hipLaunchKernelGGL((aah_fwd_kernel<T, KC, VC>), dim3((g.H * g.W + HQ - 1) / HQ, g.B * g.nh), dim3(HQ), smem, st, qkv, rel_h, rel_w, o, lse, g);
+  CX_KTAG("aa_heads_fwd<%s,%d,%d>", tname<T>(), KC, VC);
   return launch_status();
 }
 
@@ -488,6 +491,7 @@ int launch_weights(const HGeo& g, const T* qkv, const float* rel_h, const float*
   const size_t smem = fwd_floats(KC, 0, g.H, g.W) * 4;
   if (smem > LDS_MAX) return CX_ESHAPE;
   hipLaunchKernelGGL((aah_weights_kernel<T, KC>), dim3((g.H * g.W + HQ - 1) / HQ, g.B * g.nh), dim3(HQ), smem, st, qkv, rel_h, rel_w, lse, wts, g);
+  CX_KTAG("aa_heads_weights<%s,%d>", tname<T>(), KC);
   return launch_status();
 }
 
@@ -509,6 +513,7 @@ int launch_bwd(const HGeo& g, const T* qkv, const float* rel_h, const float* rel
   } else {
     hipLaunchKernelGGL((aah_bwd_k_kernel<T, KC, VC, 0>), grid, dim3(HQ), smem_k, st, qkv, rel_h, rel_w, o, d_o, lse, dqkv, g);
   }
+  CX_KTAG("aa_heads_bwd<%s,%d,%d>", tname<T>(), KC, VC);
   return launch_status();
 }
 

@@ -850,15 +850,20 @@ int launch_row(int which, const void* qkv, const float* rel_h, const float* rel_
     const size_t smem_m = (tables + 64 * DVH) * 4 + 64 * KB_PITCH;
     hipLaunchKernelGGL((aa_attn_fwd_mfma_kernel<DVH, WW>), dim3((g.H * WW + AQM - 1) / AQM, g.B * g.nh), dim3(256), smem_m, st,
                        (const bf16*)qkv, rel_h, rel_w, o, lse, g);
+    CX_KTAG("aa_row_fwd<%d,%d>", DVH, WW);
   } else {
     const size_t smem_m = (tables + 2 * (WW == 40 ? 40 : 24) * DVH + (size_t)AQM * (DKH + 1 + (g.H > WW + 1 ? g.H : WW + 1)) + ((g.H + 3) & ~3)) * 4 +
                           2 * (WW == 40 ? 48 : 32) * KB_PITCH + 16;
+    // (a static of the template: one flag, and one attribute call, per <DVH, WW> instance -- the one launched right below.  The
+    // query side asks for 68.2 KB at most (<6, 40> at H = 64, the dispatch limit of cx_try_aa_row), the other two kernels for less
+    // than the 64 KB default: 22.6 KB forward, 43.4 KB key side.)
     static bool attr_m = false;
     if (!attr_m) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&aa_attn_bwd_q_mfma_kernel<DVH, WW>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 96 * 1024);
       attr_m = true;
     }
+    if (smem_m > 96 * 1024) return CX_ESHAPE;
     hipLaunchKernelGGL((aa_attn_bwd_q_mfma_kernel<DVH, WW>), dim3((g.H * WW + AQM - 1) / AQM, g.B * g.nh), dim3(256), smem_m, st,
                        (const bf16*)qkv, rel_h, rel_w, o, d_o, lse, dqkv, d_rel_h, d_rel_w, slab_h, slab_w, g);
     constexpr int NKR = 127 / WW + 2;
@@ -866,6 +871,7 @@ int launch_row(int which, const void* qkv, const float* rel_h, const float* rel_
                           (size_t)2 * (2 * g.H - 1) * KB_PITCH + 16;
     hipLaunchKernelGGL((aa_attn_bwd_k_mfma_kernel<DVH, WW>), dim3((g.H * WW + 127) / 128, g.B * g.nh), dim3(256), smem_k, st,
                        (const bf16*)qkv, rel_h, rel_w, o, d_o, lse, dqkv, g);
+    CX_KTAG("aa_row_bwd<%d,%d>", DVH, WW);
   }
   return launch_status();
 }

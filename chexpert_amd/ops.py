@@ -216,7 +216,9 @@ def last_stat_rows():
 
 
 def last_kernel():
-    """The kernel instantiation the most recent conv / weight-gradient call of this thread dispatched to, as rocprofv3 spells it."""
+    """The kernel instantiation the most recent conv / weight-gradient call of this thread dispatched to, as rocprofv3 spells it;
+    after an attention call (aa_attention_fwd / _weights / _bwd) the family, storage type and template arguments of what ran:
+    `aa_row_fwd<3,20>`, `aa_bwd<f32,5>`, `aa_weights<bf16>`, `aa_heads_fwd<bf16,32,16>`."""
     return lib().cx_last_kernel().decode()
 
 

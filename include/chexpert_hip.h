@@ -587,7 +587,10 @@ int cx_rmsprop_step_items(float* p, const float* g, float* sq, float* buf, size_
                           int skip_nonfinite, void* stream);
 
 /* ---- attention-augmented convolution (AAConv2d, models/attn_aug_conv.py:19-100) --------------------
- * qkv: bf16 (B, H*W, ldq) output of in_proj_qkv (channels [q dk | k dk | v dv], head-major), ldq % 4 == 0.
+ * qkv: bf16 (B, H*W, ldq) output of in_proj_qkv (channels [q dk | k dk | v dv], head-major), ldq % 4 == 0 and
+ * ldq >= 2 dk + dv (the kernels read q and k in chunks of four elements: 8 bytes of bf16, 16 bytes of fp32); CX_ESHAPE otherwise,
+ * before any launch.  cx_last_kernel() names the family and instance that ran: aa_row_fwd<DVH,W> / aa_row_bwd<DVH,W>,
+ * aa_fwd<bf16|f32,DVH> / aa_bwd<..> / aa_weights<bf16|f32>, aa_heads_fwd<bf16|f32,KC,VC> / aa_heads_bwd<..> / aa_heads_weights<..,KC>.
  * Head widths dkh = dk/nh and dvh = dv/nh of 1 .. 64 with dv <= 104: dkh = 20 with dvh <= 13 runs the row / generic kernels
  * of aaconv.hip + aaconv_row.hip, every other width the runtime-width kernels of aaconv_heads.hip; CX_ESHAPE beyond that, or
  * when a map's relative tables and tiles exceed the LDS of a workgroup (any H, W <= 40 fits).

@@ -85,15 +85,21 @@ def test_attention_kernels_match_closed_form(dev, dtype, nh, dkh, dvh, B, H, W, 
     o = torch.zeros(B, H * W, dv, device=dev)
     lse = torch.zeros(B * nh, H * W, device=dev)
     ops.aa_attention_fwd(qd, rel_h.to(dev), rel_w.to(dev), o, lse, nh, dk, dv)
+    # the launcher's tag: the runtime-width family, the storage type, the key / value capacities the widths are padded to
+    st, KC, VC = ("bf16" if dtype == "bf16" else "f32"), (32 if dkh <= 32 else 64), next(c for c in (8, 16, 32, 64) if dvh <= c)
+    assert ops.last_kernel() == "aa_heads_fwd<%s,%d,%d>" % (st, KC, VC), ops.last_kernel()
     close(o.cpu(), o_ref.detach(), 2e-4, "o")
     if H * W <= 400:
         wts = ops.aa_attention_weights(qd, rel_h.to(dev), rel_w.to(dev), lse, nh, dk, dv)
+        # (the maps do not depend on the value width: keys of 20 channels take the dkh = 20 kernel whatever dv/nh is)
+        assert ops.last_kernel() == ("aa_weights<%s>" % st if dkh == 20 else "aa_heads_weights<%s,%d>" % (st, KC)), ops.last_kernel()
         assert wts.shape == (B, nh, H * W, H * W)
         close(wts.cpu(), P.detach(), 2e-4, "weights")
         assert (wts.sum(-1) - 1).abs().max().item() < 1e-4
     dqkv = torch.full((B, H * W, Cq), 7.0, device=dev)
     drh, drw = torch.zeros_like(rel_h, device=dev), torch.zeros_like(rel_w, device=dev)
     ops.aa_attention_bwd(qd, rel_h.to(dev), rel_w.to(dev), o, d_o.to(dev), lse, dqkv, drh, drw, nh, dk, dv)
+    assert ops.last_kernel() == "aa_heads_bwd<%s,%d,%d>" % (st, KC, VC), ops.last_kernel()
     want = t.grad.permute(0, 2, 3, 1).reshape(B, H * W, Cq)
     close(dqkv.cpu()[..., :dk], want[..., :dk], 1e-3, "dq")
     close(dqkv.cpu()[..., dk:2 * dk], want[..., dk:2 * dk], 1e-3, "dk")
