@@ -18,6 +18,7 @@ BOOT_MAX_POINTS, BOOT_SENS, BOOT_SPEC = 8, 0, 1
 CALIB_METHODS = {"temperature": 0, "platt": 1}                     # CX_CALIB_TEMPERATURE, CX_CALIB_PLATT
 CALIB_MAX_ITER, CALIB_MAX_BINS = 1000, 64
 DELONG_MAX_ROWS, DELONG_WG_ENTRIES, DELONG_TILE = 128, 16384, 32   # 4 rows per class and model: two models of 16 classes
+HIER_MAX_LABELS, HIER_MAX_PATH = 64, 8                             # CX_HIER_MAX_LABELS, CX_HIER_MAX_PATH (loss.hip)
 
 _vp, _fp, _i32 = C.c_void_p, C.c_void_p, C.c_int32
 
@@ -126,6 +127,8 @@ SIGNATURES = {
     "cx_asl_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp],
     "cx_mc3_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp],
     "cx_mc3_collapse": [_vp, _vp, _vp, _i, _i, _vp],
+    "cx_hier_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _i, _i, _vp],
+    "cx_hier_collapse": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "cx_softmax_ce_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp],
     "cx_head_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "cx_gap_relu_bn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

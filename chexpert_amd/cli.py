@@ -58,6 +58,25 @@
                         auto), --mixup / --cutmix / --erase_prob, --fused_optimizer --graph and more than one rank.  The evaluation
                         loss in eval_results stays the (masked) cross-entropy, so it can be compared across training losses; the
                         checkpoint carries the loss's four numbers (`loss_state`), which --restore puts back
+  --labels {competition,all}
+                        the findings read from the csv: the five competition labels (default) or all 14, in the csv's column order
+                        (data.ATTR_NAMES_ALL); all sets --n_classes 14 and refuses another one
+  --loss hier           the hierarchical label loss over the findings' tree (Chen et al., MIDL 2019; Pham et al., 2019), inside the fused
+                        step (FusedNet.set_loss(kind="hier"), cx_hier_fwd_bwd) and, without --fused_optimizer, through
+                        loss.HierarchicalBCE: every logit is that of P(finding | its parent is positive).  --hier_mode conditional
+                        (default: the masked cross-entropy where every ancestor's label is positive) or unconditional (the
+                        cross-entropy of the product of probabilities along the path); --hier_parents `auto` (default: the CheXpert
+                        tree data.CHEXPERT_PARENT, needs --labels all) or n_classes integers, each label's parent or -1, parents first
+                        (synthetic data, other label sets).  The label tables get data.hierarchy_closure after the --uncertain policy
+                        (a positive child makes its ancestors positive; --no_hier_closure leaves them).  Evaluation turns the
+                        conditional logits into unconditional ones right after the forward (loss.collapse_hierarchy), so the
+                        evaluation loss, AUROC, --bootstrap*, --delong, --calibrate*, --plot_roc, --evaluate_ensemble and the
+                        eval_results files see them; the maps of --visualize are those of the conditional logits.  The checkpoint
+                        carries kind, table, mode and the closure choice (`loss_state`); --restore and --evaluate_* read them: a run
+                        without --hier_mode continues in the stored mode, a --hier_parents or --hier_mode that contradicts them
+                        is refused, and an evaluation without --loss hier closes its validation table iff the training run did
+                        (with --loss hier the run's own --no_hier_closure decides).  Takes --pos_weight, --uncertain (but multiclass), --fused_optimizer --graph and more
+                        than one rank; not with --mixup / --cutmix, nor with the five competition labels and `auto`
   --pool KIND           the global pooling in front of the classifier (FusedNet.set_pool, csrc/pool_head.hip): avg (default), max, lse
                         (log-sum-exp, --pool_r R: sharpness, default 10) or gem (generalised mean, --pool_p P: start of the trained
                         exponent in [1, 16], default 3); every --model, with --fused_optimizer --graph and more than one rank.  The
@@ -199,9 +218,19 @@ def build_parser():
     p.add_argument("--erase_fill", type=int, default=136, metavar="V", help="grey level 0..255 an erased rectangle gets (default: the dataset mean)")
     p.add_argument("--uncertain", default="ones", choices=list(UNCERTAIN_POLICIES), help="policy for the uncertain (-1) training labels")
     p.add_argument("--pos_weight", nargs="+", default=None, metavar="W", help="`auto` or n_classes floats: positive-term weights of the loss")
-    p.add_argument("--loss", default="bce", choices=["bce", "aucm", "focal", "asl"],
-                   help="training loss: cross-entropy, the AUC min-max-margin loss, the focal loss or the asymmetric loss (the evaluation "
-                        "loss written to eval_results stays the cross-entropy, comparable across training losses)")
+    p.add_argument("--loss", default="bce", choices=["bce", "aucm", "focal", "asl", "hier"],
+                   help="training loss: cross-entropy, the AUC min-max-margin loss, the focal loss, the asymmetric loss or the hierarchical "
+                        "label loss (the evaluation loss written to eval_results stays the cross-entropy, comparable across training losses)")
+    p.add_argument("--labels", default="competition", choices=["competition", "all"],
+                   help="the findings read from the csv: the five competition labels, or all 14 in the csv's column order (sets --n_classes 14)")
+    p.add_argument("--hier_mode", default=None, choices=["conditional", "unconditional"],
+                   help="with --loss hier: the cross-entropy of each conditional logit where the ancestors are positive (default), or of "
+                        "the product of probabilities along the path from the root")
+    p.add_argument("--hier_parents", nargs="+", default=None, metavar="P",
+                   help="with --loss hier: `auto` (default: the CheXpert tree, needs --labels all) or n_classes integers, the index of "
+                        "each label's parent, -1 for a root, parents before children")
+    p.add_argument("--no_hier_closure", action="store_true",
+                   help="with --loss hier: leave the label tables as they are (default: a positive child makes its ancestors positive)")
     p.add_argument("--focal_gamma", type=float, default=None, metavar="G", help="focusing exponent of --loss focal (>= 0; default 2)")
     p.add_argument("--focal_alpha", type=float, default=None, metavar="A", help="class balance of --loss focal, in (0, 1) (default: none)")
     p.add_argument("--asl_gamma_pos", type=float, default=None, metavar="GP", help="positives' exponent of --loss asl (>= 0; default 0)")
@@ -303,9 +332,18 @@ def parse_args(argv=None):
     --clahe grid that does not divide the crop size is an argument error, not a kernel status; so are the ranges of the sample-mixing
     flags and their combination with --loss aucm."""
     parser = build_parser()
+    n_default = parser.get_default("n_classes")
+    parser.set_defaults(n_classes=None)            # (so that a --n_classes that was given can contradict --labels all)
     args = parser.parse_args(argv)
     if args.load_config:
         args.__dict__.update(json.load(open(args.load_config)))
+    if getattr(args, "labels", "competition") == "all":
+        from .data import ATTR_NAMES_ALL
+        if args.n_classes not in (None, len(ATTR_NAMES_ALL)):
+            parser.error("--labels all reads the %d findings of the csv: --n_classes %d contradicts it" % (len(ATTR_NAMES_ALL), args.n_classes))
+        args.n_classes = len(ATTR_NAMES_ALL)
+    elif args.n_classes is None:
+        args.n_classes = n_default
     if getattr(args, "clahe", False):
         from .augment import check_clahe_grid, clahe_clip_count
         size = args.resize or 320
@@ -554,7 +592,11 @@ def resolve_pos_weight(spec, targets, n_classes):
     return w
 
 
-def class_names(n_classes):
+def class_names(n_classes, labels="competition"):
+    if labels == "all":
+        from .data import ATTR_NAMES_ALL
+        if n_classes == len(ATTR_NAMES_ALL):
+            return list(ATTR_NAMES_ALL)
     return ATTR_NAMES[:n_classes] if n_classes <= len(ATTR_NAMES) else ["class %d" % i for i in range(n_classes)]
 
 
@@ -653,6 +695,77 @@ def multiclass_options(args):
         if on:
             raise ValueError("--uncertain multiclass cannot be combined with %s: %s" % (flag, why))
     return True
+
+
+def hier_options(args):
+    """--loss hier and its flags checked before anything runs: None for the other losses, else {"parent": the table as a list of
+    ints, "mode": --hier_mode, None where it was not given (a restored checkpoint's mode fills it in, hier_for_checkpoint; the default
+    'conditional' comes after that: hier_mode_of), "closure": whether the label tables get data.hierarchy_closure, "explicit":
+    whether --hier_parents gave the table}.  What has no meaning for the loss is refused by naming both flags."""
+    loss = getattr(args, "loss", "bce")
+    mode, spec, keep = getattr(args, "hier_mode", None), getattr(args, "hier_parents", None), getattr(args, "no_hier_closure", False)
+    if loss != "hier":
+        if mode is not None or spec is not None or keep:
+            raise ValueError("--hier_mode / --hier_parents / --no_hier_closure belong to --loss hier: pass it with them")
+        return None
+    soft = "a blended label is positive for no ancestor test and closed under no tree (--erase_prob leaves the labels alone and is allowed)"
+    for flag, on, why in (("--uncertain multiclass", getattr(args, "uncertain", "ones") == "multiclass", "the three-way softmax is that policy's loss"),
+                          ("--mixup", getattr(args, "mixup", 0.0) > 0, soft), ("--cutmix", getattr(args, "cutmix", 0.0) > 0, soft)):
+        if on:
+            raise ValueError("--loss hier cannot be combined with %s: %s" % (flag, why))
+    spec = ["auto"] if spec is None else [spec] if isinstance(spec, str) else [str(v) for v in spec]
+    if spec == ["auto"]:
+        if getattr(args, "labels", "competition") != "all":
+            raise ValueError("--loss hier with --hier_parents auto needs --labels all: the five competition labels have no relation among "
+                             "them (pass --labels all for the CheXpert tree, or --hier_parents as %d integers)" % args.n_classes)
+        from .data import CHEXPERT_PARENT
+        parent = list(CHEXPERT_PARENT)
+    else:
+        try:
+            parent = [int(v) for v in spec]
+        except ValueError:
+            raise ValueError("--hier_parents takes `auto` or %d integers (got %s)" % (args.n_classes, spec))
+    from .ops import check_hier_parent
+    parent = check_hier_parent("--hier_parents", parent, args.n_classes).tolist()
+    return {"parent": parent, "mode": mode, "closure": not keep, "explicit": spec != ["auto"]}
+
+
+def hier_mode_of(hier):
+    """The mode of a run's hierarchical loss once a restored checkpoint has had its say: --hier_mode or the checkpoint's, else 'conditional'."""
+    return hier["mode"] or "conditional"
+
+
+def hier_for_checkpoint(hier, loss_state, path, train=False):
+    """The hierarchical loss of a run against a checkpoint's `loss_state`: a checkpoint of --loss hier brings its parent table, its mode
+    and whether its label tables were closed under the tree (`closure`, which the command line writes beside them; absent: they
+    were).  A --hier_parents or a --hier_mode that contradicts what is stored is refused (ValueError); a run without --hier_mode takes
+    the stored mode; a run that evaluates without --loss hier takes everything from the checkpoint (its logits are conditional ones
+    and have to be collapsed, and its validation table is treated as that run's was).  Returns the run's options, a new dict where
+    the checkpoint changed them."""
+    if (loss_state or {}).get("kind") != "hier":
+        return hier
+    stored = [int(v) for v in torch.as_tensor(loss_state["parent"]).tolist()]
+    mode = loss_state.get("mode") or "conditional"
+    if hier is None:
+        if train:
+            raise ValueError("--restore %s: the checkpoint was trained with --loss hier: pass it (and its flags) to go on training" % path)
+        return {"parent": stored, "mode": mode, "closure": bool(loss_state.get("closure", True)), "explicit": False}
+    if hier["parent"] != stored:
+        raise ValueError("--restore %s: the checkpoint was trained with the parent table %s, --hier_parents gives %s" % (path, stored, hier["parent"]))
+    if hier["mode"] not in (None, mode):
+        raise ValueError("--restore %s: the checkpoint was trained with --hier_mode %s, this run asks for --hier_mode %s" % (path, mode, hier["mode"]))
+    return hier if hier["mode"] == mode else dict(hier, mode=mode)
+
+
+def check_member_hier(hier, ck, name):
+    """A member of --evaluate_ensemble against the run: every member's logits go through one collapse, so either the run has --loss hier
+    and every member was trained with it on the run's table, or neither has."""
+    trained = checkpoint_loss_kind(ck) == "hier"
+    if trained != (hier is not None):
+        raise ValueError("--evaluate_ensemble: %s was trained %s --loss hier, this run is %s it: pass --loss hier and its table with a "
+                         "folder of such checkpoints, and only then" % (name, "with" if trained else "without", "with" if hier is not None else "without"))
+    if trained:
+        hier_for_checkpoint(hier, ck["loss_state"], name)
 
 
 def head_width(args):
@@ -1017,24 +1130,46 @@ def make_model(args, device, pool=None, head=None):
     raise RuntimeError("Model architecture not supported.")
 
 
+def collapse_of(collapse):
+    """The function that makes (N, n_classes) binary logits of a forward's output: None where they are that already, for True the
+    collapse of the three-way head (loss.collapse_multiclass), for a parent table that of the hierarchical loss's conditional
+    logits (loss.collapse_hierarchy); a host table is checked here, once, and copied to a device with the first batch from it."""
+    if collapse is None or collapse is False:
+        return None
+    if collapse is True:
+        from .loss import collapse_multiclass
+        return collapse_multiclass
+    from .loss import collapse_hierarchy
+    if isinstance(collapse, torch.Tensor) and collapse.is_cuda:
+        return lambda o: collapse_hierarchy(o, collapse)
+    from .ops import check_hier_parent
+    table, on = check_hier_parent("collapse_of", collapse), {}
+
+    def run(o):
+        if o.device not in on:
+            on[o.device] = table.to(o.device)
+        return collapse_hierarchy(o, on[o.device])
+    return run
+
+
 @torch.no_grad()
 def evaluate(model, ds, indices, batch_size, device, pre=None, collapse=False):
     """chexpert.py:198-211 on this rank's slice of the validation set; returns logits, targets, per-element losses, indices.
     `pre`: the deterministic preprocessing of the uint8 batch on the GPU (--clahe), or None.  `collapse`: the model has the three-way
     head of --uncertain multiclass; its logits become binary ones right after the forward (loss.collapse_multiclass), so everything
-    from the element losses on sees (N, n_classes)."""
+    from the element losses on sees (N, n_classes).  A parent table as `collapse`: the model was trained with --loss hier; its
+    conditional logits become unconditional ones at the same place (loss.collapse_hierarchy)."""
     model.eval()
     outs, tgts, losses, ids = [], [], [], []
     loss_fn = nn.BCEWithLogitsLoss(reduction="none")
     if bool((ds.targets < 0).any()):               # ignored labels in this table: their element losses are 0 (cx_bce_masked_fwd_bwd)
         from .loss import MaskedBCE
         loss_fn = MaskedBCE().elementwise
-    if collapse:
-        from .loss import collapse_multiclass
+    collapse = collapse_of(collapse)
     for x, t, idx in batches(ds, indices, batch_size, False):
         o = model(x.to(device) if pre is None else pre(x.to(device)))
-        if collapse:
-            o = collapse_multiclass(o)
+        if collapse is not None:
+            o = collapse(o)
         losses.append(loss_fn(o, t.to(device)))
         outs.append(o)
         tgts.append(t.to(device))
@@ -1137,6 +1272,7 @@ def main(argv=None):
     aucm = aucm_options(args, world)
     focus = focus_options(args)
     multiclass = multiclass_options(args)
+    hier = hier_options(args)
     pool = resolve_pool(args)
     head = resolve_head(args, pool)
     if world > 1:
@@ -1168,12 +1304,17 @@ def main(argv=None):
         from .data import ChexpertCSV
         if not args.data_path:
             raise RuntimeError("pass --data_path <folder holding CheXpert-v1.0-small> or --synthetic N (no download here)")
-        train_ds = ChexpertCSV(args.data_path, "train", args.resize, mini_data=args.mini_data, uncertain=args.uncertain, seed=args.seed)
+        train_ds = ChexpertCSV(args.data_path, "train", args.resize, mini_data=args.mini_data, uncertain=args.uncertain, seed=args.seed,
+                               labels=getattr(args, "labels", "competition"))
         # (under torch.distributed.run the ranks of a node share one table: --cache_decoded is then the node's budget)
         if args.cache_decoded > 0 and not train_ds.enable_decoded_cache(int(args.cache_decoded * 2 ** 30),
                                                                          node_shared=int(os.environ.get("WORLD_SIZE", "1")) > 1):
             print("decoded-image cache off: %d images of %d^2 bytes exceed --cache_decoded %.1f GB" % (len(train_ds), train_ds.crop, args.cache_decoded))
-        valid_ds = ChexpertCSV(args.data_path, "valid", args.resize, mini_data=args.mini_data)
+        valid_ds = ChexpertCSV(args.data_path, "valid", args.resize, mini_data=args.mini_data, labels=getattr(args, "labels", "competition"))
+    if hier is not None and hier["closure"]:   # after the uncertain policy, before anything reads a table (weights, loader, evaluation)
+        from .data import hierarchy_closure
+        train_ds.targets = hierarchy_closure(train_ds.targets, hier["parent"])
+        valid_ds.targets = hierarchy_closure(valid_ds.targets, hier["parent"])
     pos_weight = resolve_pos_weight(args.pos_weight, train_ds.targets, args.n_classes)
     if pos_weight is not None and rank == 0 and new_cfg:       # the resolved vector goes beside the flags that asked for it: a config
         # kept from an earlier run (restore into its output_dir) stays whole, as that run wrote it
@@ -1214,10 +1355,16 @@ def main(argv=None):
     if args.restore and os.path.isfile(args.restore):
         try:
             restored_loss = restore(args, model, optimizer, scheduler, device, multiclass)
+            adopted = hier is None
+            hier = hier_for_checkpoint(hier, restored_loss, args.restore, args.train)
+            if adopted and hier is not None and hier["closure"]:   # an evaluation of a --loss hier checkpoint without the flag: the
+                from .data import hierarchy_closure                # validation table as that run saw it
+                valid_ds.targets = hierarchy_closure(valid_ds.targets, hier["parent"])
         except ValueError:
             if train_loader is not None:
                 train_loader.close()
             raise
+    collapse = hier["parent"] if hier is not None else multiclass       # what evaluate() does to a forward's output
     loss_fn = nn.BCEWithLogitsLoss(reduction="none")
     masked_loss = None
     if focus is not None:
@@ -1239,6 +1386,13 @@ def main(argv=None):
     elif args.train and restored_loss is not None and restored_loss.get("kind") in ("focal", "asl"):
         train_loader.close()
         raise ValueError("--restore: the checkpoint was trained with --loss %s: pass it (and its flags) to go on training" % restored_loss["kind"])
+    elif hier is not None:
+        # the fused step's loss and, by the same kernel, the autograd route's (the table a restored checkpoint brought is this one:
+        # hier_for_checkpoint); one storage for the table and the weights: the module reads what the model holds
+        from .loss import HierarchicalBCE
+        model.set_loss(kind="hier", parent=hier["parent"], mode=hier_mode_of(hier), pos_weight=pos_weight)
+        masked_loss = HierarchicalBCE(hier["parent"], hier_mode_of(hier), pos_weight)
+        masked_loss.parent, masked_loss.pos_weight = model.loss_parent, model.loss_pos_weight
     elif multiclass:
         # the fused step's loss and, by the same kernel, the autograd route's; a restored checkpoint brings its class weights
         from .loss import MultiClassUncertain
@@ -1289,7 +1443,7 @@ def main(argv=None):
 
     def run_eval(tag):
         with averaged():
-            o, t, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, multiclass)
+            o, t, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, collapse)
         res = M.compute_metrics(o, t, l)
         if rank == 0:
             print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
@@ -1381,7 +1535,7 @@ def main(argv=None):
                 if args.step % args.eval_interval == 0:
                     ema_sd = None
                     with averaged():
-                        res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, multiclass))
+                        res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, collapse))
                         if ex.get("ema_decay") is not None and rank == 0:
                             ema_sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
                     if rank == 0:
@@ -1399,8 +1553,10 @@ def main(argv=None):
                         if aucm is not None:          # the auxiliary scalars are trained state: restore continues from them
                             sync_loss_aux()
                             ckpt["loss_state"] = model.loss_state()
-                        elif focus is not None or multiclass:      # the loss's numbers: restore checks the kind and puts them back
+                        elif focus is not None or multiclass or hier is not None:      # the loss's numbers: restore checks the kind and puts them back
                             ckpt["loss_state"] = model.loss_state()
+                            if hier is not None:          # how the label tables were made: an evaluation without the flags does the same
+                                ckpt["loss_state"]["closure"] = hier["closure"]
                         save_checkpoint(ckpt, optimizer.state_dict(), sched_state, args)
                     model.train()
             sync_loss_aux()      # (also current when no checkpoint followed the last step)
@@ -1419,10 +1575,11 @@ def main(argv=None):
         for c in sorted(f for f in os.listdir(args.restore) if f.startswith("checkpoint") and f.endswith(".pt")):
             ck = torch.load(os.path.join(args.restore, c), map_location=device)
             check_checkpoint_head(ck, multiclass, c)
+            check_member_hier(hier, ck, c)
             check_checkpoint_pool(ck, model, c)
             check_checkpoint_head_kind(ck, model, c)
             model.load_state_dict(model_weights(ck, args, c))
-            o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, multiclass)
+            o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, collapse)
             outs.append(o)
             losses.append(l)
             members.append(c)
@@ -1440,7 +1597,8 @@ def main(argv=None):
         # attention-augmented models the attention-map grids of the stored softmax weights
         from . import vis
         from .gradcam import class_cam, grad_cam
-        names = class_names(args.n_classes)
+        names = class_names(args.n_classes, getattr(args, "labels", "competition"))
+        to_binary = collapse_of(hier["parent"]) if hier is not None else None    # the figures' scores are unconditional probabilities;
         groups = vis.select_vis_subset(valid_ds.targets, names)
         flat = sorted({i for g in groups[1] for i in g})
         pos = {i: k for k, i in enumerate(flat)}
@@ -1456,8 +1614,8 @@ def main(argv=None):
             if clahe is not None:                # the figures show what the network saw
                 xd = clahe(xd)
                 x = xd.cpu()
-            with torch.no_grad():
-                scores.append(model(xd).float().cpu())
+            with torch.no_grad():              # the maps below stay those of the conditional logits: evidence for a finding GIVEN its parent
+                scores.append((model(xd) if to_binary is None else to_binary(model(xd))).float().cpu())
             if avg_pool:                         # (another pooling: the saliency maps are the figures, visualize_needs_avg)
                 masks.append(grad_cam(model, xd).float().cpu())
             if cam_classes is not None and (csra or pcam):

@@ -6,6 +6,8 @@
 //                                                           term, four terms (plain, masked and weighted BCE, focal / asymmetric)
 //   cx_mc3_fwd_bwd, cx_mc3_collapse                         the same sum over elements of THREE logits each (U-MultiClass), in the
 //                                                           skeleton's sibling mc3_loss_kernel; the collapse to binary logits
+//   cx_hier_fwd_bwd, cx_hier_collapse                       the findings as a forest: the masked BCE under positive ancestors, or the
+//                                                           cross-entropy of the product of sigmoids along a path; the collapse
 //   cx_softmax_ce_fwd_bwd                                   one wave per sample, its own final sum
 //   cx_aucm_fwd_bwd, cx_aucm_aux_step                       a function of each class's whole batch column: column trees, two passes
 #include "common.h"
@@ -258,6 +260,201 @@ __global__ __launch_bounds__(NT) void mc3_collapse_kernel(const float* __restric
   }
 }
 
+// ---- hierarchical labels --------------------------------------------------------------------------------------------------------
+// The findings as a forest (include/chexpert_hip.h, cx_hier_fwd_bwd): parent[k] is -1 for a root, else an index below k, and every
+// logit is the logit of P(k | parent(k) positive).  Two losses over it (Chen et al., MIDL 2019): the conditional one (mode 0) is the
+// masked BCE with one more reason to skip an element -- an ancestor whose target is not positive --, the unconditional one (mode 1)
+// the cross-entropy of the product of the sigmoids along the path.  Both are sums over the B x n elements, so both keep the element
+// skeleton: one workgroup, thread t takes elements t, t + 256, ..., the fixed tree over LDS, stride and tree stated on blockDim.x.
+//
+// A path is held as a 64-bit mask (n <= 64): bit j of anc[k] says that j is k or one of its ancestors.  Parents come before children,
+// so the set bits in ascending order ARE the path, root first.  The masks are built once per workgroup, into LDS, by the one walk up
+// the table there is (hier_stage_masks).  The table is device memory whose values the host entry cannot see, so that walk is safe by
+// itself: an entry outside [-1, k) is read as a root and a path is cut after HPATH nodes.  No index leaves the row, whatever the
+// table holds.
+constexpr int HMAXN = CX_HIER_MAX_LABELS, HPATH = CX_HIER_MAX_PATH;
+constexpr float LN2 = 0.693147180559945f;
+typedef unsigned long long hmask;
+
+// anc[k] for k < n; desc[j] (where given) = the k whose path holds j, j itself among them.  Ends in a barrier.
+__device__ __forceinline__ void hier_stage_masks(const int* __restrict__ parent, hmask* anc, hmask* desc, const int n) {
+  for (int k = threadIdx.x; k < n; k += blockDim.x) {
+    hmask m = 0;
+    int node = k;
+#pragma unroll
+    for (int s = 0; s < HPATH; ++s) {
+      if (node >= 0) {
+        m |= 1ull << node;
+        const int p = parent[node];
+        node = (p >= 0 && p < node) ? p : -1;
+      }
+    }
+    anc[k] = m;
+  }
+  __syncthreads();
+  if (desc) {
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+      hmask m = 0;
+      for (int k = j; k < n; ++k) m |= ((anc[k] >> j) & 1ull) << k;
+      desc[j] = m;
+    }
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ int hier_pop(hmask& m) {       // the lowest set bit's index, which leaves the mask
+  const int b = __ffsll((long long)m) - 1;
+  m &= m - 1;
+  return b;
+}
+
+// log sigmoid(z) and log sigmoid(-z) from one e, as AslTerm takes its two softplus values
+__device__ __forceinline__ void log_sigmoid_pair(const float z, float& lp, float& lq) {
+  const float e = log1pf(expf(-fabsf(z)));
+  lp = -(fmaxf(-z, 0.f) + e);
+  lq = -(fmaxf(z, 0.f) + e);
+}
+
+// u = log P and l1m = log(1 - P) of the product of sigmoids along the path `path` (a mask), root first; logs(node, lp, lq) gives a
+// node's pair.  The a_j = (sum of the lp before j) + lq_j are formed twice, by the same additions, rather than kept.
+template <typename Logs>
+__device__ __forceinline__ void hier_log_probs(const hmask path, Logs logs, float& u, float& l1m) {
+  float m = -INFINITY;
+  u = 0.f;
+  for (hmask rest = path; rest;) {
+    float lp, lq;
+    logs(hier_pop(rest), lp, lq);
+    m = fmaxf(m, u + lq);
+    u += lp;
+  }
+  if (u <= -LN2) {
+    l1m = log1pf(-expf(u));
+  } else {
+    float sum = 0.f, pre = 0.f;
+    for (hmask rest = path; rest;) {
+      float lp, lq;
+      logs(hier_pop(rest), lp, lq);
+      sum += expf((pre + lq) - m);
+      pre += lp;
+    }
+    l1m = m + logf(sum);
+  }
+}
+
+// mode 0: Term is MaskedBceTerm or WeightedBceTerm, and the kernel is elem_loss_kernel but for the ancestors' targets
+template <typename Term>
+__global__ __launch_bounds__(NT) void hier_cond_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                       const int* __restrict__ parent, const float* __restrict__ pos_weight, float* loss,
+                                                       float* loss_elem, float* dlogits, float grad_scale, int B, int n) {
+  using Acc = typename Term::Acc;
+  __shared__ Acc red[NT];
+  __shared__ hmask anc[HMAXN];
+  hier_stage_masks(parent, anc, nullptr, n);
+  const Term term(pos_weight, nullptr);
+  const float invB = 1.f / B;
+  Acc acc = 0;
+  for (int i = threadIdx.x; i < B * n; i += blockDim.x) {
+    const int k = i % n;
+    bool live = true;
+    for (hmask above = anc[k] & ~(1ull << k); above;) live = target[i - k + hier_pop(above)] >= 0.5f && live;
+    float l = 0.f, d = 0.f;
+    if (live) term(logits[i], target[i], k, invB, grad_scale, l, d);
+    acc += l;
+    if (loss_elem) loss_elem[i] = l;
+    if (dlogits) dlogits[i] = d;
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && loss) *loss = Term::mean(red[0], B, invB);
+}
+
+// mode 1.  A term of element (b, k) reaches every logit on k's path, so the thread of element (b, j) gathers: it adds the terms of
+// the live k of j's subtree (desc[j]) in ascending k, and k = j itself gives the element's loss.  What the gathering threads share
+// goes through LDS, one round of 256 elements at a time: the window is the whole rows those elements lie in (at most 256 + 2n
+// elements), and its logits, targets and lp / lq (phase A) and u / l1m (phase B) are each read or computed once, by whichever
+// thread the window's stride gives them to; a row that two rounds share is computed in both, to the same bits.  The gather itself
+// (phase C) reads LDS alone.  Nothing depends on which outputs were asked for.
+constexpr int HWIN = NT + 2 * HMAXN;
+
+__global__ __launch_bounds__(NT) void hier_uncond_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                         const int* __restrict__ parent, const float* __restrict__ pos_weight, float* loss,
+                                                         float* loss_elem, float* dlogits, float grad_scale, int B, int n) {
+  __shared__ double red[NT];
+  __shared__ hmask anc[HMAXN], desc[HMAXN];
+  __shared__ float s_z[HWIN], s_t[HWIN], s_lp[HWIN], s_lq[HWIN], s_u[HWIN], s_l1m[HWIN], s_w[HMAXN];
+  for (int k = threadIdx.x; k < n; k += blockDim.x) s_w[k] = pos_weight ? pos_weight[k] : 1.f;
+  hier_stage_masks(parent, anc, desc, n);
+  const float invB = 1.f / B;
+  const int total = B * n;
+  double acc = 0;
+  for (int base = 0; base < total; base += blockDim.x) {
+    const int last = min(base + (int)blockDim.x, total) - 1;        // this round's elements: base .. last
+    const int w0 = base / n * n, wlen = (last / n + 1) * n - w0;    // its window: whole rows, wlen < blockDim.x + 2n
+    for (int e = threadIdx.x; e < wlen; e += blockDim.x) {
+      const float z = logits[w0 + e];
+      s_z[e] = z;
+      s_t[e] = target[w0 + e];
+      log_sigmoid_pair(z, s_lp[e], s_lq[e]);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < wlen; e += blockDim.x) {
+      const int k = e % n, r = e - k;
+      float u, l1m;
+      hier_log_probs(anc[k], [&](int node, float& lp, float& lq) { lp = s_lp[r + node]; lq = s_lq[r + node]; }, u, l1m);
+      s_u[e] = u;
+      s_l1m[e] = l1m;
+    }
+    __syncthreads();
+    const int i = base + threadIdx.x;
+    if (i < total) {
+      const int e = i - w0, j = e % n, r = e - j;
+      const float lqj = s_lq[e], qj = 1.f / (1.f + expf(s_z[e]));
+      float l = 0.f, g = 0.f;
+      for (hmask sub = desc[j]; sub;) {
+        const int k = hier_pop(sub);
+        const float t = s_t[r + k];
+        if (t >= 0.f) {
+          const float u = s_u[r + k], l1m = s_l1m[r + k];
+          const float w = s_w[k];
+          const float omt = 1.f - t;
+          if (k == j) l = -w * t * u - omt * l1m;
+          g += omt * expf(u + lqj - l1m) - w * t * qj;
+        }
+      }
+      acc += l;
+      if (loss_elem) loss_elem[i] = l;
+      if (dlogits) dlogits[i] = g * invB * grad_scale;
+    }
+    __syncthreads();                   // the window is rewritten by the next round
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = blockDim.x / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && loss) *loss = (float)(red[0] / B);
+}
+
+// One thread per (b, k), no reduction; each workgroup stages the masks for itself.
+__global__ __launch_bounds__(NT) void hier_collapse_kernel(const float* __restrict__ logits, const int* __restrict__ parent,
+                                                           float* __restrict__ z, float* __restrict__ p, long long total, int n) {
+  __shared__ hmask anc[HMAXN];
+  hier_stage_masks(parent, anc, nullptr, n);
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int k = (int)(i % n);
+  const float* row = logits + (i - k);
+  float u, l1m;
+  hier_log_probs(anc[k], [&](int node, float& lp, float& lq) { log_sigmoid_pair(row[node], lp, lq); }, u, l1m);
+  z[i] = anc[k] == 1ull << k ? logits[i] : u - l1m;
+  if (p) p[i] = expf(u);
+}
+
 // ---- softmax cross-entropy ------------------------------------------------------------------------------------------------------
 // one wave per sample: row maximum and sum of exponentials by DPP-free shuffles, loss = mean_b (logsumexp - logit[target]);
 // the per-sample terms are summed by ONE workgroup in sample order (bit-reproducible)
@@ -448,6 +645,24 @@ int cx_mc3_collapse(const float* logits, float* z, float* p_unc, int B, int n, v
   if (!logits || !z || B < 1 || n < 1 || (long long)B * n > INT_MAX - NT) return CX_EINVAL;
   const long long total = (long long)B * n;
   hipLaunchKernelGGL(mc3_collapse_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, as_stream(stream), logits, z, p_unc, total);
+  return launch_status();
+}
+
+int cx_hier_fwd_bwd(const float* logits, const float* target, const int* parent, const float* pos_weight, int mode, float* loss,
+                    float* loss_elem, float* dlogits, float grad_scale, int B, int n, void* stream) {
+  if (!logits || !target || !parent || B < 1 || n < 1 || n > HMAXN || (mode != 0 && mode != 1) || (long long)B * n > INT_MAX - NT)
+    return CX_EINVAL;
+  auto kernel = mode == 1 ? hier_uncond_kernel : (pos_weight ? hier_cond_kernel<WeightedBceTerm> : hier_cond_kernel<MaskedBceTerm>);
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(NT), 0, as_stream(stream), logits, target, parent, pos_weight, loss, loss_elem, dlogits,
+                     grad_scale, B, n);
+  return launch_status();
+}
+
+int cx_hier_collapse(const float* logits, const int* parent, float* z, float* p, int B, int n, void* stream) {
+  if (!logits || !parent || !z || B < 1 || n < 1 || n > HMAXN || (long long)B * n > INT_MAX - NT) return CX_EINVAL;
+  const long long total = (long long)B * n;
+  hipLaunchKernelGGL(hier_collapse_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, as_stream(stream), logits, parent, z, p,
+                     total, n);
   return launch_status();
 }
 

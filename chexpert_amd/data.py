@@ -17,6 +17,13 @@ from PIL import Image
 
 ATTR_NAMES = ["Atelectasis", "Cardiomegaly", "Consolidation", "Edema", "Pleural Effusion"]      # dataset.py:26
 DIR_NAME = "CheXpert-v1.0-small"                                                                  # dataset.py:18-19
+# all 14 findings, in the csv's column order, and their tree (Irvin et al., "CheXpert", AAAI 2019, Fig. 1): entry k is the index of
+# finding k's parent, -1 for a root.  Lung Opacity -> {Lung Lesion, Edema, Consolidation -> Pneumonia, Atelectasis}; Enlarged
+# Cardiomediastinum -> Cardiomegaly.  Parents come before children, as FusedNet.set_loss(kind="hier") wants them.
+ATTR_NAMES_ALL = ["No Finding", "Enlarged Cardiomediastinum", "Cardiomegaly", "Lung Opacity", "Lung Lesion", "Edema", "Consolidation",
+                  "Pneumonia", "Atelectasis", "Pneumothorax", "Pleural Effusion", "Pleural Other", "Fracture", "Support Devices"]
+CHEXPERT_PARENT = [-1, -1, 1, -1, 3, 3, 3, 6, 3, -1, -1, -1, -1, -1]
+LABEL_SETS = {"competition": ATTR_NAMES, "all": ATTR_NAMES_ALL}
 
 
 UNCERTAIN_POLICIES = ("ones", "zeros", "ignore", "ones_lsr", "zeros_lsr", "multiclass")
@@ -46,6 +53,27 @@ def apply_uncertain(labels, policy, seed=0):
     return lab
 
 
+def hierarchy_closure(table, parent):
+    """The label table made consistent with the tree `parent` (CHEXPERT_PARENT): a positive child (>= 0.5, the "positive" of the
+    losses) makes every one of its ancestors 1, whatever it held -- blank, negative, uncertain or a smoothed value.  The labeler does
+    not enforce the tree (a Cardiomegaly positive under a blank Enlarged Cardiomediastinum is common), and the conditional mode of
+    the hierarchical loss drops an element whose ancestor is not positive.  Nothing else moves: a negative or ignored child says
+    nothing about its parent.  It runs after the uncertain policy.  table: (N, n) numpy array or tensor; returns a new one of the
+    same kind."""
+    par = [int(a) for a in parent]
+    tensor = isinstance(table, torch.Tensor)
+    lab = table.clone() if tensor else np.array(table, dtype=np.float32)
+    if lab.ndim != 2 or lab.shape[1] != len(par):
+        raise ValueError("hierarchy_closure takes an (N, %d) table for a parent table of %d entries (got %s)" % (len(par), len(par), tuple(lab.shape)))
+    for k, a in enumerate(par):
+        if a < -1 or a >= k:
+            raise ValueError("hierarchy_closure: parent[%d] = %d; an entry is -1 (a root) or the index of an earlier label" % (k, a))
+    for k in range(len(par) - 1, 0, -1):           # children before parents: a positive travels the whole path in one sweep
+        if par[k] >= 0:
+            lab[lab[:, k] >= 0.5, par[k]] = 1.0
+    return lab
+
+
 def resize_center_crop(img, resize, crop):
     """T.Resize(resize) (shorter side to `resize`, bilinear, aspect kept; skipped when `resize` is falsy) then T.CenterCrop(crop)
     (chexpert.py:67-69), on a PIL image; returns the grey bytes (crop, crop) uint8."""
@@ -70,12 +98,18 @@ def resize_center_crop(img, resize, crop):
 class ChexpertCSV(torch.utils.data.Dataset):
     """mode 'train' / 'valid' / 'vis': `root` holds the extracted CheXpert-v1.0-small folder; 'test': `root` is a csv of image paths.
     Items are (uint8 (1,S,S), float32 labels (5,), row index in the source table) like the reference's (img, attr, idx).
-    uncertain / seed: the policy for the -1 labels of the training table (apply_uncertain) and the seed of its label-smoothing draws."""
+    uncertain / seed: the policy for the -1 labels of the training table (apply_uncertain) and the seed of its label-smoothing draws.
+    labels: 'competition' (the five findings of ATTR_NAMES) or 'all' (the 14 of ATTR_NAMES_ALL, in the csv's column order: labels
+    (14,)); `attr_names` is the list in use."""
     attr_names = ATTR_NAMES
 
-    def __init__(self, root, mode="train", resize=None, data_filter=None, mini_data=None, uncertain="ones", seed=0):
+    def __init__(self, root, mode="train", resize=None, data_filter=None, mini_data=None, uncertain="ones", seed=0, labels="competition"):
         import pandas as pd
         assert mode in ("train", "valid", "test", "vis")
+        if labels not in LABEL_SETS:
+            raise ValueError("labels must be 'competition' or 'all' (got %r)" % (labels,))
+        if labels != "competition":
+            self.attr_names = LABEL_SETS[labels]
         if uncertain not in UNCERTAIN_POLICIES:
             raise ValueError("uncertain policy must be one of %s (got %r)" % (", ".join(UNCERTAIN_POLICIES), uncertain))
         self.uncertain = uncertain         # acts on the training table only

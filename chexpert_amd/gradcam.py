@@ -97,7 +97,10 @@ def grad_cam(model, x, hooks=None, cls_idx=None):
     """Hook targets of the reference: DenseNet `features.norm5` / `classifier` (chexpert.py:468), ResNet `layer4` / `fc`
     (:484, :490), EfficientNet `head[1]` / `head[-1]` (:498).  The map tensor and the pooled input of the final Linear both
     exist in the engine's workspace after one eval forward.  The channel weights here do not depend on the class (module
-    docstring); for class-specific maps use `class_cam`."""
+    docstring); for class-specific maps use `class_cam`.
+    Under set_loss(kind="hier") the logits are CONDITIONAL ones -- P(finding | its parent is positive) -- and the maps are taken on them
+    as they are: a map shows the evidence for a finding given its parent, not for the unconditional probability
+    (loss.collapse_hierarchy gives that number, and it has no single map)."""
     if not x.is_cuda:
         raise RuntimeError("grad_cam runs on the GPU only")
     _require_avg(model, "grad_cam")
@@ -200,7 +203,11 @@ def class_cam(model, x, classes=None, *, relu=True, normalize=True, upsample=Tru
     (ops.cam_norm_upsample on the (B*K, h*w) rows); normalize without upsample gives the scaled (B, K, h, w) maps; with neither,
     the raw M (relu=False) or relu(M).  relu=False with normalize scales the signed map the same way.  Both storage types, all three
     families; registered Grad-CAM hooks are ignored (the hooked path is never taken); model.training and the running statistics are
-    left as they were."""
+    left as they were.
+
+    Under set_loss(kind="hier") logit c is a CONDITIONAL one -- P(finding c | its parent is positive) -- and M is taken on it as it is:
+    the map shows the evidence for the finding given its parent, and the CAM identity above holds for that logit, not for the
+    unconditional one of loss.collapse_hierarchy."""
     _require_avg(model, "class_cam")          # M is Grad-CAM only when the pool is the mean
     act, lin = cam_source(model)
     kind, K, payload = _cam_classes(classes, lin.out_features)

@@ -159,7 +159,10 @@ def class_maps(model, x):
     fp32 tensors on x's device.  scores is the classifier applied at every pixel of the last feature map (without the bias), attention
     its softmax over the pixels at temperature T, which sums to 1 over the pixels of every (image, class); logits equal model(x).
     With the pcam head (set_head("pcam")): (P (B, n, h, w), w (B, n, h, w), logits (B, n)), P = sigmoid(s + bias) the per-class
-    probability map in [0, 1] and w = P / sum_p P the pooling weights, which sum to 1 over the pixels; logits equal model(x)."""
+    probability map in [0, 1] and w = P / sum_p P the pooling weights, which sum to 1 over the pixels; logits equal model(x).
+    Under set_loss(kind="hier") the logits are CONDITIONAL ones -- P(finding | its parent is positive) -- and the maps are taken on them
+    as they are: a map shows the evidence for a finding given its parent, not for the unconditional probability
+    (loss.collapse_hierarchy gives that number, and it has no single map)."""
     import torch
     if getattr(model, "head_kind", "linear") not in ("csra", "pcam"):
         raise NotImplementedError("class_maps reads the score map of the csra or pcam head: this model has set_head(%r)"

@@ -5,14 +5,16 @@ evaluation -- over the same `launch`, so the autograd route and the fused step r
 the cross-entropy with uncertain-label handling (cx_bce_fwd_bwd / cx_bce_masked_fwd_bwd), AUCMLoss for kind "aucm" (cx_aucm_fwd_bwd),
 with its auxiliary scalars as parameters, FocalLoss and AsymmetricLoss for kinds "focal" and "asl" (cx_asl_fwd_bwd),
 MultiClassUncertain for kind "multiclass" (cx_mc3_fwd_bwd), the three-way softmax of the U-MultiClass policy, whose logits are (B, 3n)
-and which `collapse_multiclass` turns into binary ones (cx_mc3_collapse).  Device tensors only: there is no CPU path."""
+and which `collapse_multiclass` turns into binary ones (cx_mc3_collapse), HierarchicalBCE for kind "hier" (cx_hier_fwd_bwd), the
+conditional / unconditional loss over the findings' tree, whose conditional logits `collapse_hierarchy` turns into unconditional
+ones (cx_hier_collapse).  Device tensors only: there is no CPU path."""
 import torch
 import torch.nn as nn
 
 from . import ops
 
 KERNEL = {"bce": "cx_bce_masked_fwd_bwd", "aucm": "cx_aucm_fwd_bwd", "focal": "cx_asl_fwd_bwd", "asl": "cx_asl_fwd_bwd",
-          "multiclass": "cx_mc3_fwd_bwd"}
+          "multiclass": "cx_mc3_fwd_bwd", "hier": "cx_hier_fwd_bwd"}
 WIDTH = {"multiclass": 3}          # logits per target element, where it is not 1
 
 
@@ -71,10 +73,21 @@ def check_prior(who, prior, margin, n=None):
     return p
 
 
+def check_hier_mode(who, mode):
+    """'conditional' / 'unconditional' (or cx_hier_fwd_bwd's 0 / 1) as the name."""
+    names = {v: k for k, v in ops.HIER_MODES.items()}
+    if isinstance(mode, str) and mode in ops.HIER_MODES:
+        return mode
+    if isinstance(mode, int) and not isinstance(mode, bool) and mode in names:
+        return names[mode]
+    raise ValueError("%s takes mode 'conditional' or 'unconditional' (got %r)" % (who, mode))
+
+
 # ------------------------------------------------------------------------------------------------ the loss of a step
 class Loss:
-    """The loss of a step: `kind` ('bce', 'aucm', 'focal', 'asl', 'multiclass'), `ignore_negative`, `margin` (a host float, passed by
-    value) and the fp32 device tensors the kernels read -- `pos_weight` (n,), `focus` (4,) = [gamma+, gamma-, clip, alpha or -1],
+    """The loss of a step: `kind` ('bce', 'aucm', 'focal', 'asl', 'multiclass', 'hier'), `ignore_negative`, `margin` (a host float, passed
+    by value), `mode` (kind 'hier': 'conditional' or 'unconditional', a host value like the margin, None elsewhere), `parent` (kind
+    'hier': the int32 (n,) device table of each label's parent, -1 for a root) and the fp32 device tensors the kernels read -- `pos_weight` (n,), `focus` (4,) = [gamma+, gamma-, clip, alpha or -1],
     `aux` and `daux` (3, n) = rows a, b, alpha and their gradients, `prior` (n,), `lr_aux` (1,), `class_weight` (n, 3) = the weights
     of kind 'multiclass', whose head has 3n outputs --, None where the kind has none.  Plain
     tensors, neither buffers nor parameters.  Behind them stands held storage (`_held`, by name) that outlives a change of kind: a
@@ -83,8 +96,9 @@ class Loss:
     one per call from its own attributes."""
 
     def __init__(self, kind="bce", ignore_negative=False, margin=1.0, pos_weight=None, focus=None, aux=None, daux=None, prior=None,
-                 lr_aux=None, class_weight=None):
+                 lr_aux=None, class_weight=None, parent=None, mode=None):
         self.kind, self.ignore_negative, self.margin = kind, ignore_negative, margin
+        self.parent, self.mode = parent, mode
         self.pos_weight, self.focus, self.aux, self.daux, self.prior, self.lr_aux = pos_weight, focus, aux, daux, prior, lr_aux
         self.class_weight = class_weight
         self._held = {}
@@ -100,6 +114,8 @@ class Loss:
             ops.aucm_fwd_bwd(logits, target, self.prior, self.aux, self.margin, loss, None, dlogits, self.daux)
         elif self.kind == "multiclass":
             ops.mc3_fwd_bwd(logits, target, self.class_weight, loss, loss_elem, dlogits)
+        elif self.kind == "hier":
+            ops.hier_fwd_bwd(logits, target, self.parent, self.pos_weight, self.mode, loss, loss_elem, dlogits)
         elif self.kind in ("focal", "asl"):
             ops.asl_fwd_bwd(logits, target, self.pos_weight, self.focus, loss, loss_elem, dlogits)
         elif self.ignore_negative or self.pos_weight is not None:
@@ -107,22 +123,22 @@ class Loss:
         else:
             ops.bce_fwd_bwd(logits, target, loss, loss_elem, dlogits)
 
-    def _hold(self, name, values, dev, keep=False):
+    def _hold(self, name, values, dev, keep=False, dtype=torch.float32):
         """`values` copied into the held storage `name`, which is made anew for another shape or another device; with `keep`,
         storage that is already there stays as it is.  None: None (the storage is kept for the next time)."""
         if values is None:
             return None
-        v = torch.as_tensor(values, dtype=torch.float32)
+        v = torch.as_tensor(values, dtype=dtype)
         held = self._held.get(name)
         fresh = held is None or held.shape != v.shape or held.device != dev
         if fresh:
-            held = self._held[name] = torch.empty(v.shape, dtype=torch.float32, device=dev)
+            held = self._held[name] = torch.empty(v.shape, dtype=dtype, device=dev)
         if fresh or not keep:
             held.copy_(v)
         return held
 
     def _put(self, who, dev, kind, ignore_negative, pos_weight=None, focus=None, prior=None, margin=None, lr_aux=None,
-             class_weight=None):
+             class_weight=None, parent=None, mode=None):
         """The one place that writes the state, after every check: each field is assigned, to None where `kind` has none, so nothing
         of the previous kind is left over.  `aux` starts at zero coming from another kind and stays as trained coming from 'aucm';
         the margin stays what the last 'aucm' made it."""
@@ -134,15 +150,18 @@ class Loss:
         self.pos_weight, self.focus = self._hold("pos_weight", pos_weight, dev), self._hold("focus", focus, dev)
         self.prior, self.lr_aux = self._hold("prior", prior, dev), self._hold("lr_aux", None if lr_aux is None else [lr_aux], dev)
         self.class_weight = self._hold("class_weight", class_weight, dev)
+        self.parent, self.mode = self._hold("parent", parent, dev, dtype=torch.int32), mode
         self.kind, self.ignore_negative = kind, ignore_negative
         if margin is not None:
             self.margin = float(margin)
 
     def set(self, dev, n, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
-            alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None):
+            alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None):
         """FusedNet.set_loss for a model whose head has n outputs, with its parameters on dev.  A refused call changes nothing."""
         if kind not in KERNEL:
-            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal', 'asl' or 'multiclass' (got %r)" % (kind,))
+            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal', 'asl', 'multiclass' or 'hier' (got %r)" % (kind,))
+        if kind != "hier" and (parent is not None or mode is not None):
+            raise ValueError("set_loss: parent and mode belong to kind='hier'")
         if kind != "multiclass" and class_weight is not None:
             raise ValueError("set_loss: class_weight belongs to kind='multiclass'")
         if kind != "aucm" and (prior is not None or lr_aux is not None or margin != 1.0):
@@ -169,6 +188,14 @@ class Loss:
             if n % 3:
                 raise ValueError("%s needs a head of three outputs per finding (negative, positive, uncertain); this head has %d" % (who, n))
             self._put(who, dev, kind, False, class_weight=check_class_weight(who, class_weight, n // 3))
+        elif kind == "hier":
+            if ignore_negative:
+                raise ValueError("%s always ignores a target < 0; ignore_negative is the cross-entropy's switch" % who)
+            if parent is None:
+                raise ValueError("%s needs parent: for each of the head's %d outputs the index of its parent label, -1 for a root" % (who, n))
+            table = ops.check_hier_parent(who, parent, n)
+            self._put(who, dev, kind, True, check_pos_weight(who, pos_weight, n), parent=table,
+                      mode=check_hier_mode(who, "conditional" if mode is None else mode))
         else:
             if kind == "focal":
                 g = 2.0 if gamma is None else gamma
@@ -192,6 +219,8 @@ class Loss:
             d["focus"] = cpu(self.focus)
         if self.kind == "multiclass":
             d["class_weight"] = cpu(self.class_weight)
+        if self.kind == "hier":
+            d["parent"], d["mode"] = cpu(self.parent), self.mode
         return d
 
     def load_state(self, d, dev, n):
@@ -213,6 +242,10 @@ class Loss:
             self.aux.copy_(aux)
         elif kind == "multiclass":
             self.set(dev, n, kind="multiclass", class_weight=d.get("class_weight"))
+        elif kind == "hier":
+            if d.get("parent") is None:
+                raise ValueError("load_loss_state: kind 'hier' needs parent, the table of the labels' parents")
+            self.set(dev, n, kind="hier", parent=d["parent"], mode=d.get("mode"), pos_weight=self.pos_weight)   # (the held weights stay)
         elif kind != "bce":
             raise ValueError("load_loss_state: unknown loss kind %r" % (kind,))
         elif self.kind != "bce":               # (a model that holds the cross-entropy keeps its options)
@@ -417,3 +450,50 @@ def collapse_multiclass(logits, return_uncertain=False):
     if x.shape[0]:
         ops.mc3_collapse(x, z, p)
     return (z, p) if return_uncertain else z
+
+
+class HierarchicalBCE(_LossModule):
+    """The hierarchical label loss of (B, n) logits over a tree of findings (Chen et al., "Deep hierarchical multi-label classification
+    of chest X-ray images", MIDL 2019; the conditional training of Pham et al., 2019): every logit is the logit of
+    P(finding | its parent is positive).  parent: for each finding the index of its parent, -1 for a root, parents before children
+    (data.CHEXPERT_PARENT for the 14 CheXpert findings).  mode 'conditional' (HLCP): the masked cross-entropy of each logit, in which
+    an element also drops out where an ancestor's target is not positive (< 0.5, or ignored).  mode 'unconditional' (HLUP): the
+    cross-entropy of the product of the sigmoids along the path from the root, against the element's own target.  A target < 0 is
+    ignored (the divisor stays the batch size), soft targets are valid, pos_weight weights the positive term.  The loss of
+    FusedNet.set_loss(kind="hier") for the autograd route, by the same kernel, bit for bit.  elementwise() gives the (B, n) terms;
+    collapse_hierarchy() the unconditional logits an evaluation reads."""
+    kind = "hier"
+
+    def __init__(self, parent, mode="conditional", pos_weight=None):
+        super().__init__()
+        self.parent = ops.check_hier_parent("HierarchicalBCE", parent)
+        self.mode = check_hier_mode("HierarchicalBCE", mode)
+        self.pos_weight = check_pos_weight("HierarchicalBCE", pos_weight, self.parent.numel())
+
+    def _state(self, logits):
+        self._on(logits.device, "parent", "pos_weight")
+        if logits.shape[1] != self.parent.numel():
+            raise RuntimeError("HierarchicalBCE holds %d findings, the logits have %d columns" % (self.parent.numel(), logits.shape[1]))
+        return Loss("hier", True, pos_weight=self.pos_weight, parent=self.parent, mode=self.mode)
+
+
+@torch.no_grad()
+def collapse_hierarchy(logits, parent, return_prob=False):
+    """The unconditional logits of (B, n) conditional ones (cx_hier_collapse): a root keeps its logit bit for bit, any other finding gets
+    z = log P - log(1 - P) with P the product of the sigmoids along its path from the root, so that sigmoid(z) = P; everything that
+    takes (B, n) logits -- evaluation losses, AUROC, bootstrap, DeLong, calibration, ensembles -- takes z.  parent: the table of
+    HierarchicalBCE (a list, a CPU tensor, or the int32 device tensor a model holds as `loss_parent`).  return_prob: (z, P)."""
+    if not logits.is_cuda:
+        raise RuntimeError("collapse_hierarchy runs on the GPU only (cx_hier_collapse); there is no CPU fallback")
+    if logits.dim() != 2 or logits.shape[1] == 0:
+        raise RuntimeError("collapse_hierarchy takes (B, n) logits (got %s)" % (tuple(logits.shape),))
+    x = logits.detach().contiguous().float()
+    if isinstance(parent, torch.Tensor) and parent.is_cuda:
+        parent = parent.to(device=x.device, dtype=torch.int32).contiguous()
+    z = torch.empty_like(x)
+    p = torch.empty_like(x) if return_prob else None
+    if x.shape[0]:
+        ops.hier_collapse(x, parent, z, p)
+    else:
+        ops.check_hier_parent("collapse_hierarchy", parent.cpu() if isinstance(parent, torch.Tensor) else parent, x.shape[1])
+    return (z, p) if return_prob else z

@@ -123,7 +123,7 @@ class FusedNet(nn.Module):
         self._head_kind = "linear"       # set_head(): "csra" adds the buffer head_attn = [lambda, T]; "pcam" adds nothing
 
     def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
-                 alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None):
+                 alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None):
         """The loss of forward_backward.  ignore_negative: a target < 0 (an uncertain label kept as -1, the U-Ignore policy) adds no
         loss and no gradient; the divisor stays the batch size.  pos_weight: None, or n_classes positive-term weights as in torch's
         BCEWithLogitsLoss(pos_weight).  Either option routes the step through cx_bce_masked_fwd_bwd, which skips every target < 0:
@@ -176,10 +176,26 @@ class FusedNet(nn.Module):
         in one fp32 tensor, `loss_class_weight`, neither buffer nor parameter, under the storage rule of the weights: a repeated call
         with the same shape copies into the held storage, which a captured step's replay sees (as it sees an in-place change);
         from no weights to weights or back needs a new capture.  Nothing changes per step, and the data-parallel step needs nothing
-        new.  At test time loss.collapse_multiclass(logits) gives the binary (B, n) logits z = z_positive - z_negative."""
+        new.  At test time loss.collapse_multiclass(logits) gives the binary (B, n) logits z = z_positive - z_negative.
+
+        kind="hier" (parent=, mode="conditional" | "unconditional", pos_weight=None) is the hierarchical label loss over a tree of
+        findings (Chen et al., MIDL 2019; the conditional training of Pham et al., 2019; cx_hier_fwd_bwd, whose arithmetic stands in
+        include/chexpert_hip.h): every logit is the logit of P(finding | its parent is positive).  parent: one entry per output of
+        the head, the index of the finding's parent or -1 for a root, parents before children, no path longer than 8
+        (data.CHEXPERT_PARENT for the 14 CheXpert findings); a table of another length is a ValueError.  'conditional' is the masked
+        cross-entropy in which an element also drops out where an ancestor's target is not positive (< 0.5, or ignored);
+        'unconditional' is the cross-entropy of the product of the sigmoids along the path from the root.  Both skip every target
+        < 0 (ignore_negative=True is refused: there is nothing left to decide), take soft targets and accept pos_weight.  The
+        table lives in one int32 device tensor, `loss_parent`, under the storage rule of the weights: a repeated call with a table
+        of the same length copies into the held storage, which a captured step's replay sees (as it sees an in-place change; such
+        a change is the caller's to keep a valid table).  The mode is passed by value, like the margin: a change of mode, like a
+        change of kind or from no pos_weight to weights, needs a new capture.  Nothing changes per step; the loss is a sum over
+        elements with divisor B, so the data-parallel step reduces it as it does the cross-entropy.  At test time
+        loss.collapse_hierarchy(logits, model.loss_parent) gives the unconditional logits; class_cam, Grad-CAM and heads.class_maps
+        work on the conditional logits as they are, so their maps show the evidence for a finding GIVEN its parent."""
         self._loss.set(next(self.parameters()).device, self._n_classes(), ignore_negative, pos_weight, kind=kind, prior=prior,
                        margin=margin, lr_aux=lr_aux, gamma=gamma, alpha=alpha, gamma_pos=gamma_pos, gamma_neg=gamma_neg, clip=clip,
-                       class_weight=class_weight)
+                       class_weight=class_weight, parent=parent, mode=mode)
         return self
 
     # ---- the global pooling in front of the classifier
@@ -317,7 +333,8 @@ class FusedNet(nn.Module):
     def loss_state(self):
         """What set_loss(kind=...) holds beyond the model's state_dict, as CPU tensors and floats: {kind, aux, prior, margin, lr_aux}
         (aux, prior and lr_aux are None for kind 'bce').  Kinds 'focal' and 'asl' add `focus`, the four numbers of `loss_focus`, kind
-        'multiclass' adds `class_weight` (the (n, 3) table, or None).  A checkpoint keeps it beside the weights."""
+        'multiclass' adds `class_weight` (the (n, 3) table, or None), kind 'hier' adds `parent` (the int32 table) and `mode` (the name).  A
+        checkpoint keeps it beside the weights."""
         return self._loss.state()
 
     def load_loss_state(self, d):
@@ -325,7 +342,8 @@ class FusedNet(nn.Module):
         are copied in (into the held storage when there is one for this number of classes).  Kind 'bce' leaves the options of
         the cross-entropy (ignore_negative, pos_weight) as they are.  Kinds 'focal' and 'asl' set the loss with the stored `focus`
         (checked like set_loss's operands) and keep the pos_weight the model holds.  Kind 'multiclass' sets the loss with the stored
-        `class_weight`.  Returns self."""
+        `class_weight`.  Kind 'hier' sets the loss with the stored `parent` and `mode` and keeps the pos_weight the model holds.
+        Returns self."""
         self._loss.load_state(d, next(self.parameters()).device, self._n_classes())
         return self
 
@@ -381,7 +399,8 @@ class FusedNet(nn.Module):
         and a train-mode step ends with the update of its auxiliary scalars (`loss_aux`), from the gradients of this step; the
         eval-mode step computes the gradients and leaves `loss_aux` alone.  After set_loss(kind="focal" | "asl") the loss is the
         focal / asymmetric loss (ops.asl_fwd_bwd), in either mode.  After set_loss(kind="multiclass") the logits are (B, 3n) against
-        the (B, n) target and the loss is the three-way softmax cross-entropy per finding (ops.mc3_fwd_bwd), in either mode."""
+        the (B, n) target and the loss is the three-way softmax cross-entropy per finding (ops.mc3_fwd_bwd), in either mode.  After
+        set_loss(kind="hier") the loss is the hierarchical one over the held parent table (ops.hier_fwd_bwd), in either mode."""
         eng = self._eng()
         if input_grad is not None:
             check_input_grad(input_grad, x)
@@ -402,7 +421,7 @@ class FusedNet(nn.Module):
 
 
 # what set_loss holds, readable on the model (read-only: set_loss writes; a tensor may be written in place)
-for _name in ("kind", "ignore_negative", "pos_weight", "margin", "aux", "prior", "lr_aux", "focus", "class_weight", "daux"):
+for _name in ("kind", "ignore_negative", "pos_weight", "margin", "aux", "prior", "lr_aux", "focus", "class_weight", "parent", "mode", "daux"):
     setattr(FusedNet, ("_loss_" if _name == "daux" else "loss_") + _name, property(lambda self, _name=_name: getattr(self._loss, _name)))
 
 

@@ -10,8 +10,8 @@ import torch
 
 from . import _lib as L
 from ._lib import (BOOT_MAX_POINTS, BOOT_MAX_TILES, BOOT_MAX_UNITS, BOOT_SENS, BOOT_SPEC, BOOT_TILE, CALIB_MAX_BINS, CALIB_MAX_ITER,
-                   CALIB_METHODS, DELONG_MAX_ROWS, DELONG_TILE, DELONG_WG_ENTRIES, EPI_JOIN, EPI_MASK, EPI_STORE, MODE_CONV, MODE_POOL2,
-                   MODE_STEM, PRO_AFFINE2, PRO_AFFINE_RELU, PRO_JOIN, PRO_NONE, CxConv, CxWgrad, check, lib, ptr, require_cuda, stream_ptr)
+                   CALIB_METHODS, DELONG_MAX_ROWS, DELONG_TILE, DELONG_WG_ENTRIES, EPI_JOIN, EPI_MASK, EPI_STORE, HIER_MAX_LABELS, HIER_MAX_PATH,
+                   MODE_CONV, MODE_POOL2, MODE_STEM, PRO_AFFINE2, PRO_AFFINE_RELU, PRO_JOIN, PRO_NONE, CxConv, CxWgrad, check, lib, ptr, require_cuda, stream_ptr)
 import ctypes as C
 
 
@@ -737,6 +737,80 @@ def mc3_collapse(logits, z, p_unc=None):
     _f32(z, p_unc)
     require_cuda(logits, z, p_unc)
     check(lib().cx_mc3_collapse(ptr(logits), ptr(z), ptr(p_unc), B, n, stream_ptr()), "cx_mc3_collapse")
+    return z
+
+
+HIER_MODES = {"conditional": 0, "unconditional": 1}          # cx_hier_fwd_bwd's mode
+
+
+def check_hier_parent(who, parent, n=None):
+    """The parent table of the hierarchical loss, checked on the host (ValueError in the name of `who`) and returned as a CPU int32
+    vector: at most HIER_MAX_LABELS entries (n of them where n is given), entry k either -1 (a root) or in [0, k) (parents come
+    before children, so the table has no cycle), no path -- a node and its ancestors -- longer than HIER_MAX_PATH."""
+    try:
+        p = torch.as_tensor(parent).detach().cpu().reshape(-1)
+        if p.numel() and (p.dtype.is_floating_point or p.dtype == torch.bool) and not bool((p == p.round()).all()):
+            raise ValueError
+        p = p.to(torch.int64)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("%s takes a parent table of integers (got %r)" % (who, parent))
+    if p.numel() < 1 or p.numel() > HIER_MAX_LABELS or (n is not None and p.numel() != n):
+        raise ValueError("%s takes a parent table of %s entries (got %d)"
+                         % (who, "1 .. %d" % HIER_MAX_LABELS if n is None else "%d, one per output of the head" % n, p.numel()))
+    table, depth = p.tolist(), []
+    for k, a in enumerate(table):
+        if a < -1 or a >= k:
+            raise ValueError("%s: parent[%d] = %d; an entry is -1 (a root) or the index of an EARLIER label" % (who, k, a))
+        depth.append(1 if a < 0 else depth[a] + 1)
+        if depth[k] > HIER_MAX_PATH:
+            raise ValueError("%s: label %d has %d ancestors; a path holds at most %d labels" % (who, k, depth[k] - 1, HIER_MAX_PATH))
+    return p.to(torch.int32)
+
+
+def _hier_parent(who, parent, n, device):
+    """The table as the kernels take it: an int32 (n,) tensor on `device` is the caller's to have checked (Loss.set did: its values
+    stay on the device); anything on the host -- a list, a CPU tensor -- is checked here and copied over."""
+    if isinstance(parent, torch.Tensor) and parent.is_cuda:
+        assert parent.dtype == torch.int32 and parent.is_contiguous() and tuple(parent.shape) == (n,) and parent.device == device
+        return parent
+    p = check_hier_parent(who, parent, n)
+    return p if device.type != "cuda" else p.to(device)
+
+
+def hier_fwd_bwd(logits, target, parent, pos_weight, mode, loss, loss_elem, dlogits, grad_scale=1.0):
+    """The hierarchical label loss of the (B, n) logits with d loss / d logits in one launch (cx_hier_fwd_bwd): parent the int32 (n,)
+    table ON THE DEVICE, read by the kernel (a captured step sees a table rewritten in place), or a host table, which is checked
+    (check_hier_parent) and copied over; mode 0 / 'conditional' or 1 / 'unconditional', passed by value; a target < 0 is ignored,
+    pos_weight (fp32 (n,), or None) weights the positive term.  loss (1,), loss_elem and dlogits (B, n) are optional; grad_scale
+    multiplies dlogits alone."""
+    if isinstance(mode, str):
+        mode = HIER_MODES.get(mode)
+    if not isinstance(mode, int) or isinstance(mode, bool) or mode not in (0, 1):
+        raise ValueError("hier_fwd_bwd takes mode 0 / 'conditional' or 1 / 'unconditional' (got %r)" % (mode,))
+    if logits.dim() == 2 and logits.shape[1] > HIER_MAX_LABELS:
+        raise ValueError("hier_fwd_bwd takes at most %d labels (got %d)" % (HIER_MAX_LABELS, logits.shape[1]))
+    B, n = _loss_operands(logits, target, (pos_weight,), loss, (loss_elem, dlogits))
+    assert B >= 1 and n >= 1
+    parent = _hier_parent("hier_fwd_bwd", parent, n, logits.device)
+    require_cuda(logits, target, parent, pos_weight, loss, loss_elem, dlogits)
+    check(lib().cx_hier_fwd_bwd(ptr(logits), ptr(target), ptr(parent), ptr(pos_weight), mode, ptr(loss), ptr(loss_elem), ptr(dlogits),
+                                grad_scale, B, n, stream_ptr()), "cx_hier_fwd_bwd")
+
+
+def hier_collapse(logits, parent, z, p=None):
+    """The unconditional logits of (B, n) conditional ones (cx_hier_collapse): a root's z is its logit bit for bit, any other
+    z = log P - log(1 - P) of the product P of the sigmoids along its path, so that sigmoid(z) = P; p (optional) = P.  parent as
+    in hier_fwd_bwd.  Returns z."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape[0] >= 1 and logits.shape[1] >= 1
+    B, n = logits.shape
+    if n > HIER_MAX_LABELS:
+        raise ValueError("hier_collapse takes at most %d labels (got %d)" % (HIER_MAX_LABELS, n))
+    assert z is not None and tuple(z.shape) == (B, n) and (p is None or tuple(p.shape) == (B, n))
+    assert all(t is None or t.device == logits.device for t in (z, p))
+    _f32(z, p)
+    parent = _hier_parent("hier_collapse", parent, n, logits.device)
+    require_cuda(logits, parent, z, p)
+    check(lib().cx_hier_collapse(ptr(logits), ptr(parent), ptr(z), ptr(p), B, n, stream_ptr()), "cx_hier_collapse")
     return z
 
 

@@ -18,6 +18,10 @@ forward (loss.collapse_multiclass: z = z_positive - z_negative, sigmoid(z) = p1 
 Any other count is an error, and the checkpoints of a folder must agree.  The pooling of the head (chexpert.py --pool) is read from
 the checkpoint's `pool_state` (none: the average); the checkpoints of a folder must agree on it too.  The head (chexpert.py --head) is
 read from the checkpoint's `head_state` (none: linear; csra or pcam) in the same way.
+
+A checkpoint of a `--loss hier` run carries the parent table of its findings in `loss_state`: a table of 14 entries reads all 14
+findings of the csv (one probability column each), and the conditional logits of every forward become unconditional ones on the GPU
+(loss.collapse_hierarchy) before --calibration and --tta act on them.  The checkpoints of a folder must agree on the table.
 """
 import argparse
 import os
@@ -86,6 +90,14 @@ def head_is_multiclass(state_dict, key, n, path=""):
     return rows == 3 * n
 
 
+def hier_parent_of(ck):
+    """The parent table of a --loss hier checkpoint (its `loss_state`) as a list of ints; None for a checkpoint of another loss."""
+    st = ck.get("loss_state") or {}
+    if st.get("kind") != "hier":
+        return None
+    return [int(v) for v in torch.as_tensor(st["parent"]).tolist()]
+
+
 @torch.no_grad()
 def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None, cal=None, collapse=False):
     """DataFrame indexed by study ('.../patient64541/study1') with one probability column per finding (predict.py:33-52).
@@ -99,18 +111,26 @@ def predict(model, dataset, batch_size, device, tta=1, tta_seed=0, clahe=None, c
     clahe: an augment.Clahe (or None): the uint8 batch is equalised once on the GPU, before the forward and before each draw's warp.
     cal: a calibration fit (or None): every forward's probabilities are sigmoid(a z + b) (`probabilities`), before the mean over the draws.
     collapse: the model has the three-way head of a --uncertain multiclass run; every forward's (B, 3n) logits become the binary
-    z = z_positive - z_negative (loss.collapse_multiclass) before `probabilities`."""
+    z = z_positive - z_negative (loss.collapse_multiclass) before `probabilities`.  A parent table as `collapse`: the model was trained
+    with the hierarchical loss; every forward's conditional logits become unconditional ones (loss.collapse_hierarchy) there."""
     import pandas as pd
     from .data import extract_patient_ids
     if tta < 1:
         raise ValueError("tta must be >= 1")
     model.eval()
     forward = model
-    if collapse:
+    if collapse is True:
         from .loss import collapse_multiclass
 
         def forward(xb):
             return collapse_multiclass(model(xb))
+    elif collapse:
+        from .loss import collapse_hierarchy
+        from .ops import check_hier_parent
+        table = collapse if isinstance(collapse, torch.Tensor) and collapse.is_cuda else check_hier_parent("predict", collapse).to(device)
+
+        def forward(xb):
+            return collapse_hierarchy(model(xb), table)
     probs, studies = [], []
     for k in range(0, len(dataset), batch_size):
         items = [dataset[i] for i in range(k, min(k + batch_size, len(dataset)))]
@@ -143,8 +163,6 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise RuntimeError("predict runs on the GPU only (there is no CPU path)")
     device = torch.device("cuda:%d" % args.cuda)
-    ds = ChexpertCSV(args.data_path, "test", args.resize, mini_data=args.mini_data)
-    n = len(ds.attr_names)
     key = "classifier.weight" if args.model == "densenet121" else "fc.weight"
 
     def build(width, pool_state, head_state):
@@ -161,6 +179,17 @@ def main(argv=None):
         print("Running ensemble prediction using %d checkpoints." % len(files))
     else:
         files = [args.restore_path]
+    # a --loss hier checkpoint carries its parent table (`loss_state`): the table says how many findings the run read (14: --labels
+    # all) and how the conditional logits are collapsed; the checkpoints of a folder must agree on it
+    from .data import ATTR_NAMES, ATTR_NAMES_ALL
+    first = torch.load(files[0], map_location=device)
+    parent = hier_parent_of(first)
+    if parent is not None and len(parent) not in (len(ATTR_NAMES), len(ATTR_NAMES_ALL)):
+        raise ValueError("checkpoint %s: its parent table has %d entries; predict reads the %d competition findings or all %d"
+                         % (files[0], len(parent), len(ATTR_NAMES), len(ATTR_NAMES_ALL)))
+    ds = ChexpertCSV(args.data_path, "test", args.resize, mini_data=args.mini_data,
+                     labels="all" if parent is not None and len(parent) == len(ATTR_NAMES_ALL) else "competition")
+    n = len(ds.attr_names)
     frames = []
     clahe = None
     if args.clahe:
@@ -172,10 +201,13 @@ def main(argv=None):
         cal = load_calibration(args.calibration)
     model = wide = None
     for f in files:
-        ck = torch.load(f, map_location=device)
+        ck = first if f == files[0] else torch.load(f, map_location=device)
         sd, pool_kind = ck["state_dict"], (ck.get("pool_state") or {}).get("kind", "avg")
         head_kind = (ck.get("head_state") or {}).get("kind", "linear")
         w = head_is_multiclass(sd, key, n, f)
+        if hier_parent_of(ck) != parent:
+            raise ValueError("the checkpoints of %s disagree: %s has the parent table %s, %s has %s (None: no hierarchical loss)"
+                             % (args.restore_path, files[0], parent, f, hier_parent_of(ck)))
         if model is None:                   # the first checkpoint's head decides; the others of a folder must agree
             model, wide = build(n * (3 if w else 1), ck.get("pool_state"), ck.get("head_state")), w
         elif head_kind != model.head_kind:
@@ -188,7 +220,8 @@ def main(argv=None):
             raise ValueError("the checkpoints of %s disagree: %s has %d logits per finding, %s has %d" % (args.restore_path, files[0],
                                                                                                        3 if wide else 1, f, 3 if w else 1))
         model.load_state_dict(sd)
-        frames.append(predict(model, ds, args.batch_size, device, tta=args.tta, tta_seed=args.tta_seed, clahe=clahe, cal=cal, collapse=wide))
+        frames.append(predict(model, ds, args.batch_size, device, tta=args.tta, tta_seed=args.tta_seed, clahe=clahe, cal=cal,
+                              collapse=wide if parent is None else parent))
     df = frames[0] if len(frames) == 1 else sum(frames[1:], frames[0]) / float(len(frames))      # mean over checkpoints
     df.to_csv(args.output_path)
     return df

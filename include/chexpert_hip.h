@@ -416,6 +416,38 @@ int cx_mc3_fwd_bwd(const float* logits, const float* target, const float* class_
  * given, p_unc[b][k] = e2 / s with m, e, s as above.  One thread per (b, k), no reduction; any B * n <= INT_MAX - 256 (a whole
  * validation table in one call).  CX_EINVAL before anything is launched: NULL logits / z, B < 1, n < 1, the size cap.            */
 int cx_mc3_collapse(const float* logits, float* z, float* p_unc, int B, int n, void* stream);
+/* Hierarchical label loss (Chen et al., "Deep hierarchical multi-label classification of chest X-ray images", MIDL 2019: HLCP and HLUP;
+ * the conditional training of Pham et al., 2019) on the (B, n) logits of a step, with d loss / d logits, one launch (loss.hip).  The
+ * labels form a forest: parent[k] == -1 is a root, else 0 <= parent[k] < k (parents come before children); parent is int32 [n] ON THE
+ * DEVICE, read by the kernel, so a captured step sees a table rewritten in place.  path(k) is k and its ancestors, root first, at most
+ * CX_HIER_MAX_PATH nodes; n <= CX_HIER_MAX_LABELS.  EVERY logit is the logit of the conditional probability P(k | parent(k) positive),
+ * in both modes.  target: the (B, n) table of cx_bce_masked_fwd_bwd (t < 0 ignored, soft targets in [0, 1] valid); pos_weight: fp32 [n]
+ * on the device, or NULL.
+ *   mode 0, conditional: element (b, k) is live iff t >= 0 and the target of every proper ancestor is >= 0.5; a live element is the
+ *     element of cx_bce_masked_fwd_bwd (its unweighted or weighted expressions, its fp32 or double sum, its stride and tree), any other
+ *     gives loss_elem = 0 and dlogits = 0.  A table of roots gives cx_bce_masked_fwd_bwd's bits in all three outputs.
+ *   mode 1, unconditional: the cross-entropy of P_k = prod_{j in path(k)} sigmoid(z_j); element (b, k) is live iff t >= 0 (ancestors'
+ *     targets are not read).  Per node, from one e = log1pf(expf(-|z|)):  lp = -(max(-z, 0) + e) = log sigmoid(z),  lq = -(max(z, 0) + e)
+ *     = log sigmoid(-z).  Along the path, root first:  u = sum lp_j = log P_k;  a_j = (sum_{i before j} lp_i) + lq_j, the logarithms of
+ *     the positive terms of 1 - P = sum_j (prod_{i<j} p_i) q_j.  l1m = log(1 - P_k) = log1pf(-expf(u)) where u <= -ln 2, else
+ *     max_j a_j + logf(sum_j expf(a_j - max)): no 1 - P is formed from a rounded P, and a small loss keeps its digits.  With
+ *     w = pos_weight ? pos_weight[k] : 1:   l = -w t u - (1 - t) l1m,   dl/dz_j = (1 - t) expf(u + lq_j - l1m) - w t q_j  for every j in
+ *     path(k), q_j = 1 / (1 + expf(z_j)) (the exponent form: q_j expf(u - l1m) is 0 * inf at z = +1e4).  dlogits[b][j] is the sum of these
+ *     over the k of j's subtree in ascending k, times 1 / B * grad_scale.  A pos_weight of ones gives the bits of NULL.
+ * loss = sum l / B (the divisor stays the batch size).  loss (one float), loss_elem and dlogits (B, n) may each be NULL; each alone
+ * has the bits it has beside the others.  One workgroup, a fixed tree (the sum in double in mode 1), no atomics: bit-reproducible.
+ * CX_EINVAL before anything is launched: NULL logits / target / parent, B < 1, n < 1, n > CX_HIER_MAX_LABELS, a mode other than 0 / 1,
+ * B * n > INT_MAX - 256.  The table's VALUES are the caller's to keep in range (it is device memory); for memory safety alone the
+ * kernels read an entry outside [-1, k) as a root and cut a path after CX_HIER_MAX_PATH nodes.  Additive entry points of ABI 10.    */
+#define CX_HIER_MAX_LABELS 64
+#define CX_HIER_MAX_PATH 8
+int cx_hier_fwd_bwd(const float* logits, const float* target, const int* parent, const float* pos_weight, int mode, float* loss,
+                    float* loss_elem, float* dlogits, float grad_scale, int B, int n, void* stream);
+/* The test-time form of those logits: the logit of the UNCONDITIONAL probability.  A root's z is its logit, copied bit for bit; any other
+ * z[b][k] = u - l1m with the expressions of mode 1, so that sigmoid(z) = P_k; p (optional) = expf(u).  One thread per (b, k), no
+ * reduction; any B (a whole validation table in one call).  CX_EINVAL before anything is launched: NULL logits / parent / z, B < 1,
+ * n < 1, n > CX_HIER_MAX_LABELS, B * n > INT_MAX - 256.                                                                             */
+int cx_hier_collapse(const float* logits, const int* parent, float* z, float* p, int B, int n, void* stream);
 /* loss = CrossEntropyLoss(logits, target) (mean over the batch of logsumexp - logit[target]);
  * dlogits = (softmax - onehot)/B * grad_scale; loss_elem (optional) = the per-sample terms
  * (models/test_model.py:118, :143, :331: the CIFAR harness criterion)                              */

@@ -1,0 +1,753 @@
+"""GPU: the hierarchical label loss -- cx_hier_fwd_bwd in both modes against the float64 oracle (shared with tests/test_hier_cpu.py, which
+checks it against central differences and the masked cross-entropy), mode 0 against cx_bce_masked_fwd_bwd bit for bit and its masking,
+mode 1 on confident elements one by one and at +-1e4, cx_hier_collapse, FusedNet.set_loss(kind="hier") in the fused step against the
+autograd route, under graph replay and data-parallel, and the command line with predict."""
+import json
+import math
+import os
+import time
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from chexpert_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+CHEXPERT = [-1, -1, 1, -1, 3, 3, 3, 6, 3, -1, -1, -1, -1, -1]
+LN2 = math.log(2.0)
+MODES = ["conditional", "unconditional"]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from chexpert_amd import _lib
+    _lib.lib()          # fail loudly if the HIP library is missing
+    return torch.device("cuda:0")
+
+
+def close(got, want, rel, what=""):
+    """The bound of tests/test_kernels_gpu.py: max error against the largest reference magnitude."""
+    scale = want.abs().max().item() + 1e-6
+    err = (got - want).abs().max().item()
+    print("%s: max err %.3e vs scale %.3e (rel %.2e)" % (what, err, scale, err / scale))
+    assert err <= rel * scale, "%s: max err %.3e vs scale %.3e (rel %.2e)" % (what, err, scale, err / scale)
+
+
+# ------------------------------------------------------------------------------------------------ float64 oracle (as in test_hier_cpu.py)
+def paths_of(parent):
+    """path(k) for every k: k and its ancestors, root first."""
+    out = []
+    for k, a in enumerate(parent):
+        out.append(([] if a < 0 else out[a]) + [k])
+    return out
+
+
+def log1mexp(u):
+    """log(1 - exp(u)) for u < 0: log(-expm1(u)) above -ln 2, log1p(-exp(u)) below; each branch sees only its own arguments, so autograd
+    meets no infinity behind the where."""
+    hi = u > -LN2
+    return torch.where(hi, torch.log(-torch.expm1(torch.where(hi, u, -torch.ones_like(u)))),
+                       torch.log1p(-torch.exp(torch.where(hi, -torch.ones_like(u), u))))
+
+
+def _elem64(x, t, parent, mode, w):
+    """The (B, n) element losses in float64, differentiable in x.  mode 0: the cross-entropy of sigmoid(x_k) where t >= 0 and every
+    proper ancestor's target is >= 0.5.  mode 1: the cross-entropy of P_k = prod_{path} sigmoid(x_j) where t >= 0; log P_k is a sum of
+    logsigmoids.  w: None or (n,) weights of the positive term."""
+    B, n = x.shape
+    paths = paths_of(parent)
+    t = t.double()
+    live = t >= 0
+    tt = torch.where(live, t, torch.zeros_like(t))
+    ww = torch.ones(n, dtype=torch.float64) if w is None else w.double()
+    if mode == 0:
+        for k, p in enumerate(paths):
+            for a in p[:-1]:
+                live[:, k] &= t[:, a] >= 0.5
+        le = -(ww * tt * F.logsigmoid(x) + (1 - tt) * F.logsigmoid(-x))
+    else:
+        ls = F.logsigmoid(x)
+        u = torch.stack([ls[:, p].sum(1) for p in paths], 1)
+        le = -(ww * tt * u + (1 - tt) * log1mexp(u))
+    return torch.where(live, le, torch.zeros_like(le))
+
+
+def oracle(logits, t, parent, mode, w=None):
+    """(loss, element losses (B, n), d loss / d logits (B, n)) by autograd in float64; loss = sum of elements / B."""
+    x = logits.double().clone().requires_grad_(True)
+    le = _elem64(x, t, parent, mode, w)
+    loss = le.sum() / x.shape[0]
+    loss.backward()
+    return loss.detach(), le.detach(), x.grad
+
+
+def case(seed, B, parent):
+    """Logits uniform in +-8, targets from {-1, 0, 1, 0.3, 0.7}, weights in [0.5, 8]."""
+    n = len(parent)
+    x = synth.uniform(seed, (B, n), -8.0, 8.0)
+    t = torch.tensor([-1.0, 0.0, 1.0, 0.3, 0.7])[synth.uniform(seed + 1, (B, n), 0.0, 5.0).long().clamp(max=4)]
+    return x, t, synth.uniform(seed + 2, (n,), 0.5, 8.0)
+
+
+def confident_case(which, B=64, parent=CHEXPERT):
+    """0: all logits in [4, 12], t = 1.  1: all in [-12, -4], t = 0 (the smallest loss, a product of three such sigmoids, is about
+    5e-15).  2: confident-positive inner nodes (t = 1) over confident-negative leaves (t = 0)."""
+    n = len(parent)
+    mag = synth.uniform(91 + which, (B, n), 4.0, 12.0)
+    if which == 0:
+        return mag, torch.ones(B, n)
+    if which == 1:
+        return -mag, torch.zeros(B, n)
+    inner = torch.tensor([k in parent for k in range(n)])
+    return torch.where(inner, mag, -mag), inner.float().expand(B, n).contiguous()
+
+
+# a forest of 64 labels with a chain of depth 8 inside (labels 10 .. 17), some two-level families and roots
+WIDE = [-1] * 10 + [-1, 10, 11, 12, 13, 14, 15, 16] + [k - 18 for k in range(18, 28)] + [16 if k % 3 == 0 else -1 for k in range(28, 64)]
+TABLES = {(1, 1): [-1], (1, 3): [-1, 0, 1], (3, 5): [-1, 0, 0, -1, 3], (256, 14): CHEXPERT, (300, 14): CHEXPERT, (5, 64): WIDE}
+
+
+def run(dev, x, t, parent, w, mode, outputs="led", grad_scale=1.0):
+    """cx_hier_fwd_bwd on device copies: (loss, loss_elem, dlogits), each None where `outputs` leaves its letter out."""
+    from chexpert_amd import ops
+    B, n = x.shape
+    loss = torch.full((1,), 7.0, device=dev) if "l" in outputs else None
+    le = torch.full((B, n), 7.0, device=dev) if "e" in outputs else None
+    dl = torch.full((B, n), 7.0, device=dev) if "d" in outputs else None
+    par = ops.check_hier_parent("run", parent, n).to(dev)                # (a device table is the caller's to have checked)
+    ops.hier_fwd_bwd(x.to(dev), t.to(dev), par, None if w is None else w.to(dev), mode, loss, le, dl, grad_scale)
+    return loss, le, dl
+
+
+# ------------------------------------------------------------------------------------------------ the kernel
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("B,n", sorted(TABLES))
+def test_kernel_against_float64(dev, B, n, mode):
+    """Both modes, with and without pos_weight, against the float64 oracle at the bounds of the project's loss kernels: the loss to
+    1e-5 max(1, |ref|), loss_elem and dlogits to 1e-5 of the largest reference magnitude.  Then: each output alone has the same bits,
+    grad_scale scales the gradient alone, two calls give equal bits, and -- in mode 1, whose weight multiplies the positive term as a
+    factor -- a pos_weight of ones gives the bits of the call without one.  (In mode 0 the header's other statement decides: a live
+    element runs WeightedBceTerm's expressions and its double sum when weights are given, MaskedBceTerm's and its fp32 sum when not,
+    so that a table of roots is cx_bce_masked_fwd_bwd bit for bit either way; those two differ in the last bits for weights of
+    one, as they do in cx_bce_masked_fwd_bwd itself, and the test below pins mode 0 to that kernel instead.)
+
+    The (1, 1) input is stated, not drawn: x = -3.74 with t = 1, a live root whose loss and gradient are both of order 1."""
+    parent = TABLES[(B, n)]
+    assert len(parent) == n and (n != 64 or max(len(p) for p in paths_of(parent)) == 8)
+    x, t, w = case(1000 + 10 * B + n, B, parent)
+    if (B, n) == (1, 1):
+        x, t = torch.tensor([[-3.74]]), torch.tensor([[1.0]])
+    for pw in (None, w):
+        ref, le_ref, g_ref = oracle(x, t, parent, mode, pw)
+        loss, le, dl = run(dev, x, t, parent, pw, mode)
+        print("(%d, %d) mode %d weighted=%s: loss %.7f, float64 %.7f" % (B, n, mode, pw is not None, loss.item(), ref.item()))
+        assert abs(loss.item() - ref.item()) <= 1e-5 * max(1.0, abs(ref.item()))
+        close(le.cpu().double(), le_ref, 1e-5, "loss_elem")
+        close(dl.cpu().double(), g_ref, 1e-5, "dlogits")
+        assert bool((le[t.to(dev) < 0] == 0).all()) and bool((dl.cpu()[(t < 0) & torch.tensor([k not in parent for k in range(n)])] == 0).all())
+        for letter, full in (("l", loss), ("e", le), ("d", dl)):        # each output alone
+            alone = [v for v in run(dev, x, t, parent, pw, mode, outputs=letter) if v is not None]
+            assert len(alone) == 1 and torch.equal(alone[0], full), letter
+        l2, e2, d2 = run(dev, x, t, parent, pw, mode, grad_scale=0.25)
+        assert torch.equal(l2, loss) and torch.equal(e2, le) and torch.equal(d2, dl * 0.25)
+        again = run(dev, x, t, parent, pw, mode)
+        assert all(torch.equal(a, b) for a, b in zip(again, (loss, le, dl)))
+    if mode == 1:
+        plain, ones = run(dev, x, t, parent, None, mode), run(dev, x, t, parent, torch.ones(n), mode)
+        assert all(torch.equal(a, b) for a, b in zip(plain, ones))
+
+
+@pytest.mark.parametrize("B,n", [(1, 1), (3, 5), (256, 14), (300, 14)])
+def test_conditional_mode_with_a_table_of_roots_is_the_masked_bce(dev, B, n):
+    from chexpert_amd import ops
+    x, t, w = case(200 + B, B, [-1] * n)
+    for pw in (None, w, torch.ones(n)):
+        loss, le, dl = run(dev, x, t, [-1] * n, pw, 0)
+        l0, e0, d0 = torch.zeros(1, device=dev), torch.zeros(B, n, device=dev), torch.zeros(B, n, device=dev)
+        ops.bce_masked_fwd_bwd(x.to(dev), t.to(dev), None if pw is None else pw.to(dev), l0, e0, d0)
+        assert torch.equal(loss, l0) and torch.equal(le, e0) and torch.equal(dl, d0)
+        assert float(dl.abs().max()) > 0 or bool((t < 0).all())
+
+
+def test_conditional_mode_masks_under_an_ancestor_that_is_not_positive(dev):
+    """A child under an ancestor with target 0, 0.3 or -1 has loss 0 and gradient 0 exactly; under 0.7 or 1 it has the BCE's, bit for
+    bit.  The grandchild of a chain needs both ancestors."""
+    from chexpert_amd import ops
+    chain = [-1, 0, 1]
+    anc = [0.0, 0.3, -1.0, 0.7, 1.0]
+    rows = [(a, b, c) for a in anc for b in anc for c in (0.0, 1.0, 0.3, -1.0)]
+    t = torch.tensor(rows)
+    B = len(rows)
+    x = synth.uniform(301, (B, 3), -8.0, 8.0)
+    for pw in (None, synth.uniform(302, (3,), 0.5, 8.0)):
+        loss, le, dl = run(dev, x, t, chain, pw, 0)
+        l0, e0, d0 = torch.zeros(1, device=dev), torch.zeros(B, 3, device=dev), torch.zeros(B, 3, device=dev)
+        ops.bce_masked_fwd_bwd(x.to(dev), t.to(dev), None if pw is None else pw.to(dev), l0, e0, d0)
+        on1 = (t[:, 0] >= 0.5).to(dev)
+        on2 = on1 & (t[:, 1] >= 0.5).to(dev)
+        assert int(on1.sum()) == 2 * B // 5 and int(on2.sum()) == 4 * B // 25
+        assert torch.equal(le[:, 0], e0[:, 0]) and torch.equal(dl[:, 0], d0[:, 0])
+        for col, on in ((1, on1), (2, on2)):
+            assert bool((le[~on, col] == 0).all()) and bool((dl[~on, col] == 0).all())
+            assert torch.equal(le[on, col], e0[on, col]) and torch.equal(dl[on, col], d0[on, col])
+            live = on & (t[:, col] >= 0).to(dev)
+            assert bool((le[live, col] > 0).all()) and bool((dl[live, col] != 0).all())
+        ref, _, _ = oracle(x, t, chain, 0, pw)
+        assert abs(loss.item() - ref.item()) <= 1e-5 * max(1.0, abs(ref.item())) and loss.item() < l0.item()
+
+
+def test_confident_elements_keep_their_digits(dev):
+    """Mode 1 on the CheXpert tree, the three confident cases: the loss of every element and every gradient within 2e-5 OF ITS OWN
+    float64 value, the bound of the project's tests of the same name.  Measured worst case on the MI355X: 2.7e-6 for a loss and 3.7e-6
+    for a gradient, both on case 1, whose smallest loss is 5.4e-15 (case 0: 6.4e-7 / 7.0e-7; case 2: 1.2e-6 / 1.7e-6); the fp32 torch
+    restatement of tests/test_hier_cpu.py measures 2.1e-6 and 2.7e-6 there."""
+    for which in range(3):
+        z, t = confident_case(which)
+        B = z.shape[0]
+        _, le_ref, g_ref = oracle(z, t, CHEXPERT, 1)
+        assert bool((le_ref > 0).all()) and bool((g_ref != 0).all())
+        _, le, dl = run(dev, z, t, CHEXPERT, None, 1)
+        rl = float(((le.cpu().double() - le_ref).abs() / le_ref).max())
+        rg = float(((dl.cpu().double() - g_ref).abs() / g_ref.abs()).max())
+        print("case %d: worst relative error of an element's loss %.3e, of a gradient %.3e (smallest loss %.3e)" % (which, rl, rg, float(le_ref.min())))
+        assert rl < 2e-5 and rg < 2e-5
+
+
+def test_extremes_stay_finite_and_meet_the_closed_form(dev):
+    """A chain of depth 3 at +-1e4.  All +1e4 with t = 0: 1 - P_k is k + 1 equal terms of e^-1e4, so the element of depth d is
+    1e4 - ln d (the leaf: 1e4 - ln 3); all -1e4 with t = 1: 1e4 x depth.  Everything is finite: the gradient's exponent form is, where
+    q_j exp(u - l1m) is 0 * inf."""
+    chain = [-1, 0, 1]
+    B = 4
+    loss, le, dl = run(dev, torch.full((B, 3), 1e4), torch.zeros(B, 3), chain, None, 1)
+    assert all(bool(torch.isfinite(v).all()) for v in (loss, le, dl))
+    want = torch.tensor([1e4, 1e4 - math.log(2), 1e4 - math.log(3)], dtype=torch.float64)
+    assert float(((le.cpu().double() - want).abs() / want).max()) <= 1e-5
+    assert abs(loss.item() - float(want.sum())) <= 1e-5 * float(want.sum())
+    # every term of 1 - P has the same size: the leaf's gradient reaches each node of its path with 1/3, to the 1e-3 spacing of 1e4
+    assert float((dl.cpu()[:, 2] * B - 1 / 3).abs().max()) < 1e-3 and bool((dl > 0).all())
+    loss, le, dl = run(dev, torch.full((B, 3), -1e4), torch.ones(B, 3), chain, None, 1)
+    assert all(bool(torch.isfinite(v).all()) for v in (loss, le, dl))
+    want = torch.tensor([1e4, 2e4, 3e4], dtype=torch.float64)
+    assert float(((le.cpu().double() - want).abs() / want).max()) <= 1e-5 and abs(loss.item() - 6e4) <= 1e-5 * 6e4
+    assert torch.equal(dl.cpu() * B, torch.tensor([-3.0, -2.0, -1.0]).expand(B, 3))
+    # mode 0 at the same inputs is the masked BCE's
+    loss, le, dl = run(dev, torch.full((B, 3), 1e4), torch.zeros(B, 3), chain, None, 0)
+    assert le.cpu()[:, 0].tolist() == [1e4] * B and bool((le[:, 1:] == 0).all()) and bool(torch.isfinite(dl).all())
+
+
+@pytest.mark.parametrize("B,n", [(3, 5), (1000, 14)])
+def test_collapse(dev, B, n):
+    from chexpert_amd import ops
+    from chexpert_amd.loss import collapse_hierarchy
+    parent = TABLES[(3, 5)] if n == 5 else CHEXPERT
+    x = synth.uniform(400 + B, (B, n), -8.0, 8.0)
+    xd, par = x.to(dev), torch.tensor(parent, dtype=torch.int32, device=dev)
+    z, p = torch.full((B, n), 7.0, device=dev), torch.full((B, n), 7.0, device=dev)
+    assert ops.hier_collapse(xd, par, z, p) is z
+    roots = [k for k, a in enumerate(parent) if a < 0]
+    kids = [k for k, a in enumerate(parent) if a >= 0]
+    assert torch.equal(z[:, roots], xd[:, roots])                       # a root's logit, bit for bit
+    ls = F.logsigmoid(x.double())
+    P = torch.stack([ls[:, q].sum(1) for q in paths_of(parent)], 1).exp()
+    es, ep = float((torch.sigmoid(z).cpu().double() - P).abs().max()), float((p.cpu().double() - P).abs().max())
+    print("(%d, %d): sigmoid(z) within %.3e, p within %.3e of the float64 product" % (B, n, es, ep))
+    assert es <= 1e-6 and ep <= 1e-6
+    for k in kids:                                                      # a child is never more probable than its parent
+        zk, za = z[:, k], z[:, parent[k]]
+        assert bool((zk <= za + 1e-5 * zk.abs().clamp(min=1.0)).all()), k
+    z_alone = torch.empty(B, n, device=dev)
+    ops.hier_collapse(xd, parent, z_alone)                              # a host table is checked and copied over; p is optional
+    assert torch.equal(z_alone, z)
+    for table in (parent, torch.tensor(parent), par):
+        assert torch.equal(collapse_hierarchy(xd, table), z)
+        z2, p2 = collapse_hierarchy(xd, table, return_prob=True)
+        assert torch.equal(z2, z) and torch.equal(p2, p)
+    assert tuple(collapse_hierarchy(xd[:0], parent).shape) == (0, n)
+    with pytest.raises(ValueError):
+        collapse_hierarchy(xd, parent[:-1])
+
+
+# ------------------------------------------------------------------------------------------------ the fused step
+def _net(dev, seed=3, width=14):
+    """densenet121 with a 14-wide head, at the 64 x 64 input of the other loss tests."""
+    import torch.nn as nn
+    from chexpert_amd.models import densenet121
+    torch.manual_seed(seed)
+    model = densenet121(pretrained=False)
+    model.classifier = nn.Linear(model.classifier.in_features, width)
+    return model.to(dev).train(), 64
+
+
+def _twin(dev):
+    a, S = _net(dev)
+    b, _ = _net(dev)
+    b.load_state_dict({k: v.clone() for k, v in a.state_dict().items()})
+    return a, b, S
+
+
+def _targets(seed, B, n=14):
+    """(B, n) targets drawn from {-1, 0, 1, 0.3, 0.7}, as they come (no closure under a tree)."""
+    return torch.tensor([-1.0, 0.0, 1.0, 0.3, 0.7])[synth.uniform(seed, (B, n), 0.0, 5.0).long().clamp(max=4)]
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_fused_step_equals_the_autograd_route(dev, mode):
+    from chexpert_amd import ops
+    from chexpert_amd.loss import HierarchicalBCE, MaskedBCE
+    a, b, S = _twin(dev)
+    B, n = 4, 14
+    x = synth.xray_batch(3500, B, S).to(dev)
+    t = _targets(3510, B).to(dev)
+    w = synth.uniform(3520, (n,), 0.5, 8.0).to(dev)
+    keys = list(a.state_dict().keys())
+    assert a.set_loss(kind="hier", parent=CHEXPERT, mode=mode, pos_weight=w) is a
+    crit = HierarchicalBCE(CHEXPERT, mode=mode, pos_weight=w)
+    assert list(a.state_dict().keys()) == keys and a.loss_step_state() == []      # neither buffer nor parameter; nothing per step
+    assert a.loss_kind == "hier" and a.loss_mode == mode and a.loss_ignore_negative is True and a.loss_focus is None and a.loss_class_weight is None
+    par = a.loss_parent
+    assert par.is_cuda and par.dtype == torch.int32 and par.tolist() == CHEXPERT and torch.equal(a.loss_pos_weight, w)
+    loss_a, logits_a = a.forward_backward(x, t)
+    assert tuple(logits_a.shape) == (B, n)
+    out = b(x)
+    loss_b = crit(out, t)
+    loss_b.backward()
+    assert loss_b.dim() == 0 and torch.equal(loss_a.reshape(()), loss_b.detach())
+    assert torch.equal(logits_a, out.detach())
+    ga, gb = dict(a.named_parameters()), dict(b.named_parameters())
+    for k in ga:
+        assert torch.equal(ga[k].grad, gb[k].grad), k
+    assert max(float(p.grad.abs().max()) for p in ga.values()) > 0
+    # the loss is the float64 oracle's, and so are the element losses outside autograd
+    ref, le_ref, _ = oracle(logits_a.cpu(), t.cpu(), CHEXPERT, MODES.index(mode), w.cpu())
+    print("%s: fused loss %.7f, float64 oracle %.7f" % (mode, loss_a.item(), ref.item()))
+    assert abs(loss_a.item() - ref.item()) <= 1e-5 * max(1.0, abs(ref.item()))
+    le = crit.elementwise(out, t)
+    assert not le.requires_grad and tuple(le.shape) == (B, n)
+    close(le.cpu().double(), le_ref, rel=1e-5, what="elementwise")
+    # backward scales by the incoming gradient
+    xl = logits_a.clone().requires_grad_(True)
+    (3.0 * crit(xl, t)).backward()
+    dl = torch.empty_like(logits_a)
+    ops.hier_fwd_bwd(logits_a, t, a.loss_parent, a.loss_pos_weight, mode, None, None, dl)
+    assert torch.equal(xl.grad, dl * 3.0)
+    # teeth: these are not the gradients of the masked cross-entropy, nor of the other mode
+    zl = logits_a.clone().requires_grad_(True)
+    MaskedBCE(w)(zl, t).backward()
+    other = torch.empty_like(dl)
+    ops.hier_fwd_bwd(logits_a, t, a.loss_parent, a.loss_pos_weight, MODES[1 - MODES.index(mode)], None, None, other)
+    assert not torch.equal(zl.grad, dl) and not torch.equal(other, dl)
+    with pytest.raises(RuntimeError, match="14 findings"):
+        crit(out[:, :5], t[:, :5])
+
+
+def test_set_loss_walk_leaves_nothing_of_the_previous_kind(dev):
+    """bce (weights) -> hier conditional (weights) -> asl (weights) -> hier unconditional (none) -> hier unconditional (another table,
+    weights): after every move the public attributes are the new kind's alone, the step's loss and d loss / d logits are those of
+    the matching module on the same logits, bit for bit, the held storage of a second visit is that of the first, and loss_state()
+    round-trips."""
+    from chexpert_amd.loss import AsymmetricLoss, HierarchicalBCE, MaskedBCE
+    model, S = _net(dev)
+    other, _ = _net(dev)
+    B, n = 2, 14
+    x = synth.xray_batch(3700, B, S).to(dev)
+    t = _targets(3710, B).to(dev)
+    pw = synth.uniform(3730, (n,), 0.5, 8.0)
+    flat = [-1, 0] + [-1] * 12
+    bce_state = {"kind": "bce", "aux": None, "prior": None, "margin": 1.0, "lr_aux": None}
+    assert model.loss_state() == bce_state
+    # (kind, set_loss keywords, the module, then what the model must hold: ignore_negative, pos_weight, focus, parent, mode)
+    walk = [("bce", dict(pos_weight=pw), lambda: MaskedBCE(pw, ignore_negative=False), False, pw, None, None, None),
+            ("hier", dict(kind="hier", parent=CHEXPERT, pos_weight=pw), lambda: HierarchicalBCE(CHEXPERT, pos_weight=pw), True, pw, None, CHEXPERT, "conditional"),
+            ("asl", dict(kind="asl", pos_weight=pw), lambda: AsymmetricLoss(pos_weight=pw), True, pw, torch.tensor([0.0, 4.0, 0.05, -1.0]), None, None),
+            ("hier", dict(kind="hier", parent=CHEXPERT, mode="unconditional"), lambda: HierarchicalBCE(CHEXPERT, "unconditional"), True, None, None, CHEXPERT,
+             "unconditional"),
+            ("hier", dict(kind="hier", parent=flat, mode="unconditional", pos_weight=2 * pw), lambda: HierarchicalBCE(flat, "unconditional", 2 * pw), True,
+             2 * pw, None, flat, "unconditional")]
+    eng, seen, ptrs = model._eng(), [], {}
+    backward = eng.backward
+
+    def spy(ws, dl, dx=None):                                           # d loss / d logits, as the step hands it to the backward pass
+        seen.append(dl.clone())
+        return backward(ws, dl, dx=dx)
+    eng.backward = spy
+    for kind, kw, make, ign, w, focus, parent, mode in walk:
+        assert model.set_loss(**kw) is model
+        assert (model.loss_kind, model.loss_ignore_negative, model.loss_mode) == (kind, ign, mode), kw
+        assert model.loss_aux is None and model.loss_prior is None and model.loss_lr_aux is None and model.loss_class_weight is None
+        for name, want in (("loss_pos_weight", w), ("loss_focus", focus), ("loss_parent", None if parent is None else torch.tensor(parent, dtype=torch.int32))):
+            got = getattr(model, name)
+            assert (got is None) == (want is None), (kw, name)
+            if got is not None:
+                assert got.is_cuda and got.dtype == want.dtype and torch.equal(got.cpu(), want), (kw, name)
+                assert ptrs.setdefault(name, got.data_ptr()) == got.data_ptr(), (kw, name)
+        st = model.loss_state()
+        assert st["kind"] == kind and model.loss_step_state() == [] and ("parent" in st) == ("mode" in st) == (kind == "hier")
+        if kind == "hier":                                              # round trip through another model
+            assert not st["parent"].is_cuda and st["parent"].tolist() == parent and st["mode"] == mode
+            assert other.load_loss_state(st) is other and other.loss_kind == "hier"
+            st2 = other.loss_state()
+            assert st2.keys() == st.keys() and st2["parent"].tolist() == parent and st2["mode"] == mode
+        model.zero_grad(set_to_none=True)
+        loss, logits = model.forward_backward(x, t)
+        xl = logits.clone().requires_grad_(True)
+        lm = make()(xl, t)
+        lm.backward()
+        assert torch.equal(lm.detach(), loss.reshape(())) and torch.equal(xl.grad, seen[-1]), kw
+        assert math.isfinite(loss.item()) and float(seen[-1].abs().max()) > 0
+    assert len(seen) == len(walk) and set(ptrs) == {"loss_pos_weight", "loss_focus", "loss_parent"}
+    with pytest.raises(ValueError):                                     # refused: nothing changes
+        model.set_loss(kind="hier", parent=[-1] * 5)
+    assert model.loss_kind == "hier" and model.loss_parent.tolist() == flat and model.loss_mode == "unconditional"
+    assert model.set_loss() is model and model.loss_parent is None and model.loss_mode is None and model.loss_state() == bce_state
+    assert other.load_loss_state(bce_state) is other and other.loss_kind == "bce" and other.loss_parent is None and other.loss_mode is None
+
+
+def _eager_dev_step(model, opt, x, t):
+    """The step GraphedTrainStep captures, launched one by one (the command line's partial-minibatch step)."""
+    opt.zero_grad()
+    loss, _ = model.forward_backward(x, t)
+    opt.step_dev()
+    opt.tick()
+    model._eng().packed_version = None
+    return loss.clone()
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_graphed_step_equals_eager_and_sees_a_parent_table_rewritten_in_place(dev, mode):
+    from chexpert_amd.graph import GraphedTrainStep
+    from chexpert_amd.loss import HierarchicalBCE
+    from chexpert_amd.optim import FusedAdam
+    m_e, m_g, S = _twin(dev)
+    B, n = 4, 14
+    xs = [synth.xray_batch(3800 + i, B, S).to(dev) for i in range(4)]
+    ts = [_targets(3810 + 10 * i, B).to(dev) for i in range(4)]
+    for m in (m_e, m_g):
+        m.set_loss(kind="hier", parent=CHEXPERT, mode=mode)
+    opt_e, opt_g = FusedAdam(m_e, lr=1e-3), FusedAdam(m_g, lr=1e-3)
+    # captured on a batch WITHOUT ignored labels: what a replay reads is the target copied in, not the one captured
+    gs = GraphedTrainStep(m_g, opt_g, xs[0], synth.targets(3830, B, n).to(dev))
+    held = m_g.loss_parent.data_ptr()
+    flat = lambda m: torch.cat([p.detach().flatten() for p in m.parameters()])                               # noqa: E731
+    for i in range(3):
+        le = _eager_dev_step(m_e, opt_e, xs[i], ts[i])
+        lg, logits = gs.replay(xs[i], ts[i])
+        assert tuple(logits.shape) == (B, n) and torch.equal(le, lg), (i, le.item(), lg.item())
+        assert torch.equal(flat(m_e), flat(m_g)), i
+        assert torch.equal(m_e._eng().flat_grad, m_g._eng().flat_grad)
+    # the table changes: set_loss with a table of the same length copies into the held storage, and the next replay reads it
+    other = [-1, 0, 1, 2, -1, 4, 4, -1, 7, 8, -1, -1, 11, 11]
+    m_g.set_loss(kind="hier", parent=other, mode=mode)
+    m_e.set_loss(kind="hier", parent=other, mode=mode)
+    assert m_g.loss_parent.data_ptr() == held and m_g.loss_parent.tolist() == other
+    le = _eager_dev_step(m_e, opt_e, xs[3], ts[3])
+    lg, logits = gs.replay(xs[3], ts[3])
+    assert torch.equal(le, lg) and torch.equal(flat(m_e), flat(m_g))
+    # ... and it matters: the same logits under the first table give another loss
+    assert HierarchicalBCE(CHEXPERT, mode)(logits, ts[3]).item() != lg.item() == HierarchicalBCE(other, mode)(logits, ts[3]).item()
+
+
+# ------------------------------------------------------------------------------------------------ data parallel
+def _dp_worker(rank, world, port, out_dir):
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from chexpert_amd.parallel import broadcast_module_state
+    dev = torch.device("cuda:0")
+    model, S = _net(dev)
+    broadcast_module_state(model)
+    x = synth.xray_batch(4100 + rank, 4, S).to(dev)
+    t = _targets(4200 + 10 * rank, 4).to(dev)
+    model.set_loss(kind="hier", parent=CHEXPERT, mode="unconditional", pos_weight=synth.uniform(9, (14,), 0.5, 8.0))
+    loss, logits = model.forward_backward(x, t)           # binds the engine; the single-process gradient of this shard, no reducer yet
+    eng = model._eng()
+    g_local = eng.flat_grad.detach().cpu().clone()
+    gathered = [torch.empty_like(g_local) for _ in range(world)]
+    dist.all_gather(gathered, g_local)
+    want = sum(gathered) / world
+    eng.enable_data_parallel(bucket_bytes=1 << 20)
+    model.zero_grad()
+    model.forward_backward(x, t)
+    torch.cuda.synchronize()
+    got = eng.flat_grad.detach().cpu().clone()
+    both = [torch.empty_like(got) for _ in range(world)]
+    dist.all_gather(both, got)
+    torch.save({"got": got, "want": want, "local": g_local, "same": bool(torch.equal(both[0], both[1])), "logits": logits.cpu(), "t": t.cpu(),
+                "loss": loss.item(), "n_ignored": int((t < 0).sum()), "n_buckets": len(eng.reducer.ranges)}, os.path.join(out_dir, "rank%d.pt" % rank))
+    dist.destroy_process_group()
+
+
+def _spawn_with_time_limit(fn, args, nprocs, seconds):
+    """mp.spawn whose processes are killed when they outlive `seconds` (a hung rank must not outlive its test)."""
+    import torch.multiprocessing as mp
+    ctx = mp.spawn(fn, args=args, nprocs=nprocs, join=False)
+    deadline = time.time() + seconds
+    try:
+        while not ctx.join(timeout=5):
+            if time.time() > deadline:
+                raise TimeoutError("the ranks ran longer than %d s" % seconds)
+    finally:
+        for p in ctx.processes:
+            if p.is_alive():
+                p.kill()
+                p.join()
+
+
+def test_data_parallel_gradients_two_ranks_one_gpu(dev, tmp_path):
+    """Two ranks on one GPU: the gradients the reducer leaves on both ranks are the mean of the two single-process gradients, to the
+    1e-6 relative of the masked BCE's data-parallel test.  That mean is the gradient of the joined batch under data-parallel semantics
+    -- BatchNorm statistics per rank --, and the loss kernel's own share of the statement holds bit for bit: on the joined logits
+    (B = 8) it returns each shard's dlogits at grad_scale 1/2, and the mean of the two losses."""
+    from chexpert_amd import ops
+    port = 36900 + (os.getpid() % 400)
+    _spawn_with_time_limit(_dp_worker, (2, port, str(tmp_path)), 2, 300)
+    recs = [torch.load(os.path.join(str(tmp_path), "rank%d.pt" % r)) for r in range(2)]
+    assert not torch.equal(recs[0]["local"], recs[1]["local"])
+    for r, rec in enumerate(recs):
+        assert rec["same"], "ranks ended with different gradients"
+        assert rec["n_buckets"] >= 3 and rec["n_ignored"] >= 2
+        g, w = rec["got"].double(), rec["want"].double()
+        rel = float((g - w).norm() / w.norm())
+        print("rank %d: rel %.3e, %d ignored labels, %d buckets" % (r, rel, rec["n_ignored"], rec["n_buckets"]))
+        assert rel < 1e-6, rel
+    # the joined batch through the loss kernel
+    w = synth.uniform(9, (14,), 0.5, 8.0).to(dev)
+    par = torch.tensor(CHEXPERT, dtype=torch.int32, device=dev)
+    xj, tj = torch.cat([r["logits"] for r in recs]).to(dev), torch.cat([r["t"] for r in recs]).to(dev)
+    lj, dj = torch.zeros(1, device=dev), torch.zeros(8, 14, device=dev)
+    ops.hier_fwd_bwd(xj, tj, par, w, 1, lj, None, dj)
+    halves = []
+    for r in recs:
+        d = torch.zeros(4, 14, device=dev)
+        ops.hier_fwd_bwd(r["logits"].to(dev), r["t"].to(dev), par, w, 1, None, None, d, grad_scale=0.5)
+        halves.append(d)
+    assert torch.equal(dj, torch.cat(halves)) and float(dj.abs().max()) > 0
+    assert abs(lj.item() - 0.5 * (recs[0]["loss"] + recs[1]["loss"])) <= 1e-6 * max(1.0, abs(lj.item()))
+
+
+# ------------------------------------------------------------------------------------------------ predict
+class _Studies(torch.utils.data.Dataset):
+    """What predict() needs of a ChexpertCSV: uint8 items, attr_names, and a Path column for the study names."""
+
+    def __init__(self, n, size):
+        import pandas as pd
+        from chexpert_amd.data import ATTR_NAMES_ALL
+        self.attr_names = ATTR_NAMES_ALL
+        self.x = synth.xray_u8(123, n, size)
+        # study 0 has two views
+        self.data = pd.DataFrame({"Path": ["valid/patient%05d/study1/view%d_frontal.jpg" % (max(i, 1), i) for i in range(n)]})
+
+    def __len__(self):
+        return len(self.x)
+
+    def __getitem__(self, i):
+        return self.x[i], torch.zeros(14), i
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def _losses(capsys):
+    out = capsys.readouterr().out
+    return [json.loads(l)["train_loss"] for l in out.splitlines() if l.startswith('{"step"')]
+
+
+_CLI = ["--train", "--synthetic", "32", "--batch_size", "4", "--resize", "64", "--eval_interval", "8", "--log_interval", "1", "--seed", "3",
+        "--lr", "0.001"]
+_TABLE = ["-1", "0", "0", "-1", "3"]
+_HIER = ["--synthetic_uncertain", "0.2", "--uncertain", "ignore", "--loss", "hier", "--hier_mode", "unconditional", "--hier_parents"] + _TABLE
+_GRAPH = _HIER + ["--fused_optimizer", "--graph"]
+
+
+@pytest.fixture(scope="module")
+def graphed_run(dev, tmp_path_factory):
+    """One `--loss hier --fused_optimizer --graph --bootstrap 50 --calibrate platt` training run on synthetic data, shared by the tests
+    below: (output folder, model, its stdout)."""
+    import contextlib
+    import io
+    from chexpert_amd import cli
+    out = str(tmp_path_factory.mktemp("hier") / "g")
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        model = cli.main(_CLI + _GRAPH + ["--bootstrap", "50", "--calibrate", "platt", "--output_dir", out])
+    return out, model, buf.getvalue()
+
+
+def test_cli_graphed_run_writes_collapsed_results_and_the_loss_state(dev, graphed_run):
+    from chexpert_amd import cli, loss as loss_mod
+    out, model, text = graphed_run
+    lg = [json.loads(l)["train_loss"] for l in text.splitlines() if l.startswith('{"step"')]
+    assert len(lg) == 8 and all(math.isfinite(v) for v in lg), lg
+    assert model.loss_kind == "hier" and model.loss_mode == "unconditional" and model.loss_parent.tolist() == [-1, 0, 0, -1, 3]
+    assert model.classifier.out_features == 5
+    cfg = json.load(open(os.path.join(out, "config.json")))
+    assert cfg["loss"] == "hier" and cfg["hier_mode"] == "unconditional" and cfg["n_classes"] == 5 and cfg["labels"] == "competition"
+    saved = torch.load(os.path.join(out, "checkpoint_latest.pt"), map_location="cpu")
+    st = saved["loss_state"]
+    assert st["kind"] == "hier" and st["mode"] == "unconditional" and st["parent"].tolist() == [-1, 0, 0, -1, 3] and st["parent"].dtype == torch.int32
+    res = json.load(open(os.path.join(out, "eval_results_step_8.json")))
+    assert len(res["aucs"]) == 5 and len(res["loss"]) == 5 and all(math.isfinite(v) for v in res["loss"].values())
+    ci = json.load(open(os.path.join(out, "auc_ci_step_8.json")))
+    assert len(ci["aucs"]) == len(ci["lo"]) == len(ci["hi"]) == 5
+    cal = json.load(open(os.path.join(out, "calibration_step_8.json")))
+    assert cal["fit"]["method"] == "platt" and len(cal["ece_before"]["point"]) == 5
+    # what the evaluation saw are the collapsed logits: an evaluation of the same model gives them, and the loss in eval_results is
+    # the cross-entropy on them
+    from chexpert_amd import metrics as M
+    from chexpert_amd.data import hierarchy_closure
+    valid = cli.SyntheticXrays(6, 64, 5, 11)                            # the run's validation set: max(batch_size, 32 // 5) images, closed
+    valid.targets = hierarchy_closure(valid.targets, [-1, 0, 0, -1, 3])
+    o, t, l = cli.evaluate_sharded(model, valid, 4, dev, 0, 1, None, [-1, 0, 0, -1, 3])
+    raw, _, _ = cli.evaluate_sharded(model, valid, 4, dev, 0, 1, None, False)
+    assert torch.equal(o, loss_mod.collapse_hierarchy(raw.to(dev), [-1, 0, 0, -1, 3]).cpu()) and not torch.equal(o, raw)
+    assert torch.equal(o[:, [0, 3]], raw[:, [0, 3]]) and bool((o[:, [1, 2]] <= o[:, [0]] + 1e-5).all())
+    assert torch.allclose(l, F.binary_cross_entropy_with_logits(o, t, reduction="none"), atol=1e-6)
+    again = {str(k): v for k, v in M.compute_metrics(o, t, l)["loss"].items()}                   # (json's keys are strings)
+    assert again.keys() == res["loss"].keys() and all(abs(again[k] - v) <= 1e-5 * max(1.0, abs(v)) for k, v in res["loss"].items())
+
+
+def test_cli_restores_and_refuses_a_contradicting_table(dev, graphed_run, tmp_path, capsys):
+    from chexpert_amd import cli
+    capsys.readouterr()
+    ck = os.path.join(graphed_run[0], "checkpoint_latest.pt")
+    out2 = str(tmp_path / "r")
+    model2 = cli.main(_CLI + _GRAPH + ["--restore", ck, "--output_dir", out2])
+    lr_ = _losses(capsys)
+    assert len(lr_) == 8 and all(math.isfinite(v) for v in lr_), lr_
+    st2 = torch.load(os.path.join(out2, "checkpoint_latest.pt"), map_location="cpu")
+    assert model2.loss_kind == "hier" and st2["global_step"] == 16 and st2["loss_state"]["kind"] == "hier"
+    assert st2["loss_state"]["parent"].tolist() == [-1, 0, 0, -1, 3] and st2["loss_state"]["mode"] == "unconditional"
+    assert st2["loss_state"]["closure"] is True
+    # a run that does not name the mode continues in the checkpoint's, and writes it on; one that names the other mode is refused
+    bare = [f for f in _GRAPH if f not in ("--hier_mode", "unconditional")]
+    assert "--hier_mode" not in bare and "--loss" in bare and len(bare) == len(_GRAPH) - 2
+    out4 = str(tmp_path / "m")
+    model4 = cli.main(_CLI + bare + ["--restore", ck, "--output_dir", out4])
+    capsys.readouterr()
+    st4 = torch.load(os.path.join(out4, "checkpoint_latest.pt"), map_location="cpu")["loss_state"]
+    assert model4.loss_mode == "unconditional" and st4["mode"] == "unconditional" and st4["parent"].tolist() == [-1, 0, 0, -1, 3]
+    with pytest.raises(ValueError, match="--hier_mode unconditional.*--hier_mode conditional"):
+        cli.main(_CLI + [f if f != "unconditional" else "conditional" for f in _GRAPH] + ["--restore", ck, "--output_dir", str(tmp_path / "c")])
+    # another table is refused by name, and so is training on without the flag
+    other = [f if f != "3" else "0" for f in _GRAPH]
+    with pytest.raises(ValueError, match=r"parent table \[-1, 0, 0, -1, 3\].*--hier_parents"):
+        cli.main(_CLI + other + ["--restore", ck, "--output_dir", str(tmp_path / "x")])
+    with pytest.raises(ValueError, match="trained with --loss hier"):
+        cli.main(_CLI + ["--fused_optimizer", "--restore", ck, "--output_dir", str(tmp_path / "y")])
+    # an evaluation without the flag reads table and mode from the checkpoint and collapses
+    out3 = str(tmp_path / "e")
+    m3 = cli.main(["--evaluate_single_model", "--synthetic", "32", "--batch_size", "4", "--resize", "64", "--restore", ck, "--output_dir", out3])
+    res3 = json.load(open(os.path.join(out3, "eval_results_step_8.json")))
+    res = json.load(open(os.path.join(graphed_run[0], "eval_results_step_8.json")))
+    assert json.dumps(res3) == json.dumps(res) and m3.loss_parent.tolist() == [-1, 0, 0, -1, 3]
+
+
+def test_predict_collapses_with_the_stored_table(dev, graphed_run):
+    """predict(collapse=table): the probabilities are the unconditional ones of every forward, the max over a study's views as always;
+    predict.hier_parent_of reads the table from the run's checkpoint."""
+    from chexpert_amd import predict
+    from chexpert_amd.loss import collapse_hierarchy
+    saved = torch.load(os.path.join(graphed_run[0], "checkpoint_latest.pt"), map_location="cpu")
+    assert predict.hier_parent_of(saved) == [-1, 0, 0, -1, 3]
+    model, S = _net(dev)
+    model.eval()
+    ds, bs = _Studies(8, S), 3
+    with torch.no_grad():
+        out = torch.cat([model(ds.x[k:k + bs].to(dev)).float() for k in range(0, 8, bs)])
+    plain = torch.sigmoid(collapse_hierarchy(out, CHEXPERT)).cpu()
+    p1 = predict.predict(model, ds, bs, dev, collapse=CHEXPERT)
+    assert len(p1) == 7 and list(p1.columns) == ds.attr_names
+    assert torch.equal(torch.from_numpy(p1.values[1:]), plain[2:])                          # the other studies: one view each
+    assert torch.equal(torch.from_numpy(p1.values[0]), torch.maximum(plain[0], plain[1]))   # max over the two views
+    p0 = predict.predict(model, ds, bs, dev)
+    roots = [k for k, a in enumerate(CHEXPERT) if a < 0]
+    assert p0.iloc[:, roots].equals(p1.iloc[:, roots]) and not p0.equals(p1) and bool((p1.values <= p0.values + 1e-6).all())
+
+
+def test_predict_main_reads_the_table_from_the_checkpoint(dev, graphed_run, tmp_path):
+    """predict.main on the run's checkpoint and a csv of four images in three studies: the columns are the findings the table's length
+    names, the probabilities the unconditional ones of the restored model (max over a study's views), and a folder whose checkpoints
+    carry different tables is refused."""
+    from PIL import Image
+    from chexpert_amd import predict
+    from chexpert_amd.data import ATTR_NAMES, ChexpertCSV
+    from chexpert_amd.loss import collapse_hierarchy
+    out, model, _ = graphed_run
+    ck = os.path.join(out, "checkpoint_latest.pt")
+    px = synth.xray_u8(321, 4, 64)
+    paths = []
+    for i, study in enumerate(("patient00001/study1", "patient00001/study1", "patient00002/study1", "patient00002/study2")):
+        d = tmp_path / "test" / study
+        d.mkdir(parents=True, exist_ok=True)
+        paths.append(str(d / ("view%d_frontal.png" % i)))
+        Image.fromarray(px[i, 0].numpy()).save(paths[-1])
+    csv, pred = str(tmp_path / "paths.csv"), str(tmp_path / "pred.csv")
+    open(csv, "w").write("Path\n" + "\n".join(paths) + "\n")
+    df = predict.main([csv, pred, "--restore_path", ck, "--resize", "64", "--batch_size", "4"])
+    assert list(df.columns) == ATTR_NAMES and len(df) == 3 and os.path.isfile(pred)
+    ds = ChexpertCSV(csv, "test", 64)
+    model.eval()
+    with torch.no_grad():
+        logits = model(torch.stack([ds[i][0] for i in range(4)]).to(dev)).float()
+    want = torch.sigmoid(collapse_hierarchy(logits, [-1, 0, 0, -1, 3])).cpu()
+    got = torch.from_numpy(df.values).float()
+    assert torch.equal(got[0], torch.maximum(want[0], want[1])) and torch.equal(got[1:], want[2:])
+    assert not torch.equal(got[1:], torch.sigmoid(logits).cpu()[2:]) and bool((got[:, [1, 2]] <= got[:, [0]]).all()) and bool((got[:, 4] <= got[:, 3]).all())
+    # a folder: two members with the run's table give the same frame; a member with another table is refused
+    folder = tmp_path / "members"
+    folder.mkdir()
+    saved = torch.load(ck, map_location="cpu")
+    torch.save(saved, str(folder / "checkpoint_0.pt"))
+    torch.save(saved, str(folder / "checkpoint_1.pt"))
+    both = predict.main([csv, pred, "--restore_path", str(folder), "--resize", "64", "--batch_size", "4"])
+    assert torch.equal(torch.from_numpy(both.values).float(), got)
+    saved["loss_state"] = dict(saved["loss_state"], parent=torch.tensor([-1, 0, 1, -1, 3], dtype=torch.int32))
+    torch.save(saved, str(folder / "checkpoint_1.pt"))
+    with pytest.raises(ValueError, match="disagree.*parent table"):
+        predict.main([csv, pred, "--restore_path", str(folder), "--resize", "64", "--batch_size", "4"])
+
+
+def test_cli_autograd_route_is_the_same_kernel(dev, tmp_path, capsys):
+    """Without --fused_optimizer the loss module computes the loss: the first batch's loss line is the fused route's."""
+    from chexpert_amd import cli
+    capsys.readouterr()
+    flags = _HIER[:6] + ["--hier_parents"] + _TABLE + ["--synthetic", "16", "--eval_interval", "4", "--pos_weight", "auto"]
+    m1 = cli.main(_CLI + flags + ["--output_dir", str(tmp_path / "e")])
+    le = _losses(capsys)
+    m2 = cli.main(_CLI + flags + ["--fused_optimizer", "--output_dir", str(tmp_path / "f")])
+    lf = _losses(capsys)
+    assert len(le) == len(lf) == 4 and all(math.isfinite(v) for v in le + lf) and le[0] == lf[0], (le, lf)
+    for m, d in ((m1, "e"), (m2, "f")):
+        assert m.loss_kind == "hier" and m.loss_mode == "conditional" and m.loss_pos_weight is not None
+        st = torch.load(os.path.join(str(tmp_path / d), "checkpoint_latest.pt"), map_location="cpu")["loss_state"]
+        assert st["kind"] == "hier" and st["mode"] == "conditional"
+
+
+def test_cli_default_flags_never_reach_the_new_kernels(dev, tmp_path, capsys, monkeypatch):
+    from chexpert_amd import cli, ops
+
+    def refuse(*a, **k):
+        raise AssertionError("a cx_hier wrapper was reached without --loss hier")
+    monkeypatch.setattr(ops, "hier_fwd_bwd", refuse)
+    monkeypatch.setattr(ops, "hier_collapse", refuse)
+    capsys.readouterr()
+    out = str(tmp_path / "p")
+    model = cli.main(_CLI[:2] + ["16"] + _CLI[3:] + ["--eval_interval", "4", "--fused_optimizer", "--graph", "--output_dir", out])
+    lp = _losses(capsys)
+    assert len(lp) == 4 and all(math.isfinite(v) for v in lp), lp
+    assert model.loss_kind == "bce" and model.loss_parent is None and model.loss_mode is None and model.classifier.out_features == 5
+    assert "loss_state" not in torch.load(os.path.join(out, "checkpoint_latest.pt"), map_location="cpu")
+    cfg = json.load(open(os.path.join(out, "config.json")))
+    assert cfg["loss"] == "bce" and cfg["labels"] == "competition" and cfg["n_classes"] == 5
+    # the patches have teeth: these are the names FusedNet.forward_backward, the loss module and the collapse call
+    from chexpert_amd.loss import collapse_hierarchy
+    from chexpert_amd.models import DenseNet
+    wide = DenseNet(32, (2, 2, 2, 2), 64, num_classes=5).to(dev).train()
+    wide.set_loss(kind="hier", parent=[-1, 0, 0, -1, 3])
+    x, t = synth.xray_batch(3900, 4, 64).to(dev), synth.targets(3910, 4, 5).to(dev)
+    with pytest.raises(AssertionError, match="was reached"):
+        wide.forward_backward(x, t)
+    with pytest.raises(AssertionError, match="was reached"):
+        collapse_hierarchy(torch.zeros(2, 5, device=dev), [-1, 0, 0, -1, 3])
