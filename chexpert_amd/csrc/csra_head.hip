@@ -346,36 +346,33 @@ template <typename T> bool shape_ok(int B, int HW, int C, int ld) {
 int nt_of(int n) { return n <= 16 ? 16 : n <= 32 ? 32 : 64; }
 int group_size(int B) { return (B + CS_GROUPS - 1) / CS_GROUPS; }
 
-long long scratch_floats(int B, int HW, int C, int n) {
+enum Head { CSRA, PCAM };                                     // pcam: no [lambda, T]; its backward keeps dl_eff (B n) behind the partials
+
+long long scratch_floats(Head head, int B, int HW, int C, int n) {
   const int GB = group_size(B), groups = (B + GB - 1) / GB;
-  return (long long)B * HW * nt_of(n) + (long long)groups * n * C;
+  return (long long)B * HW * nt_of(n) + (long long)groups * n * C + (head == PCAM ? (long long)B * n : 0);
+}
+
+long long bwd_scratch(Head head, int B, int HW, int C, int n) {
+  if (B <= 0 || HW <= 0 || C <= 0 || n < 1) return CX_ESHAPE;
+  if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
+  return scratch_floats(head, B, HW, C, n);
 }
 
 template <typename T>
-int csra_fwd_t(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, const float* lam_T,
-               float* logits, float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
-  if (!x || !sc || !sh || !W || !lam_T || !logits || !s || !stat || !known_act(act)) return CX_EINVAL;
+int head_fwd_t(Head head, const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias,
+               const float* lam_T, float* logits, float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
+  if (!x || !sc || !sh || !W || (head == CSRA && !lam_T) || !logits || !s || !stat || !known_act(act)) return CX_EINVAL;
   if (n < 1 || !shape_ok<T>(B, HW, C, ldx)) return CX_ESHAPE;
   if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
   if (!aligned16(x)) return CX_EALIGN;
   const size_t rows = (size_t)B * HW, per = CS_WAVES * CS_PT, BN = (size_t)B * n;
   hipLaunchKernelGGL((csra_score_kernel<T>), dim3((rows + per - 1) / per), dim3(CS_THREADS), 0, as_stream(stream), (const T*)x, sc, sh, m, W, s,
                      rows, HW, C, ldx, n, act);
-  hipLaunchKernelGGL(csra_stat_kernel, dim3((BN + 3) / 4), dim3(256), 0, as_stream(stream), s, bias, lam_T, logits, stat, BN, n, HW);
-  return launch_status();
-}
-
-template <typename T>
-int pcam_fwd_t(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, float* logits, float* s,
-               float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
-  if (!x || !sc || !sh || !W || !logits || !s || !stat || !known_act(act)) return CX_EINVAL;
-  if (n < 1 || !shape_ok<T>(B, HW, C, ldx)) return CX_ESHAPE;
-  if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
-  if (!aligned16(x)) return CX_EALIGN;
-  const size_t rows = (size_t)B * HW, per = CS_WAVES * CS_PT, BN = (size_t)B * n;
-  hipLaunchKernelGGL((csra_score_kernel<T>), dim3((rows + per - 1) / per), dim3(CS_THREADS), 0, as_stream(stream), (const T*)x, sc, sh, m, W, s,
-                     rows, HW, C, ldx, n, act);
-  hipLaunchKernelGGL(pcam_stat_kernel, dim3((BN + 3) / 4), dim3(256), 0, as_stream(stream), s, bias, logits, stat, BN, n, HW);
+  if (head == CSRA)
+    hipLaunchKernelGGL(csra_stat_kernel, dim3((BN + 3) / 4), dim3(256), 0, as_stream(stream), s, bias, lam_T, logits, stat, BN, n, HW);
+  else
+    hipLaunchKernelGGL(pcam_stat_kernel, dim3((BN + 3) / 4), dim3(256), 0, as_stream(stream), s, bias, logits, stat, BN, n, HW);
   return launch_status();
 }
 
@@ -388,63 +385,38 @@ void launch_bwd(const float* ds, const void* x, const float* sc, const float* sh
                      m, mean, rstd, e_scale, W, (T*)g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB);
 }
 
+// scratch = ds | the weight-gradient partials (| pcam: dl_eff (B n), which feeds the bias gradient in the place of dlogits)
 template <typename T>
-int csra_bwd_t(const float* dlogits, const float* s, const float* stat, const float* lam_T, const void* x, const float* sc, const float* sh,
-               const float* m, const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1, float* S2,
-               float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n, int act,
+int head_bwd_t(Head head, const float* dlogits, const float* s, const float* stat, const float* lam_T, const void* x, const float* sc,
+               const float* sh, const float* m, const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1,
+               float* S2, float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n, int act,
                int stat_rows, void* stream) {
-  if (!dlogits || !s || !stat || !lam_T || !x || !sc || !sh || !mean || !rstd || !e_scale || !W || !g || !S1 || !S2 || !dW || !scratch ||
-      !known_act(act))
+  if (!dlogits || !s || !stat || (head == CSRA && !lam_T) || !x || !sc || !sh || !mean || !rstd || !e_scale || !W || !g || !S1 || !S2 || !dW ||
+      !scratch || !known_act(act))
     return CX_EINVAL;
   if (n < 1 || !shape_ok<T>(B, HW, C, ldx) || !shape_ok<T>(B, HW, C, ldg)) return CX_ESHAPE;
   if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
-  if (scratch_len < scratch_floats(B, HW, C, n)) return CX_EUNSUPPORTED;      // refused, no other path
+  if (scratch_len < scratch_floats(head, B, HW, C, n)) return CX_EUNSUPPORTED;   // refused, no other path
   if (!aligned16(x) || !aligned16(g) || !aligned16(scratch)) return CX_EALIGN;
   if (stat_rows > 0) { if (stat_rows < B) return CX_ESTATROWS; cx_tl_stat_rows = B; }
   const int NT = nt_of(n), GB = group_size(B), groups = (B + GB - 1) / GB, det = stat_rows > 0 ? 1 : 0;
   const size_t total = (size_t)B * HW * NT, nC = (size_t)n * C;
   float* ds = scratch;
   float* part = scratch + total;
+  float* dleff = scratch + scratch_floats(CSRA, B, HW, C, n);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(csra_ds_kernel, dim3((total + 255) / 256), dim3(256), 0, st, dlogits, s, stat, lam_T, ds, total, n, HW, NT);
+  if (head == CSRA)
+    hipLaunchKernelGGL(csra_ds_kernel, dim3((total + 255) / 256), dim3(256), 0, st, dlogits, s, stat, lam_T, ds, total, n, HW, NT);
+  else
+    hipLaunchKernelGGL(pcam_ds_kernel, dim3(B), dim3(256), 0, st, dlogits, s, stat, ds, dleff, n, HW, NT);
   if (NT == 16)
     launch_bwd<T, 16, 4>(ds, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB, groups, st);
   else if (NT == 32)
     launch_bwd<T, 32, 2>(ds, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB, groups, st);
   else
     launch_bwd<T, 64, 1>(ds, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB, groups, st);
-  hipLaunchKernelGGL(csra_reduce_kernel, dim3((nC + n + 255) / 256), dim3(256), 0, st, part, dlogits, dW, db, groups, B, n, nC);
-  return launch_status();
-}
-
-// csra_bwd_t with pcam_ds_kernel in the place of csra_ds_kernel; scratch = ds | the weight-gradient partials | dl_eff (B n)
-template <typename T>
-int pcam_bwd_t(const float* dlogits, const float* s, const float* stat, const void* x, const float* sc, const float* sh, const float* m,
-               const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1, float* S2,
-               float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n, int act,
-               int stat_rows, void* stream) {
-  if (!dlogits || !s || !stat || !x || !sc || !sh || !mean || !rstd || !e_scale || !W || !g || !S1 || !S2 || !dW || !scratch || !known_act(act))
-    return CX_EINVAL;
-  if (n < 1 || !shape_ok<T>(B, HW, C, ldx) || !shape_ok<T>(B, HW, C, ldg)) return CX_ESHAPE;
-  if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
-  const long long base = scratch_floats(B, HW, C, n);
-  if (scratch_len < base + (long long)B * n) return CX_EUNSUPPORTED;           // refused, no other path
-  if (!aligned16(x) || !aligned16(g) || !aligned16(scratch)) return CX_EALIGN;
-  if (stat_rows > 0) { if (stat_rows < B) return CX_ESTATROWS; cx_tl_stat_rows = B; }
-  const int NT = nt_of(n), GB = group_size(B), groups = (B + GB - 1) / GB, det = stat_rows > 0 ? 1 : 0;
-  const size_t total = (size_t)B * HW * NT, nC = (size_t)n * C;
-  float* ds = scratch;
-  float* part = scratch + total;
-  float* dleff = scratch + base;
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(pcam_ds_kernel, dim3(B), dim3(256), 0, st, dlogits, s, stat, ds, dleff, n, HW, NT);
-  if (NT == 16)
-    launch_bwd<T, 16, 4>(ds, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB, groups, st);
-  else if (NT == 32)
-    launch_bwd<T, 32, 2>(ds, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB, groups, st);
-  else
-    launch_bwd<T, 64, 1>(ds, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, part, B, HW, C, ldx, ldg, n, act, det, GB, groups, st);
-  hipLaunchKernelGGL(csra_reduce_kernel, dim3((nC + n + 255) / 256), dim3(256), 0, st, part, dleff, dW, db, groups, B, n, nC);
+  hipLaunchKernelGGL(csra_reduce_kernel, dim3((nC + n + 255) / 256), dim3(256), 0, st, part, head == CSRA ? dlogits : dleff, dW, db, groups, B,
+                     n, nC);
   return launch_status();
 }
 
@@ -454,58 +426,54 @@ extern "C" {
 
 int cx_csra_head_fwd(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, const float* lam_T,
                      float* logits, float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
-  return csra_fwd_t<bf16>(x, sc, sh, m, W, bias, lam_T, logits, s, stat, B, HW, C, ldx, n, act, stream);
+  return head_fwd_t<bf16>(CSRA, x, sc, sh, m, W, bias, lam_T, logits, s, stat, B, HW, C, ldx, n, act, stream);
 }
 int cx_csra_head_fwd_f32(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, const float* lam_T,
                          float* logits, float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
-  return csra_fwd_t<float>(x, sc, sh, m, W, bias, lam_T, logits, s, stat, B, HW, C, ldx, n, act, stream);
+  return head_fwd_t<float>(CSRA, x, sc, sh, m, W, bias, lam_T, logits, s, stat, B, HW, C, ldx, n, act, stream);
 }
 int cx_csra_head_bwd(const float* dlogits, const float* s, const float* stat, const float* lam_T, const void* x, const float* sc, const float* sh,
                      const float* m, const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1, float* S2,
                      float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n, int act,
                      int stat_rows, void* stream) {
-  return csra_bwd_t<bf16>(dlogits, s, stat, lam_T, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx,
+  return head_bwd_t<bf16>(CSRA, dlogits, s, stat, lam_T, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx,
                           ldg, n, act, stat_rows, stream);
 }
 int cx_csra_head_bwd_f32(const float* dlogits, const float* s, const float* stat, const float* lam_T, const void* x, const float* sc,
                          const float* sh, const float* m, const float* mean, const float* rstd, const float* e_scale, const float* W, void* g,
                          float* S1, float* S2, float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg,
                          int n, int act, int stat_rows, void* stream) {
-  return csra_bwd_t<float>(dlogits, s, stat, lam_T, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx,
+  return head_bwd_t<float>(CSRA, dlogits, s, stat, lam_T, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx,
                            ldg, n, act, stat_rows, stream);
 }
 long long cx_csra_bwd_scratch(int B, int HW, int C, int n) {
-  if (B <= 0 || HW <= 0 || C <= 0 || n < 1) return CX_ESHAPE;
-  if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
-  return scratch_floats(B, HW, C, n);
+  return bwd_scratch(CSRA, B, HW, C, n);
 }
 
 int cx_pcam_head_fwd(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, float* logits,
                      float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
-  return pcam_fwd_t<bf16>(x, sc, sh, m, W, bias, logits, s, stat, B, HW, C, ldx, n, act, stream);
+  return head_fwd_t<bf16>(PCAM, x, sc, sh, m, W, bias, nullptr, logits, s, stat, B, HW, C, ldx, n, act, stream);
 }
 int cx_pcam_head_fwd_f32(const void* x, const float* sc, const float* sh, const float* m, const float* W, const float* bias, float* logits,
                          float* s, float* stat, int B, int HW, int C, int ldx, int n, int act, void* stream) {
-  return pcam_fwd_t<float>(x, sc, sh, m, W, bias, logits, s, stat, B, HW, C, ldx, n, act, stream);
+  return head_fwd_t<float>(PCAM, x, sc, sh, m, W, bias, nullptr, logits, s, stat, B, HW, C, ldx, n, act, stream);
 }
 int cx_pcam_head_bwd(const float* dlogits, const float* s, const float* stat, const void* x, const float* sc, const float* sh, const float* m,
                      const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1, float* S2, float* dW,
                      float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n, int act, int stat_rows,
                      void* stream) {
-  return pcam_bwd_t<bf16>(dlogits, s, stat, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx, ldg, n,
+  return head_bwd_t<bf16>(PCAM, dlogits, s, stat, nullptr, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx, ldg, n,
                           act, stat_rows, stream);
 }
 int cx_pcam_head_bwd_f32(const float* dlogits, const float* s, const float* stat, const void* x, const float* sc, const float* sh,
                          const float* m, const float* mean, const float* rstd, const float* e_scale, const float* W, void* g, float* S1,
                          float* S2, float* dW, float* db, float* scratch, long long scratch_len, int B, int HW, int C, int ldx, int ldg, int n,
                          int act, int stat_rows, void* stream) {
-  return pcam_bwd_t<float>(dlogits, s, stat, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx, ldg,
+  return head_bwd_t<float>(PCAM, dlogits, s, stat, nullptr, x, sc, sh, m, mean, rstd, e_scale, W, g, S1, S2, dW, db, scratch, scratch_len, B, HW, C, ldx, ldg,
                            n, act, stat_rows, stream);
 }
 long long cx_pcam_bwd_scratch(int B, int HW, int C, int n) {
-  if (B <= 0 || HW <= 0 || C <= 0 || n < 1) return CX_ESHAPE;
-  if (n > CX_CSRA_MAX_CLASSES) return CX_EUNSUPPORTED;
-  return scratch_floats(B, HW, C, n) + (long long)B * n;
+  return bwd_scratch(PCAM, B, HW, C, n);
 }
 
 }  // extern "C"

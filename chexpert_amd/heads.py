@@ -138,20 +138,19 @@ def pcam_backward_reference(dlogits, x, sc, sh, mean, rstd, e_scale, W, b, act="
     return dz * np.asarray(e_scale, dtype=np.float64), dz.sum((0, 1)), t2.sum((0, 1)), dW, (dl * (1.0 + r)).sum(0)
 
 
-def _pcam_maps(model, x):
+def _csra_maps(model, s, st):
+    """(scores, attention) of the csra head from the forward's score map s (B, n, HW) and its stat rows."""
     import torch
-    with torch.no_grad():
-        eng = model._eng()
-        ws = eng.forward(x, False)
-        B, n = ws.logits.shape
-        h, w = ws.csra_hw
-        st = ws.csra_stat
-        u = ws.csra_s + st[:, :, 3:4]                                  # the kernel's u = s + bias, the same rounding
-        P = torch.sigmoid(u)
-        wgt = torch.exp(torch.nn.functional.logsigmoid(u) - torch.nn.functional.logsigmoid(st[:, :, 0:1])) * st[:, :, 1:2]
-        logits = ws.logits.clone()
-        eng.release(ws)
-    return P.view(B, n, h, w), wgt.view(B, n, h, w), logits
+    s = s.clone()
+    return s, torch.exp(model.head_attn[1] * (s - st[:, :, 0:1])) * st[:, :, 1:2]
+
+
+def _pcam_maps(model, s, st):
+    """(P, w) of the pcam head from the forward's score map s (B, n, HW) and its stat rows."""
+    import torch
+    u = s + st[:, :, 3:4]                                              # the kernel's u = s + bias, the same rounding
+    wgt = torch.exp(torch.nn.functional.logsigmoid(u) - torch.nn.functional.logsigmoid(st[:, :, 0:1])) * st[:, :, 1:2]
+    return torch.sigmoid(u), wgt
 
 
 def class_maps(model, x):
@@ -171,16 +170,12 @@ def class_maps(model, x):
         raise RuntimeError("class_maps runs in eval mode (model.eval())")
     if not x.is_cuda:
         raise RuntimeError("class_maps runs on the GPU only: move the model and the input to cuda")
-    if model.head_kind == "pcam":
-        return _pcam_maps(model, x)
     with torch.no_grad():
         eng = model._eng()
         ws = eng.forward(x, False)
         B, n = ws.logits.shape
-        h, w = ws.csra_hw
-        s, st = ws.csra_s.clone(), ws.csra_stat
-        T = model.head_attn[1]
-        attn = torch.exp(T * (s - st[:, :, 0:1])) * st[:, :, 1:2]
+        h, w = ws.head_hw
+        a, b = (_pcam_maps if model.head_kind == "pcam" else _csra_maps)(model, ws.head_s, ws.head_stat)
         logits = ws.logits.clone()
         eng.release(ws)
-    return s.view(B, n, h, w), attn.view(B, n, h, w), logits
+    return a.view(B, n, h, w), b.view(B, n, h, w), logits

@@ -655,81 +655,97 @@ class FusedEngine:
         ch, v = self._ch, self._v
         return dict(g_prologue=ops.PRO_AFFINE2, g2=ch(y, c_), ga=ch(v(ws, S.pa), c_), gb=ch(v(ws, S.pb), c_), gc=ch(v(ws, S.pc), c_))
 
-    # ---- the head's pooling when it is not the average (FusedNet.set_pool): pool_head_fwd + linear_fwd on the way up, head_bwd,
-    # pool_p_grad (gem) and pool_head_bwd on the way back; the engines keep their own average calls
+    # ---- the classifier head of every engine, from the last feature map x (read as act(x*sc + sh), act an ops.POOL_ACT_*) to ws.logits
+    # and back.  FusedNet.set_head / set_pool choose the path (_head_path); the average pool's kernels follow the activation:
+    #   ReLU:  head_fwd (pool and classifier in one kernel);   head_bwd, gap_relu_bn_bwd
+    #   Swish: gap_affine_act, linear_fwd;                      head_bwd, se_act_bwd
+    # another pooling (max / lse / gem) runs pool_head_fwd + linear_fwd and head_bwd, pool_p_grad (gem), pool_head_bwd; a head that
+    # pools a per-pixel score map (csra / pcam) runs map_head_fwd in the place of pool + classifier and map_head_bwd in the place of
+    # head_bwd + the pool's backward.  Every backward leaves g / S1 / S2 as the average's does.  mask: None, or the (B, C) Dropout
+    # mask in front of the classifier (EfficientNet), which a score-map head's kernels apply themselves.
     def pool_kind(self):
         return getattr(self.model, "pool_kind", "avg")
 
-    def _pool_fwd(self, ws, x, sc, sh, act):
-        """ws.pooled = pool act(x*sc + sh) of the last feature map (ws.pool_aux: GeM's T, which pool_p_grad reads; LSE's offset, which its backward reads)."""
-        m, kind = self.model, self.pool_kind()
-        if kind != "max" and getattr(ws, "pool_aux", None) is None:
-            ws.pool_aux = torch.empty_like(ws.pooled)
-        ops.pool_head_fwd(x, sc, sh, ws.pooled, ws.pool_aux if kind != "max" else None, m.pool_param(), act=act, kind=kind)
-
-    def _pool_bwd(self, ws, dpooled, x, sc, sh, mean, rstd, e_scale, g, S1, S2, stat_rows, act, done):
-        """The pooling's backward from dpooled (the gradient of ws.pooled): pool_p's gradient first (reported to the reducer: it is
-        the last parameter of the flat buffer), then g / S1 / S2 as the average's backward leaves them.  Returns the statistic rows."""
-        m, kind = self.model, self.pool_kind()
-        if kind == "gem":
-            ops.pool_p_grad(dpooled, ws.pooled, ws.pool_aux, m.pool_p, self.grad_of(m.pool_p))
-            done(m.pool_p)
-        return ops.pool_head_bwd(dpooled, ws.pooled, ws.pool_aux if kind != "max" else None, m.pool_param(), x, sc, sh, mean, rstd,
-                                 e_scale, g, S1, S2, act=act, kind=kind, stat_rows=stat_rows)
-
-    # ---- the csra head (FusedNet.set_head): csra_head_fwd in the place of pool + classifier, csra_head_bwd in the place of head_bwd +
-    # the pool's backward; g / S1 / S2 leave as the average's backward leaves them
     def head_kind(self):
         return getattr(self.model, "head_kind", "linear")
 
-    def _map_slots(self, ws, x, n):
-        """The workspace slots of a head that pools a per-pixel score map: ws.csra_s (the score map) and ws.csra_stat stay for the way
-        back and for class_maps; ws.csra_scratch is allocated by the first backward."""
+    def _head_path(self):
+        """The head's path by one name: set_head's "csra" / "pcam" (they stand on the average pool), else set_pool's "avg" / "max" /
+        "lse" / "gem" in front of the linear classifier."""
+        head = self.head_kind()
+        return head if head != "linear" else self.pool_kind()
+
+    def _head_fwd(self, ws, x, sc, sh, fc, act, mask=None, rows=None):
+        """Fills ws.logits, and ws.pooled where the path has one.  ws.drop (the mask) and ws.fc_in (what the classifier read) stay for
+        the way back.  rows: the scratch rows of the Swish average (gap_affine_act)."""
+        m, path = self.model, self._head_path()
+        ws.drop, ws.fc_in = mask, ws.pooled
+        if path in ("csra", "pcam"):
+            return self._map_fwd(ws, path, x, sc, sh, mask, fc, act)
+        if path == "avg" and act == ops.POOL_ACT_RELU:
+            assert mask is None, "head_fwd applies the classifier itself: nothing comes in between"
+            return ops.head_fwd(x, sc, sh, fc.weight, fc.bias, ws.pooled, ws.logits)
+        if path == "avg":
+            ops.gap_affine_act(x, sc, sh, ws.pooled, act=act, rows=rows)
+        else:
+            # ws.pool_aux: GeM's T, which pool_p_grad reads; LSE's offset, which its backward reads
+            if path != "max" and getattr(ws, "pool_aux", None) is None:
+                ws.pool_aux = torch.empty_like(ws.pooled)
+            ops.pool_head_fwd(x, sc, sh, ws.pooled, ws.pool_aux if path != "max" else None, m.pool_param(), act=act, kind=path)
+        if mask is not None:
+            ws.pooled_d = torch.empty_like(ws.pooled)
+            ops.mul_f32(ws.pooled, mask, ws.pooled_d)
+            ws.fc_in = ws.pooled_d
+        ops.linear_fwd(ws.fc_in, fc.weight, fc.bias, ws.logits)
+
+    def _head_bwd(self, ws, dlogits, x, sc, sh, mean, rstd, e_scale, g, S1, S2, stat_rows, fc, act, mask, done):
+        """The head's backward from dlogits: the classifier's gradients, then g = e_scale * dz and the BatchNorm backward sums S1 / S2
+        of dz.  The reducer hears of pool_p first (gem: it is the last parameter of the flat buffer) and of fc.weight after a
+        score-map head's backward.  Returns the statistic rows."""
+        m, G, path = self.model, self.grad_of, self._head_path()
+        db = G(fc.bias) if fc.bias is not None else None
+        if path in ("csra", "pcam"):
+            return self._map_bwd(ws, path, dlogits, x, sc, sh, mask, mean, rstd, e_scale, g, S1, S2, stat_rows, fc, db, act, done)
+        dpooled = torch.empty_like(ws.pooled)
+        ops.head_bwd(dlogits, ws.fc_in, fc.weight, G(fc.weight), db, dpooled)
+        if mask is not None:
+            ops.mul_f32(dpooled, mask, dpooled)
+        if path == "avg" and act == ops.POOL_ACT_RELU:
+            return ops.gap_relu_bn_bwd(dpooled, x, sc, sh, mean, rstd, e_scale, g, S1, S2, stat_rows)
+        if path == "avg":                      # (se_act_bwd takes no e_scale: the Swish head's is 1)
+            return ops.se_act_bwd(None, x, sc, sh, mean, rstd, None, dpooled, g, S1, S2, stat_rows)
+        if path == "gem":
+            ops.pool_p_grad(dpooled, ws.pooled, ws.pool_aux, m.pool_p, G(m.pool_p))
+            done(m.pool_p)
+        return ops.pool_head_bwd(dpooled, ws.pooled, ws.pool_aux if path != "max" else None, m.pool_param(), x, sc, sh, mean, rstd,
+                                 e_scale, g, S1, S2, act=act, kind=path, stat_rows=stat_rows)
+
+    def _map_fwd(self, ws, kind, x, sc, sh, m, fc, act):
+        """ws.logits of the csra / pcam head.  ws.head_s (the per-pixel score map) and ws.head_stat stay for the way back and for
+        class_maps; ws.head_scratch is allocated by the first backward."""
         B, H, W, _ = x.shape
-        if getattr(ws, "csra_s", None) is None:
-            ws.csra_s = torch.empty(B, n, H * W, dtype=torch.float32, device=self.device)
-            ws.csra_stat = torch.empty(B, n, ops.CSRA_STAT, dtype=torch.float32, device=self.device)
-            ws.csra_scratch = None
-        ws.csra_hw = (H, W)
+        n = fc.out_features
+        if getattr(ws, "head_s", None) is None:
+            ws.head_s = torch.empty(B, n, H * W, dtype=torch.float32, device=self.device)
+            ws.head_stat = torch.empty(B, n, ops.CSRA_STAT, dtype=torch.float32, device=self.device)
+            ws.head_scratch = None
+        ws.head_hw = (H, W)
+        ops.map_head_fwd(kind, x, sc, sh, m, fc.weight, fc.bias, self._head_attn(kind), ws.logits, ws.head_s, ws.head_stat, act=act)
 
-    def _map_scratch(self, ws, x, n, size):
+    def _map_bwd(self, ws, kind, dlogits, x, sc, sh, m, mean, rstd, e_scale, g, S1, S2, stat_rows, fc, db, act, done):
+        """The csra / pcam head's backward: the classifier's gradients are added where head_bwd adds them (pcam's bias gradient is the
+        kernel's sum_b dlogit (1 + r)).  Returns the statistic rows."""
         B, H, W, C = x.shape
-        if ws.csra_scratch is None:
-            ws.csra_scratch = torch.empty(size(B, H * W, C, n), dtype=torch.float32, device=self.device)
-        return ws.csra_scratch
-
-    def _csra_fwd(self, ws, x, sc, sh, m, fc, act):
-        """ws.logits from the last feature map x."""
-        self._map_slots(ws, x, fc.out_features)
-        ops.csra_head_fwd(x, sc, sh, m, fc.weight, fc.bias, self.model.head_attn, ws.logits, ws.csra_s, ws.csra_stat, act=act)
-
-    def _csra_bwd(self, ws, dlogits, x, sc, sh, m, mean, rstd, e_scale, g, S1, S2, stat_rows, fc, act, done):
-        """The head's backward from dlogits: the classifier's gradients (added where head_bwd adds them, reported to the reducer),
-        g / S1 / S2.  Returns the statistic rows."""
-        G = self.grad_of
-        scratch = self._map_scratch(ws, x, fc.out_features, ops.csra_bwd_scratch)
-        rows = ops.csra_head_bwd(dlogits, ws.csra_s, ws.csra_stat, self.model.head_attn, x, sc, sh, m, mean, rstd, e_scale, fc.weight, g, S1,
-                                 S2, G(fc.weight), G(fc.bias) if fc.bias is not None else None, scratch, act=act, stat_rows=stat_rows)
+        if ws.head_scratch is None:
+            ws.head_scratch = torch.empty(ops.map_bwd_scratch(kind, B, H * W, C, fc.out_features), dtype=torch.float32, device=self.device)
+        rows = ops.map_head_bwd(kind, dlogits, ws.head_s, ws.head_stat, self._head_attn(kind), x, sc, sh, m, mean, rstd, e_scale, fc.weight,
+                                g, S1, S2, self.grad_of(fc.weight), db, ws.head_scratch, act=act, stat_rows=stat_rows)
         done(fc.weight)
         return rows
 
-    def _pcam_fwd(self, ws, x, sc, sh, m, fc, act):
-        """_csra_fwd for set_head("pcam"): the same workspace slots, no [lambda, T]."""
-        self._map_slots(ws, x, fc.out_features)
-        ops.pcam_head_fwd(x, sc, sh, m, fc.weight, fc.bias, ws.logits, ws.csra_s, ws.csra_stat, act=act)
-
-    def _pcam_bwd(self, ws, dlogits, x, sc, sh, m, mean, rstd, e_scale, g, S1, S2, stat_rows, fc, act, done):
-        """_csra_bwd for set_head("pcam"): the bias gradient is the kernel's sum_b dlogit (1 + r).  Returns the statistic rows."""
-        G = self.grad_of
-        scratch = self._map_scratch(ws, x, fc.out_features, ops.pcam_bwd_scratch)
-        rows = ops.pcam_head_bwd(dlogits, ws.csra_s, ws.csra_stat, x, sc, sh, m, mean, rstd, e_scale, fc.weight, g, S1, S2, G(fc.weight),
-                                 G(fc.bias) if fc.bias is not None else None, scratch, act=act, stat_rows=stat_rows)
-        done(fc.weight)
-        return rows
-
-    def _map_head(self):
-        """(forward, backward) of a head that pools a per-pixel score map, None for the linear head."""
-        return {"csra": (self._csra_fwd, self._csra_bwd), "pcam": (self._pcam_fwd, self._pcam_bwd)}.get(self.head_kind())
+    def _head_attn(self, kind):
+        """csra's [lambda, T] in device memory; pcam has none."""
+        return self.model.head_attn if kind == "csra" else None
 
     # ---- workspaces
     def acquire(self, B, H, W):

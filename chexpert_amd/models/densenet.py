@@ -558,16 +558,10 @@ class _Engine(FusedEngine):
         return self._fresh(ws, rows, 0, cn)
 
     def _head_forward(self, ws, bi, fresh):
-        """norm5's coefficients; ReLU -> global average pool -> classifier in one kernel.  Another pooling (set_pool): its kernel,
-        then the classifier."""
+        """norm5's coefficients, then the shared head (FusedEngine._head_fwd) behind ReLU."""
         m, blk = self.model, self.plan.blocks[bi]
         self._bn_block(ws, blk, blk, m.features.norm5, self._count(ws.buf[bi]), fresh)
-        if self.head_kind() in ("csra", "pcam"):    # set_head: the classifier at every pixel, pooled per class
-            return self._map_head()[0](ws, ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), None, m.classifier, ops.POOL_ACT_RELU)
-        if self.pool_kind() != "avg":
-            self._pool_fwd(ws, ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), ops.POOL_ACT_RELU)
-            return ops.linear_fwd(ws.pooled, m.classifier.weight, m.classifier.bias, ws.logits)
-        ops.head_fwd(ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), m.classifier.weight, m.classifier.bias, ws.pooled, ws.logits)
+        self._head_fwd(ws, ws.buf[bi], self._v(ws, blk.sc), self._v(ws, blk.sh), m.classifier, ops.POOL_ACT_RELU)
 
     def _aa_forward(self, ws, bi, fresh):
         """InstanceNorm -> ReLU -> AAConv2d(3x3, stride 2) from block buffer bi into the first channels of buffer bi+1.  No BatchNorm
@@ -677,26 +671,14 @@ class _Engine(FusedEngine):
                          *out, n, replicas=r[2], rstride=r[3], q=q, lo=lo)
 
     def _head_backward(self, ws, dlogits, done):
-        """classifier -> global pool (the average, or set_pool's) -> ReLU -> norm5, into the last block's gradient buffer."""
-        m, v, G = self.model, self._v, self.grad_of
+        """The shared head's backward (FusedEngine._head_bwd) -> norm5, into the last block's gradient buffer."""
+        m, v = self.model, self._v
         bi = len(self.blocks) - 1
         blk, ct = self.plan.blocks[bi], self.plan.blocks[bi].C
-        csra = self.head_kind() in ("csra", "pcam")
-        if not csra:
-            dpooled = torch.empty(ws.B, ct, dtype=torch.float32, device=self.device)
-            ops.head_bwd(dlogits, ws.pooled, m.classifier.weight, G(m.classifier.weight), G(m.classifier.bias) if
-                         m.classifier.bias is not None else None, dpooled)
         if ws.B * ct > self.SLAB:
             raise RuntimeError("batch too large for the statistic-row scratch (B*C = %d > %d)" % (ws.B * ct, self.SLAB))
-        if csra:
-            rows = self._map_head()[1](ws, dlogits, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), None, v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
-                                  ws.gbuf[bi], *self._ew(ws, ct, bwd=True, rows=self.SLAB // ct), m.classifier, ops.POOL_ACT_RELU, done)
-        elif self.pool_kind() != "avg":
-            rows = self._pool_bwd(ws, dpooled, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
-                                  ws.gbuf[bi], *self._ew(ws, ct, bwd=True, rows=self.SLAB // ct), ops.POOL_ACT_RELU, done)
-        else:
-            rows = ops.gap_relu_bn_bwd(dpooled, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
-                                       ws.gbuf[bi], *self._ew(ws, ct, bwd=True, rows=self.SLAB // ct))
+        rows = self._head_bwd(ws, dlogits, ws.buf[bi], v(ws, blk.sc), v(ws, blk.sh), v(ws, blk.mean), v(ws, blk.rstd), v(ws, blk.sc),
+                              ws.gbuf[bi], *self._ew(ws, ct, bwd=True, rows=self.SLAB // ct), m.classifier, ops.POOL_ACT_RELU, None, done)
         self._norm_bwd(ws, m.features.norm5, blk, self._sc(ws, ct, rows), self._count(ws.buf[bi]), acc=blk,
                        q=self._slice_q(ws, bi, self.blocks[bi][1] - 1))
 

@@ -271,34 +271,20 @@ class _Engine(FusedEngine):
         return t["out"]
 
     def _head_forward(self, ws, xin, train):
-        """1x1 convolution to 1280 channels, BatchNorm, Swish + global average pool in one kernel, Dropout, classifier"""
+        """1x1 convolution to 1280 channels, BatchNorm, the Dropout mask, then the shared head behind Swish"""
         m, v, B = self.model, self._v, ws.B
         Sh = self.bn[id(m.head[1])]
         rows = ops.conv_gemm(xin, self.w_fwd(m.head[0]), ws.yh, N=1280, **self._sp(ws, Sh))
         self._bn_coef(ws, m.head[1], B * ws.hw_last[0] * ws.hw_last[1], train, rows)
-        if self.head_kind() in ("csra", "pcam"):    # set_head: Swish, Dropout mask and classifier at every pixel, pooled per class
-            p_do = m.head[5].p if train else 0.0
-            ws.drop = None
-            if p_do > 0.0:
-                ws.drop = torch.empty(B, 1280, dtype=torch.float32, device=self.device)
-                ops.dropout_mask_dev(ws.drop, 1.0 - p_do, self._seed_base(len(self.mb)), self.step_dev)
-                self.last_masks["head"] = ws.drop
-            return self._map_head()[0](ws, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.drop, m.head[6], ops.POOL_ACT_SWISH)
-        if self.pool_kind() != "avg":               # set_pool: the pooling's kernel in the average's place
-            self._pool_fwd(ws, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ops.POOL_ACT_SWISH)
-        else:
-            ops.gap_affine_act(ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.pooled, act=2, rows=ws.slab[0])
-        # Dropout in front of the classifier (efficientnet.py:169-171), train mode only
+        # Dropout in front of the classifier (efficientnet.py:169-171), train mode only: the mask is drawn here, the shared head
+        # (FusedEngine._head_fwd) applies it
         p_do = m.head[5].p if train else 0.0
-        ws.drop, ws.fc_in = None, ws.pooled
+        mask = None
         if p_do > 0.0:
-            ws.drop = torch.empty(B, 1280, dtype=torch.float32, device=self.device)
-            ops.dropout_mask_dev(ws.drop, 1.0 - p_do, self._seed_base(len(self.mb)), self.step_dev)
-            ws.pooled_d = torch.empty_like(ws.pooled)
-            ops.mul_f32(ws.pooled, ws.drop, ws.pooled_d)
-            ws.fc_in = ws.pooled_d
-            self.last_masks["head"] = ws.drop
-        ops.linear_fwd(ws.fc_in, m.head[6].weight, m.head[6].bias, ws.logits)
+            mask = torch.empty(B, 1280, dtype=torch.float32, device=self.device)
+            ops.dropout_mask_dev(mask, 1.0 - p_do, self._seed_base(len(self.mb)), self.step_dev)
+            self.last_masks["head"] = mask
+        self._head_fwd(ws, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), m.head[6], ops.POOL_ACT_SWISH, mask, rows=ws.slab[0])
 
     def _seed_base(self, idx):
         """Host part of the 64-bit seed of the mask of block `idx`: (model seed, block); the kernel adds the device-side count of
@@ -335,23 +321,10 @@ class _Engine(FusedEngine):
     def _head_backward(self, ws, dlogits, done):
         """Returns the gradient of the last block's output."""
         m, v, G, B = self.model, self._v, self.grad_of, ws.B
-        fc, Sh = m.head[6], self.bn[id(m.head[1])]
-        csra = self.head_kind() in ("csra", "pcam")
-        if not csra:
-            dpool = torch.empty(B, 1280, dtype=torch.float32, device=self.device)
-            ops.head_bwd(dlogits, ws.fc_in, fc.weight, G(fc.weight), G(fc.bias), dpool)
-            if ws.drop is not None:
-                ops.mul_f32(dpool, ws.drop, dpool)
+        Sh = self.bn[id(m.head[1])]
         dzh = ws.bwd["dze"][:ws.yh.numel()].view(ws.yh.shape)
-        if csra:
-            rows = self._map_head()[1](ws, dlogits, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), ws.drop, v(ws, Sh.mean), v(ws, Sh.rstd), v(ws, self.ones, 1280),
-                                  dzh, *self._ew(ws, Sh, bwd=True), fc, ops.POOL_ACT_SWISH, done)
-        elif self.pool_kind() != "avg":
-            rows = self._pool_bwd(ws, dpool, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), v(ws, Sh.mean), v(ws, Sh.rstd), v(ws, self.ones, 1280), dzh,
-                                  *self._ew(ws, Sh, bwd=True), ops.POOL_ACT_SWISH, done)
-        else:
-            rows = ops.se_act_bwd(None, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), v(ws, Sh.mean), v(ws, Sh.rstd), None, dpool, dzh,
-                                  *self._ew(ws, Sh, bwd=True))
+        rows = self._head_bwd(ws, dlogits, ws.yh, v(ws, Sh.sc), v(ws, Sh.sh), v(ws, Sh.mean), v(ws, Sh.rstd), v(ws, self.ones, 1280), dzh,
+                              *self._ew(ws, Sh, bwd=True), m.head[6], ops.POOL_ACT_SWISH, ws.drop, done)
         self._bn_bwd(ws, m.head[1], rows, B * ws.hw_last[0] * ws.hw_last[1])
         g, xlast = ws.bwd["g"][-1], ws.blk[-1]["out"]
         ops.conv_gemm(dzh, self.w_bwd(m.head[0]), g, N=xlast.shape[3], **self._pro_bnbwd(ws, ws.yh, Sh))

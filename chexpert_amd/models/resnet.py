@@ -304,7 +304,7 @@ class _Engine(FusedEngine):
     def forward(self, x, train, record=False):
         """train: batch statistics (and running-statistic updates); eval: running statistics.  record (eval): also keep what
         backward reads -- the join ReLU sign bits, which an eval forward without a backward skips."""
-        m, v = self.model, self._v
+        m = self.model
         u8 = x.dtype == torch.uint8             # decoded grey bytes (B,1,H,W): whitened + expanded on the GPU (cx_u8_to_nhwc4)
         if x.dim() != 4 or x.shape[1] != (1 if u8 else 3):
             raise RuntimeError("expected a (B,3,H,W) float input or a (B,1,H,W) uint8 image")
@@ -323,16 +323,15 @@ class _Engine(FusedEngine):
                 xin = self._basic_forward(ws, bi, xin)
             else:
                 xin, xin_lo, pending = self._bottleneck_forward(ws, bi, xin, xin_lo, pending)
-        if self.head_kind() in ("csra", "pcam"):    # set_head: the classifier at every pixel, pooled per class
-            self._map_head()[0](ws, xin, v(ws, self.ones), v(ws, self.zeros), None, m.fc, ops.POOL_ACT_RELU)
-        elif self.pool_kind() != "avg":             # set_pool: the pooling's kernel, then the classifier
-            self._pool_fwd(ws, xin, v(ws, self.ones), v(ws, self.zeros), ops.POOL_ACT_RELU)
-            ops.linear_fwd(ws.pooled, m.fc.weight, m.fc.bias, ws.logits)
-        else:
-            ops.head_fwd(xin, v(ws, self.ones), v(ws, self.zeros), m.fc.weight, m.fc.bias, ws.pooled, ws.logits)
+        self._head_forward(ws, xin)
         if train:
             m._nbt_pending += 1
         return ws
+
+    def _head_forward(self, ws, xin):
+        """The shared head (FusedEngine._head_fwd) on the last block's output, which is already activated: ReLU of x * 1 + 0."""
+        v = self._v
+        self._head_fwd(ws, xin, v(ws, self.ones), v(ws, self.zeros), self.model.fc, ops.POOL_ACT_RELU)
 
     def _stem_forward(self, ws, x):
         """7x7 stride-2 convolution, BatchNorm + ReLU + 3x3 stride-2 max-pool in one kernel"""
@@ -492,20 +491,12 @@ class _Engine(FusedEngine):
             self._stem_backward(ws, dx)
 
     def _head_backward(self, ws, dlogits, done):
-        m, v, G = self.model, self._v, self.grad_of
+        v = self._v
         last = ws.blk[-1]["out"]
         Cl = last.shape[3]
         ones, zeros = v(ws, self.ones, Cl), v(ws, self.zeros, Cl)
-        if self.head_kind() in ("csra", "pcam"):
-            return self._map_head()[1](ws, dlogits, last, ones, zeros, None, zeros, ones, ones, ws.bwd["g"][-1], v(ws, self.scratch[0], Cl),
-                                  v(ws, self.scratch[1], Cl), 0, m.fc, ops.POOL_ACT_RELU, done)
-        dpooled = torch.empty(ws.B, Cl, dtype=torch.float32, device=self.device)
-        ops.head_bwd(dlogits, ws.pooled, m.fc.weight, G(m.fc.weight), G(m.fc.bias) if m.fc.bias is not None else None, dpooled)
-        if self.pool_kind() != "avg":
-            return self._pool_bwd(ws, dpooled, last, ones, zeros, zeros, ones, ones, ws.bwd["g"][-1], v(ws, self.scratch[0], Cl),
-                                  v(ws, self.scratch[1], Cl), 0, ops.POOL_ACT_RELU, done)
-        ops.gap_relu_bn_bwd(dpooled, last, ones, zeros, zeros, ones, ones, ws.bwd["g"][-1], v(ws, self.scratch[0], Cl),
-                            v(ws, self.scratch[1], Cl))
+        self._head_bwd(ws, dlogits, last, ones, zeros, zeros, ones, ones, ws.bwd["g"][-1], v(ws, self.scratch[0], Cl),
+                       v(ws, self.scratch[1], Cl), 0, self.model.fc, ops.POOL_ACT_RELU, None, done)
 
     def _join_backward(self, ws, bi, rows=None):
         """Residual join backward of block bi: dz = dOut * [out > 0] in place in the block's gradient buffer g, with the backward

@@ -887,95 +887,91 @@ CSRA_MAX_CLASSES = 64                                       # CX_CSRA_MAX_CLASSE
 CSRA_STAT = 4                                               # floats per (image, class) the forward leaves for the way back
 
 
-def _csra_args(x, m, w, attn, act):
+def _map_args(kind, x, m, w, attn, act):
+    """The shared argument check of the two heads that pool a per-pixel score map.  Returns (B, HW, C, ldx, n, the [lambda, T] argument of
+    the cx_csra_* entry points: cx_pcam_* take none)."""
+    assert kind in ("csra", "pcam")
     require_cuda(x, m, w, attn)
     B, H, W, Cc, ldx = _nhwc(x)
     n = w.shape[0]
     assert act in (POOL_ACT_RELU, POOL_ACT_SWISH)
     assert tuple(w.shape) == (n, Cc) and w.dtype == torch.float32 and w.is_contiguous()
-    assert attn.dtype == torch.float32 and attn.numel() == 2 and attn.is_contiguous(), "csra_head_*: attn is the fp32 device tensor [lambda, T]"
+    if kind == "csra":
+        assert attn.dtype == torch.float32 and attn.numel() == 2 and attn.is_contiguous(), "csra_head_*: attn is the fp32 device tensor [lambda, T]"
     assert m is None or (tuple(m.shape) == (B, Cc) and m.dtype == torch.float32 and m.is_contiguous())
-    return B, H * W, Cc, ldx, n
+    return B, H * W, Cc, ldx, n, ((ptr(attn),) if kind == "csra" else ())
+
+
+def map_bwd_scratch(kind, B, HW, Cc, n):
+    """cx_<kind>_bwd_scratch: the floats of scratch map_head_bwd needs at this shape (pcam: csra's + B n)."""
+    name = "cx_%s_bwd_scratch" % kind
+    r = getattr(lib(), name)(B, HW, Cc, n)
+    if r < 0:
+        check(int(r), name)
+    return int(r)
+
+
+def map_head_fwd(kind, x, sc, sh, m, w, bias, attn, logits, s, stat, *, act):
+    """cx_<kind>_head_fwd, kind "csra" or "pcam": s (B,n,HW) fp32 = the classifier w (n,C) at every pixel of act(x*sc + sh) * m (m (B,C)
+    fp32 or None); logits (B,n) pooled from it per class; stat (B,n,4) is what the backward reads.
+    csra: logits = bias + mean_p s + lambda * softmax_p(T s) . s with attn = [lambda, T] in device memory.
+    pcam: logits = sum_p w_p (s_p + bias) with w_p = sigmoid(s_p + bias) / sum_q sigmoid(s_q + bias); attn is not read."""
+    B, HW, Cc, ldx, n, lam = _map_args(kind, x, m, w, attn, act)
+    for t, shape in ((logits, (B, n)), (s, (B, n, HW)), (stat, (B, n, CSRA_STAT))):
+        assert tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous()
+    name = "cx_%s_head_fwd" % kind
+    check(_fn(name, x)(ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(w), ptr(bias), *lam, ptr(logits), ptr(s), ptr(stat), B, HW, Cc, ldx, n, act,
+                       stream_ptr()), name)
+
+
+def map_head_bwd(kind, dlogits, s, stat, attn, x, sc, sh, m, mean, rstd, e_scale, w, g, S1, S2, dw, db, scratch, *, act, stat_rows=0):
+    """cx_<kind>_head_bwd: the backward of map_head_fwd with the contract of gap_relu_bn_bwd (g = e_scale * dz, S1 / S2; stat_rows > 0:
+    one statistic row per image); dw (n,C) and db (n,; or None) are added to, in a fixed order through `scratch` (fp32, at least
+    map_bwd_scratch floats).  Returns the row count in rows mode."""
+    B, HW, Cc, ldx, n, lam = _map_args(kind, x, m, w, attn, act)
+    require_cuda(dlogits, s, stat, g, dw, db, scratch)
+    assert tuple(dlogits.shape) == (B, n) and dlogits.dtype == torch.float32 and dlogits.is_contiguous()
+    assert g.dtype == x.dtype and g.shape == x.shape
+    assert dw.numel() == n * Cc and dw.dtype == torch.float32 and dw.is_contiguous() and (db is None or db.numel() == n)
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous()
+    name = "cx_%s_head_bwd" % kind
+    check(_fn(name, x)(ptr(dlogits), ptr(s), ptr(stat), *lam, ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(mean), ptr(rstd), ptr(e_scale), ptr(w),
+                       ptr(g), ptr(S1), ptr(S2), ptr(dw), ptr(db), ptr(scratch), scratch.numel(), B, HW, Cc, ldx, _nhwc(g)[4], n, act,
+                       stat_rows, stream_ptr()), name)
+    return lib().cx_last_stat_rows() if stat_rows else None
 
 
 def csra_bwd_scratch(B, HW, Cc, n):
     """cx_csra_bwd_scratch: the floats of scratch csra_head_bwd needs at this shape."""
-    r = lib().cx_csra_bwd_scratch(B, HW, Cc, n)
-    if r < 0:
-        check(int(r), "cx_csra_bwd_scratch")
-    return int(r)
+    return map_bwd_scratch("csra", B, HW, Cc, n)
 
 
 def csra_head_fwd(x, sc, sh, m, w, bias, attn, logits, s, stat, *, act):
-    """cx_csra_head_fwd: s (B,n,HW) fp32 = the classifier w (n,C) at every pixel of act(x*sc + sh) * m (m (B,C) fp32 or None), logits
-    (B,n) = bias + mean_p s + lambda * softmax_p(T s) . s with attn = [lambda, T] in device memory; stat (B,n,4) is what the backward
-    reads."""
-    B, HW, Cc, ldx, n = _csra_args(x, m, w, attn, act)
-    for t, shape in ((logits, (B, n)), (s, (B, n, HW)), (stat, (B, n, CSRA_STAT))):
-        assert tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous()
-    check(_fn("cx_csra_head_fwd", x)(ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(w), ptr(bias), ptr(attn), ptr(logits), ptr(s), ptr(stat), B, HW, Cc,
-                                     ldx, n, act, stream_ptr()), "cx_csra_head_fwd")
+    """map_head_fwd of the csra head."""
+    return map_head_fwd("csra", x, sc, sh, m, w, bias, attn, logits, s, stat, act=act)
 
 
 def csra_head_bwd(dlogits, s, stat, attn, x, sc, sh, m, mean, rstd, e_scale, w, g, S1, S2, dw, db, scratch, *, act, stat_rows=0):
-    """cx_csra_head_bwd: the backward of csra_head_fwd with the contract of gap_relu_bn_bwd (g = e_scale * dz, S1 / S2; stat_rows > 0:
-    one statistic row per image); dw (n,C) and db (n,; or None) are added to, in a fixed order through `scratch` (fp32, at least
-    csra_bwd_scratch floats).  Returns the row count in rows mode."""
-    B, HW, Cc, ldx, n = _csra_args(x, m, w, attn, act)
-    require_cuda(dlogits, s, stat, g, dw, db, scratch)
-    assert tuple(dlogits.shape) == (B, n) and dlogits.dtype == torch.float32 and dlogits.is_contiguous()
-    assert g.dtype == x.dtype and g.shape == x.shape
-    assert dw.numel() == n * Cc and dw.dtype == torch.float32 and dw.is_contiguous() and (db is None or db.numel() == n)
-    assert scratch.dtype == torch.float32 and scratch.is_contiguous()
-    check(_fn("cx_csra_head_bwd", x)(ptr(dlogits), ptr(s), ptr(stat), ptr(attn), ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(mean), ptr(rstd),
-                                     ptr(e_scale), ptr(w), ptr(g), ptr(S1), ptr(S2), ptr(dw), ptr(db), ptr(scratch), scratch.numel(), B, HW,
-                                     Cc, ldx, _nhwc(g)[4], n, act, stat_rows, stream_ptr()), "cx_csra_head_bwd")
-    return lib().cx_last_stat_rows() if stat_rows else None
+    """map_head_bwd of the csra head."""
+    return map_head_bwd("csra", dlogits, s, stat, attn, x, sc, sh, m, mean, rstd, e_scale, w, g, S1, S2, dw, db, scratch, act=act,
+                        stat_rows=stat_rows)
 
 
 # ---- probabilistic-CAM pooling head (csrc/csra_head.hip): the csra operands without [lambda, T]
-def _pcam_args(x, m, w, act):
-    require_cuda(x, m, w)
-    B, H, W, Cc, ldx = _nhwc(x)
-    n = w.shape[0]
-    assert act in (POOL_ACT_RELU, POOL_ACT_SWISH)
-    assert tuple(w.shape) == (n, Cc) and w.dtype == torch.float32 and w.is_contiguous()
-    assert m is None or (tuple(m.shape) == (B, Cc) and m.dtype == torch.float32 and m.is_contiguous())
-    return B, H * W, Cc, ldx, n
-
-
 def pcam_bwd_scratch(B, HW, Cc, n):
     """cx_pcam_bwd_scratch: the floats of scratch pcam_head_bwd needs at this shape (csra_bwd_scratch + B n)."""
-    r = lib().cx_pcam_bwd_scratch(B, HW, Cc, n)
-    if r < 0:
-        check(int(r), "cx_pcam_bwd_scratch")
-    return int(r)
+    return map_bwd_scratch("pcam", B, HW, Cc, n)
 
 
 def pcam_head_fwd(x, sc, sh, m, w, bias, logits, s, stat, *, act):
-    """cx_pcam_head_fwd: s (B,n,HW) fp32 = the classifier w (n,C) at every pixel of act(x*sc + sh) * m (csra_head_fwd's score map),
-    logits (B,n) = sum_p w_p (s_p + bias) with w_p = sigmoid(s_p + bias) / sum_q sigmoid(s_q + bias); stat (B,n,4) is what the
-    backward reads."""
-    B, HW, Cc, ldx, n = _pcam_args(x, m, w, act)
-    for t, shape in ((logits, (B, n)), (s, (B, n, HW)), (stat, (B, n, CSRA_STAT))):
-        assert tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous()
-    check(_fn("cx_pcam_head_fwd", x)(ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(w), ptr(bias), ptr(logits), ptr(s), ptr(stat), B, HW, Cc, ldx, n, act,
-                                     stream_ptr()), "cx_pcam_head_fwd")
+    """map_head_fwd of the pcam head: csra_head_fwd's arguments without attn."""
+    return map_head_fwd("pcam", x, sc, sh, m, w, bias, None, logits, s, stat, act=act)
 
 
 def pcam_head_bwd(dlogits, s, stat, x, sc, sh, m, mean, rstd, e_scale, w, g, S1, S2, dw, db, scratch, *, act, stat_rows=0):
-    """cx_pcam_head_bwd: the backward of pcam_head_fwd with the contract of csra_head_bwd; `scratch` holds at least pcam_bwd_scratch
-    floats.  Returns the row count in rows mode."""
-    B, HW, Cc, ldx, n = _pcam_args(x, m, w, act)
-    require_cuda(dlogits, s, stat, g, dw, db, scratch)
-    assert tuple(dlogits.shape) == (B, n) and dlogits.dtype == torch.float32 and dlogits.is_contiguous()
-    assert g.dtype == x.dtype and g.shape == x.shape
-    assert dw.numel() == n * Cc and dw.dtype == torch.float32 and dw.is_contiguous() and (db is None or db.numel() == n)
-    assert scratch.dtype == torch.float32 and scratch.is_contiguous()
-    check(_fn("cx_pcam_head_bwd", x)(ptr(dlogits), ptr(s), ptr(stat), ptr(x), ptr(sc), ptr(sh), ptr(m), ptr(mean), ptr(rstd), ptr(e_scale),
-                                     ptr(w), ptr(g), ptr(S1), ptr(S2), ptr(dw), ptr(db), ptr(scratch), scratch.numel(), B, HW, Cc, ldx,
-                                     _nhwc(g)[4], n, act, stat_rows, stream_ptr()), "cx_pcam_head_bwd")
-    return lib().cx_last_stat_rows() if stat_rows else None
+    """map_head_bwd of the pcam head: csra_head_bwd's arguments without attn."""
+    return map_head_bwd("pcam", dlogits, s, stat, None, x, sc, sh, m, mean, rstd, e_scale, w, g, S1, S2, dw, db, scratch, act=act,
+                        stat_rows=stat_rows)
 
 
 def unpool2_mask(d, x, sc, sh, mean, rstd, e_scale, g, S1, S2, stat_rows=0):

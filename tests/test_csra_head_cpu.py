@@ -147,7 +147,7 @@ def test_set_head_is_refused_once_the_engine_has_bound():
         eng = model._eng()
         model.set_head("csra")                                         # an engine that has not bound yet does not lock the choice
         eng = model._eng()
-        assert eng.head_kind() == "csra"
+        assert eng.head_kind() == "csra" and eng._head_path() == "csra"  # (the one name _head_fwd / _head_bwd pick their kernels by)
         eng.flat = torch.zeros(4)                                      # what bind_params leaves behind
         with pytest.raises(RuntimeError, match="before the engine has bound"):
             model.set_head("linear")

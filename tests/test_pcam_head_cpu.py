@@ -209,7 +209,7 @@ def test_set_head_is_refused_once_the_engine_has_bound():
         eng = model._eng()
         model.set_head("pcam")                                         # an engine that has not bound yet does not lock the choice
         eng = model._eng()
-        assert eng.head_kind() == "pcam" and eng._map_head() == (eng._pcam_fwd, eng._pcam_bwd)
+        assert eng.head_kind() == "pcam" and eng._head_path() == "pcam"  # (the one name _head_fwd / _head_bwd pick their kernels by)
         eng.flat = torch.zeros(4)                                      # what bind_params leaves behind
         for kind in ("linear", "csra"):
             with pytest.raises(RuntimeError, match="before the engine has bound"):
