@@ -165,6 +165,12 @@ SIGNATURES = {
     "cx_adam_step_items": [_vp, _vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _f, _i, _f, _f, _f, _f, _vp, _vp, _f, _i, _i, _vp],
     "cx_sgd_nesterov_step_items": [_vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _f, _i, _f, _f, _vp, _vp, _f, _i, _i, _vp],
     "cx_rmsprop_step_items": [_vp, _vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _f, _i, _f, _f, _f, _f, _vp, _vp, _f, _i, _i, _vp],
+    # (the Adam / SGD lists up to skip_nonfinite, then tensor_items, n_tensors, part_w, part_u, trust, [u | coef, eps], trust_clip,
+    # always_adapt, stream)
+    "cx_lamb_step_items": [_vp, _vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _f, _i, _f, _f, _f, _f, _vp, _vp, _f, _i, _i,
+                           _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "cx_lars_step_items": [_vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _f, _i, _f, _f, _vp, _vp, _f, _i, _i,
+                           _vp, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp],
     "cx_aa_attention_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "cx_aa_attention_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "cx_aa_attention_weights": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],

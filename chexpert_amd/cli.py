@@ -120,6 +120,16 @@
   --freeze_backbone_steps N   the classifier trains alone for the first N minibatches, then the backbone is thawed (-1: for the whole
                         run, a linear probe).  The backward pass still fills every gradient and BatchNorm running statistics keep
                         moving; the optimiser kernels skip the frozen tensors.  Works with --graph (the group table lives on the device)
+  --optimizer lamb|lars the layer-wise trust-ratio optimisers (optim.FusedLAMB on Adam, optim.FusedLARS on SGD with Nesterov momentum and its
+                        MultiStepLR) instead of the model's own, for every --model (needs --fused_optimizer): each tensor's update is
+                        rescaled by |p| / |update|, computed inside the step on the device, so one --lr serves every layer at a large
+                        global batch.  Works with --graph, more than one rank, --clip_grad_norm, --skip_nonfinite, --ema_decay,
+                        --weight_decay, --no_decay_norm_bias (the 1-D parameters then get neither decay nor adaptation),
+                        --head_lr_mult, --backbone_lr_mult and --freeze_backbone_steps; not with --decoupled_decay (LAMB's decay
+                        already sits outside the moments, LARS's is part of the ratio).  --trust_coef C: the coefficient of lars
+                        (default 0.001; lars only); --trust_clip: ratios capped at 1; --always_adapt: tensors without weight decay are
+                        adapted too.  The json log line gains trust_min / trust_max over the adapted tensors.  --restore of a
+                        checkpoint written under another optimiser is refused
   --bootstrap B         B > 0: every eval_results_<tag>.json gets an auc_ci_<tag>.json beside it (rank 0): AUROC per class and for the mean
                         with its (1 - A) percentile bootstrap interval over B replicates, computed on the GPU (metrics.bootstrap_auc);
                         --bootstrap_seed S (default: --seed), --bootstrap_unit image|study|patient (what is resampled; study and
@@ -260,6 +270,11 @@ def build_parser():
     p.add_argument("--backbone_lr_mult", type=float, default=None, metavar="M", help="learning-rate multiplier of everything but the classifier")
     p.add_argument("--freeze_backbone_steps", type=int, default=0, metavar="N",
                    help="train the classifier alone for the first N minibatches (-1: the whole run)")
+    p.add_argument("--optimizer", default=None, choices=["lamb", "lars"],
+                   help="layer-wise trust-ratio optimiser instead of the model's own (needs --fused_optimizer)")
+    p.add_argument("--trust_coef", type=float, default=None, metavar="C", help="with --optimizer lars: the trust coefficient > 0 (default 0.001)")
+    p.add_argument("--trust_clip", action="store_true", help="with --optimizer: trust ratios capped at 1")
+    p.add_argument("--always_adapt", action="store_true", help="with --optimizer: adapt the tensors without weight decay too")
     p.add_argument("--bootstrap", type=int, default=0, metavar="B", help="bootstrap replicates of the AUROC intervals written beside every eval_results file (0: none)")
     p.add_argument("--bootstrap_seed", type=int, default=None, metavar="S", help="seed of the bootstrap draws (default: --seed)")
     p.add_argument("--bootstrap_unit", default="image", choices=list(BOOTSTRAP_UNITS), help="what the bootstrap resamples")
@@ -1045,6 +1060,43 @@ def group_options(args):
     return {"weight_decay": wd or 0.0, "decoupled": bool(dec), "finetune": finetune, "freeze_steps": fz}
 
 
+def trust_options(args):
+    """--optimizer / --trust_coef / --trust_clip / --always_adapt, validated: {} without --optimizer (the model's own optimiser, as
+    ever), else {"kind", "trust_clip", "always_adapt"} and, for lars, "trust_coef"."""
+    import math
+    kind, coef = getattr(args, "optimizer", None), getattr(args, "trust_coef", None)
+    clip, adapt = getattr(args, "trust_clip", False), getattr(args, "always_adapt", False)
+    if kind is None:
+        for flag, on in (("--trust_coef", coef is not None), ("--trust_clip", clip), ("--always_adapt", adapt)):
+            if on:
+                raise ValueError("%s belongs to the trust-ratio optimisers: pass --optimizer lamb|lars with it" % flag)
+        return {}
+    if kind not in ("lamb", "lars"):
+        raise ValueError("--optimizer takes lamb or lars (got %r)" % (kind,))
+    if not args.fused_optimizer:
+        raise ValueError("--optimizer %s works inside the fused optimiser step: pass --fused_optimizer with it" % kind)
+    if getattr(args, "decoupled_decay", False):
+        raise ValueError("--decoupled_decay cannot be combined with --optimizer %s: %s" % (kind, (
+            "LAMB's weight decay already sits outside the moments" if kind == "lamb" else "LARS's weight decay is part of the trust ratio")))
+    out = {"kind": kind, "trust_clip": bool(clip), "always_adapt": bool(adapt)}
+    if coef is not None:
+        if kind != "lars":
+            raise ValueError("--trust_coef is the coefficient of --optimizer lars; lamb's ratio has none")
+        if not (math.isfinite(coef) and coef > 0):
+            raise ValueError("--trust_coef takes a finite coefficient > 0 (got %r)" % coef)
+        out["trust_coef"] = float(coef)
+    return out
+
+
+def trust_optimizer(args, model, tr):
+    """(optimiser, scheduler) of --optimizer lamb|lars over `model`: FusedLAMB has no schedule, FusedLARS its parent's MultiStepLR."""
+    from . import optim as O
+    kw = dict(fused_optimizer_kwargs(args, model), **{k: v for k, v in tr.items() if k != "kind"})
+    if tr["kind"] == "lamb":
+        return O.FusedLAMB(model, lr=args.lr, **kw), None
+    return O.FusedLARS(model, lr=args.lr, **kw), "fused"
+
+
 def fused_optimizer_kwargs(args, model):
     """Keyword arguments of the fused optimiser's constructor for the clip / skip / EMA and the parameter-group flags."""
     from . import optim as O
@@ -1076,6 +1128,15 @@ def model_weights(ck, args, path=""):
 
 
 def make_model(args, device, pool=None, head=None):
+    """`model_and_own_optimizer`, or with --optimizer lamb|lars the same model under that optimiser (every --model alike)."""
+    tr = trust_options(args)                                 # validated before a model is built
+    model, opt, sched = model_and_own_optimizer(args, device, pool, head)
+    if tr:
+        opt, sched = trust_optimizer(args, model, tr)
+    return model, opt, sched
+
+
+def model_and_own_optimizer(args, device, pool=None, head=None):
     """Model zoo and optimiser wiring of chexpert.py:461-502.  pool: the keywords of FusedNet.set_pool (None: the average), applied
     before the optimiser is built -- GeM's exponent is one of its parameters.  head: the keywords of FusedNet.set_head (None: linear)."""
     from . import optim as O
@@ -1262,6 +1323,7 @@ def main(argv=None):
         raise ValueError("--synthetic_uncertain takes a fraction in [0, 1] (got %r)" % args.synthetic_uncertain)
     if args.synthetic_uncertain > 0 and not args.synthetic:
         raise ValueError("--synthetic_uncertain marks labels of the synthetic set: pass --synthetic N with it")
+    trust_on = trust_options(args)
     ex = optimizer_options(args)
     groups_on = group_options(args)
     cam_classes = resolve_cam_classes(getattr(args, "cam_classes", None), args.n_classes)
@@ -1531,6 +1593,10 @@ def main(argv=None):
                         line["grad_norm"] = round(optimizer.grad_norm(), 5)
                         if optimizer.skipped_steps():
                             line["skipped"] = optimizer.skipped_steps()
+                    if trust_on:
+                        ratios = optimizer.adapted_ratios()
+                        if ratios:
+                            line["trust_min"], line["trust_max"] = round(min(ratios), 6), round(max(ratios), 6)
                     print(json.dumps(line), flush=True)
                 if args.step % args.eval_interval == 0:
                     ema_sd = None

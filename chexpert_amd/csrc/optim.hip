@@ -14,6 +14,8 @@
 //   cx_*_step_items       parameter groups (per-group learning-rate multiplier, weight decay (L2 or decoupled), frozen groups, a
 //                         per-group step count): a workgroup takes slices of items, reads the item's group row once per slice and
 //                         streams it with 16-byte loads and stores; an item of a frozen group is skipped: no byte written
+//   cx_lamb_step_items    the grouped steps with a per-tensor trust ratio |p| / |update| (LAMB on Adam, LARS on SGD-Nesterov): per-item
+//   cx_lars_step_items    partial sums, ONE workgroup that adds them per tensor in item order, then the update (three launches)
 //
 // The grouped kernels walk a table of work items instead of the flat index range.  The flat buffers hold every parameter tensor at
 // an offset that is a multiple of 4 floats, zero-padded to a multiple of 4:
@@ -407,12 +409,14 @@ int launch_rmsprop(float* p, const float* g, float* sq, float* buf, size_t n, co
 
 // ---- the grouped steps ----------------------------------------------------------------------------------------------------------
 // begin() takes what the group row fixes: lr_g = lr * lr_mult and the group's own 1-based step t_g = t - t0.
-template <class Rule>
+// TRUST (cx_lars_step_items): the decayed gradient is multiplied by trust[item.tensor].r ahead of update(); `trust` is not read
+// otherwise, and the TRUST = false instantiations are the kernels they were before the flag existed.
+template <class Rule, bool TRUST = false>
 __global__ __launch_bounds__(THREADS) void step_items_kernel(Rule r, float* __restrict__ p, const float* __restrict__ g,
                                                               const Item* __restrict__ items, int n_items,
                                                               const float* __restrict__ groups, int decoupled,
                                                               const float* __restrict__ hyper, float lr, int step, float gscale,
-                                                              Tail x) {
+                                                              Tail x, const float* __restrict__ trust, uint32_t n_tensors) {
   Launch q;
   if (!begin_launch(x, hyper, lr, step, gscale, q)) return;
   f32x4* __restrict__ p4 = reinterpret_cast<f32x4*>(p);
@@ -434,6 +438,11 @@ __global__ __launch_bounds__(THREADS) void step_items_kernel(Rule r, float* __re
     const float lr_g = q.lr * lr_mult;
     r.begin(lr_g, q.t - t0);
     const float keep = 1.f - lr_g * wd;
+    float ratio = 1.f;
+    if constexpr (TRUST) {
+      if (item.tensor >= n_tensors) continue;                        // a table that names no row of `trust`: nothing is read or written
+      ratio = trust[4 * (size_t)item.tensor];
+    }
     const uint32_t last = first + OG_SLOT_VEC4 < item.len4 ? first + OG_SLOT_VEC4 : item.len4;
     const size_t lo = (size_t)item.start4 + first, hi = (size_t)item.start4 + last;
     for (size_t i = lo + threadIdx.x; i < hi; i += THREADS) {
@@ -448,6 +457,7 @@ __global__ __launch_bounds__(THREADS) void step_items_kernel(Rule r, float* __re
         float gi = gv[c] * q.gs, pi = pv[c];
         float a = av[c], b = bv[c];
         decay(gi, pi, decoupled, wd, keep);
+        if constexpr (TRUST) gi *= ratio;
         const float pn = r.update(gi, pi, a, b);
         av[c] = a;
         bv[c] = b;
@@ -471,17 +481,204 @@ int check_tables(size_t n, const void* items, int n_items, const void* groups, i
   return 0;
 }
 
+// CX_EINVAL / CX_EALIGN of a grouped step, before any launch (s0, s1: the rule's state pointers)
+int check_step_items(const float* p, const float* g, const float* s0, const float* s1, size_t n, const uint32_t* items, int n_items,
+                     const float* groups, int n_groups, const float* hyper, int step, const Tail& x) {
+  if (!p || !g || !s0) return CX_EINVAL;
+  if (const int e = check_tables(n, items, n_items, groups, n_groups)) return e;
+  if (const int e = check_tail(hyper, step, x.ema, x.ema_decay, true)) return e;
+  if (!aligned16(p) || !aligned16(g) || !aligned16(s0) || !aligned16(s1)) return CX_EALIGN;
+  return 0;
+}
+
 template <class Rule>
 int launch_step_items(const Rule& r, float* p, const float* g, size_t n, const uint32_t* items, int n_items, const float* groups,
                       int n_groups, int decoupled, const float* hyper, float lr, int step, float gscale, const Tail& x, void* stream) {
-  if (!p || !g || !r.s0) return CX_EINVAL;
-  if (const int e = check_tables(n, items, n_items, groups, n_groups)) return e;
-  if (const int e = check_tail(hyper, step, x.ema, x.ema_decay, true)) return e;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(r.s0) || !aligned16(r.s1)) return CX_EALIGN;
+  if (const int e = check_step_items(p, g, r.s0, r.s1, n, items, n_items, groups, n_groups, hyper, step, x)) return e;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(step_items_kernel<Rule>, dim3(blocks_for((long long)n_items * OG_SLOTS)), dim3(THREADS), 0, as_stream(stream), r, p,
-                     g, reinterpret_cast<const Item*>(items), n_items, groups, decoupled ? 1 : 0, hyper, lr, step, gscale, x);
+  hipLaunchKernelGGL((step_items_kernel<Rule, false>), dim3(blocks_for((long long)n_items * OG_SLOTS)), dim3(THREADS), 0,
+                     as_stream(stream), r, p, g, reinterpret_cast<const Item*>(items), n_items, groups, decoupled ? 1 : 0, hyper, lr,
+                     step, gscale, x, (const float*)nullptr, 0u);
   return launch_status();
+}
+
+// ---- layer-wise trust ratios: LAMB and LARS -------------------------------------------------------------------------------------
+// Three launches on one stream, no atomics, nothing read on the host:
+//
+//   1. trust_partial_kernel  one workgroup per item: part_w[item] = sum p^2, part_u[item] = sum u^2.  LARS: u is the scaled
+//                            gradient g = grad_scale * clip[1] * grad.  LAMB: the Adam moments are advanced here (m, v written) and
+//                            u = (m / (1 - b1^t_g)) / (sqrt(v) / sqrt(1 - b2^t_g) + eps) + wd * p is stored in a scratch buffer
+//   2. trust_ratio_kernel    ONE workgroup, thread k, k + 256, ... owns tensor k: it adds the partials of the tensor's items
+//                            tensor_items[k] .. tensor_items[k + 1] - 1 one by one in item order and writes
+//                            trust[k] = {r, |p|, |u|, adapted}
+//   3. the apply             LAMB: p -= lr_g * r * u from the STORED u (a second kernel compiling the expression of u may round it
+//                            differently: the norm would then belong to another u than the one applied); LARS:
+//                            step_items_kernel<SgdRule, true>
+//
+// Every summation tree is a function of the item table alone.  An item of a frozen group writes partials of 0 and nothing else;
+// on a skipped step (begin_launch) none of the three kernels writes anything.  The zero padding of the flat layout adds 0 to both
+// sums and stays 0: p = g = m = v = 0 gives u = 0 / (0 + eps) + wd * 0 = 0 (eps > 0).
+struct TrustArgs {
+  const uint32_t* tensor_items;     // uint32[n_tensors + 1]: the first item of every tensor, then n_items
+  int n_tensors;
+  float *part_w, *part_u;           // n_items floats each
+  float* trust;                     // float[4] per tensor
+  float coef, eps;                  // LARS
+  int clip, always_adapt;
+};
+
+// the four-accumulator sums of sq_units for one 16-byte unit
+__device__ __forceinline__ void sq_acc(const f32x4& v, float (&a)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) a[c] = fmaf(v[c], v[c], a[c]);
+}
+
+template <bool LAMB>
+__global__ __launch_bounds__(THREADS) void trust_partial_kernel(AdamRule r, const float* __restrict__ p, const float* __restrict__ g,
+                                                                 float* __restrict__ u, const Item* __restrict__ items, int n_items,
+                                                                 const float* __restrict__ groups, const float* __restrict__ hyper,
+                                                                 float lr, int step, float gscale, Tail x,
+                                                                 float* __restrict__ part_w, float* __restrict__ part_u) {
+  Launch q;
+  if (!begin_launch(x, hyper, lr, step, gscale, q)) return;
+  const f32x4* __restrict__ p4 = reinterpret_cast<const f32x4*>(p);
+  const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g);
+  f32x4* __restrict__ m4 = reinterpret_cast<f32x4*>(r.s0);
+  f32x4* __restrict__ v4 = reinterpret_cast<f32x4*>(r.s1);
+  f32x4* __restrict__ u4 = reinterpret_cast<f32x4*>(u);
+  for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
+    const Item item = items[it];
+    const float* __restrict__ row = groups + 4 * (size_t)item.group;
+    const float wd = row[1], frozen = row[2], t0 = row[3];
+    if (frozen != 0.f) {                                             // uniform over the workgroup
+      if (threadIdx.x == 0) {
+        part_w[it] = 0.f;
+        part_u[it] = 0.f;
+      }
+      continue;
+    }
+    // the reciprocals of the bias corrections, once per item: one division and one square root per element are left.  DenseNet121's
+    // 212 whole items are fewer than the CUs, so a CU mostly runs ONE workgroup here and the launch is bound by the arithmetic of
+    // its four waves, not by memory (profiles/optim_trust_bench.txt)
+    float inv_bc1 = 1.f, inv_bc2_sqrt = 1.f;
+    if constexpr (LAMB) {
+      inv_bc1 = 1.f / (1.f - powf(r.b1, q.t - t0));
+      inv_bc2_sqrt = 1.f / sqrtf(1.f - powf(r.b2, q.t - t0));
+    }
+    float aw[4] = {0.f, 0.f, 0.f, 0.f}, au[4] = {0.f, 0.f, 0.f, 0.f};
+    const size_t lo = item.start4, hi = (size_t)item.start4 + item.len4;
+#pragma unroll 2
+    for (size_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+      // every load of the unit ahead of its stores
+      f32x4 gv = g4[i];
+      const f32x4 pv = p4[i];
+      if constexpr (LAMB) {
+        f32x4 mv = m4[i];
+        f32x4 vv = v4[i];
+        f32x4 uv;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float gi = gv[c] * q.gs;
+          mv[c] = r.b1 * mv[c] + (1.f - r.b1) * gi;
+          vv[c] = r.b2 * vv[c] + (1.f - r.b2) * gi * gi;
+          uv[c] = (mv[c] * inv_bc1) / (sqrtf(vv[c]) * inv_bc2_sqrt + r.eps) + wd * pv[c];
+        }
+        m4[i] = mv;
+        v4[i] = vv;
+        u4[i] = uv;
+        sq_acc(uv, au);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gv[c] *= q.gs;
+        sq_acc(gv, au);
+      }
+      sq_acc(pv, aw);
+    }
+    const float sw = block_fold((aw[0] + aw[1]) + (aw[2] + aw[3]));
+    __syncthreads();
+    const float su = block_fold((au[0] + au[1]) + (au[2] + au[3]));
+    if (threadIdx.x == 0) {
+      part_w[it] = sw;
+      part_u[it] = su;
+    }
+    __syncthreads();
+  }
+}
+
+template <bool LAMB>
+__global__ __launch_bounds__(THREADS) void trust_ratio_kernel(const Item* __restrict__ items, int n_items,
+                                                               const float* __restrict__ groups, int n_groups, Tail x, TrustArgs a) {
+  if (x.clip && x.skip_nonfinite && x.clip[2] != 0.f) return;       // begin_launch's test: a skipped step writes nothing
+  for (int k = threadIdx.x; k < a.n_tensors; k += THREADS) {
+    uint32_t first = a.tensor_items[k], last = a.tensor_items[k + 1];
+    if (last > (uint32_t)n_items) last = (uint32_t)n_items;
+    float sw = 0.f, su = 0.f;
+    for (uint32_t it = first; it < last; ++it) {
+      sw += a.part_w[it];
+      su += a.part_u[it];
+    }
+    const float wn = sqrtf(sw), un = sqrtf(su);
+    float ratio = 1.f, adapted = 0.f;
+    if (first < last) {
+      const uint32_t grp = items[first].group;
+      const float wd = grp < (uint32_t)n_groups ? groups[4 * (size_t)grp + 1] : 0.f;
+      const bool frozen = grp < (uint32_t)n_groups && groups[4 * (size_t)grp + 2] != 0.f;
+      if (!frozen && (wd != 0.f || a.always_adapt)) {
+        adapted = 1.f;
+        if (wn > 0.f && un > 0.f) {
+          ratio = LAMB ? wn / un : a.coef * wn / (un + wd * wn + a.eps);
+          if (a.clip) ratio = fminf(ratio, 1.f);
+        }
+      }
+    }
+    float* __restrict__ out = a.trust + 4 * (size_t)k;
+    out[0] = ratio;
+    out[1] = wn;
+    out[2] = un;
+    out[3] = adapted;
+  }
+}
+
+// The LAMB apply: step_items_kernel's slots over p, the stored u and the EMA.
+__global__ __launch_bounds__(THREADS) void lamb_apply_kernel(float* __restrict__ p, const float* __restrict__ u,
+                                                              const Item* __restrict__ items, int n_items,
+                                                              const float* __restrict__ groups, const float* __restrict__ hyper,
+                                                              float lr, int step, float gscale, Tail x,
+                                                              const float* __restrict__ trust, uint32_t n_tensors) {
+  Launch q;
+  if (!begin_launch(x, hyper, lr, step, gscale, q)) return;
+  f32x4* __restrict__ p4 = reinterpret_cast<f32x4*>(p);
+  const f32x4* __restrict__ u4 = reinterpret_cast<const f32x4*>(u);
+  f32x4* e4 = reinterpret_cast<f32x4*>(x.ema);
+  for (long long s = blockIdx.x; s < (long long)n_items * OG_SLOTS; s += gridDim.x) {
+    const Item item = items[s % n_items];
+    const uint32_t first = (uint32_t)(s / n_items) * OG_SLOT_VEC4;
+    if (first >= item.len4 || item.tensor >= n_tensors) continue;
+    const float* __restrict__ row = groups + 4 * (size_t)item.group;
+    if (row[2] != 0.f) continue;                                     // frozen: uniform over the workgroup
+    const float scale = q.lr * row[0] * trust[4 * (size_t)item.tensor];
+    const uint32_t last = first + OG_SLOT_VEC4 < item.len4 ? first + OG_SLOT_VEC4 : item.len4;
+    const size_t lo = (size_t)item.start4 + first, hi = (size_t)item.start4 + last;
+    for (size_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+      const f32x4 uv = u4[i];
+      f32x4 pv = p4[i];
+      f32x4 ev = e4 ? e4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        pv[c] = pv[c] - scale * uv[c];
+        ev[c] = q.d * ev[c] + q.omd * pv[c];
+      }
+      p4[i] = pv;
+      if (e4) e4[i] = ev;
+    }
+  }
+}
+
+int check_trust(const TrustArgs& a, size_t n, bool lars) {
+  if (!a.tensor_items || a.n_tensors < 1 || !a.trust) return CX_EINVAL;
+  if (n && (!a.part_w || !a.part_u)) return CX_EINVAL;
+  if (lars ? !(a.coef > 0.f && a.eps >= 0.f) : !(a.eps > 0.f)) return CX_EINVAL;
+  return 0;
 }
 
 // ---- cx_optim_tick applies the reference's schedulers (chexpert.py:165: stepped once per minibatch from lr_warmup_steps on; :480
@@ -616,6 +813,53 @@ int cx_sgd_nesterov_step_items(float* p, const float* g, float* buf, size_t n, c
   const SgdRule r = {buf, nullptr, momentum, 0, 0.f};
   return launch_step_items(r, p, g, n, items, n_items, groups, n_groups, decoupled, hyper, lr, step, grad_scale,
                            {clip, ema, ema_decay, ema_warmup, skip_nonfinite}, stream);
+}
+
+// ---- LAMB and LARS: the grouped Adam / SGD argument lists plus the trust tables.  Everything is validated before the first of the
+// three launches.  `decoupled` is refused: LAMB's decay already sits outside the moments, LARS's is part of the ratio.
+int cx_lamb_step_items(float* p, const float* g, float* m, float* v, size_t n, const uint32_t* items, int n_items, const float* groups,
+                       int n_groups, int decoupled, const float* hyper, float lr, int step, float beta1, float beta2, float eps,
+                       float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup, int skip_nonfinite,
+                       const uint32_t* tensor_items, int n_tensors, float* part_w, float* part_u, float* trust, float* u,
+                       int trust_clip, int always_adapt, void* stream) {
+  if (!v || decoupled || (n && !u)) return CX_EINVAL;
+  const Tail x = {clip, ema, ema_decay, ema_warmup, skip_nonfinite};
+  const TrustArgs a = {tensor_items, n_tensors, part_w, part_u, trust, 0.f, eps, trust_clip ? 1 : 0, always_adapt ? 1 : 0};
+  if (const int e = check_step_items(p, g, m, v, n, items, n_items, groups, n_groups, hyper, step, x)) return e;
+  if (const int e = check_trust(a, n, false)) return e;
+  if (!aligned16(u)) return CX_EALIGN;
+  if (n == 0) return 0;
+  const AdamRule r = {m, v, beta1, beta2, eps, 1.f, 1.f, false, 0.f};
+  const Item* tab = reinterpret_cast<const Item*>(items);
+  hipLaunchKernelGGL(trust_partial_kernel<true>, dim3(blocks_for(n_items)), dim3(THREADS), 0, as_stream(stream), r, p, g, u, tab, n_items,
+                     groups, hyper, lr, step, grad_scale, x, part_w, part_u);
+  hipLaunchKernelGGL(trust_ratio_kernel<true>, dim3(1), dim3(THREADS), 0, as_stream(stream), tab, n_items, groups, n_groups, x, a);
+  hipLaunchKernelGGL(lamb_apply_kernel, dim3(blocks_for((long long)n_items * OG_SLOTS)), dim3(THREADS), 0, as_stream(stream), p, u, tab,
+                     n_items, groups, hyper, lr, step, grad_scale, x, trust, (uint32_t)n_tensors);
+  return launch_status();
+}
+
+int cx_lars_step_items(float* p, const float* g, float* buf, size_t n, const uint32_t* items, int n_items, const float* groups,
+                       int n_groups, int decoupled, const float* hyper, float lr, int step, float momentum, float grad_scale,
+                       const float* clip, float* ema, float ema_decay, int ema_warmup, int skip_nonfinite,
+                       const uint32_t* tensor_items, int n_tensors, float* part_w, float* part_u, float* trust, float coef, float eps,
+                       int trust_clip, int always_adapt, void* stream) {
+  if (decoupled) return CX_EINVAL;
+  const Tail x = {clip, ema, ema_decay, ema_warmup, skip_nonfinite};
+  const TrustArgs a = {tensor_items, n_tensors, part_w, part_u, trust, coef, eps, trust_clip ? 1 : 0, always_adapt ? 1 : 0};
+  if (const int e = check_step_items(p, g, buf, nullptr, n, items, n_items, groups, n_groups, hyper, step, x)) return e;
+  if (const int e = check_trust(a, n, true)) return e;
+  if (n == 0) return 0;
+  const SgdRule r = {buf, nullptr, momentum, 0, 0.f};
+  const AdamRule none = {nullptr, nullptr, 0.f, 0.f, 0.f, 1.f, 1.f, false, 0.f};
+  const Item* tab = reinterpret_cast<const Item*>(items);
+  hipLaunchKernelGGL(trust_partial_kernel<false>, dim3(blocks_for(n_items)), dim3(THREADS), 0, as_stream(stream), none, p, g,
+                     (float*)nullptr, tab, n_items, groups, hyper, lr, step, grad_scale, x, part_w, part_u);
+  hipLaunchKernelGGL(trust_ratio_kernel<false>, dim3(1), dim3(THREADS), 0, as_stream(stream), tab, n_items, groups, n_groups, x, a);
+  hipLaunchKernelGGL((step_items_kernel<SgdRule, true>), dim3(blocks_for((long long)n_items * OG_SLOTS)), dim3(THREADS), 0,
+                     as_stream(stream), r, p, g, tab, n_items, groups, 0, hyper, lr, step, grad_scale, x, (const float*)trust,
+                     (uint32_t)n_tensors);
+  return launch_status();
 }
 
 // ---- RMSprop.  momentum == 0: buf is never touched and may be null.

@@ -1177,6 +1177,53 @@ def rmsprop_step_items(p, g, sq, buf, items, groups, decoupled, alpha, eps, mome
                                       *_optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)), "cx_rmsprop_step_items")
 
 
+def _trust_tables(ni, tensor_items, partials, trust):
+    """Checks of the trust-ratio tables of one launch; returns (tensor_items pointer, n_tensors, part_w pointer, part_u pointer,
+    trust pointer).  tensor_items: int32 (T + 1,), the first item of every tensor in increasing order, then n_items."""
+    part_w, part_u = partials
+    require_cuda(tensor_items, part_w, part_u, trust)
+    if tensor_items.dtype != torch.int32 or tensor_items.dim() != 1 or not tensor_items.is_contiguous() or tensor_items.numel() < 2:
+        raise ValueError("tensor_items: a contiguous int32 tensor (n_tensors + 1,) with n_tensors >= 1")
+    T = tensor_items.numel() - 1
+    _f32(part_w, part_u, n=ni)
+    _f32(trust, n=4 * T)
+    return ptr(tensor_items), T, ptr(part_w), ptr(part_u), ptr(trust)
+
+
+def lamb_step_items(p, g, m, v, items, groups, decoupled, beta1, beta2, eps, tensor_items, partials, trust, u, trust_clip=False,
+                    always_adapt=False, hyper=None, lr=0.0, step=0, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0, ema_warmup=True,
+                    skip_nonfinite=False):
+    """LAMB over the item table: Adam's moments, the update u stored in `u` (n floats of scratch), trust[k] = {r, |p|, |u|, adapted}
+    per tensor (partials: two buffers of n_items floats), then p -= lr_g * r * u.  Three launches."""
+    if decoupled:
+        raise ValueError("LAMB's weight decay already sits outside the moments: decoupled=True has no meaning")
+    if not eps > 0:
+        raise ValueError("eps must be > 0 (got %r): it keeps the update of the zero padding at 0" % (eps,))
+    n, pi, ni, pg, ng = _group_tables(p, items, groups, g, m, v, u, ema)
+    check(lib().cx_lamb_step_items(ptr(p), ptr(g), ptr(m), ptr(v), n, pi, ni, pg, ng, 0, ptr(hyper), lr, int(step), beta1, beta2, eps,
+                                   grad_scale, *_optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)[:-1],
+                                   *_trust_tables(ni, tensor_items, partials, trust), ptr(u), int(bool(trust_clip)),
+                                   int(bool(always_adapt)), stream_ptr()), "cx_lamb_step_items")
+
+
+def lars_step_items(p, g, buf, items, groups, decoupled, momentum, tensor_items, partials, trust, coef, eps, trust_clip=False,
+                    always_adapt=False, hyper=None, lr=0.0, step=0, grad_scale=1.0, clip=None, ema=None, ema_decay=0.0, ema_warmup=True,
+                    skip_nonfinite=False):
+    """LARS over the item table (`buf` starts as zeros): trust[k] = {r, |p|, |g|, adapted} per tensor with
+    r = coef |p| / (|g| + wd |p| + eps), then SGD with Nesterov momentum on r * (g + wd * p).  Three launches."""
+    if decoupled:
+        raise ValueError("LARS's weight decay is part of the trust ratio: decoupled=True has no meaning")
+    if not coef > 0:
+        raise ValueError("the trust coefficient must be > 0 (got %r)" % (coef,))
+    if not eps >= 0:
+        raise ValueError("eps must be >= 0 (got %r)" % (eps,))
+    n, pi, ni, pg, ng = _group_tables(p, items, groups, g, buf, ema)
+    check(lib().cx_lars_step_items(ptr(p), ptr(g), ptr(buf), n, pi, ni, pg, ng, 0, ptr(hyper), lr, int(step), momentum, grad_scale,
+                                   *_optim_tail(clip, ema, ema_decay, ema_warmup, skip_nonfinite)[:-1],
+                                   *_trust_tables(ni, tensor_items, partials, trust), coef, eps, int(bool(trust_clip)),
+                                   int(bool(always_adapt)), stream_ptr()), "cx_lars_step_items")
+
+
 def bf16_to_f32_nchw(x, out=None):
     B, H, W, Cc, ldx = _nhwc(x)
     if out is None:

@@ -4,6 +4,9 @@ Same update rules and defaults as the torch.optim classes the reference wires up
 (/root/reference/chexpert.py:470 Adam(lr); :479 SGD(momentum=0.9, nesterov=True); :499
 RMSprop(momentum=0.9, eps=1e-3)), with the schedulers of :480 (MultiStepLR[40000, 60000]) and :500
 (ExponentialLR(gamma)) folded in as `scheduler_step()`.
+
+Beside them, for large global batches, the layer-wise trust-ratio rules the reference does not have: `FusedLAMB` (on Adam's moments)
+and `FusedLARS` (on SGD with Nesterov momentum), stated in float64 as `reference_trust_step`.
 """
 import contextlib
 import math
@@ -66,6 +69,74 @@ def reference_step(kind, p, g, state, lr, t, lr_mult=1.0, weight_decay=0.0, froz
         state[1] = momentum * state[1] + g / (state[0].sqrt() + e)
         return p - lr_g * state[1]
     raise ValueError("unknown optimiser kind %r" % (kind,))
+
+
+def tensor_items(items, n_tensors):
+    """The first item of every tensor in an `item_table`, then the number of items: T + 1 entries (what cx_lamb_step_items and
+    cx_lars_step_items take as `tensor_items`).  Items come in buffer order and none crosses a tensor, so tensor k owns the items
+    [out[k], out[k + 1]); a tensor without elements owns none."""
+    out, at = [], 0
+    for k in range(int(n_tensors)):
+        out.append(at)
+        while at < len(items) and items[at][3] == k:
+            at += 1
+    if at != len(items):
+        raise ValueError("the items are not in tensor order, or name a tensor >= %d" % n_tensors)
+    return out + [at]
+
+
+def reference_trust_step(kind, tensors, grads, states, lr, t, group_rows, group_of, grad_scale=1.0, clip_coef=1.0, betas=(0.9, 0.999),
+                         eps=None, momentum=0.9, trust_coef=0.001, always_adapt=False, trust_clip=False):
+    """float64 statement of one LAMB / LARS step (what cx_lamb_step_items / cx_lars_step_items compute) over a LIST of tensors,
+    because the rule is per tensor: tensor k is in group group_of[k] with the row group_rows[j] = {lr_mult, weight_decay, frozen, t0}
+    (a sequence of four, or a dict with those keys).  t is the 1-based number of the minibatch.  Returns (new tensors, ratios) with
+    ratios[k] = (r, |p|, |u|, adapted) (LARS: |g| for |u|); `states[k]` (two float64 tensors shaped like tensor k, zeros before the
+    first step: m and v, or buf and an unused one) is updated in place.  A frozen group writes nothing (r = 1, norms 0).
+
+      lamb   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  u = (m / (1 - b1^tg)) / (sqrt(v / (1 - b2^tg)) + eps) + wd p
+             r = |p| / |u|;  p <- p - lr_g r u                                            (timm's Lamb, apex's FusedLAMB)
+      lars   r = coef |p| / (|g| + wd |p| + eps);  g' = r (g + wd p);  buf = momentum buf + g';  p <- p - lr_g (g' + momentum buf)
+                                                                                          (timm's Lars with nesterov=True)
+
+    with g = grad_scale * clip_coef * grad, lr_g = lr * lr_mult, tg = t - t0.  r is 1 unless the tensor is adapted (its group has
+    wd != 0, or always_adapt) and both norms are > 0; trust_clip: r = min(r, 1)."""
+    if kind not in ("lamb", "lars"):
+        raise ValueError("unknown trust-ratio optimiser kind %r" % (kind,))
+    e = (1e-6 if kind == "lamb" else 1e-8) if eps is None else float(eps)
+    out, ratios = [], []
+    for k, (p, grad) in enumerate(zip(tensors, grads)):
+        row = group_rows[group_of[k]]
+        if isinstance(row, dict):
+            row = [row.get("lr_mult", 1.0), row.get("weight_decay", 0.0), row.get("frozen", False), row.get("t0", 0)]
+        lr_mult, wd, frozen, t0 = float(row[0]), float(row[1]), bool(row[2]), row[3]
+        if frozen:
+            out.append(p)
+            ratios.append((1.0, 0.0, 0.0, False))
+            continue
+        p = p.double()
+        g = float(grad_scale) * float(clip_coef) * grad.double()
+        lr_g, tg = float(lr) * lr_mult, t - t0
+        adapted = wd != 0 or bool(always_adapt)
+        wn = float(p.pow(2).sum().sqrt())
+        if kind == "lamb":
+            states[k][0] = betas[0] * states[k][0] + (1 - betas[0]) * g
+            states[k][1] = betas[1] * states[k][1] + (1 - betas[1]) * g * g
+            u = (states[k][0] / (1 - betas[0] ** tg)) / ((states[k][1] / (1 - betas[1] ** tg)).sqrt() + e) + wd * p
+            un = float(u.pow(2).sum().sqrt())
+            r = wn / un if adapted and wn > 0 and un > 0 else 1.0
+            if trust_clip:
+                r = min(r, 1.0)
+            out.append(p - lr_g * r * u)
+        else:
+            un = float(g.pow(2).sum().sqrt())
+            r = trust_coef * wn / (un + wd * wn + e) if adapted and wn > 0 and un > 0 else 1.0
+            if trust_clip:
+                r = min(r, 1.0)
+            g2 = r * (g + wd * p)
+            states[k][0] = momentum * states[k][0] + g2
+            out.append(p - lr_g * (g2 + momentum * states[k][0]))
+        ratios.append((r, wn, un, adapted))
+    return out, ratios
 
 
 def finetune_groups(model, weight_decay=0.0, no_decay_norm_bias=False, head_lr_mult=1.0, backbone_lr_mult=1.0, freeze_backbone=False):
@@ -461,6 +532,120 @@ class FusedSGDNesterov(_Flat):
     def scheduler_step(self):
         self.sched_steps += 1
         self.lr = self.base_lr * self.gamma ** sum(self.sched_steps >= m for m in self.milestones)
+
+
+class _Trust:
+    """What FusedLAMB and FusedLARS share: the layer-wise trust ratio r_k = |p_k| / |update_k| of every parameter tensor, computed
+    on the device inside the step (csrc/optim.hip: per-item partial sums, one workgroup that adds them per tensor, the update).
+    Both always take the grouped path (`groups=None`: one default group) and refuse `decoupled`.  A tensor is adapted when its
+    group's weight decay is not 0, or when `always_adapt` is set (timm's rule): with finetune_groups(no_decay_norm_bias=True)
+    BatchNorm weights, biases and `pool_p` get neither decay nor adaptation.  `trust_clip`: r = min(r, 1)."""
+    USCRATCH = False                # LAMB: n floats that hold the update between the norm and the apply
+
+    def _init_trust(self, coef, eps, trust_clip, always_adapt):
+        if not (math.isfinite(float(coef)) and float(coef) > 0.0):
+            raise ValueError("trust_coef must be finite and > 0 (got %r)" % (coef,))
+        self.trust_coef, self.trust_eps = float(coef), float(eps)
+        self.trust_clip, self.always_adapt = bool(trust_clip), bool(always_adapt)
+        self._titems = self._tpart = self._trust = self._u = None
+
+    @staticmethod
+    def _refuse_decoupled(decoupled, why):
+        if decoupled:
+            raise ValueError("decoupled=True is refused: " + why)
+
+    def _bufs(self, n):
+        out = super()._bufs(self.NSTATE)
+        eng = self.model._eng()
+        dev, numel = eng.flat.device, eng.flat.numel()
+        if self._titems is None or self._titems.device != dev or self._tnumel != numel:
+            # beside the states: nothing is allocated while a graph is being captured.  Not state: every step rewrites them
+            T = len(eng.params)
+            starts = tensor_items(self._items.cpu().tolist(), T)
+            self._titems = torch.tensor(starts, dtype=torch.int32).to(dev)
+            self._tpart = (torch.zeros(max(1, self._items.shape[0]), dtype=torch.float32, device=dev),
+                           torch.zeros(max(1, self._items.shape[0]), dtype=torch.float32, device=dev))
+            self._trust = torch.zeros(max(1, T), 4, dtype=torch.float32, device=dev)
+            self._trust[:, 0] = 1.0
+            self._u = torch.zeros_like(eng.flat) if self.USCRATCH else None
+            self._tnumel = numel
+        return out
+
+    def _trust_args(self):
+        return {"tensor_items": self._titems, "partials": self._tpart, "trust": self._trust, "trust_clip": self.trust_clip,
+                "always_adapt": self.always_adapt}
+
+    def trust_ratios(self):
+        """{parameter name: (r, |p|, |u|)} of the most recent step that was not skipped (LARS: |g|, the scaled gradient's norm, for
+        |u|); r = 1 for a tensor that is not adapted or belongs to a frozen group.  Reads the device: synchronises."""
+        if self._trust is None:
+            return {}
+        name_of = {id(q): n for n, q in self.model.named_parameters()}
+        rows = self._trust.cpu().tolist()
+        return {name_of[id(q)]: tuple(rows[k][:3]) for k, q in enumerate(self.model._eng().params)}
+
+    def adapted_ratios(self):
+        """The ratios of the adapted tensors of the most recent step, as a list.  Reads the device: synchronises."""
+        return [] if self._trust is None else [r[0] for r in self._trust.cpu().tolist() if r[3] != 0.0]
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["trust"] = {"coef": self.trust_coef, "eps": self.trust_eps, "trust_clip": self.trust_clip, "always_adapt": self.always_adapt}
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        tr = sd.get("trust")
+        if tr is not None:
+            self._set_trust(tr)
+
+    def _set_trust(self, tr):
+        self.trust_coef, self.trust_eps = float(tr["coef"]), float(tr["eps"])
+        self.trust_clip, self.always_adapt = bool(tr["trust_clip"]), bool(tr["always_adapt"])
+
+
+class FusedLAMB(_Trust, _Flat):
+    """LAMB (You et al., ICLR 2020) in the bias-corrected form of timm's `Lamb` and apex's `FusedLAMB`: Adam's moments, the weight
+    decay added to the update outside them, the update of every tensor rescaled to lr * |p| (reference_trust_step).  `eps` is Adam's
+    (the ratio itself has none)."""
+    NSTATE = 2
+    KIND = "lamb"
+    USCRATCH = True
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, always_adapt=False, trust_clip=False, groups=None,
+                 decoupled=False, **options):
+        self._refuse_decoupled(decoupled, "LAMB's weight decay already sits outside the moments")
+        if not float(eps) > 0.0:
+            raise ValueError("eps must be > 0 (got %r): it keeps the update of the zero padding at 0" % (eps,))
+        super().__init__(model, lr, weight_decay=weight_decay, groups=groups or [], **options)
+        self.betas, self.eps = betas, float(eps)
+        self._init_trust(1.0, eps, trust_clip, always_adapt)
+
+    def _rule(self):
+        return dict(self._trust_args(), beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, u=self._u)
+
+    def _set_trust(self, tr):
+        super()._set_trust(tr)
+        self.eps = self.trust_eps
+
+
+class FusedLARS(_Trust, FusedSGDNesterov):
+    """LARS (You, Gitman, Ginsburg 2017) on SGD with Nesterov momentum, timm's `Lars` with nesterov=True (without its
+    trust_clip / lr quirk): r = trust_coef |p| / (|g| + wd |p| + eps) scales the decayed gradient ahead of the momentum
+    (reference_trust_step).  Keeps FusedSGDNesterov's MultiStepLR."""
+    KIND = "lars"
+
+    def __init__(self, model, lr, momentum=0.9, weight_decay=0.0, trust_coef=0.001, eps=1e-8, always_adapt=False, trust_clip=False,
+                 milestones=(40000, 60000), gamma=0.1, groups=None, decoupled=False, **options):
+        self._refuse_decoupled(decoupled, "LARS's weight decay is part of the trust ratio")
+        if not float(eps) >= 0.0:
+            raise ValueError("eps must be >= 0 (got %r)" % (eps,))
+        self._init_trust(trust_coef, eps, trust_clip, always_adapt)
+        super().__init__(model, lr, momentum=momentum, weight_decay=weight_decay, milestones=milestones, gamma=gamma, groups=groups or [],
+                         **options)
+
+    def _rule(self):
+        return dict(self._trust_args(), momentum=self.momentum, coef=self.trust_coef, eps=self.trust_eps)
 
 
 class FusedRMSprop(_Flat):

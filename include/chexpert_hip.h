@@ -618,6 +618,33 @@ int cx_rmsprop_step_items(float* p, const float* g, float* sq, float* buf, size_
                           float momentum, float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup,
                           int skip_nonfinite, void* stream);
 
+/* Layer-wise trust ratios over the same tables: LAMB (You et al., ICLR 2020) on Adam's moments, LARS (You, Gitman, Ginsburg 2017) on
+ * SGD with Nesterov momentum.  Each call enqueues three launches on `stream`, with no atomics and nothing read on the host.  With
+ * g = grad_scale * clip[1] * grad, lr_k = lr * lr_mult_k and t_k = step - t0_k of the tensor's group k:
+ *   LAMB  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  u = (m / (1 - b1^t_k)) / (sqrt(v / (1 - b2^t_k)) + eps) + wd_k p;
+ *         r = |p| / |u|;  p -= lr_k r u
+ *   LARS  r = coef |p| / (|g| + wd_k |p| + eps);  g' = r (g + wd_k p);  buf = momentum buf + g';  p -= lr_k (g' + momentum buf)
+ * r is 1 unless the tensor is adapted (wd_k != 0, or always_adapt != 0) and both norms are > 0; trust_clip != 0: r = min(r, 1).
+ * Launch 1, one workgroup per item: part_w[item] = sum p^2, part_u[item] = sum u^2 (LARS: sum g^2); LAMB also writes m, v and the
+ * update u (n floats of scratch: the apply reads the stored u, so the norm belongs to the u that is applied).  Launch 2, one
+ * workgroup: the partials of tensor k's items tensor_items[k] .. tensor_items[k + 1] - 1 (uint32[n_tensors + 1], the first item of
+ * every tensor, then n_items) added one by one in item order give trust[k] = float[4] {r, |p|, |u| (LARS: |g|), adapted}, for the
+ * tensors of frozen groups too (r = 1).  Launch 3: the update, with ema as in the *_step_items.  Every summation tree is a function of
+ * the item table alone.  An item of a frozen group gets partials of 0 and no other byte written; on a step that skip_nonfinite drops,
+ * nothing at all is written.  Padding floats stay 0.
+ * CX_EINVAL / CX_EALIGN before any launch as for cx_*_step_items, and CX_EINVAL for decoupled != 0, n_tensors < 1, a null
+ * tensor_items / trust / partial buffer / u, eps <= 0 (LAMB), coef <= 0 or eps < 0 (LARS).                                          */
+int cx_lamb_step_items(float* p, const float* g, float* m, float* v, size_t n, const uint32_t* items, int n_items, const float* groups,
+                       int n_groups, int decoupled, const float* hyper, float lr, int step, float beta1, float beta2, float eps,
+                       float grad_scale, const float* clip, float* ema, float ema_decay, int ema_warmup, int skip_nonfinite,
+                       const uint32_t* tensor_items, int n_tensors, float* part_w, float* part_u, float* trust, float* u,
+                       int trust_clip, int always_adapt, void* stream);
+int cx_lars_step_items(float* p, const float* g, float* buf, size_t n, const uint32_t* items, int n_items, const float* groups,
+                       int n_groups, int decoupled, const float* hyper, float lr, int step, float momentum, float grad_scale,
+                       const float* clip, float* ema, float ema_decay, int ema_warmup, int skip_nonfinite,
+                       const uint32_t* tensor_items, int n_tensors, float* part_w, float* part_u, float* trust, float coef, float eps,
+                       int trust_clip, int always_adapt, void* stream);
+
 /* ---- attention-augmented convolution (AAConv2d, models/attn_aug_conv.py:19-100) --------------------
  * qkv: bf16 (B, H*W, ldq) output of in_proj_qkv (channels [q dk | k dk | v dv], head-major), ldq % 4 == 0 and
  * ldq >= 2 dk + dv (the kernels read q and k in chunks of four elements: 8 bytes of bf16, 16 bytes of fp32); CX_ESHAPE otherwise,
