@@ -171,6 +171,10 @@ SIGNATURES = {
                            _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "cx_lars_step_items": [_vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _f, _i, _f, _f, _vp, _vp, _f, _i, _i,
                            _vp, _i, _vp, _vp, _vp, _f, _f, _i, _i, _vp],
+    # (p, g | p, g, backup | p, backup; then n, items, items_host, n_items, groups, n_groups)
+    "cx_sam_norm_items": [_vp, _vp, _sz, _vp, _vp, _i, _vp, _i, _vp, _f, _i, _vp, _vp, _vp],
+    "cx_sam_perturb_items": [_vp, _vp, _vp, _sz, _vp, _vp, _i, _vp, _i, _vp, _f, _i, _vp],
+    "cx_sam_restore_items": [_vp, _vp, _sz, _vp, _vp, _i, _vp, _i, _vp, _vp],
     "cx_aa_attention_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "cx_aa_attention_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "cx_aa_attention_weights": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],

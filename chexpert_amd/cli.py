@@ -130,6 +130,13 @@
                         (default 0.001; lars only); --trust_clip: ratios capped at 1; --always_adapt: tensors without weight decay are
                         adapted too.  The json log line gains trust_min / trust_max over the adapted tensors.  --restore of a
                         checkpoint written under another optimiser is refused
+  --sam_rho R           R > 0: sharpness-aware minimisation (optim.FusedSAM) around the fused optimiser the other flags choose (needs
+                        --fused_optimizer): each step takes the gradient twice, the second time at the weights moved by R along the
+                        normalised first gradient, which costs a second forward/backward pass; --sam_adaptive: the scale-invariant
+                        form (ASAM: the step is scaled by the weights, elementwise).  Works with and without --graph, every
+                        --optimizer, --loss (but aucm), --pool and --head and the clip / skip / EMA / group flags; not on more than
+                        one rank.  The json log line gains sam_norm; the optimiser checkpoint carries a `sam` entry beside the
+                        base optimiser's state, so --restore of a SAM run into a run without it, and the reverse, both work
   --bootstrap B         B > 0: every eval_results_<tag>.json gets an auc_ci_<tag>.json beside it (rank 0): AUROC per class and for the mean
                         with its (1 - A) percentile bootstrap interval over B replicates, computed on the GPU (metrics.bootstrap_auc);
                         --bootstrap_seed S (default: --seed), --bootstrap_unit image|study|patient (what is resampled; study and
@@ -275,6 +282,9 @@ def build_parser():
     p.add_argument("--trust_coef", type=float, default=None, metavar="C", help="with --optimizer lars: the trust coefficient > 0 (default 0.001)")
     p.add_argument("--trust_clip", action="store_true", help="with --optimizer: trust ratios capped at 1")
     p.add_argument("--always_adapt", action="store_true", help="with --optimizer: adapt the tensors without weight decay too")
+    p.add_argument("--sam_rho", type=float, default=None, metavar="R",
+                   help="sharpness-aware minimisation around the fused optimiser with neighbourhood radius R > 0 (needs --fused_optimizer)")
+    p.add_argument("--sam_adaptive", action="store_true", help="with --sam_rho: the scale-invariant form (ASAM)")
     p.add_argument("--bootstrap", type=int, default=0, metavar="B", help="bootstrap replicates of the AUROC intervals written beside every eval_results file (0: none)")
     p.add_argument("--bootstrap_seed", type=int, default=None, metavar="S", help="seed of the bootstrap draws (default: --seed)")
     p.add_argument("--bootstrap_unit", default="image", choices=list(BOOTSTRAP_UNITS), help="what the bootstrap resamples")
@@ -1088,6 +1098,27 @@ def trust_options(args):
     return out
 
 
+def sam_options(args, world=1):
+    """--sam_rho / --sam_adaptive, validated before anything runs: {} without --sam_rho, else {"rho", "adaptive"}."""
+    import math
+    rho, adaptive = getattr(args, "sam_rho", None), getattr(args, "sam_adaptive", False)
+    if rho is None:
+        if adaptive:
+            raise ValueError("--sam_adaptive chooses the form of sharpness-aware minimisation: pass --sam_rho R with it")
+        return {}
+    if not args.fused_optimizer:
+        raise ValueError("--sam_rho works around the fused optimiser step: pass --fused_optimizer with it")
+    if not (math.isfinite(rho) and rho > 0):
+        raise ValueError("--sam_rho takes a finite radius > 0 (got %r)" % rho)
+    if getattr(args, "loss", "bce") == "aucm":
+        raise ValueError("--sam_rho cannot be combined with --loss aucm: the auxiliary update of the AUC-margin loss runs inside the "
+                         "fused step and would run twice")
+    if world > 1:
+        raise ValueError("--sam_rho is not supported on more than one rank (world size %d): the first pass would have to skip the "
+                         "all-reduce" % world)
+    return {"rho": float(rho), "adaptive": bool(adaptive)}
+
+
 def trust_optimizer(args, model, tr):
     """(optimiser, scheduler) of --optimizer lamb|lars over `model`: FusedLAMB has no schedule, FusedLARS its parent's MultiStepLR."""
     from . import optim as O
@@ -1128,11 +1159,16 @@ def model_weights(ck, args, path=""):
 
 
 def make_model(args, device, pool=None, head=None):
-    """`model_and_own_optimizer`, or with --optimizer lamb|lars the same model under that optimiser (every --model alike)."""
+    """`model_and_own_optimizer`, or with --optimizer lamb|lars the same model under that optimiser (every --model alike); with
+    --sam_rho the optimiser is wrapped in optim.FusedSAM."""
     tr = trust_options(args)                                 # validated before a model is built
+    sam = sam_options(args)
     model, opt, sched = model_and_own_optimizer(args, device, pool, head)
     if tr:
         opt, sched = trust_optimizer(args, model, tr)
+    if sam:                                                  # around whichever fused optimiser the flags chose; same scheduler
+        from . import optim as O
+        opt = O.FusedSAM(opt, **sam)
     return model, opt, sched
 
 
@@ -1332,6 +1368,7 @@ def main(argv=None):
     sal = resolve_saliency(args)
     rank, world, local = P.dist_info()
     aucm = aucm_options(args, world)
+    sam_on = sam_options(args, world)
     focus = focus_options(args)
     multiclass = multiclass_options(args)
     hier = hier_options(args)
@@ -1558,6 +1595,8 @@ def main(argv=None):
                                                                                           warmup_steps=int(args.lr_warmup_steps))
                     if x.shape[0] == args.batch_size:
                         loss, _ = gstep.replay(x, t)
+                    elif sam_on:                            # (two passes around the ascent step: optim.FusedSAM.train_step)
+                        loss, _ = optimizer.train_step(model, x, t, dev=True)
                     else:                                   # same device-resident optimiser / scheduler state, launched one by one
                         optimizer.zero_grad()
                         loss, _ = model.forward_backward(x, t)
@@ -1565,9 +1604,12 @@ def main(argv=None):
                         optimizer.tick()
                         model._eng().packed_version = None
                 elif fused:
-                    optimizer.zero_grad()
-                    loss, _ = model.forward_backward(x, t)  # chexpert.py:159-163 as one fused schedule
-                    optimizer.step()
+                    if sam_on:
+                        loss, _ = optimizer.train_step(model, x, t)
+                    else:
+                        optimizer.zero_grad()
+                        loss, _ = model.forward_backward(x, t)  # chexpert.py:159-163 as one fused schedule
+                        optimizer.step()
                     if scheduler == "fused" and args.step >= args.lr_warmup_steps:
                         optimizer.scheduler_step()
                 else:
@@ -1593,6 +1635,8 @@ def main(argv=None):
                         line["grad_norm"] = round(optimizer.grad_norm(), 5)
                         if optimizer.skipped_steps():
                             line["skipped"] = optimizer.skipped_steps()
+                    if sam_on:
+                        line["sam_norm"] = round(optimizer.perturbation_norm(), 6)
                     if trust_on:
                         ratios = optimizer.adapted_ratios()
                         if ratios:

@@ -16,6 +16,8 @@
 //                         streams it with 16-byte loads and stores; an item of a frozen group is skipped: no byte written
 //   cx_lamb_step_items    the grouped steps with a per-tensor trust ratio |p| / |update| (LAMB on Adam, LARS on SGD-Nesterov): per-item
 //   cx_lars_step_items    partial sums, ONE workgroup that adds them per tensor in item order, then the update (three launches)
+//   cx_sam_*_items        sharpness-aware minimisation around any of the steps: the norm of the (ASAM: weight-scaled) gradient in two
+//                         launches, the ascent step with a backup of the weights, the copy back
 //
 // The grouped kernels walk a table of work items instead of the flat index range.  The flat buffers hold every parameter tensor at
 // an offset that is a multiple of 4 floats, zero-padded to a multiple of 4:
@@ -681,6 +683,125 @@ int check_trust(const TrustArgs& a, size_t n, bool lars) {
   return 0;
 }
 
+// ---- sharpness-aware minimisation: SAM and ASAM around any of the steps above ---------------------------------------------------
+// The ascent step p <- p + rho * s^2 g / |s g| of Foret et al. (s = 1) and Kwon et al. (s = |p|, elementwise), g = grad_scale * grad,
+// over the item table and the group rows of the grouped steps.  Nothing is read on the host and rho lives in device memory, so a
+// captured step replays all of it under a rho schedule:
+//
+//   cx_sam_norm_items     launch 1: one partial per item of sum (g s)^2, summed and folded as item_sq_partial_kernel sums an item; an
+//                         item of a frozen group is not read and gets the partial 0.  Launch 2, ONE workgroup: thread t adds the
+//                         partials [t * per, (t + 1) * per) in item order (per = ceil(n_items / 256)), the 256 sums are folded as
+//                         everywhere here, and thread 0 writes sam[4] = {norm, scale = rho / (norm + eps), nonfinite, 0}.  The tree is
+//                         a function of the item table alone: a frozen item adds +0 (exact), the group is otherwise only a label
+//   cx_sam_perturb_items  backup = p, p = p + scale * s^2 * g over the slots of the unfrozen items; nothing when sam[2] != 0
+//   cx_sam_restore_items  p = backup over the same slots (a copy: the weights come back with their own bits); nothing when sam[2] != 0
+//
+// The tables live in device memory, so the host cannot see them: every kernel skips an item whose units end past n / 4 or whose
+// group is >= n_groups (no byte read or written), and a caller that passes a host copy of the table has it checked before any launch.
+__device__ __forceinline__ bool sam_item_ok(const Item& item, size_t n4, int n_groups) {
+  return (size_t)item.start4 + item.len4 <= n4 && item.group < (uint32_t)n_groups;
+}
+
+template <bool ADAPTIVE>
+__global__ __launch_bounds__(THREADS) void sam_sq_partial_kernel(const float* __restrict__ p, const float* __restrict__ g, size_t n4,
+                                                                  const Item* __restrict__ items, int n_items,
+                                                                  const float* __restrict__ groups, int n_groups, float gscale,
+                                                                  float* __restrict__ part) {
+  const f32x4* __restrict__ p4 = reinterpret_cast<const f32x4*>(p);
+  const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g);
+  for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
+    const Item item = items[it];
+    if (!sam_item_ok(item, n4, n_groups) || groups[4 * (size_t)item.group + 2] != 0.f) {      // uniform over the workgroup
+      if (threadIdx.x == 0) part[it] = 0.f;
+      continue;
+    }
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    const size_t lo = item.start4, hi = (size_t)item.start4 + item.len4;
+#pragma unroll 4
+    for (size_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+      f32x4 gv = g4[i];
+      if constexpr (ADAPTIVE) {
+        const f32x4 pv = p4[i];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gv[c] = gv[c] * gscale * fabsf(pv[c]);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gv[c] *= gscale;
+      }
+      sq_acc(gv, a);
+    }
+    const float s = block_fold((a[0] + a[1]) + (a[2] + a[3]));
+    if (threadIdx.x == 0) part[it] = s;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void sam_norm_final_kernel(const float* __restrict__ part, int n_items,
+                                                                  const float* __restrict__ rho_eps, float* __restrict__ sam) {
+  const int per = (n_items + THREADS - 1) / THREADS;
+  const int lo = threadIdx.x * per;
+  const int hi = lo + per < n_items ? lo + per : n_items;
+  float acc = 0.f;
+  for (int i = lo; i < hi; ++i) acc += part[i];
+  const float sum = block_fold(acc);
+  if (threadIdx.x != 0) return;
+  const float norm = sqrtf(sum);
+  sam[0] = norm;
+  sam[1] = rho_eps[0] / (norm + rho_eps[1]);
+  sam[2] = !(sum < INFINITY) ? 1.f : 0.f;                   // inf or NaN (the sum of squares is never negative)
+  sam[3] = 0.f;
+}
+
+// step_items_kernel's slots over p, g and the backup.  RESTORE: p = backup, g is not read.
+template <bool ADAPTIVE, bool RESTORE>
+__global__ __launch_bounds__(THREADS) void sam_move_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ backup,
+                                                            size_t n4, const Item* __restrict__ items, int n_items,
+                                                            const float* __restrict__ groups, int n_groups,
+                                                            const float* __restrict__ sam, float gscale) {
+  if (sam[2] != 0.f) return;                                 // the whole grid takes the same side: nothing is written
+  const float scale = sam[1];
+  f32x4* __restrict__ p4 = reinterpret_cast<f32x4*>(p);
+  const f32x4* __restrict__ g4 = reinterpret_cast<const f32x4*>(g);
+  f32x4* __restrict__ b4 = reinterpret_cast<f32x4*>(backup);
+  for (long long s = blockIdx.x; s < (long long)n_items * OG_SLOTS; s += gridDim.x) {
+    const Item item = items[s % n_items];
+    const uint32_t first = (uint32_t)(s / n_items) * OG_SLOT_VEC4;
+    if (first >= item.len4 || !sam_item_ok(item, n4, n_groups)) continue;
+    if (groups[4 * (size_t)item.group + 2] != 0.f) continue;          // frozen: uniform over the workgroup
+    const uint32_t last = first + OG_SLOT_VEC4 < item.len4 ? first + OG_SLOT_VEC4 : item.len4;
+    const size_t lo = (size_t)item.start4 + first, hi = (size_t)item.start4 + last;
+#pragma unroll 2
+    for (size_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+      if constexpr (RESTORE) {
+        p4[i] = b4[i];
+      } else {
+        const f32x4 gv = g4[i];
+        f32x4 pv = p4[i];
+        b4[i] = pv;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float e = ADAPTIVE ? (pv[c] * pv[c]) * (gv[c] * gscale) : gv[c] * gscale;
+          pv[c] = pv[c] + scale * e;
+        }
+        p4[i] = pv;
+      }
+    }
+  }
+}
+
+// CX_EINVAL / CX_EALIGN of the three SAM entry points, before any launch.  items_host (may be null): a host copy of the table
+int check_sam(size_t n, const uint32_t* items, const uint32_t* items_host, int n_items, const float* groups, int n_groups) {
+  if (const int e = check_tables(n, items, n_items, groups, n_groups)) return e;
+  if (items_host) {
+    const size_t n4 = n >> 2;
+    for (int it = 0; it < n_items; ++it) {
+      const uint32_t* q = items_host + 4 * (size_t)it;
+      if ((size_t)q[0] + q[1] > n4 || q[2] >= (uint32_t)n_groups) return CX_EINVAL;
+    }
+  }
+  return 0;
+}
+
 // ---- cx_optim_tick applies the reference's schedulers (chexpert.py:165: stepped once per minibatch from lr_warmup_steps on; :480
 // MultiStepLR, :500 ExponentialLR)
 __global__ void optim_tick_kernel(float* hyper) {
@@ -859,6 +980,58 @@ int cx_lars_step_items(float* p, const float* g, float* buf, size_t n, const uin
   hipLaunchKernelGGL((step_items_kernel<SgdRule, true>), dim3(blocks_for((long long)n_items * OG_SLOTS)), dim3(THREADS), 0,
                      as_stream(stream), r, p, g, tab, n_items, groups, 0, hyper, lr, step, grad_scale, x, (const float*)trust,
                      (uint32_t)n_tensors);
+  return launch_status();
+}
+
+// ---- SAM / ASAM.  Everything is validated before the first launch; p of the norm may be null when adaptive == 0 (it is not read).
+int cx_sam_norm_items(const float* p, const float* g, size_t n, const uint32_t* items, const uint32_t* items_host, int n_items,
+                      const float* groups, int n_groups, const float* rho_eps, float grad_scale, int adaptive, float* partials,
+                      float* sam, void* stream) {
+  if (!sam || !rho_eps || (n && (!g || !partials || (adaptive && !p)))) return CX_EINVAL;
+  if (const int e = check_sam(n, items, items_host, n_items, groups, n_groups)) return e;
+  if (n && (!aligned16(g) || (adaptive && !aligned16(p)))) return CX_EALIGN;
+  const Item* tab = reinterpret_cast<const Item*>(items);
+  if (n == 0) n_items = 0;
+  if (n_items) {
+    const dim3 grid(blocks_for(n_items));
+    if (adaptive)
+      hipLaunchKernelGGL(sam_sq_partial_kernel<true>, grid, dim3(THREADS), 0, as_stream(stream), p, g, n >> 2, tab, n_items, groups,
+                         n_groups, grad_scale, partials);
+    else
+      hipLaunchKernelGGL(sam_sq_partial_kernel<false>, grid, dim3(THREADS), 0, as_stream(stream), p, g, n >> 2, tab, n_items, groups,
+                         n_groups, grad_scale, partials);
+  }
+  hipLaunchKernelGGL(sam_norm_final_kernel, dim3(1), dim3(THREADS), 0, as_stream(stream), partials, n_items, rho_eps, sam);
+  return launch_status();
+}
+
+int cx_sam_perturb_items(float* p, const float* g, float* backup, size_t n, const uint32_t* items, const uint32_t* items_host,
+                         int n_items, const float* groups, int n_groups, const float* sam, float grad_scale, int adaptive,
+                         void* stream) {
+  if (!p || !g || !backup || !sam) return CX_EINVAL;
+  if (const int e = check_sam(n, items, items_host, n_items, groups, n_groups)) return e;
+  if (!aligned16(p) || !aligned16(g) || !aligned16(backup)) return CX_EALIGN;
+  if (n == 0) return 0;
+  const Item* tab = reinterpret_cast<const Item*>(items);
+  const dim3 grid(blocks_for((long long)n_items * OG_SLOTS));
+  if (adaptive)
+    hipLaunchKernelGGL((sam_move_kernel<true, false>), grid, dim3(THREADS), 0, as_stream(stream), p, g, backup, n >> 2, tab, n_items,
+                       groups, n_groups, sam, grad_scale);
+  else
+    hipLaunchKernelGGL((sam_move_kernel<false, false>), grid, dim3(THREADS), 0, as_stream(stream), p, g, backup, n >> 2, tab, n_items,
+                       groups, n_groups, sam, grad_scale);
+  return launch_status();
+}
+
+int cx_sam_restore_items(float* p, const float* backup, size_t n, const uint32_t* items, const uint32_t* items_host, int n_items,
+                         const float* groups, int n_groups, const float* sam, void* stream) {
+  if (!p || !backup || !sam) return CX_EINVAL;
+  if (const int e = check_sam(n, items, items_host, n_items, groups, n_groups)) return e;
+  if (!aligned16(p) || !aligned16(backup)) return CX_EALIGN;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL((sam_move_kernel<false, true>), dim3(blocks_for((long long)n_items * OG_SLOTS)), dim3(THREADS), 0,
+                     as_stream(stream), p, (const float*)nullptr, const_cast<float*>(backup), n >> 2,
+                     reinterpret_cast<const Item*>(items), n_items, groups, n_groups, sam, 0.f);
   return launch_status();
 }
 

@@ -28,6 +28,9 @@ class GraphedTrainStep:
         # (Dropout / DropConnect masks: their step counter lives in device memory and is bumped inside the captured step --
         # efficientnet.py, cx_dropout_mask_dev -- so every replay draws new masks)
         model.train()
+        # an optimiser with a train_step of its own (optim.FusedSAM: two forward/backward passes around its ascent step) is captured
+        # through it; the warm-up runs both kinds of pass but no optimiser, so the parameters stay as they are
+        two_pass = hasattr(optimizer, "train_step")
         # construction is free of side effects on the model: the warm-up steps below really run (they update BatchNorm running
         # statistics), so the module buffers and the num_batches_tracked bookkeeping are put back afterwards
         # (so are the auxiliary scalars of set_loss(kind="aucm"), which a train-mode step updates: loss_step_state)
@@ -41,6 +44,9 @@ class GraphedTrainStep:
             for _ in range(max(1, warmup_iters)):
                 model.zero_grad()
                 self.loss, self.logits = model.forward_backward(self.x, self.target)
+            if two_pass:                                            # the second pass's path through the engine, warmed up as well
+                model.zero_grad()
+                model.forward_backward(self.x, self.target, track_stats=False)
             if optimizer is not None:
                 optimizer._bufs(2 if hasattr(optimizer, "betas") or hasattr(optimizer, "alpha") else 1)
                 optimizer.hyper(warmup_steps)
@@ -48,11 +54,14 @@ class GraphedTrainStep:
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            model.zero_grad()
-            self.loss, self.logits = model.forward_backward(self.x, self.target)
-            if optimizer is not None:
-                optimizer.step_dev()
-                optimizer.tick()
+            if two_pass:
+                self.loss, self.logits = optimizer.train_step(model, self.x, self.target, dev=True)
+            else:
+                model.zero_grad()
+                self.loss, self.logits = model.forward_backward(self.x, self.target)
+                if optimizer is not None:
+                    optimizer.step_dev()
+                    optimizer.tick()
         with torch.no_grad():
             for b, v in saved:
                 b.copy_(v)
@@ -98,6 +107,9 @@ class SegmentedTrainStep:
     def __init__(self, model, optimizer, x, target, warmup_steps=0, warmup_iters=2):
         if not x.is_cuda:
             raise RuntimeError("SegmentedTrainStep needs device tensors (no CPU path)")
+        if hasattr(optimizer, "train_step"):
+            raise RuntimeError("SegmentedTrainStep refuses FusedSAM: data-parallel SAM is not supported (the first pass would have to "
+                               "skip the all-reduce)")
         eng = model._eng()
         red = getattr(eng, "reducer", None)
         if red is None:

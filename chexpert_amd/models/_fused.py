@@ -390,7 +390,7 @@ class FusedNet(nn.Module):
         return out
 
     # fused training step (bench / trainer fast path; same arithmetic as chexpert.py:159-163)
-    def forward_backward(self, x, target, input_grad=None):
+    def forward_backward(self, x, target, input_grad=None, track_stats=True):
         """logits = model(x); loss = BCEWithLogits(logits, target).sum(1).mean(0); loss.backward().
         Returns (loss, logits) as device tensors without a host sync.  input_grad: None, or a preallocated fp32 (B,3,H,W) tensor that
         also receives d loss / d x (what x.grad would hold), still without a host sync.  In eval mode this is the frozen-BatchNorm
@@ -400,14 +400,21 @@ class FusedNet(nn.Module):
         eval-mode step computes the gradients and leaves `loss_aux` alone.  After set_loss(kind="focal" | "asl") the loss is the
         focal / asymmetric loss (ops.asl_fwd_bwd), in either mode.  After set_loss(kind="multiclass") the logits are (B, 3n) against
         the (B, n) target and the loss is the three-way softmax cross-entropy per finding (ops.mc3_fwd_bwd), in either mode.  After
-        set_loss(kind="hier") the loss is the hierarchical one over the held parent table (ops.hier_fwd_bwd), in either mode."""
+        set_loss(kind="hier") the loss is the hierarchical one over the held parent table (ops.hier_fwd_bwd), in either mode.
+        track_stats=False: a train-mode step computes with batch statistics as always, but writes no BatchNorm running statistic
+        and counts no batch (the second pass of optim.FusedSAM); the launches are the same, the coefficient kernels get no running
+        buffers."""
         eng = self._eng()
         if input_grad is not None:
             check_input_grad(input_grad, x)
         L = self._loss
         if L.kind == "aucm":
             check_aucm_single_process(eng.reducer)
-        ws = eng.forward(x, self.training, record=True)
+        eng.track_stats = bool(track_stats)
+        try:
+            ws = eng.forward(x, self.training, record=True)
+        finally:
+            eng.track_stats = True
         B, n = ws.logits.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dl = torch.empty(B, n, dtype=torch.float32, device=x.device)
@@ -483,6 +490,9 @@ class FusedEngine:
         self.flat = self.flat_grad = self.device = None
         self.pool = {}
         self.reducer = None          # chexpert_amd.parallel.GradReducer when data-parallel
+        # False for the span of one forward (FusedNet.forward_backward(track_stats=False)): a train-mode forward computes with batch
+        # statistics, writes no running_mean / running_var and counts no batch
+        self.track_stats = True
         self.packed_version = None
 
     # ---- binding
@@ -598,11 +608,11 @@ class FusedEngine:
         ops.bn_bwd_coef_eval(S1, S2, mean, rstd, bn.running_mean[lo:lo + Cn], bn.running_var[lo:lo + Cn], gamma, bn.eps, dgamma,
                              dbeta, pa, pb, pc, Cn, replicas=replicas, rstride=rstride, q=q)
 
-    @staticmethod
-    def _bn_train(bn):
+    def _bn_train(self, bn):
         """(gamma, beta, eps, momentum, running mean, running var) of a training BatchNorm as the coefficient kernels take them:
-        momentum None counts as 0.1, the running buffers are None when the module tracks none."""
-        track = bn.track_running_stats
+        momentum None counts as 0.1, the running buffers are None when the module tracks none -- or when this forward tracks none
+        (`track_stats` off: the second pass of FusedSAM)."""
+        track = bn.track_running_stats and self.track_stats
         return (bn.weight, bn.bias, bn.eps, bn.momentum if bn.momentum is not None else 0.1,
                 bn.running_mean if track else None, bn.running_var if track else None)
 

@@ -502,7 +502,7 @@ class _Engine(FusedEngine):
                 fresh = self._aa_forward(ws, bi, fresh)
             else:
                 fresh = self._transition_forward(ws, bi, fresh)
-        if train:
+        if train and self.track_stats:
             self.model._nbt_pending += 1
         return ws
 
@@ -1025,10 +1025,11 @@ class _PaddedEngine(FusedEngine):
         self._map(self.flat, in_.flat, self.ptab, 0)              # parameters: real -> padded
         self._map(self.stat, self.tstat, self.stab, 0)            # running statistics
         in_.packed_version = None
+        in_.track_stats = self.track_stats
         ws = in_.forward(x, train, record)
         for raa, taa in self.twin.aa_pairs:                       # AAConv2d.weights of the real module (attn_aug_conv.py:87)
             object.__setattr__(raa, "_last", taa._last)
-        if train:
+        if train and self.track_stats:
             self._map(self.stat, self.tstat, self.stab, 1)        # updated running statistics: padded -> real
             self.twin._nbt_pending = 0
             self.model._nbt_pending += 1

@@ -223,7 +223,7 @@ class _Engine(FusedEngine):
         for bi in range(len(self.mb)):
             xin = self._mbconv_forward(ws, bi, xin, train)
         self._head_forward(ws, xin, train)
-        if train:
+        if train and self.track_stats:
             self.model._nbt_pending += 1
         return ws
 

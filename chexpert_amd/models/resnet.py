@@ -275,7 +275,8 @@ class _Engine(FusedEngine):
         S, v = self.bn[id(bn)], self._v
         mom = bn.momentum if bn.momentum is not None else 0.1
         c = lambda t_: t_[lo:lo + n]
-        ops.bn_coef(ws.slab[0], ws.slab[1], count, c(bn.weight), c(bn.bias), bn.eps, mom, c(bn.running_mean), c(bn.running_var),
+        rm, rv = (c(bn.running_mean), c(bn.running_var)) if self.track_stats else (None, None)
+        ops.bn_coef(ws.slab[0], ws.slab[1], count, c(bn.weight), c(bn.bias), bn.eps, mom, rm, rv,
                     c(v(ws, S.sc)), c(v(ws, S.sh)), c(v(ws, S.mean)), c(v(ws, S.rstd)), n, replicas=rows, rstride=n)
 
     # ---- forward
@@ -324,7 +325,7 @@ class _Engine(FusedEngine):
             else:
                 xin, xin_lo, pending = self._bottleneck_forward(ws, bi, xin, xin_lo, pending)
         self._head_forward(ws, xin)
-        if train:
+        if train and self.track_stats:
             m._nbt_pending += 1
         return ws
 

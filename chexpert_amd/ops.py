@@ -1224,6 +1224,47 @@ def lars_step_items(p, g, buf, items, groups, decoupled, momentum, tensor_items,
                                    int(bool(always_adapt)), stream_ptr()), "cx_lars_step_items")
 
 
+# ---- sharpness-aware minimisation over the same tables (csrc/optim.hip: cx_sam_*_items)
+def _items_host(items, items_host):
+    """Pointer of the host copy of the item table (None: none), which the library checks against the buffer before it launches."""
+    if items_host is None:
+        return None
+    if items_host.is_cuda or items_host.dtype != torch.int32 or not items_host.is_contiguous() or items_host.shape != items.shape:
+        raise ValueError("items_host: a contiguous int32 CPU tensor shaped like items")
+    return ptr(items_host)
+
+
+def sam_norm_items(p, g, items, groups, rho_eps, partials, sam, grad_scale=1.0, adaptive=False, items_host=None):
+    """sam = {norm, rho / (norm + eps), nonfinite, 0} with norm = |grad_scale * g * s| over the unfrozen groups, s = 1 or, adaptive,
+    |p| elementwise; rho_eps: device float[2] {rho, eps}.  Two launches, no atomics, the same bits on every call.  partials:
+    n_items floats."""
+    n, pi, ni, pg, ng = _group_tables(g, items, groups, p)
+    require_cuda(rho_eps, partials, sam)
+    _f32(rho_eps, n=2)
+    _f32(partials, n=ni)
+    _f32(sam, n=4)
+    check(lib().cx_sam_norm_items(ptr(p), ptr(g), n, pi, _items_host(items, items_host), ni, pg, ng, ptr(rho_eps), grad_scale,
+                                  int(bool(adaptive)), ptr(partials), ptr(sam), stream_ptr()), "cx_sam_norm_items")
+
+
+def sam_perturb_items(p, g, backup, items, groups, sam, grad_scale=1.0, adaptive=False, items_host=None):
+    """backup = p, then p += sam[1] * s^2 * grad_scale * g on the items of the unfrozen groups; nothing when sam[2] != 0."""
+    n, pi, ni, pg, ng = _group_tables(p, items, groups, g, backup)
+    require_cuda(sam)
+    _f32(sam, n=4)
+    check(lib().cx_sam_perturb_items(ptr(p), ptr(g), ptr(backup), n, pi, _items_host(items, items_host), ni, pg, ng, ptr(sam),
+                                     grad_scale, int(bool(adaptive)), stream_ptr()), "cx_sam_perturb_items")
+
+
+def sam_restore_items(p, backup, items, groups, sam, items_host=None):
+    """p = backup on the items of the unfrozen groups (a copy); nothing when sam[2] != 0."""
+    n, pi, ni, pg, ng = _group_tables(p, items, groups, backup)
+    require_cuda(sam)
+    _f32(sam, n=4)
+    check(lib().cx_sam_restore_items(ptr(p), ptr(backup), n, pi, _items_host(items, items_host), ni, pg, ng, ptr(sam), stream_ptr()),
+          "cx_sam_restore_items")
+
+
 def bf16_to_f32_nchw(x, out=None):
     B, H, W, Cc, ldx = _nhwc(x)
     if out is None:

@@ -7,6 +7,9 @@ RMSprop(momentum=0.9, eps=1e-3)), with the schedulers of :480 (MultiStepLR[40000
 
 Beside them, for large global batches, the layer-wise trust-ratio rules the reference does not have: `FusedLAMB` (on Adam's moments)
 and `FusedLARS` (on SGD with Nesterov momentum), stated in float64 as `reference_trust_step`.
+
+Around any of them, `FusedSAM`: sharpness-aware minimisation (SAM / ASAM), two forward/backward passes per step, its ascent step
+stated in float64 as `reference_sam_step`.
 """
 import contextlib
 import math
@@ -137,6 +140,29 @@ def reference_trust_step(kind, tensors, grads, states, lr, t, group_rows, group_
             out.append(p - lr_g * (g2 + momentum * states[k][0]))
         ratios.append((r, wn, un, adapted))
     return out, ratios
+
+
+def reference_sam_step(tensors, grads, group_rows, group_of, rho, adaptive=False, eps=1e-12, grad_scale=1.0):
+    """float64 statement of the ascent step of sharpness-aware minimisation (what cx_sam_norm_items + cx_sam_perturb_items compute)
+    over a LIST of tensors: tensor k is in group group_of[k] with the row group_rows[j] = {lr_mult, weight_decay, frozen, t0} (a
+    sequence of four, or a dict with those keys), of which only `frozen` is read.  With g = grad_scale * grad and s = 1 (SAM, Foret et
+    al.) or s = |p| elementwise (ASAM, Kwon et al.):
+
+      norm = sqrt(sum over the unfrozen tensors of (s g)^2);  p <- p + rho / (norm + eps) * s^2 g
+
+    Returns (perturbed tensors, norm).  A tensor of a frozen group is returned as it came and is absent from the norm."""
+    def frozen(k):
+        row = group_rows[group_of[k]]
+        return bool(row.get("frozen", False)) if isinstance(row, dict) else bool(row[2])
+    live = [k for k in range(len(tensors)) if not frozen(k)]
+    sg = {}
+    for k in live:
+        p, g = tensors[k].double(), float(grad_scale) * grads[k].double()
+        sg[k] = (p, g, p.abs() if adaptive else torch.ones_like(p))
+    norm = math.sqrt(sum(float((s * g).pow(2).sum()) for _, g, s in sg.values()))
+    scale = float(rho) / (norm + float(eps))
+    out = [sg[k][0] + scale * sg[k][2].pow(2) * sg[k][1] if k in sg else tensors[k] for k in range(len(tensors))]
+    return out, norm
 
 
 def finetune_groups(model, weight_decay=0.0, no_decay_norm_bias=False, head_lr_mult=1.0, backbone_lr_mult=1.0, freeze_backbone=False):
@@ -664,3 +690,165 @@ class FusedRMSprop(_Flat):
     def scheduler_step(self):
         self.sched_steps += 1
         self.lr = self.base_lr * self.decay ** self.sched_steps
+
+
+class FusedSAM:
+    """Sharpness-aware minimisation (Foret et al., ICLR 2021) and, with `adaptive`, its scale-invariant form ASAM (Kwon et al., ICML
+    2021) around any fused optimiser `base` (Adam, SGDNesterov, RMSprop, LAMB, LARS; grouped or not).  One step is two
+    forward/backward passes: the first gradient g gives the ascent step p + rho * s^2 g / |s g| (s = 1, or |p| elementwise;
+    reference_sam_step), the gradient at the perturbed weights is what the base optimiser then applies to the restored weights.
+    Three kernels on the flat buffers (csrc/optim.hip: cx_sam_norm_items, cx_sam_perturb_items, cx_sam_restore_items); rho lives in
+    device memory (`set_rho`), so a captured step follows a schedule.  A grouped base shares its item table and group rows: frozen
+    groups are neither perturbed nor counted in the norm, and `set_group` is honoured; an ungrouped base gets a table with every
+    tensor in group 0.
+
+    Decided semantics:
+      - the base's clipping, non-finite skip and EMA act on the second pass's gradient;
+      - a non-finite first gradient leaves the weights unperturbed (no byte written); the second pass then recomputes the same
+        gradient and the base treats it as it always does;
+      - the EMA never sees perturbed weights (the base's kernel writes it after the weights are restored);
+      - the second pass computes with batch statistics but moves no BatchNorm running statistic and counts no batch;
+      - Dropout and DropConnect draw fresh masks in the second pass (their device counter advances per forward), as in the usual
+        SAM implementations;
+      - the scheduler and Adam's step count advance once per SAM step;
+      - refused: set_loss(kind="aucm") (its auxiliary update runs inside forward_backward and would run twice), an engine with a
+        data-parallel reducer (the first pass would have to skip the all-reduce), a model in eval mode, SegmentedTrainStep.
+
+    Every attribute and method this class does not define (grad_norm, skipped_steps, ema_weights, set_group, hyper, tick,
+    sync_from_device, scheduler_step, trust_ratios, lr, ...) is the base's, for reading and for writing."""
+    _OWN = ("base", "rho", "adaptive", "eps", "_sam", "_rho_dev", "_backup", "_spart", "_sitems", "_sgtab", "_sitems_host", "_snumel")
+
+    def __init__(self, base, rho=0.05, adaptive=False, eps=1e-12):
+        if not isinstance(base, _Flat):
+            raise TypeError("FusedSAM wraps a fused optimiser (FusedAdam, FusedSGDNesterov, FusedRMSprop, FusedLAMB, FusedLARS), got %s"
+                            % type(base).__name__)
+        if not (math.isfinite(float(rho)) and float(rho) >= 0.0):
+            raise ValueError("rho must be finite and >= 0 (got %r)" % (rho,))
+        if not (math.isfinite(float(eps)) and float(eps) > 0.0):
+            raise ValueError("eps must be finite and > 0 (got %r): it keeps the perturbation of a zero gradient at 0" % (eps,))
+        self.base = base
+        self.rho, self.adaptive, self.eps = float(rho), bool(adaptive), float(eps)
+        self._sam = self._rho_dev = self._backup = self._spart = self._sitems = self._sgtab = self._sitems_host = None
+        self._snumel = -1
+
+    def __getattr__(self, name):                            # (only for names this object does not hold)
+        if name == "base":
+            raise AttributeError(name)
+        return getattr(self.base, name)
+
+    def __setattr__(self, name, value):
+        if name in self._OWN:
+            object.__setattr__(self, name, value)
+        else:
+            setattr(self.base, name, value)
+
+    # ---- buffers: beside the base's states, so that nothing is allocated while a graph is being captured
+    def _bufs(self, n=None):
+        base = self.base
+        out = base._bufs(base.NSTATE)
+        eng = base.model._eng()
+        dev, numel = eng.flat.device, eng.flat.numel()
+        if self._sam is None or self._sam.device != dev or self._snumel != numel:
+            if base._grouped:
+                self._sitems_host = base._items.cpu().contiguous()
+            else:
+                items = item_table([q.numel() for q in eng.params], [0] * len(eng.params))
+                if (items and 4 * (items[-1][0] + items[-1][1]) != numel) or (not items and numel):
+                    raise RuntimeError("the item table does not match the layout of the flat parameter buffer")
+                self._sitems_host = torch.tensor(items, dtype=torch.int32).reshape(-1, 4)
+                self._sitems = self._sitems_host.to(dev)
+                self._sgtab = torch.tensor([[1.0, 0.0, 0.0, 0.0]], dtype=torch.float32).to(dev)
+            self._backup = torch.zeros_like(eng.flat)
+            self._spart = torch.zeros(max(1, self._sitems_host.shape[0]), dtype=torch.float32, device=dev)
+            self._sam = torch.zeros(4, dtype=torch.float32, device=dev)
+            self._rho_dev = torch.tensor([self.rho, self.eps], dtype=torch.float32).to(dev)
+            self._snumel = numel
+        return out
+
+    def _tables(self):
+        base = self.base
+        return (base._items, base._gtab) if base._grouped else (self._sitems, self._sgtab)
+
+    def _refuse(self):
+        model = self.base.model
+        if getattr(model, "loss_kind", None) == "aucm":
+            raise RuntimeError("FusedSAM refuses set_loss(kind='aucm'): its auxiliary update runs inside forward_backward and would run "
+                               "twice per step")
+        if getattr(model._eng(), "reducer", None) is not None:
+            raise RuntimeError("FusedSAM is not supported data-parallel: the first pass would have to skip the all-reduce "
+                               "(DESIGN.md: leftovers of the SAM section)")
+
+    # ---- the two halves of a step
+    def first_step(self, dev=False, grad_scale=1.0):
+        """The norm of the gradient in the flat gradient buffer and the ascent step: backup = p, p += rho * s^2 g / |s g| on the
+        unfrozen groups.  Marks the engine's packed weights stale, as GraphedTrainStep.replay does.  (`dev` changes nothing here:
+        rho is always the device's.)"""
+        self._refuse()
+        p, g, _ = self._bufs()
+        items, gtab = self._tables()
+        ops.sam_norm_items(p, g, items, gtab, self._rho_dev, self._spart, self._sam, grad_scale, self.adaptive, self._sitems_host)
+        ops.sam_perturb_items(p, g, self._backup, items, gtab, self._sam, grad_scale, self.adaptive, self._sitems_host)
+        self.base.model._eng().packed_version = None
+
+    def second_step(self, dev=False, grad_scale=1.0):
+        """p = backup (a copy: the weights come back with their own bits), packed weights stale, then the base's step() or, `dev`,
+        step_dev() on the gradient now in the flat gradient buffer."""
+        p, _, _ = self._bufs()
+        items, gtab = self._tables()
+        ops.sam_restore_items(p, self._backup, items, gtab, self._sam, self._sitems_host)
+        self.base.model._eng().packed_version = None
+        if dev:
+            self.base.step_dev(grad_scale)
+        else:
+            self.base.step(grad_scale)
+
+    def step(self, grad_scale=1.0):
+        raise RuntimeError("FusedSAM needs two gradients per step: call train_step(model, x, target), or first_step() / second_step() "
+                           "around a second forward_backward(..., track_stats=False)")
+
+    step_dev = step
+
+    def train_step(self, model, x, target, dev=False):
+        """One SAM step on the minibatch; returns (loss, logits) of the first pass, at the unperturbed weights.  zero_grad,
+        forward_backward, first_step, zero_grad, a second forward_backward that leaves the BatchNorm running statistics and the
+        count of batches alone, second_step and, `dev`, the base's tick()."""
+        if model is not self.base.model:
+            raise RuntimeError("train_step: the model is not the one the base optimiser was built over")
+        if not model.training:
+            raise RuntimeError("FusedSAM needs the model in training mode (eval-mode SAM with frozen BatchNorm is not supported)")
+        self._refuse()
+        self.zero_grad()
+        loss, logits = model.forward_backward(x, target)
+        self.first_step(dev)
+        self.zero_grad()
+        model.forward_backward(x, target, track_stats=False)
+        self.second_step(dev)
+        if dev:
+            self.base.tick()
+        return loss, logits
+
+    # ---- what the wrapper adds to the base's surface
+    def perturbation_norm(self):
+        """|s g| of the most recent first_step (the norm the ascent step was divided by).  Reads the device: synchronises."""
+        return 0.0 if self._sam is None else float(self._sam.cpu()[0])
+
+    def set_rho(self, rho):
+        """One small host-to-device copy on the current stream, so the next step -- a replay of a captured one included -- sees it."""
+        if not (math.isfinite(float(rho)) and float(rho) >= 0.0):
+            raise ValueError("rho must be finite and >= 0 (got %r)" % (rho,))
+        self.rho = float(rho)
+        if self._rho_dev is not None:
+            self._rho_dev.copy_(torch.tensor([self.rho, self.eps], dtype=torch.float32))
+
+    def state_dict(self):
+        """The base's state (a checkpoint of a SAM run restores into the bare base optimiser, and the reverse) plus the `sam` entry."""
+        sd = self.base.state_dict()
+        sd["sam"] = {"rho": self.rho, "adaptive": self.adaptive, "eps": self.eps}
+        return sd
+
+    def load_state_dict(self, sd):
+        self.base.load_state_dict(sd)
+        s = sd.get("sam")
+        if s is not None:                              # (a checkpoint written without SAM leaves it as constructed)
+            self.adaptive, self.eps = bool(s["adaptive"]), float(s["eps"])
+            self.set_rho(s["rho"])

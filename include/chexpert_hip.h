@@ -645,6 +645,31 @@ int cx_lars_step_items(float* p, const float* g, float* buf, size_t n, const uin
                        const uint32_t* tensor_items, int n_tensors, float* part_w, float* part_u, float* trust, float coef, float eps,
                        int trust_clip, int always_adapt, void* stream);
 
+/* Sharpness-aware minimisation (SAM: Foret et al., ICLR 2021; ASAM: Kwon et al., ICML 2021) over the same item table and group rows
+ * (optim.hip): the ascent step p <- p + rho * s^2 g / |s g| with g = grad_scale * grad and s = 1 (adaptive == 0) or s = |p|
+ * elementwise (adaptive != 0), taken over the groups with frozen == 0.
+ * cx_sam_norm_items: two launches, no atomics.  Launch 1 plain-stores one partial sum of (g s)^2 per item to `partials` (n_items
+ * floats; 0 for an item of a frozen group, which is not read).  Launch 2, one workgroup, adds the partials in item order in a tree
+ * that is a function of n_items alone and writes sam = float[4] {norm, scale = rho / (norm + eps), nonfinite, 0}; rho_eps =
+ * float[2] {rho, eps} in DEVICE memory, so a captured hipGraph follows a rho schedule.  norm == 0 gives scale = rho / eps (eps > 0
+ * is the caller's to guarantee) and with it a perturbation of 0; an inf or NaN sum sets nonfinite = 1.  p may be null when
+ * adaptive == 0.
+ * cx_sam_perturb_items: per element of every item of an unfrozen group backup = p, then p = p + scale * s^2 * g (scale = sam[1]).
+ * cx_sam_restore_items: p = backup on the same elements (a copy).  Both write nothing at all when sam[2] != 0, and no byte of p or
+ * backup of a frozen group.  Padding floats (p = g = 0) stay 0.
+ * The kernels skip an item with start4 + len4 > n / 4 or group >= n_groups.  items_host (may be null): a host copy of the table,
+ * checked for exactly that before any launch.
+ * CX_EINVAL before any launch: a null pointer (items_host aside), n_groups outside [1, 256], n % 4 != 0, n_items == 0 with n > 0,
+ * an item of items_host past the buffer or with a group >= n_groups.  CX_EALIGN: a buffer or table that is not 16-byte aligned.    */
+int cx_sam_norm_items(const float* p, const float* g, size_t n, const uint32_t* items, const uint32_t* items_host, int n_items,
+                      const float* groups, int n_groups, const float* rho_eps, float grad_scale, int adaptive, float* partials,
+                      float* sam, void* stream);
+int cx_sam_perturb_items(float* p, const float* g, float* backup, size_t n, const uint32_t* items, const uint32_t* items_host,
+                         int n_items, const float* groups, int n_groups, const float* sam, float grad_scale, int adaptive,
+                         void* stream);
+int cx_sam_restore_items(float* p, const float* backup, size_t n, const uint32_t* items, const uint32_t* items_host, int n_items,
+                         const float* groups, int n_groups, const float* sam, void* stream);
+
 /* ---- attention-augmented convolution (AAConv2d, models/attn_aug_conv.py:19-100) --------------------
  * qkv: bf16 (B, H*W, ldq) output of in_proj_qkv (channels [q dk | k dk | v dv], head-major), ldq % 4 == 0 and
  * ldq >= 2 dk + dv (the kernels read q and k in chunks of four elements: 8 bytes of bf16, 16 bytes of fp32); CX_ESHAPE otherwise,
