@@ -167,12 +167,28 @@ replica and a shard of each minibatch stream (per-rank BatchNorm statistics, ave
 validation set is sharded too and its logits are gathered to rank 0, which alone writes checkpoints and results.
 Images travel as decoded grey bytes (1 B per pixel); whitening `(u/255 - 0.5330)/0.0349` and the expansion to three identical
 channels (chexpert.py:70-72) happen on the GPU.  Logging goes to stdout / JSON (tensorboardX is not used).
+
+`main()` is a sequence of phases, each a function of this module; what a later phase reads of an earlier one travels in one
+plain container (`run`, a SimpleNamespace without methods):
+
+  1. check_flags               every refusal a flag earns on its own, before a process group, a directory or a dataset exists
+  2. open_output_dir           --output_dir and config.json (add_to_config: a resolved key of a config this run created)
+  3. load_datasets             synthetic or ChexpertCSV, the decoded cache, the hierarchy closure; resolve_label_statistics
+  4. make_loader               the RingLoader, before the first GPU call; from here to the end of training one try/finally closes it
+  5. build_model               restore_source / restore_pool / restore_head / make_model / restore / hier_for_checkpoint
+  6. wire_loss                 FusedNet.set_loss, the autograd route's criterion, the AUCM module and its optimiser
+  7. train                     the epoch loop: preprocess, then the graphed / eager / autograd step, log_line, evaluate_and_checkpoint;
+                               every fused step is `optimizer.train_step(model, x, t, dev=...)` (optim._Flat, optim.FusedSAM), replayed
+                               from graph.GraphedTrainStep / SegmentedTrainStep or launched one by one
+  8. run_eval / evaluate_ensemble / visualize / plot_all_roc, and the process group's teardown
 """
 import argparse
+import contextlib
 import json
 import os
 import pprint
 import time
+import types
 
 import numpy as np
 import torch
@@ -847,16 +863,30 @@ def pool_for_checkpoint(pool, ck_pool):
     return out
 
 
-def restore_pool(args, pool):
-    """What make_model hands set_pool: --pool without --restore; with --restore the pool_state of the checkpoint file (of the first
-    checkpoint of a folder), checked against the flag (pool_for_checkpoint)."""
+def checkpoint_files(folder):
+    """The checkpoint files of a folder, in the order every reader of it walks them (the members of --evaluate_ensemble)."""
+    return sorted(f for f in os.listdir(folder) if f.startswith("checkpoint") and f.endswith(".pt"))
+
+
+def restore_source(args):
+    """(path, checkpoint) of the file --restore names, or of the first checkpoint of a folder, loaded to the CPU: what the model is
+    shaped after before its weights are read (restore_pool, restore_head).  (None, None) without --restore or without such a file."""
     path = args.restore
     if path and os.path.isdir(path):
-        files = sorted(f for f in os.listdir(path) if f.startswith("checkpoint") and f.endswith(".pt"))
+        files = checkpoint_files(path)
         path = os.path.join(path, files[0]) if files else None
     if not path or not os.path.isfile(path):
+        return None, None
+    return path, torch.load(path, map_location="cpu")
+
+
+def restore_pool(args, pool, source=None):
+    """What make_model hands set_pool: --pool without --restore; with --restore the pool_state of the checkpoint file (of the first
+    checkpoint of a folder), checked against the flag (pool_for_checkpoint).  source: restore_source(args), where the caller has it."""
+    _, ck = source or restore_source(args)
+    if ck is None:
         return {k: v for k, v in (pool or {"kind": "avg"}).items() if v is not None}
-    return pool_for_checkpoint(pool, torch.load(path, map_location="cpu").get("pool_state"))
+    return pool_for_checkpoint(pool, ck.get("pool_state"))
 
 
 def check_checkpoint_pool(ck, model, path):
@@ -904,18 +934,15 @@ def head_for_checkpoint(head, ck_head):
     return {"kind": "csra", "lam": pick("lam", DEFAULT_LAMBDA), "T": pick("T", DEFAULT_T)}
 
 
-def restore_head(args, head, pool_kind="avg"):
+def restore_head(args, head, pool_kind="avg", source=None):
     """What make_model hands set_head: --head without --restore; with --restore the head_state of the checkpoint file (of the first
-    checkpoint of a folder), checked against the flag (head_for_checkpoint) and against the pooling."""
-    path = args.restore
-    if path and os.path.isdir(path):
-        files = sorted(f for f in os.listdir(path) if f.startswith("checkpoint") and f.endswith(".pt"))
-        path = os.path.join(path, files[0]) if files else None
-    ck_head = torch.load(path, map_location="cpu").get("head_state") if path and os.path.isfile(path) else None
+    checkpoint of a folder), checked against the flag (head_for_checkpoint) and against the pooling.  source: restore_source(args), where the caller has it."""
+    _, ck = source or restore_source(args)
+    ck_head = ck.get("head_state") if ck is not None else None
     out = head_for_checkpoint(head, ck_head)
     if out["kind"] != "linear" and pool_kind != "avg":
         raise ValueError("--head %s stands on the average pool: the checkpoint pools with --pool %s" % (out["kind"], pool_kind))
-    if out["kind"] == "pcam" and path and os.path.isfile(path) and (ck_head or {}).get("kind", "linear") == "linear":
+    if out["kind"] == "pcam" and ck is not None and (ck_head or {}).get("kind", "linear") == "linear":
         print("--head pcam on a linear-head checkpoint: the weights load (the keys are equal), but the head computes another function "
               "of them (unlike --head csra at lambda 0): the first losses are not the checkpoint's")
     return out
@@ -1181,50 +1208,44 @@ def model_and_own_optimizer(args, device, pool=None, head=None):
     fused = args.fused_optimizer
     optimizer_options(args)                                  # validated before a model is built
     group_options(args)
-    sched = None
     n_out = head_width(args)                                 # (three logits per finding under --uncertain multiclass)
-    pool, head = pool or {}, head or {}
-
-    def ex():                                                # the constructor's keyword arguments, once `model` exists
-        return fused_optimizer_kwargs(args, model)
+    size = args.resize or 320
+    attn = {"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)}
+    # the bare module and the family of its own optimiser
     if name == "densenet121":
-        model = densenet121(pretrained=args.pretrained)
+        model, own = densenet121(pretrained=args.pretrained), "adam"
         model.classifier = nn.Linear(model.classifier.in_features, n_out)
         nn.init.constant_(model.classifier.bias, 0)
-        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
-        opt = O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)
-        return model, opt, None
-    if name in ("aadensenet121", "densenet121_attn_aug"):      # chexpert.py:474-480 (README row name accepted too)
+    elif name in ("aadensenet121", "densenet121_attn_aug"):    # chexpert.py:474-480 (README row name accepted too)
         from .models import DenseNet
-        size = args.resize or 320
-        model = DenseNet(32, (6, 12, 24, 16), 64, num_classes=n_out,
-                         attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
-        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
-        if fused:
-            return model, O.FusedSGDNesterov(model, lr=args.lr, **ex()), "fused"
+        model, own = DenseNet(32, (6, 12, 24, 16), 64, num_classes=n_out, attn_params=attn), "sgd"
+    elif name == "resnet152":                                 # chexpert.py:481-486
+        from .models import resnet152
+        model, own = resnet152(pretrained=args.pretrained), "adam"
+        model.fc = nn.Linear(model.fc.in_features, n_out)
+    elif "efficientnet" in name:                              # chexpert.py:496-500
+        from .models import construct_model
+        model, own = construct_model(name, n_classes=n_out), "rmsprop"
+    elif name == "aaresnet152":                               # chexpert.py:486-494
+        from .models import Bottleneck, ResNet
+        model, own = ResNet(Bottleneck, [3, 8, 36, 3], num_classes=n_out, attn_params=attn), "adam"
+    else:
+        raise RuntimeError("Model architecture not supported.")
+    model = model.storage_dtype(args.dtype).to(device).set_pool(**(pool or {})).set_head(**(head or {}))
+    if fused:
+        kw = fused_optimizer_kwargs(args, model)             # the constructor's keyword arguments, now that `model` exists
+        if own == "adam":
+            return model, O.FusedAdam(model, lr=args.lr, **kw), None
+        if own == "sgd":
+            return model, O.FusedSGDNesterov(model, lr=args.lr, **kw), "fused"
+        return model, O.FusedRMSprop(model, lr=args.lr, decay=args.lr_decay_factor, **kw), "fused"
+    if own == "adam":
+        return model, torch.optim.Adam(model.parameters(), lr=args.lr), None
+    if own == "sgd":
         opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, nesterov=True)
         return model, opt, torch.optim.lr_scheduler.MultiStepLR(opt, [40000, 60000])
-    if name == "resnet152":                                   # chexpert.py:481-486
-        from .models import resnet152
-        model = resnet152(pretrained=args.pretrained)
-        model.fc = nn.Linear(model.fc.in_features, n_out)
-        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
-        return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
-    if "efficientnet" in name:                                # chexpert.py:496-500
-        from .models import construct_model
-        model = construct_model(name, n_classes=n_out).storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
-        if fused:
-            return model, O.FusedRMSprop(model, lr=args.lr, decay=args.lr_decay_factor, **ex()), "fused"
-        opt = torch.optim.RMSprop(model.parameters(), lr=args.lr, momentum=0.9, eps=0.001)
-        return model, opt, torch.optim.lr_scheduler.ExponentialLR(opt, args.lr_decay_factor)
-    if name == "aaresnet152":                                 # chexpert.py:486-494
-        from .models import Bottleneck, ResNet
-        size = args.resize or 320
-        model = ResNet(Bottleneck, [3, 8, 36, 3], num_classes=n_out,
-                       attn_params={"k": 0.2, "v": 0.1, "nh": 8, "relative": True, "input_dims": (size, size)})
-        model = model.storage_dtype(args.dtype).to(device).set_pool(**pool).set_head(**head)
-        return model, (O.FusedAdam(model, lr=args.lr, **ex()) if fused else torch.optim.Adam(model.parameters(), lr=args.lr)), None
-    raise RuntimeError("Model architecture not supported.")
+    opt = torch.optim.RMSprop(model.parameters(), lr=args.lr, momentum=0.9, eps=0.001)
+    return model, opt, torch.optim.lr_scheduler.ExponentialLR(opt, args.lr_decay_factor)
 
 
 def collapse_of(collapse):
@@ -1353,53 +1374,77 @@ def plot_roc(res, args, name):
     plt.close()
 
 
-def main(argv=None):
+def check_flags(argv=None):
+    """Phase 1: every refusal a flag can earn on its own, in a fixed order, before a process group, a directory or a dataset exists.
+    Returns the run's container: `args`, rank / world / local and what the option families resolved to (None or empty: off)."""
     args = parse_args(argv)
     if not 0.0 <= args.synthetic_uncertain <= 1.0:
         raise ValueError("--synthetic_uncertain takes a fraction in [0, 1] (got %r)" % args.synthetic_uncertain)
     if args.synthetic_uncertain > 0 and not args.synthetic:
         raise ValueError("--synthetic_uncertain marks labels of the synthetic set: pass --synthetic N with it")
-    trust_on = trust_options(args)
-    ex = optimizer_options(args)
-    groups_on = group_options(args)
-    cam_classes = resolve_cam_classes(getattr(args, "cam_classes", None), args.n_classes)
-    if cam_classes is not None and not args.visualize:
+    run = types.SimpleNamespace(args=args)
+    run.trust_on = trust_options(args)
+    run.ex = optimizer_options(args)
+    run.groups_on = group_options(args)
+    run.cam_classes = resolve_cam_classes(getattr(args, "cam_classes", None), args.n_classes)
+    if run.cam_classes is not None and not args.visualize:
         raise ValueError("--cam_classes draws class maps over the 'vis' subset: pass --visualize with it")
-    sal = resolve_saliency(args)
-    rank, world, local = P.dist_info()
-    aucm = aucm_options(args, world)
-    sam_on = sam_options(args, world)
-    focus = focus_options(args)
-    multiclass = multiclass_options(args)
-    hier = hier_options(args)
-    pool = resolve_pool(args)
-    head = resolve_head(args, pool)
+    run.sal = resolve_saliency(args)
+    run.rank, run.world, run.local = P.dist_info()
+    run.aucm = aucm_options(args, run.world)
+    run.sam_on = sam_options(args, run.world)
+    run.focus = focus_options(args)
+    run.multiclass = multiclass_options(args)
+    run.hier = hier_options(args)
+    run.pool = resolve_pool(args)
+    run.head = resolve_head(args, run.pool)
+    return run
+
+
+def start_process_group(args, world, local):
+    """The process group comes first, before anything touches the GPU; one rank per GPU over RCCL ("nccl"), or ranks sharing a
+    device over gloo when the box has fewer GPUs than ranks (tests)."""
     if world > 1:
-        # the process group comes first, before anything touches the GPU; one rank per GPU over RCCL ("nccl"), or ranks sharing
-        # a device over gloo when the box has fewer GPUs than ranks (tests)
         import torch.distributed as dist
         one_per_gpu = torch.cuda.device_count() >= world
         dist.init_process_group("nccl" if one_per_gpu else "gloo")
         args.cuda = local if one_per_gpu else 0
+
+
+def open_output_dir(args, rank):
+    """Phase 2: --output_dir (default results/<time>) and, on rank 0, its config.json.  Returns whether this run wrote the config: one
+    kept from an earlier run (restore into its output_dir) stays whole, as that run wrote it."""
     if not args.output_dir:
         if args.restore:
             raise RuntimeError("Must specify `output_dir` argument")
         args.output_dir = os.path.join("results", time.strftime("%Y-%m-%d_%H-%M-%S", time.gmtime()))
-    if rank == 0:
-        os.makedirs(args.output_dir, exist_ok=True)
-        cfg_path = os.path.join(args.output_dir, "config.json")
-        new_cfg = not os.path.exists(cfg_path)
-        if new_cfg:
-            json.dump(args.__dict__, open(cfg_path, "w"), indent=4)
-    # datasets and the training loader come BEFORE the first GPU call: its worker processes are forked from a process that has
-    # not initialised the GPU runtime and never touch the card (chexpert_amd/loader.py)
+    if rank != 0:
+        return False
+    os.makedirs(args.output_dir, exist_ok=True)
+    cfg_path = os.path.join(args.output_dir, "config.json")
+    new_cfg = not os.path.exists(cfg_path)
+    if new_cfg:
+        json.dump(args.__dict__, open(cfg_path, "w"), indent=4)
+    return new_cfg
+
+
+def add_to_config(args, key, value):
+    """A resolved value goes beside the flags that asked for it, into the config.json this run created."""
+    cfg_path = os.path.join(args.output_dir, "config.json")
+    cfg = json.load(open(cfg_path))
+    cfg[key] = value
+    json.dump(cfg, open(cfg_path, "w"), indent=4)
+
+
+def load_datasets(args, hier):
+    """Phase 3: (training set, validation set): synthetic, or chexpert.py:64-79 over the extracted CheXpert-v1.0-small folder (uint8 to
+    the GPU) with the decoded cache; under --loss hier both label tables are closed over the tree."""
     size = args.resize or 320
-    device = torch.device("cuda:%d" % (args.cuda or 0))
     if args.synthetic:
         n_valid = max(args.batch_size, args.synthetic // 5)
         train_ds = SyntheticXrays(args.mini_data or args.synthetic, size, args.n_classes, 7, args.synthetic_uncertain, args.uncertain)
         valid_ds = SyntheticXrays(n_valid, size, args.n_classes, 11)
-    else:                                  # chexpert.py:64-79 over the extracted CheXpert-v1.0-small folder (uint8 to the GPU)
+    else:
         from .data import ChexpertCSV
         if not args.data_path:
             raise RuntimeError("pass --data_path <folder holding CheXpert-v1.0-small> or --synthetic N (no download here)")
@@ -1414,58 +1459,76 @@ def main(argv=None):
         from .data import hierarchy_closure
         train_ds.targets = hierarchy_closure(train_ds.targets, hier["parent"])
         valid_ds.targets = hierarchy_closure(valid_ds.targets, hier["parent"])
-    pos_weight = resolve_pos_weight(args.pos_weight, train_ds.targets, args.n_classes)
-    if pos_weight is not None and rank == 0 and new_cfg:       # the resolved vector goes beside the flags that asked for it: a config
-        # kept from an earlier run (restore into its output_dir) stays whole, as that run wrote it
-        cfg = json.load(open(cfg_path))
-        cfg["pos_weight_resolved"] = pos_weight
-        json.dump(cfg, open(cfg_path, "w"), indent=4)
-    if aucm is not None:
-        aucm["prior"] = resolve_aucm_prior(args.aucm_prior, train_ds.targets, args.n_classes)
-        if rank == 0 and new_cfg:
-            cfg = json.load(open(cfg_path))
-            cfg["aucm_prior_resolved"] = aucm["prior"]
-            json.dump(cfg, open(cfg_path, "w"), indent=4)
-    train_loader = None
-    if args.train:
-        from .loader import RingLoader
-        train_loader = RingLoader(train_ds, args.batch_size, num_workers=args.num_workers, slots=4, device=device)
+    return train_ds, valid_ds
+
+
+def resolve_label_statistics(run):
+    """--pos_weight and --aucm_prior from the training table (`auto`) or the flag; what they resolved to goes into the config."""
+    args = run.args
+    run.pos_weight = resolve_pos_weight(args.pos_weight, run.train_ds.targets, args.n_classes)
+    if run.pos_weight is not None and run.new_cfg:
+        add_to_config(args, "pos_weight_resolved", run.pos_weight)
+    if run.aucm is not None:
+        run.aucm["prior"] = resolve_aucm_prior(args.aucm_prior, run.train_ds.targets, args.n_classes)
+        if run.new_cfg:
+            add_to_config(args, "aucm_prior_resolved", run.aucm["prior"])
+
+
+def make_loader(args, train_ds, device):
+    """Phase 4: the training loader (None without --train).  It comes BEFORE the first GPU call: its worker processes are forked from
+    a process that has not initialised the GPU runtime and never touch the card (chexpert_amd/loader.py)."""
+    if not args.train:
+        return None
+    from .loader import RingLoader
+    return RingLoader(train_ds, args.batch_size, num_workers=args.num_workers, slots=4, device=device)
+
+
+def start_gpu(args, device):
     if not torch.cuda.is_available():
         raise RuntimeError("chexpert_amd needs an MI355X (no CPU fallback)")
     torch.cuda.set_device(device)
     if args.seed:
         torch.manual_seed(args.seed)
         np.random.seed(args.seed)
-    try:
-        pool = restore_pool(args, pool)        # the checkpoint's pooling; a --pool flag that contradicts it is refused here
-        why = visualize_needs_avg(args, pool["kind"])
-        if why:
-            raise ValueError(why)
-        head = restore_head(args, head, pool["kind"])      # the checkpoint's head; --head linear on a csra checkpoint is refused here
-        why = visualize_needs_linear(args, head["kind"])
-        if why:
-            raise ValueError(why)
-    except ValueError:
-        if train_loader is not None:
-            train_loader.close()
-        raise
-    model, optimizer, scheduler = make_model(args, device, pool, head)
-    restored_loss = None
+
+
+def build_model(run):
+    """Phase 5: pooling and head as the flags and the checkpoint of --restore agree on them, the model under its optimiser, and the
+    checkpoint's weights, step, optimiser state and loss state (`run.restored_loss`)."""
+    args = run.args
+    source = restore_source(args)
+    run.pool = restore_pool(args, run.pool, source)    # the checkpoint's pooling; a --pool flag that contradicts it is refused here
+    why = visualize_needs_avg(args, run.pool["kind"])
+    if why:
+        raise ValueError(why)
+    run.head = restore_head(args, run.head, run.pool["kind"], source)  # the checkpoint's head; --head linear on a csra checkpoint is refused here
+    why = visualize_needs_linear(args, run.head["kind"])
+    if why:
+        raise ValueError(why)
+    del source
+    run.model, run.optimizer, run.scheduler = make_model(args, run.device, run.pool, run.head)
+    run.restored_loss = None
     if args.restore and os.path.isfile(args.restore):
-        try:
-            restored_loss = restore(args, model, optimizer, scheduler, device, multiclass)
-            adopted = hier is None
-            hier = hier_for_checkpoint(hier, restored_loss, args.restore, args.train)
-            if adopted and hier is not None and hier["closure"]:   # an evaluation of a --loss hier checkpoint without the flag: the
-                from .data import hierarchy_closure                # validation table as that run saw it
-                valid_ds.targets = hierarchy_closure(valid_ds.targets, hier["parent"])
-        except ValueError:
-            if train_loader is not None:
-                train_loader.close()
-            raise
-    collapse = hier["parent"] if hier is not None else multiclass       # what evaluate() does to a forward's output
-    loss_fn = nn.BCEWithLogitsLoss(reduction="none")
-    masked_loss = None
+        run.restored_loss = restore(args, run.model, run.optimizer, run.scheduler, run.device, run.multiclass)
+        adopted = run.hier is None
+        run.hier = hier_for_checkpoint(run.hier, run.restored_loss, args.restore, args.train)
+        if adopted and run.hier is not None and run.hier["closure"]:   # an evaluation of a --loss hier checkpoint without the flag: the
+            from .data import hierarchy_closure                        # validation table as that run saw it
+            run.valid_ds.targets = hierarchy_closure(run.valid_ds.targets, run.hier["parent"])
+    run.collapse = run.hier["parent"] if run.hier is not None else run.multiclass       # what evaluate() does to a forward's output
+
+
+def summed_bce(out, t):
+    return nn.BCEWithLogitsLoss(reduction="none")(out, t).sum(1).mean(0)                # chexpert.py:160
+
+
+def wire_loss(run):
+    """Phase 6: the loss of the fused step (FusedNet.set_loss) as the flags and a restored checkpoint's `loss_state` decide it.
+    Returns (criterion, aucm_loss, aucm_opt) of the autograd route: the module that reads the storage the model holds, and under
+    --loss aucm without --fused_optimizer the loss module with the optimiser of its auxiliary scalars (else None, None)."""
+    args, model, pos_weight, restored_loss = run.args, run.model, run.pos_weight, run.restored_loss
+    focus, hier, aucm = run.focus, run.hier, run.aucm
+    criterion = summed_bce
     if focus is not None:
         # the fused step's loss and, by the same kernel, the autograd route's; a restored checkpoint of the same kind brings its four
         # numbers (loss_focus: a schedule may have moved them), one of another kind is refused
@@ -1473,37 +1536,33 @@ def main(argv=None):
         model.set_loss(pos_weight=pos_weight, **focus)
         if restored_loss is not None:
             if restored_loss.get("kind") != focus["kind"]:
-                if train_loader is not None:
-                    train_loader.close()
                 raise ValueError("--restore: the checkpoint was trained with --loss %s, this run asks for --loss %s"
                                  % (restored_loss.get("kind"), focus["kind"]))
             model.load_loss_state(restored_loss)
-        crit = (FocalLoss if focus["kind"] == "focal" else AsymmetricLoss)(pos_weight=model.loss_pos_weight,
-                                                                           **{k: v for k, v in focus.items() if k != "kind"})
-        crit.focus = model.loss_focus                    # one storage: the module reads what the model holds
-        masked_loss = crit
+        criterion = (FocalLoss if focus["kind"] == "focal" else AsymmetricLoss)(pos_weight=model.loss_pos_weight,
+                                                                                **{k: v for k, v in focus.items() if k != "kind"})
+        criterion.focus = model.loss_focus               # one storage: the module reads what the model holds
     elif args.train and restored_loss is not None and restored_loss.get("kind") in ("focal", "asl"):
-        train_loader.close()
         raise ValueError("--restore: the checkpoint was trained with --loss %s: pass it (and its flags) to go on training" % restored_loss["kind"])
     elif hier is not None:
         # the fused step's loss and, by the same kernel, the autograd route's (the table a restored checkpoint brought is this one:
         # hier_for_checkpoint); one storage for the table and the weights: the module reads what the model holds
         from .loss import HierarchicalBCE
         model.set_loss(kind="hier", parent=hier["parent"], mode=hier_mode_of(hier), pos_weight=pos_weight)
-        masked_loss = HierarchicalBCE(hier["parent"], hier_mode_of(hier), pos_weight)
-        masked_loss.parent, masked_loss.pos_weight = model.loss_parent, model.loss_pos_weight
-    elif multiclass:
+        criterion = HierarchicalBCE(hier["parent"], hier_mode_of(hier), pos_weight)
+        criterion.parent, criterion.pos_weight = model.loss_parent, model.loss_pos_weight
+    elif run.multiclass:
         # the fused step's loss and, by the same kernel, the autograd route's; a restored checkpoint brings its class weights
         from .loss import MultiClassUncertain
         model.set_loss(kind="multiclass")
         if restored_loss is not None:
             model.load_loss_state(restored_loss)
-        masked_loss = MultiClassUncertain()
-        masked_loss.class_weight = model.loss_class_weight      # one storage: the module reads what the model holds
+        criterion = MultiClassUncertain()
+        criterion.class_weight = model.loss_class_weight        # one storage: the module reads what the model holds
     elif args.uncertain == "ignore" or pos_weight is not None:
         from .loss import MaskedBCE
         model.set_loss(ignore_negative=args.uncertain == "ignore", pos_weight=pos_weight)      # the fused step's loss
-        masked_loss = MaskedBCE(model.loss_pos_weight, ignore_negative=args.uncertain == "ignore")   # the autograd route's
+        criterion = MaskedBCE(model.loss_pos_weight, ignore_negative=args.uncertain == "ignore")     # the autograd route's
     aucm_loss = aucm_opt = None
     if aucm is not None:
         # the fused step's loss; a restored checkpoint brings its auxiliary scalars, the flags of this run keep the last word on
@@ -1515,288 +1574,360 @@ def main(argv=None):
             # the autograd route: the loss module's a, b, alpha under plain SGD at the auxiliary rate, then alpha >= 0 -- the update
             # of the fused step; they start from, and a checkpoint reads them back through, model.loss_aux
             from .loss import AUCMLoss
-            aucm_loss = AUCMLoss(aucm["prior"], aucm["margin"]).to(device)
+            aucm_loss = AUCMLoss(aucm["prior"], aucm["margin"]).to(run.device)
             with torch.no_grad():
                 for p_, row in zip((aucm_loss.a, aucm_loss.b, aucm_loss.alpha), model.loss_aux):
                     p_.copy_(row)
             aucm_opt = torch.optim.SGD(aucm_loss.parameters(), lr=aucm["lr_aux"])
+    return criterion, aucm_loss, aucm_opt
 
-    def sync_loss_aux():
-        """Autograd route: model.loss_aux (what loss_state() and a checkpoint read) follows the loss module's parameters."""
-        if aucm_loss is not None:
-            with torch.no_grad():
-                model.loss_aux.copy_(torch.stack([aucm_loss.a, aucm_loss.b, aucm_loss.alpha]))
-    if rank == 0:
-        print("Loaded %s (number of parameters: %s; weights trained to step %d)" % (
-            model._get_name(), format(sum(p.numel() for p in model.parameters()), ","), args.step))
 
-    clahe = make_clahe(args)
+def sync_loss_aux(model, aucm_loss):
+    """Autograd route: model.loss_aux (what loss_state() and a checkpoint read) follows the loss module's parameters."""
+    if aucm_loss is not None:
+        with torch.no_grad():
+            model.loss_aux.copy_(torch.stack([aucm_loss.a, aucm_loss.b, aucm_loss.alpha]))
 
-    def averaged():
-        """The weights an evaluation during training sees: the EMA where --ema_decay keeps one (and a step has bound it)."""
-        import contextlib
-        on = ex.get("ema_decay") is not None and args.train and model._eng().flat is not None
-        return optimizer.ema_weights() if on else contextlib.nullcontext()
 
-    boot_groups = bootstrap_groups(args, valid_ds) if getattr(args, "bootstrap", 0) > 0 or getattr(args, "delong", False) else None
+def averaged_weights(run):
+    """The weights an evaluation during training sees: the EMA where --ema_decay keeps one (and a step has bound it)."""
+    on = run.ex.get("ema_decay") is not None and run.args.train and run.model._eng().flat is not None
+    return run.optimizer.ema_weights() if on else contextlib.nullcontext()
 
-    def run_eval(tag):
-        with averaged():
-            o, t, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, collapse)
-        res = M.compute_metrics(o, t, l)
-        if rank == 0:
-            print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
-            json.dump(res, open(os.path.join(args.output_dir, tag + ".json"), "w"), indent=4)
-            write_auc_ci(args, tag, o, t, boot_groups)
-            write_delong(args, tag, o, t, boot_groups)
-            write_metrics_ci(args, tag, o, t, boot_groups)
-            write_calibration(args, tag, o, t, boot_groups)
-        return res
 
-    def jitter(x_u8, step):
-        from . import ops
-        B = x_u8.shape[0]
-        u = synth.uniform(step * 7919 + 13 + rank, (3, B), 0.0, 1.0)
-        return ops.u8_jitter(x_u8, (0.75 + 0.5 * u[0]).to(device), (0.75 + 0.5 * u[1]).to(device),
-                             (u[2] > 0.5).to(torch.int32).to(device))
+def validate(run):
+    """(logits, targets, element losses) of the validation set in dataset order, every rank its shard."""
+    return evaluate_sharded(run.model, run.valid_ds, run.args.batch_size, run.device, run.rank, run.world, run.clahe, run.collapse)
 
+
+def run_eval(run, tag):
+    args = run.args
+    with averaged_weights(run):
+        o, t, l = validate(run)
+    res = M.compute_metrics(o, t, l)
+    if run.rank == 0:
+        print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
+        json.dump(res, open(os.path.join(args.output_dir, tag + ".json"), "w"), indent=4)
+        write_auc_ci(args, tag, o, t, run.boot_groups)
+        write_delong(args, tag, o, t, run.boot_groups)
+        write_metrics_ci(args, tag, o, t, run.boot_groups)
+        write_calibration(args, tag, o, t, run.boot_groups)
+    return res
+
+
+def jitter(x_u8, step, rank, device):
+    from . import ops
+    B = x_u8.shape[0]
+    u = synth.uniform(step * 7919 + 13 + rank, (3, B), 0.0, 1.0)
+    return ops.u8_jitter(x_u8, (0.75 + 0.5 * u[0]).to(device), (0.75 + 0.5 * u[1]).to(device),
+                         (u[2] > 0.5).to(torch.int32).to(device))
+
+
+def preprocess(run, affine, mix, x, t, step):
+    """The chain on the uint8 minibatch of training step `step`, every link optional."""
+    if run.clahe is not None:                   # deterministic preprocessing first, then the random steps
+        x = run.clahe(x)
+    if affine is not None:                      # geometric first, photometric second
+        x = affine(x, step)
+    if run.args.jitter:
+        x = jitter(x, step, run.rank, run.device)
+    if mix is not None:                         # per-sample transforms first, then the collated batch is mixed
+        x, t = mix(x, t, step)
+    return x, t
+
+
+def autograd_step(run, x, t):
+    """The step without --fused_optimizer: torch's optimiser (and scheduler) over the autograd route of the fused network."""
+    args, optimizer, scheduler, aucm_loss, aucm_opt = run.args, run.optimizer, run.scheduler, run.aucm_loss, run.aucm_opt
+    out = run.model(x)
+    if aucm_loss is not None:
+        loss = aucm_loss(out, t)
+        aucm_opt.zero_grad()
+    else:
+        loss = run.criterion(out, t)
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
+    if aucm_loss is not None:
+        aucm_opt.step()
+        aucm_loss.clamp_()
+    if scheduler and args.step >= args.lr_warmup_steps:
+        scheduler.step()
+    return loss
+
+
+def log_line(run, loss):
+    """What a --log_interval step prints, as a dict.  (loss.item() synchronises; the optimiser's figures then read the device.)"""
+    ex, optimizer = run.ex, run.optimizer
+    line = {"step": run.args.step, "train_loss": round(loss.item(), 5)}
+    if ex.get("max_grad_norm") is not None or ex.get("skip_nonfinite"):
+        line["grad_norm"] = round(optimizer.grad_norm(), 5)
+        if optimizer.skipped_steps():
+            line["skipped"] = optimizer.skipped_steps()
+    if run.sam_on:
+        line["sam_norm"] = round(optimizer.perturbation_norm(), 6)
+    if run.trust_on:
+        ratios = optimizer.adapted_ratios()
+        if ratios:
+            line["trust_min"], line["trust_max"] = round(min(ratios), 6), round(max(ratios), 6)
+    return line
+
+
+def checkpoint_dict(run, res, ema_sd):
+    """The model checkpoint after the evaluation `res`, with the entries only some runs have."""
+    model, hier = run.model, run.hier
+    ckpt = {"global_step": run.args.step, "eval_loss": float(np.sum(list(res["loss"].values()))),
+            "avg_auc": M.mean_auc(res), "state_dict": model.state_dict()}
+    if model.pool_kind != "avg":  # (a checkpoint without it is the average's: the keys of before)
+        ckpt["pool_state"] = model.pool_state()
+    if model.head_kind != "linear":
+        ckpt["head_state"] = model.head_state()
+    if ema_sd is not None:        # beside the live weights, which restore continues from
+        ckpt["ema_state_dict"] = ema_sd
+    if run.aucm is not None:      # the auxiliary scalars are trained state: restore continues from them
+        sync_loss_aux(model, run.aucm_loss)
+        ckpt["loss_state"] = model.loss_state()
+    elif run.focus is not None or run.multiclass or hier is not None:      # the loss's numbers: restore checks the kind and puts them back
+        ckpt["loss_state"] = model.loss_state()
+        if hier is not None:          # how the label tables were made: an evaluation without the flags does the same
+            ckpt["loss_state"]["closure"] = hier["closure"]
+    return ckpt
+
+
+def evaluate_and_checkpoint(run, graphed):
+    """An --eval_interval step: the validation metrics under the averaged weights and, on rank 0, the checkpoint files."""
+    model, optimizer, scheduler = run.model, run.optimizer, run.scheduler
+    ema_sd = None
+    with averaged_weights(run):
+        res = M.compute_metrics(*validate(run))
+        if run.ex.get("ema_decay") is not None and run.rank == 0:
+            ema_sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    if run.rank == 0:
+        if graphed:
+            optimizer.sync_from_device()
+        sched_state = scheduler.state_dict() if scheduler is not None and scheduler != "fused" else None
+        save_checkpoint(checkpoint_dict(run, res, ema_sd), optimizer.state_dict(), sched_state, run.args)
+    model.train()
+
+
+def train(run):
+    """Phase 7: the epoch loop.  Every fused step is the optimiser's train_step (optim._Flat.train_step, optim.FusedSAM.train_step):
+    replayed from the graph captured on the first full minibatch, launched one by one on the device-resident state for a partial
+    minibatch of a graphed run, or launched with the host's learning rate and scheduler."""
+    args, model, optimizer, scheduler, rank, world, device = run.args, run.model, run.optimizer, run.scheduler, run.rank, run.world, run.device
     affine = make_affine(args, rank, device)
     mix = make_mix(args, rank, device)
-    if args.train:
-        fused = args.fused_optimizer
-        gstep = None
-        if world > 1:            # replicas start identical (parameters, buffers) and average their gradients inside backward from
-            model._eng().bind(device)                 # the first step on: bind the flat buffers now, before any optimiser state exists
-            P.broadcast_module_state(model)
-            model._eng().enable_data_parallel()
-        for epoch in range(args.n_epochs):
-            model.train()
-            idx = P.shard_indices(len(train_ds), rank, world, seed=args.seed or 1, epoch=epoch)
-            if not idx:
-                raise RuntimeError("the training set (%d images over %d ranks) yields no minibatch" % (len(train_ds), world))
-            t_epoch = time.perf_counter()
-            # every image is seen each epoch, as with the reference's DataLoader (drop_last=False, chexpert.py:76): the last,
-            # partial minibatch runs as an eager step (the hipGraph is captured on the full batch's shapes)
-            for x, t, _ in train_loader.batches(idx, drop_last=False):
-                args.step += 1
-                if clahe is not None:                       # deterministic preprocessing first, then the random steps
-                    x = clahe(x)
-                if affine is not None:                      # geometric first, photometric second
-                    x = affine(x, args.step)
-                if args.jitter:
-                    x = jitter(x, args.step)
-                if mix is not None:                         # per-sample transforms first, then the collated batch is mixed
-                    x, t = mix(x, t, args.step)
-                if args.graph and fused and (gstep is not None or x.shape[0] == args.batch_size):
-                    if gstep is None:                       # captured on the first full minibatch's shapes
-                        # (data-parallel: graph segments cut at the gradient buckets, the all-reduces enqueued between them)
-                        from .graph import GraphedTrainStep, SegmentedTrainStep
-                        gstep = (GraphedTrainStep if world == 1 else SegmentedTrainStep)(model, optimizer, x, t,
-                                                                                          warmup_steps=int(args.lr_warmup_steps))
-                    if x.shape[0] == args.batch_size:
-                        loss, _ = gstep.replay(x, t)
-                    elif sam_on:                            # (two passes around the ascent step: optim.FusedSAM.train_step)
-                        loss, _ = optimizer.train_step(model, x, t, dev=True)
-                    else:                                   # same device-resident optimiser / scheduler state, launched one by one
-                        optimizer.zero_grad()
-                        loss, _ = model.forward_backward(x, t)
-                        optimizer.step_dev()
-                        optimizer.tick()
-                        model._eng().packed_version = None
-                elif fused:
-                    if sam_on:
-                        loss, _ = optimizer.train_step(model, x, t)
-                    else:
-                        optimizer.zero_grad()
-                        loss, _ = model.forward_backward(x, t)  # chexpert.py:159-163 as one fused schedule
-                        optimizer.step()
-                    if scheduler == "fused" and args.step >= args.lr_warmup_steps:
-                        optimizer.scheduler_step()
-                else:
-                    out = model(x)
-                    if aucm_loss is not None:
-                        loss = aucm_loss(out, t)
-                        aucm_opt.zero_grad()
-                    else:
-                        loss = masked_loss(out, t) if masked_loss is not None else loss_fn(out, t).sum(1).mean(0)   # chexpert.py:160
-                    optimizer.zero_grad()
-                    loss.backward()
-                    optimizer.step()
-                    if aucm_loss is not None:
-                        aucm_opt.step()
-                        aucm_loss.clamp_()
-                    if scheduler and args.step >= args.lr_warmup_steps:
-                        scheduler.step()
-                if groups_on.get("freeze_steps", 0) > 0 and args.step == groups_on["freeze_steps"]:
-                    thaw_backbone(optimizer)                # every rank alike: the table is the same on all of them, no collective
-                if args.step % args.log_interval == 0 and rank == 0:
-                    line = {"step": args.step, "train_loss": round(loss.item(), 5)}
-                    if ex.get("max_grad_norm") is not None or ex.get("skip_nonfinite"):      # (loss.item() has synchronised already)
-                        line["grad_norm"] = round(optimizer.grad_norm(), 5)
-                        if optimizer.skipped_steps():
-                            line["skipped"] = optimizer.skipped_steps()
-                    if sam_on:
-                        line["sam_norm"] = round(optimizer.perturbation_norm(), 6)
-                    if trust_on:
-                        ratios = optimizer.adapted_ratios()
-                        if ratios:
-                            line["trust_min"], line["trust_max"] = round(min(ratios), 6), round(max(ratios), 6)
-                    print(json.dumps(line), flush=True)
-                if args.step % args.eval_interval == 0:
-                    ema_sd = None
-                    with averaged():
-                        res = M.compute_metrics(*evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, collapse))
-                        if ex.get("ema_decay") is not None and rank == 0:
-                            ema_sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
-                    if rank == 0:
-                        if gstep is not None:
-                            optimizer.sync_from_device()
-                        sched_state = scheduler.state_dict() if scheduler is not None and scheduler != "fused" else None
-                        ckpt = {"global_step": args.step, "eval_loss": float(np.sum(list(res["loss"].values()))),
-                                "avg_auc": M.mean_auc(res), "state_dict": model.state_dict()}
-                        if model.pool_kind != "avg":  # (a checkpoint without it is the average's: the keys of before)
-                            ckpt["pool_state"] = model.pool_state()
-                        if model.head_kind != "linear":
-                            ckpt["head_state"] = model.head_state()
-                        if ema_sd is not None:        # beside the live weights, which restore continues from
-                            ckpt["ema_state_dict"] = ema_sd
-                        if aucm is not None:          # the auxiliary scalars are trained state: restore continues from them
-                            sync_loss_aux()
-                            ckpt["loss_state"] = model.loss_state()
-                        elif focus is not None or multiclass or hier is not None:      # the loss's numbers: restore checks the kind and puts them back
-                            ckpt["loss_state"] = model.loss_state()
-                            if hier is not None:          # how the label tables were made: an evaluation without the flags does the same
-                                ckpt["loss_state"]["closure"] = hier["closure"]
-                        save_checkpoint(ckpt, optimizer.state_dict(), sched_state, args)
-                    model.train()
-            sync_loss_aux()      # (also current when no checkpoint followed the last step)
-            torch.cuda.synchronize()
-            if rank == 0:        # input pipeline + step, end to end (the figure to hold against bench.py's device-resident rate)
-                print(json.dumps({"epoch": epoch, "images_per_sec": round(len(idx) * world / (time.perf_counter() - t_epoch), 1),
-                                  "loader_workers": args.num_workers,
-                                  "decoded_cache_fill": round(train_ds.cache_fill(), 3) if hasattr(train_ds, "cache_fill") else None}), flush=True)
-            run_eval("eval_results_step_%d" % args.step)
-        train_loader.close()
+    fused = args.fused_optimizer
+    gstep = None
+    if world > 1:            # replicas start identical (parameters, buffers) and average their gradients inside backward from
+        model._eng().bind(device)                 # the first step on: bind the flat buffers now, before any optimiser state exists
+        P.broadcast_module_state(model)
+        model._eng().enable_data_parallel()
+    for epoch in range(args.n_epochs):
+        model.train()
+        idx = P.shard_indices(len(run.train_ds), rank, world, seed=args.seed or 1, epoch=epoch)
+        if not idx:
+            raise RuntimeError("the training set (%d images over %d ranks) yields no minibatch" % (len(run.train_ds), world))
+        t_epoch = time.perf_counter()
+        # every image is seen each epoch, as with the reference's DataLoader (drop_last=False, chexpert.py:76): the last,
+        # partial minibatch runs as an eager step (the hipGraph is captured on the full batch's shapes)
+        for x, t, _ in run.train_loader.batches(idx, drop_last=False):
+            args.step += 1
+            x, t = preprocess(run, affine, mix, x, t, args.step)
+            if args.graph and fused and (gstep is not None or x.shape[0] == args.batch_size):
+                if gstep is None:                       # captured on the first full minibatch's shapes
+                    # (data-parallel: graph segments cut at the gradient buckets, the all-reduces enqueued between them)
+                    from .graph import GraphedTrainStep, SegmentedTrainStep
+                    gstep = (GraphedTrainStep if world == 1 else SegmentedTrainStep)(model, optimizer, x, t,
+                                                                                      warmup_steps=int(args.lr_warmup_steps))
+                if x.shape[0] == args.batch_size:
+                    loss, _ = gstep.replay(x, t)
+                else:                                   # same device-resident optimiser / scheduler state, launched one by one
+                    loss, _ = optimizer.train_step(model, x, t, dev=True)
+            elif fused:
+                loss, _ = optimizer.train_step(model, x, t)         # chexpert.py:159-163 as one fused schedule
+                if scheduler == "fused" and args.step >= args.lr_warmup_steps:
+                    optimizer.scheduler_step()
+            else:
+                loss = autograd_step(run, x, t)
+            if run.groups_on.get("freeze_steps", 0) > 0 and args.step == run.groups_on["freeze_steps"]:
+                thaw_backbone(optimizer)                # every rank alike: the table is the same on all of them, no collective
+            if args.step % args.log_interval == 0 and rank == 0:
+                print(json.dumps(log_line(run, loss)), flush=True)
+            if args.step % args.eval_interval == 0:
+                evaluate_and_checkpoint(run, gstep is not None)
+        sync_loss_aux(model, run.aucm_loss)      # (also current when no checkpoint followed the last step)
+        torch.cuda.synchronize()
+        if rank == 0:        # input pipeline + step, end to end (the figure to hold against bench.py's device-resident rate)
+            print(json.dumps({"epoch": epoch, "images_per_sec": round(len(idx) * world / (time.perf_counter() - t_epoch), 1),
+                              "loader_workers": args.num_workers,
+                              "decoded_cache_fill": round(run.train_ds.cache_fill(), 3) if hasattr(run.train_ds, "cache_fill") else None}), flush=True)
+        run_eval(run, "eval_results_step_%d" % args.step)
+
+
+def evaluate_ensemble(run):
+    """chexpert.py:214-240: the mean of the logits of every checkpoint of the folder --restore names."""
+    args, model, boot_groups = run.args, run.model, run.boot_groups
+    assert args.restore and os.path.isdir(args.restore), "Restore argument must be directory with saved checkpoints"
+    outs, losses, members = [], [], []
+    for c in checkpoint_files(args.restore):
+        ck = torch.load(os.path.join(args.restore, c), map_location=run.device)
+        check_checkpoint_head(ck, run.multiclass, c)
+        check_member_hier(run.hier, ck, c)
+        check_checkpoint_pool(ck, model, c)
+        check_checkpoint_head_kind(ck, model, c)
+        model.load_state_dict(model_weights(ck, args, c))
+        o, tg, l = validate(run)
+        outs.append(o)
+        losses.append(l)
+        members.append(c)
+    mean_out = torch.stack(outs, 2).mean(2)                                                      # mean of logits, chexpert.py:233
+    res = M.compute_metrics(mean_out, tg, torch.stack(losses, 2).mean(2))
+    if run.rank == 0:
+        json.dump(res, open(os.path.join(args.output_dir, "eval_results_ensemble.json"), "w"), indent=4)
+        print("AUC:\n", pprint.pformat(res["aucs"]))
+        write_auc_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
+        write_delong(args, "eval_results_ensemble", mean_out, tg, boot_groups, members=dict(zip(members, outs)))
+        write_metrics_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
+        write_calibration(args, "eval_results_ensemble", mean_out, tg, boot_groups)
+
+
+def visualize(run):
+    """chexpert.py:556-563: Grad-CAM grids over the 'vis' subset (three examples per finding category), and for the
+    attention-augmented models the attention-map grids of the stored softmax weights; the class maps of --cam_classes and the
+    pixel attributions of --saliency."""
+    from . import vis
+    from .gradcam import class_cam, grad_cam
+    args, model, device, valid_ds, clahe, hier, cam_classes, sal = (run.args, run.model, run.device, run.valid_ds, run.clahe, run.hier,
+                                                                    run.cam_classes, run.sal)
+    names = class_names(args.n_classes, getattr(args, "labels", "competition"))
+    to_binary = collapse_of(hier["parent"]) if hier is not None else None    # the figures' scores are unconditional probabilities;
+    groups = vis.select_vis_subset(valid_ds.targets, names)
+    flat = sorted({i for g in groups[1] for i in g})
+    pos = {i: k for k, i in enumerate(flat)}
+    imgs, labels, scores, masks, class_maps, sal_maps = [], [], [], [], [], []
+    model.eval()
+    attn_layers = [m for m in model.modules() if type(m).__name__ == "AAConv2d"]
+    csra = model.head_kind == "csra"       # (its figures: the score and attention maps of --cam_classes, and the saliency maps)
+    pcam = model.head_kind == "pcam"       # (its figures: the probability maps of --cam_classes, and the saliency maps)
+    avg_pool = model.pool_kind == "avg" and not csra and not pcam
+    csra_maps, pcam_up = [], []
+    for x, tg, idx in batches(valid_ds, flat, args.batch_size, False):
+        xd = x.to(device)
+        if clahe is not None:                # the figures show what the network saw
+            xd = clahe(xd)
+            x = xd.cpu()
+        with torch.no_grad():              # the maps below stay those of the conditional logits: evidence for a finding GIVEN its parent
+            scores.append((model(xd) if to_binary is None else to_binary(model(xd))).float().cpu())
+        if avg_pool:                         # (another pooling: the saliency maps are the figures, visualize_needs_avg)
+            masks.append(grad_cam(model, xd).float().cpu())
+        if cam_classes is not None and (csra or pcam):
+            from .heads import class_maps as head_maps
+            sc_map, at_map, _ = head_maps(model, xd)
+            csra_maps.append(torch.stack([sc_map[:, cam_classes], at_map[:, cam_classes]], 1).cpu())
+            if pcam:                        # the overlays: P of the requested classes, scaled per map and up-sampled on the GPU
+                from . import ops
+                pm = sc_map[:, cam_classes].contiguous()
+                up = torch.empty(pm.shape[0] * pm.shape[1], 1, xd.shape[2], xd.shape[3], dtype=torch.float32, device=device)
+                ops.cam_norm_upsample(pm.view(up.shape[0], -1), up, pm.shape[2], pm.shape[3])
+                pcam_up.append(up.view(pm.shape[0], pm.shape[1], xd.shape[2], xd.shape[3]).half().cpu())
+        elif cam_classes is not None:       # the raw low-resolution relu(M): up-sampled maps of 14 classes would be hundreds of MB
+            class_maps.append(class_cam(model, xd, cam_classes, normalize=False, upsample=False)[0].cpu())
+        if sal is not None:                 # float interface: whitened, three identical channels (as the attention figures below)
+            xf = ((xd.float().div(255.0) - vis.MEAN) / vis.STD).expand(-1, 3, -1, -1) if xd.dtype == torch.uint8 else xd.float()
+            sal_maps.append(saliency_maps(model, xf.contiguous(), sal).cpu())
+        imgs.append(x.float().div(255.0)[:, 0] if x.dtype == torch.uint8 else (x.float()[:, 0] * vis.STD + vis.MEAN))
+        labels.append(tg)
+        if attn_layers:
+            xn = (x.float().div(255.0) - vis.MEAN) / vis.STD if x.dtype == torch.uint8 else x.float()
+            for k in range(len(x)):
+                vis.vis_attn(xn, ["synthetic/%d" % int(i) for i in idx], idx, attn_layers, args.output_dir, k)
+    imgs, labels, scores = torch.cat(imgs), torch.cat(labels), torch.cat(scores)
+    groups = (groups[0], [[pos[i] for i in g] for g in groups[1]])
+    if avg_pool:
+        cam = masks = torch.cat(masks)
+        files = vis.visualize(imgs.numpy(), labels.numpy(), scores.numpy(), masks[:, 0].numpy(), ["synthetic/%d" % i for i in flat], names,
+                              groups, args.output_dir, getattr(args, "step", 0))
+        np.save(os.path.join(args.output_dir, "vis", "grad_cam.npy"), cam.numpy())
+        print("grad-cam maps:", tuple(cam.shape), "figures:", len(files))
+    if cam_classes is not None and pcam:
+        csra_maps = torch.cat(csra_maps)
+        files = vis.visualize_classes(imgs.numpy(), labels.numpy(), scores.numpy(), torch.cat(pcam_up).float().numpy(),
+                                      ["synthetic/%d" % i for i in flat], names, cam_classes, args.output_dir, getattr(args, "step", 0),
+                                      prefix="pcam")
+        np.save(os.path.join(args.output_dir, "vis", "pcam_maps_lowres.npy"), csra_maps.numpy())
+        print("pcam probability / weight maps:", tuple(csra_maps.shape), "figures:", len(files))
+    elif cam_classes is not None and csra:
+        csra_maps = torch.cat(csra_maps)
+        os.makedirs(os.path.join(args.output_dir, "vis"), exist_ok=True)
+        np.save(os.path.join(args.output_dir, "vis", "csra_maps_lowres.npy"), csra_maps.numpy())
+        print("csra score / attention maps:", tuple(csra_maps.shape))
+    elif cam_classes is not None:
+        class_maps = torch.cat(class_maps)
+        files = vis.visualize_classes(imgs.numpy(), labels.numpy(), scores.numpy(), class_maps.numpy(), ["synthetic/%d" % i for i in flat],
+                                      names, cam_classes, args.output_dir, getattr(args, "step", 0))
+        np.save(os.path.join(args.output_dir, "vis", "class_cam_lowres.npy"), class_maps.numpy())
+        print("class maps:", tuple(class_maps.shape), "figures:", len(files))
+    if sal is not None:
+        sal_maps = torch.cat(sal_maps)
+        files = vis.visualize_saliency(imgs.numpy(), labels.numpy(), scores.numpy(), sal_maps.numpy(), ["synthetic/%d" % i for i in flat],
+                                       names, sal["classes"], sal["method"], args.output_dir, getattr(args, "step", 0),
+                                       signed=sal["method"] == "ig")
+        # fp16 on disk: every map divided by its largest magnitude (gradients of a logit per pixel are far below fp16's range)
+        scale = sal_maps.abs().amax((2, 3))
+        np.save(os.path.join(args.output_dir, "vis", "saliency_%s.npy" % sal["method"]),
+                (sal_maps / scale.clamp_min(1e-30)[:, :, None, None]).numpy().astype(np.float16))
+        np.save(os.path.join(args.output_dir, "vis", "saliency_%s_scale.npy" % sal["method"]), scale.numpy())
+        print("saliency (%s) maps:" % sal["method"], tuple(sal_maps.shape), "figures:", len(files))
+
+
+def plot_all_roc(args):
+    files = [f for f in os.listdir(args.output_dir) if f.startswith("eval_results") and f.endswith(".json")]
+    if not files:
+        raise RuntimeError("No `eval_results` files found in `%s` to plot results from." % args.output_dir)
+    for f in files:
+        plot_roc(json.load(open(os.path.join(args.output_dir, f))), args, "roc_pr_" + f.split(".")[0])
+
+
+def main(argv=None):
+    """The phases of the module docstring, in order; returns the model."""
+    run = check_flags(argv)
+    args = run.args
+    start_process_group(args, run.world, run.local)
+    run.new_cfg = open_output_dir(args, run.rank)
+    run.device = torch.device("cuda:%d" % (args.cuda or 0))
+    run.train_ds, run.valid_ds = load_datasets(args, run.hier)
+    resolve_label_statistics(run)
+    run.train_loader = make_loader(args, run.train_ds, run.device)
+    try:            # the loader's worker processes end with training, however it ends
+        start_gpu(args, run.device)
+        build_model(run)
+        run.criterion, run.aucm_loss, run.aucm_opt = wire_loss(run)
+        if run.rank == 0:
+            print("Loaded %s (number of parameters: %s; weights trained to step %d)" % (
+                run.model._get_name(), format(sum(p.numel() for p in run.model.parameters()), ","), args.step))
+        run.clahe = make_clahe(args)
+        run.boot_groups = None
+        if getattr(args, "bootstrap", 0) > 0 or getattr(args, "delong", False):
+            run.boot_groups = bootstrap_groups(args, run.valid_ds)
+        if args.train:
+            train(run)
+    finally:
+        if run.train_loader is not None:
+            run.train_loader.close()
     if args.evaluate_single_model:
-        run_eval("eval_results_step_%d" % args.step)
+        run_eval(run, "eval_results_step_%d" % args.step)
     if args.evaluate_ensemble:
-        assert args.restore and os.path.isdir(args.restore), "Restore argument must be directory with saved checkpoints"
-        outs, losses, members = [], [], []
-        for c in sorted(f for f in os.listdir(args.restore) if f.startswith("checkpoint") and f.endswith(".pt")):
-            ck = torch.load(os.path.join(args.restore, c), map_location=device)
-            check_checkpoint_head(ck, multiclass, c)
-            check_member_hier(hier, ck, c)
-            check_checkpoint_pool(ck, model, c)
-            check_checkpoint_head_kind(ck, model, c)
-            model.load_state_dict(model_weights(ck, args, c))
-            o, tg, l = evaluate_sharded(model, valid_ds, args.batch_size, device, rank, world, clahe, collapse)
-            outs.append(o)
-            losses.append(l)
-            members.append(c)
-        mean_out = torch.stack(outs, 2).mean(2)                                                      # mean of logits, chexpert.py:233
-        res = M.compute_metrics(mean_out, tg, torch.stack(losses, 2).mean(2))
-        if rank == 0:
-            json.dump(res, open(os.path.join(args.output_dir, "eval_results_ensemble.json"), "w"), indent=4)
-            print("AUC:\n", pprint.pformat(res["aucs"]))
-            write_auc_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
-            write_delong(args, "eval_results_ensemble", mean_out, tg, boot_groups, members=dict(zip(members, outs)))
-            write_metrics_ci(args, "eval_results_ensemble", mean_out, tg, boot_groups)
-            write_calibration(args, "eval_results_ensemble", mean_out, tg, boot_groups)
-    if args.visualize and rank == 0:
-        # chexpert.py:556-563: Grad-CAM grids over the 'vis' subset (three examples per finding category), and for the
-        # attention-augmented models the attention-map grids of the stored softmax weights
-        from . import vis
-        from .gradcam import class_cam, grad_cam
-        names = class_names(args.n_classes, getattr(args, "labels", "competition"))
-        to_binary = collapse_of(hier["parent"]) if hier is not None else None    # the figures' scores are unconditional probabilities;
-        groups = vis.select_vis_subset(valid_ds.targets, names)
-        flat = sorted({i for g in groups[1] for i in g})
-        pos = {i: k for k, i in enumerate(flat)}
-        imgs, labels, scores, masks, class_maps, sal_maps = [], [], [], [], [], []
-        model.eval()
-        attn_layers = [m for m in model.modules() if type(m).__name__ == "AAConv2d"]
-        csra = model.head_kind == "csra"       # (its figures: the score and attention maps of --cam_classes, and the saliency maps)
-        pcam = model.head_kind == "pcam"       # (its figures: the probability maps of --cam_classes, and the saliency maps)
-        avg_pool = model.pool_kind == "avg" and not csra and not pcam
-        csra_maps, pcam_up = [], []
-        for x, tg, idx in batches(valid_ds, flat, args.batch_size, False):
-            xd = x.to(device)
-            if clahe is not None:                # the figures show what the network saw
-                xd = clahe(xd)
-                x = xd.cpu()
-            with torch.no_grad():              # the maps below stay those of the conditional logits: evidence for a finding GIVEN its parent
-                scores.append((model(xd) if to_binary is None else to_binary(model(xd))).float().cpu())
-            if avg_pool:                         # (another pooling: the saliency maps are the figures, visualize_needs_avg)
-                masks.append(grad_cam(model, xd).float().cpu())
-            if cam_classes is not None and (csra or pcam):
-                from .heads import class_maps as head_maps
-                sc_map, at_map, _ = head_maps(model, xd)
-                csra_maps.append(torch.stack([sc_map[:, cam_classes], at_map[:, cam_classes]], 1).cpu())
-                if pcam:                        # the overlays: P of the requested classes, scaled per map and up-sampled on the GPU
-                    from . import ops
-                    pm = sc_map[:, cam_classes].contiguous()
-                    up = torch.empty(pm.shape[0] * pm.shape[1], 1, xd.shape[2], xd.shape[3], dtype=torch.float32, device=device)
-                    ops.cam_norm_upsample(pm.view(up.shape[0], -1), up, pm.shape[2], pm.shape[3])
-                    pcam_up.append(up.view(pm.shape[0], pm.shape[1], xd.shape[2], xd.shape[3]).half().cpu())
-            elif cam_classes is not None:       # the raw low-resolution relu(M): up-sampled maps of 14 classes would be hundreds of MB
-                class_maps.append(class_cam(model, xd, cam_classes, normalize=False, upsample=False)[0].cpu())
-            if sal is not None:                 # float interface: whitened, three identical channels (as the attention figures below)
-                xf = ((xd.float().div(255.0) - vis.MEAN) / vis.STD).expand(-1, 3, -1, -1) if xd.dtype == torch.uint8 else xd.float()
-                sal_maps.append(saliency_maps(model, xf.contiguous(), sal).cpu())
-            imgs.append(x.float().div(255.0)[:, 0] if x.dtype == torch.uint8 else (x.float()[:, 0] * vis.STD + vis.MEAN))
-            labels.append(tg)
-            if attn_layers:
-                xn = (x.float().div(255.0) - vis.MEAN) / vis.STD if x.dtype == torch.uint8 else x.float()
-                for k in range(len(x)):
-                    vis.vis_attn(xn, ["synthetic/%d" % int(i) for i in idx], idx, attn_layers, args.output_dir, k)
-        imgs, labels, scores = torch.cat(imgs), torch.cat(labels), torch.cat(scores)
-        groups = (groups[0], [[pos[i] for i in g] for g in groups[1]])
-        if avg_pool:
-            cam = masks = torch.cat(masks)
-            files = vis.visualize(imgs.numpy(), labels.numpy(), scores.numpy(), masks[:, 0].numpy(), ["synthetic/%d" % i for i in flat], names,
-                                  groups, args.output_dir, getattr(args, "step", 0))
-            np.save(os.path.join(args.output_dir, "vis", "grad_cam.npy"), cam.numpy())
-            print("grad-cam maps:", tuple(cam.shape), "figures:", len(files))
-        if cam_classes is not None and pcam:
-            csra_maps = torch.cat(csra_maps)
-            files = vis.visualize_classes(imgs.numpy(), labels.numpy(), scores.numpy(), torch.cat(pcam_up).float().numpy(),
-                                          ["synthetic/%d" % i for i in flat], names, cam_classes, args.output_dir, getattr(args, "step", 0),
-                                          prefix="pcam")
-            np.save(os.path.join(args.output_dir, "vis", "pcam_maps_lowres.npy"), csra_maps.numpy())
-            print("pcam probability / weight maps:", tuple(csra_maps.shape), "figures:", len(files))
-        elif cam_classes is not None and csra:
-            csra_maps = torch.cat(csra_maps)
-            os.makedirs(os.path.join(args.output_dir, "vis"), exist_ok=True)
-            np.save(os.path.join(args.output_dir, "vis", "csra_maps_lowres.npy"), csra_maps.numpy())
-            print("csra score / attention maps:", tuple(csra_maps.shape))
-        elif cam_classes is not None:
-            class_maps = torch.cat(class_maps)
-            files = vis.visualize_classes(imgs.numpy(), labels.numpy(), scores.numpy(), class_maps.numpy(), ["synthetic/%d" % i for i in flat],
-                                          names, cam_classes, args.output_dir, getattr(args, "step", 0))
-            np.save(os.path.join(args.output_dir, "vis", "class_cam_lowres.npy"), class_maps.numpy())
-            print("class maps:", tuple(class_maps.shape), "figures:", len(files))
-        if sal is not None:
-            sal_maps = torch.cat(sal_maps)
-            files = vis.visualize_saliency(imgs.numpy(), labels.numpy(), scores.numpy(), sal_maps.numpy(), ["synthetic/%d" % i for i in flat],
-                                           names, sal["classes"], sal["method"], args.output_dir, getattr(args, "step", 0),
-                                           signed=sal["method"] == "ig")
-            # fp16 on disk: every map divided by its largest magnitude (gradients of a logit per pixel are far below fp16's range)
-            scale = sal_maps.abs().amax((2, 3))
-            np.save(os.path.join(args.output_dir, "vis", "saliency_%s.npy" % sal["method"]),
-                    (sal_maps / scale.clamp_min(1e-30)[:, :, None, None]).numpy().astype(np.float16))
-            np.save(os.path.join(args.output_dir, "vis", "saliency_%s_scale.npy" % sal["method"]), scale.numpy())
-            print("saliency (%s) maps:" % sal["method"], tuple(sal_maps.shape), "figures:", len(files))
-    if args.plot_roc and rank == 0:
-        files = [f for f in os.listdir(args.output_dir) if f.startswith("eval_results") and f.endswith(".json")]
-        if not files:
-            raise RuntimeError("No `eval_results` files found in `%s` to plot results from." % args.output_dir)
-        for f in files:
-            plot_roc(json.load(open(os.path.join(args.output_dir, f))), args, "roc_pr_" + f.split(".")[0])
-    if world > 1:
+        evaluate_ensemble(run)
+    if args.visualize and run.rank == 0:
+        visualize(run)
+    if args.plot_roc and run.rank == 0:
+        plot_all_roc(args)
+    if run.world > 1:
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
-    return model
+    return run.model
 
 
 if __name__ == "__main__":

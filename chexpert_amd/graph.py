@@ -6,6 +6,9 @@ becomes the floor once the GPU side of the step is faster than that.  A replay c
 `hipGraphLaunch`).  Shapes are static: the caller copies each minibatch into `x` / `target` (device tensors owned by this
 object) and calls `replay()`.  Learning rate and step count live in device memory (`optim._Flat.hyper`), so the optimiser and
 the scheduler advance inside the graph.
+
+What is captured is the optimiser's own statement of the step, `optimizer.train_step(model, x, target, dev=True)`
+(optim._Flat.train_step; optim.FusedSAM.train_step for its two passes), the one the command line launches eagerly as well.
 """
 import torch
 
@@ -15,67 +18,67 @@ def _step_state(model):
     return list(model.buffers()) + list(getattr(model, "loss_step_state", lambda: [])())
 
 
-class GraphedTrainStep:
-    def __init__(self, model, optimizer, x, target, warmup_steps=0, warmup_iters=2):
-        if not x.is_cuda:
-            raise RuntimeError("GraphedTrainStep needs device tensors (no CPU path)")
+class _CapturedStep:
+    """What GraphedTrainStep and SegmentedTrainStep share: the tensors a replay reads, the eager warm-up on a side stream, the
+    step that is captured, putting back what the warm-up changed, and the two ends of `replay()`."""
+
+    def _warm_up(self, model, optimizer, x, target, warmup_steps, warmup_iters):
+        """Binds the object to `model` / `optimizer` and clones of `x` / `target`, then runs the step eagerly on the side stream
+        it returns: that binds the engine, allocates the workspaces, sets kernel attributes and creates the optimiser state, none
+        of which may happen during capture.  It runs every kind of pass the step has but no optimiser, so the parameters stay as
+        they are (an optimiser of two passes, optim.FusedSAM, gets its second pass's path through the engine warmed up too)."""
         self.model, self.opt = model, optimizer
-        self.x = x.clone()
-        self.target = target.clone()
-        eng = model._eng()
-        if getattr(eng, "reducer", None) is not None:
-            raise RuntimeError("graph capture of the data-parallel step is not supported (collectives are enqueued eagerly)")
+        self.x, self.target = x.clone(), target.clone()
         # (Dropout / DropConnect masks: their step counter lives in device memory and is bumped inside the captured step --
         # efficientnet.py, cx_dropout_mask_dev -- so every replay draws new masks)
         model.train()
-        # an optimiser with a train_step of its own (optim.FusedSAM: two forward/backward passes around its ascent step) is captured
-        # through it; the warm-up runs both kinds of pass but no optimiser, so the parameters stay as they are
-        two_pass = hasattr(optimizer, "train_step")
-        # construction is free of side effects on the model: the warm-up steps below really run (they update BatchNorm running
-        # statistics), so the module buffers and the num_batches_tracked bookkeeping are put back afterwards
+        # construction is free of side effects on the model: the warm-up steps really run (they update BatchNorm running
+        # statistics), so the module buffers and the num_batches_tracked bookkeeping are put back afterwards (`_restore`)
         # (so are the auxiliary scalars of set_loss(kind="aucm"), which a train-mode step updates: loss_step_state)
-        saved = [(b, b.detach().clone()) for b in _step_state(model)]
-        nbt = getattr(model, "_nbt_pending", 0)
-        # eager warm-up on a side stream: binds the engine, allocates the workspaces, sets kernel attributes, creates the
-        # optimiser state -- none of which may happen during capture
+        self._saved = [(b, b.detach().clone()) for b in _step_state(model)]
+        self._nbt = getattr(model, "_nbt_pending", 0)
         s = torch.cuda.Stream(device=x.device)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            for _ in range(max(1, warmup_iters)):
+            for _ in range(max(1, warmup_iters)):                  # (data-parallel: real collectives, every rank alike)
                 model.zero_grad()
                 self.loss, self.logits = model.forward_backward(self.x, self.target)
-            if two_pass:                                            # the second pass's path through the engine, warmed up as well
+            if optimizer is not None and optimizer.PASSES == 2:
                 model.zero_grad()
                 model.forward_backward(self.x, self.target, track_stats=False)
             if optimizer is not None:
-                optimizer._bufs(2 if hasattr(optimizer, "betas") or hasattr(optimizer, "alpha") else 1)
+                optimizer._bufs(optimizer.NSTATE)
                 optimizer.hyper(warmup_steps)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            if two_pass:
-                self.loss, self.logits = optimizer.train_step(model, self.x, self.target, dev=True)
-            else:
-                model.zero_grad()
-                self.loss, self.logits = model.forward_backward(self.x, self.target)
-                if optimizer is not None:
-                    optimizer.step_dev()
-                    optimizer.tick()
-        with torch.no_grad():
-            for b, v in saved:
-                b.copy_(v)
-        if hasattr(model, "_nbt_pending"):
-            model._nbt_pending = nbt
-        self.replays = 0
+        return s
 
-    def replay(self, x=None, target=None):
-        """Run one step; returns (loss, logits) device tensors that the NEXT replay overwrites."""
+    def _step(self):
+        """The step under capture: the optimiser's train_step on the device-resident learning rate and step count."""
+        if self.opt is None:
+            self.model.zero_grad()
+            self.loss, self.logits = self.model.forward_backward(self.x, self.target)
+        else:
+            self.loss, self.logits = self.opt.train_step(self.model, self.x, self.target, dev=True)
+
+    def _restore(self, s):
+        """Joins the side stream and puts the buffers the warm-up steps changed back (they really ran)."""
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for b, v in self._saved:
+                b.copy_(v)
+        if hasattr(self.model, "_nbt_pending"):
+            self.model._nbt_pending = self._nbt
+        self._saved = None
+
+    def _copy_in(self, x, target):
         if x is not None:
             self.x.copy_(x, non_blocking=True)
         if target is not None:
             self.target.copy_(target, non_blocking=True)
-        self.graph.replay()
+
+    def _replayed(self):
         self.replays += 1
         # the captured optimiser kernel has just changed the fp32 masters without touching tensor versions: an eval forward that
         # follows must repack the weights (Engine.pack(train=False) compares versions)
@@ -84,10 +87,30 @@ class GraphedTrainStep:
         return self.loss, self.logits
 
 
+class GraphedTrainStep(_CapturedStep):
+    def __init__(self, model, optimizer, x, target, warmup_steps=0, warmup_iters=2):
+        if not x.is_cuda:
+            raise RuntimeError("GraphedTrainStep needs device tensors (no CPU path)")
+        if getattr(model._eng(), "reducer", None) is not None:
+            raise RuntimeError("graph capture of the data-parallel step is not supported (collectives are enqueued eagerly)")
+        s = self._warm_up(model, optimizer, x, target, warmup_steps, warmup_iters)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._step()
+        self._restore(s)
+        self.replays = 0
+
+    def replay(self, x=None, target=None):
+        """Run one step; returns (loss, logits) device tensors that the NEXT replay overwrites."""
+        self._copy_in(x, target)
+        self.graph.replay()
+        return self._replayed()
+
+
 _TEST_FAIL_CAPTURE = 0          # tests/test_dp_gpu.py: N > 0 raises at the N-th cut, i.e. in the middle of a captured backward pass
 
 
-class SegmentedTrainStep:
+class SegmentedTrainStep(_CapturedStep):
     """The data-parallel training step as a CHAIN of hipGraphs.
 
     Collectives are enqueued from Python (parallel.GradReducer), so the whole step cannot be one graph.  Enqueued launch by
@@ -107,29 +130,14 @@ class SegmentedTrainStep:
     def __init__(self, model, optimizer, x, target, warmup_steps=0, warmup_iters=2):
         if not x.is_cuda:
             raise RuntimeError("SegmentedTrainStep needs device tensors (no CPU path)")
-        if hasattr(optimizer, "train_step"):
+        if optimizer is not None and optimizer.PASSES == 2:
             raise RuntimeError("SegmentedTrainStep refuses FusedSAM: data-parallel SAM is not supported (the first pass would have to "
                                "skip the all-reduce)")
-        eng = model._eng()
-        red = getattr(eng, "reducer", None)
+        red = getattr(model._eng(), "reducer", None)
         if red is None:
             raise RuntimeError("SegmentedTrainStep is the data-parallel form (engine.enable_data_parallel() first); a single process uses GraphedTrainStep")
-        self.model, self.opt, self.red = model, optimizer, red
-        self.x, self.target = x.clone(), target.clone()
-        model.train()
-        saved = [(b, b.detach().clone()) for b in _step_state(model)]
-        nbt = getattr(model, "_nbt_pending", 0)
-        s = torch.cuda.Stream(device=x.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(max(1, warmup_iters)):                  # eager warm-up: real collectives, every rank alike
-                model.zero_grad()
-                self.loss, self.logits = model.forward_backward(self.x, self.target)
-            if optimizer is not None:
-                optimizer._bufs(2 if hasattr(optimizer, "betas") or hasattr(optimizer, "alpha") else 1)
-                optimizer.hyper(warmup_steps)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+        self.red = red
+        s = self._warm_up(model, optimizer, x, target, warmup_steps, warmup_iters)
         self.segs = []                                              # [(graph, actions)]; an action: ("launch", lo, hi) | ("finish",)
         self._pool = torch.cuda.graph_pool_handle()
         self._g = None
@@ -138,11 +146,7 @@ class SegmentedTrainStep:
             with torch.cuda.stream(s):
                 try:
                     self._begin()
-                    model.zero_grad()
-                    self.loss, self.logits = model.forward_backward(self.x, self.target)
-                    if optimizer is not None:
-                        optimizer.step_dev()
-                        optimizer.tick()
+                    self._step()
                     self._g.capture_end()
                     self.segs.append((self._g, ()))
                     self._g = None
@@ -165,24 +169,13 @@ class SegmentedTrainStep:
             # must still see the ORIGINAL error (bench.py logs it and falls back to the eager step), chained, not replaced
             red.capture = None
             try:
-                self._restore(s, saved, model, nbt)
+                self._restore(s)
             except Exception as cleanup_error:
                 raise capture_error from cleanup_error
             raise
         red.capture = None
-        self._restore(s, saved, model, nbt)
+        self._restore(s)
         self.replays = 0
-
-    @staticmethod
-    def _restore(s, saved, model, nbt):
-        """Joins the capture stream and puts the buffers the warm-up steps changed back (they really ran)."""
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        with torch.no_grad():
-            for b, v in saved:
-                b.copy_(v)
-        if hasattr(model, "_nbt_pending"):
-            model._nbt_pending = nbt
 
     def _begin(self):
         self._g = torch.cuda.CUDAGraph()
@@ -198,10 +191,7 @@ class SegmentedTrainStep:
             raise RuntimeError("forced capture failure (test hook)")
 
     def replay(self, x=None, target=None):
-        if x is not None:
-            self.x.copy_(x, non_blocking=True)
-        if target is not None:
-            self.target.copy_(target, non_blocking=True)
+        self._copy_in(x, target)
         red = self.red
         red.begin()
         for g, actions in self.segs:
@@ -211,7 +201,4 @@ class SegmentedTrainStep:
                     red._launch(action[1], action[2])
                 else:
                     red.wait()
-        self.replays += 1
-        self.model._eng().packed_version = None
-        self.model._nbt_pending += 1
-        return self.loss, self.logits
+        return self._replayed()

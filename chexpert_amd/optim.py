@@ -218,6 +218,7 @@ class _Flat:
     The step is then `cx_grad_norm_items` (when clipping or skipping) + `cx_*_step_items`, walking a per-tensor item table and
     the group rows {lr_mult, weight_decay, frozen, t0} in device memory (`set_group` rewrites a row, between graph replays too)."""
     NSTATE = 0
+    PASSES = 1                      # forward/backward passes of one train_step (FusedSAM: 2)
     KIND = None
     SCHED = (0, 1.0, (0, 0))        # (kind, gamma, milestones): 0 none, 1 ExponentialLR, 2 MultiStepLR
     # what the host-lr entry point of each family takes beside the rule's own arguments, by the family's suffix
@@ -373,6 +374,24 @@ class _Flat:
 
     def step_dev(self, grad_scale=1.0):
         self._step(grad_scale, True)
+
+    def train_step(self, model, x, target, dev=False):
+        """One training step on the minibatch (chexpert.py:159-164), the statement of it that the command line and the captured
+        steps of graph.py share; returns (loss, logits) of the forward pass.  zero_grad, forward_backward, then step() or, `dev`
+        (learning rate, step count and scheduler in device memory), step_dev(), tick() and the engine's packed weights marked
+        stale: the device-side update leaves the tensor versions as they were.  The host-side scheduler_step() stays with the
+        caller, who knows the warm-up and the global step."""
+        if model is not self.model:
+            raise RuntimeError("train_step: the model is not the one the optimiser was built over")
+        self.zero_grad()
+        loss, logits = model.forward_backward(x, target)
+        if dev:
+            self.step_dev()
+            self.tick()
+            model._eng().packed_version = None
+        else:
+            self.step()
+        return loss, logits
 
     def _norm_on(self):
         return self.max_grad_norm is not None or self.skip_nonfinite
@@ -716,6 +735,7 @@ class FusedSAM:
 
     Every attribute and method this class does not define (grad_norm, skipped_steps, ema_weights, set_group, hyper, tick,
     sync_from_device, scheduler_step, trust_ratios, lr, ...) is the base's, for reading and for writing."""
+    PASSES = 2                      # (on this class itself: __getattr__ would answer with the base's 1)
     _OWN = ("base", "rho", "adaptive", "eps", "_sam", "_rho_dev", "_backup", "_spart", "_sitems", "_sgtab", "_sitems_host", "_snumel")
 
     def __init__(self, base, rho=0.05, adaptive=False, eps=1e-12):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from chexpert_amd import synth
+from eager_step import _eager_dev_step
 
 pytestmark = pytest.mark.gpu
 
@@ -406,16 +407,6 @@ def test_loss_state_round_trip(dev):
     held, ptr = a.loss_aux.clone(), a.loss_aux.data_ptr()
     a.set_loss(kind="aucm", prior=[0.2] * 5, margin=0.9, lr_aux=0.05)
     assert a.loss_aux.data_ptr() == ptr and torch.equal(a.loss_aux, held) and a.loss_prior.tolist() == torch.tensor([0.2] * 5).tolist()
-
-
-def _eager_dev_step(model, opt, x, t):
-    """The step GraphedTrainStep captures, launched one by one (the command line's partial-minibatch step)."""
-    opt.zero_grad()
-    loss, _ = model.forward_backward(x, t)
-    opt.step_dev()
-    opt.tick()
-    model._eng().packed_version = None
-    return loss.clone()
 
 
 def test_graphed_step_replays_the_loss_and_its_update(dev):

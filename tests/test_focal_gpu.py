@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from chexpert_amd import synth
+from eager_step import _eager_dev_step
 
 pytestmark = pytest.mark.gpu
 
@@ -381,16 +382,6 @@ def test_set_loss_walk_leaves_nothing_of_the_previous_kind(dev):
             if kind == "aucm":                                          # the train-mode step has moved the scalars: a later kind must not see them
                 assert float(model.loss_aux.abs().max()) > 0
     assert len(seen) == 2 * len(walk) and set(ptrs) == {"loss_pos_weight", "loss_aux", "loss_prior", "loss_lr_aux", "loss_focus", "_loss_daux"}
-
-
-def _eager_dev_step(model, opt, x, t):
-    """The step GraphedTrainStep captures, launched one by one (the command line's partial-minibatch step)."""
-    opt.zero_grad()
-    loss, _ = model.forward_backward(x, t)
-    opt.step_dev()
-    opt.tick()
-    model._eng().packed_version = None
-    return loss.clone()
 
 
 def test_graphed_step_sees_focus_changes_and_ignored_targets(dev):

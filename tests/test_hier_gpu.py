@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from chexpert_amd import synth
+from eager_step import _eager_dev_step
 
 pytestmark = pytest.mark.gpu
 
@@ -405,16 +406,6 @@ def test_set_loss_walk_leaves_nothing_of_the_previous_kind(dev):
     assert model.loss_kind == "hier" and model.loss_parent.tolist() == flat and model.loss_mode == "unconditional"
     assert model.set_loss() is model and model.loss_parent is None and model.loss_mode is None and model.loss_state() == bce_state
     assert other.load_loss_state(bce_state) is other and other.loss_kind == "bce" and other.loss_parent is None and other.loss_mode is None
-
-
-def _eager_dev_step(model, opt, x, t):
-    """The step GraphedTrainStep captures, launched one by one (the command line's partial-minibatch step)."""
-    opt.zero_grad()
-    loss, _ = model.forward_backward(x, t)
-    opt.step_dev()
-    opt.tick()
-    model._eng().packed_version = None
-    return loss.clone()
 
 
 @pytest.mark.parametrize("mode", MODES)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from chexpert_amd import synth
+from eager_step import _eager_dev_step
 
 pytestmark = pytest.mark.gpu
 
@@ -331,16 +332,6 @@ def test_set_loss_walk_leaves_nothing_of_the_previous_kind(dev):
     assert model.loss_kind == "multiclass" and torch.equal(model.loss_class_weight.cpu(), 2 * cw)
     assert model.set_loss() is model and model.loss_class_weight is None and model.loss_state() == bce_state
     assert other.load_loss_state(bce_state) is other and other.loss_kind == "bce" and other.loss_class_weight is None
-
-
-def _eager_dev_step(model, opt, x, t):
-    """The step GraphedTrainStep captures, launched one by one (the command line's partial-minibatch step)."""
-    opt.zero_grad()
-    loss, _ = model.forward_backward(x, t)
-    opt.step_dev()
-    opt.tick()
-    model._eng().packed_version = None
-    return loss.clone()
 
 
 def test_graphed_step_equals_eager_and_sees_class_weight_changes(dev):

@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from chexpert_amd import heads as H
 from chexpert_amd import synth
+from eager_step import _eager_dev_step
 
 pytestmark = pytest.mark.gpu
 
@@ -472,16 +473,6 @@ def test_class_maps(dev, net):
     model.train()
     with pytest.raises(RuntimeError, match="eval mode"):
         H.class_maps(model, x)
-
-
-def _eager_dev_step(model, opt, x, t):
-    """The step GraphedTrainStep captures, launched one by one (tests/test_multiclass_gpu.py)."""
-    opt.zero_grad()
-    loss, _ = model.forward_backward(x, t)
-    opt.step_dev()
-    opt.tick()
-    model._eng().packed_version = None
-    return loss.clone()
 
 
 def test_graphed_step_equals_eager(dev):

@@ -27,6 +27,7 @@ import torch.nn.functional as F
 
 from chexpert_amd import pooling as P
 from chexpert_amd import synth
+from eager_step import _eager_dev_step
 
 pytestmark = pytest.mark.gpu
 
@@ -422,16 +423,6 @@ def test_avg_is_untouched_and_refusals(dev):
     lse.eval()
     with torch.no_grad():
         assert bool(torch.isfinite(lse(x)).all())
-
-
-def _eager_dev_step(model, opt, x, t):
-    """The step GraphedTrainStep captures, launched one by one (tests/test_multiclass_gpu.py)."""
-    opt.zero_grad()
-    loss, _ = model.forward_backward(x, t)
-    opt.step_dev()
-    opt.tick()
-    model._eng().packed_version = None
-    return loss.clone()
 
 
 @pytest.mark.parametrize("kind", ["gem", "lse"])

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from chexpert_amd import synth
+from eager_step import _eager_dev_step
 
 pytestmark = pytest.mark.gpu
 
@@ -277,16 +278,6 @@ def test_ignoring_has_teeth(dev):
     model.forward_backward(x, t)
     gw, gb = model.classifier.weight.grad, model.classifier.bias.grad
     assert float(gw[c].abs().max()) > 0 and gb[c].item() != 0.0
-
-
-def _eager_dev_step(model, opt, x, t):
-    """The step GraphedTrainStep captures, launched one by one (the command line's partial-minibatch step)."""
-    opt.zero_grad()
-    loss, _ = model.forward_backward(x, t)
-    opt.step_dev()
-    opt.tick()
-    model._eng().packed_version = None
-    return loss.clone()
 
 
 def test_graphed_step_replays_ignored_targets_and_sees_weight_updates(dev):
