@@ -19,6 +19,7 @@ CALIB_METHODS = {"temperature": 0, "platt": 1}                     # CX_CALIB_TE
 CALIB_MAX_ITER, CALIB_MAX_BINS = 1000, 64
 DELONG_MAX_ROWS, DELONG_WG_ENTRIES, DELONG_TILE = 128, 16384, 32   # 4 rows per class and model: two models of 16 classes
 HIER_MAX_LABELS, HIER_MAX_PATH = 64, 8                             # CX_HIER_MAX_LABELS, CX_HIER_MAX_PATH (loss.hip)
+NTXENT_MAX_N, NTXENT_MAX_D = 4096, 1024                            # CX_NTXENT_MAX_N, CX_NTXENT_MAX_D (loss.hip)
 
 _vp, _fp, _i32 = C.c_void_p, C.c_void_p, C.c_int32
 
@@ -129,6 +130,8 @@ SIGNATURES = {
     "cx_mc3_collapse": [_vp, _vp, _vp, _i, _i, _vp],
     "cx_hier_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _i, _i, _vp],
     "cx_hier_collapse": [_vp, _vp, _vp, _vp, _i, _i, _vp],
+    "cx_ntxent_scratch": [_i, _i],
+    "cx_ntxent_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, C.c_longlong, _i, _i, _vp],
     "cx_softmax_ce_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp],
     "cx_head_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "cx_gap_relu_bn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
@@ -284,7 +287,7 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = C.c_char_p if name in ("cx_error_string", "cx_last_kernel") else \
-                C.c_longlong if name in ("cx_csra_bwd_scratch", "cx_pcam_bwd_scratch") else C.c_int
+                C.c_longlong if name in ("cx_csra_bwd_scratch", "cx_pcam_bwd_scratch", "cx_ntxent_scratch") else C.c_int
         if l.cx_abi_version() != 10:
             raise RuntimeError("chexpert_amd: ABI version mismatch")
         _lib = l

@@ -463,3 +463,26 @@ def make_sample_mix(mixup_alpha=0.0, cutmix_alpha=0.0, prob=1.0, switch_prob=0.5
     launched or allocated."""
     sm = SampleMix(mixup_alpha, cutmix_alpha, prob, switch_prob, mode, erase_prob, erase_fill, rank, device)
     return sm if (sm.mixing or sm.erase_prob > 0) else None
+
+
+# ------------------------------------------------------------------------------------------------ two views (contrastive pretraining)
+def duplicate_views(x_u8):
+    """[x; x]: the uint8 minibatch twice, rows i and i + B the same image, ahead of the per-row random steps (RandomAffine, the
+    jitter), which draw parameters for each of the 2B rows."""
+    return torch.cat([x_u8, x_u8])
+
+
+def contrastive_ids(rows, groups=None):
+    """The (2B, 1) fp32 ids of the contrastive loss for the duplicated minibatch of duplicate_views.  rows: the B dataset indices of
+    the minibatch.  groups None (--positive view): the row's position 0 .. B - 1, so the two views of an image are each other's only
+    positive.  groups: one integer per value `rows` can take (the index of the image's study or patient, indexed the way `rows` counts: the
+    loader's row labels, or positions): the id is that of the image's group, so other
+    images of the group in the minibatch are positives too (MedAug).  Ids must be exact in fp32: below 2^24."""
+    rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+    if groups is None:
+        ids = torch.arange(rows.numel(), dtype=torch.int64)
+    else:
+        ids = torch.as_tensor(groups, dtype=torch.int64)[rows]
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= 1 << 24):
+            raise ValueError("contrastive_ids takes group indices in [0, 2^24) (got %d .. %d)" % (int(ids.min()), int(ids.max())))
+    return torch.cat([ids, ids]).to(torch.float32).reshape(-1, 1)

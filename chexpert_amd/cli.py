@@ -161,6 +161,25 @@
   --calibration_from FILE   apply the fit stored in FILE (a calibration_<tag>.json, e.g. of another split) instead of fitting; exclusive with
                         --calibrate.  Before / after measured on the split the map was fitted on is optimistic: fit on one split, report
                         on another.  --calibration_bins alone applies no map and reports the uncalibrated metrics only
+  --pretrain contrastive   contrastive pretraining of the backbone on the images themselves (SimCLR's NT-Xent, SupCon's L_out with several
+                        positives; MoCo-CXR and MedAug are the sources for chest X-rays): the classifier nn.Linear becomes the projection of
+                        width --proj_dim D (default 128), every minibatch is equalised once (--clahe), duplicated into [x; x] and each copy
+                        gets its own --affine / --jitter draw, and the step's loss is FusedNet.set_loss(kind="ntxent", temperature=T)
+                        with --temperature T (default 0.2) over the 2 x --batch_size rows (both views share BatchNorm's batch
+                        statistics).  --positive view (default): the two views of an image are each other's only positives; study |
+                        patient: every row of the same study / patient in the minibatch is one (MedAug; needs the real data's paths).  The
+                        labels are not read.  Needs --train and --affine or --jitter; refuses --mixup / --cutmix / --erase_prob, --loss,
+                        --pos_weight, --uncertain multiclass, --head csra|pcam, more than one rank and the --evaluate_* / --visualize /
+                        --plot_roc modes.  An --eval_interval step computes the contrastive loss and the top-1 share (the anchors whose
+                        nearest row is a positive) over the validation set from two views drawn from a fixed seed, prints them and writes
+                        pretrain_eval_step_<n>.json; the checkpoint carries loss_state, "pretrain": "contrastive" and eval_loss, and its
+                        avg_auc is -eval_loss, so that the best_checkpoints are the lowest-loss ones.  --restore continues such a run and
+                        is refused into a supervised one (and the other way round); the log line gains top1
+  --init_backbone FILE  with --train: every tensor of FILE's state_dict but the classifier's weight and bias (whatever their width) is loaded
+                        before the first step, BatchNorm's running statistics included (the pooling's own numbers, GeM's exponent and
+                        log-sum-exp's sharpness, where the checkpoint and this run's --pool both have them); the step, the
+                        optimiser state and the loss state are not.  A missing or mis-shaped key is an error that names it.  --pool, --head
+                        and --loss stay free; exclusive with --restore.  (--freeze_backbone_steps / --head_lr_mult give the linear probe)
 
 Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N chexpert.py --train ...`; every rank holds a
 replica and a shard of each minibatch stream (per-rank BatchNorm statistics, averaged gradients: DDP semantics), the
@@ -175,7 +194,7 @@ plain container (`run`, a SimpleNamespace without methods):
   2. open_output_dir           --output_dir and config.json (add_to_config: a resolved key of a config this run created)
   3. load_datasets             synthetic or ChexpertCSV, the decoded cache, the hierarchy closure; resolve_label_statistics
   4. make_loader               the RingLoader, before the first GPU call; from here to the end of training one try/finally closes it
-  5. build_model               restore_source / restore_pool / restore_head / make_model / restore / hier_for_checkpoint
+  5. build_model               restore_source / restore_pool / restore_head / make_model / restore / hier_for_checkpoint / init_backbone
   6. wire_loss                 FusedNet.set_loss, the autograd route's criterion, the AUCM module and its optimiser
   7. train                     the epoch loop: preprocess, then the graphed / eager / autograd step, log_line, evaluate_and_checkpoint;
                                every fused step is `optimizer.train_step(model, x, t, dev=...)` (optim._Flat, optim.FusedSAM), replayed
@@ -330,6 +349,14 @@ def build_parser():
                         "per-pixel probabilities as weights (probabilistic-CAM pooling) and gives per-class probability maps")
     p.add_argument("--csra_lambda", type=float, default=None, metavar="L", help="with --head csra: the attention term's weight >= 0 (default 0.1)")
     p.add_argument("--csra_T", type=float, default=None, metavar="T", help="with --head csra: the softmax temperature > 0 (default 1)")
+    p.add_argument("--pretrain", default=None, choices=["contrastive"],
+                   help="contrastive pretraining (NT-Xent / SupCon) on two augmented views of every image instead of the supervised loss")
+    p.add_argument("--proj_dim", type=int, default=None, metavar="D", help="with --pretrain: width of the projection, the classifier nn.Linear (default 128)")
+    p.add_argument("--temperature", type=float, default=None, metavar="T", help="with --pretrain: temperature of the contrastive loss, > 0 (default 0.2)")
+    p.add_argument("--positive", default=None, choices=["view", "study", "patient"],
+                   help="with --pretrain: what counts as a positive -- the other view of the image (default), or every row of its study / patient")
+    p.add_argument("--init_backbone", default=None, metavar="FILE",
+                   help="with --train: load every tensor of FILE's state_dict but the classifier's before the first step (exclusive with --restore)")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
                    "16); 0 = in-process")
     p.add_argument("--cache_decoded", type=float, default=float(os.environ.get("CHEXPERT_CACHE_GB", "0")), metavar="GB",
@@ -462,17 +489,38 @@ def report_name(tag, stem, ext=".json"):
     return stem + "_" + (tag[len("eval_results_"):] if tag.startswith("eval_results_") else tag) + ext
 
 
-def bootstrap_groups(args, ds):
-    """One resampling-unit id per validation row, or None for --bootstrap_unit image: the study ('.../patientN/studyK', what
-    data.extract_patient_ids returns) or the patient (that without its last path component)."""
-    unit = getattr(args, "bootstrap_unit", "image")
-    if unit == "image":
+def unit_groups(unit, ds, flag="--bootstrap_unit", none="image"):
+    """One unit id per row of `ds`, or None for the unit `none`: the study ('.../patientN/studyK', what data.extract_patient_ids
+    returns) or the patient (that without its last path component)."""
+    if unit == none:
         return None
     if not hasattr(ds, "data"):
-        raise ValueError("--bootstrap_unit %s groups the images by their file paths; this dataset has none (use image)" % unit)
+        raise ValueError("%s %s groups the images by their file paths; this dataset has none (use %s)" % (flag, unit, none))
     from .data import extract_patient_ids
     ids = [str(v) for v in extract_patient_ids(ds, ds.data.index)]
     return np.array(ids if unit == "study" else [v.rsplit("/", 1)[0] for v in ids])
+
+
+def positive_codes(unit, ds, by_label=False):
+    """--positive: None for `view`, else one integer per image of `ds`, the index of its study or patient.  The array is indexed by the
+    image's position in `ds` (what `batches` yields) or, with by_label, by the csv row label that `ds[i]` returns as its third item
+    (what the training loader yields; the two differ for a filtered or re-indexed frame): a table as long as the largest label, -1
+    where no image has the label (augment.contrastive_ids refuses such an id)."""
+    groups = unit_groups(unit, ds, "--positive", "view")
+    if groups is None:
+        return None
+    codes = np.unique(groups, return_inverse=True)[1].astype(np.int64)
+    if not by_label:
+        return codes
+    labels = np.asarray(ds.data.index, dtype=np.int64)
+    table = np.full(int(labels.max()) + 1, -1, dtype=np.int64)
+    table[labels] = codes
+    return table
+
+
+def bootstrap_groups(args, ds):
+    """One resampling-unit id per validation row, or None for --bootstrap_unit image."""
+    return unit_groups(getattr(args, "bootstrap_unit", "image"), ds)
 
 
 def _interval_options(args):
@@ -809,8 +857,143 @@ def check_member_hier(hier, ck, name):
         hier_for_checkpoint(hier, ck["loss_state"], name)
 
 
+def init_backbone_options(args):
+    """--init_backbone checked before anything runs: it belongs to a --train run, excludes --restore and names a file.  Returns the
+    path, or None without the flag."""
+    init = getattr(args, "init_backbone", None)
+    if init is not None:
+        if not args.train:
+            raise ValueError("--init_backbone starts a training run from a pretrained backbone: pass --train with it")
+        if args.restore:
+            raise ValueError("--init_backbone and --restore are exclusive: one starts a run from a backbone, the other continues a run")
+        if not os.path.isfile(init):
+            raise ValueError("--init_backbone: no file %s" % init)
+    return init
+
+
+def pretrain_options(args, world=1):
+    """--pretrain contrastive and its flags checked before anything runs: None without it, else {"proj_dim", "temperature" (None: a
+    restored checkpoint's, else 0.2: temperature_of), "positive"}.  What the contrastive step cannot be combined with is refused with a
+    one-line reason (ValueError)."""
+    proj, tau, positive = getattr(args, "proj_dim", None), getattr(args, "temperature", None), getattr(args, "positive", None)
+    if getattr(args, "pretrain", None) is None:
+        if proj is not None or tau is not None or positive is not None:
+            raise ValueError("--proj_dim / --temperature / --positive belong to --pretrain contrastive: pass it with them")
+        return None
+    from ._lib import NTXENT_MAX_D, NTXENT_MAX_N
+    from .loss import check_temperature
+
+    def no(flag, why):
+        raise ValueError("--pretrain contrastive cannot be combined with %s: %s" % (flag, why))
+    if not args.train:
+        raise ValueError("--pretrain contrastive is a training mode: pass --train with it")
+    for flag in ("evaluate_single_model", "evaluate_ensemble", "visualize", "plot_roc"):
+        if getattr(args, flag, False):
+            no("--" + flag, "the head is a projection, not a classifier: there are no findings to score or draw")
+    if not (args.affine or args.jitter):
+        raise ValueError("--pretrain contrastive needs --affine or --jitter (or both): without a random step the two views of an image are identical")
+    if getattr(args, "mixup", 0.0) > 0 or getattr(args, "cutmix", 0.0) > 0 or getattr(args, "erase_prob", 0.0) > 0:
+        no("--mixup / --cutmix / --erase_prob", "they mix or blank rows of the batch, whose labels the contrastive step does not read")
+    if getattr(args, "loss", "bce") != "bce":
+        no("--loss %s" % args.loss, "the contrastive loss is the step's loss")
+    if getattr(args, "pos_weight", None) is not None:
+        no("--pos_weight", "the labels are not read")
+    if getattr(args, "uncertain", "ones") == "multiclass":
+        no("--uncertain multiclass", "its head of three outputs per finding is a classifier's, the contrastive head is a projection")
+    if getattr(args, "head", None) in ("csra", "pcam"):
+        no("--head %s" % args.head, "the projection is the linear head")
+    if world > 1:
+        no("more than one rank (world size %d)" % world, "each rank would contrast its own rows only; gathering embeddings is not built")
+    proj = 128 if proj is None else proj
+    if not 1 <= proj <= NTXENT_MAX_D:
+        raise ValueError("--proj_dim takes 1 .. %d (got %r)" % (NTXENT_MAX_D, proj))
+    if 2 * args.batch_size > NTXENT_MAX_N:
+        raise ValueError("--pretrain contrastive sees 2 x --batch_size rows per step, at most %d (got 2 x %d)" % (NTXENT_MAX_N, args.batch_size))
+    if tau is not None:
+        check_temperature("--temperature", tau)
+    positive = positive or "view"
+    if positive != "view" and getattr(args, "synthetic", 0):
+        raise ValueError("--positive %s groups the images by their file paths; --synthetic images have none (use view)" % positive)
+    return {"proj_dim": int(proj), "temperature": tau, "positive": positive}
+
+
+def temperature_of(pretrain, restored_loss=None):
+    """The temperature of a pretraining run: --temperature, else a restored checkpoint's, else 0.2."""
+    if pretrain["temperature"] is not None:
+        return float(pretrain["temperature"])
+    return float((restored_loss or {}).get("temperature", 0.2))
+
+
+def check_checkpoint_pretrain(ck, pretrain, path, weight_key=None):
+    """A checkpoint of --pretrain contrastive continues such a run and nothing else (its head is a projection: --init_backbone takes
+    its backbone into a supervised run); a supervised checkpoint does not continue a pretraining run.  weight_key: the state_dict key
+    of the classifier's weight (classifier_keys), whose rows are the checkpoint's --proj_dim."""
+    stored = ck.get("pretrain")
+    if stored is not None and pretrain is None:
+        raise ValueError("--restore %s: the checkpoint is one of --pretrain %s, whose head is a projection: continue it with --pretrain "
+                         "%s, or start a supervised run from its backbone with --init_backbone" % (path, stored, stored))
+    if stored is None and pretrain is not None:
+        raise ValueError("--restore %s: the checkpoint is a supervised one; --pretrain contrastive continues a pretraining run (its "
+                         "backbone can start one: --init_backbone)" % path)
+    if stored is not None and weight_key is not None and weight_key in ck["state_dict"]:
+        width = ck["state_dict"][weight_key].shape[0]
+        if width != pretrain["proj_dim"]:
+            raise ValueError("--restore %s: the checkpoint's projection has %d outputs, --proj_dim asks for %d" % (path, width, pretrain["proj_dim"]))
+
+
+POOL_KEYS = ("pool_p", "pool_r")         # the pooling's own numbers: GeM's trained exponent, log-sum-exp's sharpness (FusedNet.set_pool)
+
+
+def classifier_keys(model):
+    """(weight, bias): the state_dict keys of the classifier, the last nn.Linear of every family."""
+    last = [name for name, m in model.named_modules() if isinstance(m, nn.Linear)][-1]
+    return last + ".weight", last + ".bias"
+
+
+def backbone_state(model_sd, ckpt_sd, head_keys, path="", free=POOL_KEYS):
+    """What --init_backbone loads: for every key of the model's state_dict outside `head_keys` the checkpoint's tensor.  A key the
+    checkpoint lacks, one of another shape, or one the model has no place for is a ValueError that names it.  The keys of `free` --
+    the pooling's numbers, which exist only under some --pool -- are taken where both sides hold them in one shape (a GeM exponent
+    trained during pretraining goes on into a --pool gem run) and left alone otherwise: --pool stays free."""
+    out = {}
+    for k, v in model_sd.items():
+        if k in head_keys:
+            continue
+        if k in free:
+            if k in ckpt_sd and tuple(ckpt_sd[k].shape) == tuple(v.shape):
+                out[k] = ckpt_sd[k]
+            continue
+        if k not in ckpt_sd:
+            raise ValueError("--init_backbone %s: the checkpoint has no tensor %r (another --model?)" % (path, k))
+        if tuple(ckpt_sd[k].shape) != tuple(v.shape):
+            raise ValueError("--init_backbone %s: tensor %r has shape %s in the checkpoint, %s in this model"
+                             % (path, k, tuple(ckpt_sd[k].shape), tuple(v.shape)))
+        out[k] = ckpt_sd[k]
+    for k in ckpt_sd:
+        if k not in model_sd and k not in head_keys and k not in free:
+            raise ValueError("--init_backbone %s: this model has no place for the checkpoint's tensor %r (another --model?)" % (path, k))
+    return out
+
+
+def init_backbone(model, path, device):
+    """--init_backbone: the checkpoint's backbone (BatchNorm's running statistics included) into the model; the classifier, the step,
+    the optimiser state and the loss state stay this run's.  Returns the keys loaded."""
+    ck = torch.load(path, map_location=device)
+    if not isinstance(ck, dict) or "state_dict" not in ck:
+        raise ValueError("--init_backbone %s: not a checkpoint of this command line (no state_dict)" % path)
+    own = model.state_dict()
+    taken = backbone_state(own, ck["state_dict"], set(classifier_keys(model)), path)
+    with torch.no_grad():
+        for k, v in taken.items():
+            own[k].copy_(v)
+    return sorted(taken)
+
+
 def head_width(args):
-    """Outputs of the classifier: --n_classes findings, three logits each under --uncertain multiclass."""
+    """Outputs of the classifier: --n_classes findings, three logits each under --uncertain multiclass; under --pretrain contrastive
+    the width of the projection, --proj_dim."""
+    if getattr(args, "pretrain", None) is not None:
+        return getattr(args, "proj_dim", None) or 128
     return args.n_classes * (3 if getattr(args, "uncertain", "ones") == "multiclass" else 1)
 
 
@@ -1332,11 +1515,12 @@ def save_checkpoint(ckpt, optim_state, sched_state, args, max_records=10):
         torch.save(ckpt, os.path.join(d, "best_checkpoints", "checkpoint_%d.pt" % file_id))
 
 
-def restore(args, model, optimizer, scheduler, device, multiclass=False):
+def restore(args, model, optimizer, scheduler, device, multiclass=False, pretrain=None):
     """chexpert.py:504-518: model weights + step from the file; when training also `optim_<name>` / `sched_<name>` beside it.
     Returns the checkpoint's `loss_state` entry (FusedNet.loss_state() of a --loss aucm, focal or asl or --uncertain multiclass run),
     or None.  A checkpoint whose head is not this run's (`multiclass`) is refused (ValueError) before anything is loaded."""
     ck = torch.load(args.restore, map_location=device)
+    check_checkpoint_pretrain(ck, pretrain, args.restore, classifier_keys(model)[0])
     check_checkpoint_head(ck, multiclass, args.restore)
     check_checkpoint_pool(ck, model, args.restore)
     check_checkpoint_head_kind(ck, model, args.restore)
@@ -1396,6 +1580,8 @@ def check_flags(argv=None):
     run.focus = focus_options(args)
     run.multiclass = multiclass_options(args)
     run.hier = hier_options(args)
+    init_backbone_options(args)
+    run.pretrain = pretrain_options(args, run.world)
     run.pool = resolve_pool(args)
     run.head = resolve_head(args, run.pool)
     return run
@@ -1509,12 +1695,16 @@ def build_model(run):
     run.model, run.optimizer, run.scheduler = make_model(args, run.device, run.pool, run.head)
     run.restored_loss = None
     if args.restore and os.path.isfile(args.restore):
-        run.restored_loss = restore(args, run.model, run.optimizer, run.scheduler, run.device, run.multiclass)
+        run.restored_loss = restore(args, run.model, run.optimizer, run.scheduler, run.device, run.multiclass, run.pretrain)
         adopted = run.hier is None
         run.hier = hier_for_checkpoint(run.hier, run.restored_loss, args.restore, args.train)
         if adopted and run.hier is not None and run.hier["closure"]:   # an evaluation of a --loss hier checkpoint without the flag: the
             from .data import hierarchy_closure                        # validation table as that run saw it
             run.valid_ds.targets = hierarchy_closure(run.valid_ds.targets, run.hier["parent"])
+    if getattr(args, "init_backbone", None):
+        keys = init_backbone(run.model, args.init_backbone, run.device)
+        if run.rank == 0:
+            print("--init_backbone %s: %d tensors loaded, the classifier is this run's" % (args.init_backbone, len(keys)))
     run.collapse = run.hier["parent"] if run.hier is not None else run.multiclass       # what evaluate() does to a forward's output
 
 
@@ -1529,6 +1719,15 @@ def wire_loss(run):
     args, model, pos_weight, restored_loss = run.args, run.model, run.pos_weight, run.restored_loss
     focus, hier, aucm = run.focus, run.hier, run.aucm
     criterion = summed_bce
+    if run.pretrain is not None:
+        # the fused step's loss and, by the same kernels, the autograd route's; one storage for the temperature: the module reads what
+        # the model holds.  --temperature has the last word, else a restored checkpoint's value
+        from .loss import NTXentLoss
+        tau = temperature_of(run.pretrain, restored_loss)
+        model.set_loss(kind="ntxent", temperature=tau)
+        criterion = NTXentLoss(tau)
+        criterion.temperature = model.loss_temperature
+        return criterion, None, None
     if focus is not None:
         # the fused step's loss and, by the same kernel, the autograd route's; a restored checkpoint of the same kind brings its four
         # numbers (loss_focus: a schedule may have moved them), one of another kind is refused
@@ -1623,8 +1822,25 @@ def jitter(x_u8, step, rank, device):
                          (u[2] > 0.5).to(torch.int32).to(device))
 
 
-def preprocess(run, affine, mix, x, t, step):
-    """The chain on the uint8 minibatch of training step `step`, every link optional."""
+def two_views(run, affine, x, idx, step, groups=None):
+    """--pretrain contrastive: the uint8 minibatch, equalised once, as [x; x] with an own affine / jitter draw for each of the 2B rows,
+    and the (2B, 1) ids of the contrastive loss (augment.contrastive_ids: the row's position, or its study / patient)."""
+    from .augment import contrastive_ids, duplicate_views
+    if run.clahe is not None:
+        x = run.clahe(x)
+    x = duplicate_views(x)
+    if affine is not None:
+        x = affine(x, step)
+    if run.args.jitter:
+        x = jitter(x, step, run.rank, run.device)
+    return x, contrastive_ids(idx, groups).to(run.device)
+
+
+def preprocess(run, affine, mix, x, t, step, idx=None):
+    """The chain on the uint8 minibatch of training step `step`, every link optional.  Under --pretrain contrastive the minibatch
+    becomes its two views and the target the column of ids (two_views)."""
+    if run.pretrain is not None:
+        return two_views(run, affine, x, idx, step, run.positive_groups)
     if run.clahe is not None:                   # deterministic preprocessing first, then the random steps
         x = run.clahe(x)
     if affine is not None:                      # geometric first, photometric second
@@ -1640,6 +1856,8 @@ def autograd_step(run, x, t):
     """The step without --fused_optimizer: torch's optimiser (and scheduler) over the autograd route of the fused network."""
     args, optimizer, scheduler, aucm_loss, aucm_opt = run.args, run.optimizer, run.scheduler, run.aucm_loss, run.aucm_opt
     out = run.model(x)
+    if run.pretrain is not None:            # (what log_line's top1 reads)
+        run.last_logits = out.detach()
     if aucm_loss is not None:
         loss = aucm_loss(out, t)
         aucm_opt.zero_grad()
@@ -1660,6 +1878,9 @@ def log_line(run, loss):
     """What a --log_interval step prints, as a dict.  (loss.item() synchronises; the optimiser's figures then read the device.)"""
     ex, optimizer = run.ex, run.optimizer
     line = {"step": run.args.step, "train_loss": round(loss.item(), 5)}
+    if run.pretrain is not None:            # the share of this minibatch's anchors whose nearest row is a positive
+        from .loss import contrastive_top1
+        line["top1"] = round(contrastive_top1(run.last_logits, run.last_ids), 4)
     if ex.get("max_grad_norm") is not None or ex.get("skip_nonfinite"):
         line["grad_norm"] = round(optimizer.grad_norm(), 5)
         if optimizer.skipped_steps():
@@ -1677,14 +1898,17 @@ def checkpoint_dict(run, res, ema_sd):
     """The model checkpoint after the evaluation `res`, with the entries only some runs have."""
     model, hier = run.model, run.hier
     ckpt = {"global_step": run.args.step, "eval_loss": float(np.sum(list(res["loss"].values()))),
-            "avg_auc": M.mean_auc(res), "state_dict": model.state_dict()}
+            "avg_auc": M.mean_auc(res) if run.pretrain is None else 0.0, "state_dict": model.state_dict()}
     if model.pool_kind != "avg":  # (a checkpoint without it is the average's: the keys of before)
         ckpt["pool_state"] = model.pool_state()
     if model.head_kind != "linear":
         ckpt["head_state"] = model.head_state()
     if ema_sd is not None:        # beside the live weights, which restore continues from
         ckpt["ema_state_dict"] = ema_sd
-    if run.aucm is not None:      # the auxiliary scalars are trained state: restore continues from them
+    if run.pretrain is not None:  # eval_loss is the contrastive loss; avg_auc = -eval_loss: save_checkpoint keeps the lowest-loss files
+        ckpt["pretrain"], ckpt["avg_auc"] = "contrastive", -ckpt["eval_loss"]
+        ckpt["loss_state"] = dict(model.loss_state(), positive=run.pretrain["positive"])
+    elif run.aucm is not None:    # the auxiliary scalars are trained state: restore continues from them
         sync_loss_aux(model, run.aucm_loss)
         ckpt["loss_state"] = model.loss_state()
     elif run.focus is not None or run.multiclass or hier is not None:      # the loss's numbers: restore checks the kind and puts them back
@@ -1694,12 +1918,41 @@ def checkpoint_dict(run, res, ema_sd):
     return ckpt
 
 
+EVAL_VIEW_STEP = 1 << 30          # the "step" the validation views of --pretrain contrastive are drawn from: minibatch b uses this + b
+
+
+@torch.no_grad()
+def contrastive_eval(run):
+    """--pretrain contrastive at an evaluation: the contrastive loss (the mean over the anchors of the whole set, each contrasted within
+    its minibatch of two views) and the top-1 share over the validation set, in eval mode, from views drawn from a fixed seed.
+    Printed, written to pretrain_eval_step_<n>.json, and returned in the shape checkpoint_dict reads ({"loss": {...}})."""
+    from .loss import contrastive_top1
+    args, model = run.args, run.model
+    model.eval()
+    codes = positive_codes(run.pretrain["positive"], run.valid_ds)          # (`batches` yields positions)
+    total, hits, anchors = 0.0, 0, 0
+    for b, (x, _, idx) in enumerate(batches(run.valid_ds, list(range(len(run.valid_ds))), args.batch_size, False)):
+        x, ids = two_views(run, run.affine, x.to(run.device), idx, EVAL_VIEW_STEP + b, codes)
+        out = model(x)
+        le = run.criterion.elementwise(out, ids)
+        h, a = contrastive_top1(out, ids, return_counts=True)
+        total, hits, anchors = total + float(le.sum().item()), hits + h, anchors + a
+    res = {"pretrain": "contrastive", "step": args.step, "loss": {"contrastive": total / max(anchors, 1)},
+           "top1": hits / max(anchors, 1), "anchors": anchors, "temperature": float(model.loss_temperature.item()),
+           "positive": run.pretrain["positive"]}
+    if run.rank == 0:
+        print("Evaluate contrastive pretraining @ step %d: loss %.5f, top1 %.4f over %d anchors" % (args.step, res["loss"]["contrastive"],
+                                                                                                 res["top1"], anchors))
+        json.dump(res, open(os.path.join(args.output_dir, "pretrain_eval_step_%d.json" % args.step), "w"), indent=4)
+    return res
+
+
 def evaluate_and_checkpoint(run, graphed):
     """An --eval_interval step: the validation metrics under the averaged weights and, on rank 0, the checkpoint files."""
     model, optimizer, scheduler = run.model, run.optimizer, run.scheduler
     ema_sd = None
     with averaged_weights(run):
-        res = M.compute_metrics(*validate(run))
+        res = M.compute_metrics(*validate(run)) if run.pretrain is None else contrastive_eval(run)
         if run.ex.get("ema_decay") is not None and run.rank == 0:
             ema_sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
     if run.rank == 0:
@@ -1715,10 +1968,14 @@ def train(run):
     replayed from the graph captured on the first full minibatch, launched one by one on the device-resident state for a partial
     minibatch of a graphed run, or launched with the host's learning rate and scheduler."""
     args, model, optimizer, scheduler, rank, world, device = run.args, run.model, run.optimizer, run.scheduler, run.rank, run.world, run.device
-    affine = make_affine(args, rank, device)
+    affine = run.affine = make_affine(args, rank, device)
     mix = make_mix(args, rank, device)
+    run.positive_groups = None
+    if run.pretrain is not None:                  # --positive study | patient: the index of every training row's study / patient,
+        run.positive_groups = positive_codes(run.pretrain["positive"], run.train_ds, by_label=True)      # by the loader's row label
     fused = args.fused_optimizer
     gstep = None
+    full = args.batch_size * (2 if run.pretrain is not None else 1)     # rows of a full minibatch as the step sees it
     if world > 1:            # replicas start identical (parameters, buffers) and average their gradients inside backward from
         model._eng().bind(device)                 # the first step on: bind the flat buffers now, before any optimiser state exists
         P.broadcast_module_state(model)
@@ -1731,21 +1988,22 @@ def train(run):
         t_epoch = time.perf_counter()
         # every image is seen each epoch, as with the reference's DataLoader (drop_last=False, chexpert.py:76): the last,
         # partial minibatch runs as an eager step (the hipGraph is captured on the full batch's shapes)
-        for x, t, _ in run.train_loader.batches(idx, drop_last=False):
+        for x, t, rows in run.train_loader.batches(idx, drop_last=False):
             args.step += 1
-            x, t = preprocess(run, affine, mix, x, t, args.step)
-            if args.graph and fused and (gstep is not None or x.shape[0] == args.batch_size):
+            x, t = preprocess(run, affine, mix, x, t, args.step, rows)
+            run.last_ids = t
+            if args.graph and fused and (gstep is not None or x.shape[0] == full):
                 if gstep is None:                       # captured on the first full minibatch's shapes
                     # (data-parallel: graph segments cut at the gradient buckets, the all-reduces enqueued between them)
                     from .graph import GraphedTrainStep, SegmentedTrainStep
                     gstep = (GraphedTrainStep if world == 1 else SegmentedTrainStep)(model, optimizer, x, t,
                                                                                       warmup_steps=int(args.lr_warmup_steps))
-                if x.shape[0] == args.batch_size:
-                    loss, _ = gstep.replay(x, t)
+                if x.shape[0] == full:
+                    loss, run.last_logits = gstep.replay(x, t)
                 else:                                   # same device-resident optimiser / scheduler state, launched one by one
-                    loss, _ = optimizer.train_step(model, x, t, dev=True)
+                    loss, run.last_logits = optimizer.train_step(model, x, t, dev=True)
             elif fused:
-                loss, _ = optimizer.train_step(model, x, t)         # chexpert.py:159-163 as one fused schedule
+                loss, run.last_logits = optimizer.train_step(model, x, t)         # chexpert.py:159-163 as one fused schedule
                 if scheduler == "fused" and args.step >= args.lr_warmup_steps:
                     optimizer.scheduler_step()
             else:
@@ -1762,7 +2020,11 @@ def train(run):
             print(json.dumps({"epoch": epoch, "images_per_sec": round(len(idx) * world / (time.perf_counter() - t_epoch), 1),
                               "loader_workers": args.num_workers,
                               "decoded_cache_fill": round(run.train_ds.cache_fill(), 3) if hasattr(run.train_ds, "cache_fill") else None}), flush=True)
-        run_eval(run, "eval_results_step_%d" % args.step)
+        if run.pretrain is None:
+            run_eval(run, "eval_results_step_%d" % args.step)
+        else:
+            with averaged_weights(run):
+                contrastive_eval(run)
 
 
 def evaluate_ensemble(run):
@@ -1772,6 +2034,7 @@ def evaluate_ensemble(run):
     outs, losses, members = [], [], []
     for c in checkpoint_files(args.restore):
         ck = torch.load(os.path.join(args.restore, c), map_location=run.device)
+        check_checkpoint_pretrain(ck, None, c)
         check_checkpoint_head(ck, run.multiclass, c)
         check_member_hier(run.hier, ck, c)
         check_checkpoint_pool(ck, model, c)

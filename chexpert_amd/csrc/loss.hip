@@ -10,6 +10,8 @@
 //                                                           cross-entropy of the product of sigmoids along a path; the collapse
 //   cx_softmax_ce_fwd_bwd                                   one wave per sample, its own final sum
 //   cx_aucm_fwd_bwd, cx_aucm_aux_step                       a function of each class's whole batch column: column trees, two passes
+//   cx_ntxent_fwd_bwd                                       the contrastive loss on (N, d) embeddings, which couples the rows: the one
+//                                                           exception to the single workgroup, three launches of a workgroup per row
 #include "common.h"
 
 #include <climits>
@@ -612,7 +614,221 @@ __global__ void aucm_aux_step_kernel(float* __restrict__ aux, const float* __res
   aux[2 * n + k] = fmaxf(aux[2 * n + k] + lr * daux[2 * n + k], 0.f);
 }
 
+// ---- NT-Xent / SupCon -----------------------------------------------------------------------------------------------------------
+// The contrastive loss over the (N, d) embeddings of a step (include/chexpert_hip.h, cx_ntxent_fwd_bwd): the one loss here that
+// couples the ROWS of a batch.  Row i with id g_i >= 0 is in the batch (V); its positives P(i) are the other rows of V with its id,
+// its candidates A(i) all other rows of V; l_i = lse_i - mean_{p in P(i)} s_ip over the rows with a positive (the anchors), with
+// s_ij = z_i . z_j / tau and z = e / max(|e|, 1e-12).  N is a few hundred, so the N x N similarities are some ten MFLOP: fp32 on the
+// VALU, and never stored -- three launches over the caller's scratch of N d + 4 N floats (z | norm | lse | 1/|P| | l):
+//   ntx_norm_kernel   one wave per row: |e_i|, z_i (zeros for a row outside V, so that it cannot reach another row's sums)
+//   ntx_row_kernel    one workgroup per row i: the row s_i. into LDS (one wave per j, d split over its lanes), then row maximum and
+//                     top-1, sum of exponentials relative to the maximum, |P(i)| and the positives' sum; writes lse_i, 1/|P(i)|, l_i
+//   ntx_grad_kernel   one workgroup per row i: the anchor count M and (workgroup 0) the loss = sum l / M in double; the coefficients
+//                     c_j = dS_ij + dS_ji into LDS, dS_ij = [i anchor](exp(s_ij - lse_i) - [j in P(i)] / |P(i)|) and dS_ji the same
+//                     from s_ij (s is symmetric, and ntx_wave_dot gives s_ij = s_ji bit for bit), lse_j and |P(j)|;
+//                     dz_i = sum_j c_j z_j / (tau M) with consecutive threads on consecutive k; the step back through the normalisation
+// Every sum has a fixed order (a lane's ascending k, a xor butterfly, trees over LDS, ascending j): no atomics, the same bits on every
+// run, and no output depends on which others were asked for.  tau is read from memory: a captured step sees it rewritten in place.
+constexpr int NTX_MAX_N = CX_NTXENT_MAX_N, NTX_MAX_D = CX_NTXENT_MAX_D, NTX_WAVES = NT / 64;
+constexpr float NTX_EPS = 1e-12f;
+
+// a . b by one wave: lane l adds k = l, l + 64, ... in ascending k, then a xor butterfly, after which every lane holds the sum.  The
+// products and the additions commute, so the value is the same with a and b exchanged.
+__device__ __forceinline__ float ntx_wave_dot(const float* a, const float* __restrict__ b, const int d, const int lane) {
+  float acc = 0.f;
+  for (int k = lane; k < d; k += 64) acc = fmaf(a[k], b[k], acc);
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  return acc;
+}
+
+__global__ __launch_bounds__(NT) void ntx_norm_kernel(const float* __restrict__ e, const float* __restrict__ ids, float* __restrict__ z,
+                                                      float* __restrict__ nrm, int N, int d) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * NTX_WAVES + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const float* er = e + (size_t)row * d;
+  const float n = sqrtf(ntx_wave_dot(er, er, d, lane));
+  const float den = fmaxf(n, NTX_EPS);
+  const bool in = ids[row] >= 0.f;
+  for (int k = lane; k < d; k += 64) z[(size_t)row * d + k] = in ? er[k] / den : 0.f;
+  if (lane == 0) nrm[row] = n;
+}
+
+__global__ __launch_bounds__(NT) void ntx_row_kernel(const float* __restrict__ z, const float* __restrict__ ids,
+                                                     const float* __restrict__ temperature, float* __restrict__ lse,
+                                                     float* __restrict__ invp, float* __restrict__ ell, float* __restrict__ loss_elem,
+                                                     int* __restrict__ top1, int N, int d) {
+  __shared__ float zi[NTX_MAX_D], srow[NTX_MAX_N], red_a[NT], red_b[NT];
+  __shared__ int red_i[NT];
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float gi = ids[i];
+  bool live = gi >= 0.f;
+  if (live) {                                     // (the branch is the workgroup's: gi is one value)
+    for (int k = tid; k < d; k += NT) zi[k] = z[(size_t)i * d + k];
+    __syncthreads();
+    const float tau = *temperature;
+    for (int j = wave; j < N; j += NTX_WAVES) {
+      const float dot = ntx_wave_dot(zi, z + (size_t)j * d, d, lane);
+      if (lane == 0) srow[j] = (j != i && ids[j] >= 0.f) ? dot / tau : -INFINITY;
+    }
+    __syncthreads();
+    float best = -INFINITY;                       // the row maximum and where it stands first; INT_MAX: nowhere yet
+    int bj = INT_MAX;
+    for (int j = tid; j < N; j += NT) {
+      const float s = srow[j];
+      if (s > best) { best = s; bj = j; }
+    }
+    red_a[tid] = best;
+    red_i[tid] = bj;
+    __syncthreads();
+    for (int h = NT / 2; h > 0; h >>= 1) {
+      if (tid < h) {
+        const float v = red_a[tid + h];
+        const int q = red_i[tid + h];
+        if (v > red_a[tid] || (v == red_a[tid] && q < red_i[tid])) { red_a[tid] = v; red_i[tid] = q; }
+      }
+      __syncthreads();
+    }
+    const float m = red_a[0];
+    const int top = red_i[0];
+    __syncthreads();
+    live = top != INT_MAX;                        // A(i) is empty: the only row of V
+    if (live) {
+      float se = 0.f, ps = 0.f;
+      int cnt = 0;
+      for (int j = tid; j < N; j += NT) {
+        const float s = srow[j];
+        se += expf(s - m);                        // (a row outside A(i) stands at -inf: 0)
+        if (j != i && ids[j] == gi) { ps += s - m; ++cnt; }
+      }
+      red_a[tid] = se;
+      red_b[tid] = ps;
+      red_i[tid] = cnt;
+      __syncthreads();
+      for (int h = NT / 2; h > 0; h >>= 1) {
+        if (tid < h) { red_a[tid] += red_a[tid + h]; red_b[tid] += red_b[tid + h]; red_i[tid] += red_i[tid + h]; }
+        __syncthreads();
+      }
+      if (tid == 0) {
+        const float lg = logf(red_a[0]);
+        const int P = red_i[0];
+        const float l = P > 0 ? lg - red_b[0] / (float)P : 0.f;       // lse_i - mean s_ip, both relative to the maximum
+        lse[i] = m + lg;
+        invp[i] = P > 0 ? 1.f / (float)P : 0.f;
+        ell[i] = l;
+        if (loss_elem) loss_elem[i] = l;
+        if (top1) top1[i] = top;
+      }
+    }
+  }
+  if (!live && tid == 0) {
+    lse[i] = 0.f;
+    invp[i] = 0.f;
+    ell[i] = 0.f;
+    if (loss_elem) loss_elem[i] = 0.f;
+    if (top1) top1[i] = -1;
+  }
+}
+
+__global__ __launch_bounds__(NT) void ntx_grad_kernel(const float* __restrict__ z, const float* __restrict__ nrm,
+                                                      const float* __restrict__ ids, const float* __restrict__ temperature,
+                                                      const float* __restrict__ lse, const float* __restrict__ invp,
+                                                      const float* __restrict__ ell, float* __restrict__ loss,
+                                                      float* __restrict__ dlogits, float grad_scale, int N, int d) {
+  __shared__ float zi[NTX_MAX_D], dzs[NTX_MAX_D], crow[NTX_MAX_N], part[NT];
+  __shared__ double red_d[NT];
+  __shared__ int red_i[NT];
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int cnt = 0;                                    // the anchors: every workgroup counts them for itself
+  double sum = 0.0;
+  for (int j = tid; j < N; j += NT) {
+    cnt += invp[j] > 0.f ? 1 : 0;
+    sum += ell[j];
+  }
+  red_i[tid] = cnt;
+  red_d[tid] = sum;
+  __syncthreads();
+  for (int h = NT / 2; h > 0; h >>= 1) {
+    if (tid < h) { red_i[tid] += red_i[tid + h]; red_d[tid] += red_d[tid + h]; }
+    __syncthreads();
+  }
+  const int M = red_i[0];
+  if (i == 0 && tid == 0 && loss) *loss = M > 0 ? (float)(red_d[0] / M) : 0.f;
+  if (!dlogits) return;
+  const float gi = ids[i];
+  if (!(gi >= 0.f) || M == 0) {                   // outside V, or a batch without an anchor: exactly 0
+    for (int k = tid; k < d; k += NT) dlogits[(size_t)i * d + k] = 0.f;
+    return;
+  }
+  for (int k = tid; k < d; k += NT) zi[k] = z[(size_t)i * d + k];
+  __syncthreads();
+  const float tau = *temperature, lse_i = lse[i], invp_i = invp[i];
+  for (int j = wave; j < N; j += NTX_WAVES) {
+    const float dot = ntx_wave_dot(zi, z + (size_t)j * d, d, lane);
+    if (lane == 0) {
+      float c = 0.f;
+      if (j != i && ids[j] >= 0.f) {
+        const float s = dot / tau, pos = ids[j] == gi ? 1.f : 0.f, invp_j = invp[j];
+        if (invp_i > 0.f) c += expf(s - lse_i) - pos * invp_i;
+        if (invp_j > 0.f) c += expf(s - lse[j]) - pos * invp_j;
+      }
+      crow[j] = c;
+    }
+  }
+  __syncthreads();
+  // dz_i: KW consecutive k at a time, the rows j dealt out to the NT / KW thread groups and the groups' sums added in group order
+  int KW = 64;
+  while (KW < d && KW < NT) KW <<= 1;
+  const int G = NT / KW, grp = tid / KW, c = tid % KW;
+  const float scale = 1.f / (tau * (float)M);
+  for (int k0 = 0; k0 < d; k0 += KW) {
+    const int k = k0 + c;
+    float acc = 0.f;
+    if (k < d) {
+#pragma unroll 8
+      for (int j = grp; j < N; j += G) acc = fmaf(crow[j], z[(size_t)j * d + k], acc);
+    }
+    part[tid] = acc;
+    __syncthreads();
+    if (grp == 0 && k < d) {
+      float t = part[c];
+      for (int h = 1; h < G; ++h) t += part[c + h * KW];
+      dzs[k] = t * scale;
+    }
+    __syncthreads();
+  }
+  // back through z = e / max(|e|, eps): (dz - (dz . z) z) / |e| above the clamp, dz / eps below it
+  double dp = 0.0;
+  for (int k = tid; k < d; k += NT) dp += (double)dzs[k] * zi[k];
+  red_d[tid] = dp;
+  __syncthreads();
+  for (int h = NT / 2; h > 0; h >>= 1) {
+    if (tid < h) red_d[tid] += red_d[tid + h];
+    __syncthreads();
+  }
+  const float n = nrm[i], den = fmaxf(n, NTX_EPS), proj = n >= NTX_EPS ? (float)red_d[0] : 0.f;
+  for (int k = tid; k < d; k += NT) dlogits[(size_t)i * d + k] = (dzs[k] - proj * zi[k]) / den * grad_scale;
+}
+
 }  // namespace
+
+long long cx_ntxent_scratch(int N, int d) {
+  if (N < 1 || d < 1 || N > NTX_MAX_N || d > NTX_MAX_D) return 0;
+  return (long long)N * d + 4ll * N;
+}
+
+int cx_ntxent_fwd_bwd(const float* e, const float* ids, const float* temperature, float* loss, float* loss_elem, float* dlogits,
+                      int* top1, float grad_scale, float* scratch, long long scratch_floats, int N, int d, void* stream) {
+  if (!e || !ids || !temperature || !scratch || N < 1 || d < 1) return CX_EINVAL;
+  if (N > NTX_MAX_N || d > NTX_MAX_D) return CX_ESHAPE;
+  if (scratch_floats < cx_ntxent_scratch(N, d)) return CX_EINVAL;
+  float *z = scratch, *nrm = z + (size_t)N * d, *lse = nrm + N, *invp = lse + N, *ell = invp + N;
+  hipLaunchKernelGGL(ntx_norm_kernel, dim3((N + NTX_WAVES - 1) / NTX_WAVES), dim3(NT), 0, as_stream(stream), e, ids, z, nrm, N, d);
+  hipLaunchKernelGGL(ntx_row_kernel, dim3(N), dim3(NT), 0, as_stream(stream), z, ids, temperature, lse, invp, ell, loss_elem, top1, N, d);
+  if (loss || dlogits)
+    hipLaunchKernelGGL(ntx_grad_kernel, dim3(dlogits ? N : 1), dim3(NT), 0, as_stream(stream), z, nrm, ids, temperature, lse, invp, ell,
+                       loss, dlogits, grad_scale, N, d);
+  return launch_status();
+}
 
 int cx_bce_fwd_bwd(const float* logits, const float* target, float* loss, float* loss_elem, float* dlogits, float grad_scale,
                    int B, int n_classes, void* stream) {

@@ -7,14 +7,19 @@ with its auxiliary scalars as parameters, FocalLoss and AsymmetricLoss for kinds
 MultiClassUncertain for kind "multiclass" (cx_mc3_fwd_bwd), the three-way softmax of the U-MultiClass policy, whose logits are (B, 3n)
 and which `collapse_multiclass` turns into binary ones (cx_mc3_collapse), HierarchicalBCE for kind "hier" (cx_hier_fwd_bwd), the
 conditional / unconditional loss over the findings' tree, whose conditional logits `collapse_hierarchy` turns into unconditional
-ones (cx_hier_collapse).  Device tensors only: there is no CPU path."""
+ones (cx_hier_collapse), NTXentLoss for kind "ntxent" (cx_ntxent_fwd_bwd), the contrastive NT-Xent / SupCon loss of (N, d)
+embeddings against an (N, 1) column of ids, the one loss that couples the rows of a batch; `reference_ntxent` states it in float64
+numpy and `contrastive_top1` is its accuracy figure.  Device tensors only: there is no CPU path (but for the numpy statement)."""
+import math
+
+import numpy as np
 import torch
 import torch.nn as nn
 
 from . import ops
 
 KERNEL = {"bce": "cx_bce_masked_fwd_bwd", "aucm": "cx_aucm_fwd_bwd", "focal": "cx_asl_fwd_bwd", "asl": "cx_asl_fwd_bwd",
-          "multiclass": "cx_mc3_fwd_bwd", "hier": "cx_hier_fwd_bwd"}
+          "multiclass": "cx_mc3_fwd_bwd", "hier": "cx_hier_fwd_bwd", "ntxent": "cx_ntxent_fwd_bwd"}
 WIDTH = {"multiclass": 3}          # logits per target element, where it is not 1
 
 
@@ -83,21 +88,35 @@ def check_hier_mode(who, mode):
     raise ValueError("%s takes mode 'conditional' or 'unconditional' (got %r)" % (who, mode))
 
 
+def check_temperature(who, temperature):
+    """The temperature of the contrastive loss as a float: finite and > 0."""
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError("%s takes a temperature, a number > 0 (got %r)" % (who, temperature))
+    if not 0 < t < float("inf"):
+        raise ValueError("%s takes a finite temperature > 0 (got %r)" % (who, temperature))
+    return t
+
+
 # ------------------------------------------------------------------------------------------------ the loss of a step
 class Loss:
-    """The loss of a step: `kind` ('bce', 'aucm', 'focal', 'asl', 'multiclass', 'hier'), `ignore_negative`, `margin` (a host float, passed
+    """The loss of a step: `kind` ('bce', 'aucm', 'focal', 'asl', 'multiclass', 'hier', 'ntxent'), `ignore_negative`, `margin` (a host float, passed
     by value), `mode` (kind 'hier': 'conditional' or 'unconditional', a host value like the margin, None elsewhere), `parent` (kind
     'hier': the int32 (n,) device table of each label's parent, -1 for a root) and the fp32 device tensors the kernels read -- `pos_weight` (n,), `focus` (4,) = [gamma+, gamma-, clip, alpha or -1],
     `aux` and `daux` (3, n) = rows a, b, alpha and their gradients, `prior` (n,), `lr_aux` (1,), `class_weight` (n, 3) = the weights
-    of kind 'multiclass', whose head has 3n outputs --, None where the kind has none.  Plain
+    of kind 'multiclass', whose head has 3n outputs, `temperature` (1,) of kind 'ntxent', whose logits are (N, d) embeddings and whose
+    target is the (N, 1) column of ids --, None where the kind has none.  Kind 'ntxent' also holds the kernels' scratch, sized by the
+    first launch that needs it (never under a graph capture: a captured step's warm-up runs have sized it).  Plain
     tensors, neither buffers nor parameters.  Behind them stands held storage (`_held`, by name) that outlives a change of kind: a
     repeated set() with the same sizes copies into it, so a captured step, which replays the storage it was captured with, sees the
     new values.  FusedNet keeps one (set / state / load_state are its set_loss / loss_state / load_loss_state); a loss module makes
     one per call from its own attributes."""
 
     def __init__(self, kind="bce", ignore_negative=False, margin=1.0, pos_weight=None, focus=None, aux=None, daux=None, prior=None,
-                 lr_aux=None, class_weight=None, parent=None, mode=None):
+                 lr_aux=None, class_weight=None, parent=None, mode=None, temperature=None):
         self.kind, self.ignore_negative, self.margin = kind, ignore_negative, margin
+        self.temperature = temperature
         self.parent, self.mode = parent, mode
         self.pos_weight, self.focus, self.aux, self.daux, self.prior, self.lr_aux = pos_weight, focus, aux, daux, prior, lr_aux
         self.class_weight = class_weight
@@ -108,7 +127,9 @@ class Loss:
         the kind's; for 'bce' the masked one when ignore_negative is set or there are weights (it skips every target < 0: the
         weighted loss has no arithmetic for a negative target), else the plain one, to which a negative target is a number.  Kind
         'multiclass' takes (B, 3n) logits and dlogits beside the (B, n) target and element losses."""
-        if self.kind == "aucm":
+        if self.kind == "ntxent":
+            ops.ntxent_fwd_bwd(logits, target, self.temperature, loss, loss_elem, dlogits, None, self._scratch(logits))
+        elif self.kind == "aucm":
             if loss_elem is not None:
                 raise RuntimeError("the AUC-margin loss has no element losses")
             ops.aucm_fwd_bwd(logits, target, self.prior, self.aux, self.margin, loss, None, dlogits, self.daux)
@@ -122,6 +143,18 @@ class Loss:
             ops.bce_masked_fwd_bwd(logits, target, self.pos_weight, loss, loss_elem, dlogits)
         else:
             ops.bce_fwd_bwd(logits, target, loss, loss_elem, dlogits)
+
+    def _scratch(self, logits):
+        """The held scratch of kind 'ntxent' for these (N, d) embeddings: made on first use and when it is too small or on another
+        device, which a stream under capture must not do."""
+        need = ops.ntxent_scratch(*logits.shape)
+        held = self._held.get("scratch")
+        if held is None or held.numel() < need or held.device != logits.device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the contrastive loss would allocate its scratch (%d floats) under a graph capture: run one step of "
+                                   "this batch size before capturing" % need)
+            held = self._held["scratch"] = torch.empty(need, dtype=torch.float32, device=logits.device)
+        return held
 
     def _hold(self, name, values, dev, keep=False, dtype=torch.float32):
         """`values` copied into the held storage `name`, which is made anew for another shape or another device; with `keep`,
@@ -138,7 +171,7 @@ class Loss:
         return held
 
     def _put(self, who, dev, kind, ignore_negative, pos_weight=None, focus=None, prior=None, margin=None, lr_aux=None,
-             class_weight=None, parent=None, mode=None):
+             class_weight=None, parent=None, mode=None, temperature=None):
         """The one place that writes the state, after every check: each field is assigned, to None where `kind` has none, so nothing
         of the previous kind is left over.  `aux` starts at zero coming from another kind and stays as trained coming from 'aucm';
         the margin stays what the last 'aucm' made it."""
@@ -151,15 +184,18 @@ class Loss:
         self.prior, self.lr_aux = self._hold("prior", prior, dev), self._hold("lr_aux", None if lr_aux is None else [lr_aux], dev)
         self.class_weight = self._hold("class_weight", class_weight, dev)
         self.parent, self.mode = self._hold("parent", parent, dev, dtype=torch.int32), mode
+        self.temperature = self._hold("temperature", None if temperature is None else [temperature], dev)
         self.kind, self.ignore_negative = kind, ignore_negative
         if margin is not None:
             self.margin = float(margin)
 
     def set(self, dev, n, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
-            alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None):
+            alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None, temperature=None):
         """FusedNet.set_loss for a model whose head has n outputs, with its parameters on dev.  A refused call changes nothing."""
         if kind not in KERNEL:
-            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal', 'asl', 'multiclass' or 'hier' (got %r)" % (kind,))
+            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal', 'asl', 'multiclass', 'hier' or 'ntxent' (got %r)" % (kind,))
+        if kind != "ntxent" and temperature is not None:
+            raise ValueError("set_loss: temperature belongs to kind='ntxent'")
         if kind != "hier" and (parent is not None or mode is not None):
             raise ValueError("set_loss: parent and mode belong to kind='hier'")
         if kind != "multiclass" and class_weight is not None:
@@ -188,6 +224,13 @@ class Loss:
             if n % 3:
                 raise ValueError("%s needs a head of three outputs per finding (negative, positive, uncertain); this head has %d" % (who, n))
             self._put(who, dev, kind, False, class_weight=check_class_weight(who, class_weight, n // 3))
+        elif kind == "ntxent":
+            if pos_weight is not None or ignore_negative:
+                raise ValueError("%s cannot be combined with pos_weight or ignore_negative: its target is a column of ids, of which a "
+                                 "negative one takes its row out of the batch" % who)
+            if n > ops.NTXENT_MAX_D:
+                raise ValueError("%s takes embeddings of at most %d values; this head has %d outputs" % (who, ops.NTXENT_MAX_D, n))
+            self._put(who, dev, kind, False, temperature=check_temperature(who, 0.2 if temperature is None else temperature))
         elif kind == "hier":
             if ignore_negative:
                 raise ValueError("%s always ignores a target < 0; ignore_negative is the cross-entropy's switch" % who)
@@ -221,6 +264,8 @@ class Loss:
             d["class_weight"] = cpu(self.class_weight)
         if self.kind == "hier":
             d["parent"], d["mode"] = cpu(self.parent), self.mode
+        if self.kind == "ntxent":
+            d["temperature"] = float(self.temperature.item())
         return d
 
     def load_state(self, d, dev, n):
@@ -246,6 +291,10 @@ class Loss:
             if d.get("parent") is None:
                 raise ValueError("load_loss_state: kind 'hier' needs parent, the table of the labels' parents")
             self.set(dev, n, kind="hier", parent=d["parent"], mode=d.get("mode"), pos_weight=self.pos_weight)   # (the held weights stay)
+        elif kind == "ntxent":
+            if d.get("temperature") is None:
+                raise ValueError("load_loss_state: kind 'ntxent' needs temperature")
+            self.set(dev, n, kind="ntxent", temperature=d["temperature"])
         elif kind != "bce":
             raise ValueError("load_loss_state: unknown loss kind %r" % (kind,))
         elif self.kind != "bce":               # (a model that holds the cross-entropy keeps its options)
@@ -254,10 +303,15 @@ class Loss:
 
 # ------------------------------------------------------------------------------------------------ the autograd route
 def _operands(logits, target, who, kind):
-    """The contiguous fp32 logits and targets of a loss module: (B, n) both, or (B, 3n) against (B, n) for kind 'multiclass'."""
+    """The contiguous fp32 logits and targets of a loss module: (B, n) both, or (B, 3n) against (B, n) for kind 'multiclass', or (N, d)
+    embeddings against an (N, 1) column of ids for kind 'ntxent'."""
     width = WIDTH.get(kind, 1)
     if not logits.is_cuda:
         raise RuntimeError("%s runs on the GPU only (%s); there is no CPU fallback" % (who, KERNEL[kind]))
+    if kind == "ntxent":
+        if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or tuple(target.shape) != (logits.shape[0], 1):
+            raise RuntimeError("%s takes (N, d) embeddings and an (N, 1) column of ids (got %s and %s)" % (who, tuple(logits.shape), tuple(target.shape)))
+        return logits.detach().contiguous().float(), target.detach().contiguous().float()
     if logits.dim() != 2 or logits.shape[1] % width or tuple(target.shape) != (logits.shape[0], logits.shape[1] // width):
         raise RuntimeError("%s takes %s (got %s and %s)" % (who, "(B, n) logits and targets of one shape" if width == 1 else
                                                             "(B, %dn) logits and (B, n) targets" % width, tuple(logits.shape), tuple(target.shape)))
@@ -497,3 +551,99 @@ def collapse_hierarchy(logits, parent, return_prob=False):
     else:
         ops.check_hier_parent("collapse_hierarchy", parent.cpu() if isinstance(parent, torch.Tensor) else parent, x.shape[1])
     return (z, p) if return_prob else z
+
+
+# ------------------------------------------------------------------------------------------------ contrastive pretraining
+NTXENT_EPS = 1e-12          # the clamp of the normalisation: z = e / max(|e|, eps)
+
+
+def reference_ntxent(e, ids, temperature, dtype=np.float64):
+    """The statement of cx_ntxent_fwd_bwd in numpy, in `dtype` (float64: the reference; float32: the model of the kernel's rounding
+    that the tests hold their tolerance against).  e (N, d), ids (N,) or (N, 1), temperature > 0.  With V = {i : ids_i >= 0},
+    z_i = e_i / max(|e_i|, 1e-12), s_ij = z_i . z_j / temperature, A(i) = V \\ {i} and P(i) = {j in A(i) : ids_j == ids_i}:
+    l_i = -(1 / |P(i)|) sum_{p in P(i)} (s_ip - log sum_{a in A(i)} exp s_ia) for the anchors (the rows of V with a positive), 0 for
+    every other row, loss = the mean of l_i over the anchors (0 without one).  Every id occurring twice: SimCLR's NT-Xent; otherwise
+    SupCon's L_out.  Returns {"loss": float, "loss_elem": (N,), "grad": (N, d) = d loss / d e through the normalisation,
+    "top1": (N,) int64, the a in A(i) with the largest s_ia (the lowest on a tie), -1 outside V or where A(i) is empty, "s": the (N, N)
+    similarities with -inf outside A(i), "anchors": the boolean (N,) mask, "p": the (N, N) softmax of s over A(i) in the anchors' rows
+    (0 elsewhere), "dS": d (M loss) / d s, row i the part that comes from l_i}."""
+    e = np.asarray(e, dtype=dtype)
+    g = np.asarray(ids, dtype=np.float64).reshape(-1)
+    N, d = e.shape
+    tau = dtype(temperature)
+    norm = np.sqrt((e * e).sum(1, dtype=dtype))
+    den = np.maximum(norm, dtype(NTXENT_EPS))
+    V = g >= 0
+    z = np.where(V[:, None], e / den[:, None], dtype(0))
+    A = V[:, None] & V[None, :] & ~np.eye(N, dtype=bool)
+    P = A & (g[:, None] == g[None, :])
+    s = np.where(A, (z @ z.T) / tau, -np.inf).astype(dtype)
+    nP = P.sum(1)
+    nPf = np.maximum(nP, 1).astype(dtype)
+    anchors = nP > 0
+    M = int(anchors.sum())
+    has = A.any(1)
+    top1 = np.where(has, np.argmax(np.where(has[:, None], s, 0), axis=1), -1)
+    m = np.where(has, np.max(np.where(has[:, None], s, 0), axis=1), dtype(0))
+    ex = np.where(A, np.exp(np.where(A, s - m[:, None], 0)), dtype(0)).astype(dtype)
+    se = ex.sum(1, dtype=dtype)
+    lg = np.log(np.where(has, se, 1)).astype(dtype)
+    ps = np.where(P, s - m[:, None], dtype(0)).sum(1, dtype=dtype)
+    ell = np.where(anchors, lg - ps / nPf, dtype(0)).astype(dtype)
+    p = np.where(anchors[:, None], ex / np.where(has, se, 1)[:, None], dtype(0)).astype(dtype)
+    dS = np.where(anchors[:, None], p - P / nPf[:, None], dtype(0)).astype(dtype)
+    out = {"loss_elem": ell, "top1": top1.astype(np.int64), "s": s, "anchors": anchors, "p": p, "dS": dS}
+    if M == 0:
+        out["loss"], out["grad"] = 0.0, np.zeros_like(e)
+        return out
+    out["loss"] = float(ell.sum(dtype=dtype) / dtype(M))
+    dz = ((dS + dS.T) @ z) / (tau * dtype(M))
+    above = (norm >= dtype(NTXENT_EPS))[:, None]
+    proj = np.where(above, (dz * z).sum(1, dtype=dtype)[:, None] * z, dtype(0))
+    out["grad"] = np.where(V[:, None], (dz - proj) / den[:, None], dtype(0)).astype(dtype)
+    return out
+
+
+class NTXentLoss(_LossModule):
+    """The contrastive loss of (N, d) embeddings against an (N, 1) column of ids: SimCLR's NT-Xent (Chen et al., ICML 2020) where every
+    id occurs exactly twice, SupCon's L_out (Khosla et al., NeurIPS 2020) otherwise; `reference_ntxent` is the definition.  Rows with
+    the same id >= 0 are each other's positives, every other row with an id >= 0 is a negative, a row with an id < 0 is out of the
+    batch.  The embeddings are normalised inside (z = e / max(|e|, 1e-12)) and the gradient goes back through that.  The loss of
+    FusedNet.set_loss(kind="ntxent") for the autograd route, by the same kernels, so `loss.backward()` leaves the fused step's d loss /
+    d logits bit for bit.  temperature: a finite number > 0; it lives in a one-float tensor (`temperature`) that may be rewritten in
+    place.  elementwise() gives the (N, 1) terms l_i, 0 for a row that is not an anchor."""
+    kind = "ntxent"
+
+    def __init__(self, temperature=0.2):
+        super().__init__()
+        self.temperature = torch.tensor([check_temperature("NTXentLoss", temperature)], dtype=torch.float32)
+        self._scratch = None
+
+    def _state(self, logits):
+        self._on(logits.device, "temperature")
+        state = Loss("ntxent", False, temperature=self.temperature)
+        if self._scratch is not None:
+            state._held["scratch"] = self._scratch
+        self._scratch = state._scratch(logits)               # (the module keeps it from call to call)
+        return state
+
+
+@torch.no_grad()
+def contrastive_top1(logits, ids, return_counts=False):
+    """The share of anchors -- rows with an id >= 0 that have a positive among the other rows -- whose nearest other row (the largest
+    cosine similarity; cx_ntxent_fwd_bwd's top1) is one of their positives: the accuracy figure of contrastive pretraining.  logits
+    (N, d) device embeddings, ids (N, 1) or (N,).  A float, NaN without an anchor; return_counts: (hits, anchors) as ints."""
+    x, t = _operands(logits, ids.reshape(-1, 1), "contrastive_top1", "ntxent")
+    top = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+    one = torch.ones(1, dtype=torch.float32, device=x.device)              # (the nearest row does not depend on the temperature)
+    ops.ntxent_fwd_bwd(x, t, one, None, None, None, top)
+    g = t.reshape(-1)
+    valid = g >= 0
+    same = (g[:, None] == g[None, :]) & valid[:, None] & valid[None, :]
+    anchors = (same.sum(1) - valid.long()) > 0
+    near = top.long().clamp(min=0)
+    hit = anchors & (top >= 0) & (g[near] == g)
+    hits, total = int(hit.sum().item()), int(anchors.sum().item())
+    if return_counts:
+        return hits, total
+    return hits / total if total else math.nan

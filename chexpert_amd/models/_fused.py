@@ -68,11 +68,22 @@ AUCM_DATA_PARALLEL = ("the AUC-margin loss (kind='aucm') is not supported data-p
                       "cross-entropy")
 
 
-def check_aucm_single_process(reducer):
-    """Raises when gradients are averaged over more than one rank (`reducer`: the engine's GradReducer, or None)."""
+NTXENT_DATA_PARALLEL = ("the contrastive loss (kind='ntxent') is not supported data-parallel (world size %d): each rank would contrast "
+                        "its own rows only, and gathering the embeddings across ranks (with the gradient's way back) has not been built "
+                        "-- pretrain on one GPU")
+
+
+def check_single_process(reducer, message):
+    """Raises RuntimeError(message % world size) when gradients are averaged over more than one rank (`reducer`: the engine's
+    GradReducer, or None): the losses that are not a sum over a rank's own elements."""
     world = getattr(reducer, "world", 1) if reducer is not None else 1
     if world > 1:
-        raise RuntimeError(AUCM_DATA_PARALLEL % world)
+        raise RuntimeError(message % world)
+
+
+def check_aucm_single_process(reducer):
+    """check_single_process for the AUC-margin loss."""
+    check_single_process(reducer, AUCM_DATA_PARALLEL)
 
 
 # --------------------------------------------------------------------------------------------- module side
@@ -123,7 +134,7 @@ class FusedNet(nn.Module):
         self._head_kind = "linear"       # set_head(): "csra" adds the buffer head_attn = [lambda, T]; "pcam" adds nothing
 
     def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
-                 alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None):
+                 alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None, temperature=None):
         """The loss of forward_backward.  ignore_negative: a target < 0 (an uncertain label kept as -1, the U-Ignore policy) adds no
         loss and no gradient; the divisor stays the batch size.  pos_weight: None, or n_classes positive-term weights as in torch's
         BCEWithLogitsLoss(pos_weight).  Either option routes the step through cx_bce_masked_fwd_bwd, which skips every target < 0:
@@ -192,10 +203,21 @@ class FusedNet(nn.Module):
         change of kind or from no pos_weight to weights, needs a new capture.  Nothing changes per step; the loss is a sum over
         elements with divisor B, so the data-parallel step reduces it as it does the cross-entropy.  At test time
         loss.collapse_hierarchy(logits, model.loss_parent) gives the unconditional logits; class_cam, Grad-CAM and heads.class_maps
-        work on the conditional logits as they are, so their maps show the evidence for a finding GIVEN its parent."""
+        work on the conditional logits as they are, so their maps show the evidence for a finding GIVEN its parent.
+
+        kind="ntxent" (temperature=0.2) is contrastive pretraining: the head's n outputs are an EMBEDDING (the classifier nn.Linear is
+        the projection), the target of forward_backward is an (N, 1) fp32 column of ids, and the loss is NT-Xent / SupCon over the rows
+        of the batch (cx_ntxent_fwd_bwd; the definition stands in include/chexpert_hip.h and, in numpy, in loss.reference_ntxent):
+        rows with the same id >= 0 are each other's positives, a row with an id < 0 is out of the batch.  pos_weight,
+        ignore_negative=True and every other kind's keyword are refused.  The temperature (finite, > 0) lives in one fp32 device
+        tensor, `loss_temperature`, under the storage rule of the weights: a repeated call copies into the held storage, and a
+        captured step's replay sees that, as it sees `model.loss_temperature.fill_(0.1)`.  The kernels' scratch is held with the loss
+        state and sized by the first step of a batch size (a capture's warm-up steps).  Both views of an image pass through the
+        network in ONE batch, so BatchNorm's statistics are shared between them, as in SimCLR.  The data-parallel step is refused:
+        the negatives would be each rank's own, and gathering embeddings across ranks is a feature of its own."""
         self._loss.set(next(self.parameters()).device, self._n_classes(), ignore_negative, pos_weight, kind=kind, prior=prior,
                        margin=margin, lr_aux=lr_aux, gamma=gamma, alpha=alpha, gamma_pos=gamma_pos, gamma_neg=gamma_neg, clip=clip,
-                       class_weight=class_weight, parent=parent, mode=mode)
+                       class_weight=class_weight, parent=parent, mode=mode, temperature=temperature)
         return self
 
     # ---- the global pooling in front of the classifier
@@ -400,7 +422,8 @@ class FusedNet(nn.Module):
         eval-mode step computes the gradients and leaves `loss_aux` alone.  After set_loss(kind="focal" | "asl") the loss is the
         focal / asymmetric loss (ops.asl_fwd_bwd), in either mode.  After set_loss(kind="multiclass") the logits are (B, 3n) against
         the (B, n) target and the loss is the three-way softmax cross-entropy per finding (ops.mc3_fwd_bwd), in either mode.  After
-        set_loss(kind="hier") the loss is the hierarchical one over the held parent table (ops.hier_fwd_bwd), in either mode.
+        set_loss(kind="hier") the loss is the hierarchical one over the held parent table (ops.hier_fwd_bwd), in either mode.  After
+        set_loss(kind="ntxent") the target is the (B, 1) column of ids and the loss the contrastive one over the rows (ops.ntxent_fwd_bwd).
         track_stats=False: a train-mode step computes with batch statistics as always, but writes no BatchNorm running statistic
         and counts no batch (the second pass of optim.FusedSAM); the launches are the same, the coefficient kernels get no running
         buffers."""
@@ -410,6 +433,8 @@ class FusedNet(nn.Module):
         L = self._loss
         if L.kind == "aucm":
             check_aucm_single_process(eng.reducer)
+        if L.kind == "ntxent":
+            check_single_process(eng.reducer, NTXENT_DATA_PARALLEL)
         eng.track_stats = bool(track_stats)
         try:
             ws = eng.forward(x, self.training, record=True)
@@ -428,7 +453,7 @@ class FusedNet(nn.Module):
 
 
 # what set_loss holds, readable on the model (read-only: set_loss writes; a tensor may be written in place)
-for _name in ("kind", "ignore_negative", "pos_weight", "margin", "aux", "prior", "lr_aux", "focus", "class_weight", "parent", "mode", "daux"):
+for _name in ("kind", "ignore_negative", "pos_weight", "margin", "aux", "prior", "lr_aux", "focus", "class_weight", "parent", "mode", "temperature", "daux"):
     setattr(FusedNet, ("_loss_" if _name == "daux" else "loss_") + _name, property(lambda self, _name=_name: getattr(self._loss, _name)))
 
 

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib as L
 from ._lib import (BOOT_MAX_POINTS, BOOT_MAX_TILES, BOOT_MAX_UNITS, BOOT_SENS, BOOT_SPEC, BOOT_TILE, CALIB_MAX_BINS, CALIB_MAX_ITER,
-                   CALIB_METHODS, DELONG_MAX_ROWS, DELONG_TILE, DELONG_WG_ENTRIES, EPI_JOIN, EPI_MASK, EPI_STORE, HIER_MAX_LABELS, HIER_MAX_PATH,
+                   CALIB_METHODS, DELONG_MAX_ROWS, DELONG_TILE, DELONG_WG_ENTRIES, EPI_JOIN, EPI_MASK, EPI_STORE, HIER_MAX_LABELS, HIER_MAX_PATH, NTXENT_MAX_D, NTXENT_MAX_N,
                    MODE_CONV, MODE_POOL2, MODE_STEM, PRO_AFFINE2, PRO_AFFINE_RELU, PRO_JOIN, PRO_NONE, CxConv, CxWgrad, check, lib, ptr, require_cuda, stream_ptr)
 import ctypes as C
 
@@ -812,6 +812,43 @@ def hier_collapse(logits, parent, z, p=None):
     require_cuda(logits, parent, z, p)
     check(lib().cx_hier_collapse(ptr(logits), ptr(parent), ptr(z), ptr(p), B, n, stream_ptr()), "cx_hier_collapse")
     return z
+
+
+def ntxent_scratch(N, d):
+    """The floats of scratch ntxent_fwd_bwd needs for (N, d) embeddings (cx_ntxent_scratch): N d + 4 N, for the normalised rows, their
+    norms, and each row's log-sum-exp, 1 / |P| and loss.  Sizes the loss refuses are a ValueError."""
+    N, d = int(N), int(d)
+    if not (1 <= N <= NTXENT_MAX_N and 1 <= d <= NTXENT_MAX_D):
+        raise ValueError("the contrastive loss takes 1 .. %d rows of 1 .. %d values (got %d x %d)" % (NTXENT_MAX_N, NTXENT_MAX_D, N, d))
+    return int(lib().cx_ntxent_scratch(N, d))
+
+
+def ntxent_fwd_bwd(logits, ids, temperature, loss, loss_elem, dlogits, top1=None, scratch=None, grad_scale=1.0):
+    """The NT-Xent / SupCon loss of the (N, d) embeddings with its exact gradient (cx_ntxent_fwd_bwd, three launches; the definition
+    stands in include/chexpert_hip.h): ids fp32 (N, 1), integer-valued, rows with the same id >= 0 are each other's positives and a
+    row with an id < 0 is out of the batch; temperature a one-float DEVICE tensor, read by the kernels (a captured step sees a changed
+    value).  loss (1,), loss_elem (N, 1), dlogits (N, d) and top1 (N,) int32 -- each row's nearest other row -- are optional;
+    grad_scale multiplies dlogits alone.  scratch: fp32, at least ntxent_scratch(N, d) floats (None: allocated here, which a graph
+    capture must not do -- hold one).  Returns the scratch."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    N, d = logits.shape
+    need = ntxent_scratch(N, d)
+    assert ids.dtype == torch.float32 and ids.is_contiguous() and tuple(ids.shape) == (N, 1)
+    assert temperature is not None and temperature.numel() == 1
+    assert loss_elem is None or tuple(loss_elem.shape) == (N, 1)
+    assert dlogits is None or tuple(dlogits.shape) == (N, d)
+    assert top1 is None or (top1.dtype == torch.int32 and top1.is_contiguous() and tuple(top1.shape) == (N,))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=logits.device)
+    assert scratch.dim() == 1 and scratch.numel() >= need
+    assert all(t is None or t.device == logits.device for t in (ids, temperature, loss, loss_elem, dlogits, top1, scratch))
+    _f32(loss, temperature, n=1)
+    _f32(loss_elem, dlogits)
+    _f32(scratch, n=scratch.numel())
+    require_cuda(logits, ids, temperature, loss, loss_elem, dlogits, top1, scratch)
+    check(lib().cx_ntxent_fwd_bwd(ptr(logits), ptr(ids), ptr(temperature), ptr(loss), ptr(loss_elem), ptr(dlogits), ptr(top1), grad_scale,
+                                  ptr(scratch), scratch.numel(), N, d, stream_ptr()), "cx_ntxent_fwd_bwd")
+    return scratch
 
 
 def softmax_ce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):

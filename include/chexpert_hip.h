@@ -448,6 +448,30 @@ int cx_hier_fwd_bwd(const float* logits, const float* target, const int* parent,
  * reduction; any B (a whole validation table in one call).  CX_EINVAL before anything is launched: NULL logits / parent / z, B < 1,
  * n < 1, n > CX_HIER_MAX_LABELS, B * n > INT_MAX - 256.                                                                             */
 int cx_hier_collapse(const float* logits, const int* parent, float* z, float* p, int B, int n, void* stream);
+/* NT-Xent / SupCon (Chen et al., "A Simple Framework for Contrastive Learning of Visual Representations", ICML 2020; Khosla et al.,
+ * "Supervised Contrastive Learning", NeurIPS 2020, L_out) on the (N, d) embeddings e of a step, with the exact d loss / d e, three launches
+ * (loss.hip).  ids: fp32 (N, 1) ON THE DEVICE, integer-valued (exact below 2^24); temperature: one fp32 value ON THE DEVICE, read by the
+ * kernels, so a captured step sees it rewritten in place.
+ *   V = {i : ids_i >= 0}; a row outside V is neither an anchor nor a negative: its element loss and its gradient row are 0, top1 is -1,
+ *     and its embedding reaches no other row's bits.
+ *   z_i = e_i / max(|e_i|, 1e-12);  s_ij = z_i . z_j / tau;  for i in V:  A(i) = V \ {i},  P(i) = {j in A(i) : ids_j == ids_i}
+ *   anchors: the rows of V with |P(i)| >= 1, M of them.  With m_i = max_{a in A(i)} s_ia:
+ *     lse_i = m_i + logf(sum_a expf(s_ia - m_i));   l_i = logf(sum_a expf(s_ia - m_i)) - sum_p (s_ip - m_i) / |P(i)|
+ *   loss = sum l_i / M (0 where M == 0, and then every gradient is 0);  loss_elem (N, 1) = l_i (0 for a row that is no anchor)
+ *   top1 (N,) int32 = the a in A(i) with the largest s_ia, the lowest such a on a tie; -1 outside V or where A(i) is empty
+ *   dS_ij = [i anchor] (expf(s_ij - lse_i) - [j in P(i)] / |P(i)|);   dz_i = sum_{j in A(i)} (dS_ij + dS_ji) z_j / (tau M)
+ *   dlogits (N, d) = (dz_i - (dz_i . z_i) z_i) / |e_i| * grad_scale where |e_i| >= 1e-12, dz_i / 1e-12 * grad_scale below the clamp
+ * Every id occurring exactly twice is SimCLR's NT-Xent.  fp32 on the VALU; every sum in a fixed order, no atomics: bit-reproducible, and
+ * each output alone has the bits it has beside the others.  loss, loss_elem, dlogits and top1 may each be NULL.  scratch: the caller's,
+ * cx_ntxent_scratch(N, d) = N d + 4 N floats (z | |e| | lse | 1 / |P| | l), nothing is allocated here.  CX_EINVAL before anything is
+ * launched: NULL e / ids / temperature / scratch, N < 1, d < 1, scratch_floats below cx_ntxent_scratch(N, d); CX_ESHAPE: N >
+ * CX_NTXENT_MAX_N or d > CX_NTXENT_MAX_D (the row of similarities and two d-vectors live in LDS).  cx_ntxent_scratch returns 0 for sizes
+ * the loss refuses.  |e_i|^2 is formed in fp32: embeddings beyond 1e18 overflow it.  Additive entry points of ABI 10.                */
+#define CX_NTXENT_MAX_N 4096
+#define CX_NTXENT_MAX_D 1024
+long long cx_ntxent_scratch(int N, int d);
+int cx_ntxent_fwd_bwd(const float* e, const float* ids, const float* temperature, float* loss, float* loss_elem, float* dlogits,
+                      int* top1, float grad_scale, float* scratch, long long scratch_floats, int N, int d, void* stream);
 /* loss = CrossEntropyLoss(logits, target) (mean over the batch of logsumexp - logit[target]);
  * dlogits = (softmax - onehot)/B * grad_scale; loss_elem (optional) = the per-sample terms
  * (models/test_model.py:118, :143, :331: the CIFAR harness criterion)                              */
