@@ -20,6 +20,7 @@ CALIB_MAX_ITER, CALIB_MAX_BINS = 1000, 64
 DELONG_MAX_ROWS, DELONG_WG_ENTRIES, DELONG_TILE = 128, 16384, 32   # 4 rows per class and model: two models of 16 classes
 HIER_MAX_LABELS, HIER_MAX_PATH = 64, 8                             # CX_HIER_MAX_LABELS, CX_HIER_MAX_PATH (loss.hip)
 NTXENT_MAX_N, NTXENT_MAX_D = 4096, 1024                            # CX_NTXENT_MAX_N, CX_NTXENT_MAX_D (loss.hip)
+KNN_MAX_K, KNN_MAX_D, KNN_MAX_SPLITS, KNN_MAX_CLASSES = 256, 4096, 256, 64   # CX_KNN_MAX_* (knn.hip)
 
 _vp, _fp, _i32 = C.c_void_p, C.c_void_p, C.c_int32
 
@@ -265,6 +266,10 @@ SIGNATURES = {
     "cx_copy_stream": [_vp, _vp, _sz, _vp],
     "cx_affine_to_f32_nchw": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "cx_bf16_to_f32_nchw": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "cx_knn_scratch": [_i, _i, _i, _i],
+    "cx_knn_normalize": [_vp, _vp, _i, _i, _vp],
+    "cx_knn_topk": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i, _i, _i, _vp],
+    "cx_knn_vote": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp],
 }
 
 _lib = None
@@ -287,7 +292,7 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = C.c_char_p if name in ("cx_error_string", "cx_last_kernel") else \
-                C.c_longlong if name in ("cx_csra_bwd_scratch", "cx_pcam_bwd_scratch", "cx_ntxent_scratch") else C.c_int
+                C.c_longlong if name in ("cx_csra_bwd_scratch", "cx_pcam_bwd_scratch", "cx_ntxent_scratch", "cx_knn_scratch") else C.c_int
         if l.cx_abi_version() != 10:
             raise RuntimeError("chexpert_amd: ABI version mismatch")
         _lib = l

@@ -175,6 +175,17 @@
                         pretrain_eval_step_<n>.json; the checkpoint carries loss_state, "pretrain": "contrastive" and eval_loss, and its
                         avg_auc is -eval_loss, so that the best_checkpoints are the lowest-loss ones.  --restore continues such a run and
                         is refused into a supervised one (and the other way round); the log line gains top1
+  --knn_probe K         the weighted k-nearest-neighbour probe of the backbone (Wu et al., CVPR 2018; chexpert_amd/knn.py, csrc/knn.hip): a bank
+                        of training images and the validation set are embedded with the frozen network in eval mode (FusedNet.embed: the
+                        pooled features the classifier reads; the deterministic preprocessing only, --clahe if set, no views), each
+                        validation image's K nearest bank rows by cosine similarity (1 <= K <= 256, cut to the bank's size) vote on its
+                        findings with weight exp(s / T), --knn_temperature T (default 0.1), and the AUROC per finding is reported.
+                        --knn_bank N (default 8192): the bank is N training images at an even stride, the same ones every time; 0 = the
+                        whole training set.  The bank's labels follow --uncertain / --labels, an ignored (-1) label does not vote.  With
+                        --pretrain contrastive every evaluation adds "knn": {k, temperature, bank, aucs, mean_auc} to
+                        pretrain_eval_step_<n>.json and prints one line (checkpoint selection stays by the contrastive loss); with
+                        --evaluate_single_model it writes knn_step_<n>.json beside eval_results_step_<n>.json, for any checkpoint.
+                        Needs one of the two modes, one rank and the linear head (not --head csra|pcam)
   --init_backbone FILE  with --train: every tensor of FILE's state_dict but the classifier's weight and bias (whatever their width) is loaded
                         before the first step, BatchNorm's running statistics included (the pooling's own numbers, GeM's exponent and
                         log-sum-exp's sharpness, where the checkpoint and this run's --pool both have them); the step, the
@@ -355,6 +366,11 @@ def build_parser():
     p.add_argument("--temperature", type=float, default=None, metavar="T", help="with --pretrain: temperature of the contrastive loss, > 0 (default 0.2)")
     p.add_argument("--positive", default=None, choices=["view", "study", "patient"],
                    help="with --pretrain: what counts as a positive -- the other view of the image (default), or every row of its study / patient")
+    p.add_argument("--knn_probe", type=int, default=None, metavar="K",
+                   help="with --pretrain contrastive or --evaluate_single_model: the weighted kNN probe of the pooled features, K neighbours (1 .. 256)")
+    p.add_argument("--knn_temperature", type=float, default=None, metavar="T", help="with --knn_probe: temperature of the vote's weights exp(s / T), > 0 (default 0.1)")
+    p.add_argument("--knn_bank", type=int, default=None, metavar="N",
+                   help="with --knn_probe: the bank is N training images at an even stride (default 8192); 0 = the whole training set")
     p.add_argument("--init_backbone", default=None, metavar="FILE",
                    help="with --train: load every tensor of FILE's state_dict but the classifier's before the first step (exclusive with --restore)")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
@@ -915,6 +931,49 @@ def pretrain_options(args, world=1):
     if positive != "view" and getattr(args, "synthetic", 0):
         raise ValueError("--positive %s groups the images by their file paths; --synthetic images have none (use view)" % positive)
     return {"proj_dim": int(proj), "temperature": tau, "positive": positive}
+
+
+KNN_DEFAULT_T, KNN_DEFAULT_BANK = 0.1, 8192
+
+
+def knn_options(args, world=1):
+    """--knn_probe and its flags checked before anything runs: None without it, else {"k", "temperature", "bank"} (bank 0: the whole
+    training set).  What the probe cannot run with is refused with a one-line reason (ValueError)."""
+    k, T, bank = getattr(args, "knn_probe", None), getattr(args, "knn_temperature", None), getattr(args, "knn_bank", None)
+    if k is None:
+        if T is not None or bank is not None:
+            raise ValueError("--knn_temperature / --knn_bank belong to --knn_probe K: pass it with them")
+        return None
+    from ._lib import KNN_MAX_K
+    if getattr(args, "pretrain", None) is None and not getattr(args, "evaluate_single_model", False):
+        raise ValueError("--knn_probe runs at the evaluations of --pretrain contrastive or with --evaluate_single_model: pass one of them")
+    if world > 1:
+        raise ValueError("--knn_probe cannot be combined with more than one rank (world size %d): gathering embeddings across ranks is "
+                         "not built" % world)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError("--knn_probe takes 1 .. %d neighbours (got %r)" % (KNN_MAX_K, k))
+    T = KNN_DEFAULT_T if T is None else T
+    if not (T > 0 and np.isfinite(T)):
+        raise ValueError("--knn_temperature must be finite and > 0 (got %r)" % (T,))
+    bank = KNN_DEFAULT_BANK if bank is None else bank
+    if bank < 0:
+        raise ValueError("--knn_bank takes a number of training images >= 0, 0 being all of them (got %r)" % (bank,))
+    if getattr(args, "head", None) in ("csra", "pcam"):
+        raise ValueError("--knn_probe cannot be combined with --head %s: that head pools per-class score maps and has no pooled feature "
+                         "vector" % args.head)
+    return {"k": int(k), "temperature": float(T), "bank": int(bank)}
+
+
+def knn_probe(run):
+    """The kNN probe of run.model (knn.probe) under the run's deterministic preprocessing, as the dictionary the reports carry."""
+    from . import knn
+    o = run.knn
+    return knn.probe(run.model, run.train_ds, run.valid_ds, o["k"], o["temperature"], o["bank"], run.args.batch_size, run.device, run.clahe)
+
+
+def print_knn(res, step):
+    print("kNN probe @ step %d: mean AUROC %.4f (k %d, T %g, bank %d)\n%s" % (step, res["mean_auc"], res["k"], res["temperature"], res["bank"],
+                                                                           pprint.pformat(res["aucs"])))
 
 
 def temperature_of(pretrain, restored_loss=None):
@@ -1582,6 +1641,7 @@ def check_flags(argv=None):
     run.hier = hier_options(args)
     init_backbone_options(args)
     run.pretrain = pretrain_options(args, run.world)
+    run.knn = knn_options(args, run.world)
     run.pool = resolve_pool(args)
     run.head = resolve_head(args, run.pool)
     return run
@@ -1803,7 +1863,11 @@ def run_eval(run, tag):
     args = run.args
     with averaged_weights(run):
         o, t, l = validate(run)
+        knn_res = knn_probe(run) if getattr(run, "knn", None) is not None else None
     res = M.compute_metrics(o, t, l)
+    if knn_res is not None and run.rank == 0:
+        print_knn(knn_res, args.step)
+        json.dump(knn_res, open(os.path.join(args.output_dir, report_name(tag, "knn")), "w"), indent=4)
     if run.rank == 0:
         print("Evaluate metrics @ step %d:\nAUC:\n%s\nLoss:\n%s" % (args.step, pprint.pformat(res["aucs"]), pprint.pformat(res["loss"])))
         json.dump(res, open(os.path.join(args.output_dir, tag + ".json"), "w"), indent=4)
@@ -1940,6 +2004,11 @@ def contrastive_eval(run):
     res = {"pretrain": "contrastive", "step": args.step, "loss": {"contrastive": total / max(anchors, 1)},
            "top1": hits / max(anchors, 1), "anchors": anchors, "temperature": float(model.loss_temperature.item()),
            "positive": run.pretrain["positive"]}
+    if getattr(run, "knn", None) is not None:
+        res["knn"] = knn_probe(run)
+        model.eval()
+        if run.rank == 0:
+            print_knn(res["knn"], args.step)
     if run.rank == 0:
         print("Evaluate contrastive pretraining @ step %d: loss %.5f, top1 %.4f over %d anchors" % (args.step, res["loss"]["contrastive"],
                                                                                                  res["top1"], anchors))

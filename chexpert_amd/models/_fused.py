@@ -411,6 +411,29 @@ class FusedNet(nn.Module):
         eng.release(ws)
         return out
 
+    def embed(self, x, return_logits=False):
+        """The (B, C) fp32 vector the classifier reads -- the pooled features of one eval-mode forward (a clone of the engine's
+        `pooled`, after set_pool's pooling of whichever kind) -- for the kNN probe and retrieval (chexpert_amd.knn).  The launches are
+        those of model(x); return_logits=True returns (features, logits) of that one forward, the logits bit for bit model(x)'s.  A
+        model in train mode is refused (batch statistics would make a row depend on its batch), as is a csra / pcam head, which has
+        no pooled vector."""
+        if not x.is_cuda:
+            raise RuntimeError("chexpert_amd %s runs on the GPU only (hand-written HIP kernels); there is no CPU fallback -- move "
+                               "the model and the input to cuda" % type(self).__name__)
+        if self.training:
+            raise RuntimeError("embed() needs the model in eval mode: with batch statistics a row's features would depend on its batch "
+                               "(call model.eval())")
+        if self._head_kind != "linear":
+            raise NotImplementedError("embed() needs the linear head: the %s head (set_head) pools per-class score maps and has no pooled "
+                                      "feature vector" % self._head_kind)
+        eng = self._eng()
+        with torch.no_grad():
+            ws = eng.forward(x, False)
+            feats = ws.pooled.clone()
+            logits = ws.logits.clone() if return_logits else None
+            eng.release(ws)
+        return (feats, logits) if return_logits else feats
+
     # fused training step (bench / trainer fast path; same arithmetic as chexpert.py:159-163)
     def forward_backward(self, x, target, input_grad=None, track_stats=True):
         """logits = model(x); loss = BCEWithLogits(logits, target).sum(1).mean(0); loss.backward().

@@ -11,6 +11,7 @@ import torch
 from . import _lib as L
 from ._lib import (BOOT_MAX_POINTS, BOOT_MAX_TILES, BOOT_MAX_UNITS, BOOT_SENS, BOOT_SPEC, BOOT_TILE, CALIB_MAX_BINS, CALIB_MAX_ITER,
                    CALIB_METHODS, DELONG_MAX_ROWS, DELONG_TILE, DELONG_WG_ENTRIES, EPI_JOIN, EPI_MASK, EPI_STORE, HIER_MAX_LABELS, HIER_MAX_PATH, NTXENT_MAX_D, NTXENT_MAX_N,
+                   KNN_MAX_CLASSES, KNN_MAX_D, KNN_MAX_K, KNN_MAX_SPLITS,
                    MODE_CONV, MODE_POOL2, MODE_STEM, PRO_AFFINE2, PRO_AFFINE_RELU, PRO_JOIN, PRO_NONE, CxConv, CxWgrad, check, lib, ptr, require_cuda, stream_ptr)
 import ctypes as C
 
@@ -849,6 +850,73 @@ def ntxent_fwd_bwd(logits, ids, temperature, loss, loss_elem, dlogits, top1=None
     check(lib().cx_ntxent_fwd_bwd(ptr(logits), ptr(ids), ptr(temperature), ptr(loss), ptr(loss_elem), ptr(dlogits), ptr(top1), grad_scale,
                                   ptr(scratch), scratch.numel(), N, d, stream_ptr()), "cx_ntxent_fwd_bwd")
     return scratch
+
+
+def knn_scratch(Q, M, k, splits=0):
+    """The floats of scratch knn_topk needs (cx_knn_scratch): Q x slices x k 64-bit keys, `splits` = 0 being the library's own choice of
+    slices.  Sizes the search refuses are a ValueError."""
+    Q, M, k, splits = int(Q), int(M), int(k), int(splits)
+    if not (Q >= 1 and 1 <= M < 2 ** 31 and 1 <= k <= KNN_MAX_K and 0 <= splits <= KNN_MAX_SPLITS):
+        raise ValueError("the search takes Q >= 1 queries, 1 <= M < 2^31 bank rows, 1 <= k <= %d and 0 <= splits <= %d (got Q %d, M %d, k %d, "
+                         "splits %d)" % (KNN_MAX_K, KNN_MAX_SPLITS, Q, M, k, splits))
+    return int(lib().cx_knn_scratch(Q, M, k, splits))
+
+
+def knn_normalize(x, y):
+    """y = x / max(|x|, 1e-12) per row of the (rows, d) fp32 matrix (cx_knn_normalize), the normalisation of the contrastive loss."""
+    assert x.dim() == 2 and y.shape == x.shape
+    _f32(x, y)
+    require_cuda(x, y)
+    rows, d = x.shape
+    if not 1 <= d <= KNN_MAX_D:
+        raise ValueError("rows of 1 .. %d values (got %d)" % (KNN_MAX_D, d))
+    if rows:
+        check(lib().cx_knn_normalize(ptr(x), ptr(y), rows, d, stream_ptr()), "cx_knn_normalize")
+    return y
+
+
+def knn_topk(q, bank, k, out_sim, out_idx, q_group=None, bank_group=None, scratch=None, splits=0):
+    """The k nearest bank rows of every query by inner product (cx_knn_topk; the order is defined in include/chexpert_hip.h): q (Q, d),
+    bank (M, d) fp32; out_sim (Q, k) fp32 and out_idx (Q, k) int32, descending, ties to the lower index, idx -1 / sim -inf where a query
+    has fewer than k candidates.  q_group / bank_group int32, both or neither: a bank row of the query's own group (>= 0) is no
+    candidate.  scratch: fp32, at least knn_scratch(Q, M, k, splits) floats (None: allocated here).  Returns the scratch."""
+    assert q.dim() == 2 and bank.dim() == 2 and q.shape[1] == bank.shape[1]
+    (Q, d), M = q.shape, bank.shape[0]
+    if not 1 <= d <= KNN_MAX_D:
+        raise ValueError("rows of 1 .. %d values (got %d)" % (KNN_MAX_D, d))
+    need = knn_scratch(Q, M, k, splits)
+    _f32(q, bank, out_sim)
+    assert tuple(out_sim.shape) == (Q, k) and tuple(out_idx.shape) == (Q, k) and out_idx.dtype == torch.int32 and out_idx.is_contiguous()
+    if (q_group is None) != (bank_group is None):
+        raise ValueError("q_group and bank_group are given together or not at all")
+    for g, n in ((q_group, Q), (bank_group, M)):
+        assert g is None or (g.dtype == torch.int32 and g.is_contiguous() and tuple(g.shape) == (n,))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=q.device)
+    _f32(scratch, n=need)
+    assert all(t is None or t.device == q.device for t in (bank, out_sim, out_idx, q_group, bank_group, scratch))
+    require_cuda(q, bank, out_sim, out_idx, q_group, bank_group, scratch)
+    check(lib().cx_knn_topk(ptr(q), ptr(bank), ptr(q_group), ptr(bank_group), ptr(out_sim), ptr(out_idx), ptr(scratch), scratch.numel(),
+                            Q, M, d, int(k), int(splits), stream_ptr()), "cx_knn_topk")
+    return scratch
+
+
+def knn_vote(sim, idx, labels, out_score, out_support, inv_T):
+    """The weighted vote of each query's neighbours (cx_knn_vote): labels (M, n) fp32 in [0, 1], < 0 = ignored; weights
+    exp((s_j - s_0) * inv_T) relative to the nearest neighbour; out_score (Q, n) = num / den, out_support (Q, n) = den, 0.5 / 0 where no
+    neighbour has the label."""
+    Q, k = sim.shape
+    n = labels.shape[1]
+    if not (1 <= k <= KNN_MAX_K and 1 <= n <= KNN_MAX_CLASSES and inv_T >= 0):
+        raise ValueError("the vote takes 1 <= k <= %d, 1 <= n <= %d and inv_T >= 0 (got k %d, n %d, inv_T %r)"
+                         % (KNN_MAX_K, KNN_MAX_CLASSES, k, n, inv_T))
+    _f32(sim, labels, out_score, out_support)
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and tuple(idx.shape) == (Q, k) and labels.dim() == 2
+    assert tuple(out_score.shape) == (Q, n) and tuple(out_support.shape) == (Q, n)
+    require_cuda(sim, idx, labels, out_score, out_support)
+    if Q:
+        check(lib().cx_knn_vote(ptr(sim), ptr(idx), ptr(labels), ptr(out_score), ptr(out_support), float(inv_T), Q, k, n, stream_ptr()),
+              "cx_knn_vote")
 
 
 def softmax_ce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):

@@ -1268,6 +1268,44 @@ int cx_affine_to_f32_nchw(const void* x, const float* scale, const float* shift,
                           int ldx, void* stream);
 int cx_bf16_to_f32_nchw(const void* x, float* y, int B, int H, int W, int C, int ldx, void* stream);
 
+/* ---- exact k-nearest-neighbour search and the weighted vote (csrc/knn.hip): the kNN probe of a frozen backbone (Wu et al., CVPR 2018)
+ * and image retrieval on the pooled features.  No reference counterpart.  Additive entry points of ABI 10.
+ *
+ * The order that defines "nearest".  A (similarity, bank index) pair is one 64-bit key: the high word is the fp32 similarity as an
+ * order-preserving unsigned integer (u = the bits; u >= 2^31 ? ~u : u | 2^31; a NaN similarity counts as -inf, -0 as +0), the low
+ * word is 0xFFFFFFFF - index.  The result of a query is its k largest keys in descending key order: the larger similarity first, the
+ * lower bank index among equal similarities.  The order is total, so the result does not depend on how the bank was tiled or split.
+ *
+ * cx_knn_normalize: y = x / max(|x|, 1e-12) per row of the (rows, d) fp32 matrix, |x| = sqrtf of the fp32 sum of squares (the
+ *   normalisation of the contrastive loss); x == y is allowed.  CX_EINVAL: NULL x / y, rows < 1, d outside [1, CX_KNN_MAX_D].
+ * cx_knn_topk: q (Q, d), bank (M, d) fp32 row-major; the similarity is the plain inner product (cosine: normalise both sides first),
+ *   in fp32 on the fp32-input MFMA, an fmaf chain over two interleaved halves of d.  q_group (Q,) / bank_group (M,) int32, both or
+ *   neither: a bank row whose group equals the query's group, that group >= 0, is no candidate (the group = the row's own position:
+ *   leave-one-out; = the patient: patient-disjoint search).  out_sim (Q, k) fp32, out_idx (Q, k) int32; a query with fewer than k
+ *   candidates has idx = -1, sim = -inf in the tail.  splits = the slices the bank is cut into (of whole 128-row tiles; a slice past
+ *   the bank's end is empty): 0 = chosen here from Q, M and the device's compute units, a positive value forces that many (the
+ *   kernel_hint of this entry point).  scratch: the caller's, cx_knn_scratch floats (Q x slices x k keys), 8-byte aligned; nothing
+ *   is allocated, nothing is sized by Q x M, no atomics: the same bits on every run and for every value of splits.
+ *   CX_EINVAL before any launch: NULL q / bank / out_sim / out_idx / scratch, one group pointer without the other, Q < 1, M < 1,
+ *   d outside [1, CX_KNN_MAX_D], k outside [1, CX_KNN_MAX_K], splits outside [0, CX_KNN_MAX_SPLITS], scratch_floats too small.
+ *   CX_EALIGN: a pointer that is not 4-byte aligned, a scratch that is not 8-byte aligned.  cx_knn_scratch returns 0 for refused sizes.
+ * cx_knn_vote: labels (M, n) fp32, targets in [0, 1], a value < 0 = ignored.  For query q over its valid neighbours j (idx >= 0) in
+ *   list order, s_0 the first of them: w_j = exp((s_j - s_0) * inv_T) (1 where inv_T == 0 or s_j == s_0);
+ *   num_c = sum_j w_j y[idx_j, c] and den_c = sum_j w_j over the neighbours whose label c is not ignored; out_score (Q, n) = num_c /
+ *   den_c, out_support (Q, n) = den_c; den_c == 0: score 0.5, support 0.  Weights and sums in double, in list order, each result
+ *   rounded to fp32 once: bit-reproducible.
+ *   CX_EINVAL: a NULL pointer, Q < 1, k outside [1, CX_KNN_MAX_K], n outside [1, CX_KNN_MAX_CLASSES], inv_T < 0 or NaN.            */
+#define CX_KNN_MAX_K 256
+#define CX_KNN_MAX_D 4096
+#define CX_KNN_MAX_SPLITS 256
+#define CX_KNN_MAX_CLASSES 64
+long long cx_knn_scratch(int Q, int M, int k, int splits);
+int cx_knn_normalize(const float* x, float* y, int rows, int d, void* stream);
+int cx_knn_topk(const float* q, const float* bank, const int* q_group, const int* bank_group, float* out_sim, int* out_idx, float* scratch,
+                long long scratch_floats, int Q, int M, int d, int k, int splits, void* stream);
+int cx_knn_vote(const float* sim, const int* idx, const float* labels, float* out_score, float* out_support, float inv_T, int Q, int k,
+                int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
