@@ -402,7 +402,9 @@ class _Engine(FusedEngine):
         else:
             # conv3x3(width, width, stride, groups, dilation) (attn_aug_conv.py:183): one launch per group on its channel slice of
             # y1 / y2; the statistic rows of the groups sit side by side at the pitch of the whole BatchNorm
-            d_, gr = b.conv2.dilation[0], b.conv2.groups          # d > 1 under replace_stride_with_dilation: padding = dilation, stride 1
+            # d > 1 under replace_stride_with_dilation: padding = dilation.  The block's own stride stays on conv2, so a dilated conv2
+            # can have stride 2 (rd = [True, False, True]: layer3[0] has dilation 2 from layer2 and stride 2 of its own)
+            d_, gr = b.conv2.dilation[0], b.conv2.groups
             kg = p_ // gr
             for g_ in range(gr):
                 c_, wg = (slice(g_ * kg, (g_ + 1) * kg), g_) if gr > 1 else (None, None)
@@ -606,7 +608,9 @@ class _Engine(FusedEngine):
                            **self._x_bnrelu(ws, S1))
             ops.conv_wgrad(dQ, t["y1"], G(aa.in_proj_qkv.weight), stride=s_, **self._x_bnrelu(ws, S1))
             return (rows or 0) + (rows2 or 0)
-        d_, gr = b.conv2.dilation[0], b.conv2.groups      # (a dilated conv2 has stride 1: its input gradient's padding is d (2d - d))
+        # the input gradient's padding is (extent - 1) - forward padding = 2d - d = d at either stride: a dilated conv2 has stride 1
+        # or, as layer3[0] under replace_stride_with_dilation = [True, False, True], stride 2 (tstride = 2 with taps d pixels apart)
+        d_, gr = b.conv2.dilation[0], b.conv2.groups
         kg, ch = p_ // gr, self._ch
         n_w = kg * kg * 9
         for g_ in range(gr):

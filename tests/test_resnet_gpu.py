@@ -121,11 +121,12 @@ def test_wide_bottleneck_width_per_group_matches_fp32_oracle(dev):
             assert c > 0.97 and abs(n - 1) < 0.05, (k, c, n)
 
 
-@pytest.mark.parametrize("dtype,rd", [("bf16", [False, True, True]), ("fp32", [True, False, True])])
+@pytest.mark.parametrize("dtype,rd", [("bf16", [False, True, True]), ("fp32", [True, False, True]), ("bf16", [True, False, True])])
 def test_replace_stride_with_dilation_matches_fp32_oracle(dev, dtype, rd):
     """ResNet(Bottleneck, ..., replace_stride_with_dilation=rd) (attn_aug_conv.py:218-220, :266-271: a stage's stride becomes the
     dilation of its 3x3 convolutions, padding = dilation, :183) against the fp32 oracle: CxConv.dil / CxWgrad.dil on the generic
-    implicit-GEMM kernels (forward, input gradient, weight gradient), in the bf16 and in the fp32 storage mode."""
+    implicit-GEMM kernels (forward, input gradient, weight gradient), in the bf16 and in the fp32 storage mode.  rd = [True, False,
+    True] puts a dilation and a stride on one convolution (layer3[0].conv2: dil = 2, stride = 2; input gradient tstride = 2)."""
     from chexpert_amd.models import Bottleneck, ResNet
     from oracle import nets, step
     layers, B, S, n_cls = (1, 2, 2, 2), 4, 128, 5
