@@ -21,6 +21,7 @@ DELONG_MAX_ROWS, DELONG_WG_ENTRIES, DELONG_TILE = 128, 16384, 32   # 4 rows per 
 HIER_MAX_LABELS, HIER_MAX_PATH = 64, 8                             # CX_HIER_MAX_LABELS, CX_HIER_MAX_PATH (loss.hip)
 NTXENT_MAX_N, NTXENT_MAX_D = 4096, 1024                            # CX_NTXENT_MAX_N, CX_NTXENT_MAX_D (loss.hip)
 KNN_MAX_K, KNN_MAX_D, KNN_MAX_SPLITS, KNN_MAX_CLASSES = 256, 4096, 256, 64   # CX_KNN_MAX_* (knn.hip)
+PROBE_MAX_SPLITS, PROBE_MAX_HISTORY = 1024, 16                                # CX_PROBE_MAX_* (probe.hip)
 
 _vp, _fp, _i32 = C.c_void_p, C.c_void_p, C.c_int32
 
@@ -270,6 +271,13 @@ SIGNATURES = {
     "cx_knn_normalize": [_vp, _vp, _i, _i, _vp],
     "cx_knn_topk": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i, _i, _i, _vp],
     "cx_knn_vote": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp],
+    "cx_probe_scratch": [_i, _i, _i, _i],
+    "cx_probe_colstats": [_vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp],
+    "cx_probe_standardize": [_vp, _vp, _vp, _vp, C.c_longlong, _i, _vp],
+    "cx_probe_logits": [_vp, _vp, _vp, _i, _i, _i, _vp],
+    "cx_probe_loss_grad": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp],
+    "cx_probe_lbfgs_direction": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "cx_probe_lbfgs_advance": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
 }
 
 _lib = None
@@ -292,7 +300,8 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = C.c_char_p if name in ("cx_error_string", "cx_last_kernel") else \
-                C.c_longlong if name in ("cx_csra_bwd_scratch", "cx_pcam_bwd_scratch", "cx_ntxent_scratch", "cx_knn_scratch") else C.c_int
+                C.c_longlong if name in ("cx_csra_bwd_scratch", "cx_pcam_bwd_scratch", "cx_ntxent_scratch", "cx_knn_scratch",
+                                     "cx_probe_scratch") else C.c_int
         if l.cx_abi_version() != 10:
             raise RuntimeError("chexpert_amd: ABI version mismatch")
         _lib = l

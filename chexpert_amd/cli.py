@@ -186,11 +186,26 @@
                         pretrain_eval_step_<n>.json and prints one line (checkpoint selection stays by the contrastive loss); with
                         --evaluate_single_model it writes knn_step_<n>.json beside eval_results_step_<n>.json, for any checkpoint.
                         Needs one of the two modes, one rank and the linear head (not --head csra|pcam)
+  --linear_probe        the linear evaluation of the backbone (SimCLR, MoCo, MoCo-CXR; chexpert_amd/probe.py, csrc/probe.hip): the bank and
+                        the validation set are embedded as for --knn_probe (once where both are given and read the same bank), then one
+                        logistic regression per finding is fitted on the bank's standardised features by L-BFGS on the GPU -- no backward
+                        pass through the network, and the result is the optimum, the same for the same checkpoint -- and the AUROC per
+                        finding on the validation set is reported.  --probe_l2 L [L ...] (default 0.001): one fit per value, in descending
+                        order, each warm-started from the one before; the report lists every value, the choice is the reader's.
+                        --probe_bank N (default 8192; 0 = the whole training set) at an even stride: a label fraction.  The labels are the
+                        training table's (--uncertain / --labels); an ignored (-1) label is no row of its finding.  --probe_max_iter I
+                        (default 200).  With --pretrain contrastive every evaluation adds "linear_probe": {bank, l2, fits: [{l2, aucs,
+                        mean_auc, status, iterations, passes, train_loss}]} to pretrain_eval_step_<n>.json and prints one line; with
+                        --evaluate_single_model it writes probe_step_<n>.json beside eval_results_step_<n>.json.  --probe_save FILE
+                        (--evaluate_single_model and exactly one --probe_l2): a checkpoint of the restored weights with the classifier
+                        replaced by the fit (folded back to raw features), the pooling's numbers kept, no optimiser and no loss state
+                        (the probe is a BCE model), the step the source's: --restore FILE --evaluate_single_model evaluates it.  Needs
+                        one of the two modes, one rank, the linear head and one logit per finding (not --uncertain multiclass, --loss hier)
   --init_backbone FILE  with --train: every tensor of FILE's state_dict but the classifier's weight and bias (whatever their width) is loaded
                         before the first step, BatchNorm's running statistics included (the pooling's own numbers, GeM's exponent and
                         log-sum-exp's sharpness, where the checkpoint and this run's --pool both have them); the step, the
                         optimiser state and the loss state are not.  A missing or mis-shaped key is an error that names it.  --pool, --head
-                        and --loss stay free; exclusive with --restore.  (--freeze_backbone_steps / --head_lr_mult give the linear probe)
+                        and --loss stay free; exclusive with --restore.  (The linear evaluation of such a backbone is --linear_probe)
 
 Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N chexpert.py --train ...`; every rank holds a
 replica and a shard of each minibatch stream (per-rank BatchNorm statistics, averaged gradients: DDP semantics), the
@@ -371,6 +386,15 @@ def build_parser():
     p.add_argument("--knn_temperature", type=float, default=None, metavar="T", help="with --knn_probe: temperature of the vote's weights exp(s / T), > 0 (default 0.1)")
     p.add_argument("--knn_bank", type=int, default=None, metavar="N",
                    help="with --knn_probe: the bank is N training images at an even stride (default 8192); 0 = the whole training set")
+    p.add_argument("--linear_probe", action="store_true",
+                   help="with --pretrain contrastive or --evaluate_single_model: the linear probe, logistic regression fitted on the pooled features")
+    p.add_argument("--probe_l2", type=float, nargs="+", default=None, metavar="L",
+                   help="with --linear_probe: the L2 penalties of the fit, each >= 0 (default 0.001); one report entry per value")
+    p.add_argument("--probe_bank", type=int, default=None, metavar="N",
+                   help="with --linear_probe: the bank is N training images at an even stride (default 8192); 0 = the whole training set")
+    p.add_argument("--probe_max_iter", type=int, default=None, metavar="I", help="with --linear_probe: L-BFGS iterations per class, >= 1 (default 200)")
+    p.add_argument("--probe_save", default=None, metavar="FILE",
+                   help="with --linear_probe, --evaluate_single_model and one --probe_l2: write a checkpoint whose classifier is the fit")
     p.add_argument("--init_backbone", default=None, metavar="FILE",
                    help="with --train: load every tensor of FILE's state_dict but the classifier's before the first step (exclusive with --restore)")
     p.add_argument("--num_workers", type=int, default=int(os.environ.get("CHEXPERT_NUM_WORKERS", "16")), help="decode / crop worker processes of the training loader (chexpert.py:77: "
@@ -964,11 +988,108 @@ def knn_options(args, world=1):
     return {"k": int(k), "temperature": float(T), "bank": int(bank)}
 
 
-def knn_probe(run):
+def knn_probe(run, embedded=None):
     """The kNN probe of run.model (knn.probe) under the run's deterministic preprocessing, as the dictionary the reports carry."""
     from . import knn
     o = run.knn
-    return knn.probe(run.model, run.train_ds, run.valid_ds, o["k"], o["temperature"], o["bank"], run.args.batch_size, run.device, run.clahe)
+    return knn.probe(run.model, run.train_ds, run.valid_ds, o["k"], o["temperature"], o["bank"], run.args.batch_size, run.device, run.clahe,
+                     embedded=embedded)
+
+
+PROBE_DEFAULT_L2, PROBE_DEFAULT_MAX_ITER = 1e-3, 200
+
+
+def probe_options(args, world=1):
+    """--linear_probe and its flags checked before anything runs: None without it, else {"l2": [...], "bank", "max_iter", "save"} (bank
+    0: the whole training set).  What the probe cannot run with is refused with a one-line reason (ValueError)."""
+    on = getattr(args, "linear_probe", False)
+    l2, bank = getattr(args, "probe_l2", None), getattr(args, "probe_bank", None)
+    max_iter, save = getattr(args, "probe_max_iter", None), getattr(args, "probe_save", None)
+    if not on:
+        if l2 is not None or bank is not None or max_iter is not None or save is not None:
+            raise ValueError("--probe_l2 / --probe_bank / --probe_max_iter / --probe_save belong to --linear_probe: pass it with them")
+        return None
+    if getattr(args, "pretrain", None) is None and not getattr(args, "evaluate_single_model", False):
+        raise ValueError("--linear_probe runs at the evaluations of --pretrain contrastive or with --evaluate_single_model: pass one of them")
+    if world > 1:
+        raise ValueError("--linear_probe cannot be combined with more than one rank (world size %d): gathering embeddings across ranks "
+                         "is not built" % world)
+    if getattr(args, "head", None) in ("csra", "pcam"):
+        raise ValueError("--linear_probe cannot be combined with --head %s: that head pools per-class score maps and has no pooled "
+                         "feature vector" % args.head)
+    if getattr(args, "uncertain", "ones") == "multiclass":
+        raise ValueError("--linear_probe cannot be combined with --uncertain multiclass: its head has three logits per finding, the "
+                         "probe fits one")
+    if getattr(args, "loss", "bce") == "hier":
+        raise ValueError("--linear_probe cannot be combined with --loss hier: its targets are conditional on the parent finding, the "
+                         "probe fits one independent logit per finding")
+    l2 = [PROBE_DEFAULT_L2] if l2 is None else [float(v) for v in l2]
+    for v in l2:
+        if not (v >= 0 and np.isfinite(v)):
+            raise ValueError("--probe_l2 takes finite penalties >= 0 (got %r)" % (v,))
+    bank = KNN_DEFAULT_BANK if bank is None else bank
+    if bank < 0:
+        raise ValueError("--probe_bank takes a number of training images >= 0, 0 being all of them (got %r)" % (bank,))
+    max_iter = PROBE_DEFAULT_MAX_ITER if max_iter is None else max_iter
+    if max_iter < 1:
+        raise ValueError("--probe_max_iter takes a number of iterations >= 1 (got %r)" % (max_iter,))
+    if save is not None:
+        if not getattr(args, "evaluate_single_model", False):
+            raise ValueError("--probe_save writes the evaluated checkpoint with the fitted classifier: pass --evaluate_single_model with it")
+        if len(l2) != 1:
+            raise ValueError("--probe_save takes the fit of exactly one --probe_l2 (got %d values)" % len(l2))
+    return {"l2": l2, "bank": int(bank), "max_iter": int(max_iter), "save": save}
+
+
+def run_probes(run):
+    """(the kNN probe's report or None, the linear probe's or None) of run.model.  Where both are asked for and read the same bank, the
+    two sets are embedded once.  The linear probe's report carries its fits under "_fits" (dropped before it is written)."""
+    from . import knn, probe
+    kn, lp = getattr(run, "knn", None), getattr(run, "probe", None)
+    if kn is None and lp is None:
+        return None, None
+    sets = {}
+
+    def embedded(n_bank):
+        idx = knn.bank_indices(len(run.train_ds), n_bank)
+        if len(idx) not in sets:
+            sets[len(idx)] = (knn.embed_dataset(run.model, run.train_ds, idx, run.args.batch_size, run.device, run.clahe) +
+                              knn.embed_dataset(run.model, run.valid_ds, range(len(run.valid_ds)), run.args.batch_size, run.device, run.clahe))
+        return sets[len(idx)]
+
+    knn_res = None if kn is None else knn_probe(run, embedded(kn["bank"]))
+    lin_res = None if lp is None else probe.probe(run.model, run.train_ds, run.valid_ds, lp["l2"], lp["bank"], run.args.batch_size,
+                                                  run.device, run.clahe, max_iter=lp["max_iter"], embedded=embedded(lp["bank"]))
+    return knn_res, lin_res
+
+
+def probe_report(res):
+    """The linear probe's result as the reports carry it."""
+    return {k: v for k, v in res.items() if not k.startswith("_")}
+
+
+def print_probe(res, step):
+    for f in res["fits"]:
+        print("linear probe @ step %d: mean AUROC %.4f (l2 %g, bank %d, status %s, %d passes)\n%s" % (
+            step, f["mean_auc"], f["l2"], res["bank"], "".join(str(s) for s in f["status"]), f["passes"], pprint.pformat(f["aucs"])))
+
+
+def save_probe_checkpoint(run, res):
+    """--probe_save: the model's weights with the classifier's two tensors replaced by the fit, the pooling's numbers, the source's
+    step; no optimiser state and no loss_state (the probe is a BCE model whatever the backbone was trained with)."""
+    fit, f = res["_fits"][0], res["fits"][0]
+    sd = {k: v.detach().clone() for k, v in run.model.state_dict().items()}
+    wk, bk = classifier_keys(run.model)
+    sd[wk], sd[bk] = fit["W"].to(sd[wk].dtype), fit["b"].to(sd[bk].dtype)
+    auc = f["mean_auc"]
+    ckpt = {"global_step": run.args.step, "eval_loss": float(np.sum(f["train_loss"])), "avg_auc": 0.0 if np.isnan(auc) else float(auc),
+            "state_dict": sd, "linear_probe": {"l2": f["l2"], "bank": res["bank"]}}
+    if run.model.pool_kind != "avg":
+        ckpt["pool_state"] = run.model.pool_state()
+    folder = os.path.dirname(run.probe["save"])
+    if folder:
+        os.makedirs(folder, exist_ok=True)
+    torch.save(ckpt, run.probe["save"])
 
 
 def print_knn(res, step):
@@ -1642,6 +1763,7 @@ def check_flags(argv=None):
     init_backbone_options(args)
     run.pretrain = pretrain_options(args, run.world)
     run.knn = knn_options(args, run.world)
+    run.probe = probe_options(args, run.world)
     run.pool = resolve_pool(args)
     run.head = resolve_head(args, run.pool)
     return run
@@ -1863,8 +1985,13 @@ def run_eval(run, tag):
     args = run.args
     with averaged_weights(run):
         o, t, l = validate(run)
-        knn_res = knn_probe(run) if getattr(run, "knn", None) is not None else None
+        knn_res, lin_res = run_probes(run)
     res = M.compute_metrics(o, t, l)
+    if lin_res is not None and run.rank == 0:
+        print_probe(lin_res, args.step)
+        json.dump(probe_report(lin_res), open(os.path.join(args.output_dir, report_name(tag, "probe")), "w"), indent=4)
+        if run.probe["save"] is not None:
+            save_probe_checkpoint(run, lin_res)
     if knn_res is not None and run.rank == 0:
         print_knn(knn_res, args.step)
         json.dump(knn_res, open(os.path.join(args.output_dir, report_name(tag, "knn")), "w"), indent=4)
@@ -2004,11 +2131,16 @@ def contrastive_eval(run):
     res = {"pretrain": "contrastive", "step": args.step, "loss": {"contrastive": total / max(anchors, 1)},
            "top1": hits / max(anchors, 1), "anchors": anchors, "temperature": float(model.loss_temperature.item()),
            "positive": run.pretrain["positive"]}
-    if getattr(run, "knn", None) is not None:
-        res["knn"] = knn_probe(run)
-        model.eval()
+    knn_res, lin_res = run_probes(run)
+    model.eval()
+    if knn_res is not None:
+        res["knn"] = knn_res
         if run.rank == 0:
-            print_knn(res["knn"], args.step)
+            print_knn(knn_res, args.step)
+    if lin_res is not None:
+        res["linear_probe"] = probe_report(lin_res)
+        if run.rank == 0:
+            print_probe(lin_res, args.step)
     if run.rank == 0:
         print("Evaluate contrastive pretraining @ step %d: loss %.5f, top1 %.4f over %d anchors" % (args.step, res["loss"]["contrastive"],
                                                                                                  res["top1"], anchors))

@@ -160,11 +160,15 @@ def bank_indices(n_train, n_bank):
 
 
 @torch.no_grad()
-def probe(model, train_ds, valid_ds, k, T, n_bank, batch_size, device, pre=None):
-    """The kNN probe of `model`: {"k", "temperature", "bank", "aucs", "mean_auc"} (k is cut to the bank's size)."""
+def probe(model, train_ds, valid_ds, k, T, n_bank, batch_size, device, pre=None, embedded=None):
+    """The kNN probe of `model`: {"k", "temperature", "bank", "aucs", "mean_auc"} (k is cut to the bank's size).  embedded: (bank,
+    labels, queries, targets) where the caller has embedded the two sets already (the linear probe of the same evaluation)."""
     idx = bank_indices(len(train_ds), n_bank)
-    bank, labels = embed_dataset(model, train_ds, idx, batch_size, device, pre)
-    q, targets = embed_dataset(model, valid_ds, range(len(valid_ds)), batch_size, device, pre)
+    if embedded is None:
+        bank, labels = embed_dataset(model, train_ds, idx, batch_size, device, pre)
+        q, targets = embed_dataset(model, valid_ds, range(len(valid_ds)), batch_size, device, pre)
+    else:
+        bank, labels, q, targets = embedded
     k = min(int(k), bank.shape[0])
     score, support = knn_predict(q, bank, labels, k, T)
     aucs = knn_auc(score, support, targets)

@@ -352,6 +352,22 @@ class FusedNet(nn.Module):
         """Width of the final Linear layer (the classifier of every family)."""
         return [m for m in self.modules() if isinstance(m, nn.Linear)][-1].out_features
 
+    def resize_classifier(self, n_out):
+        """Replaces the classifier (the last nn.Linear) by a fresh one of n_out outputs on the same device -- a contrastive
+        checkpoint's projection becomes a head of one logit per finding (probe.load_into) -- and drops the engine, which is built
+        anew over the new parameters at the next forward.  Refused once a fused optimiser holds the parameters.  Returns self."""
+        name, old = [(k, m) for k, m in self.named_modules() if isinstance(m, nn.Linear)][-1]
+        if old.out_features == n_out:
+            return self
+        if self._pool_locked:
+            raise RuntimeError("resize_classifier: the classifier has %d outputs, %d are asked for, and a fused optimiser holds the "
+                               "parameters: build the model anew" % (old.out_features, n_out))
+        new = nn.Linear(old.in_features, n_out).to(device=old.weight.device, dtype=old.weight.dtype)
+        parent, _, leaf = name.rpartition(".")
+        setattr(self.get_submodule(parent) if parent else self, leaf, new)
+        object.__setattr__(self, "_engine", None)
+        return self
+
     def loss_state(self):
         """What set_loss(kind=...) holds beyond the model's state_dict, as CPU tensors and floats: {kind, aux, prior, margin, lr_aux}
         (aux, prior and lr_aux are None for kind 'bce').  Kinds 'focal' and 'asl' add `focus`, the four numbers of `loss_focus`, kind

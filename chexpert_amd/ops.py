@@ -11,7 +11,7 @@ import torch
 from . import _lib as L
 from ._lib import (BOOT_MAX_POINTS, BOOT_MAX_TILES, BOOT_MAX_UNITS, BOOT_SENS, BOOT_SPEC, BOOT_TILE, CALIB_MAX_BINS, CALIB_MAX_ITER,
                    CALIB_METHODS, DELONG_MAX_ROWS, DELONG_TILE, DELONG_WG_ENTRIES, EPI_JOIN, EPI_MASK, EPI_STORE, HIER_MAX_LABELS, HIER_MAX_PATH, NTXENT_MAX_D, NTXENT_MAX_N,
-                   KNN_MAX_CLASSES, KNN_MAX_D, KNN_MAX_K, KNN_MAX_SPLITS,
+                   KNN_MAX_CLASSES, KNN_MAX_D, KNN_MAX_K, KNN_MAX_SPLITS, PROBE_MAX_HISTORY, PROBE_MAX_SPLITS,
                    MODE_CONV, MODE_POOL2, MODE_STEM, PRO_AFFINE2, PRO_AFFINE_RELU, PRO_JOIN, PRO_NONE, CxConv, CxWgrad, check, lib, ptr, require_cuda, stream_ptr)
 import ctypes as C
 
@@ -917,6 +917,148 @@ def knn_vote(sim, idx, labels, out_score, out_support, inv_T):
     if Q:
         check(lib().cx_knn_vote(ptr(sim), ptr(idx), ptr(labels), ptr(out_score), ptr(out_support), float(inv_T), Q, k, n, stream_ptr()),
               "cx_knn_vote")
+
+
+def probe_scratch(M, d, n, splits=0):
+    """The floats of scratch probe_loss_grad and probe_colstats need for a bank of M rows (cx_probe_scratch), `splits` = 0 being the
+    library's own choice of slices.  Sizes the kernels refuse are a ValueError."""
+    M, d, n, splits = int(M), int(d), int(n), int(splits)
+    if not (1 <= M < 2 ** 31 and 1 <= d <= KNN_MAX_D and 1 <= n <= KNN_MAX_CLASSES and 0 <= splits <= PROBE_MAX_SPLITS):
+        raise ValueError("the probe takes 1 <= M < 2^31 rows of 1 .. %d features, 1 .. %d classes and 0 <= splits <= %d (got M %d, d %d, "
+                         "n %d, splits %d)" % (KNN_MAX_D, KNN_MAX_CLASSES, PROBE_MAX_SPLITS, M, d, n, splits))
+    return int(lib().cx_probe_scratch(M, d, n, splits))
+
+
+def _probe_scratch(scratch, need, like):
+    if scratch is None:
+        scratch = torch.empty(need + (need & 1), dtype=torch.float32, device=like.device)
+    _f32(scratch, n=need)
+    assert scratch.device == like.device and scratch.data_ptr() % 8 == 0
+    return scratch
+
+
+def probe_colstats(x, mean, rstd, scratch=None):
+    """mean (d,) and rstd (d,) = 1 / max(population std, 1e-6) of the columns of x (M, d) fp32 (cx_probe_colstats): double sums in a
+    fixed order, rounded once.  scratch: fp32, at least probe_scratch(M, d, 1) floats (None: allocated here).  Returns the scratch."""
+    assert x.dim() == 2
+    M, d = x.shape
+    need = probe_scratch(M, d, 1)
+    _f32(x)
+    _f32(mean, rstd, n=d)
+    assert mean.numel() == d and rstd.numel() == d and mean.device == x.device and rstd.device == x.device
+    scratch = _probe_scratch(scratch, need, x)
+    require_cuda(x, mean, rstd, scratch)
+    check(lib().cx_probe_colstats(ptr(x), ptr(mean), ptr(rstd), ptr(scratch), scratch.numel(), M, d, stream_ptr()), "cx_probe_colstats")
+    return scratch
+
+
+def probe_standardize(x, mean, rstd, y):
+    """y = (x - mean) * rstd per column of the (rows, d) fp32 matrix, two roundings (cx_probe_standardize); y may be x."""
+    assert x.dim() == 2 and y.shape == x.shape
+    rows, d = x.shape
+    if not 1 <= d <= KNN_MAX_D:
+        raise ValueError("rows of 1 .. %d values (got %d)" % (KNN_MAX_D, d))
+    _f32(x, y)
+    _f32(mean, rstd, n=d)
+    assert mean.numel() == d and rstd.numel() == d and all(t.device == x.device for t in (mean, rstd, y))
+    require_cuda(x, mean, rstd, y)
+    if rows:
+        check(lib().cx_probe_standardize(ptr(x), ptr(mean), ptr(rstd), ptr(y), rows, d, stream_ptr()), "cx_probe_standardize")
+    return y
+
+
+def _probe_theta(theta, n, d, *same):
+    _f32(theta, *same)
+    assert tuple(theta.shape) == (n, d + 1), "theta is (n, d + 1): the weights, then the bias"
+    assert all(t is None or (tuple(t.shape) == (n, d + 1) and t.device == theta.device) for t in same)
+
+
+def probe_logits(x, theta, out):
+    """out (rows, n) = x w^T + b for theta (n, d + 1) = [w | b] (cx_probe_logits), fp32 on the fp32-input MFMA."""
+    assert x.dim() == 2 and theta.dim() == 2
+    rows, d = x.shape
+    n = theta.shape[0]
+    if rows:
+        probe_scratch(rows, d, n)                                            # (checks d and n)
+    _f32(x, out)
+    _probe_theta(theta, n, d)
+    assert tuple(out.shape) == (rows, n) and out.device == x.device and theta.device == x.device
+    require_cuda(x, theta, out)
+    if rows:
+        check(lib().cx_probe_logits(ptr(x), ptr(theta), ptr(out), rows, d, n, stream_ptr()), "cx_probe_logits")
+    return out
+
+
+def _probe_flags(t, n, like):
+    assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n and t.device == like.device)
+
+
+def probe_loss_grad(x, y, theta, loss, grad, count, pos_weight=None, l2=0.0, active=None, scratch=None, splits=0):
+    """Loss (n,), gradient (n, d + 1) and count (n, 3) = live rows, sum y, sum (1 - y) of the multi-label logistic regression of
+    include/chexpert_hip.h (cx_probe_loss_grad): x (M, d), y (M, n) with < 0 = ignored, theta (n, d + 1), pos_weight (n,) or None, l2 >= 0.
+    active (n,) int32 or None: a class whose flag is 0 keeps its previous outputs.  scratch: fp32, at least probe_scratch(M, d, n, splits)
+    floats (None: allocated here).  Returns the scratch."""
+    assert x.dim() == 2 and y.dim() == 2 and y.shape[0] == x.shape[0]
+    (M, d), n = x.shape, y.shape[1]
+    need = probe_scratch(M, d, n, splits)
+    l2 = float(l2)
+    if not (0.0 <= l2 < float("inf")):
+        raise ValueError("l2 must be finite and >= 0 (got %r)" % (l2,))
+    _f32(x, y)
+    _probe_theta(theta, n, d, grad)
+    _f32(loss, pos_weight, n=n)
+    _f32(count, n=3 * n)
+    assert loss.numel() == n and count.numel() == 3 * n and (pos_weight is None or pos_weight.numel() == n)
+    _probe_flags(active, n, x)
+    scratch = _probe_scratch(scratch, need, x)
+    assert all(t is None or t.device == x.device for t in (y, theta, loss, grad, count, pos_weight))
+    require_cuda(x, y, theta, loss, grad, count, pos_weight, active, scratch)
+    check(lib().cx_probe_loss_grad(ptr(x), ptr(y), ptr(theta), ptr(pos_weight), l2, ptr(active), ptr(loss), ptr(grad), ptr(count),
+                                   ptr(scratch), scratch.numel(), M, d, n, int(splits), stream_ptr()), "cx_probe_loss_grad")
+    return scratch
+
+
+def _probe_history(s_hist, y_hist, hist, n, d, like):
+    _f32(s_hist, y_hist)
+    assert s_hist.dim() == 3 and s_hist.shape == y_hist.shape and s_hist.shape[0] == n and s_hist.shape[2] == d + 1
+    m = s_hist.shape[1]
+    if not 1 <= m <= PROBE_MAX_HISTORY:
+        raise ValueError("a history of 1 .. %d pairs (got %d)" % (PROBE_MAX_HISTORY, m))
+    assert hist.dtype == torch.int32 and hist.is_contiguous() and tuple(hist.shape) == (n, 2)
+    assert all(t.device == like.device for t in (s_hist, y_hist, hist))
+    return m
+
+
+def probe_lbfgs_direction(grad, s_hist, y_hist, hist, direction, stats, active=None):
+    """direction (n, d + 1) = -H grad per class by the L-BFGS two-loop recursion over the pairs in s_hist / y_hist (n, m, d + 1), hist
+    (n, 2) int32 = pairs held, next slot (cx_probe_lbfgs_direction); -grad where that does not descend.  stats (n, 4): g . dir, max |g|,
+    sum |g|, 1 where the fallback was taken.  active (n,) int32 or None: a class whose flag is 0 keeps its previous outputs."""
+    n, d = grad.shape[0], grad.shape[1] - 1
+    _probe_theta(grad, n, d, direction)
+    m = _probe_history(s_hist, y_hist, hist, n, d, grad)
+    _f32(stats, n=4 * n)
+    assert stats.numel() == 4 * n and stats.device == grad.device
+    _probe_flags(active, n, grad)
+    require_cuda(grad, s_hist, y_hist, hist, direction, stats, active)
+    check(lib().cx_probe_lbfgs_direction(ptr(grad), ptr(s_hist), ptr(y_hist), ptr(hist), ptr(active), ptr(direction), ptr(stats), n, d, m,
+                                         stream_ptr()), "cx_probe_lbfgs_direction")
+
+
+def probe_lbfgs_advance(theta, grad, direction, t, mode, theta_t, grad_t, s_hist, y_hist, hist, tstats):
+    """Per class by mode (n,) int32 (cx_probe_lbfgs_advance): 1 forms the trial point theta_t = theta + t dir; 2 accepts it: the pair
+    (theta_t - theta, grad_t - grad) joins the history unless s.y <= 0, then theta = theta_t, grad = grad_t; 3 writes the trial's slope
+    and size, tstats (n, 2) = grad_t . dir, max |grad_t|; 0 writes nothing."""
+    n, d = theta.shape[0], theta.shape[1] - 1
+    _probe_theta(theta, n, d, grad, direction, theta_t, grad_t)
+    m = _probe_history(s_hist, y_hist, hist, n, d, theta)
+    _f32(t, n=n)
+    _f32(tstats, n=2 * n)
+    assert t.numel() == n and t.device == theta.device and tstats.numel() == 2 * n and tstats.device == theta.device
+    _probe_flags(mode, n, theta)
+    assert mode is not None
+    require_cuda(theta, grad, direction, t, mode, theta_t, grad_t, s_hist, y_hist, hist, tstats)
+    check(lib().cx_probe_lbfgs_advance(ptr(theta), ptr(grad), ptr(direction), ptr(t), ptr(mode), ptr(theta_t), ptr(grad_t), ptr(s_hist),
+                                       ptr(y_hist), ptr(hist), ptr(tstats), n, d, m, stream_ptr()), "cx_probe_lbfgs_advance")
 
 
 def softmax_ce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):

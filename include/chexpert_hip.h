@@ -1306,6 +1306,50 @@ int cx_knn_topk(const float* q, const float* bank, const int* q_group, const int
 int cx_knn_vote(const float* sim, const int* idx, const float* labels, float* out_score, float* out_support, float inv_T, int Q, int k,
                 int n, void* stream);
 
+/* ---- the linear probe (csrc/probe.hip): multi-label L2-regularised logistic regression on a bank of pooled features, the linear
+ * evaluation of SimCLR / MoCo / MoCo-CXR, and the vector arithmetic of its L-BFGS solver.  No reference counterpart.  Additive entry
+ * points of ABI 10.  The definition in float64 is chexpert_amd/probe.py (reference_loss_grad).
+ *
+ * x (M, d) fp32; y (M, n) fp32 in [0, 1], a value < 0 = ignored; theta (n, d + 1) fp32 row-major, theta[c, :d] = w_c, theta[c, d] =
+ * b_c; pos_weight (n,) or NULL (ones); l2 >= 0.  Per class c over its live rows (N_c = max(their number, 1)), z = x . w_c + b_c:
+ *   loss_c = (1 / N_c) sum [pw y softplus(-z) + (1 - y) softplus(z)] + (l2 / 2) |w_c|^2      (the bias is not regularised)
+ *   r      = (pw y + 1 - y) sigmoid(z) - pw y;   grad_c[:d] = (1 / N_c) sum r x + l2 w_c;   grad_c[d] = (1 / N_c) sum r
+ * cx_probe_scratch: the floats of scratch for a bank of M rows (the larger of what cx_probe_loss_grad and cx_probe_colstats need);
+ *   0 for refused sizes: M < 1, d outside [1, CX_KNN_MAX_D], n outside [1, CX_KNN_MAX_CLASSES], splits outside [0, CX_PROBE_MAX_SPLITS].
+ * cx_probe_colstats: mean (d,) = the column means of x, rstd (d,) = 1 / max(population standard deviation, 1e-6).  Two passes (the
+ *   sum, then the squared distances from the double mean), each accumulated in double: slices of rows first, then the slices in
+ *   order; each result rounded to fp32 once.  scratch 8-byte aligned.
+ * cx_probe_standardize: y = (x - mean) * rstd, the difference and the product rounded separately; x == y is allowed.
+ * cx_probe_logits: out (rows, n) = x w^T + b on v_mfma_f32_16x16x4_f32 (the tile code of cx_probe_loss_grad).
+ * cx_probe_loss_grad: loss (n,), grad (n, d + 1), count (n, 3) = live rows, sum y, sum (1 - y) over them.  Two launches: each slice
+ *   of the bank leaves its partial sums in the scratch, then the slices are added in slice order, divided by N_c once (fp32) and
+ *   l2 w is added by one fma.  active (n,) int32 or NULL: a class whose flag is 0 keeps the previous bits of its loss, grad and count.
+ *   splits: 0 = chosen here from M and the device's compute units.  No atomics: the same bits on every run for the same splits;
+ *   another splits is another summation order.
+ * cx_probe_lbfgs_direction: one workgroup per active class.  dir_c = -H g_c by the two-loop recursion over the class's history of
+ *   pairs (s_hist, y_hist: (n, m, d + 1); hist (n, 2) int32: the pairs held and the slot the next one goes to; both zero at the
+ *   start), initial scaling s.y / y.y of the newest pair, every dot product a fixed-order reduction; -g_c where that does not
+ *   descend.  stats (n, 4): g . dir, max |g|, sum |g|, 1 where the fallback was taken.
+ * cx_probe_lbfgs_advance: per class by mode (n,) int32.  1: theta_t = theta + t_c dir_c.  2: the trial is accepted: the pair
+ *   (theta_t - theta, grad_t - grad) joins the history unless s.y <= 0, then theta = theta_t and grad = grad_t.  3: tstats (n, 2) =
+ *   grad_t . dir_c, max |grad_t|: the trial's slope (f is convex, so f(theta_t) <= f(theta) + t grad_t . dir: a slope that is still
+ *   steep enough certifies the sufficient decrease where the fp32 loss cannot resolve it).  0: nothing is written.
+ * CX_EINVAL before any launch: a NULL pointer that is not optional, a size outside the limits above, m outside
+ *   [1, CX_PROBE_MAX_HISTORY], l2 < 0 or not finite, scratch_floats too small.  CX_EALIGN: a misaligned pointer.                        */
+#define CX_PROBE_MAX_SPLITS 1024
+#define CX_PROBE_MAX_HISTORY 16
+long long cx_probe_scratch(int M, int d, int n, int splits);
+int cx_probe_colstats(const float* x, float* mean, float* rstd, float* scratch, long long scratch_floats, int M, int d, void* stream);
+int cx_probe_standardize(const float* x, const float* mean, const float* rstd, float* y, long long rows, int d, void* stream);
+int cx_probe_logits(const float* x, const float* theta, float* out, int rows, int d, int n, void* stream);
+int cx_probe_loss_grad(const float* x, const float* y, const float* theta, const float* pos_weight, float l2, const int* active,
+                       float* loss, float* grad, float* count, float* scratch, long long scratch_floats, int M, int d, int n, int splits,
+                       void* stream);
+int cx_probe_lbfgs_direction(const float* grad, const float* s_hist, const float* y_hist, const int* hist, const int* active, float* dir,
+                             float* stats, int n, int d, int m, void* stream);
+int cx_probe_lbfgs_advance(float* theta, float* grad, const float* dir, const float* t, const int* mode, float* theta_t,
+                           const float* grad_t, float* s_hist, float* y_hist, int* hist, float* tstats, int n, int d, int m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
