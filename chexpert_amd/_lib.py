@@ -20,6 +20,7 @@ CALIB_MAX_ITER, CALIB_MAX_BINS = 1000, 64
 DELONG_MAX_ROWS, DELONG_WG_ENTRIES, DELONG_TILE = 128, 16384, 32   # 4 rows per class and model: two models of 16 classes
 HIER_MAX_LABELS, HIER_MAX_PATH = 64, 8                             # CX_HIER_MAX_LABELS, CX_HIER_MAX_PATH (loss.hip)
 NTXENT_MAX_N, NTXENT_MAX_D = 4096, 1024                            # CX_NTXENT_MAX_N, CX_NTXENT_MAX_D (loss.hip)
+BARLOW_MAX_N, BARLOW_MAX_D = 4096, 1024                            # CX_BARLOW_MAX_N, CX_BARLOW_MAX_D (barlow.hip)
 KNN_MAX_K, KNN_MAX_D, KNN_MAX_SPLITS, KNN_MAX_CLASSES = 256, 4096, 256, 64   # CX_KNN_MAX_* (knn.hip)
 PROBE_MAX_SPLITS, PROBE_MAX_HISTORY = 1024, 16                                # CX_PROBE_MAX_* (probe.hip)
 
@@ -134,6 +135,8 @@ SIGNATURES = {
     "cx_hier_collapse": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "cx_ntxent_scratch": [_i, _i],
     "cx_ntxent_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, C.c_longlong, _i, _i, _vp],
+    "cx_barlow_scratch": [_i, _i],
+    "cx_barlow_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, C.c_longlong, _i, _i, _vp],
     "cx_softmax_ce_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp],
     "cx_head_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "cx_gap_relu_bn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
@@ -301,7 +304,7 @@ def lib():
             fn.argtypes = args
             fn.restype = C.c_char_p if name in ("cx_error_string", "cx_last_kernel") else \
                 C.c_longlong if name in ("cx_csra_bwd_scratch", "cx_pcam_bwd_scratch", "cx_ntxent_scratch", "cx_knn_scratch",
-                                     "cx_probe_scratch") else C.c_int
+                                     "cx_probe_scratch", "cx_barlow_scratch") else C.c_int
         if l.cx_abi_version() != 10:
             raise RuntimeError("chexpert_amd: ABI version mismatch")
         _lib = l

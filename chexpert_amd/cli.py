@@ -175,6 +175,17 @@
                         pretrain_eval_step_<n>.json; the checkpoint carries loss_state, "pretrain": "contrastive" and eval_loss, and its
                         avg_auc is -eval_loss, so that the best_checkpoints are the lowest-loss ones.  --restore continues such a run and
                         is refused into a supervised one (and the other way round); the log line gains top1
+  --pretrain barlow     Barlow Twins pretraining (Zbontar et al., ICML 2021), the pretext loss that needs neither negatives nor a large
+                        batch: the same two views as --pretrain contrastive (needs --train and --affine or --jitter, refuses what it
+                        refuses), but the step's loss is FusedNet.set_loss(kind="barlow", lambd=L) with --barlow_lambda L (default 0.0051,
+                        the paper's): both views' embeddings are batch-normalised over the minibatch and their cross-correlation matrix is
+                        pushed towards the identity (csrc/barlow.hip, on the fp32-input MFMA).  --proj_dim D defaults to 512 here (1 ..
+                        1024); --temperature and --positive study|patient are refused.  The log line gains on_diag / off_diag; an
+                        evaluation writes pretrain_eval_step_<n>.json with "pretrain": "barlow", "loss": {"barlow": the mean over the
+                        validation minibatches weighted by their pairs}, on_diag, off_diag, mean_diag, pairs and lambda (and the
+                        --knn_probe / --linear_probe results); the checkpoint carries "pretrain": "barlow"; --restore continues such a run
+                        (the stored lambda is used unless --barlow_lambda is given) and is refused into a supervised or a contrastive one,
+                        --init_backbone takes its backbone as it takes a contrastive checkpoint's
   --knn_probe K         the weighted k-nearest-neighbour probe of the backbone (Wu et al., CVPR 2018; chexpert_amd/knn.py, csrc/knn.hip): a bank
                         of training images and the validation set are embedded with the frozen network in eval mode (FusedNet.embed: the
                         pooled features the classifier reads; the deterministic preprocessing only, --clahe if set, no views), each
@@ -375,9 +386,10 @@ def build_parser():
                         "per-pixel probabilities as weights (probabilistic-CAM pooling) and gives per-class probability maps")
     p.add_argument("--csra_lambda", type=float, default=None, metavar="L", help="with --head csra: the attention term's weight >= 0 (default 0.1)")
     p.add_argument("--csra_T", type=float, default=None, metavar="T", help="with --head csra: the softmax temperature > 0 (default 1)")
-    p.add_argument("--pretrain", default=None, choices=["contrastive"],
-                   help="contrastive pretraining (NT-Xent / SupCon) on two augmented views of every image instead of the supervised loss")
-    p.add_argument("--proj_dim", type=int, default=None, metavar="D", help="with --pretrain: width of the projection, the classifier nn.Linear (default 128)")
+    p.add_argument("--pretrain", default=None, choices=["contrastive", "barlow"],
+                   help="pretraining on two augmented views of every image instead of the supervised loss: contrastive (NT-Xent / SupCon) or barlow (Barlow Twins)")
+    p.add_argument("--barlow_lambda", type=float, default=None, metavar="L", help="with --pretrain barlow: weight of the off-diagonal term, >= 0 (default 0.0051)")
+    p.add_argument("--proj_dim", type=int, default=None, metavar="D", help="with --pretrain: width of the projection, the classifier nn.Linear (default 128; 512 under barlow)")
     p.add_argument("--temperature", type=float, default=None, metavar="T", help="with --pretrain: temperature of the contrastive loss, > 0 (default 0.2)")
     p.add_argument("--positive", default=None, choices=["view", "study", "patient"],
                    help="with --pretrain: what counts as a positive -- the other view of the image (default), or every row of its study / patient")
@@ -911,27 +923,47 @@ def init_backbone_options(args):
     return init
 
 
+PRETRAIN_PROJ_DIM = {"contrastive": 128, "barlow": 512}         # the default --proj_dim of each kind
+
+
+def pretrain_kind(pretrain):
+    """'contrastive' or 'barlow' of a pretrain_options dict (the contrastive one has no "kind" entry), None for None."""
+    return None if pretrain is None else pretrain.get("kind", "contrastive")
+
+
 def pretrain_options(args, world=1):
-    """--pretrain contrastive and its flags checked before anything runs: None without it, else {"proj_dim", "temperature" (None: a
-    restored checkpoint's, else 0.2: temperature_of), "positive"}.  What the contrastive step cannot be combined with is refused with a
-    one-line reason (ValueError)."""
+    """--pretrain contrastive | barlow and its flags checked before anything runs: None without it; for contrastive {"proj_dim",
+    "temperature" (None: a restored checkpoint's, else 0.2: temperature_of), "positive"}; for barlow {"kind": "barlow", "proj_dim",
+    "lambd" (None: a restored checkpoint's, else 0.0051: lambda_of), "positive": "view"}.  What the step cannot be combined with is
+    refused with a one-line reason (ValueError)."""
     proj, tau, positive = getattr(args, "proj_dim", None), getattr(args, "temperature", None), getattr(args, "positive", None)
-    if getattr(args, "pretrain", None) is None:
+    lambd = getattr(args, "barlow_lambda", None)
+    kind = getattr(args, "pretrain", None)
+    if kind is None:
         if proj is not None or tau is not None or positive is not None:
             raise ValueError("--proj_dim / --temperature / --positive belong to --pretrain contrastive: pass it with them")
+        if lambd is not None:
+            raise ValueError("--barlow_lambda belongs to --pretrain barlow: pass it with it")
         return None
     from ._lib import NTXENT_MAX_D, NTXENT_MAX_N
-    from .loss import check_temperature
+    from .loss import check_lambda, check_temperature
 
     def no(flag, why):
-        raise ValueError("--pretrain contrastive cannot be combined with %s: %s" % (flag, why))
+        raise ValueError("--pretrain %s cannot be combined with %s: %s" % (kind, flag, why))
+    if kind == "barlow":
+        if tau is not None:
+            no("--temperature", "the Barlow Twins loss has none (its one number is --barlow_lambda)")
+        if positive not in (None, "view"):
+            no("--positive %s" % positive, "the loss pairs the two views of an image and has no notion of several positives")
+    elif lambd is not None:
+        no("--barlow_lambda", "it belongs to --pretrain barlow")
     if not args.train:
-        raise ValueError("--pretrain contrastive is a training mode: pass --train with it")
+        raise ValueError("--pretrain %s is a training mode: pass --train with it" % kind)
     for flag in ("evaluate_single_model", "evaluate_ensemble", "visualize", "plot_roc"):
         if getattr(args, flag, False):
             no("--" + flag, "the head is a projection, not a classifier: there are no findings to score or draw")
     if not (args.affine or args.jitter):
-        raise ValueError("--pretrain contrastive needs --affine or --jitter (or both): without a random step the two views of an image are identical")
+        raise ValueError("--pretrain %s needs --affine or --jitter (or both): without a random step the two views of an image are identical" % kind)
     if getattr(args, "mixup", 0.0) > 0 or getattr(args, "cutmix", 0.0) > 0 or getattr(args, "erase_prob", 0.0) > 0:
         no("--mixup / --cutmix / --erase_prob", "they mix or blank rows of the batch, whose labels the contrastive step does not read")
     if getattr(args, "loss", "bce") != "bce":
@@ -944,11 +976,15 @@ def pretrain_options(args, world=1):
         no("--head %s" % args.head, "the projection is the linear head")
     if world > 1:
         no("more than one rank (world size %d)" % world, "each rank would contrast its own rows only; gathering embeddings is not built")
-    proj = 128 if proj is None else proj
-    if not 1 <= proj <= NTXENT_MAX_D:
+    proj = PRETRAIN_PROJ_DIM[kind] if proj is None else proj
+    if not 1 <= proj <= NTXENT_MAX_D:                  # (BARLOW_MAX_D and BARLOW_MAX_N are the same caps)
         raise ValueError("--proj_dim takes 1 .. %d (got %r)" % (NTXENT_MAX_D, proj))
     if 2 * args.batch_size > NTXENT_MAX_N:
-        raise ValueError("--pretrain contrastive sees 2 x --batch_size rows per step, at most %d (got 2 x %d)" % (NTXENT_MAX_N, args.batch_size))
+        raise ValueError("--pretrain %s sees 2 x --batch_size rows per step, at most %d (got 2 x %d)" % (kind, NTXENT_MAX_N, args.batch_size))
+    if kind == "barlow":
+        if lambd is not None:
+            check_lambda("--barlow_lambda", lambd)
+        return {"kind": "barlow", "proj_dim": int(proj), "lambd": lambd, "positive": "view"}
     if tau is not None:
         check_temperature("--temperature", tau)
     positive = positive or "view"
@@ -1104,8 +1140,15 @@ def temperature_of(pretrain, restored_loss=None):
     return float((restored_loss or {}).get("temperature", 0.2))
 
 
+def lambda_of(pretrain, restored_loss=None):
+    """The lambda of a --pretrain barlow run: --barlow_lambda, else a restored checkpoint's, else 0.0051 (the paper's)."""
+    if pretrain["lambd"] is not None:
+        return float(pretrain["lambd"])
+    return float((restored_loss or {}).get("lambd", 0.0051))
+
+
 def check_checkpoint_pretrain(ck, pretrain, path, weight_key=None):
-    """A checkpoint of --pretrain contrastive continues such a run and nothing else (its head is a projection: --init_backbone takes
+    """A checkpoint of --pretrain contrastive | barlow continues a run of its own kind and nothing else (its head is a projection: --init_backbone takes
     its backbone into a supervised run); a supervised checkpoint does not continue a pretraining run.  weight_key: the state_dict key
     of the classifier's weight (classifier_keys), whose rows are the checkpoint's --proj_dim."""
     stored = ck.get("pretrain")
@@ -1113,8 +1156,11 @@ def check_checkpoint_pretrain(ck, pretrain, path, weight_key=None):
         raise ValueError("--restore %s: the checkpoint is one of --pretrain %s, whose head is a projection: continue it with --pretrain "
                          "%s, or start a supervised run from its backbone with --init_backbone" % (path, stored, stored))
     if stored is None and pretrain is not None:
-        raise ValueError("--restore %s: the checkpoint is a supervised one; --pretrain contrastive continues a pretraining run (its "
-                         "backbone can start one: --init_backbone)" % path)
+        raise ValueError("--restore %s: the checkpoint is a supervised one; --pretrain %s continues a pretraining run (its "
+                         "backbone can start one: --init_backbone)" % (path, pretrain_kind(pretrain)))
+    if stored is not None and stored != pretrain_kind(pretrain):
+        raise ValueError("--restore %s: the checkpoint is one of --pretrain %s, this run is --pretrain %s: the two losses train "
+                         "different projections (its backbone can start this run: --init_backbone)" % (path, stored, pretrain_kind(pretrain)))
     if stored is not None and weight_key is not None and weight_key in ck["state_dict"]:
         width = ck["state_dict"][weight_key].shape[0]
         if width != pretrain["proj_dim"]:
@@ -1173,7 +1219,7 @@ def head_width(args):
     """Outputs of the classifier: --n_classes findings, three logits each under --uncertain multiclass; under --pretrain contrastive
     the width of the projection, --proj_dim."""
     if getattr(args, "pretrain", None) is not None:
-        return getattr(args, "proj_dim", None) or 128
+        return getattr(args, "proj_dim", None) or PRETRAIN_PROJ_DIM[args.pretrain]
     return args.n_classes * (3 if getattr(args, "uncertain", "ones") == "multiclass" else 1)
 
 
@@ -1901,6 +1947,14 @@ def wire_loss(run):
     args, model, pos_weight, restored_loss = run.args, run.model, run.pos_weight, run.restored_loss
     focus, hier, aucm = run.focus, run.hier, run.aucm
     criterion = summed_bce
+    if pretrain_kind(run.pretrain) == "barlow":
+        # as below, with lambda in the place of the temperature: --barlow_lambda has the last word, else a restored checkpoint's value
+        from .loss import BarlowTwinsLoss
+        lambd = lambda_of(run.pretrain, restored_loss)
+        model.set_loss(kind="barlow", lambd=lambd)
+        criterion = BarlowTwinsLoss(lambd)
+        criterion.lambd = model.loss_lambda
+        return criterion, None, None
     if run.pretrain is not None:
         # the fused step's loss and, by the same kernels, the autograd route's; one storage for the temperature: the module reads what
         # the model holds.  --temperature has the last word, else a restored checkpoint's value
@@ -2069,7 +2123,11 @@ def log_line(run, loss):
     """What a --log_interval step prints, as a dict.  (loss.item() synchronises; the optimiser's figures then read the device.)"""
     ex, optimizer = run.ex, run.optimizer
     line = {"step": run.args.step, "train_loss": round(loss.item(), 5)}
-    if run.pretrain is not None:            # the share of this minibatch's anchors whose nearest row is a positive
+    if pretrain_kind(run.pretrain) == "barlow":     # the two terms of this minibatch's loss, the off-diagonal one without its weight
+        from .loss import barlow_terms
+        on, off, _, _ = barlow_terms(run.last_logits, run.last_ids)
+        line["on_diag"], line["off_diag"] = round(on, 5), round(off, 5)
+    elif run.pretrain is not None:            # the share of this minibatch's anchors whose nearest row is a positive
         from .loss import contrastive_top1
         line["top1"] = round(contrastive_top1(run.last_logits, run.last_ids), 4)
     if ex.get("max_grad_norm") is not None or ex.get("skip_nonfinite"):
@@ -2097,7 +2155,7 @@ def checkpoint_dict(run, res, ema_sd):
     if ema_sd is not None:        # beside the live weights, which restore continues from
         ckpt["ema_state_dict"] = ema_sd
     if run.pretrain is not None:  # eval_loss is the contrastive loss; avg_auc = -eval_loss: save_checkpoint keeps the lowest-loss files
-        ckpt["pretrain"], ckpt["avg_auc"] = "contrastive", -ckpt["eval_loss"]
+        ckpt["pretrain"], ckpt["avg_auc"] = pretrain_kind(run.pretrain), -ckpt["eval_loss"]
         ckpt["loss_state"] = dict(model.loss_state(), positive=run.pretrain["positive"])
     elif run.aucm is not None:    # the auxiliary scalars are trained state: restore continues from them
         sync_loss_aux(model, run.aucm_loss)
@@ -2117,6 +2175,8 @@ def contrastive_eval(run):
     """--pretrain contrastive at an evaluation: the contrastive loss (the mean over the anchors of the whole set, each contrasted within
     its minibatch of two views) and the top-1 share over the validation set, in eval mode, from views drawn from a fixed seed.
     Printed, written to pretrain_eval_step_<n>.json, and returned in the shape checkpoint_dict reads ({"loss": {...}})."""
+    if pretrain_kind(run.pretrain) == "barlow":
+        return barlow_eval(run)
     from .loss import contrastive_top1
     args, model = run.args, run.model
     model.eval()
@@ -2144,6 +2204,44 @@ def contrastive_eval(run):
     if run.rank == 0:
         print("Evaluate contrastive pretraining @ step %d: loss %.5f, top1 %.4f over %d anchors" % (args.step, res["loss"]["contrastive"],
                                                                                                  res["top1"], anchors))
+        json.dump(res, open(os.path.join(args.output_dir, "pretrain_eval_step_%d.json" % args.step), "w"), indent=4)
+    return res
+
+
+@torch.no_grad()
+def barlow_eval(run):
+    """--pretrain barlow at an evaluation: the Barlow Twins loss and its terms over the validation set, in eval mode, from views drawn
+    from a fixed seed -- each minibatch of two views is normalised and correlated within itself, and the figures are the means over
+    the minibatches weighted by their pairs m (a last minibatch of one image has no pair statistics and weighs nothing).  Printed,
+    written to pretrain_eval_step_<n>.json, and returned in the shape checkpoint_dict reads ({"loss": {...}})."""
+    from .loss import barlow_terms
+    args, model = run.args, run.model
+    model.eval()
+    lambd = float(model.loss_lambda.item())
+    sums, pairs = np.zeros(4), 0
+    for b, (x, _, idx) in enumerate(batches(run.valid_ds, list(range(len(run.valid_ds))), args.batch_size, False)):
+        x, ids = two_views(run, run.affine, x.to(run.device), idx, EVAL_VIEW_STEP + b, None)
+        out = model(x)
+        on, off, diag, m = barlow_terms(out, ids)
+        if m >= 2:
+            sums += m * np.array([float(run.criterion(out, ids).item()), on, off, diag])
+            pairs += m
+    mean = sums / max(pairs, 1)
+    res = {"pretrain": "barlow", "step": args.step, "loss": {"barlow": float(mean[0])}, "on_diag": float(mean[1]), "off_diag": float(mean[2]),
+           "mean_diag": float(mean[3]), "pairs": int(pairs), "lambda": lambd}
+    knn_res, lin_res = run_probes(run)
+    model.eval()
+    if knn_res is not None:
+        res["knn"] = knn_res
+        if run.rank == 0:
+            print_knn(knn_res, args.step)
+    if lin_res is not None:
+        res["linear_probe"] = probe_report(lin_res)
+        if run.rank == 0:
+            print_probe(lin_res, args.step)
+    if run.rank == 0:
+        print("Evaluate Barlow Twins pretraining @ step %d: loss %.5f (on %.5f, off %.5f, mean diagonal %.4f) over %d pairs"
+              % (args.step, res["loss"]["barlow"], res["on_diag"], res["off_diag"], res["mean_diag"], pairs))
         json.dump(res, open(os.path.join(args.output_dir, "pretrain_eval_step_%d.json" % args.step), "w"), indent=4)
     return res
 

@@ -9,7 +9,9 @@ and which `collapse_multiclass` turns into binary ones (cx_mc3_collapse), Hierar
 conditional / unconditional loss over the findings' tree, whose conditional logits `collapse_hierarchy` turns into unconditional
 ones (cx_hier_collapse), NTXentLoss for kind "ntxent" (cx_ntxent_fwd_bwd), the contrastive NT-Xent / SupCon loss of (N, d)
 embeddings against an (N, 1) column of ids, the one loss that couples the rows of a batch; `reference_ntxent` states it in float64
-numpy and `contrastive_top1` is its accuracy figure.  Device tensors only: there is no CPU path (but for the numpy statement)."""
+numpy and `contrastive_top1` is its accuracy figure, BarlowTwinsLoss for kind "barlow" (cx_barlow_fwd_bwd, csrc/barlow.hip), the
+cross-correlation loss of the two views' batch-normalised embeddings, with `reference_barlow` as its float64 statement and
+`barlow_terms` as its monitor.  Device tensors only: there is no CPU path (but for the numpy statement)."""
 import math
 
 import numpy as np
@@ -19,7 +21,8 @@ import torch.nn as nn
 from . import ops
 
 KERNEL = {"bce": "cx_bce_masked_fwd_bwd", "aucm": "cx_aucm_fwd_bwd", "focal": "cx_asl_fwd_bwd", "asl": "cx_asl_fwd_bwd",
-          "multiclass": "cx_mc3_fwd_bwd", "hier": "cx_hier_fwd_bwd", "ntxent": "cx_ntxent_fwd_bwd"}
+          "multiclass": "cx_mc3_fwd_bwd", "hier": "cx_hier_fwd_bwd", "ntxent": "cx_ntxent_fwd_bwd",
+          "barlow": "cx_barlow_fwd_bwd"}
 WIDTH = {"multiclass": 3}          # logits per target element, where it is not 1
 
 
@@ -99,14 +102,26 @@ def check_temperature(who, temperature):
     return t
 
 
+def check_lambda(who, lambd):
+    """The off-diagonal weight of the Barlow Twins loss as a float: finite and >= 0."""
+    try:
+        v = float(lambd)
+    except (TypeError, ValueError):
+        raise ValueError("%s takes lambd, a number >= 0 (got %r)" % (who, lambd))
+    if not 0 <= v < float("inf"):
+        raise ValueError("%s takes a finite lambd >= 0 (got %r)" % (who, lambd))
+    return v
+
+
 # ------------------------------------------------------------------------------------------------ the loss of a step
 class Loss:
-    """The loss of a step: `kind` ('bce', 'aucm', 'focal', 'asl', 'multiclass', 'hier', 'ntxent'), `ignore_negative`, `margin` (a host float, passed
+    """The loss of a step: `kind` ('bce', 'aucm', 'focal', 'asl', 'multiclass', 'hier', 'ntxent', 'barlow'), `ignore_negative`, `margin` (a host float, passed
     by value), `mode` (kind 'hier': 'conditional' or 'unconditional', a host value like the margin, None elsewhere), `parent` (kind
     'hier': the int32 (n,) device table of each label's parent, -1 for a root) and the fp32 device tensors the kernels read -- `pos_weight` (n,), `focus` (4,) = [gamma+, gamma-, clip, alpha or -1],
     `aux` and `daux` (3, n) = rows a, b, alpha and their gradients, `prior` (n,), `lr_aux` (1,), `class_weight` (n, 3) = the weights
     of kind 'multiclass', whose head has 3n outputs, `temperature` (1,) of kind 'ntxent', whose logits are (N, d) embeddings and whose
-    target is the (N, 1) column of ids --, None where the kind has none.  Kind 'ntxent' also holds the kernels' scratch, sized by the
+    target is the (N, 1) column of ids, `lambd` (1,) of kind 'barlow', which takes the same operands --, None where the kind has none.
+    Kinds 'ntxent' and 'barlow' also hold the kernels' scratch, sized by the
     first launch that needs it (never under a graph capture: a captured step's warm-up runs have sized it).  Plain
     tensors, neither buffers nor parameters.  Behind them stands held storage (`_held`, by name) that outlives a change of kind: a
     repeated set() with the same sizes copies into it, so a captured step, which replays the storage it was captured with, sees the
@@ -114,9 +129,9 @@ class Loss:
     one per call from its own attributes."""
 
     def __init__(self, kind="bce", ignore_negative=False, margin=1.0, pos_weight=None, focus=None, aux=None, daux=None, prior=None,
-                 lr_aux=None, class_weight=None, parent=None, mode=None, temperature=None):
+                 lr_aux=None, class_weight=None, parent=None, mode=None, temperature=None, lambd=None):
         self.kind, self.ignore_negative, self.margin = kind, ignore_negative, margin
-        self.temperature = temperature
+        self.temperature, self.lambd = temperature, lambd
         self.parent, self.mode = parent, mode
         self.pos_weight, self.focus, self.aux, self.daux, self.prior, self.lr_aux = pos_weight, focus, aux, daux, prior, lr_aux
         self.class_weight = class_weight
@@ -129,6 +144,10 @@ class Loss:
         'multiclass' takes (B, 3n) logits and dlogits beside the (B, n) target and element losses."""
         if self.kind == "ntxent":
             ops.ntxent_fwd_bwd(logits, target, self.temperature, loss, loss_elem, dlogits, None, self._scratch(logits))
+        elif self.kind == "barlow":
+            if loss_elem is not None:
+                raise RuntimeError("the Barlow Twins loss has no element losses")
+            ops.barlow_fwd_bwd(logits, target, self.lambd, loss, dlogits, None, self._scratch(logits))
         elif self.kind == "aucm":
             if loss_elem is not None:
                 raise RuntimeError("the AUC-margin loss has no element losses")
@@ -145,14 +164,15 @@ class Loss:
             ops.bce_fwd_bwd(logits, target, loss, loss_elem, dlogits)
 
     def _scratch(self, logits):
-        """The held scratch of kind 'ntxent' for these (N, d) embeddings: made on first use and when it is too small or on another
-        device, which a stream under capture must not do."""
-        need = ops.ntxent_scratch(*logits.shape)
+        """The held scratch of kinds 'ntxent' and 'barlow' for these (N, d) embeddings: made on first use and when it is too small or
+        on another device, which a stream under capture must not do."""
+        barlow = self.kind == "barlow"
+        need = (ops.barlow_scratch if barlow else ops.ntxent_scratch)(*logits.shape)
         held = self._held.get("scratch")
         if held is None or held.numel() < need or held.device != logits.device:
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("the contrastive loss would allocate its scratch (%d floats) under a graph capture: run one step of "
-                                   "this batch size before capturing" % need)
+                raise RuntimeError("the %s loss would allocate its scratch (%d floats) under a graph capture: run one step of "
+                                   "this batch size before capturing" % ("Barlow Twins" if barlow else "contrastive", need))
             held = self._held["scratch"] = torch.empty(need, dtype=torch.float32, device=logits.device)
         return held
 
@@ -171,7 +191,7 @@ class Loss:
         return held
 
     def _put(self, who, dev, kind, ignore_negative, pos_weight=None, focus=None, prior=None, margin=None, lr_aux=None,
-             class_weight=None, parent=None, mode=None, temperature=None):
+             class_weight=None, parent=None, mode=None, temperature=None, lambd=None):
         """The one place that writes the state, after every check: each field is assigned, to None where `kind` has none, so nothing
         of the previous kind is left over.  `aux` starts at zero coming from another kind and stays as trained coming from 'aucm';
         the margin stays what the last 'aucm' made it."""
@@ -185,15 +205,19 @@ class Loss:
         self.class_weight = self._hold("class_weight", class_weight, dev)
         self.parent, self.mode = self._hold("parent", parent, dev, dtype=torch.int32), mode
         self.temperature = self._hold("temperature", None if temperature is None else [temperature], dev)
+        self.lambd = self._hold("lambd", None if lambd is None else [lambd], dev)
         self.kind, self.ignore_negative = kind, ignore_negative
         if margin is not None:
             self.margin = float(margin)
 
     def set(self, dev, n, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
-            alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None, temperature=None):
+            alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None, temperature=None,
+            lambd=None):
         """FusedNet.set_loss for a model whose head has n outputs, with its parameters on dev.  A refused call changes nothing."""
         if kind not in KERNEL:
-            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal', 'asl', 'multiclass', 'hier' or 'ntxent' (got %r)" % (kind,))
+            raise ValueError("set_loss(kind=...) takes 'bce', 'aucm', 'focal', 'asl', 'multiclass', 'hier', 'ntxent' or 'barlow' (got %r)" % (kind,))
+        if kind != "barlow" and lambd is not None:
+            raise ValueError("set_loss: lambd belongs to kind='barlow'")
         if kind != "ntxent" and temperature is not None:
             raise ValueError("set_loss: temperature belongs to kind='ntxent'")
         if kind != "hier" and (parent is not None or mode is not None):
@@ -231,6 +255,13 @@ class Loss:
             if n > ops.NTXENT_MAX_D:
                 raise ValueError("%s takes embeddings of at most %d values; this head has %d outputs" % (who, ops.NTXENT_MAX_D, n))
             self._put(who, dev, kind, False, temperature=check_temperature(who, 0.2 if temperature is None else temperature))
+        elif kind == "barlow":
+            if pos_weight is not None or ignore_negative:
+                raise ValueError("%s cannot be combined with pos_weight or ignore_negative: its target is a column of ids, of which a "
+                                 "negative one takes its pair out of the batch" % who)
+            if n > ops.BARLOW_MAX_D:
+                raise ValueError("%s takes embeddings of at most %d values; this head has %d outputs" % (who, ops.BARLOW_MAX_D, n))
+            self._put(who, dev, kind, False, lambd=check_lambda(who, 0.0051 if lambd is None else lambd))
         elif kind == "hier":
             if ignore_negative:
                 raise ValueError("%s always ignores a target < 0; ignore_negative is the cross-entropy's switch" % who)
@@ -266,6 +297,8 @@ class Loss:
             d["parent"], d["mode"] = cpu(self.parent), self.mode
         if self.kind == "ntxent":
             d["temperature"] = float(self.temperature.item())
+        if self.kind == "barlow":
+            d["lambd"] = float(self.lambd.item())
         return d
 
     def load_state(self, d, dev, n):
@@ -295,6 +328,10 @@ class Loss:
             if d.get("temperature") is None:
                 raise ValueError("load_loss_state: kind 'ntxent' needs temperature")
             self.set(dev, n, kind="ntxent", temperature=d["temperature"])
+        elif kind == "barlow":
+            if d.get("lambd") is None:
+                raise ValueError("load_loss_state: kind 'barlow' needs lambd")
+            self.set(dev, n, kind="barlow", lambd=d["lambd"])
         elif kind != "bce":
             raise ValueError("load_loss_state: unknown loss kind %r" % (kind,))
         elif self.kind != "bce":               # (a model that holds the cross-entropy keeps its options)
@@ -304,12 +341,12 @@ class Loss:
 # ------------------------------------------------------------------------------------------------ the autograd route
 def _operands(logits, target, who, kind):
     """The contiguous fp32 logits and targets of a loss module: (B, n) both, or (B, 3n) against (B, n) for kind 'multiclass', or (N, d)
-    embeddings against an (N, 1) column of ids for kind 'ntxent'."""
+    embeddings against an (N, 1) column of ids for kinds 'ntxent' and 'barlow' (which needs N >= 2)."""
     width = WIDTH.get(kind, 1)
     if not logits.is_cuda:
         raise RuntimeError("%s runs on the GPU only (%s); there is no CPU fallback" % (who, KERNEL[kind]))
-    if kind == "ntxent":
-        if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or tuple(target.shape) != (logits.shape[0], 1):
+    if kind in ("ntxent", "barlow"):
+        if logits.dim() != 2 or logits.shape[0] < (2 if kind == "barlow" else 1) or logits.shape[1] < 1 or tuple(target.shape) != (logits.shape[0], 1):
             raise RuntimeError("%s takes (N, d) embeddings and an (N, 1) column of ids (got %s and %s)" % (who, tuple(logits.shape), tuple(target.shape)))
         return logits.detach().contiguous().float(), target.detach().contiguous().float()
     if logits.dim() != 2 or logits.shape[1] % width or tuple(target.shape) != (logits.shape[0], logits.shape[1] // width):
@@ -647,3 +684,98 @@ def contrastive_top1(logits, ids, return_counts=False):
     if return_counts:
         return hits, total
     return hits / total if total else math.nan
+
+
+# ------------------------------------------------------------------------------------------------ Barlow Twins pretraining
+BARLOW_EPS = 1e-5           # CX_BARLOW_EPS: the epsilon of the batch normalisation
+
+
+def reference_barlow(e, ids, lambd, dtype=np.float64):
+    """The statement of cx_barlow_fwd_bwd in numpy, in `dtype` (float64: the reference; float32: a model of fp32 rounding in another
+    summation order than the kernels', which the tests hold their tolerance against).  e (N, d), ids (N,) or (N, 1), lambd >= 0 (used
+    as the fp32 value the kernels read).  h = N // 2; row p < h is view A of pair p, row p + h view B, an odd last row belongs to no
+    pair; V = {p : ids_p >= 0 and ids_{p+h} >= 0}, m = |V|.  Per view and column over V: mu = mean, v = the biased variance (two
+    passes), a^ = (a - mu) / sqrt(v + 1e-5); C = A^T B^ / m; on = sum_k (1 - C_kk)^2, off = sum_{k != l} C_kl^2, loss = on + lambd
+    off.  The gradient is the full chain: G_kk = -2 (1 - C_kk), G_kl = 2 lambd C_kl, da^ = b^ G^T / m, db^ = a^ G / m, then
+    BatchNorm's backward da = (da^ - mean_p da^ - a^ mean_p (da^ o a^)) / sqrt(v + eps); rows outside V and the odd row are zeros,
+    and what they hold (NaN included) is never read.  m < 2: loss 0, gradient 0.  Returns {"loss", "on", "off": floats, "C": (d, d),
+    "grad": (N, d), "m": int, "mean_diag": float, "ahat", "bhat": (m, d), "valid": the boolean (h,) mask, "istd": (2, d)}."""
+    e = np.asarray(e)
+    g = np.asarray(ids, dtype=np.float64).reshape(-1)
+    N, d = e.shape
+    h = N // 2
+    lam = dtype(np.float32(lambd))
+    valid = (g[:h] >= 0) & (g[h:2 * h] >= 0)
+    m = int(valid.sum())
+    out = {"m": m, "valid": valid, "grad": np.zeros((N, d), dtype=dtype)}
+    if m < 2:
+        out.update(loss=0.0, on=0.0, off=0.0, mean_diag=0.0, C=np.zeros((d, d), dtype=dtype), ahat=np.zeros((m, d), dtype=dtype),
+                   bhat=np.zeros((m, d), dtype=dtype), istd=np.zeros((2, d), dtype=dtype))
+        return out
+    mm, eps = dtype(m), dtype(BARLOW_EPS)
+
+    def normalise(x):
+        mu = x.sum(0, dtype=dtype) / mm
+        c = x - mu
+        v = (c * c).sum(0, dtype=dtype) / mm
+        istd = dtype(1) / np.sqrt(v + eps)
+        return (c * istd).astype(dtype), istd.astype(dtype)
+
+    a, b = np.asarray(e[:h][valid], dtype=dtype), np.asarray(e[h:2 * h][valid], dtype=dtype)
+    ah, ia = normalise(a)
+    bh, ib = normalise(b)
+    C = ((ah.T @ bh) / mm).astype(dtype)
+    eye = np.eye(d, dtype=bool)
+    t = dtype(1) - np.diag(C)
+    on = (t * t).sum(dtype=dtype)
+    off = np.where(eye, dtype(0), C * C).sum(1, dtype=dtype).sum(dtype=dtype)
+    G = np.where(eye, dtype(-2) * (dtype(1) - C), dtype(2) * lam * C).astype(dtype)
+    dah, dbh = ((bh @ G.T) / mm).astype(dtype), ((ah @ G) / mm).astype(dtype)
+
+    def back(dx, xh, istd):
+        return ((dx - dx.sum(0, dtype=dtype) / mm - xh * ((dx * xh).sum(0, dtype=dtype) / mm)) * istd).astype(dtype)
+
+    rows = np.flatnonzero(valid)
+    out["grad"][rows] = back(dah, ah, ia)
+    out["grad"][rows + h] = back(dbh, bh, ib)
+    out.update(loss=float(on + lam * off), on=float(on), off=float(off), mean_diag=float(np.diag(C).sum(dtype=dtype) / dtype(d)), C=C,
+               ahat=ah, bhat=bh, istd=np.stack([ia, ib]))
+    return out
+
+
+class BarlowTwinsLoss(_LossModule):
+    """The Barlow Twins loss (Zbontar et al., ICML 2021) of (N, d) embeddings whose rows p and p + N // 2 are two views of one image
+    (augment.duplicate_views' [x; x] layout), against an (N, 1) column of ids read as a mask (a pair with an id < 0 in either row is out
+    of the batch): both views are batch-normalised over the pairs, and their d x d cross-correlation matrix is pushed towards the
+    identity, loss = sum_k (1 - C_kk)^2 + lambd sum_{k != l} C_kl^2; `reference_barlow` is the definition.  The loss of
+    FusedNet.set_loss(kind="barlow") for the autograd route, by the same kernels, so `loss.backward()` leaves the fused step's d loss /
+    d logits bit for bit.  lambd: finite, >= 0; it lives in a one-float tensor (`lambd`) that may be rewritten in place.  There are no
+    element losses: elementwise() raises."""
+    kind = "barlow"
+
+    def __init__(self, lambd=0.0051):
+        super().__init__()
+        self.lambd = torch.tensor([check_lambda("BarlowTwinsLoss", lambd)], dtype=torch.float32)
+        self._scratch = None
+
+    def _state(self, logits):
+        self._on(logits.device, "lambd")
+        state = Loss("barlow", False, lambd=self.lambd)
+        if self._scratch is not None:
+            state._held["scratch"] = self._scratch
+        self._scratch = state._scratch(logits)               # (the module keeps it from call to call)
+        return state
+
+
+@torch.no_grad()
+def barlow_terms(logits, ids):
+    """(on, off, mean_diag, m) of the Barlow Twins loss of these device embeddings (cx_barlow_fwd_bwd's stats): the diagonal term
+    sum_k (1 - C_kk)^2, the off-diagonal term sum_{k != l} C_kl^2 without its weight, the mean of the diagonal of C (1 when the two
+    views agree in every coordinate) and the pairs in the batch: the monitor of this pretraining, next to contrastive_top1.  logits
+    (N, d), ids (N, 1) or (N,).  Floats and an int; zeros where fewer than two pairs are in the batch."""
+    x, t = _operands(logits, ids.reshape(-1, 1), "barlow_terms", "barlow")
+    stats = torch.empty(4, dtype=torch.float32, device=x.device)
+    zero = torch.zeros(1, dtype=torch.float32, device=x.device)               # (the terms do not depend on lambd)
+    ops.barlow_fwd_bwd(x, t, zero, None, None, stats)
+    on, off, diag, m = stats.tolist()
+    return on, off, diag, int(m)

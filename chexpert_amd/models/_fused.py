@@ -68,6 +68,11 @@ AUCM_DATA_PARALLEL = ("the AUC-margin loss (kind='aucm') is not supported data-p
                       "cross-entropy")
 
 
+BARLOW_DATA_PARALLEL = ("the Barlow Twins loss (kind='barlow') is not supported data-parallel (world size %d): each rank would normalise and "
+                        "correlate its own rows only, and gathering the embeddings across ranks (with the gradient's way back) has not "
+                        "been built -- pretrain on one GPU")
+
+
 NTXENT_DATA_PARALLEL = ("the contrastive loss (kind='ntxent') is not supported data-parallel (world size %d): each rank would contrast "
                         "its own rows only, and gathering the embeddings across ranks (with the gradient's way back) has not been built "
                         "-- pretrain on one GPU")
@@ -134,7 +139,8 @@ class FusedNet(nn.Module):
         self._head_kind = "linear"       # set_head(): "csra" adds the buffer head_attn = [lambda, T]; "pcam" adds nothing
 
     def set_loss(self, ignore_negative=False, pos_weight=None, *, kind="bce", prior=None, margin=1.0, lr_aux=None, gamma=None,
-                 alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None, temperature=None):
+                 alpha=None, gamma_pos=None, gamma_neg=None, clip=None, class_weight=None, parent=None, mode=None, temperature=None,
+                 lambd=None):
         """The loss of forward_backward.  ignore_negative: a target < 0 (an uncertain label kept as -1, the U-Ignore policy) adds no
         loss and no gradient; the divisor stays the batch size.  pos_weight: None, or n_classes positive-term weights as in torch's
         BCEWithLogitsLoss(pos_weight).  Either option routes the step through cx_bce_masked_fwd_bwd, which skips every target < 0:
@@ -214,10 +220,19 @@ class FusedNet(nn.Module):
         captured step's replay sees that, as it sees `model.loss_temperature.fill_(0.1)`.  The kernels' scratch is held with the loss
         state and sized by the first step of a batch size (a capture's warm-up steps).  Both views of an image pass through the
         network in ONE batch, so BatchNorm's statistics are shared between them, as in SimCLR.  The data-parallel step is refused:
-        the negatives would be each rank's own, and gathering embeddings across ranks is a feature of its own."""
+        the negatives would be each rank's own, and gathering embeddings across ranks is a feature of its own.
+
+        kind="barlow" (lambd=0.0051) is Barlow Twins pretraining, the loss that needs neither negatives nor a large batch: the same
+        operands as kind="ntxent" -- the head's n <= 1024 outputs are an embedding, the target an (N, 1) fp32 column of ids, rows p and
+        p + N // 2 the two views of an image -- but the ids are a mask only (a pair with an id < 0 in either row is out of the batch).
+        Both views are batch-normalised over the pairs, and loss = sum_k (1 - C_kk)^2 + lambd sum_{k != l} C_kl^2 over their d x d
+        cross-correlation matrix C (cx_barlow_fwd_bwd, csrc/barlow.hip: the products run on the fp32-input MFMA; the definition stands
+        in include/chexpert_hip.h and, in numpy, in loss.reference_barlow).  lambd (finite, >= 0) lives in one fp32 device tensor,
+        `loss_lambda`, under the storage rule of `loss_temperature`; the scratch is held and sized the same way.  pos_weight,
+        ignore_negative=True, temperature and every other kind's keyword are refused; so is the data-parallel step."""
         self._loss.set(next(self.parameters()).device, self._n_classes(), ignore_negative, pos_weight, kind=kind, prior=prior,
                        margin=margin, lr_aux=lr_aux, gamma=gamma, alpha=alpha, gamma_pos=gamma_pos, gamma_neg=gamma_neg, clip=clip,
-                       class_weight=class_weight, parent=parent, mode=mode, temperature=temperature)
+                       class_weight=class_weight, parent=parent, mode=mode, temperature=temperature, lambd=lambd)
         return self
 
     # ---- the global pooling in front of the classifier
@@ -474,6 +489,8 @@ class FusedNet(nn.Module):
             check_aucm_single_process(eng.reducer)
         if L.kind == "ntxent":
             check_single_process(eng.reducer, NTXENT_DATA_PARALLEL)
+        if L.kind == "barlow":
+            check_single_process(eng.reducer, BARLOW_DATA_PARALLEL)
         eng.track_stats = bool(track_stats)
         try:
             ws = eng.forward(x, self.training, record=True)
@@ -494,6 +511,7 @@ class FusedNet(nn.Module):
 # what set_loss holds, readable on the model (read-only: set_loss writes; a tensor may be written in place)
 for _name in ("kind", "ignore_negative", "pos_weight", "margin", "aux", "prior", "lr_aux", "focus", "class_weight", "parent", "mode", "temperature", "daux"):
     setattr(FusedNet, ("_loss_" if _name == "daux" else "loss_") + _name, property(lambda self, _name=_name: getattr(self._loss, _name)))
+FusedNet.loss_lambda = property(lambda self: self._loss.lambd)
 
 
 # --------------------------------------------------------------------------------------------- engine side

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib as L
 from ._lib import (BOOT_MAX_POINTS, BOOT_MAX_TILES, BOOT_MAX_UNITS, BOOT_SENS, BOOT_SPEC, BOOT_TILE, CALIB_MAX_BINS, CALIB_MAX_ITER,
-                   CALIB_METHODS, DELONG_MAX_ROWS, DELONG_TILE, DELONG_WG_ENTRIES, EPI_JOIN, EPI_MASK, EPI_STORE, HIER_MAX_LABELS, HIER_MAX_PATH, NTXENT_MAX_D, NTXENT_MAX_N,
+                   CALIB_METHODS, DELONG_MAX_ROWS, DELONG_TILE, DELONG_WG_ENTRIES, EPI_JOIN, EPI_MASK, EPI_STORE, HIER_MAX_LABELS, HIER_MAX_PATH, NTXENT_MAX_D, NTXENT_MAX_N, BARLOW_MAX_D, BARLOW_MAX_N,
                    KNN_MAX_CLASSES, KNN_MAX_D, KNN_MAX_K, KNN_MAX_SPLITS, PROBE_MAX_HISTORY, PROBE_MAX_SPLITS,
                    MODE_CONV, MODE_POOL2, MODE_STEM, PRO_AFFINE2, PRO_AFFINE_RELU, PRO_JOIN, PRO_NONE, CxConv, CxWgrad, check, lib, ptr, require_cuda, stream_ptr)
 import ctypes as C
@@ -1059,6 +1059,44 @@ def probe_lbfgs_advance(theta, grad, direction, t, mode, theta_t, grad_t, s_hist
     require_cuda(theta, grad, direction, t, mode, theta_t, grad_t, s_hist, y_hist, hist, tstats)
     check(lib().cx_probe_lbfgs_advance(ptr(theta), ptr(grad), ptr(direction), ptr(t), ptr(mode), ptr(theta_t), ptr(grad_t), ptr(s_hist),
                                        ptr(y_hist), ptr(hist), ptr(tstats), n, d, m, stream_ptr()), "cx_probe_lbfgs_advance")
+
+
+def barlow_scratch(N, d):
+    """The floats of scratch barlow_fwd_bwd needs for (N, d) embeddings (cx_barlow_scratch; the layout stands in
+    include/chexpert_hip.h): the two normalised views, the d x d matrix G, the per-column vectors and the tiles' partial sums.  Sizes
+    the loss refuses are a ValueError."""
+    N, d = int(N), int(d)
+    if not (2 <= N <= BARLOW_MAX_N and 1 <= d <= BARLOW_MAX_D):
+        raise ValueError("the Barlow Twins loss takes 2 .. %d rows of 1 .. %d values (got %d x %d)" % (BARLOW_MAX_N, BARLOW_MAX_D, N, d))
+    return int(lib().cx_barlow_scratch(N, d))
+
+
+def barlow_fwd_bwd(logits, ids, lambd, loss, dlogits, stats=None, scratch=None, grad_scale=1.0):
+    """The Barlow Twins loss of the (N, d) embeddings with its exact gradient (cx_barlow_fwd_bwd, four launches, the products on the
+    fp32-input MFMA; the definition stands in include/chexpert_hip.h): rows p and p + N // 2 are the two views of pair p; ids fp32
+    (N, 1) is a mask, a pair with an id < 0 in either row is out of the batch; lambd a one-float DEVICE tensor, read by the kernels (a
+    captured step sees a changed value).  loss (1,), dlogits (N, d) and stats (4,) = [on, off, mean_k C_kk, m] are optional;
+    grad_scale multiplies dlogits alone.  scratch: fp32, at least barlow_scratch(N, d) floats (None: allocated here, which a graph
+    capture must not do -- hold one).  Returns the scratch."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    N, d = logits.shape
+    need = barlow_scratch(N, d)
+    assert ids.dtype == torch.float32 and ids.is_contiguous() and tuple(ids.shape) == (N, 1)
+    assert lambd is not None and lambd.numel() == 1
+    assert dlogits is None or tuple(dlogits.shape) == (N, d)
+    assert stats is None or tuple(stats.shape) == (4,)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=logits.device)
+    assert scratch.dim() == 1 and scratch.numel() >= need
+    assert all(t is None or t.device == logits.device for t in (ids, lambd, loss, dlogits, stats, scratch))
+    _f32(loss, lambd, n=1)
+    _f32(dlogits)
+    _f32(stats, n=4)
+    _f32(scratch, n=scratch.numel())
+    require_cuda(logits, ids, lambd, loss, dlogits, stats, scratch)
+    check(lib().cx_barlow_fwd_bwd(ptr(logits), ptr(ids), ptr(lambd), ptr(loss), ptr(dlogits), ptr(stats), grad_scale, ptr(scratch),
+                                  scratch.numel(), N, d, stream_ptr()), "cx_barlow_fwd_bwd")
+    return scratch
 
 
 def softmax_ce_fwd_bwd(logits, target, loss, loss_elem, dlogits, grad_scale=1.0):

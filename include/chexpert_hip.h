@@ -472,6 +472,37 @@ int cx_hier_collapse(const float* logits, const int* parent, float* z, float* p,
 long long cx_ntxent_scratch(int N, int d);
 int cx_ntxent_fwd_bwd(const float* e, const float* ids, const float* temperature, float* loss, float* loss_elem, float* dlogits,
                       int* top1, float grad_scale, float* scratch, long long scratch_floats, int N, int d, void* stream);
+/* Barlow Twins (Zbontar et al., "Barlow Twins: Self-Supervised Learning via Redundancy Reduction", ICML 2021) on the (N, d) embeddings e
+ * of a step, with the exact d loss / d e through the batch normalisation; four launches (barlow.hip), the three products on the
+ * fp32-input MFMA.  ids: fp32 (N, 1) ON THE DEVICE, read as a mask only; lambda: one fp32 value ON THE DEVICE, read by the kernels, so a
+ * captured step sees it rewritten in place.
+ *   h = N / 2; row p < h is view A of pair p, row p + h view B (the [x; x] layout); with an odd N the last row belongs to no pair.
+ *   V = {p < h : ids_p >= 0 and ids_{p+h} >= 0}, m = |V| counted on the device.  A row of a pair outside V, and the odd last row, get a
+ *     gradient row of exact zeros, and their embeddings reach no other output's bits, even when they hold NaN.
+ *   per view and column k, over p in V:  mu_k = sum a_pk / m;  v_k = sum (a_pk - mu_k)^2 / m (biased, two passes);
+ *     a^_pk = (a_pk - mu_k) / sqrt(v_k + CX_BARLOW_EPS), 0 for p outside V;  b^ likewise from view B
+ *   C_kl = sum_p a^_pk b^_pl / m;  on = sum_k (1 - C_kk)^2;  off = sum_{k != l} C_kl^2;  loss = on + lambda off (no further scale)
+ *   G_kk = -2 (1 - C_kk), G_kl = 2 lambda C_kl (k != l);  da^ = b^ G^T / m;  db^ = a^ G / m
+ *   da_p. = (da^_p. - mean_p da^ - a^_p. * mean_p (da^ o a^)) / sqrt(v + eps), db likewise (BatchNorm's backward).  The kernels use the
+ *     closed forms mean_p da^ = 0 and mean_p (da^ o a^)_k = sum_l G_kl C_kl / m (for view B the column sums), which hold in exact
+ *     arithmetic, so the way back through the normalisation is the epilogue of the product.
+ *   dlogits (N, d) = these rows * grad_scale;  stats (4,) = [on, off, mean_k C_kk, m]
+ *   m < 2: loss and every gradient are exactly 0, stats = [0, 0, 0, m].  A constant column gives a^ = 0 and C_kk = 0; all stays finite.
+ * fp32; every sum in a fixed order (the tiles' shares of on / off / the diagonal are added in tile order in double), no atomics:
+ * bit-reproducible, and each output alone has the bits it has beside the others.  loss, dlogits and stats may each be NULL.  scratch: the
+ * caller's, nothing is allocated here.  With r4(x) = x rounded up to a multiple of 4, d4 = r4(d), nt = ceil(d / 64) it holds, in floats:
+ *   a^ (r4(h d)) | b^ (r4(h d)) | G (r4(d d)) | 1 / sqrt(v + eps) of view A, of view B (d4 each) | sum_l G_kl C_kl (d4) |
+ *   sum_k G_kl C_kl (d4) | m (4) | the 64 x 64 tiles' [on, off, sum C_kk, -] (4 nt nt) | the tiles' row sums of G o C (nt d4) | their
+ *   column sums (nt d4);  cx_barlow_scratch(N, d) is the total.
+ * CX_EINVAL before anything is launched: NULL e / ids / lambda / scratch, N < 2, d < 1, scratch_floats below cx_barlow_scratch(N, d);
+ * CX_ESHAPE: N > CX_BARLOW_MAX_N or d > CX_BARLOW_MAX_D (the pair mask lives in LDS; 1024 is the width the head is exercised at).
+ * cx_barlow_scratch returns 0 for sizes the loss refuses.  Additive entry points of ABI 10.                                           */
+#define CX_BARLOW_MAX_N 4096
+#define CX_BARLOW_MAX_D 1024
+#define CX_BARLOW_EPS 1e-5f
+long long cx_barlow_scratch(int N, int d);
+int cx_barlow_fwd_bwd(const float* e, const float* ids, const float* lambda, float* loss, float* dlogits, float* stats, float grad_scale,
+                      float* scratch, long long scratch_floats, int N, int d, void* stream);
 /* loss = CrossEntropyLoss(logits, target) (mean over the batch of logsumexp - logit[target]);
  * dlogits = (softmax - onehot)/B * grad_scale; loss_elem (optional) = the per-sample terms
  * (models/test_model.py:118, :143, :331: the CIFAR harness criterion)                              */
